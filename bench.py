@@ -17,6 +17,8 @@ CPU restatement of the reference (oracle/, labelled "port").
 
     --config C5        BASELINE configs[4]'s per-GPU share: 12.5M rows per GPU, m=16 (the 8-GPU job)
     --collective torch the all-reduce through torch.distributed instead of below the C ABI
+    --dump-outputs DIR the codes of the last timed step (and the codebooks they were encoded with) as DIR/*.npy in
+                       float32, for output-for-output comparison of two builds (inputs are seeded: same arguments, same inputs)
 
 One JSON line on stdout (rank 0).
 """
@@ -42,6 +44,7 @@ PEAK_HBM_GBS = 8000.0
 N_PER_GPU, DIM, M, K = 1_000_000, 128, 8, 256
 DATA_SEED, TRAIN_ITERS = 66, 4
 PREWARM_STEPS = 200  # untimed encode passes in front of the warmup (GPU clocks back up after the host-side gap)
+SIDE_STEPS = 20  # passes of the side timings (cold passes, f16 output, the N > 1 blocks): --steps sets the headline's alone
 WORKLOADS = {  # BASELINE.json configs[1] and configs[4] (per-GPU share of the 100M x 128 job on 8 GPUs)
     "C2": dict(rows=1_000_000, dim=128, m=8, k=256, label="BASELINE.json configs[1]"),
     "C5": dict(rows=12_500_000, dim=128, m=16, k=256, label="BASELINE.json configs[4], one GPU's rows of 100M x 128 on 8 GPUs"),
@@ -156,6 +159,44 @@ def strided_init(n_global, m, k):
     import numpy as np
 
     return np.array([[(j * (n_global // k) + s) % n_global for j in range(k)] for s in range(m)], np.int64)
+
+
+DUMP_BUDGET_BYTES = 60 << 20  # --dump-outputs: at most this much in all (64 MB with room for the headers)
+DUMP_SAMPLE_SEED = 20240613
+
+
+def dump_codes_rows(n, m, world):
+    """rows of a rank's (n, m) code matrix that --dump-outputs writes: all of them when every rank's codes fit the budget as
+    float32, else a fixed, seeded, sorted sample (the same rows on every run with the same arguments)"""
+    import numpy as np
+
+    per_rank = (DUMP_BUDGET_BYTES - (1 << 20)) // max(1, world)  # 1 MB kept for the codebooks
+    if n * 4 * m <= per_rank:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, per_rank // (4 * m + 8), replace=False))  # + f64 index
+
+
+def dump_outputs(dirname, rank, codes, codebooks, world, row_offset=0):
+    """--dump-outputs: rank r's codes as `codes.npy` (rank 0) / `codes_rank<r>.npy`, float32 (n_or_sample, m); the sampled
+    rows' global indices as `codes_rows[_rank<r>].npy` (float64) when the codes are sampled; `codebooks.npy` (float32,
+    (m, k, sub_dim)) from rank 0.  Returns the names written."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    codes = np.asarray(codes)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    names = []
+    rows = dump_codes_rows(codes.shape[0], codes.shape[1], world)
+    if rows is not None:
+        codes = codes[rows]
+        np.save(os.path.join(dirname, f"codes_rows{suffix}.npy"), (rows + row_offset).astype(np.float64))
+        names.append(f"codes_rows{suffix}")
+    np.save(os.path.join(dirname, f"codes{suffix}.npy"), codes.astype(np.float32))
+    names.append(f"codes{suffix}")
+    if rank == 0:
+        np.save(os.path.join(dirname, "codebooks.npy"), np.asarray(codebooks, np.float32))
+        names.append("codebooks")
+    return names
 
 
 def pmc_issue_model(kernel_name):
@@ -755,7 +796,13 @@ def parse_args(argv=None):
                     help="second launcher mode: ONE process drives the --gpus devices through the library's worker threads "
                          "(vqhip_mdataset / vqhip_mkmeans / vqhip_mpq_encoder: what ProductQuantizer(..., devices=) uses)")
     ap.add_argument("--device-list", default="", help="--one-process: comma-separated device ids (default 0..gpus-1; a device may repeat)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's codes (float32; a fixed seeded row sample if they pass "
+                         "60 MB) and the codebooks as DIR/*.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main(argv=None):
@@ -829,7 +876,11 @@ def one_process(args) -> int:
     t0 = time.perf_counter()
     codes = enc.encode_dataset(mds, repeat=args.steps, want_codes=False)
     dt = time.perf_counter() - t0
-    checksum = int(enc.encode_dataset(mds, repeat=1, want_codes=True)[: mds.rows_per_device()[0]].astype(np.int64).sum())
+    last = enc.encode_dataset(mds, repeat=1, want_codes=True)  # the timed pass once more, its codes back
+    checksum = int(last[: mds.rows_per_device()[0]].astype(np.int64).sum())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, 0, last, codebooks, 1)
+    del last
     rechecked, used_engine = 0, 3
     step_ms = dt / args.steps * 1e3
     rows_rank0 = int(mds.rows_per_device()[0])
@@ -907,10 +958,12 @@ class Ranks:
             self.dist.destroy_process_group()
 
 
-def measure(args, ranks, wl_name, scaling, *, torch, _lib, engine, ncomm, collective, steps, warmup, want_f16=True, group=None):
+def measure(args, ranks, wl_name, scaling, *, torch, _lib, engine, ncomm, collective, steps, warmup, want_f16=True, group=None,
+            snapshot=False):
     """One workload on this rank's shard: codebooks from TRAIN_ITERS global Lloyd iterations, then the timed k-means
     iterations (every timed run starts from the same initial centroids, so all m subspaces execute every iteration)
-    and the timed encode passes.  Returns (dict for the line, codebooks, handles to keep)."""
+    and the timed encode passes.  Returns (dict for the line, codebooks, handles to keep); with `snapshot` the dict also
+    holds "_dump": (the last timed step's codes on the host, this shard's first global row) for --dump-outputs."""
     import numpy as np
 
     from vq_amd.sharded import HipShard, ShardedKMeans, shard_rows
@@ -1029,17 +1082,17 @@ def measure(args, ranks, wl_name, scaling, *, torch, _lib, engine, ncomm, collec
     # the host work between the k-means block and here leaves the GPU idle and its clocks down; the first ~30 passes after
     # that run up to 10 % slow (0.44, 0.44, 0.41, 0.39 ms per pass in groups of ten, 0.365 after ~300: tools/ab_screen.py).  PREWARM_STEPS
     # untimed passes bring the clocks back before the W warmup steps the contract asks for; reported in the line.
-    # first the same W + K passes with NO prewarm (`cold_ms_per_step`: what a caller sees right after host-side work)
+    # first W + SIDE_STEPS passes with NO prewarm (`cold_ms_per_step`: what a caller sees right after host-side work)
     for _ in range(warmup):
         enc.encode_device(xptr, n, codes.data_ptr(), None)
     sync()
     ranks.barrier()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(SIDE_STEPS):
         enc.encode_device(xptr, n, codes.data_ptr(), None)
     sync()
     ranks.barrier()
-    cold_ms = ranks.reduce(time.perf_counter() - t0, "max") / steps * 1e3
+    cold_ms = ranks.reduce(time.perf_counter() - t0, "max") / SIDE_STEPS * 1e3
     for _ in range(PREWARM_STEPS):
         enc.encode_device(xptr, n, codes.data_ptr(), None)
     for _ in range(warmup):
@@ -1077,6 +1130,8 @@ def measure(args, ranks, wl_name, scaling, *, torch, _lib, engine, ncomm, collec
             "algorithmic_bytes_per_launch": (4.0 * dim + m_) * n}),
         "codes_checksum_rank0": int(codes.to(torch.int64).sum().item()),
     })
+    if snapshot:  # before anything else writes `codes`
+        out["_dump"] = (codes.cpu().numpy(), offset)
     if want_f16:  # same pass with the reference-shaped f16 reconstruction written too
         f16 = torch.empty((n, dim), dtype=torch.float16, device="cuda")
         # (the host work in front of this -- checksum, k-means bookkeeping -- lets the clocks fall: two warm-up calls and five
@@ -1085,7 +1140,7 @@ def measure(args, ranks, wl_name, scaling, *, torch, _lib, engine, ncomm, collec
             enc.encode_device(xptr, n, codes.data_ptr(), f16.data_ptr())
         sync()
         t0 = time.perf_counter()
-        reps = max(10, steps)
+        reps = SIDE_STEPS
         for _ in range(reps):
             enc.encode_device(xptr, n, codes.data_ptr(), f16.data_ptr())
         sync()
@@ -1178,7 +1233,9 @@ def worker(args) -> int:
             ncomm = _lib.NativeComm(None, 1, 0)  # identity communicator
 
         main_out, codebooks, keep = measure(args, ranks, args.config, args.scaling, torch=torch, _lib=_lib, engine=engine,
-                                            ncomm=ncomm, collective=collective, steps=args.steps, warmup=args.warmup, group=group)
+                                            ncomm=ncomm, collective=collective, steps=args.steps, warmup=args.warmup, group=group,
+                                            snapshot=bool(args.dump_outputs))
+        dump = main_out.pop("_dump", None)
         ds, enc, codes = keep
         n, dim, m_, k_ = main_out["rows_this_rank"], main_out["dim"], main_out["m"], main_out["k"]
 
@@ -1292,7 +1349,7 @@ def worker(args) -> int:
             def block(name, wl_name, scaling):
                 try:
                     o, _, kp = measure(args, ranks, wl_name, scaling, torch=torch, _lib=_lib, engine=engine, ncomm=ncomm,
-                                       collective=collective, steps=max(5, args.steps // 2), warmup=2, want_f16=False, group=group)
+                                       collective=collective, steps=SIDE_STEPS // 2, warmup=2, want_f16=False, group=group)
                     kp[1].close()
                     kp[0].close()
                     del kp
@@ -1309,6 +1366,8 @@ def worker(args) -> int:
         if rank == 0 and world == 1 and not args.no_configs:
             configs = other_configs(_lib, torch, engine)
 
+    if dump is not None:
+        dump_outputs(args.dump_outputs, rank, dump[0], codebooks, world, row_offset=dump[1])
     rc = 0
     if rank == 0:
         o = main_out

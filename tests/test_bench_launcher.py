@@ -83,3 +83,44 @@ def test_main_picks_the_launcher_only_without_a_launcher_environment():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], capture_output=True, text=True,
                        timeout=300, env=e)
     assert p.returncode == 2 and "WORLD_SIZE=4" in p.stderr
+
+
+def test_dump_outputs_writes_float32_codes_and_codebooks(tmp_path):
+    """--dump-outputs' writer: every code row when they fit, float32, and the codebooks beside them"""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    codes = np.arange(1000 * 8, dtype=np.int64).reshape(1000, 8).astype(np.uint8)
+    cb = np.linspace(0, 1, 8 * 256 * 16, dtype=np.float32).reshape(8, 256, 16)
+    names = bench.dump_outputs(str(tmp_path / "out"), 0, codes, cb, 1)
+    assert sorted(names) == ["codebooks", "codes"]
+    got = np.load(tmp_path / "out" / "codes.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, codes.astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "out" / "codebooks.npy"), cb)
+    assert bench.dump_outputs(str(tmp_path / "out"), 1, codes, cb, 2) == ["codes_rank1"]  # codebooks from rank 0 only
+
+
+def test_dump_outputs_samples_large_code_matrices_within_the_budget():
+    """a shard whose float32 codes pass the budget (the C5 shard: 12.5M x 16) is written as a fixed seeded row sample"""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    assert bench.dump_codes_rows(1_000_000, 8, 1) is None  # C2's 32 MB go out whole
+    rows = bench.dump_codes_rows(12_500_000, 16, 1)
+    assert rows is not None and np.array_equal(rows, bench.dump_codes_rows(12_500_000, 16, 1))
+    assert np.all(np.diff(rows) > 0) and rows[-1] < 12_500_000
+    assert rows.size * (4 * 16 + 8) + 8 * 256 * 16 * 4 <= 64 << 20
+    for world in (2, 8):  # every rank's share together stays inside the budget
+        r = bench.dump_codes_rows(1_000_000, 8, world)
+        n = 1_000_000 if r is None else r.size
+        assert world * n * (4 * 8 + (0 if r is None else 8)) <= 63 << 20
+
+
+def test_steps_below_one_are_refused():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 2 and "--steps" in p.stderr

@@ -83,3 +83,22 @@ def test_one_process_launcher_two_slots_on_the_gpu():
     assert two["value"] > 1e7 and two["config"]["kmeans_iter_per_s"] > 0
     solo = _bench(["--gpus", "1", "--one-process", "--rows", "200001", "--scaling", "strong"] + SMALL)
     assert solo["comm_world"] == 1 and solo["codebooks_abs_sum"] == one["codebooks_abs_sum"]
+
+
+def test_dump_outputs_are_the_timed_codes(tmp_path):
+    """--dump-outputs DIR: the last timed step's codes (float32) sum to the line's checksum, the same inputs give the same
+    codes and codebooks, and --steps sets the count of timed steps"""
+    import numpy as np
+
+    a, b = tmp_path / "a", tmp_path / "b"
+    la = _bench(["--gpus", "1", "--rows", "200000", "--dump-outputs", str(a)] + SMALL)
+    lb = _bench(["--gpus", "1", "--rows", "200000", "--dump-outputs", str(b), "--steps", "3"] + SMALL[2:])
+    assert la["steps"] == 2 and lb["steps"] == 3 and la["ms_per_step"] > 0
+    ca = np.load(a / "codes.npy")
+    assert ca.dtype == np.float32 and ca.shape == (200000, 8)
+    assert int(ca.astype(np.int64).sum()) == la["codes_checksum_rank0"]
+    assert np.array_equal(ca, np.load(b / "codes.npy"))
+    cba = np.load(a / "codebooks.npy")
+    assert cba.dtype == np.float32 and cba.shape == (8, 256, 16)
+    assert np.array_equal(cba, np.load(b / "codebooks.npy"))
+    assert abs(float(np.abs(cba.astype(np.float64)).sum()) - la["codebooks_abs_sum"]) <= 1e-9 * la["codebooks_abs_sum"]
