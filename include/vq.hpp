@@ -7,6 +7,8 @@
 //   vq::VqError            src/core/error.rs:4-28   (what() == the Rust Display text)
 //   vq::ProductQuantizer   src/pq.rs:83-210         (new / getters / Quantizer::quantize / dequantize)
 //   vq::TSVQ               src/tsvq.rs:195-266
+//   vq::ScalarQuantizer    src/sq.rs                (new / getters / quantize / dequantize)
+//   vq::BinaryQuantizer    src/bq.rs
 //   vq::lbg_quantize       src/core/vector.rs:390-461
 // Validation happens before anything touches the device (same order and messages as the
 // reference); the bodies run on the MI355X.  Random draws (src/core/vector.rs:412-413, 448-452) come
@@ -566,6 +568,76 @@ class TSVQ {
     std::vector<std::int32_t> left_, right_;
     std::unique_ptr<vqhip_tsvq, detail::TsvqDel> enc_;
     std::unique_ptr<vqhip_mtsvq, detail::MTsvqDel> menc_;
+};
+
+// ----------------------------------------------------------- ScalarQuantizer / BinaryQuantizer ----
+namespace detail {
+// a *_check status -> VqError::InvalidParameter from the library's `Display` text ("Invalid parameter 'p': reason")
+inline void check_param(int status) {
+    if (status == VQHIP_OK) return;
+    const std::string msg = vqhip_last_error(), head = "Invalid parameter '";
+    const std::size_t q = msg.find("': ", head.size());
+    if (status == VQHIP_ERR_INVALID_INPUT && msg.compare(0, head.size(), head) == 0 && q != std::string::npos)
+        throw VqError::InvalidParameter(msg.substr(head.size(), q - head.size()), msg.substr(q + 3));
+    throw VqError::FfiError(msg);
+}
+}  // namespace detail
+
+// src/sq.rs: [min, max] into `levels` codes; bit-identical codes and values, on the device (vqhip_sq_*)
+class ScalarQuantizer {
+   public:
+    ScalarQuantizer(float min, float max, std::size_t levels) : min_(min), max_(max), levels_(levels) {
+        // levels beyond u32 fail the same "no more than 256" check as any value above 256
+        detail::check_param(vqhip_sq_check(min, max, levels > 0xFFFFFFFFu ? 0xFFFFFFFFu : (std::uint32_t)levels, &step_));
+    }
+    float min() const { return min_; }
+    float max() const { return max_; }
+    std::size_t levels() const { return levels_; }
+    float step() const { return step_; }
+
+    std::vector<std::uint8_t> quantize(const float *x, std::size_t count) const {
+        std::vector<std::uint8_t> out(count);
+        detail::check(vqhip_sq_encode(min_, max_, (std::uint32_t)levels_, x, count, out.data()));
+        return out;
+    }
+    std::vector<std::uint8_t> quantize(const std::vector<float> &vector) const { return quantize(vector.data(), vector.size()); }
+    std::vector<float> dequantize(const std::vector<std::uint8_t> &codes) const {
+        std::vector<float> out(codes.size());
+        detail::check(vqhip_sq_decode(min_, max_, (std::uint32_t)levels_, codes.data(), codes.size(), out.data()));
+        return out;
+    }
+
+   private:
+    float min_, max_;
+    std::size_t levels_;
+    float step_ = 0;
+};
+
+// src/bq.rs: x >= threshold -> high, else low; a code >= high decodes to high, any other to low (vqhip_bq_*)
+class BinaryQuantizer {
+   public:
+    BinaryQuantizer(float threshold, std::uint8_t low, std::uint8_t high) : threshold_(threshold), low_(low), high_(high) {
+        detail::check_param(vqhip_bq_check(threshold, low, high));
+    }
+    float threshold() const { return threshold_; }
+    std::uint8_t low() const { return low_; }
+    std::uint8_t high() const { return high_; }
+
+    std::vector<std::uint8_t> quantize(const float *x, std::size_t count) const {
+        std::vector<std::uint8_t> out(count);
+        detail::check(vqhip_bq_encode(threshold_, low_, high_, x, count, out.data()));
+        return out;
+    }
+    std::vector<std::uint8_t> quantize(const std::vector<float> &vector) const { return quantize(vector.data(), vector.size()); }
+    std::vector<float> dequantize(const std::vector<std::uint8_t> &codes) const {
+        std::vector<float> out(codes.size());
+        detail::check(vqhip_bq_decode(threshold_, low_, high_, codes.data(), codes.size(), out.data()));
+        return out;
+    }
+
+   private:
+    float threshold_;
+    std::uint8_t low_, high_;
 };
 
 // ---------------------------------------------------------------------- lbg_quantize ----

@@ -393,6 +393,32 @@ int vqhip_pq_decode(vqhip_pq_encoder *enc, const uint8_t *codes, uint64_t n, flo
 int vqhip_pq_decode_device(vqhip_pq_encoder *enc, const void *dev_codes, uint64_t n, void *dev_out);
 int vqhip_dequantize_f16_device(const void *dev_f16_in, uint64_t count, void *dev_out);
 
+/* ---- ScalarQuantizer / BinaryQuantizer (src/sq.rs, src/bq.rs) ------------------------
+ * Stateless elementwise maps, bit-identical to the reference's `quantize` / `dequantize`:
+ *   SQ encode  code = min(sat(round((clamp(x, min, max) - min) / step)), levels - 1), step = (max - min) / (levels - 1)
+ *              (f32 throughout; round half away from zero; NaN -> 0, +inf -> levels - 1)
+ *   SQ decode  min + (float)code * step for every byte (codes >= levels included; no fused multiply-add)
+ *   BQ encode  x >= threshold ? high : low (NaN -> low)
+ *   BQ decode  code >= high ? high : low
+ * Parameters are checked first, in the reference's order, before any device is touched: VQHIP_ERR_INVALID_INPUT with
+ * its `Display` text ("Invalid parameter 'max': must be greater than min") in vqhip_last_error.  count == 0 is OK.
+ * Host forms take host buffers and return when the results are there; the _device forms take device pointers of any
+ * element alignment and are asynchronous on the current stream. */
+int vqhip_sq_check(float min, float max, uint32_t levels, float *step); /* no device; step may be NULL */
+/* b[0..levels): b[0] = -inf, b[i] = the smallest f32 whose code is >= i (NaN if no input reaches i); no device */
+int vqhip_sq_thresholds(float min, float max, uint32_t levels, float *b);
+int vqhip_sq_encode(float min, float max, uint32_t levels, const float *x, uint64_t count, uint8_t *codes);
+int vqhip_sq_encode_device(float min, float max, uint32_t levels, const void *dev_x, uint64_t count, void *dev_codes);
+int vqhip_sq_decode(float min, float max, uint32_t levels, const uint8_t *codes, uint64_t count, float *out);
+int vqhip_sq_decode_device(float min, float max, uint32_t levels, const void *dev_codes, uint64_t count, void *dev_out);
+int vqhip_bq_check(float threshold, uint32_t low, uint32_t high); /* no device; low, high <= 255 */
+int vqhip_bq_encode(float threshold, uint32_t low, uint32_t high, const float *x, uint64_t count, uint8_t *codes);
+int vqhip_bq_encode_device(float threshold, uint32_t low, uint32_t high, const void *dev_x, uint64_t count,
+                           void *dev_codes);
+int vqhip_bq_decode(float threshold, uint32_t low, uint32_t high, const uint8_t *codes, uint64_t count, float *out);
+int vqhip_bq_decode_device(float threshold, uint32_t low, uint32_t high, const void *dev_codes, uint64_t count,
+                           void *dev_out);
+
 /* ---- pairwise distances --------------------------------------------------------------
  * Distance::compute (src/core/distance.rs:48-64, scalar paths 76-82, 94, 107-119) for n
  * independent pairs: out[i] = metric(a[i][0..d), b[i][0..d)).  Host buffers. */

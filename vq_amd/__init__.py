@@ -1,5 +1,6 @@
 """vq_amd -- MI355X (gfx950) back end for the k-means codebook-training and nearest-centroid
-encode path of CogitatorTech/vq, behind the reference's own Quantizer interface.
+encode path of CogitatorTech/vq, and of its elementwise scalar / binary quantizers, behind the
+reference's own Quantizer interface.
 
 The compute path is libvqhip.so (hand-written HIP for CDNA4, C ABI in include/vqhip.h).
 Importing the package does not need a GPU; using any quantizer does, and fails loudly
@@ -8,11 +9,13 @@ Importing the package does not need a GPU; using any quantizer does, and fails l
 from .distance import Distance
 from .errors import (DimensionMismatch, EmptyInput, FfiError, InvalidData, InvalidParameter,
                      VqError)
+from .bq import BinaryQuantizer
 from .pq import ProductQuantizer, fit_codebooks
+from .sq import ScalarQuantizer
 from .tsvq import TSVQ
 
 __all__ = [
-    "Distance", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
+    "Distance", "BinaryQuantizer", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
     "InvalidParameter", "InvalidData", "FfiError", "get_simd_backend",
 ]
 

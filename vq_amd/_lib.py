@@ -145,6 +145,17 @@ SIGNATURES = {
     "vqhip_mtsvq_dequantize_f16": (C.c_int, [_vp, _u16p, C.c_uint64, _f32p]),
     "vqhip_mtsvq_last_stats": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
     "vqhip_mtsvq_destroy": (C.c_int, [_vp]),
+    "vqhip_sq_check": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p]),
+    "vqhip_sq_thresholds": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p]),
+    "vqhip_sq_encode": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p, C.c_uint64, _u8p]),
+    "vqhip_sq_encode_device": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _vp, C.c_uint64, _vp]),
+    "vqhip_sq_decode": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _u8p, C.c_uint64, _f32p]),
+    "vqhip_sq_decode_device": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _vp, C.c_uint64, _vp]),
+    "vqhip_bq_check": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32]),
+    "vqhip_bq_encode": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _u8p]),
+    "vqhip_bq_encode_device": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp]),
+    "vqhip_bq_decode": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, _u8p, C.c_uint64, _f32p]),
+    "vqhip_bq_decode_device": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp]),
 }
 
 _lib = None
@@ -821,3 +832,35 @@ def last_assign_stats():
     r, e = C.c_uint64(), C.c_int()
     check(load().vqhip_last_assign_stats(C.byref(r), C.byref(e)))
     return int(r.value), int(e.value)
+
+
+# ---- ScalarQuantizer / BinaryQuantizer (stateless elementwise maps; include/vqhip.h) ----
+def param_check(rc: int) -> None:
+    """a *_check status -> InvalidParameter(parameter, reason) from the library's `Display` text, else FfiError"""
+    if rc == OK:
+        return
+    import re
+
+    from .errors import InvalidParameter
+
+    msg = last_error()
+    m = re.fullmatch(r"Invalid parameter '([^']*)': (.*)", msg, flags=re.S)
+    if rc == ERR_INVALID_INPUT and m:
+        raise InvalidParameter(m.group(1), m.group(2))
+    raise FfiError(msg or f"libvqhip status {rc}", rc)
+
+
+def elementwise(fn: str, params, a, in_dtype, out_dtype, out=None) -> np.ndarray:
+    """host form `fn(*params, in, count, out)` over an array of any shape; out: an array of the same shape and
+    out_dtype to fill (numpy's `out=`)"""
+    x = np.ascontiguousarray(a, dtype=in_dtype)
+    if out is None:
+        out = np.empty(x.shape, out_dtype)
+    elif (not isinstance(out, np.ndarray) or out.shape != x.shape or out.dtype != np.dtype(out_dtype)
+          or not out.flags.c_contiguous or not out.flags.writeable):
+        raise FfiError(f"out must be a writable C-contiguous {np.dtype(out_dtype).name} array of shape {x.shape}",
+                       ERR_INVALID_INPUT)
+    in_ty = _f32p if np.dtype(in_dtype) == np.float32 else _u8p
+    out_ty = _f32p if np.dtype(out_dtype) == np.float32 else _u8p
+    check(getattr(load(), fn)(*params, ptr(x, in_ty), x.size, ptr(out, out_ty)))
+    return out

@@ -768,6 +768,62 @@ static int spin_wait(hipStream_t s) {
     return VQHIP_OK;
 }
 
+// Host form of a stateless elementwise map (SQ / BQ): count elements of in_sz bytes in -> count of out_sz bytes out,
+// `launch(dev_in, dev_out, count, stream)` enqueueing the kernel.  A per-vector call (both sides <= 64 KB) stages
+// through a call-owned pinned, device-mapped buffer and one launch (the kernel reads and writes host memory); a batch
+// large enough for the transfer lanes goes through them in chunks; anything between copies in, launches, copies out.
+constexpr size_t kElementwiseSmallBytes = 65536;
+template <class Launch>
+static int host_elementwise(const void *in, size_t in_sz, void *out, size_t out_sz, uint64_t count, Launch launch) {
+    const size_t in_b = (size_t)count * in_sz, out_b = (size_t)count * out_sz;
+    const size_t out_off = (in_b + 15) & ~(size_t)15;
+    static const char *no_small = getenv("VQHIP_NO_SMALL_PATH");
+    if (out_off + out_b <= kElementwiseSmallBytes && !(no_small && no_small[0] == '1')) {
+        hipStream_t s;
+        VQ_TRY(current_stream(&s));
+        StageLease stage;
+        VQ_TRY(stage.acquire(out_off + out_b));
+        memcpy(stage.host(), in, in_b);
+        VQ_TRY(launch(stage.dev(), stage.dev() + out_off, count, s));
+        VQ_TRY(spin_wait(s));
+        memcpy(out, stage.host() + out_off, out_b);
+        return VQHIP_OK;
+    }
+    if (xfer_lanes_pay(in_b, out_b)) {
+        const uint64_t per = std::max<uint64_t>(16, (xfer_chunk_bytes() / in_sz) & ~(uint64_t)15);
+        const uint64_t chunks = (count + per - 1) / per;
+        std::mutex h2d_turn;
+        return run_lanes([&](int tl, XferLane &ln, int n_lanes) -> int {
+            VQ_TRY(ln.dev_in.ensure((size_t)per * in_sz));
+            VQ_TRY(ln.dev_out.ensure((size_t)per * out_sz));
+            for (uint64_t c = (uint64_t)tl; c < chunks; c += (uint64_t)n_lanes) {
+                const uint64_t e0 = c * per, ne = std::min(per, count - e0);
+                {
+                    std::lock_guard<std::mutex> turn(h2d_turn);
+                    VQ_HIP(hipMemcpyAsync(ln.dev_in.p, static_cast<const char *>(in) + e0 * in_sz, (size_t)ne * in_sz,
+                                          hipMemcpyHostToDevice, ln.stream));
+                    VQ_HIP(hipStreamSynchronize(ln.stream));
+                }
+                VQ_TRY(launch(ln.dev_in.as<char>(), ln.dev_out.as<char>(), ne, ln.stream));
+                VQ_HIP(hipMemcpyAsync(static_cast<char *>(out) + e0 * out_sz, ln.dev_out.p, (size_t)ne * out_sz,
+                                      hipMemcpyDeviceToHost, ln.stream));
+                VQ_HIP(hipStreamSynchronize(ln.stream));
+            }
+            return VQHIP_OK;
+        });
+    }
+    hipStream_t s;
+    VQ_TRY(current_stream(&s));
+    DevBuf din, dout;
+    VQ_TRY(din.alloc(in_b));
+    VQ_TRY(dout.alloc(out_b));
+    VQ_HIP(hipMemcpyAsync(din.p, in, in_b, hipMemcpyHostToDevice, s));
+    VQ_TRY(launch(din.as<char>(), dout.as<char>(), count, s));
+    VQ_HIP(hipMemcpyAsync(out, dout.p, out_b, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipStreamSynchronize(s));
+    return VQHIP_OK;
+}
+
 struct vqhip_pq_encoder {
     HandleSync sync;
     uint64_t ws_id = 0;
@@ -2507,6 +2563,131 @@ int vqhip_dequantize_f16_device(const void *dev_f16_in, uint64_t count, void *de
     hipStream_t s;
     VQ_TRY(current_stream(&s));
     return launch_dequant_f16(static_cast<const uint16_t *>(dev_f16_in), count, static_cast<float *>(dev_out), s);
+    VQ_API_END
+}
+
+// ---------------------------------------------------------------- ScalarQuantizer / BinaryQuantizer ----
+// Parameters are checked (and the tables built) before anything touches a device; see k_sqbq.hip for the arithmetic.
+int vqhip_sq_check(float min, float max, uint32_t levels, float *step) {
+    VQ_API_BEGIN
+    return sq_check(min, max, levels, step);
+    VQ_API_END
+}
+
+int vqhip_sq_thresholds(float min, float max, uint32_t levels, float *b) {
+    VQ_API_BEGIN
+    float step = 0;
+    VQ_TRY(sq_check(min, max, levels, &step));
+    if (!b) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    sq_thresholds(min, max, levels, step, b);
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+static int sqbq_encode_host(const SqbqEncodeOp &op, const float *x, uint64_t count, uint8_t *codes) {
+    if (count == 0) return VQHIP_OK;
+    if (!x || !codes) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    VQ_TRY(require_gfx950());
+    return host_elementwise(x, 4, codes, 1, count, [&](const char *di, char *dout, uint64_t n, hipStream_t s) {
+        return launch_sqbq_encode(op, reinterpret_cast<const float *>(di), n, reinterpret_cast<uint8_t *>(dout), s);
+    });
+}
+static int sqbq_decode_host(const SqbqDecodeLut &lut, const uint8_t *codes, uint64_t count, float *out) {
+    if (count == 0) return VQHIP_OK;
+    if (!codes || !out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    VQ_TRY(require_gfx950());
+    return host_elementwise(codes, 1, out, 4, count, [&](const char *di, char *dout, uint64_t n, hipStream_t s) {
+        return launch_sqbq_decode(lut, reinterpret_cast<const uint8_t *>(di), n, reinterpret_cast<float *>(dout), s);
+    });
+}
+static int sqbq_encode_dev(const SqbqEncodeOp &op, const void *dev_x, uint64_t count, void *dev_codes) {
+    if (count == 0) return VQHIP_OK;
+    if (!dev_x || !dev_codes) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (reinterpret_cast<uintptr_t>(dev_x) & 3) return fail(VQHIP_ERR_INVALID_INPUT, "x is not 4-byte aligned");
+    VQ_TRY(require_gfx950());
+    hipStream_t s;
+    VQ_TRY(current_stream(&s));
+    return launch_sqbq_encode(op, static_cast<const float *>(dev_x), count, static_cast<uint8_t *>(dev_codes), s);
+}
+static int sqbq_decode_dev(const SqbqDecodeLut &lut, const void *dev_codes, uint64_t count, void *dev_out) {
+    if (count == 0) return VQHIP_OK;
+    if (!dev_codes || !dev_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (reinterpret_cast<uintptr_t>(dev_out) & 3) return fail(VQHIP_ERR_INVALID_INPUT, "out is not 4-byte aligned");
+    VQ_TRY(require_gfx950());
+    hipStream_t s;
+    VQ_TRY(current_stream(&s));
+    return launch_sqbq_decode(lut, static_cast<const uint8_t *>(dev_codes), count, static_cast<float *>(dev_out), s);
+}
+
+int vqhip_sq_encode(float min, float max, uint32_t levels, const float *x, uint64_t count, uint8_t *codes) {
+    VQ_API_BEGIN
+    SqbqEncodeOp op;
+    VQ_TRY(sq_encode_op(min, max, levels, &op));
+    return sqbq_encode_host(op, x, count, codes);
+    VQ_API_END
+}
+
+int vqhip_sq_encode_device(float min, float max, uint32_t levels, const void *dev_x, uint64_t count, void *dev_codes) {
+    VQ_API_BEGIN
+    SqbqEncodeOp op;
+    VQ_TRY(sq_encode_op(min, max, levels, &op));
+    return sqbq_encode_dev(op, dev_x, count, dev_codes);
+    VQ_API_END
+}
+
+int vqhip_sq_decode(float min, float max, uint32_t levels, const uint8_t *codes, uint64_t count, float *out) {
+    VQ_API_BEGIN
+    SqbqDecodeLut lut;
+    VQ_TRY(sq_decode_lut(min, max, levels, &lut));
+    return sqbq_decode_host(lut, codes, count, out);
+    VQ_API_END
+}
+
+int vqhip_sq_decode_device(float min, float max, uint32_t levels, const void *dev_codes, uint64_t count, void *dev_out) {
+    VQ_API_BEGIN
+    SqbqDecodeLut lut;
+    VQ_TRY(sq_decode_lut(min, max, levels, &lut));
+    return sqbq_decode_dev(lut, dev_codes, count, dev_out);
+    VQ_API_END
+}
+
+int vqhip_bq_check(float threshold, uint32_t low, uint32_t high) {
+    VQ_API_BEGIN
+    return bq_check(threshold, low, high);
+    VQ_API_END
+}
+
+int vqhip_bq_encode(float threshold, uint32_t low, uint32_t high, const float *x, uint64_t count, uint8_t *codes) {
+    VQ_API_BEGIN
+    SqbqEncodeOp op;
+    VQ_TRY(bq_encode_op(threshold, low, high, &op));
+    return sqbq_encode_host(op, x, count, codes);
+    VQ_API_END
+}
+
+int vqhip_bq_encode_device(float threshold, uint32_t low, uint32_t high, const void *dev_x, uint64_t count,
+                           void *dev_codes) {
+    VQ_API_BEGIN
+    SqbqEncodeOp op;
+    VQ_TRY(bq_encode_op(threshold, low, high, &op));
+    return sqbq_encode_dev(op, dev_x, count, dev_codes);
+    VQ_API_END
+}
+
+int vqhip_bq_decode(float threshold, uint32_t low, uint32_t high, const uint8_t *codes, uint64_t count, float *out) {
+    VQ_API_BEGIN
+    SqbqDecodeLut lut;
+    VQ_TRY(bq_decode_lut(threshold, low, high, &lut));
+    return sqbq_decode_host(lut, codes, count, out);
+    VQ_API_END
+}
+
+int vqhip_bq_decode_device(float threshold, uint32_t low, uint32_t high, const void *dev_codes, uint64_t count,
+                           void *dev_out) {
+    VQ_API_BEGIN
+    SqbqDecodeLut lut;
+    VQ_TRY(bq_decode_lut(threshold, low, high, &lut));
+    return sqbq_decode_dev(lut, dev_codes, count, dev_out);
     VQ_API_END
 }
 

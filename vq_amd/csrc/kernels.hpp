@@ -300,4 +300,32 @@ int launch_synth_uniform(float *X, uint64_t n, uint32_t d, uint64_t seed, uint64
                          hipStream_t stream);
 void synth_uniform_host(float *out, uint64_t n, uint32_t d, uint64_t seed, uint64_t row_offset);
 
+// ---- ScalarQuantizer / BinaryQuantizer (k_sqbq.hip) --------------------------------
+// Parameters travel by value as kernel arguments; the tables are built on the host with the reference's arithmetic.
+enum { SQBQ_TABLE = 0, SQBQ_DIRECT = 1, SQBQ_BINARY = 2 };
+constexpr uint32_t kSqTable = 257;  // b[0] = -inf, b[1..levels-1] thresholds, b[levels] = NaN
+struct SqbqEncodeOp {
+    int mode = SQBQ_DIRECT;
+    float mn = 0, mx = 0, step = 0, inv = 0;  // SQ
+    uint32_t top = 0;                         // SQ: levels - 1
+    float thr = 0;                            // BQ
+    uint32_t low = 0, high = 0;               // BQ
+    float b[kSqTable] = {};                   // SQ, SQBQ_TABLE: b[i] = smallest f32 whose code is >= i
+};
+struct SqbqDecodeLut {
+    float lut[256];  // the reference's dequantize of each code byte
+};
+// validation in the reference's order; the texts are its `Display` ("Invalid parameter '<p>': <reason>")
+int sq_check(float mn, float mx, uint32_t levels, float *step);
+int bq_check(float threshold, uint32_t low, uint32_t high);
+// b[0..levels): b[0] = -inf, b[i] = the smallest f32 whose code is >= i (NaN if none); parameters already checked
+void sq_thresholds(float mn, float mx, uint32_t levels, float step, float *b);
+int sq_encode_op(float mn, float mx, uint32_t levels, SqbqEncodeOp *p);
+int bq_encode_op(float threshold, uint32_t low, uint32_t high, SqbqEncodeOp *p);
+int sq_decode_lut(float mn, float mx, uint32_t levels, SqbqDecodeLut *p);
+int bq_decode_lut(float threshold, uint32_t low, uint32_t high, SqbqDecodeLut *p);
+// any alignment of x (4 bytes) / codes (1 byte), any count
+int launch_sqbq_encode(const SqbqEncodeOp &p, const float *x, uint64_t count, uint8_t *codes, hipStream_t stream);
+int launch_sqbq_decode(const SqbqDecodeLut &p, const uint8_t *codes, uint64_t count, float *out, hipStream_t stream);
+
 }  // namespace vqhip

@@ -3,12 +3,18 @@
 
     python -m vq_amd.evalcli pq   [--seed 66 --dim 384 --m 16 --k 256 --max-iters 10]
     python -m vq_amd.evalcli tsvq [--seed 66 --dim 384 --max-depth 5]
+    python -m vq_amd.evalcli sq   [--seed 66 --dim 384 --levels 256]
+    python -m vq_amd.evalcli bq   [--seed 66 --dim 384]
 
 For every sample count of `NUM_SAMPLES` it prints the reference's three lines -- training time,
 quantization time (host matrix in, f16 matrix out: what `quantize` per vector produces there)
 and the mean squared reconstruction error -- and the two `BenchmarkResult` fields the binaries
 compute nowhere: recall@k with `calculate_recall`'s windowed protocol (common.rs:91-130) and
 the memory reduction ratio.  `--json` emits one `BenchmarkResult`-shaped object per line.
+
+`sq` / `bq` follow src/bin/eval_sq.rs / eval_bq.rs: ScalarQuantizer(0, 1, levels) and
+BinaryQuantizer(0.5, 0, 1), "training" being the constructor; the reference's two lines plus the
+mean squared error of dequantize(quantize(x)).
 
 Data: i.i.d. Uniform[0,1) like common.rs:43-53, from the library's counter-based generator
 (the reference's StdRng stream is not reproducible outside Rust).
@@ -89,9 +95,44 @@ def _report(title, make_quantizer, args, code_bytes_per_vector):
               f"{res['memory_reduction_ratio_codes']:.1f}x as codes")
 
 
+def _report_elementwise(title, make_quantizer, args):
+    """eval_sq.rs / eval_bq.rs: the constructor timed as training, one batch quantize of the whole matrix (what
+    quantize per vector gives), then the reconstruction error of dequantize"""
+    from . import _lib
+
+    print(title)
+    print("=" * len(title))
+    for n in args.samples:
+        X = _lib.synth_uniform_host(n, args.dim, args.seed, 0)
+        t0 = time.perf_counter()
+        q = make_quantizer()
+        train_ms = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        codes = q.quantize_batch(X)
+        quant_ms = (time.perf_counter() - t0) * 1e3
+        err = reconstruction_error(X, q.dequantize_batch(codes))
+        if args.json:
+            print(json.dumps({"n_samples": n, "n_dims": args.dim, "training_time_ms": train_ms,
+                              "quantization_time_ms": quant_ms, "reconstruction_error": err,
+                              "memory_reduction_ratio": 4.0}))
+            continue
+        print(f"\nSamples: {n}")
+        print(f"  Training time: {train_ms:.0f} ms")
+        print(f"  Quantization time: {quant_ms:.0f} ms")
+        print(f"  Reconstruction error: {err:.6f}")
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="vq_amd.evalcli")
     sub = ap.add_subparsers(dest="alg", required=True)
+    for name in ("sq", "bq"):
+        p = sub.add_parser(name)
+        p.add_argument("--seed", type=int, default=SEED)
+        p.add_argument("--dim", type=int, default=DIM)
+        p.add_argument("--samples", type=int, nargs="+", default=NUM_SAMPLES)
+        p.add_argument("--json", action="store_true")
+        if name == "sq":
+            p.add_argument("--levels", type=int, default=256)
     for name in ("pq", "tsvq"):
         p = sub.add_parser(name)
         p.add_argument("--seed", type=int, default=SEED)
@@ -106,9 +147,13 @@ def main(argv=None) -> int:
         else:
             p.add_argument("--max-depth", type=int, default=5)
     args = ap.parse_args(argv)
-    from . import TSVQ, Distance, ProductQuantizer
+    from . import TSVQ, BinaryQuantizer, Distance, ProductQuantizer, ScalarQuantizer
 
-    if args.alg == "pq":
+    if args.alg == "sq":
+        _report_elementwise("Scalar Quantizer Evaluation", lambda: ScalarQuantizer(0.0, 1.0, args.levels), args)
+    elif args.alg == "bq":
+        _report_elementwise("Binary Quantizer Evaluation", lambda: BinaryQuantizer(0.5, 0, 1), args)
+    elif args.alg == "pq":
         _report("Product Quantizer Evaluation",
                 lambda X: ProductQuantizer(X, args.m, args.k, args.max_iters, Distance.euclidean(), args.seed),
                 args, lambda q: q.num_subspaces)
