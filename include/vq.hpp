@@ -662,6 +662,72 @@ inline std::vector<std::vector<float>> lbg_quantize(const std::vector<std::vecto
     return out;
 }
 
+// Exact k-NN search over rows kept on the device (include/vqhip.h, vqhip_flat_*): rows [n][dim] f32 or f16, uploaded once
+// by the constructor; search / rerank give (row index, distance) pairs [nq][topk], nearest first, NaN last, ties to the
+// lower row.  The arguments are checked before the device is touched.
+class FlatIndex {
+   public:
+    FlatIndex(const float *rows, std::size_t n, std::size_t dim, Distance distance = Distance()) {
+        init(rows, 0, n, dim, distance);
+    }
+    FlatIndex(const f16 *rows, std::size_t n, std::size_t dim, Distance distance = Distance()) {
+        init(rows, 1, n, dim, distance);
+    }
+    std::size_t size() const { return n_; }
+    std::size_t dim() const { return dim_; }
+    const char *distance_metric() const { return distance_.name(); }
+
+    struct Result {
+        std::vector<std::uint32_t> idx;  // [nq][topk]
+        std::vector<float> dist;         // [nq][topk]
+    };
+    // queries [nq][dim]
+    Result search(const float *queries, std::size_t nq, std::size_t topk) const {
+        if (topk == 0 || topk > 1024 || topk > n_)
+            throw VqError::InvalidParameter("topk", "must be between 1 and min(n, 1024)");
+        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
+        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
+        if (nq) detail::check(vqhip_flat_search(flat_.get(), queries, (std::uint32_t)nq, (std::uint32_t)topk, r.idx.data(), r.dist.data()));
+        return r;
+    }
+    Result search(const std::vector<float> &queries, std::size_t topk) const {
+        if (queries.size() % dim_) throw VqError::DimensionMismatch(dim_, queries.size() % dim_);
+        return search(queries.data(), queries.size() / dim_, topk);
+    }
+    // per query the topk nearest of its c candidate row ids cand [nq][c] (distinct within a query, each < n)
+    Result rerank(const float *queries, std::size_t nq, const std::uint32_t *cand, std::size_t c, std::size_t topk) const {
+        if (c == 0 || c > 4096) throw VqError::InvalidParameter("candidates", "between 1 and 4096 per query");
+        if (topk == 0 || topk > c) throw VqError::InvalidParameter("topk", "must be between 1 and the number of candidates");
+        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
+        for (std::size_t e = 0; e < nq * c; ++e)
+            if (cand[e] >= n_) throw VqError::InvalidParameter("candidates", "a row id is outside [0, n)");
+        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
+        if (nq)
+            detail::check(vqhip_flat_rerank(flat_.get(), queries, (std::uint32_t)nq, cand, (std::uint32_t)c, (std::uint32_t)topk,
+                                            r.idx.data(), r.dist.data()));
+        return r;
+    }
+
+   private:
+    struct Del {
+        void operator()(vqhip_flat *p) const { (void)vqhip_flat_destroy(p); }
+    };
+    void init(const void *rows, int dtype, std::size_t n, std::size_t dim, Distance distance) {
+        if (n == 0) throw VqError::EmptyInput();
+        if (dim == 0) throw VqError::InvalidParameter("dim", "must be at least 1");
+        if (n >= (std::size_t(1) << 32) || dim > 0xFFFFFFFFu) throw VqError::InvalidParameter("rows", "at most 2^32 - 1 rows of 2^32 - 1 dimensions");
+        vqhip_flat *f = nullptr;
+        detail::check(vqhip_flat_create(rows, n, (std::uint32_t)dim, dtype, (int)distance.kind(), &f));
+        flat_.reset(f);
+        n_ = n;
+        dim_ = dim;
+        distance_ = distance;
+    }
+    std::unique_ptr<vqhip_flat, Del> flat_;
+    std::size_t n_ = 0, dim_ = 0;
+    Distance distance_;
+};
+
 // analogue of vq::get_simd_backend (src/lib.rs): names the device backend
 inline std::string get_simd_backend() { return vqhip_backend(); }
 

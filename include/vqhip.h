@@ -449,6 +449,35 @@ int vqhip_pq_adc_search_resident(vqhip_pq_encoder *enc, const float *queries, ui
                                  uint32_t topk, uint32_t *idx_out, float *dist_out);
 int vqhip_pq_adc_last_redone(vqhip_pq_encoder *enc, uint32_t *queries_out);
 
+/* ---- exact k-NN search over resident rows, exact rerank (k_knn.hip) ------------------------
+ * No reference counterpart (the crate has no search function).  An index holds n rows of d floats, given as f32
+ * (dtype 0) or as f16 bits (dtype 1: the output of quantize / vqhip_pq_encode's f16_out, widened exactly to f32 before
+ * any arithmetic), uploaded once (create_device copies).  Limits: 1 <= d, 1 <= n < 2^32, any of the five metrics.
+ *   D(q, i) = vqhip_distance_batch(metric, q, row_i) bit for bit: each pair summed sequentially over t = 0..d-1 from
+ *             -0.0f, no fused multiply-add; Euclidean = sqrtf of the squared sum; cosine through the EPSILON rule and
+ *             the clamp (neither for VQHIP_COSINE_UNCLAMPED), the norms sqrtf(sum x_t^2) computed once per row (at
+ *             create) and once per query (per call) -- a norm depends on its own vector only, no bit changes.
+ *   search  = per query the topk rows by (D, row index) ascending, 1 <= topk <= min(n, 1024), in the order of the
+ *             order-preserving key of the ADC search: NaN sorts last and is reported as 0x7FC00000, ties go to the
+ *             lower row.  Unlike ADC, Euclidean orders by the REPORTED sqrtf value: two rows whose squared sums differ
+ *             but round to the same root tie, and the lower row wins.
+ *   rerank  = per query the topk (<= c) of its c candidate ids (1 <= c <= 4096, distinct within the query) under the
+ *             same order.  An id >= n reads nothing; the device flags it and the call returns VQHIP_ERR_INVALID_INPUT.
+ * queries [nq][d] f32, idx / dist [nq][topk].  Parameters are checked before any device work.  Host forms return
+ * when the results are there; search_device is asynchronous on the current stream.  The handle has a lock like the
+ * encoders' (one call at a time runs on it).  info: any output pointer may be NULL. */
+typedef struct vqhip_flat vqhip_flat;
+int vqhip_flat_create(const void *rows, uint64_t n, uint32_t d, int dtype, int metric, vqhip_flat **out);
+int vqhip_flat_create_device(const void *dev_rows, uint64_t n, uint32_t d, int dtype, int metric, vqhip_flat **out);
+int vqhip_flat_destroy(vqhip_flat *f);
+int vqhip_flat_info(const vqhip_flat *f, uint64_t *n, uint32_t *d, int *dtype, int *metric);
+int vqhip_flat_search(vqhip_flat *f, const float *queries, uint32_t nq, uint32_t topk, uint32_t *idx_out,
+                      float *dist_out);
+int vqhip_flat_search_device(vqhip_flat *f, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx,
+                             void *dev_dist);
+int vqhip_flat_rerank(vqhip_flat *f, const float *queries, uint32_t nq, const uint32_t *cand, uint32_t c,
+                      uint32_t topk, uint32_t *idx_out, float *dist_out);
+
 /* ---- TSVQ ----------------------------------------------------------------------------
  * build replaces TSVQNode::build (src/tsvq.rs:31-115); the tree comes back flattened in
  * pre-order (node 0 = root, left subtree, right subtree): centroids [cap][d], left/right

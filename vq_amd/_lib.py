@@ -145,6 +145,13 @@ SIGNATURES = {
     "vqhip_mtsvq_dequantize_f16": (C.c_int, [_vp, _u16p, C.c_uint64, _f32p]),
     "vqhip_mtsvq_last_stats": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
     "vqhip_mtsvq_destroy": (C.c_int, [_vp]),
+    "vqhip_flat_create": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_int, C.c_int, _vpp]),
+    "vqhip_flat_create_device": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_int, C.c_int, _vpp]),
+    "vqhip_flat_destroy": (C.c_int, [_vp]),
+    "vqhip_flat_info": (C.c_int, [_vp, _u64p, _u32p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vqhip_flat_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "vqhip_flat_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "vqhip_flat_rerank": (C.c_int, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
     "vqhip_sq_check": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p]),
     "vqhip_sq_thresholds": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p]),
     "vqhip_sq_encode": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p, C.c_uint64, _u8p]),
@@ -717,6 +724,46 @@ class PQEncoder(Handle):
     def decode_device(self, dev_codes: int, n: int, dev_out: int):
         """device pointers, asynchronous on the current stream; codes in [0, k) are the caller's responsibility"""
         check(load().vqhip_pq_decode_device(self.raw, C.c_void_p(dev_codes), int(n), C.c_void_p(dev_out)))
+
+
+class Flat(Handle):
+    """vqhip_flat: rows resident on the device, exact k-NN search and exact rerank (k_knn.hip)"""
+
+    _destroy = "vqhip_flat_destroy"
+
+    def __init__(self, rows: np.ndarray, metric: int, dev_rows: int | None = None, shape=None):
+        """rows: a C-contiguous (n, d) float32 or float16 array, or dev_rows (a device pointer) with shape (n, d) and
+        rows giving the dtype"""
+        dtype = 1 if np.dtype(rows.dtype) == np.float16 else 0
+        n, d = shape if dev_rows is not None else rows.shape
+        h = C.c_void_p()
+        if dev_rows is not None:
+            check(load().vqhip_flat_create_device(C.c_void_p(dev_rows), int(n), int(d), dtype, int(metric), C.byref(h)))
+        else:
+            check(load().vqhip_flat_create(rows.ctypes.data_as(_vp), int(n), int(d), dtype, int(metric), C.byref(h)))
+        super().__init__(h)
+        self.n, self.d, self.dtype, self.metric = int(n), int(d), dtype, int(metric)
+
+    def search(self, q: np.ndarray, topk: int):
+        nq = q.shape[0]
+        idx = np.empty((nq, topk), np.uint32)
+        dist = np.empty((nq, topk), np.float32)
+        if nq:
+            check(load().vqhip_flat_search(self.raw, ptr(q, _f32p), nq, int(topk), ptr(idx, _u32p), ptr(dist, _f32p)))
+        return idx, dist
+
+    def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int):
+        check(load().vqhip_flat_search_device(self.raw, C.c_void_p(dev_queries), int(nq), int(topk), C.c_void_p(dev_idx),
+                                              C.c_void_p(dev_dist)))
+
+    def rerank(self, q: np.ndarray, cand: np.ndarray, topk: int):
+        nq, c = cand.shape
+        idx = np.empty((nq, topk), np.uint32)
+        dist = np.empty((nq, topk), np.float32)
+        if nq:
+            check(load().vqhip_flat_rerank(self.raw, ptr(q, _f32p), nq, ptr(cand, _u32p), int(c), int(topk), ptr(idx, _u32p),
+                                           ptr(dist, _f32p)))
+        return idx, dist
 
 
 def dequantize_f16(f16) -> np.ndarray:

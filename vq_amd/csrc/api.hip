@@ -2712,6 +2712,178 @@ int vqhip_distance_batch(int metric, const float *a, const float *b, uint64_t n,
     VQ_API_END
 }
 
+// ------------------------------------------------------------------ exact k-NN (k_knn.hip) ----
+}  // extern "C"
+
+struct vqhip_flat {
+    HandleSync sync;
+    uint64_t n = 0;
+    uint32_t d = 0;
+    int dtype = 0, metric = VQHIP_EUCLIDEAN;
+    DevBuf rows, rnorm;                            // the index: [n][d] f32 or f16 bits, |row| for cosine
+    DevBuf q, qnorm, dist, state, cand, idx, out;  // per-call workspaces
+    DevBuf rr_cand, rr_err;                        // rerank: candidate ids, the out-of-range flag
+};
+
+static int flat_check(uint64_t n, uint32_t d, int dtype, int metric) {
+    if (d == 0) return fail(VQHIP_ERR_INVALID_INPUT, "d must be at least 1");
+    if (n == 0 || n >= (1ull << 32)) return fail(VQHIP_ERR_INVALID_INPUT, "n must be in [1, 2^32)");
+    if (dtype != 0 && dtype != 1) return fail(VQHIP_ERR_INVALID_INPUT, "dtype must be 0 (f32) or 1 (f16), not %d", dtype);
+    if (metric < VQHIP_SQUARED_EUCLIDEAN || metric > VQHIP_COSINE_UNCLAMPED) return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
+    return VQHIP_OK;
+}
+
+// rows from host (kind = H2D) or device (D2D) memory into a new index
+static int flat_create(const void *src, hipMemcpyKind kind, uint64_t n, uint32_t d, int dtype, int metric, vqhip_flat **out) {
+    if (!out) return fail(VQHIP_ERR_NULL_PTR, "out is NULL");
+    *out = nullptr;
+    if (!src) return fail(VQHIP_ERR_NULL_PTR, "rows is NULL");
+    VQ_TRY(flat_check(n, d, dtype, metric));
+    VQ_TRY(require_gfx950());
+    hipStream_t s;
+    VQ_TRY(current_stream(&s));
+    std::unique_ptr<vqhip_flat> f(new vqhip_flat());
+    f->n = n;
+    f->d = d;
+    f->dtype = dtype;
+    f->metric = metric;
+    const size_t bytes = (size_t)n * d * (dtype == 1 ? 2 : 4);
+    VQ_TRY(f->rows.alloc(bytes));
+    VQ_HIP(hipMemcpyAsync(f->rows.p, src, bytes, kind, s));
+    if (vq_is_cos(metric)) {
+        VQ_TRY(f->rnorm.alloc((size_t)n * 4));
+        VQ_TRY(launch_knn_norms(f->rows.p, dtype, n, d, f->rnorm.as<float>(), s));
+    }
+    VQ_HIP(hipStreamSynchronize(s));  // the caller may free or change its rows once this returns
+    *out = f.release();
+    return VQHIP_OK;
+}
+
+static int flat_check_topk(const vqhip_flat *f, uint32_t topk) {
+    if (topk == 0 || topk > 1024 || topk > f->n)
+        return fail(VQHIP_ERR_INVALID_INPUT, "topk %u must be in [1, min(n, 1024)] (n = %llu)", topk, (unsigned long long)f->n);
+    return VQHIP_OK;
+}
+
+// queries_dev [nq][d] f32 on the device -> [nq][topk] results on the device, enqueued on s
+static int flat_search_enqueue(vqhip_flat *f, const float *queries_dev, uint32_t nq, uint32_t topk, uint32_t *idx_dev,
+                               float *dist_dev, hipStream_t s) {
+    const uint32_t qb = knn_query_batch(f->n, nq);
+    VQ_TRY(f->dist.ensure((size_t)qb * f->n * 4));
+    VQ_TRY(f->state.ensure(knn_state_bytes(qb)));
+    VQ_TRY(f->cand.ensure(knn_cand_bytes(qb)));
+    const float *qn = nullptr;
+    if (vq_is_cos(f->metric)) {
+        VQ_TRY(f->qnorm.ensure((size_t)nq * 4));
+        VQ_TRY(launch_knn_norms(queries_dev, 0, nq, f->d, f->qnorm.as<float>(), s));
+        qn = f->qnorm.as<float>();
+    }
+    return launch_knn_search(f->metric, f->rows.p, f->dtype, f->n, f->d, f->rnorm.as<float>(), queries_dev, qn, nq, topk,
+                             f->dist.as<float>(), f->state.p, f->cand.as<unsigned long long>(), idx_dev, dist_dev, s);
+}
+
+extern "C" {
+
+int vqhip_flat_create(const void *rows, uint64_t n, uint32_t d, int dtype, int metric, vqhip_flat **out) {
+    VQ_API_BEGIN
+    return flat_create(rows, hipMemcpyHostToDevice, n, d, dtype, metric, out);
+    VQ_API_END
+}
+
+int vqhip_flat_create_device(const void *dev_rows, uint64_t n, uint32_t d, int dtype, int metric, vqhip_flat **out) {
+    VQ_API_BEGIN
+    return flat_create(dev_rows, hipMemcpyDeviceToDevice, n, d, dtype, metric, out);
+    VQ_API_END
+}
+
+int vqhip_flat_destroy(vqhip_flat *f) {
+    delete f;
+    return VQHIP_OK;
+}
+
+int vqhip_flat_info(const vqhip_flat *f, uint64_t *n, uint32_t *d, int *dtype, int *metric) {
+    if (!f) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (n) *n = f->n;
+    if (d) *d = f->d;
+    if (dtype) *dtype = f->dtype;
+    if (metric) *metric = f->metric;
+    return VQHIP_OK;
+}
+
+int vqhip_flat_search(vqhip_flat *f, const float *queries, uint32_t nq, uint32_t topk, uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    if (!f || !queries || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    VQ_TRY(flat_check_topk(f, topk));
+    if (nq == 0) return VQHIP_OK;
+    VQ_TRY(require_gfx950());
+    Entry in(f->sync);
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    VQ_TRY(f->q.ensure((size_t)nq * f->d * 4));
+    VQ_TRY(f->idx.ensure((size_t)nq * topk * 4));
+    VQ_TRY(f->out.ensure((size_t)nq * topk * 4));
+    VQ_HIP(hipMemcpyAsync(f->q.p, queries, (size_t)nq * f->d * 4, hipMemcpyHostToDevice, s));
+    VQ_TRY(flat_search_enqueue(f, f->q.as<float>(), nq, topk, f->idx.as<uint32_t>(), f->out.as<float>(), s));
+    VQ_HIP(hipMemcpyAsync(idx_out, f->idx.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipMemcpyAsync(dist_out, f->out.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipStreamSynchronize(s));
+    in.synced();
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_flat_search_device(vqhip_flat *f, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx, void *dev_dist) {
+    VQ_API_BEGIN
+    if (!f || !dev_queries || !dev_idx || !dev_dist) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    VQ_TRY(flat_check_topk(f, topk));
+    if (nq == 0) return VQHIP_OK;
+    VQ_TRY(require_gfx950());
+    Entry in(f->sync);
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    return flat_search_enqueue(f, reinterpret_cast<const float *>(dev_queries), nq, topk, reinterpret_cast<uint32_t *>(dev_idx),
+                               reinterpret_cast<float *>(dev_dist), s);
+    VQ_API_END
+}
+
+int vqhip_flat_rerank(vqhip_flat *f, const float *queries, uint32_t nq, const uint32_t *cand, uint32_t c, uint32_t topk,
+                      uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    if (!f || !queries || !cand || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (c == 0 || c > 4096) return fail(VQHIP_ERR_INVALID_INPUT, "candidates per query %u must be in [1, 4096]", c);
+    if (topk == 0 || topk > c) return fail(VQHIP_ERR_INVALID_INPUT, "topk %u must be in [1, candidates = %u]", topk, c);
+    if (nq == 0) return VQHIP_OK;
+    VQ_TRY(require_gfx950());
+    Entry in(f->sync);
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    VQ_TRY(f->q.ensure((size_t)nq * f->d * 4));
+    VQ_TRY(f->rr_cand.ensure((size_t)nq * c * 4));
+    VQ_TRY(f->idx.ensure((size_t)nq * topk * 4));
+    VQ_TRY(f->out.ensure((size_t)nq * topk * 4));
+    VQ_TRY(f->rr_err.ensure(4));
+    VQ_HIP(hipMemcpyAsync(f->q.p, queries, (size_t)nq * f->d * 4, hipMemcpyHostToDevice, s));
+    VQ_HIP(hipMemcpyAsync(f->rr_cand.p, cand, (size_t)nq * c * 4, hipMemcpyHostToDevice, s));
+    VQ_HIP(hipMemsetAsync(f->rr_err.p, 0, 4, s));
+    const float *qn = nullptr;
+    if (vq_is_cos(f->metric)) {
+        VQ_TRY(f->qnorm.ensure((size_t)nq * 4));
+        VQ_TRY(launch_knn_norms(f->q.p, 0, nq, f->d, f->qnorm.as<float>(), s));
+        qn = f->qnorm.as<float>();
+    }
+    VQ_TRY(launch_knn_rerank(f->metric, f->rows.p, f->dtype, f->n, f->d, f->rnorm.as<float>(), f->q.as<float>(), qn, nq,
+                             f->rr_cand.as<uint32_t>(), c, topk, f->idx.as<uint32_t>(), f->out.as<float>(), f->rr_err.as<uint32_t>(), s));
+    uint32_t err = 0;
+    VQ_HIP(hipMemcpyAsync(&err, f->rr_err.p, 4, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipMemcpyAsync(idx_out, f->idx.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipMemcpyAsync(dist_out, f->out.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipStreamSynchronize(s));
+    in.synced();
+    if (err) return fail(VQHIP_ERR_INVALID_INPUT, "a candidate row id is >= n = %llu", (unsigned long long)f->n);
+    return VQHIP_OK;
+    VQ_API_END
+}
+
 // ---------------------------------------------------------------------------- TSVQ ----
 int vqhip_tsvq_build(const vqhip_dataset *ds, uint32_t max_depth, uint32_t cap, float *centroids, int32_t *left,
                      int32_t *right, int32_t *n_nodes) {

@@ -257,6 +257,19 @@ int launch_adc_search_fast(const float *cb, uint32_t m, uint32_t k, uint32_t sd,
                            unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev, uint32_t *redo_dev,
                            hipStream_t stream);
 
+// exact k-NN search over resident rows and exact rerank of candidate lists (k_knn.hip); X [n][d] f32 (dtype 0) or f16
+// bits (dtype 1), rnorm [n] the rows' norms (cosine only, else unused)
+int launch_knn_norms(const void *X, int dtype, uint64_t n, uint32_t d, float *out, hipStream_t stream);
+uint32_t knn_query_batch(uint64_t n, uint32_t nq);
+size_t knn_state_bytes(uint32_t qb);
+size_t knn_cand_bytes(uint32_t qb);
+int launch_knn_search(int metric, const void *X, int dtype, uint64_t n, uint32_t d, const float *rnorm, const float *queries_dev,
+                      const float *qnorm_dev, uint32_t nq, uint32_t topk, float *dist_ws, void *state_ws,
+                      unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev, hipStream_t stream);
+int launch_knn_rerank(int metric, const void *X, int dtype, uint64_t n, uint32_t d, const float *rnorm, const float *queries_dev,
+                      const float *qnorm_dev, uint32_t nq, const uint32_t *cand_dev, uint32_t c, uint32_t topk,
+                      uint32_t *idx_out_dev, float *dist_out_dev, uint32_t *err_dev, hipStream_t stream);
+
 // prepared per-node data of the screened squared-L2 / Euclidean descent (k_tsvq_screen.hip)
 struct TsvqScreen {
     const float *w = nullptr;     // [n_int][d]  c_left - c_right of every two-child node; cosine: [n_int][2][d] unit vectors of the children

@@ -10,7 +10,8 @@ For every sample count of `NUM_SAMPLES` it prints the reference's three lines --
 quantization time (host matrix in, f16 matrix out: what `quantize` per vector produces there)
 and the mean squared reconstruction error -- and the two `BenchmarkResult` fields the binaries
 compute nowhere: recall@k with `calculate_recall`'s windowed protocol (common.rs:91-130) and
-the memory reduction ratio.  `--json` emits one `BenchmarkResult`-shaped object per line.
+the memory reduction ratio.  `--recall-full` replaces the window by an exact search of every
+sampled query over all n rows (FlatIndex) on the device.  `--json` emits one `BenchmarkResult`-shaped object per line.
 
 `sq` / `bq` follow src/bin/eval_sq.rs / eval_bq.rs: ScalarQuantizer(0, 1, levels) and
 BinaryQuantizer(0.5, 0, 1), "training" being the constructor; the reference's two lines plus the
@@ -60,6 +61,33 @@ def recall_at_k(original: np.ndarray, approx: np.ndarray, k: int = 10) -> float:
     return total / (n // step)
 
 
+def recall_at_k_full(original: np.ndarray, approx_f16: np.ndarray, k: int = 10) -> float:
+    """recall@k without the window: the same <= 1000 strided queries, each searched exactly (FlatIndex, squared
+    Euclidean) over ALL n originals (f32 index) and over all n f16 reconstructions (f16 index, the query being its own
+    reconstruction).  A query's own row is excluded by searching k + 1 and dropping that row where it is returned,
+    else the last one; ties go to the lower row."""
+    from .distance import Distance
+    from .flat import FlatIndex
+
+    n = original.shape[0]
+    k = min(k, n - 1)
+    step = max(n // min(n, 1000), 1)
+    qi = np.arange(0, n, step)
+    dist = Distance.squared_euclidean()
+
+    def neighbours(rows, queries):
+        idx, _ = FlatIndex(rows, dist).search(queries, k + 1)
+        out = np.empty((len(qi), k), idx.dtype)
+        for j, i in enumerate(qi):
+            hit = np.flatnonzero(idx[j] == i)
+            out[j] = np.delete(idx[j], hit[0]) if hit.size else idx[j, :k]
+        return out
+
+    t = neighbours(original, original[qi])
+    a = neighbours(approx_f16, approx_f16[qi].astype(np.float32))
+    return float(np.mean([len(np.intersect1d(t[j], a[j])) / k for j in range(len(qi))]))
+
+
 def _report(title, make_quantizer, args, code_bytes_per_vector):
     from . import _lib
 
@@ -78,7 +106,8 @@ def _report(title, make_quantizer, args, code_bytes_per_vector):
         res = {"n_samples": n, "n_dims": args.dim, "training_time_ms": train_ms,
                "quantization_time_ms": quant_ms, "reconstruction_error": err}
         if args.recall_k > 0:
-            res["recall"] = recall_at_k(X, rec, args.recall_k)
+            res["recall"] = (recall_at_k_full(X, f16, args.recall_k) if args.recall_full
+                             else recall_at_k(X, rec, args.recall_k))
         # the reference keeps the f16 reconstruction (2 bytes per dimension); the codes are smaller
         res["memory_reduction_ratio"] = 4.0 * args.dim / (2.0 * args.dim)
         res["memory_reduction_ratio_codes"] = 4.0 * args.dim / code_bytes_per_vector(q)
@@ -90,7 +119,8 @@ def _report(title, make_quantizer, args, code_bytes_per_vector):
         print(f"  Quantization time: {quant_ms:.0f} ms")
         print(f"  Reconstruction error: {err:.6f}")
         if "recall" in res:
-            print(f"  Recall@{args.recall_k}: {res['recall']:.4f}")
+            full = " (exact, all rows)" if args.recall_full else ""
+            print(f"  Recall@{args.recall_k}{full}: {res['recall']:.4f}")
         print(f"  Memory reduction: {res['memory_reduction_ratio']:.1f}x as f16, "
               f"{res['memory_reduction_ratio_codes']:.1f}x as codes")
 
@@ -139,6 +169,8 @@ def main(argv=None) -> int:
         p.add_argument("--dim", type=int, default=DIM)
         p.add_argument("--samples", type=int, nargs="+", default=NUM_SAMPLES)
         p.add_argument("--recall-k", type=int, default=10, help="0 skips the recall estimate")
+        p.add_argument("--recall-full", action="store_true",
+                       help="recall@k by exact search over all rows on the device instead of the windowed protocol")
         p.add_argument("--json", action="store_true")
         if name == "pq":
             p.add_argument("--m", type=int, default=M)

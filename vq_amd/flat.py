@@ -1,0 +1,154 @@
+"""``FlatIndex`` -- exact k-nearest-neighbour search over rows kept on the device.
+
+The reference has no search function; the semantics are include/vqhip.h's (vqhip_flat_*, vq_amd/csrc/k_knn.hip):
+``D(q, i)`` is ``Distance.compute(q, rows[i])`` bit for bit (f16 rows widened exactly to f32 first), the result per
+query is the ``topk`` rows by ``(D, row index)`` ascending with NaN last, and ``rerank`` applies the same order to a
+caller's candidate lists.  Every argument is checked here before the device is touched; the rows go to the device once,
+on the first search (until then the index refers to the caller's array, which must not change in between).
+"""
+from __future__ import annotations
+
+import operator
+
+import numpy as np
+
+from . import _lib
+from .distance import Distance
+from .errors import DimensionMismatch, EmptyInput, InvalidParameter
+
+MAX_TOPK = 1024
+MAX_CANDIDATES = 4096
+
+
+def _count(v, name: str) -> int:
+    try:
+        return operator.index(v)
+    except TypeError:
+        raise InvalidParameter(name, f"must be an integer, got {v!r}") from None
+
+
+class FlatIndex:
+    """Exact search over `rows` (n, d) float32 or float16 under `distance` (any metric, cosine included)."""
+
+    def __init__(self, rows, distance: Distance | None = None):
+        if distance is None:
+            distance = Distance.euclidean()
+        if not isinstance(distance, Distance):
+            raise InvalidParameter("distance", f"expected a Distance, got {type(distance).__name__}")
+        a = rows if isinstance(rows, np.ndarray) else np.asarray(rows)
+        if a.dtype not in (np.float32, np.float16):
+            raise InvalidParameter("rows", f"dtype must be float32 or float16, got {a.dtype}")
+        if a.ndim != 2:
+            raise ValueError("expected a 2D array (n, dim)")
+        if a.shape[0] == 0:
+            raise EmptyInput()
+        if a.shape[1] == 0:
+            raise InvalidParameter("rows", "dimension must be at least 1")
+        if a.shape[0] >= 1 << 32:
+            raise InvalidParameter("rows", f"at most 2^32 - 1 rows, got {a.shape[0]}")
+        self._rows = np.ascontiguousarray(a)
+        self._n, self._dim = a.shape
+        self._dtype = a.dtype
+        self._distance = distance
+        self._flat = None
+
+    def __len__(self) -> int:
+        return self._n
+
+    @property
+    def dim(self) -> int:
+        return self._dim
+
+    @property
+    def dtype(self) -> np.dtype:
+        return np.dtype(self._dtype)
+
+    @property
+    def distance(self) -> Distance:
+        return self._distance
+
+    def __repr__(self) -> str:
+        return f"FlatIndex(n={self._n}, dim={self._dim}, dtype={np.dtype(self._dtype).name}, distance={self._distance!r})"
+
+    def _index(self) -> "_lib.Flat":
+        if self._flat is None:
+            self._flat = _lib.Flat(self._rows, self._distance.metric)
+            self._rows = None  # on the device now
+        return self._flat
+
+    def _queries(self, queries) -> np.ndarray:
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2:
+            raise ValueError("expected a 2D array (nq, dim)")
+        if q.shape[1] != self._dim:
+            raise DimensionMismatch(self._dim, q.shape[1])
+        return q
+
+    def _topk(self, topk, limit: int, what: str) -> int:
+        k = _count(topk, "topk")
+        if not 1 <= k <= limit:
+            raise InvalidParameter("topk", f"must be between 1 and {what}, got {k}")
+        return k
+
+    def search(self, queries, topk: int = 10):
+        """(nq, d) float32 queries -> (indices uint32 (nq, topk), distances float32 (nq, topk)), nearest first"""
+        q = self._queries(queries)
+        k = self._topk(topk, min(self._n, MAX_TOPK), "min(n, 1024)")
+        if q.shape[0] == 0:
+            return np.empty((0, k), np.uint32), np.empty((0, k), np.float32)
+        return self._index().search(q, k)
+
+    def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int) -> None:
+        """device pointers: queries [nq][d] f32, results [nq][topk] uint32 / f32 (4-byte aligned); asynchronous on the
+        current stream"""
+        k = self._topk(topk, min(self._n, MAX_TOPK), "min(n, 1024)")
+        n_q = _count(nq, "nq")
+        if n_q < 0 or n_q >= 1 << 32:
+            raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
+        self._index().search_device(int(dev_queries), n_q, k, int(dev_idx), int(dev_dist))
+
+    def rerank(self, queries, candidates, topk: int = 10):
+        """per query, the `topk` nearest of its candidate row ids (nq, c), 1 <= c <= 4096, distinct within a query;
+        returns (indices uint32 (nq, topk), distances float32 (nq, topk)) in the order of `search`"""
+        q = self._queries(queries)
+        c = np.asarray(candidates)
+        if c.ndim == 1 and q.shape[0] == 1:
+            c = c[None, :]
+        if c.ndim != 2:
+            raise ValueError("expected candidates as a 2D array (nq, c)")
+        if c.shape[0] != q.shape[0]:
+            raise DimensionMismatch(q.shape[0], c.shape[0])
+        if c.dtype.kind not in "iu":
+            raise InvalidParameter("candidates", f"row ids must be integers, got {c.dtype}")
+        if not 1 <= c.shape[1] <= MAX_CANDIDATES:
+            raise InvalidParameter("candidates", f"between 1 and {MAX_CANDIDATES} per query, got {c.shape[1]}")
+        k = self._topk(topk, c.shape[1], "the number of candidates")
+        if q.shape[0] == 0:
+            return np.empty((0, k), np.uint32), np.empty((0, k), np.float32)
+        lo, hi = int(c.min()), int(c.max())
+        if lo < 0 or hi >= self._n:
+            bad = lo if lo < 0 else hi
+            raise InvalidParameter("candidates", f"row id {bad} is outside [0, {self._n})")
+        s = np.sort(c, axis=1)
+        if c.shape[1] > 1 and bool((s[:, 1:] == s[:, :-1]).any()):
+            raise InvalidParameter("candidates", "row ids must be distinct within a query")
+        return self._index().rerank(q, np.ascontiguousarray(c, dtype=np.uint32), k)
+
+
+def adc_then_rerank(adc_search, n: int, dim: int, queries: np.ndarray, topk: int, rerank, candidates):
+    """the standard PQ pipeline: `adc_search(queries, c)` for a short list of c candidates per query (default 4 topk,
+    at most 1024 -- ADC's own limit -- and n), then the exact rerank of that list through the FlatIndex `rerank` over
+    the same n rows.  The flat index's metric is its own (cosine allowed)."""
+    if not isinstance(rerank, FlatIndex):
+        raise InvalidParameter("rerank", f"expected a FlatIndex, got {type(rerank).__name__}")
+    if len(rerank) != n:
+        raise DimensionMismatch(n, len(rerank))
+    if rerank.dim != dim:
+        raise DimensionMismatch(dim, rerank.dim)
+    c = min(4 * topk, MAX_TOPK, n) if candidates is None else _count(candidates, "candidates")
+    if not topk <= c <= min(n, MAX_TOPK):
+        raise InvalidParameter("candidates", f"must be between topk and min(n, 1024), got {c}")
+    idx, _ = adc_search(queries, c)
+    return rerank.rerank(queries, idx, topk)

@@ -273,10 +273,19 @@ class ProductQuantizer:
             return np.empty((0, self._m), _lib.code_dtype(self._k))
         return self._batch_encoder(X.shape[0]).encode(X, want_codes=True, want_f16=False)[0]
 
-    def search(self, codes, queries, topk: int = 10):
+    def search(self, codes, queries, topk: int = 10, *, rerank=None, candidates: int | None = None):
         """Asymmetric-distance search: the `topk` rows of `codes` (n, m) (uint8, uint16 above 256 centroids)
         nearest to each query under this quantizer's metric, distances from per-subspace tables.
-        Returns (indices uint32 (nq, topk), distances float32 (nq, topk)); ties by lower row."""
+        Returns (indices uint32 (nq, topk), distances float32 (nq, topk)); ties by lower row.
+        rerank: a FlatIndex over the same n rows -- ADC then finds `candidates` rows per query (default 4 topk, at most
+        1024) and the result is their exact top-k under the flat index's metric (FlatIndex.rerank)."""
+        if rerank is not None:
+            from .flat import adc_then_rerank
+
+            q = np.ascontiguousarray(queries, dtype=np.float32)
+            q = q[None, :] if q.ndim == 1 else q
+            n = np.asarray(codes).shape[0]
+            return adc_then_rerank(lambda qq, c: self.search(codes, qq, c), n, self._dim, q, topk, rerank, candidates)
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
             q = q[None, :]

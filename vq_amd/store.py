@@ -91,10 +91,18 @@ class PQIndex:
         """what `ProductQuantizer::quantize` returned for these rows (f16, RNE; src/pq.rs:192-196)"""
         return self.reconstruct(rows).astype(np.float16)
 
-    def search(self, queries, topk: int = 10):
-        """top-k stored rows per query by asymmetric distance (device path; see ProductQuantizer.search)"""
+    def search(self, queries, topk: int = 10, *, rerank=None, candidates: int | None = None):
+        """top-k stored rows per query by asymmetric distance (device path; see ProductQuantizer.search, also for
+        `rerank` / `candidates`: exact rerank of an ADC short list through a FlatIndex over the same rows)"""
         from . import _lib
         from .errors import DimensionMismatch, InvalidParameter
+
+        if rerank is not None:
+            from .flat import adc_then_rerank
+
+            q = np.ascontiguousarray(queries, dtype=np.float32)
+            q = q[None, :] if q.ndim == 1 else q
+            return adc_then_rerank(lambda qq, c: self.search(qq, c), len(self), self.dim, q, topk, rerank, candidates)
 
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
