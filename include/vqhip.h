@@ -436,7 +436,9 @@ int vqhip_distance_batch(int metric, const float *a, const float *b, uint64_t n,
  * queries against a threshold from a sample of the rows and keep only the rows at or below it; a
  * query whose threshold let fewer than topk (or more than 8192) rows pass -- and every other shape
  * -- goes through the full pass (all distances, histogram cut).  vqhip_pq_adc_last_redone: how many
- * queries of the encoder's last call took the full pass (diagnostics; VQHIP_ADC_FAST=0 sends all). */
+ * queries of the encoder's last call took the full pass (diagnostics; VQHIP_ADC_FAST=0 sends all).
+ * Table limit: m * k <= 38400 (one query's f32 table in 150 KiB of LDS), the same for both schedules;
+ * a larger table is refused with VQHIP_ERR_UNSUPPORTED before any work, whatever n and topk. */
 int vqhip_pq_adc_search(vqhip_pq_encoder *enc, const uint8_t *codes, uint64_t n, const float *queries,
                         uint32_t nq, uint32_t topk, uint32_t *idx_out, float *dist_out);
 int vqhip_pq_adc_search_device(vqhip_pq_encoder *enc, const void *dev_codes, uint64_t n,

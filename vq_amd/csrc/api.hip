@@ -15,6 +15,7 @@
 #include <thread>
 #include <vector>
 
+#include "adc_plan.hpp"
 #include "kernels.hpp"
 
 namespace vqhip {
@@ -2343,6 +2344,8 @@ int vqhip_pq_adc_search_device(vqhip_pq_encoder *enc, const void *dev_codes, uin
         enc->adc_last_redone = redone;
         return VQHIP_OK;
     }
+    // (refused before any workspace is sized by the table: both schedules take m * k <= kAdcMaxTable, adc_plan.hpp)
+    if (!vq_is_cos(enc->metric) && !adc_table_fits(m, k)) return fail_adc_table(m, k);
     VQ_TRY(enc->adc_q.ensure((size_t)nq * dim * 4));
     VQ_TRY(enc->adc_idx.ensure((size_t)nq * topk * 4));
     VQ_TRY(enc->adc_out.ensure((size_t)nq * topk * 4));

@@ -13,6 +13,7 @@
 //   * the full pass: the table t (k_adc_lut), a byte-gather scan of the codes with the tables of 8 queries in LDS that
 //     writes every D(q, i) (k_adc_scan), a histogram cut + candidate sort (k_adc_pick_bin / _collect / _sort_out) and an
 //     exact per-query radix select where the cut is too dense (k_adc_topk).
+#include "adc_plan.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
 #include "topk.hpp"
@@ -80,7 +81,7 @@ __global__ __launch_bounds__(256) void k_adc_scan(const uint8_t *__restrict__ co
                                                   uint32_t k, const float *__restrict__ lut, uint32_t nq_group, uint32_t qb,
                                                   const float *__restrict__ bounds, float *__restrict__ dist,
                                                   uint32_t *__restrict__ hist) {
-    extern __shared__ float lds_lut[];  // [nqb][m][k], then the block's histograms [nqb][kAdcBins]
+    extern __shared__ __attribute__((aligned(16))) float lds_lut[];  // [nqb][m][k], then the block's histograms [nqb][kAdcBins]
     const uint32_t tab = m * k;
     const uint32_t q_first = blockIdx.y * qb;
     const uint32_t nqb = min(qb, nq_group - q_first);
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(256) void k_adc_collect(const float *__restrict__ d
 // k_adc_sort_thr flags the queries where that fails and the caller sends those through the pass above.
 // Tables are interleaved over the batch's queries, [s][j][QB]: one LDS address per (row, subspace) yields all QB terms
 // (QB / 4 ds_read_b128 instead of QB ds_read_b32 and their offsets).
-__host__ __device__ __forceinline__ uint32_t adc_tabp(uint32_t m, uint32_t k, uint32_t qb) { return (m * k * qb + 3u) & ~3u; }  // floats per batch of tables (16-byte units)
+// (floats per batch of tables: adc_tabp, adc_plan.hpp)
 template <uint32_t QB>
 __global__ __launch_bounds__(256) void k_adc_lut_i(const float *__restrict__ queries, uint32_t nq, uint32_t m, uint32_t k,
                                                    uint32_t sd, const float *__restrict__ cb, int l1, float *__restrict__ lut) {
@@ -247,7 +248,6 @@ __device__ __forceinline__ void adc_tables_to_lds(float *__restrict__ lds, const
 // its threshold: for j well below 16 G that is close to the j-th smallest of all S = 1024 G rpt sampled distances, the
 // j / S quantile -- about n j / S rows at or below it (the host picks G, rpt, j for 1024-4096 of them).  One workgroup
 // per batch (round 6's first form) spent 40 us reading its own CU's LDS; the tables' 64 KB per workgroup are the cost now.
-constexpr uint32_t kAdcStage = 128;    // candidates a workgroup stages per query before it appends them to the query's list
 constexpr uint32_t kAdcCntStride = 64;  // the queries' list counters sit 256 bytes apart: 64 of them in two cache lines took
                                         // every append of every workgroup through one L2 channel (~10 ns each: 320 us of a 64-query scan)
 constexpr uint32_t kAdcMaxG = 64;  // sampler workgroups per batch (16 kAdcMaxG minima per query at most)
@@ -255,7 +255,7 @@ template <uint32_t QB>
 __global__ __launch_bounds__(1024) void k_adc_thresh(const uint8_t *__restrict__ codes, uint64_t n, uint32_t m, uint32_t k,
                                                      const float *__restrict__ lut, uint32_t rpt, float *__restrict__ wmins,
                                                      uint32_t *__restrict__ cand_n) {
-    extern __shared__ float lds_lut[];  // [m][k][QB]
+    extern __shared__ __attribute__((aligned(16))) float lds_lut[];  // [m][k][QB]
     const uint32_t tab = adc_tabp(m, k, QB), batch = blockIdx.y, G = gridDim.x;
     adc_tables_to_lds(lds_lut, lut + (size_t)batch * tab, tab, 1024);
     // (the candidate lists' counters start at zero: one launch less than a memset in front)
@@ -319,12 +319,14 @@ __global__ __launch_bounds__(NT) void k_adc_scan_thr(const uint8_t *__restrict__
     static_assert(NT >= 64 * QB, "one wave per query places its threshold");
     static_assert(QB % LQ == 0 && (LQ == 1 || QB / LQ == 4), "a lane holds all of the batch's queries or four of them");
     constexpr uint32_t QL = QB / LQ, RPB = NT / LQ;  // queries per lane, rows per pass of the workgroup
-    extern __shared__ float lds_lut[];  // [m][k][QB], then the staged candidates [QB][kAdcStage] (8 bytes each) and their counts [QB]
+    // [m][k][QB], then the staged candidates [QB][kAdcStage] (8 bytes each), their counts [QB], the list bases [QB] and
+    // the thresholds [QB] (adc_scan_thr_lds; no static LDS in front of the tables)
+    extern __shared__ __attribute__((aligned(16))) float lds_lut[];
     const uint32_t tab = adc_tabp(m, k, QB), batch = blockIdx.y, q_first = batch * QB;
     unsigned long long *stage = reinterpret_cast<unsigned long long *>(lds_lut + tab);
     uint32_t *stage_n = reinterpret_cast<uint32_t *>(stage + QB * kAdcStage);
-    __shared__ uint32_t s_base[QB];
-    __shared__ float s_T[QB];
+    uint32_t *s_base = stage_n + QB;
+    float *s_T = reinterpret_cast<float *>(s_base + QB);
     adc_tables_to_lds(lds_lut, lut + (size_t)batch * tab, tab, NT);
     if (threadIdx.x < QB) stage_n[threadIdx.x] = 0u;
     if (threadIdx.x < 64 * QB) {  // wave qq: the threshold of the batch's query qq (padding queries: nothing passes)
@@ -468,11 +470,12 @@ int adc_fast_launch(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int l1
                     const float *queries_dev, uint32_t nq, uint32_t topk, float *lut_ws, void *state_ws,
                     unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev, uint32_t *redo_dev,
                     hipStream_t stream, uint32_t G, uint32_t rpt, uint32_t order, int force_redo) {
-    const size_t tab_b = (size_t)adc_tabp(m, k, QB) * 4;
+    const AdcPlan plan = adc_fast_plan(m, k);
     static PerDeviceOnce attr;
-    if (attr.needed()) {
-        VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_adc_scan_thr<QB, LQ, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
-        VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_adc_thresh<QB>), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
+    if (attr.needed()) {  // the most this instantiation's plans ask for
+        VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_adc_scan_thr<QB, LQ, NT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)adc_scan_thr_lds_max(QB)));
+        VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_adc_thresh<QB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAdcTableLds));
         VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_adc_sort_thr), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kAdcCand * 8)));
         attr.done();
     }
@@ -482,9 +485,9 @@ int adc_fast_launch(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int l1
     uint32_t *cand_n = reinterpret_cast<uint32_t *>(wmins + (size_t)batches * QB * 16 * kAdcMaxG);
     hipLaunchKernelGGL(k_adc_lut_i<QB>, dim3(batches * QB, m), dim3(256), 0, stream, queries_dev, nq, m, k, sd, cb, l1, lut_ws);
     VQ_LAUNCH_CHECK("k_adc_lut_i");
-    hipLaunchKernelGGL(k_adc_thresh<QB>, dim3(G, batches), dim3(1024), tab_b, stream, codes, n, m, k, lut_ws, rpt, wmins, cand_n);
+    hipLaunchKernelGGL(k_adc_thresh<QB>, dim3(G, batches), dim3(1024), plan.lut_lds, stream, codes, n, m, k, lut_ws, rpt, wmins, cand_n);
     VQ_LAUNCH_CHECK("k_adc_thresh");
-    const size_t scan_lds = tab_b + QB * kAdcStage * 8 + QB * 4;
+    const size_t scan_lds = plan.scan_lds;
     const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>(2048 / NT, (158 * 1024) / scan_lds));
     uint64_t blocks = (n + NT / LQ - 1) / (NT / LQ);
     const uint64_t cap = std::max<uint64_t>(1, ((uint64_t)num_cus() * per_cu + batches - 1) / batches);
@@ -508,14 +511,14 @@ int launch_adc_search(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int 
     if (vq_is_cos(metric))
         return fail(VQHIP_ERR_UNSUPPORTED, "cosine distance is not a sum over subspaces: no ADC form");
     if (topk == 0 || topk > 1024 || topk > n) return fail(VQHIP_ERR_INVALID_INPUT, "topk must be in [1, min(n, 1024)]");
-    // queries per scan pass: as many tables as the LDS holds, at most kAdcQB
-    const size_t lds_budget = 150 * 1024;
-    uint32_t qb = (uint32_t)std::min<size_t>(kAdcQB, lds_budget / (((size_t)m * k + kAdcBins) * 4));
-    if (qb == 0) return fail(VQHIP_ERR_UNSUPPORTED, "one ADC table (m=%u, k=%u) exceeds the LDS", m, k);
+    // queries per scan pass: as many tables as the LDS holds, at most kAdcQB (adc_plan.hpp)
+    const AdcPlan plan = adc_full_plan(m, k);
+    if (plan.qb == 0) return fail_adc_table(m, k);
+    const uint32_t qb = plan.qb;
     static PerDeviceOnce attr;
     if (attr.needed()) {
         VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_adc_scan), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   150 * 1024));
+                                   (int)kAdcFullScanLdsMax));
         VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_adc_sort_out),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kAdcCand * 8)));
         attr.done();
@@ -525,7 +528,7 @@ int launch_adc_search(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int 
     // the scan: every workgroup first copies the batch's tables (64 KB at m = 8, k = 256, 8 queries) into LDS -- two
     // workgroups per CU is what that LDS allows, and 2048 of them spent the pass re-reading tables (128 MB of L2 traffic for
     // 8 MB of codes: 70 us per pass at 1M rows)
-    const size_t scan_lds = (size_t)qb * ((size_t)m * k + kAdcBins) * 4;
+    const size_t scan_lds = plan.scan_lds;
     const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>(8, (150 * 1024) / std::max<size_t>(scan_lds, 1)));
     // A GROUP of up to `qgroup` queries (the caller's workspaces: adc_query_group(n)) goes through one set of launches: the
     // six kernels of a pass are dependent and tiny (5-25 us each, 110 us per pass whatever the work), so eight passes one
@@ -547,7 +550,7 @@ int launch_adc_search(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int 
         hipLaunchKernelGGL(k_adc_lut, dim3(nqg, m), dim3(256), 0, stream, queries_dev + (size_t)q0 * m * sd, nqg, m, k, sd,
                            cb, l1, lut_ws, bounds);
         VQ_LAUNCH_CHECK("k_adc_lut");
-        hipLaunchKernelGGL(k_adc_scan, dim3((uint32_t)blocks, batches), dim3(256), (size_t)qb * (m * k + kAdcBins) * 4, stream,
+        hipLaunchKernelGGL(k_adc_scan, dim3((uint32_t)blocks, batches), dim3(256), scan_lds, stream,
                            codes, n, m, k, lut_ws, nqg, qb, bounds, dist_ws, hist);
         VQ_LAUNCH_CHECK("k_adc_scan");
         // top-k: candidates below a histogram cut, sorted in LDS; dense cuts fall back to the radix select
@@ -577,20 +580,22 @@ uint32_t adc_query_group(uint64_t n, uint32_t nq) {
 bool adc_fast_eligible(uint32_t m, uint32_t k, uint64_t n, uint32_t topk) {
     static const char *env = getenv("VQHIP_ADC_FAST");
     if (env && env[0] == '0') return false;
-    return n >= 32768 && topk <= 256 && (size_t)m * k * 4 <= 150 * 1024;
+    return n >= 32768 && topk <= 256 && adc_fast_plan(m, k).qb != 0;
 }
-// queries per scan batch: the largest power of two up to eight whose interleaved tables fit the LDS.  (Sixteen per batch,
-// four lanes per row, one workgroup of 1024 per CU: scan 59.8 us against ~57 for 64 queries over 1M rows, and the
-// sampler's workgroups load 128 KB of tables each -- 14.6 us against 7.9: not kept.)
+// queries per scan batch: the largest power of two up to eight whose interleaved tables fit the LDS (adc_fast_plan).
+// (Sixteen per batch, four lanes per row, one workgroup of 1024 per CU: scan 59.8 us against ~57 for 64 queries over 1M
+// rows, and the sampler's workgroups load 128 KB of tables each -- 14.6 us against 7.9: not kept.)
 uint32_t adc_fast_batch(uint32_t m, uint32_t k, uint32_t nq) {
     (void)nq;
-    uint32_t qb = 8;
-    while (qb > 1 && (size_t)m * k * qb * 4 > 150 * 1024) qb >>= 1;
-    return qb;
+    return adc_fast_plan(m, k).qb;
+}
+int fail_adc_table(uint32_t m, uint32_t k) {
+    return fail(VQHIP_ERR_UNSUPPORTED, "one ADC table (m=%u, k=%u: m*k = %llu) exceeds the LDS: m*k must be at most %u", m, k,
+                (unsigned long long)m * k, kAdcMaxTable);
 }
 size_t adc_fast_lut_bytes(uint32_t m, uint32_t k, uint32_t nq) {
     const uint32_t qb = adc_fast_batch(m, k, nq);
-    return (size_t)((nq + qb - 1) / qb) * (((size_t)m * k * qb + 3) & ~(size_t)3) * 4;
+    return (size_t)((nq + qb - 1) / qb) * adc_tabp(m, k, qb) * 4;
 }
 size_t adc_fast_state_bytes(uint32_t m, uint32_t k, uint32_t nq) {
     const uint32_t qb = adc_fast_batch(m, k, nq);

@@ -246,6 +246,8 @@ uint32_t adc_query_batch();
 uint32_t adc_query_group(uint64_t n, uint32_t nq);  // queries that go through one set of launches (a multiple of the batch)
 size_t adc_state_bytes(uint32_t qgroup);
 size_t adc_cand_bytes(uint32_t qgroup);
+// VQHIP_ERR_UNSUPPORTED for a table above the LDS plan's limit (m * k > kAdcMaxTable, adc_plan.hpp): both schedules refuse it
+int fail_adc_table(uint32_t m, uint32_t k);
 // the threshold pass (one scan of the codes, candidates only): all queries in one set of launches; redo_dev[q] = 1 where
 // query q has to be repeated through launch_adc_search
 bool adc_fast_eligible(uint32_t m, uint32_t k, uint64_t n, uint32_t topk);

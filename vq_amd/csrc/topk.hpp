@@ -5,6 +5,7 @@
 //   k_adc_sort_out      : the candidates of a query sorted by (key, row) in LDS, the first topk out
 //   k_adc_topk          : exact radix select where the candidate cut was too dense
 #pragma once
+#include "adc_plan.hpp"
 #include "common.hpp"
 
 #pragma clang fp contract(off)
@@ -22,7 +23,7 @@ __device__ __forceinline__ float adc_unkey(uint32_t k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
-constexpr uint32_t kAdcBins = 512;  // histogram bins of the candidate filter
+// (kAdcBins, the histogram bins of the candidate filter: adc_plan.hpp)
 constexpr uint32_t kAdcCand = 8192; // candidates the fast top-k path sorts in LDS
 
 // fast top-k, step 1: the bin that holds the k-th smallest value; sel[q] = {bin, candidates up to it}

@@ -277,6 +277,8 @@ class ProductQuantizer:
         """Asymmetric-distance search: the `topk` rows of `codes` (n, m) (uint8, uint16 above 256 centroids)
         nearest to each query under this quantizer's metric, distances from per-subspace tables.
         Returns (indices uint32 (nq, topk), distances float32 (nq, topk)); ties by lower row.
+        Tables of m * k <= 38400 entries (one query's table in 150 KiB of LDS); larger ones raise FfiError
+        (VQHIP_ERR_UNSUPPORTED).
         rerank: a FlatIndex over the same n rows -- ADC then finds `candidates` rows per query (default 4 topk, at most
         1024) and the result is their exact top-k under the flat index's metric (FlatIndex.rerank)."""
         if rerank is not None:

@@ -35,21 +35,62 @@ def _code_dtype(k: int):
     return np.dtype(np.uint8) if k <= 256 else np.dtype("<u2")
 
 
+def _checked(codebooks, codes):
+    """(codebooks f32 (m, k, sub_dim), codes (n, m) in the library's code width) after the checks of a store"""
+    cb = np.ascontiguousarray(codebooks, dtype=np.float32)
+    if cb.ndim != 3:
+        raise ValueError("codebooks must have shape (m, k, sub_dim)")
+    if cb.shape[1] > 65536:
+        raise ValueError("codes are at most two bytes: k <= 65536")
+    codes = np.asarray(codes)
+    if codes.ndim != 2 or codes.shape[1] != cb.shape[0]:
+        raise ValueError(f"codes must have shape (n, {cb.shape[0]})")
+    if codes.size and (int(codes.min()) < 0 or int(codes.max()) >= cb.shape[1]):
+        raise ValueError("code out of range for the codebooks")
+    return cb, np.ascontiguousarray(codes, dtype=_code_dtype(cb.shape[1]))
+
+
 class PQIndex:
+    """codebooks + codes + distance.  `search` keeps an encoder with the codes on the device; reassigning `codes`,
+    `codebooks` or `distance` drops it, so the next search answers for the new store.  Changing the arrays IN PLACE is
+    not seen: reassign them after such a change."""
+
     def __init__(self, codebooks: np.ndarray, codes: np.ndarray, distance: Distance | None = None):
-        cb = np.ascontiguousarray(codebooks, dtype=np.float32)
-        if cb.ndim != 3:
-            raise ValueError("codebooks must have shape (m, k, sub_dim)")
-        if cb.shape[1] > 65536:
-            raise ValueError("codes are at most two bytes: k <= 65536")
-        codes = np.asarray(codes)
-        if codes.ndim != 2 or codes.shape[1] != cb.shape[0]:
-            raise ValueError(f"codes must have shape (n, {cb.shape[0]})")
-        if codes.size and (int(codes.min()) < 0 or int(codes.max()) >= cb.shape[1]):
-            raise ValueError("code out of range for the codebooks")
-        codes = np.ascontiguousarray(codes, dtype=_code_dtype(cb.shape[1]))
-        self.codebooks, self.codes = cb, codes
-        self.distance = distance if distance is not None else Distance.euclidean()
+        self._codebooks, self._codes = _checked(codebooks, codes)
+        self._distance = distance if distance is not None else Distance.euclidean()
+
+    # -- the store (reassigning a part drops the device copy search keeps) ----------------------
+    def _drop_encoder(self) -> None:
+        enc = self.__dict__.pop("_enc", None)
+        if enc is not None:
+            enc.close()
+
+    @property
+    def codebooks(self) -> np.ndarray:
+        return self._codebooks
+
+    @codebooks.setter
+    def codebooks(self, value) -> None:
+        self._codebooks, self._codes = _checked(value, self._codes)
+        self._drop_encoder()
+
+    @property
+    def codes(self) -> np.ndarray:
+        return self._codes
+
+    @codes.setter
+    def codes(self, value) -> None:
+        self._codebooks, self._codes = _checked(self._codebooks, value)
+        self._drop_encoder()
+
+    @property
+    def distance(self) -> Distance:
+        return self._distance
+
+    @distance.setter
+    def distance(self, value: Distance) -> None:
+        self._distance = value
+        self._drop_encoder()
 
     # -- shape ------------------------------------------------------------------------------
     @property
@@ -93,7 +134,9 @@ class PQIndex:
 
     def search(self, queries, topk: int = 10, *, rerank=None, candidates: int | None = None):
         """top-k stored rows per query by asymmetric distance (device path; see ProductQuantizer.search, also for
-        `rerank` / `candidates`: exact rerank of an ADC short list through a FlatIndex over the same rows)"""
+        `rerank` / `candidates`: exact rerank of an ADC short list through a FlatIndex over the same rows).
+        Tables of m * k <= 38400 entries (one query's table in 150 KiB of LDS); larger ones raise FfiError
+        (VQHIP_ERR_UNSUPPORTED).  Answers for the current codes, codebooks and distance (see the class)."""
         from . import _lib
         from .errors import DimensionMismatch, InvalidParameter
 
@@ -113,8 +156,9 @@ class PQIndex:
             raise InvalidParameter("topk", f"must be between 1 and min(n, 1024), got {topk}")
         if self.distance.metric in (_lib.COSINE, _lib.COSINE_UNCLAMPED):
             raise InvalidParameter("distance", "cosine distance is not a sum over subspaces: no ADC form")
-        # the codes go to the device ONCE (checked against k there); later searches only send the queries
-        enc = getattr(self, "_enc", None)
+        # the codes go to the device ONCE (checked against k there); later searches only send the queries, until a
+        # reassignment of the store drops the encoder
+        enc = self.__dict__.get("_enc")
         if enc is None:
             enc = _lib.PQEncoder(self.codebooks, self.distance.metric)
             enc.adc_set_codes(np.asarray(self.codes))
@@ -156,8 +200,8 @@ class PQIndex:
         for r0 in range(0, n, 1 << 22):
             if codes[r0:r0 + (1 << 22)].size and int(codes[r0:r0 + (1 << 22)].max()) >= k:
                 raise ValueError(f"corrupt index: a code is outside [0, {k})")
-        self = cls.__new__(cls)
-        self.codebooks = cb.reshape(m, k, sd).astype(np.float32)
-        self.codes = codes
-        self.distance = Distance(_METRIC_NAMES[metric])
+        self = cls.__new__(cls)  # (the codes, maybe a memmap, were checked above: not through _checked's copy)
+        self._codebooks = cb.reshape(m, k, sd).astype(np.float32)
+        self._codes = codes
+        self._distance = Distance(_METRIC_NAMES[metric])
         return self
