@@ -273,7 +273,7 @@ int vqhip_comm_kind(const vqhip_comm *comm, int *kind);
  * VQHIP_ERR_RUNTIME at once instead of waiting for it; a poisoned group stays poisoned, its handles destroy normally.
  * vqhip_comm_create_local ends -- and vqhip_comm_create with an id continues -- with an exchange self-test: a
  * rank-dependent pattern is published, every peer's buffer is read on its own and all-reduced, and a wrong word fails
- * the call naming the device pair (VQHIP_COMM_SELFTEST=0 skips it).
+ * the call naming the device pair.
  *   comm_abort : from ANY thread: poison the group of an in-process communicator / ncclCommAbort an owned RCCL one, so
  *                that a thread blocked in a collective with it returns (what the one-process handles below do when one
  *                of their ranks fails) */

@@ -19,7 +19,7 @@ MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 # kernels launched with dynamic LDS, and the instantiations the schedules launch
 DYNAMIC = {"k_adc_scan", "k_adc_thresh", "k_adc_scan_thr", "k_adc_sort_thr", "k_adc_sort_out"}
 EXPECTED = ["k_adc_scanE", "k_adc_sort_thrE", "k_adc_sort_outE"] + [f"k_adc_threshILj{q}E" for q in (1, 2, 4, 8)] + [
-    f"k_adc_scan_thrILj{q}ELj{lq}ELj512E" for q, lq in ((1, 1), (2, 1), (4, 1), (8, 1), (8, 2))]
+    f"k_adc_scan_thrILj{q}ELj{lq}ELj512E" for q, lq in ((1, 1), (2, 1), (4, 1), (8, 2))]
 
 
 def _tool(name):

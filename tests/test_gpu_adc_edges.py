@@ -188,13 +188,12 @@ _CHILD = textwrap.dedent("""
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("env,shape,all_redone", [
-    ({"VQHIP_ADC_LQ1": "1"}, (40_000, 8, 256, 2, 11, 10), False),    # qb 8, a row per lane: k_adc_scan_thr<8, 1, 512>
     ({"VQHIP_ADC_FAST": "0"}, (40_000, 32, 256, 1, 6, 10), True),    # qb 4 table, n >= 32768: the full pass
     ({"VQHIP_ADC_FAST": "0"}, (40_000, 64, 256, 1, 3, 10), True),    # qb 2 table
     ({"VQHIP_TEST_ADC_REDO": "1"}, (40_000, 32, 256, 1, 6, 10), True),   # every query of a qb 4 one-scan repeated
     ({"VQHIP_TEST_ADC_REDO": "1"}, (40_000, 64, 256, 1, 3, 10), True),   # qb 2
     ({"VQHIP_TEST_ADC_REDO": "1"}, (40_000, 100, 256, 1, 3, 10), True),  # qb 1
-], ids=["lq1-qb8", "fast0-qb4", "fast0-qb2", "redo-qb4", "redo-qb2", "redo-qb1"])
+], ids=["fast0-qb4", "fast0-qb2", "redo-qb4", "redo-qb2", "redo-qb1"])
 def test_gpu_adc_env_switches_give_the_same_bits(oracle, tmp_path, env, shape, all_redone):
     n, m, k, sd, nq, topk = shape
     metric = O.EUCLIDEAN

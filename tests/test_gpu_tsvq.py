@@ -252,8 +252,7 @@ def test_screened_descent_adversarial(oracle):
 def test_folded_continuation_with_full_lists(oracle, metric):
     """Round 6: a wave finishes its own undecided rows.  Here most rows are undecided -- on or within an ulp of the root's
     bisecting plane -- so every wave's list (64 entries in LDS) fills up several times and the tile loop is left and
-    re-entered; leaves and f16 rows equal the oracle's, and the two-kernel form's (VQHIP_TSVQ_FOLD is read once per
-    process: compared through the oracle)."""
+    re-entered; leaves and f16 rows equal the oracle's."""
     rng = np.random.default_rng(31)
     n0, d, depth = 6000, 128, 8
     X = rng.standard_normal((n0, d)).astype(F)

@@ -1,5 +1,5 @@
 """Host-buffer entry points at C2's shape: rows in host memory -> codes / f16 in host memory, and the data-set upload.
-    python tools/host_xfer.py            (VQHIP_NO_XFER_LANES=1, VQHIP_XFER_LANES=n, VQHIP_XFER_CHUNK_MB=m for A/B)"""
+    python tools/host_xfer.py"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -2,8 +2,7 @@
 
 Device forms at 1M x 384 (HIP-event ms per call, median of --reps; effective TB/s = bytes read + bytes written per call:
 5 bytes per element either way), the host form (host array in, host codes out, caller's `out=`), and the per-vector
-call latency at d = 384 (median wall time of `quantize` / `dequantize`).  A/B of the SQ encoder through the environment,
-read once per process: VQHIP_SQ_DIRECT=1 (the division kernel for every step instead of the threshold table).
+call latency at d = 384 (median wall time of `quantize` / `dequantize`).
 
     python tools/sqbq_time.py [--reps 50]
 """
@@ -56,9 +55,9 @@ def main():
     out = torch.empty((n, d), dtype=torch.float32, device="cuda")
     torch.cuda.synchronize()
     sq, bq = vq_amd.ScalarQuantizer(-1.0, 1.0, 256), vq_amd.BinaryQuantizer(0.0)
-    sq_inf = vq_amd.ScalarQuantizer(-3e38, 3e38, 256)  # step = inf: the direct kernel whatever the environment
+    sq_inf = vq_amd.ScalarQuantizer(-3e38, 3e38, 256)  # step = inf: the direct kernel
     nbytes = 5 * count
-    res = {"n": n, "d": d, "env": {k: os.environ[k] for k in ("VQHIP_SQ_DIRECT",) if k in os.environ}}
+    res = {"n": n, "d": d}
     kernels = {
         "sq_encode": lambda: sq.quantize_device(x.data_ptr(), count, codes.data_ptr()),
         "sq_encode_direct_inf_step": lambda: sq_inf.quantize_device(x.data_ptr(), count, codes.data_ptr()),

@@ -300,9 +300,8 @@ static int run_assign(CodebookState &cs, AssignWorkspace &ws, const float *X, ui
         engine = VQHIP_ENGINE_EXACT;
     // small work (C1's encode: 10k rows x 4 subspaces x 16 centroids x 16 dimensions): the exact scan is one launch of a
     // few microseconds, the screen is two (+ its codebook images) -- launch latency is all there is at that size
-    static const char *small_exact_env = getenv("VQHIP_SMALL_EXACT");  // =0: never (A/B)
     if (engine_req == VQHIP_ENGINE_AUTO && engine != VQHIP_ENGINE_EXACT && !(fused && fused->sums) &&
-        (double)n * cs.m * cs.k * cs.sd <= 32.0e6 && !(small_exact_env && small_exact_env[0] == '0'))
+        (double)n * cs.m * cs.k * cs.sd <= 32.0e6)
         engine = VQHIP_ENGINE_EXACT;
     const bool x32_only = engine == VQHIP_ENGINE_MFMA_BF16 && cs.x32_groups == 1 && x32_padded_sd(cs.sd) <= 64 &&
                           (metric == VQHIP_SQUARED_EUCLIDEAN || metric == VQHIP_EUCLIDEAN) && cs.metric != VQHIP_COSINE;
@@ -330,10 +329,9 @@ static int run_assign(CodebookState &cs, AssignWorkspace &ws, const float *X, ui
     }
     // many subspaces: the single-pass bf16 screen writes its codes subspace-major into a scratch and a transposition
     // forms [n][m] (k_screen_bf16.hip): at m = 96 the byte stores m apart were 1.46 GB of write traffic for 96 MB of codes
-    static const char *ct_env = getenv("VQHIP_CODES_TRANSPOSE");  // =0: never, =1: whenever the shape allows (A/B)
     const bool ct_shape = engine == VQHIP_ENGINE_MFMA_BF16 && cs.x32_groups == 1 && x32_padded_sd(cs.sd) <= 64 && cs.k <= 256 &&
                           cs.m % 4 == 0 && (size_t)256 * codes_transpose_pitch(cs.m) + cs.m <= 60 * 1024 && (reinterpret_cast<uintptr_t>(codes) & 3) == 0;
-    if (ct_shape && !(ct_env && ct_env[0] == '0') && (cs.m >= 16 || (ct_env && ct_env[0] == '1'))) {
+    if (ct_shape && cs.m >= 16) {
         const uint64_t pitch = (n + 255) / 256 * 256;
         VQ_TRY(ws.codes_t.ensure((size_t)cs.m * pitch));
         a.codes_t = ws.codes_t.as<uint8_t>();
@@ -625,29 +623,13 @@ struct XferLane {
         return VQHIP_OK;
     }
 };
-constexpr int kXferLanesMax = 8;
-static int xfer_lanes() {  // host threads per large transfer (VQHIP_XFER_LANES, 1..8; A/B)
-    static const int v = [] {
-        const char *e = getenv("VQHIP_XFER_LANES");
-        const int x = e ? atoi(e) : 3;  // (two suffice when they stay out of phase, 9.7 ms at 1M x 128 rows in / f16 out, but now and then a call falls back to 14 ms; three: 10.2-10.5 ms every time)
-        return x < 1 ? 1 : (x > kXferLanesMax ? kXferLanesMax : x);
-    }();
-    return v;
-}
-static size_t xfer_chunk_bytes() {  // bytes of input per chunk (VQHIP_XFER_CHUNK_MB; A/B)
-    static const size_t v = [] {
-        const char *e = getenv("VQHIP_XFER_CHUNK_MB");
-        const int x = e ? atoi(e) : 32;
-        return (size_t)(x < 1 ? 1 : (x > 1024 ? 1024 : x)) << 20;
-    }();
-    return v;
-}
+// host threads per large transfer: two suffice when they stay out of phase (9.7 ms at 1M x 128 rows in / f16 out), but
+// now and then a call fell back to 14 ms; three took 10.2-10.5 ms every time
+constexpr int kXferLanes = 3;
+constexpr size_t kXferChunkBytes = (size_t)32 << 20;  // bytes of input per chunk
 constexpr size_t kXferMinBytes = (size_t)96 << 20;  // smaller batches keep the one-stream path (two host threads to start)
 // lanes pay when the results are at least a quarter of the rows in bytes (f16 reconstructions); codes alone are 1-6 %
-static bool xfer_lanes_pay(size_t in_b, size_t out_b) {
-    static const char *no_lanes = getenv("VQHIP_NO_XFER_LANES");  // =1: one stream, copies and kernels in turn (A/B)
-    return in_b >= kXferMinBytes && 4 * out_b >= in_b && !(no_lanes && no_lanes[0] == '1');
-}
+static bool xfer_lanes_pay(size_t in_b, size_t out_b) { return in_b >= kXferMinBytes && 4 * out_b >= in_b; }
 struct XferPool {  // leaked on purpose, like StagePool
     std::mutex mu;
     std::vector<XferLane *> idle;
@@ -664,8 +646,8 @@ static int run_lanes(Fn fn) {
     int dev = 0;
     VQ_HIP(hipGetDevice(&dev));
     g_xfer_lane_calls.fetch_add(1);
-    const int n_lanes = xfer_lanes();
-    XferLane *lanes[kXferLanesMax] = {};
+    const int n_lanes = kXferLanes;
+    XferLane *lanes[kXferLanes] = {};
     {
         XferPool &p = xfer_pool();
         std::lock_guard<std::mutex> lk(p.mu);
@@ -682,9 +664,9 @@ static int run_lanes(Fn fn) {
             lanes[got]->device = dev;
         }
     }
-    int rcs[kXferLanesMax];
-    std::string errs[kXferLanesMax];
-    std::thread th[kXferLanesMax];
+    int rcs[kXferLanes];
+    std::string errs[kXferLanes];
+    std::thread th[kXferLanes];
     for (int t = 0; t < n_lanes; ++t)
         th[t] = std::thread([&, t] {
             rcs[t] = VQHIP_OK;
@@ -778,8 +760,7 @@ template <class Launch>
 static int host_elementwise(const void *in, size_t in_sz, void *out, size_t out_sz, uint64_t count, Launch launch) {
     const size_t in_b = (size_t)count * in_sz, out_b = (size_t)count * out_sz;
     const size_t out_off = (in_b + 15) & ~(size_t)15;
-    static const char *no_small = getenv("VQHIP_NO_SMALL_PATH");
-    if (out_off + out_b <= kElementwiseSmallBytes && !(no_small && no_small[0] == '1')) {
+    if (out_off + out_b <= kElementwiseSmallBytes) {
         hipStream_t s;
         VQ_TRY(current_stream(&s));
         StageLease stage;
@@ -791,7 +772,7 @@ static int host_elementwise(const void *in, size_t in_sz, void *out, size_t out_
         return VQHIP_OK;
     }
     if (xfer_lanes_pay(in_b, out_b)) {
-        const uint64_t per = std::max<uint64_t>(16, (xfer_chunk_bytes() / in_sz) & ~(uint64_t)15);
+        const uint64_t per = std::max<uint64_t>(16, (kXferChunkBytes / in_sz) & ~(uint64_t)15);
         const uint64_t chunks = (count + per - 1) / per;
         std::mutex h2d_turn;
         return run_lanes([&](int tl, XferLane &ln, int n_lanes) -> int {
@@ -1328,8 +1309,7 @@ int vqhip_kmeans_create(const vqhip_dataset *ds, uint32_t m, uint32_t k, vqhip_k
     VQ_TRY(km->codes.alloc((size_t)ds->n * m * code_bytes(k)));
     if (!km->sums_by_chains) {
         size_t sums_b = km->plan.partial_floats * km->plan.n_row_chunks * 4, cnt_b = km->plan.partial_counts * km->plan.n_row_chunks * 4;
-        static const char *no_fused = getenv("VQHIP_FUSED_UPDATE");  // =0: always the separate accumulate pass (A/B)
-        if (km->cs.x32_ok && screen_bf16_fused_update_supported(sd, k) && !(no_fused && no_fused[0] == '0')) {
+        if (km->cs.x32_ok && screen_bf16_fused_update_supported(sd, k)) {
             // fused update: one slab per (screen wave chunk or patch chunk, active subspace); <= 8 waves per CU
             km->fused_slabs = (uint32_t)num_cus() * 8 + 16 * m;
             sums_b = std::max(sums_b, (size_t)km->fused_slabs * k * sd * 4);
@@ -1758,7 +1738,6 @@ static int kmeans_run_impl(vqhip_kmeans *km, Comm *comm, uint32_t max_iters, uin
     int local_rc = require_gfx950();
     if (local_rc == VQHIP_OK) local_rc = in.stream(&s);
     if (local_rc == VQHIP_OK) local_rc = pick_engine(km->engine, km->cs, VQHIP_SQUARED_EUCLIDEAN, &engine);
-    static const char *host_loop_env = getenv("VQHIP_RUN_ON_HOST");  // =1: decisions on the host (A/B)
     uint32_t n_active = 0;
     for (uint32_t i = 0; i < m; ++i) n_active += km->active[i] ? 1u : 0u;
     // the device-driven loop needs the fused update: exactly run_assign's predicate (engine, one centroid group, a slab
@@ -1767,11 +1746,11 @@ static int kmeans_run_impl(vqhip_kmeans *km, Comm *comm, uint32_t max_iters, uin
     bool device_loop = local_rc == VQHIP_OK && km->fused_slabs && !km->exact_update && !km->sums_by_chains &&
                        engine == VQHIP_ENGINE_MFMA_BF16 && km->cs.x32_groups == 1 && screen_bf16_fused_update_supported(km->cs.sd, k) &&
                        km->fused_slabs / n_active > FusedAcc().n_patch && km->ds->n != 0 && km->ds->n < (1ull << 32) &&
-                       !g_prof.on && !(host_loop_env && host_loop_env[0] == '1');
-    if (local_rc == VQHIP_OK && kmeans_small_eligible(km) && !(host_loop_env && host_loop_env[0] == '1')) device_loop = true;
+                       !g_prof.on;
+    if (local_rc == VQHIP_OK && kmeans_small_eligible(km)) device_loop = true;
     if (world > 1) {
-        // every rank must queue the same number of all-reduces: the decision depends on per-rank state (environment,
-        // profiling hooks, the local row count), so the ranks agree on it -- device loop only if ALL of them can -- and
+        // every rank must queue the same number of all-reduces: the decision depends on per-rank state (profiling
+        // hooks, the local row count), so the ranks agree on it -- device loop only if ALL of them can -- and
         // in the same collective on whether every rank got this far: {ranks that are ready, ranks that can loop on
         // the device}.  `agree` was allocated with the handle, so a rank short of memory still takes part.
         const std::string my_error = local_rc == VQHIP_OK ? std::string() : tls().last_error;
@@ -1791,7 +1770,7 @@ static int kmeans_run_impl(vqhip_kmeans *km, Comm *comm, uint32_t max_iters, uin
     VQ_TRY(local_rc);
     // small problems: one launch per iteration on a single GPU (small_loop); row-sharded, the slab form of the same kernel
     // + all-reduce + k_finalize<true>, still without the host
-    const bool small_ok = local_rc == VQHIP_OK && kmeans_small_eligible(km) && !(host_loop_env && host_loop_env[0] == '1');
+    const bool small_ok = local_rc == VQHIP_OK && kmeans_small_eligible(km);
     const bool small_loop = world == 1 && small_ok;
     if (!device_loop) {
         std::vector<uint32_t> cnt((size_t)m * k);
@@ -1836,9 +1815,8 @@ static int kmeans_run_impl(vqhip_kmeans *km, Comm *comm, uint32_t max_iters, uin
     }
     VQ_TRY(km->run_state.ensure((size_t)(2 * m + 3) * 4));
     VQ_HIP(hipMemsetAsync(km->run_state.p, 0, (size_t)(2 * m + 3) * 4, s));
-    // one rank: nothing is exchanged between the sums and the means, so both are one launch (VQHIP_FUSED_FINALIZE=0: two, for A/B)
-    static const char *ff_env = getenv("VQHIP_FUSED_FINALIZE");
-    const bool fuse_finalize = world == 1 && !small_loop && !(ff_env && ff_env[0] == '0');
+    // one rank: nothing is exchanged between the sums and the means, so both are one launch
+    const bool fuse_finalize = world == 1 && !small_loop;
     if (small_loop) {  // the small form keeps the loop's decisions in two flag sets (k_lloyd_small.hip)
         VQ_TRY(kmeans_small_workspace(km, s));
         VQ_HIP(hipMemsetAsync(km->sm_tick.p, 0, (size_t)6 * m * 4, s));
@@ -2223,8 +2201,7 @@ int vqhip_pq_encode(vqhip_pq_encoder *enc, const float *rows, uint64_t n, uint8_
     hipStream_t s;
     const uint32_t m = enc->cs.m, d = enc->cs.m * enc->cs.sd;
     const size_t cw = code_bytes(enc->cs.k);  // bytes per code: 1 (k <= 256) or 2
-    static const char *no_small = getenv("VQHIP_NO_SMALL_PATH");
-    const bool small = n <= kSmallRows && !(no_small && no_small[0] == '1');
+    const bool small = n <= kSmallRows;
     // (the per-vector path needs no order behind the handle's queued batch work once its images are known to be complete:
     // it shares nothing mutable with it)
     if (small && enc->small_ready) VQ_TRY(current_stream(&s));
@@ -2273,7 +2250,7 @@ int vqhip_pq_encode(vqhip_pq_encoder *enc, const float *rows, uint64_t n, uint8_
         // queued stays its tail) and the handle orders the lanes' launches.
         in.release();
         const size_t row_b = (size_t)d * 4;
-        const uint64_t per = std::max<uint64_t>(1, xfer_chunk_bytes() / row_b), chunks = (n + per - 1) / per;
+        const uint64_t per = std::max<uint64_t>(1, kXferChunkBytes / row_b), chunks = (n + per - 1) / per;
         std::mutex h2d_turn;  // one lane's rows on the bus at a time: the lanes stay out of phase (both copying in, then both out, overlaps nothing: 13.3 against 10.6 ms)
         const int rc_lanes = run_lanes([&](int t, XferLane &ln, int n_lanes) -> int {
             VQ_TRY(ln.dev_in.ensure((size_t)per * row_b));
@@ -3025,8 +3002,7 @@ int vqhip_tsvq_encode(vqhip_tsvq *t, const float *rows, uint64_t n, int32_t *lea
     Entry in(t->sync);
     hipStream_t s;
     const uint32_t d = t->d;
-    static const char *no_small = getenv("VQHIP_NO_SMALL_PATH");
-    const bool small = n <= kSmallRows && tsvq_small_supported(d) && !(no_small && no_small[0] == '1');
+    const bool small = n <= kSmallRows && tsvq_small_supported(d);
     if (small) VQ_TRY(current_stream(&s));  // nothing mutable shared with the handle's queued batch work: no order needed
     else VQ_TRY(in.stream(&s));
     if (small) {
@@ -3051,7 +3027,7 @@ int vqhip_tsvq_encode(vqhip_tsvq *t, const float *rows, uint64_t n, int32_t *lea
     if (xfer_lanes_pay((size_t)n * d * 4, (leaf ? (size_t)n * 4 : 0) + (f16_out ? (size_t)n * d * 2 : 0))) {  // two lanes, as vqhip_pq_encode
         in.release();
         const size_t row_b = (size_t)d * 4;
-        const uint64_t per = std::max<uint64_t>(1, xfer_chunk_bytes() / row_b), chunks = (n + per - 1) / per;
+        const uint64_t per = std::max<uint64_t>(1, kXferChunkBytes / row_b), chunks = (n + per - 1) / per;
         std::mutex h2d_turn;
         return run_lanes([&](int tl, XferLane &ln, int n_lanes) -> int {
             VQ_TRY(ln.dev_in.ensure((size_t)per * row_b));

@@ -353,8 +353,7 @@ int comm_create_local(LocalGroup *g, int rank, Comm **out) {
     c->world = g->world;
     c->rank = rank;
     c->local = g;
-    static const char *skip = getenv("VQHIP_COMM_SELFTEST");  // =0: skip (A/B of the constructor's cost)
-    if (g->world > 1 && !(skip && skip[0] == '0')) {
+    if (g->world > 1) {
         hipStream_t st = nullptr;
         rc = current_stream(&st);
         if (rc != VQHIP_OK) g->fail_all(rank, tls().last_error.c_str());
@@ -511,15 +510,12 @@ int comm_create(const uint8_t *id128, int world, int rank, Comm **out) {
             return fail(VQHIP_ERR_RUNTIME, "communicator reports rank %d of %d, asked for rank %d of %d (%s)", rk, w, rank, world,
                         r == ncclSuccess ? "mismatch" : api->GetErrorString(r));
         }
-        static const char *skip = getenv("VQHIP_COMM_SELFTEST");
-        if (!(skip && skip[0] == '0')) {
-            const int rc2 = rccl_selftest(c);
-            if (rc2 != VQHIP_OK) {
-                const std::string keep = tls().last_error;
-                (void)api->CommDestroy(c->comm);
-                delete c;
-                return fail(rc2, "%s", keep.c_str());
-            }
+        const int rc2 = rccl_selftest(c);
+        if (rc2 != VQHIP_OK) {
+            const std::string keep = tls().last_error;
+            (void)api->CommDestroy(c->comm);
+            delete c;
+            return fail(rc2, "%s", keep.c_str());
         }
     }
     *out = c;

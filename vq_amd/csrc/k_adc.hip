@@ -627,16 +627,12 @@ int launch_adc_search_fast(const float *cb, uint32_t m, uint32_t k, uint32_t sd,
     order = (uint32_t)std::min<double>(std::max<double>(std::floor(want * (1024.0 * G * rpt) / (double)n + 0.5), 1.0), 8.0);
     static const char *force_env = getenv("VQHIP_TEST_ADC_REDO");  // tests: every query flagged, the caller's repeat path runs
     const int force_redo = (force_env && force_env[0] == '1') ? 1 : 0;
-    static const char *lq_env = getenv("VQHIP_ADC_LQ1");  // =1: a row per lane at eight queries per batch (A/B)
-    const bool lq1 = lq_env && lq_env[0] == '1';
     // (workgroups of 1024, one per CU, half the table loads: 113 us against 105 per 64-query call -- not kept)
 #define VQ_ADC_FAST(QB, LQ, NT)                                                                                                     \
     return adc_fast_launch<QB, LQ, NT>(cb, m, k, sd, l1, take_sqrt, codes, n, queries_dev, nq, topk, lut_ws, state_ws, cand_ws,     \
                                        idx_out_dev, dist_out_dev, redo_dev, stream, G, rpt, order, force_redo);
     switch (adc_fast_batch(m, k, nq)) {
-        case 8:
-            if (lq1) VQ_ADC_FAST(8, 1, 512)
-            VQ_ADC_FAST(8, 2, 512)
+        case 8: VQ_ADC_FAST(8, 2, 512)
         case 4: VQ_ADC_FAST(4, 1, 512)
         case 2: VQ_ADC_FAST(2, 1, 512)
         case 1: VQ_ADC_FAST(1, 1, 512)

@@ -222,9 +222,7 @@ int launch_gather_f16(const CodebookView &cb, const uint8_t *codes, uint64_t n, 
     const bool vec8 = (cb.sd % 8 == 0) && ((reinterpret_cast<uintptr_t>(f16_out) & 15) == 0) &&
                       ((reinterpret_cast<uintptr_t>(cb.cb) & 15) == 0);
     const size_t cb_bytes = (size_t)cb.m * cb.k * cb.sd * 4;
-    static const char *lds_env = getenv("VQHIP_DECODE_LDS");  // =0: the gather from L2 (A/B)
-    if (vec8 && cb_bytes <= 144 * 1024 && n * (uint64_t)(cb.m * cb.sd / 8) >= (1u << 19) && (uint64_t)cb.m * cb.sd / 8 + 8192 < (1ull << 31) &&
-        !(lds_env && lds_env[0] == '0')) {
+    if (vec8 && cb_bytes <= 144 * 1024 && n * (uint64_t)(cb.m * cb.sd / 8) >= (1u << 19) && (uint64_t)cb.m * cb.sd / 8 + 8192 < (1ull << 31)) {
         constexpr int U = 2;
         static PerDeviceOnce attr;
         if (attr.needed()) {
@@ -253,8 +251,7 @@ int launch_decode_f32(const CodebookView &cb, const uint8_t *codes, uint64_t n, 
     const bool vec4 = (cb.sd % 4 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0) && ((reinterpret_cast<uintptr_t>(cb.cb) & 15) == 0) &&
                       (uint64_t)cb.m * cb.sd / 4 + 256 < (1ull << 31);
     const size_t cb_bytes = (size_t)cb.m * cb.k * cb.sd * 4;
-    static const char *lds_env = getenv("VQHIP_DECODE_LDS");  // =0: the gather from L2 (A/B)
-    if (vec4 && cb_bytes <= 144 * 1024 && n * (uint64_t)(cb.m * cb.sd / 4) >= (1u << 20) && !(lds_env && lds_env[0] == '0')) {
+    if (vec4 && cb_bytes <= 144 * 1024 && n * (uint64_t)(cb.m * cb.sd / 4) >= (1u << 20)) {
         constexpr int U = 4;
         static PerDeviceOnce attr;
         if (attr.needed()) {

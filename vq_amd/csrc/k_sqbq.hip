@@ -221,8 +221,7 @@ int sq_encode_op(float mn, float mx, uint32_t levels, SqbqEncodeOp *p) {
     *p = SqbqEncodeOp{};
     p->mn = mn, p->mx = mx, p->step = step, p->top = levels - 1;
     p->inv = 1.0f / step;
-    static const char *direct = getenv("VQHIP_SQ_DIRECT");  // =1: the division kernel for every step (A/B)
-    const bool table = std::isfinite(step) && step > 0.0f && std::isfinite(p->inv) && !(direct && direct[0] == '1');
+    const bool table = std::isfinite(step) && step > 0.0f && std::isfinite(p->inv);
     p->mode = table ? SQBQ_TABLE : SQBQ_DIRECT;
     if (table) {
         sq_thresholds(mn, mx, levels, step, p->b);

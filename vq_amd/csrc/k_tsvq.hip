@@ -26,7 +26,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstddef>
 #include <type_traits>
 #include <utility>
@@ -1092,7 +1091,7 @@ __device__ __forceinline__ float fs_value(float x, float mu) {
 // plain f64 sums per (tile, column): only used to guess the binade of the running sum at a tile.
 // samp > 1: only every samp-th group of 32 rows is read and the sum scaled up -- 1/samp of the traffic for a guess whose
 // relative error (~ sigma/mu / sqrt(rows read so far)) only moves the tiles next to a binade crossing into the
-// re-addition path of k_fs_chain; the sums themselves stay exact whatever the guess.
+// re-addition path of the chain kernels; the sums themselves stay exact whatever the guess.
 // Is a guess from every r-th row good enough?  Its error is ~ sigma sqrt(r N) against a sum of ~ |mean| N: fine for
 // columns with |mean| >= sigma (non-negative features), useless for zero-mean columns, whose running sum is a random
 // walk no larger than that error (measured on N(0,1) data: 1.14 M re-added tiles and 31 ms per build with sampling,
@@ -1255,7 +1254,7 @@ __global__ __launch_bounds__(1024) void k_fs_prefix(uint32_t d, const uint32_t *
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-// LDS exchange inside ONE wave (k_fs_fold and k_fs_chain run one-wave workgroups): the LDS serves a wave's instructions
+// LDS exchange inside ONE wave (k_fs_fold and k_fs_chain3 run one-wave workgroups; k_fs_chain4 is a loader and a walker wave): the LDS serves a wave's instructions
 // in order, so all that is needed is that the compiler keeps the order and waits for the LDS counter.  __syncthreads()
 // would also wait for every global load in flight (s_waitcnt vmcnt(0)) -- the rows of the next block, the next batches
 // of summaries, the parked addends: exactly the loads these kernels issue early to hide their latency.
@@ -1649,17 +1648,14 @@ __global__ __launch_bounds__(64, 2) void k_fs_fold(const float *__restrict__ X, 
     }
 }
 
-// the exact chain: one wave per (node, column).  The segment summaries are themselves parity transducers: every lane
+// the exact chain (k_fs_chain4): one walk per (node, column).  The segment summaries are themselves parity transducers: every lane
 // composes kFsSpl consecutive ones (they must share a binade), a wave scan composes the lanes, lane l learns the exact
 // S entering its first segment (as if everything before it in the batch held) and checks its run (same binade as the
 // guesses, every prefix strictly inside it).  The first lane that fails marks where the scan stops: the lanes before
 // it are applied in one step, that lane's segments are walked one by one -- applied, or their 64 rows re-added in the
 // reference's order -- and the scan resumes behind it over the SAME registers (lanes already consumed scan as the
-// identity): no summary is loaded twice.  The next batch of 256 summaries is requested before the current one is
-// scanned, and so are the addends of the first kFsAhead segments the fold kernel predicted to fail (it parked them
-// contiguously): a re-addition costs its 64 additions, not a memory round trip.
+// identity): no summary is loaded twice.
 constexpr int kFsSpl = 8;     // segments per lane and batch
-constexpr int kFsAhead = 8;   // parked segments whose addends travel together (two such groups: one complete, one in flight)
 
 // The chain's scans only place the runs: what they need of a composition is where it leaves S (d0 / d1 by the parity
 // of the S entering) -- whether a run holds is tested against its OWN prefix bounds.  Two fields instead of six: 2 DPP
@@ -1705,453 +1701,11 @@ __device__ __forceinline__ bool fs_inside(int32_t S, int32_t lo, int32_t hi) {
     return (S > 0) ? (S + lo > (1 << 23) && S + hi <= (1 << 24) - 1) : (S + hi < -(1 << 23) && S + lo >= -((1 << 24) - 1));
 }
 
-// DBG (VQHIP_TSVQ_DEBUG): the instantiation with the counters; the production one carries none of it
-template <int MODE, bool DBG>
-__global__ __launch_bounds__(64) void k_fs_chain(const float *__restrict__ X, uint32_t d,
-                                                 const uint32_t *__restrict__ perm,
-                                                 const uint32_t *__restrict__ fast_nodes,
-                                                 const uint32_t *__restrict__ tile_base, NodeArrays na,
-                                                 const FsS *__restrict__ summ, const FsS *__restrict__ summ_odd,
-                                                 const float *__restrict__ side, uint32_t *__restrict__ n_fallback,
-                                                 const LevelInfo *__restrict__ lv, uint32_t *__restrict__ dbg_arg,
-                                                 const uint32_t *__restrict__ only_sampled) {
-    uint32_t *const dbg = DBG ? dbg_arg : nullptr;  // folds every `if (dbg)` below away when !DBG
-    // (round 5: the mean pass's columns with an exact guess -- zero-mean columns -- go through k_fs_prep / k_fs_chain3)
-    if (only_sampled && only_sampled[blockIdx.y / kFsCols] == 0u) return;
-    // dbg: 8 counters of this (level, pass): chains, re-added segments, most in one chain, and the first reason the
-    // re-added segment failed: unusable summary / other binade than guessed / prefix leaves the binade / sum not normal
-    __shared__ int plist[64 * kFsSpl];                            // side slots of the batch's parked segments, in order
-    __shared__ __attribute__((aligned(16))) FsS lsum[64 * kFsSpl];  // the batch's summaries [lane][j], staged at its first failing lane
-    __shared__ __attribute__((aligned(16))) FsS lsum2[64 * kFsSpl];  // ... and their odd streams (batches with an exact tie)
-    __shared__ __attribute__((aligned(16))) float ladd[64];         // the addends of a gathered (not parked) segment being re-added
-    __shared__ __attribute__((aligned(16))) float lpark[kFsAhead * 64];  // group A: the addends of kFsAhead parked segments
-    if (blockIdx.x >= lv->n_fast) return;
-    const uint32_t node = fast_nodes[blockIdx.x], c = blockIdx.y, lane = threadIdx.x;
-    const uint32_t a = na.seg_start[node], len = na.seg_len[node];
-    const uint32_t nseg = (len + kFsSeg - 1) / kFsSeg;
-    const size_t seg0 = (size_t)tile_base[blockIdx.x] * kFsSegsPerTile;
-    const FsS *sp = summ + (size_t)c * na.fs_seg_stride + seg0, *sp2 = summ_odd + (size_t)c * na.fs_seg_stride + seg0;
-    const float mu = (MODE == 1) ? na.centroid[(size_t)node * d + c] : 0.0f;
-    float s = (MODE == 0) ? 0.0f : -0.0f;
-    uint32_t fallbacks = 0;
-    // dbg: core cycles (s_memtime) of the whole chain, inside the failing lanes' walks, inside the re-additions, in the
-    // wave-wide scan passes of two-stream batches (one stream: the fetch of the staged summaries); failing lanes
-    unsigned long long cyc_all = dbg ? clock64() : 0ull, cyc_walk = 0ull, cyc_readd = 0ull, cyc_lds = 0ull;
-    uint32_t n_walks = 0;
-    unsigned long long cy_fetch = 0ull, cy_scan = 0ull, cy_apply = 0ull, cy_pre = 0ull, cy_add = 0ull;  // dbg, chain (0, 0): parts of a failing lane's walk
-    uint32_t n_iter = 0;
-    // UNCONDITIONAL loads (index clamped): a load under `if (t < nseg)` is followed by the merge with the other branch's
-    // value, i.e. by s_waitcnt vmcnt(0) right behind the load -- every batch then cost four serial memory round trips
-    // (~3 us).  What lies past the node's end is marked unusable when the registers are consumed.
-    auto load4 = [&](uint32_t tstart, FsS (&m)[kFsSpl]) {
-#pragma unroll
-        for (int j = 0; j < kFsSpl; ++j) m[j] = sp[min(tstart + kFsSpl * lane + (uint32_t)j, nseg - 1u)];
-    };
-    // summaries of the next batches in flight behind the one being scanned (a batch's scan is shorter than a memory round
-    // trip): a set is consumed two iterations after its loads were issued
-    constexpr uint32_t kBatch = 64 * kFsSpl;
-    FsS cur[kFsSpl], nx1[kFsSpl], nx2[kFsSpl];
-    load4(0, cur);
-    load4(kBatch, nx1);
-    load4(2 * kBatch, nx2);
-    for (uint32_t t0 = 0; t0 < nseg; t0 += kBatch) {
-        const uint32_t cnt = min(kBatch, nseg - t0), nl = (cnt + kFsSpl - 1) / kFsSpl;  // segments / lanes of this batch
-        FsS m[kFsSpl];
-#pragma unroll
-        for (int j = 0; j < kFsSpl; ++j) {
-            m[j] = cur[j], cur[j] = nx1[j], nx1[j] = nx2[j];
-            if (t0 + kFsSpl * lane + (uint32_t)j >= nseg) m[j].d = m[j].lo = m[j].hi = 0, m[j].ef = 1;  // past the node's end: unusable
-        }
-        load4(t0 + 3 * kBatch, nx2);  // (into the set the shift has just freed: no register move waits for this load)
-        // the odd streams (runs with an exact tie: rare), else a copy of the even ones
-        FsS m2[kFsSpl];
-        bool two_l = false;
-#pragma unroll
-        for (int j = 0; j < kFsSpl; ++j) {
-            m2[j] = m[j];
-            two_l = two_l || ((m[j].ef & 3) == 2);
-        }
-        const bool two = __ballot(two_l) != 0ull;
-        if (two) {
-#pragma unroll
-            for (int j = 0; j < kFsSpl; ++j)
-                if ((m[j].ef & 3) == 2) {
-                    const FsS o = sp2[t0 + kFsSpl * lane + (uint32_t)j];
-                    m2[j].d = o.d, m2[j].lo = o.lo, m2[j].hi = o.hi;
-                }
-        }
-        // ---- parked segments of the batch, in segment order: slots into LDS, the first kFsAhead requested ----
-        uint32_t pk = 0;  // this lane's parked segments, bit j
-#pragma unroll
-        for (int j = 0; j < kFsSpl; ++j) pk |= (fs_ef_slot(m[j].ef) >= 0) ? (1u << j) : 0u;
-        const uint32_t pc = (uint32_t)__builtin_popcount(pk);
-        uint32_t pincl = pc;  // inclusive prefix of pc over the lanes
-        {
-#define VQ_FS_ADD(CTRL, COND) { const int32_t t = __builtin_amdgcn_update_dpp(0, (int32_t)pincl, CTRL, 0xF, 0xF, true); if (COND) pincl += (uint32_t)t; }
-            VQ_FS_ADD(0x111, (lane & 15u) >= 1u)
-            VQ_FS_ADD(0x112, (lane & 15u) >= 2u)
-            VQ_FS_ADD(0x114, (lane & 15u) >= 4u)
-            VQ_FS_ADD(0x118, (lane & 15u) >= 8u)
-            VQ_FS_ADD(0x142, (lane & 16u) != 0u)
-            VQ_FS_ADD(0x143, lane >= 32u)
-#undef VQ_FS_ADD
-        }
-        const uint32_t pbefore = pincl - pc, ptotal = (uint32_t)__builtin_amdgcn_readlane((int)pincl, 63);
-        if (dbg && lane == 0) atomicAdd(dbg + 14, ptotal);
-        if (ptotal) {  // uniform
-            fs_wave_lds_sync();  // the previous batch's reads of plist are done
-            uint32_t r = pbefore;
-#pragma unroll
-            for (int j = 0; j < kFsSpl; ++j)
-                if (pk & (1u << j)) plist[r++] = fs_ef_slot(m[j].ef);
-            fs_wave_lds_sync();
-        }
-        // addends of the parked segments, kFsAhead at a time: group A is complete (plain registers: reading it waits for
-        // nothing), group B in flight behind it; when the walk passes A's last rank B becomes A and the next group is
-        // requested.  The batch starts with its first group in B.
-        float pb[kFsAhead];
-        int32_t pa_base = -kFsAhead;  // rank of group A's first segment (lpark[0 .. 63])
-        auto request_b = [&](uint32_t base) {
-#pragma unroll
-            for (int k = 0; k < kFsAhead; ++k) {
-                pb[k] = 0.0f;
-                if (base + (uint32_t)k < ptotal) pb[k] = side[(size_t)plist[base + (uint32_t)k] * kFsSeg + lane];
-            }
-        };
-        request_b(0);
-        // ---- this lane's run: its segments composed, usable iff all are and share a binade ----
-        FsT mine;
-        mine.d0 = m[0].d, mine.lo0 = m[0].lo, mine.hi0 = m[0].hi, mine.d1 = m2[0].d, mine.lo1 = m2[0].lo, mine.hi1 = m2[0].hi;
-        int lane_bad = m[0].ef & 1;
-        const int lane_e = fs_ef_e(m[0].ef);
-#pragma unroll
-        for (int j = 1; j < kFsSpl; ++j) {
-            FsT gj;
-            gj.d0 = m[j].d, gj.lo0 = m[j].lo, gj.hi0 = m[j].hi, gj.d1 = m2[j].d, gj.lo1 = m2[j].lo, gj.hi1 = m2[j].hi;
-            lane_bad |= (m[j].ef & 1) | (fs_ef_e(m[j].ef) != lane_e ? 1 : 0);
-            if (two) {
-                mine = fs_compose(mine, gj);
-            } else {
-                mine.lo0 = min(mine.lo0, mine.d0 + gj.lo0);
-                mine.hi0 = max(mine.hi0, mine.d0 + gj.hi0);
-                mine.d0 = mine.d0 + gj.d0;
-                mine.d1 = mine.d0, mine.lo1 = mine.lo0, mine.hi1 = mine.hi0;
-            }
-        }
-        // the 64 rows of segment `seg` re-added in the reference's order (uniform: every lane carries the same s)
-        // The 64 additions in row order, the addends in LDS: sixteen BROADCAST reads (every lane reads the same 16 bytes:
-        // four addends per ds_read_b128, no bank conflicts), all in flight ahead of the additions that use them -- the
-        // chain is 64 dependent v_add_f32 on VGPR operands at the add's own ~4 cycles.  (Round 3 handed the addends from
-        // lane to SGPR with 64 v_readlane, sixteen ahead: 32 SGPRs of a kernel that spills 45 already, and ~1300 cycles
-        // per segment measured in place -- 20 per addition.)
-        auto add64 = [&](const float *lds64) {
-            const f32x4_t *l4 = reinterpret_cast<const f32x4_t *>(lds64);
-            f32x4_t rq[16];
-#pragma unroll
-            for (int g = 0; g < 16; ++g) rq[g] = l4[g];
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                s = s + rq[g][0];
-                s = s + rq[g][1];
-                s = s + rq[g][2];
-                s = s + rq[g][3];
-            }
-        };
-        // the 64 rows of segment `seg` re-added in the reference's order (uniform: every lane carries the same s).  Parked
-        // segments: the group of kFsAhead that has arrived sits in LDS (written when it became group A: the fold parked
-        // +0.0 for rows past the node's end), the re-addition reads its 256 bytes from there; the two sources of addends
-        // do NOT join before the additions (joined, the gathered path's wait for its load -- vmcnt(0): everything in
-        // flight, the group just requested included, a full memory round trip at every eighth parked segment -- was paid
-        // by the parked path too; picking one of eight registers by a run-time rank went through scratch memory).
-        auto readd = [&](uint32_t seg, int32_t gef, int32_t rank) {
-            ++fallbacks;
-            const unsigned long long c_in = dbg ? clock64() : 0ull;
-            const int slot = fs_ef_slot(gef);
-            if (slot >= 0) {  // parked by k_fs_fold: contiguous, requested a group ahead
-                while (rank >= pa_base + kFsAhead) {  // uniform: group B has arrived and becomes A, the next one is requested
-                    fs_wave_lds_sync();  // the reads of the old group A are done
-#pragma unroll
-                    for (int k = 0; k < kFsAhead; ++k) lpark[k * 64 + (int)lane] = pb[k];
-                    pa_base += kFsAhead;
-                    request_b((uint32_t)(pa_base + kFsAhead));
-                    fs_wave_lds_sync();
-                }
-                const unsigned long long q3 = dbg ? clock64() : 0ull;
-                if (dbg) cy_pre += q3 - c_in;
-                add64(lpark + (rank - pa_base) * 64);
-                if (dbg) {
-                    asm volatile("" ::"v"(s));
-                    cy_add += clock64() - q3;
-                }
-            } else {
-                const uint32_t r0 = seg * kFsSeg, rows_here = min(kFsSeg, len - r0);
-                const float vv = (lane < rows_here) ? fs_value<MODE>(X[(size_t)perm[a + r0 + lane] * d + c], mu) : 0.0f;  // (+0.0 past the end)
-                if (dbg && lane == 0) atomicAdd(dbg + 7, 1u);
-                fs_wave_lds_sync();
-                ladd[lane] = vv;
-                fs_wave_lds_sync();
-                add64(ladd);
-            }
-            if (dbg) {
-                asm volatile("" ::"v"(s));
-                cyc_readd += clock64() - c_in;
-            }
-        };
-        // One stream: the failing lane's eight segments are SCANNED, not walked.  Walking them one by one (four
-        // v_readlane and ~25 dependent scalar-ish instructions per segment, whether it holds or not) was ~1100 of the
-        // ~2000 cycles a failing lane costs -- and on zero-mean columns 10-28 % of the segments fail, one wave per column
-        // paying for each in series.  The batch's summaries go to LDS once (at its first failing lane), lanes 0..7 fetch
-        // the failing lane's eight (one ds_read_b128), a three-step prefix gives every segment its incoming S, one ballot
-        // finds the first that does not hold: the segments in front of it are applied in one step, it is re-added, the
-        // ballot is repeated behind it.
-        bool staged = false;
-        auto walk_lane = [&](uint32_t good) {
-            const unsigned long long w_in = dbg ? clock64() : 0ull;
-            ++n_walks;
-            if (!staged) {  // uniform
-                fs_wave_lds_sync();  // the previous batch's reads of lsum are done
-#pragma unroll
-                for (int j = 0; j < kFsSpl; ++j) lsum[lane * kFsSpl + (uint32_t)j] = m[j];
-                fs_wave_lds_sync();
-                staged = true;
-            }
-            const uint32_t pb_g = (uint32_t)__builtin_amdgcn_readlane((int)pbefore, (int)good),
-                           pk_g = (uint32_t)__builtin_amdgcn_readlane((int)pk, (int)good);
-            const uint32_t jl = lane & 7u;
-            FsS g = lsum[good * kFsSpl + jl];  // every group of eight lanes holds a copy; lanes 0..7 decide
-            if (dbg) {
-                asm volatile("" : "+v"(g.d), "+v"(g.lo), "+v"(g.hi), "+v"(g.ef));
-                cyc_lds += clock64() - w_in;
-            }
-            const uint32_t seg_first = t0 + kFsSpl * good;
-            const uint32_t nvalid = min((uint32_t)kFsSpl, nseg - seg_first);  // this lane's segments inside the node (>= 1)
-            int32_t incl8 = g.d;
-#define VQ_FS_ADD8(CTRL, K) { const int32_t t = __builtin_amdgcn_update_dpp(0, incl8, CTRL, 0xF, 0xF, true); if (jl >= K) incl8 += t; }
-            VQ_FS_ADD8(0x111, 1u)
-            VQ_FS_ADD8(0x112, 2u)
-            VQ_FS_ADD8(0x114, 4u)
-#undef VQ_FS_ADD8
-            const int32_t before8 = incl8 - g.d;
-            const bool usable = !(g.ef & 1);
-            const int g_e = fs_ef_e(g.ef);
-            const uint32_t beyond = ~0u << nvalid;  // (nvalid <= 8)
-            uint32_t start2 = 0;
-            int32_t base2 = 0;
-            for (;;) {
-                const uint32_t sb1 = __float_as_uint(s), se1 = (sb1 >> 23) & 0xFFu;
-                const int32_t mag1 = (int32_t)((sb1 & 0x7FFFFFu) | 0x800000u);
-                const int32_t S1 = (sb1 >> 31) ? -mag1 : mag1;
-                const bool ok = (se1 != 0u) && (se1 != 255u) && usable && ((int)se1 - 127 == g_e) && fs_inside(S1 + before8 - base2, g.lo, g.hi);
-                const uint32_t bad8 = (uint32_t)__ballot(!ok) & 0xFFu;
-                const uint32_t js = (uint32_t)__builtin_ctz((bad8 | beyond) & (~0u << start2));  // first that does not hold, or nvalid
-                if (js > start2) {
-                    const int32_t S2 = S1 + __builtin_amdgcn_readlane(incl8, (int)js - 1) - base2;
-                    const uint32_t m2a = (uint32_t)(S2 < 0 ? -S2 : S2);
-                    s = __uint_as_float((S2 < 0 ? 0x80000000u : 0u) | (se1 << 23) | (m2a & 0x7FFFFFu));
-                }
-                if (js >= nvalid) break;
-                const int32_t gef = __builtin_amdgcn_readlane(g.ef, (int)js);
-                if (dbg && lane == 0) {
-                    const uint32_t sb2 = __float_as_uint(s), se2 = (sb2 >> 23) & 0xFFu;  // the S the failing segment meets
-                    const int why = (se2 == 0u || se2 == 255u) ? 6 : (gef & 1) ? 3 : ((int)se2 - 127 != fs_ef_e(gef)) ? 4 : 5;
-                    atomicAdd(dbg + why, 1u);
-                }
-                readd(seg_first + js, gef, (int32_t)(pb_g + (uint32_t)__builtin_popcount(pk_g & ((1u << js) - 1u))));
-                base2 = __builtin_amdgcn_readlane(incl8, (int)js);
-                start2 = js + 1;
-                if (start2 >= nvalid) break;
-            }
-            if (dbg) {
-                asm volatile("" ::"v"(s));
-                cyc_walk += clock64() - w_in;
-            }
-        };
-        // Two streams (an exact tie somewhere in the batch -- every batch of zero-mean data, whose sums stay small against
-        // their addends): the same, with the segments' parity transducers composed over the eight lanes; the scan is
-        // repeated behind every segment that does not hold, the segments already consumed scanning as the identity --
-        // the wave's own loop at the scale of one lane.  (Round 3 walked the eight segments one by one through
-        // v_readlane and SGPRs: 580 cycles per segment visited, holding or not, 4600 of the 9500 a failing lane cost.)
-        auto walk_lane2 = [&](uint32_t good) {
-            if (!staged) {  // uniform
-                fs_wave_lds_sync();
-#pragma unroll
-                for (int j = 0; j < kFsSpl; ++j) lsum[lane * kFsSpl + (uint32_t)j] = m[j], lsum2[lane * kFsSpl + (uint32_t)j] = m2[j];
-                fs_wave_lds_sync();
-                staged = true;
-            }
-            const uint32_t pb_g = (uint32_t)__builtin_amdgcn_readlane((int)pbefore, (int)good),
-                           pk_g = (uint32_t)__builtin_amdgcn_readlane((int)pk, (int)good);
-            const uint32_t jl = lane & 7u;
-            const unsigned long long q0 = dbg ? clock64() : 0ull;
-            FsS g = lsum[good * kFsSpl + jl], g2 = lsum2[good * kFsSpl + jl];
-            if (dbg) {
-                asm volatile("" : "+v"(g.d), "+v"(g2.d));
-                cy_fetch += clock64() - q0;
-            }
-            const uint32_t seg_first = t0 + kFsSpl * good;
-            const uint32_t nvalid = min((uint32_t)kFsSpl, nseg - seg_first);
-            const bool usable = !(g.ef & 1);
-            const int g_e = fs_ef_e(g.ef);
-            const uint32_t beyond = ~0u << nvalid;
-            uint32_t start2 = 0;
-            for (;;) {
-                const unsigned long long q1 = dbg ? clock64() : 0ull;
-                ++n_iter;
-                const uint32_t sb1 = __float_as_uint(s), se1 = (sb1 >> 23) & 0xFFu;
-                const int32_t mag1 = (int32_t)((sb1 & 0x7FFFFFu) | 0x800000u);
-                const int32_t S1 = (sb1 >> 31) ? -mag1 : mag1;
-                const bool in = jl >= start2;
-                FsD v;
-                v.d0 = in ? g.d : 0, v.d1 = in ? g2.d : 0;
-                fs_scan_incl8_d(v, jl);
-                const int32_t incl_d = (S1 & 1) ? v.d1 : v.d0;  // delta from segment start2 through this one, for the actual parity of S
-                int32_t before8 = __builtin_amdgcn_update_dpp(0, incl_d, 0x111, 0xF, 0xF, true);  // row_shr:1
-                if (jl == 0u) before8 = 0;
-                const int32_t Sin = S1 + before8;
-                const bool podd = (Sin & 1) != 0;
-                const bool ok = (se1 != 0u) && (se1 != 255u) && usable && ((int)se1 - 127 == g_e) &&
-                                fs_inside(Sin, podd ? g2.lo : g.lo, podd ? g2.hi : g.hi);
-                const uint32_t bad8 = (uint32_t)__ballot(!ok) & 0xFFu;
-                uint32_t js = (uint32_t)__builtin_ctz((bad8 | beyond) & (~0u << start2));
-                const unsigned long long q2 = dbg ? clock64() : 0ull;
-                if (dbg) {
-                    asm volatile("" : "+s"(js));
-                    cy_scan += q2 - q1;
-                }
-                if (js > start2) {
-                    const int32_t S2 = S1 + __builtin_amdgcn_readlane(incl_d, (int)js - 1);
-                    const uint32_t m2a = (uint32_t)(S2 < 0 ? -S2 : S2);
-                    s = __uint_as_float((S2 < 0 ? 0x80000000u : 0u) | (se1 << 23) | (m2a & 0x7FFFFFu));
-                }
-                if (dbg) {
-                    asm volatile("" ::"v"(s));
-                    cy_apply += clock64() - q2;
-                }
-                if (js >= nvalid) break;
-                const int32_t gef = __builtin_amdgcn_readlane(g.ef, (int)js);
-                if (dbg && lane == 0) {
-                    const uint32_t sb2 = __float_as_uint(s), se2 = (sb2 >> 23) & 0xFFu;
-                    const int why = (se2 == 0u || se2 == 255u) ? 6 : (gef & 1) ? 3 : ((int)se2 - 127 != fs_ef_e(gef)) ? 4 : 5;
-                    atomicAdd(dbg + why, 1u);
-                }
-                readd(seg_first + js, gef, (int32_t)(pb_g + (uint32_t)__builtin_popcount(pk_g & ((1u << js) - 1u))));
-                start2 = js + 1;
-                if (start2 >= nvalid) break;
-            }
-        };
-        const uint64_t past = nl < 64 ? (~0ull << nl) : 0ull;  // lanes behind the batch's last
-        if (!two) {
-            // One stream (no exact tie anywhere in the batch: every batch of continuous data): the deltas simply add, so ONE
-            // scan serves the whole batch -- behind a lane that did not hold, the S entering lane l is the S the walk
-            // arrived at plus the deltas of the lanes in between.
-            int32_t incl = mine.d0;
-#define VQ_FS_ADD(CTRL, COND) { const int32_t t = __builtin_amdgcn_update_dpp(0, incl, CTRL, 0xF, 0xF, true); if (COND) incl += t; }
-            VQ_FS_ADD(0x111, (lane & 15u) >= 1u)
-            VQ_FS_ADD(0x112, (lane & 15u) >= 2u)
-            VQ_FS_ADD(0x114, (lane & 15u) >= 4u)
-            VQ_FS_ADD(0x118, (lane & 15u) >= 8u)
-            VQ_FS_ADD(0x142, (lane & 16u) != 0u)
-            VQ_FS_ADD(0x143, lane >= 32u)
-#undef VQ_FS_ADD
-            int32_t before = __shfl_up(incl, 1);
-            if (lane == 0) before = 0;
-            const bool lane_ok = (lane < nl) && !lane_bad;
-            uint32_t start = 0;   // first lane of the batch not yet applied
-            int32_t base_d = 0;   // inclusive delta of lane start - 1
-            for (;;) {
-                const uint32_t sb = __float_as_uint(s), se = (sb >> 23) & 0xFFu;
-                const bool s_normal = (se != 0u) && (se != 255u);
-                const int32_t mag = (int32_t)((sb & 0x7FFFFFu) | 0x800000u);
-                const int32_t S = (sb >> 31) ? -mag : mag;
-                const bool ok = s_normal && lane_ok && ((int)se - 127 == lane_e) && fs_inside(S + before - base_d, mine.lo0, mine.hi0);
-                const uint64_t below = start ? ((~0ull) >> (64 - start)) : 0ull;
-                const uint64_t bad_mask = (__ballot(!ok) | past) & ~below;
-                const uint32_t good = bad_mask ? (uint32_t)__builtin_ctzll(bad_mask) : 64u;  // lanes start .. good-1 hold (uniform)
-                if (good > start) {
-                    const int32_t S2 = S + __builtin_amdgcn_readlane(incl, (int)good - 1) - base_d;
-                    const uint32_t m2a = (uint32_t)(S2 < 0 ? -S2 : S2);
-                    s = __uint_as_float((S2 < 0 ? 0x80000000u : 0u) | (se << 23) | (m2a & 0x7FFFFFu));
-                }
-                if (good >= nl) break;
-                walk_lane(good);
-                base_d = __builtin_amdgcn_readlane(incl, (int)good);
-                start = good + 1;
-                if (start >= nl) break;
-            }
-        } else {
-            // exact ties in the batch: which stream a lane's run takes depends on the parity of the S entering it, so the
-            // scan is repeated behind every lane that did not hold (lanes already consumed scan as the identity)
-            uint32_t start = 0;
-            for (;;) {
-                const uint32_t sb = __float_as_uint(s), se = (sb >> 23) & 0xFFu;
-                const bool s_normal = (se != 0u) && (se != 255u);
-                const int32_t mag = (int32_t)((sb & 0x7FFFFFu) | 0x800000u);
-                const int32_t S = (sb >> 31) ? -mag : mag;
-                const bool in = lane >= start;
-                const unsigned long long sc_in = dbg ? clock64() : 0ull;
-                FsD v;
-                v.d0 = in ? mine.d0 : 0, v.d1 = in ? mine.d1 : 0;
-                fs_scan_incl_d(v, lane);
-                const int32_t incl_d = (S & 1) ? v.d1 : v.d0;  // delta from position `start`, for the actual parity of S
-                int32_t before = __shfl_up(incl_d, 1);
-                if (lane == 0) before = 0;
-                const int32_t Sin = S + before;
-                const bool podd = (Sin & 1) != 0;
-                bool ok = s_normal && (lane < nl) && !lane_bad && ((int)se - 127 == lane_e);
-                ok = ok && fs_inside(Sin, podd ? mine.lo1 : mine.lo0, podd ? mine.hi1 : mine.hi0);
-                const uint64_t below = start ? ((~0ull) >> (64 - start)) : 0ull;
-                const uint64_t bad_mask = (__ballot(!ok) | past) & ~below;
-                const uint32_t good = bad_mask ? (uint32_t)__builtin_ctzll(bad_mask) : 64u;
-                if (good > start) {
-                    const int32_t S2 = S + __builtin_amdgcn_readlane(incl_d, (int)good - 1);
-                    const uint32_t m2a = (uint32_t)(S2 < 0 ? -S2 : S2);
-                    s = __uint_as_float((S2 < 0 ? 0x80000000u : 0u) | (se << 23) | (m2a & 0x7FFFFFu));
-                }
-                if (dbg) {
-                    asm volatile("" ::"v"(s));
-                    cyc_lds += clock64() - sc_in;  // (two streams: scan + test + apply)
-                }
-                if (good >= nl) break;
-                const unsigned long long w_in = dbg ? clock64() : 0ull;
-                ++n_walks;
-                walk_lane2(good);
-                if (dbg) {
-                    asm volatile("" ::"v"(s));
-                    cyc_walk += clock64() - w_in;
-                }
-                start = good + 1;
-                if (start >= nl) break;
-            }
-        }
-    }
-    if (lane == 0) {
-        if (MODE == 0) na.centroid[(size_t)node * d + c] = s / (float)len;  // T::from_usize(n)
-        else na.var[(size_t)node * d + c] = s;
-        if (n_fallback && fallbacks) atomicAdd(n_fallback, fallbacks);
-        if (dbg) {
-            atomicAdd(dbg + 0, 1u);
-            atomicAdd(dbg + 1, fallbacks);
-            atomicMax(dbg + 2, fallbacks);
-            atomicAdd(dbg + 8, (uint32_t)((clock64() - cyc_all) >> 6));
-            atomicAdd(dbg + 9, (uint32_t)(cyc_walk >> 6));
-            atomicAdd(dbg + 10, (uint32_t)(cyc_readd >> 6));
-            atomicAdd(dbg + 11, (uint32_t)(cyc_lds >> 6));
-            atomicAdd(dbg + 12, n_walks);
-            atomicMax(dbg + 13, (uint32_t)((clock64() - cyc_all) >> 6));
-            if (blockIdx.x == 0 && blockIdx.y == 0 && n_walks)
-                printf("[vqhip-dev] chain(0,0) mode %d: %u failing lanes, %u scan passes, %u re-added; cycles per failing lane: fetch %.0f; per scan pass: "
-                       "scan+test %.0f, apply %.0f; per re-added segment: before the additions %.0f, additions %.0f; all %.0f k\n",
-                       MODE, n_walks, n_iter, fallbacks, (double)cy_fetch / n_walks, (double)cy_scan / n_iter, (double)cy_apply / n_iter,
-                       (double)cy_pre / (fallbacks ? fallbacks : 1), (double)cy_add / (fallbacks ? fallbacks : 1), (double)(clock64() - cyc_all) / 1e3);
-        }
-    }
-}
-
 // ---- the chain with its operands in LDS ahead of time (round 5) -------------------------------------------------------
-// k_fs_chain above keeps the next batches of summaries in registers and fetches parked addends eight segments at a time
-// on demand.  Measured (VQHIP_TSVQ_DEBUG, C4): a batch of 512 summaries that holds costs ~6000 cycles where its
-// instructions are ~2000, and the first re-addition of a batch waits 600 .. 25000 cycles for its addends (the groups of
-// eight are requested one after the other).  Here a workgroup is two waves.  The LOADER keeps a queue of LDS-DMA loads
+// The chain's first form (rounds 3-4, one wave; removed) kept the next batches of summaries in registers and fetched
+// parked addends eight segments at a time on demand.  Measured at C4: a batch of 512 summaries that holds cost ~6000
+// cycles where its instructions are ~2000, and the first re-addition of a batch waited 600 .. 25000 cycles for its
+// addends (the groups of eight were requested one after the other).  Here a workgroup is two waves.  The LOADER keeps a queue of LDS-DMA loads
 // (global_load_lds_dwordx4: no destination registers) filled -- the summaries of the batch after next, the parked addends
 // of the next batch's first PCAP parked segments, listed from the summaries that have just landed -- and hands batches to
 // the WALKER through two LDS words; the walker reads nothing from memory on its way: summaries, parked addends and the
@@ -2161,24 +1715,21 @@ __global__ __launch_bounds__(64) void k_fs_chain(const float *__restrict__ X, ui
 // profiles/ubench/lds_dma.hip checks where the data lands and the ordering on the device.  A ring three batches deep
 // with exact wait counts (every iteration padded to the same number of DMA instructions) was built too and measured no
 // faster: one batch of look-ahead covers the round trip once the loader runs beside the walker.
-// Everything else -- lane runs of eight segments, wave scan, the eight-lane scan of a failing lane, 64 dependent
-// additions per re-added segment -- is k_fs_chain's; every sum is still the reference's bit pattern.
+// Every sum is still the reference's bit pattern.
 // (M0 = the LDS address; gfx9 and later need M0 for nothing else a compute kernel of this file does -- no LDS bounds, no
-// v_movrel, no ds_gws; the compiler's only own use, checked in the ISA, is the s_sendmsg of a printf in the DEBUG
-// instantiations, set right in front of it -- so no value lives in M0 across the statement)
+// v_movrel, no ds_gws; checked in the ISA, the compiler makes no use of its own of M0 in these kernels -- so no value
+// lives in M0 across the statement)
 __device__ __forceinline__ void fs_dma16(const void *gp, uint32_t lds_byte_addr) {  // lane l: 16 bytes from gp to lds_byte_addr + 16 l
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gp), "s"(lds_byte_addr) : "memory");
 }
 __device__ __forceinline__ void fs_wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
-template <int MODE, bool DBG>
+template <int MODE>
 __global__ __launch_bounds__(128) void k_fs_chain4(const float *__restrict__ X, uint32_t d, const uint32_t *__restrict__ perm,
                                                    const uint32_t *__restrict__ fast_nodes, const uint32_t *__restrict__ tile_base,
                                                    NodeArrays na, const FsS *__restrict__ summ, const FsS *__restrict__ summ_odd,
                                                    const float *__restrict__ side, uint32_t *__restrict__ n_fallback,
-                                                   const LevelInfo *__restrict__ lv, uint32_t *__restrict__ dbg_arg,
-                                                   const uint32_t *__restrict__ only_sampled) {
-    uint32_t *const dbg = DBG ? dbg_arg : nullptr;
+                                                   const LevelInfo *__restrict__ lv, const uint32_t *__restrict__ only_sampled) {
     if (only_sampled && only_sampled[blockIdx.y / kFsCols] == 0u) return;
     constexpr uint32_t kBatch = 64 * kFsSpl;
     constexpr int A = 1, B = 2;                        // batches ahead: parked addends, summaries
@@ -2273,35 +1824,25 @@ __global__ __launch_bounds__(128) void k_fs_chain4(const float *__restrict__ X, 
         fs_wave_lds_sync();
 #pragma unroll
         for (int b = 0; b < A; ++b) issue_parked((uint32_t)b);
-        unsigned long long l_all = dbg ? clock64() : 0ull, l_vm = 0ull, l_done = 0ull;  // VQHIP_TSVQ_DEBUG
         for (uint32_t t = 0; t < nb; ++t) {
-            const unsigned long long q0 = dbg ? clock64() : 0ull;
             // batch t is complete once its parked addends and (for the list built next) the summaries of batch t + A have
             // landed: everything issued so far
             fs_wait_vm0();
-            if (dbg) l_vm += clock64() - q0;
             flag_set(&sync_ready, t + 1u);
             if (t + (uint32_t)A >= nb) continue;  // nothing left to request
-            const unsigned long long q1 = dbg ? clock64() : 0ull;
             if (t > 0u) flag_wait(&sync_done, t);  // the slots written next are batch t - 1's
-            if (dbg) l_done += clock64() - q1;
             issue_parked(t + (uint32_t)A);
             issue_summ(t + (uint32_t)B);
         }
         fs_wait_vm0();  // (nothing may land in LDS after the wave has gone)
-        if (dbg && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0)
-            printf("[vqhip-dev] chain4(0,0) mode %d loader: %u batches, %.0f k cycles: waiting for DMA %.0f k, for the walker %.0f k\n", MODE, nb,
-                   (double)(clock64() - l_all) / 1e3, (double)l_vm / 1e3, (double)l_done / 1e3);
         return;
     }
 
-    // ===================== the walker: k_fs_chain's batch loop over operands that are already in LDS ====================
+    // ===================== the walker: the batch loop over operands that are already in LDS ===========================
     const float mu = (MODE == 1) ? na.centroid[(size_t)node * d + c] : 0.0f;
     float s = (MODE == 0) ? 0.0f : -0.0f;
-    uint32_t fallbacks = 0, n_walks = 0;
-    const unsigned long long cyc_all = dbg ? clock64() : 0ull;
-    unsigned long long w_ready = 0ull, w_walk = 0ull;  // VQHIP_TSVQ_DEBUG: waiting for the loader, inside failing lanes
-    auto add64 = [&](const float *lds64) {  // 64 additions in row order, the addends by broadcast LDS reads (k_fs_chain)
+    uint32_t fallbacks = 0;
+    auto add64 = [&](const float *lds64) {  // 64 additions in row order, the addends by broadcast LDS reads
         const f32x4_t *l4 = reinterpret_cast<const f32x4_t *>(lds64);
         f32x4_t rq[16];
 #pragma unroll
@@ -2316,9 +1857,7 @@ __global__ __launch_bounds__(128) void k_fs_chain4(const float *__restrict__ X, 
     };
     for (uint32_t t = 0; t < nb; ++t) {
         const uint32_t t0 = t * kBatch, cnt = min(kBatch, nseg - t0), nl = (cnt + kFsSpl - 1) / kFsSpl;
-        const unsigned long long w0 = dbg ? clock64() : 0ull;
         flag_wait(&sync_ready, t + 1u);
-        if (dbg) w_ready += clock64() - w0;
         const uint32_t ss = t % (uint32_t)NS, ps = t % (uint32_t)NP;
         FsS m[kFsSpl];
 #pragma unroll
@@ -2330,7 +1869,6 @@ __global__ __launch_bounds__(128) void k_fs_chain4(const float *__restrict__ X, 
                 if (kFsSpl * lane + (uint32_t)j >= cnt) m[j].d = m[j].lo = m[j].hi = 0, m[j].ef = 1;
         }
         const uint32_t pbefore = pi.x, pk = pi.y;
-        if (dbg && lane == 63) atomicAdd(dbg + 14, pbefore + (uint32_t)__builtin_popcount(pk));
         // flags of the lane's run: any summary unusable, binades differ, any odd stream (bit 1; with bit 0 set the run is
         // unusable anyway and the two-stream path is merely taken for nothing)
         uint32_t ef_or = (uint32_t)m[0].ef, ef_x = 0u;
@@ -2395,7 +1933,6 @@ __global__ __launch_bounds__(128) void k_fs_chain4(const float *__restrict__ X, 
                     fs_wait_vm0();
                     fs_wave_lds_sync();
                     pr_base = rank;
-                    if (dbg && lane == 0) atomicAdd(dbg + 7, 1u);
                 }
                 add64(&pring[ps][(rank - pr_base) * 64u]);
             } else {
@@ -2403,7 +1940,6 @@ __global__ __launch_bounds__(128) void k_fs_chain4(const float *__restrict__ X, 
                 {
                     const uint32_t r0 = seg * kFsSeg, rows_here = min(kFsSeg, len - r0);
                     vv = (lane < rows_here) ? fs_value<MODE>(X[(size_t)perm[a + r0 + lane] * d + c], mu) : 0.0f;  // (+0.0 past the end)
-                    if (dbg && lane == 0) atomicAdd(dbg + 7, 1u);
                 }
                 fs_wave_lds_sync();
                 ladd[lane] = vv;
@@ -2411,7 +1947,7 @@ __global__ __launch_bounds__(128) void k_fs_chain4(const float *__restrict__ X, 
                 add64(ladd);
             }
         };
-        // a failing lane's eight segments, scanned over eight lanes (k_fs_chain's walk_lane; the summaries come from the ring)
+        // a failing lane's eight segments, scanned over eight lanes (the summaries come from the ring)
         auto walk_lane = [&](uint32_t good) {
             const uint32_t pb_g = (uint32_t)__builtin_amdgcn_readlane((int)pbefore, (int)good),
                            pk_g = (uint32_t)__builtin_amdgcn_readlane((int)pk, (int)good);
@@ -2446,11 +1982,6 @@ __global__ __launch_bounds__(128) void k_fs_chain4(const float *__restrict__ X, 
                 }
                 if (js >= nvalid) break;
                 const int32_t gef = __builtin_amdgcn_readlane(g.ef, (int)js);
-                if (dbg && lane == 0) {
-                    const uint32_t sb2 = __float_as_uint(s), se2 = (sb2 >> 23) & 0xFFu;  // the S the failing segment meets
-                    const int why = (se2 == 0u || se2 == 255u) ? 6 : (gef & 1) ? 3 : ((int)se2 - 127 != fs_ef_e(gef)) ? 4 : 5;
-                    atomicAdd(dbg + why, 1u);
-                }
                 readd(seg_first + js, gef, pb_g + (uint32_t)__builtin_popcount(pk_g & ((1u << js) - 1u)));
                 base2 = __builtin_amdgcn_readlane(incl8, (int)js);
                 start2 = js + 1;
@@ -2458,7 +1989,7 @@ __global__ __launch_bounds__(128) void k_fs_chain4(const float *__restrict__ X, 
             }
         };
         // two streams (an exact tie somewhere in the batch): the same with the segments' parity transducers composed over the
-        // eight lanes, the scan repeated behind every segment that does not hold (k_fs_chain's walk_lane2)
+        // eight lanes, the scan repeated behind every segment that does not hold 
         auto walk_lane2 = [&](uint32_t good) {
             const uint32_t pb_g = (uint32_t)__builtin_amdgcn_readlane((int)pbefore, (int)good),
                            pk_g = (uint32_t)__builtin_amdgcn_readlane((int)pk, (int)good);
@@ -2503,11 +2034,6 @@ __global__ __launch_bounds__(128) void k_fs_chain4(const float *__restrict__ X, 
                 }
                 if (js >= nvalid) break;
                 const int32_t gef = __builtin_amdgcn_readlane(g.ef, (int)js);
-                if (dbg && lane == 0) {
-                    const uint32_t sb2 = __float_as_uint(s), se2 = (sb2 >> 23) & 0xFFu;
-                    const int why = (se2 == 0u || se2 == 255u) ? 6 : (gef & 1) ? 3 : ((int)se2 - 127 != fs_ef_e(gef)) ? 4 : 5;
-                    atomicAdd(dbg + why, 1u);
-                }
                 readd(seg_first + js, gef, pb_g + (uint32_t)__builtin_popcount(pk_g & ((1u << js) - 1u)));
                 start2 = js + 1;
                 if (start2 >= nvalid) break;
@@ -2582,13 +2108,7 @@ __global__ __launch_bounds__(128) void k_fs_chain4(const float *__restrict__ X, 
                     s = __uint_as_float((S2 < 0 ? 0x80000000u : 0u) | (se << 23) | (m2a & 0x7FFFFFu));
                 }
                 if (good >= nl) break;
-                const unsigned long long q2 = dbg ? clock64() : 0ull;
-                ++n_walks;
                 walk_lane(good);
-                if (dbg) {
-                    asm volatile("" ::"v"(s));
-                    w_walk += clock64() - q2;
-                }
                 base_d = __builtin_amdgcn_readlane(incl, (int)good);
                 start = good + 1;
                 if (start >= nl) break;
@@ -2600,23 +2120,13 @@ __global__ __launch_bounds__(128) void k_fs_chain4(const float *__restrict__ X, 
         if (MODE == 0) na.centroid[(size_t)node * d + c] = s / (float)len;  // T::from_usize(n)
         else na.var[(size_t)node * d + c] = s;
         if (n_fallback && fallbacks) atomicAdd(n_fallback, fallbacks);
-        if (dbg) {
-            atomicAdd(dbg + 0, 1u);
-            atomicAdd(dbg + 1, fallbacks);
-            atomicMax(dbg + 2, fallbacks);
-            atomicAdd(dbg + 8, (uint32_t)((clock64() - cyc_all) >> 6));
-            atomicMax(dbg + 13, (uint32_t)((clock64() - cyc_all) >> 6));
-            if (blockIdx.x == 0 && blockIdx.y == 0)
-                printf("[vqhip-dev] chain4(0,0) mode %d walker: %u batches, %.0f k cycles: waiting for the loader %.0f k, %u failing lanes %.0f k, %u re-added\n",
-                       MODE, nb, (double)(clock64() - cyc_all) / 1e3, (double)w_ready / 1e3, n_walks, (double)w_walk / 1e3, fallbacks);
-        }
     }
 }
 
 // ---- round 5: re-additions looked up, not executed --------------------------------------------------------------------
 // On zero-mean columns the running sum is a random walk that keeps crossing binade edges near zero: 10-30 % of the
 // 64-row segments are parked (their guess comes close to an edge), half of those really leave the binade their summary
-// was folded under, and k_fs_chain above pays ~2000 cycles in series for each (64 dependent additions, an eight-lane scan
+// was folded under, and k_fs_chain4 above pays ~2000 cycles in series for each (64 dependent additions, an eight-lane scan
 // pass, a wave-wide rescan) on the ONE wave a column has.  Two kernels take that work off the column's wave:
 //
 // k_fs_prep, TABLES.  For a parked segment let F be the map "incoming f32 sum -> sum after the segment's 64 additions".
@@ -2762,7 +2272,7 @@ __device__ __forceinline__ FsR fs_run_compose(const FsR &f, const FsR &g) {  // 
 
 constexpr uint32_t kFsBatch = 64 * kFsSpl;         // segments per batch: one lane's eight are one 512-row tile
 constexpr uint32_t kFsItemCap = kFsBatch + 1;      // items of a batch: at most one per segment, plus the end (the two-item form of
-                                                   // a parked segment -- types 3 and 4 -- is not emitted: its columns keep k_fs_chain)
+                                                   // a parked segment -- types 3 and 4 -- is not emitted: its columns keep k_fs_chain4)
 // An item is a run and what ends it, 32 bytes: {rmin0, rmax0, dm0, rmin1}, {rmax1, dm1, info, 0}.  With r the raw bits
 // of the running sum and p = r & 1 (the parity of S: the same as that of |S|), the run holds iff rmin_p <= r <= rmax_p
 // (unsigned: one range per sign and binade) and leaves the sum at r + dm_p.  info = type | tseg << 3 | slot << 12:
@@ -2930,7 +2440,7 @@ __global__ __launch_bounds__(256) void k_fs_prep(const float *__restrict__ side,
     const uint32_t cq = (d + 3) / 4, q = blockIdx.x - n_tab_blocks, G = q / cq, c0 = (q - G * cq) * 4u, c = c0 + w;
     if (G >= lv->pad) return;  // (pad = the level's batches; launched over an upper bound)
     const bool seg_first = policy ? policy[c0 / kFsCols] != 0u : seg_first_default != 0;  // (policy: 1 = sampled guess allowed for the column block)
-    if (seg_first) return;  // columns under a sampled guess keep k_fs_chain (uniform over the workgroup: four columns of one block of 32)
+    if (seg_first) return;  // columns under a sampled guess keep k_fs_chain4 (uniform over the workgroup: four columns of one block of 32)
     if (c >= d) return;
     const uint2 bt = batch_tab[G];
     const uint32_t node = fast_nodes[bt.x], len = na.seg_len[node];
@@ -2961,7 +2471,7 @@ __global__ __launch_bounds__(256) void k_fs_prep(const float *__restrict__ side,
 // hold: walked segment by segment from the summaries in memory, or -- a parked segment's own summary -- followed by its
 // table; a sum outside the table's window: the 64 additions from the parked addends; a segment without a summary: its
 // rows gathered) leaves the loop for one item.  Every lane carries the same sum: all branches are uniform.
-template <int MODE, bool DBG>
+template <int MODE>
 __global__ __launch_bounds__(64) void k_fs_chain3(const float *__restrict__ X, uint32_t d, const uint32_t *__restrict__ perm,
                                                   const uint32_t *__restrict__ fast_nodes, const uint32_t *__restrict__ tile_base,
                                                   const uint32_t *__restrict__ batch_base, NodeArrays na,
@@ -2969,9 +2479,7 @@ __global__ __launch_bounds__(64) void k_fs_chain3(const float *__restrict__ X, u
                                                   const float *__restrict__ side, const float *__restrict__ tab,
                                                   const int4 *__restrict__ tmeta, const int4 *__restrict__ items,
                                                   const uint32_t *__restrict__ ihdr, uint32_t *__restrict__ n_fallback,
-                                                  const LevelInfo *__restrict__ lv, uint32_t *__restrict__ dbg_arg,
-                                                  const uint32_t *__restrict__ skip_sampled) {
-    uint32_t *const dbg = DBG ? dbg_arg : nullptr;
+                                                  const LevelInfo *__restrict__ lv, const uint32_t *__restrict__ skip_sampled) {
     // the chunk being walked / the next one: per item {run fields a, b; m = its table's validity record, or a record that
     // always / never holds for an item without a table: the loop tests nothing else}, one 48-byte record (one address)
     struct __attribute__((aligned(16))) LItem {
@@ -2984,7 +2492,7 @@ __global__ __launch_bounds__(64) void k_fs_chain3(const float *__restrict__ X, u
     __shared__ __attribute__((aligned(16))) FsS lwk[64], lwk2[64];          // summaries of a run being walked
     __shared__ uint32_t lhdr[1024];                                        // items per batch
     if (blockIdx.x >= lv->n_fast) return;
-    if (skip_sampled && skip_sampled[blockIdx.y / kFsCols] != 0u) return;  // columns under a sampled guess keep k_fs_chain
+    if (skip_sampled && skip_sampled[blockIdx.y / kFsCols] != 0u) return;  // columns under a sampled guess keep k_fs_chain4
     const uint32_t fidx = blockIdx.x, node = fast_nodes[fidx], c = blockIdx.y, lane = threadIdx.x;
     const uint32_t a = na.seg_start[node], len = na.seg_len[node];
     const uint32_t nseg = (len + kFsSeg - 1) / kFsSeg, nbat = (nseg + kFsBatch - 1) / kFsBatch, G0 = batch_base[fidx];
@@ -2992,8 +2500,7 @@ __global__ __launch_bounds__(64) void k_fs_chain3(const float *__restrict__ X, u
     const FsS *sp = summ + (size_t)c * na.fs_seg_stride + seg0, *sp2 = summ_odd + (size_t)c * na.fs_seg_stride + seg0;
     const float mu = (MODE == 1) ? na.centroid[(size_t)node * d + c] : 0.0f;
     float s = (MODE == 0) ? 0.0f : -0.0f;
-    uint32_t n_readd = 0, n_hit = 0, n_miss = 0, n_slow = 0, n_parked = 0, n_own = 0, n_out = 0;
-    unsigned long long cy_all = DBG ? clock64() : 0ull, cy_out = 0ull, cy_miss = 0ull, cy_stage = 0ull;  // VQHIP_TSVQ_DEBUG
+    uint32_t n_readd = 0;
     plist[lane] = 0;  // (clamped table requests read entries nobody wrote: slot 0 is a valid address)
     auto add64 = [&](const float *lds64) {  // 64 additions in row order, the addends by broadcast LDS reads
         const f32x4_t *l4 = reinterpret_cast<const f32x4_t *>(lds64);
@@ -3021,7 +2528,6 @@ __global__ __launch_bounds__(64) void k_fs_chain3(const float *__restrict__ X, u
     };
     // a run that did not hold: its segments [from, to) of the column one by one -- 64 summaries at a time through LDS
     auto walk = [&](uint32_t from, uint32_t to) {
-        ++n_slow;
         for (uint32_t q0 = from; q0 < to; q0 += 64u) {
             const uint32_t q = min(q0 + lane, to - 1u);
             const FsS g = sp[q];
@@ -3126,7 +2632,6 @@ __global__ __launch_bounds__(64) void k_fs_chain3(const float *__restrict__ X, u
     int buf = 0;
     uint32_t pos = 0;                   // next segment of the batch not yet consumed when the chunk starts
     while (cn != 0u) {                  // uniform
-        const unsigned long long q_st = DBG ? clock64() : 0ull;
         // this chunk: its validity records and tables (requested a chunk ago) into LDS; the NEXT chunk: out of its registers
         // into the other buffer, its tables requested; the chunk after it requested
         // (an item that ends in nothing passes the table test whatever the sum, a gathered one never does; a parked segment
@@ -3145,12 +2650,10 @@ __global__ __launch_bounds__(64) void k_fs_chain3(const float *__restrict__ X, u
 #pragma unroll
                 for (int k = 8 * g8; k < 8 * g8 + 8; ++k) ltab[k * 64 + (int)lane] = pf[k];  // tables 2k and 2k + 1
             }
-        if (DBG) n_parked += ptot_cur;
         const uint32_t nn = rn, nt0 = rt;
         ptot_next = stage(buf ^ 1);
         const uint32_t ntype = stype;
         request();
-        if (DBG) cy_stage += clock64() - q_st;
         // (the item index goes through fs_vgpr: an LDS read at a uniform address is moved to SGPRs -- eleven v_readfirstlane --
         // right behind the read, i.e. the wave waits for the item it has just asked for; as vector registers the next
         // item's fields are waited for when they are used, an item later)
@@ -3174,10 +2677,7 @@ __global__ __launch_bounds__(64) void k_fs_chain3(const float *__restrict__ X, u
             const bool fast = (sb - rmin) <= span && tail_ok;
             if (__ballot(fast) != 0ull) {  // (every lane holds the same sum: any == all)
                 s = is_tab ? tv + (float)(mml + M.y) * __int_as_float(M.w) : __uint_as_float(s1);
-                if (DBG) n_hit += is_tab ? 1u : 0u;
             } else {
-                const unsigned long long q_o = DBG ? clock64() : 0ull;
-                ++n_out;
                 const uint32_t info = (uint32_t)__builtin_amdgcn_readfirstlane(B.z), ty = info & 7u, tseg = (info >> 3) & 511u;
                 const bool ok = (sb - rmin) <= span;
                 // where the run starts: behind what the item in front consumed
@@ -3199,22 +2699,11 @@ __global__ __launch_bounds__(64) void k_fs_chain3(const float *__restrict__ X, u
                     if (__ballot(hit3) != 0ull) {
                         const float tv3 = ltab[(((uint32_t)B.w & 0x7FFFFFFFu) >> 2) + (sb3 & 31u)];
                         s = tv3 + (float)(m3 + M.y) * __int_as_float(M.w);
-                        if (DBG) ++n_hit;
                     } else {
-                        const unsigned long long q_ms = DBG ? clock64() : 0ull;
                         readd_from(side[(size_t)(info >> 12) * kFsSeg + lane]);
-                        if (DBG) {
-                            asm volatile("" ::"v"(s));
-                            cy_miss += clock64() - q_ms;
-                        }
-                        ++n_miss;
                     }
                 } else if (ty == kFsItGather) {
                     gather_add(ct0 + tseg);
-                }
-                if (DBG) {
-                    asm volatile("" ::"v"(s));
-                    cy_out += clock64() - q_o;
                 }
             }
             A = nA, B = nB, M = nM;
@@ -3230,66 +2719,6 @@ __global__ __launch_bounds__(64) void k_fs_chain3(const float *__restrict__ X, u
         if (MODE == 0) na.centroid[(size_t)node * d + c] = s / (float)len;  // T::from_usize(n)
         else na.var[(size_t)node * d + c] = s;
         if (n_fallback && n_readd) atomicAdd(n_fallback, n_readd);
-        if (dbg) {  // VQHIP_TSVQ_DEBUG: chains, re-added segments (most in one chain), table hits / misses, runs walked, core cycles
-            atomicAdd(dbg + 0, 1u);
-            atomicAdd(dbg + 1, n_readd);
-            atomicMax(dbg + 2, n_readd);
-            atomicAdd(dbg + 3, n_hit);
-            atomicAdd(dbg + 4, n_miss);
-            atomicAdd(dbg + 5, n_slow);
-            atomicAdd(dbg + 6, n_own);
-            atomicAdd(dbg + 7, n_out);
-            atomicAdd(dbg + 14, n_parked);
-            atomicAdd(dbg + 8, (uint32_t)((clock64() - cy_all) >> 6));
-            atomicAdd(dbg + 9, (uint32_t)(cy_out >> 6));
-            atomicAdd(dbg + 10, (uint32_t)(cy_miss >> 6));
-            atomicAdd(dbg + 11, (uint32_t)(cy_stage >> 6));
-            atomicMax(dbg + 13, (uint32_t)((clock64() - cy_all) >> 6));
-        }
-    }
-}
-
-// debug aid (VQHIP_TSVQ_CHECK=1): per (node, column) walk the segments one by one, compare the summary-applied
-// sum with the row-by-row sum and report the first disagreement
-template <int MODE>
-__global__ __launch_bounds__(64) void k_fs_check(const float *__restrict__ X, uint32_t d, const uint32_t *__restrict__ perm,
-                                                 const uint32_t *__restrict__ fast_nodes,
-                                                 const uint32_t *__restrict__ tile_base, NodeArrays na,
-                                                 const FsS *__restrict__ summ, const FsS *__restrict__ summ_odd,
-                                                 const LevelInfo *__restrict__ lv) {
-    if (blockIdx.x >= lv->n_fast) return;
-    const uint32_t node = fast_nodes[blockIdx.x], c = blockIdx.y;
-    if (threadIdx.x != 0) return;
-    const uint32_t a = na.seg_start[node], len = na.seg_len[node];
-    const uint32_t nseg = (len + kFsSeg - 1) / kFsSeg;
-    const size_t seg0 = (size_t)tile_base[blockIdx.x] * kFsSegsPerTile;
-    const float mu = (MODE == 1) ? na.centroid[(size_t)node * d + c] : 0.0f;
-    float s = (MODE == 0) ? 0.0f : -0.0f;
-    for (uint32_t t = 0; t < nseg; ++t) {
-        const FsS sm = summ[(size_t)c * na.fs_seg_stride + seg0 + t];
-        FsS so = sm;
-        if ((sm.ef & 3) == 2) so = summ_odd[(size_t)c * na.fs_seg_stride + seg0 + t];
-        float seq = s;
-        const uint32_t r0 = t * kFsSeg, r1 = min(len, r0 + kFsSeg);
-        for (uint32_t r = r0; r < r1; ++r) seq = seq + fs_value<MODE>(X[(size_t)perm[a + r] * d + c], mu);
-        const uint32_t sb = __float_as_uint(s), se = (sb >> 23) & 0xFFu;
-        if (((sm.ef & 1) == 0) && se != 0u && se != 255u && ((int)se - 127 == fs_ef_e(sm.ef))) {
-            const int32_t mag = (int32_t)((sb & 0x7FFFFFu) | 0x800000u);
-            const int32_t S = (sb >> 31) ? -mag : mag;
-            const bool odd = (S & 1) != 0;
-            const int32_t D = odd ? so.d : sm.d, lo = odd ? so.lo : sm.lo, hi = odd ? so.hi : sm.hi;
-            if (fs_inside(S, lo, hi)) {
-                const int32_t S2 = S + D;
-                const uint32_t m2 = (uint32_t)(S2 < 0 ? -S2 : S2);
-                const float fast = __uint_as_float((S2 < 0 ? 0x80000000u : 0u) | (se << 23) | (m2 & 0x7FFFFFu));
-                if (__float_as_uint(fast) != __float_as_uint(seq)) {
-                    printf("[fs_check] mode %d node %u col %u segment %u: s=%.9g (S=%d odd=%d e=%d) summary D=%d lo=%d hi=%d -> %.9g, row by row %.9g\n",
-                           MODE, node, c, t, s, S, (int)odd, fs_ef_e(sm.ef), D, lo, hi, fast, seq);
-                    return;
-                }
-            }
-        }
-        s = seq;
     }
 }
 
@@ -3598,23 +3027,6 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
     // levels: the root is level 0; a tree over n rows is at most n - 1 levels deep whatever max_depth says
     const uint32_t n_levels = (uint32_t)std::min<uint64_t>((uint64_t)max_depth, (uint64_t)n - 1) + 1;
 
-    // VQHIP_TSVQ_TIMING=<ms>: host-side timeline of every build slower than <ms> (where did an outlier spend its time?)
-    static const char *timing_env = getenv("VQHIP_TSVQ_TIMING");
-    struct Marks {
-        double limit_ms = -1.0;
-        std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-        std::vector<std::pair<const char *, double>> v;
-        void mark(const char *what) {
-            if (limit_ms >= 0.0) v.emplace_back(what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-        }
-        ~Marks() {
-            if (limit_ms < 0.0 || v.empty() || v.back().second < limit_ms) return;
-            fprintf(stderr, "[vqhip] tsvq build timeline (ms):");
-            for (auto &m : v) fprintf(stderr, " %s %.2f", m.first, m.second);
-            fprintf(stderr, "\n");
-        }
-    } marks;
-    marks.limit_ms = timing_env ? atof(timing_env) : -1.0;
     static thread_local TsvqBuildWs ws;
     {
         int dev = 0;
@@ -3631,12 +3043,11 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
     // widest level: min(2^level, n) nodes
     auto level_width = [&](uint32_t L) -> uint32_t { return (L >= 31) ? n : (uint32_t)std::min<uint64_t>(1ull << L, n); };
     const uint32_t wmax = level_width(n_levels - 1);
-    static const char *minrows_env = getenv("VQHIP_TSVQ_FAST_MIN_ROWS");  // nodes at least this long take the tile-parallel emulation
-    // The plain chain costs one dependent v_add_f32 per row and column chain (~4.9 ns per row, measured, whatever d is
-    // while its workgroups fit the chip); the emulation costs about what streaming the level's rows at ~1.7 TB/s does.
+    // Nodes at least fs_min_rows long take the tile-parallel emulation.  The plain chain costs one dependent v_add_f32 per
+    // row and column chain (~4.9 ns per row, measured, whatever d is while its workgroups fit the chip); the emulation costs about what streaming the level's rows at ~1.7 TB/s does.
     // A node of `len` rows is cheaper through the emulation when len * 4.9 ns > n * d * 4 B / 1.7 TB/s.
     const uint32_t fs_model_rows = (uint32_t)std::min<double>(4.0e9, 4.8e-4 * (double)d * (double)n);
-    const uint32_t fs_min_rows = minrows_env ? (uint32_t)std::max(4096, atoi(minrows_env)) : std::max(kFsMinRows, fs_model_rows);
+    const uint32_t fs_min_rows = std::max(kFsMinRows, fs_model_rows);
     const uint32_t fast_max = n / fs_min_rows + 1, tiles_max = n / kFsTile + fast_max + 1;
     for (int q = 0; q < 2; ++q) {
         VQ_TRY(ws.b_perm[q].ensure((size_t)n * 4));
@@ -3652,10 +3063,9 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
     VQ_TRY(ws.b_lvl2.ensure((size_t)wmax * 4));
     VQ_TRY(ws.b_remap2.ensure((size_t)wmax * 4));
     VQ_TRY(ws.b_lvl_slow.ensure((size_t)wmax * 4));
-    // median: three radix rounds of 11 / 11 / 10 bits (2048 bins per node and rank) while the widest level's histograms
-    // stay small, else four rounds of 8 bits
-    static const char *radix_env = getenv("VQHIP_TSVQ_RADIX8");  // =1: four 8-bit rounds (A/B)
-    const bool radix11 = wmax <= 4096 && !(radix_env && radix_env[0] == '1');
+    // median: one 11-bit round over linear bins plus candidate lists (2048 bins per node and rank) while the widest
+    // level's histograms stay small, else four radix rounds of 8 bits
+    const bool radix11 = wmax <= 4096;
     const uint32_t hist_bins = radix11 ? 2048u : 256u;
     VQ_TRY(ws.b_hist.ensure(((size_t)wmax * 2 * hist_bins + 2 * (size_t)wmax) * 4));  // + the candidate counters (k_select_collect)
     VQ_TRY(ws.b_seg_start.ensure((size_t)dcap * 4));
@@ -3673,7 +3083,7 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
     VQ_TRY(ws.b_cent.ensure((size_t)dcap * d * 4));
     VQ_TRY(ws.b_var.ensure((size_t)dcap * d * 4));
     VQ_TRY(ws.b_lv.ensure((size_t)(n_levels + 1) * sizeof(LevelInfo)));
-    VQ_TRY(ws.b_fs_fb.ensure(8 + 64 * 2 * 64 + 4096));  // [0] tile re-additions (diagnostic), [1] side-buffer slots handed out, [2..] VQHIP_TSVQ_DEBUG counters: 8 per (level < 64, pass)
+    VQ_TRY(ws.b_fs_fb.ensure(8 + 4096));  // [0] tile re-additions (diagnostic), [1] side-buffer slots handed out, [2..] the sampling policy
     NodeArrays na;
     na.seg_start = ws.b_seg_start.as<uint32_t>();
     na.seg_len = ws.b_seg_len.as<uint32_t>();
@@ -3691,25 +3101,21 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
     int32_t *node_left = ws.b_left.as<int32_t>(), *node_right = ws.b_right.as<int32_t>();
     LevelInfo *lv = ws.b_lv.as<LevelInfo>();
 
-    static const char *nopark = getenv("VQHIP_TSVQ_NOPARK");
     static const char *seq_env = getenv("VQHIP_TSVQ_SEQSUM");  // =1: plain chain everywhere (A/B)
     const bool can_fast = (d % 4 == 0) && !(seq_env && seq_env[0] == '1');  // 16-byte row parts
-    static const char *samp_env = getenv("VQHIP_TSVQ_SAMPLE");  // rows read for the mean pass's binade guess: 1/N (default 1/4)
-    const uint32_t fs_sample = samp_env ? (uint32_t)std::max(1, std::min(16, atoi(samp_env))) : 4u;  // (1/8 until k_fs_chain4: 17 us a level against 30, but twice the segments folded under the wrong binade -- C4 3.90 against 3.84 ms)
-    // sampling policy per block of 32 columns (k_fs_policy), behind the diagnostics in b_fs_fb; a forced VQHIP_TSVQ_SAMPLE
-    // applies to every column
+    // rows read for the mean pass's binade guess: 1/4 (1/8 until k_fs_chain4: 17 us a level against 30, but twice the
+    // segments folded under the wrong binade -- C4 3.90 against 3.84 ms)
+    constexpr uint32_t fs_sample = 4;
+    // sampling policy per block of 32 columns (k_fs_policy), behind the counters in b_fs_fb
     const uint32_t n_cblk = (d + kFsCols - 1) / kFsCols;
-    const bool adaptive_sampling = !samp_env && can_fast && n_cblk <= 1024;
-    const float park_rel = fs_sample > 1 ? 3.0f * 0.6f * sqrtf((float)fs_sample / (float)kFsTile) : 0.0f;  // k_fs_fold: parking margin
+    const bool adaptive_sampling = can_fast && n_cblk <= 1024;
+    const float park_rel = 3.0f * 0.6f * sqrtf((float)fs_sample / (float)kFsTile);  // k_fs_fold: parking margin
     // segment summaries [segment slot][column]: eight slots per tile, a node's segments contiguous
     const size_t seg_slots = (size_t)tiles_max * kFsSegsPerTile;
     na.fs_seg_stride = (uint32_t)seg_slots;  // (a multiple of 8: a tile's eight summaries of a column are one aligned 128-byte line)
     // parked segments per pass (256 bytes each; beyond the cap the re-addition gathers its rows, two dependent loads): half
     // of all segments (zero-mean columns park up to a third at the deeper levels), 256 MB at most
-    const uint32_t side_cap = (nopark && nopark[0] == '1') ? 0u : (uint32_t)std::min<uint64_t>(seg_slots * d / 2 + 1, 1ull << 20);
-    // VQHIP_TSVQ_CHAIN=1: round 4's chain (re-additions executed on the column's wave) instead of the table form (A/B)
-    static const char *chain_env = getenv("VQHIP_TSVQ_CHAIN");
-    const bool use_tables = side_cap > 0 && !(chain_env && chain_env[0] == '1');
+    const uint32_t side_cap = (uint32_t)std::min<uint64_t>(seg_slots * d / 2 + 1, 1ull << 20);
     const uint32_t batches_max = tiles_max / 64 + fast_max + 1;
     if (can_fast) {
         VQ_TRY(ws.b_fs_tiles.ensure((size_t)tiles_max * sizeof(FsTile)));
@@ -3723,15 +3129,13 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
             VQ_TRY(ws.b_fs_summ.ensure(seg_slots * d * sizeof(FsS)));
             VQ_TRY(ws.b_fs_summ2.ensure(seg_slots * d * sizeof(FsS)));
             VQ_TRY(ws.b_fs_side.ensure(std::max<size_t>((size_t)side_cap * kFsSeg * 4, 16)));
-            if (use_tables) {
-                VQ_TRY(ws.b_fs_tab.ensure(std::max<size_t>((size_t)side_cap * kFsTabN * 4, 16)));
-                VQ_TRY(ws.b_fs_smeta.ensure(std::max<size_t>((size_t)side_cap * 2 * sizeof(uint4), 16)));  // two records per slot
-                VQ_TRY(ws.b_fs_tmeta.ensure(std::max<size_t>((size_t)side_cap * sizeof(int4), 16)));
-                VQ_TRY(ws.b_fs_bbase.ensure((size_t)fast_max * 4));
-                VQ_TRY(ws.b_fs_btab.ensure((size_t)batches_max * sizeof(uint2)));
-                VQ_TRY(ws.b_fs_items.ensure((size_t)batches_max * d * kFsItemCap * 2 * sizeof(int4)));
-                VQ_TRY(ws.b_fs_ihdr.ensure((size_t)batches_max * d * 4));
-            }
+            VQ_TRY(ws.b_fs_tab.ensure(std::max<size_t>((size_t)side_cap * kFsTabN * 4, 16)));
+            VQ_TRY(ws.b_fs_smeta.ensure(std::max<size_t>((size_t)side_cap * 2 * sizeof(uint4), 16)));  // two records per slot
+            VQ_TRY(ws.b_fs_tmeta.ensure(std::max<size_t>((size_t)side_cap * sizeof(int4), 16)));
+            VQ_TRY(ws.b_fs_bbase.ensure((size_t)fast_max * 4));
+            VQ_TRY(ws.b_fs_btab.ensure((size_t)batches_max * sizeof(uint2)));
+            VQ_TRY(ws.b_fs_items.ensure((size_t)batches_max * d * kFsItemCap * 2 * sizeof(int4)));
+            VQ_TRY(ws.b_fs_ihdr.ensure((size_t)batches_max * d * 4));
         }
     } else {
         VQ_TRY(ws.b_fs_tiles.ensure(16));
@@ -3741,17 +3145,16 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
     }
     const bool have_fast = can_fast && n >= fs_min_rows;
 
-    marks.mark("allocated");
     // initial state (k_build_init), then the sampling policy; nothing comes from the host, so nothing waits for it here
     static_assert(sizeof(LevelInfo) == 32 && offsetof(LevelInfo, count) == 4, "k_build_init writes LevelInfo[0].count as word 1");
     hipLaunchKernelGGL(k_build_init, dim3(std::min<uint32_t>((n + 255) / 256, (uint32_t)num_cus() * 16)), dim3(256), 0, stream,
                        ws.b_perm[0].as<uint32_t>(), ws.b_nodeof[0].as<uint32_t>(), n, ws.b_left.as<int32_t>(), ws.b_right.as<int32_t>(), dcap,
                        ws.b_lv.as<uint32_t>(), (uint32_t)((n_levels + 1) * sizeof(LevelInfo) / 4), na.seg_start, na.seg_len,
-                       ws.b_fs_fb.as<uint32_t>(), (uint32_t)((8 + 64 * 2 * 64) / 4), ws.b_hist.as<uint32_t>(), wmax * 2 * hist_bins + 2 * wmax);
+                       ws.b_fs_fb.as<uint32_t>(), 2u, ws.b_hist.as<uint32_t>(), wmax * 2 * hist_bins + 2 * wmax);
     VQ_LAUNCH_CHECK("k_build_init");
     // the sampling policy: from the data set's cache if an earlier build left it there, else the kernel (into the cache's
     // buffer when there is one)
-    uint32_t *policy_buf = ws.b_fs_fb.as<uint32_t>() + 2 + 64 * 2 * 16;
+    uint32_t *policy_buf = ws.b_fs_fb.as<uint32_t>() + 2;
     bool policy_cached = false, any_sampled = true, any_exact = true;
     if (adaptive_sampling && n >= fs_min_rows) {
         if (policy_cache) {
@@ -3770,8 +3173,6 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
             VQ_LAUNCH_CHECK("k_fs_policy");
         }
     }
-    marks.mark("queued");
-    marks.mark("setup");
     int cur = 0;
     const uint32_t ncb = (d + kFsCols - 1) / kFsCols;
     uint32_t *const lvl_split_buf[2] = {ws.b_lvl.as<uint32_t>(), ws.b_lvl2.as<uint32_t>()};  // by level parity: k_plan_fused writes
@@ -3785,11 +3186,10 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
     const uint32_t *fn = ws.b_fs_nodes.as<uint32_t>(), *fb = ws.b_fs_base.as<uint32_t>(), *fc = ws.b_fs_nt.as<uint32_t>();
     float *side = ws.b_fs_side.as<float>();
     float *tabs = ws.b_fs_tab.as<float>();
-    uint4 *smeta = use_tables ? ws.b_fs_smeta.as<uint4>() : nullptr;
+    uint4 *smeta = ws.b_fs_smeta.as<uint4>();
     int4 *tmeta = ws.b_fs_tmeta.as<int4>();
-    const bool have_prep = use_tables && can_fast && n >= fs_min_rows;
-    uint32_t *bbase = have_prep ? ws.b_fs_bbase.as<uint32_t>() : nullptr;
-    uint2 *btab = have_prep ? ws.b_fs_btab.as<uint2>() : nullptr;
+    uint32_t *bbase = have_fast ? ws.b_fs_bbase.as<uint32_t>() : nullptr;
+    uint2 *btab = have_fast ? ws.b_fs_btab.as<uint2>() : nullptr;
     int4 *items = ws.b_fs_items.as<int4>();
     uint32_t *ihdr = ws.b_fs_ihdr.as<uint32_t>();
     // tags of this build's passes: never a value an earlier pass (of this or an earlier build over the same scratch) used
@@ -3799,16 +3199,12 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
 
     // sequential-order column sums of the level's nodes: long nodes through the tile-parallel exact emulation (k_fs_*),
     // the rest through the plain chain kernel.  Grids are upper bounds; the kernels read the level's counts.
-    static const bool fs_debug = getenv("VQHIP_TSVQ_DEBUG") != nullptr;
     auto colsum = [&](int mode, const LevelInfo *lvp, uint32_t ub_nodes, const uint32_t *perm, bool with_fast, bool with_slow) -> int {
-        const uint32_t lvl_idx = (uint32_t)(lvp - lv);
-        uint32_t *dbg = (fs_debug && lvl_idx < 64) ? fbk + 2 + (lvl_idx * 2 + (uint32_t)mode) * 16 : nullptr;
         const uint32_t ub_fast = (have_fast && with_fast) ? std::min(ub_nodes, fast_max) : 0u;
         // few nodes: 16 columns per workgroup (more chains in flight); many: 32 (fewer, fuller workgroups)
         const uint32_t g16 = (d + 15) / 16, g32 = (d + 31) / 32;
-        static const char *narrow_env = getenv("VQHIP_TSVQ_NARROW_WGS");
-        const uint64_t narrow_max = narrow_env ? (uint64_t)atoi(narrow_env) : (uint64_t)num_cus();  // measured: 16-column workgroups pay only while they leave CUs idle otherwise
-        const bool narrow = (uint64_t)ub_nodes * g16 <= narrow_max;
+        // (measured: 16-column workgroups pay only while they leave CUs idle otherwise)
+        const bool narrow = (uint64_t)ub_nodes * g16 <= (uint64_t)num_cus();
         if (!with_slow) {
             // (speculation, below: no node of this level is expected on the plain chain)
         } else if (narrow) {
@@ -3832,16 +3228,13 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
         const uint32_t ub_batches = std::min(batches_max, ub_tiles / 64 + ub_fast);
         const dim3 bgrid(n_tab_blocks + ub_batches * ((d + 3) / 4));
         // Mean pass: columns with an exact guess (k_fs_policy: zero-mean columns, where 10-30 % of the segments leave their
-        // binade) through the tables + items + one-pass chain of round 5; columns under a sampled guess (most parked segments
-        // hold there, and the guess is off by far more than a table's window) and the variance pass (monotone sums: a
-        // handful of crossings per column) keep round 4's chain.
+        // binade) through the tables + items + one-pass chain of round 5 (k_fs_chain3); columns under a sampled guess (most
+        // parked segments hold there, and the guess is off by far more than a table's window) and the variance pass
+        // (monotone sums: a handful of crossings per column) take k_fs_chain4 (loader + walker, operands in LDS ahead of time).
         // (a cached policy tells the host which of the two has columns at all: no empty launches)
-        const bool new_any = use_tables && mode == 0 && (policy != nullptr ? any_exact : fs_sample == 1);
-        const bool old_any = !(use_tables && mode == 0) || (policy != nullptr ? any_sampled : fs_sample > 1);
+        const bool new_any = mode == 0 && policy != nullptr && any_exact;
+        const bool old_any = mode != 0 || policy == nullptr || any_sampled;
         const uint32_t *only_sampled = (new_any && old_any) ? policy : nullptr;
-        // k_fs_chain4 (loader + walker, operands in LDS ahead of time) unless VQHIP_TSVQ_CHAIN4=0 (A/B: k_fs_chain)
-        static const char *c4_env = getenv("VQHIP_TSVQ_CHAIN4");
-        const bool use_chain4 = !(c4_env && c4_env[0] == '0');
         if (mode == 0) {
             // the binade guesses: f64 sums of every 4th group of rows of each tile where k_fs_policy allows (|mean| >= sigma),
             // of every row elsewhere; prefix over the node's tiles
@@ -3850,39 +3243,18 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
             hipLaunchKernelGGL(k_fs_fold<0>, xgrid, dim3(64), 0, stream, X, d, perm, tl, lvp, na, tp, sm, sm2, side, side_cap, fbk + 1, mom, park_rel, policy, new_any ? smeta : (uint4 *)nullptr, tag);
             if (new_any) {
                 hipLaunchKernelGGL(k_fs_prep, bgrid, dim3(256), 0, stream, side, smeta, tag, fbk + 1, side_cap, tabs, tmeta, n_tab_blocks, d, fn, fb, btab, na, sm, sm2, items, ihdr, lvp, policy, 0);
-                if (dbg) hipLaunchKernelGGL((k_fs_chain3<0, true>), cgrid, dim3(64), 0, stream, X, d, perm, fn, fb, bbase, na, sm, sm2, side, tabs, tmeta, items, ihdr, fbk, lvp, dbg, policy);
-                else hipLaunchKernelGGL((k_fs_chain3<0, false>), cgrid, dim3(64), 0, stream, X, d, perm, fn, fb, bbase, na, sm, sm2, side, tabs, tmeta, items, ihdr, fbk, lvp, dbg, policy);
+                hipLaunchKernelGGL(k_fs_chain3<0>, cgrid, dim3(64), 0, stream, X, d, perm, fn, fb, bbase, na, sm, sm2, side, tabs, tmeta, items, ihdr, fbk, lvp, policy);
             }
-            if (old_any) {
-                // (VQHIP_TSVQ_DEBUG counts one form per pass: the new one where both run)
-                uint32_t *const dbg0 = (dbg && !new_any) ? dbg : nullptr;
-                if (!use_chain4) {
-                    if (dbg0) hipLaunchKernelGGL((k_fs_chain<0, true>), cgrid, dim3(64), 0, stream, X, d, perm, fn, fb, na, sm, sm2, side, fbk, lvp, dbg0, only_sampled);
-                    else hipLaunchKernelGGL((k_fs_chain<0, false>), cgrid, dim3(64), 0, stream, X, d, perm, fn, fb, na, sm, sm2, side, fbk, lvp, (uint32_t *)nullptr, only_sampled);
-                } else {
-                    if (dbg0) hipLaunchKernelGGL((k_fs_chain4<0, true>), cgrid, dim3(128), 0, stream, X, d, perm, fn, fb, na, sm, sm2, side, fbk, lvp, dbg0, only_sampled);
-                    else hipLaunchKernelGGL((k_fs_chain4<0, false>), cgrid, dim3(128), 0, stream, X, d, perm, fn, fb, na, sm, sm2, side, fbk, lvp, (uint32_t *)nullptr, only_sampled);
-                }
-            }
+            if (old_any)
+                hipLaunchKernelGGL(k_fs_chain4<0>, cgrid, dim3(128), 0, stream, X, d, perm, fn, fb, na, sm, sm2, side, fbk, lvp, only_sampled);
         } else {
             // the guess comes from the sums the mean pass of the same level left behind (same tile table: every node
             // long enough for the emulation has more than one row, so it is a split node whenever the level splits)
             hipLaunchKernelGGL(k_fs_prefix<true>, pgrid, dim3(1024), 0, stream, d, fn, fb, fc, na, ts, mom, tp, lvp, fbk + 1);
             hipLaunchKernelGGL(k_fs_fold<1>, xgrid, dim3(64), 0, stream, X, d, perm, tl, lvp, na, tp, sm, sm2, side, side_cap, fbk + 1, (double2 *)nullptr, 0.0f, (const uint32_t *)nullptr, (uint4 *)nullptr, 0u);
-            if (!use_chain4) {
-                if (dbg) hipLaunchKernelGGL((k_fs_chain<1, true>), cgrid, dim3(64), 0, stream, X, d, perm, fn, fb, na, sm, sm2, side, fbk, lvp, dbg, (const uint32_t *)nullptr);
-                else hipLaunchKernelGGL((k_fs_chain<1, false>), cgrid, dim3(64), 0, stream, X, d, perm, fn, fb, na, sm, sm2, side, fbk, lvp, dbg, (const uint32_t *)nullptr);
-            } else {
-                if (dbg) hipLaunchKernelGGL((k_fs_chain4<1, true>), cgrid, dim3(128), 0, stream, X, d, perm, fn, fb, na, sm, sm2, side, fbk, lvp, dbg, (const uint32_t *)nullptr);
-                else hipLaunchKernelGGL((k_fs_chain4<1, false>), cgrid, dim3(128), 0, stream, X, d, perm, fn, fb, na, sm, sm2, side, fbk, lvp, dbg, (const uint32_t *)nullptr);
-            }
+            hipLaunchKernelGGL(k_fs_chain4<1>, cgrid, dim3(128), 0, stream, X, d, perm, fn, fb, na, sm, sm2, side, fbk, lvp, (const uint32_t *)nullptr);
         }
         VQ_LAUNCH_CHECK("k_fs_*");
-        if (getenv("VQHIP_TSVQ_CHECK")) {
-            if (mode == 0) hipLaunchKernelGGL(k_fs_check<0>, cgrid, dim3(64), 0, stream, X, d, perm, fn, fb, na, sm, sm2, lvp);
-            else hipLaunchKernelGGL(k_fs_check<1>, cgrid, dim3(64), 0, stream, X, d, perm, fn, fb, na, sm, sm2, lvp);
-            VQ_HIP(hipStreamSynchronize(stream));
-        }
         return VQHIP_OK;
     };
 
@@ -3894,27 +3266,24 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
     bool fast_possible = have_fast;
     uint32_t ask_from = 0;
     while (ask_from < 31 && (uint64_t)(n >> ask_from) >= fs_min_rows) ++ask_from;
-    static const char *noask_env = getenv("VQHIP_TSVQ_NO_LEVEL_ASK");  // =1: always launch both halves (A/B)
     // Speculation: a median split halves a node (up to ties on the split dimension), so above level `ask_from` every node is
     // long and from it on none is -- the build launches ONLY the kernels of the path each level is expected to take (an empty
     // launch costs ~5 us: ten k_seg_colsum launches over no nodes at C4) and does not ask.  The level table read back at the
     // end says whether a level held a node of the other kind (heavy ties: uneven children); then the build is repeated
     // with both paths launched everywhere, and a data set remembers that (policy cache).
-    static const char *spec_env = getenv("VQHIP_TSVQ_SPECULATE");  // =0: never
     bool cache_says_no = false;
     if (policy_cache) {
         std::lock_guard<std::mutex> lk(policy_cache->mu);
         cache_says_no = policy_cache->no_speculation;
     }
-    const bool speculate = have_fast && !tl_tsvq_conservative && !cache_says_no && !(spec_env && spec_env[0] == '0') &&
-                           !(noask_env && noask_env[0] == '1') && !getenv("VQHIP_TSVQ_DEBUG");
+    const bool speculate = have_fast && !tl_tsvq_conservative && !cache_says_no;
     hipLaunchKernelGGL(k_plan_level, dim3(1), dim3(1024), 0, stream, &lv[0], max_depth > 0 ? 1 : 0, can_fast ? 1 : 0, fs_min_rows, na, lvl_split_buf[0],
                        remap_buf[0], ws.b_fs_nodes.as<uint32_t>(), slow_nodes, ws.b_fs_base.as<uint32_t>(), ws.b_fs_nt.as<uint32_t>(),
                        ws.b_fs_tiles.as<FsTile>(), bbase, btab);
     VQ_LAUNCH_CHECK("k_plan_level");
     for (uint32_t L = 0; L < n_levels; ++L) {
         uint32_t ub_nodes = level_width(L);
-        const bool ask = !speculate && fast_possible && L >= ask_from && !(noask_env && noask_env[0] == '1');
+        const bool ask = !speculate && fast_possible && L >= ask_from;
         const bool lvl_fast = speculate ? L < ask_from : fast_possible, lvl_slow = speculate ? L >= ask_from : true;
         if (ub_nodes > 1024 || ask) {
             // wide levels: read the level's node count (one small copy + synchronisation) instead of launching the
@@ -3922,7 +3291,6 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
             LevelInfo h;
             VQ_HIP(hipMemcpyAsync(&h, &lv[L], sizeof(LevelInfo), hipMemcpyDeviceToHost, stream));
             VQ_HIP(hipStreamSynchronize(stream));
-            marks.mark("level-sync");
             if (h.count == 0) break;
             ub_nodes = std::min(ub_nodes, h.count);
             if (h.n_fast == 0) fast_possible = false;
@@ -3939,7 +3307,7 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
         VQ_TRY(colsum(1, lvp, ub_nodes, perm, lvl_fast, lvl_slow));
         hipLaunchKernelGGL(k_pick_split, dim3((ub_nodes + 3) / 4), dim3(256), 0, stream, lvl_split, lvp, d, na);
         VQ_LAUNCH_CHECK("k_pick_split");
-        // median (tsvq.rs:68-81): radix select (three rounds of 11 / 11 / 10 bits) of the two middle order statistics; the first round gathers the
+        // median (tsvq.rs:68-81): select of the two middle order statistics (radix11 or four 8-bit rounds); the first round gathers the
         // split dimension's values
         {
             const uint32_t hblocks = std::min<uint32_t>((n + 2047) / 2048, (uint32_t)num_cus() * 4);
@@ -3955,23 +3323,16 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
             using T = std::true_type;
             using F = std::false_type;
             if (radix11) {
-                static const char *rounds_env = getenv("VQHIP_TSVQ_RADIX_ROUNDS");  // =1: three histogram rounds on the keys' bits instead of linear bins + candidate lists (A/B)
-                if (rounds_env && rounds_env[0] == '1') {
-                    round(T{}, std::integral_constant<int, 11>{}, 21u, 11u);
-                    round(F{}, std::integral_constant<int, 11>{}, 10u, 11u);
-                    round(F{}, std::integral_constant<int, 11>{}, 0u, 10u);  // (the low 10 bits: bins 1024.. stay empty)
-                } else {
-                    // one round over k_pick_split's linear bins, then the chosen bin's keys collected per (node, rank) -- b_scan /
-                    // b_flags are free until k_flags_scan -- and the rank picked among them
-                    hipLaunchKernelGGL((k_select_hist<true, 11, true>), dim3(hblocks), dim3(256), 0, stream, X, d, perm, ws.b_vals.as<float>(), n, hchunk,
-                                       node_of, remap, lvl_split, na, 21u, ws.b_hist.as<uint32_t>(), 11u);
-                    hipLaunchKernelGGL((k_select_pick<true, 11>), dim3(ub_nodes * 2), dim3(64), 0, stream, lvl_split, lvp, na, 21u, ws.b_hist.as<uint32_t>());
-                    uint32_t *cnt = ws.b_hist.as<uint32_t>() + (size_t)wmax * 2 * hist_bins;
-                    hipLaunchKernelGGL(k_select_collect, dim3(hblocks), dim3(256), 0, stream, ws.b_vals.as<float>(), n, hchunk, node_of, remap, lvl_split, na,
-                                       ws.b_scan.as<uint32_t>(), ws.b_flags.as<uint32_t>(), cnt);
-                    hipLaunchKernelGGL(k_select_final, dim3(ub_nodes * 2), dim3(1024), 0, stream, lvl_split, lvp, na, ws.b_scan.as<uint32_t>(),
-                                       ws.b_flags.as<uint32_t>(), cnt);
-                }
+                // one round over k_pick_split's linear bins, then the chosen bin's keys collected per (node, rank) -- b_scan /
+                // b_flags are free until k_flags_scan -- and the rank picked among them
+                hipLaunchKernelGGL((k_select_hist<true, 11, true>), dim3(hblocks), dim3(256), 0, stream, X, d, perm, ws.b_vals.as<float>(), n, hchunk,
+                                   node_of, remap, lvl_split, na, 21u, ws.b_hist.as<uint32_t>(), 11u);
+                hipLaunchKernelGGL((k_select_pick<true, 11>), dim3(ub_nodes * 2), dim3(64), 0, stream, lvl_split, lvp, na, 21u, ws.b_hist.as<uint32_t>());
+                uint32_t *cnt = ws.b_hist.as<uint32_t>() + (size_t)wmax * 2 * hist_bins;
+                hipLaunchKernelGGL(k_select_collect, dim3(hblocks), dim3(256), 0, stream, ws.b_vals.as<float>(), n, hchunk, node_of, remap, lvl_split, na,
+                                   ws.b_scan.as<uint32_t>(), ws.b_flags.as<uint32_t>(), cnt);
+                hipLaunchKernelGGL(k_select_final, dim3(ub_nodes * 2), dim3(1024), 0, stream, lvl_split, lvp, na, ws.b_scan.as<uint32_t>(),
+                                   ws.b_flags.as<uint32_t>(), cnt);
             } else {
                 round(T{}, std::integral_constant<int, 8>{}, 24u, 8u);
                 round(F{}, std::integral_constant<int, 8>{}, 16u, 8u);
@@ -3999,10 +3360,8 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
 
     // level table -> host: node count, error flags; then the nodes
     std::vector<LevelInfo> hlv(n_levels + 1);
-    marks.mark("launched");
     VQ_HIP(hipMemcpyAsync(hlv.data(), lv, (size_t)(n_levels + 1) * sizeof(LevelInfo), hipMemcpyDeviceToHost, stream));
     VQ_HIP(hipStreamSynchronize(stream));
-    marks.mark("kernels-done");
     if (speculate) {
         bool wrong = false;
         for (uint32_t L = 0; L < n_levels && hlv[L].count; ++L) wrong = wrong || (L < ask_from ? hlv[L].n_slow != 0 : hlv[L].n_fast != 0);
@@ -4029,42 +3388,6 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
     }
     (void)levels_run;
     if (total == 0 || total > dcap) return fail(VQHIP_ERR_FAILURE, "TSVQ build produced %u nodes (bound %u)", total, dcap);
-    if (getenv("VQHIP_TSVQ_DEBUG")) {
-        uint32_t fbn[2 + 64 * 2 * 16];
-        VQ_HIP(hipMemcpyAsync(fbn, fbk, sizeof(fbn), hipMemcpyDeviceToHost, stream));
-        VQ_HIP(hipStreamSynchronize(stream));
-        fprintf(stderr, "[vqhip] tsvq build: %u re-added 64-row segments in the exact column sums\n", fbn[0]);
-        if (policy) {
-            uint32_t pol[1024];
-            VQ_HIP(hipMemcpy(pol, policy, (size_t)n_cblk * 4, hipMemcpyDeviceToHost));
-            uint32_t on = 0;
-            for (uint32_t q = 0; q < n_cblk; ++q) on += pol[q] ? 1u : 0u;
-            fprintf(stderr, "[vqhip]   sampled binade guess (1/%u rows) allowed for %u of %u column blocks\n", fs_sample, on, n_cblk);
-        }
-        for (uint32_t q = 0; q < 128; ++q) {
-            const uint32_t *c8 = fbn + 2 + q * 16;
-            if (c8[0] && use_tables && !(q & 1) && c8[7] + c8[3] + c8[14] != 0 && c8[12] == 0) {
-                fprintf(stderr, "[vqhip]   level %u %s: %u chains, %u segments parked: %u held by their own summary, %u looked up in their tables, %u outside the "
-                                "table's window or without one (%.2f %% of the parked: re-added from the parked addends); %u segments re-added in all (most in one chain %u), "
-                                "%u runs walked segment by segment\n",
-                        q / 2, (q & 1) ? "variance" : "mean", c8[0], c8[14], c8[6], c8[3], c8[4], 100.0 * c8[4] / (c8[14] ? c8[14] : 1), c8[1], c8[2], c8[5]);
-                fprintf(stderr, "[vqhip]     core cycles per chain (average; longest %.0f k): %.0f k, of which %u items off the fast path %.0f k (table misses "
-                                "%.0f k, %.0f each), staging chunks %.0f k\n",
-                        c8[13] * 64.0 / 1e3, c8[8] * 64.0 / c8[0] / 1e3, c8[7] / c8[0], c8[9] * 64.0 / c8[0] / 1e3, c8[10] * 64.0 / c8[0] / 1e3,
-                        c8[10] * 64.0 / (c8[4] ? c8[4] : 1), c8[11] * 64.0 / c8[0] / 1e3);
-                continue;
-            }
-            if (c8[0])
-                fprintf(stderr, "[vqhip]   level %u %s: %u chains, %u segments re-added (most in one chain %u): unusable summary %u, "
-                                "other binade than guessed %u, prefix leaves the binade %u, sum not normal %u; %u gathered (not parked)\n",
-                        q / 2, (q & 1) ? "variance" : "mean", c8[0], c8[1], c8[2], c8[3], c8[4], c8[5], c8[6], c8[7]);
-            if (c8[0] && c8[12])
-                fprintf(stderr, "[vqhip]     core cycles per chain (average; longest %.0f k): %.0f k, of which in %u failing lanes %.0f k "
-                                "(%.0f per lane; wave-wide scan pass / summary fetch %.0f; re-additions %.0f per segment); %u segments parked\n",
-                        c8[13] * 64.0 / 1e3, c8[8] * 64.0 / c8[0] / 1e3, c8[12] / c8[0], c8[9] * 64.0 / c8[0] / 1e3, c8[9] * 64.0 / c8[12],
-                        c8[11] * 64.0 / c8[12], c8[10] * 64.0 / (c8[1] ? c8[1] : 1), c8[14]);
-        }
-    }
     // nodes -> host, then BFS -> pre-order (the oracle's numbering)
     const size_t cent_bytes = (size_t)total * d * 4, idx_bytes = (((size_t)total * 4) + 15) & ~(size_t)15;
     VQ_TRY(ws.ensure_host(cent_bytes + 2 * idx_bytes));
@@ -4075,7 +3398,6 @@ int tsvq_build_device(const float *X, uint64_t n64, uint32_t d, uint32_t max_dep
     VQ_HIP(hipMemcpyAsync(const_cast<int32_t *>(hl), node_left, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
     VQ_HIP(hipMemcpyAsync(const_cast<int32_t *>(hr), node_right, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
     VQ_HIP(hipStreamSynchronize(stream));
-    marks.mark("downloaded");
     std::vector<int32_t> order;  // pre-order list of BFS ids
     order.reserve(total);
     std::vector<int32_t> stack = {0};

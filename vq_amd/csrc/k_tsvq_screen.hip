@@ -10,12 +10,11 @@
 // (mu = root centroid, so |y| and |a| are small and the error bound is tight), with
 // w = c_l - c_r, b = |a_l|^2 - |a_r|^2 prepared per node on the host in f64.  A row continues
 // while |delta^| > T(row, node) (DESIGN.md 4.4 "descent soundness"); otherwise (row, node) goes to
-// a work list and k_tsvq_continue finishes it from that node in the reference's arithmetic.
+// a work list and the continuation finishes it from that node in the reference's arithmetic.
 //
 // Mapping: 8 lanes per row, each lane keeps its D/8 values of y in registers for the whole
 // descent; the tree's w vectors live in LDS (130 KB at depth 8, D = 128).
 #include <cstdint>
-#include <cstdlib>
 
 #include "common.hpp"
 #include "kernels.hpp"
@@ -354,28 +353,6 @@ __device__ __forceinline__ void tsvq_continue_entries(const uint2 *wl, const uin
     }
 }
 
-// COS: the two running sums are the dot products x.c_l, x.c_r (same order), the row's own squared norm is summed
-// once before the walk through the same lane chain
-template <int D, int MODE>
-__global__ __launch_bounds__(256) void k_tsvq_continue(const float *__restrict__ X,
-                                                       const float *__restrict__ centroids,
-                                                       const float *__restrict__ cnorm,
-                                                       const int32_t *__restrict__ left,
-                                                       const int32_t *__restrict__ right, int euclid,
-                                                       const int32_t *__restrict__ slot_node,
-                                                       const uint2 *__restrict__ wl,
-                                                       const uint32_t *__restrict__ wl_count, uint32_t d_real,
-                                                       int32_t *__restrict__ leaf_out, const uint4 *__restrict__ table16,
-                                                       uint4 *__restrict__ f16_out, const float *__restrict__ w_g,
-                                                       const int4 *__restrict__ info_g, const int32_t *__restrict__ node_slot,
-                                                       const float *__restrict__ mu_g, float R, float coef_a, float coef_b,
-                                                       uint32_t *__restrict__ clear_next) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *clear_next = 0u;  // the next call's counter (nobody reads or appends to it in this call)
-    tsvq_continue_entries<D, MODE>(wl, *wl_count, (blockIdx.x * 256 + threadIdx.x) >> 4, (gridDim.x * 256) >> 4, threadIdx.x & 63, X,
-                                   centroids, cnorm, left, right, euclid, slot_node, d_real, leaf_out, table16, f16_out, w_g, info_g,
-                                   node_slot, mu_g, R, coef_a, coef_b);
-}
-
 // WAVES per workgroup: 16 while a row's registers (3 x D/8 floats) fit 128 VGPRs, 8 or 4 for the long rows
 //
 // COS (Distance::CosineDistance, src/core/distance.rs:95-118): a slot holds the two UNIT vectors c_l/|c_l|, c_r/|c_r|
@@ -399,9 +376,9 @@ __global__ __launch_bounds__(256) void k_tsvq_continue(const float *__restrict__
 // round trip before its first level.  Without the path (the usual case: depth <= 8 at d = 128) the rows travel while the
 // descent runs.
 // FOLD (round 6): a wave finishes its OWN undecided rows -- tsvq_continue_entries over its list in LDS, four entries at a
-// time -- when its tiles are done (or the list is full), instead of flushing them to a global list for k_tsvq_continue: the
-// pass is one kernel (the continuation's launch, its ramp over 3000 entries and the gap in front of it were 18 of
-// 181 us at C4).  A wave holds ~0.7 entries on uniform rows; the loads of the continuation sit behind the tile loop
+// time -- when its tiles are done (or the list is full), instead of flushing them to a global list for a second
+// continuation kernel: the pass is one kernel (that kernel's launch, its ramp over 3000 entries and the gap in front of it
+// were 18 of 181 us at C4; the two-kernel form was removed).  Without FOLD the list goes to k_tsvq_continue_any.  A wave holds ~0.7 entries on uniform rows; the loads of the continuation sit behind the tile loop
 // (a break out of it when the list is full), so the descent's own waits are the ones it always had.
 template <int D, int LPR, int WAVES, int MODE, bool DEEP, bool FOLD = false>
 __global__ __launch_bounds__(WAVES * 64) void k_tsvq_screen_descend(
@@ -634,8 +611,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_tsvq_screen_descend(
     }
 }
 
-// the same continuation for a dimension without a k_tsvq_continue instantiation (padded screen widths): one lane per
-// entry, run-time-length loops in the reference's order; the entries are few
+// the continuation for d < 32, which rides on the 32-wide screen and which tsvq_continue_entries does not serve: one lane
+// per entry, run-time-length loops in the reference's order; the entries are few
 __global__ __launch_bounds__(256) void k_tsvq_continue_any(const float *__restrict__ X, uint32_t d,
                                                            const float *__restrict__ centroids,
                                                            const float *__restrict__ cnorm,
@@ -701,18 +678,6 @@ __global__ __launch_bounds__(256) void k_tsvq_continue_any(const float *__restri
             for (uint32_t q = 0; q < pieces; ++q) f16_out[(size_t)ent.x * pieces + q] = table16[(size_t)node * pieces + q];
         }
     }
-}
-
-template <int D, int MODE>
-static int launch_continue(const float *X, const float *centroids, const float *cnorm, const int32_t *left,
-                           const int32_t *right, int euclid, const TsvqScreen &s, int32_t *leaf, hipStream_t stream,
-                           uint32_t d_real, const uint4 *table16, uint4 *f16_out, uint32_t *count, uint32_t *clear_next) {
-    const bool rescreen = s.node_slot != nullptr;
-    hipLaunchKernelGGL((k_tsvq_continue<D, MODE>), dim3(1024), dim3(256), 0, stream, X, centroids, cnorm, left, right, euclid,
-                       s.slot_node, s.wl, count, d_real, leaf, table16, f16_out, rescreen ? s.w : nullptr,
-                       rescreen ? s.info : nullptr, rescreen ? s.node_slot : nullptr, s.mu, s.R, s.coef_a, s.coef_b, clear_next);
-    VQ_LAUNCH_CHECK("k_tsvq_continue");
-    return VQHIP_OK;
 }
 
 template <int D, int LPR, int MODE, bool FOLD>
@@ -785,18 +750,16 @@ int launch_tsvq_screen_encode(const float *X, uint64_t n, uint32_t d, const floa
     const int euclid = metric == VQHIP_EUCLIDEAN ? 1 : 0;
     const int mode = metric == VQHIP_COSINE ? kScrCos : metric == VQHIP_MANHATTAN ? kScrMan : kScrL2;
     const uint32_t dp = tsvq_screen_width(d);  // instantiated width serving d (d itself, or the next one up: zero padding)
-    // one kernel: the descent finishes its own undecided rows (FOLD) wherever k_tsvq_continue has an instantiation for the
-    // width (VQHIP_TSVQ_FOLD=0: the two-kernel form, for A/B)
-    static const char *fold_env = getenv("VQHIP_TSVQ_FOLD");
-    const bool fold_on = !(fold_env && fold_env[0] == '0');
+    // one kernel: the descent finishes its own undecided rows (FOLD) wherever tsvq_continue_entries has an instantiation
+    // for the width; d < 32 (padded to 32) flushes them to k_tsvq_continue_any below
     const TsvqCont ct{centroids, cnorm, left, right, s.slot_node, s.node_slot, euclid, clear_next};
 #define VQ_TSVQ_DM(DV, MV)                                                                         \
-    if ((DV >= 64 || d == DV) && fold_on) {                                                        \
+    if constexpr (DV >= 64) {                                                                      \
+        VQ_TRY((launch_screen<DV, 8, MV, true>(X, n, d, s, stream, leaf, table16, f16_out, count, ct)));   \
+    } else if (d == DV) {                                                                          \
         VQ_TRY((launch_screen<DV, 8, MV, true>(X, n, d, s, stream, leaf, table16, f16_out, count, ct)));   \
     } else {                                                                                       \
         VQ_TRY((launch_screen<DV, 8, MV, false>(X, n, d, s, stream, leaf, table16, f16_out, count, ct)));  \
-        if (DV >= 64 || d == DV)                                                                   \
-            VQ_TRY((launch_continue<DV, MV>(X, centroids, cnorm, left, right, euclid, s, leaf, stream, d, table16, f16_out, count, clear_next))); \
     }
 #define VQ_TSVQ_D(DV)                                                                              \
     case DV:                                                                                       \
@@ -815,7 +778,7 @@ int launch_tsvq_screen_encode(const float *X, uint64_t n, uint32_t d, const floa
     }
 #undef VQ_TSVQ_D
 #undef VQ_TSVQ_DM
-    if (d != dp && dp < 64) {  // d < 32 (8-byte pieces in k_tsvq_continue): the run-time-length kernel
+    if (d != dp && dp < 64) {  // d < 32 (8-byte pieces in tsvq_continue_entries): the run-time-length kernel
         hipLaunchKernelGGL(k_tsvq_continue_any, dim3(256), dim3(256), 0, stream, X, d, centroids, cnorm, left, right, euclid,
                            mode, s.slot_node, s.wl, count, leaf, table16, f16_out, clear_next);
         VQ_LAUNCH_CHECK("k_tsvq_continue_any");
