@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+import ref_centroids as RC
 from vq_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -116,6 +117,7 @@ def test_c2_lloyd_step_all_rows(oracle):
         assert bool(changed[s]) == ch_ref
         err = np.max(np.abs(c_out[s] - c1) / np.maximum(1.0, np.abs(c1)))
         assert err <= 1e-5, f"subspace {s}: centroid deviation {err:g}"
+        RC.assert_centroids(X[:, s * sd:(s + 1) * sd], a_ref, c_out[s], c1.shape[0], what=f"subspace {s}")  # f64 mean, L = c
 
 
 def test_c4_every_leaf(oracle):
@@ -211,6 +213,7 @@ def test_c2_clustered_rows_codes_and_lloyd_step(oracle):
         assert bool(changed[s]) == ch_ref
         err = np.max(np.abs(c_out[s] - c1) / np.maximum(1.0, np.abs(c1)))
         assert err <= 1e-5, f"subspace {s}: centroid deviation {err:g}"
+        RC.assert_centroids(X[:, s * sd:(s + 1) * sd], a_ref, c_out[s], c1.shape[0], what=f"subspace {s}")  # f64 mean, L = c
     enc = _lib.PQEncoder(c_out, _lib.SQUARED_EUCLIDEAN)
     codes = torch.empty((n, m), dtype=torch.uint8, device="cuda")
     enc.encode_device(Xd.data_ptr(), n, codes.data_ptr(), None)
@@ -253,6 +256,7 @@ def test_c2_normal_rows_codes_and_lloyd_step(oracle):
         assert bool(changed[s]) == ch_ref
         err = np.max(np.abs(c_out[s] - c1) / np.maximum(1.0, np.abs(c1)))
         assert err <= 1e-5, f"subspace {s}: centroid deviation {err:g}"
+        RC.assert_centroids(X[:, s * sd:(s + 1) * sd], a_ref, c_out[s], c1.shape[0], what=f"subspace {s}")  # f64 mean, L = c
     codes = torch.empty((n, m), dtype=torch.uint8, device="cuda")
     for lib_metric, o_metric in ((_lib.SQUARED_EUCLIDEAN, O.SQUARED_EUCLIDEAN), (_lib.COSINE, O.COSINE)):
         enc = _lib.PQEncoder(c_out, lib_metric)
@@ -298,6 +302,7 @@ def test_c2_kmeans_run_10_iterations(oracle):
         np.testing.assert_array_equal(counts[s], n_ref)
         assert bool(changed[s]) == ch_ref
         assert np.max(np.abs(c_gpu[s] - c1) / np.maximum(1.0, np.abs(c1))) <= 1e-5
+        RC.assert_centroids(xs, a_ref, c_gpu[s], c1.shape[0], what=f"subspace {s}")  # f64 mean, L = c
         # the whole trajectory: the oracle's loop from the same initial rows
         c_ref, it_ref, _ = oracle.lloyd(xs, k, iters, init[s], threads=0)
         assert it_ref == iters

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+import ref_centroids as RC
 from vq_amd import _lib
 from vq_amd.pq import ProductQuantizer, fit_codebooks
 from vq_amd.distance import Distance
@@ -164,6 +165,7 @@ def test_lloyd_step_parity(oracle, shape, kind):
         nonempty = n_ref > 0
         err = np.abs(cent[s][nonempty] - c1[nonempty]) / np.maximum(1.0, np.abs(c1[nonempty]))
         assert err.max() <= CENTROID_RTOL
+        RC.assert_centroids(X[:, s * sd:(s + 1) * sd], a_ref, cent[s], k, what=f"subspace {s}")  # f64 mean, L = c
         np.testing.assert_array_equal(cent[s][~nonempty], c0[~nonempty])
         assert bool(changed[s]) == ch_ref
     km.close()

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+import ref_centroids as RC
 from vq_amd import TSVQ, Distance, _lib
 from vq_amd.tsvq import build_tree
 
@@ -13,6 +14,8 @@ pytestmark = pytest.mark.gpu
 F = np.float32
 SCALE = int(os.environ.get("VQ_FUZZ_SCALE", "1"))  # VQ_FUZZ_SCALE=20 for a long hunt
 KINDS = ["uniform", "normal", "lattice", "clustered", "offset", "mixed_scale", "sparse", "dupes"]
+# the Lloyd fuzz tests' own extra kinds (KINDS sets which kind every existing seed draws: it stays as it is)
+LLOYD_TINY_KINDS = ["tiny", "subnormal"]
 
 
 def _draw_data(rng, n, d, kind):
@@ -33,6 +36,10 @@ def _draw_data(rng, n, d, kind):
         x = rng.standard_normal((n, d)).astype(F)
         x[rng.random((n, d)) < 0.8] = 0
         return x
+    if kind == "tiny":  # squared distances in the subnormal range
+        return (rng.standard_normal((n, d)) * 1e-20).astype(F)
+    if kind == "subnormal":  # subnormal and normal-edge values mixed in every row
+        return (rng.standard_normal((n, d)) * np.where(rng.random((n, d)) < 0.5, 1e-40, 1e-38)).astype(F)
     if kind == "dupes":  # many identical rows
         base = rng.standard_normal((max(3, n // 50), d)).astype(F)
         return base[rng.integers(0, len(base), n)]
@@ -71,6 +78,15 @@ def test_fuzz_pq_encode(oracle, seed):
 
 @pytest.mark.parametrize("seed", range(16 * SCALE))
 def test_fuzz_lloyd_step(oracle, seed):
+    _lloyd_step_case(oracle, seed)
+
+
+@pytest.mark.parametrize("seed", range(6 * SCALE))
+def test_fuzz_lloyd_step_tiny_kinds(oracle, seed):
+    _lloyd_step_case(oracle, 500 + seed, LLOYD_TINY_KINDS[seed % len(LLOYD_TINY_KINDS)])
+
+
+def _lloyd_step_case(oracle, seed, kind_override=None):
     rng = np.random.default_rng(2000 + seed)
     sd = int(rng.choice([2, 4, 6, 7, 8, 10, 12, 14, 16, 20, 24, 30, 31, 32, 40, 48, 50, 64, 70, 96, 128]))
     m = int(rng.choice([1, 2, 4, 8]))
@@ -78,6 +94,7 @@ def test_fuzz_lloyd_step(oracle, seed):
     k = int(rng.choice([2, 16, 50, 128, 230, 256, 256]))
     n = int(rng.integers(k, 6000))
     kind = KINDS[int(rng.integers(0, len(KINDS)))]
+    kind = kind_override or kind
     X = _draw_data(rng, n, d, kind)
     init = np.stack([rng.choice(n, k, replace=False) for _ in range(m)]).astype(np.uint64)
     ds = _lib.Dataset.from_host(X)
@@ -135,6 +152,15 @@ def test_fuzz_pq_encode_wide(oracle, seed):
 
 @pytest.mark.parametrize("seed", range(10 * SCALE))
 def test_fuzz_lloyd_step_wide(oracle, seed):
+    _lloyd_step_wide_case(oracle, seed)
+
+
+@pytest.mark.parametrize("seed", range(6 * SCALE))
+def test_fuzz_lloyd_step_wide_tiny_kinds(oracle, seed):
+    _lloyd_step_wide_case(oracle, 500 + seed, LLOYD_TINY_KINDS[seed % len(LLOYD_TINY_KINDS)])
+
+
+def _lloyd_step_wide_case(oracle, seed, kind_override=None):
     rng = np.random.default_rng(6000 + seed)
     sd = int(rng.choice([2, 4, 8, 12, 16, 24, 32, 48, 64, 128]))
     m = int(rng.choice([1, 2, 4]))
@@ -142,6 +168,7 @@ def test_fuzz_lloyd_step_wide(oracle, seed):
     k = int(rng.choice(WIDE_K))
     n = int(rng.integers(k, 3 * k + 2000))
     kind = KINDS[int(rng.integers(0, len(KINDS)))]
+    kind = kind_override or kind
     exact = bool(rng.random() < 0.5)
     X = _draw_data(rng, n, d, kind)
     init = np.stack([rng.choice(n, k, replace=False) for _ in range(m)]).astype(np.uint64)
@@ -169,6 +196,7 @@ def test_fuzz_lloyd_step_wide(oracle, seed):
                 err = np.abs(cent[s][ne] - c1[ne]) / scale
             fin = np.isfinite(c1[ne])
             assert (err[fin] <= 1e-5).all(), msg
+            RC.assert_centroids(X[:, s * sd:(s + 1) * sd], a_ref, cent[s], k, what=msg)  # f64 mean, L = c
     km.close()
     ds.close()
 

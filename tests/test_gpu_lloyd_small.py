@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+import ref_centroids as RC
 from vq_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -60,6 +61,7 @@ def test_step_against_the_oracle(oracle, shape):
             np.testing.assert_array_equal(counts[s], n_ref)
             assert bool(changed[s]) == ch_ref
             assert np.max(np.abs(got[s] - c1) / np.maximum(1.0, np.abs(c1))) <= 1e-5
+            RC.assert_centroids(X[:, s * sd:(s + 1) * sd], a_ref, got[s], k, R=RC.SM_ROWS, what=f"subspace {s}")
         cb = got  # the next step starts from the library's centroids on both sides
     km.close()
     ds.close()

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+import ref_centroids as RC
 from vq_amd import _lib
 from vq_amd.errors import FfiError
 from vq_amd.pq import fit_codebooks
@@ -105,10 +106,11 @@ def test_several_slots_one_gpu_fit(oracle, slots):
     km.close()
     mds.close()
     for s in range(m):
-        c1, _, n_ref, ch_ref = oracle.lloyd_step(X[:, s * sd:(s + 1) * sd], want[s], threads=0)
+        c1, a_ref, n_ref, ch_ref = oracle.lloyd_step(X[:, s * sd:(s + 1) * sd], want[s], threads=0)
         np.testing.assert_array_equal(counts[s], n_ref)
         assert bool(changed[s]) == ch_ref
         assert np.max(np.abs(got[s] - c1) / np.maximum(1.0, np.abs(c1))) <= 1e-5
+        RC.assert_centroids(X[:, s * sd:(s + 1) * sd], a_ref, got[s], c1.shape[0], what=f"subspace {s}")  # f64 mean, L = c
 
 
 def test_encode_row_blocks_over_slots(oracle):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+import ref_centroids as RC
 from vq_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -396,6 +397,7 @@ def test_lloyd_step_parity(oracle, shape, kind, engine):
         nonempty = n_ref > 0
         err = np.abs(cent[s][nonempty] - c1[nonempty]) / np.maximum(1.0, np.abs(c1[nonempty]))
         assert err.max() <= CENTROID_RTOL
+        RC.assert_centroids(X[:, s * sd:(s + 1) * sd], a_ref, cent[s], k, what=f"subspace {s}")  # f64 mean, L = c
         # empty clusters keep their centroid until the caller reseeds (vector.rs:448-452)
         np.testing.assert_array_equal(cent[s][~nonempty], c0[~nonempty])
         assert bool(changed[s]) == ch_ref

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+import ref_centroids as RC
 from vq_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -81,6 +82,7 @@ def test_piped_lloyd_step_ragged_rows(oracle, shape):
         assert bool(changed[s]) == ch_ref
         err = np.max(np.abs(c_out[s] - c1) / np.maximum(1.0, np.abs(c1)))
         assert err <= 1e-5, f"subspace {s}: centroid deviation {err:g}"
+        RC.assert_centroids(X[:, s * sd:(s + 1) * sd], a_ref, c_out[s], c1.shape[0], what=f"subspace {s}")  # f64 mean, L = c
     km.close()
     ds.close()
 

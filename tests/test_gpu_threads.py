@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+import ref_centroids as RC
 from vq_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -139,6 +140,7 @@ def test_eight_encoders_one_shared_dataset(oracle):
             assert np.array_equal(assign[:, s].astype(np.uint32), a_ref)
             assert np.array_equal(counts[s], n_ref)
             assert np.max(np.abs(cb[s] - c1) / np.maximum(1.0, np.abs(c1))) <= 1e-5
+            RC.assert_centroids(X[:, s * sd:(s + 1) * sd], a_ref, cb[s], c1.shape[0], what=f"subspace {s}")  # f64 mean, L = c
         km.close()
         ref_cb = np.stack([want[t][s][0] for s in range(m)])
         enc = _lib.PQEncoder(ref_cb, _lib.EUCLIDEAN)

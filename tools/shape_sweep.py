@@ -29,7 +29,7 @@ def timed(fn, reps=3):
     return (time.perf_counter() - t0) / reps
 
 
-def pq_case(n, d, m, k, metric):
+def pq_case(n, d, m, k, metric, step_reps=2):
     ds = _lib.Dataset.synthetic(n, d, 66, 0)
     rng = np.random.default_rng(1)
     cb = rng.random((m, k, d // m), dtype=np.float32)
@@ -39,7 +39,7 @@ def pq_case(n, d, m, k, metric):
     _, engine = _lib.last_assign_stats()
     km = _lib.KMeans(ds, m, k)
     km.init_from_rows(np.array([[(j * (n // k) + s) % n for j in range(k)] for s in range(m)], np.uint64))
-    dk = timed(lambda: km.step(), reps=2)
+    dk = timed(lambda: km.step(), reps=step_reps)
     km.close()
     enc.close()
     ds.close()
@@ -61,6 +61,10 @@ def tsvq_case(n, d, depth, name):
 
 
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["--pq"]:  # --pq n,d,m,k ...: only these PQ shapes, squared L2, 10 timed k-means steps each
+        for spec in sys.argv[2:]:
+            pq_case(*map(int, spec.split(",")), 0, step_reps=10)
+        sys.exit(0)
     for metric in (0, 1, 2, 3):
         pq_case(1_000_000, 128, 8, 256, metric)
     for (n, d, m, k) in ((1_000_000, 100, 10, 256), (1_000_000, 105, 15, 256), (1_000_000, 96, 32, 256),

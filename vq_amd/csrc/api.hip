@@ -553,6 +553,7 @@ struct vqhip_kmeans {
     int exact_update = 0;
     uint32_t fused_slabs = 0;     // > 0: partial buffers sized for the fused update (screen + list-driven slabs)
     bool sums_by_chains = false;  // sub_dim beyond the LDS update kernels: cluster sums always through launch_exact_sums
+    bool chain_update = false;    // no wave-owned accumulate for this shape / row alignment: the unfused update's sums through launch_exact_sums
     bool accumulated = false;
     uint32_t *counts_host = nullptr;   // pinned [m*k]
     uint32_t *changed_host = nullptr;  // pinned [m]
@@ -1317,6 +1318,9 @@ int vqhip_kmeans_create(const vqhip_dataset *ds, uint32_t m, uint32_t k, vqhip_k
         }
         VQ_TRY(km->partial_sums.alloc(sums_b));
         VQ_TRY(km->partial_counts.alloc(cnt_b));
+        // the LDS-atomic accumulate adds in whatever order its atomics land: where no wave-owned kernel serves the shape,
+        // the reference-order chains give the same bits every run (k beyond their limit keeps the atomic kernel)
+        km->chain_update = !accumulate_owned(km->plan, ds->X, ds->d) && exact_sums_supported(k);
     }
     VQ_TRY(km->slab.alloc((size_t)m * k * (sd + 1) * 8));
     VQ_TRY(km->counts.alloc((size_t)m * k * 4));
@@ -1517,7 +1521,7 @@ static int kmeans_accumulate_enqueue(vqhip_kmeans *km, hipStream_t s, bool gated
                                           km->partial_counts.as<uint32_t>(), fused.chunks, (uint32_t)subs.size(),
                                           km->ws.sub_pos.as<int32_t>(), km->slab.as<double>(), s, fused.gate_active,
                                           fused.gate_halt, gated ? km->changed.as<uint32_t>() : nullptr));
-    } else if (km->exact_update || km->sums_by_chains) {
+    } else if (km->exact_update || km->sums_by_chains || km->chain_update) {
         size_t need = exact_sums_workspace_bytes(km->cs.m, km->cs.k, ds->n);
         VQ_TRY(km->xs_ws.ensure(need));
         VQ_TRY(launch_exact_sums(km->cs.m, km->cs.k, km->cs.sd, ds->X, ds->n, ds->d, km->codes.as<uint8_t>(), act,
@@ -1603,7 +1607,7 @@ int vqhip_kmeans_finalize(vqhip_kmeans *km, uint32_t *counts, uint8_t *changed) 
 static bool kmeans_graph_eligible(const vqhip_kmeans *km) {
     static const char *env = getenv("VQHIP_GRAPH");
     if (env && env[0] == '0') return false;
-    if (km->graph_failed || km->exact_update || km->sums_by_chains || g_prof.on) return false;
+    if (km->graph_failed || km->exact_update || km->sums_by_chains || km->chain_update || g_prof.on) return false;
     if (env && env[0] == '1') return true;
     return (uint64_t)km->ds->n * km->cs.m <= (4ull << 20);
 }

@@ -714,7 +714,10 @@ int plan_update(uint32_t m, uint32_t k, uint32_t sd, uint64_t n, UpdatePlan *p) 
         // few subspaces: the other waves of the workgroup take further parts of the rows (own slab each)
         uint32_t split = (w > 0) ? w_fit / w : 1u;
         if (split < 1) split = 1;
-        if (w * split < 2) w = 0;  // accumulators filling the LDS: one wave per workgroup, the atomic kernel's 16 waves win
+        // accumulators filling the LDS (one wave per workgroup): the k-means update sums through the reference-order chains,
+        // which ran faster here (sub_dim 96, k 256, 1M rows: a k-means step of 8.4 ms, against 17.0 ms with one owned
+        // wave per CU and 11.6 ms with the LDS-atomic kernel)
+        if (w * split < 2) w = 0;
         p->owned_row_split = split;
         p->owned_waves = w * split;
         if (w > 0) {
@@ -754,6 +757,23 @@ static int launch_owned(const UpdatePlan &p, const float *X, uint64_t n, uint32_
                        p.k, wpb, rows_per_chunk, codes, active, partial_sums, partial_counts, split);
     VQ_LAUNCH_CHECK("k_accumulate_owned");
     return VQHIP_OK;
+}
+
+// sub_dims served by launch_accumulate's wave-owned kernels, by the alignment each needs
+static bool owned_narrow_sub_dim(uint32_t sd) { return (sd >= 5 && sd <= 23 && sd % 4 != 0) || sd == 26 || sd == 30; }
+static bool owned_wide_sub_dim(uint32_t sd) {
+    switch (sd) {
+    case 4: case 8: case 12: case 16: case 20: case 24: case 28: case 32: case 36: case 40: case 44: case 48: case 52:
+    case 56: case 60: case 64: case 96: case 128: case 256: return true;
+    default: return false;
+    }
+}
+
+bool accumulate_owned(const UpdatePlan &p, const float *X, uint32_t d) {
+    if (p.owned_waves == 0) return false;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(X);
+    if (owned_narrow_sub_dim(p.sd) && (a & 7) == 0) return true;
+    return owned_wide_sub_dim(p.sd) && d % 4 == 0 && (a & 15) == 0;
 }
 
 int launch_accumulate(const UpdatePlan &p, const float *X, uint64_t n, uint32_t d,
@@ -1135,6 +1155,8 @@ __global__ __launch_bounds__(64) void k_chain_sums(const float *__restrict__ X, 
 }
 
 }  // namespace
+
+bool exact_sums_supported(uint32_t k) { return k <= kXsMaxK; }
 
 size_t exact_sums_workspace_bytes(uint32_t m, uint32_t k, uint64_t n) {
     // members [m][n] | chunk offsets [chunks][m][k] | start [m][k + 1] | totals [m][k] | block sums [m][k][8]

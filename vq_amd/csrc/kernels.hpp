@@ -138,6 +138,9 @@ struct UpdatePlan {
 };
 int plan_update(uint32_t m, uint32_t k, uint32_t sd, uint64_t n, UpdatePlan *plan);
 
+// true when launch_accumulate adds the rows with a wave-owned kernel (ascending row order inside a cluster, the same
+// bits every run); the k-means update sends every other shape with k <= 16384 to launch_exact_sums
+bool accumulate_owned(const UpdatePlan &p, const float *X, uint32_t d);
 // per-workgroup LDS accumulation of sums/counts by code -> partial slabs
 int launch_accumulate(const UpdatePlan &p, const float *X, uint64_t n, uint32_t d,
                       const uint8_t *codes, const uint8_t *active, float *partial_sums,
@@ -162,6 +165,7 @@ int launch_exact_sums(uint32_t m, uint32_t k, uint32_t sd, const float *X, uint6
                       const uint8_t *codes, const uint8_t *active, void *workspace,
                       size_t workspace_bytes, double *slab, hipStream_t stream);
 size_t exact_sums_workspace_bytes(uint32_t m, uint32_t k, uint64_t n);
+bool exact_sums_supported(uint32_t k);  // k <= 16384
 // means + 1e-6 convergence test; exact_div: slab sums are f32-exact values -> f32 divide
 int launch_finalize(uint32_t m, uint32_t k, uint32_t sd, const double *slab, const uint8_t *active,
                     float *centroids, uint32_t *counts, uint32_t *changed, int exact_div,
