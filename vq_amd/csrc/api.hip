@@ -752,58 +752,111 @@ static int spin_wait(hipStream_t s) {
     return VQHIP_OK;
 }
 
-// Host form of a stateless elementwise map (SQ / BQ): count elements of in_sz bytes in -> count of out_sz bytes out,
-// `launch(dev_in, dev_out, count, stream)` enqueueing the kernel.  A per-vector call (both sides <= 64 KB) stages
-// through a call-owned pinned, device-mapped buffer and one launch (the kernel reads and writes host memory); a batch
-// large enough for the transfer lanes goes through them in chunks; anything between copies in, launches, copies out.
-constexpr size_t kElementwiseSmallBytes = 65536;
-template <class Launch>
-static int host_elementwise(const void *in, size_t in_sz, void *out, size_t out_sz, uint64_t count, Launch launch) {
-    const size_t in_b = (size_t)count * in_sz, out_b = (size_t)count * out_sz;
-    const size_t out_off = (in_b + 15) & ~(size_t)15;
-    if (out_off + out_b <= kElementwiseSmallBytes) {
-        hipStream_t s;
+// One rule carries a caller's host rows through a device-form launch and back, for every host form with tiers (PQ and
+// TSVQ encode, the SQ / BQ maps):
+//   * per-vector: a call the caller judges tiny stages through a call-owned pinned, device-mapped buffer (input, then the
+//     outputs at 16-byte-aligned offsets), makes one launch that reads and writes host memory, and polls;
+//   * transfer lanes: a batch of kXferMinBytes and more whose results are at least a quarter of its input
+//     (xfer_lanes_pay) goes through run_lanes in chunks of kXferChunkBytes of input;
+//   * one stream: anything else, in passes of at most 1 GiB of input through the buffers the caller names.
+// A handle's call passes its Entry: the handle is given back before the per-vector launch and before the lanes (which
+// take it per chunk through the device form), and the one-stream passes leave the stream synchronised.
+// Both launches are `launch(dev_in, rows, dev_out0, dev_out1, stream)`; dev_out1 is null when out1 is.
+enum class XferTier { kVector, kLanes, kStream };
+struct HostBatch {
+    const void *in;
+    size_t in_b;     // bytes per row (SQ / BQ: per element); out0_b and out1_b likewise
+    void *out0;      // null: still written on the device (the launch needs it), not copied back
+    size_t out0_b;
+    void *out1;      // null: not produced
+    size_t out1_b;
+    uint64_t rows;
+    uint64_t grain;  // chunks hold a multiple of this many rows
+    size_t out0_off() const { return ((size_t)rows * in_b + 15) & ~(size_t)15; }
+    size_t out1_off() const { return out0_off() + (((size_t)rows * out0_b + 15) & ~(size_t)15); }
+    size_t stage_bytes() const { return out1 ? out1_off() + (size_t)rows * out1_b : out0_off() + (size_t)rows * out0_b; }
+};
+constexpr size_t kElementwiseSmallBytes = 65536;  // SQ / BQ: per-vector while the staging fits this
+
+template <class VecLaunch, class ChunkLaunch>
+static int host_batch(const HostBatch &b, Entry *entry, bool per_vector, VecLaunch vec_launch, ChunkLaunch chunk_launch,
+                      DevBuf &buf_in, DevBuf &buf_out0, DevBuf &buf_out1, XferTier *tier = nullptr) {
+    const uint64_t n = b.rows, g = b.grain;
+    const char *in = static_cast<const char *>(b.in);
+    char *out0 = static_cast<char *>(b.out0), *out1 = static_cast<char *>(b.out1);
+    hipStream_t s;
+    if (per_vector) {
+        if (tier) *tier = XferTier::kVector;
+        if (entry) entry->release();
         VQ_TRY(current_stream(&s));
         StageLease stage;
-        VQ_TRY(stage.acquire(out_off + out_b));
-        memcpy(stage.host(), in, in_b);
-        VQ_TRY(launch(stage.dev(), stage.dev() + out_off, count, s));
+        VQ_TRY(stage.acquire(b.stage_bytes()));
+        char *hb = stage.host(), *db = stage.dev();
+        memcpy(hb, in, (size_t)n * b.in_b);
+        VQ_TRY(vec_launch(db, n, db + b.out0_off(), out1 ? db + b.out1_off() : nullptr, s));
         VQ_TRY(spin_wait(s));
-        memcpy(out, stage.host() + out_off, out_b);
+        if (out0) memcpy(out0, hb + b.out0_off(), (size_t)n * b.out0_b);
+        if (out1) memcpy(out1, hb + b.out1_off(), (size_t)n * b.out1_b);
         return VQHIP_OK;
     }
-    if (xfer_lanes_pay(in_b, out_b)) {
-        const uint64_t per = std::max<uint64_t>(16, (kXferChunkBytes / in_sz) & ~(uint64_t)15);
-        const uint64_t chunks = (count + per - 1) / per;
-        std::mutex h2d_turn;
-        return run_lanes([&](int tl, XferLane &ln, int n_lanes) -> int {
-            VQ_TRY(ln.dev_in.ensure((size_t)per * in_sz));
-            VQ_TRY(ln.dev_out.ensure((size_t)per * out_sz));
-            for (uint64_t c = (uint64_t)tl; c < chunks; c += (uint64_t)n_lanes) {
-                const uint64_t e0 = c * per, ne = std::min(per, count - e0);
+    if (xfer_lanes_pay((size_t)n * b.in_b, (out0 ? (size_t)n * b.out0_b : 0) + (out1 ? (size_t)n * b.out1_b : 0))) {
+        if (entry) {
+            VQ_TRY(entry->stream(&s));  // (what the handle still has queued stays its tail: the lanes order behind it)
+            entry->release();
+        }
+        if (tier) *tier = XferTier::kLanes;
+        const uint64_t per = std::max<uint64_t>(g, kXferChunkBytes / b.in_b / g * g), chunks = (n + per - 1) / per;
+        std::mutex h2d_turn;  // one lane's rows on the bus at a time: the lanes stay out of phase (both copying in, then both out, overlaps nothing: 13.3 against 10.6 ms)
+        return run_lanes([&](int t, XferLane &ln, int n_lanes) -> int {
+            VQ_TRY(ln.dev_in.ensure((size_t)per * b.in_b));
+            VQ_TRY(ln.dev_out.ensure((size_t)per * b.out0_b));
+            if (out1) VQ_TRY(ln.dev_out2.ensure((size_t)per * b.out1_b));
+            for (uint64_t c = (uint64_t)t; c < chunks; c += (uint64_t)n_lanes) {
+                const uint64_t r0 = c * per, nr = std::min(per, n - r0);
                 {
                     std::lock_guard<std::mutex> turn(h2d_turn);
-                    VQ_HIP(hipMemcpyAsync(ln.dev_in.p, static_cast<const char *>(in) + e0 * in_sz, (size_t)ne * in_sz,
-                                          hipMemcpyHostToDevice, ln.stream));
+                    VQ_HIP(hipMemcpyAsync(ln.dev_in.p, in + r0 * b.in_b, (size_t)nr * b.in_b, hipMemcpyHostToDevice, ln.stream));
                     VQ_HIP(hipStreamSynchronize(ln.stream));
                 }
-                VQ_TRY(launch(ln.dev_in.as<char>(), ln.dev_out.as<char>(), ne, ln.stream));
-                VQ_HIP(hipMemcpyAsync(static_cast<char *>(out) + e0 * out_sz, ln.dev_out.p, (size_t)ne * out_sz,
-                                      hipMemcpyDeviceToHost, ln.stream));
+                VQ_TRY(chunk_launch(ln.dev_in.p, nr, ln.dev_out.p, out1 ? ln.dev_out2.p : nullptr, ln.stream));
+                if (out0) VQ_HIP(hipMemcpyAsync(out0 + r0 * b.out0_b, ln.dev_out.p, (size_t)nr * b.out0_b, hipMemcpyDeviceToHost, ln.stream));
+                if (out1) VQ_HIP(hipMemcpyAsync(out1 + r0 * b.out1_b, ln.dev_out2.p, (size_t)nr * b.out1_b, hipMemcpyDeviceToHost, ln.stream));
                 VQ_HIP(hipStreamSynchronize(ln.stream));
             }
             return VQHIP_OK;
         });
     }
-    hipStream_t s;
-    VQ_TRY(current_stream(&s));
-    DevBuf din, dout;
-    VQ_TRY(din.alloc(in_b));
-    VQ_TRY(dout.alloc(out_b));
-    VQ_HIP(hipMemcpyAsync(din.p, in, in_b, hipMemcpyHostToDevice, s));
-    VQ_TRY(launch(din.as<char>(), dout.as<char>(), count, s));
-    VQ_HIP(hipMemcpyAsync(out, dout.p, out_b, hipMemcpyDeviceToHost, s));
-    VQ_HIP(hipStreamSynchronize(s));
+    if (tier) *tier = XferTier::kStream;
+    if (entry) VQ_TRY(entry->stream(&s));
+    else VQ_TRY(current_stream(&s));
+    const uint64_t chunk = std::min<uint64_t>(n, std::max<uint64_t>(g, (1ull << 30) / b.in_b / g * g));
+    VQ_TRY(buf_in.ensure((size_t)chunk * b.in_b));
+    VQ_TRY(buf_out0.ensure((size_t)chunk * b.out0_b));
+    if (out1) VQ_TRY(buf_out1.ensure((size_t)chunk * b.out1_b));
+    for (uint64_t r0 = 0; r0 < n; r0 += chunk) {
+        const uint64_t nr = std::min(chunk, n - r0);
+        VQ_HIP(hipMemcpyAsync(buf_in.p, in + r0 * b.in_b, (size_t)nr * b.in_b, hipMemcpyHostToDevice, s));
+        VQ_TRY(chunk_launch(buf_in.p, nr, buf_out0.p, out1 ? buf_out1.p : nullptr, s));
+        if (out0) VQ_HIP(hipMemcpyAsync(out0 + r0 * b.out0_b, buf_out0.p, (size_t)nr * b.out0_b, hipMemcpyDeviceToHost, s));
+        if (out1) VQ_HIP(hipMemcpyAsync(out1 + r0 * b.out1_b, buf_out1.p, (size_t)nr * b.out1_b, hipMemcpyDeviceToHost, s));
+        VQ_HIP(hipStreamSynchronize(s));
+    }
+    if (entry) entry->synced();
+    return VQHIP_OK;
+}
+
+// host codes (one or two bytes each, the caller's pointer at any alignment) inside [0, k)
+static int check_codes(const uint8_t *codes, uint64_t count, uint32_t k) {
+    const bool wide = code_bytes(k) == 2;
+    for (uint64_t i = 0; i < count; ++i) {
+        uint32_t c = codes[i];
+        if (wide) {
+            uint16_t w;
+            memcpy(&w, codes + 2 * i, 2);
+            c = w;
+        }
+        if (c >= k) return fail(VQHIP_ERR_INVALID_INPUT, "code %u at element %llu is outside [0, %u)", c, (unsigned long long)i, k);
+    }
     return VQHIP_OK;
 }
 
@@ -2202,101 +2255,55 @@ int vqhip_pq_encode(vqhip_pq_encoder *enc, const float *rows, uint64_t n, uint8_
     if (!rows) return fail(VQHIP_ERR_NULL_PTR, "rows is NULL");
     VQ_TRY(require_gfx950());
     Entry in(enc->sync);
-    hipStream_t s;
-    const uint32_t m = enc->cs.m, d = enc->cs.m * enc->cs.sd;
-    const size_t cw = code_bytes(enc->cs.k);  // bytes per code: 1 (k <= 256) or 2
+    const uint32_t m = enc->cs.m, k = enc->cs.k, sd = enc->cs.sd, d = m * sd;
+    const size_t cw = code_bytes(k);  // bytes per code: 1 (k <= 256) or 2
+    // per-vector calls (Quantizer::quantize): one kernel over mapped pinned memory, exact arithmetic.  The kernel reads
+    // only what an encoder never changes after its first use (codebooks, centroid norms), and the staging belongs to the
+    // call: the handle is given back before the launch, so calls from many threads on one encoder (`quantize(&self)` on
+    // a Sync type, src/pq.rs:39-45) run side by side on their threads' streams, with no order behind the handle's queued
+    // batch work once the images are known to be complete.
     const bool small = n <= kSmallRows;
-    // (the per-vector path needs no order behind the handle's queued batch work once its images are known to be complete:
-    // it shares nothing mutable with it)
-    if (small && enc->small_ready) VQ_TRY(current_stream(&s));
-    else VQ_TRY(in.stream(&s));
     if (small) {
-        // per-vector calls (Quantizer::quantize): one kernel over mapped pinned memory, exact arithmetic.  The kernel
-        // reads only what an encoder never changes after its first use (codebooks, centroid norms), and the staging
-        // belongs to the call: the handle is given back before the launch, so calls from many threads on one encoder
-        // (`quantize(&self)` on a Sync type, src/pq.rs:39-45) run side by side on their threads' streams.
-        const size_t in_b = (size_t)n * d * 4, code_b = ((size_t)n * m * cw + 15) & ~(size_t)15, f16_b = (size_t)n * d * 2;
         if (!enc->small_ready) {
             // once per encoder: s is ordered behind the handle's tail here (in.stream), so the wait also covers a prepare
             // another thread's asynchronous batch call enqueued on ITS stream; other threads' streams read the images
             // without any order from now on
+            hipStream_t s;
+            VQ_TRY(in.stream(&s));
             if (!(enc->cs.prepared && enc->cs.prepared_base)) VQ_TRY(enc->cs.prepare(s));  // centroid norms (cosine)
             VQ_HIP(hipStreamSynchronize(s));
             in.synced();
             enc->small_ready = true;
         }
-        const int metric = enc->metric;
-        const uint32_t k = enc->cs.k, sd = enc->cs.sd;
-        const float *cb = enc->cs.cb.as<float>(), *cnsqrt = enc->cs.cnsqrt.as<float>();
         enc->ws.stats_pending = false;
         enc->ws.last_engine = VQHIP_ENGINE_EXACT;
-        in.release();
-        StageLease stage;
-        VQ_TRY(stage.acquire(in_b + code_b + f16_b));
-        char *hb = stage.host(), *db = stage.dev();
-        memcpy(hb, rows, in_b);
-        VQ_TRY(launch_pq_encode_small(reinterpret_cast<const float *>(db), (uint32_t)n, d, m, k, sd, metric, cb, cnsqrt,
-                                      reinterpret_cast<uint8_t *>(db + in_b),
-                                      f16_out ? reinterpret_cast<uint16_t *>(db + in_b + code_b) : nullptr, s));
-        VQ_TRY(spin_wait(s));
-        if (codes) memcpy(codes, hb + in_b, (size_t)n * m * cw);
-        if (f16_out) memcpy(f16_out, hb + in_b + code_b, f16_b);
+    }
+    const int metric = enc->metric;
+    const float *cb = enc->cs.cb.as<float>(), *cnsqrt = enc->cs.cnsqrt.as<float>();
+    auto small_launch = [&](const void *di, uint64_t nr, void *dc, void *df, hipStream_t s) {
+        return launch_pq_encode_small(static_cast<const float *>(di), (uint32_t)nr, d, m, k, sd, metric, cb, cnsqrt,
+                                      static_cast<uint8_t *>(dc), static_cast<uint16_t *>(df), s);
+    };
+    // (the device form takes the handle itself; on a lane that is the lane's thread, on the lane's stream)
+    auto chunk_launch = [enc](const void *di, uint64_t nr, void *dc, void *df, hipStream_t) {
+        return vqhip_pq_encode_device(enc, di, nr, dc, df);
+    };
+    XferTier tier = XferTier::kStream;
+    const int rc = host_batch(HostBatch{rows, (size_t)d * 4, codes, m * cw, f16_out, (size_t)d * 2, n, 1}, &in, small,
+                              small_launch, chunk_launch, enc->xbuf, enc->codes, enc->f16buf, &tier);
+    if (tier == XferTier::kLanes) {
+        // "the most recent pass of this thread" for vqhip_last_assign_stats: the lanes' passes were this call's
+        g_last_ws = enc->ws_id;
+        std::lock_guard<std::recursive_mutex> lk(enc->sync.mu);
+        tls().last_engine = enc->ws.last_engine;
+    }
+    VQ_TRY(rc);
+    if (tier == XferTier::kVector) {
         ThreadState &st = tls();
         st.last_engine = VQHIP_ENGINE_EXACT;
         st.last_rechecked = 0;
         g_last_ws = 0;
-        return VQHIP_OK;
     }
-    if (xfer_lanes_pay((size_t)n * d * 4, (codes ? (size_t)n * m * cw : 0) + (f16_out ? (size_t)n * d * 2 : 0))) {
-        // large host batch with the f16 reconstruction coming back: alternate chunks on two lanes (see XferLane), so the
-        // results of one chunk travel while the rows of the next do.  The lanes call vqhip_pq_encode_device themselves,
-        // from their own threads: this call gives the handle back first (its lock is per thread; whatever it still has
-        // queued stays its tail) and the handle orders the lanes' launches.
-        in.release();
-        const size_t row_b = (size_t)d * 4;
-        const uint64_t per = std::max<uint64_t>(1, kXferChunkBytes / row_b), chunks = (n + per - 1) / per;
-        std::mutex h2d_turn;  // one lane's rows on the bus at a time: the lanes stay out of phase (both copying in, then both out, overlaps nothing: 13.3 against 10.6 ms)
-        const int rc_lanes = run_lanes([&](int t, XferLane &ln, int n_lanes) -> int {
-            VQ_TRY(ln.dev_in.ensure((size_t)per * row_b));
-            VQ_TRY(ln.dev_out.ensure((size_t)per * m * cw));
-            if (f16_out) VQ_TRY(ln.dev_out2.ensure((size_t)per * d * 2));
-            for (uint64_t c = (uint64_t)t; c < chunks; c += (uint64_t)n_lanes) {
-                const uint64_t r0 = c * per, nr = std::min(per, n - r0);
-                {
-                    std::lock_guard<std::mutex> turn(h2d_turn);
-                    VQ_HIP(hipMemcpyAsync(ln.dev_in.p, rows + r0 * d, (size_t)nr * row_b, hipMemcpyHostToDevice, ln.stream));
-                    VQ_HIP(hipStreamSynchronize(ln.stream));
-                }
-                VQ_TRY(vqhip_pq_encode_device(enc, ln.dev_in.p, nr, ln.dev_out.p, f16_out ? ln.dev_out2.p : nullptr));
-                if (codes) VQ_HIP(hipMemcpyAsync(codes + r0 * m * cw, ln.dev_out.p, (size_t)nr * m * cw, hipMemcpyDeviceToHost, ln.stream));
-                if (f16_out) VQ_HIP(hipMemcpyAsync(f16_out + r0 * d, ln.dev_out2.p, (size_t)nr * d * 2, hipMemcpyDeviceToHost, ln.stream));
-                VQ_HIP(hipStreamSynchronize(ln.stream));
-            }
-            return VQHIP_OK;
-        });
-        // "the most recent pass of this thread" for vqhip_last_assign_stats: the lanes' passes were this call's
-        g_last_ws = enc->ws_id;
-        {
-            std::lock_guard<std::recursive_mutex> lk(enc->sync.mu);
-            tls().last_engine = enc->ws.last_engine;
-        }
-        return rc_lanes;
-    }
-    // bounded staging: at most ~1 GiB of rows per pass
-    uint64_t chunk = std::max<uint64_t>(1, (1ull << 30) / ((uint64_t)d * 4));
-    if (chunk > n) chunk = n;
-    VQ_TRY(enc->xbuf.ensure((size_t)chunk * d * 4));
-    VQ_TRY(enc->codes.ensure((size_t)chunk * m * cw));
-    if (f16_out) VQ_TRY(enc->f16buf.ensure((size_t)chunk * d * 2));
-    for (uint64_t r0 = 0; r0 < n; r0 += chunk) {
-        const uint64_t nr = std::min(chunk, n - r0);
-        VQ_HIP(hipMemcpyAsync(enc->xbuf.p, rows + r0 * d, (size_t)nr * d * 4, hipMemcpyHostToDevice, s));
-        VQ_TRY(vqhip_pq_encode_device(enc, enc->xbuf.p, nr, enc->codes.p, f16_out ? enc->f16buf.p : nullptr));
-        if (codes) VQ_HIP(hipMemcpyAsync(codes + r0 * m * cw, enc->codes.p, (size_t)nr * m * cw, hipMemcpyDeviceToHost, s));
-        if (f16_out) VQ_HIP(hipMemcpyAsync(f16_out + r0 * d, enc->f16buf.p, (size_t)nr * d * 2, hipMemcpyDeviceToHost, s));
-        VQ_HIP(hipStreamSynchronize(s));
-    }
-    in.synced();
     return VQHIP_OK;
     VQ_API_END
 }
@@ -2421,11 +2428,7 @@ int vqhip_pq_adc_set_codes(vqhip_pq_encoder *enc, const uint8_t *codes, uint64_t
     if (n >= (1ull << 32)) return fail(VQHIP_ERR_INVALID_INPUT, "n must be below 2^32");
     VQ_TRY(require_gfx950());
     const uint32_t m = enc->cs.m, k = enc->cs.k, cw = code_bytes(k);
-    // the scan indexes its LDS tables by code: checked here, once, not per search
-    for (uint64_t i = 0; i < n * m; ++i) {
-        const uint32_t c = cw == 1 ? codes[i] : reinterpret_cast<const uint16_t *>(codes)[i];
-        if (c >= k) return fail(VQHIP_ERR_INVALID_INPUT, "code %u at element %llu is outside [0, %u)", c, (unsigned long long)i, k);
-    }
+    VQ_TRY(check_codes(codes, n * m, k));  // the scan indexes its LDS tables by code: checked here, once, not per search
     Entry in(enc->sync);
     hipStream_t s;
     VQ_TRY(in.stream(&s));
@@ -2503,15 +2506,7 @@ int vqhip_pq_decode(vqhip_pq_encoder *enc, const uint8_t *codes, uint64_t n, flo
     VQ_TRY(in.stream(&s));
     const uint32_t m = enc->cs.m, d = enc->cs.m * enc->cs.sd;
     const size_t cw = code_bytes(enc->cs.k);
-    for (uint64_t i = 0; i < n * m; ++i) {
-        uint32_t c = codes[i];
-        if (cw == 2) {
-            uint16_t w;
-            memcpy(&w, codes + 2 * i, 2);
-            c = w;
-        }
-        if (c >= enc->cs.k) return fail(VQHIP_ERR_INVALID_INPUT, "code %u >= k=%u", c, enc->cs.k);
-    }
+    VQ_TRY(check_codes(codes, n * m, enc->cs.k));
     VQ_TRY(enc->codes.ensure((size_t)n * m * cw));
     VQ_TRY(enc->f32buf.ensure((size_t)n * d * 4));
     VQ_HIP(hipMemcpyAsync(enc->codes.p, codes, (size_t)n * m * cw, hipMemcpyHostToDevice, s));
@@ -2572,17 +2567,23 @@ static int sqbq_encode_host(const SqbqEncodeOp &op, const float *x, uint64_t cou
     if (count == 0) return VQHIP_OK;
     if (!x || !codes) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
     VQ_TRY(require_gfx950());
-    return host_elementwise(x, 4, codes, 1, count, [&](const char *di, char *dout, uint64_t n, hipStream_t s) {
-        return launch_sqbq_encode(op, reinterpret_cast<const float *>(di), n, reinterpret_cast<uint8_t *>(dout), s);
-    });
+    const HostBatch b{x, 4, codes, 1, nullptr, 0, count, 16};
+    auto launch = [&](const void *dx, uint64_t n, void *dc, void *, hipStream_t s) {
+        return launch_sqbq_encode(op, static_cast<const float *>(dx), n, static_cast<uint8_t *>(dc), s);
+    };
+    DevBuf dx, dc;
+    return host_batch(b, nullptr, b.stage_bytes() <= kElementwiseSmallBytes, launch, launch, dx, dc, dc);
 }
 static int sqbq_decode_host(const SqbqDecodeLut &lut, const uint8_t *codes, uint64_t count, float *out) {
     if (count == 0) return VQHIP_OK;
     if (!codes || !out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
     VQ_TRY(require_gfx950());
-    return host_elementwise(codes, 1, out, 4, count, [&](const char *di, char *dout, uint64_t n, hipStream_t s) {
-        return launch_sqbq_decode(lut, reinterpret_cast<const uint8_t *>(di), n, reinterpret_cast<float *>(dout), s);
-    });
+    const HostBatch b{codes, 1, out, 4, nullptr, 0, count, 16};
+    auto launch = [&](const void *dc, uint64_t n, void *dout, void *, hipStream_t s) {
+        return launch_sqbq_decode(lut, static_cast<const uint8_t *>(dc), n, static_cast<float *>(dout), s);
+    };
+    DevBuf dc, dout;
+    return host_batch(b, nullptr, b.stage_bytes() <= kElementwiseSmallBytes, launch, launch, dc, dout, dout);
 }
 static int sqbq_encode_dev(const SqbqEncodeOp &op, const void *dev_x, uint64_t count, void *dev_codes) {
     if (count == 0) return VQHIP_OK;
@@ -3004,70 +3005,21 @@ int vqhip_tsvq_encode(vqhip_tsvq *t, const float *rows, uint64_t n, int32_t *lea
     if (!rows) return fail(VQHIP_ERR_NULL_PTR, "rows is NULL");
     VQ_TRY(require_gfx950());
     Entry in(t->sync);
-    hipStream_t s;
     const uint32_t d = t->d;
+    // per-vector calls: the kernel reads the tree only (fixed at creation, complete before the handle existed) and
+    // stages through a buffer of its own, so the handle is given back before the launch (see vqhip_pq_encode)
     const bool small = n <= kSmallRows && tsvq_small_supported(d);
-    if (small) VQ_TRY(current_stream(&s));  // nothing mutable shared with the handle's queued batch work: no order needed
-    else VQ_TRY(in.stream(&s));
-    if (small) {
-        // per-vector calls: the kernel reads the tree only (fixed at creation, complete before the handle existed) and
-        // stages through a buffer of its own, so the handle is given back before the launch (see vqhip_pq_encode)
-        const size_t in_b = (size_t)n * d * 4, leaf_b = ((size_t)n * 4 + 15) & ~(size_t)15, f16_b = (size_t)n * d * 2;
-        t->last_screened = false;
-        in.release();
-        StageLease stage;
-        VQ_TRY(stage.acquire(in_b + leaf_b + f16_b));
-        char *hb = stage.host(), *db = stage.dev();
-        memcpy(hb, rows, in_b);
-        VQ_TRY(launch_tsvq_encode_small(reinterpret_cast<const float *>(db), (uint32_t)n, d, t->metric,
-                                        t->centroids.as<float>(), t->cnorm.as<float>(), t->left.as<int32_t>(),
-                                        t->right.as<int32_t>(), reinterpret_cast<int32_t *>(db + in_b),
-                                        f16_out ? reinterpret_cast<uint16_t *>(db + in_b + leaf_b) : nullptr, s));
-        VQ_TRY(spin_wait(s));
-        if (leaf) memcpy(leaf, hb + in_b, (size_t)n * 4);
-        if (f16_out) memcpy(f16_out, hb + in_b + leaf_b, f16_b);
-        return VQHIP_OK;
-    }
-    if (xfer_lanes_pay((size_t)n * d * 4, (leaf ? (size_t)n * 4 : 0) + (f16_out ? (size_t)n * d * 2 : 0))) {  // two lanes, as vqhip_pq_encode
-        in.release();
-        const size_t row_b = (size_t)d * 4;
-        const uint64_t per = std::max<uint64_t>(1, kXferChunkBytes / row_b), chunks = (n + per - 1) / per;
-        std::mutex h2d_turn;
-        return run_lanes([&](int tl, XferLane &ln, int n_lanes) -> int {
-            VQ_TRY(ln.dev_in.ensure((size_t)per * row_b));
-            VQ_TRY(ln.dev_out.ensure((size_t)per * 4));
-            if (f16_out) VQ_TRY(ln.dev_out2.ensure((size_t)per * d * 2));
-            for (uint64_t c = (uint64_t)tl; c < chunks; c += (uint64_t)n_lanes) {
-                const uint64_t r0 = c * per, nr = std::min(per, n - r0);
-                {
-                    std::lock_guard<std::mutex> turn(h2d_turn);
-                    VQ_HIP(hipMemcpyAsync(ln.dev_in.p, rows + r0 * d, (size_t)nr * row_b, hipMemcpyHostToDevice, ln.stream));
-                    VQ_HIP(hipStreamSynchronize(ln.stream));
-                }
-                VQ_TRY(vqhip_tsvq_encode_device(t, ln.dev_in.p, nr, ln.dev_out.p, f16_out ? ln.dev_out2.p : nullptr));
-                if (leaf) VQ_HIP(hipMemcpyAsync(leaf + r0, ln.dev_out.p, (size_t)nr * 4, hipMemcpyDeviceToHost, ln.stream));
-                if (f16_out) VQ_HIP(hipMemcpyAsync(f16_out + r0 * d, ln.dev_out2.p, (size_t)nr * d * 2, hipMemcpyDeviceToHost, ln.stream));
-                VQ_HIP(hipStreamSynchronize(ln.stream));
-            }
-            return VQHIP_OK;
-        });
-    }
-    uint64_t chunk = std::max<uint64_t>(1, (1ull << 30) / ((uint64_t)d * 4));
-    if (chunk > n) chunk = n;
-    VQ_TRY(t->xbuf.ensure((size_t)chunk * d * 4));
-    DevBuf leafdev;
-    VQ_TRY(leafdev.alloc((size_t)chunk * 4));
-    if (f16_out) VQ_TRY(t->f16buf.ensure((size_t)chunk * d * 2));
-    for (uint64_t r0 = 0; r0 < n; r0 += chunk) {
-        const uint64_t nr = std::min(chunk, n - r0);
-        VQ_HIP(hipMemcpyAsync(t->xbuf.p, rows + r0 * d, (size_t)nr * d * 4, hipMemcpyHostToDevice, s));
-        VQ_TRY(vqhip_tsvq_encode_device(t, t->xbuf.p, nr, leafdev.p, f16_out ? t->f16buf.p : nullptr));
-        if (leaf) VQ_HIP(hipMemcpyAsync(leaf + r0, leafdev.p, (size_t)nr * 4, hipMemcpyDeviceToHost, s));
-        if (f16_out) VQ_HIP(hipMemcpyAsync(f16_out + r0 * d, t->f16buf.p, (size_t)nr * d * 2, hipMemcpyDeviceToHost, s));
-        VQ_HIP(hipStreamSynchronize(s));
-    }
-    in.synced();
-    return VQHIP_OK;
+    if (small) t->last_screened = false;
+    auto small_launch = [&](const void *di, uint64_t nr, void *dl, void *df, hipStream_t s) {
+        return launch_tsvq_encode_small(static_cast<const float *>(di), (uint32_t)nr, d, t->metric, t->centroids.as<float>(),
+                                        t->cnorm.as<float>(), t->left.as<int32_t>(), t->right.as<int32_t>(),
+                                        static_cast<int32_t *>(dl), static_cast<uint16_t *>(df), s);
+    };
+    auto chunk_launch = [t](const void *di, uint64_t nr, void *dl, void *df, hipStream_t) {
+        return vqhip_tsvq_encode_device(t, di, nr, dl, df);
+    };
+    return host_batch(HostBatch{rows, (size_t)d * 4, leaf, 4, f16_out, (size_t)d * 2, n, 1}, &in, small, small_launch,
+                      chunk_launch, t->xbuf, t->leafbuf, t->f16buf);
     VQ_API_END
 }
 
