@@ -728,6 +728,91 @@ class FlatIndex {
     Distance distance_;
 };
 
+// Inverted-file index over PQ codes (include/vqhip.h, vqhip_ivfpq_*): coarse centroids [nlist][dim], codebooks
+// [m][k][sub_dim], rows added as (list id, codes).  search scans only the nprobe lists nearest to a query and gives
+// (row id, ADC distance) pairs [nq][topk], nearest first; slots past the probed rows hold (0xFFFFFFFF, +inf).  The
+// constructor, add and list_sizes need no device; the arguments are checked before the device is touched.
+class IVFPQIndex {
+   public:
+    IVFPQIndex(const float *coarse, std::size_t nlist, const float *codebooks, std::size_t m, std::size_t k, std::size_t sub_dim,
+               Distance distance = Distance()) {
+        if (nlist == 0 || nlist > 65536) throw VqError::InvalidParameter("nlist", "must be between 1 and 65536");
+        if (m == 0 || k == 0 || sub_dim == 0) throw VqError::InvalidParameter("codebooks", "m, k and sub_dim must be positive");
+        if (k > 65536 || m * k > 38400) throw VqError::InvalidParameter("codebooks", "m * k must be at most 38400");
+        if (m * sub_dim > 0xFFFFFFFFu) throw VqError::InvalidParameter("codebooks", "dim must be below 2^32");
+        if (distance.kind() == Distance::CosineDistance)
+            throw VqError::InvalidParameter("distance", "cosine distance is not a sum over subspaces: no ADC form");
+        vqhip_ivfpq *ix = nullptr;
+        detail::check(vqhip_ivfpq_create(coarse, (std::uint32_t)nlist, codebooks, (std::uint32_t)m, (std::uint32_t)k,
+                                         (std::uint32_t)sub_dim, (int)distance.kind(), &ix));
+        ix_.reset(ix);
+        nlist_ = nlist;
+        m_ = m;
+        k_ = k;
+        dim_ = m * sub_dim;
+        distance_ = distance;
+    }
+    std::size_t size() const { return n_; }
+    std::size_t nlist() const { return nlist_; }
+    std::size_t dim() const { return dim_; }
+    const char *distance_metric() const { return distance_.name(); }
+
+    // rows appended in order: list_ids [n] < nlist, codes [n][m] < k (one byte per code up to k = 256, u16 above: the
+    // library's code width); returns the first new row id
+    std::size_t add(const std::uint32_t *list_ids, const void *codes, std::size_t n) {
+        if (n >= (std::size_t(1) << 32) - n_) throw VqError::InvalidParameter("codes", "an index holds at most 2^32 - 1 rows");
+        for (std::size_t i = 0; i < n; ++i)
+            if (list_ids[i] >= nlist_) throw VqError::InvalidParameter("list_ids", "a list id is outside [0, nlist)");
+        for (std::size_t e = 0; e < n * m_; ++e) {
+            const std::uint32_t c = k_ <= 256 ? static_cast<const std::uint8_t *>(codes)[e] : static_cast<const std::uint16_t *>(codes)[e];
+            if (c >= k_) throw VqError::InvalidParameter("codes", "a code is outside [0, k)");
+        }
+        const std::size_t first = n_;
+        if (n) detail::check(vqhip_ivfpq_add(ix_.get(), list_ids, codes, n));
+        n_ += n;
+        return first;
+    }
+    std::vector<std::uint64_t> list_sizes() const {
+        std::vector<std::uint64_t> s(nlist_);
+        detail::check(vqhip_ivfpq_list_sizes(ix_.get(), s.data()));
+        return s;
+    }
+
+    struct Result {
+        std::vector<std::uint32_t> idx;  // [nq][topk]
+        std::vector<float> dist;         // [nq][topk]
+    };
+    // queries [nq][dim] -> the lists each query scans [nq][nprobe], nearest first
+    std::vector<std::uint32_t> probe(const float *queries, std::size_t nq, std::size_t nprobe) const {
+        check_probe(nprobe, nq);
+        std::vector<std::uint32_t> out(nq * nprobe);
+        if (nq) detail::check(vqhip_ivfpq_probe(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, out.data()));
+        return out;
+    }
+    Result search(const float *queries, std::size_t nq, std::size_t topk, std::size_t nprobe) const {
+        check_probe(nprobe, nq);
+        if (topk == 0 || topk > 1024 || topk > n_) throw VqError::InvalidParameter("topk", "must be between 1 and min(n, 1024)");
+        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
+        if (nq)
+            detail::check(vqhip_ivfpq_search(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, (std::uint32_t)topk,
+                                             r.idx.data(), r.dist.data()));
+        return r;
+    }
+
+   private:
+    struct Del {
+        void operator()(vqhip_ivfpq *p) const { (void)vqhip_ivfpq_destroy(p); }
+    };
+    void check_probe(std::size_t nprobe, std::size_t nq) const {
+        if (nprobe == 0 || nprobe > 1024 || nprobe > nlist_)
+            throw VqError::InvalidParameter("nprobe", "must be between 1 and min(nlist, 1024)");
+        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
+    }
+    std::unique_ptr<vqhip_ivfpq, Del> ix_;
+    std::size_t n_ = 0, nlist_ = 0, m_ = 0, k_ = 0, dim_ = 0;
+    Distance distance_;
+};
+
 // analogue of vq::get_simd_backend (src/lib.rs): names the device backend
 inline std::string get_simd_backend() { return vqhip_backend(); }
 

@@ -480,6 +480,42 @@ int vqhip_flat_search_device(vqhip_flat *f, const void *dev_queries, uint32_t nq
 int vqhip_flat_rerank(vqhip_flat *f, const float *queries, uint32_t nq, const uint32_t *cand, uint32_t c,
                       uint32_t topk, uint32_t *idx_out, float *dist_out);
 
+/* ---- inverted-file PQ index: search only the probed lists (k_ivf.hip) -----------------------
+ * No reference counterpart.  An index holds coarse centroids C [nlist][dim] f32 (1 <= nlist <= 65536), PQ codebooks
+ * cb [m][k][sub_dim] (dim = m * sub_dim) and a metric: squared Euclidean, Euclidean or Manhattan (cosine is refused with
+ * VQHIP_ERR_UNSUPPORTED, as ADC refuses it; m * k <= 38400, ADC's table limit).  add appends rows: row i (ids in add
+ * order, n < 2^32 in all) gets a list id list[i] < nlist and codes[i][m] in the library's code width (one byte up to
+ * k = 256, u16 above), both checked on the host.  Several adds equal one add of the concatenation.  Non-residual: the
+ * codes encode the rows themselves, so the ADC tables are per query and a PQIndex's codes go into lists unchanged.
+ *   P(q)    = the nprobe lists vqhip_flat_search over C (same metric) returns: Distance::compute bit for bit, ordered by
+ *             (key, list id); Euclidean by the reported root, as in the flat index.  1 <= nprobe <= min(nlist, 1024).
+ *   S(q)    = { i : list[i] in P(q) }.
+ *   D(q, i) = the ADC definition (vqhip_pq_adc_search): per-subspace distance2 or L1 terms summed in subspace order, f32.
+ *   search  = the topk rows of S(q) by (key(D), row id) ascending, 1 <= topk <= min(n, 1024): NaN sorts last and is
+ *             reported as 0x7FC00000, ties go to the lower row, Euclidean orders by the squared sum and reports sqrtf.
+ *             If |S(q)| < topk the remaining slots hold idx 0xFFFFFFFF and dist +inf, after every real row.
+ *             With nprobe == nlist the result equals vqhip_pq_adc_search over the codes in row order, bit for bit.
+ *             Run-to-run deterministic.
+ * queries [nq][dim] f32, lists_out [nq][nprobe], idx / dist [nq][topk]; nq = 0 is a no-op.  create, add, info and
+ * list_sizes (sizes [nlist]) are host-only, and every parameter is checked before any device work.  The index belongs to
+ * the device current at create (when create sees no device: the one current at the first probe or search); the first
+ * probe or search builds its device state there (the flat index over C, the rows in list order), the first one after an
+ * add rebuilds it, and a call made with another device current returns VQHIP_ERR_INVALID_INPUT.  Host forms return when the results are there;
+ * search_device takes device queries and results and is asynchronous on the current stream.  One lock per handle. */
+typedef struct vqhip_ivfpq vqhip_ivfpq;
+int vqhip_ivfpq_create(const float *coarse, uint32_t nlist, const float *codebooks, uint32_t m, uint32_t k,
+                       uint32_t sub_dim, int metric, vqhip_ivfpq **out);
+int vqhip_ivfpq_destroy(vqhip_ivfpq *ix);
+int vqhip_ivfpq_add(vqhip_ivfpq *ix, const uint32_t *list_ids, const void *codes, uint64_t n);
+int vqhip_ivfpq_info(const vqhip_ivfpq *ix, uint64_t *n, uint32_t *nlist, uint32_t *dim, uint32_t *m, uint32_t *k,
+                     int *metric);
+int vqhip_ivfpq_list_sizes(vqhip_ivfpq *ix, uint64_t *sizes);
+int vqhip_ivfpq_probe(vqhip_ivfpq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t *lists_out);
+int vqhip_ivfpq_search(vqhip_ivfpq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                       uint32_t *idx_out, float *dist_out);
+int vqhip_ivfpq_search_device(vqhip_ivfpq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                              void *dev_idx, void *dev_dist);
+
 /* ---- TSVQ ----------------------------------------------------------------------------
  * build replaces TSVQNode::build (src/tsvq.rs:31-115); the tree comes back flattened in
  * pre-order (node 0 = root, left subtree, right subtree): centroids [cap][d], left/right

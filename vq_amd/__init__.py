@@ -1,6 +1,7 @@
 """vq_amd -- MI355X (gfx950) back end for the k-means codebook-training and nearest-centroid
 encode path of CogitatorTech/vq, and of its elementwise scalar / binary quantizers, behind the
-reference's own Quantizer interface, and exact k-NN search over resident rows (FlatIndex).
+reference's own Quantizer interface, exact k-NN search over resident rows (FlatIndex) and an inverted-file
+index over PQ codes (IVFPQIndex).
 
 The compute path is libvqhip.so (hand-written HIP for CDNA4, C ABI in include/vqhip.h).
 Importing the package does not need a GPU; using any quantizer does, and fails loudly
@@ -11,12 +12,13 @@ from .errors import (DimensionMismatch, EmptyInput, FfiError, InvalidData, Inval
                      VqError)
 from .bq import BinaryQuantizer
 from .flat import FlatIndex
+from .ivf import IVFPQIndex
 from .pq import ProductQuantizer, fit_codebooks
 from .sq import ScalarQuantizer
 from .tsvq import TSVQ
 
 __all__ = [
-    "Distance", "BinaryQuantizer", "FlatIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
+    "Distance", "BinaryQuantizer", "FlatIndex", "IVFPQIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
     "InvalidParameter", "InvalidData", "FfiError", "get_simd_backend",
 ]
 

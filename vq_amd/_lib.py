@@ -152,6 +152,14 @@ SIGNATURES = {
     "vqhip_flat_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
     "vqhip_flat_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
     "vqhip_flat_rerank": (C.c_int, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "vqhip_ivfpq_create": (C.c_int, [_f32p, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _vpp]),
+    "vqhip_ivfpq_destroy": (C.c_int, [_vp]),
+    "vqhip_ivfpq_add": (C.c_int, [_vp, _u32p, _vp, C.c_uint64]),
+    "vqhip_ivfpq_info": (C.c_int, [_vp, _u64p, _u32p, _u32p, _u32p, _u32p, C.POINTER(C.c_int)]),
+    "vqhip_ivfpq_list_sizes": (C.c_int, [_vp, _u64p]),
+    "vqhip_ivfpq_probe": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p]),
+    "vqhip_ivfpq_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "vqhip_ivfpq_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
     "vqhip_sq_check": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p]),
     "vqhip_sq_thresholds": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p]),
     "vqhip_sq_encode": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p, C.c_uint64, _u8p]),
@@ -764,6 +772,56 @@ class Flat(Handle):
             check(load().vqhip_flat_rerank(self.raw, ptr(q, _f32p), nq, ptr(cand, _u32p), int(c), int(topk), ptr(idx, _u32p),
                                            ptr(dist, _f32p)))
         return idx, dist
+
+
+class IVFPQ(Handle):
+    """vqhip_ivfpq: inverted-file PQ index -- coarse centroids, codebooks, rows in lists (k_ivf.hip).  Create, add and
+    list_sizes are host-only; the device state is built by the first probe or search."""
+
+    _destroy = "vqhip_ivfpq_destroy"
+
+    def __init__(self, coarse, codebooks, metric: int):
+        c = f32c(coarse)
+        cb = f32c(codebooks)
+        m, k, sd = cb.shape
+        h = C.c_void_p()
+        check(load().vqhip_ivfpq_create(ptr(c, _f32p), c.shape[0], ptr(cb, _f32p), m, k, sd, int(metric), C.byref(h)))
+        super().__init__(h)
+        self.nlist, self.m, self.k, self.sd, self.metric = c.shape[0], m, k, sd, int(metric)
+
+    def add(self, list_ids, codes):
+        lid = np.ascontiguousarray(list_ids, dtype=np.uint32)
+        c = np.ascontiguousarray(codes, dtype=code_dtype(self.k))
+        check(load().vqhip_ivfpq_add(self.raw, ptr(lid, _u32p), c.ctypes.data_as(_vp), lid.shape[0]))
+
+    def info(self):
+        n, nlist, dim, m, k, metric = (C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_int())
+        check(load().vqhip_ivfpq_info(self.raw, C.byref(n), C.byref(nlist), C.byref(dim), C.byref(m), C.byref(k),
+                                      C.byref(metric)))
+        return int(n.value), int(nlist.value), int(dim.value), int(m.value), int(k.value), int(metric.value)
+
+    def list_sizes(self) -> np.ndarray:
+        out = np.empty(self.nlist, np.uint64)
+        check(load().vqhip_ivfpq_list_sizes(self.raw, ptr(out, _u64p)))
+        return out
+
+    def probe(self, q: np.ndarray, nprobe: int) -> np.ndarray:
+        nq = q.shape[0]
+        out = np.empty((nq, nprobe), np.uint32)
+        check(load().vqhip_ivfpq_probe(self.raw, ptr(q, _f32p), nq, int(nprobe), ptr(out, _u32p)))
+        return out
+
+    def search(self, q: np.ndarray, nprobe: int, topk: int):
+        nq = q.shape[0]
+        idx = np.empty((nq, topk), np.uint32)
+        dist = np.empty((nq, topk), np.float32)
+        check(load().vqhip_ivfpq_search(self.raw, ptr(q, _f32p), nq, int(nprobe), int(topk), ptr(idx, _u32p),
+                                        ptr(dist, _f32p)))
+        return idx, dist
+
+    def search_device(self, dev_queries: int, nq: int, nprobe: int, topk: int, dev_idx: int, dev_dist: int):
+        check(load().vqhip_ivfpq_search_device(self.raw, C.c_void_p(dev_queries), int(nq), int(nprobe), int(topk),
+                                               C.c_void_p(dev_idx), C.c_void_p(dev_dist)))
 
 
 def dequantize_f16(f16) -> np.ndarray:

@@ -2869,6 +2869,280 @@ int vqhip_flat_rerank(vqhip_flat *f, const float *queries, uint32_t nq, const ui
     VQ_API_END
 }
 
+}  // extern "C"
+
+// ------------------------------------------------------------------ inverted-file PQ (k_ivf.hip) ----
+// Host state: the coarse centroids, the codebooks, and every added row's list id and codes in row order.  The device
+// state -- a flat index over the centroids, the codebooks, and the rows in list order (off / ids / codes) -- is built on
+// the current device by the first probe or search, and the list order is rebuilt there after an add (a host counting
+// sort, O(n) per rebuild, uploaded once).
+struct vqhip_ivfpq {
+    HandleSync sync;
+    uint32_t nlist = 0, m = 0, k = 0, sd = 0, dim = 0;
+    int metric = VQHIP_EUCLIDEAN;
+    std::vector<float> coarse, cb;    // [nlist][dim], [m][k][sd]
+    std::vector<uint32_t> row_list;   // [n] list id of each row
+    std::vector<uint8_t> row_codes;   // [n][m] codes, code_bytes(k) each
+    std::vector<uint64_t> sizes;      // [nlist] rows per list
+    uint64_t n = 0;
+    bool dirty = true;                     // rows added since the last upload
+    int dev = -1;                          // the device of the index's state: current at create (-1: create saw no device;
+                                           // then the first probe or search takes the current one)
+    std::vector<uint64_t> largest_prefix;  // [nlist + 1] sums of the largest list sizes (the bound on |S(q)|)
+    vqhip_flat *flat = nullptr;            // the coarse centroids on the device
+    DevBuf d_cb, d_off, d_ids, d_codes;
+    DevBuf q, probe, probe_dist, lut, bounds, pref, seg, W, state, cand, idx, out;  // per-call workspaces
+    ~vqhip_ivfpq() { delete flat; }
+};
+
+static int ivfpq_check_probe(const vqhip_ivfpq *ix, uint32_t nprobe) {
+    const uint32_t hi = std::min<uint32_t>(ix->nlist, 1024);
+    if (nprobe == 0 || nprobe > hi) return fail(VQHIP_ERR_INVALID_INPUT, "nprobe %u must be in [1, min(nlist, 1024)] = [1, %u]", nprobe, hi);
+    return VQHIP_OK;
+}
+
+static int ivfpq_check_topk(const vqhip_ivfpq *ix, uint32_t topk) {
+    if (topk == 0 || topk > 1024 || topk > ix->n)
+        return fail(VQHIP_ERR_INVALID_INPUT, "topk %u must be in [1, min(n, 1024)] (n = %llu)", topk, (unsigned long long)ix->n);
+    return VQHIP_OK;
+}
+
+// the device state, current with the host's rows (enqueued on s and waited for: the host vectors are the copies' sources)
+static int ivfpq_ready(vqhip_ivfpq *ix, hipStream_t s) {
+    if (!ix->flat) {
+        VQ_TRY(flat_create(ix->coarse.data(), hipMemcpyHostToDevice, ix->nlist, ix->dim, 0, ix->metric, &ix->flat));
+        VQ_TRY(ix->d_cb.alloc(ix->cb.size() * 4));
+        VQ_HIP(hipMemcpyAsync(ix->d_cb.p, ix->cb.data(), ix->cb.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    if (ix->dirty) {
+        const uint32_t cw = code_bytes(ix->k);
+        const size_t row_b = (size_t)ix->m * cw;
+        std::vector<uint32_t> off(ix->nlist + 1, 0), at(ix->nlist), ids(ix->n);
+        std::vector<uint8_t> codes(ix->n * row_b);
+        for (uint32_t l = 0; l < ix->nlist; ++l) off[l + 1] = off[l] + (uint32_t)ix->sizes[l];
+        std::copy(off.begin(), off.end() - 1, at.begin());
+        for (uint64_t i = 0; i < ix->n; ++i) {  // ascending row ids within each list
+            const uint32_t p = at[ix->row_list[i]]++;
+            ids[p] = (uint32_t)i;
+            memcpy(codes.data() + (size_t)p * row_b, ix->row_codes.data() + (size_t)i * row_b, row_b);
+        }
+        VQ_TRY(ix->d_off.alloc(off.size() * 4));
+        VQ_TRY(ix->d_ids.alloc(ids.size() * 4));
+        VQ_TRY(ix->d_codes.alloc(codes.size()));
+        VQ_HIP(hipMemcpyAsync(ix->d_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, s));
+        if (ix->n) {
+            VQ_HIP(hipMemcpyAsync(ix->d_ids.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, s));
+            VQ_HIP(hipMemcpyAsync(ix->d_codes.p, codes.data(), codes.size(), hipMemcpyHostToDevice, s));
+        }
+        VQ_HIP(hipStreamSynchronize(s));
+        std::vector<uint64_t> sorted(ix->sizes);
+        std::sort(sorted.begin(), sorted.end(), std::greater<uint64_t>());
+        ix->largest_prefix.assign(ix->nlist + 1, 0);
+        for (uint32_t l = 0; l < ix->nlist; ++l) ix->largest_prefix[l + 1] = ix->largest_prefix[l] + sorted[l];
+        ix->dirty = false;
+    }
+    return VQHIP_OK;
+}
+
+// every device call runs on the index's device
+static int ivfpq_device(vqhip_ivfpq *ix) {
+    int cur = 0;
+    VQ_HIP(hipGetDevice(&cur));
+    if (ix->dev < 0) ix->dev = cur;
+    if (cur != ix->dev) return fail(VQHIP_ERR_INVALID_INPUT, "the index lives on device %d, but device %d is current", ix->dev, cur);
+    return VQHIP_OK;
+}
+
+// queries_dev [nq][dim] f32 -> probe lists [nq][nprobe] on the device
+static int ivfpq_probe_enqueue(vqhip_ivfpq *ix, const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t *lists_dev,
+                               hipStream_t s) {
+    VQ_TRY(ix->probe_dist.ensure((size_t)nq * nprobe * 4));
+    return flat_search_enqueue(ix->flat, queries_dev, nq, nprobe, lists_dev, ix->probe_dist.as<float>(), s);
+}
+
+// queries_dev [nq][dim] f32 -> [nq][topk] results on the device, enqueued on s.  Batches of queries bound the workspace:
+// the distances of a batch (4 bytes per position of S(q), sized by the nprobe largest lists) under 1 GB -- or one query's
+// when that alone is more -- its tables under 256 MB, at most 1024 queries.
+static int ivfpq_search_enqueue(vqhip_ivfpq *ix, const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                                uint32_t *idx_dev, float *dist_dev, hipStream_t s) {
+    const uint64_t wstride = std::max<uint64_t>(ix->largest_prefix[nprobe], 1);
+    const uint64_t tab_b = (uint64_t)ix->m * ix->k * 4;
+    uint64_t qb = std::min<uint64_t>({(uint64_t)nq, 1024, std::max<uint64_t>(1, (1ull << 30) / (4 * wstride)),
+                                      std::max<uint64_t>(1, (256ull << 20) / tab_b)});
+    const uint32_t nb_max = (uint32_t)qb;
+    VQ_TRY(ix->probe.ensure((size_t)nb_max * nprobe * 4));
+    VQ_TRY(ix->lut.ensure((size_t)nb_max * tab_b));
+    VQ_TRY(ix->bounds.ensure((size_t)nb_max * 2 * 4));
+    VQ_TRY(ix->pref.ensure((size_t)nb_max * (nprobe + 1) * 4));
+    VQ_TRY(ix->seg.ensure((size_t)nb_max * nprobe * 4));
+    VQ_TRY(ix->W.ensure((size_t)nb_max * wstride * 4));
+    VQ_TRY(ix->state.ensure(ivf_state_bytes(nb_max)));
+    VQ_TRY(ix->cand.ensure(ivf_cand_bytes(nb_max)));
+    // expected positions per query: the mean list size times nprobe
+    const uint64_t per_q = std::max<uint64_t>(1, (uint64_t)((double)ix->n * nprobe / ix->nlist));
+    for (uint32_t q0 = 0; q0 < nq; q0 += nb_max) {
+        const uint32_t nb = std::min(nb_max, nq - q0);
+        const float *Q = queries_dev + (size_t)q0 * ix->dim;
+        VQ_TRY(ivfpq_probe_enqueue(ix, Q, nb, nprobe, ix->probe.as<uint32_t>(), s));
+        VQ_TRY(launch_adc_lut(Q, nb, ix->m, ix->k, ix->sd, ix->d_cb.as<float>(), ix->metric, ix->lut.as<float>(),
+                              ix->bounds.as<float>(), s));
+        VQ_TRY(launch_ivf_search(ix->d_codes.as<uint8_t>(), ix->d_ids.as<uint32_t>(), ix->d_off.as<uint32_t>(), ix->nlist, ix->m, ix->k,
+                                 ix->metric, ix->lut.as<float>(), ix->probe.as<uint32_t>(), nb, nprobe, topk,
+                                 ivf_chunk((uint64_t)nb * per_q), wstride, ix->W.as<float>(), ix->pref.as<uint32_t>(),
+                                 ix->seg.as<uint32_t>(), ix->bounds.as<float>(), ix->state.p,
+                                 ix->cand.as<unsigned long long>(), idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s));
+    }
+    return VQHIP_OK;
+}
+
+extern "C" {
+
+int vqhip_ivfpq_create(const float *coarse, uint32_t nlist, const float *codebooks, uint32_t m, uint32_t k, uint32_t sub_dim,
+                       int metric, vqhip_ivfpq **out) {
+    VQ_API_BEGIN
+    if (!out) return fail(VQHIP_ERR_NULL_PTR, "out is NULL");
+    *out = nullptr;
+    if (!coarse || !codebooks) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (nlist == 0 || nlist > 65536) return fail(VQHIP_ERR_INVALID_INPUT, "nlist %u must be in [1, 65536]", nlist);
+    if (m == 0 || k == 0 || sub_dim == 0) return fail(VQHIP_ERR_INVALID_INPUT, "m, k and sub_dim must be positive");
+    if (k > kMaxCentroids) return fail(VQHIP_ERR_UNSUPPORTED, "k=%u > 65536: codes are at most two bytes per subspace", k);
+    if ((uint64_t)m * sub_dim >= (1ull << 32)) return fail(VQHIP_ERR_INVALID_INPUT, "dim = m * sub_dim must be below 2^32");
+    if (metric < VQHIP_SQUARED_EUCLIDEAN || metric > VQHIP_COSINE_UNCLAMPED) return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
+    if (vq_is_cos(metric)) return fail(VQHIP_ERR_UNSUPPORTED, "cosine distance is not a sum over subspaces: no ADC form");
+    if (!adc_table_fits(m, k)) return fail_adc_table(m, k);
+    std::unique_ptr<vqhip_ivfpq> ix(new vqhip_ivfpq());
+    ix->nlist = nlist;
+    ix->m = m;
+    ix->k = k;
+    ix->sd = sub_dim;
+    ix->dim = m * sub_dim;
+    ix->metric = metric;
+    ix->coarse.assign(coarse, coarse + (size_t)nlist * ix->dim);
+    ix->cb.assign(codebooks, codebooks + (size_t)m * k * sub_dim);
+    ix->sizes.assign(nlist, 0);
+    int ndev = 0, cur = -1;  // (the device is named, not touched: the state is built by the first probe or search)
+    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && hipGetDevice(&cur) == hipSuccess) ix->dev = cur;
+    *out = ix.release();
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_ivfpq_destroy(vqhip_ivfpq *ix) {
+    delete ix;
+    return VQHIP_OK;
+}
+
+int vqhip_ivfpq_add(vqhip_ivfpq *ix, const uint32_t *list_ids, const void *codes, uint64_t n) {
+    VQ_API_BEGIN
+    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (n == 0) return VQHIP_OK;
+    if (!list_ids || !codes) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);
+    if (n >= (1ull << 32) - ix->n)
+        return fail(VQHIP_ERR_INVALID_INPUT, "the index would hold %llu + %llu rows: at most 2^32 - 1", (unsigned long long)ix->n,
+                    (unsigned long long)n);
+    for (uint64_t i = 0; i < n; ++i)
+        if (list_ids[i] >= ix->nlist)
+            return fail(VQHIP_ERR_INVALID_INPUT, "list id %u of row %llu is outside [0, %u)", list_ids[i], (unsigned long long)i, ix->nlist);
+    VQ_TRY(check_codes(reinterpret_cast<const uint8_t *>(codes), n * ix->m, ix->k));
+    const size_t row_b = (size_t)ix->m * code_bytes(ix->k);
+    ix->row_list.insert(ix->row_list.end(), list_ids, list_ids + n);
+    const uint8_t *c = reinterpret_cast<const uint8_t *>(codes);
+    ix->row_codes.insert(ix->row_codes.end(), c, c + n * row_b);
+    for (uint64_t i = 0; i < n; ++i) ++ix->sizes[list_ids[i]];
+    ix->n += n;
+    ix->dirty = true;
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_ivfpq_info(const vqhip_ivfpq *ix, uint64_t *n, uint32_t *nlist, uint32_t *dim, uint32_t *m, uint32_t *k, int *metric) {
+    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    std::lock_guard<std::recursive_mutex> lock(const_cast<vqhip_ivfpq *>(ix)->sync.mu);  // (n changes under add)
+    if (n) *n = ix->n;
+    if (nlist) *nlist = ix->nlist;
+    if (dim) *dim = ix->dim;
+    if (m) *m = ix->m;
+    if (k) *k = ix->k;
+    if (metric) *metric = ix->metric;
+    return VQHIP_OK;
+}
+
+int vqhip_ivfpq_list_sizes(vqhip_ivfpq *ix, uint64_t *sizes) {
+    VQ_API_BEGIN
+    if (!ix || !sizes) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);
+    memcpy(sizes, ix->sizes.data(), ix->sizes.size() * 8);
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_ivfpq_probe(vqhip_ivfpq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t *lists_out) {
+    VQ_API_BEGIN
+    if (!ix || !queries || !lists_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);  // (n changes under add: read under the lock)
+    VQ_TRY(ivfpq_check_probe(ix, nprobe));
+    if (nq == 0) return VQHIP_OK;
+    VQ_TRY(require_gfx950());
+    VQ_TRY(ivfpq_device(ix));
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    VQ_TRY(ivfpq_ready(ix, s));
+    VQ_TRY(ix->q.ensure((size_t)nq * ix->dim * 4));
+    VQ_TRY(ix->idx.ensure((size_t)nq * nprobe * 4));
+    VQ_HIP(hipMemcpyAsync(ix->q.p, queries, (size_t)nq * ix->dim * 4, hipMemcpyHostToDevice, s));
+    VQ_TRY(ivfpq_probe_enqueue(ix, ix->q.as<float>(), nq, nprobe, ix->idx.as<uint32_t>(), s));
+    VQ_HIP(hipMemcpyAsync(lists_out, ix->idx.p, (size_t)nq * nprobe * 4, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipStreamSynchronize(s));
+    in.synced();
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_ivfpq_search(vqhip_ivfpq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_out,
+                       float *dist_out) {
+    VQ_API_BEGIN
+    if (!ix || !queries || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);  // (n changes under add: read under the lock)
+    VQ_TRY(ivfpq_check_probe(ix, nprobe));
+    VQ_TRY(ivfpq_check_topk(ix, topk));
+    if (nq == 0) return VQHIP_OK;
+    VQ_TRY(require_gfx950());
+    VQ_TRY(ivfpq_device(ix));
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    VQ_TRY(ivfpq_ready(ix, s));
+    VQ_TRY(ix->q.ensure((size_t)nq * ix->dim * 4));
+    VQ_TRY(ix->idx.ensure((size_t)nq * topk * 4));
+    VQ_TRY(ix->out.ensure((size_t)nq * topk * 4));
+    VQ_HIP(hipMemcpyAsync(ix->q.p, queries, (size_t)nq * ix->dim * 4, hipMemcpyHostToDevice, s));
+    VQ_TRY(ivfpq_search_enqueue(ix, ix->q.as<float>(), nq, nprobe, topk, ix->idx.as<uint32_t>(), ix->out.as<float>(), s));
+    VQ_HIP(hipMemcpyAsync(idx_out, ix->idx.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipMemcpyAsync(dist_out, ix->out.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipStreamSynchronize(s));
+    in.synced();
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_ivfpq_search_device(vqhip_ivfpq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk, void *dev_idx,
+                              void *dev_dist) {
+    VQ_API_BEGIN
+    if (!ix || !dev_queries || !dev_idx || !dev_dist) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);  // (n changes under add: read under the lock)
+    VQ_TRY(ivfpq_check_probe(ix, nprobe));
+    VQ_TRY(ivfpq_check_topk(ix, topk));
+    if (nq == 0) return VQHIP_OK;
+    VQ_TRY(require_gfx950());
+    VQ_TRY(ivfpq_device(ix));
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    VQ_TRY(ivfpq_ready(ix, s));
+    return ivfpq_search_enqueue(ix, reinterpret_cast<const float *>(dev_queries), nq, nprobe, topk,
+                                reinterpret_cast<uint32_t *>(dev_idx), reinterpret_cast<float *>(dev_dist), s);
+    VQ_API_END
+}
+
 // ---------------------------------------------------------------------------- TSVQ ----
 int vqhip_tsvq_build(const vqhip_dataset *ds, uint32_t max_depth, uint32_t cap, float *centroids, int32_t *left,
                      int32_t *right, int32_t *n_nodes) {

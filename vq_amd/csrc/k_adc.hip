@@ -195,49 +195,7 @@ __global__ __launch_bounds__(256) void k_adc_lut_i(const float *__restrict__ que
     }
 }
 
-// QL consecutive table entries (QL queries' terms of one (subspace, code)) from float offset `at`
-template <uint32_t QL>
-__device__ __forceinline__ void adc_terms(const float *__restrict__ lds, uint32_t at, float (&v)[QL]) {
-    if constexpr (QL == 1) {
-        v[0] = lds[at];
-    } else if constexpr (QL == 2) {
-        const float2 a = *reinterpret_cast<const float2 *>(lds + at);
-        v[0] = a.x, v[1] = a.y;
-    } else {
-#pragma unroll
-        for (uint32_t h = 0; h < QL / 4; ++h) {
-            const float4 a = *reinterpret_cast<const float4 *>(lds + at + 4 * h);
-            v[4 * h] = a.x, v[4 * h + 1] = a.y, v[4 * h + 2] = a.z, v[4 * h + 3] = a.w;
-        }
-    }
-}
-
-// D(q, i) of QL of the batch's qb queries (those from `first` on) for row i, subspace 0 first (the order of k_adc_scan and
-// of the oracle)
-template <uint32_t QL>
-__device__ __forceinline__ void adc_row(const uint8_t *__restrict__ codes, uint64_t i, uint32_t m, uint32_t k, bool words,
-                                        const float *__restrict__ lds, uint32_t qb, uint32_t first, float (&acc)[QL]) {
-    float v[QL];
-    if (words) {  // one-byte codes, rows of whole 8-byte words
-        for (uint32_t s8 = 0; s8 < m; s8 += 8) {
-            const uint2 w = *reinterpret_cast<const uint2 *>(codes + i * m + s8);
-#pragma unroll
-            for (uint32_t b = 0; b < 8; ++b) {
-                const uint32_t s = s8 + b;
-                adc_terms<QL>(lds, (s * k + (((b < 4 ? w.x : w.y) >> (8 * (b & 3))) & 255u)) * qb + first, v);
-#pragma unroll
-                for (uint32_t qq = 0; qq < QL; ++qq) acc[qq] = (s == 0) ? v[qq] : acc[qq] + v[qq];
-            }
-        }
-    } else {
-        for (uint32_t s = 0; s < m; ++s) {
-            adc_terms<QL>(lds, (s * k + load_code(codes, i * m + s, k)) * qb + first, v);
-#pragma unroll
-            for (uint32_t qq = 0; qq < QL; ++qq) acc[qq] = (s == 0) ? v[qq] : acc[qq] + v[qq];
-        }
-    }
-}
-
+// (adc_terms / adc_row, the per-row sum over the LDS tables: topk.hpp, shared with the IVF scan)
 __device__ __forceinline__ void adc_tables_to_lds(float *__restrict__ lds, const float *__restrict__ src, uint32_t floats, uint32_t nt) {
     for (uint32_t e = 4 * threadIdx.x; e < floats; e += 4 * nt)  // (adc_tabp floats: whole 16-byte units)
         *reinterpret_cast<float4 *>(lds + e) = *reinterpret_cast<const float4 *>(src + e);
@@ -562,6 +520,17 @@ int launch_adc_search(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int 
                            idx_out_dev + (size_t)q0 * topk, dist_out_dev + (size_t)q0 * topk);
         VQ_LAUNCH_CHECK("k_adc_topk");
     }
+    return VQHIP_OK;
+}
+
+// the per-query tables t alone (the IVF search, k_ivf.hip): lut [nq][m][k]; bounds [nq][2] receives k_adc_lut's
+// float-atomic range sums (the caller's scratch: the IVF search recomputes its range in a fixed order)
+int launch_adc_lut(const float *queries_dev, uint32_t nq, uint32_t m, uint32_t k, uint32_t sd, const float *cb, int metric,
+                   float *lut, float *bounds, hipStream_t stream) {
+    if (nq == 0) return VQHIP_OK;
+    hipLaunchKernelGGL(k_adc_lut, dim3(nq, m), dim3(256), 0, stream, queries_dev, nq, m, k, sd, cb, metric == VQHIP_MANHATTAN ? 1 : 0,
+                       lut, bounds);
+    VQ_LAUNCH_CHECK("k_adc_lut");
     return VQHIP_OK;
 }
 

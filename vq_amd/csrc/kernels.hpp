@@ -263,6 +263,18 @@ int launch_adc_search_fast(const float *cb, uint32_t m, uint32_t k, uint32_t sd,
                            unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev, uint32_t *redo_dev,
                            hipStream_t stream);
 
+// the ADC tables alone, k_adc_lut over nq queries (k_adc.hip): lut [nq][m][k], bounds [nq][2] scratch
+int launch_adc_lut(const float *queries_dev, uint32_t nq, uint32_t m, uint32_t k, uint32_t sd, const float *cb, int metric,
+                   float *lut, float *bounds, hipStream_t stream);
+// inverted-file search over list-ordered PQ codes (k_ivf.hip): one batch of nb queries whose probe lists and tables are on
+// the device; W [nb][wstride] (wstride >= every query's |S(q)|), pref [nb][nprobe + 1], seg [nb][nprobe], bounds [nb][2]
+size_t ivf_state_bytes(uint32_t qb);
+size_t ivf_cand_bytes(uint32_t qb);
+uint32_t ivf_chunk(uint64_t expected_positions);
+int launch_ivf_search(const uint8_t *codes, const uint32_t *ids, const uint32_t *off, uint32_t nlist, uint32_t m, uint32_t k, int metric,
+                      const float *lut, const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk,
+                      uint64_t wstride, float *W, uint32_t *pref, uint32_t *seg, float *bounds, void *state,
+                      unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream);
 // exact k-NN search over resident rows and exact rerank of candidate lists (k_knn.hip); X [n][d] f32 (dtype 0) or f16
 // bits (dtype 1), rnorm [n] the rows' norms (cosine only, else unused)
 int launch_knn_norms(const void *X, int dtype, uint64_t n, uint32_t d, float *out, hipStream_t stream);

@@ -4,9 +4,12 @@
 //   k_adc_pick_bin      : the histogram bin that holds the topk-th smallest value
 //   k_adc_sort_out      : the candidates of a query sorted by (key, row) in LDS, the first topk out
 //   k_adc_topk          : exact radix select where the candidate cut was too dense
+//   adc_terms / adc_row : D(q, i) of one row from ADC tables in LDS, subspace 0 first -- the one operation order of the ADC
+//                         scans (k_adc.hip) and the IVF scan (k_ivf.hip)
 #pragma once
 #include "adc_plan.hpp"
 #include "common.hpp"
+#include "kernels.hpp"
 
 #pragma clang fp contract(off)
 
@@ -23,11 +26,54 @@ __device__ __forceinline__ float adc_unkey(uint32_t k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
+// QL consecutive table entries (QL queries' terms of one (subspace, code)) from float offset `at`
+template <uint32_t QL>
+__device__ __forceinline__ void adc_terms(const float *__restrict__ lds, uint32_t at, float (&v)[QL]) {
+    if constexpr (QL == 1) {
+        v[0] = lds[at];
+    } else if constexpr (QL == 2) {
+        const float2 a = *reinterpret_cast<const float2 *>(lds + at);
+        v[0] = a.x, v[1] = a.y;
+    } else {
+#pragma unroll
+        for (uint32_t h = 0; h < QL / 4; ++h) {
+            const float4 a = *reinterpret_cast<const float4 *>(lds + at + 4 * h);
+            v[4 * h] = a.x, v[4 * h + 1] = a.y, v[4 * h + 2] = a.z, v[4 * h + 3] = a.w;
+        }
+    }
+}
+
+// D(q, i) of QL of the batch's qb queries (those from `first` on) for row i, subspace 0 first (the order of k_adc_scan and
+// of the oracle)
+template <uint32_t QL>
+__device__ __forceinline__ void adc_row(const uint8_t *__restrict__ codes, uint64_t i, uint32_t m, uint32_t k, bool words,
+                                        const float *__restrict__ lds, uint32_t qb, uint32_t first, float (&acc)[QL]) {
+    float v[QL];
+    if (words) {  // one-byte codes, rows of whole 8-byte words
+        for (uint32_t s8 = 0; s8 < m; s8 += 8) {
+            const uint2 w = *reinterpret_cast<const uint2 *>(codes + i * m + s8);
+#pragma unroll
+            for (uint32_t b = 0; b < 8; ++b) {
+                const uint32_t s = s8 + b;
+                adc_terms<QL>(lds, (s * k + (((b < 4 ? w.x : w.y) >> (8 * (b & 3))) & 255u)) * qb + first, v);
+#pragma unroll
+                for (uint32_t qq = 0; qq < QL; ++qq) acc[qq] = (s == 0) ? v[qq] : acc[qq] + v[qq];
+            }
+        }
+    } else {
+        for (uint32_t s = 0; s < m; ++s) {
+            adc_terms<QL>(lds, (s * k + load_code(codes, i * m + s, k)) * qb + first, v);
+#pragma unroll
+            for (uint32_t qq = 0; qq < QL; ++qq) acc[qq] = (s == 0) ? v[qq] : acc[qq] + v[qq];
+        }
+    }
+}
+
 // (kAdcBins, the histogram bins of the candidate filter: adc_plan.hpp)
 constexpr uint32_t kAdcCand = 8192; // candidates the fast top-k path sorts in LDS
 
 // fast top-k, step 1: the bin that holds the k-th smallest value; sel[q] = {bin, candidates up to it}
-__global__ __launch_bounds__(64) void k_adc_pick_bin(const uint32_t *__restrict__ hist, uint32_t topk,
+__attribute__((unused)) __global__ __launch_bounds__(64) void k_adc_pick_bin(const uint32_t *__restrict__ hist, uint32_t topk,
                                                      uint32_t *__restrict__ sel) {
     const uint32_t q = blockIdx.x;
     if (threadIdx.x != 0) return;
@@ -41,7 +87,7 @@ __global__ __launch_bounds__(64) void k_adc_pick_bin(const uint32_t *__restrict_
 }
 
 // step 3: sort the candidates by (key, row) in LDS, emit the first topk
-__global__ __launch_bounds__(1024) void k_adc_sort_out(const unsigned long long *__restrict__ cand,
+__attribute__((unused)) __global__ __launch_bounds__(1024) void k_adc_sort_out(const unsigned long long *__restrict__ cand,
                                                        const uint32_t *__restrict__ sel, uint32_t topk, int take_sqrt,
                                                        uint32_t *__restrict__ idx_out, float *__restrict__ dist_out) {
     extern __shared__ unsigned long long sort_buf[];  // [kAdcCand]
@@ -78,7 +124,7 @@ __global__ __launch_bounds__(1024) void k_adc_sort_out(const unsigned long long 
 
 // exact top-k of one query's distances: radix select of the k-th key, ordered collection (ties by
 // row index), bitonic sort of the <= 1024 winners by (key, index)
-__global__ __launch_bounds__(1024) void k_adc_topk(const float *__restrict__ dist, uint64_t n, uint32_t topk, int take_sqrt,
+__attribute__((unused)) __global__ __launch_bounds__(1024) void k_adc_topk(const float *__restrict__ dist, uint64_t n, uint32_t topk, int take_sqrt,
                                                    const uint32_t *__restrict__ sel, uint32_t *__restrict__ idx_out,
                                                    float *__restrict__ dist_out) {
     __shared__ uint32_t hist[256];

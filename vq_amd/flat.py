@@ -141,6 +141,14 @@ def adc_then_rerank(adc_search, n: int, dim: int, queries: np.ndarray, topk: int
     """the standard PQ pipeline: `adc_search(queries, c)` for a short list of c candidates per query (default 4 topk,
     at most 1024 -- ADC's own limit -- and n), then the exact rerank of that list through the FlatIndex `rerank` over
     the same n rows.  The flat index's metric is its own (cosine allowed)."""
+    c = rerank_candidates(n, dim, topk, rerank, candidates)
+    idx, _ = adc_search(queries, c)
+    return rerank.rerank(queries, idx, topk)
+
+
+def rerank_candidates(n: int, dim: int, topk: int, rerank, candidates) -> int:
+    """the checks of a short list reranked through the FlatIndex `rerank` over the same n rows of dim: the list's length
+    (default 4 topk, at most 1024 and n)"""
     if not isinstance(rerank, FlatIndex):
         raise InvalidParameter("rerank", f"expected a FlatIndex, got {type(rerank).__name__}")
     if len(rerank) != n:
@@ -150,5 +158,4 @@ def adc_then_rerank(adc_search, n: int, dim: int, queries: np.ndarray, topk: int
     c = min(4 * topk, MAX_TOPK, n) if candidates is None else _count(candidates, "candidates")
     if not topk <= c <= min(n, MAX_TOPK):
         raise InvalidParameter("candidates", f"must be between topk and min(n, 1024), got {c}")
-    idx, _ = adc_search(queries, c)
-    return rerank.rerank(queries, idx, topk)
+    return c
