@@ -734,8 +734,9 @@ class FlatIndex {
 // constructor, add and list_sizes need no device; the arguments are checked before the device is touched.
 class IVFPQIndex {
    public:
+    // residual: the codes of a row in list l quantise x - C[l] (include/vqhip.h, VQHIP_IVF_RESIDUAL)
     IVFPQIndex(const float *coarse, std::size_t nlist, const float *codebooks, std::size_t m, std::size_t k, std::size_t sub_dim,
-               Distance distance = Distance()) {
+               Distance distance = Distance(), bool residual = false) {
         if (nlist == 0 || nlist > 65536) throw VqError::InvalidParameter("nlist", "must be between 1 and 65536");
         if (m == 0 || k == 0 || sub_dim == 0) throw VqError::InvalidParameter("codebooks", "m, k and sub_dim must be positive");
         if (k > 65536 || m * k > 38400) throw VqError::InvalidParameter("codebooks", "m * k must be at most 38400");
@@ -743,16 +744,18 @@ class IVFPQIndex {
         if (distance.kind() == Distance::CosineDistance)
             throw VqError::InvalidParameter("distance", "cosine distance is not a sum over subspaces: no ADC form");
         vqhip_ivfpq *ix = nullptr;
-        detail::check(vqhip_ivfpq_create(coarse, (std::uint32_t)nlist, codebooks, (std::uint32_t)m, (std::uint32_t)k,
-                                         (std::uint32_t)sub_dim, (int)distance.kind(), &ix));
+        detail::check(vqhip_ivfpq_create_ex(coarse, (std::uint32_t)nlist, codebooks, (std::uint32_t)m, (std::uint32_t)k,
+                                            (std::uint32_t)sub_dim, (int)distance.kind(), residual ? VQHIP_IVF_RESIDUAL : 0u, &ix));
         ix_.reset(ix);
         nlist_ = nlist;
         m_ = m;
         k_ = k;
         dim_ = m * sub_dim;
         distance_ = distance;
+        residual_ = residual;
     }
     std::size_t size() const { return n_; }
+    bool residual() const { return residual_; }
     std::size_t nlist() const { return nlist_; }
     std::size_t dim() const { return dim_; }
     const char *distance_metric() const { return distance_.name(); }
@@ -811,6 +814,7 @@ class IVFPQIndex {
     std::unique_ptr<vqhip_ivfpq, Del> ix_;
     std::size_t n_ = 0, nlist_ = 0, m_ = 0, k_ = 0, dim_ = 0;
     Distance distance_;
+    bool residual_ = false;
 };
 
 // analogue of vq::get_simd_backend (src/lib.rs): names the device backend

@@ -516,6 +516,24 @@ int vqhip_ivfpq_search(vqhip_ivfpq *ix, const float *queries, uint32_t nq, uint3
 int vqhip_ivfpq_search_device(vqhip_ivfpq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
                               void *dev_idx, void *dev_dist);
 
+/* Residual lists (IVFADC): create_ex with flags = VQHIP_IVF_RESIDUAL (unknown bits: VQHIP_ERR_INVALID_INPUT, before any
+ * device work; create is create_ex with flags 0).  The parts, the limits, P(q), S(q), the order, ties, NaN, Euclidean's
+ * sqrtf and the padding are those above; the probe does not depend on the flag.  What changes: the codes of a row in
+ * list l quantise x - C[l], so for i in list l
+ *   r       = q - C[l], element by element in f32 (one rounding each),
+ *   D(q, i) = the ADC definition at r in place of q: per subspace s, diff = r[t] - cb[s][j][t] for t ascending,
+ *             accumulated from -0.0 (squared terms) or 0.0 (Manhattan, |diff|) with no contraction, the terms summed in
+ *             subspace order in f32.
+ * When every C[l] is the zero vector, r == q bit for bit (-0.0, inf and NaN included) and the result equals the
+ * non-residual index's with the same codebooks and rows.  The device state also holds C; a search builds one table per
+ * (query, probed list), batches of queries keep those under 256 MB (a batch of one query always runs).
+ * vqhip_ivfpq_flags reports the flags given at create; add, probe, search, search_device, info, list_sizes and destroy
+ * serve both kinds. */
+#define VQHIP_IVF_RESIDUAL 1u
+int vqhip_ivfpq_create_ex(const float *coarse, uint32_t nlist, const float *codebooks, uint32_t m, uint32_t k,
+                          uint32_t sub_dim, int metric, uint32_t flags, vqhip_ivfpq **out);
+int vqhip_ivfpq_flags(const vqhip_ivfpq *ix, uint32_t *flags);
+
 /* ---- TSVQ ----------------------------------------------------------------------------
  * build replaces TSVQNode::build (src/tsvq.rs:31-115); the tree comes back flattened in
  * pre-order (node 0 = root, left subtree, right subtree): centroids [cap][d], left/right

@@ -11,7 +11,12 @@ host form against PQIndex.search of the same queries (wall ms, median of --reps)
 scan and selection comes from a kernel trace of --quick (rocprofv3 --kernel-trace --stats).  Last: 10M x 128 at
 nprobe = 32 (lists drawn with k-means-like unevenness, random codes: the timing does not depend on them).
 
-    python tools/ivf_time.py [--reps 5] [--quick] [--out profiles/ivf/time.json]
+--residual: the same set, shapes and figures for a residual index (IVFPQIndex.train(..., residual=True): codebooks fit
+on the rows' residuals to their lists, rows stored as the codes of x - C[list]); the full ADC scan row is left out (its
+codes are residuals), and the non-residual index trained on the same rows is timed beside it at nq = 1024, nprobe 32,
+alternating the two.
+
+    python tools/ivf_time.py [--reps 5] [--quick] [--residual] [--out profiles/ivf/time.json]
 """
 import argparse
 import json
@@ -90,6 +95,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--quick", action="store_true", help="nq = 1024, nprobe = 32, topk = 10 only (for a kernel trace)")
+    ap.add_argument("--residual", action="store_true", help="a residual index (IVFADC)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     _lib.load()
@@ -106,7 +112,7 @@ def main():
 
     X, Q = clustered(1 << 20, 128, 4096, 7)
     t0 = time.perf_counter()
-    ix = vq_amd.IVFPQIndex.train(X[::4], 1024, 8, 256, max_iters=10)
+    ix = vq_amd.IVFPQIndex.train(X[::4], 1024, 8, 256, max_iters=10, residual=a.residual)
     train_s = time.perf_counter() - t0
     ix.add(X)
     sizes = ix.list_sizes().astype(np.int64)
@@ -114,7 +120,7 @@ def main():
     if a.quick:
         emit(shape(ix, flat_coarse, Q, 32, 1024, 10, a.reps, sizes))
         return
-    emit({"shape": "index", "n": len(ix), "nlist": ix.nlist, "train_s": round(train_s, 2),
+    emit({"shape": "index", "residual": ix.residual, "n": len(ix), "nlist": ix.nlist, "train_s": round(train_s, 2),
           "list_size_min": int(sizes.min()), "list_size_max": int(sizes.max()), "list_size_mean": round(float(sizes.mean()), 1)})
     flat_rows = vq_amd.FlatIndex(X)
     exact = flat_rows.search(Q, 10)[0]
@@ -123,19 +129,33 @@ def main():
         return round(float(np.mean([len(set(got[j, :10]) & set(exact[j])) / 10 for j in range(got.shape[0])])), 4)
 
     # what limits recall on this set: the full ADC scan over the same codes, and the IVF hits reranked exactly
-    pq = PQIndex(ix.codebooks, ix.codes, ix.distance)
-    r = {"shape": "recall@10 of 1024 queries against an exact FlatIndex search", "full_adc_scan": recall(pq.search(Q, 10)[0])}
+    pq = None if ix.residual else PQIndex(ix.codebooks, ix.codes, ix.distance)
+    r = {"shape": "recall@10 of 1024 queries against an exact FlatIndex search", "residual": ix.residual}
+    if pq is not None:
+        r["full_adc_scan"] = recall(pq.search(Q, 10)[0])
     for nprobe in (8, 32):
         r[f"ivf_nprobe_{nprobe}"] = recall(ix.search(Q, topk=10, nprobe=nprobe)[0])
         r[f"ivf_nprobe_{nprobe}_rerank_100"] = recall(ix.search(Q, topk=10, nprobe=nprobe, rerank=flat_rows, candidates=100)[0])
     emit(r)
     del flat_rows
+    if ix.residual:  # the non-residual index of the same rows, timed alternately with the residual one
+        plain = vq_amd.IVFPQIndex.train(X[::4], 1024, 8, 256, max_iters=10)
+        plain.add(X)
+        t = {"residual": [], "non_residual": []}
+        for _ in range(3):
+            t["residual"].append(shape(ix, flat_coarse, Q, 32, 1024, 10, a.reps, sizes)["ms"])
+            t["non_residual"].append(shape(plain, flat_coarse, Q, 32, 1024, 10, a.reps, plain.list_sizes().astype(np.int64))["ms"])
+        emit({"shape": "device form, 1024 queries, nprobe 32, topk 10: residual against non-residual (3 alternations)",
+              "residual_ms": t["residual"], "non_residual_ms": t["non_residual"],
+              "ratio": round(float(np.median(t["residual"]) / np.median(t["non_residual"])), 3)})
+        plain.close()
+        del plain
     for nprobe in (1, 8, 32, 128):
         for nq in (1, 64, 1024):
             for topk in (10, 100):
                 emit(shape(ix, flat_coarse, Q, nprobe, nq, topk, a.reps, sizes, exact[:nq]))
     # the host forms at nq = 1024 against a full ADC scan of the same codes
-    for topk in (10, 100):
+    for topk in ((10, 100) if pq is not None else ()):
         pq_ms = wall_ms(lambda: pq.search(Q, topk), a.reps)
         for nprobe in (8, 32):
             ivf_ms = wall_ms(lambda: ix.search(Q, topk=topk, nprobe=nprobe), a.reps)
@@ -147,7 +167,7 @@ def main():
     rng = np.random.default_rng(10)
     n = 10 * (1 << 20)
     w = rng.gamma(2.0, 1.0, 1024)
-    big = vq_amd.IVFPQIndex(ix.coarse_centroids, ix.codebooks)
+    big = vq_amd.IVFPQIndex(ix.coarse_centroids, ix.codebooks, residual=ix.residual)
     big.add_codes(rng.choice(1024, n, p=w / w.sum()).astype(np.uint32), rng.integers(0, 256, (n, 8), dtype=np.uint8))
     bsizes = big.list_sizes().astype(np.int64)
     for nq in (1, 64, 1024):

@@ -23,6 +23,7 @@ ERR_NULL_PTR, ERR_INVALID_INPUT, ERR_NO_DEVICE, ERR_RUNTIME, ERR_UNSUPPORTED, ER
     -1, -3, -4, -5, -6, -99)
 
 SQUARED_EUCLIDEAN, EUCLIDEAN, MANHATTAN, COSINE, COSINE_UNCLAMPED = 0, 1, 2, 3, 4
+IVF_RESIDUAL = 1  # vqhip_ivfpq_create_ex flag (include/vqhip.h VQHIP_IVF_RESIDUAL)
 ENGINE_AUTO, ENGINE_EXACT, ENGINE_MFMA, ENGINE_MFMA_BF16 = 0, 1, 2, 3
 
 _u8p = C.POINTER(C.c_uint8)
@@ -160,6 +161,9 @@ SIGNATURES = {
     "vqhip_ivfpq_probe": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p]),
     "vqhip_ivfpq_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _f32p]),
     "vqhip_ivfpq_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "vqhip_ivfpq_create_ex": (C.c_int, [_f32p, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
+                                        _vpp]),
+    "vqhip_ivfpq_flags": (C.c_int, [_vp, _u32p]),
     "vqhip_sq_check": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p]),
     "vqhip_sq_thresholds": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p]),
     "vqhip_sq_encode": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p, C.c_uint64, _u8p]),
@@ -776,18 +780,25 @@ class Flat(Handle):
 
 class IVFPQ(Handle):
     """vqhip_ivfpq: inverted-file PQ index -- coarse centroids, codebooks, rows in lists (k_ivf.hip).  Create, add and
-    list_sizes are host-only; the device state is built by the first probe or search."""
+    list_sizes are host-only; the device state is built by the first probe or search.  flags: IVF_RESIDUAL for lists
+    whose codes quantise x - C[list]."""
 
     _destroy = "vqhip_ivfpq_destroy"
 
-    def __init__(self, coarse, codebooks, metric: int):
+    def __init__(self, coarse, codebooks, metric: int, flags: int = 0):
         c = f32c(coarse)
         cb = f32c(codebooks)
         m, k, sd = cb.shape
         h = C.c_void_p()
-        check(load().vqhip_ivfpq_create(ptr(c, _f32p), c.shape[0], ptr(cb, _f32p), m, k, sd, int(metric), C.byref(h)))
+        check(load().vqhip_ivfpq_create_ex(ptr(c, _f32p), c.shape[0], ptr(cb, _f32p), m, k, sd, int(metric), int(flags),
+                                           C.byref(h)))
         super().__init__(h)
         self.nlist, self.m, self.k, self.sd, self.metric = c.shape[0], m, k, sd, int(metric)
+
+    def flags(self) -> int:
+        f = C.c_uint32()
+        check(load().vqhip_ivfpq_flags(self.raw, C.byref(f)))
+        return int(f.value)
 
     def add(self, list_ids, codes):
         lid = np.ascontiguousarray(list_ids, dtype=np.uint32)

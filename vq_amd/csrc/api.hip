@@ -2875,10 +2875,12 @@ int vqhip_flat_rerank(vqhip_flat *f, const float *queries, uint32_t nq, const ui
 // Host state: the coarse centroids, the codebooks, and every added row's list id and codes in row order.  The device
 // state -- a flat index over the centroids, the codebooks, and the rows in list order (off / ids / codes) -- is built on
 // the current device by the first probe or search, and the list order is rebuilt there after an add (a host counting
-// sort, O(n) per rebuild, uploaded once).
+// sort, O(n) per rebuild, uploaded once).  A residual index (VQHIP_IVF_RESIDUAL) also keeps the coarse centroids on the
+// device for its tables.
 struct vqhip_ivfpq {
     HandleSync sync;
     uint32_t nlist = 0, m = 0, k = 0, sd = 0, dim = 0;
+    uint32_t flags = 0;  // VQHIP_IVF_RESIDUAL: codes of x - C[list]
     int metric = VQHIP_EUCLIDEAN;
     std::vector<float> coarse, cb;    // [nlist][dim], [m][k][sd]
     std::vector<uint32_t> row_list;   // [n] list id of each row
@@ -2890,8 +2892,8 @@ struct vqhip_ivfpq {
                                            // then the first probe or search takes the current one)
     std::vector<uint64_t> largest_prefix;  // [nlist + 1] sums of the largest list sizes (the bound on |S(q)|)
     vqhip_flat *flat = nullptr;            // the coarse centroids on the device
-    DevBuf d_cb, d_off, d_ids, d_codes;
-    DevBuf q, probe, probe_dist, lut, bounds, pref, seg, W, state, cand, idx, out;  // per-call workspaces
+    DevBuf d_cb, d_off, d_ids, d_codes, d_coarse;
+    DevBuf q, probe, probe_dist, lut, bounds, pref, seg, W, state, cand, idx, out, rtab, rmm;  // per-call workspaces
     ~vqhip_ivfpq() { delete flat; }
 };
 
@@ -2913,6 +2915,10 @@ static int ivfpq_ready(vqhip_ivfpq *ix, hipStream_t s) {
         VQ_TRY(flat_create(ix->coarse.data(), hipMemcpyHostToDevice, ix->nlist, ix->dim, 0, ix->metric, &ix->flat));
         VQ_TRY(ix->d_cb.alloc(ix->cb.size() * 4));
         VQ_HIP(hipMemcpyAsync(ix->d_cb.p, ix->cb.data(), ix->cb.size() * 4, hipMemcpyHostToDevice, s));
+        if (ix->flags & VQHIP_IVF_RESIDUAL) {
+            VQ_TRY(ix->d_coarse.alloc(ix->coarse.size() * 4));
+            VQ_HIP(hipMemcpyAsync(ix->d_coarse.p, ix->coarse.data(), ix->coarse.size() * 4, hipMemcpyHostToDevice, s));
+        }
     }
     if (ix->dirty) {
         const uint32_t cw = code_bytes(ix->k);
@@ -2962,16 +2968,23 @@ static int ivfpq_probe_enqueue(vqhip_ivfpq *ix, const float *queries_dev, uint32
 
 // queries_dev [nq][dim] f32 -> [nq][topk] results on the device, enqueued on s.  Batches of queries bound the workspace:
 // the distances of a batch (4 bytes per position of S(q), sized by the nprobe largest lists) under 1 GB -- or one query's
-// when that alone is more -- its tables under 256 MB, at most 1024 queries.
+// when that alone is more -- its tables under 256 MB (a residual index: nprobe tables per query; one query's when that
+// alone is more), at most 1024 queries.
 static int ivfpq_search_enqueue(vqhip_ivfpq *ix, const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk,
                                 uint32_t *idx_dev, float *dist_dev, hipStream_t s) {
+    const bool residual = (ix->flags & VQHIP_IVF_RESIDUAL) != 0;
     const uint64_t wstride = std::max<uint64_t>(ix->largest_prefix[nprobe], 1);
-    const uint64_t tab_b = (uint64_t)ix->m * ix->k * 4;
+    const uint64_t tab_b = (uint64_t)ix->m * ix->k * 4 * (residual ? nprobe : 1);
     uint64_t qb = std::min<uint64_t>({(uint64_t)nq, 1024, std::max<uint64_t>(1, (1ull << 30) / (4 * wstride)),
                                       std::max<uint64_t>(1, (256ull << 20) / tab_b)});
     const uint32_t nb_max = (uint32_t)qb;
     VQ_TRY(ix->probe.ensure((size_t)nb_max * nprobe * 4));
-    VQ_TRY(ix->lut.ensure((size_t)nb_max * tab_b));
+    if (residual) {
+        VQ_TRY(ix->rtab.ensure(ivf_rtab_bytes(nb_max, nprobe, ix->m, ix->k)));
+        VQ_TRY(ix->rmm.ensure(ivf_rmm_bytes(nb_max, nprobe)));
+    } else {
+        VQ_TRY(ix->lut.ensure((size_t)nb_max * tab_b));
+    }
     VQ_TRY(ix->bounds.ensure((size_t)nb_max * 2 * 4));
     VQ_TRY(ix->pref.ensure((size_t)nb_max * (nprobe + 1) * 4));
     VQ_TRY(ix->seg.ensure((size_t)nb_max * nprobe * 4));
@@ -2984,6 +2997,15 @@ static int ivfpq_search_enqueue(vqhip_ivfpq *ix, const float *queries_dev, uint3
         const uint32_t nb = std::min(nb_max, nq - q0);
         const float *Q = queries_dev + (size_t)q0 * ix->dim;
         VQ_TRY(ivfpq_probe_enqueue(ix, Q, nb, nprobe, ix->probe.as<uint32_t>(), s));
+        if (residual) {
+            VQ_TRY(launch_ivf_rsearch(ix->d_codes.as<uint8_t>(), ix->d_ids.as<uint32_t>(), ix->d_off.as<uint32_t>(),
+                                      ix->d_coarse.as<float>(), ix->nlist, ix->d_cb.as<float>(), ix->m, ix->k, ix->sd, ix->metric, Q,
+                                      ix->probe.as<uint32_t>(), nb, nprobe, topk, ivf_rchunk((uint64_t)nb * per_q, ix->k), wstride,
+                                      ix->rtab.as<float>(), ix->rmm.as<float>(), ix->W.as<float>(), ix->pref.as<uint32_t>(),
+                                      ix->seg.as<uint32_t>(), ix->bounds.as<float>(), ix->state.p, ix->cand.as<unsigned long long>(),
+                                      idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s));
+            continue;
+        }
         VQ_TRY(launch_adc_lut(Q, nb, ix->m, ix->k, ix->sd, ix->d_cb.as<float>(), ix->metric, ix->lut.as<float>(),
                               ix->bounds.as<float>(), s));
         VQ_TRY(launch_ivf_search(ix->d_codes.as<uint8_t>(), ix->d_ids.as<uint32_t>(), ix->d_off.as<uint32_t>(), ix->nlist, ix->m, ix->k,
@@ -2999,9 +3021,15 @@ extern "C" {
 
 int vqhip_ivfpq_create(const float *coarse, uint32_t nlist, const float *codebooks, uint32_t m, uint32_t k, uint32_t sub_dim,
                        int metric, vqhip_ivfpq **out) {
+    return vqhip_ivfpq_create_ex(coarse, nlist, codebooks, m, k, sub_dim, metric, 0u, out);
+}
+
+int vqhip_ivfpq_create_ex(const float *coarse, uint32_t nlist, const float *codebooks, uint32_t m, uint32_t k, uint32_t sub_dim,
+                          int metric, uint32_t flags, vqhip_ivfpq **out) {
     VQ_API_BEGIN
     if (!out) return fail(VQHIP_ERR_NULL_PTR, "out is NULL");
     *out = nullptr;
+    if (flags & ~(uint32_t)VQHIP_IVF_RESIDUAL) return fail(VQHIP_ERR_INVALID_INPUT, "unknown flag bits 0x%x", flags & ~(uint32_t)VQHIP_IVF_RESIDUAL);
     if (!coarse || !codebooks) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
     if (nlist == 0 || nlist > 65536) return fail(VQHIP_ERR_INVALID_INPUT, "nlist %u must be in [1, 65536]", nlist);
     if (m == 0 || k == 0 || sub_dim == 0) return fail(VQHIP_ERR_INVALID_INPUT, "m, k and sub_dim must be positive");
@@ -3017,6 +3045,7 @@ int vqhip_ivfpq_create(const float *coarse, uint32_t nlist, const float *codeboo
     ix->sd = sub_dim;
     ix->dim = m * sub_dim;
     ix->metric = metric;
+    ix->flags = flags;
     ix->coarse.assign(coarse, coarse + (size_t)nlist * ix->dim);
     ix->cb.assign(codebooks, codebooks + (size_t)m * k * sub_dim);
     ix->sizes.assign(nlist, 0);
@@ -3065,6 +3094,12 @@ int vqhip_ivfpq_info(const vqhip_ivfpq *ix, uint64_t *n, uint32_t *nlist, uint32
     if (m) *m = ix->m;
     if (k) *k = ix->k;
     if (metric) *metric = ix->metric;
+    return VQHIP_OK;
+}
+
+int vqhip_ivfpq_flags(const vqhip_ivfpq *ix, uint32_t *flags) {
+    if (!ix || !flags) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    *flags = ix->flags;  // (fixed at create)
     return VQHIP_OK;
 }
 

@@ -275,6 +275,16 @@ int launch_ivf_search(const uint8_t *codes, const uint32_t *ids, const uint32_t 
                       const float *lut, const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk,
                       uint64_t wstride, float *W, uint32_t *pref, uint32_t *seg, float *bounds, void *state,
                       unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream);
+// the same over residual lists (a row of list l encodes x - C[l]): the tables per (query, probe slot) are built here from
+// the queries, coarse [nlist][dim] and cb [m][k][sd]; tabs [nb][nprobe][m][k], mm [nb][nprobe][2]
+size_t ivf_rtab_bytes(uint32_t qb, uint32_t nprobe, uint32_t m, uint32_t k);
+size_t ivf_rmm_bytes(uint32_t qb, uint32_t nprobe);
+uint32_t ivf_rchunk(uint64_t expected_positions, uint32_t k);
+int launch_ivf_rsearch(const uint8_t *codes, const uint32_t *ids, const uint32_t *off, const float *coarse, uint32_t nlist,
+                       const float *cb, uint32_t m, uint32_t k, uint32_t sd, int metric, const float *queries,
+                       const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
+                       float *tabs, float *mm, float *W, uint32_t *pref, uint32_t *seg, float *bounds, void *state,
+                       unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream);
 // exact k-NN search over resident rows and exact rerank of candidate lists (k_knn.hip); X [n][d] f32 (dtype 0) or f16
 // bits (dtype 1), rnorm [n] the rows' norms (cosine only, else unused)
 int launch_knn_norms(const void *X, int dtype, uint64_t n, uint32_t d, float *out, hipStream_t stream);

@@ -3,13 +3,15 @@
 The reference has no search function; the semantics are include/vqhip.h's (vqhip_ivfpq_*, vq_amd/csrc/k_ivf.hip):
 ``P(q)`` is ``FlatIndex(coarse, distance).search(q, nprobe)``, ``S(q)`` the rows whose list is in ``P(q)``, and the result
 the ``topk`` rows of ``S(q)`` by ``(ADC distance, row id)`` ascending -- with ``nprobe == nlist`` exactly
-``PQIndex(codebooks, codes).search``.  Slots past ``|S(q)|`` hold id ``0xFFFFFFFF`` and distance ``+inf``.  Non-residual:
-the codes encode the rows themselves.  Constructing, adding codes, saving and loading need no GPU; the device handle is
-created by the first probe or search and follows every later add.
+``PQIndex(codebooks, codes).search``.  Slots past ``|S(q)|`` hold id ``0xFFFFFFFF`` and distance ``+inf``.  By default
+non-residual: the codes encode the rows themselves.  ``residual=True`` (IVFADC): a row ``x`` in list ``l`` is stored as the
+codes of ``x - C[l]``, and its distance to ``q`` is the ADC distance of those codes to ``r = q - C[l]`` (f32, one rounding
+per element); probing, order, ties, NaN and padding are as above.  Constructing, adding codes, saving and loading need
+no GPU; the device handle is created by the first probe or search and follows every later add.
 
 File layout (little endian), in the manner of store.py's:
 
-    0   8   magic  b"VQIVFPQ1"
+    0   8   magic  b"VQIVFPQ1" (non-residual) or b"VQIVFRP1" (residual)
     8   4   u32    metric (0 squared_euclidean, 1 euclidean, 2 manhattan)
     12  4   u32    dim
     16  4   u32    nlist
@@ -34,6 +36,7 @@ from .distance import Distance
 from .errors import DimensionMismatch, InvalidParameter
 
 MAGIC = b"VQIVFPQ1"
+MAGIC_RESIDUAL = b"VQIVFRP1"
 _HEADER = struct.Struct("<8sIIIIIIQ")
 _METRIC_NAMES = ["squared_euclidean", "euclidean", "manhattan"]
 MAX_NLIST = 65536
@@ -81,12 +84,26 @@ def _check_shape(coarse, codebooks, distance):
     return c, cb
 
 
+def _nearest_lists(coarse, X, metric: int) -> np.ndarray:
+    """(n,) uint32: each row's nearest coarse centroid (the reference's nearest-centroid rule: a PQ encode with one
+    subspace of nlist centroids)"""
+    enc = _lib.PQEncoder(coarse[None, :, :], metric)
+    try:
+        lists, _ = enc.encode(X, want_f16=False)
+    finally:
+        enc.close()
+    return np.asarray(lists).reshape(-1).astype(np.uint32)
+
+
 class IVFPQIndex:
     """coarse centroids (nlist, dim) + PQ codebooks (m, k, dim / m) + distance, and the rows added to it"""
 
-    def __init__(self, coarse_centroids, codebooks, distance: Distance | None = None):
+    def __init__(self, coarse_centroids, codebooks, distance: Distance | None = None, *, residual: bool = False):
+        if not isinstance(residual, (bool, np.bool_)):
+            raise InvalidParameter("residual", f"must be a bool, got {type(residual).__name__}")
         self._distance = distance if distance is not None else Distance.euclidean()
         self._coarse, self._codebooks = _check_shape(coarse_centroids, codebooks, self._distance)
+        self._residual = bool(residual)
         m, k = self._codebooks.shape[:2]
         self._lists = np.empty(0, np.uint32)
         self._codes = np.empty((0, m), _code_dtype(k))
@@ -108,6 +125,11 @@ class IVFPQIndex:
     @property
     def k(self) -> int:
         return self._codebooks.shape[1]
+
+    @property
+    def residual(self) -> bool:
+        """True: the codes of a row in list l quantise x - C[l]"""
+        return self._residual
 
     @property
     def distance(self) -> Distance:
@@ -136,7 +158,7 @@ class IVFPQIndex:
 
     def __repr__(self) -> str:
         return (f"IVFPQIndex(n={len(self)}, nlist={self.nlist}, dim={self.dim}, m={self.m}, k={self.k}, "
-                f"distance={self._distance!r})")
+                f"distance={self._distance!r}" + (", residual=True)" if self._residual else ")"))
 
     def list_sizes(self) -> np.ndarray:
         """(nlist,) uint64: rows per list"""
@@ -145,15 +167,21 @@ class IVFPQIndex:
     # -- build ------------------------------------------------------------------------------
     @classmethod
     def train(cls, X, nlist: int, m: int, k: int, max_iters: int = 10, distance: Distance | None = None,
-              seed: int = 42) -> "IVFPQIndex":
+              seed: int = 42, residual: bool = False) -> "IVFPQIndex":
         """fit the coarse quantizer (k-means of whole rows: a ProductQuantizer with one subspace of nlist centroids) and
-        the PQ codebooks on X; the index holds no rows yet (add them with `add`)"""
+        the PQ codebooks on X -- with residual=True on the residuals X - C[list] of X's rows in their nearest lists; the
+        index holds no rows yet (add them with `add`)"""
         from .pq import ProductQuantizer
 
+        if not isinstance(residual, (bool, np.bool_)):
+            raise InvalidParameter("residual", f"must be a bool, got {type(residual).__name__}")
         distance = distance if distance is not None else Distance.euclidean()
         coarse = ProductQuantizer(X, 1, nlist, max_iters, distance, seed).codebooks[0]
+        if residual:
+            X = np.ascontiguousarray(X, dtype=np.float32)
+            X = X - coarse[_nearest_lists(coarse, X, distance.metric)]
         cb = ProductQuantizer(X, m, k, max_iters, distance, seed).codebooks
-        return cls(coarse, cb, distance)
+        return cls(coarse, cb, distance, residual=bool(residual))
 
     def add(self, X) -> np.ndarray:
         """assign each row of X (n, dim) to its nearest coarse centroid (the reference's nearest-centroid rule: a PQ encode
@@ -167,15 +195,15 @@ class IVFPQIndex:
             raise DimensionMismatch(self.dim, X.shape[1])
         if X.shape[0] == 0:
             return np.empty(0, np.uint32)
-        coarse = _lib.PQEncoder(self._coarse[None, :, :], self._distance.metric)
+        lists = _nearest_lists(self._coarse, X, self._distance.metric)
+        if self._residual:
+            X = X - self._coarse[lists]  # (f32, one rounding per element)
         pq = _lib.PQEncoder(self._codebooks, self._distance.metric)
         try:
-            lists, _ = coarse.encode(X, want_f16=False)
             codes, _ = pq.encode(X, want_f16=False)
         finally:
-            coarse.close()
             pq.close()
-        return self.add_codes(np.asarray(lists).reshape(-1), codes)
+        return self.add_codes(lists, codes)
 
     def add_codes(self, list_ids, codes) -> np.ndarray:
         """append rows given as list ids (n,) < nlist and codes (n, m) < k; returns the new row ids"""
@@ -204,7 +232,8 @@ class IVFPQIndex:
 
     def _handle(self) -> "_lib.IVFPQ":
         if self._ix is None:
-            ix = _lib.IVFPQ(self._coarse, self._codebooks, self._distance.metric)
+            ix = _lib.IVFPQ(self._coarse, self._codebooks, self._distance.metric,
+                            _lib.IVF_RESIDUAL if self._residual else 0)
             if len(self):
                 ix.add(self._lists, self._codes)
             self._ix = ix
@@ -292,7 +321,8 @@ class IVFPQIndex:
     # -- file -------------------------------------------------------------------------------
     def save(self, path) -> None:
         with open(path, "wb") as f:
-            f.write(_HEADER.pack(MAGIC, self._distance.metric, self.dim, self.nlist, self.m, self.k, 0, len(self)))
+            magic = MAGIC_RESIDUAL if self._residual else MAGIC
+            f.write(_HEADER.pack(magic, self._distance.metric, self.dim, self.nlist, self.m, self.k, 0, len(self)))
             f.write(self._coarse.astype("<f4").tobytes())
             f.write(self._codebooks.astype("<f4").tobytes())
             f.write(self._lists.astype("<u4").tobytes())
@@ -300,14 +330,15 @@ class IVFPQIndex:
 
     @classmethod
     def load(cls, path) -> "IVFPQIndex":
-        """read a VQIVFPQ1 file; every range is checked here, before anything can reach the device"""
+        """read a VQIVFPQ1 (non-residual) or VQIVFRP1 (residual) file; every range is checked here, before anything can
+        reach the device"""
         with open(path, "rb") as f:
             head = f.read(_HEADER.size)
             if len(head) != _HEADER.size:
                 raise ValueError("truncated index header")
             magic, metric, dim, nlist, m, k, reserved, n = _HEADER.unpack(head)
-            if magic != MAGIC:
-                raise ValueError("not a VQIVFPQ1 file")
+            if magic not in (MAGIC, MAGIC_RESIDUAL):
+                raise ValueError("not a VQIVFPQ1 or VQIVFRP1 file")
             if (metric >= len(_METRIC_NAMES) or reserved != 0 or not 1 <= nlist <= MAX_NLIST or m == 0 or k == 0
                     or k > 65536 or m * k > MAX_TABLE or dim == 0 or dim % m != 0 or n >= 1 << 32):
                 raise ValueError("corrupt index header")
@@ -330,7 +361,7 @@ class IVFPQIndex:
             raise ValueError(f"corrupt index: a list id is outside [0, {nlist})")
         if n and int(codes.max()) >= k:
             raise ValueError(f"corrupt index: a code is outside [0, {k})")
-        self = cls(coarse, cb, Distance(_METRIC_NAMES[metric]))
+        self = cls(coarse, cb, Distance(_METRIC_NAMES[metric]), residual=magic == MAGIC_RESIDUAL)
         self._lists = lists.astype(np.uint32)
         self._codes = codes.astype(_code_dtype(k))
         return self
