@@ -491,7 +491,7 @@ int launch_adc_search(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int 
     // A GROUP of up to `qgroup` queries (the caller's workspaces: adc_query_group(n)) goes through one set of launches: the
     // six kernels of a pass are dependent and tiny (5-25 us each, 110 us per pass whatever the work), so eight passes one
     // after the other cost eight times that for 64 queries
-    const uint32_t qg = std::max(qb, qgroup / qb * qb);
+    const uint32_t qg = qgroup >= nq ? nq : (qgroup >= qb ? qgroup / qb * qb : qgroup);  // (<= qgroup: the workspaces' size)
     // small state per query of the group: bounds [2] f32 | hist [bins] u32 | sel [2] u32 | cand_n u32
     float *bounds = reinterpret_cast<float *>(state_ws);
     uint32_t *hist = reinterpret_cast<uint32_t *>(bounds + 2 * (size_t)qg);
@@ -537,11 +537,14 @@ int launch_adc_lut(const float *queries_dev, uint32_t nq, uint32_t m, uint32_t k
 size_t adc_state_bytes(uint32_t qgroup) { return (size_t)qgroup * (2 + kAdcBins + 2 + 1) * 4; }
 size_t adc_cand_bytes(uint32_t qgroup) { return (size_t)qgroup * kAdcCand * 8; }
 uint32_t adc_query_batch() { return kAdcQB; }
-// queries that share one set of launches: up to 64, as long as their distance rows (4 n bytes each) stay under 1 GB
+// queries that share one set of launches: up to 64 while their distance rows (4 n bytes each) stay under 1 GB -- a whole
+// number of scan batches (kAdcQB) where one batch fits, fewer queries (down to one) where it does not -- and never more
+// than the call's nq.  So the distance workspace is at most max(1 GB, 4 n): 8.6 GB at n = 2^31 + 4099, whatever nq.
+// (Where a batch's rows pass 1 GB, n >= 2^25, writing the distances costs more than reading the codes again per group.)
 uint32_t adc_query_group(uint64_t n, uint32_t nq) {
     uint64_t g = (1ull << 30) / std::max<uint64_t>(4 * n, 1);
-    g = std::min<uint64_t>(std::max<uint64_t>(g / kAdcQB * kAdcQB, kAdcQB), 64);
-    return (uint32_t)std::min<uint64_t>(g, ((uint64_t)nq + kAdcQB - 1) / kAdcQB * kAdcQB);
+    g = g >= kAdcQB ? std::min<uint64_t>(g / kAdcQB * kAdcQB, 64) : std::max<uint64_t>(g, 1);
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(g, nq));
 }
 
 // ---- the threshold pass (round 6) ----

@@ -247,7 +247,7 @@ int launch_adc_search(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int 
                       void *state_ws, unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev,
                       hipStream_t stream, uint32_t qgroup);
 uint32_t adc_query_batch();
-uint32_t adc_query_group(uint64_t n, uint32_t nq);  // queries that go through one set of launches (a multiple of the batch)
+uint32_t adc_query_group(uint64_t n, uint32_t nq);  // queries that go through one set of launches (a multiple of the batch, all nq, or fewer where 4 n passes 1 GB)
 size_t adc_state_bytes(uint32_t qgroup);
 size_t adc_cand_bytes(uint32_t qgroup);
 // VQHIP_ERR_UNSUPPORTED for a table above the LDS plan's limit (m * k > kAdcMaxTable, adc_plan.hpp): both schedules refuse it
