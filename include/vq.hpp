@@ -728,6 +728,90 @@ class FlatIndex {
     Distance distance_;
 };
 
+// Hamming index over packed BQ codes (include/vqhip.h, vqhip_binary_*): rows binarised by a BinaryQuantizer (f32 rows,
+// u8 codes or packed words [n][ceil(dim / 32)]), searched under squared Euclidean, Euclidean or Manhattan on the
+// dequantized vectors; (row id, distance) pairs [nq][topk], nearest first, ties to the lower row.  Cosine and every
+// other bad argument are refused before the device is touched.
+class BinaryIndex {
+   public:
+    enum class Source { Rows = VQHIP_BINARY_F32, Codes = VQHIP_BINARY_U8, Packed = VQHIP_BINARY_PACKED };
+    BinaryIndex(const float *rows, std::size_t n, std::size_t dim, BinaryQuantizer quantizer = BinaryQuantizer(0.0f, 0, 1),
+                Distance distance = Distance(Distance::Manhattan))
+        : quantizer_(quantizer) {
+        init(rows, Source::Rows, n, dim, distance);
+    }
+    BinaryIndex(const std::uint8_t *codes, std::size_t n, std::size_t dim, BinaryQuantizer quantizer,
+                Distance distance = Distance(Distance::Manhattan))
+        : quantizer_(quantizer) {
+        init(codes, Source::Codes, n, dim, distance);
+    }
+    BinaryIndex(const std::uint32_t *words, std::size_t n, std::size_t dim, BinaryQuantizer quantizer,
+                Distance distance = Distance(Distance::Manhattan))
+        : quantizer_(quantizer) {
+        init(words, Source::Packed, n, dim, distance);
+    }
+    std::size_t size() const { return n_; }
+    std::size_t dim() const { return dim_; }
+    std::size_t words_per_row() const { return (dim_ + 31) / 32; }
+    const BinaryQuantizer &quantizer() const { return quantizer_; }
+    const char *distance_metric() const { return distance_.name(); }
+
+    struct Result {
+        std::vector<std::uint32_t> idx;  // [nq][topk]
+        std::vector<float> dist;         // [nq][topk]
+    };
+    // queries [nq][dim] f32, binarised by the index's quantizer on the device
+    Result search(const float *queries, std::size_t nq, std::size_t topk) const {
+        if (topk == 0 || topk > 1024 || topk > n_)
+            throw VqError::InvalidParameter("topk", "must be between 1 and min(n, 1024)");
+        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
+        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
+        if (nq) detail::check(vqhip_binary_search(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)topk, r.idx.data(), r.dist.data()));
+        return r;
+    }
+    Result search(const std::vector<float> &queries, std::size_t topk) const {
+        if (queries.size() % dim_) throw VqError::DimensionMismatch(dim_, queries.size() % dim_);
+        return search(queries.data(), queries.size() / dim_, topk);
+    }
+    // the packed rows [n][words_per_row()]
+    std::vector<std::uint32_t> packed() const {
+        std::vector<std::uint32_t> out(n_ * words_per_row());
+        detail::check(vqhip_binary_packed(ix_.get(), out.data()));
+        return out;
+    }
+
+   private:
+    struct Del {
+        void operator()(vqhip_binary *p) const { (void)vqhip_binary_destroy(p); }
+    };
+    void init(const void *src, Source kind, std::size_t n, std::size_t dim, Distance distance) {
+        if (n == 0) throw VqError::EmptyInput();
+        if (dim == 0 || dim > VQHIP_BINARY_MAX_DIM) throw VqError::InvalidParameter("dim", "must be between 1 and 8192");
+        if (n >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("rows", "at most 2^32 - 1 rows");
+        if (distance.kind() != Distance::SquaredEuclidean && distance.kind() != Distance::Euclidean &&
+            distance.kind() != Distance::Manhattan)
+            throw VqError::InvalidParameter("distance", "must be squared_euclidean, euclidean or manhattan");
+        if (kind == Source::Packed && dim % 32) {
+            const std::size_t w = (dim + 31) / 32;
+            const std::uint32_t mask = (1u << (dim % 32)) - 1u;
+            for (std::size_t i = 0; i < n; ++i)
+                if (static_cast<const std::uint32_t *>(src)[i * w + w - 1] & ~mask)
+                    throw VqError::InvalidParameter("words", "a row has a pad bit set");
+        }
+        vqhip_binary *b = nullptr;
+        detail::check(vqhip_binary_create(src, (int)kind, n, (std::uint32_t)dim, quantizer_.threshold(), quantizer_.low(),
+                                          quantizer_.high(), (int)distance.kind(), &b));
+        ix_.reset(b);
+        n_ = n;
+        dim_ = dim;
+        distance_ = distance;
+    }
+    BinaryQuantizer quantizer_;
+    std::unique_ptr<vqhip_binary, Del> ix_;
+    std::size_t n_ = 0, dim_ = 0;
+    Distance distance_;
+};
+
 // Inverted-file index over PQ codes (include/vqhip.h, vqhip_ivfpq_*): coarse centroids [nlist][dim], codebooks
 // [m][k][sub_dim], rows added as (list id, codes).  search scans only the nprobe lists nearest to a query and gives
 // (row id, ADC distance) pairs [nq][topk], nearest first; slots past the probed rows hold (0xFFFFFFFF, +inf).  The

@@ -480,6 +480,44 @@ int vqhip_flat_search_device(vqhip_flat *f, const void *dev_queries, uint32_t nq
 int vqhip_flat_rerank(vqhip_flat *f, const float *queries, uint32_t nq, const uint32_t *cand, uint32_t c,
                       uint32_t topk, uint32_t *idx_out, float *dist_out);
 
+/* ---- binary index: Hamming top-k over packed BQ codes (k_binary.hip) -------------------------
+ * No reference counterpart.  A BinaryQuantizer(threshold, low, high) fixes the bit rule; nothing else depends on it.
+ *   bits    f32 x: x >= threshold (NaN -> 0, -0.0 == 0.0), the BQ encode rule; u8 code c: c >= high, the decode rule.
+ *   layout  row i, dimension t in u32 word i * W + t / 32, bit t % 32 (LSB first), W = ceil(d / 32), pad bits zero,
+ *           little-endian words: np.packbits(bits, bitorder="little") padded to 32 bits and viewed as "<u4".
+ *   D(q, i) = Distance::compute(dequantize(quantize(q)), dequantize(code_i)) bit for bit, for squared Euclidean,
+ *           Euclidean and Manhattan: with H = popcount(bits(q) xor bits(row_i)), a = f32(high) - f32(low) (an exact
+ *           integer in 1..255) and t = a * a (squared / Euclidean) or a (Manhattan), the sequential sum is the table
+ *           S(0) = +0.0, S(j) = fl(S(j - 1) + t) (an agreeing dimension adds +0.0, which changes no non-negative sum and
+ *           turns the -0.0 start into +0.0), D = S(H), Euclidean sqrtf(S(H)).  Cosine: VQHIP_ERR_UNSUPPORTED.
+ *   search  per query the topk rows by (D, row id) ascending, ties to the lower row, no NaN possible.  Every table is
+ *           strictly increasing for a in 1..255 and d <= 8192, so the order is that of (H, row id).
+ * Limits: 1 <= d <= 8192, 1 <= n < 2^32, 1 <= topk <= min(n, 1024), nq < 2^32 (internal batches of 1024).  The source
+ * of create is f32 rows [n][d] (kind VQHIP_BINARY_F32), u8 codes [n][d] (VQHIP_BINARY_U8) or packed words [n][W]
+ * (VQHIP_BINARY_PACKED: a set pad bit is VQHIP_ERR_INVALID_INPUT); create_device copies.  Queries are f32 [nq][d],
+ * binarised on the device by the same rule.  Every parameter is checked before any device work.  Host forms return
+ * when the results are there; search_device and bq_pack_device are asynchronous on the current stream.  One lock per
+ * handle.  info: any output pointer may be NULL.  vqhip_binary_packed copies the words [n][W] to the host. */
+#define VQHIP_BINARY_F32 0
+#define VQHIP_BINARY_U8 1
+#define VQHIP_BINARY_PACKED 2
+#define VQHIP_BINARY_MAX_DIM 8192
+int vqhip_bq_pack(float threshold, const float *x, uint64_t n, uint32_t d, uint32_t *words);
+int vqhip_bq_pack_device(float threshold, const void *dev_x, uint64_t n, uint32_t d, void *dev_words);
+typedef struct vqhip_binary vqhip_binary;
+int vqhip_binary_create(const void *src, int kind, uint64_t n, uint32_t d, float threshold, uint32_t low, uint32_t high,
+                        int metric, vqhip_binary **out);
+int vqhip_binary_create_device(const void *dev_src, int kind, uint64_t n, uint32_t d, float threshold, uint32_t low,
+                               uint32_t high, int metric, vqhip_binary **out);
+int vqhip_binary_destroy(vqhip_binary *b);
+int vqhip_binary_info(const vqhip_binary *b, uint64_t *n, uint32_t *d, float *threshold, uint32_t *low, uint32_t *high,
+                      int *metric);
+int vqhip_binary_packed(vqhip_binary *b, uint32_t *words);
+int vqhip_binary_search(vqhip_binary *b, const float *queries, uint32_t nq, uint32_t topk, uint32_t *idx_out,
+                        float *dist_out);
+int vqhip_binary_search_device(vqhip_binary *b, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx,
+                               void *dev_dist);
+
 /* ---- inverted-file PQ index: search only the probed lists (k_ivf.hip) -----------------------
  * No reference counterpart.  An index holds coarse centroids C [nlist][dim] f32 (1 <= nlist <= 65536), PQ codebooks
  * cb [m][k][sub_dim] (dim = m * sub_dim) and a metric: squared Euclidean, Euclidean or Manhattan (cosine is refused with

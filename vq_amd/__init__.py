@@ -1,7 +1,7 @@
 """vq_amd -- MI355X (gfx950) back end for the k-means codebook-training and nearest-centroid
 encode path of CogitatorTech/vq, and of its elementwise scalar / binary quantizers, behind the
-reference's own Quantizer interface, exact k-NN search over resident rows (FlatIndex) and an inverted-file
-index over PQ codes (IVFPQIndex).
+reference's own Quantizer interface, exact k-NN search over resident rows (FlatIndex), an inverted-file
+index over PQ codes (IVFPQIndex) and a Hamming index over packed BQ codes (BinaryIndex).
 
 The compute path is libvqhip.so (hand-written HIP for CDNA4, C ABI in include/vqhip.h).
 Importing the package does not need a GPU; using any quantizer does, and fails loudly
@@ -10,6 +10,7 @@ Importing the package does not need a GPU; using any quantizer does, and fails l
 from .distance import Distance
 from .errors import (DimensionMismatch, EmptyInput, FfiError, InvalidData, InvalidParameter,
                      VqError)
+from .binary import BinaryIndex
 from .bq import BinaryQuantizer
 from .flat import FlatIndex
 from .ivf import IVFPQIndex
@@ -18,7 +19,7 @@ from .sq import ScalarQuantizer
 from .tsvq import TSVQ
 
 __all__ = [
-    "Distance", "BinaryQuantizer", "FlatIndex", "IVFPQIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
+    "Distance", "BinaryIndex", "BinaryQuantizer", "FlatIndex", "IVFPQIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
     "InvalidParameter", "InvalidData", "FfiError", "get_simd_backend",
 ]
 

@@ -153,6 +153,16 @@ SIGNATURES = {
     "vqhip_flat_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
     "vqhip_flat_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
     "vqhip_flat_rerank": (C.c_int, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "vqhip_bq_pack": (C.c_int, [C.c_float, _f32p, C.c_uint64, C.c_uint32, _u32p]),
+    "vqhip_bq_pack_device": (C.c_int, [C.c_float, _vp, C.c_uint64, C.c_uint32, _vp]),
+    "vqhip_binary_create": (C.c_int, [_vp, C.c_int, C.c_uint64, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_int, _vpp]),
+    "vqhip_binary_create_device": (C.c_int, [_vp, C.c_int, C.c_uint64, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_int,
+                                             _vpp]),
+    "vqhip_binary_destroy": (C.c_int, [_vp]),
+    "vqhip_binary_info": (C.c_int, [_vp, _u64p, _u32p, C.POINTER(C.c_float), _u32p, _u32p, C.POINTER(C.c_int)]),
+    "vqhip_binary_packed": (C.c_int, [_vp, _u32p]),
+    "vqhip_binary_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "vqhip_binary_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
     "vqhip_ivfpq_create": (C.c_int, [_f32p, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _vpp]),
     "vqhip_ivfpq_destroy": (C.c_int, [_vp]),
     "vqhip_ivfpq_add": (C.c_int, [_vp, _u32p, _vp, C.c_uint64]),
@@ -776,6 +786,46 @@ class Flat(Handle):
             check(load().vqhip_flat_rerank(self.raw, ptr(q, _f32p), nq, ptr(cand, _u32p), int(c), int(topk), ptr(idx, _u32p),
                                            ptr(dist, _f32p)))
         return idx, dist
+
+
+BINARY_F32, BINARY_U8, BINARY_PACKED = 0, 1, 2
+
+
+class Binary(Handle):
+    """vqhip_binary: BQ bits packed 32 to a word on the device, exact Hamming top-k search (k_binary.hip)"""
+
+    _destroy = "vqhip_binary_destroy"
+
+    def __init__(self, src, kind: int, n: int, d: int, threshold: float, low: int, high: int, metric: int,
+                 dev_src: int | None = None):
+        """src: a C-contiguous host array of the kind (f32 [n][d], u8 [n][d], u32 [n][W]), or dev_src a device pointer"""
+        h = C.c_void_p()
+        if dev_src is not None:
+            check(load().vqhip_binary_create_device(C.c_void_p(dev_src), int(kind), int(n), int(d), float(threshold), int(low),
+                                                    int(high), int(metric), C.byref(h)))
+        else:
+            check(load().vqhip_binary_create(src.ctypes.data_as(_vp), int(kind), int(n), int(d), float(threshold), int(low),
+                                             int(high), int(metric), C.byref(h)))
+        super().__init__(h)
+        self.n, self.d, self.metric = int(n), int(d), int(metric)
+        self.words = (self.d + 31) // 32
+
+    def packed(self) -> np.ndarray:
+        out = np.empty((self.n, self.words), np.uint32)
+        check(load().vqhip_binary_packed(self.raw, ptr(out, _u32p)))
+        return out
+
+    def search(self, q: np.ndarray, topk: int):
+        nq = q.shape[0]
+        idx = np.empty((nq, topk), np.uint32)
+        dist = np.empty((nq, topk), np.float32)
+        if nq:
+            check(load().vqhip_binary_search(self.raw, ptr(q, _f32p), nq, int(topk), ptr(idx, _u32p), ptr(dist, _f32p)))
+        return idx, dist
+
+    def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int):
+        check(load().vqhip_binary_search_device(self.raw, C.c_void_p(dev_queries), int(nq), int(topk), C.c_void_p(dev_idx),
+                                                C.c_void_p(dev_dist)))
 
 
 class IVFPQ(Handle):

@@ -1,0 +1,239 @@
+"""``BinaryIndex`` -- exact Hamming top-k search over BQ codes packed 32 to a word on the device.
+
+The reference has no search function; the semantics are include/vqhip.h's (vqhip_binary_*, vq_amd/csrc/k_binary.hip):
+a ``BinaryQuantizer(threshold, low, high)`` fixes the bit rule (x >= threshold for f32 rows and queries, c >= high for
+u8 codes), row i / dimension t sits in word ``i * W + t // 32``, bit ``t % 32`` (``W = ceil(d / 32)``, pad bits zero),
+and ``D(q, i) = Distance.compute(bq.dequantize(bq.quantize(q)), bq.dequantize(code_i))`` bit for bit for squared
+Euclidean, Euclidean and Manhattan -- a function of the Hamming distance alone, read from a table the library builds.
+Cosine is refused.  The result per query is the ``topk`` rows by ``(D, row id)`` ascending, ties to the lower row.
+
+Every argument is checked here before the device is touched; the index goes to the device on the first search (until
+then it refers to the caller's array, which must not change in between).  ``save`` / ``load`` need no device.
+"""
+from __future__ import annotations
+
+import struct
+
+import numpy as np
+
+from . import _lib
+from .bq import BinaryQuantizer
+from .distance import Distance
+from .errors import DimensionMismatch, EmptyInput, InvalidData, InvalidParameter
+from .flat import MAX_TOPK, _count, adc_then_rerank
+
+MAGIC = b"VQBINIX1"
+_HEADER = struct.Struct("<8sIIfIIQ")  # magic, metric, dim, threshold, low, high, n
+MAX_DIM = 8192
+_METRICS = (_lib.SQUARED_EUCLIDEAN, _lib.EUCLIDEAN, _lib.MANHATTAN)
+
+
+def words_per_row(dim: int) -> int:
+    return (int(dim) + 31) // 32
+
+
+def pack_bits(bits: np.ndarray) -> np.ndarray:
+    """bool / 0-1 array (n, d) -> uint32 (n, W), the layout of the index (host numpy)"""
+    b = np.asarray(bits).astype(bool)
+    n, d = b.shape
+    w = words_per_row(d)
+    padded = np.zeros((n, 32 * w), bool)
+    padded[:, :d] = b
+    return np.packbits(padded, axis=1, bitorder="little").view("<u4").astype(np.uint32).reshape(n, w)
+
+
+def _pad_ok(words: np.ndarray, dim: int) -> bool:
+    if dim % 32 == 0 or words.shape[0] == 0:
+        return True
+    mask = np.uint32((1 << (dim % 32)) - 1)
+    return not bool((words[:, -1] & ~mask).any())
+
+
+def _check_params(dim: int, quantizer, distance) -> None:
+    if not isinstance(quantizer, BinaryQuantizer):
+        raise InvalidParameter("quantizer", f"expected a BinaryQuantizer, got {type(quantizer).__name__}")
+    if not isinstance(distance, Distance):
+        raise InvalidParameter("distance", f"expected a Distance, got {type(distance).__name__}")
+    if distance.metric not in _METRICS:
+        raise InvalidParameter("distance", f"{distance.name()} is not a function of the Hamming distance alone; "
+                                           "use squared_euclidean, euclidean or manhattan")
+    if not 1 <= dim <= MAX_DIM:
+        raise InvalidParameter("dim", f"must be between 1 and {MAX_DIM}, got {dim}")
+
+
+class BinaryIndex:
+    """Exact Hamming top-k over rows binarised by `quantizer` (default ``BinaryQuantizer(0.0)``) under `distance`
+    (default Manhattan: with the default quantizer, D is the Hamming count)."""
+
+    def __init__(self, rows, quantizer: BinaryQuantizer | None = None, distance: Distance | None = None):
+        a = rows if isinstance(rows, np.ndarray) else np.asarray(rows)
+        if a.dtype != np.float32:
+            raise InvalidParameter("rows", f"dtype must be float32, got {a.dtype}")
+        self._setup(a, _lib.BINARY_F32, quantizer, distance)
+
+    @classmethod
+    def from_codes(cls, codes, quantizer: BinaryQuantizer | None = None, distance: Distance | None = None) -> "BinaryIndex":
+        """u8 BQ codes (n, d), e.g. ``quantizer.quantize_batch(rows)``; bit = code >= high"""
+        a = codes if isinstance(codes, np.ndarray) else np.asarray(codes)
+        if a.dtype != np.uint8:
+            raise InvalidParameter("codes", f"dtype must be uint8, got {a.dtype}")
+        self = cls.__new__(cls)
+        self._setup(a, _lib.BINARY_U8, quantizer, distance)
+        return self
+
+    @classmethod
+    def from_packed(cls, words, dim: int, quantizer: BinaryQuantizer | None = None,
+                    distance: Distance | None = None) -> "BinaryIndex":
+        """uint32 (n, ceil(dim / 32)) packed rows in the index layout, pad bits zero"""
+        a = words if isinstance(words, np.ndarray) else np.asarray(words)
+        if a.dtype != np.uint32:
+            raise InvalidParameter("words", f"dtype must be uint32, got {a.dtype}")
+        d = _count(dim, "dim")
+        if a.ndim != 2:
+            raise ValueError("expected a 2D array (n, words)")
+        if not 1 <= d <= MAX_DIM:
+            raise InvalidParameter("dim", f"must be between 1 and {MAX_DIM}, got {d}")
+        if a.shape[1] != words_per_row(d):
+            raise DimensionMismatch(words_per_row(d), a.shape[1])
+        if not _pad_ok(a, d):
+            raise InvalidParameter("words", f"a row has a pad bit (dimension >= {d}) set")
+        self = cls.__new__(cls)
+        self._setup(a, _lib.BINARY_PACKED, quantizer, distance, dim=d)
+        return self
+
+    def _setup(self, a: np.ndarray, kind: int, quantizer, distance, dim: int | None = None) -> None:
+        if quantizer is None:
+            quantizer = BinaryQuantizer(0.0)
+        if distance is None:
+            distance = Distance.manhattan()
+        if a.ndim != 2:
+            raise ValueError("expected a 2D array (n, dim)")
+        if a.shape[0] == 0:
+            raise EmptyInput()
+        d = a.shape[1] if dim is None else dim
+        _check_params(d, quantizer, distance)
+        if a.shape[0] >= 1 << 32:
+            raise InvalidParameter("rows", f"at most 2^32 - 1 rows, got {a.shape[0]}")
+        self._src = np.ascontiguousarray(a)
+        self._kind = kind
+        self._n, self._dim = int(a.shape[0]), int(d)
+        self._quantizer, self._distance = quantizer, distance
+        self._ix = None
+
+    def __len__(self) -> int:
+        return self._n
+
+    @property
+    def dim(self) -> int:
+        return self._dim
+
+    @property
+    def quantizer(self) -> BinaryQuantizer:
+        return self._quantizer
+
+    @property
+    def distance(self) -> Distance:
+        return self._distance
+
+    def __repr__(self) -> str:
+        return f"BinaryIndex(n={self._n}, dim={self._dim}, quantizer={self._quantizer!r}, distance={self._distance!r})"
+
+    def _index(self) -> "_lib.Binary":
+        if self._ix is None:
+            q = self._quantizer
+            self._ix = _lib.Binary(self._src, self._kind, self._n, self._dim, q.threshold, q.low, q.high,
+                                   self._distance.metric)
+            self._src = None  # on the device now
+        return self._ix
+
+    def _queries(self, queries) -> np.ndarray:
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2:
+            raise ValueError("expected a 2D array (nq, dim)")
+        if q.shape[1] != self._dim:
+            raise DimensionMismatch(self._dim, q.shape[1])
+        if q.shape[0] >= 1 << 32:
+            raise InvalidParameter("queries", f"at most 2^32 - 1 queries, got {q.shape[0]}")
+        return q
+
+    def _topk(self, topk) -> int:
+        k = _count(topk, "topk")
+        if not 1 <= k <= min(self._n, MAX_TOPK):
+            raise InvalidParameter("topk", f"must be between 1 and min(n, 1024), got {k}")
+        return k
+
+    def search(self, queries, topk: int = 10, *, rerank=None, candidates=None):
+        """(nq, d) float32 queries -> (indices uint32 (nq, topk), distances float32 (nq, topk)), nearest first.
+        rerank: a FlatIndex over the same rows -- the binary search gives `candidates` per query (default 4 topk, at
+        most 1024 and n), the flat index reranks them exactly in its own metric."""
+        q = self._queries(queries)
+        k = self._topk(topk)
+        if rerank is not None:
+            return adc_then_rerank(self.search, self._n, self._dim, q, k, rerank, candidates)
+        if candidates is not None:
+            raise InvalidParameter("candidates", "only with rerank")
+        if q.shape[0] == 0:
+            return np.empty((0, k), np.uint32), np.empty((0, k), np.float32)
+        return self._index().search(q, k)
+
+    def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int) -> None:
+        """device pointers: queries [nq][d] f32, results [nq][topk] uint32 / f32 (4-byte aligned); asynchronous on the
+        current stream"""
+        k = self._topk(topk)
+        n_q = _count(nq, "nq")
+        if n_q < 0 or n_q >= 1 << 32:
+            raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
+        self._index().search_device(int(dev_queries), n_q, k, int(dev_idx), int(dev_dist))
+
+    def packed(self) -> np.ndarray:
+        """the packed rows, uint32 (n, ceil(dim / 32)), from the device"""
+        return self._index().packed()
+
+    def _host_words(self) -> np.ndarray:
+        if self._ix is not None:
+            return self._ix.packed()
+        if self._kind == _lib.BINARY_PACKED:
+            return self._src
+        if self._kind == _lib.BINARY_U8:
+            return pack_bits(self._src >= np.uint8(self._quantizer.high))
+        return pack_bits(self._src >= np.float32(self._quantizer.threshold))
+
+    # -- file -------------------------------------------------------------------------------
+    def save(self, path) -> None:
+        q = self._quantizer
+        with open(path, "wb") as f:
+            f.write(_HEADER.pack(MAGIC, self._distance.metric, self._dim, np.float32(q.threshold), q.low, q.high, self._n))
+            f.write(np.ascontiguousarray(self._host_words(), dtype="<u4").tobytes())
+
+    @classmethod
+    def load(cls, path) -> "BinaryIndex":
+        """read a VQBINIX1 file; every field is checked here, before anything can reach the device"""
+        with open(path, "rb") as f:
+            head = f.read(_HEADER.size)
+            if len(head) != _HEADER.size:
+                raise InvalidData("truncated binary index header")
+            magic, metric, dim, thr, low, high, n = _HEADER.unpack(head)
+            if magic != MAGIC:
+                raise InvalidData("not a VQBINIX1 file")
+            if metric not in _METRICS:
+                raise InvalidParameter("distance", f"metric id {metric} is not squared_euclidean, euclidean or manhattan")
+            if not 1 <= dim <= MAX_DIM:
+                raise InvalidParameter("dim", f"must be between 1 and {MAX_DIM}, got {dim}")
+            if not 1 <= n < 1 << 32:
+                raise InvalidData(f"row count {n} is outside [1, 2^32)")
+            if low > 255 or high > 255:
+                raise InvalidParameter("low/high", f"must fit in u8, got {low} / {high}")
+            quantizer = BinaryQuantizer(float(thr), low, high)  # the reference's own checks
+            w = words_per_row(dim)
+            raw = f.read(n * w * 4)
+            if len(raw) != n * w * 4:
+                raise InvalidData("truncated packed rows")
+            if f.read(1):
+                raise InvalidData("trailing bytes after the packed rows")
+        words = np.frombuffer(raw, dtype="<u4").astype(np.uint32).reshape(n, w)
+        if not _pad_ok(words, dim):
+            raise InvalidData(f"a row has a pad bit (dimension >= {dim}) set")
+        names = {_lib.SQUARED_EUCLIDEAN: "squared_euclidean", _lib.EUCLIDEAN: "euclidean", _lib.MANHATTAN: "manhattan"}
+        return cls.from_packed(words, dim, quantizer, Distance(names[metric]))

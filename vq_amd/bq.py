@@ -74,6 +74,34 @@ class BinaryQuantizer:
         """uint8 codes of any shape -> float32 of the same shape; out: a float32 array of that shape to fill"""
         return _lib.elementwise("vqhip_bq_decode", self._params, codes, np.uint8, np.float32, out)
 
+    def pack_batch(self, X, out=None) -> np.ndarray:
+        """float32 (n, d) -> uint32 (n, ceil(d / 32)) on the device: bit t % 32 of word t // 32 is x[t] >= threshold
+        (the layout of BinaryIndex, pad bits zero); out: a uint32 array of that shape to fill"""
+        x = np.ascontiguousarray(X, dtype=np.float32)
+        if x.ndim != 2:
+            raise ValueError("expected a 2D array (n, dim)")
+        n, d = x.shape
+        if d == 0:
+            raise ValueError("dimension must be at least 1")
+        w = (d + 31) // 32
+        if out is None:
+            out = np.empty((n, w), np.uint32)
+        elif out.dtype != np.uint32 or out.shape != (n, w) or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous uint32 array of shape {(n, w)}")
+        if n:
+            _lib.check(_lib.load().vqhip_bq_pack(self._threshold, x.ctypes.data_as(C.POINTER(C.c_float)), n, d,
+                                                 out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def unpack_batch(self, words, dim: int) -> np.ndarray:
+        """uint32 (n, ceil(dim / 32)) packed bits -> uint8 codes (n, dim): high where the bit is set, else low (host)"""
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        d = operator.index(dim)
+        if w.ndim != 2 or d < 1 or w.shape[1] != (d + 31) // 32:
+            raise ValueError(f"expected a 2D array (n, {(max(d, 1) + 31) // 32}) for dim {d}")
+        bits = np.unpackbits(w.astype("<u4").view(np.uint8).reshape(w.shape[0], -1), axis=1, bitorder="little")[:, :d]
+        return np.where(bits.astype(bool), np.uint8(self._high), np.uint8(self._low))
+
     def quantize_device(self, dev_x: int, count: int, dev_codes: int):
         """device pointers (x 4-byte aligned, any count), asynchronous on the current stream"""
         _lib.check(_lib.load().vqhip_bq_encode_device(*self._params, C.c_void_p(dev_x), int(count), C.c_void_p(dev_codes)))

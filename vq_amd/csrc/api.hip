@@ -2871,6 +2871,244 @@ int vqhip_flat_rerank(vqhip_flat *f, const float *queries, uint32_t nq, const ui
 
 }  // extern "C"
 
+// ------------------------------------------------------------------ binary index (k_binary.hip) ----
+struct vqhip_binary {
+    HandleSync sync;
+    uint64_t n = 0;
+    uint32_t d = 0, W = 0, low = 0, high = 1;
+    float thr = 0;
+    int metric = VQHIP_MANHATTAN;
+    DevBuf words, table;                              // [n][W] packed rows, S [d + 1]
+    DevBuf q, qw, hist, sel, adc_sel, cnt, cand, idx, out;  // per-call workspaces
+};
+
+static constexpr uint32_t kBinaryBatch = 1024;  // queries per internal batch
+
+static int binary_check(int kind, uint64_t n, uint32_t d, float threshold, uint32_t low, uint32_t high, int metric) {
+    if (kind != VQHIP_BINARY_F32 && kind != VQHIP_BINARY_U8 && kind != VQHIP_BINARY_PACKED)
+        return fail(VQHIP_ERR_INVALID_INPUT, "source kind must be 0 (f32), 1 (u8 codes) or 2 (packed words), not %d", kind);
+    if (d == 0 || d > VQHIP_BINARY_MAX_DIM) return fail(VQHIP_ERR_INVALID_INPUT, "d %u must be in [1, 8192]", d);
+    if (n == 0 || n >= (1ull << 32)) return fail(VQHIP_ERR_INVALID_INPUT, "n must be in [1, 2^32)");
+    VQ_TRY(bq_check(threshold, low, high));
+    if (vq_is_cos(metric)) return fail(VQHIP_ERR_UNSUPPORTED, "cosine is not a function of the Hamming distance alone");
+    if (metric != VQHIP_SQUARED_EUCLIDEAN && metric != VQHIP_EUCLIDEAN && metric != VQHIP_MANHATTAN)
+        return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
+    return VQHIP_OK;
+}
+
+static int binary_create(const void *src, hipMemcpyKind kind_copy, int kind, uint64_t n, uint32_t d, float threshold,
+                         uint32_t low, uint32_t high, int metric, vqhip_binary **out) {
+    if (!out) return fail(VQHIP_ERR_NULL_PTR, "out is NULL");
+    *out = nullptr;
+    if (!src) return fail(VQHIP_ERR_NULL_PTR, "source is NULL");
+    VQ_TRY(binary_check(kind, n, d, threshold, low, high, metric));
+    const uint32_t W = bin_words(d);
+    if (kind == VQHIP_BINARY_PACKED && kind_copy == hipMemcpyHostToDevice && d % 32) {
+        const uint32_t *w = static_cast<const uint32_t *>(src), mask = (1u << (d % 32)) - 1u;
+        for (uint64_t i = 0; i < n; ++i)
+            if (w[i * W + W - 1] & ~mask) return fail(VQHIP_ERR_INVALID_INPUT, "row %llu has a pad bit set", (unsigned long long)i);
+    }
+    VQ_TRY(require_gfx950());
+    hipStream_t s;
+    VQ_TRY(current_stream(&s));
+    std::unique_ptr<vqhip_binary> b(new vqhip_binary());
+    b->n = n, b->d = d, b->W = W, b->low = low, b->high = high, b->thr = threshold, b->metric = metric;
+    std::vector<float> S(d + 1);
+    binary_table(d, low, high, metric, S.data());
+    VQ_TRY(b->table.alloc((size_t)(d + 1) * 4));
+    VQ_HIP(hipMemcpyAsync(b->table.p, S.data(), (size_t)(d + 1) * 4, hipMemcpyHostToDevice, s));
+    VQ_TRY(b->words.alloc((size_t)n * W * 4));
+    if (kind == VQHIP_BINARY_PACKED) {
+        VQ_HIP(hipMemcpyAsync(b->words.p, src, (size_t)n * W * 4, kind_copy, s));
+        if (kind_copy == hipMemcpyDeviceToDevice && d % 32) {
+            DevBuf bad;
+            uint32_t h_bad = 0;
+            VQ_TRY(bad.alloc(4));
+            VQ_HIP(hipMemsetAsync(bad.p, 0, 4, s));
+            VQ_TRY(launch_bin_padcheck(b->words.as<uint32_t>(), n, d, bad.as<uint32_t>(), s));
+            VQ_HIP(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, s));
+            VQ_HIP(hipStreamSynchronize(s));
+            if (h_bad) return fail(VQHIP_ERR_INVALID_INPUT, "a packed row has a pad bit set");
+        }
+    } else if (kind_copy == hipMemcpyDeviceToDevice) {
+        VQ_TRY(launch_bq_pack(src, kind, n, d, threshold, high, b->words.as<uint32_t>(), s));
+    } else {
+        // host rows: through a staging buffer of at most 256 MB at a time
+        const size_t esz = kind == VQHIP_BINARY_U8 ? 1 : 4;
+        const uint64_t per = std::max<uint64_t>(1, (256ull << 20) / ((uint64_t)d * esz));
+        DevBuf stage;
+        VQ_TRY(stage.alloc((size_t)std::min<uint64_t>(per, n) * d * esz));
+        for (uint64_t r0 = 0; r0 < n; r0 += per) {
+            const uint64_t rn = std::min<uint64_t>(per, n - r0);
+            VQ_HIP(hipMemcpyAsync(stage.p, static_cast<const char *>(src) + r0 * d * esz, (size_t)rn * d * esz,
+                                  hipMemcpyHostToDevice, s));
+            VQ_TRY(launch_bq_pack(stage.p, kind, rn, d, threshold, high, b->words.as<uint32_t>() + r0 * W, s));
+            VQ_HIP(hipStreamSynchronize(s));
+        }
+    }
+    VQ_HIP(hipStreamSynchronize(s));  // the caller may free or change its source once this returns
+    *out = b.release();
+    return VQHIP_OK;
+}
+
+static int binary_check_topk(const vqhip_binary *b, uint32_t topk) {
+    if (topk == 0 || topk > 1024 || topk > b->n)
+        return fail(VQHIP_ERR_INVALID_INPUT, "topk %u must be in [1, min(n, 1024)] (n = %llu)", topk, (unsigned long long)b->n);
+    return VQHIP_OK;
+}
+
+// queries_dev [nq][d] f32 on the device -> [nq][topk] results on the device, enqueued on s in batches of 1024
+static int binary_search_enqueue(vqhip_binary *b, const float *queries_dev, uint32_t nq, uint32_t topk, uint32_t *idx_dev,
+                                 float *dist_dev, hipStream_t s) {
+    const uint32_t qb = std::min(nq, kBinaryBatch);
+    VQ_TRY(b->qw.ensure((size_t)qb * b->W * 4));
+    VQ_TRY(b->hist.ensure(binary_hist_bytes(qb, b->d)));
+    VQ_TRY(b->sel.ensure((size_t)qb * sizeof(BinSel)));
+    VQ_TRY(b->adc_sel.ensure((size_t)qb * 8));
+    VQ_TRY(b->cnt.ensure((size_t)qb * 4));
+    VQ_TRY(b->cand.ensure(binary_cand_bytes(qb)));
+    for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
+        const uint32_t nb = std::min(qb, nq - q0);
+        VQ_TRY(launch_bq_pack(queries_dev + (size_t)q0 * b->d, VQHIP_BINARY_F32, nb, b->d, b->thr, b->high, b->qw.as<uint32_t>(), s));
+        VQ_TRY(launch_binary_search(b->words.as<uint32_t>(), b->n, b->d, b->metric, b->table.as<float>(), b->qw.as<uint32_t>(), nb,
+                                    topk, b->hist.as<uint32_t>(), b->sel.as<BinSel>(), b->adc_sel.as<uint32_t>(),
+                                    b->cnt.as<uint32_t>(), b->cand.as<unsigned long long>(), idx_dev + (size_t)q0 * topk,
+                                    dist_dev + (size_t)q0 * topk, s));
+    }
+    return VQHIP_OK;
+}
+
+extern "C" {
+
+int vqhip_bq_pack(float threshold, const float *x, uint64_t n, uint32_t d, uint32_t *words) {
+    VQ_API_BEGIN
+    VQ_TRY(bq_check(threshold, 0, 1));
+    if (n == 0) return VQHIP_OK;
+    if (d == 0) return fail(VQHIP_ERR_INVALID_INPUT, "d must be at least 1");
+    if (!x || !words) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    VQ_TRY(require_gfx950());
+    hipStream_t s;
+    VQ_TRY(current_stream(&s));
+    const uint32_t W = bin_words(d);
+    const uint64_t per = std::max<uint64_t>(1, (256ull << 20) / ((uint64_t)d * 4));
+    const uint64_t rows = std::min<uint64_t>(per, n);
+    DevBuf dx, dw;
+    VQ_TRY(dx.alloc((size_t)rows * d * 4));
+    VQ_TRY(dw.alloc((size_t)rows * W * 4));
+    for (uint64_t r0 = 0; r0 < n; r0 += per) {
+        const uint64_t rn = std::min<uint64_t>(per, n - r0);
+        VQ_HIP(hipMemcpyAsync(dx.p, x + r0 * d, (size_t)rn * d * 4, hipMemcpyHostToDevice, s));
+        VQ_TRY(launch_bq_pack(dx.p, VQHIP_BINARY_F32, rn, d, threshold, 1, dw.as<uint32_t>(), s));
+        VQ_HIP(hipMemcpyAsync(words + r0 * W, dw.p, (size_t)rn * W * 4, hipMemcpyDeviceToHost, s));
+        VQ_HIP(hipStreamSynchronize(s));
+    }
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_bq_pack_device(float threshold, const void *dev_x, uint64_t n, uint32_t d, void *dev_words) {
+    VQ_API_BEGIN
+    VQ_TRY(bq_check(threshold, 0, 1));
+    if (n == 0) return VQHIP_OK;
+    if (d == 0) return fail(VQHIP_ERR_INVALID_INPUT, "d must be at least 1");
+    if (!dev_x || !dev_words) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (reinterpret_cast<uintptr_t>(dev_x) & 3) return fail(VQHIP_ERR_INVALID_INPUT, "x is not 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(dev_words) & 3) return fail(VQHIP_ERR_INVALID_INPUT, "words is not 4-byte aligned");
+    VQ_TRY(require_gfx950());
+    hipStream_t s;
+    VQ_TRY(current_stream(&s));
+    return launch_bq_pack(dev_x, VQHIP_BINARY_F32, n, d, threshold, 1, static_cast<uint32_t *>(dev_words), s);
+    VQ_API_END
+}
+
+int vqhip_binary_create(const void *src, int kind, uint64_t n, uint32_t d, float threshold, uint32_t low, uint32_t high,
+                        int metric, vqhip_binary **out) {
+    VQ_API_BEGIN
+    return binary_create(src, hipMemcpyHostToDevice, kind, n, d, threshold, low, high, metric, out);
+    VQ_API_END
+}
+
+int vqhip_binary_create_device(const void *dev_src, int kind, uint64_t n, uint32_t d, float threshold, uint32_t low,
+                               uint32_t high, int metric, vqhip_binary **out) {
+    VQ_API_BEGIN
+    if (kind == VQHIP_BINARY_F32 && (reinterpret_cast<uintptr_t>(dev_src) & 3))
+        return fail(VQHIP_ERR_INVALID_INPUT, "rows are not 4-byte aligned");
+    if (kind == VQHIP_BINARY_PACKED && (reinterpret_cast<uintptr_t>(dev_src) & 3))
+        return fail(VQHIP_ERR_INVALID_INPUT, "words are not 4-byte aligned");
+    return binary_create(dev_src, hipMemcpyDeviceToDevice, kind, n, d, threshold, low, high, metric, out);
+    VQ_API_END
+}
+
+int vqhip_binary_destroy(vqhip_binary *b) {
+    delete b;
+    return VQHIP_OK;
+}
+
+int vqhip_binary_info(const vqhip_binary *b, uint64_t *n, uint32_t *d, float *threshold, uint32_t *low, uint32_t *high,
+                      int *metric) {
+    if (!b) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (n) *n = b->n;
+    if (d) *d = b->d;
+    if (threshold) *threshold = b->thr;
+    if (low) *low = b->low;
+    if (high) *high = b->high;
+    if (metric) *metric = b->metric;
+    return VQHIP_OK;
+}
+
+int vqhip_binary_packed(vqhip_binary *b, uint32_t *words) {
+    VQ_API_BEGIN
+    if (!b || !words) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    VQ_TRY(require_gfx950());
+    Entry in(b->sync);
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    VQ_HIP(hipMemcpyAsync(words, b->words.p, (size_t)b->n * b->W * 4, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipStreamSynchronize(s));
+    in.synced();
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_binary_search(vqhip_binary *b, const float *queries, uint32_t nq, uint32_t topk, uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    if (!b || !queries || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    VQ_TRY(binary_check_topk(b, topk));
+    if (nq == 0) return VQHIP_OK;
+    VQ_TRY(require_gfx950());
+    Entry in(b->sync);
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    VQ_TRY(b->q.ensure((size_t)nq * b->d * 4));
+    VQ_TRY(b->idx.ensure((size_t)nq * topk * 4));
+    VQ_TRY(b->out.ensure((size_t)nq * topk * 4));
+    VQ_HIP(hipMemcpyAsync(b->q.p, queries, (size_t)nq * b->d * 4, hipMemcpyHostToDevice, s));
+    VQ_TRY(binary_search_enqueue(b, b->q.as<float>(), nq, topk, b->idx.as<uint32_t>(), b->out.as<float>(), s));
+    VQ_HIP(hipMemcpyAsync(idx_out, b->idx.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipMemcpyAsync(dist_out, b->out.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipStreamSynchronize(s));
+    in.synced();
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_binary_search_device(vqhip_binary *b, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx, void *dev_dist) {
+    VQ_API_BEGIN
+    if (!b || !dev_queries || !dev_idx || !dev_dist) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    VQ_TRY(binary_check_topk(b, topk));
+    if (nq == 0) return VQHIP_OK;
+    if (reinterpret_cast<uintptr_t>(dev_queries) & 3) return fail(VQHIP_ERR_INVALID_INPUT, "queries are not 4-byte aligned");
+    VQ_TRY(require_gfx950());
+    Entry in(b->sync);
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    return binary_search_enqueue(b, reinterpret_cast<const float *>(dev_queries), nq, topk, reinterpret_cast<uint32_t *>(dev_idx),
+                                 reinterpret_cast<float *>(dev_dist), s);
+    VQ_API_END
+}
+
+}  // extern "C"
+
 // ------------------------------------------------------------------ inverted-file PQ (k_ivf.hip) ----
 // Host state: the coarse centroids, the codebooks, and every added row's list id and codes in row order.  The device
 // state -- a flat index over the centroids, the codebooks, and the rows in list order (off / ids / codes) -- is built on

@@ -1,0 +1,410 @@
+// k_binary.hip -- the binary index: BQ bits packed 32 to a word, exact Hamming top-k over them.
+// No reference counterpart (the crate has no search function); the semantics are the ones include/vqhip.h states:
+//   bits    = x >= threshold for f32 (NaN -> 0, -0.0 == 0.0), c >= high for u8 codes (the BQ encode / decode rules)
+//   layout  = row i, dimension t in word i * W + t / 32, bit t % 32, W = ceil(d / 32), pad bits zero
+//   D(q, i) = S[H] (sqrtf(S[H]) for Euclidean), H = popcount(bits(q) xor bits(row_i)), S the host's sequential f32 table;
+//             S is strictly increasing, so (H, row) orders like (D, row) and the scans select on the integer H.
+// Schedule of one search (launch_binary_search), per batch of <= 1024 packed queries:
+//   k_bin_scan<HIST>     workgroup = (a slice of <= 65535 rows) x (a group of QG queries, their words in LDS); every lane
+//                        takes two rows at a time, XORs their words against each query's and counts bits; per query an
+//                        LDS histogram of H in 16-bit halves (a slice cannot carry a half past 65535), added to the
+//                        batch's global [q][d + 1] histogram at the end, non-zero bins only
+//   k_bin_pick           per query the cut H* (the smallest H whose cumulative count reaches topk), the rows below it and
+//                        the rows at it
+//   k_bin_scan<COLLECT>  the same scan again: rows with H < H*, and those with H == H* unless the cut is heavy, into the
+//                        query's candidate list (key adc_key(S[H]), row)
+//   k_bin_ties           heavy cut (more than 8192 candidates): the lowest need = topk - less row ids with H == H*, found
+//                        by an ordered scan over the rows that stops once it has them
+//   k_adc_sort_out       (topk.hpp) the candidates sorted by (key, row) in LDS, the first topk out, sqrtf for Euclidean
+// Roofline: VALU, 2 operations (v_xor, v_bcnt with accumulate) per 32 dimensions per (query, row) pair and scan.
+#include "kernels.hpp"
+#include "topk.hpp"
+
+#include <algorithm>
+#include <vector>
+
+namespace vqhip {
+namespace {
+
+constexpr uint32_t kPackBlock = 256;
+constexpr uint32_t kScanBlock = 256;
+constexpr uint32_t kScanRR = 2;                 // rows per lane and step of the scan
+constexpr uint64_t kSliceMax = 65535;           // rows per scan workgroup: a 16-bit histogram half never carries
+constexpr uint32_t kTiesBlock = 1024;
+
+enum { BIN_HIST = 0, BIN_COLLECT = 1 };
+
+__device__ __forceinline__ bool bq_bit(float v, float thr, uint32_t) { return v >= thr; }
+__device__ __forceinline__ bool bq_bit(uint8_t v, float, uint32_t high) { return (uint32_t)v >= high; }
+
+// bit i of the byte b -> bit 4 i
+__device__ __forceinline__ uint32_t spread4(uint32_t b) {
+    b = (b | (b << 12)) & 0x000F000Fu;
+    b = (b | (b << 6)) & 0x03030303u;
+    b = (b | (b << 3)) & 0x11111111u;
+    return b;
+}
+
+// One wave per row (grid-stride over rows).  VEC (d % 4 == 0, x 4-element aligned): windows of 256 elements, four per
+// lane in one load, four ballots; lane j < 8 assembles word j of the window from byte j of each.  Otherwise windows of 64
+// elements, one per lane, one ballot, two words.  Elements past d contribute 0: the pad bits.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kPackBlock) void k_bq_pack(const T *__restrict__ x, uint64_t n, uint32_t d, uint32_t W, float thr,
+                                                       uint32_t high, uint32_t *__restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t waves = (uint64_t)gridDim.x * (kPackBlock / 64);
+    for (uint64_t r = (uint64_t)blockIdx.x * (kPackBlock / 64) + (threadIdx.x >> 6); r < n; r += waves) {
+        const T *xr = x + r * d;
+        uint32_t *o = out + r * W;
+        if constexpr (VEC) {
+            for (uint32_t t0 = 0; t0 < d; t0 += 256) {
+                const uint32_t t = t0 + 4 * lane;
+                bool b0 = false, b1 = false, b2 = false, b3 = false;
+                if (t < d) {
+                    if constexpr (sizeof(T) == 4) {
+                        const float4 v = *reinterpret_cast<const float4 *>(xr + t);
+                        b0 = bq_bit(v.x, thr, high), b1 = bq_bit(v.y, thr, high);
+                        b2 = bq_bit(v.z, thr, high), b3 = bq_bit(v.w, thr, high);
+                    } else {
+                        const uint32_t v = *reinterpret_cast<const uint32_t *>(xr + t);
+                        b0 = (v & 0xffu) >= high, b1 = ((v >> 8) & 0xffu) >= high;
+                        b2 = ((v >> 16) & 0xffu) >= high, b3 = (v >> 24) >= high;
+                    }
+                }
+                const uint64_t m0 = __ballot(b0), m1 = __ballot(b1), m2 = __ballot(b2), m3 = __ballot(b3);
+                const uint32_t c = t0 / 32 + lane;
+                if (lane < 8 && c < W) {
+                    const uint32_t s = 8 * lane;
+                    o[c] = spread4((uint32_t)(m0 >> s) & 0xffu) | (spread4((uint32_t)(m1 >> s) & 0xffu) << 1) |
+                           (spread4((uint32_t)(m2 >> s) & 0xffu) << 2) | (spread4((uint32_t)(m3 >> s) & 0xffu) << 3);
+                }
+            }
+        } else {
+            for (uint32_t t0 = 0; t0 < d; t0 += 64) {
+                const uint32_t t = t0 + lane;
+                const uint64_t m = __ballot(t < d && bq_bit(xr[t], thr, high));
+                const uint32_t c = t0 / 32;
+                if (lane == 0) o[c] = (uint32_t)m;
+                if (lane == 1 && c + 1 < W) o[c + 1] = (uint32_t)(m >> 32);
+            }
+        }
+    }
+}
+
+// nonzero where a pad bit (dimension >= d) of a packed row is set
+__global__ __launch_bounds__(256) void k_bin_padcheck(const uint32_t *__restrict__ P, uint64_t n, uint32_t W, uint32_t mask,
+                                                      uint32_t *__restrict__ bad) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
+        if (P[i * W + (W - 1)] & ~mask) atomicOr(bad, 1u);
+}
+
+// H of QG queries for the lane's rows r[0..RR): words of the rows from global memory, of the queries from LDS
+template <uint32_t QG, bool V4>
+__device__ __forceinline__ void bin_hamming(const uint32_t *__restrict__ P, const uint64_t (&r)[kScanRR], const bool (&ok)[kScanRR],
+                                            uint32_t W, const uint32_t *qs, uint32_t (&h)[kScanRR][QG]) {
+#pragma unroll
+    for (uint32_t j = 0; j < kScanRR; ++j)
+#pragma unroll
+        for (uint32_t q = 0; q < QG; ++q) h[j][q] = 0;
+    if constexpr (V4) {
+        for (uint32_t c = 0; c < W; c += 4) {
+            uint4 w[kScanRR];
+#pragma unroll
+            for (uint32_t j = 0; j < kScanRR; ++j)
+                w[j] = ok[j] ? *reinterpret_cast<const uint4 *>(P + r[j] * W + c) : make_uint4(0, 0, 0, 0);
+#pragma unroll
+            for (uint32_t q = 0; q < QG; ++q) {
+                const uint4 v = *reinterpret_cast<const uint4 *>(qs + q * W + c);
+#pragma unroll
+                for (uint32_t j = 0; j < kScanRR; ++j) {
+                    uint32_t a = h[j][q];
+                    a = __builtin_popcount(w[j].x ^ v.x) + a;
+                    a = __builtin_popcount(w[j].y ^ v.y) + a;
+                    a = __builtin_popcount(w[j].z ^ v.z) + a;
+                    a = __builtin_popcount(w[j].w ^ v.w) + a;
+                    h[j][q] = a;
+                }
+            }
+        }
+    } else {
+        for (uint32_t c = 0; c < W; ++c) {
+            uint32_t w[kScanRR];
+#pragma unroll
+            for (uint32_t j = 0; j < kScanRR; ++j) w[j] = ok[j] ? P[r[j] * W + c] : 0u;
+#pragma unroll
+            for (uint32_t q = 0; q < QG; ++q) {
+                const uint32_t v = qs[q * W + c];
+#pragma unroll
+                for (uint32_t j = 0; j < kScanRR; ++j) h[j][q] = __builtin_popcount(w[j] ^ v) + h[j][q];
+            }
+        }
+    }
+}
+
+// Q [nb][W] packed queries of the batch; workgroup (x, y) scans rows [x * slice, (x + 1) * slice) for queries
+// [y * QG, y * QG + QG) of them.  HIST: adds each query's histogram of H to hist [nb][d + 1].  COLLECT: appends the rows
+// that sel admits to cand [nb][kAdcCand] through the counters cnt [nb].
+template <uint32_t QG, bool V4, int MODE>
+__global__ __launch_bounds__(kScanBlock) void k_bin_scan(const uint32_t *__restrict__ P, uint64_t n, uint32_t W, uint32_t d,
+                                                        const uint32_t *__restrict__ Q, uint32_t nb, uint64_t slice,
+                                                        uint32_t *__restrict__ hist, const BinSel *__restrict__ sel,
+                                                        const float *__restrict__ S, unsigned long long *__restrict__ cand,
+                                                        uint32_t *__restrict__ cnt) {
+    extern __shared__ uint32_t lds[];
+    uint32_t *qs = lds;                 // [QG][W]
+    uint32_t *hs = lds + QG * W;        // HIST: [QG][(d + 2) / 2] bin pairs; COLLECT: [QG][2] (cut, take ties)
+    const uint32_t q0 = blockIdx.y * QG;
+    const uint32_t qn = min(QG, nb - q0);
+    const uint32_t H2 = (d + 2) / 2;
+    for (uint32_t e = threadIdx.x; e < QG * W; e += kScanBlock) qs[e] = e / W < qn ? Q[(size_t)(q0 + e / W) * W + e % W] : 0u;
+    if constexpr (MODE == BIN_HIST) {
+        for (uint32_t e = threadIdx.x; e < QG * H2; e += kScanBlock) hs[e] = 0;
+    } else {
+        for (uint32_t q = threadIdx.x; q < QG; q += kScanBlock) {
+            hs[2 * q] = q < qn ? sel[q0 + q].hstar : 0u;
+            hs[2 * q + 1] = q < qn ? (sel[q0 + q].heavy ? 0u : 1u) : 0u;
+        }
+    }
+    __syncthreads();
+    const uint64_t lo = (uint64_t)blockIdx.x * slice, hi = min(n, lo + slice);
+    for (uint64_t base = lo + threadIdx.x; base < hi; base += kScanBlock * kScanRR) {
+        uint64_t r[kScanRR];
+        bool ok[kScanRR];
+#pragma unroll
+        for (uint32_t j = 0; j < kScanRR; ++j) {
+            r[j] = base + (uint64_t)j * kScanBlock;
+            ok[j] = r[j] < hi;
+        }
+        uint32_t h[kScanRR][QG];
+        bin_hamming<QG, V4>(P, r, ok, W, qs, h);
+#pragma unroll
+        for (uint32_t q = 0; q < QG; ++q) {
+#pragma unroll
+            for (uint32_t j = 0; j < kScanRR; ++j) {
+                if (!ok[j] || q >= qn) continue;
+                const uint32_t v = h[j][q];
+                if constexpr (MODE == BIN_HIST) {
+                    atomicAdd(&hs[q * H2 + (v >> 1)], 1u << ((v & 1u) << 4));
+                } else {
+                    const uint32_t cut = hs[2 * q];
+                    if (v < cut || (v == cut && hs[2 * q + 1])) {
+                        const uint32_t pos = atomicAdd(&cnt[q0 + q], 1u);
+                        if (pos < kAdcCand)
+                            cand[(size_t)(q0 + q) * kAdcCand + pos] =
+                                ((unsigned long long)adc_key(S[v]) << 32) | (uint32_t)r[j];
+                    }
+                }
+            }
+        }
+    }
+    if constexpr (MODE == BIN_HIST) {
+        __syncthreads();
+        for (uint32_t e = threadIdx.x; e < qn * H2; e += kScanBlock) {
+            const uint32_t v = hs[e];
+            if (!v) continue;
+            const uint32_t q = e / H2, b = 2 * (e % H2);
+            uint32_t *g = hist + (size_t)(q0 + q) * (d + 1);
+            if (v & 0xffffu) atomicAdd(&g[b], v & 0xffffu);
+            if ((v >> 16) && b + 1 <= d) atomicAdd(&g[b + 1], v >> 16);
+        }
+    }
+}
+
+// per query: the cut H* = the smallest H with count(H' <= H) >= topk; rows below it, rows at it; adc_sel [2 q + 1] = the
+// candidates k_adc_sort_out will find (heavy: topk)
+__global__ __launch_bounds__(256) void k_bin_pick(const uint32_t *__restrict__ hist, uint32_t d, uint32_t topk,
+                                                  BinSel *__restrict__ sel, uint32_t *__restrict__ adc_sel,
+                                                  uint32_t *__restrict__ cnt) {
+    __shared__ unsigned long long seg_sum[256];
+    __shared__ unsigned long long s_before;
+    __shared__ uint32_t s_seg;
+    const uint32_t q = blockIdx.x, t = threadIdx.x;
+    const uint32_t bins = d + 1, per = (bins + 255) / 256;
+    const uint32_t *hq = hist + (size_t)q * bins;
+    const uint32_t b0 = min(bins, t * per), b1 = min(bins, b0 + per);
+    unsigned long long s = 0;
+    for (uint32_t b = b0; b < b1; ++b) s += hq[b];
+    seg_sum[t] = s;
+    __syncthreads();
+    if (t == 0) {
+        unsigned long long cum = 0;
+        uint32_t j = 0;
+        for (; j < 255; ++j) {
+            if (cum + seg_sum[j] >= topk) break;
+            cum += seg_sum[j];
+        }
+        s_before = cum;
+        s_seg = j;
+    }
+    __syncthreads();
+    if (t == s_seg) {
+        unsigned long long cum = s_before;
+        uint32_t b = b0;
+        for (; b + 1 < b1; ++b) {
+            if (cum + hq[b] >= topk) break;
+            cum += hq[b];
+        }
+        const unsigned long long eq = hq[b];
+        const bool heavy = cum + eq > kAdcCand;
+        sel[q] = BinSel{b, (uint32_t)cum, topk - (uint32_t)cum, heavy ? 1u : 0u};
+        adc_sel[2 * q] = b;
+        adc_sel[2 * q + 1] = heavy ? topk : (uint32_t)(cum + eq);
+        cnt[q] = 0;
+    }
+}
+
+// heavy cut: the lowest sel.need row ids with H == H*, by an ordered scan in chunks of 1024 rows, to cand [q][less ..)
+__global__ __launch_bounds__(kTiesBlock) void k_bin_ties(const uint32_t *__restrict__ P, uint64_t n, uint32_t W,
+                                                         const uint32_t *__restrict__ Q, const BinSel *__restrict__ sel,
+                                                         const float *__restrict__ S, unsigned long long *__restrict__ cand) {
+    const uint32_t q = blockIdx.x;
+    const BinSel s = sel[q];
+    if (!s.heavy) return;
+    extern __shared__ uint32_t qw[];  // [W]
+    __shared__ uint32_t wsum[kTiesBlock / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (uint32_t c = tid; c < W; c += kTiesBlock) qw[c] = Q[(size_t)q * W + c];
+    __syncthreads();
+    const unsigned long long key = (unsigned long long)adc_key(S[s.hstar]) << 32;
+    unsigned long long *out = cand + (size_t)q * kAdcCand + s.less;
+    uint32_t taken = 0;  // uniform
+    for (uint64_t base = 0; base < n && taken < s.need; base += kTiesBlock) {
+        const uint64_t i = base + tid;
+        bool eq = false;
+        if (i < n) {
+            uint32_t h = 0;
+            for (uint32_t c = 0; c < W; ++c) h = __builtin_popcount(P[i * W + c] ^ qw[c]) + h;
+            eq = h == s.hstar;
+        }
+        const uint64_t m = __ballot(eq);
+        if (lane == 0) wsum[wv] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t before = (uint32_t)__popcll(m & ((1ull << lane) - 1ull)), total = 0;
+        for (uint32_t w = 0; w < kTiesBlock / 64; ++w) {
+            if (w < wv) before += wsum[w];
+            total += wsum[w];
+        }
+        if (eq && taken + before < s.need) out[taken + before] = key | (uint32_t)i;
+        taken += total;
+        __syncthreads();
+    }
+}
+
+// QG queries per scan workgroup: their H histograms in 16-bit halves must fit in LDS with room for two workgroups a CU
+// where d allows it
+uint32_t bin_qg(uint32_t d) { return d <= 1024 ? 32u : 8u; }
+
+size_t bin_scan_lds(uint32_t qg, uint32_t W, uint32_t d, int mode) {
+    return (size_t)qg * W * 4 + (mode == BIN_HIST ? (size_t)qg * ((d + 2) / 2) * 4 : (size_t)qg * 2 * 4);
+}
+
+template <uint32_t QG, bool V4, int MODE>
+int bin_scan_launch(dim3 grid, size_t lds, const uint32_t *P, uint64_t n, uint32_t W, uint32_t d, const uint32_t *Q, uint32_t nb,
+                    uint64_t slice, uint32_t *hist, const BinSel *sel, const float *S, unsigned long long *cand, uint32_t *cnt,
+                    hipStream_t stream) {
+    static PerDeviceOnce attr;
+    if (attr.needed()) {
+        VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bin_scan<QG, V4, MODE>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr.done();
+    }
+    hipLaunchKernelGGL((k_bin_scan<QG, V4, MODE>), grid, dim3(kScanBlock), lds, stream, P, n, W, d, Q, nb, slice, hist, sel, S,
+                       cand, cnt);
+    VQ_LAUNCH_CHECK("k_bin_scan");
+    return VQHIP_OK;
+}
+
+template <int MODE>
+int bin_scan(const uint32_t *P, uint64_t n, uint32_t W, uint32_t d, const uint32_t *Q, uint32_t nb, uint32_t *hist,
+             const BinSel *sel, const float *S, unsigned long long *cand, uint32_t *cnt, hipStream_t stream) {
+    const uint32_t qg = bin_qg(d), groups = (nb + qg - 1) / qg;
+    // slices: at most 65535 rows each, and about 2048 workgroups in all where n allows 512 rows a workgroup
+    uint64_t slices = std::max<uint64_t>((n + kSliceMax - 1) / kSliceMax,
+                                         std::min<uint64_t>((2048 + groups - 1) / groups, (n + 511) / 512));
+    const uint64_t slice = (n + slices - 1) / slices;
+    slices = (n + slice - 1) / slice;
+    const dim3 grid((uint32_t)slices, groups);
+    const size_t lds = bin_scan_lds(qg, W, d, MODE);
+    const bool v4 = W % 4 == 0;
+    if (qg == 32)
+        return v4 ? bin_scan_launch<32, true, MODE>(grid, lds, P, n, W, d, Q, nb, slice, hist, sel, S, cand, cnt, stream)
+                  : bin_scan_launch<32, false, MODE>(grid, lds, P, n, W, d, Q, nb, slice, hist, sel, S, cand, cnt, stream);
+    return v4 ? bin_scan_launch<8, true, MODE>(grid, lds, P, n, W, d, Q, nb, slice, hist, sel, S, cand, cnt, stream)
+              : bin_scan_launch<8, false, MODE>(grid, lds, P, n, W, d, Q, nb, slice, hist, sel, S, cand, cnt, stream);
+}
+
+template <typename T, bool VEC>
+int pack_launch(const T *x, uint64_t n, uint32_t d, float thr, uint32_t high, uint32_t *out, hipStream_t stream) {
+    const uint64_t blocks = std::min<uint64_t>((n + kPackBlock / 64 - 1) / (kPackBlock / 64), 8192);
+    hipLaunchKernelGGL((k_bq_pack<T, VEC>), dim3((uint32_t)std::max<uint64_t>(blocks, 1)), dim3(kPackBlock), 0, stream, x, n, d,
+                       bin_words(d), thr, high, out);
+    VQ_LAUNCH_CHECK("k_bq_pack");
+    return VQHIP_OK;
+}
+
+}  // namespace
+
+uint32_t bin_words(uint32_t d) { return (d + 31) / 32; }
+
+int binary_table(uint32_t d, uint32_t low, uint32_t high, int metric, float *S) {
+    const float a = (float)high - (float)low;
+    const float t = metric == VQHIP_MANHATTAN ? a : a * a;
+    float s = 0.0f;  // -0.0 + +0.0 (d >= 1 agreeing dimensions or not) = +0.0
+    S[0] = s;
+    for (uint32_t j = 1; j <= d; ++j) {
+        s = s + t;
+        S[j] = s;
+    }
+    return VQHIP_OK;
+}
+
+int launch_bq_pack(const void *x, int kind, uint64_t n, uint32_t d, float thr, uint32_t high, uint32_t *out, hipStream_t stream) {
+    if (n == 0) return VQHIP_OK;
+    if (kind == VQHIP_BINARY_U8) {
+        const uint8_t *c = static_cast<const uint8_t *>(x);
+        if (d % 4 == 0 && (reinterpret_cast<uintptr_t>(c) & 3) == 0) return pack_launch<uint8_t, true>(c, n, d, thr, high, out, stream);
+        return pack_launch<uint8_t, false>(c, n, d, thr, high, out, stream);
+    }
+    const float *f = static_cast<const float *>(x);
+    if (d % 4 == 0 && (reinterpret_cast<uintptr_t>(f) & 15) == 0) return pack_launch<float, true>(f, n, d, thr, high, out, stream);
+    return pack_launch<float, false>(f, n, d, thr, high, out, stream);
+}
+
+int launch_bin_padcheck(const uint32_t *P, uint64_t n, uint32_t d, uint32_t *bad, hipStream_t stream) {
+    if (d % 32 == 0 || n == 0) return VQHIP_OK;
+    const uint32_t W = bin_words(d), mask = (1u << (d % 32)) - 1u;
+    const uint64_t blocks = std::min<uint64_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_bin_padcheck, dim3((uint32_t)blocks), dim3(256), 0, stream, P, n, W, mask, bad);
+    VQ_LAUNCH_CHECK("k_bin_padcheck");
+    return VQHIP_OK;
+}
+
+size_t binary_hist_bytes(uint32_t qb, uint32_t d) { return (size_t)qb * (d + 1) * 4; }
+size_t binary_cand_bytes(uint32_t qb) { return (size_t)qb * kAdcCand * 8; }
+
+int launch_binary_search(const uint32_t *P, uint64_t n, uint32_t d, int metric, const float *S, const uint32_t *Q, uint32_t nb,
+                         uint32_t topk, uint32_t *hist, BinSel *sel, uint32_t *adc_sel, uint32_t *cnt,
+                         unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream) {
+    if (topk == 0 || topk > 1024 || topk > n) return fail(VQHIP_ERR_INVALID_INPUT, "topk must be in [1, min(n, 1024)]");
+    if (nb == 0) return VQHIP_OK;
+    static PerDeviceOnce attr;
+    if (attr.needed()) {
+        VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_adc_sort_out), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)(kAdcCand * 8)));
+        attr.done();
+    }
+    const uint32_t W = bin_words(d);
+    VQ_HIP(hipMemsetAsync(hist, 0, binary_hist_bytes(nb, d), stream));
+    VQ_TRY(bin_scan<BIN_HIST>(P, n, W, d, Q, nb, hist, sel, S, cand, cnt, stream));
+    hipLaunchKernelGGL(k_bin_pick, dim3(nb), dim3(256), 0, stream, hist, d, topk, sel, adc_sel, cnt);
+    VQ_LAUNCH_CHECK("k_bin_pick");
+    VQ_TRY(bin_scan<BIN_COLLECT>(P, n, W, d, Q, nb, hist, sel, S, cand, cnt, stream));
+    hipLaunchKernelGGL(k_bin_ties, dim3(nb), dim3(kTiesBlock), (size_t)W * 4, stream, P, n, W, Q, sel, S, cand);
+    VQ_LAUNCH_CHECK("k_bin_ties");
+    hipLaunchKernelGGL(k_adc_sort_out, dim3(nb), dim3(1024), (size_t)kAdcCand * 8, stream, cand, adc_sel, topk,
+                       metric == VQHIP_EUCLIDEAN ? 1 : 0, idx_out, dist_out);
+    VQ_LAUNCH_CHECK("k_adc_sort_out");
+    return VQHIP_OK;
+}
+
+}  // namespace vqhip

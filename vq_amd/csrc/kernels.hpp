@@ -337,6 +337,25 @@ int launch_gather_f16(const CodebookView &cb, const uint8_t *codes, uint64_t n, 
 int launch_decode_f32(const CodebookView &cb, const uint8_t *codes, uint64_t n, float *out,
                       hipStream_t stream);
 int launch_dequant_f16(const uint16_t *in, uint64_t count, float *out, hipStream_t stream);
+// binary index: BQ bits packed 32 to a word, exact Hamming top-k (k_binary.hip).  x [n][d] f32 (kind VQHIP_BINARY_F32:
+// bit = x >= thr) or u8 codes (VQHIP_BINARY_U8: bit = c >= high) -> out [n][bin_words(d)], pad bits zero.
+struct BinSel {
+    uint32_t hstar, less, need, heavy;  // the cut, rows below it, rows at it that belong to the result, cut too dense
+};
+uint32_t bin_words(uint32_t d);
+// S [d + 1]: S[0] = +0.0, S[j] = S[j - 1] + t in sequential f32, t = a * a (squared / Euclidean) or a (Manhattan)
+int binary_table(uint32_t d, uint32_t low, uint32_t high, int metric, float *S);
+int launch_bq_pack(const void *x, int kind, uint64_t n, uint32_t d, float thr, uint32_t high, uint32_t *out, hipStream_t stream);
+// *bad |= 1 where a packed row has a pad bit set (the caller zeroes it first)
+int launch_bin_padcheck(const uint32_t *P, uint64_t n, uint32_t d, uint32_t *bad, hipStream_t stream);
+size_t binary_hist_bytes(uint32_t qb, uint32_t d);
+size_t binary_cand_bytes(uint32_t qb);
+// Q [nb][W] packed queries, nb <= 1024; workspaces hist >= binary_hist_bytes(nb, d), sel [nb], adc_sel [2 nb], cnt [nb],
+// cand >= binary_cand_bytes(nb); results [nb][topk] on the device
+int launch_binary_search(const uint32_t *P, uint64_t n, uint32_t d, int metric, const float *S, const uint32_t *Q, uint32_t nb,
+                         uint32_t topk, uint32_t *hist, BinSel *sel, uint32_t *adc_sel, uint32_t *cnt,
+                         unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream);
+
 int launch_synth_uniform(float *X, uint64_t n, uint32_t d, uint64_t seed, uint64_t row_offset,
                          hipStream_t stream);
 void synth_uniform_host(float *out, uint64_t n, uint32_t d, uint64_t seed, uint64_t row_offset);
