@@ -100,7 +100,7 @@ def test_data_corners(orc, metric):
 
 @pytest.mark.parametrize("metric", METRICS)
 def test_dense_cut_radix_select(orc, metric):
-    """cuts of more than 8192 positions go to k_ivf_topk_dense, the exact radix select over (key, row id).  Every probed
+    """cuts of more than 8192 positions go to k_adc_topk (topk.hpp), the exact radix select over (key, row id).  Every probed
     list here holds about 10000 rows, so |S(q)| > 8192 at every nprobe, and each query puts more than 8192 of them in one
     histogram bin: a NaN or +-inf component (all distances NaN / inf: the range collapses, every position in one bin), a
     query on a block of 27000 duplicate rows (more than 8192 equal smallest distances per list), and all codes equal."""

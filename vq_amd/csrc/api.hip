@@ -2356,7 +2356,7 @@ int vqhip_pq_adc_search_device(vqhip_pq_encoder *enc, const void *dev_codes, uin
         VQ_TRY(enc->adc_lut.ensure((size_t)qg * m * k * 4));
         VQ_TRY(enc->adc_dist.ensure((size_t)qg * n * 4));
         VQ_TRY(enc->adc_state.ensure(adc_state_bytes(qg)));
-        VQ_TRY(enc->adc_cand.ensure(adc_cand_bytes(qg)));
+        VQ_TRY(enc->adc_cand.ensure(topk_cand_bytes(qg)));
         return launch_adc_search(enc->cs.cb.as<float>(), m, k, sd, enc->metric, reinterpret_cast<const uint8_t *>(dev_codes), n,
                                  enc->adc_q.as<float>() + (size_t)q0 * dim, cnt, topk, enc->adc_lut.as<float>(), enc->adc_dist.as<float>(),
                                  enc->adc_state.p, enc->adc_cand.as<unsigned long long>(), enc->adc_idx.as<uint32_t>() + (size_t)q0 * topk,
@@ -2744,9 +2744,29 @@ static int flat_create(const void *src, hipMemcpyKind kind, uint64_t n, uint32_t
     return VQHIP_OK;
 }
 
-static int flat_check_topk(const vqhip_flat *f, uint32_t topk) {
-    if (topk == 0 || topk > 1024 || topk > f->n)
-        return fail(VQHIP_ERR_INVALID_INPUT, "topk %u must be in [1, min(n, 1024)] (n = %llu)", topk, (unsigned long long)f->n);
+// every index's search takes 1 <= topk <= min(n, 1024)
+static int check_topk(uint64_t n, uint32_t topk) {
+    if (topk == 0 || topk > 1024 || topk > n)
+        return fail(VQHIP_ERR_INVALID_INPUT, "topk %u must be in [1, min(n, 1024)] (n = %llu)", topk, (unsigned long long)n);
+    return VQHIP_OK;
+}
+
+// The host form of a search: nq rows of `width` floats go up into q, `enqueue` queues the device form over q / idx / out
+// on s, and the [nq][rw] results come down into idx_out and dist_out after one wait.  out and dist_out NULL: a search with
+// one result array (the probe).
+template <class F>
+static int host_search(Entry &in, hipStream_t s, DevBuf &q, DevBuf &idx, DevBuf *out, const float *queries, uint32_t nq,
+                       uint32_t width, uint32_t rw, uint32_t *idx_out, float *dist_out, F &&enqueue) {
+    const size_t res_b = (size_t)nq * rw * 4;
+    VQ_TRY(q.ensure((size_t)nq * width * 4));
+    VQ_TRY(idx.ensure(res_b));
+    if (out) VQ_TRY(out->ensure(res_b));
+    VQ_HIP(hipMemcpyAsync(q.p, queries, (size_t)nq * width * 4, hipMemcpyHostToDevice, s));
+    VQ_TRY(enqueue());
+    VQ_HIP(hipMemcpyAsync(idx_out, idx.p, res_b, hipMemcpyDeviceToHost, s));
+    if (out) VQ_HIP(hipMemcpyAsync(dist_out, out->p, res_b, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipStreamSynchronize(s));
+    in.synced();
     return VQHIP_OK;
 }
 
@@ -2756,7 +2776,7 @@ static int flat_search_enqueue(vqhip_flat *f, const float *queries_dev, uint32_t
     const uint32_t qb = knn_query_batch(f->n, nq);
     VQ_TRY(f->dist.ensure((size_t)qb * f->n * 4));
     VQ_TRY(f->state.ensure(knn_state_bytes(qb)));
-    VQ_TRY(f->cand.ensure(knn_cand_bytes(qb)));
+    VQ_TRY(f->cand.ensure(topk_cand_bytes(qb)));
     const float *qn = nullptr;
     if (vq_is_cos(f->metric)) {
         VQ_TRY(f->qnorm.ensure((size_t)nq * 4));
@@ -2798,29 +2818,22 @@ int vqhip_flat_info(const vqhip_flat *f, uint64_t *n, uint32_t *d, int *dtype, i
 int vqhip_flat_search(vqhip_flat *f, const float *queries, uint32_t nq, uint32_t topk, uint32_t *idx_out, float *dist_out) {
     VQ_API_BEGIN
     if (!f || !queries || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    VQ_TRY(flat_check_topk(f, topk));
+    VQ_TRY(check_topk(f->n, topk));
     if (nq == 0) return VQHIP_OK;
     VQ_TRY(require_gfx950());
     Entry in(f->sync);
     hipStream_t s;
     VQ_TRY(in.stream(&s));
-    VQ_TRY(f->q.ensure((size_t)nq * f->d * 4));
-    VQ_TRY(f->idx.ensure((size_t)nq * topk * 4));
-    VQ_TRY(f->out.ensure((size_t)nq * topk * 4));
-    VQ_HIP(hipMemcpyAsync(f->q.p, queries, (size_t)nq * f->d * 4, hipMemcpyHostToDevice, s));
-    VQ_TRY(flat_search_enqueue(f, f->q.as<float>(), nq, topk, f->idx.as<uint32_t>(), f->out.as<float>(), s));
-    VQ_HIP(hipMemcpyAsync(idx_out, f->idx.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
-    VQ_HIP(hipMemcpyAsync(dist_out, f->out.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
-    VQ_HIP(hipStreamSynchronize(s));
-    in.synced();
-    return VQHIP_OK;
+    return host_search(in, s, f->q, f->idx, &f->out, queries, nq, f->d, topk, idx_out, dist_out, [&] {
+        return flat_search_enqueue(f, f->q.as<float>(), nq, topk, f->idx.as<uint32_t>(), f->out.as<float>(), s);
+    });
     VQ_API_END
 }
 
 int vqhip_flat_search_device(vqhip_flat *f, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx, void *dev_dist) {
     VQ_API_BEGIN
     if (!f || !dev_queries || !dev_idx || !dev_dist) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    VQ_TRY(flat_check_topk(f, topk));
+    VQ_TRY(check_topk(f->n, topk));
     if (nq == 0) return VQHIP_OK;
     VQ_TRY(require_gfx950());
     Entry in(f->sync);
@@ -2951,12 +2964,6 @@ static int binary_create(const void *src, hipMemcpyKind kind_copy, int kind, uin
     return VQHIP_OK;
 }
 
-static int binary_check_topk(const vqhip_binary *b, uint32_t topk) {
-    if (topk == 0 || topk > 1024 || topk > b->n)
-        return fail(VQHIP_ERR_INVALID_INPUT, "topk %u must be in [1, min(n, 1024)] (n = %llu)", topk, (unsigned long long)b->n);
-    return VQHIP_OK;
-}
-
 // queries_dev [nq][d] f32 on the device -> [nq][topk] results on the device, enqueued on s in batches of 1024
 static int binary_search_enqueue(vqhip_binary *b, const float *queries_dev, uint32_t nq, uint32_t topk, uint32_t *idx_dev,
                                  float *dist_dev, hipStream_t s) {
@@ -2966,7 +2973,7 @@ static int binary_search_enqueue(vqhip_binary *b, const float *queries_dev, uint
     VQ_TRY(b->sel.ensure((size_t)qb * sizeof(BinSel)));
     VQ_TRY(b->adc_sel.ensure((size_t)qb * 8));
     VQ_TRY(b->cnt.ensure((size_t)qb * 4));
-    VQ_TRY(b->cand.ensure(binary_cand_bytes(qb)));
+    VQ_TRY(b->cand.ensure(topk_cand_bytes(qb)));
     for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
         const uint32_t nb = std::min(qb, nq - q0);
         VQ_TRY(launch_bq_pack(queries_dev + (size_t)q0 * b->d, VQHIP_BINARY_F32, nb, b->d, b->thr, b->high, b->qw.as<uint32_t>(), s));
@@ -3073,29 +3080,22 @@ int vqhip_binary_packed(vqhip_binary *b, uint32_t *words) {
 int vqhip_binary_search(vqhip_binary *b, const float *queries, uint32_t nq, uint32_t topk, uint32_t *idx_out, float *dist_out) {
     VQ_API_BEGIN
     if (!b || !queries || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    VQ_TRY(binary_check_topk(b, topk));
+    VQ_TRY(check_topk(b->n, topk));
     if (nq == 0) return VQHIP_OK;
     VQ_TRY(require_gfx950());
     Entry in(b->sync);
     hipStream_t s;
     VQ_TRY(in.stream(&s));
-    VQ_TRY(b->q.ensure((size_t)nq * b->d * 4));
-    VQ_TRY(b->idx.ensure((size_t)nq * topk * 4));
-    VQ_TRY(b->out.ensure((size_t)nq * topk * 4));
-    VQ_HIP(hipMemcpyAsync(b->q.p, queries, (size_t)nq * b->d * 4, hipMemcpyHostToDevice, s));
-    VQ_TRY(binary_search_enqueue(b, b->q.as<float>(), nq, topk, b->idx.as<uint32_t>(), b->out.as<float>(), s));
-    VQ_HIP(hipMemcpyAsync(idx_out, b->idx.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
-    VQ_HIP(hipMemcpyAsync(dist_out, b->out.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
-    VQ_HIP(hipStreamSynchronize(s));
-    in.synced();
-    return VQHIP_OK;
+    return host_search(in, s, b->q, b->idx, &b->out, queries, nq, b->d, topk, idx_out, dist_out, [&] {
+        return binary_search_enqueue(b, b->q.as<float>(), nq, topk, b->idx.as<uint32_t>(), b->out.as<float>(), s);
+    });
     VQ_API_END
 }
 
 int vqhip_binary_search_device(vqhip_binary *b, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx, void *dev_dist) {
     VQ_API_BEGIN
     if (!b || !dev_queries || !dev_idx || !dev_dist) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    VQ_TRY(binary_check_topk(b, topk));
+    VQ_TRY(check_topk(b->n, topk));
     if (nq == 0) return VQHIP_OK;
     if (reinterpret_cast<uintptr_t>(dev_queries) & 3) return fail(VQHIP_ERR_INVALID_INPUT, "queries are not 4-byte aligned");
     VQ_TRY(require_gfx950());
@@ -3138,12 +3138,6 @@ struct vqhip_ivfpq {
 static int ivfpq_check_probe(const vqhip_ivfpq *ix, uint32_t nprobe) {
     const uint32_t hi = std::min<uint32_t>(ix->nlist, 1024);
     if (nprobe == 0 || nprobe > hi) return fail(VQHIP_ERR_INVALID_INPUT, "nprobe %u must be in [1, min(nlist, 1024)] = [1, %u]", nprobe, hi);
-    return VQHIP_OK;
-}
-
-static int ivfpq_check_topk(const vqhip_ivfpq *ix, uint32_t topk) {
-    if (topk == 0 || topk > 1024 || topk > ix->n)
-        return fail(VQHIP_ERR_INVALID_INPUT, "topk %u must be in [1, min(n, 1024)] (n = %llu)", topk, (unsigned long long)ix->n);
     return VQHIP_OK;
 }
 
@@ -3227,8 +3221,8 @@ static int ivfpq_search_enqueue(vqhip_ivfpq *ix, const float *queries_dev, uint3
     VQ_TRY(ix->pref.ensure((size_t)nb_max * (nprobe + 1) * 4));
     VQ_TRY(ix->seg.ensure((size_t)nb_max * nprobe * 4));
     VQ_TRY(ix->W.ensure((size_t)nb_max * wstride * 4));
-    VQ_TRY(ix->state.ensure(ivf_state_bytes(nb_max)));
-    VQ_TRY(ix->cand.ensure(ivf_cand_bytes(nb_max)));
+    VQ_TRY(ix->state.ensure(topk_state_bytes(nb_max)));
+    VQ_TRY(ix->cand.ensure(topk_cand_bytes(nb_max)));
     // expected positions per query: the mean list size times nprobe
     const uint64_t per_q = std::max<uint64_t>(1, (uint64_t)((double)ix->n * nprobe / ix->nlist));
     for (uint32_t q0 = 0; q0 < nq; q0 += nb_max) {
@@ -3361,14 +3355,9 @@ int vqhip_ivfpq_probe(vqhip_ivfpq *ix, const float *queries, uint32_t nq, uint32
     hipStream_t s;
     VQ_TRY(in.stream(&s));
     VQ_TRY(ivfpq_ready(ix, s));
-    VQ_TRY(ix->q.ensure((size_t)nq * ix->dim * 4));
-    VQ_TRY(ix->idx.ensure((size_t)nq * nprobe * 4));
-    VQ_HIP(hipMemcpyAsync(ix->q.p, queries, (size_t)nq * ix->dim * 4, hipMemcpyHostToDevice, s));
-    VQ_TRY(ivfpq_probe_enqueue(ix, ix->q.as<float>(), nq, nprobe, ix->idx.as<uint32_t>(), s));
-    VQ_HIP(hipMemcpyAsync(lists_out, ix->idx.p, (size_t)nq * nprobe * 4, hipMemcpyDeviceToHost, s));
-    VQ_HIP(hipStreamSynchronize(s));
-    in.synced();
-    return VQHIP_OK;
+    return host_search(in, s, ix->q, ix->idx, nullptr, queries, nq, ix->dim, nprobe, lists_out, nullptr, [&] {
+        return ivfpq_probe_enqueue(ix, ix->q.as<float>(), nq, nprobe, ix->idx.as<uint32_t>(), s);
+    });
     VQ_API_END
 }
 
@@ -3378,23 +3367,16 @@ int vqhip_ivfpq_search(vqhip_ivfpq *ix, const float *queries, uint32_t nq, uint3
     if (!ix || !queries || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
     Entry in(ix->sync);  // (n changes under add: read under the lock)
     VQ_TRY(ivfpq_check_probe(ix, nprobe));
-    VQ_TRY(ivfpq_check_topk(ix, topk));
+    VQ_TRY(check_topk(ix->n, topk));
     if (nq == 0) return VQHIP_OK;
     VQ_TRY(require_gfx950());
     VQ_TRY(ivfpq_device(ix));
     hipStream_t s;
     VQ_TRY(in.stream(&s));
     VQ_TRY(ivfpq_ready(ix, s));
-    VQ_TRY(ix->q.ensure((size_t)nq * ix->dim * 4));
-    VQ_TRY(ix->idx.ensure((size_t)nq * topk * 4));
-    VQ_TRY(ix->out.ensure((size_t)nq * topk * 4));
-    VQ_HIP(hipMemcpyAsync(ix->q.p, queries, (size_t)nq * ix->dim * 4, hipMemcpyHostToDevice, s));
-    VQ_TRY(ivfpq_search_enqueue(ix, ix->q.as<float>(), nq, nprobe, topk, ix->idx.as<uint32_t>(), ix->out.as<float>(), s));
-    VQ_HIP(hipMemcpyAsync(idx_out, ix->idx.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
-    VQ_HIP(hipMemcpyAsync(dist_out, ix->out.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
-    VQ_HIP(hipStreamSynchronize(s));
-    in.synced();
-    return VQHIP_OK;
+    return host_search(in, s, ix->q, ix->idx, &ix->out, queries, nq, ix->dim, topk, idx_out, dist_out, [&] {
+        return ivfpq_search_enqueue(ix, ix->q.as<float>(), nq, nprobe, topk, ix->idx.as<uint32_t>(), ix->out.as<float>(), s);
+    });
     VQ_API_END
 }
 
@@ -3404,7 +3386,7 @@ int vqhip_ivfpq_search_device(vqhip_ivfpq *ix, const void *dev_queries, uint32_t
     if (!ix || !dev_queries || !dev_idx || !dev_dist) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
     Entry in(ix->sync);  // (n changes under add: read under the lock)
     VQ_TRY(ivfpq_check_probe(ix, nprobe));
-    VQ_TRY(ivfpq_check_topk(ix, topk));
+    VQ_TRY(check_topk(ix->n, topk));
     if (nq == 0) return VQHIP_OK;
     VQ_TRY(require_gfx950());
     VQ_TRY(ivfpq_device(ix));

@@ -11,8 +11,8 @@
 //     (k_adc_scan_thr: LDS-bound on the table reads), the exact top-k of those (k_adc_sort_thr); a query whose
 //     threshold let fewer than topk or more than 8192 rows pass is flagged and repeated by
 //   * the full pass: the table t (k_adc_lut), a byte-gather scan of the codes with the tables of 8 queries in LDS that
-//     writes every D(q, i) (k_adc_scan), a histogram cut + candidate sort (k_adc_pick_bin / _collect / _sort_out) and an
-//     exact per-query radix select where the cut is too dense (k_adc_topk).
+//     writes every D(q, i) and their histogram (k_adc_scan), and the shared selection stage over them (topk.hpp,
+//     launch_topk_select).
 #include "adc_plan.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
@@ -68,11 +68,18 @@ __global__ __launch_bounds__(256) void k_adc_lut(const float *__restrict__ queri
 
 constexpr uint32_t kAdcQB = 8;      // queries per scan pass (their tables share the LDS)
 
-// monotone (non-decreasing in d) bin of a distance; NaN and out-of-range values go to the last bin
-__device__ __forceinline__ uint32_t adc_bin(float dval, float lo, float scale) {
-    const float t = (dval - lo) * scale;
-    return (t >= 0.0f && t < (float)(kAdcBins - 1)) ? (uint32_t)t : ((t < 0.0f) ? 0u : kAdcBins - 1);
-}
+// the full pass as a source of the selection stage (topk.hpp): dense rows, the scan's float bins over bounds[q]
+struct AdcSource : TopkRows {
+    const float *bounds;
+    float lo = 0, scale = 0;  // (device: of the opened query)
+    __device__ void open(uint32_t q) {
+        TopkRows::open(q);
+        lo = bounds[2 * q];
+        scale = adc_scale(lo, bounds[2 * q + 1]);
+    }
+    __device__ uint32_t bin(float dval) const { return adc_bin(dval, lo, scale); }
+    uint32_t blocks() const { return 64; }
+};
 
 // dist[qq][i] for the queries q0 .. q0+nqb-1
 // blockIdx.y = batch of kAdcQB queries inside a group (round 6: the batches of a group run in ONE set of launches; the
@@ -97,7 +104,7 @@ __global__ __launch_bounds__(256) void k_adc_scan(const uint8_t *__restrict__ co
     for (uint32_t qq = 0; qq < kAdcQB; ++qq) {
         const float lo = (qq < nqb) ? bounds[2 * qq] : 0.0f, hi = (qq < nqb) ? bounds[2 * qq + 1] : 1.0f;
         blo[qq] = lo;
-        bsc[qq] = (hi > lo) ? (float)kAdcBins / (hi - lo) : 0.0f;
+        bsc[qq] = adc_scale(lo, hi);
     }
     __syncthreads();
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
@@ -136,26 +143,6 @@ __global__ __launch_bounds__(256) void k_adc_scan(const uint8_t *__restrict__ co
     __syncthreads();
     for (uint32_t e = threadIdx.x; e < nqb * kAdcBins; e += 256)
         if (lds_hist[e]) atomicAdd(&hist[e], lds_hist[e]);
-}
-
-
-// step 2: every row whose bin is <= the selected one becomes a candidate (key, row); any order
-__global__ __launch_bounds__(256) void k_adc_collect(const float *__restrict__ dist, uint64_t n,
-                                                     const float *__restrict__ bounds, const uint32_t *__restrict__ sel,
-                                                     unsigned long long *__restrict__ cand, uint32_t *__restrict__ cand_n) {
-    const uint32_t q = blockIdx.y;
-    if (sel[2 * q + 1] > kAdcCand) return;  // too dense: the exact radix select handles this query
-    const float lo = bounds[2 * q], hi = bounds[2 * q + 1];
-    const float scale = (hi > lo) ? (float)kAdcBins / (hi - lo) : 0.0f;
-    const uint32_t bmax = sel[2 * q];
-    const float *dq = dist + (size_t)q * n;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
-        const float dv = dq[i];
-        if (adc_bin(dv, lo, scale) <= bmax) {
-            const uint32_t pos = atomicAdd(&cand_n[q], 1u);
-            if (pos < kAdcCand) cand[(size_t)q * kAdcCand + pos] = ((unsigned long long)adc_key(dv) << 32) | (uint32_t)i;
-        }
-    }
 }
 
 
@@ -342,7 +329,7 @@ __global__ __launch_bounds__(1024) void k_adc_sort_thr(const unsigned long long 
                                                        const uint32_t *__restrict__ cand_n, uint32_t topk, int take_sqrt,
                                                        uint32_t *__restrict__ idx_out, float *__restrict__ dist_out,
                                                        uint32_t *__restrict__ redo, int force_redo) {
-    extern __shared__ unsigned long long sort_buf[];  // [kAdcCand]
+    extern __shared__ __attribute__((aligned(16))) unsigned long long sort_buf[];  // [kAdcCand]
     const uint32_t q = blockIdx.x, cnt = cand_n[(size_t)q * kAdcCntStride];
     if (threadIdx.x == 0) redo[gridDim.x + q] = cnt;  // (diagnostics: candidates the threshold let pass)
     if (cnt > kAdcCand || cnt < topk || force_redo) {
@@ -386,41 +373,16 @@ __global__ __launch_bounds__(1024) void k_adc_sort_thr(const unsigned long long 
             __syncthreads();
             if ((wv & (2 * stride - 1)) == 0) best = fold(best, sort_buf[(wv + stride) * 64 + lane]);
         }
-        if (wv == 0 && lane < topk) {
-            float dv = adc_unkey((uint32_t)(best >> 32));
-            if (take_sqrt) dv = sqrtf(dv);
-            idx_out[(size_t)q * topk + lane] = (uint32_t)best;
-            dist_out[(size_t)q * topk + lane] = dv;
-        }
+        if (wv == 0 && lane < topk) adc_emit(best, true, take_sqrt, idx_out + (size_t)q * topk + lane, dist_out + (size_t)q * topk + lane);
         return;
     }
     uint32_t len = 1024;
     while (len < cnt) len <<= 1;
     for (uint32_t e = threadIdx.x; e < len; e += 1024) sort_buf[e] = (e < cnt) ? cq[e] : ~0ull;
-    __syncthreads();
-    for (uint32_t size = 2; size <= len; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t t = threadIdx.x; t < len; t += 1024) {
-                const uint32_t partner = t ^ stride;
-                if (partner > t) {
-                    const bool up = (t & size) == 0;
-                    const unsigned long long a = sort_buf[t], b = sort_buf[partner];
-                    if ((a > b) == up) {
-                        sort_buf[t] = b;
-                        sort_buf[partner] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (threadIdx.x < topk) {
-        const unsigned long long w = sort_buf[threadIdx.x];
-        float dv = adc_unkey((uint32_t)(w >> 32));
-        if (take_sqrt) dv = sqrtf(dv);
-        idx_out[(size_t)q * topk + threadIdx.x] = (uint32_t)w;
-        dist_out[(size_t)q * topk + threadIdx.x] = dv;
-    }
+    adc_bitonic<1024>(sort_buf, len);
+    if (threadIdx.x < topk)
+        adc_emit(sort_buf[threadIdx.x], true, take_sqrt, idx_out + (size_t)q * topk + threadIdx.x,
+                 dist_out + (size_t)q * topk + threadIdx.x);
 }
 
 template <uint32_t QB, uint32_t LQ, uint32_t NT>
@@ -461,7 +423,7 @@ int adc_fast_launch(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int l1
 }  // namespace
 
 // queries_dev [nq][m*sd]; workspaces sized for a group of `qgroup` queries (adc_query_group): lut_ws >= qgroup*m*k floats,
-// dist_ws >= qgroup*n floats, state_ws >= adc_state_bytes(qgroup), cand_ws >= adc_cand_bytes(qgroup); outputs on the device
+// dist_ws >= qgroup*n floats, state_ws >= adc_state_bytes(qgroup), cand_ws >= topk_cand_bytes(qgroup); outputs on the device
 int launch_adc_search(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int metric, const uint8_t *codes, uint64_t n,
                       const float *queries_dev, uint32_t nq, uint32_t topk, float *lut_ws, float *dist_ws,
                       void *state_ws, unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev,
@@ -477,8 +439,6 @@ int launch_adc_search(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int 
     if (attr.needed()) {
         VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_adc_scan), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)kAdcFullScanLdsMax));
-        VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_adc_sort_out),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kAdcCand * 8)));
         attr.done();
     }
     const int l1 = metric == VQHIP_MANHATTAN ? 1 : 0;
@@ -492,11 +452,9 @@ int launch_adc_search(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int 
     // six kernels of a pass are dependent and tiny (5-25 us each, 110 us per pass whatever the work), so eight passes one
     // after the other cost eight times that for 64 queries
     const uint32_t qg = qgroup >= nq ? nq : (qgroup >= qb ? qgroup / qb * qb : qgroup);  // (<= qgroup: the workspaces' size)
-    // small state per query of the group: bounds [2] f32 | hist [bins] u32 | sel [2] u32 | cand_n u32
+    // small state per query of the group: bounds [2] f32 | the selection's (topk.hpp)
     float *bounds = reinterpret_cast<float *>(state_ws);
-    uint32_t *hist = reinterpret_cast<uint32_t *>(bounds + 2 * (size_t)qg);
-    uint32_t *sel = hist + (size_t)qg * kAdcBins;
-    uint32_t *cand_n = sel + 2 * (size_t)qg;
+    const TopkState st = topk_state(bounds + 2 * (size_t)qg, qg);
     const size_t state_bytes = adc_state_bytes(qg);
     for (uint32_t q0 = 0; q0 < nq; q0 += qg) {
         const uint32_t nqg = (nq - q0 < qg) ? nq - q0 : qg;
@@ -509,16 +467,10 @@ int launch_adc_search(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int 
                            cb, l1, lut_ws, bounds);
         VQ_LAUNCH_CHECK("k_adc_lut");
         hipLaunchKernelGGL(k_adc_scan, dim3((uint32_t)blocks, batches), dim3(256), scan_lds, stream,
-                           codes, n, m, k, lut_ws, nqg, qb, bounds, dist_ws, hist);
+                           codes, n, m, k, lut_ws, nqg, qb, bounds, dist_ws, st.hist);
         VQ_LAUNCH_CHECK("k_adc_scan");
-        // top-k: candidates below a histogram cut, sorted in LDS; dense cuts fall back to the radix select
-        hipLaunchKernelGGL(k_adc_pick_bin, dim3(nqg), dim3(64), 0, stream, hist, topk, sel);
-        hipLaunchKernelGGL(k_adc_collect, dim3(64, nqg), dim3(256), 0, stream, dist_ws, n, bounds, sel, cand_ws, cand_n);
-        hipLaunchKernelGGL(k_adc_sort_out, dim3(nqg), dim3(1024), (size_t)kAdcCand * 8, stream, cand_ws, sel, topk, take_sqrt,
-                           idx_out_dev + (size_t)q0 * topk, dist_out_dev + (size_t)q0 * topk);
-        hipLaunchKernelGGL(k_adc_topk, dim3(nqg), dim3(1024), 0, stream, dist_ws, n, topk, take_sqrt, sel,
-                           idx_out_dev + (size_t)q0 * topk, dist_out_dev + (size_t)q0 * topk);
-        VQ_LAUNCH_CHECK("k_adc_topk");
+        VQ_TRY(launch_topk_select(AdcSource{{dist_ws, n}, bounds}, nqg, topk, take_sqrt, st, cand_ws, idx_out_dev + (size_t)q0 * topk,
+                                  dist_out_dev + (size_t)q0 * topk, stream));
     }
     return VQHIP_OK;
 }
@@ -534,8 +486,9 @@ int launch_adc_lut(const float *queries_dev, uint32_t nq, uint32_t m, uint32_t k
     return VQHIP_OK;
 }
 
-size_t adc_state_bytes(uint32_t qgroup) { return (size_t)qgroup * (2 + kAdcBins + 2 + 1) * 4; }
-size_t adc_cand_bytes(uint32_t qgroup) { return (size_t)qgroup * kAdcCand * 8; }
+size_t topk_state_bytes(uint32_t qb) { return (size_t)qb * (kAdcBins + 2 + 1) * 4; }
+size_t topk_cand_bytes(uint32_t qb) { return (size_t)qb * kAdcCand * 8; }
+size_t adc_state_bytes(uint32_t qgroup) { return (size_t)qgroup * 2 * 4 + topk_state_bytes(qgroup); }
 uint32_t adc_query_batch() { return kAdcQB; }
 // queries that share one set of launches: up to 64 while their distance rows (4 n bytes each) stay under 1 GB -- a whole
 // number of scan batches (kAdcQB) where one batch fits, fewer queries (down to one) where it does not -- and never more

@@ -15,7 +15,8 @@
 //                        query's candidate list (key adc_key(S[H]), row)
 //   k_bin_ties           heavy cut (more than 8192 candidates): the lowest need = topk - less row ids with H == H*, found
 //                        by an ordered scan over the rows that stops once it has them
-//   k_adc_sort_out       (topk.hpp) the candidates sorted by (key, row) in LDS, the first topk out, sqrtf for Euclidean
+//   k_adc_sort_out       (topk.hpp) the candidates sorted by (key, row) in LDS, the first topk out,
+//                        sqrtf for Euclidean
 // Roofline: VALU, 2 operations (v_xor, v_bcnt with accumulate) per 32 dimensions per (query, row) pair and scan.
 #include "kernels.hpp"
 #include "topk.hpp"
@@ -380,19 +381,13 @@ int launch_bin_padcheck(const uint32_t *P, uint64_t n, uint32_t d, uint32_t *bad
 }
 
 size_t binary_hist_bytes(uint32_t qb, uint32_t d) { return (size_t)qb * (d + 1) * 4; }
-size_t binary_cand_bytes(uint32_t qb) { return (size_t)qb * kAdcCand * 8; }
 
 int launch_binary_search(const uint32_t *P, uint64_t n, uint32_t d, int metric, const float *S, const uint32_t *Q, uint32_t nb,
                          uint32_t topk, uint32_t *hist, BinSel *sel, uint32_t *adc_sel, uint32_t *cnt,
                          unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream) {
     if (topk == 0 || topk > 1024 || topk > n) return fail(VQHIP_ERR_INVALID_INPUT, "topk must be in [1, min(n, 1024)]");
     if (nb == 0) return VQHIP_OK;
-    static PerDeviceOnce attr;
-    if (attr.needed()) {
-        VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_adc_sort_out), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)(kAdcCand * 8)));
-        attr.done();
-    }
+    VQ_TRY(topk_sort_attr());
     const uint32_t W = bin_words(d);
     VQ_HIP(hipMemsetAsync(hist, 0, binary_hist_bytes(nb, d), stream));
     VQ_TRY(bin_scan<BIN_HIST>(P, n, W, d, Q, nb, hist, sel, S, cand, cnt, stream));

@@ -7,10 +7,9 @@
 //             idx 0xFFFFFFFF, dist +inf.
 // Schedule (launch_ivf_search): k_ivf_plan (each query's prefix over its probed lists' lengths, and the histogram range)
 // -> k_ivf_scan (work items = one query x one chunk of its positions: the table in LDS, D written per position, an LDS
-// histogram of the distances) -> k_adc_pick_bin (topk.hpp) -> k_ivf_collect (the positions at or below the cut, as
-// (key, row id) words) -> k_ivf_sort_out (sort in LDS) / k_ivf_topk_dense (exact radix select over (key, row id) where
-// the cut was too dense: heavy ties).  The histogram only decides which positions become candidates; every candidate
-// carries its exact unique key, so the result does not depend on the bins.
+// histogram of the distances) -> launch_topk_select (topk.hpp) over IvfSource: the positions of
+// S(q), the row id of each through the plan's prefix.  The histogram only decides which positions become candidates;
+// every candidate carries its exact unique key, so the result does not depend on the bins.
 #include "adc_plan.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
@@ -86,13 +85,6 @@ __global__ __launch_bounds__(1024) void k_ivf_plan(const uint32_t *__restrict__ 
     }
 }
 
-// the same monotone bin as k_adc.hip's full pass: NaN and values past the range in the last bin
-__device__ __forceinline__ uint32_t ivf_bin(float dval, float lo, float scale) {
-    const float t = (dval - lo) * scale;
-    return (t >= 0.0f && t < (float)(kAdcBins - 1)) ? (uint32_t)t : ((t < 0.0f) ? 0u : kAdcBins - 1);
-}
-__device__ __forceinline__ float ivf_scale(float lo, float hi) { return (hi > lo) ? (float)kAdcBins / (hi - lo) : 0.0f; }
-
 // the probe slot of position pos: the last slot whose first position is <= pos (pq[0] = 0 <= pos < pq[nprobe])
 __device__ __forceinline__ uint32_t ivf_slot(const uint32_t *__restrict__ pq, uint32_t nprobe, uint32_t pos) {
     uint32_t lo = 0, hi = nprobe;
@@ -129,7 +121,7 @@ __global__ __launch_bounds__(256) void k_ivf_scan(const uint8_t *__restrict__ co
     const float *lq = lut + (size_t)q * tab;
     for (uint32_t e = threadIdx.x; e < tab; e += 256) lds_lut[e] = lq[e];
     for (uint32_t e = threadIdx.x; e < kAdcBins; e += 256) lds_hist[e] = 0u;
-    const float lo = bounds[2 * q], scale = ivf_scale(lo, bounds[2 * q + 1]);
+    const float lo = bounds[2 * q], scale = adc_scale(lo, bounds[2 * q + 1]);
     __syncthreads();
     const bool words = k <= 256 && (m & 7u) == 0 && (reinterpret_cast<uintptr_t>(codes) & 7u) == 0;
     float *wq = W + (size_t)q * wstride;
@@ -146,7 +138,7 @@ __global__ __launch_bounds__(256) void k_ivf_scan(const uint8_t *__restrict__ co
             adc_row<1>(codes, (uint64_t)sq[slot] + (pos - first), m, k, words, lds_lut, 1u, 0u, acc);
             const float dv = acc[0];
             wq[pos] = dv;
-            atomicAdd(&lds_hist[ivf_bin(dv, lo, scale)], 1u);
+            atomicAdd(&lds_hist[adc_bin(dv, lo, scale)], 1u);
         }
     }
     __syncthreads();
@@ -154,155 +146,31 @@ __global__ __launch_bounds__(256) void k_ivf_scan(const uint8_t *__restrict__ co
         if (lds_hist[e]) atomicAdd(&hist[(size_t)q * kAdcBins + e], lds_hist[e]);
 }
 
-// every position whose bin is <= the selected one becomes a candidate (key, row id); any order (the sort orders them)
-__global__ __launch_bounds__(256) void k_ivf_collect(const float *__restrict__ W, uint64_t wstride, const uint32_t *__restrict__ pref,
-                                                     const uint32_t *__restrict__ seg, const uint32_t *__restrict__ ids,
-                                                     uint32_t nprobe, const float *__restrict__ bounds,
-                                                     const uint32_t *__restrict__ sel, unsigned long long *__restrict__ cand,
-                                                     uint32_t *__restrict__ cand_n) {
-    const uint32_t q = blockIdx.y;
-    if (sel[2 * q + 1] > kAdcCand) return;  // too dense: k_ivf_topk_dense
-    const uint32_t *pq = pref + (size_t)q * (nprobe + 1);
-    const uint32_t *sq = seg + (size_t)q * nprobe;
-    const uint32_t total = (uint32_t)min((uint64_t)pq[nprobe], wstride);
-    const float lo = bounds[2 * q], scale = ivf_scale(lo, bounds[2 * q + 1]);
-    const uint32_t bmax = sel[2 * q];
-    const float *wq = W + (size_t)q * wstride;
-    for (uint32_t pos = blockIdx.x * 256 + threadIdx.x; pos < total; pos += gridDim.x * 256) {
-        const float dv = wq[pos];
-        if (ivf_bin(dv, lo, scale) <= bmax) {
-            const uint32_t row = ids[ivf_row(pq, sq, nprobe, pos)];
-            const uint32_t at = atomicAdd(&cand_n[q], 1u);
-            if (at < kAdcCand) cand[(size_t)q * kAdcCand + at] = ((unsigned long long)adc_key(dv) << 32) | row;
-        }
+// the scans' output as a source of the selection stage (topk.hpp): W[q][wstride] over the positions of S(q), the row id
+// of a position through the plan's prefix, the scans' float bins over bounds[q]
+struct IvfSource {
+    using Pos = uint32_t;
+    const float *W;
+    uint64_t wstride;
+    const uint32_t *pref, *seg, *ids;
+    uint32_t nprobe;
+    const float *bounds;
+    uint32_t total = 0;  // (device: of the opened query)
+    float lo = 0, scale = 0;
+    __device__ void open(uint32_t q) {
+        W += (size_t)q * wstride;
+        pref += (size_t)q * (nprobe + 1);
+        seg += (size_t)q * nprobe;
+        total = (uint32_t)min((uint64_t)pref[nprobe], wstride);
+        lo = bounds[2 * q];
+        scale = adc_scale(lo, bounds[2 * q + 1]);
     }
-}
-
-__device__ __forceinline__ void ivf_emit(unsigned long long w, bool real, int take_sqrt, uint32_t *idx, float *dist) {
-    if (!real) {
-        *idx = 0xFFFFFFFFu;
-        *dist = __builtin_inff();
-        return;
-    }
-    float dv = adc_unkey((uint32_t)(w >> 32));
-    if (take_sqrt) dv = sqrtf(dv);
-    *idx = (uint32_t)w;
-    *dist = dv;
-}
-
-// bitonic sort of len (a power of two, a multiple of the block) words in LDS, ascending
-__device__ __forceinline__ void ivf_bitonic(unsigned long long *buf, uint32_t len) {
-    for (uint32_t size = 2; size <= len; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t t = threadIdx.x; t < len; t += blockDim.x) {
-                const uint32_t partner = t ^ stride;
-                if (partner > t) {
-                    const bool up = (t & size) == 0;
-                    const unsigned long long a = buf[t], b = buf[partner];
-                    if ((a > b) == up) {
-                        buf[t] = b;
-                        buf[partner] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// the candidates of a query sorted in LDS, the first topk out (all of S(q) when it holds fewer than topk rows: padding)
-__global__ __launch_bounds__(1024) void k_ivf_sort_out(const unsigned long long *__restrict__ cand, const uint32_t *__restrict__ sel,
-                                                       uint32_t topk, int take_sqrt, uint32_t *__restrict__ idx_out,
-                                                       float *__restrict__ dist_out) {
-    extern __shared__ unsigned long long sort_buf[];  // [kAdcCand]
-    const uint32_t q = blockIdx.x, cnt = sel[2 * q + 1];
-    if (cnt > kAdcCand) return;  // k_ivf_topk_dense
-    uint32_t len = 1024;
-    while (len < cnt) len <<= 1;
-    for (uint32_t e = threadIdx.x; e < len; e += 1024) sort_buf[e] = (e < cnt) ? cand[(size_t)q * kAdcCand + e] : ~0ull;
-    __syncthreads();
-    ivf_bitonic(sort_buf, len);
-    if (threadIdx.x < topk)
-        ivf_emit(sort_buf[threadIdx.x], threadIdx.x < cnt, take_sqrt, idx_out + (size_t)q * topk + threadIdx.x,
-                 dist_out + (size_t)q * topk + threadIdx.x);
-}
-
-// a query whose cut held more than kAdcCand positions (ties piled on one value): exact radix select of the topk-th
-// smallest (key, row id) -- the key's four bytes over all positions, then the row id's four over the positions of that
-// key -- and the topk words at or below it, sorted.  |S(q)| > kAdcCand >= topk here: no padding.
-__global__ __launch_bounds__(1024) void k_ivf_topk_dense(const float *__restrict__ W, uint64_t wstride,
-                                                         const uint32_t *__restrict__ pref, const uint32_t *__restrict__ seg,
-                                                         const uint32_t *__restrict__ ids, uint32_t nprobe, uint32_t topk,
-                                                         int take_sqrt, const uint32_t *__restrict__ sel,
-                                                         uint32_t *__restrict__ idx_out, float *__restrict__ dist_out) {
-    const uint32_t q = blockIdx.x;
-    if (sel[2 * q + 1] <= kAdcCand) return;  // the candidate sort produced this query's result
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t s_prefix, s_rank, s_count;
-    __shared__ unsigned long long win[1024];
-    const uint32_t *pq = pref + (size_t)q * (nprobe + 1);
-    const uint32_t *sq = seg + (size_t)q * nprobe;
-    const uint32_t total = (uint32_t)min((uint64_t)pq[nprobe], wstride);
-    const float *wq = W + (size_t)q * wstride;
-    const uint32_t tid = threadIdx.x;
-    if (tid == 0) {
-        s_prefix = 0;
-        s_rank = topk - 1;
-    }
-    __syncthreads();
-    // pass 0 finds the key T of the topk-th word and its rank among the words of key T; pass 1 the row id R of that rank
-    uint32_t T = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        for (int shift = 24; shift >= 0; shift -= 8) {
-            if (tid < 256) hist[tid] = 0;
-            __syncthreads();
-            const uint32_t prefix = s_prefix, himask = (shift == 24) ? 0u : (0xFFFFFFFFu << (shift + 8));
-            for (uint32_t pos = tid; pos < total; pos += 1024) {
-                const uint32_t key = adc_key(wq[pos]);
-                uint32_t v = key;
-                if (pass == 1) {
-                    if (key != T) continue;
-                    v = ids[ivf_row(pq, sq, nprobe, pos)];
-                }
-                if ((v & himask) == prefix) atomicAdd(&hist[(v >> shift) & 255u], 1u);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                uint32_t rank = s_rank, b = 0;
-                for (; b < 255; ++b) {
-                    if (rank < hist[b]) break;
-                    rank -= hist[b];
-                }
-                s_rank = rank;
-                s_prefix = prefix | (b << shift);
-            }
-            __syncthreads();
-        }
-        if (pass == 0) {
-            T = s_prefix;
-            __syncthreads();
-            if (tid == 0) s_prefix = 0;  // (s_rank: the rank among the words of key T, carried into pass 1)
-            __syncthreads();
-        }
-    }
-    const unsigned long long cut = ((unsigned long long)T << 32) | s_prefix;  // the topk-th smallest word
-    if (tid == 0) s_count = 0;
-    for (uint32_t e = tid; e < 1024; e += 1024) win[e] = ~0ull;
-    __syncthreads();
-    for (uint32_t pos = tid; pos < total; pos += 1024) {
-        const uint32_t key = adc_key(wq[pos]);
-        if (key > T) continue;
-        const unsigned long long w = ((unsigned long long)key << 32) | ids[ivf_row(pq, sq, nprobe, pos)];
-        if (w <= cut) {
-            const uint32_t at = atomicAdd(&s_count, 1u);
-            if (at < 1024) win[at] = w;  // (exactly topk words pass)
-        }
-    }
-    __syncthreads();
-    ivf_bitonic(win, 1024);
-    if (tid < topk)
-        ivf_emit(win[tid], true, take_sqrt, idx_out + (size_t)q * topk + tid, dist_out + (size_t)q * topk + tid);
-}
+    __device__ Pos count() const { return total; }
+    __device__ float at(Pos pos) const { return W[pos]; }
+    __device__ uint32_t id(Pos pos) const { return ids[ivf_row(pref, seg, nprobe, pos)]; }
+    __device__ uint32_t bin(float dval) const { return adc_bin(dval, lo, scale); }
+    uint32_t blocks() const { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((wstride + 255) / 256, 1), 64); }
+};
 
 // ---- residual lists (VQHIP_IVF_RESIDUAL) ----
 // A row of list l holds the codes of x - C[l], so its distance to q is the ADC definition applied to r = q - C[l] (f32,
@@ -460,7 +328,7 @@ __global__ __launch_bounds__(256) void k_ivf_rscan(const uint8_t *__restrict__ c
     const uint32_t p1 = (uint32_t)min((uint64_t)total, p0 + chunk);
     uint32_t *lds_hist = reinterpret_cast<uint32_t *>(lds_lut + tab);
     for (uint32_t e = threadIdx.x; e < kAdcBins; e += 256) lds_hist[e] = 0u;
-    const float lo = bounds[2 * q], scale = ivf_scale(lo, bounds[2 * q + 1]);
+    const float lo = bounds[2 * q], scale = adc_scale(lo, bounds[2 * q + 1]);
     const bool words = k <= 256 && (m & 7u) == 0 && (reinterpret_cast<uintptr_t>(codes) & 7u) == 0;
     const bool vec = (tab & 3u) == 0;  // (every table then starts on 16 bytes)
     float *wq = W + (size_t)q * wstride;
@@ -481,7 +349,7 @@ __global__ __launch_bounds__(256) void k_ivf_rscan(const uint8_t *__restrict__ c
             adc_row<1>(codes, (uint64_t)sq[slot] + (pos - pq[slot]), m, k, words, lds_lut, 1u, 0u, acc);
             const float dv = acc[0];
             wq[pos] = dv;
-            atomicAdd(&lds_hist[ivf_bin(dv, lo, scale)], 1u);
+            atomicAdd(&lds_hist[adc_bin(dv, lo, scale)], 1u);
         }
     }
     __syncthreads();
@@ -491,9 +359,6 @@ __global__ __launch_bounds__(256) void k_ivf_rscan(const uint8_t *__restrict__ c
 
 }  // namespace
 
-size_t ivf_state_bytes(uint32_t qb) { return (size_t)qb * (kAdcBins + 2 + 1) * 4; }
-size_t ivf_cand_bytes(uint32_t qb) { return (size_t)qb * kAdcCand * 8; }
-
 // positions per scan work item: about four items per CU over the batch's expected positions, whole passes of the block
 uint32_t ivf_chunk(uint64_t expected_positions) {
     const uint64_t per_item = expected_positions / (4 * (uint64_t)num_cus());
@@ -501,7 +366,7 @@ uint32_t ivf_chunk(uint64_t expected_positions) {
     return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(c, 512), 8192);
 }
 
-// the dynamic LDS the scans (up to the table limit) and the candidate sort take, once per device
+// the dynamic LDS the scans take (up to the table limit), once per device
 static int ivf_attrs() {
     static PerDeviceOnce attr;
     if (attr.needed()) {
@@ -509,41 +374,15 @@ static int ivf_attrs() {
                                    (int)kAdcFullScanLdsMax));
         VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ivf_rscan), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)kAdcFullScanLdsMax));
-        VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ivf_sort_out), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)(kAdcCand * 8)));
         attr.done();
     }
     return VQHIP_OK;
 }
 
-// the selection after a scan, shared by both kinds of list: the histogram's cut, the candidates at or below it, their
-// sort (k_ivf_sort_out) or the exact radix select (k_ivf_topk_dense)
-static int ivf_select(const uint32_t *ids, uint32_t nb, uint32_t nprobe, uint32_t topk, int metric, uint64_t wstride, const float *W,
-                      const uint32_t *pref, const uint32_t *seg, const float *bounds, void *state, unsigned long long *cand,
-                      uint32_t *idx_out, float *dist_out, hipStream_t stream) {
-    const int take_sqrt = metric == VQHIP_EUCLIDEAN ? 1 : 0;
-    uint32_t *hist = reinterpret_cast<uint32_t *>(state);
-    uint32_t *sel = hist + (size_t)nb * kAdcBins;
-    uint32_t *cand_n = sel + 2 * (size_t)nb;
-    hipLaunchKernelGGL(k_adc_pick_bin, dim3(nb), dim3(64), 0, stream, hist, topk, sel);
-    VQ_LAUNCH_CHECK("k_adc_pick_bin");
-    const uint32_t cblocks = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((wstride + 255) / 256, 1), 64);
-    hipLaunchKernelGGL(k_ivf_collect, dim3(cblocks, nb), dim3(256), 0, stream, W, wstride, pref, seg, ids, nprobe, bounds, sel, cand,
-                       cand_n);
-    VQ_LAUNCH_CHECK("k_ivf_collect");
-    hipLaunchKernelGGL(k_ivf_sort_out, dim3(nb), dim3(1024), (size_t)kAdcCand * 8, stream, cand, sel, topk, take_sqrt, idx_out,
-                       dist_out);
-    VQ_LAUNCH_CHECK("k_ivf_sort_out");
-    hipLaunchKernelGGL(k_ivf_topk_dense, dim3(nb), dim3(1024), 0, stream, W, wstride, pref, seg, ids, nprobe, topk, take_sqrt, sel,
-                       idx_out, dist_out);
-    VQ_LAUNCH_CHECK("k_ivf_topk_dense");
-    return VQHIP_OK;
-}
-
 // One batch of nb queries whose probe lists (probe [nb][nprobe], launch_knn_search) and tables (lut [nb][m][k],
 // launch_adc_lut) are on the device.  codes / ids / off: the index in list order.  W [nb][wstride] with wstride >= every
-// |S(q)|; pref [nb][nprobe + 1], seg [nb][nprobe], bounds [nb][2], state >= ivf_state_bytes(nb) (zeroed here),
-// cand >= ivf_cand_bytes(nb).  Results [nb][topk] on the device.
+// |S(q)|; pref [nb][nprobe + 1], seg [nb][nprobe], bounds [nb][2], state >= topk_state_bytes(nb) (zeroed here),
+// cand >= topk_cand_bytes(nb).  Results [nb][topk] on the device.
 int launch_ivf_search(const uint8_t *codes, const uint32_t *ids, const uint32_t *off, uint32_t nlist, uint32_t m, uint32_t k, int metric,
                       const float *lut, const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk,
                       uint64_t wstride, float *W, uint32_t *pref, uint32_t *seg, float *bounds, void *state,
@@ -554,17 +393,18 @@ int launch_ivf_search(const uint8_t *codes, const uint32_t *ids, const uint32_t 
     if (!adc_table_fits(m, k)) return fail_adc_table(m, k);
     const size_t scan_lds = ((size_t)m * k + kAdcBins) * 4;
     VQ_TRY(ivf_attrs());
-    uint32_t *hist = reinterpret_cast<uint32_t *>(state);
-    VQ_HIP(hipMemsetAsync(state, 0, ivf_state_bytes(nb), stream));
+    const TopkState st = topk_state(state, nb);
+    VQ_HIP(hipMemsetAsync(state, 0, topk_state_bytes(nb), stream));
     hipLaunchKernelGGL(k_ivf_plan, dim3(nb), dim3(1024), 0, stream, probe, nprobe, nlist, off, lut, m, k, pref, seg, bounds);
     VQ_LAUNCH_CHECK("k_ivf_plan");
     const uint64_t items = (wstride + chunk - 1) / chunk;
     if (items > 0) {
         hipLaunchKernelGGL(k_ivf_scan, dim3((uint32_t)items, nb), dim3(256), scan_lds, stream, codes, m, k, lut, pref, seg, nprobe,
-                           bounds, chunk, wstride, W, hist);
+                           bounds, chunk, wstride, W, st.hist);
         VQ_LAUNCH_CHECK("k_ivf_scan");
     }
-    return ivf_select(ids, nb, nprobe, topk, metric, wstride, W, pref, seg, bounds, state, cand, idx_out, dist_out, stream);
+    return launch_topk_select(IvfSource{W, wstride, pref, seg, ids, nprobe, bounds}, nb, topk, metric == VQHIP_EUCLIDEAN ? 1 : 0, st, cand,
+                              idx_out, dist_out, stream);
 }
 
 size_t ivf_rtab_bytes(uint32_t qb, uint32_t nprobe, uint32_t m, uint32_t k) { return (size_t)qb * nprobe * m * k * 4; }
@@ -593,8 +433,8 @@ int launch_ivf_rsearch(const uint8_t *codes, const uint32_t *ids, const uint32_t
     const size_t scan_lds = ((size_t)m * k + kAdcBins) * 4;
     VQ_TRY(ivf_attrs());
     const int l1 = metric == VQHIP_MANHATTAN ? 1 : 0;
-    uint32_t *hist = reinterpret_cast<uint32_t *>(state);
-    VQ_HIP(hipMemsetAsync(state, 0, ivf_state_bytes(nb), stream));
+    const TopkState st = topk_state(state, nb);
+    VQ_HIP(hipMemsetAsync(state, 0, topk_state_bytes(nb), stream));
     const dim3 tgrid((nprobe + kIvfRSlots - 1) / kIvfRSlots, nb);
     auto *rlut = sd == 16 ? k_ivf_rlut<16> : sd == 8 ? k_ivf_rlut<8> : sd == 4 ? k_ivf_rlut<4> : k_ivf_rlut<0>;
     hipLaunchKernelGGL(rlut, tgrid, dim3(256), 0, stream, queries, coarse, probe, nprobe, nlist, off, cb, m, k, sd, l1, tabs, mm);
@@ -604,10 +444,11 @@ int launch_ivf_rsearch(const uint8_t *codes, const uint32_t *ids, const uint32_t
     const uint64_t items = (wstride + chunk - 1) / chunk;
     if (items > 0) {
         hipLaunchKernelGGL(k_ivf_rscan, dim3((uint32_t)items, nb), dim3(256), scan_lds, stream, codes, m, k, tabs, pref, seg, nprobe,
-                           bounds, chunk, wstride, W, hist);
+                           bounds, chunk, wstride, W, st.hist);
         VQ_LAUNCH_CHECK("k_ivf_rscan");
     }
-    return ivf_select(ids, nb, nprobe, topk, metric, wstride, W, pref, seg, bounds, state, cand, idx_out, dist_out, stream);
+    return launch_topk_select(IvfSource{W, wstride, pref, seg, ids, nprobe, bounds}, nb, topk, metric == VQHIP_EUCLIDEAN ? 1 : 0, st, cand,
+                              idx_out, dist_out, stream);
 }
 
 }  // namespace vqhip

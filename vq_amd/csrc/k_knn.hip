@@ -11,8 +11,7 @@
 //                  register; writes every D and the per-query range [min, max] of the non-NaN keys
 //   k_knn_hist     a 512-bin histogram per query, bins linear in KEY space over that range (monotone in D whatever the
 //                  values: +-inf, NaN, huge ranges), NaN alone in the last bin
-//   k_adc_pick_bin / k_knn_collect / k_adc_sort_out   the rows up to the bin of the topk-th key, sorted in LDS
-//   k_adc_topk     exact radix select for a query whose cut held more than 8192 rows (heavy ties)
+//   launch_topk_select   the shared selection stage (topk.hpp) over those distances and bins
 // Roofline: VALU.  Squared L2 / Euclidean cost 3 unfused operations per (query, row, dimension), L1 2 (sub, then an add
 // that takes |.| as a source modifier), cosine 2 (mul, add).
 #include "kernels.hpp"
@@ -211,22 +210,18 @@ __global__ __launch_bounds__(256) void k_knn_hist(const float *__restrict__ dist
         if (h[e]) atomicAdd(&hist[(size_t)q * kAdcBins + e], h[e]);
 }
 
-// every row whose bin is <= the selected one becomes a candidate (key, row); any order
-__global__ __launch_bounds__(256) void k_knn_collect(const float *__restrict__ dist, uint64_t n, const uint32_t *__restrict__ kmin,
-                                                     const uint32_t *__restrict__ kmax, const uint32_t *__restrict__ sel,
-                                                     unsigned long long *__restrict__ cand, uint32_t *__restrict__ cand_n) {
-    const uint32_t q = blockIdx.y;
-    if (sel[2 * q + 1] > kAdcCand) return;  // too dense: the exact radix select handles this query
-    const uint32_t lo = kmin[q], hi = kmax[q], bmax = sel[2 * q];
-    const float *dq = dist + (size_t)q * n;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
-        const uint32_t key = adc_key(dq[i]);
-        if (knn_bin(key, lo, hi) <= bmax) {
-            const uint32_t pos = atomicAdd(&cand_n[q], 1u);
-            if (pos < kAdcCand) cand[(size_t)q * kAdcCand + pos] = ((unsigned long long)key << 32) | (uint32_t)i;
-        }
+// the search as a source of the selection stage (topk.hpp): dense rows, k_knn_hist's key bins over [kmin[q], kmax[q]]
+struct KnnSource : TopkRows {
+    const uint32_t *kmin, *kmax;
+    uint32_t lo = 0, hi = 0;  // (device: of the opened query)
+    __device__ void open(uint32_t q) {
+        TopkRows::open(q);
+        lo = kmin[q];
+        hi = kmax[q];
     }
-}
+    __device__ uint32_t bin(float dval) const { return knn_bin(adc_key(dval), lo, hi); }
+    uint32_t blocks() const { return (uint32_t)std::min<uint64_t>((n + 255) / 256, 64); }
+};
 
 // rerank: one workgroup per query computes D for its c candidates (the row of each gathered from the index), sorts the
 // (key, row) pairs in LDS and writes the first topk.  An id >= n reads nothing: it sets *err and sorts last.
@@ -258,28 +253,8 @@ __global__ __launch_bounds__(1024) void k_knn_rerank(const float *__restrict__ Q
         }
         buf[e] = w;
     }
-    __syncthreads();
-    for (uint32_t size = 2; size <= len; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t t = tid; t < len; t += 1024) {
-                const uint32_t partner = t ^ stride;
-                if (partner > t) {
-                    const bool up = (t & size) == 0;
-                    const unsigned long long a = buf[t], b = buf[partner];
-                    if ((a > b) == up) {
-                        buf[t] = b;
-                        buf[partner] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (uint32_t e = tid; e < topk; e += 1024) {
-        const unsigned long long w = buf[e];
-        idx_out[(size_t)q * topk + e] = (uint32_t)w;
-        dist_out[(size_t)q * topk + e] = adc_unkey((uint32_t)(w >> 32));
-    }
+    adc_bitonic<1024>(buf, len);
+    for (uint32_t e = tid; e < topk; e += 1024) adc_emit(buf[e], true, 0, idx_out + (size_t)q * topk + e, dist_out + (size_t)q * topk + e);
 }
 
 uint32_t knn_grid(uint64_t items, uint32_t per_cu) {
@@ -346,29 +321,20 @@ uint32_t knn_query_batch(uint64_t n, uint32_t nq) {
     if (g >= kKnnTQ) g = g / kKnnTQ * kKnnTQ;
     return (uint32_t)std::min<uint64_t>(g, std::max<uint32_t>(nq, 1));
 }
-// per query of a batch: kmin | kmax | hist [kAdcBins] | sel [2] | cand_n
-size_t knn_state_bytes(uint32_t qb) { return (size_t)qb * (1 + 1 + kAdcBins + 2 + 1) * 4; }
-size_t knn_cand_bytes(uint32_t qb) { return (size_t)qb * kAdcCand * 8; }
+// per query of a batch: kmin | kmax | the selection's state (topk.hpp)
+size_t knn_state_bytes(uint32_t qb) { return (size_t)qb * 2 * 4 + topk_state_bytes(qb); }
 
 // queries_dev [nq][d] f32, qnorm_dev [nq] (cosine; launch_knn_norms), workspaces sized for knn_query_batch(n, nq) queries:
-// dist_ws >= qb * n floats, state_ws >= knn_state_bytes(qb), cand_ws >= knn_cand_bytes(qb); outputs [nq][topk] on the device
+// dist_ws >= qb * n floats, state_ws >= knn_state_bytes(qb), cand_ws >= topk_cand_bytes(qb); outputs [nq][topk] on the device
 int launch_knn_search(int metric, const void *X, int dtype, uint64_t n, uint32_t d, const float *rnorm, const float *queries_dev,
                       const float *qnorm_dev, uint32_t nq, uint32_t topk, float *dist_ws, void *state_ws,
                       unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev, hipStream_t stream) {
     if (topk == 0 || topk > 1024 || topk > n) return fail(VQHIP_ERR_INVALID_INPUT, "topk must be in [1, min(n, 1024)]");
-    static PerDeviceOnce attr;
-    if (attr.needed()) {
-        VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_adc_sort_out), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)(kAdcCand * 8)));
-        attr.done();
-    }
     const uint32_t qb = knn_query_batch(n, nq);
     uint32_t *kmin = reinterpret_cast<uint32_t *>(state_ws);
     uint32_t *kmax = kmin + qb;
-    uint32_t *hist = kmax + qb;
-    uint32_t *sel = hist + (size_t)qb * kAdcBins;
-    uint32_t *cand_n = sel + 2 * (size_t)qb;
-    const uint32_t scan_blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, 64);
+    const TopkState st = topk_state(kmax + qb, qb);
+    const KnnSource src{{dist_ws, n}, kmin, kmax};
     for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
         const uint32_t nb = std::min(qb, nq - q0);
         const float *Qb = queries_dev + (size_t)q0 * d;
@@ -380,16 +346,10 @@ int launch_knn_search(int metric, const void *X, int dtype, uint64_t n, uint32_t
             return knn_dist_launch<decltype(mtag)::value, RT>(Qb, nb, reinterpret_cast<const RT *>(X), n, d, qn, rnorm, dist_ws,
                                                              kmin, kmax, stream);
         }));
-        hipLaunchKernelGGL(k_knn_hist, dim3(scan_blocks, nb), dim3(256), 0, stream, dist_ws, n, kmin, kmax, hist);
+        hipLaunchKernelGGL(k_knn_hist, dim3(src.blocks(), nb), dim3(256), 0, stream, dist_ws, n, kmin, kmax, st.hist);
         VQ_LAUNCH_CHECK("k_knn_hist");
-        hipLaunchKernelGGL(k_adc_pick_bin, dim3(nb), dim3(64), 0, stream, hist, topk, sel);
-        hipLaunchKernelGGL(k_knn_collect, dim3(scan_blocks, nb), dim3(256), 0, stream, dist_ws, n, kmin, kmax, sel, cand_ws, cand_n);
-        VQ_LAUNCH_CHECK("k_knn_collect");
-        hipLaunchKernelGGL(k_adc_sort_out, dim3(nb), dim3(1024), (size_t)kAdcCand * 8, stream, cand_ws, sel, topk, 0,
-                           idx_out_dev + (size_t)q0 * topk, dist_out_dev + (size_t)q0 * topk);
-        hipLaunchKernelGGL(k_adc_topk, dim3(nb), dim3(1024), 0, stream, dist_ws, n, topk, 0, sel,
-                           idx_out_dev + (size_t)q0 * topk, dist_out_dev + (size_t)q0 * topk);
-        VQ_LAUNCH_CHECK("k_adc_topk");
+        VQ_TRY(launch_topk_select(src, nb, topk, 0, st, cand_ws, idx_out_dev + (size_t)q0 * topk, dist_out_dev + (size_t)q0 * topk,
+                                  stream));
     }
     return VQHIP_OK;
 }

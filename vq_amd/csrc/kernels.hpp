@@ -249,7 +249,10 @@ int launch_adc_search(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int 
 uint32_t adc_query_batch();
 uint32_t adc_query_group(uint64_t n, uint32_t nq);  // queries that go through one set of launches (a multiple of the batch, all nq, or fewer where 4 n passes 1 GB)
 size_t adc_state_bytes(uint32_t qgroup);
-size_t adc_cand_bytes(uint32_t qgroup);
+// the selection stage's workspaces for a batch of qb queries (topk.hpp): its state hist | sel | cand_n, which every family's
+// state workspace ends in (the IVF search's is nothing else), and the candidate words [qb][kAdcCand] of every search
+size_t topk_state_bytes(uint32_t qb);
+size_t topk_cand_bytes(uint32_t qb);
 // VQHIP_ERR_UNSUPPORTED for a table above the LDS plan's limit (m * k > kAdcMaxTable, adc_plan.hpp): both schedules refuse it
 int fail_adc_table(uint32_t m, uint32_t k);
 // the threshold pass (one scan of the codes, candidates only): all queries in one set of launches; redo_dev[q] = 1 where
@@ -267,9 +270,8 @@ int launch_adc_search_fast(const float *cb, uint32_t m, uint32_t k, uint32_t sd,
 int launch_adc_lut(const float *queries_dev, uint32_t nq, uint32_t m, uint32_t k, uint32_t sd, const float *cb, int metric,
                    float *lut, float *bounds, hipStream_t stream);
 // inverted-file search over list-ordered PQ codes (k_ivf.hip): one batch of nb queries whose probe lists and tables are on
-// the device; W [nb][wstride] (wstride >= every query's |S(q)|), pref [nb][nprobe + 1], seg [nb][nprobe], bounds [nb][2]
-size_t ivf_state_bytes(uint32_t qb);
-size_t ivf_cand_bytes(uint32_t qb);
+// the device; W [nb][wstride] (wstride >= every query's |S(q)|), pref [nb][nprobe + 1], seg [nb][nprobe], bounds [nb][2],
+// state >= topk_state_bytes(nb), cand >= topk_cand_bytes(nb)
 uint32_t ivf_chunk(uint64_t expected_positions);
 int launch_ivf_search(const uint8_t *codes, const uint32_t *ids, const uint32_t *off, uint32_t nlist, uint32_t m, uint32_t k, int metric,
                       const float *lut, const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk,
@@ -290,7 +292,6 @@ int launch_ivf_rsearch(const uint8_t *codes, const uint32_t *ids, const uint32_t
 int launch_knn_norms(const void *X, int dtype, uint64_t n, uint32_t d, float *out, hipStream_t stream);
 uint32_t knn_query_batch(uint64_t n, uint32_t nq);
 size_t knn_state_bytes(uint32_t qb);
-size_t knn_cand_bytes(uint32_t qb);
 int launch_knn_search(int metric, const void *X, int dtype, uint64_t n, uint32_t d, const float *rnorm, const float *queries_dev,
                       const float *qnorm_dev, uint32_t nq, uint32_t topk, float *dist_ws, void *state_ws,
                       unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev, hipStream_t stream);
@@ -349,9 +350,8 @@ int launch_bq_pack(const void *x, int kind, uint64_t n, uint32_t d, float thr, u
 // *bad |= 1 where a packed row has a pad bit set (the caller zeroes it first)
 int launch_bin_padcheck(const uint32_t *P, uint64_t n, uint32_t d, uint32_t *bad, hipStream_t stream);
 size_t binary_hist_bytes(uint32_t qb, uint32_t d);
-size_t binary_cand_bytes(uint32_t qb);
 // Q [nb][W] packed queries, nb <= 1024; workspaces hist >= binary_hist_bytes(nb, d), sel [nb], adc_sel [2 nb], cnt [nb],
-// cand >= binary_cand_bytes(nb); results [nb][topk] on the device
+// cand >= topk_cand_bytes(nb); results [nb][topk] on the device
 int launch_binary_search(const uint32_t *P, uint64_t n, uint32_t d, int metric, const float *S, const uint32_t *Q, uint32_t nb,
                          uint32_t topk, uint32_t *hist, BinSel *sel, uint32_t *adc_sel, uint32_t *cnt,
                          unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream);

@@ -1,15 +1,31 @@
-// topk.hpp -- exact per-query top-k over f32 distances, shared by the ADC search (k_adc.hip) and the exact
-// k-NN search (k_knn.hip).  Device code only; every including file gets its own copy of the kernels.
+// topk.hpp -- the one exact top-k selection stage behind the ADC full pass (k_adc.hip), the exact k-NN search (k_knn.hip),
+// the inverted-file search (k_ivf.hip) and, from the sort on, the binary index (k_binary.hip).  Every including file gets
+// its own copy of the kernels (an anonymous namespace: no relocatable device code).
+// A scan leaves one f32 distance per (query, position) and a histogram of them, hist[q][kAdcBins].  The result of a query
+// is the first topk words (adc_key(D) << 32) | row id, ascending: NaN last, ties to the lower row id, whatever the bins.
+//   source              : what a family hands the stage, a small struct passed by value to the kernels:
+//                           Pos          the type of a position (uint64_t for dense rows, uint32_t for probed lists)
+//                           open(q)      turns the kernel's copy into the view of query q of the batch
+//                           count()      the query's positions;  at(pos) the distance;  id(pos) the row id behind it
+//                           bin(d)       the histogram bin of a distance (the bin the scan filled hist with)
+//                           blocks()     (host) the collect kernel's workgroups per query
+//                         TopkRows is the dense part (dist[q][n], id = position) of the ADC and k-NN sources
 //   adc_key / adc_unkey : the order-preserving key of a distance (NaN sorts last, reported back as 0x7FC00000)
-//   k_adc_pick_bin      : the histogram bin that holds the topk-th smallest value
-//   k_adc_sort_out      : the candidates of a query sorted by (key, row) in LDS, the first topk out
-//   k_adc_topk          : exact radix select where the candidate cut was too dense
+//   adc_scale / adc_bin : the float histogram bin of the ADC and IVF scans
+//   adc_bitonic         : the bitonic sort of (key, id) words in LDS;  adc_emit: one result slot from a word
+//   TopkState           : hist | sel | cand_n of a batch, carved from a workspace by topk_state
+//   launch_topk_select  : k_adc_pick_bin (the bin of the topk-th smallest value) -> k_adc_collect (the positions at or
+//                         below it as words) -> k_adc_sort_out (sorted in LDS, the first topk out, padding past a short
+//                         query's rows) -> k_adc_topk (exact radix select over (key, id) where the cut held more than
+//                         kAdcCand positions; k_adc_topk_rows for the sources built on TopkRows, chosen from the type)
 //   adc_terms / adc_row : D(q, i) of one row from ADC tables in LDS, subspace 0 first -- the one operation order of the ADC
 //                         scans (k_adc.hip) and the IVF scan (k_ivf.hip)
 #pragma once
 #include "adc_plan.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
+
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -72,7 +88,73 @@ __device__ __forceinline__ void adc_row(const uint8_t *__restrict__ codes, uint6
 // (kAdcBins, the histogram bins of the candidate filter: adc_plan.hpp)
 constexpr uint32_t kAdcCand = 8192; // candidates the fast top-k path sorts in LDS
 
-// fast top-k, step 1: the bin that holds the k-th smallest value; sel[q] = {bin, candidates up to it}
+// monotone (non-decreasing in d) bin of a distance over the range [lo, hi] of a query, scale = adc_scale(lo, hi); NaN and
+// out-of-range values go to the last bin
+__device__ __forceinline__ float adc_scale(float lo, float hi) { return (hi > lo) ? (float)kAdcBins / (hi - lo) : 0.0f; }
+__device__ __forceinline__ uint32_t adc_bin(float dval, float lo, float scale) {
+    const float t = (dval - lo) * scale;
+    return (t >= 0.0f && t < (float)(kAdcBins - 1)) ? (uint32_t)t : ((t < 0.0f) ? 0u : kAdcBins - 1);
+}
+
+// the dense part of a source: dist[q][n], the row id is the position (offsets q * n + pos stay 64-bit)
+struct TopkRows {
+    using Pos = uint64_t;
+    const float *dist;
+    uint64_t n;
+    __device__ void open(uint32_t q) { dist += (size_t)q * n; }
+    __device__ Pos count() const { return n; }
+    __device__ float at(Pos pos) const { return dist[pos]; }
+    __device__ uint32_t id(Pos pos) const { return (uint32_t)pos; }
+};
+
+// per query of a batch of qb: hist [kAdcBins] | sel [2] = {bin of the cut, positions up to it} | cand_n, in this order
+// (topk_state_bytes(qb), kernels.hpp; a family's own prefix -- ADC's bounds, k-NN's kmin / kmax -- sits in front)
+struct TopkState {
+    uint32_t *hist, *sel, *cand_n;
+};
+inline TopkState topk_state(void *ws, uint32_t qb) {
+    uint32_t *hist = reinterpret_cast<uint32_t *>(ws);
+    return {hist, hist + (size_t)qb * kAdcBins, hist + (size_t)qb * (kAdcBins + 2)};
+}
+
+// ascending bitonic sort of buf[0 .. len) in LDS by a workgroup of NT threads, len a power of two; a barrier in front
+// (the buffer's writers) and behind
+template <uint32_t NT>
+__device__ __forceinline__ void adc_bitonic(unsigned long long *buf, uint32_t len) {
+    __syncthreads();
+    for (uint32_t size = 2; size <= len; size <<= 1) {
+        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+            for (uint32_t t = threadIdx.x; t < len; t += NT) {
+                const uint32_t partner = t ^ stride;
+                if (partner > t) {
+                    const bool up = (t & size) == 0;
+                    const unsigned long long a = buf[t], b = buf[partner];
+                    if ((a > b) == up) {
+                        buf[t] = b;
+                        buf[partner] = a;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// one result slot from a word: the row id and the distance behind the key (sqrtf for Euclidean); !real: padding
+__device__ __forceinline__ void adc_emit(unsigned long long w, bool real, int take_sqrt, uint32_t *idx, float *dist) {
+    if (!real) {
+        *idx = 0xFFFFFFFFu;
+        *dist = __builtin_inff();
+        return;
+    }
+    float dv = adc_unkey((uint32_t)(w >> 32));
+    if (take_sqrt) dv = sqrtf(dv);
+    *idx = (uint32_t)w;
+    *dist = dv;
+}
+
+// step 1: the bin that holds the k-th smallest value; sel[q] = {bin, candidates up to it} ({kAdcBins, all of them} for a
+// query with fewer than topk positions)
 __attribute__((unused)) __global__ __launch_bounds__(64) void k_adc_pick_bin(const uint32_t *__restrict__ hist, uint32_t topk,
                                                      uint32_t *__restrict__ sel) {
     const uint32_t q = blockIdx.x;
@@ -86,53 +168,129 @@ __attribute__((unused)) __global__ __launch_bounds__(64) void k_adc_pick_bin(con
     sel[2 * q + 1] = cum;
 }
 
-// step 3: sort the candidates by (key, row) in LDS, emit the first topk
-__attribute__((unused)) __global__ __launch_bounds__(1024) void k_adc_sort_out(const unsigned long long *__restrict__ cand,
-                                                       const uint32_t *__restrict__ sel, uint32_t topk, int take_sqrt,
-                                                       uint32_t *__restrict__ idx_out, float *__restrict__ dist_out) {
-    extern __shared__ unsigned long long sort_buf[];  // [kAdcCand]
-    const uint32_t q = blockIdx.x, cnt = sel[2 * q + 1];
-    if (cnt > kAdcCand) return;  // handled by k_adc_topk
-    uint32_t len = 1024;
-    while (len < cnt) len <<= 1;
-    for (uint32_t e = threadIdx.x; e < len; e += 1024) sort_buf[e] = (e < cnt) ? cand[(size_t)q * kAdcCand + e] : ~0ull;
-    __syncthreads();
-    for (uint32_t size = 2; size <= len; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t t = threadIdx.x; t < len; t += 1024) {
-                const uint32_t partner = t ^ stride;
-                if (partner > t) {
-                    const bool up = (t & size) == 0;
-                    const unsigned long long a = sort_buf[t], b = sort_buf[partner];
-                    if ((a > b) == up) {
-                        sort_buf[t] = b;
-                        sort_buf[partner] = a;
-                    }
-                }
-            }
-            __syncthreads();
+// step 2: every position whose bin is <= the selected one becomes a candidate word; any order (the sort orders them)
+template <class Src>
+__global__ __launch_bounds__(256) void k_adc_collect(Src src, const uint32_t *__restrict__ sel,
+                                                     unsigned long long *__restrict__ cand, uint32_t *__restrict__ cand_n) {
+    using Pos = typename Src::Pos;
+    const uint32_t q = blockIdx.y;
+    if (sel[2 * q + 1] > kAdcCand) return;  // too dense: k_adc_topk
+    src.open(q);
+    const uint32_t bmax = sel[2 * q];
+    const Pos total = src.count();
+    for (Pos pos = (Pos)blockIdx.x * 256 + threadIdx.x; pos < total; pos += (Pos)gridDim.x * 256) {
+        const float dv = src.at(pos);
+        if (src.bin(dv) <= bmax) {
+            const uint32_t at = atomicAdd(&cand_n[q], 1u);
+            if (at < kAdcCand) cand[(size_t)q * kAdcCand + at] = ((unsigned long long)adc_key(dv) << 32) | src.id(pos);
         }
-    }
-    if (threadIdx.x < topk) {
-        const unsigned long long w = sort_buf[threadIdx.x];
-        float dv = adc_unkey((uint32_t)(w >> 32));
-        if (take_sqrt) dv = sqrtf(dv);
-        idx_out[(size_t)q * topk + threadIdx.x] = (uint32_t)w;
-        dist_out[(size_t)q * topk + threadIdx.x] = dv;
     }
 }
 
-// exact top-k of one query's distances: radix select of the k-th key, ordered collection (ties by
-// row index), bitonic sort of the <= 1024 winners by (key, index)
-__attribute__((unused)) __global__ __launch_bounds__(1024) void k_adc_topk(const float *__restrict__ dist, uint64_t n, uint32_t topk, int take_sqrt,
-                                                   const uint32_t *__restrict__ sel, uint32_t *__restrict__ idx_out,
-                                                   float *__restrict__ dist_out) {
+// step 3: the candidates sorted in LDS, the first topk out; slots at or past the candidate count (a query with fewer
+// than topk positions) are padding
+__attribute__((unused)) __global__ __launch_bounds__(1024) void k_adc_sort_out(const unsigned long long *__restrict__ cand,
+                                                       const uint32_t *__restrict__ sel, uint32_t topk, int take_sqrt,
+                                                       uint32_t *__restrict__ idx_out, float *__restrict__ dist_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long sort_buf[];  // [kAdcCand]
+    const uint32_t q = blockIdx.x, cnt = sel[2 * q + 1];
+    if (cnt > kAdcCand) return;  // k_adc_topk
+    uint32_t len = 1024;
+    while (len < cnt) len <<= 1;
+    for (uint32_t e = threadIdx.x; e < len; e += 1024) sort_buf[e] = (e < cnt) ? cand[(size_t)q * kAdcCand + e] : ~0ull;
+    adc_bitonic<1024>(sort_buf, len);
+    if (threadIdx.x < topk)
+        adc_emit(sort_buf[threadIdx.x], threadIdx.x < cnt, take_sqrt, idx_out + (size_t)q * topk + threadIdx.x,
+                 dist_out + (size_t)q * topk + threadIdx.x);
+}
+
+// step 4, a query whose cut held more than kAdcCand positions (ties piled on one value): exact radix select of the
+// topk-th smallest word -- the key's four bytes over all positions, then the row id's four over the positions of that
+// key -- and the topk words at or below it, sorted.  More than kAdcCand >= topk positions here: no padding.
+template <class Src>
+__global__ __launch_bounds__(1024) void k_adc_topk(Src src, uint32_t topk, int take_sqrt, const uint32_t *__restrict__ sel,
+                                                   uint32_t *__restrict__ idx_out, float *__restrict__ dist_out) {
+    using Pos = typename Src::Pos;
+    const uint32_t q = blockIdx.x;
+    if (sel[2 * q + 1] <= kAdcCand) return;  // the candidate sort produced this query's result
     __shared__ uint32_t hist[256];
-    if (sel && sel[2 * blockIdx.x + 1] <= kAdcCand) return;  // the candidate path produced this query's result
+    __shared__ uint32_t s_prefix, s_rank, s_count;
+    __shared__ unsigned long long win[1024];
+    src.open(q);
+    const Pos total = src.count();
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) {
+        s_prefix = 0;
+        s_rank = topk - 1;
+    }
+    __syncthreads();
+    // pass 0 finds the key T of the topk-th word and its rank among the words of key T; pass 1 the row id R of that rank
+    uint32_t T = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) hist[tid] = 0;
+            __syncthreads();
+            const uint32_t prefix = s_prefix, himask = (shift == 24) ? 0u : (0xFFFFFFFFu << (shift + 8));
+            for (Pos pos = tid; pos < total; pos += 1024) {
+                const uint32_t key = adc_key(src.at(pos));
+                uint32_t v = key;
+                if (pass == 1) {
+                    if (key != T) continue;
+                    v = src.id(pos);
+                }
+                if ((v & himask) == prefix) atomicAdd(&hist[(v >> shift) & 255u], 1u);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                uint32_t rank = s_rank, b = 0;
+                for (; b < 255; ++b) {
+                    if (rank < hist[b]) break;
+                    rank -= hist[b];
+                }
+                s_rank = rank;
+                s_prefix = prefix | (b << shift);
+            }
+            __syncthreads();
+        }
+        if (pass == 0) {
+            T = s_prefix;
+            __syncthreads();
+            if (tid == 0) s_prefix = 0;  // (s_rank: the rank among the words of key T, carried into pass 1)
+            __syncthreads();
+        }
+    }
+    const unsigned long long cut = ((unsigned long long)T << 32) | s_prefix;  // the topk-th smallest word
+    if (tid == 0) s_count = 0;
+    win[tid] = ~0ull;
+    __syncthreads();
+    for (Pos pos = tid; pos < total; pos += 1024) {
+        const uint32_t key = adc_key(src.at(pos));
+        if (key > T) continue;
+        const unsigned long long w = ((unsigned long long)key << 32) | src.id(pos);
+        if (w <= cut) {
+            const uint32_t at = atomicAdd(&s_count, 1u);
+            if (at < 1024) win[at] = w;  // (exactly topk words pass)
+        }
+    }
+    adc_bitonic<1024>(win, 1024);
+    if (tid < topk) adc_emit(win[tid], true, take_sqrt, idx_out + (size_t)q * topk + tid, dist_out + (size_t)q * topk + tid);
+}
+
+// step 4 for dense rows (TopkRows: the row id is the position): the key's four bytes as above, then an ORDERED collection
+// in chunks of 1024 rows (block prefix sums keep row order) that ends at the topk-th word -- ties go to the lowest rows
+// without the four passes over the row id.  Kept beside k_adc_topk because it is faster there: 3.2 against 5.3 ms (ADC)
+// and 2.7 against 4.6 ms (k-NN) for 64 queries over 1M rows with 62500 ties at the cut (profiles/topk/ab.json).
+__attribute__((unused)) __global__ __launch_bounds__(1024) void k_adc_topk_rows(TopkRows src, uint32_t topk, int take_sqrt,
+                                                        const uint32_t *__restrict__ sel, uint32_t *__restrict__ idx_out,
+                                                        float *__restrict__ dist_out) {
+    if (sel[2 * blockIdx.x + 1] <= kAdcCand) return;  // the candidate sort produced this query's result
+    __shared__ uint32_t hist[256];
     __shared__ uint32_t s_prefix, s_rank, s_count;
     __shared__ uint32_t wsum[16];
     __shared__ unsigned long long win[1024];
-    const float *dq = dist + (size_t)blockIdx.x * n;
+    src.open(blockIdx.x);
+    const float *dq = src.dist;
+    const uint64_t n = src.n;
     const uint32_t tid = threadIdx.x;
     if (tid == 0) {
         s_prefix = 0;
@@ -207,33 +365,42 @@ __attribute__((unused)) __global__ __launch_bounds__(1024) void k_adc_topk(const
         __syncthreads();
         if (s_count >= topk) break;  // uniform
     }
-    const uint32_t got = s_count < topk ? s_count : topk;
-    for (uint32_t e = tid; e < 1024; e += 1024)
-        if (e >= got) win[e] = ~0ull;
-    __syncthreads();
-    // bitonic sort of 1024 (key, index) pairs
-    for (uint32_t size = 2; size <= 1024; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            const uint32_t partner = tid ^ stride;
-            if (partner > tid) {
-                const bool up = (tid & size) == 0;
-                const unsigned long long a = win[tid], b = win[partner];
-                if ((a > b) == up) {
-                    win[tid] = b;
-                    win[partner] = a;
-                }
-            }
-            __syncthreads();
-        }
+    if (tid >= topk) win[tid] = ~0ull;  // (exactly topk words were taken)
+    adc_bitonic<1024>(win, 1024);
+    if (tid < topk)
+        adc_emit(win[tid], true, take_sqrt, idx_out + (size_t)blockIdx.x * topk + tid, dist_out + (size_t)blockIdx.x * topk + tid);
+}
+
+// the dynamic LDS of k_adc_sort_out (this file's copy), once per device
+inline int topk_sort_attr() {
+    static PerDeviceOnce attr;
+    if (attr.needed()) {
+        VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_adc_sort_out), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)(kAdcCand * 8)));
+        attr.done();
     }
-    if (tid < topk) {
-        const unsigned long long w = win[tid];
-        const bool valid = tid < got;
-        float dv = adc_unkey((uint32_t)(w >> 32));
-        if (take_sqrt) dv = sqrtf(dv);
-        idx_out[(size_t)blockIdx.x * topk + tid] = valid ? (uint32_t)w : 0xFFFFFFFFu;
-        dist_out[(size_t)blockIdx.x * topk + tid] = valid ? dv : __uint_as_float(0x7FC00000u);
-    }
+    return VQHIP_OK;
+}
+
+// The selection of one batch of nb queries whose scan has filled st.hist (st zeroed before the scan): results
+// [nb][topk] on the device.  cand >= topk_cand_bytes(nb).
+template <class Src>
+int launch_topk_select(const Src &src, uint32_t nb, uint32_t topk, int take_sqrt, const TopkState &st, unsigned long long *cand,
+                       uint32_t *idx_out, float *dist_out, hipStream_t stream) {
+    VQ_TRY(topk_sort_attr());
+    hipLaunchKernelGGL(k_adc_pick_bin, dim3(nb), dim3(64), 0, stream, st.hist, topk, st.sel);
+    VQ_LAUNCH_CHECK("k_adc_pick_bin");
+    hipLaunchKernelGGL(k_adc_collect<Src>, dim3(src.blocks(), nb), dim3(256), 0, stream, src, st.sel, cand, st.cand_n);
+    VQ_LAUNCH_CHECK("k_adc_collect");
+    hipLaunchKernelGGL(k_adc_sort_out, dim3(nb), dim3(1024), (size_t)kAdcCand * 8, stream, cand, st.sel, topk, take_sqrt, idx_out,
+                       dist_out);
+    VQ_LAUNCH_CHECK("k_adc_sort_out");
+    if constexpr (std::is_base_of<TopkRows, Src>::value)
+        hipLaunchKernelGGL(k_adc_topk_rows, dim3(nb), dim3(1024), 0, stream, src, topk, take_sqrt, st.sel, idx_out, dist_out);
+    else
+        hipLaunchKernelGGL(k_adc_topk<Src>, dim3(nb), dim3(1024), 0, stream, src, topk, take_sqrt, st.sel, idx_out, dist_out);
+    VQ_LAUNCH_CHECK("k_adc_topk");
+    return VQHIP_OK;
 }
 
 }  // namespace
