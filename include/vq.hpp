@@ -812,6 +812,89 @@ class BinaryIndex {
     Distance distance_;
 };
 
+// Exact index over SQ codes kept on the device, one byte per dimension (include/vqhip.h, vqhip_sqindex_*): built from f32
+// rows (encoded on the device; only the codes stay) or from u8 codes, searched with f32 queries under any metric.  Every
+// result equals FlatIndex over quantizer.dequantize(codes): (row index, distance) pairs [nq][topk], nearest first, NaN
+// last, ties to the lower row.  The arguments are checked before the device is touched.
+class ScalarIndex {
+   public:
+    ScalarIndex(const float *rows, std::size_t n, std::size_t dim, ScalarQuantizer quantizer, Distance distance = Distance())
+        : quantizer_(quantizer) {
+        init(rows, true, n, dim, distance);
+    }
+    ScalarIndex(const std::uint8_t *codes, std::size_t n, std::size_t dim, ScalarQuantizer quantizer, Distance distance = Distance())
+        : quantizer_(quantizer) {
+        init(codes, false, n, dim, distance);
+    }
+    std::size_t size() const { return n_; }
+    std::size_t dim() const { return dim_; }
+    const ScalarQuantizer &quantizer() const { return quantizer_; }
+    const char *distance_metric() const { return distance_.name(); }
+
+    struct Result {
+        std::vector<std::uint32_t> idx;  // [nq][topk]
+        std::vector<float> dist;         // [nq][topk]
+    };
+    // queries [nq][dim] f32, never quantized
+    Result search(const float *queries, std::size_t nq, std::size_t topk) const {
+        if (topk == 0 || topk > 1024 || topk > n_)
+            throw VqError::InvalidParameter("topk", "must be between 1 and min(n, 1024)");
+        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
+        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
+        if (nq) detail::check(vqhip_sqindex_search(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)topk, r.idx.data(), r.dist.data()));
+        return r;
+    }
+    Result search(const std::vector<float> &queries, std::size_t topk) const {
+        if (queries.size() % dim_) throw VqError::DimensionMismatch(dim_, queries.size() % dim_);
+        return search(queries.data(), queries.size() / dim_, topk);
+    }
+    // per query the topk nearest of its c candidate row ids cand [nq][c] (distinct within a query, each < n)
+    Result rerank(const float *queries, std::size_t nq, const std::uint32_t *cand, std::size_t c, std::size_t topk) const {
+        if (c == 0 || c > 4096) throw VqError::InvalidParameter("candidates", "between 1 and 4096 per query");
+        if (topk == 0 || topk > c) throw VqError::InvalidParameter("topk", "must be between 1 and the number of candidates");
+        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
+        for (std::size_t e = 0; e < nq * c; ++e)
+            if (cand[e] >= n_) throw VqError::InvalidParameter("candidates", "a row id is outside [0, n)");
+        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
+        if (nq)
+            detail::check(vqhip_sqindex_rerank(ix_.get(), queries, (std::uint32_t)nq, cand, (std::uint32_t)c, (std::uint32_t)topk,
+                                               r.idx.data(), r.dist.data()));
+        return r;
+    }
+    // the codes [n][dim]
+    std::vector<std::uint8_t> codes() const {
+        std::vector<std::uint8_t> out(n_ * dim_);
+        detail::check(vqhip_sqindex_codes(ix_.get(), out.data()));
+        return out;
+    }
+
+   private:
+    struct Del {
+        void operator()(vqhip_sqindex *p) const { (void)vqhip_sqindex_destroy(p); }
+    };
+    void init(const void *src, bool rows, std::size_t n, std::size_t dim, Distance distance) {
+        if (n == 0) throw VqError::EmptyInput();
+        if (dim == 0) throw VqError::InvalidParameter("dim", "must be at least 1");
+        if (n >= (std::size_t(1) << 32) || dim > 0xFFFFFFFFu) throw VqError::InvalidParameter("rows", "at most 2^32 - 1 rows of 2^32 - 1 dimensions");
+        vqhip_sqindex *x = nullptr;
+        const std::uint32_t levels = (std::uint32_t)quantizer_.levels();
+        if (rows)
+            detail::check(vqhip_sqindex_create_rows(quantizer_.min(), quantizer_.max(), levels, static_cast<const float *>(src), n,
+                                                    (std::uint32_t)dim, (int)distance.kind(), &x));
+        else
+            detail::check(vqhip_sqindex_create(quantizer_.min(), quantizer_.max(), levels, static_cast<const std::uint8_t *>(src), n,
+                                               (std::uint32_t)dim, (int)distance.kind(), &x));
+        ix_.reset(x);
+        n_ = n;
+        dim_ = dim;
+        distance_ = distance;
+    }
+    ScalarQuantizer quantizer_;
+    std::unique_ptr<vqhip_sqindex, Del> ix_;
+    std::size_t n_ = 0, dim_ = 0;
+    Distance distance_;
+};
+
 // Inverted-file index over PQ codes (include/vqhip.h, vqhip_ivfpq_*): coarse centroids [nlist][dim], codebooks
 // [m][k][sub_dim], rows added as (list id, codes).  search scans only the nprobe lists nearest to a query and gives
 // (row id, ADC distance) pairs [nq][topk], nearest first; slots past the probed rows hold (0xFFFFFFFF, +inf).  The

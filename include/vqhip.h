@@ -518,6 +518,47 @@ int vqhip_binary_search(vqhip_binary *b, const float *queries, uint32_t nq, uint
 int vqhip_binary_search_device(vqhip_binary *b, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx,
                                void *dev_dist);
 
+/* ---- scalar index: exact top-k over resident SQ codes (k_sqindex.hip) -------------------------
+ * No reference counterpart.  An index is fixed by a ScalarQuantizer(min, max, levels), a metric (any of the five, as in
+ * the flat index) and codes [n][d] u8, one byte per dimension, kept on the device; the f32 rows are never kept.  The
+ * quantizer passes vqhip_sq_check first and its error text is reported unchanged.  Queries are f32 and never quantized.
+ *   v(c)    = min + (float)c * step, step = (max - min) / (levels - 1): the SQ decode rule above, un-fused, for every
+ *             byte value.  Codes >= levels are legal and decode by the same formula, as vqhip_sq_decode does.
+ *   D(q, i) = Distance::compute(q, v(codes[i])) bit for bit: the pair summed sequentially over t = 0..d-1 from -0.0f, one
+ *             rounding per operation, no fused multiply-add; Euclidean = sqrtf of the sum; cosine through
+ *             vq_cosine_finish, the row norm sqrtf(sum v^2) computed once at create and the query norm once per call.
+ *   search / rerank = vqhip_flat_search / vqhip_flat_rerank over the rows vqhip_sq_decode gives for the codes: equal
+ *             indices, distances equal as uint32 bits.  That is the order (key(D), row), NaN last and reported as
+ *             0x7FC00000, ties to the lower row, Euclidean ordered by the reported root; a rerank id >= n is flagged on
+ *             the device, never read, and gives VQHIP_ERR_INVALID_INPUT.
+ *   A degenerate quantizer is no special case: (-3e38, 3e38, 2) has step = inf, v(0) = 0 * inf = NaN; such rows have NaN
+ *   distances and sort last by row id.
+ * Limits: 1 <= d, 1 <= n < 2^32, 1 <= topk <= min(n, 1024), nq < 2^32 (served in batches), rerank lists of 1..4096
+ * distinct ids.  create / create_device take codes (host: uploaded once; device: copied, any alignment);
+ * create_rows / create_rows_device take f32 rows [n][d] (device: 4-byte aligned) and encode them on the device with
+ * the SQ encode rule, so that only the codes stay.  vqhip_sqindex_codes copies the codes [n][d] to the host.  Every
+ * parameter is checked before any device work.  Host forms return when the results are there; search_device is
+ * asynchronous on the current stream.  One lock per handle, as vqhip_flat's.  info: any output pointer may be NULL. */
+typedef struct vqhip_sqindex vqhip_sqindex;
+int vqhip_sqindex_create(float min, float max, uint32_t levels, const uint8_t *codes, uint64_t n, uint32_t d, int metric,
+                         vqhip_sqindex **out);
+int vqhip_sqindex_create_device(float min, float max, uint32_t levels, const void *dev_codes, uint64_t n, uint32_t d,
+                                int metric, vqhip_sqindex **out);
+int vqhip_sqindex_create_rows(float min, float max, uint32_t levels, const float *rows, uint64_t n, uint32_t d, int metric,
+                              vqhip_sqindex **out);
+int vqhip_sqindex_create_rows_device(float min, float max, uint32_t levels, const void *dev_rows, uint64_t n, uint32_t d,
+                                     int metric, vqhip_sqindex **out);
+int vqhip_sqindex_destroy(vqhip_sqindex *x);
+int vqhip_sqindex_info(const vqhip_sqindex *x, uint64_t *n, uint32_t *d, int *metric, float *min, float *max,
+                       uint32_t *levels);
+int vqhip_sqindex_codes(vqhip_sqindex *x, uint8_t *codes);
+int vqhip_sqindex_search(vqhip_sqindex *x, const float *queries, uint32_t nq, uint32_t topk, uint32_t *idx_out,
+                         float *dist_out);
+int vqhip_sqindex_search_device(vqhip_sqindex *x, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx,
+                                void *dev_dist);
+int vqhip_sqindex_rerank(vqhip_sqindex *x, const float *queries, uint32_t nq, const uint32_t *cand, uint32_t c,
+                         uint32_t topk, uint32_t *idx_out, float *dist_out);
+
 /* ---- inverted-file PQ index: search only the probed lists (k_ivf.hip) -----------------------
  * No reference counterpart.  An index holds coarse centroids C [nlist][dim] f32 (1 <= nlist <= 65536), PQ codebooks
  * cb [m][k][sub_dim] (dim = m * sub_dim) and a metric: squared Euclidean, Euclidean or Manhattan (cosine is refused with

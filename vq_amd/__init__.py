@@ -1,7 +1,8 @@
 """vq_amd -- MI355X (gfx950) back end for the k-means codebook-training and nearest-centroid
 encode path of CogitatorTech/vq, and of its elementwise scalar / binary quantizers, behind the
 reference's own Quantizer interface, exact k-NN search over resident rows (FlatIndex), an inverted-file
-index over PQ codes (IVFPQIndex) and a Hamming index over packed BQ codes (BinaryIndex).
+index over PQ codes (IVFPQIndex), a Hamming index over packed BQ codes (BinaryIndex) and an exact index over
+resident SQ codes (ScalarIndex).
 
 The compute path is libvqhip.so (hand-written HIP for CDNA4, C ABI in include/vqhip.h).
 Importing the package does not need a GPU; using any quantizer does, and fails loudly
@@ -15,11 +16,12 @@ from .bq import BinaryQuantizer
 from .flat import FlatIndex
 from .ivf import IVFPQIndex
 from .pq import ProductQuantizer, fit_codebooks
+from .scalar_index import ScalarIndex
 from .sq import ScalarQuantizer
 from .tsvq import TSVQ
 
 __all__ = [
-    "Distance", "BinaryIndex", "BinaryQuantizer", "FlatIndex", "IVFPQIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
+    "Distance", "BinaryIndex", "BinaryQuantizer", "FlatIndex", "IVFPQIndex", "ScalarIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
     "InvalidParameter", "InvalidData", "FfiError", "get_simd_backend",
 ]
 

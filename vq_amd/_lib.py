@@ -163,6 +163,17 @@ SIGNATURES = {
     "vqhip_binary_packed": (C.c_int, [_vp, _u32p]),
     "vqhip_binary_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
     "vqhip_binary_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "vqhip_sqindex_create": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_int, _vpp]),
+    "vqhip_sqindex_create_device": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_int, _vpp]),
+    "vqhip_sqindex_create_rows": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_int, _vpp]),
+    "vqhip_sqindex_create_rows_device": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_int,
+                                                   _vpp]),
+    "vqhip_sqindex_destroy": (C.c_int, [_vp]),
+    "vqhip_sqindex_info": (C.c_int, [_vp, _u64p, _u32p, C.POINTER(C.c_int), _f32p, _f32p, _u32p]),
+    "vqhip_sqindex_codes": (C.c_int, [_vp, _u8p]),
+    "vqhip_sqindex_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "vqhip_sqindex_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "vqhip_sqindex_rerank": (C.c_int, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
     "vqhip_ivfpq_create": (C.c_int, [_f32p, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _vpp]),
     "vqhip_ivfpq_destroy": (C.c_int, [_vp]),
     "vqhip_ivfpq_add": (C.c_int, [_vp, _u32p, _vp, C.c_uint64]),
@@ -826,6 +837,50 @@ class Binary(Handle):
     def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int):
         check(load().vqhip_binary_search_device(self.raw, C.c_void_p(dev_queries), int(nq), int(topk), C.c_void_p(dev_idx),
                                                 C.c_void_p(dev_dist)))
+
+
+class SQIndex(Handle):
+    """vqhip_sqindex: SQ codes resident on the device, one byte per dimension, exact top-k search and exact rerank against
+    f32 queries (k_sqindex.hip)"""
+
+    _destroy = "vqhip_sqindex_destroy"
+
+    def __init__(self, src, rows: bool, n: int, d: int, mn: float, mx: float, levels: int, metric: int,
+                 dev_src: int | None = None):
+        """src: a C-contiguous host array, u8 codes [n][d] or (rows) f32 rows [n][d] to encode; or dev_src, a device
+        pointer to the same"""
+        h = C.c_void_p()
+        name = "vqhip_sqindex_create" + ("_rows" if rows else "") + ("_device" if dev_src is not None else "")
+        p = C.c_void_p(dev_src) if dev_src is not None else src.ctypes.data_as(_vp)
+        check(getattr(load(), name)(mn, mx, int(levels), p, int(n), int(d), int(metric), C.byref(h)))
+        super().__init__(h)
+        self.n, self.d, self.metric = int(n), int(d), int(metric)
+
+    def codes(self) -> np.ndarray:
+        out = np.empty((self.n, self.d), np.uint8)
+        check(load().vqhip_sqindex_codes(self.raw, ptr(out, _u8p)))
+        return out
+
+    def search(self, q: np.ndarray, topk: int):
+        nq = q.shape[0]
+        idx = np.empty((nq, topk), np.uint32)
+        dist = np.empty((nq, topk), np.float32)
+        if nq:
+            check(load().vqhip_sqindex_search(self.raw, ptr(q, _f32p), nq, int(topk), ptr(idx, _u32p), ptr(dist, _f32p)))
+        return idx, dist
+
+    def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int):
+        check(load().vqhip_sqindex_search_device(self.raw, C.c_void_p(dev_queries), int(nq), int(topk), C.c_void_p(dev_idx),
+                                                 C.c_void_p(dev_dist)))
+
+    def rerank(self, q: np.ndarray, cand: np.ndarray, topk: int):
+        nq, c = cand.shape
+        idx = np.empty((nq, topk), np.uint32)
+        dist = np.empty((nq, topk), np.float32)
+        if nq:
+            check(load().vqhip_sqindex_rerank(self.raw, ptr(q, _f32p), nq, ptr(cand, _u32p), int(c), int(topk), ptr(idx, _u32p),
+                                              ptr(dist, _f32p)))
+        return idx, dist
 
 
 class IVFPQ(Handle):

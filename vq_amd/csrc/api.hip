@@ -2884,6 +2884,216 @@ int vqhip_flat_rerank(vqhip_flat *f, const float *queries, uint32_t nq, const ui
 
 }  // extern "C"
 
+// ------------------------------------------------------------------ scalar index (k_sqindex.hip) ----
+struct vqhip_sqindex {
+    HandleSync sync;
+    uint64_t n = 0;
+    uint32_t d = 0, levels = 0;
+    float mn = 0, mx = 0, step = 0;
+    int metric = VQHIP_EUCLIDEAN;
+    DevBuf codes, rnorm;                           // the index: [n][d] u8, |v(row)| for cosine
+    DevBuf q, qnorm, dist, state, cand, idx, out;  // per-call workspaces
+    DevBuf rr_cand, rr_err;                        // rerank: candidate ids, the out-of-range flag
+};
+
+// src: u8 codes [n][d] (rows == false) or f32 rows [n][d] to encode (rows == true), in host (kind = H2D) or device memory
+static int sqindex_create(const void *src, hipMemcpyKind kind, bool rows, float mn, float mx, uint32_t levels, uint64_t n,
+                          uint32_t d, int metric, vqhip_sqindex **out) {
+    if (!out) return fail(VQHIP_ERR_NULL_PTR, "out is NULL");
+    *out = nullptr;
+    SqbqEncodeOp op;
+    float step = 0;
+    VQ_TRY(sq_check(mn, mx, levels, &step));
+    if (!src) return fail(VQHIP_ERR_NULL_PTR, rows ? "rows is NULL" : "codes is NULL");
+    if (d == 0) return fail(VQHIP_ERR_INVALID_INPUT, "d must be at least 1");
+    if (n == 0 || n >= (1ull << 32)) return fail(VQHIP_ERR_INVALID_INPUT, "n must be in [1, 2^32)");
+    if (metric < VQHIP_SQUARED_EUCLIDEAN || metric > VQHIP_COSINE_UNCLAMPED) return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
+    if (rows && kind == hipMemcpyDeviceToDevice && (reinterpret_cast<uintptr_t>(src) & 3))
+        return fail(VQHIP_ERR_INVALID_INPUT, "rows are not 4-byte aligned");
+    if (rows) VQ_TRY(sq_encode_op(mn, mx, levels, &op));
+    VQ_TRY(require_gfx950());
+    hipStream_t s;
+    VQ_TRY(current_stream(&s));
+    std::unique_ptr<vqhip_sqindex> x(new vqhip_sqindex());
+    x->n = n, x->d = d, x->levels = levels, x->mn = mn, x->mx = mx, x->step = step, x->metric = metric;
+    const size_t bytes = (size_t)n * d;
+    VQ_TRY(x->codes.alloc(bytes));
+    if (!rows) {
+        VQ_HIP(hipMemcpyAsync(x->codes.p, src, bytes, kind, s));
+    } else if (kind == hipMemcpyDeviceToDevice) {
+        VQ_TRY(launch_sqbq_encode(op, static_cast<const float *>(src), bytes, x->codes.as<uint8_t>(), s));
+    } else {
+        // host rows: encoded through a staging buffer of at most 256 MB at a time, so that only the codes stay
+        const uint64_t per = std::max<uint64_t>(1, (256ull << 20) / ((uint64_t)d * 4));
+        DevBuf stage;
+        VQ_TRY(stage.alloc((size_t)std::min<uint64_t>(per, n) * d * 4));
+        for (uint64_t r0 = 0; r0 < n; r0 += per) {
+            const uint64_t rn = std::min<uint64_t>(per, n - r0);
+            VQ_HIP(hipMemcpyAsync(stage.p, static_cast<const float *>(src) + r0 * d, (size_t)rn * d * 4, hipMemcpyHostToDevice, s));
+            VQ_TRY(launch_sqbq_encode(op, stage.as<float>(), rn * d, x->codes.as<uint8_t>() + r0 * d, s));
+            VQ_HIP(hipStreamSynchronize(s));
+        }
+    }
+    if (vq_is_cos(metric)) {
+        VQ_TRY(x->rnorm.alloc((size_t)n * 4));
+        VQ_TRY(launch_sq_norms(x->codes.as<uint8_t>(), n, d, mn, step, x->rnorm.as<float>(), s));
+    }
+    VQ_HIP(hipStreamSynchronize(s));  // the caller may free or change its source once this returns
+    *out = x.release();
+    return VQHIP_OK;
+}
+
+// the query norms of a cosine index into x->qnorm (NULL otherwise)
+static int sqindex_qnorms(vqhip_sqindex *x, const float *queries_dev, uint32_t nq, const float **qn, hipStream_t s) {
+    *qn = nullptr;
+    if (!vq_is_cos(x->metric)) return VQHIP_OK;
+    VQ_TRY(x->qnorm.ensure((size_t)nq * 4));
+    VQ_TRY(launch_knn_norms(queries_dev, 0, nq, x->d, x->qnorm.as<float>(), s));
+    *qn = x->qnorm.as<float>();
+    return VQHIP_OK;
+}
+
+// queries_dev [nq][d] f32 on the device -> [nq][topk] results on the device, enqueued on s
+static int sqindex_search_enqueue(vqhip_sqindex *x, const float *queries_dev, uint32_t nq, uint32_t topk, uint32_t *idx_dev,
+                                  float *dist_dev, hipStream_t s) {
+    const uint32_t qb = knn_query_batch(x->n, nq);
+    VQ_TRY(x->dist.ensure((size_t)qb * x->n * 4));
+    VQ_TRY(x->state.ensure(knn_state_bytes(qb)));
+    VQ_TRY(x->cand.ensure(topk_cand_bytes(qb)));
+    const float *qn = nullptr;
+    VQ_TRY(sqindex_qnorms(x, queries_dev, nq, &qn, s));
+    return launch_sq_search(x->metric, x->codes.as<uint8_t>(), x->n, x->d, x->mn, x->step, x->rnorm.as<float>(), queries_dev, qn, nq,
+                            topk, x->dist.as<float>(), x->state.p, x->cand.as<unsigned long long>(), idx_dev, dist_dev, s);
+}
+
+extern "C" {
+
+int vqhip_sqindex_create(float min, float max, uint32_t levels, const uint8_t *codes, uint64_t n, uint32_t d, int metric,
+                         vqhip_sqindex **out) {
+    VQ_API_BEGIN
+    return sqindex_create(codes, hipMemcpyHostToDevice, false, min, max, levels, n, d, metric, out);
+    VQ_API_END
+}
+
+int vqhip_sqindex_create_device(float min, float max, uint32_t levels, const void *dev_codes, uint64_t n, uint32_t d, int metric,
+                                vqhip_sqindex **out) {
+    VQ_API_BEGIN
+    return sqindex_create(dev_codes, hipMemcpyDeviceToDevice, false, min, max, levels, n, d, metric, out);
+    VQ_API_END
+}
+
+int vqhip_sqindex_create_rows(float min, float max, uint32_t levels, const float *rows, uint64_t n, uint32_t d, int metric,
+                              vqhip_sqindex **out) {
+    VQ_API_BEGIN
+    return sqindex_create(rows, hipMemcpyHostToDevice, true, min, max, levels, n, d, metric, out);
+    VQ_API_END
+}
+
+int vqhip_sqindex_create_rows_device(float min, float max, uint32_t levels, const void *dev_rows, uint64_t n, uint32_t d,
+                                     int metric, vqhip_sqindex **out) {
+    VQ_API_BEGIN
+    return sqindex_create(dev_rows, hipMemcpyDeviceToDevice, true, min, max, levels, n, d, metric, out);
+    VQ_API_END
+}
+
+int vqhip_sqindex_destroy(vqhip_sqindex *x) {
+    delete x;
+    return VQHIP_OK;
+}
+
+int vqhip_sqindex_info(const vqhip_sqindex *x, uint64_t *n, uint32_t *d, int *metric, float *min, float *max, uint32_t *levels) {
+    if (!x) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (n) *n = x->n;
+    if (d) *d = x->d;
+    if (metric) *metric = x->metric;
+    if (min) *min = x->mn;
+    if (max) *max = x->mx;
+    if (levels) *levels = x->levels;
+    return VQHIP_OK;
+}
+
+int vqhip_sqindex_codes(vqhip_sqindex *x, uint8_t *codes) {
+    VQ_API_BEGIN
+    if (!x || !codes) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    VQ_TRY(require_gfx950());
+    Entry in(x->sync);
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    VQ_HIP(hipMemcpyAsync(codes, x->codes.p, (size_t)x->n * x->d, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipStreamSynchronize(s));
+    in.synced();
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_sqindex_search(vqhip_sqindex *x, const float *queries, uint32_t nq, uint32_t topk, uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    if (!x || !queries || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    VQ_TRY(check_topk(x->n, topk));
+    if (nq == 0) return VQHIP_OK;
+    VQ_TRY(require_gfx950());
+    Entry in(x->sync);
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    return host_search(in, s, x->q, x->idx, &x->out, queries, nq, x->d, topk, idx_out, dist_out, [&] {
+        return sqindex_search_enqueue(x, x->q.as<float>(), nq, topk, x->idx.as<uint32_t>(), x->out.as<float>(), s);
+    });
+    VQ_API_END
+}
+
+int vqhip_sqindex_search_device(vqhip_sqindex *x, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx,
+                                void *dev_dist) {
+    VQ_API_BEGIN
+    if (!x || !dev_queries || !dev_idx || !dev_dist) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    VQ_TRY(check_topk(x->n, topk));
+    if (nq == 0) return VQHIP_OK;
+    if (reinterpret_cast<uintptr_t>(dev_queries) & 3) return fail(VQHIP_ERR_INVALID_INPUT, "queries are not 4-byte aligned");
+    VQ_TRY(require_gfx950());
+    Entry in(x->sync);
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    return sqindex_search_enqueue(x, reinterpret_cast<const float *>(dev_queries), nq, topk, reinterpret_cast<uint32_t *>(dev_idx),
+                                  reinterpret_cast<float *>(dev_dist), s);
+    VQ_API_END
+}
+
+int vqhip_sqindex_rerank(vqhip_sqindex *x, const float *queries, uint32_t nq, const uint32_t *cand, uint32_t c, uint32_t topk,
+                         uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    if (!x || !queries || !cand || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (c == 0 || c > 4096) return fail(VQHIP_ERR_INVALID_INPUT, "candidates per query %u must be in [1, 4096]", c);
+    if (topk == 0 || topk > c) return fail(VQHIP_ERR_INVALID_INPUT, "topk %u must be in [1, candidates = %u]", topk, c);
+    if (nq == 0) return VQHIP_OK;
+    VQ_TRY(require_gfx950());
+    Entry in(x->sync);
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    VQ_TRY(x->q.ensure((size_t)nq * x->d * 4));
+    VQ_TRY(x->rr_cand.ensure((size_t)nq * c * 4));
+    VQ_TRY(x->idx.ensure((size_t)nq * topk * 4));
+    VQ_TRY(x->out.ensure((size_t)nq * topk * 4));
+    VQ_TRY(x->rr_err.ensure(4));
+    VQ_HIP(hipMemcpyAsync(x->q.p, queries, (size_t)nq * x->d * 4, hipMemcpyHostToDevice, s));
+    VQ_HIP(hipMemcpyAsync(x->rr_cand.p, cand, (size_t)nq * c * 4, hipMemcpyHostToDevice, s));
+    VQ_HIP(hipMemsetAsync(x->rr_err.p, 0, 4, s));
+    const float *qn = nullptr;
+    VQ_TRY(sqindex_qnorms(x, x->q.as<float>(), nq, &qn, s));
+    VQ_TRY(launch_sq_rerank(x->metric, x->codes.as<uint8_t>(), x->n, x->d, x->mn, x->step, x->rnorm.as<float>(), x->q.as<float>(), qn,
+                            nq, x->rr_cand.as<uint32_t>(), c, topk, x->idx.as<uint32_t>(), x->out.as<float>(),
+                            x->rr_err.as<uint32_t>(), s));
+    uint32_t err = 0;
+    VQ_HIP(hipMemcpyAsync(&err, x->rr_err.p, 4, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipMemcpyAsync(idx_out, x->idx.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipMemcpyAsync(dist_out, x->out.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipStreamSynchronize(s));
+    in.synced();
+    if (err) return fail(VQHIP_ERR_INVALID_INPUT, "a candidate row id is >= n = %llu", (unsigned long long)x->n);
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+}  // extern "C"
+
 // ------------------------------------------------------------------ binary index (k_binary.hip) ----
 struct vqhip_binary {
     HandleSync sync;

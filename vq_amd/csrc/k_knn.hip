@@ -15,6 +15,7 @@
 // Roofline: VALU.  Squared L2 / Euclidean cost 3 unfused operations per (query, row, dimension), L1 2 (sub, then an add
 // that takes |.| as a source modifier), cosine 2 (mul, add).
 #include "kernels.hpp"
+#include "knn_tile.hpp"
 #include "topk.hpp"
 
 #include <type_traits>
@@ -24,38 +25,10 @@
 namespace vqhip {
 namespace {
 
-constexpr uint32_t kKnnRQ = 8, kKnnRR = 4;                  // (query, row) pairs per lane
-constexpr uint32_t kKnnTQ = 16 * kKnnRQ, kKnnTR = 16 * kKnnRR; // tile: 16 query groups x 16 row groups = 256 lanes
-constexpr uint32_t kKnnKC = 32;                              // dimensions per LDS chunk
-constexpr uint32_t kKnnRerankMax = 4096;                     // candidates per query of a rerank
-
 template <typename RT>
 __device__ __forceinline__ float knn_widen(RT v) {
     if constexpr (std::is_same<RT, uint16_t>::value) return (float)__builtin_bit_cast(_Float16, v);  // exact
     else return v;
-}
-
-// one pair's running sum advanced by one element
-template <int METRIC>
-__device__ __forceinline__ float knn_step(float acc, float q, float r) {
-    if constexpr (METRIC == VQHIP_SQUARED_EUCLIDEAN || METRIC == VQHIP_EUCLIDEAN) {
-        const float diff = q - r;
-        const float sq = diff * diff;
-        return acc + sq;
-    } else if constexpr (METRIC == VQHIP_MANHATTAN) {
-        const float diff = q - r;
-        return acc + fabsf(diff);
-    } else {
-        const float p = q * r;
-        return acc + p;
-    }
-}
-
-template <int METRIC>
-__device__ __forceinline__ float knn_finish(float acc, float qn, float rn) {
-    if constexpr (METRIC == VQHIP_EUCLIDEAN) return sqrtf(acc);
-    else if constexpr (vq_is_cos(METRIC)) return vq_cosine_finish(METRIC, acc, qn, rn);
-    else return acc;
 }
 
 // sqrtf(sum_t x_t^2) per vector, sequential from -0.0f (the norm chains of exact_distance_rt)
@@ -189,40 +162,6 @@ __global__ __launch_bounds__(256) void k_knn_dist(const float *__restrict__ Q, u
     }
 }
 
-// monotone bin of a key: non-NaN keys (all within [lo, hi]) linearly over bins 0 .. kAdcBins-2, NaN in the last bin
-__device__ __forceinline__ uint32_t knn_bin(uint32_t key, uint32_t lo, uint32_t hi) {
-    if (key > hi) return kAdcBins - 1;
-    if (key <= lo) return 0;
-    return (uint32_t)(((uint64_t)(key - lo) * (kAdcBins - 1)) / ((uint64_t)(hi - lo) + 1));
-}
-
-__global__ __launch_bounds__(256) void k_knn_hist(const float *__restrict__ dist, uint64_t n, const uint32_t *__restrict__ kmin,
-                                                  const uint32_t *__restrict__ kmax, uint32_t *__restrict__ hist) {
-    __shared__ uint32_t h[kAdcBins];
-    const uint32_t q = blockIdx.y, lo = kmin[q], hi = kmax[q];
-    for (uint32_t e = threadIdx.x; e < kAdcBins; e += 256) h[e] = 0u;
-    __syncthreads();
-    const float *dq = dist + (size_t)q * n;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
-        atomicAdd(&h[knn_bin(adc_key(dq[i]), lo, hi)], 1u);
-    __syncthreads();
-    for (uint32_t e = threadIdx.x; e < kAdcBins; e += 256)
-        if (h[e]) atomicAdd(&hist[(size_t)q * kAdcBins + e], h[e]);
-}
-
-// the search as a source of the selection stage (topk.hpp): dense rows, k_knn_hist's key bins over [kmin[q], kmax[q]]
-struct KnnSource : TopkRows {
-    const uint32_t *kmin, *kmax;
-    uint32_t lo = 0, hi = 0;  // (device: of the opened query)
-    __device__ void open(uint32_t q) {
-        TopkRows::open(q);
-        lo = kmin[q];
-        hi = kmax[q];
-    }
-    __device__ uint32_t bin(float dval) const { return knn_bin(adc_key(dval), lo, hi); }
-    uint32_t blocks() const { return (uint32_t)std::min<uint64_t>((n + 255) / 256, 64); }
-};
-
 // rerank: one workgroup per query computes D for its c candidates (the row of each gathered from the index), sorts the
 // (key, row) pairs in LDS and writes the first topk.  An id >= n reads nothing: it sets *err and sorts last.
 template <int METRIC, typename RT>
@@ -255,11 +194,6 @@ __global__ __launch_bounds__(1024) void k_knn_rerank(const float *__restrict__ Q
     }
     adc_bitonic<1024>(buf, len);
     for (uint32_t e = tid; e < topk; e += 1024) adc_emit(buf[e], true, 0, idx_out + (size_t)q * topk + e, dist_out + (size_t)q * topk + e);
-}
-
-uint32_t knn_grid(uint64_t items, uint32_t per_cu) {
-    const uint64_t cap = (uint64_t)num_cus() * per_cu;
-    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, cap));
 }
 
 template <int METRIC, typename RT>

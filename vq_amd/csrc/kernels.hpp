@@ -299,6 +299,17 @@ int launch_knn_rerank(int metric, const void *X, int dtype, uint64_t n, uint32_t
                       const float *qnorm_dev, uint32_t nq, const uint32_t *cand_dev, uint32_t c, uint32_t topk,
                       uint32_t *idx_out_dev, float *dist_out_dev, uint32_t *err_dev, hipStream_t stream);
 
+// exact search and rerank over resident SQ codes (k_sqindex.hip): C [n][d] u8, v(c) = mn + (float)c * step decoded on
+// the fly, rnorm [n] the decoded rows' norms (cosine only).  Batches and workspaces as launch_knn_search / _rerank; the
+// query norms come from launch_knn_norms.
+int launch_sq_norms(const uint8_t *C, uint64_t n, uint32_t d, float mn, float step, float *out, hipStream_t stream);
+int launch_sq_search(int metric, const uint8_t *C, uint64_t n, uint32_t d, float mn, float step, const float *rnorm,
+                     const float *queries_dev, const float *qnorm_dev, uint32_t nq, uint32_t topk, float *dist_ws, void *state_ws,
+                     unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev, hipStream_t stream);
+int launch_sq_rerank(int metric, const uint8_t *C, uint64_t n, uint32_t d, float mn, float step, const float *rnorm,
+                     const float *queries_dev, const float *qnorm_dev, uint32_t nq, const uint32_t *cand_dev, uint32_t c,
+                     uint32_t topk, uint32_t *idx_out_dev, float *dist_out_dev, uint32_t *err_dev, hipStream_t stream);
+
 // prepared per-node data of the screened squared-L2 / Euclidean descent (k_tsvq_screen.hip)
 struct TsvqScreen {
     const float *w = nullptr;     // [n_int][d]  c_left - c_right of every two-child node; cosine: [n_int][2][d] unit vectors of the children

@@ -139,18 +139,20 @@ class FlatIndex:
 
 def adc_then_rerank(adc_search, n: int, dim: int, queries: np.ndarray, topk: int, rerank, candidates):
     """the standard PQ pipeline: `adc_search(queries, c)` for a short list of c candidates per query (default 4 topk,
-    at most 1024 -- ADC's own limit -- and n), then the exact rerank of that list through the FlatIndex `rerank` over
-    the same n rows.  The flat index's metric is its own (cosine allowed)."""
+    at most 1024 -- ADC's own limit -- and n), then the exact rerank of that list through `rerank`, a FlatIndex or a
+    ScalarIndex over the same n rows.  The rerank index's metric is its own (cosine allowed)."""
     c = rerank_candidates(n, dim, topk, rerank, candidates)
     idx, _ = adc_search(queries, c)
     return rerank.rerank(queries, idx, topk)
 
 
 def rerank_candidates(n: int, dim: int, topk: int, rerank, candidates) -> int:
-    """the checks of a short list reranked through the FlatIndex `rerank` over the same n rows of dim: the list's length
-    (default 4 topk, at most 1024 and n)"""
-    if not isinstance(rerank, FlatIndex):
-        raise InvalidParameter("rerank", f"expected a FlatIndex, got {type(rerank).__name__}")
+    """the checks of a short list reranked through `rerank`, a FlatIndex or a ScalarIndex over the same n rows of dim:
+    the list's length (default 4 topk, at most 1024 and n)"""
+    from .scalar_index import ScalarIndex
+
+    if not isinstance(rerank, (FlatIndex, ScalarIndex)):
+        raise InvalidParameter("rerank", f"expected a FlatIndex or a ScalarIndex, got {type(rerank).__name__}")
     if len(rerank) != n:
         raise DimensionMismatch(n, len(rerank))
     if rerank.dim != dim:

@@ -272,7 +272,7 @@ class IVFPQIndex:
 
     def search(self, queries, topk: int = 10, nprobe: int = 8, *, rerank=None, candidates: int | None = None):
         """(nq, dim) float32 queries -> (indices uint32 (nq, topk), distances float32 (nq, topk)), nearest first; slots
-        past the probed rows hold 0xFFFFFFFF / +inf.  rerank: a FlatIndex over the same rows -- the IVF search then
+        past the probed rows hold 0xFFFFFFFF / +inf.  rerank: a FlatIndex or a ScalarIndex over the same rows -- the IVF search then
         returns `candidates` hits per query (default 4 topk, at most 1024 and n) and the exact rerank of the real ones"""
         q = self._queries(queries)
         p = self._nprobe(nprobe)

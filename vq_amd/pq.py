@@ -279,8 +279,8 @@ class ProductQuantizer:
         Returns (indices uint32 (nq, topk), distances float32 (nq, topk)); ties by lower row.
         Tables of m * k <= 38400 entries (one query's table in 150 KiB of LDS); larger ones raise FfiError
         (VQHIP_ERR_UNSUPPORTED).
-        rerank: a FlatIndex over the same n rows -- ADC then finds `candidates` rows per query (default 4 topk, at most
-        1024) and the result is their exact top-k under the flat index's metric (FlatIndex.rerank)."""
+        rerank: a FlatIndex or a ScalarIndex over the same n rows -- ADC then finds `candidates` rows per query (default
+        4 topk, at most 1024) and the result is their exact top-k under that index's metric (its `rerank`)."""
         if rerank is not None:
             from .flat import adc_then_rerank
 

@@ -134,7 +134,7 @@ class PQIndex:
 
     def search(self, queries, topk: int = 10, *, rerank=None, candidates: int | None = None):
         """top-k stored rows per query by asymmetric distance (device path; see ProductQuantizer.search, also for
-        `rerank` / `candidates`: exact rerank of an ADC short list through a FlatIndex over the same rows).
+        `rerank` / `candidates`: exact rerank of an ADC short list through a FlatIndex or a ScalarIndex over the same rows).
         Tables of m * k <= 38400 entries (one query's table in 150 KiB of LDS); larger ones raise FfiError
         (VQHIP_ERR_UNSUPPORTED).  Answers for the current codes, codebooks and distance (see the class)."""
         from . import _lib
