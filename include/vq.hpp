@@ -984,6 +984,83 @@ class IVFPQIndex {
     bool residual_ = false;
 };
 
+// Inverted-file index over the rows themselves (include/vqhip.h, vqhip_ivfflat_*): coarse centroids [nlist][dim], rows added
+// as (list id, row) in f32 or as the f16 bits quantize returns.  search computes the exact distance (FlatIndex's, any
+// metric) to the rows of the nprobe lists nearest to a query and gives (row id, distance) pairs [nq][topk], nearest
+// first; slots past the probed rows hold (0xFFFFFFFF, +inf); with nprobe == nlist it is FlatIndex's search.  The
+// constructor, add and list_sizes need no device; the arguments are checked before the device is touched.
+class IVFFlatIndex {
+   public:
+    enum class Rows { F32 = 0, F16 = 1 };
+    IVFFlatIndex(const float *coarse, std::size_t nlist, std::size_t dim, Distance distance = Distance(), Rows rows = Rows::F32) {
+        if (nlist == 0 || nlist > 65536) throw VqError::InvalidParameter("nlist", "must be between 1 and 65536");
+        if (dim == 0 || dim > 0xFFFFFFFFu) throw VqError::InvalidParameter("dim", "must be between 1 and 2^32 - 1");
+        vqhip_ivfflat *ix = nullptr;
+        detail::check(vqhip_ivfflat_create(coarse, (std::uint32_t)nlist, (std::uint32_t)dim, (int)rows, (int)distance.kind(), &ix));
+        ix_.reset(ix);
+        nlist_ = nlist;
+        dim_ = dim;
+        rows_ = rows;
+        distance_ = distance;
+    }
+    std::size_t size() const { return n_; }
+    std::size_t nlist() const { return nlist_; }
+    std::size_t dim() const { return dim_; }
+    Rows rows() const { return rows_; }
+    const char *distance_metric() const { return distance_.name(); }
+
+    // rows appended in order: list_ids [n] < nlist, rows [n][dim] in the index's row type; returns the first new row id
+    std::size_t add(const std::uint32_t *list_ids, const void *rows, std::size_t n) {
+        if (n >= (std::size_t(1) << 32) - n_) throw VqError::InvalidParameter("rows", "an index holds at most 2^32 - 1 rows");
+        for (std::size_t i = 0; i < n; ++i)
+            if (list_ids[i] >= nlist_) throw VqError::InvalidParameter("list_ids", "a list id is outside [0, nlist)");
+        const std::size_t first = n_;
+        if (n) detail::check(vqhip_ivfflat_add(ix_.get(), list_ids, rows, n));
+        n_ += n;
+        return first;
+    }
+    std::vector<std::uint64_t> list_sizes() const {
+        std::vector<std::uint64_t> s(nlist_);
+        detail::check(vqhip_ivfflat_list_sizes(ix_.get(), s.data()));
+        return s;
+    }
+
+    struct Result {
+        std::vector<std::uint32_t> idx;  // [nq][topk]
+        std::vector<float> dist;         // [nq][topk]
+    };
+    // queries [nq][dim] -> the lists each query scans [nq][nprobe], nearest first
+    std::vector<std::uint32_t> probe(const float *queries, std::size_t nq, std::size_t nprobe) const {
+        check_probe(nprobe, nq);
+        std::vector<std::uint32_t> out(nq * nprobe);
+        if (nq) detail::check(vqhip_ivfflat_probe(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, out.data()));
+        return out;
+    }
+    Result search(const float *queries, std::size_t nq, std::size_t topk, std::size_t nprobe) const {
+        check_probe(nprobe, nq);
+        if (topk == 0 || topk > 1024 || topk > n_) throw VqError::InvalidParameter("topk", "must be between 1 and min(n, 1024)");
+        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
+        if (nq)
+            detail::check(vqhip_ivfflat_search(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, (std::uint32_t)topk,
+                                               r.idx.data(), r.dist.data()));
+        return r;
+    }
+
+   private:
+    struct Del {
+        void operator()(vqhip_ivfflat *p) const { (void)vqhip_ivfflat_destroy(p); }
+    };
+    void check_probe(std::size_t nprobe, std::size_t nq) const {
+        if (nprobe == 0 || nprobe > 1024 || nprobe > nlist_)
+            throw VqError::InvalidParameter("nprobe", "must be between 1 and min(nlist, 1024)");
+        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
+    }
+    std::unique_ptr<vqhip_ivfflat, Del> ix_;
+    std::size_t n_ = 0, nlist_ = 0, dim_ = 0;
+    Rows rows_ = Rows::F32;
+    Distance distance_;
+};
+
 // analogue of vq::get_simd_backend (src/lib.rs): names the device backend
 inline std::string get_simd_backend() { return vqhip_backend(); }
 

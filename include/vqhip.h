@@ -613,6 +613,45 @@ int vqhip_ivfpq_create_ex(const float *coarse, uint32_t nlist, const float *code
                           uint32_t sub_dim, int metric, uint32_t flags, vqhip_ivfpq **out);
 int vqhip_ivfpq_flags(const vqhip_ivfpq *ix, uint32_t *flags);
 
+/* ---- inverted-file flat index: exact distances over the probed lists (k_ivfflat.hip) ---------
+ * No reference counterpart.  An index holds coarse centroids C [nlist][dim] f32 (1 <= nlist <= 65536), a metric (any of
+ * the five: nothing is summed over subspaces, so the cosines are allowed) and a row dtype: 0 (f32) or 1 (the f16 bits
+ * vqhip_quantize returns, widened exactly to f32 as the flat index widens them).  add appends rows: row i (ids in add
+ * order, n < 2^32 in all) gets a list id list[i] < nlist, checked on the host before anything is stored, and row_i [dim].
+ * Several adds equal one add of the concatenation.
+ *   P(q)    = the nprobe lists vqhip_flat_search over C (same metric) returns, ordered by (key, list id).
+ *             1 <= nprobe <= min(nlist, 1024).
+ *   S(q)    = { i : list[i] in P(q) }.
+ *   D(q, i) = the flat index's distance, Distance::compute(q, row_i) bit for bit: the pair summed sequentially over
+ *             t = 0..dim-1 from -0.0f, one rounding per operation, no fused multiply-add; Euclidean = sqrtf of the sum;
+ *             cosine through vq_cosine_finish, the row norms (sequential chains) computed once per add's upload and the
+ *             query norms once per call.
+ *   search  = the topk rows of S(q) by (key(D), row id) ascending, 1 <= topk <= min(n, 1024): NaN sorts last and is
+ *             reported as 0x7FC00000, ties go to the lower row, Euclidean orders by the reported root (as the flat index,
+ *             unlike ADC).  If |S(q)| < topk the remaining slots hold idx 0xFFFFFFFF and dist +inf, after every real row.
+ *             With nprobe == nlist the result equals vqhip_flat_search over the rows in add order: indices and distance
+ *             bits.  Run-to-run deterministic.
+ * queries [nq][dim] f32, lists_out [nq][nprobe], idx / dist [nq][topk]; nq = 0 is a no-op.  create, add, info and
+ * list_sizes (sizes [nlist]) are host-only, and every parameter is checked before any device work.  The device
+ * ownership rule is vqhip_ivfpq's: the index belongs to the device current at create (or, when create sees none, at the
+ * first probe or search); the first probe or search builds its device state there (the flat index over C, the rows in
+ * list order, uploaded through a bounded staging buffer), the first one after an add rebuilds it, and a call made with
+ * another device current returns VQHIP_ERR_INVALID_INPUT.  Host forms return when the results are there; search_device
+ * takes device queries and results and is asynchronous on the current stream.  Queries are served in batches of at most
+ * 1024 whose distances stay under 1 GB (one query's when that alone is more).  One lock per handle.  info: any output
+ * pointer may be NULL. */
+typedef struct vqhip_ivfflat vqhip_ivfflat;
+int vqhip_ivfflat_create(const float *coarse, uint32_t nlist, uint32_t dim, int dtype, int metric, vqhip_ivfflat **out);
+int vqhip_ivfflat_destroy(vqhip_ivfflat *ix);
+int vqhip_ivfflat_add(vqhip_ivfflat *ix, const uint32_t *list_ids, const void *rows, uint64_t n);
+int vqhip_ivfflat_info(const vqhip_ivfflat *ix, uint64_t *n, uint32_t *nlist, uint32_t *dim, int *dtype, int *metric);
+int vqhip_ivfflat_list_sizes(vqhip_ivfflat *ix, uint64_t *sizes);
+int vqhip_ivfflat_probe(vqhip_ivfflat *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t *lists_out);
+int vqhip_ivfflat_search(vqhip_ivfflat *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                         uint32_t *idx_out, float *dist_out);
+int vqhip_ivfflat_search_device(vqhip_ivfflat *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                                void *dev_idx, void *dev_dist);
+
 /* ---- TSVQ ----------------------------------------------------------------------------
  * build replaces TSVQNode::build (src/tsvq.rs:31-115); the tree comes back flattened in
  * pre-order (node 0 = root, left subtree, right subtree): centroids [cap][d], left/right

@@ -1,7 +1,7 @@
 """vq_amd -- MI355X (gfx950) back end for the k-means codebook-training and nearest-centroid
 encode path of CogitatorTech/vq, and of its elementwise scalar / binary quantizers, behind the
 reference's own Quantizer interface, exact k-NN search over resident rows (FlatIndex), an inverted-file
-index over PQ codes (IVFPQIndex), a Hamming index over packed BQ codes (BinaryIndex) and an exact index over
+index over PQ codes (IVFPQIndex) and one over the rows themselves (IVFFlatIndex), a Hamming index over packed BQ codes (BinaryIndex) and an exact index over
 resident SQ codes (ScalarIndex).
 
 The compute path is libvqhip.so (hand-written HIP for CDNA4, C ABI in include/vqhip.h).
@@ -15,13 +15,14 @@ from .binary import BinaryIndex
 from .bq import BinaryQuantizer
 from .flat import FlatIndex
 from .ivf import IVFPQIndex
+from .ivf_flat import IVFFlatIndex
 from .pq import ProductQuantizer, fit_codebooks
 from .scalar_index import ScalarIndex
 from .sq import ScalarQuantizer
 from .tsvq import TSVQ
 
 __all__ = [
-    "Distance", "BinaryIndex", "BinaryQuantizer", "FlatIndex", "IVFPQIndex", "ScalarIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
+    "Distance", "BinaryIndex", "BinaryQuantizer", "FlatIndex", "IVFFlatIndex", "IVFPQIndex", "ScalarIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
     "InvalidParameter", "InvalidData", "FfiError", "get_simd_backend",
 ]
 

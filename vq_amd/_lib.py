@@ -182,6 +182,14 @@ SIGNATURES = {
     "vqhip_ivfpq_probe": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p]),
     "vqhip_ivfpq_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _f32p]),
     "vqhip_ivfpq_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "vqhip_ivfflat_create": (C.c_int, [_f32p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, _vpp]),
+    "vqhip_ivfflat_destroy": (C.c_int, [_vp]),
+    "vqhip_ivfflat_add": (C.c_int, [_vp, _u32p, _vp, C.c_uint64]),
+    "vqhip_ivfflat_info": (C.c_int, [_vp, _u64p, _u32p, _u32p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vqhip_ivfflat_list_sizes": (C.c_int, [_vp, _u64p]),
+    "vqhip_ivfflat_probe": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p]),
+    "vqhip_ivfflat_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "vqhip_ivfflat_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
     "vqhip_ivfpq_create_ex": (C.c_int, [_f32p, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
                                         _vpp]),
     "vqhip_ivfpq_flags": (C.c_int, [_vp, _u32p]),
@@ -938,6 +946,56 @@ class IVFPQ(Handle):
     def search_device(self, dev_queries: int, nq: int, nprobe: int, topk: int, dev_idx: int, dev_dist: int):
         check(load().vqhip_ivfpq_search_device(self.raw, C.c_void_p(dev_queries), int(nq), int(nprobe), int(topk),
                                                C.c_void_p(dev_idx), C.c_void_p(dev_dist)))
+
+
+class IVFFlat(Handle):
+    """vqhip_ivfflat: inverted-file flat index -- coarse centroids, f32 or f16 rows in lists, exact distances over the
+    probed lists (k_ivfflat.hip).  Create, add, info and list_sizes are host-only; the device state is built by the first
+    probe or search."""
+
+    _destroy = "vqhip_ivfflat_destroy"
+
+    def __init__(self, coarse, metric: int, dtype=np.float32):
+        c = f32c(coarse)
+        self.row_dtype = np.dtype(dtype)
+        h = C.c_void_p()
+        check(load().vqhip_ivfflat_create(ptr(c, _f32p), c.shape[0], c.shape[1], 1 if self.row_dtype == np.float16 else 0,
+                                          int(metric), C.byref(h)))
+        super().__init__(h)
+        self.nlist, self.dim, self.metric = c.shape[0], c.shape[1], int(metric)
+
+    def add(self, list_ids, rows):
+        lid = np.ascontiguousarray(list_ids, dtype=np.uint32)
+        r = np.ascontiguousarray(rows, dtype=self.row_dtype)
+        check(load().vqhip_ivfflat_add(self.raw, ptr(lid, _u32p), r.ctypes.data_as(_vp), lid.shape[0]))
+
+    def info(self):
+        n, nlist, dim, dtype, metric = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_int(), C.c_int()
+        check(load().vqhip_ivfflat_info(self.raw, C.byref(n), C.byref(nlist), C.byref(dim), C.byref(dtype), C.byref(metric)))
+        return int(n.value), int(nlist.value), int(dim.value), int(dtype.value), int(metric.value)
+
+    def list_sizes(self) -> np.ndarray:
+        out = np.empty(self.nlist, np.uint64)
+        check(load().vqhip_ivfflat_list_sizes(self.raw, ptr(out, _u64p)))
+        return out
+
+    def probe(self, q: np.ndarray, nprobe: int) -> np.ndarray:
+        nq = q.shape[0]
+        out = np.empty((nq, nprobe), np.uint32)
+        check(load().vqhip_ivfflat_probe(self.raw, ptr(q, _f32p), nq, int(nprobe), ptr(out, _u32p)))
+        return out
+
+    def search(self, q: np.ndarray, nprobe: int, topk: int):
+        nq = q.shape[0]
+        idx = np.empty((nq, topk), np.uint32)
+        dist = np.empty((nq, topk), np.float32)
+        check(load().vqhip_ivfflat_search(self.raw, ptr(q, _f32p), nq, int(nprobe), int(topk), ptr(idx, _u32p),
+                                          ptr(dist, _f32p)))
+        return idx, dist
+
+    def search_device(self, dev_queries: int, nq: int, nprobe: int, topk: int, dev_idx: int, dev_dist: int):
+        check(load().vqhip_ivfflat_search_device(self.raw, C.c_void_p(dev_queries), int(nq), int(nprobe), int(topk),
+                                                 C.c_void_p(dev_idx), C.c_void_p(dev_dist)))
 
 
 def dequantize_f16(f16) -> np.ndarray:

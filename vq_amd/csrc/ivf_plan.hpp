@@ -1,0 +1,55 @@
+// ivf_plan.hpp -- the per-query plan the inverted-file searches share (k_ivf.hip over PQ codes, k_ivfflat.hip over rows):
+// S(q) as ONE sequence of positions, probe slot 0's list first; pref[q][slot] the first position of a slot, seg[q][slot]
+// the first row (in list order) of its list.  Every including file gets its own copy (an anonymous namespace).
+#pragma once
+#include "common.hpp"
+
+namespace vqhip {
+namespace {
+
+// pref[q][0..nprobe] and seg[q][0..nprobe) of the block's query q = blockIdx.x (1024 threads); returns slot t's length
+__device__ __forceinline__ uint32_t ivf_plan_prefix(const uint32_t *__restrict__ probe, uint32_t nprobe, uint32_t nlist,
+                                                    const uint32_t *__restrict__ off, uint32_t *__restrict__ pref,
+                                                    uint32_t *__restrict__ seg) {
+    __shared__ uint32_t s_len[1024];
+    const uint32_t q = blockIdx.x, t = threadIdx.x;
+    uint32_t len = 0;
+    if (t < nprobe) {
+        const uint32_t l = probe[(size_t)q * nprobe + t];  // (< nlist: the flat search returns real rows; an empty slot else)
+        const uint32_t o = l < nlist ? off[l] : 0u;
+        len = l < nlist ? off[l + 1] - o : 0u;
+        seg[(size_t)q * nprobe + t] = o;
+    }
+    s_len[t] = len;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {  // inclusive scan
+        const uint32_t v = t >= d ? s_len[t - d] : 0u;
+        __syncthreads();
+        s_len[t] += v;
+        __syncthreads();
+    }
+    uint32_t *pq = pref + (size_t)q * (nprobe + 1);
+    if (t < nprobe) pq[t + 1] = s_len[t];
+    if (t == 0) pq[0] = 0u;
+    return len;
+}
+
+// the probe slot of position pos: the last slot whose first position is <= pos (pq[0] = 0 <= pos < pq[nprobe])
+__device__ __forceinline__ uint32_t ivf_slot(const uint32_t *__restrict__ pq, uint32_t nprobe, uint32_t pos) {
+    uint32_t lo = 0, hi = nprobe;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (pq[mid] <= pos) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// the row (in list order) behind position pos of a query
+__device__ __forceinline__ uint32_t ivf_row(const uint32_t *__restrict__ pq, const uint32_t *__restrict__ sq, uint32_t nprobe,
+                                            uint32_t pos) {
+    const uint32_t slot = ivf_slot(pq, nprobe, pos);
+    return sq[slot] + (pos - pq[slot]);
+}
+
+}  // namespace
+}  // namespace vqhip

@@ -12,6 +12,7 @@
 // every candidate carries its exact unique key, so the result does not depend on the bins.
 #include "adc_plan.hpp"
 #include "common.hpp"
+#include "ivf_plan.hpp"
 #include "kernels.hpp"
 #include "topk.hpp"
 
@@ -19,33 +20,6 @@
 
 namespace vqhip {
 namespace {
-
-// pref[q][0..nprobe] and seg[q][0..nprobe) of the block's query q = blockIdx.x (1024 threads); returns slot t's length
-__device__ __forceinline__ uint32_t ivf_plan_prefix(const uint32_t *__restrict__ probe, uint32_t nprobe, uint32_t nlist,
-                                                    const uint32_t *__restrict__ off, uint32_t *__restrict__ pref,
-                                                    uint32_t *__restrict__ seg) {
-    __shared__ uint32_t s_len[1024];
-    const uint32_t q = blockIdx.x, t = threadIdx.x;
-    uint32_t len = 0;
-    if (t < nprobe) {
-        const uint32_t l = probe[(size_t)q * nprobe + t];  // (< nlist: the flat search returns real rows; an empty slot else)
-        const uint32_t o = l < nlist ? off[l] : 0u;
-        len = l < nlist ? off[l + 1] - o : 0u;
-        seg[(size_t)q * nprobe + t] = o;
-    }
-    s_len[t] = len;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {  // inclusive scan
-        const uint32_t v = t >= d ? s_len[t - d] : 0u;
-        __syncthreads();
-        s_len[t] += v;
-        __syncthreads();
-    }
-    uint32_t *pq = pref + (size_t)q * (nprobe + 1);
-    if (t < nprobe) pq[t + 1] = s_len[t];
-    if (t == 0) pq[0] = 0u;
-    return len;
-}
 
 // pref[q][0..nprobe]: the first position of each probe slot (pref[q][nprobe] = |S(q)|); seg[q][slot] = off[list];
 // bounds[q] = {sum_s min_j t_s, sum_s max_j t_s} in a fixed reduction order (the histogram's range: any monotone bin
@@ -83,23 +57,6 @@ __global__ __launch_bounds__(1024) void k_ivf_plan(const uint32_t *__restrict__ 
         bounds[2 * q + 0] = s_lo[0];
         bounds[2 * q + 1] = s_hi[0];
     }
-}
-
-// the probe slot of position pos: the last slot whose first position is <= pos (pq[0] = 0 <= pos < pq[nprobe])
-__device__ __forceinline__ uint32_t ivf_slot(const uint32_t *__restrict__ pq, uint32_t nprobe, uint32_t pos) {
-    uint32_t lo = 0, hi = nprobe;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (pq[mid] <= pos) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-// the row (in list order) behind position pos of a query
-__device__ __forceinline__ uint32_t ivf_row(const uint32_t *__restrict__ pq, const uint32_t *__restrict__ sq, uint32_t nprobe,
-                                            uint32_t pos) {
-    const uint32_t slot = ivf_slot(pq, nprobe, pos);
-    return sq[slot] + (pos - pq[slot]);
 }
 
 // work item (blockIdx.x, blockIdx.y = query): positions [x chunk, (x + 1) chunk) of S(q); items past |S(q)| leave at once.

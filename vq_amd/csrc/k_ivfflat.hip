@@ -1,0 +1,448 @@
+// Inverted-file search over the rows themselves (include/vqhip.h, vqhip_ivfflat_*).  The index keeps
+// its rows in list order: list l holds the rows ids[off[l] .. off[l + 1]) (ascending) as one contiguous run of X, and
+// their norms under the cosines.  Per query:
+//   P(q)    = the nprobe lists the flat search over the coarse centroids returns (launch_knn_search, k_knn.hip),
+//   S(q)    = the rows of those lists as ONE sequence of positions: probe slot 0's list, then slot 1's, ... (ivf_plan.hpp),
+//   D(q, i) = the flat index's distance (knn_tile.hpp: knn_step from -0.0 over ascending dimensions, knn_finish),
+//   result  = the topk rows of S(q) by (adc_key(D), row id) ascending; Euclidean ordered by the reported root; padding
+//             (|S(q)| < topk) idx 0xFFFFFFFF, dist +inf.
+// Schedule of one batch (launch_ivfflat_search):
+//   k_ivff_plan    each query's prefix over its probed lists' lengths; cnt[l] = the batch's queries that probe list l
+//   k_ivff_lists   prefix sums over the lists: lstart[l] (the list's run of the inverted table) and tstart[l] (its query
+//                  tiles; none for a list probed by fewer than kIvffTileMin queries)
+//   k_ivff_invert  the inverted probe table: inv[lstart[l] ..] = the (query, slot) pairs that probe l, in any order
+//   k_ivff_tile    work item = one list x one tile of 128 of its queries x a column of tiles of 64 of its rows: k_knn_dist's
+//                  8 x 4 register block over 32-dimension LDS chunks, the queries gathered through inv, every D written to
+//                  W[q][pref[q][slot] + r]; a list's rows are read once per query tile
+//   k_ivff_scan    the lists probed by fewer than kIvffTileMin queries: work item = one query x one chunk of its positions,
+//                  the query in LDS, one position per lane, the same per-pair operation order
+//   k_ivff_hist    the key-space histogram of W[q][0 .. |S(q)|) over the range the two kernels found (integer atomics)
+//   launch_topk_select over IvffSource: IvfSource's positions and ids, KnnSource's bins.
+// Which kernel computes a pair depends on the batch; both run one pair's operations in one order, so the bits do not.
+#include "common.hpp"
+#include "ivf_plan.hpp"
+#include "kernels.hpp"
+#include "knn_tile.hpp"
+#include "topk.hpp"
+
+#include <type_traits>
+
+#pragma clang fp contract(off)
+
+namespace vqhip {
+namespace {
+
+constexpr uint32_t kIvffTileMin = 16;  // queries of a batch probing a list from which the tile kernel takes it
+constexpr uint32_t kIvffQC = 1024;     // query dimensions k_ivff_scan holds in LDS at a time
+
+template <typename RT>
+__device__ __forceinline__ float ivff_widen(RT v) {
+    if constexpr (std::is_same<RT, uint16_t>::value) return (float)__builtin_bit_cast(_Float16, v);  // exact
+    else return v;
+}
+
+__device__ __forceinline__ bool ivff_real(uint32_t l, uint32_t nlist, const uint32_t *__restrict__ off) {
+    return l < nlist && off[l + 1] > off[l];
+}
+
+// block = query (1024 threads): pref / seg as k_ivf_plan; cnt[l] += 1 for every non-empty list the query probes
+__global__ __launch_bounds__(1024) void k_ivff_plan(const uint32_t *__restrict__ probe, uint32_t nprobe, uint32_t nlist,
+                                                    const uint32_t *__restrict__ off, uint32_t *__restrict__ pref,
+                                                    uint32_t *__restrict__ seg, uint32_t *__restrict__ cnt) {
+    const uint32_t len = ivf_plan_prefix(probe, nprobe, nlist, off, pref, seg);
+    if (threadIdx.x < nprobe && len > 0) atomicAdd(&cnt[probe[(size_t)blockIdx.x * nprobe + threadIdx.x]], 1u);
+}
+
+__device__ __forceinline__ uint32_t ivff_tiles(uint32_t c) { return c >= kIvffTileMin ? (c + kKnnTQ - 1) / kKnnTQ : 0u; }
+
+// one block of 1024 threads: exclusive prefix sums of cnt[l] and of the lists' query tiles; lstart / tstart [nlist + 1]
+__global__ __launch_bounds__(1024) void k_ivff_lists(const uint32_t *__restrict__ cnt, uint32_t nlist, uint32_t *__restrict__ lstart,
+                                                     uint32_t *__restrict__ tstart) {
+    __shared__ uint32_t s_c[1024], s_t[1024];
+    const uint32_t t = threadIdx.x, per = (nlist + 1023) / 1024;
+    const uint32_t a = min(nlist, t * per), b = min(nlist, a + per);
+    uint32_t c = 0, tl = 0;
+    for (uint32_t l = a; l < b; ++l) {
+        c += cnt[l];
+        tl += ivff_tiles(cnt[l]);
+    }
+    s_c[t] = c;
+    s_t[t] = tl;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {  // inclusive scan
+        const uint32_t vc = t >= d ? s_c[t - d] : 0u, vt = t >= d ? s_t[t - d] : 0u;
+        __syncthreads();
+        s_c[t] += vc;
+        s_t[t] += vt;
+        __syncthreads();
+    }
+    c = s_c[t] - c;
+    tl = s_t[t] - tl;
+    for (uint32_t l = a; l < b; ++l) {
+        lstart[l] = c;
+        tstart[l] = tl;
+        c += cnt[l];
+        tl += ivff_tiles(cnt[l]);
+    }
+    if (t == 1023) {
+        lstart[nlist] = s_c[1023];
+        tstart[nlist] = s_t[1023];
+    }
+}
+
+// block = query: inv[lstart[l] + (a slot of the list's run, taken in any order)] = q * nprobe + slot
+__global__ __launch_bounds__(1024) void k_ivff_invert(const uint32_t *__restrict__ probe, uint32_t nprobe, uint32_t nlist,
+                                                      const uint32_t *__restrict__ off, const uint32_t *__restrict__ lstart,
+                                                      uint32_t *__restrict__ fill, uint32_t *__restrict__ inv) {
+    const uint32_t q = blockIdx.x, t = threadIdx.x;
+    if (t >= nprobe) return;
+    const uint32_t l = probe[(size_t)q * nprobe + t];
+    if (!ivff_real(l, nlist, off)) return;
+    const uint32_t at = atomicAdd(&fill[l], 1u);
+    if (at < lstart[l + 1] - lstart[l]) inv[lstart[l] + at] = q * nprobe + t;  // (always: fill counts what cnt counted)
+}
+
+// block (x = query tile of the batch's tstart[nlist] tiles, y = column of row tiles): k_knn_dist over the rows of one list
+// and the up to 128 queries of one tile of its run of inv.  Blocks past the last tile leave at once.
+template <int METRIC, typename RT>
+__global__ __launch_bounds__(256) void k_ivff_tile(const float *__restrict__ Q, const RT *__restrict__ X, uint32_t d,
+                                                   const float *__restrict__ qnorm, const float *__restrict__ rnorm,
+                                                   const uint32_t *__restrict__ off, uint32_t nlist, const uint32_t *__restrict__ cnt,
+                                                   const uint32_t *__restrict__ lstart, const uint32_t *__restrict__ tstart,
+                                                   const uint32_t *__restrict__ inv, const uint32_t *__restrict__ pref,
+                                                   uint32_t nprobe, uint64_t wstride, float *__restrict__ W,
+                                                   uint32_t *__restrict__ kmin, uint32_t *__restrict__ kmax) {
+    constexpr uint32_t RQ = kKnnRQ, RR = kKnnRR, TQ = kKnnTQ, TR = kKnnTR, KC = kKnnKC;
+    __shared__ __attribute__((aligned(16))) float qs[KC][TQ + 4];
+    __shared__ __attribute__((aligned(16))) float rs[KC][TR + 4];
+    __shared__ uint32_t s_q[TQ], s_p[TQ];  // the tile's queries (0xFFFFFFFF: none) and the first position of the list in each
+    const uint32_t tile = blockIdx.x;
+    if (tile >= tstart[nlist]) return;  // (uniform)
+    uint32_t l = 0;
+    {  // the last list whose first tile is <= tile, and that has tiles (tstart is non-decreasing)
+        uint32_t lo = 0, hi = nlist;
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (tstart[mid] <= tile) lo = mid;
+            else hi = mid;
+        }
+        l = lo;
+    }
+    const uint32_t tid = threadIdx.x, rg = tid & 15u, qg = tid >> 4;
+    const uint32_t e0 = (tile - tstart[l]) * TQ, en = min(TQ, cnt[l] - e0);
+    const uint32_t row0 = off[l], nrows = off[l + 1] - row0;
+    if (tid < TQ) {
+        uint32_t q = 0xFFFFFFFFu, p = 0;
+        if (tid < en) {
+            const uint32_t e = inv[lstart[l] + e0 + tid];
+            q = e / nprobe;
+            p = pref[(size_t)q * (nprobe + 1) + (e - q * nprobe)];
+        }
+        s_q[tid] = q;
+        s_p[tid] = p;
+    }
+    __syncthreads();
+    float qn[RQ];
+    uint32_t lo[RQ], hi[RQ], qi[RQ];
+#pragma unroll
+    for (uint32_t a = 0; a < RQ; ++a) {
+        qi[a] = s_q[qg * RQ + a];
+        qn[a] = (vq_is_cos(METRIC) && qi[a] != 0xFFFFFFFFu) ? qnorm[qi[a]] : 1.0f;
+        lo[a] = 0xFFFFFFFFu;
+        hi[a] = 0u;
+    }
+    const uint32_t nrt = (nrows + TR - 1) / TR;
+    for (uint32_t rt = blockIdx.y; rt < nrt; rt += gridDim.y) {
+        const uint32_t r0 = rt * TR;  // (within the list)
+        float acc[RQ][RR];
+#pragma unroll
+        for (uint32_t a = 0; a < RQ; ++a)
+#pragma unroll
+            for (uint32_t b = 0; b < RR; ++b) acc[a][b] = -0.0f;
+        for (uint32_t t0 = 0; t0 < d; t0 += KC) {
+            const uint32_t tc = min(KC, d - t0);
+            __syncthreads();  // the previous chunk's readers are done
+#pragma unroll
+            for (uint32_t e = 0; e < TQ * KC / 256; ++e) {
+                const uint32_t idx = tid + 256 * e, r = idx / KC, c = idx % KC;
+                const uint32_t q = s_q[r];
+                qs[c][r] = (q != 0xFFFFFFFFu && c < tc) ? Q[(size_t)q * d + t0 + c] : 0.0f;
+            }
+#pragma unroll
+            for (uint32_t e = 0; e < TR * KC / 256; ++e) {
+                const uint32_t idx = tid + 256 * e, r = idx / KC, c = idx % KC;
+                rs[c][r] = (r0 + r < nrows && c < tc) ? ivff_widen(X[((uint64_t)row0 + r0 + r) * d + t0 + c]) : 0.0f;
+            }
+            __syncthreads();
+            auto advance = [&](uint32_t t) {
+                const float4 qa = *reinterpret_cast<const float4 *>(&qs[t][qg * RQ]);
+                const float4 qb = *reinterpret_cast<const float4 *>(&qs[t][qg * RQ + 4]);
+                const float4 rv = *reinterpret_cast<const float4 *>(&rs[t][rg * RR]);
+                const float qv[RQ] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
+                const float rr[RR] = {rv.x, rv.y, rv.z, rv.w};
+#pragma unroll
+                for (uint32_t a = 0; a < RQ; ++a)
+#pragma unroll
+                    for (uint32_t b = 0; b < RR; ++b) acc[a][b] = knn_step<METRIC>(acc[a][b], qv[a], rr[b]);
+            };
+            if (tc == KC) {  // (unrolled by 8, as k_knn_dist: fully, the LDS reads cost a wave per SIMD)
+#pragma unroll 8
+                for (uint32_t t = 0; t < KC; ++t) advance(t);
+            } else {
+                for (uint32_t t = 0; t < tc; ++t) advance(t);
+            }
+        }
+        const uint32_t rb = r0 + rg * RR;
+        float rn[RR];
+#pragma unroll
+        for (uint32_t b = 0; b < RR; ++b) rn[b] = (vq_is_cos(METRIC) && rb + b < nrows) ? rnorm[(uint64_t)row0 + rb + b] : 1.0f;
+#pragma unroll
+        for (uint32_t a = 0; a < RQ; ++a) {
+            if (qi[a] == 0xFFFFFFFFu) continue;
+            float *wq = W + (size_t)qi[a] * wstride;
+            const uint64_t p0 = (uint64_t)s_p[qg * RQ + a] + rb;
+#pragma unroll
+            for (uint32_t b = 0; b < RR; ++b) {
+                if (rb + b >= nrows || p0 + b >= wstride) continue;
+                const float dv = knn_finish<METRIC>(acc[a][b], qn[a], rn[b]);
+                const uint32_t key = adc_key(dv);
+                if (key != 0xFFFFFFFFu) {
+                    lo[a] = min(lo[a], key);
+                    hi[a] = max(hi[a], key);
+                }
+                wq[p0 + b] = dv;  // (a run starts at any position: no 16-byte stores)
+            }
+        }
+    }
+    // the 16 lanes of a query group (lane bits 0-3) hold all of the workgroup's rows for its 8 queries
+#pragma unroll
+    for (uint32_t a = 0; a < RQ; ++a) {
+#pragma unroll
+        for (uint32_t o = 1; o < 16; o <<= 1) {
+            lo[a] = min(lo[a], (uint32_t)__shfl_xor((int)lo[a], (int)o));
+            hi[a] = max(hi[a], (uint32_t)__shfl_xor((int)hi[a], (int)o));
+        }
+        if (rg == 0 && qi[a] != 0xFFFFFFFFu && lo[a] <= hi[a]) {
+            atomicMin(&kmin[qi[a]], lo[a]);
+            atomicMax(&kmax[qi[a]], hi[a]);
+        }
+    }
+}
+
+// four consecutive elements of a row from element e (e and d multiples of 4: an 8- or 16-byte load)
+template <typename RT>
+__device__ __forceinline__ void ivff_load4(const RT *__restrict__ x, uint64_t e, float (&v)[4]) {
+    if constexpr (std::is_same<RT, uint16_t>::value) {
+        const uint2 w = *reinterpret_cast<const uint2 *>(x + e);
+        v[0] = ivff_widen<uint16_t>((uint16_t)(w.x & 0xFFFFu)), v[1] = ivff_widen<uint16_t>((uint16_t)(w.x >> 16));
+        v[2] = ivff_widen<uint16_t>((uint16_t)(w.y & 0xFFFFu)), v[3] = ivff_widen<uint16_t>((uint16_t)(w.y >> 16));
+    } else {
+        const float4 w = *reinterpret_cast<const float4 *>(x + e);
+        v[0] = w.x, v[1] = w.y, v[2] = w.z, v[3] = w.w;
+    }
+}
+
+// block (x = chunk of positions, y = query): the positions of the chunk whose list fewer than kIvffTileMin queries probe,
+// one per lane and pass; the query's dimensions in LDS, kIvffQC at a time.  Items past |S(q)| leave at once.
+template <int METRIC, typename RT>
+__global__ __launch_bounds__(256) void k_ivff_scan(const float *__restrict__ Q, const RT *__restrict__ X, uint32_t d,
+                                                   const float *__restrict__ qnorm, const float *__restrict__ rnorm,
+                                                   const uint32_t *__restrict__ probe, const uint32_t *__restrict__ cnt,
+                                                   const uint32_t *__restrict__ pref, const uint32_t *__restrict__ seg,
+                                                   uint32_t nprobe, uint32_t chunk, uint64_t wstride, float *__restrict__ W,
+                                                   uint32_t *__restrict__ kmin, uint32_t *__restrict__ kmax) {
+    __shared__ __attribute__((aligned(16))) float s_x[kIvffQC];
+    const uint32_t q = blockIdx.y, tid = threadIdx.x;
+    const uint32_t *pq = pref + (size_t)q * (nprobe + 1);
+    const uint32_t *sq = seg + (size_t)q * nprobe;
+    const uint32_t *lq = probe + (size_t)q * nprobe;
+    const uint32_t total = (uint32_t)min((uint64_t)pq[nprobe], wstride);
+    const uint64_t p0 = (uint64_t)blockIdx.x * chunk;
+    if (p0 >= total) return;  // (uniform)
+    const uint32_t p1 = (uint32_t)min((uint64_t)total, p0 + chunk);
+    const float *x = Q + (size_t)q * d;
+    const float qn = vq_is_cos(METRIC) ? qnorm[q] : 1.0f;
+    const bool once = d <= kIvffQC;  // the whole query stays in LDS
+    const bool vec = (d & 3u) == 0;
+    if (once) {
+        for (uint32_t t = tid; t < d; t += 256) s_x[t] = x[t];
+        __syncthreads();
+    }
+    float *wq = W + (size_t)q * wstride;
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+    for (uint32_t base = (uint32_t)p0; base < p1; base += 256) {
+        const uint32_t pos = base + tid;
+        bool mine = false;
+        uint64_t row = 0;
+        if (pos < p1) {
+            const uint32_t slot = ivf_slot(pq, nprobe, pos);
+            mine = cnt[lq[slot]] < kIvffTileMin;  // (a position exists: its list is real)
+            row = (uint64_t)sq[slot] + (pos - pq[slot]);
+        }
+        if (!__syncthreads_or(mine)) continue;  // (uniform)
+        const RT *r = X + row * d;
+        float acc = -0.0f;
+        for (uint32_t t0 = 0; t0 < d; t0 += kIvffQC) {
+            const uint32_t tc = min(kIvffQC, d - t0);
+            if (!once) {
+                __syncthreads();
+                for (uint32_t t = tid; t < tc; t += 256) s_x[t] = x[t0 + t];
+                __syncthreads();
+            }
+            if (!mine) continue;
+            if (vec) {
+                for (uint32_t t = 0; t < tc; t += 4) {
+                    float v[4];
+                    ivff_load4<RT>(r, (uint64_t)t0 + t, v);
+                    const float4 xv = *reinterpret_cast<const float4 *>(&s_x[t]);
+                    acc = knn_step<METRIC>(acc, xv.x, v[0]);
+                    acc = knn_step<METRIC>(acc, xv.y, v[1]);
+                    acc = knn_step<METRIC>(acc, xv.z, v[2]);
+                    acc = knn_step<METRIC>(acc, xv.w, v[3]);
+                }
+            } else {
+                for (uint32_t t = 0; t < tc; ++t) acc = knn_step<METRIC>(acc, s_x[t], ivff_widen(r[(uint64_t)t0 + t]));
+            }
+        }
+        if (mine) {
+            const float dv = knn_finish<METRIC>(acc, qn, vq_is_cos(METRIC) ? rnorm[row] : 1.0f);
+            const uint32_t key = adc_key(dv);
+            if (key != 0xFFFFFFFFu) {
+                lo = min(lo, key);
+                hi = max(hi, key);
+            }
+            wq[pos] = dv;
+        }
+    }
+#pragma unroll
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        lo = min(lo, (uint32_t)__shfl_xor((int)lo, (int)o));
+        hi = max(hi, (uint32_t)__shfl_xor((int)hi, (int)o));
+    }
+    if ((tid & 63u) == 0 && lo <= hi) {
+        atomicMin(&kmin[q], lo);
+        atomicMax(&kmax[q], hi);
+    }
+}
+
+// k_knn_hist over the positions of S(q): hist[q][bin] += 1 (integer atomics: the counts do not depend on their order)
+__global__ __launch_bounds__(256) void k_ivff_hist(const float *__restrict__ W, uint64_t wstride, const uint32_t *__restrict__ pref,
+                                                   uint32_t nprobe, const uint32_t *__restrict__ kmin,
+                                                   const uint32_t *__restrict__ kmax, uint32_t *__restrict__ hist) {
+    __shared__ uint32_t h[kAdcBins];
+    const uint32_t q = blockIdx.y, lo = kmin[q], hi = kmax[q];
+    const uint32_t total = (uint32_t)min((uint64_t)pref[(size_t)q * (nprobe + 1) + nprobe], wstride);
+    if ((uint64_t)blockIdx.x * 256 >= total) return;  // (uniform)
+    for (uint32_t e = threadIdx.x; e < kAdcBins; e += 256) h[e] = 0u;
+    __syncthreads();
+    const float *wq = W + (size_t)q * wstride;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256)
+        atomicAdd(&h[knn_bin(adc_key(wq[i]), lo, hi)], 1u);
+    __syncthreads();
+    for (uint32_t e = threadIdx.x; e < kAdcBins; e += 256)
+        if (h[e]) atomicAdd(&hist[(size_t)q * kAdcBins + e], h[e]);
+}
+
+// the two kernels' output as a source of the selection stage (topk.hpp): IvfSource's positions and row ids (k_ivf.hip),
+// KnnSource's key bins over [kmin[q], kmax[q]] (knn_tile.hpp)
+struct IvffSource {
+    using Pos = uint32_t;
+    const float *W;
+    uint64_t wstride;
+    const uint32_t *pref, *seg, *ids;
+    uint32_t nprobe;
+    const uint32_t *kmin, *kmax;
+    uint32_t total = 0, lo = 0, hi = 0;  // (device: of the opened query)
+    __device__ void open(uint32_t q) {
+        W += (size_t)q * wstride;
+        pref += (size_t)q * (nprobe + 1);
+        seg += (size_t)q * nprobe;
+        total = (uint32_t)min((uint64_t)pref[nprobe], wstride);
+        lo = kmin[q];
+        hi = kmax[q];
+    }
+    __device__ Pos count() const { return total; }
+    __device__ float at(Pos pos) const { return W[pos]; }
+    __device__ uint32_t id(Pos pos) const { return ids[ivf_row(pref, seg, nprobe, pos)]; }
+    __device__ uint32_t bin(float dval) const { return knn_bin(adc_key(dval), lo, hi); }
+    uint32_t blocks() const { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((wstride + 255) / 256, 1), 64); }
+};
+
+template <class F>
+int ivff_dispatch(int metric, int dtype, F &&f) {
+    auto by_type = [&](auto mtag) -> int {
+        if (dtype == 1) return f(mtag, (const uint16_t *)nullptr);
+        return f(mtag, (const float *)nullptr);
+    };
+    switch (metric) {
+        case VQHIP_SQUARED_EUCLIDEAN: return by_type(std::integral_constant<int, VQHIP_SQUARED_EUCLIDEAN>());
+        case VQHIP_EUCLIDEAN: return by_type(std::integral_constant<int, VQHIP_EUCLIDEAN>());
+        case VQHIP_MANHATTAN: return by_type(std::integral_constant<int, VQHIP_MANHATTAN>());
+        case VQHIP_COSINE: return by_type(std::integral_constant<int, VQHIP_COSINE>());
+        case VQHIP_COSINE_UNCLAMPED: return by_type(std::integral_constant<int, VQHIP_COSINE_UNCLAMPED>());
+    }
+    return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
+}
+
+}  // namespace
+
+// cnt | fill | lstart | tstart of a batch: [nlist] + [nlist] + [nlist + 1] + [nlist + 1] words (cnt and fill zeroed per batch)
+size_t ivfflat_lists_bytes(uint32_t nlist) { return ((size_t)4 * nlist + 2) * 4; }
+
+// One batch of nb <= 1024 queries (queries [nb][d] f32, qnorm [nb] under the cosines) whose probe lists
+// (probe [nb][nprobe], launch_knn_search) are on the device.  X / rnorm / ids / off: the index in list order.  W
+// [nb][wstride] with wstride >= every |S(q)|; pref [nb][nprobe + 1], seg and inv [nb][nprobe], lists >=
+// ivfflat_lists_bytes(nlist), state >= knn_state_bytes(nb), cand >= topk_cand_bytes(nb); max_list: the rows of the
+// largest list.  Results [nb][topk] on the device.
+int launch_ivfflat_search(int metric, const void *X, int dtype, uint32_t d, const float *rnorm, const uint32_t *ids,
+                          const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
+                          const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
+                          float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state,
+                          unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream) {
+    if (nb == 0) return VQHIP_OK;
+    if (nb > 1024) return fail(VQHIP_ERR_INVALID_INPUT, "a batch holds at most 1024 queries");
+    if (nprobe == 0 || nprobe > 1024) return fail(VQHIP_ERR_INVALID_INPUT, "nprobe must be in [1, 1024]");
+    if (topk == 0 || topk > 1024) return fail(VQHIP_ERR_INVALID_INPUT, "topk must be in [1, 1024]");
+    uint32_t *cnt = lists, *fill = cnt + nlist, *lstart = fill + nlist, *tstart = lstart + nlist + 1;
+    uint32_t *kmin = reinterpret_cast<uint32_t *>(state), *kmax = kmin + nb;
+    const TopkState st = topk_state(kmax + nb, nb);
+    VQ_HIP(hipMemsetAsync(cnt, 0, (size_t)2 * nlist * 4, stream));
+    VQ_HIP(hipMemsetAsync(kmin, 0xFF, (size_t)nb * 4, stream));
+    VQ_HIP(hipMemsetAsync(kmax, 0, knn_state_bytes(nb) - (size_t)nb * 4, stream));
+    hipLaunchKernelGGL(k_ivff_plan, dim3(nb), dim3(1024), 0, stream, probe, nprobe, nlist, off, pref, seg, cnt);
+    VQ_LAUNCH_CHECK("k_ivff_plan");
+    hipLaunchKernelGGL(k_ivff_lists, dim3(1), dim3(1024), 0, stream, cnt, nlist, lstart, tstart);
+    VQ_LAUNCH_CHECK("k_ivff_lists");
+    hipLaunchKernelGGL(k_ivff_invert, dim3(nb), dim3(1024), 0, stream, probe, nprobe, nlist, off, lstart, fill, inv);
+    VQ_LAUNCH_CHECK("k_ivff_invert");
+    // the tiles the batch can have: a list with tiles has at least kIvffTileMin pairs and one partial tile
+    const uint64_t pairs = (uint64_t)nb * nprobe;
+    const uint64_t tiles_max = std::min<uint64_t>(nlist, pairs / kIvffTileMin) + pairs / kKnnTQ;
+    const uint64_t items = (wstride + chunk - 1) / chunk;
+    VQ_TRY(ivff_dispatch(metric, dtype, [&](auto mtag, auto rtag) -> int {
+        using RT = std::remove_const_t<std::remove_pointer_t<decltype(rtag)>>;
+        constexpr int M = decltype(mtag)::value;
+        if (tiles_max > 0) {
+            // about eight workgroups per CU in all: columns of row tiles per query tile, at most the largest list's
+            const uint64_t nrt = std::max<uint64_t>(1, (max_list + kKnnTR - 1) / kKnnTR);
+            const uint64_t cols = std::min<uint64_t>({nrt, 64, ((uint64_t)num_cus() * 8 + tiles_max - 1) / tiles_max});
+            hipLaunchKernelGGL((k_ivff_tile<M, RT>), dim3((uint32_t)tiles_max, (uint32_t)cols), dim3(256), 0, stream, queries,
+                               reinterpret_cast<const RT *>(X), d, qnorm, rnorm, off, nlist, cnt, lstart, tstart, inv, pref, nprobe,
+                               wstride, W, kmin, kmax);
+            VQ_LAUNCH_CHECK("k_ivff_tile");
+        }
+        if (items > 0) {
+            hipLaunchKernelGGL((k_ivff_scan<M, RT>), dim3((uint32_t)items, nb), dim3(256), 0, stream, queries,
+                               reinterpret_cast<const RT *>(X), d, qnorm, rnorm, probe, cnt, pref, seg, nprobe, chunk, wstride, W,
+                               kmin, kmax);
+            VQ_LAUNCH_CHECK("k_ivff_scan");
+        }
+        return VQHIP_OK;
+    }));
+    const IvffSource src{W, wstride, pref, seg, ids, nprobe, kmin, kmax};
+    hipLaunchKernelGGL(k_ivff_hist, dim3(src.blocks(), nb), dim3(256), 0, stream, W, wstride, pref, nprobe, kmin, kmax, st.hist);
+    VQ_LAUNCH_CHECK("k_ivff_hist");
+    return launch_topk_select(src, nb, topk, 0, st, cand, idx_out, dist_out, stream);
+}
+
+}  // namespace vqhip

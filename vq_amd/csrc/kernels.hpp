@@ -287,6 +287,16 @@ int launch_ivf_rsearch(const uint8_t *codes, const uint32_t *ids, const uint32_t
                        const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
                        float *tabs, float *mm, float *W, uint32_t *pref, uint32_t *seg, float *bounds, void *state,
                        unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream);
+// inverted-file search over list-ordered rows (k_ivfflat.hip): one batch of nb <= 1024 queries whose probe lists are on the
+// device; X [n][d] f32 (dtype 0) or f16 bits (dtype 1) and rnorm [n] in list order, W [nb][wstride] (wstride >= every
+// query's |S(q)|), pref [nb][nprobe + 1], seg and inv [nb][nprobe], lists >= ivfflat_lists_bytes(nlist), state >=
+// knn_state_bytes(nb), cand >= topk_cand_bytes(nb); max_list the rows of the largest list
+size_t ivfflat_lists_bytes(uint32_t nlist);
+int launch_ivfflat_search(int metric, const void *X, int dtype, uint32_t d, const float *rnorm, const uint32_t *ids,
+                          const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
+                          const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
+                          float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state,
+                          unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream);
 // exact k-NN search over resident rows and exact rerank of candidate lists (k_knn.hip); X [n][d] f32 (dtype 0) or f16
 // bits (dtype 1), rnorm [n] the rows' norms (cosine only, else unused)
 int launch_knn_norms(const void *X, int dtype, uint64_t n, uint32_t d, float *out, hipStream_t stream);

@@ -48,7 +48,7 @@ __device__ __forceinline__ uint32_t knn_bin(uint32_t key, uint32_t lo, uint32_t 
     return (uint32_t)(((uint64_t)(key - lo) * (kAdcBins - 1)) / ((uint64_t)(hi - lo) + 1));
 }
 
-__global__ __launch_bounds__(256) void k_knn_hist(const float *__restrict__ dist, uint64_t n, const uint32_t *__restrict__ kmin,
+__attribute__((unused)) __global__ __launch_bounds__(256) void k_knn_hist(const float *__restrict__ dist, uint64_t n, const uint32_t *__restrict__ kmin,
                                                   const uint32_t *__restrict__ kmax, uint32_t *__restrict__ hist) {
     __shared__ uint32_t h[kAdcBins];
     const uint32_t q = blockIdx.y, lo = kmin[q], hi = kmax[q];

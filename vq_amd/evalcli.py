@@ -5,6 +5,7 @@
     python -m vq_amd.evalcli tsvq [--seed 66 --dim 384 --max-depth 5]
     python -m vq_amd.evalcli sq   [--seed 66 --dim 384 --levels 256]
     python -m vq_amd.evalcli bq   [--seed 66 --dim 384]
+    python -m vq_amd.evalcli ivfflat [--seed 66 --dim 384 --nlist 256 --nprobe 1 8 32 --max-iters 10]
 
 For every sample count of `NUM_SAMPLES` it prints the reference's three lines -- training time,
 quantization time (host matrix in, f16 matrix out: what `quantize` per vector produces there)
@@ -16,6 +17,10 @@ sampled query over all n rows (FlatIndex) on the device.  `--json` emits one `Be
 `sq` / `bq` follow src/bin/eval_sq.rs / eval_bq.rs: ScalarQuantizer(0, 1, levels) and
 BinaryQuantizer(0.5, 0, 1), "training" being the constructor; the reference's two lines plus the
 mean squared error of dequantize(quantize(x)).
+
+`ivfflat` has no reference counterpart: it trains an IVFFlatIndex (nlist coarse centroids, Euclidean), adds every row
+and reports, per nprobe, recall@k of its search against the exact search (FlatIndex) of the same <= 1000 strided
+queries over all n rows, with the mean share of the rows a query scans.
 
 Data: i.i.d. Uniform[0,1) like common.rs:43-53, from the library's counter-based generator
 (the reference's StdRng stream is not reproducible outside Rust).
@@ -152,6 +157,47 @@ def _report_elementwise(title, make_quantizer, args):
         print(f"  Reconstruction error: {err:.6f}")
 
 
+def _report_ivfflat(args):
+    """recall@k of IVFFlatIndex.search against FlatIndex.search over the same rows, per nprobe"""
+    from . import _lib
+    from .flat import FlatIndex
+    from .ivf_flat import IVFFlatIndex
+
+    title = "IVF-Flat Index Evaluation"
+    print(title)
+    print("=" * len(title))
+    for n in args.samples:
+        X = _lib.synth_uniform_host(n, args.dim, args.seed, 0)
+        nlist = min(args.nlist, n)
+        k = min(args.recall_k, n)
+        t0 = time.perf_counter()
+        ix = IVFFlatIndex.train(X, nlist, args.max_iters, seed=args.seed)
+        train_ms = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        ix.add(X)
+        add_ms = (time.perf_counter() - t0) * 1e3
+        Q = X[::max(n // min(n, 1000), 1)]
+        exact = FlatIndex(X).search(Q, k)[0]
+        sizes = ix.list_sizes().astype(np.int64)
+        if not args.json:
+            print(f"\nSamples: {n}")
+            print(f"  Training time: {train_ms:.0f} ms")
+            print(f"  Add time: {add_ms:.0f} ms")
+        for nprobe in args.nprobe:
+            p = min(nprobe, nlist)
+            t0 = time.perf_counter()
+            got = ix.search(Q, topk=k, nprobe=p)[0]
+            search_ms = (time.perf_counter() - t0) * 1e3
+            recall = float(np.mean([len(np.intersect1d(got[j], exact[j])) / k for j in range(len(Q))]))
+            scanned = float(sizes[ix.probe(Q, p)].sum() / (len(Q) * n))
+            if args.json:
+                print(json.dumps({"n_samples": n, "n_dims": args.dim, "nlist": nlist, "nprobe": p, "training_time_ms": train_ms,
+                                  "add_time_ms": add_ms, "search_time_ms": search_ms, "recall": recall, "scanned_share": scanned}))
+            else:
+                print(f"  nprobe {p}: Recall@{k} {recall:.4f}, {100 * scanned:.1f}% of the rows scanned, {search_ms:.0f} ms")
+        ix.close()
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="vq_amd.evalcli")
     sub = ap.add_subparsers(dest="alg", required=True)
@@ -178,7 +224,19 @@ def main(argv=None) -> int:
             p.add_argument("--max-iters", type=int, default=MAX_ITERS)
         else:
             p.add_argument("--max-depth", type=int, default=5)
+    p = sub.add_parser("ivfflat")
+    p.add_argument("--seed", type=int, default=SEED)
+    p.add_argument("--dim", type=int, default=DIM)
+    p.add_argument("--samples", type=int, nargs="+", default=NUM_SAMPLES)
+    p.add_argument("--nlist", type=int, default=256)
+    p.add_argument("--nprobe", type=int, nargs="+", default=[1, 8, 32])
+    p.add_argument("--max-iters", type=int, default=MAX_ITERS)
+    p.add_argument("--recall-k", type=int, default=10)
+    p.add_argument("--json", action="store_true")
     args = ap.parse_args(argv)
+    if args.alg == "ivfflat":
+        _report_ivfflat(args)
+        return 0
     from . import TSVQ, BinaryQuantizer, Distance, ProductQuantizer, ScalarQuantizer
 
     if args.alg == "sq":
