@@ -662,6 +662,37 @@ inline std::vector<std::vector<float>> lbg_quantize(const std::vector<std::vecto
     return out;
 }
 
+// The result of a range search (include/vqhip.h, vqhip_*_range_search), CSR: the hits of query q are idx / dist
+// [lims[q], lims[q + 1]) -- the rows with D(q, row) <= radius[q], in ascending row id -- and lims[0] = 0.
+struct RangeResult {
+    std::vector<std::uint64_t> lims;  // [nq + 1]
+    std::vector<std::uint32_t> idx;   // [total]
+    std::vector<float> dist;          // [total]
+};
+
+namespace detail {
+struct RangeDel {
+    void operator()(vqhip_range *p) const { (void)vqhip_range_destroy(p); }
+};
+// the argument checks of a range search, before the library is called
+inline void check_range_args(const float *radii, std::size_t nq, std::uint64_t max_results) {
+    if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
+    if (max_results == 0) throw VqError::InvalidParameter("max_results", "must be at least 1");
+    for (std::size_t q = 0; q < nq; ++q)
+        if (radii[q] != radii[q]) throw VqError::InvalidParameter("radius", "is NaN for query " + std::to_string(q));
+}
+// a finished device result to host vectors
+inline RangeResult read_range(vqhip_range *raw) {
+    std::unique_ptr<vqhip_range, RangeDel> r(raw);
+    std::uint32_t nq = 0;
+    std::uint64_t total = 0;
+    check(vqhip_range_info(r.get(), &nq, &total));
+    RangeResult out{std::vector<std::uint64_t>((std::size_t)nq + 1), std::vector<std::uint32_t>(total), std::vector<float>(total)};
+    check(vqhip_range_read(r.get(), out.lims.data(), out.idx.data(), out.dist.data()));
+    return out;
+}
+}  // namespace detail
+
 // Exact k-NN search over rows kept on the device (include/vqhip.h, vqhip_flat_*): rows [n][dim] f32 or f16, uploaded once
 // by the constructor; search / rerank give (row index, distance) pairs [nq][topk], nearest first, NaN last, ties to the
 // lower row.  The arguments are checked before the device is touched.
@@ -693,6 +724,20 @@ class FlatIndex {
     Result search(const std::vector<float> &queries, std::size_t topk) const {
         if (queries.size() % dim_) throw VqError::DimensionMismatch(dim_, queries.size() % dim_);
         return search(queries.data(), queries.size() / dim_, topk);
+    }
+    // every row within radii[q] of query q (radii [nq], none NaN), at most max_results hits in all (more: FfiError)
+    RangeResult range_search(const float *queries, std::size_t nq, const float *radii, std::uint64_t max_results = std::uint64_t(1) << 28) const {
+        detail::check_range_args(radii, nq, max_results);
+        if (nq == 0) return RangeResult{std::vector<std::uint64_t>(1, 0), {}, {}};
+        vqhip_range *r = nullptr;
+        detail::check(vqhip_flat_range_search(flat_.get(), queries, (std::uint32_t)nq, radii, max_results, &r));
+        return detail::read_range(r);
+    }
+    RangeResult range_search(const std::vector<float> &queries, const std::vector<float> &radii,
+                             std::uint64_t max_results = std::uint64_t(1) << 28) const {
+        if (queries.size() % dim_) throw VqError::DimensionMismatch(dim_, queries.size() % dim_);
+        if (radii.size() != queries.size() / dim_) throw VqError::DimensionMismatch(queries.size() / dim_, radii.size());
+        return range_search(queries.data(), queries.size() / dim_, radii.data(), max_results);
     }
     // per query the topk nearest of its c candidate row ids cand [nq][c] (distinct within a query, each < n)
     Result rerank(const float *queries, std::size_t nq, const std::uint32_t *cand, std::size_t c, std::size_t topk) const {
@@ -847,6 +892,20 @@ class ScalarIndex {
     Result search(const std::vector<float> &queries, std::size_t topk) const {
         if (queries.size() % dim_) throw VqError::DimensionMismatch(dim_, queries.size() % dim_);
         return search(queries.data(), queries.size() / dim_, topk);
+    }
+    // every row within radii[q] of query q (radii [nq], none NaN), at most max_results hits in all (more: FfiError)
+    RangeResult range_search(const float *queries, std::size_t nq, const float *radii, std::uint64_t max_results = std::uint64_t(1) << 28) const {
+        detail::check_range_args(radii, nq, max_results);
+        if (nq == 0) return RangeResult{std::vector<std::uint64_t>(1, 0), {}, {}};
+        vqhip_range *r = nullptr;
+        detail::check(vqhip_sqindex_range_search(ix_.get(), queries, (std::uint32_t)nq, radii, max_results, &r));
+        return detail::read_range(r);
+    }
+    RangeResult range_search(const std::vector<float> &queries, const std::vector<float> &radii,
+                             std::uint64_t max_results = std::uint64_t(1) << 28) const {
+        if (queries.size() % dim_) throw VqError::DimensionMismatch(dim_, queries.size() % dim_);
+        if (radii.size() != queries.size() / dim_) throw VqError::DimensionMismatch(queries.size() / dim_, radii.size());
+        return range_search(queries.data(), queries.size() / dim_, radii.data(), max_results);
     }
     // per query the topk nearest of its c candidate row ids cand [nq][c] (distinct within a query, each < n)
     Result rerank(const float *queries, std::size_t nq, const std::uint32_t *cand, std::size_t c, std::size_t topk) const {

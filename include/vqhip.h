@@ -559,6 +559,41 @@ int vqhip_sqindex_search_device(vqhip_sqindex *x, const void *dev_queries, uint3
 int vqhip_sqindex_rerank(vqhip_sqindex *x, const float *queries, uint32_t nq, const uint32_t *cand, uint32_t c,
                          uint32_t topk, uint32_t *idx_out, float *dist_out);
 
+/* ---- exact range search over the flat and the scalar index (range.hpp) ------------------------
+ * No reference counterpart.  Per query q with radius r_q (one f32 per query, radii [nq] in HOST memory in both forms):
+ *   hit     row i is a hit iff D(q, i) <= r_q as an f32 comparison, D being the index's distance exactly as search
+ *           reports it (the root for Euclidean, the finished value for cosine).  A NaN distance never hits; r_q = +inf
+ *           returns every row whose distance is not NaN; a negative radius returns nothing except where D can be
+ *           negative (VQHIP_COSINE_UNCLAMPED); -0.0 <= 0.0 holds (a float comparison, not one of keys).  A NaN radius
+ *           is VQHIP_ERR_INVALID_INPUT.
+ *   result  CSR, owned by a vqhip_range on the device: lims [nq + 1] u64 with lims[0] = 0, idx [total] u32 row ids and
+ *           dist [total] f32 (the bits of D), total = lims[nq]; the hits of query q are idx / dist [lims[q], lims[q + 1]).
+ *   order   within a query ascending row id: deterministic, no sort.  The same call on the same data returns identical
+ *           arrays every time.  nq = 0 gives lims = [0].
+ *   cap     max_results >= 1 (0: VQHIP_ERR_INVALID_INPUT) caps total.  A call that would exceed it returns
+ *           VQHIP_ERR_UNSUPPORTED -- the message gives the count reached and the cap -- and *out stays NULL; the index
+ *           is usable afterwards.
+ * Checked in this order, before any device work: out, queries / radii (NULL with nq > 0), max_results, the radii, and
+ * only then the index handle -- so every one of these checks runs without a device or an index.  dev_queries must be
+ * 4-byte aligned.  Both forms return when the result is complete (the total decides the result's size, so the host
+ * waits once per internal batch of queries -- the batches of search -- and once at the end); they take the index's lock
+ * like search.  A vqhip_range is immutable: info / read / device may be called from any thread; read copies to host
+ * arrays of nq + 1, total and total elements (any of the three may be NULL); device gives the device addresses, valid
+ * until destroy. */
+typedef struct vqhip_range vqhip_range;
+int vqhip_flat_range_search(vqhip_flat *f, const float *queries, uint32_t nq, const float *radii, uint64_t max_results,
+                            vqhip_range **out);
+int vqhip_flat_range_search_device(vqhip_flat *f, const void *dev_queries, uint32_t nq, const float *radii,
+                                   uint64_t max_results, vqhip_range **out);
+int vqhip_sqindex_range_search(vqhip_sqindex *x, const float *queries, uint32_t nq, const float *radii,
+                               uint64_t max_results, vqhip_range **out);
+int vqhip_sqindex_range_search_device(vqhip_sqindex *x, const void *dev_queries, uint32_t nq, const float *radii,
+                                      uint64_t max_results, vqhip_range **out);
+int vqhip_range_info(const vqhip_range *r, uint32_t *nq, uint64_t *total);
+int vqhip_range_read(const vqhip_range *r, uint64_t *lims, uint32_t *idx, float *dist);
+int vqhip_range_device(const vqhip_range *r, const void **dev_lims, const void **dev_idx, const void **dev_dist);
+int vqhip_range_destroy(vqhip_range *r);
+
 /* ---- inverted-file PQ index: search only the probed lists (k_ivf.hip) -----------------------
  * No reference counterpart.  An index holds coarse centroids C [nlist][dim] f32 (1 <= nlist <= 65536), PQ codebooks
  * cb [m][k][sub_dim] (dim = m * sub_dim) and a metric: squared Euclidean, Euclidean or Manhattan (cosine is refused with

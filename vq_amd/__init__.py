@@ -13,6 +13,7 @@ from .errors import (DimensionMismatch, EmptyInput, FfiError, InvalidData, Inval
                      VqError)
 from .binary import BinaryIndex
 from .bq import BinaryQuantizer
+from ._lib import RangeResult
 from .flat import FlatIndex
 from .ivf import IVFPQIndex
 from .ivf_flat import IVFFlatIndex
@@ -22,7 +23,7 @@ from .sq import ScalarQuantizer
 from .tsvq import TSVQ
 
 __all__ = [
-    "Distance", "BinaryIndex", "BinaryQuantizer", "FlatIndex", "IVFFlatIndex", "IVFPQIndex", "ScalarIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
+    "Distance", "BinaryIndex", "BinaryQuantizer", "FlatIndex", "IVFFlatIndex", "IVFPQIndex", "RangeResult", "ScalarIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
     "InvalidParameter", "InvalidData", "FfiError", "get_simd_backend",
 ]
 

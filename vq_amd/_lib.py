@@ -174,6 +174,14 @@ SIGNATURES = {
     "vqhip_sqindex_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
     "vqhip_sqindex_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
     "vqhip_sqindex_rerank": (C.c_int, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "vqhip_flat_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, _f32p, C.c_uint64, _vpp]),
+    "vqhip_flat_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, _f32p, C.c_uint64, _vpp]),
+    "vqhip_sqindex_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, _f32p, C.c_uint64, _vpp]),
+    "vqhip_sqindex_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, _f32p, C.c_uint64, _vpp]),
+    "vqhip_range_info": (C.c_int, [_vp, _u32p, _u64p]),
+    "vqhip_range_read": (C.c_int, [_vp, _u64p, _u32p, _f32p]),
+    "vqhip_range_device": (C.c_int, [_vp, _vpp, _vpp, _vpp]),
+    "vqhip_range_destroy": (C.c_int, [_vp]),
     "vqhip_ivfpq_create": (C.c_int, [_f32p, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _vpp]),
     "vqhip_ivfpq_destroy": (C.c_int, [_vp]),
     "vqhip_ivfpq_add": (C.c_int, [_vp, _u32p, _vp, C.c_uint64]),
@@ -767,6 +775,49 @@ class PQEncoder(Handle):
         check(load().vqhip_pq_decode_device(self.raw, C.c_void_p(dev_codes), int(n), C.c_void_p(dev_out)))
 
 
+class RangeResult(Handle):
+    """vqhip_range: the result of a range search, on the device.  CSR: the hits of query q are
+    ``idx[lims[q]:lims[q + 1]]`` (row ids, ascending) and ``dist[...]`` (their distances)."""
+
+    _destroy = "vqhip_range_destroy"
+
+    def __init__(self, raw: C.c_void_p):
+        super().__init__(raw)
+        nq, total = C.c_uint32(), C.c_uint64()
+        check(load().vqhip_range_info(self.raw, C.byref(nq), C.byref(total)))
+        self.nq, self.total = int(nq.value), int(total.value)
+        self._lims = None
+
+    @property
+    def lims(self) -> np.ndarray:
+        """uint64 (nq + 1,), on the host"""
+        if self._lims is None:
+            lims = np.empty(self.nq + 1, np.uint64)
+            check(load().vqhip_range_read(self.raw, ptr(lims, _u64p), None, None))
+            self._lims = lims
+        return self._lims
+
+    def device_pointers(self) -> tuple[int, int, int]:
+        """device addresses of lims (uint64 [nq + 1]), idx (uint32 [total]) and dist (float32 [total]); valid while this
+        object lives"""
+        lims, idx, dist = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(load().vqhip_range_device(self.raw, C.byref(lims), C.byref(idx), C.byref(dist)))
+        return int(lims.value or 0), int(idx.value or 0), int(dist.value or 0)
+
+    def read(self):
+        """(lims uint64 (nq + 1,), idx uint32 (total,), dist float32 (total,)) on the host"""
+        idx = np.empty(self.total, np.uint32)
+        dist = np.empty(self.total, np.float32)
+        check(load().vqhip_range_read(self.raw, None, ptr(idx, _u32p), ptr(dist, _f32p)))
+        return self.lims.copy(), idx, dist
+
+
+def _range_call(fn, raw, queries, nq: int, radii: np.ndarray, max_results: int) -> RangeResult:
+    h = C.c_void_p()
+    check(fn(raw, queries, int(nq), ptr(radii, _f32p), int(max_results), C.byref(h)))
+    return RangeResult(h)
+
+
 class Flat(Handle):
     """vqhip_flat: rows resident on the device, exact k-NN search and exact rerank (k_knn.hip)"""
 
@@ -796,6 +847,12 @@ class Flat(Handle):
     def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int):
         check(load().vqhip_flat_search_device(self.raw, C.c_void_p(dev_queries), int(nq), int(topk), C.c_void_p(dev_idx),
                                               C.c_void_p(dev_dist)))
+
+    def range_search(self, q: np.ndarray, radii: np.ndarray, max_results: int) -> RangeResult:
+        return _range_call(load().vqhip_flat_range_search, self.raw, ptr(q, _f32p), q.shape[0], radii, max_results)
+
+    def range_search_device(self, dev_queries: int, nq: int, radii: np.ndarray, max_results: int) -> RangeResult:
+        return _range_call(load().vqhip_flat_range_search_device, self.raw, C.c_void_p(dev_queries), nq, radii, max_results)
 
     def rerank(self, q: np.ndarray, cand: np.ndarray, topk: int):
         nq, c = cand.shape
@@ -880,6 +937,12 @@ class SQIndex(Handle):
     def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int):
         check(load().vqhip_sqindex_search_device(self.raw, C.c_void_p(dev_queries), int(nq), int(topk), C.c_void_p(dev_idx),
                                                  C.c_void_p(dev_dist)))
+
+    def range_search(self, q: np.ndarray, radii: np.ndarray, max_results: int) -> RangeResult:
+        return _range_call(load().vqhip_sqindex_range_search, self.raw, ptr(q, _f32p), q.shape[0], radii, max_results)
+
+    def range_search_device(self, dev_queries: int, nq: int, radii: np.ndarray, max_results: int) -> RangeResult:
+        return _range_call(load().vqhip_sqindex_range_search_device, self.raw, C.c_void_p(dev_queries), nq, radii, max_results)
 
     def rerank(self, q: np.ndarray, cand: np.ndarray, topk: int):
         nq, c = cand.shape

@@ -2708,6 +2708,7 @@ struct vqhip_flat {
     DevBuf rows, rnorm;                            // the index: [n][d] f32 or f16 bits, |row| for cosine
     DevBuf q, qnorm, dist, state, cand, idx, out;  // per-call workspaces
     DevBuf rr_cand, rr_err;                        // rerank: candidate ids, the out-of-range flag
+    DevBuf radii, range_ws;                        // range search: the radii, the stage's counts and offsets
 };
 
 static int flat_check(uint64_t n, uint32_t d, int dtype, int metric) {
@@ -2894,6 +2895,7 @@ struct vqhip_sqindex {
     DevBuf codes, rnorm;                           // the index: [n][d] u8, |v(row)| for cosine
     DevBuf q, qnorm, dist, state, cand, idx, out;  // per-call workspaces
     DevBuf rr_cand, rr_err;                        // rerank: candidate ids, the out-of-range flag
+    DevBuf radii, range_ws;                        // range search: the radii, the stage's counts and offsets
 };
 
 // src: u8 codes [n][d] (rows == false) or f32 rows [n][d] to encode (rows == true), in host (kind = H2D) or device memory
@@ -3090,6 +3092,142 @@ int vqhip_sqindex_rerank(vqhip_sqindex *x, const float *queries, uint32_t nq, co
     if (err) return fail(VQHIP_ERR_INVALID_INPUT, "a candidate row id is >= n = %llu", (unsigned long long)x->n);
     return VQHIP_OK;
     VQ_API_END
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ range search (range.hpp) ----
+struct vqhip_range {
+    RangeOut r;
+};
+
+// What a range call checks without a device or an index: the pointers it reads and writes, max_results, the radii.
+static int range_args(const void *queries, const float *radii, uint32_t nq, uint64_t max_results, vqhip_range **out) {
+    if (!out) return fail(VQHIP_ERR_NULL_PTR, "out is NULL");
+    *out = nullptr;
+    if (nq && (!queries || !radii)) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (max_results == 0) return fail(VQHIP_ERR_INVALID_INPUT, "max_results must be at least 1");
+    for (uint32_t q = 0; q < nq; ++q)
+        if (radii[q] != radii[q]) return fail(VQHIP_ERR_INVALID_INPUT, "the radius of query %u is NaN", q);
+    return VQHIP_OK;
+}
+
+// One range call on a flat or a scalar index h: the queries (host: through h->q) and the radii go up, `run` queues the
+// index's driver, which leaves *out complete.  The index is looked at after range_args, so those checks need none.
+template <class H, class F>
+static int range_search(H *h, const void *queries, bool host, uint32_t nq, const float *radii, uint64_t max_results,
+                        vqhip_range **out, F &&run) {
+    VQ_TRY(range_args(queries, radii, nq, max_results, out));
+    if (!h) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (!host && (reinterpret_cast<uintptr_t>(queries) & 3)) return fail(VQHIP_ERR_INVALID_INPUT, "queries are not 4-byte aligned");
+    VQ_TRY(require_gfx950());
+    Entry in(h->sync);
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    std::unique_ptr<vqhip_range> r(new vqhip_range());
+    const float *qdev = reinterpret_cast<const float *>(queries);
+    if (host && nq) {
+        VQ_TRY(h->q.ensure((size_t)nq * h->d * 4));
+        VQ_HIP(hipMemcpyAsync(h->q.p, queries, (size_t)nq * h->d * 4, hipMemcpyHostToDevice, s));
+        qdev = h->q.template as<float>();
+    }
+    VQ_TRY(h->radii.ensure((size_t)nq * 4));
+    if (nq) VQ_HIP(hipMemcpyAsync(h->radii.p, radii, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+    VQ_TRY(h->dist.ensure((size_t)knn_query_batch(h->n, nq) * h->n * 4));
+    VQ_TRY(h->state.ensure(knn_state_bytes(knn_query_batch(h->n, nq))));
+    VQ_TRY(h->range_ws.ensure(range_ws_bytes(h->n, nq)));
+    VQ_TRY(run(qdev, &r->r, s));  // (every exit of the driver has waited for s)
+    in.synced();
+    *out = r.release();
+    return VQHIP_OK;
+}
+
+static int flat_range(vqhip_flat *f, const void *queries, bool host, uint32_t nq, const float *radii, uint64_t max_results,
+                      vqhip_range **out) {
+    return range_search(f, queries, host, nq, radii, max_results, out, [&](const float *qdev, RangeOut *r, hipStream_t s) -> int {
+        const float *qn = nullptr;
+        if (vq_is_cos(f->metric) && nq) {
+            VQ_TRY(f->qnorm.ensure((size_t)nq * 4));
+            VQ_TRY(launch_knn_norms(qdev, 0, nq, f->d, f->qnorm.as<float>(), s));
+            qn = f->qnorm.as<float>();
+        }
+        return launch_knn_range(f->metric, f->rows.p, f->dtype, f->n, f->d, f->rnorm.as<float>(), qdev, qn, nq, f->radii.as<float>(),
+                                max_results, f->dist.as<float>(), f->state.p, f->range_ws.p, r, s);
+    });
+}
+
+static int sqindex_range(vqhip_sqindex *x, const void *queries, bool host, uint32_t nq, const float *radii, uint64_t max_results,
+                         vqhip_range **out) {
+    return range_search(x, queries, host, nq, radii, max_results, out, [&](const float *qdev, RangeOut *r, hipStream_t s) -> int {
+        const float *qn = nullptr;
+        if (nq) VQ_TRY(sqindex_qnorms(x, qdev, nq, &qn, s));
+        return launch_sq_range(x->metric, x->codes.as<uint8_t>(), x->n, x->d, x->mn, x->step, x->rnorm.as<float>(), qdev, qn, nq,
+                               x->radii.as<float>(), max_results, x->dist.as<float>(), x->state.p, x->range_ws.p, r, s);
+    });
+}
+
+extern "C" {
+
+int vqhip_flat_range_search(vqhip_flat *f, const float *queries, uint32_t nq, const float *radii, uint64_t max_results,
+                            vqhip_range **out) {
+    VQ_API_BEGIN
+    return flat_range(f, queries, true, nq, radii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_flat_range_search_device(vqhip_flat *f, const void *dev_queries, uint32_t nq, const float *radii, uint64_t max_results,
+                                   vqhip_range **out) {
+    VQ_API_BEGIN
+    return flat_range(f, dev_queries, false, nq, radii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_sqindex_range_search(vqhip_sqindex *x, const float *queries, uint32_t nq, const float *radii, uint64_t max_results,
+                               vqhip_range **out) {
+    VQ_API_BEGIN
+    return sqindex_range(x, queries, true, nq, radii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_sqindex_range_search_device(vqhip_sqindex *x, const void *dev_queries, uint32_t nq, const float *radii,
+                                      uint64_t max_results, vqhip_range **out) {
+    VQ_API_BEGIN
+    return sqindex_range(x, dev_queries, false, nq, radii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_range_info(const vqhip_range *r, uint32_t *nq, uint64_t *total) {
+    if (!r) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (nq) *nq = r->r.nq;
+    if (total) *total = r->r.total;
+    return VQHIP_OK;
+}
+
+int vqhip_range_read(const vqhip_range *r, uint64_t *lims, uint32_t *idx, float *dist) {
+    VQ_API_BEGIN
+    if (!r) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    VQ_TRY(require_gfx950());
+    hipStream_t s;
+    VQ_TRY(current_stream(&s));
+    if (lims) VQ_HIP(hipMemcpyAsync(lims, r->r.lims.p, ((size_t)r->r.nq + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (idx && r->r.total) VQ_HIP(hipMemcpyAsync(idx, r->r.idx.p, (size_t)r->r.total * 4, hipMemcpyDeviceToHost, s));
+    if (dist && r->r.total) VQ_HIP(hipMemcpyAsync(dist, r->r.dist.p, (size_t)r->r.total * 4, hipMemcpyDeviceToHost, s));
+    VQ_HIP(hipStreamSynchronize(s));
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_range_device(const vqhip_range *r, const void **dev_lims, const void **dev_idx, const void **dev_dist) {
+    if (!r) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (dev_lims) *dev_lims = r->r.lims.p;
+    if (dev_idx) *dev_idx = r->r.idx.p;
+    if (dev_dist) *dev_dist = r->r.dist.p;
+    return VQHIP_OK;
+}
+
+int vqhip_range_destroy(vqhip_range *r) {
+    delete r;
+    return VQHIP_OK;
 }
 
 }  // extern "C"

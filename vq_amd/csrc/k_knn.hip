@@ -12,10 +12,13 @@
 //   k_knn_hist     a 512-bin histogram per query, bins linear in KEY space over that range (monotone in D whatever the
 //                  values: +-inf, NaN, huge ranges), NaN alone in the last bin
 //   launch_topk_select   the shared selection stage (topk.hpp) over those distances and bins
+// A range search (launch_knn_range) runs k_knn_dist over the same batches and then the range stage (range.hpp; DESIGN.md
+// 15) in place of the histogram and the selection.
 // Roofline: VALU.  Squared L2 / Euclidean cost 3 unfused operations per (query, row, dimension), L1 2 (sub, then an add
 // that takes |.| as a source modifier), cosine 2 (mul, add).
 #include "kernels.hpp"
 #include "knn_tile.hpp"
+#include "range.hpp"
 #include "topk.hpp"
 
 #include <type_traits>
@@ -285,6 +288,33 @@ int launch_knn_search(int metric, const void *X, int dtype, uint64_t n, uint32_t
         VQ_TRY(launch_topk_select(src, nb, topk, 0, st, cand_ws, idx_out_dev + (size_t)q0 * topk, dist_out_dev + (size_t)q0 * topk,
                                   stream));
     }
+    return VQHIP_OK;
+}
+
+size_t range_ws_bytes(uint64_t n, uint32_t nq) { return range_ws_size(n, knn_query_batch(n, nq)); }
+
+// launch_knn_search with the range stage behind the distances: per batch k_knn_dist, then count -> scan -> (host: total,
+// cap, room) -> fill (range.hpp).  radii_dev [nq]; *out is complete when this returns.
+int launch_knn_range(int metric, const void *X, int dtype, uint64_t n, uint32_t d, const float *rnorm, const float *queries_dev,
+                     const float *qnorm_dev, uint32_t nq, const float *radii_dev, uint64_t max_results, float *dist_ws,
+                     void *state_ws, void *range_ws, RangeOut *out, hipStream_t stream) {
+    if (max_results == 0) return fail(VQHIP_ERR_INVALID_INPUT, "max_results must be at least 1");
+    const uint32_t qb = knn_query_batch(n, nq);
+    uint32_t *kmin = reinterpret_cast<uint32_t *>(state_ws);  // written by k_knn_dist, not read here
+    uint32_t *kmax = kmin + qb;
+    VQ_TRY(range_begin(out, nq, max_results, stream));
+    for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
+        const uint32_t nb = std::min(qb, nq - q0);
+        const float *Qb = queries_dev + (size_t)q0 * d;
+        const float *qn = qnorm_dev ? qnorm_dev + q0 : nullptr;
+        VQ_TRY(knn_dispatch(metric, dtype, [&](auto mtag, auto rtag) -> int {
+            using RT = std::remove_const_t<std::remove_pointer_t<decltype(rtag)>>;
+            return knn_dist_launch<decltype(mtag)::value, RT>(Qb, nb, reinterpret_cast<const RT *>(X), n, d, qn, rnorm, dist_ws,
+                                                             kmin, kmax, stream);
+        }));
+        VQ_TRY(range_batch(dist_ws, n, nb, q0, radii_dev + q0, range_ws, max_results, out, stream));
+    }
+    VQ_HIP(hipStreamSynchronize(stream));
     return VQHIP_OK;
 }
 

@@ -13,8 +13,10 @@
 //                  lane); the row side of a chunk is 2 KB of codes instead of 8 KB of floats
 //   k_knn_hist     the 512-bin key-space histogram per query (knn_tile.hpp)
 //   launch_topk_select   the shared selection stage (topk.hpp)
+// A range search (launch_sq_range) runs k_sq_dist over the same batches and then the range stage (range.hpp).
 #include "kernels.hpp"
 #include "knn_tile.hpp"
+#include "range.hpp"
 #include "topk.hpp"
 
 #include <type_traits>
@@ -309,6 +311,33 @@ int launch_sq_search(int metric, const uint8_t *C, uint64_t n, uint32_t d, float
         VQ_TRY(launch_topk_select(src, nb, topk, 0, st, cand_ws, idx_out_dev + (size_t)q0 * topk, dist_out_dev + (size_t)q0 * topk,
                                   stream));
     }
+    return VQHIP_OK;
+}
+
+// launch_sq_search with the range stage behind the distances (launch_knn_range): per batch k_sq_dist, then count -> scan
+// -> (host: total, cap, room) -> fill (range.hpp).  range_ws >= range_ws_bytes(n, nq); *out is complete on return.
+int launch_sq_range(int metric, const uint8_t *C, uint64_t n, uint32_t d, float mn, float step, const float *rnorm,
+                    const float *queries_dev, const float *qnorm_dev, uint32_t nq, const float *radii_dev, uint64_t max_results,
+                    float *dist_ws, void *state_ws, void *range_ws, RangeOut *out, hipStream_t stream) {
+    if (max_results == 0) return fail(VQHIP_ERR_INVALID_INPUT, "max_results must be at least 1");
+    const uint32_t qb = knn_query_batch(n, nq);
+    uint32_t *kmin = reinterpret_cast<uint32_t *>(state_ws);  // written by k_sq_dist, not read here
+    uint32_t *kmax = kmin + qb;
+    const int lw = sq_load_width(C, d);
+    VQ_TRY(range_begin(out, nq, max_results, stream));
+    for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
+        const uint32_t nb = std::min(qb, nq - q0);
+        const float *Qb = queries_dev + (size_t)q0 * d;
+        const float *qn = qnorm_dev ? qnorm_dev + q0 : nullptr;
+        VQ_TRY(sq_dispatch(metric, [&](auto mtag) -> int {
+            constexpr int M = decltype(mtag)::value;
+            if (lw == 16) return sq_dist_launch<M, 16>(Qb, nb, C, n, d, mn, step, qn, rnorm, dist_ws, kmin, kmax, stream);
+            if (lw == 4) return sq_dist_launch<M, 4>(Qb, nb, C, n, d, mn, step, qn, rnorm, dist_ws, kmin, kmax, stream);
+            return sq_dist_launch<M, 1>(Qb, nb, C, n, d, mn, step, qn, rnorm, dist_ws, kmin, kmax, stream);
+        }));
+        VQ_TRY(range_batch(dist_ws, n, nb, q0, radii_dev + q0, range_ws, max_results, out, stream));
+    }
+    VQ_HIP(hipStreamSynchronize(stream));
     return VQHIP_OK;
 }
 

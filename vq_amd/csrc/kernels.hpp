@@ -309,6 +309,26 @@ int launch_knn_rerank(int metric, const void *X, int dtype, uint64_t n, uint32_t
                       const float *qnorm_dev, uint32_t nq, const uint32_t *cand_dev, uint32_t c, uint32_t topk,
                       uint32_t *idx_out_dev, float *dist_out_dev, uint32_t *err_dev, hipStream_t stream);
 
+// exact range search (range.hpp behind k_knn.hip and k_sqindex.hip): per query every row with D <= its radius, in
+// ascending row id.  The result, on the device: lims [nq + 1] u64 (lims[0] = 0), idx / dist [total] with room for cap.
+struct RangeOut {
+    DevBuf lims, idx, dist;
+    uint32_t nq = 0;
+    uint64_t total = 0, cap = 0;
+};
+// workspace of the range stage for batches of knn_query_batch(n, nq) queries
+size_t range_ws_bytes(uint64_t n, uint32_t nq);
+// launch_knn_search's arguments with radii_dev [nq] f32 and max_results >= 1 in place of topk, range_ws >=
+// range_ws_bytes(n, nq) in place of the candidates; state_ws is written (kmin / kmax) and not read.  Waits for the
+// stream once per batch and once at the end: *out is complete on return.  More than max_results hits:
+// VQHIP_ERR_UNSUPPORTED.
+int launch_knn_range(int metric, const void *X, int dtype, uint64_t n, uint32_t d, const float *rnorm, const float *queries_dev,
+                     const float *qnorm_dev, uint32_t nq, const float *radii_dev, uint64_t max_results, float *dist_ws,
+                     void *state_ws, void *range_ws, RangeOut *out, hipStream_t stream);
+int launch_sq_range(int metric, const uint8_t *C, uint64_t n, uint32_t d, float mn, float step, const float *rnorm,
+                    const float *queries_dev, const float *qnorm_dev, uint32_t nq, const float *radii_dev, uint64_t max_results,
+                    float *dist_ws, void *state_ws, void *range_ws, RangeOut *out, hipStream_t stream);
+
 // exact search and rerank over resident SQ codes (k_sqindex.hip): C [n][d] u8, v(c) = mn + (float)c * step decoded on
 // the fly, rnorm [n] the decoded rows' norms (cosine only).  Batches and workspaces as launch_knn_search / _rerank; the
 // query norms come from launch_knn_norms.

@@ -3,7 +3,8 @@
 The reference has no search function; the semantics are include/vqhip.h's (vqhip_flat_*, vq_amd/csrc/k_knn.hip):
 ``D(q, i)`` is ``Distance.compute(q, rows[i])`` bit for bit (f16 rows widened exactly to f32 first), the result per
 query is the ``topk`` rows by ``(D, row index)`` ascending with NaN last, and ``rerank`` applies the same order to a
-caller's candidate lists.  Every argument is checked here before the device is touched; the rows go to the device once,
+caller's candidate lists; ``range_search`` returns every row with ``D(q, i) <= radius`` instead, in ascending row
+index (CSR).  Every argument is checked here before the device is touched; the rows go to the device once,
 on the first search (until then the index refers to the caller's array, which must not change in between).
 """
 from __future__ import annotations
@@ -25,6 +26,33 @@ def _count(v, name: str) -> int:
         return operator.index(v)
     except TypeError:
         raise InvalidParameter(name, f"must be an integer, got {v!r}") from None
+
+
+DEFAULT_MAX_RESULTS = 1 << 28  # hits a range search returns at most by default: 2 GB of idx + dist
+
+
+def _radii(radius, nq: int) -> np.ndarray:
+    """the per-query radii float32 (nq,) of a range search from a scalar or nq values; NaN is refused"""
+    try:
+        r = np.asarray(radius, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise InvalidParameter("radius", f"must be a number or an array of {nq} numbers, got {radius!r}") from None
+    if r.ndim == 0:
+        r = np.full(nq, r, np.float32)
+    if r.ndim != 1:
+        raise InvalidParameter("radius", f"must be a scalar or a 1D array, got {r.ndim} dimensions")
+    if r.shape[0] != nq:
+        raise DimensionMismatch(nq, r.shape[0])
+    if bool(np.isnan(r).any()):
+        raise InvalidParameter("radius", f"is NaN for query {int(np.flatnonzero(np.isnan(r))[0])}")
+    return np.ascontiguousarray(r)
+
+
+def _max_results(max_results) -> int:
+    m = _count(max_results, "max_results")
+    if not 1 <= m < 1 << 64:
+        raise InvalidParameter("max_results", f"must be in [1, 2^64), got {m}")
+    return m
 
 
 class FlatIndex:
@@ -108,6 +136,28 @@ class FlatIndex:
         if n_q < 0 or n_q >= 1 << 32:
             raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
         self._index().search_device(int(dev_queries), n_q, k, int(dev_idx), int(dev_dist))
+
+    def range_search(self, queries, radius, max_results: int = DEFAULT_MAX_RESULTS):
+        """every row within `radius` of each query: row i is a hit of query q iff D(q, i) <= radius[q] as a float32
+        comparison (NaN distances never hit).  `radius` is a scalar or nq values.  Returns (lims uint64 (nq + 1,),
+        idx uint32 (total,), dist float32 (total,)): the hits of query q are idx[lims[q]:lims[q + 1]], in ascending
+        row id.  More than `max_results` hits in all: FfiError (ERR_UNSUPPORTED)."""
+        q = self._queries(queries)
+        r = _radii(radius, q.shape[0])
+        m = _max_results(max_results)
+        if q.shape[0] == 0:
+            return np.zeros(1, np.uint64), np.empty(0, np.uint32), np.empty(0, np.float32)
+        return self._index().range_search(q, r, m).read()
+
+    def range_search_device(self, dev_queries: int, nq: int, radius, max_results: int = DEFAULT_MAX_RESULTS) -> "_lib.RangeResult":
+        """`range_search` with the queries [nq][d] f32 at a device pointer (4-byte aligned) and the result left on the
+        device: a RangeResult (.total, .lims, .device_pointers(), .read()).  Returns when the result is complete."""
+        n_q = _count(nq, "nq")
+        if n_q < 0 or n_q >= 1 << 32:
+            raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
+        r = _radii(radius, n_q)
+        m = _max_results(max_results)
+        return self._index().range_search_device(int(dev_queries), n_q, r, m)
 
     def rerank(self, queries, candidates, topk: int = 10):
         """per query, the `topk` nearest of its candidate row ids (nq, c), 1 <= c <= 4096, distinct within a query;

@@ -32,7 +32,7 @@ import numpy as np
 from . import _lib
 from .distance import Distance
 from .errors import DimensionMismatch, EmptyInput, InvalidData, InvalidParameter
-from .flat import MAX_CANDIDATES, MAX_TOPK, _count
+from .flat import DEFAULT_MAX_RESULTS, MAX_CANDIDATES, MAX_TOPK, _count, _max_results, _radii
 from .sq import ScalarQuantizer
 
 MAGIC = b"VQSQIDX1"
@@ -148,6 +148,26 @@ class ScalarIndex:
         if n_q < 0 or n_q >= 1 << 32:
             raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
         self._index().search_device(int(dev_queries), n_q, k, int(dev_idx), int(dev_dist))
+
+    def range_search(self, queries, radius, max_results: int = DEFAULT_MAX_RESULTS):
+        """every row within `radius` of each query, as ``FlatIndex.range_search`` over the dequantized codes: (lims uint64
+        (nq + 1,), idx uint32 (total,), dist float32 (total,)), the hits of a query in ascending row id"""
+        q = self._queries(queries)
+        r = _radii(radius, q.shape[0])
+        m = _max_results(max_results)
+        if q.shape[0] == 0:
+            return np.zeros(1, np.uint64), np.empty(0, np.uint32), np.empty(0, np.float32)
+        return self._index().range_search(q, r, m).read()
+
+    def range_search_device(self, dev_queries: int, nq: int, radius, max_results: int = DEFAULT_MAX_RESULTS) -> "_lib.RangeResult":
+        """`range_search` with the queries [nq][d] f32 at a device pointer (4-byte aligned) and the result left on the
+        device: a RangeResult (.total, .lims, .device_pointers(), .read()).  Returns when the result is complete."""
+        n_q = _count(nq, "nq")
+        if n_q < 0 or n_q >= 1 << 32:
+            raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
+        r = _radii(radius, n_q)
+        m = _max_results(max_results)
+        return self._index().range_search_device(int(dev_queries), n_q, r, m)
 
     def rerank(self, queries, candidates, topk: int = 10):
         """per query, the `topk` nearest of its candidate row ids (nq, c), 1 <= c <= 4096, distinct within a query;
