@@ -1120,6 +1120,101 @@ class IVFFlatIndex {
     Distance distance_;
 };
 
+// Inverted-file index over SQ codes (include/vqhip.h, vqhip_ivfsq_*): coarse centroids [nlist][dim], a ScalarQuantizer, rows
+// added as (list id, u8 codes) or as (list id, f32 row) encoded on the device.  search computes the exact distance
+// (FlatIndex's, any metric) to the dequantized rows of the nprobe lists nearest to a query and gives (row id, distance)
+// pairs [nq][topk], nearest first; slots past the probed rows hold (0xFFFFFFFF, +inf).  Every result equals IVFFlatIndex
+// over quantizer.dequantize(codes) in the same lists; with nprobe == nlist it is ScalarIndex's search.  The constructor,
+// add_codes, codes and list_sizes need no device; the arguments are checked before the device is touched.
+class IVFScalarIndex {
+   public:
+    IVFScalarIndex(const float *coarse, std::size_t nlist, std::size_t dim, ScalarQuantizer quantizer, Distance distance = Distance())
+        : quantizer_(quantizer) {
+        if (nlist == 0 || nlist > 65536) throw VqError::InvalidParameter("nlist", "must be between 1 and 65536");
+        if (dim == 0 || dim > 0xFFFFFFFFu) throw VqError::InvalidParameter("dim", "must be between 1 and 2^32 - 1");
+        vqhip_ivfsq *ix = nullptr;
+        detail::check(vqhip_ivfsq_create(quantizer_.min(), quantizer_.max(), (std::uint32_t)quantizer_.levels(), coarse,
+                                         (std::uint32_t)nlist, (std::uint32_t)dim, (int)distance.kind(), &ix));
+        ix_.reset(ix);
+        nlist_ = nlist;
+        dim_ = dim;
+        distance_ = distance;
+    }
+    std::size_t size() const { return n_; }
+    std::size_t nlist() const { return nlist_; }
+    std::size_t dim() const { return dim_; }
+    const ScalarQuantizer &quantizer() const { return quantizer_; }
+    const char *distance_metric() const { return distance_.name(); }
+
+    // rows appended in order: list_ids [n] < nlist, codes [n][dim] (every byte value is legal); returns the first new row id
+    std::size_t add_codes(const std::uint32_t *list_ids, const std::uint8_t *codes, std::size_t n) {
+        check_add(list_ids, n, "codes");
+        const std::size_t first = n_;
+        if (n) detail::check(vqhip_ivfsq_add_codes(ix_.get(), list_ids, codes, n));
+        n_ += n;
+        return first;
+    }
+    // rows [n][dim] f32, encoded on the device (the quantizer's codes); only the codes are kept
+    std::size_t add_rows(const std::uint32_t *list_ids, const float *rows, std::size_t n) {
+        check_add(list_ids, n, "rows");
+        const std::size_t first = n_;
+        if (n) detail::check(vqhip_ivfsq_add_rows(ix_.get(), list_ids, rows, n));
+        n_ += n;
+        return first;
+    }
+    std::vector<std::uint64_t> list_sizes() const {
+        std::vector<std::uint64_t> s(nlist_);
+        detail::check(vqhip_ivfsq_list_sizes(ix_.get(), s.data()));
+        return s;
+    }
+    // the codes [n][dim], in add order
+    std::vector<std::uint8_t> codes() const {
+        std::vector<std::uint8_t> out(n_ * dim_);
+        detail::check(vqhip_ivfsq_codes(ix_.get(), out.data()));
+        return out;
+    }
+
+    struct Result {
+        std::vector<std::uint32_t> idx;  // [nq][topk]
+        std::vector<float> dist;         // [nq][topk]
+    };
+    // queries [nq][dim] -> the lists each query scans [nq][nprobe], nearest first
+    std::vector<std::uint32_t> probe(const float *queries, std::size_t nq, std::size_t nprobe) const {
+        check_probe(nprobe, nq);
+        std::vector<std::uint32_t> out(nq * nprobe);
+        if (nq) detail::check(vqhip_ivfsq_probe(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, out.data()));
+        return out;
+    }
+    Result search(const float *queries, std::size_t nq, std::size_t topk, std::size_t nprobe) const {
+        check_probe(nprobe, nq);
+        if (topk == 0 || topk > 1024 || topk > n_) throw VqError::InvalidParameter("topk", "must be between 1 and min(n, 1024)");
+        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
+        if (nq)
+            detail::check(vqhip_ivfsq_search(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, (std::uint32_t)topk,
+                                             r.idx.data(), r.dist.data()));
+        return r;
+    }
+
+   private:
+    struct Del {
+        void operator()(vqhip_ivfsq *p) const { (void)vqhip_ivfsq_destroy(p); }
+    };
+    void check_add(const std::uint32_t *list_ids, std::size_t n, const char *what) const {
+        if (n >= (std::size_t(1) << 32) - n_) throw VqError::InvalidParameter(what, "an index holds at most 2^32 - 1 rows");
+        for (std::size_t i = 0; i < n; ++i)
+            if (list_ids[i] >= nlist_) throw VqError::InvalidParameter("list_ids", "a list id is outside [0, nlist)");
+    }
+    void check_probe(std::size_t nprobe, std::size_t nq) const {
+        if (nprobe == 0 || nprobe > 1024 || nprobe > nlist_)
+            throw VqError::InvalidParameter("nprobe", "must be between 1 and min(nlist, 1024)");
+        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
+    }
+    ScalarQuantizer quantizer_;
+    std::unique_ptr<vqhip_ivfsq, Del> ix_;
+    std::size_t n_ = 0, nlist_ = 0, dim_ = 0;
+    Distance distance_;
+};
+
 // analogue of vq::get_simd_backend (src/lib.rs): names the device backend
 inline std::string get_simd_backend() { return vqhip_backend(); }
 

@@ -687,6 +687,52 @@ int vqhip_ivfflat_search(vqhip_ivfflat *ix, const float *queries, uint32_t nq, u
 int vqhip_ivfflat_search_device(vqhip_ivfflat *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
                                 void *dev_idx, void *dev_dist);
 
+/* ---- inverted-file scalar index: exact distances to SQ codes over the probed lists (k_ivfsq.hip) ---------
+ * No reference counterpart.  vqhip_ivfflat with each row kept as one SQ byte per dimension.  An index is fixed by a
+ * ScalarQuantizer(min, max, levels) -- the parameters go through vqhip_sq_check, whose status and text create reports
+ * unchanged --, coarse centroids C [nlist][dim] f32 (1 <= nlist <= 65536), a metric (any of the five) and, per row i (ids
+ * in add order, n < 2^32 in all), a list id list[i] < nlist and codes[i][dim] u8.  Several adds equal one add of the
+ * concatenation.  With v(c) = min + (float)c * step as vqhip_sqindex's (un-fused, two roundings; every byte value is
+ * legal, codes >= levels decode by the same formula):
+ *   P(q)    = the nprobe lists vqhip_flat_search over C (same metric) returns, ordered by (key, list id): exactly
+ *             vqhip_ivfflat_probe.  1 <= nprobe <= min(nlist, 1024).
+ *   S(q)    = { i : list[i] in P(q) }.
+ *   D(q, i) = Distance::compute(q, v(codes[i])) bit for bit, in the flat index's arithmetic and order: the pair summed
+ *             sequentially over t = 0..dim-1 from -0.0f, one rounding per operation, no fused multiply-add; Euclidean =
+ *             sqrtf of the sum; cosine through vq_cosine_finish, the row norms sqrtf(sum v^2) (sequential chains, as
+ *             vqhip_sqindex's) computed once per add's upload and the query norms once per call.
+ *   search  = the topk rows of S(q) by (key(D), row id) ascending, 1 <= topk <= min(n, 1024): NaN sorts last and is
+ *             reported as 0x7FC00000, ties go to the lower row, Euclidean orders by the reported root.  If |S(q)| < topk
+ *             the remaining slots hold idx 0xFFFFFFFF and dist +inf, after every real row.  Run-to-run deterministic.
+ * Two identities follow.  (1) The index equals vqhip_ivfflat (dtype 0, same C and metric) over the rows vqhip_sq_decode
+ * gives for the codes, in the same lists, for every nprobe and topk: indices, and distances as uint32 bits.  (2) With
+ * nprobe == nlist it equals vqhip_sqindex_search over the codes in add order.  A degenerate quantizer is no special case:
+ * (-3e38, 3e38, 2) has step = +inf, so v(0) = NaN and v(c > 0) = +inf, and those rows sort last by id.
+ * add_codes takes host u8 codes [n][dim] and is host-only.  add_rows takes host f32 rows [n][dim], encodes them on the
+ * device as vqhip_sq_encode does (the codes are equal) and keeps only the codes; it needs the device.  Both check every
+ * list id on the host before anything is stored (VQHIP_ERR_INVALID_INPUT).  codes copies the codes out in add order
+ * (codes_out [n][dim]; host-only).  info: any output pointer may be NULL.  queries [nq][dim] f32, lists_out
+ * [nq][nprobe], idx / dist [nq][topk]; nq = 0 is a no-op; every parameter is checked before any device work.  Device
+ * ownership, the lazy build of the device state (the flat index over C, the codes in list order in a buffer the index
+ * owns, gathered through a bounded staging buffer) and its rebuild after an add, the batches (at most 1024 queries whose
+ * distances stay under 1 GB, one query's when that alone is more), the two forms of search and the lock are
+ * vqhip_ivfflat's.  The host keeps n * dim bytes, the device n * dim (+ 4 n under the cosines, + 4 n of row ids). */
+typedef struct vqhip_ivfsq vqhip_ivfsq;
+int vqhip_ivfsq_create(float min, float max, uint32_t levels, const float *coarse, uint32_t nlist, uint32_t dim, int metric,
+                       vqhip_ivfsq **out);
+int vqhip_ivfsq_destroy(vqhip_ivfsq *ix);
+int vqhip_ivfsq_add_codes(vqhip_ivfsq *ix, const uint32_t *list_ids, const uint8_t *codes, uint64_t n);
+int vqhip_ivfsq_add_rows(vqhip_ivfsq *ix, const uint32_t *list_ids, const float *rows, uint64_t n);
+int vqhip_ivfsq_info(const vqhip_ivfsq *ix, uint64_t *n, uint32_t *nlist, uint32_t *dim, int *metric, float *min, float *max,
+                     uint32_t *levels);
+int vqhip_ivfsq_list_sizes(vqhip_ivfsq *ix, uint64_t *sizes);
+int vqhip_ivfsq_codes(vqhip_ivfsq *ix, uint8_t *codes_out);
+int vqhip_ivfsq_probe(vqhip_ivfsq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t *lists_out);
+int vqhip_ivfsq_search(vqhip_ivfsq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                       uint32_t *idx_out, float *dist_out);
+int vqhip_ivfsq_search_device(vqhip_ivfsq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                              void *dev_idx, void *dev_dist);
+
 /* ---- TSVQ ----------------------------------------------------------------------------
  * build replaces TSVQNode::build (src/tsvq.rs:31-115); the tree comes back flattened in
  * pre-order (node 0 = root, left subtree, right subtree): centroids [cap][d], left/right

@@ -1,7 +1,8 @@
 """vq_amd -- MI355X (gfx950) back end for the k-means codebook-training and nearest-centroid
 encode path of CogitatorTech/vq, and of its elementwise scalar / binary quantizers, behind the
 reference's own Quantizer interface, exact k-NN search over resident rows (FlatIndex), an inverted-file
-index over PQ codes (IVFPQIndex) and one over the rows themselves (IVFFlatIndex), a Hamming index over packed BQ codes (BinaryIndex) and an exact index over
+index over PQ codes (IVFPQIndex) one over the rows themselves (IVFFlatIndex) and one over SQ codes
+(IVFScalarIndex), a Hamming index over packed BQ codes (BinaryIndex) and an exact index over
 resident SQ codes (ScalarIndex).
 
 The compute path is libvqhip.so (hand-written HIP for CDNA4, C ABI in include/vqhip.h).
@@ -17,13 +18,14 @@ from ._lib import RangeResult
 from .flat import FlatIndex
 from .ivf import IVFPQIndex
 from .ivf_flat import IVFFlatIndex
+from .ivf_scalar import IVFScalarIndex
 from .pq import ProductQuantizer, fit_codebooks
 from .scalar_index import ScalarIndex
 from .sq import ScalarQuantizer
 from .tsvq import TSVQ
 
 __all__ = [
-    "Distance", "BinaryIndex", "BinaryQuantizer", "FlatIndex", "IVFFlatIndex", "IVFPQIndex", "RangeResult", "ScalarIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
+    "Distance", "BinaryIndex", "BinaryQuantizer", "FlatIndex", "IVFFlatIndex", "IVFPQIndex", "IVFScalarIndex", "RangeResult", "ScalarIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
     "InvalidParameter", "InvalidData", "FfiError", "get_simd_backend",
 ]
 

@@ -198,6 +198,16 @@ SIGNATURES = {
     "vqhip_ivfflat_probe": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p]),
     "vqhip_ivfflat_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _f32p]),
     "vqhip_ivfflat_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "vqhip_ivfsq_create": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_int, _vpp]),
+    "vqhip_ivfsq_destroy": (C.c_int, [_vp]),
+    "vqhip_ivfsq_add_codes": (C.c_int, [_vp, _u32p, _u8p, C.c_uint64]),
+    "vqhip_ivfsq_add_rows": (C.c_int, [_vp, _u32p, _f32p, C.c_uint64]),
+    "vqhip_ivfsq_info": (C.c_int, [_vp, _u64p, _u32p, _u32p, C.POINTER(C.c_int), _f32p, _f32p, _u32p]),
+    "vqhip_ivfsq_list_sizes": (C.c_int, [_vp, _u64p]),
+    "vqhip_ivfsq_codes": (C.c_int, [_vp, _u8p]),
+    "vqhip_ivfsq_probe": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p]),
+    "vqhip_ivfsq_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "vqhip_ivfsq_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
     "vqhip_ivfpq_create_ex": (C.c_int, [_f32p, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
                                         _vpp]),
     "vqhip_ivfpq_flags": (C.c_int, [_vp, _u32p]),
@@ -1059,6 +1069,65 @@ class IVFFlat(Handle):
     def search_device(self, dev_queries: int, nq: int, nprobe: int, topk: int, dev_idx: int, dev_dist: int):
         check(load().vqhip_ivfflat_search_device(self.raw, C.c_void_p(dev_queries), int(nq), int(nprobe), int(topk),
                                                  C.c_void_p(dev_idx), C.c_void_p(dev_dist)))
+
+
+class IVFSQ(Handle):
+    """vqhip_ivfsq: inverted-file scalar index -- coarse centroids, a ScalarQuantizer's u8 codes in lists, exact distances
+    to the decoded rows over the probed lists (k_ivfsq.hip).  Create, add_codes, codes, info and list_sizes are host-only;
+    add_rows encodes on the device; the device state is built by the first probe or search."""
+
+    _destroy = "vqhip_ivfsq_destroy"
+
+    def __init__(self, coarse, mn: float, mx: float, levels: int, metric: int):
+        c = f32c(coarse)
+        h = C.c_void_p()
+        check(load().vqhip_ivfsq_create(mn, mx, int(levels), ptr(c, _f32p), c.shape[0], c.shape[1], int(metric), C.byref(h)))
+        super().__init__(h)
+        self.nlist, self.dim, self.metric = c.shape[0], c.shape[1], int(metric)
+
+    def add_codes(self, list_ids, codes):
+        lid = np.ascontiguousarray(list_ids, dtype=np.uint32)
+        c = np.ascontiguousarray(codes, dtype=np.uint8)
+        check(load().vqhip_ivfsq_add_codes(self.raw, ptr(lid, _u32p), ptr(c, _u8p), lid.shape[0]))
+
+    def add_rows(self, list_ids, rows):
+        lid = np.ascontiguousarray(list_ids, dtype=np.uint32)
+        r = f32c(rows)
+        check(load().vqhip_ivfsq_add_rows(self.raw, ptr(lid, _u32p), ptr(r, _f32p), lid.shape[0]))
+
+    def info(self):
+        n, nlist, dim, metric = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_int()
+        mn, mx, levels = C.c_float(), C.c_float(), C.c_uint32()
+        check(load().vqhip_ivfsq_info(self.raw, C.byref(n), C.byref(nlist), C.byref(dim), C.byref(metric), C.byref(mn), C.byref(mx),
+                                      C.byref(levels)))
+        return int(n.value), int(nlist.value), int(dim.value), int(metric.value), float(mn.value), float(mx.value), int(levels.value)
+
+    def list_sizes(self) -> np.ndarray:
+        out = np.empty(self.nlist, np.uint64)
+        check(load().vqhip_ivfsq_list_sizes(self.raw, ptr(out, _u64p)))
+        return out
+
+    def codes(self) -> np.ndarray:
+        out = np.empty((self.info()[0], self.dim), np.uint8)
+        check(load().vqhip_ivfsq_codes(self.raw, ptr(out, _u8p)))
+        return out
+
+    def probe(self, q: np.ndarray, nprobe: int) -> np.ndarray:
+        nq = q.shape[0]
+        out = np.empty((nq, nprobe), np.uint32)
+        check(load().vqhip_ivfsq_probe(self.raw, ptr(q, _f32p), nq, int(nprobe), ptr(out, _u32p)))
+        return out
+
+    def search(self, q: np.ndarray, nprobe: int, topk: int):
+        nq = q.shape[0]
+        idx = np.empty((nq, topk), np.uint32)
+        dist = np.empty((nq, topk), np.float32)
+        check(load().vqhip_ivfsq_search(self.raw, ptr(q, _f32p), nq, int(nprobe), int(topk), ptr(idx, _u32p), ptr(dist, _f32p)))
+        return idx, dist
+
+    def search_device(self, dev_queries: int, nq: int, nprobe: int, topk: int, dev_idx: int, dev_dist: int):
+        check(load().vqhip_ivfsq_search_device(self.raw, C.c_void_p(dev_queries), int(nq), int(nprobe), int(topk),
+                                               C.c_void_p(dev_idx), C.c_void_p(dev_dist)))
 
 
 def dequantize_f16(f16) -> np.ndarray:

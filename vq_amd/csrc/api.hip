@@ -3997,6 +3997,301 @@ int vqhip_ivfflat_search_device(vqhip_ivfflat *ix, const void *dev_queries, uint
     VQ_API_END
 }
 
+}  // extern "C"
+
+// ------------------------------------------------------------------ inverted-file scalar (k_ivfsq.hip) ----
+// vqhip_ivfflat with the rows kept as SQ codes.  Host state: the quantizer, the coarse centroids and every added row's
+// list id and codes in add order (n * dim bytes).  The device state -- a flat index over the centroids and the codes in
+// list order (off / ids / codes, the decoded rows' norms under the cosines) -- is built and rebuilt as vqhip_ivfflat's:
+// a host counting sort, the codes gathered into list order through the kIvfflatStage staging buffer.
+struct vqhip_ivfsq {
+    HandleSync sync;
+    uint32_t nlist = 0, dim = 0, levels = 0;
+    float mn = 0, mx = 0, step = 0;
+    int metric = VQHIP_EUCLIDEAN;
+    SqbqEncodeOp op;                 // add_rows: the encode of this quantizer
+    std::vector<float> coarse;       // [nlist][dim]
+    std::vector<uint32_t> row_list;  // [n] list id of each row
+    std::vector<uint8_t> row_codes;  // [n][dim]
+    std::vector<uint64_t> sizes;     // [nlist] rows per list
+    uint64_t n = 0, max_list = 0;
+    bool dirty = true;                     // rows added since the last upload
+    int dev = -1;                          // as vqhip_ivfpq's
+    std::vector<uint64_t> largest_prefix;  // [nlist + 1] sums of the largest list sizes (the bound on |S(q)|)
+    vqhip_flat *flat = nullptr;            // the coarse centroids on the device
+    DevBuf d_off, d_ids, d_codes, d_rnorm;
+    DevBuf q, qnorm, probe, probe_dist, pref, seg, inv, lists, W, state, cand, idx, out;  // per-call workspaces
+    ~vqhip_ivfsq() { delete flat; }
+};
+
+static int ivfsq_check_probe(const vqhip_ivfsq *ix, uint32_t nprobe) {
+    const uint32_t hi = std::min<uint32_t>(ix->nlist, 1024);
+    if (nprobe == 0 || nprobe > hi) return fail(VQHIP_ERR_INVALID_INPUT, "nprobe %u must be in [1, min(nlist, 1024)] = [1, %u]", nprobe, hi);
+    return VQHIP_OK;
+}
+
+// the device state, current with the host's rows (enqueued on s and waited for: host buffers are the copies' sources)
+static int ivfsq_ready(vqhip_ivfsq *ix, hipStream_t s) {
+    if (!ix->flat) VQ_TRY(flat_create(ix->coarse.data(), hipMemcpyHostToDevice, ix->nlist, ix->dim, 0, ix->metric, &ix->flat));
+    if (!ix->dirty) return VQHIP_OK;
+    const size_t row_b = ix->dim;
+    std::vector<uint32_t> off(ix->nlist + 1, 0), at(ix->nlist), ids(ix->n);
+    for (uint32_t l = 0; l < ix->nlist; ++l) off[l + 1] = off[l] + (uint32_t)ix->sizes[l];
+    std::copy(off.begin(), off.end() - 1, at.begin());
+    for (uint64_t i = 0; i < ix->n; ++i) ids[at[ix->row_list[i]]++] = (uint32_t)i;  // ascending row ids within each list
+    VQ_TRY(ix->d_off.alloc(off.size() * 4));
+    VQ_TRY(ix->d_ids.alloc(ids.size() * 4));
+    VQ_TRY(ix->d_codes.alloc((size_t)ix->n * row_b));  // (the index's own buffer: the loaders' alignment rests on its base)
+    VQ_HIP(hipMemcpyAsync(ix->d_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, s));
+    if (ix->n) {
+        VQ_HIP(hipMemcpyAsync(ix->d_ids.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, s));
+        const uint64_t per = std::max<uint64_t>(1, kIvfflatStage / row_b);
+        std::vector<uint8_t> stage((size_t)std::min<uint64_t>(per, ix->n) * row_b);
+        for (uint64_t p0 = 0; p0 < ix->n; p0 += per) {
+            const uint64_t pn = std::min<uint64_t>(per, ix->n - p0);
+            for (uint64_t p = 0; p < pn; ++p) memcpy(stage.data() + (size_t)p * row_b, ix->row_codes.data() + (size_t)ids[p0 + p] * row_b, row_b);
+            VQ_HIP(hipMemcpyAsync(ix->d_codes.as<uint8_t>() + (size_t)p0 * row_b, stage.data(), (size_t)pn * row_b, hipMemcpyHostToDevice, s));
+            VQ_HIP(hipStreamSynchronize(s));  // (the staging buffer is filled again)
+        }
+        if (vq_is_cos(ix->metric)) {
+            VQ_TRY(ix->d_rnorm.alloc((size_t)ix->n * 4));
+            VQ_TRY(launch_sq_norms(ix->d_codes.as<uint8_t>(), ix->n, ix->dim, ix->mn, ix->step, ix->d_rnorm.as<float>(), s));
+        }
+    }
+    VQ_HIP(hipStreamSynchronize(s));
+    std::vector<uint64_t> sorted(ix->sizes);
+    std::sort(sorted.begin(), sorted.end(), std::greater<uint64_t>());
+    ix->max_list = sorted[0];
+    ix->largest_prefix.assign(ix->nlist + 1, 0);
+    for (uint32_t l = 0; l < ix->nlist; ++l) ix->largest_prefix[l + 1] = ix->largest_prefix[l] + sorted[l];
+    ix->dirty = false;
+    return VQHIP_OK;
+}
+
+// every device call runs on the index's device
+static int ivfsq_device(vqhip_ivfsq *ix) {
+    int cur = 0;
+    VQ_HIP(hipGetDevice(&cur));
+    if (ix->dev < 0) ix->dev = cur;
+    if (cur != ix->dev) return fail(VQHIP_ERR_INVALID_INPUT, "the index lives on device %d, but device %d is current", ix->dev, cur);
+    return VQHIP_OK;
+}
+
+// queries_dev [nq][dim] f32 -> probe lists [nq][nprobe] on the device
+static int ivfsq_probe_enqueue(vqhip_ivfsq *ix, const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t *lists_dev,
+                               hipStream_t s) {
+    VQ_TRY(ix->probe_dist.ensure((size_t)nq * nprobe * 4));
+    return flat_search_enqueue(ix->flat, queries_dev, nq, nprobe, lists_dev, ix->probe_dist.as<float>(), s);
+}
+
+// queries_dev [nq][dim] f32 -> [nq][topk] results on the device, enqueued on s; the batches of ivfflat_search_enqueue
+static int ivfsq_search_enqueue(vqhip_ivfsq *ix, const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                                uint32_t *idx_dev, float *dist_dev, hipStream_t s) {
+    const uint64_t wstride = std::max<uint64_t>(ix->largest_prefix[nprobe], 1);
+    const uint32_t nb_max = (uint32_t)std::min<uint64_t>({(uint64_t)nq, 1024, std::max<uint64_t>(1, (1ull << 30) / (4 * wstride))});
+    VQ_TRY(ix->probe.ensure((size_t)nb_max * nprobe * 4));
+    VQ_TRY(ix->pref.ensure((size_t)nb_max * (nprobe + 1) * 4));
+    VQ_TRY(ix->seg.ensure((size_t)nb_max * nprobe * 4));
+    VQ_TRY(ix->inv.ensure((size_t)nb_max * nprobe * 4));
+    VQ_TRY(ix->lists.ensure(ivfflat_lists_bytes(ix->nlist)));
+    VQ_TRY(ix->W.ensure((size_t)nb_max * wstride * 4));
+    VQ_TRY(ix->state.ensure(knn_state_bytes(nb_max)));
+    VQ_TRY(ix->cand.ensure(topk_cand_bytes(nb_max)));
+    const float *qn = nullptr;
+    if (vq_is_cos(ix->metric)) {  // once per call
+        VQ_TRY(ix->qnorm.ensure((size_t)nq * 4));
+        VQ_TRY(launch_knn_norms(queries_dev, 0, nq, ix->dim, ix->qnorm.as<float>(), s));
+        qn = ix->qnorm.as<float>();
+    }
+    // expected positions per query: the mean list size times nprobe
+    const uint64_t per_q = std::max<uint64_t>(1, (uint64_t)((double)ix->n * nprobe / ix->nlist));
+    for (uint32_t q0 = 0; q0 < nq; q0 += nb_max) {
+        const uint32_t nb = std::min(nb_max, nq - q0);
+        const float *Q = queries_dev + (size_t)q0 * ix->dim;
+        VQ_TRY(ivfsq_probe_enqueue(ix, Q, nb, nprobe, ix->probe.as<uint32_t>(), s));
+        VQ_TRY(launch_ivfsq_search(ix->metric, ix->d_codes.as<uint8_t>(), ix->dim, ix->mn, ix->step, ix->d_rnorm.as<float>(),
+                                   ix->d_ids.as<uint32_t>(), ix->d_off.as<uint32_t>(), ix->nlist, ix->max_list, Q, qn ? qn + q0 : nullptr,
+                                   ix->probe.as<uint32_t>(), nb, nprobe, topk, ivf_chunk((uint64_t)nb * per_q), wstride,
+                                   ix->W.as<float>(), ix->pref.as<uint32_t>(), ix->seg.as<uint32_t>(), ix->inv.as<uint32_t>(),
+                                   ix->lists.as<uint32_t>(), ix->state.p, ix->cand.as<unsigned long long>(),
+                                   idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s));
+    }
+    return VQHIP_OK;
+}
+
+// the checks of an add (before anything is stored), and its bookkeeping once the codes are in row_codes
+static int ivfsq_add_begin(vqhip_ivfsq *ix, const uint32_t *list_ids, uint64_t n) {
+    if (n >= (1ull << 32) - ix->n)
+        return fail(VQHIP_ERR_INVALID_INPUT, "the index would hold %llu + %llu rows: at most 2^32 - 1", (unsigned long long)ix->n,
+                    (unsigned long long)n);
+    for (uint64_t i = 0; i < n; ++i)
+        if (list_ids[i] >= ix->nlist)
+            return fail(VQHIP_ERR_INVALID_INPUT, "list id %u of row %llu is outside [0, %u)", list_ids[i], (unsigned long long)i, ix->nlist);
+    return VQHIP_OK;
+}
+static void ivfsq_add_end(vqhip_ivfsq *ix, const uint32_t *list_ids, uint64_t n) {
+    ix->row_list.insert(ix->row_list.end(), list_ids, list_ids + n);
+    for (uint64_t i = 0; i < n; ++i) ++ix->sizes[list_ids[i]];
+    ix->n += n;
+    ix->dirty = true;
+}
+
+extern "C" {
+
+int vqhip_ivfsq_create(float min, float max, uint32_t levels, const float *coarse, uint32_t nlist, uint32_t dim, int metric,
+                       vqhip_ivfsq **out) {
+    VQ_API_BEGIN
+    if (!out) return fail(VQHIP_ERR_NULL_PTR, "out is NULL");
+    *out = nullptr;
+    float step = 0;
+    VQ_TRY(sq_check(min, max, levels, &step));
+    if (!coarse) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (nlist == 0 || nlist > 65536) return fail(VQHIP_ERR_INVALID_INPUT, "nlist %u must be in [1, 65536]", nlist);
+    if (dim == 0) return fail(VQHIP_ERR_INVALID_INPUT, "dim must be at least 1");
+    if (metric < VQHIP_SQUARED_EUCLIDEAN || metric > VQHIP_COSINE_UNCLAMPED) return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
+    std::unique_ptr<vqhip_ivfsq> ix(new vqhip_ivfsq());
+    VQ_TRY(sq_encode_op(min, max, levels, &ix->op));
+    ix->nlist = nlist;
+    ix->dim = dim;
+    ix->levels = levels;
+    ix->mn = min, ix->mx = max, ix->step = step;
+    ix->metric = metric;
+    ix->coarse.assign(coarse, coarse + (size_t)nlist * dim);
+    ix->sizes.assign(nlist, 0);
+    int ndev = 0, cur = -1;  // (the device is named, not touched: the state is built by the first probe or search)
+    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && hipGetDevice(&cur) == hipSuccess) ix->dev = cur;
+    *out = ix.release();
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_ivfsq_destroy(vqhip_ivfsq *ix) {
+    delete ix;
+    return VQHIP_OK;
+}
+
+int vqhip_ivfsq_add_codes(vqhip_ivfsq *ix, const uint32_t *list_ids, const uint8_t *codes, uint64_t n) {
+    VQ_API_BEGIN
+    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (n == 0) return VQHIP_OK;
+    if (!list_ids || !codes) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);
+    VQ_TRY(ivfsq_add_begin(ix, list_ids, n));
+    ix->row_codes.insert(ix->row_codes.end(), codes, codes + (size_t)n * ix->dim);
+    ivfsq_add_end(ix, list_ids, n);
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_ivfsq_add_rows(vqhip_ivfsq *ix, const uint32_t *list_ids, const float *rows, uint64_t n) {
+    VQ_API_BEGIN
+    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (n == 0) return VQHIP_OK;
+    if (!list_ids || !rows) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);
+    VQ_TRY(ivfsq_add_begin(ix, list_ids, n));
+    VQ_TRY(require_gfx950());
+    VQ_TRY(ivfsq_device(ix));
+    const size_t have = ix->row_codes.size();
+    ix->row_codes.resize(have + (size_t)n * ix->dim);
+    const int rc = sqbq_encode_host(ix->op, rows, n * ix->dim, ix->row_codes.data() + have);  // vqhip_sq_encode's path
+    if (rc != VQHIP_OK) {
+        ix->row_codes.resize(have);  // (nothing is stored)
+        return rc;
+    }
+    ivfsq_add_end(ix, list_ids, n);
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_ivfsq_info(const vqhip_ivfsq *ix, uint64_t *n, uint32_t *nlist, uint32_t *dim, int *metric, float *min, float *max,
+                     uint32_t *levels) {
+    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    std::lock_guard<std::recursive_mutex> lock(const_cast<vqhip_ivfsq *>(ix)->sync.mu);  // (n changes under add)
+    if (n) *n = ix->n;
+    if (nlist) *nlist = ix->nlist;
+    if (dim) *dim = ix->dim;
+    if (metric) *metric = ix->metric;
+    if (min) *min = ix->mn;
+    if (max) *max = ix->mx;
+    if (levels) *levels = ix->levels;
+    return VQHIP_OK;
+}
+
+int vqhip_ivfsq_list_sizes(vqhip_ivfsq *ix, uint64_t *sizes) {
+    VQ_API_BEGIN
+    if (!ix || !sizes) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);
+    memcpy(sizes, ix->sizes.data(), ix->sizes.size() * 8);
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_ivfsq_codes(vqhip_ivfsq *ix, uint8_t *codes_out) {
+    VQ_API_BEGIN
+    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);
+    if (ix->n == 0) return VQHIP_OK;
+    if (!codes_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    memcpy(codes_out, ix->row_codes.data(), ix->row_codes.size());
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_ivfsq_probe(vqhip_ivfsq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t *lists_out) {
+    VQ_API_BEGIN
+    if (!ix || !queries || !lists_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);  // (n changes under add: read under the lock)
+    VQ_TRY(ivfsq_check_probe(ix, nprobe));
+    if (nq == 0) return VQHIP_OK;
+    VQ_TRY(require_gfx950());
+    VQ_TRY(ivfsq_device(ix));
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    VQ_TRY(ivfsq_ready(ix, s));
+    return host_search(in, s, ix->q, ix->idx, nullptr, queries, nq, ix->dim, nprobe, lists_out, nullptr, [&] {
+        return ivfsq_probe_enqueue(ix, ix->q.as<float>(), nq, nprobe, ix->idx.as<uint32_t>(), s);
+    });
+    VQ_API_END
+}
+
+int vqhip_ivfsq_search(vqhip_ivfsq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_out,
+                       float *dist_out) {
+    VQ_API_BEGIN
+    if (!ix || !queries || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);  // (n changes under add: read under the lock)
+    VQ_TRY(ivfsq_check_probe(ix, nprobe));
+    VQ_TRY(check_topk(ix->n, topk));
+    if (nq == 0) return VQHIP_OK;
+    VQ_TRY(require_gfx950());
+    VQ_TRY(ivfsq_device(ix));
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    VQ_TRY(ivfsq_ready(ix, s));
+    return host_search(in, s, ix->q, ix->idx, &ix->out, queries, nq, ix->dim, topk, idx_out, dist_out, [&] {
+        return ivfsq_search_enqueue(ix, ix->q.as<float>(), nq, nprobe, topk, ix->idx.as<uint32_t>(), ix->out.as<float>(), s);
+    });
+    VQ_API_END
+}
+
+int vqhip_ivfsq_search_device(vqhip_ivfsq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk, void *dev_idx,
+                              void *dev_dist) {
+    VQ_API_BEGIN
+    if (!ix || !dev_queries || !dev_idx || !dev_dist) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);  // (n changes under add: read under the lock)
+    VQ_TRY(ivfsq_check_probe(ix, nprobe));
+    VQ_TRY(check_topk(ix->n, topk));
+    if (nq == 0) return VQHIP_OK;
+    VQ_TRY(require_gfx950());
+    VQ_TRY(ivfsq_device(ix));
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    VQ_TRY(ivfsq_ready(ix, s));
+    return ivfsq_search_enqueue(ix, reinterpret_cast<const float *>(dev_queries), nq, nprobe, topk,
+                                reinterpret_cast<uint32_t *>(dev_idx), reinterpret_cast<float *>(dev_dist), s);
+    VQ_API_END
+}
+
 // ---------------------------------------------------------------------------- TSVQ ----
 int vqhip_tsvq_build(const vqhip_dataset *ds, uint32_t max_depth, uint32_t cap, float *centroids, int32_t *left,
                      int32_t *right, int32_t *n_nodes) {

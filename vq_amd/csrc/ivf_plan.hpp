@@ -1,4 +1,5 @@
-// ivf_plan.hpp -- the per-query plan the inverted-file searches share (k_ivf.hip over PQ codes, k_ivfflat.hip over rows):
+// ivf_plan.hpp -- the per-query plan the inverted-file searches share (k_ivf.hip over PQ codes, k_ivfflat.hip over rows,
+// k_ivfsq.hip over SQ codes):
 // S(q) as ONE sequence of positions, probe slot 0's list first; pref[q][slot] the first position of a slot, seg[q][slot]
 // the first row (in list order) of its list.  Every including file gets its own copy (an anonymous namespace).
 #pragma once
@@ -6,6 +7,10 @@
 
 namespace vqhip {
 namespace {
+
+// the searches over rows and over SQ codes (k_ivfflat.hip, k_ivfsq.hip) switch per list and batch between two kernels
+constexpr uint32_t kIvffTileMin = 16;  // queries of a batch probing a list from which the tile kernel takes it
+constexpr uint32_t kIvffQC = 1024;     // query dimensions the scan kernels hold in LDS at a time
 
 // pref[q][0..nprobe] and seg[q][0..nprobe) of the block's query q = blockIdx.x (1024 threads); returns slot t's length
 __device__ __forceinline__ uint32_t ivf_plan_prefix(const uint32_t *__restrict__ probe, uint32_t nprobe, uint32_t nlist,

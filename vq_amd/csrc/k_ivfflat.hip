@@ -32,9 +32,6 @@
 namespace vqhip {
 namespace {
 
-constexpr uint32_t kIvffTileMin = 16;  // queries of a batch probing a list from which the tile kernel takes it
-constexpr uint32_t kIvffQC = 1024;     // query dimensions k_ivff_scan holds in LDS at a time
-
 template <typename RT>
 __device__ __forceinline__ float ivff_widen(RT v) {
     if constexpr (std::is_same<RT, uint16_t>::value) return (float)__builtin_bit_cast(_Float16, v);  // exact
@@ -389,23 +386,17 @@ int ivff_dispatch(int metric, int dtype, F &&f) {
 // cnt | fill | lstart | tstart of a batch: [nlist] + [nlist] + [nlist + 1] + [nlist + 1] words (cnt and fill zeroed per batch)
 size_t ivfflat_lists_bytes(uint32_t nlist) { return ((size_t)4 * nlist + 2) * 4; }
 
-// One batch of nb <= 1024 queries (queries [nb][d] f32, qnorm [nb] under the cosines) whose probe lists
-// (probe [nb][nprobe], launch_knn_search) are on the device.  X / rnorm / ids / off: the index in list order.  W
-// [nb][wstride] with wstride >= every |S(q)|; pref [nb][nprobe + 1], seg and inv [nb][nprobe], lists >=
-// ivfflat_lists_bytes(nlist), state >= knn_state_bytes(nb), cand >= topk_cand_bytes(nb); max_list: the rows of the
-// largest list.  Results [nb][topk] on the device.
-int launch_ivfflat_search(int metric, const void *X, int dtype, uint32_t d, const float *rnorm, const uint32_t *ids,
-                          const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
-                          const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
-                          float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state,
-                          unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream) {
-    if (nb == 0) return VQHIP_OK;
+// The stages of a batch before its distance passes, shared with k_ivfsq.hip: the batch's checks, the zeroed state, then
+// k_ivff_plan, k_ivff_lists and k_ivff_invert.  *p: where the distance passes find cnt / lstart / tstart and the key
+// range, and the grid of the tile kernel.
+int launch_ivff_plan(const uint32_t *off, uint32_t nlist, uint64_t max_list, const uint32_t *probe, uint32_t nb, uint32_t nprobe,
+                     uint32_t topk, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state, IvffPlan *p,
+                     hipStream_t stream) {
     if (nb > 1024) return fail(VQHIP_ERR_INVALID_INPUT, "a batch holds at most 1024 queries");
     if (nprobe == 0 || nprobe > 1024) return fail(VQHIP_ERR_INVALID_INPUT, "nprobe must be in [1, 1024]");
     if (topk == 0 || topk > 1024) return fail(VQHIP_ERR_INVALID_INPUT, "topk must be in [1, 1024]");
     uint32_t *cnt = lists, *fill = cnt + nlist, *lstart = fill + nlist, *tstart = lstart + nlist + 1;
     uint32_t *kmin = reinterpret_cast<uint32_t *>(state), *kmax = kmin + nb;
-    const TopkState st = topk_state(kmax + nb, nb);
     VQ_HIP(hipMemsetAsync(cnt, 0, (size_t)2 * nlist * 4, stream));
     VQ_HIP(hipMemsetAsync(kmin, 0xFF, (size_t)nb * 4, stream));
     VQ_HIP(hipMemsetAsync(kmax, 0, knn_state_bytes(nb) - (size_t)nb * 4, stream));
@@ -418,31 +409,56 @@ int launch_ivfflat_search(int metric, const void *X, int dtype, uint32_t d, cons
     // the tiles the batch can have: a list with tiles has at least kIvffTileMin pairs and one partial tile
     const uint64_t pairs = (uint64_t)nb * nprobe;
     const uint64_t tiles_max = std::min<uint64_t>(nlist, pairs / kIvffTileMin) + pairs / kKnnTQ;
+    // about eight workgroups per CU in all: columns of row tiles per query tile, at most the largest list's
+    const uint64_t nrt = std::max<uint64_t>(1, (max_list + kKnnTR - 1) / kKnnTR);
+    const uint64_t cols = tiles_max ? std::min<uint64_t>({nrt, 64, ((uint64_t)num_cus() * 8 + tiles_max - 1) / tiles_max}) : 0;
+    *p = IvffPlan{cnt, lstart, tstart, kmin, kmax, kmax + nb, tiles_max, cols};
+    return VQHIP_OK;
+}
+
+// The stages behind the distance passes: k_ivff_hist over W and the selection stage over IvffSource.
+int launch_ivff_select(const IvffPlan &p, const float *W, uint64_t wstride, const uint32_t *pref, const uint32_t *seg,
+                       const uint32_t *ids, uint32_t nb, uint32_t nprobe, uint32_t topk, unsigned long long *cand, uint32_t *idx_out,
+                       float *dist_out, hipStream_t stream) {
+    const TopkState st = topk_state(p.topk_ws, nb);
+    const IvffSource src{W, wstride, pref, seg, ids, nprobe, p.kmin, p.kmax};
+    hipLaunchKernelGGL(k_ivff_hist, dim3(src.blocks(), nb), dim3(256), 0, stream, W, wstride, pref, nprobe, p.kmin, p.kmax, st.hist);
+    VQ_LAUNCH_CHECK("k_ivff_hist");
+    return launch_topk_select(src, nb, topk, 0, st, cand, idx_out, dist_out, stream);
+}
+
+// One batch of nb <= 1024 queries (queries [nb][d] f32, qnorm [nb] under the cosines) whose probe lists
+// (probe [nb][nprobe], launch_knn_search) are on the device.  X / rnorm / ids / off: the index in list order.  W
+// [nb][wstride] with wstride >= every |S(q)|; pref [nb][nprobe + 1], seg and inv [nb][nprobe], lists >=
+// ivfflat_lists_bytes(nlist), state >= knn_state_bytes(nb), cand >= topk_cand_bytes(nb); max_list: the rows of the
+// largest list.  Results [nb][topk] on the device.
+int launch_ivfflat_search(int metric, const void *X, int dtype, uint32_t d, const float *rnorm, const uint32_t *ids,
+                          const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
+                          const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
+                          float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state,
+                          unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream) {
+    if (nb == 0) return VQHIP_OK;
+    IvffPlan p;
+    VQ_TRY(launch_ivff_plan(off, nlist, max_list, probe, nb, nprobe, topk, pref, seg, inv, lists, state, &p, stream));
     const uint64_t items = (wstride + chunk - 1) / chunk;
     VQ_TRY(ivff_dispatch(metric, dtype, [&](auto mtag, auto rtag) -> int {
         using RT = std::remove_const_t<std::remove_pointer_t<decltype(rtag)>>;
         constexpr int M = decltype(mtag)::value;
-        if (tiles_max > 0) {
-            // about eight workgroups per CU in all: columns of row tiles per query tile, at most the largest list's
-            const uint64_t nrt = std::max<uint64_t>(1, (max_list + kKnnTR - 1) / kKnnTR);
-            const uint64_t cols = std::min<uint64_t>({nrt, 64, ((uint64_t)num_cus() * 8 + tiles_max - 1) / tiles_max});
-            hipLaunchKernelGGL((k_ivff_tile<M, RT>), dim3((uint32_t)tiles_max, (uint32_t)cols), dim3(256), 0, stream, queries,
-                               reinterpret_cast<const RT *>(X), d, qnorm, rnorm, off, nlist, cnt, lstart, tstart, inv, pref, nprobe,
-                               wstride, W, kmin, kmax);
+        if (p.tiles_max > 0) {
+            hipLaunchKernelGGL((k_ivff_tile<M, RT>), dim3((uint32_t)p.tiles_max, (uint32_t)p.cols), dim3(256), 0, stream, queries,
+                               reinterpret_cast<const RT *>(X), d, qnorm, rnorm, off, nlist, p.cnt, p.lstart, p.tstart, inv, pref,
+                               nprobe, wstride, W, p.kmin, p.kmax);
             VQ_LAUNCH_CHECK("k_ivff_tile");
         }
         if (items > 0) {
             hipLaunchKernelGGL((k_ivff_scan<M, RT>), dim3((uint32_t)items, nb), dim3(256), 0, stream, queries,
-                               reinterpret_cast<const RT *>(X), d, qnorm, rnorm, probe, cnt, pref, seg, nprobe, chunk, wstride, W,
-                               kmin, kmax);
+                               reinterpret_cast<const RT *>(X), d, qnorm, rnorm, probe, p.cnt, pref, seg, nprobe, chunk, wstride, W,
+                               p.kmin, p.kmax);
             VQ_LAUNCH_CHECK("k_ivff_scan");
         }
         return VQHIP_OK;
     }));
-    const IvffSource src{W, wstride, pref, seg, ids, nprobe, kmin, kmax};
-    hipLaunchKernelGGL(k_ivff_hist, dim3(src.blocks(), nb), dim3(256), 0, stream, W, wstride, pref, nprobe, kmin, kmax, st.hist);
-    VQ_LAUNCH_CHECK("k_ivff_hist");
-    return launch_topk_select(src, nb, topk, 0, st, cand, idx_out, dist_out, stream);
+    return launch_ivff_select(p, W, wstride, pref, seg, ids, nb, nprobe, topk, cand, idx_out, dist_out, stream);
 }
 
 }  // namespace vqhip

@@ -17,6 +17,7 @@
 #include "kernels.hpp"
 #include "knn_tile.hpp"
 #include "range.hpp"
+#include "sq_decode.hpp"
 #include "topk.hpp"
 
 #include <type_traits>
@@ -25,28 +26,6 @@
 
 namespace vqhip {
 namespace {
-
-// the SQ decode rule for one byte: two roundings, never fused
-__device__ __forceinline__ float sq_val(uint32_t byte, float mn, float step) {
-    const float t = (float)byte * step;
-    return mn + t;
-}
-
-// f(t, v(row[t])) for t = 0 .. d-1 ascending; W4: the row starts on a 4-byte boundary and d % 4 == 0 (dword loads)
-template <bool W4, class F>
-__device__ __forceinline__ void sq_row_walk(const uint8_t *__restrict__ r, uint32_t d, float mn, float step, F &&f) {
-    if constexpr (W4) {
-        for (uint32_t t = 0; t < d; t += 4) {
-            const uint32_t w = *reinterpret_cast<const uint32_t *>(r + t);
-            f(t, sq_val(w & 0xffu, mn, step));
-            f(t + 1, sq_val((w >> 8) & 0xffu, mn, step));
-            f(t + 2, sq_val((w >> 16) & 0xffu, mn, step));
-            f(t + 3, sq_val(w >> 24, mn, step));
-        }
-    } else {
-        for (uint32_t t = 0; t < d; ++t) f(t, sq_val(r[t], mn, step));
-    }
-}
 
 // sqrtf(sum_t v(c_t)^2) per row, sequential from -0.0f (the row-norm chain of exact_distance_rt over the decoded row)
 template <bool W4>
@@ -233,14 +212,6 @@ __global__ __launch_bounds__(1024) void k_sq_rerank(const float *__restrict__ Q,
     }
     adc_bitonic<1024>(buf, len);
     for (uint32_t e = tid; e < topk; e += 1024) adc_emit(buf[e], true, 0, idx_out + (size_t)q * topk + e, dist_out + (size_t)q * topk + e);
-}
-
-// widest load the row loader may use: every row starts at base + i * d
-int sq_load_width(const uint8_t *C, uint32_t d) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(C);
-    if (d % 16 == 0 && a % 16 == 0) return 16;
-    if (d % 4 == 0 && a % 4 == 0) return 4;
-    return 1;
 }
 
 // METRIC as a template argument of F (a generic lambda called with a tag)

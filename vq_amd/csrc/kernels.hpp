@@ -297,6 +297,28 @@ int launch_ivfflat_search(int metric, const void *X, int dtype, uint32_t d, cons
                           const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
                           float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state,
                           unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream);
+// the stages of such a batch around its distance passes (k_ivfflat.hip), shared with the search over SQ codes: plan =
+// the batch's checks, the zeroed state, k_ivff_plan / _lists / _invert; select = k_ivff_hist and the selection stage.
+// IvffPlan: the per-list counts and starts (in lists), the key range (in state) and the tile kernel's grid.
+struct IvffPlan {
+    const uint32_t *cnt, *lstart, *tstart;
+    uint32_t *kmin, *kmax;
+    void *topk_ws;             // the selection stage's state, behind kmin / kmax
+    uint64_t tiles_max, cols;  // query tiles the batch can have; columns of row tiles per query tile (0: no tile kernel)
+};
+int launch_ivff_plan(const uint32_t *off, uint32_t nlist, uint64_t max_list, const uint32_t *probe, uint32_t nb, uint32_t nprobe,
+                     uint32_t topk, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state, IvffPlan *p,
+                     hipStream_t stream);
+int launch_ivff_select(const IvffPlan &p, const float *W, uint64_t wstride, const uint32_t *pref, const uint32_t *seg,
+                       const uint32_t *ids, uint32_t nb, uint32_t nprobe, uint32_t topk, unsigned long long *cand, uint32_t *idx_out,
+                       float *dist_out, hipStream_t stream);
+// inverted-file search over list-ordered SQ codes (k_ivfsq.hip): launch_ivfflat_search with the rows as C [n][d] u8,
+// v(c) = mn + (float)c * step decoded on the fly, rnorm [n] from launch_sq_norms over C (cosine only); the same workspaces
+int launch_ivfsq_search(int metric, const uint8_t *C, uint32_t d, float mn, float step, const float *rnorm, const uint32_t *ids,
+                        const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
+                        const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
+                        float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state,
+                        unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream);
 // exact k-NN search over resident rows and exact rerank of candidate lists (k_knn.hip); X [n][d] f32 (dtype 0) or f16
 // bits (dtype 1), rnorm [n] the rows' norms (cosine only, else unused)
 int launch_knn_norms(const void *X, int dtype, uint64_t n, uint32_t d, float *out, hipStream_t stream);

@@ -6,6 +6,7 @@
     python -m vq_amd.evalcli sq   [--seed 66 --dim 384 --levels 256]
     python -m vq_amd.evalcli bq   [--seed 66 --dim 384]
     python -m vq_amd.evalcli ivfflat [--seed 66 --dim 384 --nlist 256 --nprobe 1 8 32 --max-iters 10]
+    python -m vq_amd.evalcli ivfsq   [--seed 66 --dim 384 --nlist 256 --nprobe 1 8 32 --max-iters 10 --levels 256]
 
 For every sample count of `NUM_SAMPLES` it prints the reference's three lines -- training time,
 quantization time (host matrix in, f16 matrix out: what `quantize` per vector produces there)
@@ -21,6 +22,11 @@ mean squared error of dequantize(quantize(x)).
 `ivfflat` has no reference counterpart: it trains an IVFFlatIndex (nlist coarse centroids, Euclidean), adds every row
 and reports, per nprobe, recall@k of its search against the exact search (FlatIndex) of the same <= 1000 strided
 queries over all n rows, with the mean share of the rows a query scans.
+
+`ivfsq` is `ivfflat` for an IVFScalarIndex with ScalarQuantizer(0, 1, levels) over the same coarse centroids: per nprobe,
+recall@k against the exact search over the original rows (probing and quantization loss together), recall@k against the
+exact search over the dequantized rows (probing loss alone), and beside them IVFFlatIndex's recall over the original rows
+in the same lists.
 
 Data: i.i.d. Uniform[0,1) like common.rs:43-53, from the library's counter-based generator
 (the reference's StdRng stream is not reproducible outside Rust).
@@ -198,6 +204,63 @@ def _report_ivfflat(args):
         ix.close()
 
 
+def _report_ivfsq(args):
+    """recall@k of IVFScalarIndex.search against FlatIndex.search over the original and over the dequantized rows, per
+    nprobe, beside IVFFlatIndex's over the original rows in the same lists"""
+    from . import _lib
+    from .flat import FlatIndex
+    from .ivf_flat import IVFFlatIndex
+    from .ivf_scalar import IVFScalarIndex
+    from .sq import ScalarQuantizer
+
+    title = "IVF-Scalar Index Evaluation"
+    print(title)
+    print("=" * len(title))
+    sq = ScalarQuantizer(0.0, 1.0, args.levels)
+
+    def recall(got, want, k):
+        return float(np.mean([len(np.intersect1d(got[j], want[j])) / k for j in range(len(want))]))
+
+    for n in args.samples:
+        X = _lib.synth_uniform_host(n, args.dim, args.seed, 0)
+        nlist = min(args.nlist, n)
+        k = min(args.recall_k, n)
+        t0 = time.perf_counter()
+        ix = IVFScalarIndex.train(X, nlist, sq, args.max_iters, seed=args.seed)
+        train_ms = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        ix.add(X)
+        add_ms = (time.perf_counter() - t0) * 1e3
+        flat = IVFFlatIndex(ix.coarse_centroids, ix.distance)
+        flat.add_rows(ix.list_ids, X)
+        Q = X[::max(n // min(n, 1000), 1)]
+        exact = FlatIndex(X).search(Q, k)[0]
+        exact_deq = FlatIndex(sq.dequantize_batch(ix.codes)).search(Q, k)[0]
+        sizes = ix.list_sizes().astype(np.int64)
+        if not args.json:
+            print(f"\nSamples: {n}")
+            print(f"  Training time: {train_ms:.0f} ms")
+            print(f"  Add time: {add_ms:.0f} ms")
+            print(f"  Index bytes per row: {args.dim} (IVF-Flat f32: {4 * args.dim})")
+        for nprobe in args.nprobe:
+            p = min(nprobe, nlist)
+            t0 = time.perf_counter()
+            got = ix.search(Q, topk=k, nprobe=p)[0]
+            search_ms = (time.perf_counter() - t0) * 1e3
+            r, r_deq = recall(got, exact, k), recall(got, exact_deq, k)
+            r_flat = recall(flat.search(Q, topk=k, nprobe=p)[0], exact, k)
+            scanned = float(sizes[ix.probe(Q, p)].sum() / (len(Q) * n))
+            if args.json:
+                print(json.dumps({"n_samples": n, "n_dims": args.dim, "nlist": nlist, "nprobe": p, "levels": args.levels,
+                                  "training_time_ms": train_ms, "add_time_ms": add_ms, "search_time_ms": search_ms, "recall": r,
+                                  "recall_over_dequantized": r_deq, "ivfflat_recall": r_flat, "scanned_share": scanned}))
+            else:
+                print(f"  nprobe {p}: Recall@{k} {r:.4f} over the original rows, {r_deq:.4f} over the dequantized rows "
+                      f"(IVF-Flat {r_flat:.4f}), {100 * scanned:.1f}% of the rows scanned, {search_ms:.0f} ms")
+        ix.close()
+        flat.close()
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="vq_amd.evalcli")
     sub = ap.add_subparsers(dest="alg", required=True)
@@ -224,18 +287,24 @@ def main(argv=None) -> int:
             p.add_argument("--max-iters", type=int, default=MAX_ITERS)
         else:
             p.add_argument("--max-depth", type=int, default=5)
-    p = sub.add_parser("ivfflat")
-    p.add_argument("--seed", type=int, default=SEED)
-    p.add_argument("--dim", type=int, default=DIM)
-    p.add_argument("--samples", type=int, nargs="+", default=NUM_SAMPLES)
-    p.add_argument("--nlist", type=int, default=256)
-    p.add_argument("--nprobe", type=int, nargs="+", default=[1, 8, 32])
-    p.add_argument("--max-iters", type=int, default=MAX_ITERS)
-    p.add_argument("--recall-k", type=int, default=10)
-    p.add_argument("--json", action="store_true")
+    for name in ("ivfflat", "ivfsq"):
+        p = sub.add_parser(name)
+        p.add_argument("--seed", type=int, default=SEED)
+        p.add_argument("--dim", type=int, default=DIM)
+        p.add_argument("--samples", type=int, nargs="+", default=NUM_SAMPLES)
+        p.add_argument("--nlist", type=int, default=256)
+        p.add_argument("--nprobe", type=int, nargs="+", default=[1, 8, 32])
+        p.add_argument("--max-iters", type=int, default=MAX_ITERS)
+        p.add_argument("--recall-k", type=int, default=10)
+        p.add_argument("--json", action="store_true")
+        if name == "ivfsq":
+            p.add_argument("--levels", type=int, default=256)
     args = ap.parse_args(argv)
     if args.alg == "ivfflat":
         _report_ivfflat(args)
+        return 0
+    if args.alg == "ivfsq":
+        _report_ivfsq(args)
         return 0
     from . import TSVQ, BinaryQuantizer, Distance, ProductQuantizer, ScalarQuantizer
 
