@@ -954,16 +954,94 @@ class ScalarIndex {
     Distance distance_;
 };
 
+namespace detail {
+// What the three inverted-file indexes share over their C handles (H and its destroy / list_sizes / probe / search):
+// the shape, the add-side and probe-side checks, and the calls whose arguments are the same for every payload.
+template <class H, int (*Destroy)(H *), int (*ListSizes)(H *, std::uint64_t *),
+          int (*Probe)(H *, const float *, std::uint32_t, std::uint32_t, std::uint32_t *),
+          int (*Search)(H *, const float *, std::uint32_t, std::uint32_t, std::uint32_t, std::uint32_t *, float *)>
+class IvfIndex {
+   public:
+    std::size_t size() const { return n_; }
+    std::size_t nlist() const { return nlist_; }
+    std::size_t dim() const { return dim_; }
+    const char *distance_metric() const { return distance_.name(); }
+    std::vector<std::uint64_t> list_sizes() const {
+        std::vector<std::uint64_t> s(nlist_);
+        check(ListSizes(ix_.get(), s.data()));
+        return s;
+    }
+
+    struct Result {
+        std::vector<std::uint32_t> idx;  // [nq][topk]
+        std::vector<float> dist;         // [nq][topk]
+    };
+    // queries [nq][dim] -> the lists each query scans [nq][nprobe], nearest first
+    std::vector<std::uint32_t> probe(const float *queries, std::size_t nq, std::size_t nprobe) const {
+        check_probe(nprobe, nq);
+        std::vector<std::uint32_t> out(nq * nprobe);
+        if (nq) check(Probe(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, out.data()));
+        return out;
+    }
+    Result search(const float *queries, std::size_t nq, std::size_t topk, std::size_t nprobe) const {
+        check_probe(nprobe, nq);
+        if (topk == 0 || topk > 1024 || topk > n_) throw VqError::InvalidParameter("topk", "must be between 1 and min(n, 1024)");
+        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
+        if (nq)
+            check(Search(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, (std::uint32_t)topk, r.idx.data(), r.dist.data()));
+        return r;
+    }
+
+   protected:
+    static void check_nlist(std::size_t nlist) {
+        if (nlist == 0 || nlist > 65536) throw VqError::InvalidParameter("nlist", "must be between 1 and 65536");
+    }
+    static void check_dim(std::size_t dim) {
+        if (dim == 0 || dim > 0xFFFFFFFFu) throw VqError::InvalidParameter("dim", "must be between 1 and 2^32 - 1");
+    }
+    void adopt(H *ix, std::size_t nlist, std::size_t dim, Distance distance) {
+        ix_.reset(ix);
+        nlist_ = nlist;
+        dim_ = dim;
+        distance_ = distance;
+    }
+    void check_add(const std::uint32_t *list_ids, std::size_t n, const char *what) const {
+        if (n >= (std::size_t(1) << 32) - n_) throw VqError::InvalidParameter(what, "an index holds at most 2^32 - 1 rows");
+        for (std::size_t i = 0; i < n; ++i)
+            if (list_ids[i] >= nlist_) throw VqError::InvalidParameter("list_ids", "a list id is outside [0, nlist)");
+    }
+    // n rows are in (rc: the C add's result, VQHIP_OK when n == 0 and it was not called); the first new row id
+    std::size_t added(std::size_t n, int rc) {
+        check(rc);
+        const std::size_t first = n_;
+        n_ += n;
+        return first;
+    }
+    void check_probe(std::size_t nprobe, std::size_t nq) const {
+        if (nprobe == 0 || nprobe > 1024 || nprobe > nlist_)
+            throw VqError::InvalidParameter("nprobe", "must be between 1 and min(nlist, 1024)");
+        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
+    }
+    struct Del {
+        void operator()(H *p) const { (void)Destroy(p); }
+    };
+    std::unique_ptr<H, Del> ix_;
+    std::size_t n_ = 0, nlist_ = 0, dim_ = 0;
+    Distance distance_;
+};
+}  // namespace detail
+
 // Inverted-file index over PQ codes (include/vqhip.h, vqhip_ivfpq_*): coarse centroids [nlist][dim], codebooks
 // [m][k][sub_dim], rows added as (list id, codes).  search scans only the nprobe lists nearest to a query and gives
 // (row id, ADC distance) pairs [nq][topk], nearest first; slots past the probed rows hold (0xFFFFFFFF, +inf).  The
 // constructor, add and list_sizes need no device; the arguments are checked before the device is touched.
-class IVFPQIndex {
+class IVFPQIndex
+    : public detail::IvfIndex<vqhip_ivfpq, vqhip_ivfpq_destroy, vqhip_ivfpq_list_sizes, vqhip_ivfpq_probe, vqhip_ivfpq_search> {
    public:
     // residual: the codes of a row in list l quantise x - C[l] (include/vqhip.h, VQHIP_IVF_RESIDUAL)
     IVFPQIndex(const float *coarse, std::size_t nlist, const float *codebooks, std::size_t m, std::size_t k, std::size_t sub_dim,
                Distance distance = Distance(), bool residual = false) {
-        if (nlist == 0 || nlist > 65536) throw VqError::InvalidParameter("nlist", "must be between 1 and 65536");
+        check_nlist(nlist);
         if (m == 0 || k == 0 || sub_dim == 0) throw VqError::InvalidParameter("codebooks", "m, k and sub_dim must be positive");
         if (k > 65536 || m * k > 38400) throw VqError::InvalidParameter("codebooks", "m * k must be at most 38400");
         if (m * sub_dim > 0xFFFFFFFFu) throw VqError::InvalidParameter("codebooks", "dim must be below 2^32");
@@ -972,74 +1050,26 @@ class IVFPQIndex {
         vqhip_ivfpq *ix = nullptr;
         detail::check(vqhip_ivfpq_create_ex(coarse, (std::uint32_t)nlist, codebooks, (std::uint32_t)m, (std::uint32_t)k,
                                             (std::uint32_t)sub_dim, (int)distance.kind(), residual ? VQHIP_IVF_RESIDUAL : 0u, &ix));
-        ix_.reset(ix);
-        nlist_ = nlist;
+        adopt(ix, nlist, m * sub_dim, distance);
         m_ = m;
         k_ = k;
-        dim_ = m * sub_dim;
-        distance_ = distance;
         residual_ = residual;
     }
-    std::size_t size() const { return n_; }
     bool residual() const { return residual_; }
-    std::size_t nlist() const { return nlist_; }
-    std::size_t dim() const { return dim_; }
-    const char *distance_metric() const { return distance_.name(); }
 
     // rows appended in order: list_ids [n] < nlist, codes [n][m] < k (one byte per code up to k = 256, u16 above: the
     // library's code width); returns the first new row id
     std::size_t add(const std::uint32_t *list_ids, const void *codes, std::size_t n) {
-        if (n >= (std::size_t(1) << 32) - n_) throw VqError::InvalidParameter("codes", "an index holds at most 2^32 - 1 rows");
-        for (std::size_t i = 0; i < n; ++i)
-            if (list_ids[i] >= nlist_) throw VqError::InvalidParameter("list_ids", "a list id is outside [0, nlist)");
+        check_add(list_ids, n, "codes");
         for (std::size_t e = 0; e < n * m_; ++e) {
             const std::uint32_t c = k_ <= 256 ? static_cast<const std::uint8_t *>(codes)[e] : static_cast<const std::uint16_t *>(codes)[e];
             if (c >= k_) throw VqError::InvalidParameter("codes", "a code is outside [0, k)");
         }
-        const std::size_t first = n_;
-        if (n) detail::check(vqhip_ivfpq_add(ix_.get(), list_ids, codes, n));
-        n_ += n;
-        return first;
-    }
-    std::vector<std::uint64_t> list_sizes() const {
-        std::vector<std::uint64_t> s(nlist_);
-        detail::check(vqhip_ivfpq_list_sizes(ix_.get(), s.data()));
-        return s;
-    }
-
-    struct Result {
-        std::vector<std::uint32_t> idx;  // [nq][topk]
-        std::vector<float> dist;         // [nq][topk]
-    };
-    // queries [nq][dim] -> the lists each query scans [nq][nprobe], nearest first
-    std::vector<std::uint32_t> probe(const float *queries, std::size_t nq, std::size_t nprobe) const {
-        check_probe(nprobe, nq);
-        std::vector<std::uint32_t> out(nq * nprobe);
-        if (nq) detail::check(vqhip_ivfpq_probe(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, out.data()));
-        return out;
-    }
-    Result search(const float *queries, std::size_t nq, std::size_t topk, std::size_t nprobe) const {
-        check_probe(nprobe, nq);
-        if (topk == 0 || topk > 1024 || topk > n_) throw VqError::InvalidParameter("topk", "must be between 1 and min(n, 1024)");
-        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
-        if (nq)
-            detail::check(vqhip_ivfpq_search(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, (std::uint32_t)topk,
-                                             r.idx.data(), r.dist.data()));
-        return r;
+        return added(n, n ? vqhip_ivfpq_add(ix_.get(), list_ids, codes, n) : VQHIP_OK);
     }
 
    private:
-    struct Del {
-        void operator()(vqhip_ivfpq *p) const { (void)vqhip_ivfpq_destroy(p); }
-    };
-    void check_probe(std::size_t nprobe, std::size_t nq) const {
-        if (nprobe == 0 || nprobe > 1024 || nprobe > nlist_)
-            throw VqError::InvalidParameter("nprobe", "must be between 1 and min(nlist, 1024)");
-        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
-    }
-    std::unique_ptr<vqhip_ivfpq, Del> ix_;
-    std::size_t n_ = 0, nlist_ = 0, m_ = 0, k_ = 0, dim_ = 0;
-    Distance distance_;
+    std::size_t m_ = 0, k_ = 0;
     bool residual_ = false;
 };
 
@@ -1048,76 +1078,28 @@ class IVFPQIndex {
 // metric) to the rows of the nprobe lists nearest to a query and gives (row id, distance) pairs [nq][topk], nearest
 // first; slots past the probed rows hold (0xFFFFFFFF, +inf); with nprobe == nlist it is FlatIndex's search.  The
 // constructor, add and list_sizes need no device; the arguments are checked before the device is touched.
-class IVFFlatIndex {
+class IVFFlatIndex : public detail::IvfIndex<vqhip_ivfflat, vqhip_ivfflat_destroy, vqhip_ivfflat_list_sizes, vqhip_ivfflat_probe,
+                                             vqhip_ivfflat_search> {
    public:
     enum class Rows { F32 = 0, F16 = 1 };
     IVFFlatIndex(const float *coarse, std::size_t nlist, std::size_t dim, Distance distance = Distance(), Rows rows = Rows::F32) {
-        if (nlist == 0 || nlist > 65536) throw VqError::InvalidParameter("nlist", "must be between 1 and 65536");
-        if (dim == 0 || dim > 0xFFFFFFFFu) throw VqError::InvalidParameter("dim", "must be between 1 and 2^32 - 1");
+        check_nlist(nlist);
+        check_dim(dim);
         vqhip_ivfflat *ix = nullptr;
         detail::check(vqhip_ivfflat_create(coarse, (std::uint32_t)nlist, (std::uint32_t)dim, (int)rows, (int)distance.kind(), &ix));
-        ix_.reset(ix);
-        nlist_ = nlist;
-        dim_ = dim;
+        adopt(ix, nlist, dim, distance);
         rows_ = rows;
-        distance_ = distance;
     }
-    std::size_t size() const { return n_; }
-    std::size_t nlist() const { return nlist_; }
-    std::size_t dim() const { return dim_; }
     Rows rows() const { return rows_; }
-    const char *distance_metric() const { return distance_.name(); }
 
     // rows appended in order: list_ids [n] < nlist, rows [n][dim] in the index's row type; returns the first new row id
     std::size_t add(const std::uint32_t *list_ids, const void *rows, std::size_t n) {
-        if (n >= (std::size_t(1) << 32) - n_) throw VqError::InvalidParameter("rows", "an index holds at most 2^32 - 1 rows");
-        for (std::size_t i = 0; i < n; ++i)
-            if (list_ids[i] >= nlist_) throw VqError::InvalidParameter("list_ids", "a list id is outside [0, nlist)");
-        const std::size_t first = n_;
-        if (n) detail::check(vqhip_ivfflat_add(ix_.get(), list_ids, rows, n));
-        n_ += n;
-        return first;
-    }
-    std::vector<std::uint64_t> list_sizes() const {
-        std::vector<std::uint64_t> s(nlist_);
-        detail::check(vqhip_ivfflat_list_sizes(ix_.get(), s.data()));
-        return s;
-    }
-
-    struct Result {
-        std::vector<std::uint32_t> idx;  // [nq][topk]
-        std::vector<float> dist;         // [nq][topk]
-    };
-    // queries [nq][dim] -> the lists each query scans [nq][nprobe], nearest first
-    std::vector<std::uint32_t> probe(const float *queries, std::size_t nq, std::size_t nprobe) const {
-        check_probe(nprobe, nq);
-        std::vector<std::uint32_t> out(nq * nprobe);
-        if (nq) detail::check(vqhip_ivfflat_probe(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, out.data()));
-        return out;
-    }
-    Result search(const float *queries, std::size_t nq, std::size_t topk, std::size_t nprobe) const {
-        check_probe(nprobe, nq);
-        if (topk == 0 || topk > 1024 || topk > n_) throw VqError::InvalidParameter("topk", "must be between 1 and min(n, 1024)");
-        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
-        if (nq)
-            detail::check(vqhip_ivfflat_search(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, (std::uint32_t)topk,
-                                               r.idx.data(), r.dist.data()));
-        return r;
+        check_add(list_ids, n, "rows");
+        return added(n, n ? vqhip_ivfflat_add(ix_.get(), list_ids, rows, n) : VQHIP_OK);
     }
 
    private:
-    struct Del {
-        void operator()(vqhip_ivfflat *p) const { (void)vqhip_ivfflat_destroy(p); }
-    };
-    void check_probe(std::size_t nprobe, std::size_t nq) const {
-        if (nprobe == 0 || nprobe > 1024 || nprobe > nlist_)
-            throw VqError::InvalidParameter("nprobe", "must be between 1 and min(nlist, 1024)");
-        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
-    }
-    std::unique_ptr<vqhip_ivfflat, Del> ix_;
-    std::size_t n_ = 0, nlist_ = 0, dim_ = 0;
     Rows rows_ = Rows::F32;
-    Distance distance_;
 };
 
 // Inverted-file index over SQ codes (include/vqhip.h, vqhip_ivfsq_*): coarse centroids [nlist][dim], a ScalarQuantizer, rows
@@ -1126,46 +1108,29 @@ class IVFFlatIndex {
 // pairs [nq][topk], nearest first; slots past the probed rows hold (0xFFFFFFFF, +inf).  Every result equals IVFFlatIndex
 // over quantizer.dequantize(codes) in the same lists; with nprobe == nlist it is ScalarIndex's search.  The constructor,
 // add_codes, codes and list_sizes need no device; the arguments are checked before the device is touched.
-class IVFScalarIndex {
+class IVFScalarIndex
+    : public detail::IvfIndex<vqhip_ivfsq, vqhip_ivfsq_destroy, vqhip_ivfsq_list_sizes, vqhip_ivfsq_probe, vqhip_ivfsq_search> {
    public:
     IVFScalarIndex(const float *coarse, std::size_t nlist, std::size_t dim, ScalarQuantizer quantizer, Distance distance = Distance())
         : quantizer_(quantizer) {
-        if (nlist == 0 || nlist > 65536) throw VqError::InvalidParameter("nlist", "must be between 1 and 65536");
-        if (dim == 0 || dim > 0xFFFFFFFFu) throw VqError::InvalidParameter("dim", "must be between 1 and 2^32 - 1");
+        check_nlist(nlist);
+        check_dim(dim);
         vqhip_ivfsq *ix = nullptr;
         detail::check(vqhip_ivfsq_create(quantizer_.min(), quantizer_.max(), (std::uint32_t)quantizer_.levels(), coarse,
                                          (std::uint32_t)nlist, (std::uint32_t)dim, (int)distance.kind(), &ix));
-        ix_.reset(ix);
-        nlist_ = nlist;
-        dim_ = dim;
-        distance_ = distance;
+        adopt(ix, nlist, dim, distance);
     }
-    std::size_t size() const { return n_; }
-    std::size_t nlist() const { return nlist_; }
-    std::size_t dim() const { return dim_; }
     const ScalarQuantizer &quantizer() const { return quantizer_; }
-    const char *distance_metric() const { return distance_.name(); }
 
     // rows appended in order: list_ids [n] < nlist, codes [n][dim] (every byte value is legal); returns the first new row id
     std::size_t add_codes(const std::uint32_t *list_ids, const std::uint8_t *codes, std::size_t n) {
         check_add(list_ids, n, "codes");
-        const std::size_t first = n_;
-        if (n) detail::check(vqhip_ivfsq_add_codes(ix_.get(), list_ids, codes, n));
-        n_ += n;
-        return first;
+        return added(n, n ? vqhip_ivfsq_add_codes(ix_.get(), list_ids, codes, n) : VQHIP_OK);
     }
     // rows [n][dim] f32, encoded on the device (the quantizer's codes); only the codes are kept
     std::size_t add_rows(const std::uint32_t *list_ids, const float *rows, std::size_t n) {
         check_add(list_ids, n, "rows");
-        const std::size_t first = n_;
-        if (n) detail::check(vqhip_ivfsq_add_rows(ix_.get(), list_ids, rows, n));
-        n_ += n;
-        return first;
-    }
-    std::vector<std::uint64_t> list_sizes() const {
-        std::vector<std::uint64_t> s(nlist_);
-        detail::check(vqhip_ivfsq_list_sizes(ix_.get(), s.data()));
-        return s;
+        return added(n, n ? vqhip_ivfsq_add_rows(ix_.get(), list_ids, rows, n) : VQHIP_OK);
     }
     // the codes [n][dim], in add order
     std::vector<std::uint8_t> codes() const {
@@ -1174,45 +1139,8 @@ class IVFScalarIndex {
         return out;
     }
 
-    struct Result {
-        std::vector<std::uint32_t> idx;  // [nq][topk]
-        std::vector<float> dist;         // [nq][topk]
-    };
-    // queries [nq][dim] -> the lists each query scans [nq][nprobe], nearest first
-    std::vector<std::uint32_t> probe(const float *queries, std::size_t nq, std::size_t nprobe) const {
-        check_probe(nprobe, nq);
-        std::vector<std::uint32_t> out(nq * nprobe);
-        if (nq) detail::check(vqhip_ivfsq_probe(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, out.data()));
-        return out;
-    }
-    Result search(const float *queries, std::size_t nq, std::size_t topk, std::size_t nprobe) const {
-        check_probe(nprobe, nq);
-        if (topk == 0 || topk > 1024 || topk > n_) throw VqError::InvalidParameter("topk", "must be between 1 and min(n, 1024)");
-        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
-        if (nq)
-            detail::check(vqhip_ivfsq_search(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, (std::uint32_t)topk,
-                                             r.idx.data(), r.dist.data()));
-        return r;
-    }
-
    private:
-    struct Del {
-        void operator()(vqhip_ivfsq *p) const { (void)vqhip_ivfsq_destroy(p); }
-    };
-    void check_add(const std::uint32_t *list_ids, std::size_t n, const char *what) const {
-        if (n >= (std::size_t(1) << 32) - n_) throw VqError::InvalidParameter(what, "an index holds at most 2^32 - 1 rows");
-        for (std::size_t i = 0; i < n; ++i)
-            if (list_ids[i] >= nlist_) throw VqError::InvalidParameter("list_ids", "a list id is outside [0, nlist)");
-    }
-    void check_probe(std::size_t nprobe, std::size_t nq) const {
-        if (nprobe == 0 || nprobe > 1024 || nprobe > nlist_)
-            throw VqError::InvalidParameter("nprobe", "must be between 1 and min(nlist, 1024)");
-        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
-    }
     ScalarQuantizer quantizer_;
-    std::unique_ptr<vqhip_ivfsq, Del> ix_;
-    std::size_t n_ = 0, nlist_ = 0, dim_ = 0;
-    Distance distance_;
 };
 
 // analogue of vq::get_simd_backend (src/lib.rs): names the device backend

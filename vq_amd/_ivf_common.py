@@ -1,0 +1,249 @@
+"""What ``IVFPQIndex``, ``IVFFlatIndex`` and ``IVFScalarIndex`` share: the coarse centroids and list ids, the checks of
+queries, ``nprobe`` and ``topk``, probe / search / rerank over the device handle, and the readers of the index files.
+A subclass keeps its payload (codes or rows), its add paths, ``_handle``, ``close`` and its file layout."""
+from __future__ import annotations
+
+import operator
+
+import numpy as np
+
+from . import _lib
+from .distance import Distance
+from .errors import DimensionMismatch, InvalidParameter
+
+MAX_NLIST = 65536
+MAX_PROBE = 1024
+MAX_TOPK = 1024
+PAD_ID = 0xFFFFFFFF
+
+
+def _count(v, name: str) -> int:
+    try:
+        return operator.index(v)
+    except TypeError:
+        raise InvalidParameter(name, f"must be an integer, got {v!r}") from None
+
+
+def _nearest_lists(coarse, X, metric: int) -> np.ndarray:
+    """(n,) uint32: each row's nearest coarse centroid (the reference's nearest-centroid rule: a PQ encode with one
+    subspace of nlist centroids)"""
+    enc = _lib.PQEncoder(coarse[None, :, :], metric)
+    try:
+        lists, _ = enc.encode(X, want_f16=False)
+    finally:
+        enc.close()
+    return np.asarray(lists).reshape(-1).astype(np.uint32)
+
+
+def _check_distance(distance) -> Distance:
+    if distance is None:
+        distance = Distance.euclidean()
+    if not isinstance(distance, Distance):
+        raise InvalidParameter("distance", f"expected a Distance, got {type(distance).__name__}")
+    return distance
+
+
+def _coarse_array(coarse_centroids) -> np.ndarray:
+    c = np.ascontiguousarray(coarse_centroids, dtype=np.float32)
+    if c.ndim != 2:
+        raise InvalidParameter("coarse_centroids", "must have shape (nlist, dim)")
+    return c
+
+
+def _check_nlist(nlist: int) -> None:
+    if not 1 <= nlist <= MAX_NLIST:
+        raise InvalidParameter("nlist", f"must be between 1 and {MAX_NLIST}, got {nlist}")
+
+
+def _check_coarse(coarse_centroids) -> np.ndarray:
+    """coarse f32 (nlist, dim) after the checks of an index whose dimension is the centroids' own"""
+    c = _coarse_array(coarse_centroids)
+    _check_nlist(c.shape[0])
+    if c.shape[1] == 0:
+        raise InvalidParameter("coarse_centroids", "dimension must be at least 1")
+    return c
+
+
+def _train_coarse(X, nlist: int, max_iters: int, distance: Distance, seed: int) -> np.ndarray:
+    """the coarse quantizer: k-means of whole rows (a ProductQuantizer with one subspace of nlist centroids)"""
+    from .pq import ProductQuantizer
+
+    return ProductQuantizer(X, 1, nlist, max_iters, distance, seed).codebooks[0]
+
+
+class _Reader:
+    """the blocks of an index file, each checked for truncation"""
+
+    def __init__(self, f):
+        self._f = f
+
+    def block(self, count: int, dtype, what: str) -> np.ndarray:
+        dt = np.dtype(dtype)
+        raw = self._f.read(count * dt.itemsize)
+        if len(raw) != count * dt.itemsize:
+            raise ValueError(f"truncated {what}")
+        return np.frombuffer(raw, dtype=dt)
+
+    def lists(self, n: int) -> np.ndarray:
+        return self.block(n, "<u4", "list ids")
+
+    def end(self, what: str) -> None:
+        if self._f.read(1):
+            raise ValueError(f"trailing bytes after the {what}")
+
+
+def _check_file_lists(lists: np.ndarray, nlist: int) -> None:
+    if lists.size and int(lists.max()) >= nlist:
+        raise ValueError(f"corrupt index: a list id is outside [0, {nlist})")
+
+
+class IVFIndexBase:
+    """coarse centroids (nlist, dim) + distance + the list id of every added row; `_ix` is the device handle or None"""
+
+    def _init_lists(self, coarse: np.ndarray, distance: Distance) -> None:
+        self._distance = distance
+        self._coarse = coarse
+        self._lists = np.empty(0, np.uint32)
+        self._ix = None
+
+    # -- shape ------------------------------------------------------------------------------
+    @property
+    def nlist(self) -> int:
+        return self._coarse.shape[0]
+
+    @property
+    def dim(self) -> int:
+        return self._coarse.shape[1]
+
+    @property
+    def distance(self) -> Distance:
+        return self._distance
+
+    @property
+    def coarse_centroids(self) -> np.ndarray:
+        return self._coarse
+
+    @property
+    def list_ids(self) -> np.ndarray:
+        """(n,) uint32: the list of every row, in row order"""
+        return self._lists
+
+    def __len__(self) -> int:
+        return self._lists.shape[0]
+
+    def list_sizes(self) -> np.ndarray:
+        """(nlist,) uint64: rows per list"""
+        return np.bincount(self._lists, minlength=self.nlist).astype(np.uint64)
+
+    # -- build ------------------------------------------------------------------------------
+    def _add_rows_2d(self, X) -> np.ndarray:
+        """the rows given to `add` as float32 (n, dim)"""
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim == 1:
+            X = X[None, :]
+        if X.ndim != 2:
+            raise ValueError("expected a 2D array (n, dim)")
+        if X.shape[1] != self.dim:
+            raise DimensionMismatch(self.dim, X.shape[1])
+        return X
+
+    def add(self, X) -> np.ndarray:
+        """assign each row of X (n, dim) to its nearest coarse centroid (the reference's nearest-centroid rule, on the
+        float32 values of X) and append it with `add_rows`; returns the new row ids"""
+        X = self._add_rows_2d(X)
+        if X.shape[0] == 0:
+            return np.empty(0, np.uint32)
+        return self.add_rows(_nearest_lists(self._coarse, X, self._distance.metric), X)
+
+    def _check_list_ids(self, lid: np.ndarray) -> None:
+        if lid.size and (lid.dtype.kind not in "iu" or int(lid.min()) < 0 or int(lid.max()) >= self.nlist):
+            raise InvalidParameter("list_ids", f"must be integers in [0, {self.nlist})")
+
+    def _check_room(self, n_new: int, what: str) -> None:
+        if len(self) + n_new >= 1 << 32:
+            raise InvalidParameter(what, "an index holds at most 2^32 - 1 rows")
+
+    def _appended(self, lid: np.ndarray) -> np.ndarray:
+        n0 = len(self)
+        self._lists = np.concatenate([self._lists, lid])
+        return np.arange(n0, n0 + lid.shape[0], dtype=np.uint32)
+
+    # -- search -----------------------------------------------------------------------------
+    def _queries(self, queries) -> np.ndarray:
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2:
+            raise ValueError("expected a 2D array (nq, dim)")
+        if q.shape[1] != self.dim:
+            raise DimensionMismatch(self.dim, q.shape[1])
+        return q
+
+    def _nprobe(self, nprobe) -> int:
+        p = _count(nprobe, "nprobe")
+        if not 1 <= p <= min(self.nlist, MAX_PROBE):
+            raise InvalidParameter("nprobe", f"must be between 1 and min(nlist, 1024), got {p}")
+        return p
+
+    def _topk(self, topk) -> int:
+        t = _count(topk, "topk")
+        if not 1 <= t <= min(len(self), MAX_TOPK):
+            raise InvalidParameter("topk", f"must be between 1 and min(n, 1024), got {t}")
+        return t
+
+    def probe(self, queries, nprobe: int = 8) -> np.ndarray:
+        """(nq, nprobe) uint32: the lists each query scans, nearest first"""
+        q = self._queries(queries)
+        p = self._nprobe(nprobe)
+        if q.shape[0] == 0:
+            return np.empty((0, p), np.uint32)
+        return self._handle().probe(q, p)
+
+    def search(self, queries, topk: int = 10, nprobe: int = 8, *, rerank=None, candidates: int | None = None):
+        """(nq, dim) float32 queries -> (indices uint32 (nq, topk), distances float32 (nq, topk)), nearest first; slots
+        past the probed rows hold 0xFFFFFFFF / +inf.  rerank: a FlatIndex or a ScalarIndex over the same rows -- the search
+        then returns `candidates` hits per query (default 4 topk, at most 1024 and n) and the exact rerank of the real
+        ones"""
+        q = self._queries(queries)
+        p = self._nprobe(nprobe)
+        t = self._topk(topk)
+        if rerank is not None:
+            return self._search_rerank(q, t, p, rerank, candidates)
+        if q.shape[0] == 0:
+            return np.empty((0, t), np.uint32), np.empty((0, t), np.float32)
+        return self._handle().search(q, p, t)
+
+    def _search_rerank(self, q, topk: int, nprobe: int, rerank, candidates):
+        from .flat import rerank_candidates
+
+        c = rerank_candidates(len(self), self.dim, topk, rerank, candidates)
+        nq = q.shape[0]
+        idx = np.full((nq, topk), PAD_ID, np.uint32)
+        dist = np.full((nq, topk), np.inf, np.float32)
+        if nq == 0:
+            return idx, dist
+        hits, _ = self._handle().search(q, nprobe, c)
+        real = (hits != PAD_ID).sum(axis=1)  # (padding follows every real hit)
+        full = real == c
+        if full.any():
+            idx[full], dist[full] = rerank.rerank(q[full], hits[full], topk)
+        for j in np.flatnonzero((real > 0) & ~full):  # a query with fewer hits keeps its padding
+            r = int(real[j])
+            t = min(topk, r)
+            idx[j, :t], dist[j, :t] = (a[0] for a in rerank.rerank(q[j:j + 1], hits[j:j + 1, :r], t))
+        return idx, dist
+
+    def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int, nprobe: int = 8) -> None:
+        """device pointers: queries [nq][dim] f32, results [nq][topk] uint32 / f32; asynchronous on the current stream"""
+        p = self._nprobe(nprobe)
+        t = self._topk(topk)
+        n_q = _count(nq, "nq")
+        if n_q < 0 or n_q >= 1 << 32:
+            raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
+        self._handle().search_device(int(dev_queries), n_q, p, t, int(dev_idx), int(dev_dist))
+
+    def close(self) -> None:
+        """release the device handle (the next probe or search builds it again)"""
+        if self._ix is not None:
+            self._ix.close()
+            self._ix = None

@@ -964,11 +964,44 @@ class SQIndex(Handle):
         return idx, dist
 
 
-class IVFPQ(Handle):
+class _IVFHandle(Handle):
+    """What the three inverted-file handles share: the calls that differ only in the symbol prefix.  A subclass sets
+    `_prefix` and `nlist`."""
+
+    _prefix = ""
+
+    def _fn(self, name: str):
+        return getattr(load(), f"{self._prefix}_{name}")
+
+    def list_sizes(self) -> np.ndarray:
+        out = np.empty(self.nlist, np.uint64)
+        check(self._fn("list_sizes")(self.raw, ptr(out, _u64p)))
+        return out
+
+    def probe(self, q: np.ndarray, nprobe: int) -> np.ndarray:
+        nq = q.shape[0]
+        out = np.empty((nq, nprobe), np.uint32)
+        check(self._fn("probe")(self.raw, ptr(q, _f32p), nq, int(nprobe), ptr(out, _u32p)))
+        return out
+
+    def search(self, q: np.ndarray, nprobe: int, topk: int):
+        nq = q.shape[0]
+        idx = np.empty((nq, topk), np.uint32)
+        dist = np.empty((nq, topk), np.float32)
+        check(self._fn("search")(self.raw, ptr(q, _f32p), nq, int(nprobe), int(topk), ptr(idx, _u32p), ptr(dist, _f32p)))
+        return idx, dist
+
+    def search_device(self, dev_queries: int, nq: int, nprobe: int, topk: int, dev_idx: int, dev_dist: int):
+        check(self._fn("search_device")(self.raw, C.c_void_p(dev_queries), int(nq), int(nprobe), int(topk),
+                                        C.c_void_p(dev_idx), C.c_void_p(dev_dist)))
+
+
+class IVFPQ(_IVFHandle):
     """vqhip_ivfpq: inverted-file PQ index -- coarse centroids, codebooks, rows in lists (k_ivf.hip).  Create, add and
     list_sizes are host-only; the device state is built by the first probe or search.  flags: IVF_RESIDUAL for lists
     whose codes quantise x - C[list]."""
 
+    _prefix = "vqhip_ivfpq"
     _destroy = "vqhip_ivfpq_destroy"
 
     def __init__(self, coarse, codebooks, metric: int, flags: int = 0):
@@ -997,35 +1030,13 @@ class IVFPQ(Handle):
                                       C.byref(metric)))
         return int(n.value), int(nlist.value), int(dim.value), int(m.value), int(k.value), int(metric.value)
 
-    def list_sizes(self) -> np.ndarray:
-        out = np.empty(self.nlist, np.uint64)
-        check(load().vqhip_ivfpq_list_sizes(self.raw, ptr(out, _u64p)))
-        return out
 
-    def probe(self, q: np.ndarray, nprobe: int) -> np.ndarray:
-        nq = q.shape[0]
-        out = np.empty((nq, nprobe), np.uint32)
-        check(load().vqhip_ivfpq_probe(self.raw, ptr(q, _f32p), nq, int(nprobe), ptr(out, _u32p)))
-        return out
-
-    def search(self, q: np.ndarray, nprobe: int, topk: int):
-        nq = q.shape[0]
-        idx = np.empty((nq, topk), np.uint32)
-        dist = np.empty((nq, topk), np.float32)
-        check(load().vqhip_ivfpq_search(self.raw, ptr(q, _f32p), nq, int(nprobe), int(topk), ptr(idx, _u32p),
-                                        ptr(dist, _f32p)))
-        return idx, dist
-
-    def search_device(self, dev_queries: int, nq: int, nprobe: int, topk: int, dev_idx: int, dev_dist: int):
-        check(load().vqhip_ivfpq_search_device(self.raw, C.c_void_p(dev_queries), int(nq), int(nprobe), int(topk),
-                                               C.c_void_p(dev_idx), C.c_void_p(dev_dist)))
-
-
-class IVFFlat(Handle):
+class IVFFlat(_IVFHandle):
     """vqhip_ivfflat: inverted-file flat index -- coarse centroids, f32 or f16 rows in lists, exact distances over the
     probed lists (k_ivfflat.hip).  Create, add, info and list_sizes are host-only; the device state is built by the first
     probe or search."""
 
+    _prefix = "vqhip_ivfflat"
     _destroy = "vqhip_ivfflat_destroy"
 
     def __init__(self, coarse, metric: int, dtype=np.float32):
@@ -1047,35 +1058,13 @@ class IVFFlat(Handle):
         check(load().vqhip_ivfflat_info(self.raw, C.byref(n), C.byref(nlist), C.byref(dim), C.byref(dtype), C.byref(metric)))
         return int(n.value), int(nlist.value), int(dim.value), int(dtype.value), int(metric.value)
 
-    def list_sizes(self) -> np.ndarray:
-        out = np.empty(self.nlist, np.uint64)
-        check(load().vqhip_ivfflat_list_sizes(self.raw, ptr(out, _u64p)))
-        return out
 
-    def probe(self, q: np.ndarray, nprobe: int) -> np.ndarray:
-        nq = q.shape[0]
-        out = np.empty((nq, nprobe), np.uint32)
-        check(load().vqhip_ivfflat_probe(self.raw, ptr(q, _f32p), nq, int(nprobe), ptr(out, _u32p)))
-        return out
-
-    def search(self, q: np.ndarray, nprobe: int, topk: int):
-        nq = q.shape[0]
-        idx = np.empty((nq, topk), np.uint32)
-        dist = np.empty((nq, topk), np.float32)
-        check(load().vqhip_ivfflat_search(self.raw, ptr(q, _f32p), nq, int(nprobe), int(topk), ptr(idx, _u32p),
-                                          ptr(dist, _f32p)))
-        return idx, dist
-
-    def search_device(self, dev_queries: int, nq: int, nprobe: int, topk: int, dev_idx: int, dev_dist: int):
-        check(load().vqhip_ivfflat_search_device(self.raw, C.c_void_p(dev_queries), int(nq), int(nprobe), int(topk),
-                                                 C.c_void_p(dev_idx), C.c_void_p(dev_dist)))
-
-
-class IVFSQ(Handle):
+class IVFSQ(_IVFHandle):
     """vqhip_ivfsq: inverted-file scalar index -- coarse centroids, a ScalarQuantizer's u8 codes in lists, exact distances
     to the decoded rows over the probed lists (k_ivfsq.hip).  Create, add_codes, codes, info and list_sizes are host-only;
     add_rows encodes on the device; the device state is built by the first probe or search."""
 
+    _prefix = "vqhip_ivfsq"
     _destroy = "vqhip_ivfsq_destroy"
 
     def __init__(self, coarse, mn: float, mx: float, levels: int, metric: int):
@@ -1102,32 +1091,10 @@ class IVFSQ(Handle):
                                       C.byref(levels)))
         return int(n.value), int(nlist.value), int(dim.value), int(metric.value), float(mn.value), float(mx.value), int(levels.value)
 
-    def list_sizes(self) -> np.ndarray:
-        out = np.empty(self.nlist, np.uint64)
-        check(load().vqhip_ivfsq_list_sizes(self.raw, ptr(out, _u64p)))
-        return out
-
     def codes(self) -> np.ndarray:
         out = np.empty((self.info()[0], self.dim), np.uint8)
         check(load().vqhip_ivfsq_codes(self.raw, ptr(out, _u8p)))
         return out
-
-    def probe(self, q: np.ndarray, nprobe: int) -> np.ndarray:
-        nq = q.shape[0]
-        out = np.empty((nq, nprobe), np.uint32)
-        check(load().vqhip_ivfsq_probe(self.raw, ptr(q, _f32p), nq, int(nprobe), ptr(out, _u32p)))
-        return out
-
-    def search(self, q: np.ndarray, nprobe: int, topk: int):
-        nq = q.shape[0]
-        idx = np.empty((nq, topk), np.uint32)
-        dist = np.empty((nq, topk), np.float32)
-        check(load().vqhip_ivfsq_search(self.raw, ptr(q, _f32p), nq, int(nprobe), int(topk), ptr(idx, _u32p), ptr(dist, _f32p)))
-        return idx, dist
-
-    def search_device(self, dev_queries: int, nq: int, nprobe: int, topk: int, dev_idx: int, dev_dist: int):
-        check(load().vqhip_ivfsq_search_device(self.raw, C.c_void_p(dev_queries), int(nq), int(nprobe), int(topk),
-                                               C.c_void_p(dev_idx), C.c_void_p(dev_dist)))
 
 
 def dequantize_f16(f16) -> np.ndarray:

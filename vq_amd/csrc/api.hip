@@ -3457,81 +3457,63 @@ int vqhip_binary_search_device(vqhip_binary *b, const void *dev_queries, uint32_
 
 }  // extern "C"
 
-// ------------------------------------------------------------------ inverted-file PQ (k_ivf.hip) ----
-// Host state: the coarse centroids, the codebooks, and every added row's list id and codes in row order.  The device
-// state -- a flat index over the centroids, the codebooks, and the rows in list order (off / ids / codes) -- is built on
-// the current device by the first probe or search, and the list order is rebuilt there after an add (a host counting
-// sort, O(n) per rebuild, uploaded once).  A residual index (VQHIP_IVF_RESIDUAL) also keeps the coarse centroids on the
-// device for its tables.
-struct vqhip_ivfpq {
+// ------------------------------------------------------------------ inverted lists: the shared host layer ----
+// What vqhip_ivfpq, vqhip_ivfflat and vqhip_ivfsq have in common.  Host state: the coarse centroids and every added
+// row's list id and payload (PQ codes, f32 / f16 elements or SQ codes) in add order.  The device state -- a flat index
+// over the centroids and the rows in list order (off / ids / payload) -- is built on the current device by the first
+// probe or search and rebuilt there after an add: a host counting sort gives the order (O(n) per rebuild), and the
+// payload goes up through a staging buffer of at most kIvfflatStage bytes, list order gathered a piece at a time.
+constexpr size_t kIvfflatStage = 64u << 20;
+
+struct IvfLists {
     HandleSync sync;
-    uint32_t nlist = 0, m = 0, k = 0, sd = 0, dim = 0;
-    uint32_t flags = 0;  // VQHIP_IVF_RESIDUAL: codes of x - C[list]
+    uint32_t nlist = 0, dim = 0;
     int metric = VQHIP_EUCLIDEAN;
-    std::vector<float> coarse, cb;    // [nlist][dim], [m][k][sd]
-    std::vector<uint32_t> row_list;   // [n] list id of each row
-    std::vector<uint8_t> row_codes;   // [n][m] codes, code_bytes(k) each
-    std::vector<uint64_t> sizes;      // [nlist] rows per list
-    uint64_t n = 0;
+    size_t row_b = 0;                // bytes of one row's payload (each index sets it at create)
+    std::vector<float> coarse;       // [nlist][dim]
+    std::vector<uint32_t> row_list;  // [n] list id of each row
+    std::vector<uint8_t> payload;    // [n][row_b] in add order
+    std::vector<uint64_t> sizes;     // [nlist] rows per list
+    uint64_t n = 0, max_list = 0;
     bool dirty = true;                     // rows added since the last upload
     int dev = -1;                          // the device of the index's state: current at create (-1: create saw no device;
                                            // then the first probe or search takes the current one)
     std::vector<uint64_t> largest_prefix;  // [nlist + 1] sums of the largest list sizes (the bound on |S(q)|)
     vqhip_flat *flat = nullptr;            // the coarse centroids on the device
-    DevBuf d_cb, d_off, d_ids, d_codes, d_coarse;
-    DevBuf q, probe, probe_dist, lut, bounds, pref, seg, W, state, cand, idx, out, rtab, rmm;  // per-call workspaces
-    ~vqhip_ivfpq() { delete flat; }
+    DevBuf d_off, d_ids, d_payload;        // (d_payload is the index's own buffer: the loaders' alignment rests on its base)
+    DevBuf q, probe, probe_dist, pref, seg, W, state, cand, idx, out;  // per-call workspaces
+    ~IvfLists() { delete flat; }
 };
 
-static int ivfpq_check_probe(const vqhip_ivfpq *ix, uint32_t nprobe) {
+// the checks every create shares (each create keeps its own between them, in its documented order) and the shared fields
+static int ivf_check_lists(const void *coarse, uint32_t nlist) {
+    if (!coarse) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (nlist == 0 || nlist > 65536) return fail(VQHIP_ERR_INVALID_INPUT, "nlist %u must be in [1, 65536]", nlist);
+    return VQHIP_OK;
+}
+static int ivf_check_metric(int metric) {
+    if (metric < VQHIP_SQUARED_EUCLIDEAN || metric > VQHIP_COSINE_UNCLAMPED) return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
+    return VQHIP_OK;
+}
+static void ivf_init(IvfLists *ix, const float *coarse, uint32_t nlist, uint32_t dim, int metric, size_t row_b) {
+    ix->nlist = nlist;
+    ix->dim = dim;
+    ix->metric = metric;
+    ix->row_b = row_b;
+    ix->coarse.assign(coarse, coarse + (size_t)nlist * dim);
+    ix->sizes.assign(nlist, 0);
+    int ndev = 0, cur = -1;  // (the device is named, not touched: the state is built by the first probe or search)
+    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && hipGetDevice(&cur) == hipSuccess) ix->dev = cur;
+}
+
+static int ivf_check_probe(const IvfLists *ix, uint32_t nprobe) {
     const uint32_t hi = std::min<uint32_t>(ix->nlist, 1024);
     if (nprobe == 0 || nprobe > hi) return fail(VQHIP_ERR_INVALID_INPUT, "nprobe %u must be in [1, min(nlist, 1024)] = [1, %u]", nprobe, hi);
     return VQHIP_OK;
 }
 
-// the device state, current with the host's rows (enqueued on s and waited for: the host vectors are the copies' sources)
-static int ivfpq_ready(vqhip_ivfpq *ix, hipStream_t s) {
-    if (!ix->flat) {
-        VQ_TRY(flat_create(ix->coarse.data(), hipMemcpyHostToDevice, ix->nlist, ix->dim, 0, ix->metric, &ix->flat));
-        VQ_TRY(ix->d_cb.alloc(ix->cb.size() * 4));
-        VQ_HIP(hipMemcpyAsync(ix->d_cb.p, ix->cb.data(), ix->cb.size() * 4, hipMemcpyHostToDevice, s));
-        if (ix->flags & VQHIP_IVF_RESIDUAL) {
-            VQ_TRY(ix->d_coarse.alloc(ix->coarse.size() * 4));
-            VQ_HIP(hipMemcpyAsync(ix->d_coarse.p, ix->coarse.data(), ix->coarse.size() * 4, hipMemcpyHostToDevice, s));
-        }
-    }
-    if (ix->dirty) {
-        const uint32_t cw = code_bytes(ix->k);
-        const size_t row_b = (size_t)ix->m * cw;
-        std::vector<uint32_t> off(ix->nlist + 1, 0), at(ix->nlist), ids(ix->n);
-        std::vector<uint8_t> codes(ix->n * row_b);
-        for (uint32_t l = 0; l < ix->nlist; ++l) off[l + 1] = off[l] + (uint32_t)ix->sizes[l];
-        std::copy(off.begin(), off.end() - 1, at.begin());
-        for (uint64_t i = 0; i < ix->n; ++i) {  // ascending row ids within each list
-            const uint32_t p = at[ix->row_list[i]]++;
-            ids[p] = (uint32_t)i;
-            memcpy(codes.data() + (size_t)p * row_b, ix->row_codes.data() + (size_t)i * row_b, row_b);
-        }
-        VQ_TRY(ix->d_off.alloc(off.size() * 4));
-        VQ_TRY(ix->d_ids.alloc(ids.size() * 4));
-        VQ_TRY(ix->d_codes.alloc(codes.size()));
-        VQ_HIP(hipMemcpyAsync(ix->d_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, s));
-        if (ix->n) {
-            VQ_HIP(hipMemcpyAsync(ix->d_ids.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, s));
-            VQ_HIP(hipMemcpyAsync(ix->d_codes.p, codes.data(), codes.size(), hipMemcpyHostToDevice, s));
-        }
-        VQ_HIP(hipStreamSynchronize(s));
-        std::vector<uint64_t> sorted(ix->sizes);
-        std::sort(sorted.begin(), sorted.end(), std::greater<uint64_t>());
-        ix->largest_prefix.assign(ix->nlist + 1, 0);
-        for (uint32_t l = 0; l < ix->nlist; ++l) ix->largest_prefix[l + 1] = ix->largest_prefix[l] + sorted[l];
-        ix->dirty = false;
-    }
-    return VQHIP_OK;
-}
-
 // every device call runs on the index's device
-static int ivfpq_device(vqhip_ivfpq *ix) {
+static int ivf_device(IvfLists *ix) {
     int cur = 0;
     VQ_HIP(hipGetDevice(&cur));
     if (ix->dev < 0) ix->dev = cur;
@@ -3539,63 +3521,212 @@ static int ivfpq_device(vqhip_ivfpq *ix) {
     return VQHIP_OK;
 }
 
+// An add: the checks (before anything is stored), `store` appending the n rows to ix->payload -- or leaving it as it
+// was and returning the error -- and the bookkeeping once they are there.
+template <class F>
+static int ivf_add(IvfLists *ix, const uint32_t *list_ids, const void *data, uint64_t n, F &&store) {
+    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (n == 0) return VQHIP_OK;
+    if (!list_ids || !data) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);
+    if (n >= (1ull << 32) - ix->n)
+        return fail(VQHIP_ERR_INVALID_INPUT, "the index would hold %llu + %llu rows: at most 2^32 - 1", (unsigned long long)ix->n,
+                    (unsigned long long)n);
+    for (uint64_t i = 0; i < n; ++i)
+        if (list_ids[i] >= ix->nlist)
+            return fail(VQHIP_ERR_INVALID_INPUT, "list id %u of row %llu is outside [0, %u)", list_ids[i], (unsigned long long)i, ix->nlist);
+    VQ_TRY(store());
+    ix->row_list.insert(ix->row_list.end(), list_ids, list_ids + n);
+    for (uint64_t i = 0; i < n; ++i) ++ix->sizes[list_ids[i]];
+    ix->n += n;
+    ix->dirty = true;
+    return VQHIP_OK;
+}
+static int ivf_append(IvfLists *ix, const void *data, uint64_t n) {
+    const uint8_t *p = reinterpret_cast<const uint8_t *>(data);
+    ix->payload.insert(ix->payload.end(), p, p + (size_t)n * ix->row_b);
+    return VQHIP_OK;
+}
+
+static int ivf_list_sizes(IvfLists *ix, uint64_t *sizes) {
+    if (!ix || !sizes) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);
+    memcpy(sizes, ix->sizes.data(), ix->sizes.size() * 8);
+    return VQHIP_OK;
+}
+
+// The device state, current with the host's rows (enqueued on s and waited for: host buffers are the copies' sources).
+// `first` runs once, after the coarse centroids are resident (an index's own tables); `resident` after every upload of a
+// non-empty payload (what an index derives from it on the device).
+template <class First, class Resident>
+static int ivf_ready(IvfLists *ix, hipStream_t s, First &&first, Resident &&resident) {
+    if (!ix->flat) {
+        VQ_TRY(flat_create(ix->coarse.data(), hipMemcpyHostToDevice, ix->nlist, ix->dim, 0, ix->metric, &ix->flat));
+        VQ_TRY(first());
+    }
+    if (!ix->dirty) return VQHIP_OK;
+    const size_t row_b = ix->row_b;
+    std::vector<uint32_t> off(ix->nlist + 1, 0), at(ix->nlist), ids(ix->n);
+    for (uint32_t l = 0; l < ix->nlist; ++l) off[l + 1] = off[l] + (uint32_t)ix->sizes[l];
+    std::copy(off.begin(), off.end() - 1, at.begin());
+    for (uint64_t i = 0; i < ix->n; ++i) ids[at[ix->row_list[i]]++] = (uint32_t)i;  // ascending row ids within each list
+    VQ_TRY(ix->d_off.alloc(off.size() * 4));
+    VQ_TRY(ix->d_ids.alloc(ids.size() * 4));
+    VQ_TRY(ix->d_payload.alloc((size_t)ix->n * row_b));
+    VQ_HIP(hipMemcpyAsync(ix->d_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, s));
+    if (ix->n) {
+        VQ_HIP(hipMemcpyAsync(ix->d_ids.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, s));
+        const uint64_t per = std::max<uint64_t>(1, kIvfflatStage / row_b);
+        std::vector<uint8_t> stage((size_t)std::min<uint64_t>(per, ix->n) * row_b);
+        for (uint64_t p0 = 0; p0 < ix->n; p0 += per) {
+            const uint64_t pn = std::min<uint64_t>(per, ix->n - p0);
+            for (uint64_t p = 0; p < pn; ++p) memcpy(stage.data() + (size_t)p * row_b, ix->payload.data() + (size_t)ids[p0 + p] * row_b, row_b);
+            VQ_HIP(hipMemcpyAsync(ix->d_payload.as<uint8_t>() + (size_t)p0 * row_b, stage.data(), (size_t)pn * row_b, hipMemcpyHostToDevice, s));
+            VQ_HIP(hipStreamSynchronize(s));  // (the staging buffer is filled again)
+        }
+        VQ_TRY(resident());
+    }
+    VQ_HIP(hipStreamSynchronize(s));
+    std::vector<uint64_t> sorted(ix->sizes);
+    std::sort(sorted.begin(), sorted.end(), std::greater<uint64_t>());
+    ix->max_list = sorted[0];
+    ix->largest_prefix.assign(ix->nlist + 1, 0);
+    for (uint32_t l = 0; l < ix->nlist; ++l) ix->largest_prefix[l + 1] = ix->largest_prefix[l] + sorted[l];
+    ix->dirty = false;
+    return VQHIP_OK;
+}
+static int ivf_no_hook() { return VQHIP_OK; }
+
 // queries_dev [nq][dim] f32 -> probe lists [nq][nprobe] on the device
-static int ivfpq_probe_enqueue(vqhip_ivfpq *ix, const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t *lists_dev,
-                               hipStream_t s) {
+static int ivf_probe_enqueue(IvfLists *ix, const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t *lists_dev, hipStream_t s) {
     VQ_TRY(ix->probe_dist.ensure((size_t)nq * nprobe * 4));
     return flat_search_enqueue(ix->flat, queries_dev, nq, nprobe, lists_dev, ix->probe_dist.as<float>(), s);
 }
 
-// queries_dev [nq][dim] f32 -> [nq][topk] results on the device, enqueued on s.  Batches of queries bound the workspace:
-// the distances of a batch (4 bytes per position of S(q), sized by the nprobe largest lists) under 1 GB -- or one query's
-// when that alone is more -- its tables under 256 MB (a residual index: nprobe tables per query; one query's when that
-// alone is more), at most 1024 queries.
-static int ivfpq_search_enqueue(vqhip_ivfpq *ix, const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk,
-                                uint32_t *idx_dev, float *dist_dev, hipStream_t s) {
-    const bool residual = (ix->flags & VQHIP_IVF_RESIDUAL) != 0;
-    const uint64_t wstride = std::max<uint64_t>(ix->largest_prefix[nprobe], 1);
-    const uint64_t tab_b = (uint64_t)ix->m * ix->k * 4 * (residual ? nprobe : 1);
-    uint64_t qb = std::min<uint64_t>({(uint64_t)nq, 1024, std::max<uint64_t>(1, (1ull << 30) / (4 * wstride)),
-                                      std::max<uint64_t>(1, (256ull << 20) / tab_b)});
-    const uint32_t nb_max = (uint32_t)qb;
-    VQ_TRY(ix->probe.ensure((size_t)nb_max * nprobe * 4));
-    if (residual) {
-        VQ_TRY(ix->rtab.ensure(ivf_rtab_bytes(nb_max, nprobe, ix->m, ix->k)));
-        VQ_TRY(ix->rmm.ensure(ivf_rmm_bytes(nb_max, nprobe)));
-    } else {
-        VQ_TRY(ix->lut.ensure((size_t)nb_max * tab_b));
-    }
-    VQ_TRY(ix->bounds.ensure((size_t)nb_max * 2 * 4));
-    VQ_TRY(ix->pref.ensure((size_t)nb_max * (nprobe + 1) * 4));
-    VQ_TRY(ix->seg.ensure((size_t)nb_max * nprobe * 4));
-    VQ_TRY(ix->W.ensure((size_t)nb_max * wstride * 4));
-    VQ_TRY(ix->state.ensure(topk_state_bytes(nb_max)));
-    VQ_TRY(ix->cand.ensure(topk_cand_bytes(nb_max)));
-    // expected positions per query: the mean list size times nprobe
-    const uint64_t per_q = std::max<uint64_t>(1, (uint64_t)((double)ix->n * nprobe / ix->nlist));
-    for (uint32_t q0 = 0; q0 < nq; q0 += nb_max) {
-        const uint32_t nb = std::min(nb_max, nq - q0);
-        const float *Q = queries_dev + (size_t)q0 * ix->dim;
-        VQ_TRY(ivfpq_probe_enqueue(ix, Q, nb, nprobe, ix->probe.as<uint32_t>(), s));
-        if (residual) {
-            VQ_TRY(launch_ivf_rsearch(ix->d_codes.as<uint8_t>(), ix->d_ids.as<uint32_t>(), ix->d_off.as<uint32_t>(),
-                                      ix->d_coarse.as<float>(), ix->nlist, ix->d_cb.as<float>(), ix->m, ix->k, ix->sd, ix->metric, Q,
-                                      ix->probe.as<uint32_t>(), nb, nprobe, topk, ivf_rchunk((uint64_t)nb * per_q, ix->k), wstride,
-                                      ix->rtab.as<float>(), ix->rmm.as<float>(), ix->W.as<float>(), ix->pref.as<uint32_t>(),
-                                      ix->seg.as<uint32_t>(), ix->bounds.as<float>(), ix->state.p, ix->cand.as<unsigned long long>(),
-                                      idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s));
-            continue;
-        }
-        VQ_TRY(launch_adc_lut(Q, nb, ix->m, ix->k, ix->sd, ix->d_cb.as<float>(), ix->metric, ix->lut.as<float>(),
-                              ix->bounds.as<float>(), s));
-        VQ_TRY(launch_ivf_search(ix->d_codes.as<uint8_t>(), ix->d_ids.as<uint32_t>(), ix->d_off.as<uint32_t>(), ix->nlist, ix->m, ix->k,
-                                 ix->metric, ix->lut.as<float>(), ix->probe.as<uint32_t>(), nb, nprobe, topk,
-                                 ivf_chunk((uint64_t)nb * per_q), wstride, ix->W.as<float>(), ix->pref.as<uint32_t>(),
-                                 ix->seg.as<uint32_t>(), ix->bounds.as<float>(), ix->state.p,
-                                 ix->cand.as<unsigned long long>(), idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s));
-    }
+// Batches of queries bound a search's workspace: the distances of a batch (4 bytes per position of S(q), sized by the
+// nprobe largest lists) under 1 GB -- or one query's when that alone is more -- its tables (query_bytes each, if any)
+// under 256 MB -- or one query's -- and at most 1024 queries.  Sizes the workspaces every index has, `state` apart.
+struct IvfBatch {
+    uint64_t wstride;  // floats of W per query
+    uint32_t nb_max;   // queries per batch
+    uint64_t per_q;    // expected positions per query: the mean list size times nprobe
+};
+static int ivf_batch(IvfLists *ix, uint32_t nq, uint32_t nprobe, uint64_t query_bytes, IvfBatch *b) {
+    b->wstride = std::max<uint64_t>(ix->largest_prefix[nprobe], 1);
+    uint64_t qb = std::min<uint64_t>({(uint64_t)nq, 1024, std::max<uint64_t>(1, (1ull << 30) / (4 * b->wstride))});
+    if (query_bytes) qb = std::min(qb, std::max<uint64_t>(1, (256ull << 20) / query_bytes));
+    b->nb_max = (uint32_t)qb;
+    b->per_q = std::max<uint64_t>(1, (uint64_t)((double)ix->n * nprobe / ix->nlist));
+    VQ_TRY(ix->probe.ensure((size_t)b->nb_max * nprobe * 4));
+    VQ_TRY(ix->pref.ensure((size_t)b->nb_max * (nprobe + 1) * 4));
+    VQ_TRY(ix->seg.ensure((size_t)b->nb_max * nprobe * 4));
+    VQ_TRY(ix->W.ensure((size_t)b->nb_max * b->wstride * 4));
+    VQ_TRY(ix->cand.ensure(topk_cand_bytes(b->nb_max)));
     return VQHIP_OK;
 }
+
+// The front of every probe and search (T: an index with ready(s)): the checks in their order, the index's device, the
+// calling thread's stream, the device state -- then body(in, s).  topk NULL: a probe.
+template <class T, class F>
+static int ivf_enter(T *ix, bool args, uint32_t nq, uint32_t nprobe, const uint32_t *topk, F &&body) {
+    if (!ix || !args) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);  // (n changes under add: read under the lock)
+    VQ_TRY(ivf_check_probe(ix, nprobe));
+    if (topk) VQ_TRY(check_topk(ix->n, *topk));
+    if (nq == 0) return VQHIP_OK;
+    VQ_TRY(require_gfx950());
+    VQ_TRY(ivf_device(ix));
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    VQ_TRY(ix->ready(s));
+    return body(in, s);
+}
+
+// the three entry points of every index, over its ready(s) and search_enqueue(...)
+template <class T>
+static int ivf_probe(T *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t *lists_out) {
+    return ivf_enter(ix, queries && lists_out, nq, nprobe, nullptr, [&](Entry &in, hipStream_t s) {
+        return host_search(in, s, ix->q, ix->idx, nullptr, queries, nq, ix->dim, nprobe, lists_out, nullptr, [&] {
+            return ivf_probe_enqueue(ix, ix->q.template as<float>(), nq, nprobe, ix->idx.template as<uint32_t>(), s);
+        });
+    });
+}
+template <class T>
+static int ivf_search(T *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_out, float *dist_out) {
+    return ivf_enter(ix, queries && idx_out && dist_out, nq, nprobe, &topk, [&](Entry &in, hipStream_t s) {
+        return host_search(in, s, ix->q, ix->idx, &ix->out, queries, nq, ix->dim, topk, idx_out, dist_out, [&] {
+            return ix->search_enqueue(ix->q.template as<float>(), nq, nprobe, topk, ix->idx.template as<uint32_t>(),
+                                      ix->out.template as<float>(), s);
+        });
+    });
+}
+template <class T>
+static int ivf_search_device(T *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk, void *dev_idx, void *dev_dist) {
+    return ivf_enter(ix, dev_queries && dev_idx && dev_dist, nq, nprobe, &topk, [&](Entry &, hipStream_t s) {
+        return ix->search_enqueue(reinterpret_cast<const float *>(dev_queries), nq, nprobe, topk, reinterpret_cast<uint32_t *>(dev_idx),
+                                  reinterpret_cast<float *>(dev_dist), s);
+    });
+}
+
+// ------------------------------------------------------------------ inverted-file PQ (k_ivf.hip) ----
+// IvfLists whose payload is PQ codes (m codes of code_bytes(k) each), and the codebooks.  A residual index
+// (VQHIP_IVF_RESIDUAL) also keeps the coarse centroids on the device for its tables.
+struct vqhip_ivfpq : IvfLists {
+    uint32_t m = 0, k = 0, sd = 0;
+    uint32_t flags = 0;     // VQHIP_IVF_RESIDUAL: codes of x - C[list]
+    std::vector<float> cb;  // [m][k][sd]
+    DevBuf d_cb, d_coarse;
+    DevBuf lut, bounds, rtab, rmm;  // per-call workspaces
+
+    int ready(hipStream_t s) {
+        return ivf_ready(this, s, [&] {
+            VQ_TRY(d_cb.alloc(cb.size() * 4));
+            VQ_HIP(hipMemcpyAsync(d_cb.p, cb.data(), cb.size() * 4, hipMemcpyHostToDevice, s));
+            if (flags & VQHIP_IVF_RESIDUAL) {
+                VQ_TRY(d_coarse.alloc(coarse.size() * 4));
+                VQ_HIP(hipMemcpyAsync(d_coarse.p, coarse.data(), coarse.size() * 4, hipMemcpyHostToDevice, s));
+            }
+            return VQHIP_OK;
+        }, ivf_no_hook);
+    }
+
+    // queries_dev [nq][dim] f32 -> [nq][topk] results on the device, enqueued on s, in ivf_batch's batches: a query's
+    // tables are one ADC table, nprobe of them in a residual index
+    int search_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
+                       hipStream_t s) {
+        const bool residual = (flags & VQHIP_IVF_RESIDUAL) != 0;
+        const uint64_t tab_b = (uint64_t)m * k * 4 * (residual ? nprobe : 1);
+        IvfBatch b;
+        VQ_TRY(ivf_batch(this, nq, nprobe, tab_b, &b));
+        if (residual) {
+            VQ_TRY(rtab.ensure(ivf_rtab_bytes(b.nb_max, nprobe, m, k)));
+            VQ_TRY(rmm.ensure(ivf_rmm_bytes(b.nb_max, nprobe)));
+        } else {
+            VQ_TRY(lut.ensure((size_t)b.nb_max * tab_b));
+        }
+        VQ_TRY(bounds.ensure((size_t)b.nb_max * 2 * 4));
+        VQ_TRY(state.ensure(topk_state_bytes(b.nb_max)));
+        for (uint32_t q0 = 0; q0 < nq; q0 += b.nb_max) {
+            const uint32_t nb = std::min(b.nb_max, nq - q0);
+            const float *Q = queries_dev + (size_t)q0 * dim;
+            VQ_TRY(ivf_probe_enqueue(this, Q, nb, nprobe, probe.as<uint32_t>(), s));
+            if (residual) {
+                VQ_TRY(launch_ivf_rsearch(d_payload.as<uint8_t>(), d_ids.as<uint32_t>(), d_off.as<uint32_t>(), d_coarse.as<float>(), nlist,
+                                          d_cb.as<float>(), m, k, sd, metric, Q, probe.as<uint32_t>(), nb, nprobe, topk,
+                                          ivf_rchunk((uint64_t)nb * b.per_q, k), b.wstride, rtab.as<float>(), rmm.as<float>(), W.as<float>(),
+                                          pref.as<uint32_t>(), seg.as<uint32_t>(), bounds.as<float>(), state.p,
+                                          cand.as<unsigned long long>(), idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s));
+                continue;
+            }
+            VQ_TRY(launch_adc_lut(Q, nb, m, k, sd, d_cb.as<float>(), metric, lut.as<float>(), bounds.as<float>(), s));
+            VQ_TRY(launch_ivf_search(d_payload.as<uint8_t>(), d_ids.as<uint32_t>(), d_off.as<uint32_t>(), nlist, m, k, metric, lut.as<float>(),
+                                     probe.as<uint32_t>(), nb, nprobe, topk, ivf_chunk((uint64_t)nb * b.per_q), b.wstride, W.as<float>(),
+                                     pref.as<uint32_t>(), seg.as<uint32_t>(), bounds.as<float>(), state.p, cand.as<unsigned long long>(),
+                                     idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s));
+        }
+        return VQHIP_OK;
+    }
+};
 
 extern "C" {
 
@@ -3610,27 +3741,20 @@ int vqhip_ivfpq_create_ex(const float *coarse, uint32_t nlist, const float *code
     if (!out) return fail(VQHIP_ERR_NULL_PTR, "out is NULL");
     *out = nullptr;
     if (flags & ~(uint32_t)VQHIP_IVF_RESIDUAL) return fail(VQHIP_ERR_INVALID_INPUT, "unknown flag bits 0x%x", flags & ~(uint32_t)VQHIP_IVF_RESIDUAL);
-    if (!coarse || !codebooks) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    if (nlist == 0 || nlist > 65536) return fail(VQHIP_ERR_INVALID_INPUT, "nlist %u must be in [1, 65536]", nlist);
+    VQ_TRY(ivf_check_lists(codebooks ? coarse : nullptr, nlist));
     if (m == 0 || k == 0 || sub_dim == 0) return fail(VQHIP_ERR_INVALID_INPUT, "m, k and sub_dim must be positive");
     if (k > kMaxCentroids) return fail(VQHIP_ERR_UNSUPPORTED, "k=%u > 65536: codes are at most two bytes per subspace", k);
     if ((uint64_t)m * sub_dim >= (1ull << 32)) return fail(VQHIP_ERR_INVALID_INPUT, "dim = m * sub_dim must be below 2^32");
-    if (metric < VQHIP_SQUARED_EUCLIDEAN || metric > VQHIP_COSINE_UNCLAMPED) return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
+    VQ_TRY(ivf_check_metric(metric));
     if (vq_is_cos(metric)) return fail(VQHIP_ERR_UNSUPPORTED, "cosine distance is not a sum over subspaces: no ADC form");
     if (!adc_table_fits(m, k)) return fail_adc_table(m, k);
     std::unique_ptr<vqhip_ivfpq> ix(new vqhip_ivfpq());
-    ix->nlist = nlist;
+    ivf_init(ix.get(), coarse, nlist, m * sub_dim, metric, (size_t)m * code_bytes(k));
     ix->m = m;
     ix->k = k;
     ix->sd = sub_dim;
-    ix->dim = m * sub_dim;
-    ix->metric = metric;
     ix->flags = flags;
-    ix->coarse.assign(coarse, coarse + (size_t)nlist * ix->dim);
     ix->cb.assign(codebooks, codebooks + (size_t)m * k * sub_dim);
-    ix->sizes.assign(nlist, 0);
-    int ndev = 0, cur = -1;  // (the device is named, not touched: the state is built by the first probe or search)
-    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && hipGetDevice(&cur) == hipSuccess) ix->dev = cur;
     *out = ix.release();
     return VQHIP_OK;
     VQ_API_END
@@ -3643,25 +3767,10 @@ int vqhip_ivfpq_destroy(vqhip_ivfpq *ix) {
 
 int vqhip_ivfpq_add(vqhip_ivfpq *ix, const uint32_t *list_ids, const void *codes, uint64_t n) {
     VQ_API_BEGIN
-    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    if (n == 0) return VQHIP_OK;
-    if (!list_ids || !codes) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    Entry in(ix->sync);
-    if (n >= (1ull << 32) - ix->n)
-        return fail(VQHIP_ERR_INVALID_INPUT, "the index would hold %llu + %llu rows: at most 2^32 - 1", (unsigned long long)ix->n,
-                    (unsigned long long)n);
-    for (uint64_t i = 0; i < n; ++i)
-        if (list_ids[i] >= ix->nlist)
-            return fail(VQHIP_ERR_INVALID_INPUT, "list id %u of row %llu is outside [0, %u)", list_ids[i], (unsigned long long)i, ix->nlist);
-    VQ_TRY(check_codes(reinterpret_cast<const uint8_t *>(codes), n * ix->m, ix->k));
-    const size_t row_b = (size_t)ix->m * code_bytes(ix->k);
-    ix->row_list.insert(ix->row_list.end(), list_ids, list_ids + n);
-    const uint8_t *c = reinterpret_cast<const uint8_t *>(codes);
-    ix->row_codes.insert(ix->row_codes.end(), c, c + n * row_b);
-    for (uint64_t i = 0; i < n; ++i) ++ix->sizes[list_ids[i]];
-    ix->n += n;
-    ix->dirty = true;
-    return VQHIP_OK;
+    return ivf_add(ix, list_ids, codes, n, [&] {
+        VQ_TRY(check_codes(reinterpret_cast<const uint8_t *>(codes), n * ix->m, ix->k));
+        return ivf_append(ix, codes, n);
+    });
     VQ_API_END
 }
 
@@ -3685,191 +3794,110 @@ int vqhip_ivfpq_flags(const vqhip_ivfpq *ix, uint32_t *flags) {
 
 int vqhip_ivfpq_list_sizes(vqhip_ivfpq *ix, uint64_t *sizes) {
     VQ_API_BEGIN
-    if (!ix || !sizes) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    Entry in(ix->sync);
-    memcpy(sizes, ix->sizes.data(), ix->sizes.size() * 8);
-    return VQHIP_OK;
+    return ivf_list_sizes(ix, sizes);
     VQ_API_END
 }
 
 int vqhip_ivfpq_probe(vqhip_ivfpq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t *lists_out) {
     VQ_API_BEGIN
-    if (!ix || !queries || !lists_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    Entry in(ix->sync);  // (n changes under add: read under the lock)
-    VQ_TRY(ivfpq_check_probe(ix, nprobe));
-    if (nq == 0) return VQHIP_OK;
-    VQ_TRY(require_gfx950());
-    VQ_TRY(ivfpq_device(ix));
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    VQ_TRY(ivfpq_ready(ix, s));
-    return host_search(in, s, ix->q, ix->idx, nullptr, queries, nq, ix->dim, nprobe, lists_out, nullptr, [&] {
-        return ivfpq_probe_enqueue(ix, ix->q.as<float>(), nq, nprobe, ix->idx.as<uint32_t>(), s);
-    });
+    return ivf_probe(ix, queries, nq, nprobe, lists_out);
     VQ_API_END
 }
 
 int vqhip_ivfpq_search(vqhip_ivfpq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_out,
                        float *dist_out) {
     VQ_API_BEGIN
-    if (!ix || !queries || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    Entry in(ix->sync);  // (n changes under add: read under the lock)
-    VQ_TRY(ivfpq_check_probe(ix, nprobe));
-    VQ_TRY(check_topk(ix->n, topk));
-    if (nq == 0) return VQHIP_OK;
-    VQ_TRY(require_gfx950());
-    VQ_TRY(ivfpq_device(ix));
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    VQ_TRY(ivfpq_ready(ix, s));
-    return host_search(in, s, ix->q, ix->idx, &ix->out, queries, nq, ix->dim, topk, idx_out, dist_out, [&] {
-        return ivfpq_search_enqueue(ix, ix->q.as<float>(), nq, nprobe, topk, ix->idx.as<uint32_t>(), ix->out.as<float>(), s);
-    });
+    return ivf_search(ix, queries, nq, nprobe, topk, idx_out, dist_out);
     VQ_API_END
 }
 
 int vqhip_ivfpq_search_device(vqhip_ivfpq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk, void *dev_idx,
                               void *dev_dist) {
     VQ_API_BEGIN
-    if (!ix || !dev_queries || !dev_idx || !dev_dist) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    Entry in(ix->sync);  // (n changes under add: read under the lock)
-    VQ_TRY(ivfpq_check_probe(ix, nprobe));
-    VQ_TRY(check_topk(ix->n, topk));
-    if (nq == 0) return VQHIP_OK;
-    VQ_TRY(require_gfx950());
-    VQ_TRY(ivfpq_device(ix));
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    VQ_TRY(ivfpq_ready(ix, s));
-    return ivfpq_search_enqueue(ix, reinterpret_cast<const float *>(dev_queries), nq, nprobe, topk,
-                                reinterpret_cast<uint32_t *>(dev_idx), reinterpret_cast<float *>(dev_dist), s);
+    return ivf_search_device(ix, dev_queries, nq, nprobe, topk, dev_idx, dev_dist);
     VQ_API_END
 }
 
 }  // extern "C"
 
-// ------------------------------------------------------------------ inverted-file flat (k_ivfflat.hip) ----
-// Host state: the coarse centroids and every added row's list id and elements in add order.  The device state -- a flat
-// index over the centroids and the rows in list order (off / ids / rows, their norms under the cosines) -- is built on
-// the current device by the first probe or search and rebuilt there after an add: a host counting sort gives the order,
-// and the rows go up through a staging buffer of at most kIvfflatStage bytes, list order gathered a piece at a time.
-constexpr size_t kIvfflatStage = 64u << 20;
+// ------------------------------------------------------------------ inverted-file flat and scalar (k_ivfflat.hip, k_ivfsq.hip) ----
+// The two indexes of exact distances: IvfLists whose payload is the rows themselves (f32 or f16 elements) or their SQ
+// codes (dim bytes), with the rows' norms under the cosines.  They differ in the norms kernel and the search launch.
+struct IvfExact : IvfLists {
+    DevBuf d_rnorm;
+    DevBuf qnorm, inv, lists;  // per-call workspaces
 
-struct vqhip_ivfflat {
-    HandleSync sync;
-    uint32_t nlist = 0, dim = 0;
-    int dtype = 0, metric = VQHIP_EUCLIDEAN;
-    std::vector<float> coarse;       // [nlist][dim]
-    std::vector<uint32_t> row_list;  // [n] list id of each row
-    std::vector<uint8_t> row_data;   // [n][dim] f32 or f16 bits
-    std::vector<uint64_t> sizes;     // [nlist] rows per list
-    uint64_t n = 0, max_list = 0;
-    bool dirty = true;                     // rows added since the last upload
-    int dev = -1;                          // as vqhip_ivfpq's
-    std::vector<uint64_t> largest_prefix;  // [nlist + 1] sums of the largest list sizes (the bound on |S(q)|)
-    vqhip_flat *flat = nullptr;            // the coarse centroids on the device
-    DevBuf d_off, d_ids, d_rows, d_rnorm;
-    DevBuf q, qnorm, probe, probe_dist, pref, seg, inv, lists, W, state, cand, idx, out;  // per-call workspaces
-    ~vqhip_ivfflat() { delete flat; }
-    size_t row_bytes() const { return (size_t)dim * (dtype == 1 ? 2 : 4); }
+    // queries_dev [nq][dim] f32 -> [nq][topk] results on the device, enqueued on s, in ivf_batch's batches;
+    // launch(Q, qn or NULL, nb, batch, idx_dev, dist_dev) searches one batch
+    template <class Launch>
+    int search_batches(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
+                       hipStream_t s, Launch &&launch) {
+        IvfBatch b;
+        VQ_TRY(ivf_batch(this, nq, nprobe, 0, &b));
+        VQ_TRY(inv.ensure((size_t)b.nb_max * nprobe * 4));
+        VQ_TRY(lists.ensure(ivfflat_lists_bytes(nlist)));
+        VQ_TRY(state.ensure(knn_state_bytes(b.nb_max)));
+        const float *qn = nullptr;
+        if (vq_is_cos(metric)) {  // once per call
+            VQ_TRY(qnorm.ensure((size_t)nq * 4));
+            VQ_TRY(launch_knn_norms(queries_dev, 0, nq, dim, qnorm.as<float>(), s));
+            qn = qnorm.as<float>();
+        }
+        for (uint32_t q0 = 0; q0 < nq; q0 += b.nb_max) {
+            const uint32_t nb = std::min(b.nb_max, nq - q0);
+            const float *Q = queries_dev + (size_t)q0 * dim;
+            VQ_TRY(ivf_probe_enqueue(this, Q, nb, nprobe, probe.as<uint32_t>(), s));
+            VQ_TRY(launch(Q, qn ? qn + q0 : nullptr, nb, b, idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk));
+        }
+        return VQHIP_OK;
+    }
 };
 
-static int ivfflat_check_probe(const vqhip_ivfflat *ix, uint32_t nprobe) {
-    const uint32_t hi = std::min<uint32_t>(ix->nlist, 1024);
-    if (nprobe == 0 || nprobe > hi) return fail(VQHIP_ERR_INVALID_INPUT, "nprobe %u must be in [1, min(nlist, 1024)] = [1, %u]", nprobe, hi);
-    return VQHIP_OK;
-}
+struct vqhip_ivfflat : IvfExact {
+    int dtype = 0;
 
-// the device state, current with the host's rows (enqueued on s and waited for: host buffers are the copies' sources)
-static int ivfflat_ready(vqhip_ivfflat *ix, hipStream_t s) {
-    if (!ix->flat) VQ_TRY(flat_create(ix->coarse.data(), hipMemcpyHostToDevice, ix->nlist, ix->dim, 0, ix->metric, &ix->flat));
-    if (!ix->dirty) return VQHIP_OK;
-    const size_t row_b = ix->row_bytes();
-    std::vector<uint32_t> off(ix->nlist + 1, 0), at(ix->nlist), ids(ix->n);
-    for (uint32_t l = 0; l < ix->nlist; ++l) off[l + 1] = off[l] + (uint32_t)ix->sizes[l];
-    std::copy(off.begin(), off.end() - 1, at.begin());
-    for (uint64_t i = 0; i < ix->n; ++i) ids[at[ix->row_list[i]]++] = (uint32_t)i;  // ascending row ids within each list
-    VQ_TRY(ix->d_off.alloc(off.size() * 4));
-    VQ_TRY(ix->d_ids.alloc(ids.size() * 4));
-    VQ_TRY(ix->d_rows.alloc((size_t)ix->n * row_b));
-    VQ_HIP(hipMemcpyAsync(ix->d_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, s));
-    if (ix->n) {
-        VQ_HIP(hipMemcpyAsync(ix->d_ids.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, s));
-        const uint64_t per = std::max<uint64_t>(1, kIvfflatStage / row_b);
-        std::vector<uint8_t> stage((size_t)std::min<uint64_t>(per, ix->n) * row_b);
-        for (uint64_t p0 = 0; p0 < ix->n; p0 += per) {
-            const uint64_t pn = std::min<uint64_t>(per, ix->n - p0);
-            for (uint64_t p = 0; p < pn; ++p) memcpy(stage.data() + (size_t)p * row_b, ix->row_data.data() + (size_t)ids[p0 + p] * row_b, row_b);
-            VQ_HIP(hipMemcpyAsync(ix->d_rows.as<uint8_t>() + (size_t)p0 * row_b, stage.data(), (size_t)pn * row_b, hipMemcpyHostToDevice, s));
-            VQ_HIP(hipStreamSynchronize(s));  // (the staging buffer is filled again)
-        }
-        if (vq_is_cos(ix->metric)) {
-            VQ_TRY(ix->d_rnorm.alloc((size_t)ix->n * 4));
-            VQ_TRY(launch_knn_norms(ix->d_rows.p, ix->dtype, ix->n, ix->dim, ix->d_rnorm.as<float>(), s));
-        }
+    int ready(hipStream_t s) {
+        return ivf_ready(this, s, ivf_no_hook, [&] {
+            if (!vq_is_cos(metric)) return VQHIP_OK;
+            VQ_TRY(d_rnorm.alloc((size_t)n * 4));
+            return launch_knn_norms(d_payload.p, dtype, n, dim, d_rnorm.as<float>(), s);
+        });
     }
-    VQ_HIP(hipStreamSynchronize(s));
-    std::vector<uint64_t> sorted(ix->sizes);
-    std::sort(sorted.begin(), sorted.end(), std::greater<uint64_t>());
-    ix->max_list = sorted[0];
-    ix->largest_prefix.assign(ix->nlist + 1, 0);
-    for (uint32_t l = 0; l < ix->nlist; ++l) ix->largest_prefix[l + 1] = ix->largest_prefix[l] + sorted[l];
-    ix->dirty = false;
-    return VQHIP_OK;
-}
-
-// every device call runs on the index's device
-static int ivfflat_device(vqhip_ivfflat *ix) {
-    int cur = 0;
-    VQ_HIP(hipGetDevice(&cur));
-    if (ix->dev < 0) ix->dev = cur;
-    if (cur != ix->dev) return fail(VQHIP_ERR_INVALID_INPUT, "the index lives on device %d, but device %d is current", ix->dev, cur);
-    return VQHIP_OK;
-}
-
-// queries_dev [nq][dim] f32 -> probe lists [nq][nprobe] on the device
-static int ivfflat_probe_enqueue(vqhip_ivfflat *ix, const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t *lists_dev,
-                                 hipStream_t s) {
-    VQ_TRY(ix->probe_dist.ensure((size_t)nq * nprobe * 4));
-    return flat_search_enqueue(ix->flat, queries_dev, nq, nprobe, lists_dev, ix->probe_dist.as<float>(), s);
-}
-
-// queries_dev [nq][dim] f32 -> [nq][topk] results on the device, enqueued on s.  Batches of queries bound the workspace:
-// the distances of a batch (4 bytes per position of S(q), sized by the nprobe largest lists) under 1 GB -- or one
-// query's when that alone is more -- and at most 1024 queries.
-static int ivfflat_search_enqueue(vqhip_ivfflat *ix, const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk,
-                                  uint32_t *idx_dev, float *dist_dev, hipStream_t s) {
-    const uint64_t wstride = std::max<uint64_t>(ix->largest_prefix[nprobe], 1);
-    const uint32_t nb_max = (uint32_t)std::min<uint64_t>({(uint64_t)nq, 1024, std::max<uint64_t>(1, (1ull << 30) / (4 * wstride))});
-    VQ_TRY(ix->probe.ensure((size_t)nb_max * nprobe * 4));
-    VQ_TRY(ix->pref.ensure((size_t)nb_max * (nprobe + 1) * 4));
-    VQ_TRY(ix->seg.ensure((size_t)nb_max * nprobe * 4));
-    VQ_TRY(ix->inv.ensure((size_t)nb_max * nprobe * 4));
-    VQ_TRY(ix->lists.ensure(ivfflat_lists_bytes(ix->nlist)));
-    VQ_TRY(ix->W.ensure((size_t)nb_max * wstride * 4));
-    VQ_TRY(ix->state.ensure(knn_state_bytes(nb_max)));
-    VQ_TRY(ix->cand.ensure(topk_cand_bytes(nb_max)));
-    const float *qn = nullptr;
-    if (vq_is_cos(ix->metric)) {  // once per call
-        VQ_TRY(ix->qnorm.ensure((size_t)nq * 4));
-        VQ_TRY(launch_knn_norms(queries_dev, 0, nq, ix->dim, ix->qnorm.as<float>(), s));
-        qn = ix->qnorm.as<float>();
+    int search_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
+                       hipStream_t s) {
+        return search_batches(queries_dev, nq, nprobe, topk, idx_dev, dist_dev, s,
+                              [&](const float *Q, const float *qn, uint32_t nb, const IvfBatch &b, uint32_t *idx_b, float *dist_b) {
+            return launch_ivfflat_search(metric, d_payload.p, dtype, dim, d_rnorm.as<float>(), d_ids.as<uint32_t>(), d_off.as<uint32_t>(),
+                                         nlist, max_list, Q, qn, probe.as<uint32_t>(), nb, nprobe, topk, ivf_chunk((uint64_t)nb * b.per_q),
+                                         b.wstride, W.as<float>(), pref.as<uint32_t>(), seg.as<uint32_t>(), inv.as<uint32_t>(),
+                                         lists.as<uint32_t>(), state.p, cand.as<unsigned long long>(), idx_b, dist_b, s);
+        });
     }
-    // expected positions per query: the mean list size times nprobe
-    const uint64_t per_q = std::max<uint64_t>(1, (uint64_t)((double)ix->n * nprobe / ix->nlist));
-    for (uint32_t q0 = 0; q0 < nq; q0 += nb_max) {
-        const uint32_t nb = std::min(nb_max, nq - q0);
-        const float *Q = queries_dev + (size_t)q0 * ix->dim;
-        VQ_TRY(ivfflat_probe_enqueue(ix, Q, nb, nprobe, ix->probe.as<uint32_t>(), s));
-        VQ_TRY(launch_ivfflat_search(ix->metric, ix->d_rows.p, ix->dtype, ix->dim, ix->d_rnorm.as<float>(), ix->d_ids.as<uint32_t>(),
-                                     ix->d_off.as<uint32_t>(), ix->nlist, ix->max_list, Q, qn ? qn + q0 : nullptr,
-                                     ix->probe.as<uint32_t>(), nb, nprobe, topk, ivf_chunk((uint64_t)nb * per_q), wstride,
-                                     ix->W.as<float>(), ix->pref.as<uint32_t>(), ix->seg.as<uint32_t>(), ix->inv.as<uint32_t>(),
-                                     ix->lists.as<uint32_t>(), ix->state.p, ix->cand.as<unsigned long long>(),
-                                     idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s));
+};
+
+struct vqhip_ivfsq : IvfExact {
+    uint32_t levels = 0;
+    float mn = 0, mx = 0, step = 0;
+    SqbqEncodeOp op;  // add_rows: the encode of this quantizer
+
+    int ready(hipStream_t s) {
+        return ivf_ready(this, s, ivf_no_hook, [&] {
+            if (!vq_is_cos(metric)) return VQHIP_OK;
+            VQ_TRY(d_rnorm.alloc((size_t)n * 4));
+            return launch_sq_norms(d_payload.as<uint8_t>(), n, dim, mn, step, d_rnorm.as<float>(), s);
+        });
     }
-    return VQHIP_OK;
-}
+    int search_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
+                       hipStream_t s) {
+        return search_batches(queries_dev, nq, nprobe, topk, idx_dev, dist_dev, s,
+                              [&](const float *Q, const float *qn, uint32_t nb, const IvfBatch &b, uint32_t *idx_b, float *dist_b) {
+            return launch_ivfsq_search(metric, d_payload.as<uint8_t>(), dim, mn, step, d_rnorm.as<float>(), d_ids.as<uint32_t>(),
+                                       d_off.as<uint32_t>(), nlist, max_list, Q, qn, probe.as<uint32_t>(), nb, nprobe, topk,
+                                       ivf_chunk((uint64_t)nb * b.per_q), b.wstride, W.as<float>(), pref.as<uint32_t>(), seg.as<uint32_t>(),
+                                       inv.as<uint32_t>(), lists.as<uint32_t>(), state.p, cand.as<unsigned long long>(), idx_b, dist_b, s);
+        });
+    }
+};
 
 extern "C" {
 
@@ -3877,20 +3905,13 @@ int vqhip_ivfflat_create(const float *coarse, uint32_t nlist, uint32_t dim, int 
     VQ_API_BEGIN
     if (!out) return fail(VQHIP_ERR_NULL_PTR, "out is NULL");
     *out = nullptr;
-    if (!coarse) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    if (nlist == 0 || nlist > 65536) return fail(VQHIP_ERR_INVALID_INPUT, "nlist %u must be in [1, 65536]", nlist);
+    VQ_TRY(ivf_check_lists(coarse, nlist));
     if (dim == 0) return fail(VQHIP_ERR_INVALID_INPUT, "dim must be at least 1");
     if (dtype != 0 && dtype != 1) return fail(VQHIP_ERR_INVALID_INPUT, "dtype must be 0 (f32) or 1 (f16), not %d", dtype);
-    if (metric < VQHIP_SQUARED_EUCLIDEAN || metric > VQHIP_COSINE_UNCLAMPED) return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
+    VQ_TRY(ivf_check_metric(metric));
     std::unique_ptr<vqhip_ivfflat> ix(new vqhip_ivfflat());
-    ix->nlist = nlist;
-    ix->dim = dim;
+    ivf_init(ix.get(), coarse, nlist, dim, metric, (size_t)dim * (dtype == 1 ? 2 : 4));
     ix->dtype = dtype;
-    ix->metric = metric;
-    ix->coarse.assign(coarse, coarse + (size_t)nlist * dim);
-    ix->sizes.assign(nlist, 0);
-    int ndev = 0, cur = -1;  // (the device is named, not touched: the state is built by the first probe or search)
-    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && hipGetDevice(&cur) == hipSuccess) ix->dev = cur;
     *out = ix.release();
     return VQHIP_OK;
     VQ_API_END
@@ -3903,23 +3924,7 @@ int vqhip_ivfflat_destroy(vqhip_ivfflat *ix) {
 
 int vqhip_ivfflat_add(vqhip_ivfflat *ix, const uint32_t *list_ids, const void *rows, uint64_t n) {
     VQ_API_BEGIN
-    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    if (n == 0) return VQHIP_OK;
-    if (!list_ids || !rows) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    Entry in(ix->sync);
-    if (n >= (1ull << 32) - ix->n)
-        return fail(VQHIP_ERR_INVALID_INPUT, "the index would hold %llu + %llu rows: at most 2^32 - 1", (unsigned long long)ix->n,
-                    (unsigned long long)n);
-    for (uint64_t i = 0; i < n; ++i)
-        if (list_ids[i] >= ix->nlist)
-            return fail(VQHIP_ERR_INVALID_INPUT, "list id %u of row %llu is outside [0, %u)", list_ids[i], (unsigned long long)i, ix->nlist);
-    const uint8_t *r = reinterpret_cast<const uint8_t *>(rows);
-    ix->row_data.insert(ix->row_data.end(), r, r + (size_t)n * ix->row_bytes());
-    ix->row_list.insert(ix->row_list.end(), list_ids, list_ids + n);
-    for (uint64_t i = 0; i < n; ++i) ++ix->sizes[list_ids[i]];
-    ix->n += n;
-    ix->dirty = true;
-    return VQHIP_OK;
+    return ivf_add(ix, list_ids, rows, n, [&] { return ivf_append(ix, rows, n); });
     VQ_API_END
 }
 
@@ -3936,207 +3941,29 @@ int vqhip_ivfflat_info(const vqhip_ivfflat *ix, uint64_t *n, uint32_t *nlist, ui
 
 int vqhip_ivfflat_list_sizes(vqhip_ivfflat *ix, uint64_t *sizes) {
     VQ_API_BEGIN
-    if (!ix || !sizes) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    Entry in(ix->sync);
-    memcpy(sizes, ix->sizes.data(), ix->sizes.size() * 8);
-    return VQHIP_OK;
+    return ivf_list_sizes(ix, sizes);
     VQ_API_END
 }
 
 int vqhip_ivfflat_probe(vqhip_ivfflat *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t *lists_out) {
     VQ_API_BEGIN
-    if (!ix || !queries || !lists_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    Entry in(ix->sync);  // (n changes under add: read under the lock)
-    VQ_TRY(ivfflat_check_probe(ix, nprobe));
-    if (nq == 0) return VQHIP_OK;
-    VQ_TRY(require_gfx950());
-    VQ_TRY(ivfflat_device(ix));
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    VQ_TRY(ivfflat_ready(ix, s));
-    return host_search(in, s, ix->q, ix->idx, nullptr, queries, nq, ix->dim, nprobe, lists_out, nullptr, [&] {
-        return ivfflat_probe_enqueue(ix, ix->q.as<float>(), nq, nprobe, ix->idx.as<uint32_t>(), s);
-    });
+    return ivf_probe(ix, queries, nq, nprobe, lists_out);
     VQ_API_END
 }
 
 int vqhip_ivfflat_search(vqhip_ivfflat *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_out,
                          float *dist_out) {
     VQ_API_BEGIN
-    if (!ix || !queries || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    Entry in(ix->sync);  // (n changes under add: read under the lock)
-    VQ_TRY(ivfflat_check_probe(ix, nprobe));
-    VQ_TRY(check_topk(ix->n, topk));
-    if (nq == 0) return VQHIP_OK;
-    VQ_TRY(require_gfx950());
-    VQ_TRY(ivfflat_device(ix));
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    VQ_TRY(ivfflat_ready(ix, s));
-    return host_search(in, s, ix->q, ix->idx, &ix->out, queries, nq, ix->dim, topk, idx_out, dist_out, [&] {
-        return ivfflat_search_enqueue(ix, ix->q.as<float>(), nq, nprobe, topk, ix->idx.as<uint32_t>(), ix->out.as<float>(), s);
-    });
+    return ivf_search(ix, queries, nq, nprobe, topk, idx_out, dist_out);
     VQ_API_END
 }
 
 int vqhip_ivfflat_search_device(vqhip_ivfflat *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
                                 void *dev_idx, void *dev_dist) {
     VQ_API_BEGIN
-    if (!ix || !dev_queries || !dev_idx || !dev_dist) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    Entry in(ix->sync);  // (n changes under add: read under the lock)
-    VQ_TRY(ivfflat_check_probe(ix, nprobe));
-    VQ_TRY(check_topk(ix->n, topk));
-    if (nq == 0) return VQHIP_OK;
-    VQ_TRY(require_gfx950());
-    VQ_TRY(ivfflat_device(ix));
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    VQ_TRY(ivfflat_ready(ix, s));
-    return ivfflat_search_enqueue(ix, reinterpret_cast<const float *>(dev_queries), nq, nprobe, topk,
-                                  reinterpret_cast<uint32_t *>(dev_idx), reinterpret_cast<float *>(dev_dist), s);
+    return ivf_search_device(ix, dev_queries, nq, nprobe, topk, dev_idx, dev_dist);
     VQ_API_END
 }
-
-}  // extern "C"
-
-// ------------------------------------------------------------------ inverted-file scalar (k_ivfsq.hip) ----
-// vqhip_ivfflat with the rows kept as SQ codes.  Host state: the quantizer, the coarse centroids and every added row's
-// list id and codes in add order (n * dim bytes).  The device state -- a flat index over the centroids and the codes in
-// list order (off / ids / codes, the decoded rows' norms under the cosines) -- is built and rebuilt as vqhip_ivfflat's:
-// a host counting sort, the codes gathered into list order through the kIvfflatStage staging buffer.
-struct vqhip_ivfsq {
-    HandleSync sync;
-    uint32_t nlist = 0, dim = 0, levels = 0;
-    float mn = 0, mx = 0, step = 0;
-    int metric = VQHIP_EUCLIDEAN;
-    SqbqEncodeOp op;                 // add_rows: the encode of this quantizer
-    std::vector<float> coarse;       // [nlist][dim]
-    std::vector<uint32_t> row_list;  // [n] list id of each row
-    std::vector<uint8_t> row_codes;  // [n][dim]
-    std::vector<uint64_t> sizes;     // [nlist] rows per list
-    uint64_t n = 0, max_list = 0;
-    bool dirty = true;                     // rows added since the last upload
-    int dev = -1;                          // as vqhip_ivfpq's
-    std::vector<uint64_t> largest_prefix;  // [nlist + 1] sums of the largest list sizes (the bound on |S(q)|)
-    vqhip_flat *flat = nullptr;            // the coarse centroids on the device
-    DevBuf d_off, d_ids, d_codes, d_rnorm;
-    DevBuf q, qnorm, probe, probe_dist, pref, seg, inv, lists, W, state, cand, idx, out;  // per-call workspaces
-    ~vqhip_ivfsq() { delete flat; }
-};
-
-static int ivfsq_check_probe(const vqhip_ivfsq *ix, uint32_t nprobe) {
-    const uint32_t hi = std::min<uint32_t>(ix->nlist, 1024);
-    if (nprobe == 0 || nprobe > hi) return fail(VQHIP_ERR_INVALID_INPUT, "nprobe %u must be in [1, min(nlist, 1024)] = [1, %u]", nprobe, hi);
-    return VQHIP_OK;
-}
-
-// the device state, current with the host's rows (enqueued on s and waited for: host buffers are the copies' sources)
-static int ivfsq_ready(vqhip_ivfsq *ix, hipStream_t s) {
-    if (!ix->flat) VQ_TRY(flat_create(ix->coarse.data(), hipMemcpyHostToDevice, ix->nlist, ix->dim, 0, ix->metric, &ix->flat));
-    if (!ix->dirty) return VQHIP_OK;
-    const size_t row_b = ix->dim;
-    std::vector<uint32_t> off(ix->nlist + 1, 0), at(ix->nlist), ids(ix->n);
-    for (uint32_t l = 0; l < ix->nlist; ++l) off[l + 1] = off[l] + (uint32_t)ix->sizes[l];
-    std::copy(off.begin(), off.end() - 1, at.begin());
-    for (uint64_t i = 0; i < ix->n; ++i) ids[at[ix->row_list[i]]++] = (uint32_t)i;  // ascending row ids within each list
-    VQ_TRY(ix->d_off.alloc(off.size() * 4));
-    VQ_TRY(ix->d_ids.alloc(ids.size() * 4));
-    VQ_TRY(ix->d_codes.alloc((size_t)ix->n * row_b));  // (the index's own buffer: the loaders' alignment rests on its base)
-    VQ_HIP(hipMemcpyAsync(ix->d_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, s));
-    if (ix->n) {
-        VQ_HIP(hipMemcpyAsync(ix->d_ids.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, s));
-        const uint64_t per = std::max<uint64_t>(1, kIvfflatStage / row_b);
-        std::vector<uint8_t> stage((size_t)std::min<uint64_t>(per, ix->n) * row_b);
-        for (uint64_t p0 = 0; p0 < ix->n; p0 += per) {
-            const uint64_t pn = std::min<uint64_t>(per, ix->n - p0);
-            for (uint64_t p = 0; p < pn; ++p) memcpy(stage.data() + (size_t)p * row_b, ix->row_codes.data() + (size_t)ids[p0 + p] * row_b, row_b);
-            VQ_HIP(hipMemcpyAsync(ix->d_codes.as<uint8_t>() + (size_t)p0 * row_b, stage.data(), (size_t)pn * row_b, hipMemcpyHostToDevice, s));
-            VQ_HIP(hipStreamSynchronize(s));  // (the staging buffer is filled again)
-        }
-        if (vq_is_cos(ix->metric)) {
-            VQ_TRY(ix->d_rnorm.alloc((size_t)ix->n * 4));
-            VQ_TRY(launch_sq_norms(ix->d_codes.as<uint8_t>(), ix->n, ix->dim, ix->mn, ix->step, ix->d_rnorm.as<float>(), s));
-        }
-    }
-    VQ_HIP(hipStreamSynchronize(s));
-    std::vector<uint64_t> sorted(ix->sizes);
-    std::sort(sorted.begin(), sorted.end(), std::greater<uint64_t>());
-    ix->max_list = sorted[0];
-    ix->largest_prefix.assign(ix->nlist + 1, 0);
-    for (uint32_t l = 0; l < ix->nlist; ++l) ix->largest_prefix[l + 1] = ix->largest_prefix[l] + sorted[l];
-    ix->dirty = false;
-    return VQHIP_OK;
-}
-
-// every device call runs on the index's device
-static int ivfsq_device(vqhip_ivfsq *ix) {
-    int cur = 0;
-    VQ_HIP(hipGetDevice(&cur));
-    if (ix->dev < 0) ix->dev = cur;
-    if (cur != ix->dev) return fail(VQHIP_ERR_INVALID_INPUT, "the index lives on device %d, but device %d is current", ix->dev, cur);
-    return VQHIP_OK;
-}
-
-// queries_dev [nq][dim] f32 -> probe lists [nq][nprobe] on the device
-static int ivfsq_probe_enqueue(vqhip_ivfsq *ix, const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t *lists_dev,
-                               hipStream_t s) {
-    VQ_TRY(ix->probe_dist.ensure((size_t)nq * nprobe * 4));
-    return flat_search_enqueue(ix->flat, queries_dev, nq, nprobe, lists_dev, ix->probe_dist.as<float>(), s);
-}
-
-// queries_dev [nq][dim] f32 -> [nq][topk] results on the device, enqueued on s; the batches of ivfflat_search_enqueue
-static int ivfsq_search_enqueue(vqhip_ivfsq *ix, const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk,
-                                uint32_t *idx_dev, float *dist_dev, hipStream_t s) {
-    const uint64_t wstride = std::max<uint64_t>(ix->largest_prefix[nprobe], 1);
-    const uint32_t nb_max = (uint32_t)std::min<uint64_t>({(uint64_t)nq, 1024, std::max<uint64_t>(1, (1ull << 30) / (4 * wstride))});
-    VQ_TRY(ix->probe.ensure((size_t)nb_max * nprobe * 4));
-    VQ_TRY(ix->pref.ensure((size_t)nb_max * (nprobe + 1) * 4));
-    VQ_TRY(ix->seg.ensure((size_t)nb_max * nprobe * 4));
-    VQ_TRY(ix->inv.ensure((size_t)nb_max * nprobe * 4));
-    VQ_TRY(ix->lists.ensure(ivfflat_lists_bytes(ix->nlist)));
-    VQ_TRY(ix->W.ensure((size_t)nb_max * wstride * 4));
-    VQ_TRY(ix->state.ensure(knn_state_bytes(nb_max)));
-    VQ_TRY(ix->cand.ensure(topk_cand_bytes(nb_max)));
-    const float *qn = nullptr;
-    if (vq_is_cos(ix->metric)) {  // once per call
-        VQ_TRY(ix->qnorm.ensure((size_t)nq * 4));
-        VQ_TRY(launch_knn_norms(queries_dev, 0, nq, ix->dim, ix->qnorm.as<float>(), s));
-        qn = ix->qnorm.as<float>();
-    }
-    // expected positions per query: the mean list size times nprobe
-    const uint64_t per_q = std::max<uint64_t>(1, (uint64_t)((double)ix->n * nprobe / ix->nlist));
-    for (uint32_t q0 = 0; q0 < nq; q0 += nb_max) {
-        const uint32_t nb = std::min(nb_max, nq - q0);
-        const float *Q = queries_dev + (size_t)q0 * ix->dim;
-        VQ_TRY(ivfsq_probe_enqueue(ix, Q, nb, nprobe, ix->probe.as<uint32_t>(), s));
-        VQ_TRY(launch_ivfsq_search(ix->metric, ix->d_codes.as<uint8_t>(), ix->dim, ix->mn, ix->step, ix->d_rnorm.as<float>(),
-                                   ix->d_ids.as<uint32_t>(), ix->d_off.as<uint32_t>(), ix->nlist, ix->max_list, Q, qn ? qn + q0 : nullptr,
-                                   ix->probe.as<uint32_t>(), nb, nprobe, topk, ivf_chunk((uint64_t)nb * per_q), wstride,
-                                   ix->W.as<float>(), ix->pref.as<uint32_t>(), ix->seg.as<uint32_t>(), ix->inv.as<uint32_t>(),
-                                   ix->lists.as<uint32_t>(), ix->state.p, ix->cand.as<unsigned long long>(),
-                                   idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s));
-    }
-    return VQHIP_OK;
-}
-
-// the checks of an add (before anything is stored), and its bookkeeping once the codes are in row_codes
-static int ivfsq_add_begin(vqhip_ivfsq *ix, const uint32_t *list_ids, uint64_t n) {
-    if (n >= (1ull << 32) - ix->n)
-        return fail(VQHIP_ERR_INVALID_INPUT, "the index would hold %llu + %llu rows: at most 2^32 - 1", (unsigned long long)ix->n,
-                    (unsigned long long)n);
-    for (uint64_t i = 0; i < n; ++i)
-        if (list_ids[i] >= ix->nlist)
-            return fail(VQHIP_ERR_INVALID_INPUT, "list id %u of row %llu is outside [0, %u)", list_ids[i], (unsigned long long)i, ix->nlist);
-    return VQHIP_OK;
-}
-static void ivfsq_add_end(vqhip_ivfsq *ix, const uint32_t *list_ids, uint64_t n) {
-    ix->row_list.insert(ix->row_list.end(), list_ids, list_ids + n);
-    for (uint64_t i = 0; i < n; ++i) ++ix->sizes[list_ids[i]];
-    ix->n += n;
-    ix->dirty = true;
-}
-
-extern "C" {
 
 int vqhip_ivfsq_create(float min, float max, uint32_t levels, const float *coarse, uint32_t nlist, uint32_t dim, int metric,
                        vqhip_ivfsq **out) {
@@ -4145,21 +3972,14 @@ int vqhip_ivfsq_create(float min, float max, uint32_t levels, const float *coars
     *out = nullptr;
     float step = 0;
     VQ_TRY(sq_check(min, max, levels, &step));
-    if (!coarse) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    if (nlist == 0 || nlist > 65536) return fail(VQHIP_ERR_INVALID_INPUT, "nlist %u must be in [1, 65536]", nlist);
+    VQ_TRY(ivf_check_lists(coarse, nlist));
     if (dim == 0) return fail(VQHIP_ERR_INVALID_INPUT, "dim must be at least 1");
-    if (metric < VQHIP_SQUARED_EUCLIDEAN || metric > VQHIP_COSINE_UNCLAMPED) return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
+    VQ_TRY(ivf_check_metric(metric));
     std::unique_ptr<vqhip_ivfsq> ix(new vqhip_ivfsq());
     VQ_TRY(sq_encode_op(min, max, levels, &ix->op));
-    ix->nlist = nlist;
-    ix->dim = dim;
+    ivf_init(ix.get(), coarse, nlist, dim, metric, dim);
     ix->levels = levels;
     ix->mn = min, ix->mx = max, ix->step = step;
-    ix->metric = metric;
-    ix->coarse.assign(coarse, coarse + (size_t)nlist * dim);
-    ix->sizes.assign(nlist, 0);
-    int ndev = 0, cur = -1;  // (the device is named, not touched: the state is built by the first probe or search)
-    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && hipGetDevice(&cur) == hipSuccess) ix->dev = cur;
     *out = ix.release();
     return VQHIP_OK;
     VQ_API_END
@@ -4172,35 +3992,21 @@ int vqhip_ivfsq_destroy(vqhip_ivfsq *ix) {
 
 int vqhip_ivfsq_add_codes(vqhip_ivfsq *ix, const uint32_t *list_ids, const uint8_t *codes, uint64_t n) {
     VQ_API_BEGIN
-    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    if (n == 0) return VQHIP_OK;
-    if (!list_ids || !codes) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    Entry in(ix->sync);
-    VQ_TRY(ivfsq_add_begin(ix, list_ids, n));
-    ix->row_codes.insert(ix->row_codes.end(), codes, codes + (size_t)n * ix->dim);
-    ivfsq_add_end(ix, list_ids, n);
-    return VQHIP_OK;
+    return ivf_add(ix, list_ids, codes, n, [&] { return ivf_append(ix, codes, n); });
     VQ_API_END
 }
 
 int vqhip_ivfsq_add_rows(vqhip_ivfsq *ix, const uint32_t *list_ids, const float *rows, uint64_t n) {
     VQ_API_BEGIN
-    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    if (n == 0) return VQHIP_OK;
-    if (!list_ids || !rows) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    Entry in(ix->sync);
-    VQ_TRY(ivfsq_add_begin(ix, list_ids, n));
-    VQ_TRY(require_gfx950());
-    VQ_TRY(ivfsq_device(ix));
-    const size_t have = ix->row_codes.size();
-    ix->row_codes.resize(have + (size_t)n * ix->dim);
-    const int rc = sqbq_encode_host(ix->op, rows, n * ix->dim, ix->row_codes.data() + have);  // vqhip_sq_encode's path
-    if (rc != VQHIP_OK) {
-        ix->row_codes.resize(have);  // (nothing is stored)
+    return ivf_add(ix, list_ids, rows, n, [&] {
+        VQ_TRY(require_gfx950());
+        VQ_TRY(ivf_device(ix));
+        const size_t have = ix->payload.size();
+        ix->payload.resize(have + (size_t)n * ix->dim);
+        const int rc = sqbq_encode_host(ix->op, rows, n * ix->dim, ix->payload.data() + have);  // vqhip_sq_encode's path
+        if (rc != VQHIP_OK) ix->payload.resize(have);  // (nothing is stored)
         return rc;
-    }
-    ivfsq_add_end(ix, list_ids, n);
-    return VQHIP_OK;
+    });
     VQ_API_END
 }
 
@@ -4220,10 +4026,7 @@ int vqhip_ivfsq_info(const vqhip_ivfsq *ix, uint64_t *n, uint32_t *nlist, uint32
 
 int vqhip_ivfsq_list_sizes(vqhip_ivfsq *ix, uint64_t *sizes) {
     VQ_API_BEGIN
-    if (!ix || !sizes) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    Entry in(ix->sync);
-    memcpy(sizes, ix->sizes.data(), ix->sizes.size() * 8);
-    return VQHIP_OK;
+    return ivf_list_sizes(ix, sizes);
     VQ_API_END
 }
 
@@ -4233,62 +4036,28 @@ int vqhip_ivfsq_codes(vqhip_ivfsq *ix, uint8_t *codes_out) {
     Entry in(ix->sync);
     if (ix->n == 0) return VQHIP_OK;
     if (!codes_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    memcpy(codes_out, ix->row_codes.data(), ix->row_codes.size());
+    memcpy(codes_out, ix->payload.data(), ix->payload.size());
     return VQHIP_OK;
     VQ_API_END
 }
 
 int vqhip_ivfsq_probe(vqhip_ivfsq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t *lists_out) {
     VQ_API_BEGIN
-    if (!ix || !queries || !lists_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    Entry in(ix->sync);  // (n changes under add: read under the lock)
-    VQ_TRY(ivfsq_check_probe(ix, nprobe));
-    if (nq == 0) return VQHIP_OK;
-    VQ_TRY(require_gfx950());
-    VQ_TRY(ivfsq_device(ix));
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    VQ_TRY(ivfsq_ready(ix, s));
-    return host_search(in, s, ix->q, ix->idx, nullptr, queries, nq, ix->dim, nprobe, lists_out, nullptr, [&] {
-        return ivfsq_probe_enqueue(ix, ix->q.as<float>(), nq, nprobe, ix->idx.as<uint32_t>(), s);
-    });
+    return ivf_probe(ix, queries, nq, nprobe, lists_out);
     VQ_API_END
 }
 
 int vqhip_ivfsq_search(vqhip_ivfsq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_out,
                        float *dist_out) {
     VQ_API_BEGIN
-    if (!ix || !queries || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    Entry in(ix->sync);  // (n changes under add: read under the lock)
-    VQ_TRY(ivfsq_check_probe(ix, nprobe));
-    VQ_TRY(check_topk(ix->n, topk));
-    if (nq == 0) return VQHIP_OK;
-    VQ_TRY(require_gfx950());
-    VQ_TRY(ivfsq_device(ix));
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    VQ_TRY(ivfsq_ready(ix, s));
-    return host_search(in, s, ix->q, ix->idx, &ix->out, queries, nq, ix->dim, topk, idx_out, dist_out, [&] {
-        return ivfsq_search_enqueue(ix, ix->q.as<float>(), nq, nprobe, topk, ix->idx.as<uint32_t>(), ix->out.as<float>(), s);
-    });
+    return ivf_search(ix, queries, nq, nprobe, topk, idx_out, dist_out);
     VQ_API_END
 }
 
 int vqhip_ivfsq_search_device(vqhip_ivfsq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk, void *dev_idx,
                               void *dev_dist) {
     VQ_API_BEGIN
-    if (!ix || !dev_queries || !dev_idx || !dev_dist) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    Entry in(ix->sync);  // (n changes under add: read under the lock)
-    VQ_TRY(ivfsq_check_probe(ix, nprobe));
-    VQ_TRY(check_topk(ix->n, topk));
-    if (nq == 0) return VQHIP_OK;
-    VQ_TRY(require_gfx950());
-    VQ_TRY(ivfsq_device(ix));
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    VQ_TRY(ivfsq_ready(ix, s));
-    return ivfsq_search_enqueue(ix, reinterpret_cast<const float *>(dev_queries), nq, nprobe, topk,
-                                reinterpret_cast<uint32_t *>(dev_idx), reinterpret_cast<float *>(dev_dist), s);
+    return ivf_search_device(ix, dev_queries, nq, nprobe, topk, dev_idx, dev_dist);
     VQ_API_END
 }
 

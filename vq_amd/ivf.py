@@ -26,12 +26,14 @@ File layout (little endian), in the manner of store.py's:
 """
 from __future__ import annotations
 
-import operator
 import struct
 
 import numpy as np
 
 from . import _lib
+from ._ivf_common import (MAX_NLIST, MAX_PROBE, MAX_TOPK, PAD_ID, IVFIndexBase, _Reader,  # noqa: F401  (re-exported)
+                          _check_distance, _check_file_lists, _check_nlist, _coarse_array, _count, _nearest_lists,
+                          _train_coarse)
 from .distance import Distance
 from .errors import DimensionMismatch, InvalidParameter
 
@@ -39,18 +41,7 @@ MAGIC = b"VQIVFPQ1"
 MAGIC_RESIDUAL = b"VQIVFRP1"
 _HEADER = struct.Struct("<8sIIIIIIQ")
 _METRIC_NAMES = ["squared_euclidean", "euclidean", "manhattan"]
-MAX_NLIST = 65536
-MAX_PROBE = 1024
-MAX_TOPK = 1024
 MAX_TABLE = 38400  # m * k: one query's ADC table in the LDS (include/vqhip.h)
-PAD_ID = 0xFFFFFFFF
-
-
-def _count(v, name: str) -> int:
-    try:
-        return operator.index(v)
-    except TypeError:
-        raise InvalidParameter(name, f"must be an integer, got {v!r}") from None
 
 
 def _code_dtype(k: int):
@@ -59,20 +50,16 @@ def _code_dtype(k: int):
 
 def _check_shape(coarse, codebooks, distance):
     """(coarse f32 (nlist, dim), codebooks f32 (m, k, sub_dim)) after the index's checks"""
-    if not isinstance(distance, Distance):
-        raise InvalidParameter("distance", f"expected a Distance, got {type(distance).__name__}")
+    _check_distance(distance)
     if distance.metric not in (_lib.SQUARED_EUCLIDEAN, _lib.EUCLIDEAN, _lib.MANHATTAN):
         raise InvalidParameter("distance", "cosine distance is not a sum over subspaces: no ADC form")
-    c = np.ascontiguousarray(coarse, dtype=np.float32)
+    c = _coarse_array(coarse)
     cb = np.ascontiguousarray(codebooks, dtype=np.float32)
-    if c.ndim != 2:
-        raise InvalidParameter("coarse_centroids", "must have shape (nlist, dim)")
     if cb.ndim != 3:
         raise InvalidParameter("codebooks", "must have shape (m, k, sub_dim)")
     nlist, dim = c.shape
     m, k, sd = cb.shape
-    if not 1 <= nlist <= MAX_NLIST:
-        raise InvalidParameter("nlist", f"must be between 1 and {MAX_NLIST}, got {nlist}")
+    _check_nlist(nlist)
     if m == 0 or k == 0 or sd == 0:
         raise InvalidParameter("codebooks", "m, k and sub_dim must be positive")
     if k > 65536:
@@ -84,40 +71,20 @@ def _check_shape(coarse, codebooks, distance):
     return c, cb
 
 
-def _nearest_lists(coarse, X, metric: int) -> np.ndarray:
-    """(n,) uint32: each row's nearest coarse centroid (the reference's nearest-centroid rule: a PQ encode with one
-    subspace of nlist centroids)"""
-    enc = _lib.PQEncoder(coarse[None, :, :], metric)
-    try:
-        lists, _ = enc.encode(X, want_f16=False)
-    finally:
-        enc.close()
-    return np.asarray(lists).reshape(-1).astype(np.uint32)
-
-
-class IVFPQIndex:
+class IVFPQIndex(IVFIndexBase):
     """coarse centroids (nlist, dim) + PQ codebooks (m, k, dim / m) + distance, and the rows added to it"""
 
     def __init__(self, coarse_centroids, codebooks, distance: Distance | None = None, *, residual: bool = False):
         if not isinstance(residual, (bool, np.bool_)):
             raise InvalidParameter("residual", f"must be a bool, got {type(residual).__name__}")
-        self._distance = distance if distance is not None else Distance.euclidean()
-        self._coarse, self._codebooks = _check_shape(coarse_centroids, codebooks, self._distance)
+        distance = distance if distance is not None else Distance.euclidean()
+        coarse, self._codebooks = _check_shape(coarse_centroids, codebooks, distance)
+        self._init_lists(coarse, distance)
         self._residual = bool(residual)
         m, k = self._codebooks.shape[:2]
-        self._lists = np.empty(0, np.uint32)
         self._codes = np.empty((0, m), _code_dtype(k))
-        self._ix = None
 
     # -- shape ------------------------------------------------------------------------------
-    @property
-    def nlist(self) -> int:
-        return self._coarse.shape[0]
-
-    @property
-    def dim(self) -> int:
-        return self._coarse.shape[1]
-
     @property
     def m(self) -> int:
         return self._codebooks.shape[0]
@@ -132,37 +99,17 @@ class IVFPQIndex:
         return self._residual
 
     @property
-    def distance(self) -> Distance:
-        return self._distance
-
-    @property
-    def coarse_centroids(self) -> np.ndarray:
-        return self._coarse
-
-    @property
     def codebooks(self) -> np.ndarray:
         return self._codebooks
-
-    @property
-    def list_ids(self) -> np.ndarray:
-        """(n,) uint32: the list of every row, in row order"""
-        return self._lists
 
     @property
     def codes(self) -> np.ndarray:
         """(n, m): every row's codes, in row order"""
         return self._codes
 
-    def __len__(self) -> int:
-        return self._lists.shape[0]
-
     def __repr__(self) -> str:
         return (f"IVFPQIndex(n={len(self)}, nlist={self.nlist}, dim={self.dim}, m={self.m}, k={self.k}, "
                 f"distance={self._distance!r}" + (", residual=True)" if self._residual else ")"))
-
-    def list_sizes(self) -> np.ndarray:
-        """(nlist,) uint64: rows per list"""
-        return np.bincount(self._lists, minlength=self.nlist).astype(np.uint64)
 
     # -- build ------------------------------------------------------------------------------
     @classmethod
@@ -176,7 +123,7 @@ class IVFPQIndex:
         if not isinstance(residual, (bool, np.bool_)):
             raise InvalidParameter("residual", f"must be a bool, got {type(residual).__name__}")
         distance = distance if distance is not None else Distance.euclidean()
-        coarse = ProductQuantizer(X, 1, nlist, max_iters, distance, seed).codebooks[0]
+        coarse = _train_coarse(X, nlist, max_iters, distance, seed)
         if residual:
             X = np.ascontiguousarray(X, dtype=np.float32)
             X = X - coarse[_nearest_lists(coarse, X, distance.metric)]
@@ -186,13 +133,7 @@ class IVFPQIndex:
     def add(self, X) -> np.ndarray:
         """assign each row of X (n, dim) to its nearest coarse centroid (the reference's nearest-centroid rule: a PQ encode
         with one subspace of nlist centroids), encode it with the codebooks, append; returns the new row ids"""
-        X = np.ascontiguousarray(X, dtype=np.float32)
-        if X.ndim == 1:
-            X = X[None, :]
-        if X.ndim != 2:
-            raise ValueError("expected a 2D array (n, dim)")
-        if X.shape[1] != self.dim:
-            raise DimensionMismatch(self.dim, X.shape[1])
+        X = self._add_rows_2d(X)
         if X.shape[0] == 0:
             return np.empty(0, np.uint32)
         lists = _nearest_lists(self._coarse, X, self._distance.metric)
@@ -215,20 +156,16 @@ class IVFPQIndex:
             raise InvalidParameter("codes", f"must have shape (n, {self.m})")
         if c.shape[0] != lid.shape[0]:
             raise DimensionMismatch(lid.shape[0], c.shape[0])
-        if lid.size and (lid.dtype.kind not in "iu" or int(lid.min()) < 0 or int(lid.max()) >= self.nlist):
-            raise InvalidParameter("list_ids", f"must be integers in [0, {self.nlist})")
+        self._check_list_ids(lid)
         if c.size and (c.dtype.kind not in "iu" or int(c.min()) < 0 or int(c.max()) >= self.k):
             raise InvalidParameter("codes", f"must be integers in [0, {self.k})")
-        n0 = len(self)
-        if n0 + lid.shape[0] >= 1 << 32:
-            raise InvalidParameter("codes", "an index holds at most 2^32 - 1 rows")
+        self._check_room(lid.shape[0], "codes")
         lid = np.ascontiguousarray(lid, dtype=np.uint32)
         c = np.ascontiguousarray(c, dtype=_code_dtype(self.k))
         if self._ix is not None and lid.size:
             self._ix.add(lid, c)
-        self._lists = np.concatenate([self._lists, lid])
         self._codes = np.concatenate([self._codes, c])
-        return np.arange(n0, n0 + lid.shape[0], dtype=np.uint32)
+        return self._appended(lid)
 
     def _handle(self) -> "_lib.IVFPQ":
         if self._ix is None:
@@ -238,85 +175,6 @@ class IVFPQIndex:
                 ix.add(self._lists, self._codes)
             self._ix = ix
         return self._ix
-
-    # -- search -----------------------------------------------------------------------------
-    def _queries(self, queries) -> np.ndarray:
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.ndim != 2:
-            raise ValueError("expected a 2D array (nq, dim)")
-        if q.shape[1] != self.dim:
-            raise DimensionMismatch(self.dim, q.shape[1])
-        return q
-
-    def _nprobe(self, nprobe) -> int:
-        p = _count(nprobe, "nprobe")
-        if not 1 <= p <= min(self.nlist, MAX_PROBE):
-            raise InvalidParameter("nprobe", f"must be between 1 and min(nlist, 1024), got {p}")
-        return p
-
-    def _topk(self, topk) -> int:
-        t = _count(topk, "topk")
-        if not 1 <= t <= min(len(self), MAX_TOPK):
-            raise InvalidParameter("topk", f"must be between 1 and min(n, 1024), got {t}")
-        return t
-
-    def probe(self, queries, nprobe: int = 8) -> np.ndarray:
-        """(nq, nprobe) uint32: the lists each query scans, nearest first"""
-        q = self._queries(queries)
-        p = self._nprobe(nprobe)
-        if q.shape[0] == 0:
-            return np.empty((0, p), np.uint32)
-        return self._handle().probe(q, p)
-
-    def search(self, queries, topk: int = 10, nprobe: int = 8, *, rerank=None, candidates: int | None = None):
-        """(nq, dim) float32 queries -> (indices uint32 (nq, topk), distances float32 (nq, topk)), nearest first; slots
-        past the probed rows hold 0xFFFFFFFF / +inf.  rerank: a FlatIndex or a ScalarIndex over the same rows -- the IVF search then
-        returns `candidates` hits per query (default 4 topk, at most 1024 and n) and the exact rerank of the real ones"""
-        q = self._queries(queries)
-        p = self._nprobe(nprobe)
-        t = self._topk(topk)
-        if rerank is not None:
-            return self._search_rerank(q, t, p, rerank, candidates)
-        if q.shape[0] == 0:
-            return np.empty((0, t), np.uint32), np.empty((0, t), np.float32)
-        return self._handle().search(q, p, t)
-
-    def _search_rerank(self, q, topk: int, nprobe: int, rerank, candidates):
-        from .flat import rerank_candidates
-
-        c = rerank_candidates(len(self), self.dim, topk, rerank, candidates)
-        nq = q.shape[0]
-        idx = np.full((nq, topk), PAD_ID, np.uint32)
-        dist = np.full((nq, topk), np.inf, np.float32)
-        if nq == 0:
-            return idx, dist
-        hits, _ = self._handle().search(q, nprobe, c)
-        real = (hits != PAD_ID).sum(axis=1)  # (padding follows every real hit)
-        full = real == c
-        if full.any():
-            idx[full], dist[full] = rerank.rerank(q[full], hits[full], topk)
-        for j in np.flatnonzero((real > 0) & ~full):  # a query with fewer hits keeps its padding
-            r = int(real[j])
-            t = min(topk, r)
-            idx[j, :t], dist[j, :t] = (a[0] for a in rerank.rerank(q[j:j + 1], hits[j:j + 1, :r], t))
-        return idx, dist
-
-    def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int, nprobe: int = 8) -> None:
-        """device pointers: queries [nq][dim] f32, results [nq][topk] uint32 / f32; asynchronous on the current stream"""
-        p = self._nprobe(nprobe)
-        t = self._topk(topk)
-        n_q = _count(nq, "nq")
-        if n_q < 0 or n_q >= 1 << 32:
-            raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
-        self._handle().search_device(int(dev_queries), n_q, p, t, int(dev_idx), int(dev_dist))
-
-    def close(self) -> None:
-        """release the device handle (the next probe or search builds it again)"""
-        if self._ix is not None:
-            self._ix.close()
-            self._ix = None
 
     # -- file -------------------------------------------------------------------------------
     def save(self, path) -> None:
@@ -343,22 +201,13 @@ class IVFPQIndex:
                     or k > 65536 or m * k > MAX_TABLE or dim == 0 or dim % m != 0 or n >= 1 << 32):
                 raise ValueError("corrupt index header")
             sd = dim // m
-
-            def block(count: int, dtype, what: str) -> np.ndarray:
-                dt = np.dtype(dtype)
-                raw = f.read(count * dt.itemsize)
-                if len(raw) != count * dt.itemsize:
-                    raise ValueError(f"truncated {what}")
-                return np.frombuffer(raw, dtype=dt)
-
-            coarse = block(nlist * dim, "<f4", "coarse centroids").reshape(nlist, dim)
-            cb = block(m * k * sd, "<f4", "codebooks").reshape(m, k, sd)
-            lists = block(n, "<u4", "list ids")
-            codes = block(n * m, _code_dtype(k), "codes").reshape(n, m)
-            if f.read(1):
-                raise ValueError("trailing bytes after the codes")
-        if n and int(lists.max()) >= nlist:
-            raise ValueError(f"corrupt index: a list id is outside [0, {nlist})")
+            r = _Reader(f)
+            coarse = r.block(nlist * dim, "<f4", "coarse centroids").reshape(nlist, dim)
+            cb = r.block(m * k * sd, "<f4", "codebooks").reshape(m, k, sd)
+            lists = r.lists(n)
+            codes = r.block(n * m, _code_dtype(k), "codes").reshape(n, m)
+            r.end("codes")
+        _check_file_lists(lists, nlist)
         if n and int(codes.max()) >= k:
             raise ValueError(f"corrupt index: a code is outside [0, {k})")
         self = cls(coarse, cb, Distance(_METRIC_NAMES[metric]), residual=magic == MAGIC_RESIDUAL)

@@ -33,9 +33,10 @@ import struct
 import numpy as np
 
 from . import _lib
+from ._ivf_common import (MAX_NLIST, IVFIndexBase, _Reader, _check_coarse, _check_distance, _check_file_lists,
+                          _train_coarse)
 from .distance import Distance
 from .errors import DimensionMismatch, InvalidParameter
-from .ivf import MAX_NLIST, MAX_PROBE, MAX_TOPK, PAD_ID, _count, _nearest_lists
 from .sq import ScalarQuantizer
 
 MAGIC = b"VQIVFSQ1"
@@ -43,99 +44,41 @@ _HEADER = struct.Struct("<8sIIIffIQ")
 _METRIC_NAMES = ["squared_euclidean", "euclidean", "manhattan", "cosine", "cosine_unclamped"]
 
 
-class IVFScalarIndex:
+class IVFScalarIndex(IVFIndexBase):
     """coarse centroids (nlist, dim) + ScalarQuantizer + distance, and the rows added to it as codes"""
 
     def __init__(self, coarse_centroids, quantizer: ScalarQuantizer, distance: Distance | None = None):
         if not isinstance(quantizer, ScalarQuantizer):
             raise InvalidParameter("quantizer", f"expected a ScalarQuantizer, got {type(quantizer).__name__}")
-        if distance is None:
-            distance = Distance.euclidean()
-        if not isinstance(distance, Distance):
-            raise InvalidParameter("distance", f"expected a Distance, got {type(distance).__name__}")
-        c = np.ascontiguousarray(coarse_centroids, dtype=np.float32)
-        if c.ndim != 2:
-            raise InvalidParameter("coarse_centroids", "must have shape (nlist, dim)")
-        if not 1 <= c.shape[0] <= MAX_NLIST:
-            raise InvalidParameter("nlist", f"must be between 1 and {MAX_NLIST}, got {c.shape[0]}")
-        if c.shape[1] == 0:
-            raise InvalidParameter("coarse_centroids", "dimension must be at least 1")
+        distance = _check_distance(distance)
+        self._init_lists(_check_coarse(coarse_centroids), distance)
         self._quantizer = quantizer
-        self._distance = distance
-        self._coarse = c
-        self._lists = np.empty(0, np.uint32)
-        self._host_codes = np.empty((0, c.shape[1]), np.uint8)  # until the handle exists: it then holds the only copy
-        self._ix = None
+        self._host_codes = np.empty((0, self.dim), np.uint8)  # until the handle exists: it then holds the only copy
 
     # -- shape ------------------------------------------------------------------------------
     @property
-    def nlist(self) -> int:
-        return self._coarse.shape[0]
-
-    @property
-    def dim(self) -> int:
-        return self._coarse.shape[1]
-
-    @property
     def quantizer(self) -> ScalarQuantizer:
         return self._quantizer
-
-    @property
-    def distance(self) -> Distance:
-        return self._distance
-
-    @property
-    def coarse_centroids(self) -> np.ndarray:
-        return self._coarse
-
-    @property
-    def list_ids(self) -> np.ndarray:
-        """(n,) uint32: the list of every row, in row order"""
-        return self._lists
 
     @property
     def codes(self) -> np.ndarray:
         """(n, dim) uint8: every row's codes, in row order"""
         return self._host_codes if self._ix is None else self._ix.codes()
 
-    def __len__(self) -> int:
-        return self._lists.shape[0]
-
     def __repr__(self) -> str:
         return (f"IVFScalarIndex(n={len(self)}, nlist={self.nlist}, dim={self.dim}, quantizer={self._quantizer!r}, "
                 f"distance={self._distance!r})")
-
-    def list_sizes(self) -> np.ndarray:
-        """(nlist,) uint64: rows per list"""
-        return np.bincount(self._lists, minlength=self.nlist).astype(np.uint64)
 
     # -- build ------------------------------------------------------------------------------
     @classmethod
     def train(cls, X, nlist: int, quantizer: ScalarQuantizer, max_iters: int = 10, distance: Distance | None = None,
               seed: int = 42) -> "IVFScalarIndex":
         """fit the coarse quantizer on X (k-means of whole rows, as IVFFlatIndex.train); the scalar quantizer is given,
-        not trained; the index holds no rows yet (add them with `add`)"""
-        from .pq import ProductQuantizer
-
+        not trained; the index holds no rows yet (add them with `add`, which encodes them)"""
         if not isinstance(quantizer, ScalarQuantizer):
             raise InvalidParameter("quantizer", f"expected a ScalarQuantizer, got {type(quantizer).__name__}")
         distance = distance if distance is not None else Distance.euclidean()
-        coarse = ProductQuantizer(X, 1, nlist, max_iters, distance, seed).codebooks[0]
-        return cls(coarse, quantizer, distance)
-
-    def add(self, X) -> np.ndarray:
-        """assign each row of X (n, dim) to its nearest coarse centroid (the reference's nearest-centroid rule, on the
-        float32 values of X, as IVFFlatIndex.add), encode it and append the codes; returns the new row ids"""
-        X = np.ascontiguousarray(X, dtype=np.float32)
-        if X.ndim == 1:
-            X = X[None, :]
-        if X.ndim != 2:
-            raise ValueError("expected a 2D array (n, dim)")
-        if X.shape[1] != self.dim:
-            raise DimensionMismatch(self.dim, X.shape[1])
-        if X.shape[0] == 0:
-            return np.empty(0, np.uint32)
-        return self.add_rows(_nearest_lists(self._coarse, X, self._distance.metric), X)
+        return cls(_train_coarse(X, nlist, max_iters, distance, seed), quantizer, distance)
 
     def _check_add(self, list_ids, a, what: str):
         lid = np.asarray(list_ids)
@@ -148,16 +91,9 @@ class IVFScalarIndex:
             raise DimensionMismatch(self.dim, a.shape[1])
         if a.shape[0] != lid.shape[0]:
             raise DimensionMismatch(lid.shape[0], a.shape[0])
-        if lid.size and (lid.dtype.kind not in "iu" or int(lid.min()) < 0 or int(lid.max()) >= self.nlist):
-            raise InvalidParameter("list_ids", f"must be integers in [0, {self.nlist})")
-        if len(self) + lid.shape[0] >= 1 << 32:
-            raise InvalidParameter(what, "an index holds at most 2^32 - 1 rows")
+        self._check_list_ids(lid)
+        self._check_room(lid.shape[0], what)
         return np.ascontiguousarray(lid, dtype=np.uint32), a
-
-    def _appended(self, lid) -> np.ndarray:
-        n0 = len(self)
-        self._lists = np.concatenate([self._lists, lid])
-        return np.arange(n0, n0 + lid.shape[0], dtype=np.uint32)
 
     def add_rows(self, list_ids, rows) -> np.ndarray:
         """encode rows (n, dim) floating point, as float32, on the device (the codes of quantizer.quantize_batch) and
@@ -194,86 +130,11 @@ class IVFScalarIndex:
             self._host_codes = None
         return self._ix
 
-    # -- search -----------------------------------------------------------------------------
-    def _queries(self, queries) -> np.ndarray:
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.ndim != 2:
-            raise ValueError("expected a 2D array (nq, dim)")
-        if q.shape[1] != self.dim:
-            raise DimensionMismatch(self.dim, q.shape[1])
-        return q
-
-    def _nprobe(self, nprobe) -> int:
-        p = _count(nprobe, "nprobe")
-        if not 1 <= p <= min(self.nlist, MAX_PROBE):
-            raise InvalidParameter("nprobe", f"must be between 1 and min(nlist, 1024), got {p}")
-        return p
-
-    def _topk(self, topk) -> int:
-        t = _count(topk, "topk")
-        if not 1 <= t <= min(len(self), MAX_TOPK):
-            raise InvalidParameter("topk", f"must be between 1 and min(n, 1024), got {t}")
-        return t
-
-    def probe(self, queries, nprobe: int = 8) -> np.ndarray:
-        """(nq, nprobe) uint32: the lists each query scans, nearest first"""
-        q = self._queries(queries)
-        p = self._nprobe(nprobe)
-        if q.shape[0] == 0:
-            return np.empty((0, p), np.uint32)
-        return self._handle().probe(q, p)
-
-    def search(self, queries, topk: int = 10, nprobe: int = 8, *, rerank=None, candidates: int | None = None):
-        """(nq, dim) float32 queries -> (indices uint32 (nq, topk), distances float32 (nq, topk)), nearest first; slots
-        past the probed rows hold 0xFFFFFFFF / +inf.  rerank: a FlatIndex or a ScalarIndex over the same rows -- the search
-        then returns `candidates` hits per query (default 4 topk, at most 1024 and n) and the exact rerank of the real
-        ones, as IVFPQIndex.search"""
-        q = self._queries(queries)
-        p = self._nprobe(nprobe)
-        t = self._topk(topk)
-        if rerank is not None:
-            return self._search_rerank(q, t, p, rerank, candidates)
-        if q.shape[0] == 0:
-            return np.empty((0, t), np.uint32), np.empty((0, t), np.float32)
-        return self._handle().search(q, p, t)
-
-    def _search_rerank(self, q, topk: int, nprobe: int, rerank, candidates):
-        from .flat import rerank_candidates
-
-        c = rerank_candidates(len(self), self.dim, topk, rerank, candidates)
-        nq = q.shape[0]
-        idx = np.full((nq, topk), PAD_ID, np.uint32)
-        dist = np.full((nq, topk), np.inf, np.float32)
-        if nq == 0:
-            return idx, dist
-        hits, _ = self._handle().search(q, nprobe, c)
-        real = (hits != PAD_ID).sum(axis=1)  # (padding follows every real hit)
-        full = real == c
-        if full.any():
-            idx[full], dist[full] = rerank.rerank(q[full], hits[full], topk)
-        for j in np.flatnonzero((real > 0) & ~full):  # a query with fewer hits keeps its padding
-            r = int(real[j])
-            t = min(topk, r)
-            idx[j, :t], dist[j, :t] = (a[0] for a in rerank.rerank(q[j:j + 1], hits[j:j + 1, :r], t))
-        return idx, dist
-
-    def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int, nprobe: int = 8) -> None:
-        """device pointers: queries [nq][dim] f32, results [nq][topk] uint32 / f32; asynchronous on the current stream"""
-        p = self._nprobe(nprobe)
-        t = self._topk(topk)
-        n_q = _count(nq, "nq")
-        if n_q < 0 or n_q >= 1 << 32:
-            raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
-        self._handle().search_device(int(dev_queries), n_q, p, t, int(dev_idx), int(dev_dist))
-
     def close(self) -> None:
         """release the handle and its device state (the next probe or search builds it again); the codes stay"""
         if self._ix is not None:
             self._host_codes = self._ix.codes()
-            self._ix.close()
-            self._ix = None
+            super().close()
 
     # -- file -------------------------------------------------------------------------------
     def save(self, path) -> None:
@@ -300,21 +161,12 @@ class IVFScalarIndex:
                 quantizer = ScalarQuantizer(mn, mx, levels)  # the reference's own checks
             except InvalidParameter as e:
                 raise ValueError(f"corrupt index header: {e}") from None
-
-            def block(count: int, dtype_, what: str) -> np.ndarray:
-                dt = np.dtype(dtype_)
-                raw = f.read(count * dt.itemsize)
-                if len(raw) != count * dt.itemsize:
-                    raise ValueError(f"truncated {what}")
-                return np.frombuffer(raw, dtype=dt)
-
-            coarse = block(nlist * dim, "<f4", "coarse centroids").reshape(nlist, dim)
-            lists = block(n, "<u4", "list ids")
-            codes = block(n * dim, np.uint8, "codes").reshape(n, dim)
-            if f.read(1):
-                raise ValueError("trailing bytes after the codes")
-        if n and int(lists.max()) >= nlist:
-            raise ValueError(f"corrupt index: a list id is outside [0, {nlist})")
+            r = _Reader(f)
+            coarse = r.block(nlist * dim, "<f4", "coarse centroids").reshape(nlist, dim)
+            lists = r.lists(n)
+            codes = r.block(n * dim, np.uint8, "codes").reshape(n, dim)
+            r.end("codes")
+        _check_file_lists(lists, nlist)
         self = cls(coarse, quantizer, Distance(_METRIC_NAMES[metric]))
         self._lists = lists.astype(np.uint32)
         self._host_codes = codes.copy()
