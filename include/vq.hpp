@@ -1028,6 +1028,18 @@ class IvfIndex {
     std::unique_ptr<H, Del> ix_;
     std::size_t n_ = 0, nlist_ = 0, dim_ = 0;
     Distance distance_;
+
+    // the range search of the two indexes of exact distances (IVFFlatIndex, IVFScalarIndex; not IVFPQIndex, whose
+    // distances are approximations)
+    template <int (*Range)(H *, const float *, std::uint32_t, std::uint32_t, const float *, std::uint64_t, vqhip_range **)>
+    RangeResult range(const float *queries, std::size_t nq, const float *radii, std::size_t nprobe, std::uint64_t max_results) const {
+        check_range_args(radii, nq, max_results);
+        check_probe(nprobe, nq);
+        if (nq == 0) return RangeResult{std::vector<std::uint64_t>(1, 0), {}, {}};
+        vqhip_range *r = nullptr;
+        check(Range(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, radii, max_results, &r));
+        return read_range(r);
+    }
 };
 }  // namespace detail
 
@@ -1092,6 +1104,14 @@ class IVFFlatIndex : public detail::IvfIndex<vqhip_ivfflat, vqhip_ivfflat_destro
     }
     Rows rows() const { return rows_; }
 
+    // every row of the nprobe nearest lists within radii[q] of query q (D <= radius as a float comparison; NaN never
+    // hits), CSR and in ascending row id; with nprobe == nlist it is FlatIndex's range_search.  More than max_results
+    // hits: VqError (UNSUPPORTED)
+    RangeResult range_search(const float *queries, std::size_t nq, const float *radii, std::size_t nprobe,
+                             std::uint64_t max_results = std::uint64_t(1) << 28) const {
+        return range<vqhip_ivfflat_range_search>(queries, nq, radii, nprobe, max_results);
+    }
+
     // rows appended in order: list_ids [n] < nlist, rows [n][dim] in the index's row type; returns the first new row id
     std::size_t add(const std::uint32_t *list_ids, const void *rows, std::size_t n) {
         check_add(list_ids, n, "rows");
@@ -1121,6 +1141,12 @@ class IVFScalarIndex
         adopt(ix, nlist, dim, distance);
     }
     const ScalarQuantizer &quantizer() const { return quantizer_; }
+
+    // IVFFlatIndex's range_search over the dequantized rows; with nprobe == nlist it is ScalarIndex's range_search
+    RangeResult range_search(const float *queries, std::size_t nq, const float *radii, std::size_t nprobe,
+                             std::uint64_t max_results = std::uint64_t(1) << 28) const {
+        return range<vqhip_ivfsq_range_search>(queries, nq, radii, nprobe, max_results);
+    }
 
     // rows appended in order: list_ids [n] < nlist, codes [n][dim] (every byte value is legal); returns the first new row id
     std::size_t add_codes(const std::uint32_t *list_ids, const std::uint8_t *codes, std::size_t n) {

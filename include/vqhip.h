@@ -560,7 +560,8 @@ int vqhip_sqindex_rerank(vqhip_sqindex *x, const float *queries, uint32_t nq, co
                          uint32_t topk, uint32_t *idx_out, float *dist_out);
 
 /* ---- exact range search over the flat and the scalar index (range.hpp) ------------------------
- * No reference counterpart.  Per query q with radius r_q (one f32 per query, radii [nq] in HOST memory in both forms):
+ * No reference counterpart.  (The inverted-file forms, vqhip_ivfflat_range_search and vqhip_ivfsq_range_search, are
+ * declared with their indexes below and return the same vqhip_range.)  Per query q with radius r_q (one f32 per query, radii [nq] in HOST memory in both forms):
  *   hit     row i is a hit iff D(q, i) <= r_q as an f32 comparison, D being the index's distance exactly as search
  *           reports it (the root for Euclidean, the finished value for cosine).  A NaN distance never hits; r_q = +inf
  *           returns every row whose distance is not NaN; a negative radius returns nothing except where D can be
@@ -686,6 +687,22 @@ int vqhip_ivfflat_search(vqhip_ivfflat *ix, const float *queries, uint32_t nq, u
                          uint32_t *idx_out, float *dist_out);
 int vqhip_ivfflat_search_device(vqhip_ivfflat *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
                                 void *dev_idx, void *dev_dist);
+/* Exact range search over the probed lists (ivf_range.hpp; the result object and its rules are vqhip_flat_range_search's,
+ * above).  P(q), S(q) and D(q, i) are search's at the same nprobe; row i is a hit of query q iff i is in S(q) and
+ * D(q, i) <= radii[q] as an f32 comparison (NaN never hits, +inf returns every non-NaN row of S(q), -0.0 <= 0.0 holds; a
+ * NaN radius is VQHIP_ERR_INVALID_INPUT).  idx holds row ids, ascending within a query -- the positions of an inverted
+ * file are not in row order, so the batch's hits go through a segmented stable radix sort by id -- and dist the bits of
+ * D.  With nprobe == nlist the result equals vqhip_flat_range_search over the rows in add order: lims, idx and distance
+ * bits.  Run-to-run deterministic.  nq = 0 gives lims = [0], an index without rows all-zero lims.  max_results as
+ * above: past it VQHIP_ERR_UNSUPPORTED, *out NULL, the index usable.  Checked in this order before any device work: out,
+ * queries / radii (NULL with nq > 0), max_results, the radii, the index handle, the alignment of dev_queries (4 bytes),
+ * nprobe (search's rule).  radii [nq] is in HOST memory in both forms; both return when the result is complete (one
+ * host wait per batch of search's batches), build or rebuild the device state as search does and take the index's
+ * lock. */
+int vqhip_ivfflat_range_search(vqhip_ivfflat *ix, const float *queries, uint32_t nq, uint32_t nprobe, const float *radii,
+                               uint64_t max_results, vqhip_range **out);
+int vqhip_ivfflat_range_search_device(vqhip_ivfflat *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe,
+                                      const float *radii, uint64_t max_results, vqhip_range **out);
 
 /* ---- inverted-file scalar index: exact distances to SQ codes over the probed lists (k_ivfsq.hip) ---------
  * No reference counterpart.  vqhip_ivfflat with each row kept as one SQ byte per dimension.  An index is fixed by a
@@ -732,6 +749,14 @@ int vqhip_ivfsq_search(vqhip_ivfsq *ix, const float *queries, uint32_t nq, uint3
                        uint32_t *idx_out, float *dist_out);
 int vqhip_ivfsq_search_device(vqhip_ivfsq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
                               void *dev_idx, void *dev_dist);
+/* vqhip_ivfflat_range_search over the decoded rows: the same stage behind this index's distances.  Two identities follow,
+ * as for search: at every nprobe the result equals vqhip_ivfflat_range_search (dtype 0, same C and metric) over the rows
+ * vqhip_sq_decode gives for the codes, in the same lists; with nprobe == nlist it equals vqhip_sqindex_range_search over
+ * the codes in add order -- lims, idx and distance bits. */
+int vqhip_ivfsq_range_search(vqhip_ivfsq *ix, const float *queries, uint32_t nq, uint32_t nprobe, const float *radii,
+                             uint64_t max_results, vqhip_range **out);
+int vqhip_ivfsq_range_search_device(vqhip_ivfsq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, const float *radii,
+                                    uint64_t max_results, vqhip_range **out);
 
 /* ---- TSVQ ----------------------------------------------------------------------------
  * build replaces TSVQNode::build (src/tsvq.rs:31-115); the tree comes back flattened in

@@ -1,6 +1,7 @@
 """What ``IVFPQIndex``, ``IVFFlatIndex`` and ``IVFScalarIndex`` share: the coarse centroids and list ids, the checks of
 queries, ``nprobe`` and ``topk``, probe / search / rerank over the device handle, and the readers of the index files.
-A subclass keeps its payload (codes or rows), its add paths, ``_handle``, ``close`` and its file layout."""
+A subclass keeps its payload (codes or rows), its add paths, ``_handle``, ``close`` and its file layout.
+``IVFRangeMixin`` adds the range search of the two indexes whose distances are exact (not ``IVFPQIndex``)."""
 from __future__ import annotations
 
 import operator
@@ -10,6 +11,7 @@ import numpy as np
 from . import _lib
 from .distance import Distance
 from .errors import DimensionMismatch, InvalidParameter
+from .flat import DEFAULT_MAX_RESULTS, _max_results, _radii
 
 MAX_NLIST = 65536
 MAX_PROBE = 1024
@@ -247,3 +249,33 @@ class IVFIndexBase:
         if self._ix is not None:
             self._ix.close()
             self._ix = None
+
+
+class IVFRangeMixin:
+    """range search over the probed lists, for an IVFIndexBase whose distances are exact (IVFFlatIndex, IVFScalarIndex):
+    ``S(q)`` and ``D(q, i)`` are `search`'s at the same nprobe"""
+
+    def range_search(self, queries, radius, nprobe: int = 8, max_results: int = DEFAULT_MAX_RESULTS):
+        """every row of the nprobe nearest lists within `radius` of each query: row i is a hit of query q iff its list is
+        probed and D(q, i) <= radius[q] as a float32 comparison (NaN distances never hit).  `radius` is a scalar or nq
+        values.  Returns (lims uint64 (nq + 1,), idx uint32 (total,), dist float32 (total,)): the hits of query q are
+        idx[lims[q]:lims[q + 1]], in ascending row id.  More than `max_results` hits in all: FfiError (ERR_UNSUPPORTED)."""
+        q = self._queries(queries)
+        r = _radii(radius, q.shape[0])
+        p = self._nprobe(nprobe)
+        m = _max_results(max_results)
+        if q.shape[0] == 0:
+            return np.zeros(1, np.uint64), np.empty(0, np.uint32), np.empty(0, np.float32)
+        return self._handle().range_search(q, p, r, m).read()
+
+    def range_search_device(self, dev_queries: int, nq: int, radius, nprobe: int = 8,
+                            max_results: int = DEFAULT_MAX_RESULTS) -> "_lib.RangeResult":
+        """`range_search` with the queries [nq][dim] f32 at a device pointer (4-byte aligned) and the result left on the
+        device: a RangeResult (.total, .lims, .device_pointers(), .read()).  Returns when the result is complete."""
+        n_q = _count(nq, "nq")
+        if n_q < 0 or n_q >= 1 << 32:
+            raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
+        r = _radii(radius, n_q)
+        p = self._nprobe(nprobe)
+        m = _max_results(max_results)
+        return self._handle().range_search_device(int(dev_queries), n_q, p, r, m)

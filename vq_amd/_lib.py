@@ -198,6 +198,8 @@ SIGNATURES = {
     "vqhip_ivfflat_probe": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p]),
     "vqhip_ivfflat_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _f32p]),
     "vqhip_ivfflat_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "vqhip_ivfflat_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _vpp]),
+    "vqhip_ivfflat_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _vpp]),
     "vqhip_ivfsq_create": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_int, _vpp]),
     "vqhip_ivfsq_destroy": (C.c_int, [_vp]),
     "vqhip_ivfsq_add_codes": (C.c_int, [_vp, _u32p, _u8p, C.c_uint64]),
@@ -208,6 +210,8 @@ SIGNATURES = {
     "vqhip_ivfsq_probe": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p]),
     "vqhip_ivfsq_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _f32p]),
     "vqhip_ivfsq_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "vqhip_ivfsq_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _vpp]),
+    "vqhip_ivfsq_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _vpp]),
     "vqhip_ivfpq_create_ex": (C.c_int, [_f32p, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
                                         _vpp]),
     "vqhip_ivfpq_flags": (C.c_int, [_vp, _u32p]),
@@ -822,9 +826,10 @@ class RangeResult(Handle):
         return self.lims.copy(), idx, dist
 
 
-def _range_call(fn, raw, queries, nq: int, radii: np.ndarray, max_results: int) -> RangeResult:
+def _range_call(fn, raw, queries, nq: int, radii: np.ndarray, max_results: int, *front) -> RangeResult:
+    """one range call of the C ABI; front: the arguments an index has between nq and the radii (nprobe)"""
     h = C.c_void_p()
-    check(fn(raw, queries, int(nq), ptr(radii, _f32p), int(max_results), C.byref(h)))
+    check(fn(raw, queries, int(nq), *front, ptr(radii, _f32p), int(max_results), C.byref(h)))
     return RangeResult(h)
 
 
@@ -996,6 +1001,16 @@ class _IVFHandle(Handle):
                                         C.c_void_p(dev_idx), C.c_void_p(dev_dist)))
 
 
+class _IVFExactHandle(_IVFHandle):
+    """the two inverted-file handles of exact distances: they also answer range queries"""
+
+    def range_search(self, q: np.ndarray, nprobe: int, radii: np.ndarray, max_results: int) -> RangeResult:
+        return _range_call(self._fn("range_search"), self.raw, ptr(q, _f32p), q.shape[0], radii, max_results, int(nprobe))
+
+    def range_search_device(self, dev_queries: int, nq: int, nprobe: int, radii: np.ndarray, max_results: int) -> RangeResult:
+        return _range_call(self._fn("range_search_device"), self.raw, C.c_void_p(dev_queries), nq, radii, max_results, int(nprobe))
+
+
 class IVFPQ(_IVFHandle):
     """vqhip_ivfpq: inverted-file PQ index -- coarse centroids, codebooks, rows in lists (k_ivf.hip).  Create, add and
     list_sizes are host-only; the device state is built by the first probe or search.  flags: IVF_RESIDUAL for lists
@@ -1031,7 +1046,7 @@ class IVFPQ(_IVFHandle):
         return int(n.value), int(nlist.value), int(dim.value), int(m.value), int(k.value), int(metric.value)
 
 
-class IVFFlat(_IVFHandle):
+class IVFFlat(_IVFExactHandle):
     """vqhip_ivfflat: inverted-file flat index -- coarse centroids, f32 or f16 rows in lists, exact distances over the
     probed lists (k_ivfflat.hip).  Create, add, info and list_sizes are host-only; the device state is built by the first
     probe or search."""
@@ -1059,7 +1074,7 @@ class IVFFlat(_IVFHandle):
         return int(n.value), int(nlist.value), int(dim.value), int(dtype.value), int(metric.value)
 
 
-class IVFSQ(_IVFHandle):
+class IVFSQ(_IVFExactHandle):
     """vqhip_ivfsq: inverted-file scalar index -- coarse centroids, a ScalarQuantizer's u8 codes in lists, exact distances
     to the decoded rows over the probed lists (k_ivfsq.hip).  Create, add_codes, codes, info and list_sizes are host-only;
     add_rows encodes on the device; the device state is built by the first probe or search."""

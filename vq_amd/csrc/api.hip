@@ -3825,7 +3825,8 @@ int vqhip_ivfpq_search_device(vqhip_ivfpq *ix, const void *dev_queries, uint32_t
 // codes (dim bytes), with the rows' norms under the cosines.  They differ in the norms kernel and the search launch.
 struct IvfExact : IvfLists {
     DevBuf d_rnorm;
-    DevBuf qnorm, inv, lists;  // per-call workspaces
+    DevBuf qnorm, inv, lists;      // per-call workspaces
+    DevBuf radii, range_ws, stage;  // range search: the radii, the stage's counts and offsets, its staging areas
 
     // queries_dev [nq][dim] f32 -> [nq][topk] results on the device, enqueued on s, in ivf_batch's batches;
     // launch(Q, qn or NULL, nb, batch, idx_dev, dist_dev) searches one batch
@@ -3851,6 +3852,39 @@ struct IvfExact : IvfLists {
         }
         return VQHIP_OK;
     }
+
+    // queries_dev [nq][dim] f32 and the radii (this->radii, [nq]) -> *out, complete on return, in search_batches' batches;
+    // launch(Q, qn or NULL, nb, batch, q0, radii of the batch) runs one batch's distances and the range stage
+    template <class Launch>
+    int range_batches(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint64_t max_results, RangeOut *out, hipStream_t s,
+                      Launch &&launch) {
+        VQ_TRY(launch_ivff_range_begin(out, nq, max_results, s));
+        if (n == 0) {  // no rows: every query's range is empty
+            VQ_HIP(hipMemsetAsync(out->lims.p, 0, ((size_t)nq + 1) * 8, s));
+            VQ_HIP(hipStreamSynchronize(s));
+            return VQHIP_OK;
+        }
+        IvfBatch b;
+        VQ_TRY(ivf_batch(this, nq, nprobe, 0, &b));
+        VQ_TRY(inv.ensure((size_t)b.nb_max * nprobe * 4));
+        VQ_TRY(lists.ensure(ivfflat_lists_bytes(nlist)));
+        VQ_TRY(state.ensure(knn_state_bytes(b.nb_max)));
+        VQ_TRY(range_ws.ensure(ivff_range_ws_bytes(b.wstride, b.nb_max)));
+        const float *qn = nullptr;
+        if (vq_is_cos(metric)) {  // once per call
+            VQ_TRY(qnorm.ensure((size_t)nq * 4));
+            VQ_TRY(launch_knn_norms(queries_dev, 0, nq, dim, qnorm.as<float>(), s));
+            qn = qnorm.as<float>();
+        }
+        for (uint32_t q0 = 0; q0 < nq; q0 += b.nb_max) {
+            const uint32_t nb = std::min(b.nb_max, nq - q0);
+            const float *Q = queries_dev + (size_t)q0 * dim;
+            VQ_TRY(ivf_probe_enqueue(this, Q, nb, nprobe, probe.as<uint32_t>(), s));
+            VQ_TRY(launch(Q, qn ? qn + q0 : nullptr, nb, b, q0, radii.as<float>() + q0));
+        }
+        VQ_HIP(hipStreamSynchronize(s));
+        return VQHIP_OK;
+    }
 };
 
 struct vqhip_ivfflat : IvfExact {
@@ -3871,6 +3905,15 @@ struct vqhip_ivfflat : IvfExact {
                                          nlist, max_list, Q, qn, probe.as<uint32_t>(), nb, nprobe, topk, ivf_chunk((uint64_t)nb * b.per_q),
                                          b.wstride, W.as<float>(), pref.as<uint32_t>(), seg.as<uint32_t>(), inv.as<uint32_t>(),
                                          lists.as<uint32_t>(), state.p, cand.as<unsigned long long>(), idx_b, dist_b, s);
+        });
+    }
+    int range_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint64_t max_results, RangeOut *out, hipStream_t s) {
+        return range_batches(queries_dev, nq, nprobe, max_results, out, s,
+                             [&](const float *Q, const float *qn, uint32_t nb, const IvfBatch &b, uint32_t q0, const float *rad) {
+            return launch_ivfflat_range(metric, d_payload.p, dtype, dim, d_rnorm.as<float>(), d_ids.as<uint32_t>(), n, d_off.as<uint32_t>(),
+                                        nlist, max_list, Q, qn, probe.as<uint32_t>(), nb, nprobe, ivf_chunk((uint64_t)nb * b.per_q),
+                                        b.wstride, W.as<float>(), pref.as<uint32_t>(), seg.as<uint32_t>(), inv.as<uint32_t>(),
+                                        lists.as<uint32_t>(), state.p, q0, rad, range_ws.p, &stage, max_results, out, s);
         });
     }
 };
@@ -3897,7 +3940,52 @@ struct vqhip_ivfsq : IvfExact {
                                        inv.as<uint32_t>(), lists.as<uint32_t>(), state.p, cand.as<unsigned long long>(), idx_b, dist_b, s);
         });
     }
+    int range_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint64_t max_results, RangeOut *out, hipStream_t s) {
+        return range_batches(queries_dev, nq, nprobe, max_results, out, s,
+                             [&](const float *Q, const float *qn, uint32_t nb, const IvfBatch &b, uint32_t q0, const float *rad) {
+            return launch_ivfsq_range(metric, d_payload.as<uint8_t>(), dim, mn, step, d_rnorm.as<float>(), d_ids.as<uint32_t>(), n,
+                                      d_off.as<uint32_t>(), nlist, max_list, Q, qn, probe.as<uint32_t>(), nb, nprobe,
+                                      ivf_chunk((uint64_t)nb * b.per_q), b.wstride, W.as<float>(), pref.as<uint32_t>(), seg.as<uint32_t>(),
+                                      inv.as<uint32_t>(), lists.as<uint32_t>(), state.p, q0, rad, range_ws.p, &stage, max_results, out, s);
+        });
+    }
 };
+
+// One range call on an inverted-file flat or scalar index: range_args' checks (no device, no index), nprobe as search
+// checks it, then the index's device, the calling thread's stream and the device state as search builds it; the queries
+// (host: through ix->q) and the radii go up and range_enqueue leaves *out complete.
+template <class T>
+static int ivf_range(T *ix, const void *queries, bool host, uint32_t nq, uint32_t nprobe, const float *radii, uint64_t max_results,
+                     vqhip_range **out) {
+    VQ_TRY(range_args(queries, radii, nq, max_results, out));
+    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (!host && (reinterpret_cast<uintptr_t>(queries) & 3)) return fail(VQHIP_ERR_INVALID_INPUT, "queries are not 4-byte aligned");
+    Entry in(ix->sync);  // (n changes under add: read under the lock)
+    VQ_TRY(ivf_check_probe(ix, nprobe));
+    VQ_TRY(require_gfx950());
+    VQ_TRY(ivf_device(ix));
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    std::unique_ptr<vqhip_range> r(new vqhip_range());
+    const float *qdev = reinterpret_cast<const float *>(queries);
+    if (nq) {
+        VQ_TRY(ix->ready(s));
+        if (host) {
+            VQ_TRY(ix->q.ensure((size_t)nq * ix->dim * 4));
+            VQ_HIP(hipMemcpyAsync(ix->q.p, queries, (size_t)nq * ix->dim * 4, hipMemcpyHostToDevice, s));
+            qdev = ix->q.template as<float>();
+        }
+        VQ_TRY(ix->radii.ensure((size_t)nq * 4));
+        VQ_HIP(hipMemcpyAsync(ix->radii.p, radii, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+        VQ_TRY(ix->range_enqueue(qdev, nq, nprobe, max_results, &r->r, s));  // (every exit of the driver has waited for s)
+    } else {
+        VQ_TRY(launch_ivff_range_begin(&r->r, 0, max_results, s));
+        VQ_HIP(hipStreamSynchronize(s));
+    }
+    in.synced();
+    *out = r.release();
+    return VQHIP_OK;
+}
 
 extern "C" {
 
@@ -3962,6 +4050,20 @@ int vqhip_ivfflat_search_device(vqhip_ivfflat *ix, const void *dev_queries, uint
                                 void *dev_idx, void *dev_dist) {
     VQ_API_BEGIN
     return ivf_search_device(ix, dev_queries, nq, nprobe, topk, dev_idx, dev_dist);
+    VQ_API_END
+}
+
+int vqhip_ivfflat_range_search(vqhip_ivfflat *ix, const float *queries, uint32_t nq, uint32_t nprobe, const float *radii,
+                               uint64_t max_results, vqhip_range **out) {
+    VQ_API_BEGIN
+    return ivf_range(ix, queries, true, nq, nprobe, radii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_ivfflat_range_search_device(vqhip_ivfflat *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, const float *radii,
+                                      uint64_t max_results, vqhip_range **out) {
+    VQ_API_BEGIN
+    return ivf_range(ix, dev_queries, false, nq, nprobe, radii, max_results, out);
     VQ_API_END
 }
 
@@ -4058,6 +4160,20 @@ int vqhip_ivfsq_search_device(vqhip_ivfsq *ix, const void *dev_queries, uint32_t
                               void *dev_dist) {
     VQ_API_BEGIN
     return ivf_search_device(ix, dev_queries, nq, nprobe, topk, dev_idx, dev_dist);
+    VQ_API_END
+}
+
+int vqhip_ivfsq_range_search(vqhip_ivfsq *ix, const float *queries, uint32_t nq, uint32_t nprobe, const float *radii,
+                             uint64_t max_results, vqhip_range **out) {
+    VQ_API_BEGIN
+    return ivf_range(ix, queries, true, nq, nprobe, radii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_ivfsq_range_search_device(vqhip_ivfsq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, const float *radii,
+                                    uint64_t max_results, vqhip_range **out) {
+    VQ_API_BEGIN
+    return ivf_range(ix, dev_queries, false, nq, nprobe, radii, max_results, out);
     VQ_API_END
 }
 

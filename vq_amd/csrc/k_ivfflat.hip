@@ -19,8 +19,11 @@
 //   k_ivff_hist    the key-space histogram of W[q][0 .. |S(q)|) over the range the two kernels found (integer atomics)
 //   launch_topk_select over IvffSource: IvfSource's positions and ids, KnnSource's bins.
 // Which kernel computes a pair depends on the batch; both run one pair's operations in one order, so the bits do not.
+// A range search (launch_ivfflat_range) runs the plan and the two distance kernels as they are and then the range stage
+// over W (ivf_range.hpp) in place of the histogram and the selection.
 #include "common.hpp"
 #include "ivf_plan.hpp"
+#include "ivf_range.hpp"
 #include "kernels.hpp"
 #include "knn_tile.hpp"
 #include "topk.hpp"
@@ -427,21 +430,24 @@ int launch_ivff_select(const IvffPlan &p, const float *W, uint64_t wstride, cons
     return launch_topk_select(src, nb, topk, 0, st, cand, idx_out, dist_out, stream);
 }
 
-// One batch of nb <= 1024 queries (queries [nb][d] f32, qnorm [nb] under the cosines) whose probe lists
-// (probe [nb][nprobe], launch_knn_search) are on the device.  X / rnorm / ids / off: the index in list order.  W
-// [nb][wstride] with wstride >= every |S(q)|; pref [nb][nprobe + 1], seg and inv [nb][nprobe], lists >=
-// ivfflat_lists_bytes(nlist), state >= knn_state_bytes(nb), cand >= topk_cand_bytes(nb); max_list: the rows of the
-// largest list.  Results [nb][topk] on the device.
-int launch_ivfflat_search(int metric, const void *X, int dtype, uint32_t d, const float *rnorm, const uint32_t *ids,
-                          const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
-                          const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
-                          float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state,
-                          unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream) {
-    if (nb == 0) return VQHIP_OK;
-    IvffPlan p;
-    VQ_TRY(launch_ivff_plan(off, nlist, max_list, probe, nb, nprobe, topk, pref, seg, inv, lists, state, &p, stream));
+// The range stage behind the distance passes, shared with k_ivfsq.hip (ivf_range.hpp).
+size_t ivff_range_ws_bytes(uint64_t wstride, uint32_t nb) { return ivfr_ws_size(wstride, nb); }
+int launch_ivff_range(const float *W, uint64_t wstride, const uint32_t *pref, const uint32_t *seg, const uint32_t *ids, uint64_t n,
+                      uint32_t nb, uint32_t nprobe, uint32_t q0, const float *radii, void *range_ws, DevBuf *stage,
+                      uint64_t max_results, RangeOut *out, hipStream_t stream) {
+    return ivfr_batch(W, wstride, pref, seg, ids, n, nb, nprobe, q0, radii, range_ws, stage, max_results, out, stream);
+}
+int launch_ivff_range_begin(RangeOut *out, uint32_t nq, uint64_t max_results, hipStream_t stream) {
+    return range_begin(out, nq, max_results, stream);
+}
+
+// the two distance passes of a batch behind its plan: every D(q, i) of the probed lists into W, the key range into p
+static int ivfflat_distances(const IvffPlan &p, int metric, const void *X, int dtype, uint32_t d, const float *rnorm, const uint32_t *off,
+                             uint32_t nlist, const float *queries, const float *qnorm, const uint32_t *probe, uint32_t nb,
+                             uint32_t nprobe, uint32_t chunk, uint64_t wstride, float *W, const uint32_t *pref, const uint32_t *seg,
+                             const uint32_t *inv, hipStream_t stream) {
     const uint64_t items = (wstride + chunk - 1) / chunk;
-    VQ_TRY(ivff_dispatch(metric, dtype, [&](auto mtag, auto rtag) -> int {
+    return ivff_dispatch(metric, dtype, [&](auto mtag, auto rtag) -> int {
         using RT = std::remove_const_t<std::remove_pointer_t<decltype(rtag)>>;
         constexpr int M = decltype(mtag)::value;
         if (p.tiles_max > 0) {
@@ -457,8 +463,42 @@ int launch_ivfflat_search(int metric, const void *X, int dtype, uint32_t d, cons
             VQ_LAUNCH_CHECK("k_ivff_scan");
         }
         return VQHIP_OK;
-    }));
+    });
+}
+
+// One batch of nb <= 1024 queries (queries [nb][d] f32, qnorm [nb] under the cosines) whose probe lists
+// (probe [nb][nprobe], launch_knn_search) are on the device.  X / rnorm / ids / off: the index in list order.  W
+// [nb][wstride] with wstride >= every |S(q)|; pref [nb][nprobe + 1], seg and inv [nb][nprobe], lists >=
+// ivfflat_lists_bytes(nlist), state >= knn_state_bytes(nb), cand >= topk_cand_bytes(nb); max_list: the rows of the
+// largest list.  Results [nb][topk] on the device.
+int launch_ivfflat_search(int metric, const void *X, int dtype, uint32_t d, const float *rnorm, const uint32_t *ids,
+                          const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
+                          const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
+                          float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state,
+                          unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream) {
+    if (nb == 0) return VQHIP_OK;
+    IvffPlan p;
+    VQ_TRY(launch_ivff_plan(off, nlist, max_list, probe, nb, nprobe, topk, pref, seg, inv, lists, state, &p, stream));
+    VQ_TRY(ivfflat_distances(p, metric, X, dtype, d, rnorm, off, nlist, queries, qnorm, probe, nb, nprobe, chunk, wstride, W, pref, seg,
+                             inv, stream));
     return launch_ivff_select(p, W, wstride, pref, seg, ids, nb, nprobe, topk, cand, idx_out, dist_out, stream);
+}
+
+// launch_ivfflat_search's batch with the range stage behind the distances: the batch's hits (radii [nb] on the device)
+// go into *out behind the out->total it has, as queries q0 .. q0 + nb of the result.  n: the index's rows; range_ws >=
+// ivff_range_ws_bytes(wstride, nb).  The plan's topk check is given 1; the key range the distance passes write into
+// state is not read.  Waits for the stream once.
+int launch_ivfflat_range(int metric, const void *X, int dtype, uint32_t d, const float *rnorm, const uint32_t *ids, uint64_t n,
+                         const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
+                         const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref,
+                         uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state, uint32_t q0, const float *radii, void *range_ws,
+                         DevBuf *stage, uint64_t max_results, RangeOut *out, hipStream_t stream) {
+    if (nb == 0) return VQHIP_OK;
+    IvffPlan p;
+    VQ_TRY(launch_ivff_plan(off, nlist, max_list, probe, nb, nprobe, 1, pref, seg, inv, lists, state, &p, stream));
+    VQ_TRY(ivfflat_distances(p, metric, X, dtype, d, rnorm, off, nlist, queries, qnorm, probe, nb, nprobe, chunk, wstride, W, pref, seg,
+                             inv, stream));
+    return launch_ivff_range(W, wstride, pref, seg, ids, n, nb, nprobe, q0, radii, range_ws, stage, max_results, out, stream);
 }
 
 }  // namespace vqhip

@@ -11,6 +11,8 @@
 //   k_ivfsq_scan        k_ivff_scan with the row walked as dwords (W4) or bytes
 //   launch_ivff_select  k_ivff_hist and the selection stage over IvffSource (k_ivfflat.hip)
 // Which kernel computes a pair depends on the batch; both run one pair's operations in one order, so the bits do not.
+// A range search (launch_ivfsq_range) puts the range stage (launch_ivff_range) behind the same
+// plan and distance passes.
 #include "common.hpp"
 #include "ivf_plan.hpp"
 #include "kernels.hpp"
@@ -264,21 +266,14 @@ int ivfsq_dispatch(int metric, F &&f) {
 
 }  // namespace
 
-// One batch of nb <= 1024 queries (queries [nb][d] f32, qnorm [nb] under the cosines) whose probe lists
-// (probe [nb][nprobe], launch_knn_search) are on the device.  C / rnorm / ids / off: the index in list order, C [n][d]
-// u8 with v(c) = mn + (float)c * step, rnorm from launch_sq_norms over C.  The workspaces are launch_ivfflat_search's.
-// Results [nb][topk] on the device.
-int launch_ivfsq_search(int metric, const uint8_t *C, uint32_t d, float mn, float step, const float *rnorm, const uint32_t *ids,
-                        const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
-                        const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
-                        float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state,
-                        unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream) {
-    if (nb == 0) return VQHIP_OK;
-    IvffPlan p;
-    VQ_TRY(launch_ivff_plan(off, nlist, max_list, probe, nb, nprobe, topk, pref, seg, inv, lists, state, &p, stream));
+// the two distance passes of a batch behind its plan: every D(q, i) of the probed lists into W, the key range into p
+static int ivfsq_distances(const IvffPlan &p, int metric, const uint8_t *C, uint32_t d, float mn, float step, const float *rnorm,
+                           const uint32_t *off, uint32_t nlist, const float *queries, const float *qnorm, const uint32_t *probe,
+                           uint32_t nb, uint32_t nprobe, uint32_t chunk, uint64_t wstride, float *W, const uint32_t *pref,
+                           const uint32_t *seg, const uint32_t *inv, hipStream_t stream) {
     const uint64_t items = (wstride + chunk - 1) / chunk;
     const int lw = sq_load_width(C, d);
-    VQ_TRY(ivfsq_dispatch(metric, [&](auto mtag) -> int {
+    return ivfsq_dispatch(metric, [&](auto mtag) -> int {
         constexpr int M = decltype(mtag)::value;
         if (p.tiles_max > 0) {
             const dim3 grid((uint32_t)p.tiles_max, (uint32_t)p.cols);
@@ -301,8 +296,39 @@ int launch_ivfsq_search(int metric, const uint8_t *C, uint32_t d, float mn, floa
             VQ_LAUNCH_CHECK("k_ivfsq_scan");
         }
         return VQHIP_OK;
-    }));
+    });
+}
+
+// One batch of nb <= 1024 queries (queries [nb][d] f32, qnorm [nb] under the cosines) whose probe lists
+// (probe [nb][nprobe], launch_knn_search) are on the device.  C / rnorm / ids / off: the index in list order, C [n][d]
+// u8 with v(c) = mn + (float)c * step, rnorm from launch_sq_norms over C.  The workspaces are launch_ivfflat_search's.
+// Results [nb][topk] on the device.
+int launch_ivfsq_search(int metric, const uint8_t *C, uint32_t d, float mn, float step, const float *rnorm, const uint32_t *ids,
+                        const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
+                        const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
+                        float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state,
+                        unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream) {
+    if (nb == 0) return VQHIP_OK;
+    IvffPlan p;
+    VQ_TRY(launch_ivff_plan(off, nlist, max_list, probe, nb, nprobe, topk, pref, seg, inv, lists, state, &p, stream));
+    VQ_TRY(ivfsq_distances(p, metric, C, d, mn, step, rnorm, off, nlist, queries, qnorm, probe, nb, nprobe, chunk, wstride, W, pref, seg,
+                           inv, stream));
     return launch_ivff_select(p, W, wstride, pref, seg, ids, nb, nprobe, topk, cand, idx_out, dist_out, stream);
+}
+
+// launch_ivfsq_search's batch with the range stage behind the distances (launch_ivff_range, k_ivfflat.hip): the arguments
+// of launch_ivfflat_range with the rows as SQ codes.
+int launch_ivfsq_range(int metric, const uint8_t *C, uint32_t d, float mn, float step, const float *rnorm, const uint32_t *ids, uint64_t n,
+                       const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
+                       const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref,
+                       uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state, uint32_t q0, const float *radii, void *range_ws,
+                       DevBuf *stage, uint64_t max_results, RangeOut *out, hipStream_t stream) {
+    if (nb == 0) return VQHIP_OK;
+    IvffPlan p;
+    VQ_TRY(launch_ivff_plan(off, nlist, max_list, probe, nb, nprobe, 1, pref, seg, inv, lists, state, &p, stream));
+    VQ_TRY(ivfsq_distances(p, metric, C, d, mn, step, rnorm, off, nlist, queries, qnorm, probe, nb, nprobe, chunk, wstride, W, pref, seg,
+                           inv, stream));
+    return launch_ivff_range(W, wstride, pref, seg, ids, n, nb, nprobe, q0, radii, range_ws, stage, max_results, out, stream);
 }
 
 }  // namespace vqhip

@@ -351,6 +351,27 @@ int launch_sq_range(int metric, const uint8_t *C, uint64_t n, uint32_t d, float 
                     const float *queries_dev, const float *qnorm_dev, uint32_t nq, const float *radii_dev, uint64_t max_results,
                     float *dist_ws, void *state_ws, void *range_ws, RangeOut *out, hipStream_t stream);
 
+// exact range search over the probed lists (ivf_range.hpp behind k_ivfflat.hip and k_ivfsq.hip): launch_ivfflat_search's
+// / launch_ivfsq_search's batch with radii [nb] on the device and the range stage in place of the selection.  The
+// batch's hits go into *out (begun by launch_ivff_range_begin) as queries q0 .. q0 + nb, in ascending row id per query; n:
+// the index's rows; range_ws >= ivff_range_ws_bytes(wstride, nb); *stage: the staging areas, grown as needed.  Waits for
+// the stream once per batch.  More than max_results hits: VQHIP_ERR_UNSUPPORTED.
+size_t ivff_range_ws_bytes(uint64_t wstride, uint32_t nb);
+int launch_ivff_range_begin(RangeOut *out, uint32_t nq, uint64_t max_results, hipStream_t stream);
+int launch_ivff_range(const float *W, uint64_t wstride, const uint32_t *pref, const uint32_t *seg, const uint32_t *ids, uint64_t n,
+                      uint32_t nb, uint32_t nprobe, uint32_t q0, const float *radii, void *range_ws, DevBuf *stage,
+                      uint64_t max_results, RangeOut *out, hipStream_t stream);
+int launch_ivfflat_range(int metric, const void *X, int dtype, uint32_t d, const float *rnorm, const uint32_t *ids, uint64_t n,
+                         const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
+                         const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref,
+                         uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state, uint32_t q0, const float *radii, void *range_ws,
+                         DevBuf *stage, uint64_t max_results, RangeOut *out, hipStream_t stream);
+int launch_ivfsq_range(int metric, const uint8_t *C, uint32_t d, float mn, float step, const float *rnorm, const uint32_t *ids, uint64_t n,
+                       const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
+                       const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref,
+                       uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state, uint32_t q0, const float *radii, void *range_ws,
+                       DevBuf *stage, uint64_t max_results, RangeOut *out, hipStream_t stream);
+
 // exact search and rerank over resident SQ codes (k_sqindex.hip): C [n][d] u8, v(c) = mn + (float)c * step decoded on
 // the fly, rnorm [n] the decoded rows' norms (cosine only).  Batches and workspaces as launch_knn_search / _rerank; the
 // query norms come from launch_knn_norms.

@@ -1,5 +1,5 @@
 // range.hpp -- the exact range stage behind vqhip_flat_range_search (k_knn.hip) and vqhip_sqindex_range_search
-// (k_sqindex.hip): a deterministic threshold compaction over the dense [nb][n] f32 distances a batch's distance kernel
+// (k_sqindex.hip), and in part behind the inverted-file range searches (ivf_range.hpp): a deterministic threshold compaction over the dense [nb][n] f32 distances a batch's distance kernel
 // left, with a variable-length result.  Every including file gets its own copy of the kernels (an anonymous namespace: no
 // relocatable device code).  Semantics (include/vqhip.h): row i is a hit of query q iff dist[q][i] <= radii[q] as an f32
 // comparison (NaN never hits, -0.0 <= 0.0 holds); the hits of a query come out in ascending row id.
@@ -208,6 +208,22 @@ inline int range_grow(RangeOut *out, uint64_t need, uint64_t max_results, hipStr
     return VQHIP_OK;
 }
 
+// The host step between a batch's scan and its fill: reads the batch total k_range_scan left at `total` (8 bytes, one
+// stream wait) into *got, holds the result with it against max_results (past it: VQHIP_ERR_UNSUPPORTED) and makes room
+// for it.  out->total is the caller's to advance once the batch's hits are written.
+inline int range_room(const unsigned long long *total, uint32_t nb, uint32_t q0, uint64_t max_results, RangeOut *out, uint64_t *got,
+                      hipStream_t stream) {
+    unsigned long long g = 0;
+    VQ_HIP(hipMemcpyAsync(&g, total, 8, hipMemcpyDeviceToHost, stream));
+    VQ_HIP(hipStreamSynchronize(stream));
+    *got = g;
+    const uint64_t need = out->total + g;
+    if (need > max_results)
+        return fail(VQHIP_ERR_UNSUPPORTED, "range search reached %llu hits after %u of %u queries: more than max_results = %llu",
+                    (unsigned long long)need, q0 + nb, out->nq, (unsigned long long)max_results);
+    return g ? range_grow(out, need, max_results, stream) : VQHIP_OK;
+}
+
 // The stage over one batch: dist [nb][n] on the device (queued on `stream`), radii [nb] on the device, ws >=
 // range_ws_size(n, nb), q0 the batch's first query in the result.  Waits for the stream once.  A batch that takes the
 // result past max_results is VQHIP_ERR_UNSUPPORTED.
@@ -225,15 +241,10 @@ inline int range_batch(const float *dist, uint64_t n, uint32_t nb, uint32_t q0, 
     VQ_LAUNCH_CHECK("k_range_count");
     hipLaunchKernelGGL(k_range_scan, dim3(1), dim3(1024), 0, stream, cnt, nb, nblk, (unsigned long long)out->total, off, lims, total);
     VQ_LAUNCH_CHECK("k_range_scan");
-    unsigned long long got = 0;
-    VQ_HIP(hipMemcpyAsync(&got, total, 8, hipMemcpyDeviceToHost, stream));
-    VQ_HIP(hipStreamSynchronize(stream));
-    const uint64_t need = out->total + got;
-    if (need > max_results)
-        return fail(VQHIP_ERR_UNSUPPORTED, "range search reached %llu hits after %u of %u queries: more than max_results = %llu",
-                    (unsigned long long)need, q0 + nb, out->nq, (unsigned long long)max_results);
+    uint64_t got = 0;
+    VQ_TRY(range_room(total, nb, q0, max_results, out, &got, stream));
     if (got == 0) return VQHIP_OK;
-    VQ_TRY(range_grow(out, need, max_results, stream));
+    const uint64_t need = out->total + got;
     if (vec)
         hipLaunchKernelGGL(k_range_fill<true>, grid, block, 0, stream, dist, n, radii, nblk, cnt, off, (unsigned long long)out->total,
                            out->idx.as<uint32_t>(), out->dist.as<float>());

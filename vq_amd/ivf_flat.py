@@ -27,7 +27,7 @@ import struct
 import numpy as np
 
 from . import _lib
-from ._ivf_common import (MAX_NLIST, PAD_ID, IVFIndexBase, _Reader, _check_coarse, _check_distance,  # noqa: F401
+from ._ivf_common import (MAX_NLIST, PAD_ID, IVFIndexBase, IVFRangeMixin, _Reader, _check_coarse, _check_distance,  # noqa: F401
                           _check_file_lists, _train_coarse)  # (PAD_ID: re-exported)
 from .distance import Distance
 from .errors import DimensionMismatch, InvalidParameter
@@ -48,7 +48,7 @@ def _row_dtype(dtype) -> np.dtype:
     return dt
 
 
-class IVFFlatIndex(IVFIndexBase):
+class IVFFlatIndex(IVFRangeMixin, IVFIndexBase):
     """coarse centroids (nlist, dim) + distance + row dtype, and the rows added to it"""
 
     def __init__(self, coarse_centroids, distance: Distance | None = None, dtype=np.float32):

@@ -33,7 +33,7 @@ import struct
 import numpy as np
 
 from . import _lib
-from ._ivf_common import (MAX_NLIST, IVFIndexBase, _Reader, _check_coarse, _check_distance, _check_file_lists,
+from ._ivf_common import (MAX_NLIST, IVFIndexBase, IVFRangeMixin, _Reader, _check_coarse, _check_distance, _check_file_lists,
                           _train_coarse)
 from .distance import Distance
 from .errors import DimensionMismatch, InvalidParameter
@@ -44,7 +44,7 @@ _HEADER = struct.Struct("<8sIIIffIQ")
 _METRIC_NAMES = ["squared_euclidean", "euclidean", "manhattan", "cosine", "cosine_unclamped"]
 
 
-class IVFScalarIndex(IVFIndexBase):
+class IVFScalarIndex(IVFRangeMixin, IVFIndexBase):
     """coarse centroids (nlist, dim) + ScalarQuantizer + distance, and the rows added to it as codes"""
 
     def __init__(self, coarse_centroids, quantizer: ScalarQuantizer, distance: Distance | None = None):
