@@ -955,7 +955,7 @@ class ScalarIndex {
 };
 
 namespace detail {
-// What the three inverted-file indexes share over their C handles (H and its destroy / list_sizes / probe / search):
+// What the inverted-file indexes share over their C handles (H and its destroy / list_sizes / probe / search):
 // the shape, the add-side and probe-side checks, and the calls whose arguments are the same for every payload.
 template <class H, int (*Destroy)(H *), int (*ListSizes)(H *, std::uint64_t *),
           int (*Probe)(H *, const float *, std::uint32_t, std::uint32_t, std::uint32_t *),
@@ -1167,6 +1167,65 @@ class IVFScalarIndex
 
    private:
     ScalarQuantizer quantizer_;
+};
+
+// Inverted-file index over packed BQ bits (include/vqhip.h, vqhip_ivfbin_*): coarse centroids [nlist][dim], a BinaryQuantizer,
+// rows added as (list id, packed words [ceil(dim / 32)]), as (list id, u8 codes) packed on the host, or as (list id, f32
+// row) packed on the device.  search computes the Hamming distance to the rows of the nprobe lists nearest to the f32
+// query under coarse_distance and reports BinaryIndex's distance for it under `distance` (squared Euclidean, Euclidean or
+// Manhattan; cosine is refused); (row id, distance) pairs [nq][topk], nearest first, ties to the lower row; slots past the
+// probed rows hold (0xFFFFFFFF, +inf); with nprobe == nlist it is BinaryIndex's search.  The constructor, add_packed,
+// add_codes, packed and list_sizes need no device; the arguments are checked before the device is touched.
+class IVFBinaryIndex
+    : public detail::IvfIndex<vqhip_ivfbin, vqhip_ivfbin_destroy, vqhip_ivfbin_list_sizes, vqhip_ivfbin_probe, vqhip_ivfbin_search> {
+   public:
+    IVFBinaryIndex(const float *coarse, std::size_t nlist, std::size_t dim, BinaryQuantizer quantizer = BinaryQuantizer(0.0f, 0, 1),
+                   Distance distance = Distance(Distance::Manhattan), Distance coarse_distance = Distance())
+        : quantizer_(quantizer), coarse_distance_(coarse_distance) {
+        check_nlist(nlist);
+        if (dim == 0 || dim > VQHIP_BINARY_MAX_DIM) throw VqError::InvalidParameter("dim", "must be between 1 and 8192");
+        if (distance.kind() == Distance::CosineDistance)
+            throw VqError::InvalidParameter("distance", "cosine is not a function of the Hamming distance alone");
+        vqhip_ivfbin *ix = nullptr;
+        detail::check(vqhip_ivfbin_create(quantizer_.threshold(), quantizer_.low(), quantizer_.high(), coarse, (std::uint32_t)nlist,
+                                          (std::uint32_t)dim, (int)distance.kind(), (int)coarse_distance.kind(), &ix));
+        adopt(ix, nlist, dim, distance);
+    }
+    const BinaryQuantizer &quantizer() const { return quantizer_; }
+    const char *coarse_distance_metric() const { return coarse_distance_.name(); }
+    std::size_t words_per_row() const { return (dim_ + 31) / 32; }
+
+    // rows appended in order: list_ids [n] < nlist, words [n][words_per_row()], pad bits zero; returns the first new row id
+    std::size_t add_packed(const std::uint32_t *list_ids, const std::uint32_t *words, std::size_t n) {
+        check_add(list_ids, n, "words");
+        if (dim_ % 32) {
+            const std::uint32_t mask = (1u << (dim_ % 32)) - 1u;
+            const std::size_t w = words_per_row();
+            for (std::size_t i = 0; i < n; ++i)
+                if (words[i * w + w - 1] & ~mask) throw VqError::InvalidParameter("words", "a row has a pad bit set");
+        }
+        return added(n, n ? vqhip_ivfbin_add_packed(ix_.get(), list_ids, words, n) : VQHIP_OK);
+    }
+    // codes [n][dim] u8, packed on the host: bit = code >= high
+    std::size_t add_codes(const std::uint32_t *list_ids, const std::uint8_t *codes, std::size_t n) {
+        check_add(list_ids, n, "codes");
+        return added(n, n ? vqhip_ivfbin_add_codes(ix_.get(), list_ids, codes, n) : VQHIP_OK);
+    }
+    // rows [n][dim] f32, packed on the device: bit = x >= threshold; only the words are kept
+    std::size_t add_rows(const std::uint32_t *list_ids, const float *rows, std::size_t n) {
+        check_add(list_ids, n, "rows");
+        return added(n, n ? vqhip_ivfbin_add_rows(ix_.get(), list_ids, rows, n) : VQHIP_OK);
+    }
+    // the words [n][words_per_row()], in add order
+    std::vector<std::uint32_t> packed() const {
+        std::vector<std::uint32_t> out(n_ * words_per_row());
+        detail::check(vqhip_ivfbin_packed(ix_.get(), out.data()));
+        return out;
+    }
+
+   private:
+    BinaryQuantizer quantizer_;
+    Distance coarse_distance_;
 };
 
 // analogue of vq::get_simd_backend (src/lib.rs): names the device backend

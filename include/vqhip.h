@@ -758,6 +758,56 @@ int vqhip_ivfsq_range_search(vqhip_ivfsq *ix, const float *queries, uint32_t nq,
 int vqhip_ivfsq_range_search_device(vqhip_ivfsq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, const float *radii,
                                     uint64_t max_results, vqhip_range **out);
 
+/* ---- inverted-file binary index: Hamming top-k over packed BQ bits in the probed lists (k_ivfbin.hip) ---------
+ * No reference counterpart.  vqhip_ivfflat's probe and schedule over vqhip_binary's codes.  An index is fixed by a
+ * BinaryQuantizer(threshold, low, high) -- the parameters go through vqhip_bq_check, whose status and text create reports
+ * unchanged --, coarse centroids C [nlist][dim] f32 (1 <= nlist <= 65536, 1 <= dim <= 8192), two metrics and, per row i
+ * (ids in add order, n < 2^32 in all), a list id list[i] < nlist and words[i][W] u32, W = ceil(dim / 32), in
+ * vqhip_binary's layout: dimension t in word t / 32, bit t % 32, pad bits zero.  The bit of an f32 element (rows and
+ * queries) is x >= threshold (NaN gives 0, -0.0 equals 0.0), of a u8 code c >= high.
+ *   metric        of the reported distance: squared Euclidean, Euclidean or Manhattan; the cosines are refused exactly
+ *                 as vqhip_binary_create refuses them (VQHIP_ERR_UNSUPPORTED, the same text).
+ *   coarse_metric of the probe (and, above this ABI, of the assignment of rows to lists): any of the five.
+ *   P(q)    = the nprobe lists vqhip_flat_search over C under coarse_metric returns for the f32 query -- the query is
+ *             never binarised for probing: exactly vqhip_ivfflat_probe of an index over (C, coarse_metric).
+ *             1 <= nprobe <= min(nlist, 1024).
+ *   S(q)    = { i : list[i] in P(q) }.
+ *   H(q, i) = popcount(bits(q) xor words[i]).
+ *   D(q, i) = vqhip_binary's reported distance for H: S[H] of the sequential f32 table (S[0] = +0.0, S[j] = S[j - 1] + t,
+ *             t = (high - low)^2, or high - low under Manhattan), sqrtf(S[H]) under Euclidean: Distance::compute of the two
+ *             dequantized vectors bit for bit.
+ *   search  = the topk rows of S(q) by (D, row id) ascending, which is (H, row id): the table and its root are strictly
+ *             increasing.  Ties go to the lower row.  1 <= topk <= min(n, 1024).  If |S(q)| < topk the remaining slots
+ *             hold idx 0xFFFFFFFF and dist +inf, after every real row.  Run-to-run deterministic.
+ * Identity: with nprobe == nlist the result equals vqhip_binary_search over the words in add order (same quantizer and
+ * metric), indices and distance bits.
+ * add_packed takes host words [n][W] and is host-only; a set pad bit is refused with vqhip_binary_create's status and
+ * text (VQHIP_ERR_INVALID_INPUT, "row %llu has a pad bit set", the row counted within the call).  add_codes takes host
+ * u8 codes [n][dim], packs them on the host with c >= high and is host-only.  add_rows takes host f32 rows [n][dim] and
+ * packs them on the device as vqhip_bq_pack does with this threshold; it is the one add that needs the device.  All three
+ * check every list id on the host before anything is stored; several adds equal one add of the concatenation.  packed
+ * copies the words out in add order (words_out [n][W]; host-only).  info: any output pointer may be NULL.  queries
+ * [nq][dim] f32, lists_out [nq][nprobe], idx / dist [nq][topk]; nq = 0 is a no-op; every parameter is checked before any
+ * device work.  Device ownership, the lazy build of the device state (the flat index over C, off, ids ascending within a
+ * list, the words in list order in a buffer the index owns) and its rebuild after an add, the batches, the two forms of
+ * search and the lock are vqhip_ivfflat's.  The host keeps 4 n W bytes, the device 4 n W + 4 n of row ids. */
+typedef struct vqhip_ivfbin vqhip_ivfbin;
+int vqhip_ivfbin_create(float threshold, uint32_t low, uint32_t high, const float *coarse, uint32_t nlist, uint32_t dim,
+                        int metric, int coarse_metric, vqhip_ivfbin **out);
+int vqhip_ivfbin_destroy(vqhip_ivfbin *ix);
+int vqhip_ivfbin_add_packed(vqhip_ivfbin *ix, const uint32_t *list_ids, const uint32_t *words, uint64_t n);
+int vqhip_ivfbin_add_codes(vqhip_ivfbin *ix, const uint32_t *list_ids, const uint8_t *codes, uint64_t n);
+int vqhip_ivfbin_add_rows(vqhip_ivfbin *ix, const uint32_t *list_ids, const float *rows, uint64_t n);
+int vqhip_ivfbin_info(const vqhip_ivfbin *ix, uint64_t *n, uint32_t *nlist, uint32_t *dim, int *metric, int *coarse_metric,
+                      float *threshold, uint32_t *low, uint32_t *high);
+int vqhip_ivfbin_list_sizes(vqhip_ivfbin *ix, uint64_t *sizes);
+int vqhip_ivfbin_packed(vqhip_ivfbin *ix, uint32_t *words_out);
+int vqhip_ivfbin_probe(vqhip_ivfbin *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t *lists_out);
+int vqhip_ivfbin_search(vqhip_ivfbin *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                        uint32_t *idx_out, float *dist_out);
+int vqhip_ivfbin_search_device(vqhip_ivfbin *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                               void *dev_idx, void *dev_dist);
+
 /* ---- TSVQ ----------------------------------------------------------------------------
  * build replaces TSVQNode::build (src/tsvq.rs:31-115); the tree comes back flattened in
  * pre-order (node 0 = root, left subtree, right subtree): centroids [cap][d], left/right

@@ -2,7 +2,7 @@
 encode path of CogitatorTech/vq, and of its elementwise scalar / binary quantizers, behind the
 reference's own Quantizer interface, exact k-NN search over resident rows (FlatIndex), an inverted-file
 index over PQ codes (IVFPQIndex) one over the rows themselves (IVFFlatIndex) and one over SQ codes
-(IVFScalarIndex), a Hamming index over packed BQ codes (BinaryIndex) and an exact index over
+(IVFScalarIndex) and one over packed BQ bits (IVFBinaryIndex), a Hamming index over packed BQ codes (BinaryIndex) and an exact index over
 resident SQ codes (ScalarIndex).
 
 The compute path is libvqhip.so (hand-written HIP for CDNA4, C ABI in include/vqhip.h).
@@ -18,6 +18,7 @@ from ._lib import RangeResult
 from .flat import FlatIndex
 from .ivf import IVFPQIndex
 from .ivf_flat import IVFFlatIndex
+from .ivf_binary import IVFBinaryIndex
 from .ivf_scalar import IVFScalarIndex
 from .pq import ProductQuantizer, fit_codebooks
 from .scalar_index import ScalarIndex
@@ -25,7 +26,7 @@ from .sq import ScalarQuantizer
 from .tsvq import TSVQ
 
 __all__ = [
-    "Distance", "BinaryIndex", "BinaryQuantizer", "FlatIndex", "IVFFlatIndex", "IVFPQIndex", "IVFScalarIndex", "RangeResult", "ScalarIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
+    "Distance", "BinaryIndex", "BinaryQuantizer", "FlatIndex", "IVFBinaryIndex", "IVFFlatIndex", "IVFPQIndex", "IVFScalarIndex", "RangeResult", "ScalarIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
     "InvalidParameter", "InvalidData", "FfiError", "get_simd_backend",
 ]
 

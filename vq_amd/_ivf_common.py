@@ -1,4 +1,4 @@
-"""What ``IVFPQIndex``, ``IVFFlatIndex`` and ``IVFScalarIndex`` share: the coarse centroids and list ids, the checks of
+"""What ``IVFPQIndex``, ``IVFFlatIndex``, ``IVFScalarIndex`` and ``IVFBinaryIndex`` share: the coarse centroids and list ids, the checks of
 queries, ``nprobe`` and ``topk``, probe / search / rerank over the device handle, and the readers of the index files.
 A subclass keeps its payload (codes or rows), its add paths, ``_handle``, ``close`` and its file layout.
 ``IVFRangeMixin`` adds the range search of the two indexes whose distances are exact (not ``IVFPQIndex``)."""
@@ -155,7 +155,11 @@ class IVFIndexBase:
         X = self._add_rows_2d(X)
         if X.shape[0] == 0:
             return np.empty(0, np.uint32)
-        return self.add_rows(_nearest_lists(self._coarse, X, self._distance.metric), X)
+        return self.add_rows(_nearest_lists(self._coarse, X, self._assign_metric()), X)
+
+    def _assign_metric(self) -> int:
+        """the metric that assigns rows to lists in `add`: the one the index probes under"""
+        return self._distance.metric
 
     def _check_list_ids(self, lid: np.ndarray) -> None:
         if lid.size and (lid.dtype.kind not in "iu" or int(lid.min()) < 0 or int(lid.max()) >= self.nlist):

@@ -212,6 +212,17 @@ SIGNATURES = {
     "vqhip_ivfsq_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
     "vqhip_ivfsq_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _vpp]),
     "vqhip_ivfsq_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _vpp]),
+    "vqhip_ivfbin_create": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, _vpp]),
+    "vqhip_ivfbin_destroy": (C.c_int, [_vp]),
+    "vqhip_ivfbin_add_packed": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64]),
+    "vqhip_ivfbin_add_codes": (C.c_int, [_vp, _u32p, _u8p, C.c_uint64]),
+    "vqhip_ivfbin_add_rows": (C.c_int, [_vp, _u32p, _f32p, C.c_uint64]),
+    "vqhip_ivfbin_info": (C.c_int, [_vp, _u64p, _u32p, _u32p, C.POINTER(C.c_int), C.POINTER(C.c_int), _f32p, _u32p, _u32p]),
+    "vqhip_ivfbin_list_sizes": (C.c_int, [_vp, _u64p]),
+    "vqhip_ivfbin_packed": (C.c_int, [_vp, _u32p]),
+    "vqhip_ivfbin_probe": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p]),
+    "vqhip_ivfbin_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "vqhip_ivfbin_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
     "vqhip_ivfpq_create_ex": (C.c_int, [_f32p, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
                                         _vpp]),
     "vqhip_ivfpq_flags": (C.c_int, [_vp, _u32p]),
@@ -1109,6 +1120,52 @@ class IVFSQ(_IVFExactHandle):
     def codes(self) -> np.ndarray:
         out = np.empty((self.info()[0], self.dim), np.uint8)
         check(load().vqhip_ivfsq_codes(self.raw, ptr(out, _u8p)))
+        return out
+
+
+class IVFBin(_IVFHandle):
+    """vqhip_ivfbin: inverted-file binary index -- coarse centroids, a BinaryQuantizer's bits packed 32 to a word in lists,
+    Hamming top-k over the probed lists (k_ivfbin.hip).  Create, add_packed, add_codes, packed, info and list_sizes are
+    host-only; add_rows packs on the device; the device state is built by the first probe or search."""
+
+    _prefix = "vqhip_ivfbin"
+    _destroy = "vqhip_ivfbin_destroy"
+
+    def __init__(self, coarse, threshold: float, low: int, high: int, metric: int, coarse_metric: int):
+        c = f32c(coarse)
+        h = C.c_void_p()
+        check(load().vqhip_ivfbin_create(float(threshold), int(low), int(high), ptr(c, _f32p), c.shape[0], c.shape[1], int(metric),
+                                         int(coarse_metric), C.byref(h)))
+        super().__init__(h)
+        self.nlist, self.dim, self.metric, self.coarse_metric = c.shape[0], c.shape[1], int(metric), int(coarse_metric)
+        self.words = (self.dim + 31) // 32
+
+    def add_packed(self, list_ids, words):
+        lid = np.ascontiguousarray(list_ids, dtype=np.uint32)
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        check(load().vqhip_ivfbin_add_packed(self.raw, ptr(lid, _u32p), ptr(w, _u32p), lid.shape[0]))
+
+    def add_codes(self, list_ids, codes):
+        lid = np.ascontiguousarray(list_ids, dtype=np.uint32)
+        c = np.ascontiguousarray(codes, dtype=np.uint8)
+        check(load().vqhip_ivfbin_add_codes(self.raw, ptr(lid, _u32p), ptr(c, _u8p), lid.shape[0]))
+
+    def add_rows(self, list_ids, rows):
+        lid = np.ascontiguousarray(list_ids, dtype=np.uint32)
+        r = f32c(rows)
+        check(load().vqhip_ivfbin_add_rows(self.raw, ptr(lid, _u32p), ptr(r, _f32p), lid.shape[0]))
+
+    def info(self):
+        n, nlist, dim, metric, cmetric = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_int(), C.c_int()
+        thr, low, high = C.c_float(), C.c_uint32(), C.c_uint32()
+        check(load().vqhip_ivfbin_info(self.raw, C.byref(n), C.byref(nlist), C.byref(dim), C.byref(metric), C.byref(cmetric),
+                                       C.byref(thr), C.byref(low), C.byref(high)))
+        return (int(n.value), int(nlist.value), int(dim.value), int(metric.value), int(cmetric.value), float(thr.value),
+                int(low.value), int(high.value))
+
+    def packed(self) -> np.ndarray:
+        out = np.empty((self.info()[0], self.words), np.uint32)
+        check(load().vqhip_ivfbin_packed(self.raw, ptr(out, _u32p)))
         return out
 
 

@@ -3458,8 +3458,8 @@ int vqhip_binary_search_device(vqhip_binary *b, const void *dev_queries, uint32_
 }  // extern "C"
 
 // ------------------------------------------------------------------ inverted lists: the shared host layer ----
-// What vqhip_ivfpq, vqhip_ivfflat and vqhip_ivfsq have in common.  Host state: the coarse centroids and every added
-// row's list id and payload (PQ codes, f32 / f16 elements or SQ codes) in add order.  The device state -- a flat index
+// What vqhip_ivfpq, vqhip_ivfflat, vqhip_ivfsq and vqhip_ivfbin have in common.  Host state: the coarse centroids and every added
+// row's list id and payload (PQ codes, f32 / f16 elements, SQ codes or packed BQ words) in add order.  The device state -- a flat index
 // over the centroids and the rows in list order (off / ids / payload) -- is built on the current device by the first
 // probe or search and rebuilt there after an add: a host counting sort gives the order (O(n) per rebuild), and the
 // payload goes up through a staging buffer of at most kIvfflatStage bytes, list order gathered a piece at a time.
@@ -3469,6 +3469,7 @@ struct IvfLists {
     HandleSync sync;
     uint32_t nlist = 0, dim = 0;
     int metric = VQHIP_EUCLIDEAN;
+    int probe_metric = VQHIP_EUCLIDEAN;  // of the flat index over the centroids: `metric`, but for vqhip_ivfbin's coarse metric
     size_t row_b = 0;                // bytes of one row's payload (each index sets it at create)
     std::vector<float> coarse;       // [nlist][dim]
     std::vector<uint32_t> row_list;  // [n] list id of each row
@@ -3499,6 +3500,7 @@ static void ivf_init(IvfLists *ix, const float *coarse, uint32_t nlist, uint32_t
     ix->nlist = nlist;
     ix->dim = dim;
     ix->metric = metric;
+    ix->probe_metric = metric;
     ix->row_b = row_b;
     ix->coarse.assign(coarse, coarse + (size_t)nlist * dim);
     ix->sizes.assign(nlist, 0);
@@ -3561,7 +3563,7 @@ static int ivf_list_sizes(IvfLists *ix, uint64_t *sizes) {
 template <class First, class Resident>
 static int ivf_ready(IvfLists *ix, hipStream_t s, First &&first, Resident &&resident) {
     if (!ix->flat) {
-        VQ_TRY(flat_create(ix->coarse.data(), hipMemcpyHostToDevice, ix->nlist, ix->dim, 0, ix->metric, &ix->flat));
+        VQ_TRY(flat_create(ix->coarse.data(), hipMemcpyHostToDevice, ix->nlist, ix->dim, 0, ix->probe_metric, &ix->flat));
         VQ_TRY(first());
     }
     if (!ix->dirty) return VQHIP_OK;
@@ -3951,6 +3953,49 @@ struct vqhip_ivfsq : IvfExact {
     }
 };
 
+// ------------------------------------------------------------------ inverted-file binary (k_ivfbin.hip) ----
+// IvfLists whose payload is packed BQ words (bin_words(dim) words a row, pad bits zero).  Two metrics: `metric` of the
+// reported distance (the table S), `probe_metric` of the flat index over the centroids.
+struct vqhip_ivfbin : IvfLists {
+    uint32_t nw = 0, low = 0, high = 1;  // nw: words a row
+    float thr = 0;
+    DevBuf table;            // S [dim + 1]
+    DevBuf qw, inv, lists;   // per-call workspaces: the batch's packed queries, the inverted probe table, the lists' state
+
+    int ready(hipStream_t s) {
+        return ivf_ready(this, s, [&] {
+            std::vector<float> S(dim + 1);
+            binary_table(dim, low, high, metric, S.data());
+            VQ_TRY(table.alloc(S.size() * 4));
+            VQ_HIP(hipMemcpyAsync(table.p, S.data(), S.size() * 4, hipMemcpyHostToDevice, s));
+            VQ_HIP(hipStreamSynchronize(s));  // (S is this call's)
+            return VQHIP_OK;
+        }, ivf_no_hook);
+    }
+    int search_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
+                       hipStream_t s) {
+        IvfBatch b;
+        VQ_TRY(ivf_batch(this, nq, nprobe, 0, &b));
+        VQ_TRY(qw.ensure((size_t)b.nb_max * nw * 4));
+        VQ_TRY(inv.ensure((size_t)b.nb_max * nprobe * 4));
+        VQ_TRY(lists.ensure(ivfflat_lists_bytes(nlist)));
+        VQ_TRY(state.ensure(knn_state_bytes(b.nb_max)));
+        for (uint32_t q0 = 0; q0 < nq; q0 += b.nb_max) {
+            const uint32_t nb = std::min(b.nb_max, nq - q0);
+            const float *Q = queries_dev + (size_t)q0 * dim;
+            VQ_TRY(ivf_probe_enqueue(this, Q, nb, nprobe, probe.as<uint32_t>(), s));  // (the f32 queries: never binarised)
+            VQ_TRY(launch_bq_pack(Q, VQHIP_BINARY_F32, nb, dim, thr, high, qw.as<uint32_t>(), s));
+            VQ_TRY(launch_ivfbin_search(metric, d_payload.as<uint32_t>(), dim, table.as<float>(), d_ids.as<uint32_t>(), d_off.as<uint32_t>(),
+                                        nlist, max_list, qw.as<uint32_t>(), probe.as<uint32_t>(), nb, nprobe, topk,
+                                        ivf_chunk((uint64_t)nb * b.per_q), b.wstride, W.as<float>(), pref.as<uint32_t>(), seg.as<uint32_t>(),
+                                        inv.as<uint32_t>(), lists.as<uint32_t>(), state.p, cand.as<unsigned long long>(),
+                                        idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s));
+        }
+        return VQHIP_OK;
+    }
+};
+
+
 // One range call on an inverted-file flat or scalar index: range_args' checks (no device, no index), nprobe as search
 // checks it, then the index's device, the calling thread's stream and the device state as search builds it; the queries
 // (host: through ix->q) and the radii go up and range_enqueue leaves *out complete.
@@ -4174,6 +4219,145 @@ int vqhip_ivfsq_range_search_device(vqhip_ivfsq *ix, const void *dev_queries, ui
                                     uint64_t max_results, vqhip_range **out) {
     VQ_API_BEGIN
     return ivf_range(ix, dev_queries, false, nq, nprobe, radii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_ivfbin_create(float threshold, uint32_t low, uint32_t high, const float *coarse, uint32_t nlist, uint32_t dim, int metric,
+                        int coarse_metric, vqhip_ivfbin **out) {
+    VQ_API_BEGIN
+    if (!out) return fail(VQHIP_ERR_NULL_PTR, "out is NULL");
+    *out = nullptr;
+    VQ_TRY(bq_check(threshold, low, high));
+    VQ_TRY(ivf_check_lists(coarse, nlist));
+    if (dim == 0 || dim > VQHIP_BINARY_MAX_DIM) return fail(VQHIP_ERR_INVALID_INPUT, "d %u must be in [1, 8192]", dim);
+    if (vq_is_cos(metric)) return fail(VQHIP_ERR_UNSUPPORTED, "cosine is not a function of the Hamming distance alone");
+    if (metric != VQHIP_SQUARED_EUCLIDEAN && metric != VQHIP_EUCLIDEAN && metric != VQHIP_MANHATTAN)
+        return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
+    VQ_TRY(ivf_check_metric(coarse_metric));
+    std::unique_ptr<vqhip_ivfbin> ix(new vqhip_ivfbin());
+    ivf_init(ix.get(), coarse, nlist, dim, metric, (size_t)bin_words(dim) * 4);
+    ix->probe_metric = coarse_metric;
+    ix->nw = bin_words(dim);
+    ix->thr = threshold, ix->low = low, ix->high = high;
+    *out = ix.release();
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_ivfbin_destroy(vqhip_ivfbin *ix) {
+    delete ix;
+    return VQHIP_OK;
+}
+
+int vqhip_ivfbin_add_packed(vqhip_ivfbin *ix, const uint32_t *list_ids, const uint32_t *words, uint64_t n) {
+    VQ_API_BEGIN
+    return ivf_add(ix, list_ids, words, n, [&] {
+        if (ix->dim % 32) {
+            const uint32_t mask = (1u << (ix->dim % 32)) - 1u;
+            for (uint64_t i = 0; i < n; ++i)
+                if (words[i * ix->nw + ix->nw - 1] & ~mask)
+                    return fail(VQHIP_ERR_INVALID_INPUT, "row %llu has a pad bit set", (unsigned long long)i);
+        }
+        return ivf_append(ix, words, n);
+    });
+    VQ_API_END
+}
+
+int vqhip_ivfbin_add_codes(vqhip_ivfbin *ix, const uint32_t *list_ids, const uint8_t *codes, uint64_t n) {
+    VQ_API_BEGIN
+    return ivf_add(ix, list_ids, codes, n, [&] {
+        const size_t have = ix->payload.size();
+        ix->payload.resize(have + (size_t)n * ix->row_b, 0);
+        uint32_t *w = reinterpret_cast<uint32_t *>(ix->payload.data() + have);  // (row_b is a multiple of 4, the vector's base aligned)
+        for (uint64_t i = 0; i < n; ++i)
+            for (uint32_t t = 0; t < ix->dim; ++t)
+                if (codes[i * ix->dim + t] >= ix->high) w[i * ix->nw + t / 32] |= 1u << (t % 32);
+        return VQHIP_OK;
+    });
+    VQ_API_END
+}
+
+int vqhip_ivfbin_add_rows(vqhip_ivfbin *ix, const uint32_t *list_ids, const float *rows, uint64_t n) {
+    VQ_API_BEGIN
+    return ivf_add(ix, list_ids, rows, n, [&] {
+        VQ_TRY(require_gfx950());
+        VQ_TRY(ivf_device(ix));
+        hipStream_t s;
+        VQ_TRY(current_stream(&s));
+        const size_t have = ix->payload.size();
+        ix->payload.resize(have + (size_t)n * ix->row_b);
+        auto pack = [&]() -> int {  // vqhip_bq_pack's path with this quantizer's threshold
+            const uint64_t per = std::max<uint64_t>(1, (256ull << 20) / ((uint64_t)ix->dim * 4));
+            const uint64_t rows_b = std::min<uint64_t>(per, n);
+            DevBuf dx, dw;
+            VQ_TRY(dx.alloc((size_t)rows_b * ix->dim * 4));
+            VQ_TRY(dw.alloc((size_t)rows_b * ix->row_b));
+            for (uint64_t r0 = 0; r0 < n; r0 += per) {
+                const uint64_t rn = std::min<uint64_t>(per, n - r0);
+                VQ_HIP(hipMemcpyAsync(dx.p, rows + r0 * ix->dim, (size_t)rn * ix->dim * 4, hipMemcpyHostToDevice, s));
+                VQ_TRY(launch_bq_pack(dx.p, VQHIP_BINARY_F32, rn, ix->dim, ix->thr, ix->high, dw.as<uint32_t>(), s));
+                VQ_HIP(hipMemcpyAsync(ix->payload.data() + have + (size_t)r0 * ix->row_b, dw.p, (size_t)rn * ix->row_b,
+                                      hipMemcpyDeviceToHost, s));
+                VQ_HIP(hipStreamSynchronize(s));
+            }
+            return VQHIP_OK;
+        };
+        const int rc = pack();
+        if (rc != VQHIP_OK) ix->payload.resize(have);  // (nothing is stored)
+        return rc;
+    });
+    VQ_API_END
+}
+
+int vqhip_ivfbin_info(const vqhip_ivfbin *ix, uint64_t *n, uint32_t *nlist, uint32_t *dim, int *metric, int *coarse_metric,
+                      float *threshold, uint32_t *low, uint32_t *high) {
+    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    std::lock_guard<std::recursive_mutex> lock(const_cast<vqhip_ivfbin *>(ix)->sync.mu);  // (n changes under add)
+    if (n) *n = ix->n;
+    if (nlist) *nlist = ix->nlist;
+    if (dim) *dim = ix->dim;
+    if (metric) *metric = ix->metric;
+    if (coarse_metric) *coarse_metric = ix->probe_metric;
+    if (threshold) *threshold = ix->thr;
+    if (low) *low = ix->low;
+    if (high) *high = ix->high;
+    return VQHIP_OK;
+}
+
+int vqhip_ivfbin_list_sizes(vqhip_ivfbin *ix, uint64_t *sizes) {
+    VQ_API_BEGIN
+    return ivf_list_sizes(ix, sizes);
+    VQ_API_END
+}
+
+int vqhip_ivfbin_packed(vqhip_ivfbin *ix, uint32_t *words_out) {
+    VQ_API_BEGIN
+    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);
+    if (ix->n == 0) return VQHIP_OK;
+    if (!words_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    memcpy(words_out, ix->payload.data(), ix->payload.size());
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_ivfbin_probe(vqhip_ivfbin *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t *lists_out) {
+    VQ_API_BEGIN
+    return ivf_probe(ix, queries, nq, nprobe, lists_out);
+    VQ_API_END
+}
+
+int vqhip_ivfbin_search(vqhip_ivfbin *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_out,
+                        float *dist_out) {
+    VQ_API_BEGIN
+    return ivf_search(ix, queries, nq, nprobe, topk, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_ivfbin_search_device(vqhip_ivfbin *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk, void *dev_idx,
+                               void *dev_dist) {
+    VQ_API_BEGIN
+    return ivf_search_device(ix, dev_queries, nq, nprobe, topk, dev_idx, dev_dist);
     VQ_API_END
 }
 

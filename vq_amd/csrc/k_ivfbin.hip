@@ -1,0 +1,290 @@
+// Inverted-file search over packed BQ bits (include/vqhip.h, vqhip_ivfbin_*): section 14's probe
+// and schedule over section 12's codes.  The index keeps its words in list order: list l is the run
+// P[off[l] * W .. off[l + 1] * W) of one buffer the index owns (W = ceil(d / 32) words a row, pad bits zero), so a row
+// of any list starts on the alignment of the base and of W words.
+//   H(q, i) = popcount(bits(q) xor words[i]) over the W words, an integer: no order of operations to keep,
+//   D(q, i) = S[H] (binary_table), sqrtf(S[H]) under Euclidean -- the form k_ivff_tile stores for the metric, so the
+//             selection stage orders and reports it unchanged; S and its root are strictly increasing, so (D, row id)
+//             orders like (H, row id).
+// Schedule of one batch (launch_ivfbin_search): section 14's, step for step --
+//   launch_bq_pack      the batch's queries as words Q [nb][W] (k_binary.hip)
+//   launch_ivff_plan    k_ivff_plan, k_ivff_lists, k_ivff_invert (k_ivfflat.hip): pref / seg, cnt, the inverted probe table
+//   k_ivfbin_tile       k_ivff_tile's work item with both sides as words: an 8 x 4 register block of H over chunks of 32
+//                       words in LDS, three 16-byte LDS reads per 64 VALU operations
+//   k_ivfbin_scan       the lists probed by fewer than kIvffTileMin queries: one query x one chunk of positions, the
+//                       query's words in LDS, one position per lane
+//   launch_ivff_select  k_ivff_hist and the selection stage over IvffSource (k_ivfflat.hip)
+// Which kernel computes a pair depends on the batch; H is an integer and both look D up in one table, so the bits do not.
+// LW = words per load of the row loader (4, 2 or 1: 16, 8 or 4 bytes), chosen per launch from W and the base pointer.
+#include "common.hpp"
+#include "ivf_plan.hpp"
+#include "kernels.hpp"
+#include "knn_tile.hpp"
+
+namespace vqhip {
+namespace {
+
+constexpr uint32_t kBinWC = 32;  // words (1024 dimensions) per LDS chunk of the tile kernel
+
+// LW consecutive words from p (LW-word aligned)
+template <int LW>
+__device__ __forceinline__ void bin_load(const uint32_t *__restrict__ p, uint32_t (&w)[LW]) {
+    if constexpr (LW == 4) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(p);
+        w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+    } else if constexpr (LW == 2) {
+        const uint2 v = *reinterpret_cast<const uint2 *>(p);
+        w[0] = v.x, w[1] = v.y;
+    } else {
+        w[0] = *p;
+    }
+}
+
+// S [d + 1] into LDS as the reported distance of every H
+__device__ __forceinline__ void bin_table_load(float *s_tab, const float *__restrict__ S, uint32_t d, int root) {
+    for (uint32_t h = threadIdx.x; h <= d; h += 256) s_tab[h] = root ? sqrtf(S[h]) : S[h];
+}
+
+// block (x = query tile of the batch's tstart[nlist] tiles, y = column of row tiles): H of the rows of one list against
+// the up to 128 queries of one tile of its run of inv.  Blocks past the last tile leave at once.  A chunk of a row starts
+// at word (off[l] + r) * W + t0 with t0 a multiple of 32, so W % LW == 0 and an LW-word-aligned base align every load; a
+// load is issued only where its row is inside the list and its first word below tc (a multiple of LW).  Padded rows,
+// queries and words are 0 in the tile and never reach a result.
+template <int LW>
+__global__ __launch_bounds__(256) void k_ivfbin_tile(const uint32_t *__restrict__ Q, const uint32_t *__restrict__ P, uint32_t Wn,
+                                                     uint32_t d, const float *__restrict__ S, int root,
+                                                     const uint32_t *__restrict__ off, uint32_t nlist, const uint32_t *__restrict__ cnt,
+                                                     const uint32_t *__restrict__ lstart, const uint32_t *__restrict__ tstart,
+                                                     const uint32_t *__restrict__ inv, const uint32_t *__restrict__ pref,
+                                                     uint32_t nprobe, uint64_t wstride, float *__restrict__ W,
+                                                     uint32_t *__restrict__ kmin, uint32_t *__restrict__ kmax) {
+    constexpr uint32_t RQ = kKnnRQ, RR = kKnnRR, TQ = kKnnTQ, TR = kKnnTR, WC = kBinWC;
+    extern __shared__ float s_tab[];  // [d + 1]
+    __shared__ __attribute__((aligned(16))) uint32_t qs[WC][TQ + 4];
+    __shared__ __attribute__((aligned(16))) uint32_t rs[WC][TR + 4];
+    __shared__ uint32_t s_q[TQ], s_p[TQ];  // the tile's queries (0xFFFFFFFF: none) and the first position of the list in each
+    const uint32_t tile = blockIdx.x;
+    if (tile >= tstart[nlist]) return;  // (uniform)
+    uint32_t l = 0;
+    {  // the last list whose first tile is <= tile, and that has tiles (tstart is non-decreasing)
+        uint32_t lo = 0, hi = nlist;
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (tstart[mid] <= tile) lo = mid;
+            else hi = mid;
+        }
+        l = lo;
+    }
+    const uint32_t tid = threadIdx.x, rg = tid & 15u, qg = tid >> 4;
+    const uint32_t e0 = (tile - tstart[l]) * TQ, en = min(TQ, cnt[l] - e0);
+    const uint32_t row0 = off[l], nrows = off[l + 1] - row0;
+    const uint32_t *Pl = P + (uint64_t)row0 * Wn;  // the list's run
+    if (tid < TQ) {
+        uint32_t q = 0xFFFFFFFFu, p = 0;
+        if (tid < en) {
+            const uint32_t e = inv[lstart[l] + e0 + tid];
+            q = e / nprobe;
+            p = pref[(size_t)q * (nprobe + 1) + (e - q * nprobe)];
+        }
+        s_q[tid] = q;
+        s_p[tid] = p;
+    }
+    bin_table_load(s_tab, S, d, root);
+    __syncthreads();
+    uint32_t lo[RQ], hi[RQ], qi[RQ];
+#pragma unroll
+    for (uint32_t a = 0; a < RQ; ++a) {
+        qi[a] = s_q[qg * RQ + a];
+        lo[a] = 0xFFFFFFFFu;
+        hi[a] = 0u;
+    }
+    const uint32_t nrt = (nrows + TR - 1) / TR;
+    for (uint32_t rt = blockIdx.y; rt < nrt; rt += gridDim.y) {
+        const uint32_t r0 = rt * TR;  // (within the list)
+        uint32_t acc[RQ][RR];
+#pragma unroll
+        for (uint32_t a = 0; a < RQ; ++a)
+#pragma unroll
+            for (uint32_t b = 0; b < RR; ++b) acc[a][b] = 0u;
+        for (uint32_t t0 = 0; t0 < Wn; t0 += WC) {
+            const uint32_t tc = min(WC, Wn - t0);
+            __syncthreads();  // the previous chunk's readers are done
+#pragma unroll
+            for (uint32_t e = 0; e < TQ * WC / 256; ++e) {
+                const uint32_t idx = tid + 256 * e, r = idx / WC, c = idx % WC;
+                const uint32_t q = s_q[r];
+                qs[c][r] = (q != 0xFFFFFFFFu && c < tc) ? Q[(size_t)q * Wn + t0 + c] : 0u;
+            }
+#pragma unroll
+            for (uint32_t e = 0; e < TR * WC / LW / 256; ++e) {  // (64 rows x 32 / LW loads: 2, 4 or 8 per lane)
+                const uint32_t idx = tid + 256 * e, r = idx / (WC / LW), c0 = (idx % (WC / LW)) * LW;
+                const bool ok = r0 + r < nrows && c0 < tc;
+                uint32_t w[LW];
+#pragma unroll
+                for (uint32_t j = 0; j < LW; ++j) w[j] = 0u;
+                if (ok) bin_load<LW>(Pl + (uint64_t)(r0 + r) * Wn + t0 + c0, w);
+#pragma unroll
+                for (uint32_t j = 0; j < LW; ++j) rs[c0 + j][r] = w[j];
+            }
+            __syncthreads();
+            auto advance = [&](uint32_t t) {
+                const uint4 qa = *reinterpret_cast<const uint4 *>(&qs[t][qg * RQ]);
+                const uint4 qb = *reinterpret_cast<const uint4 *>(&qs[t][qg * RQ + 4]);
+                const uint4 rv = *reinterpret_cast<const uint4 *>(&rs[t][rg * RR]);
+                const uint32_t qv[RQ] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
+                const uint32_t rr[RR] = {rv.x, rv.y, rv.z, rv.w};
+#pragma unroll
+                for (uint32_t a = 0; a < RQ; ++a)
+#pragma unroll
+                    for (uint32_t b = 0; b < RR; ++b) acc[a][b] = __builtin_popcount(qv[a] ^ rr[b]) + acc[a][b];
+            };
+            if (tc == WC) {
+#pragma unroll 8
+                for (uint32_t t = 0; t < WC; ++t) advance(t);
+            } else {
+                for (uint32_t t = 0; t < tc; ++t) advance(t);
+            }
+        }
+        const uint32_t rb = r0 + rg * RR;
+#pragma unroll
+        for (uint32_t a = 0; a < RQ; ++a) {
+            if (qi[a] == 0xFFFFFFFFu) continue;
+            float *wq = W + (size_t)qi[a] * wstride;
+            const uint64_t p0 = (uint64_t)s_p[qg * RQ + a] + rb;
+#pragma unroll
+            for (uint32_t b = 0; b < RR; ++b) {
+                if (rb + b >= nrows || p0 + b >= wstride) continue;
+                const float dv = s_tab[min(acc[a][b], d)];  // (H <= d: the pad bits of both sides are zero)
+                const uint32_t key = adc_key(dv);
+                if (key != 0xFFFFFFFFu) {
+                    lo[a] = min(lo[a], key);
+                    hi[a] = max(hi[a], key);
+                }
+                wq[p0 + b] = dv;  // (a run starts at any position: no 16-byte stores)
+            }
+        }
+    }
+    // the 16 lanes of a query group (lane bits 0-3) hold all of the workgroup's rows for its 8 queries
+#pragma unroll
+    for (uint32_t a = 0; a < RQ; ++a) {
+#pragma unroll
+        for (uint32_t o = 1; o < 16; o <<= 1) {
+            lo[a] = min(lo[a], (uint32_t)__shfl_xor((int)lo[a], (int)o));
+            hi[a] = max(hi[a], (uint32_t)__shfl_xor((int)hi[a], (int)o));
+        }
+        if (rg == 0 && qi[a] != 0xFFFFFFFFu && lo[a] <= hi[a]) {
+            atomicMin(&kmin[qi[a]], lo[a]);
+            atomicMax(&kmax[qi[a]], hi[a]);
+        }
+    }
+}
+
+// block (x = chunk of positions, y = query): the positions of the chunk whose list fewer than kIvffTileMin queries probe,
+// one per lane and pass; the query's W <= 256 words in LDS.  Items past |S(q)| leave at once.
+template <int LW>
+__global__ __launch_bounds__(256) void k_ivfbin_scan(const uint32_t *__restrict__ Q, const uint32_t *__restrict__ P, uint32_t Wn,
+                                                     uint32_t d, const float *__restrict__ S, int root,
+                                                     const uint32_t *__restrict__ probe, const uint32_t *__restrict__ cnt,
+                                                     const uint32_t *__restrict__ pref, const uint32_t *__restrict__ seg,
+                                                     uint32_t nprobe, uint32_t chunk, uint64_t wstride, float *__restrict__ W,
+                                                     uint32_t *__restrict__ kmin, uint32_t *__restrict__ kmax) {
+    extern __shared__ float s_tab[];  // [d + 1]
+    __shared__ __attribute__((aligned(16))) uint32_t s_x[VQHIP_BINARY_MAX_DIM / 32];
+    const uint32_t q = blockIdx.y, tid = threadIdx.x;
+    const uint32_t *pq = pref + (size_t)q * (nprobe + 1);
+    const uint32_t *sq = seg + (size_t)q * nprobe;
+    const uint32_t *lq = probe + (size_t)q * nprobe;
+    const uint32_t total = (uint32_t)min((uint64_t)pq[nprobe], wstride);
+    const uint64_t p0 = (uint64_t)blockIdx.x * chunk;
+    if (p0 >= total) return;  // (uniform)
+    const uint32_t p1 = (uint32_t)min((uint64_t)total, p0 + chunk);
+    for (uint32_t t = tid; t < Wn; t += 256) s_x[t] = Q[(size_t)q * Wn + t];
+    bin_table_load(s_tab, S, d, root);
+    __syncthreads();
+    float *wq = W + (size_t)q * wstride;
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+    for (uint32_t base = (uint32_t)p0; base < p1; base += 256) {
+        const uint32_t pos = base + tid;
+        if (pos >= p1) continue;
+        const uint32_t slot = ivf_slot(pq, nprobe, pos);
+        if (cnt[lq[slot]] >= kIvffTileMin) continue;  // (a position exists: its list is real; the tile kernel has it)
+        const uint64_t row = (uint64_t)sq[slot] + (pos - pq[slot]);
+        const uint32_t *r = P + row * Wn;
+        uint32_t h = 0;
+        for (uint32_t t = 0; t < Wn; t += LW) {
+            uint32_t w[LW];
+            bin_load<LW>(r + t, w);
+#pragma unroll
+            for (uint32_t j = 0; j < LW; ++j) h = __builtin_popcount(w[j] ^ s_x[t + j]) + h;
+        }
+        const float dv = s_tab[min(h, d)];
+        const uint32_t key = adc_key(dv);
+        if (key != 0xFFFFFFFFu) {
+            lo = min(lo, key);
+            hi = max(hi, key);
+        }
+        wq[pos] = dv;
+    }
+#pragma unroll
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        lo = min(lo, (uint32_t)__shfl_xor((int)lo, (int)o));
+        hi = max(hi, (uint32_t)__shfl_xor((int)hi, (int)o));
+    }
+    if ((tid & 63u) == 0 && lo <= hi) {
+        atomicMin(&kmin[q], lo);
+        atomicMax(&kmax[q], hi);
+    }
+}
+
+}  // namespace
+
+// words per load of the row loaders: 4 (16 bytes), 2 (8 bytes) or 1, from the words of a row and the base of the buffer
+int bin_load_width(const uint32_t *P, uint32_t W) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(P);
+    if (W % 4 == 0 && a % 16 == 0) return 4;
+    if (W % 2 == 0 && a % 8 == 0) return 2;
+    return 1;
+}
+
+// One batch of nb <= 1024 queries, packed (Q [nb][bin_words(d)], launch_bq_pack), whose probe lists (probe [nb][nprobe],
+// launch_knn_search over the f32 queries) are on the device.  P / ids / off: the index in list order, P [n][bin_words(d)];
+// S [d + 1] binary_table's; metric the reported distance's (VQHIP_EUCLIDEAN: the root of S).  The workspaces are
+// launch_ivfflat_search's.  Results [nb][topk] on the device.
+int launch_ivfbin_search(int metric, const uint32_t *P, uint32_t d, const float *S, const uint32_t *ids, const uint32_t *off,
+                         uint32_t nlist, uint64_t max_list, const uint32_t *Q, const uint32_t *probe, uint32_t nb, uint32_t nprobe,
+                         uint32_t topk, uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv,
+                         uint32_t *lists, void *state, unsigned long long *cand, uint32_t *idx_out, float *dist_out,
+                         hipStream_t stream) {
+    if (nb == 0) return VQHIP_OK;
+    if (d == 0 || d > VQHIP_BINARY_MAX_DIM) return fail(VQHIP_ERR_INVALID_INPUT, "d %u must be in [1, 8192]", d);
+    IvffPlan p;
+    VQ_TRY(launch_ivff_plan(off, nlist, max_list, probe, nb, nprobe, topk, pref, seg, inv, lists, state, &p, stream));
+    const uint32_t Wn = bin_words(d);
+    const int lw = bin_load_width(P, Wn), root = metric == VQHIP_EUCLIDEAN ? 1 : 0;
+    const size_t lds = ((size_t)d + 1) * 4;
+    const uint64_t items = (wstride + chunk - 1) / chunk;
+    if (p.tiles_max > 0) {
+        const dim3 grid((uint32_t)p.tiles_max, (uint32_t)p.cols);
+        auto tile = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, Q, P, Wn, d, S, root, off, nlist, p.cnt, p.lstart, p.tstart, inv, pref,
+                               nprobe, wstride, W, p.kmin, p.kmax);
+        };
+        if (lw == 4) tile(k_ivfbin_tile<4>);
+        else if (lw == 2) tile(k_ivfbin_tile<2>);
+        else tile(k_ivfbin_tile<1>);
+        VQ_LAUNCH_CHECK("k_ivfbin_tile");
+    }
+    if (items > 0) {
+        auto scan = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((uint32_t)items, nb), dim3(256), lds, stream, Q, P, Wn, d, S, root, probe, p.cnt, pref, seg,
+                               nprobe, chunk, wstride, W, p.kmin, p.kmax);
+        };
+        if (lw == 4) scan(k_ivfbin_scan<4>);
+        else if (lw == 2) scan(k_ivfbin_scan<2>);
+        else scan(k_ivfbin_scan<1>);
+        VQ_LAUNCH_CHECK("k_ivfbin_scan");
+    }
+    return launch_ivff_select(p, W, wstride, pref, seg, ids, nb, nprobe, topk, cand, idx_out, dist_out, stream);
+}
+
+}  // namespace vqhip

@@ -319,6 +319,15 @@ int launch_ivfsq_search(int metric, const uint8_t *C, uint32_t d, float mn, floa
                         const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
                         float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state,
                         unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream);
+// inverted-file search over list-ordered packed BQ words (k_ivfbin.hip): launch_ivfflat_search with the rows as P
+// [n][bin_words(d)] and the batch's queries packed the same way (Q [nb][bin_words(d)], launch_bq_pack); D = S[H], its root
+// under VQHIP_EUCLIDEAN, S [d + 1] binary_table's on the device; the same workspaces
+int bin_load_width(const uint32_t *P, uint32_t W);
+int launch_ivfbin_search(int metric, const uint32_t *P, uint32_t d, const float *S, const uint32_t *ids, const uint32_t *off,
+                         uint32_t nlist, uint64_t max_list, const uint32_t *Q, const uint32_t *probe, uint32_t nb, uint32_t nprobe,
+                         uint32_t topk, uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv,
+                         uint32_t *lists, void *state, unsigned long long *cand, uint32_t *idx_out, float *dist_out,
+                         hipStream_t stream);
 // exact k-NN search over resident rows and exact rerank of candidate lists (k_knn.hip); X [n][d] f32 (dtype 0) or f16
 // bits (dtype 1), rnorm [n] the rows' norms (cosine only, else unused)
 int launch_knn_norms(const void *X, int dtype, uint64_t n, uint32_t d, float *out, hipStream_t stream);

@@ -7,6 +7,7 @@
     python -m vq_amd.evalcli bq   [--seed 66 --dim 384]
     python -m vq_amd.evalcli ivfflat [--seed 66 --dim 384 --nlist 256 --nprobe 1 8 32 --max-iters 10]
     python -m vq_amd.evalcli ivfsq   [--seed 66 --dim 384 --nlist 256 --nprobe 1 8 32 --max-iters 10 --levels 256]
+    python -m vq_amd.evalcli ivfbin  [--seed 66 --dim 384 --nlist 256 --nprobe 1 8 32 --max-iters 10 --threshold 0.5 --candidates 40 100]
 
 For every sample count of `NUM_SAMPLES` it prints the reference's three lines -- training time,
 quantization time (host matrix in, f16 matrix out: what `quantize` per vector produces there)
@@ -23,6 +24,8 @@ mean squared error of dequantize(quantize(x)).
 and reports, per nprobe, recall@k of its search against the exact search (FlatIndex) of the same <= 1000 strided
 queries over all n rows, with the mean share of the rows a query scans.
 
+`ivfbin` reports an IVFBinaryIndex with BinaryQuantizer(threshold): per nprobe, recall@k against FlatIndex over the original
+rows, as returned and with rerank=FlatIndex at each candidate count, beside BinaryIndex's figures on the same rows.
 `ivfsq` is `ivfflat` for an IVFScalarIndex with ScalarQuantizer(0, 1, levels) over the same coarse centroids: per nprobe,
 recall@k against the exact search over the original rows (probing and quantization loss together), recall@k against the
 exact search over the dequantized rows (probing loss alone), and beside them IVFFlatIndex's recall over the original rows
@@ -261,6 +264,67 @@ def _report_ivfsq(args):
         flat.close()
 
 
+def _report_ivfbin(args):
+    """recall@k of IVFBinaryIndex.search against FlatIndex.search over the original rows, per nprobe, as returned and with
+    rerank=FlatIndex at two candidate counts, beside BinaryIndex's over the same rows: the probing loss apart from the
+    binarisation loss"""
+    from . import _lib
+    from .binary import BinaryIndex
+    from .bq import BinaryQuantizer
+    from .flat import FlatIndex
+    from .ivf_binary import IVFBinaryIndex
+
+    title = "IVF-Binary Index Evaluation"
+    print(title)
+    print("=" * len(title))
+    bq = BinaryQuantizer(args.threshold)
+
+    def recall(got, want, k):
+        return float(np.mean([len(np.intersect1d(got[j], want[j])) / k for j in range(len(want))]))
+
+    for n in args.samples:
+        X = _lib.synth_uniform_host(n, args.dim, args.seed, 0)
+        nlist = min(args.nlist, n)
+        k = min(args.recall_k, n)
+        t0 = time.perf_counter()
+        ix = IVFBinaryIndex.train(X, nlist, bq, args.max_iters, seed=args.seed)
+        train_ms = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        ix.add(X)
+        add_ms = (time.perf_counter() - t0) * 1e3
+        bx = BinaryIndex.from_packed(ix.packed(), args.dim, bq, ix.distance)
+        flat = FlatIndex(X)
+        Q = X[::max(n // min(n, 1000), 1)]
+        exact = flat.search(Q, k)[0]
+        cands = [c for c in args.candidates if k <= c <= min(n, 1024)]
+        r_bin = recall(bx.search(Q, k)[0], exact, k)
+        r_bin_rr = {c: recall(bx.search(Q, k, rerank=flat, candidates=c)[0], exact, k) for c in cands}
+        sizes = ix.list_sizes().astype(np.int64)
+        if not args.json:
+            print(f"\nSamples: {n}")
+            print(f"  Training time: {train_ms:.0f} ms")
+            print(f"  Add time: {add_ms:.0f} ms")
+            print(f"  Index bytes per row: {4 * ((args.dim + 31) // 32)} (f32 rows: {4 * args.dim})")
+            print(f"  BinaryIndex (every row): Recall@{k} {r_bin:.4f}" + "".join(f", {v:.4f} reranked from {c}" for c, v in r_bin_rr.items()))
+        for nprobe in args.nprobe:
+            p = min(nprobe, nlist)
+            t0 = time.perf_counter()
+            got = ix.search(Q, topk=k, nprobe=p)[0]
+            search_ms = (time.perf_counter() - t0) * 1e3
+            r = recall(got, exact, k)
+            r_rr = {c: recall(ix.search(Q, topk=k, nprobe=p, rerank=flat, candidates=c)[0], exact, k) for c in cands}
+            scanned = float(sizes[ix.probe(Q, p)].sum() / (len(Q) * n))
+            if args.json:
+                print(json.dumps({"n_samples": n, "n_dims": args.dim, "nlist": nlist, "nprobe": p, "threshold": args.threshold,
+                                  "training_time_ms": train_ms, "add_time_ms": add_ms, "search_time_ms": search_ms, "recall": r,
+                                  "recall_reranked": {str(c): v for c, v in r_rr.items()}, "binary_recall": r_bin,
+                                  "binary_recall_reranked": {str(c): v for c, v in r_bin_rr.items()}, "scanned_share": scanned}))
+            else:
+                print(f"  nprobe {p}: Recall@{k} {r:.4f}" + "".join(f", {v:.4f} reranked from {c}" for c, v in r_rr.items()) +
+                      f", {100 * scanned:.1f}% of the rows scanned, {search_ms:.0f} ms")
+        ix.close()
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="vq_amd.evalcli")
     sub = ap.add_subparsers(dest="alg", required=True)
@@ -287,7 +351,7 @@ def main(argv=None) -> int:
             p.add_argument("--max-iters", type=int, default=MAX_ITERS)
         else:
             p.add_argument("--max-depth", type=int, default=5)
-    for name in ("ivfflat", "ivfsq"):
+    for name in ("ivfflat", "ivfsq", "ivfbin"):
         p = sub.add_parser(name)
         p.add_argument("--seed", type=int, default=SEED)
         p.add_argument("--dim", type=int, default=DIM)
@@ -299,12 +363,18 @@ def main(argv=None) -> int:
         p.add_argument("--json", action="store_true")
         if name == "ivfsq":
             p.add_argument("--levels", type=int, default=256)
+        if name == "ivfbin":
+            p.add_argument("--threshold", type=float, default=0.5)
+            p.add_argument("--candidates", type=int, nargs="+", default=[40, 100])
     args = ap.parse_args(argv)
     if args.alg == "ivfflat":
         _report_ivfflat(args)
         return 0
     if args.alg == "ivfsq":
         _report_ivfsq(args)
+        return 0
+    if args.alg == "ivfbin":
+        _report_ivfbin(args)
         return 0
     from . import TSVQ, BinaryQuantizer, Distance, ProductQuantizer, ScalarQuantizer
 

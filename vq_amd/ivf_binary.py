@@ -1,0 +1,212 @@
+"""``IVFBinaryIndex`` -- an inverted file over packed BQ bits: a query computes the Hamming distance to the rows of its
+nearest coarse centroids' lists only, and a row costs one bit per dimension.
+
+The reference has no search function; the semantics are include/vqhip.h's (vqhip_ivfbin_*, vq_amd/csrc/k_ivfbin.hip): a
+``BinaryQuantizer(threshold, low, high)`` fixes the bit rules of ``BinaryIndex`` (x >= threshold for f32 rows and
+queries, c >= high for u8 codes; row i / dimension t in word ``i * W + t // 32``, bit ``t % 32``, pad bits zero).
+``distance`` is the metric of the reported distance (squared Euclidean, Euclidean or Manhattan -- the default, as
+``BinaryIndex``; cosine is refused as there); ``coarse_distance`` the metric lists are probed under and rows are
+assigned under in ``add`` (any of the five, default Euclidean).  ``P(q)`` is ``FlatIndex(coarse,
+coarse_distance).search(q, nprobe)`` for the float32 query -- it is never binarised for probing --, ``S(q)`` the rows
+whose list is in ``P(q)``, ``H(q, i) = popcount(bits(q) xor words[i])``, ``D(q, i)`` ``BinaryIndex``'s reported distance
+for ``H`` and the result the ``topk`` rows of ``S(q)`` by ``(D, row id)`` ascending, which is ``(H, row id)``.  With
+``nprobe == nlist`` the result equals ``BinaryIndex.from_packed(words, dim, quantizer, distance).search`` -- indices,
+and distances as uint32 bits.  Slots past ``|S(q)|`` hold id ``0xFFFFFFFF`` and distance ``+inf``.  Constructing,
+``add_packed``, ``add_codes``, saving and loading need no GPU; ``add`` and ``add_rows`` pack on the device; the device
+state is built by the first probe or search and follows every later add.
+
+File layout (little endian), in the manner of ivf_scalar.py's:
+
+    0   8   magic  b"VQIVFBN1"
+    8   4   u32    metric (0 squared_euclidean, 1 euclidean, 2 manhattan)
+    12  4   u32    coarse metric (0 .. 4: the three, cosine, cosine_unclamped)
+    16  4   u32    dim (1..8192)
+    20  4   u32    nlist
+    24  4   f32    threshold
+    28  4   u32    low  (0..255)
+    32  4   u32    high (0..255)
+    36  8   u64    n
+    44  ..  f32    coarse centroids [nlist][dim]
+    ..  ..  u32    list ids         [n]           (row order)
+    ..  ..  u32    words            [n][ceil(dim / 32)]
+"""
+from __future__ import annotations
+
+import struct
+
+import numpy as np
+
+from . import _lib
+from ._ivf_common import MAX_NLIST, IVFIndexBase, _Reader, _check_coarse, _check_distance, _check_file_lists, _train_coarse
+from .binary import MAX_DIM, _check_params, _pad_ok, pack_bits, words_per_row
+from .bq import BinaryQuantizer
+from .distance import Distance
+from .errors import DimensionMismatch, InvalidParameter
+
+MAGIC = b"VQIVFBN1"
+_HEADER = struct.Struct("<8sIIIIfIIQ")
+_METRIC_NAMES = ["squared_euclidean", "euclidean", "manhattan", "cosine", "cosine_unclamped"]
+
+
+class IVFBinaryIndex(IVFIndexBase):
+    """coarse centroids (nlist, dim) + BinaryQuantizer (default ``BinaryQuantizer(0.0)``) + distance (default Manhattan)
+    + coarse_distance (default Euclidean), and the rows added to it as packed words"""
+
+    def __init__(self, coarse_centroids, quantizer: BinaryQuantizer | None = None, distance: Distance | None = None,
+                 coarse_distance: Distance | None = None):
+        if quantizer is None:
+            quantizer = BinaryQuantizer(0.0)
+        if distance is None:
+            distance = Distance.manhattan()
+        coarse_distance = _check_distance(coarse_distance)
+        coarse = _check_coarse(coarse_centroids)
+        _check_params(coarse.shape[1], quantizer, distance)
+        self._init_lists(coarse, distance)
+        self._coarse_distance = coarse_distance
+        self._quantizer = quantizer
+        self._host_words = np.empty((0, words_per_row(self.dim)), np.uint32)  # until the handle exists: it then holds the only copy
+
+    # -- shape ------------------------------------------------------------------------------
+    @property
+    def quantizer(self) -> BinaryQuantizer:
+        return self._quantizer
+
+    @property
+    def coarse_distance(self) -> Distance:
+        """the metric lists are probed under, and rows assigned under in `add`"""
+        return self._coarse_distance
+
+    def packed(self) -> np.ndarray:
+        """(n, ceil(dim / 32)) uint32: every row's words, in row order"""
+        return self._host_words if self._ix is None else self._ix.packed()
+
+    def __repr__(self) -> str:
+        return (f"IVFBinaryIndex(n={len(self)}, nlist={self.nlist}, dim={self.dim}, quantizer={self._quantizer!r}, "
+                f"distance={self._distance!r}, coarse_distance={self._coarse_distance!r})")
+
+    # -- build ------------------------------------------------------------------------------
+    @classmethod
+    def train(cls, X, nlist: int, quantizer: BinaryQuantizer | None = None, max_iters: int = 10, distance: Distance | None = None,
+              coarse_distance: Distance | None = None, seed: int = 42) -> "IVFBinaryIndex":
+        """fit the coarse quantizer on X (k-means of whole rows under coarse_distance, as IVFFlatIndex.train); the binary
+        quantizer is given, not trained; the index holds no rows yet (add them with `add`, which packs them)"""
+        coarse_distance = _check_distance(coarse_distance)
+        if quantizer is not None and not isinstance(quantizer, BinaryQuantizer):
+            raise InvalidParameter("quantizer", f"expected a BinaryQuantizer, got {type(quantizer).__name__}")
+        return cls(_train_coarse(X, nlist, max_iters, coarse_distance, seed), quantizer, distance, coarse_distance)
+
+    def _assign_metric(self) -> int:
+        return self._coarse_distance.metric
+
+    def _check_add(self, list_ids, a, what: str, width: int):
+        lid = np.asarray(list_ids)
+        a = np.asarray(a)
+        if lid.ndim != 1:
+            raise InvalidParameter("list_ids", "must be a 1D array (n,)")
+        if a.ndim != 2:
+            raise InvalidParameter(what, f"must have shape (n, {width})")
+        if a.shape[1] != width:
+            raise DimensionMismatch(width, a.shape[1])
+        if a.shape[0] != lid.shape[0]:
+            raise DimensionMismatch(lid.shape[0], a.shape[0])
+        self._check_list_ids(lid)
+        self._check_room(lid.shape[0], what)
+        return np.ascontiguousarray(lid, dtype=np.uint32), a
+
+    def add_rows(self, list_ids, rows) -> np.ndarray:
+        """pack rows (n, dim) floating point, as float32, on the device (bit = x >= threshold) and append the words into
+        the lists list_ids (n,) < nlist; returns the new row ids"""
+        lid, r = self._check_add(list_ids, rows, "rows", self.dim)
+        if r.dtype.kind != "f":
+            raise InvalidParameter("rows", f"must be floating point, got {r.dtype}")
+        if lid.size:
+            with np.errstate(over="ignore"):
+                self._handle().add_rows(lid, np.ascontiguousarray(r, dtype=np.float32))
+        return self._appended(lid)
+
+    def add_codes(self, list_ids, codes) -> np.ndarray:
+        """append rows given as list ids (n,) < nlist and BQ codes (n, dim) uint8 (bit = code >= high); returns the new
+        row ids"""
+        lid, c = self._check_add(list_ids, codes, "codes", self.dim)
+        if c.dtype != np.uint8:
+            raise InvalidParameter("codes", f"dtype must be uint8, got {c.dtype}")
+        c = np.ascontiguousarray(c)
+        if self._ix is not None:
+            if lid.size:
+                self._ix.add_codes(lid, c)
+        else:
+            self._host_words = np.concatenate([self._host_words, pack_bits(c >= np.uint8(self._quantizer.high))])
+        return self._appended(lid)
+
+    def add_packed(self, list_ids, words) -> np.ndarray:
+        """append rows given as list ids (n,) < nlist and packed words (n, ceil(dim / 32)) uint32 in the index layout, pad
+        bits zero; returns the new row ids"""
+        lid, w = self._check_add(list_ids, words, "words", words_per_row(self.dim))
+        if w.dtype != np.uint32:
+            raise InvalidParameter("words", f"dtype must be uint32, got {w.dtype}")
+        w = np.ascontiguousarray(w)
+        if not _pad_ok(w, self.dim):
+            raise InvalidParameter("words", f"a row has a pad bit (dimension >= {self.dim}) set")
+        if self._ix is not None:
+            if lid.size:
+                self._ix.add_packed(lid, w)
+        else:
+            self._host_words = np.concatenate([self._host_words, w])
+        return self._appended(lid)
+
+    def _handle(self) -> "_lib.IVFBin":
+        if self._ix is None:
+            q = self._quantizer
+            ix = _lib.IVFBin(self._coarse, q.threshold, q.low, q.high, self._distance.metric, self._coarse_distance.metric)
+            if len(self):
+                ix.add_packed(self._lists, self._host_words)
+            self._ix = ix
+            self._host_words = None
+        return self._ix
+
+    def close(self) -> None:
+        """release the handle and its device state (the next probe or search builds it again); the words stay"""
+        if self._ix is not None:
+            self._host_words = self._ix.packed()
+            super().close()
+
+    # -- file -------------------------------------------------------------------------------
+    def save(self, path) -> None:
+        q = self._quantizer
+        with open(path, "wb") as f:
+            f.write(_HEADER.pack(MAGIC, self._distance.metric, self._coarse_distance.metric, self.dim, self.nlist,
+                                 np.float32(q.threshold), q.low, q.high, len(self)))
+            f.write(self._coarse.astype("<f4").tobytes())
+            f.write(self._lists.astype("<u4").tobytes())
+            f.write(np.ascontiguousarray(self.packed(), dtype="<u4").tobytes())
+
+    @classmethod
+    def load(cls, path) -> "IVFBinaryIndex":
+        """read a VQIVFBN1 file; every field and every pad bit is checked here, before anything can reach the device"""
+        with open(path, "rb") as f:
+            head = f.read(_HEADER.size)
+            if len(head) != _HEADER.size:
+                raise ValueError("truncated index header")
+            magic, metric, cmetric, dim, nlist, thr, low, high, n = _HEADER.unpack(head)
+            if magic != MAGIC:
+                raise ValueError("not a VQIVFBN1 file")
+            if (metric > _lib.MANHATTAN or cmetric >= len(_METRIC_NAMES) or not 1 <= nlist <= MAX_NLIST or not 1 <= dim <= MAX_DIM
+                    or n >= 1 << 32 or low > 255 or high > 255):
+                raise ValueError("corrupt index header")
+            try:
+                quantizer = BinaryQuantizer(float(thr), low, high)  # the reference's own checks
+            except (InvalidParameter, ValueError, OverflowError) as e:
+                raise ValueError(f"corrupt index header: {e}") from None
+            w = words_per_row(dim)
+            r = _Reader(f)
+            coarse = r.block(nlist * dim, "<f4", "coarse centroids").reshape(nlist, dim)
+            lists = r.lists(n)
+            words = r.block(n * w, "<u4", "words").astype(np.uint32).reshape(n, w)
+            r.end("words")
+        _check_file_lists(lists, nlist)
+        if not _pad_ok(words, dim):
+            raise ValueError(f"corrupt index: a row has a pad bit (dimension >= {dim}) set")
+        self = cls(coarse, quantizer, Distance(_METRIC_NAMES[metric]), Distance(_METRIC_NAMES[cmetric]))
+        self._lists = lists.astype(np.uint32)
+        self._host_words = words
+        return self
