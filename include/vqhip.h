@@ -130,6 +130,9 @@ int vqhip_mfma_bf16_model_case(uint64_t seed, uint64_t trial, uint16_t *a, uint1
 /* statistics of the most recent assign/encode launch of this thread: rows sent to the
  * exact re-check, and the engine used (VQHIP_ENGINE_EXACT / _MFMA) */
 int vqhip_last_assign_stats(uint64_t *rechecked, int *engine);
+/* bf16 products per dimension of the screen kernel behind that launch: 6 (three-slice operands), 3 (the two-slice
+ * form of the sub_dim-16 encode screen), 0 when no bf16 screen ran (exact or fp32-MFMA engine).  Per calling thread. */
+int vqhip_last_screen_products(int *products);
 
 /* per-call HIP-event timing of the assignment stages on the launch stream.  While on, every
  * assign/encode call records events; collect() synchronises, returns the number of calls and

@@ -45,6 +45,7 @@ SIGNATURES = {
     "vqhip_set_stream": (C.c_int, [_vp]),
     "vqhip_synchronize": (C.c_int, []),
     "vqhip_last_assign_stats": (C.c_int, [_u64p, C.POINTER(C.c_int)]),
+    "vqhip_last_screen_products": (C.c_int, [C.POINTER(C.c_int)]),
     "vqhip_xfer_lane_calls": (C.c_int, [C.POINTER(C.c_uint64)]),
     "vqhip_set_profiling": (C.c_int, [C.c_int]),
     "vqhip_profile_collect": (C.c_int, [_u32p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -1282,6 +1283,14 @@ def last_assign_stats():
     r, e = C.c_uint64(), C.c_int()
     check(load().vqhip_last_assign_stats(C.byref(r), C.byref(e)))
     return int(r.value), int(e.value)
+
+
+def last_screen_products() -> int:
+    """bf16 products per dimension of the screen kernel behind this thread's last assign / encode: 6, 3, or 0 when
+    no bf16 screen ran"""
+    p = C.c_int()
+    check(load().vqhip_last_screen_products(C.byref(p)))
+    return int(p.value)
 
 
 # ---- ScalarQuantizer / BinaryQuantizer (stateless elementwise maps; include/vqhip.h) ----

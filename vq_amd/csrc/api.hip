@@ -97,11 +97,13 @@ struct CodebookState {
     bool prepared = false;  // false = the centroids changed: every image is stale
     bool prepared_base = false, prepared_x32 = false;
     int metric = VQHIP_SQUARED_EUCLIDEAN;  // what the prepared images are for (cosine differs)
-    DevBuf cb, prepA, prepCn, meta, cnsqrt, prepA32, cbc, cen, cn32;
+    DevBuf cb, prepA, prepCn, meta, cnsqrt, prepA32, prepA32_3, cbc, cen, cn32;
     bool x32_ok = false;
     uint32_t x32_groups = 0;  // > 1: centroid groups (sub_dim 32 / 48), partial verdicts merged per row
 
-    int init(uint32_t m_, uint32_t k_, uint32_t sd_) {
+    // encode_only: the handle never trains (a PQ encoder) -- eligible shapes also carry the two-slice image of the
+    // three-product screen; a k-means handle re-prepares its images every iteration and has no use for it
+    int init(uint32_t m_, uint32_t k_, uint32_t sd_, bool encode_only = false) {
         m = m_;
         k = k_;
         sd = sd_;
@@ -134,6 +136,7 @@ struct CodebookState {
             screen_bf16_x32_tiling(sd, k, &per, &x32_groups);
             const size_t tiles = (size_t)per * x32_groups;  // image padded to whole centroid groups
             VQ_TRY(prepA32.alloc((size_t)m * tiles * screen_bf16_x32_mfmas(sd) * 4 * 64 * 4));
+            if (encode_only && screen_bf16_three_products_supported(sd, k)) VQ_TRY(prepA32_3.alloc((size_t)m * tiles * 3 * 4 * 64 * 4));
             const uint32_t sdp = x32_padded_sd(sd);  // >= sd: the screen kernel's sub_dim (zero padding)
             VQ_TRY(cbc.alloc((size_t)m * k * sdp * 4));
             VQ_TRY(cen.alloc((size_t)m * (sdp + 4) * 4));
@@ -155,6 +158,7 @@ struct CodebookState {
         v.meta = meta.as<float>();
         v.cnsqrt = cnsqrt.as<float>();
         v.prepA32 = x32_ok ? prepA32.as<uint32_t>() : nullptr;
+        v.prepA32_3 = (x32_ok && prepA32_3.p && metric != VQHIP_COSINE) ? prepA32_3.as<uint32_t>() : nullptr;
         v.cen = x32_ok ? cen.as<float>() : nullptr;
         v.cn32 = x32_ok ? cn32.as<float>() : nullptr;
         return v;
@@ -172,7 +176,7 @@ struct CodebookState {
         }
         if (x32_ok && !prepared_x32) {
             VQ_TRY(launch_prepare_bf16_x32(v, prepA32.as<uint32_t>(), metric == VQHIP_COSINE ? 1 : 0, cbc.as<float>(),
-                                           cen.as<float>(), cn32.as<float>(), stream));
+                                           cen.as<float>(), cn32.as<float>(), stream, const_cast<uint32_t *>(v.prepA32_3)));
             prepared_x32 = true;
         }
         prepared = true;
@@ -194,6 +198,7 @@ struct AssignWorkspace {
     uint32_t stats_m = 0;
     bool stats_pending = false;
     int last_engine = 0;
+    int last_products = 0;  // bf16 products per dimension of the last screen kernel (6 or 3), 0 without a bf16 screen
     ~AssignWorkspace() {
         if (stats_host) (void)hipHostFree(stats_host);
         if (seg_host) (void)hipHostFree(seg_host);
@@ -314,6 +319,7 @@ static int run_assign(CodebookState &cs, AssignWorkspace &ws, const float *X, ui
     a.n = n;
     a.d = d;
     a.metric = metric;
+    a.encode = (fused == nullptr);
     a.sub_list = ws.sub_list.as<uint32_t>();
     a.n_sub = (uint32_t)subs.size();
     a.codes = codes;
@@ -387,8 +393,10 @@ static int run_assign(CodebookState &cs, AssignWorkspace &ws, const float *X, ui
         ws.stats_pending = false;
     }
     ws.last_engine = engine;
+    ws.last_products = (engine == VQHIP_ENGINE_MFMA_BF16) ? (int)a.products : 0;
     ThreadState &st = tls();
     st.last_engine = engine;
+    st.last_products = ws.last_products;
     st.last_rechecked = 0;
     return VQHIP_OK;
 }
@@ -1195,6 +1203,13 @@ int vqhip_last_assign_stats(uint64_t *rechecked, int *engine) {
     VQ_API_END
 }
 
+int vqhip_last_screen_products(int *products) {
+    if (!products) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    const ThreadState &st = tls();
+    *products = (st.last_engine == VQHIP_ENGINE_MFMA_BF16) ? st.last_products : 0;
+    return VQHIP_OK;
+}
+
 int vqhip_xfer_lane_calls(uint64_t *calls) {
     if (!calls) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
     *calls = g_xfer_lane_calls.load();
@@ -1735,6 +1750,7 @@ int vqhip_kmeans_step(vqhip_kmeans *km, uint32_t *counts, uint8_t *changed) {
     km->ws.stats_pending = (km->ws.last_engine == VQHIP_ENGINE_MFMA || km->ws.last_engine == VQHIP_ENGINE_MFMA_BF16);
     g_last_ws = km->ws_id;
     tls().last_engine = km->ws.last_engine;
+    tls().last_products = km->ws.last_products;
     kmeans_finalize_collect(km, counts, changed);
     return VQHIP_OK;
     VQ_API_END
@@ -1921,6 +1937,7 @@ static int kmeans_run_impl(vqhip_kmeans *km, Comm *comm, uint32_t max_iters, uin
     km->ws.stats_pending = !small_loop;
     g_last_ws = km->ws_id;
     tls().last_engine = km->ws.last_engine;
+    tls().last_products = km->ws.last_products;
     return VQHIP_OK;
     VQ_API_END
 }
@@ -2203,7 +2220,7 @@ int vqhip_pq_encoder_create(const float *codebooks, uint32_t m, uint32_t k, uint
     VQ_TRY(current_stream(&s));
     std::unique_ptr<vqhip_pq_encoder> enc(new vqhip_pq_encoder());
     enc->metric = metric;
-    VQ_TRY(enc->cs.init(m, k, sub_dim));
+    VQ_TRY(enc->cs.init(m, k, sub_dim, true));
     enc->cs.metric = (metric == VQHIP_COSINE) ? VQHIP_COSINE : VQHIP_SQUARED_EUCLIDEAN;
     VQ_HIP(hipMemcpyAsync(enc->cs.cb.p, codebooks, (size_t)m * k * sub_dim * 4, hipMemcpyHostToDevice, s));
     VQ_HIP(hipStreamSynchronize(s));
@@ -2296,6 +2313,7 @@ int vqhip_pq_encode(vqhip_pq_encoder *enc, const float *rows, uint64_t n, uint8_
         g_last_ws = enc->ws_id;
         std::lock_guard<std::recursive_mutex> lk(enc->sync.mu);
         tls().last_engine = enc->ws.last_engine;
+        tls().last_products = enc->ws.last_products;
     }
     VQ_TRY(rc);
     if (tier == XferTier::kVector) {

@@ -24,6 +24,7 @@ struct ThreadState {
     int own_stream_device = -1;
     uint64_t last_rechecked = 0;
     int last_engine = 0;
+    int last_products = 0;
 };
 
 ThreadState &tls();

@@ -18,6 +18,18 @@
 // Margin: DESIGN.md "screen soundness" (the per-MFMA accumulation bound eps_M comes from the
 // bit-exact model of the instruction's adder, tests/mfma_model.py, validated on the device).
 //
+//
+// Three-product form (pipelined kernel, NPR = 3: sub_dim-16 encode under squared-L2 / Euclidean): TWO rounded slices,
+//     v1 = RNE_bf16(v), v2 = RNE_bf16(v - v1):  |v - v1| <= 2^-8 |v| (v - v1 exact in f32),  |v - v1 - v2| <= 2^-16 |v|
+//     a.x ~= a1x1 + a2x1 + a1x2;  dropped: a2x2 + a1 rx + a2 rx + ra x < 3.02 * 2^-16 |a||x| = 773 u |a||x| per dimension
+// over a subspace <= 386.5 u B' (Cauchy-Schwarz, 2|c'||x'| <= B'/2), so
+//     E3 <= (388 + 20 NMF + sd) u B' + floor / 2,     T3 = (8 sd + 776 + 40 NMF + 160) u B' + floor = 1184 u B' + floor
+// against 544 u for six products.  Unchanged, because they do not depend on how the products are formed: the index
+// packing (128), Euclidean's +4uB and the rounding of x - mu, c - mu (16 each), the accumulation model (same
+// instruction; 3 MFMAs per tile).  floor = 1e-35 (|x'| + max|c'|) + 1e-37 still covers slices below the normal range
+// (at worst dropped whole: 3 sd products x 2^-126 x max(|a|, |x|)).  A component that is non-finite or rounds to +-inf
+// leaves inf - inf = NaN in the second slice: the row's values are all NaN and it is listed as before.
+//
 // The round-1 16x16x32 variants (registers / software-pipelined / A images in LDS with 2 and 4
 // waves per SIMD; 0.60 / 0.87 / 0.80 ms at C2 against 0.49 here) were removed in round 2; they
 // are in the history up to commit 65d0c95.
@@ -63,6 +75,35 @@ __host__ __device__ inline void split3(float v, uint32_t (&part)[3]) {
     part[2] = b2;
 }
 
+// ---- two-slice form (three products: a1x1 + a2x1 + a1x2; sub_dim 16 encode, see the pipelined kernel) ----------------
+// v1 = RNE_bf16(v), v2 = RNE_bf16(v - v1): |v - v1| <= 2^-8 |v| and v - v1 is exact in f32 (it is a multiple of ulp(v)
+// below 2^-8 |v|), so |v - v1 - v2| <= 2^-16 |v|.  Each slice as the high half of an f32 word, like split3.
+__host__ __device__ inline uint32_t rne_bf16_bits(uint32_t u) { return (u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u; }
+__host__ __device__ inline void split2_rne(float v, uint32_t (&part)[3]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t b0 = rne_bf16_bits(__float_as_uint(v));
+    const uint32_t b1 = rne_bf16_bits(__float_as_uint(v - __uint_as_float(b0)));
+#else
+    auto fu = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
+    auto uf = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
+    const uint32_t b0 = rne_bf16_bits(fu(v));
+    const uint32_t b1 = rne_bf16_bits(fu(v - uf(b0)));
+#endif
+    part[0] = b0;
+    part[1] = b1;
+    part[2] = 0u;
+}
+// the rows' side of the same split, two values at a time: {bf16(lo), bf16(hi)} in one dword, round to nearest even
+__device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
+    uint32_t r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+    return r;
+}
+// margin coefficient of the three-product form, in units of u (DESIGN.md "screen soundness"): the dropped terms
+// a2x2 + a1 rx + a2 rx + ra x are <= 3.02 * 2^-16 |a||x| per dimension = 773 u |a||x|, over a subspace <= 386.5 u B',
+// twice that in the test (776 with slack) where the six-product form has 16
+constexpr float kScreen3DroppedUlps = 776.0f;
+
 // ---- variant X32: 32x32x16 MFMA tiles, 32 rows per wave step ------------------------------------
 // Ablation of variant P showed the per-tile tail (two-level cross-lane merge, margin test, byte
 // stores, work-list append) costing a third of the kernel.  With v_mfma_f32_32x32x16_bf16 a lane's
@@ -80,13 +121,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // common translation, but the margin T is proportional to (|x - mu| + max|c - mu|)^2, so the
 // screen works on x - mu and c - mu with mu = the mean centroid of the subspace: Uniform[0,1)
 // sub-vectors of 16 dimensions shrink from |x| ~ 2.3 to ~ 1.15 (T / 4), data with a large common
-// offset by far more.  cen[s] = {mu[sd], max|c - mu|, margin coefficient, -, -}; cn32 = |c - mu|^2
+// offset by far more.  cen[s] = {mu[sd], max|c - mu|, margin coefficient, same for three products, -}; cn32 = |c - mu|^2
 // (sequential f32 like k_prepare_codebook), padded with a large finite value.
 // sdp >= sd: sub_dim of the screen kernel that serves this codebook (x32_padded_sd); the copy and mu are
 // written sdp wide with zeros in the padding, where the screen's operands are zero too.
 __global__ __launch_bounds__(256) void k_center_codebook_x32(const float *__restrict__ cb, uint32_t m, uint32_t k,
                                                              uint32_t sd, uint32_t sdp, uint32_t cn_stride, uint32_t nmf,
-                                                             float *__restrict__ cbc, float *__restrict__ cen,
+                                                             uint32_t nmf3, float *__restrict__ cbc, float *__restrict__ cen,
                                                              float *__restrict__ cn32) {
     __shared__ float s_mu[256];
     __shared__ float s_max[256];
@@ -150,7 +191,9 @@ __global__ __launch_bounds__(256) void k_center_codebook_x32(const float *__rest
         const float coef = (8.0f * (float)sdp + 16.0f + 2.0f * kBf16AssumedUlps * (float)nmf + 16.0f + 128.0f + 16.0f) * u;
         cen_s[sdp] = sqrtf(s_max[0]) * 1.0000005f + 1e-30f;
         cen_s[sdp + 1] = s_bad[0] ? __builtin_inff() : coef;
-        cen_s[sdp + 2] = 0.0f;
+        // three-product form (nmf3 MFMAs per tile, 0 = the shape has none): its own coefficient beside the other
+        const float coef3 = (8.0f * (float)sdp + kScreen3DroppedUlps + 2.0f * kBf16AssumedUlps * (float)nmf3 + 16.0f + 128.0f + 16.0f) * u;
+        cen_s[sdp + 2] = (nmf3 == 0) ? 0.0f : s_bad[0] ? __builtin_inff() : coef3;
         cen_s[sdp + 3] = 0.0f;
     }
 }
@@ -159,11 +202,12 @@ __global__ __launch_bounds__(256) void k_center_codebook_x32(const float *__rest
 // src/core/distance.rs:113-115) so that the screen forms s_j = -|x| cos(x, c_j)
 // sd_src: row length of `cb` (the codebook as is for cosine, already sd wide for the centred copy); dimensions
 // from sd_src up to the kernel's sd are zero padding
+// npairs: 6 = three truncated slices, six products; 3 = two rounded slices, products a1x1, a2x1, a1x2 (split2_rne)
 // src_stride: floats between consecutive centroids of `cb` (a 64-dimension chunk of a wider sub-vector is prepared
 // with cb advanced to the chunk and sd_src = the chunk's live dimensions)
 __global__ __launch_bounds__(256) void k_prepare_bf16_x32(const float *__restrict__ cb, uint32_t m, uint32_t k,
                                                           uint32_t sd_src, uint32_t src_stride, uint32_t sd, uint32_t nt32,
-                                                          uint32_t nmf, int cosine,
+                                                          uint32_t nmf, uint32_t npairs, int cosine,
                                                           const float *__restrict__ cnsqrt,
                                                           uint32_t *__restrict__ prepA32) {
     const uint32_t s = blockIdx.x;
@@ -177,7 +221,7 @@ __global__ __launch_bounds__(256) void k_prepare_bf16_x32(const float *__restric
         for (uint32_t hh = 0; hh < 2; ++hh) {
             const uint32_t flat = 8 * f + 2 * w + hh;  // k-slot of this lane half over all MFMAs
             const uint32_t pair = flat / dph, dd = flat - pair * dph;
-            if (pair < 6 && j < k && h * dph + dd < sd_src) {
+            if (pair < npairs && j < k && h * dph + dd < sd_src) {
                 uint32_t parts[3];
                 const float c = cbs[(size_t)j * src_stride + h * dph + dd];
                 float av = -2.0f * c;
@@ -185,7 +229,8 @@ __global__ __launch_bounds__(256) void k_prepare_bf16_x32(const float *__restric
                     const float nb = cnsqrt[(size_t)s * k + j];
                     av = (nb < 1e-10f) ? 0.0f : -(c / nb);
                 }
-                split3(av, parts);
+                if (npairs == 3) split2_rne(av, parts);  // pairs 0..2 name slices 0 and 1 only
+                else split3(av, parts);
                 half[hh] = parts[pair_a((int)pair)] >> 16;
             }
         }
@@ -205,7 +250,7 @@ __global__ __launch_bounds__(256) void k_prepare_bf16_x32(const float *__restric
 // copies of the fused update's LDS sums per wave: 2 while four (or eight) waves' accumulators still fit a CU
 // A image of NT32 tiles at sub_dim SD: NT32 x ceil(3 SD / 8) MFMA operands of 4 registers.  Up to 96 registers two
 // waves fit a SIMD (k <= 128 at sub_dim 16: 0.30 vs 0.37 ms at C2 / k = 128; k <= 256 at sub_dim 8 -- C3 and C5)
-__host__ __device__ constexpr bool x32_two_waves(int sd, int nt32) { return nt32 * ((6 * (sd / 2) + 7) / 8) * 4 <= 96; }
+__host__ __device__ constexpr bool x32_two_waves(int sd, int nt32, int npr = 6) { return nt32 * ((npr * (sd / 2) + 7) / 8) * 4 <= 96; }
 __host__ __device__ constexpr uint32_t x32_acc_copies(int sd, int nt32) {
     const uint32_t waves = x32_two_waves(sd, nt32) ? 8u : 4u;
     return (waves * (uint32_t)nt32 * 32u * (2u * (uint32_t)sd + 1u) * 4u <= 140u * 1024u) ? 2u : 1u;
@@ -739,18 +784,31 @@ __host__ __device__ constexpr uint32_t x32p_acc_bytes_per_wave(int sd, int nt32)
 // shares one tail between two steps (tail_pair_piece), so a row whose gap sits within the tags' 64 ulps of the margin may
 // land on the other side of the test -- in the re-check list or out of it.  launch_one_x32 picks this variant for chunks of at least kPipeMinSteps steps, 8 tiles (k in 225..256),
 // sub_dim 8 or 16, one centroid group.
-template <int SD, int NT32, bool ACC = false>
-__global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32) ? 2 : 1) void k_assign_screen_bf16_x32p(
+// NPR = term pairs per dimension.  6: the three truncated slices above.  3 (sub_dim 16, encode form, squared-L2 /
+// Euclidean): two ROUNDED slices per operand (split2_rne) and the products a1x1 + a2x1 + a1x2 -- MFMA f of a tile carries
+// pair f for the lane half's 8 dimensions, so b[0] and b[1] are the same registers (x1) and b[2] is x2; three MFMAs per
+// tile, a 96-register A image in VGPRs and two waves per SIMD, i.e. the sub_dim-8 kernel's MFMA and reduce structure.
+// The screen only has to PROVE winners: half the matrix work is paid for by a wider margin (the dropped terms are
+// <= 773 u |a||x| per dimension instead of 8 u; the codebook's three-product coefficient sits in cen[sd + 2]) and so by
+// more rows in the exact re-check, which settles every code either way.  Slices that round to +-inf (|v| > 3.39e38)
+// leave inf - inf = NaN in the second slice: the row's values are NaN and it goes to the list like any non-finite row.
+// PVW > 0 (NPR = 3 only): the data's sub_dim is sdr < SD, loaded in parts of PVW floats, zeros behind (see the X32 kernel).
+template <int SD, int NT32, bool ACC = false, int NPR = 6, int PVW = 0>
+__global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void k_assign_screen_bf16_x32p(
     const float *__restrict__ X, uint64_t n, uint32_t d, uint32_t m, const uint32_t *__restrict__ prepA32,
     const float *__restrict__ prepCn, uint32_t cn_stride, const float *__restrict__ meta,
     const uint32_t *__restrict__ sub_list, uint32_t n_sub, uint8_t *__restrict__ codes, uint32_t *__restrict__ wl_rows,
     uint32_t *__restrict__ wl_seg, uint32_t n_seg, uint64_t wl_stride, int cosine, uint32_t k_real,
     const float *__restrict__ cen, const uint8_t *__restrict__ gate_active, const uint32_t *__restrict__ gate_halt,
-    uint8_t *__restrict__ codes_t, uint64_t codes_t_pitch, float *__restrict__ acc_sums, uint32_t *__restrict__ acc_counts) {
+    uint8_t *__restrict__ codes_t, uint64_t codes_t_pitch, float *__restrict__ acc_sums, uint32_t *__restrict__ acc_counts,
+    uint32_t sdr) {
     static_assert(NT32 == 8 && (SD == 8 || SD == 16), "pipelined screen: 8 tiles, sub_dim 8 or 16");
+    static_assert(NPR == 6 || (NPR == 3 && SD == 16 && !ACC), "three products: sub_dim 16, encode form");
+    static_assert(PVW == 0 || NPR == 3, "padded rows: three-product form only");
     constexpr int DPH = SD / 2;
-    constexpr int NMF = (6 * DPH + 7) / 8;
-    static_assert(6 * DPH == 8 * NMF, "every MFMA carries one term pair (sub_dim 16) or two (sub_dim 8), no padding slots");
+    constexpr int NMF = (NPR * DPH + 7) / 8;
+    static_assert(NPR * DPH == 8 * NMF, "every MFMA carries one term pair (sub_dim 16) or two (sub_dim 8), no padding slots");
+    constexpr bool kTwo = x32_two_waves(SD, NT32, NPR);  // two waves per SIMD: A image in VGPRs, |c|^2 from LDS
     const bool halted = gate_halt && *gate_halt;
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t h = lane >> 5, p = lane & 31;
@@ -874,14 +932,15 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32) ? 2 : 1) void k_ass
     } else {
         const float *cs = cen + (size_t)s * (SD + 4);
         cmax = cs[SD];
-        tcoef = cs[SD + 1];
+        tcoef = cs[SD + (NPR == 3 ? 2 : 1)];
 #pragma unroll
         for (int q = 0; q < DPH; ++q) mu[q] = cs[DPH * h + q];
     }
     f32x4 mu4[DPH / 4];
 #pragma unroll
     for (int q = 0; q < DPH; ++q) mu4[q / 4][q % 4] = mu[q];
-    const char *const x_base = reinterpret_cast<const char *>(X + (size_t)s * SD + (size_t)DPH * h);
+    const size_t sub0 = (size_t)s * (PVW > 0 ? sdr : (uint32_t)SD);  // first float of the sub-vector
+    const char *const x_base = reinterpret_cast<const char *>(X + sub0 + (size_t)DPH * h);
     const uint32_t x_pitch = d * 4;
     // codes: [row][m] bytes, or the [m][pitch] scratch of the transposing caller -- one address form for both
     uint8_t *const code_base = codes_t ? codes_t + (size_t)s * codes_t_pitch : codes + s;
@@ -890,7 +949,7 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32) ? 2 : 1) void k_ass
     // latency; one step deep the wave waited 19 % of its time): at the top of step st, xn_[par ^ 1] holds step st + 1
     // (about to be consumed, then reloaded with st + 1 + kDeep) and xn_[par] step st + 2
     // (two waves per SIMD: one step deep -- the partner wave covers the latency and the registers are short)
-    constexpr int kDeep = x32_two_waves(SD, NT32) ? 1 : 2;
+    constexpr int kDeep = kTwo ? 1 : 2;
     // kept as the 16-byte vectors the loads return and consumed as such (x - mu on whole vectors): handed on as scalars,
     // the packed subtraction paired lanes 0 / 3 and 1 / 2 of a vector and the register copies that pairing needs were
     // placed right behind the LOAD -- with its wait: the sub_dim-8 kernel waited for every row load a quarter of a step
@@ -899,8 +958,30 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32) ? 2 : 1) void k_ass
     auto load_x = [&](uint32_t row, int buf) {
         row = row < n32 ? row : n32 - 1;
         const float *ptr = reinterpret_cast<const float *>(x_base + (uint64_t)row * x_pitch);
+        if constexpr (PVW > 0) {
+            // parts that run past the sub-vector re-read its first part (a valid address) and are zeroed
+            const float *first = ptr - DPH * h;
 #pragma unroll
-        for (int q = 0; q < DPH / 4; ++q) xn_[buf][q] = *reinterpret_cast<const f32x4 *>(ptr + 4 * q);
+            for (int q = 0; q < DPH; q += PVW) {
+                const bool live = (uint32_t)(DPH * h + q) < sdr;
+                const float *pq = live ? ptr + q : first;
+                if constexpr (PVW == 4) {
+                    const f32x4 t = *reinterpret_cast<const f32x4 *>(pq);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) xn_[buf][q / 4][e] = live ? t[e] : 0.0f;
+                } else if constexpr (PVW == 2) {
+                    const float2 t = *reinterpret_cast<const float2 *>(pq);
+                    xn_[buf][q / 4][q % 4 + 0] = live ? t.x : 0.0f;
+                    xn_[buf][q / 4][q % 4 + 1] = live ? t.y : 0.0f;
+                } else {
+                    const float t = *pq;
+                    xn_[buf][q / 4][q % 4] = live ? t : 0.0f;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < DPH / 4; ++q) xn_[buf][q] = *reinterpret_cast<const f32x4 *>(ptr + 4 * q);
+        }
     };
     auto init_acc = [&](f32x16 &acc, int i) {
 #pragma unroll
@@ -917,7 +998,7 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32) ? 2 : 1) void k_ass
     // accumulator's initial value for them (4 ds_read_b128 and a wait per tile; every instruction of a lone wave costs
     // an issue slot of ~5 cycles, profiles/ubench/valu_issue.hip).  (C and D of an MFMA share their register class, so
     // the 64 spare AGPRs cannot hold the other tiles' images.)  Two waves per SIMD (sub_dim 8): LDS for all tiles.
-    constexpr int kCnV = x32_two_waves(SD, NT32) ? 0 : (ACC ? 4 : 6);
+    constexpr int kCnV = kTwo ? 0 : (ACC ? 4 : 6);
     f32x16 cnr[kCnV > 0 ? kCnV : 1];
 #pragma unroll
     for (int i = 0; i < kCnV; ++i) init_acc(cnr[i], i);
@@ -928,11 +1009,12 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32) ? 2 : 1) void k_ass
         }
         // two waves per SIMD: a kernel that names AGPRs gets the register file split 128 : 128, and this one needs ~165
         // VGPRs next to the 96 of the A image -- all of it in VGPRs (256) instead of spilling through v_accvgpr moves
-        if constexpr (x32_two_waves(SD, NT32)) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(accv) : "v"(a[ti][f]), "v"(bv));
+        if constexpr (kTwo) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(accv) : "v"(a[ti][f]), "v"(bv));
         else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(accv) : "a"(a[ti][f]), "v"(bv));
     };
 
     bf16x8 b[2][NMF];
+    auto bsel = [](int f) { return (NPR == 3 && f == 1) ? 0 : f; };  // three products: pairs 0 and 1 share x1
     float q1[2][2], q2[2][2];  // [step parity][chain]: the two smallest tagged values so far (see reduce_hg)
     float xc[DPH];
     uint32_t xp[3][DPH];
@@ -951,7 +1033,7 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32) ? 2 : 1) void k_ass
         if (k == 0) {
 #pragma unroll
             for (int q = 0; q < DPH / 4; ++q) {
-                if constexpr (x32_two_waves(SD, NT32) && (!ACC || VQ_ACC_F64)) {
+                if constexpr (kTwo && (!ACC || VQ_ACC_F64)) {
                     f32x4 dv = xn_[nb % kDeep][q] - mu4[q];
                     asm volatile("" : "+v"(dv));  // consumed HERE (see reduce_hg), the registers are free for the next load
                     xc[4 * q + 0] = dv[0], xc[4 * q + 1] = dv[1], xc[4 * q + 2] = dv[2], xc[4 * q + 3] = dv[3];
@@ -969,6 +1051,19 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32) ? 2 : 1) void k_ass
 #pragma unroll
                 for (int q = 0; q < DPH / 4; ++q) asm volatile("" ::"v"(xn_[nb % kDeep][q]));
             }
+        } else if (k <= DPH / 4 && NPR == 3) {
+            // two rounded slices of four dimensions, packed as they leave the conversion: xp[0] / xp[1][w] = slice 1 / 2
+            // of dimensions 2w, 2w + 1 (low, high half) -- k-slots 2w, 2w + 1 of the MFMA that carries the slice
+#pragma unroll
+            for (int w = 2 * (k - 1); w < 2 * k; ++w) {
+                const float v0 = xc[2 * w], v1 = xc[2 * w + 1];
+                const uint32_t p1 = cvt_pk_bf16(v0, v1);
+                const float r0 = v0 - __uint_as_float(p1 << 16), r1 = v1 - __uint_as_float(p1 & 0xFFFF0000u);  // exact
+                xp[0][w] = p1;
+                xp[1][w] = cvt_pk_bf16(r0, r1);
+                xsN = fmaf(v0, v0, xsN);
+                xsN = fmaf(v1, v1, xsN);
+            }
         } else if (k <= DPH / 4) {
 #pragma unroll
             for (int q = 4 * (k - 1); q < 4 * k; ++q) {
@@ -978,6 +1073,15 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32) ? 2 : 1) void k_ass
                 xp[1][q] = parts[1];
                 xp[2][q] = parts[2];
                 xsN = fmaf(xc[q], xc[q], xsN);
+            }
+        } else if (NPR == 3) {
+            const int f = k - 1 - DPH / 4;  // b[.][1] is never written: MFMA 1 reads b[.][0] (bsel)
+            if (f != 1) {
+                u32x4 v;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) v[w] = xp[f == 0 ? 0 : 1][w];
+                b[nb][f] = __builtin_bit_cast(bf16x8, v);
+                asm volatile("" ::"v"(b[nb][f]));
             }
         } else {
             const int f = k - 1 - DPH / 4;
@@ -1309,9 +1413,9 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32) ? 2 : 1) void k_ass
     if (2 >= kCnV) init_acc(acc[2], 2);
     asm volatile("s_nop 1");
 #pragma unroll
-    for (int f = 0; f < NMF; ++f) mfma(acc[0], 0, f, b[0][f]);
+    for (int f = 0; f < NMF; ++f) mfma(acc[0], 0, f, b[0][bsel(f)]);
 #pragma unroll
-    for (int f = 0; f < NMF; ++f) mfma(acc[1], 1, f, b[0][f]);
+    for (int f = 0; f < NMF; ++f) mfma(acc[1], 1, f, b[0][bsel(f)]);
     __builtin_amdgcn_sched_barrier(0);
 
     // always an even number of steps: a step at or past st1 is a dummy (rows clamped, nothing written), so the loop body
@@ -1335,8 +1439,8 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32) ? 2 : 1) void k_ass
                 if ((i + 3) % NT32 >= kCnV) init_acc(acc[(i + 3) & 3], (i + 3) % NT32);
 #pragma unroll
                 for (int f = 0; f < NMF; ++f) {
-                    if (i + 2 < NT32) mfma(acc[(i + 2) & 3], i + 2, f, b[par][f]);
-                    else mfma(acc[(i + 2) & 3], i + 2 - NT32, f, b[par ^ 1][f]);
+                    if (i + 2 < NT32) mfma(acc[(i + 2) & 3], i + 2, f, b[par][bsel(f)]);
+                    else mfma(acc[(i + 2) & 3], i + 2 - NT32, f, b[par ^ 1][bsel(f)]);
                     // the gap's share of the phase: 4 reduce half-groups (9 VALU instructions each) and the fillers.
                     // Order of the fillers: the rows of step st + 1 are consumed (and the load of st + 2 issued) FIRST,
                     // the tail's stores follow -- the wait in front of the next consumption covers every earlier
@@ -1678,7 +1782,19 @@ template <int SD, int NT32, int G = 1, int PVW = 0, bool ACC = false>
 int launch_one_x32(const CodebookView &cb, const AssignArgs &a, hipStream_t stream, uint32_t groups_rt = 0) {
     const uint32_t groups = (G > 0) ? (uint32_t)G : groups_rt;  // G == 0: run-time group count (k > 256)
     const uint64_t n_steps = (a.n + 31) / 32;
-    const uint32_t waves_per_simd = x32_two_waves(SD, NT32) ? 2 : 1;  // small A images leave room for two
+    static const bool pipe_on = [] {
+        const char *e = std::getenv("VQHIP_SCREEN_PIPE");
+        return !(e && e[0] == '0');
+    }();
+    // Three-product form of the pipelined screen (k_assign_screen_bf16_x32p, NPR = 3): encode (no fused update) under
+    // squared-L2 / Euclidean at sub_dim 16 (or 13..15 padded onto it) and 8 tiles, when the codebook carries the
+    // two-slice image (k in 225..256) and the rows make at least one chunk of kPipeMinSteps steps.  Codes are final
+    // after the exact re-check under either form: the choice is one of speed only.
+    bool use3 = false;
+    if constexpr (G == 1 && SD == 16 && NT32 == 8 && !ACC && PVW != 4)
+        use3 = pipe_on && a.encode && cb.prepA32_3 && a.metric != VQHIP_COSINE && n_steps >= kPipeMinSteps && a.n < 0xFFFFFFC0ull;
+    a.products = use3 ? 3u : 6u;
+    const uint32_t waves_per_simd = (use3 || x32_two_waves(SD, NT32)) ? 2 : 1;  // small A images leave room for two
     const uint32_t n_virt = a.n_sub * groups;
     // Training: the chunk count comes from ALL m subspaces, listed or not.  A host-driven fit drops retired subspaces
     // from the list where the device-driven run gates them; with the geometry of the list the survivors' rows were
@@ -1694,7 +1810,15 @@ int launch_one_x32(const CodebookView &cb, const AssignArgs &a, hipStream_t stre
     if (want_waves < n_virt_geom) want_waves = n_virt_geom;
     uint32_t blocks = (uint32_t)((want_waves + kWavesPerBlock - 1) / kWavesPerBlock);
     while ((uint64_t)blocks * kWavesPerBlock < n_virt_geom) ++blocks;
-    const uint32_t n_chunks = (blocks * kWavesPerBlock) / n_virt_geom;
+    uint32_t n_chunks = (blocks * kWavesPerBlock) / n_virt_geom;
+    if (use3) {
+        // every chunk long enough for the pipelined kernel (the form has no other): fewer waves on a short input
+        const uint64_t cap = n_steps / kPipeMinSteps;
+        if (n_chunks > cap) {
+            n_chunks = (uint32_t)cap;
+            blocks = (uint32_t)(((uint64_t)n_chunks * n_virt + kWavesPerBlock - 1) / kWavesPerBlock);
+        }
+    }
     if (n_virt_geom != n_virt) blocks = (uint32_t)(((uint64_t)n_chunks * n_virt + kWavesPerBlock - 1) / kWavesPerBlock);
     if (G == 1) {
         if (!a.wl_seg || n_chunks > a.wl_seg_cap)
@@ -1722,14 +1846,19 @@ int launch_one_x32(const CodebookView &cb, const AssignArgs &a, hipStream_t stre
         }
     }
     bool piped = false;
+    if constexpr (G == 1 && SD == 16 && NT32 == 8 && !ACC && PVW != 4) {
+        if (use3) {
+            piped = true;
+            hipLaunchKernelGGL((k_assign_screen_bf16_x32p<SD, NT32, false, 3, PVW>), dim3(blocks), dim3(kBlock), 0, stream, a.X, a.n, a.d,
+                               cb.m, cb.prepA32_3, cb.cn32, NT32 * 32, cb.meta, a.sub_list, a.n_sub, a.codes, a.wl_rows, a.wl_seg,
+                               n_chunks, a.wl_stride, 0, cb.k, cb.cen, a.gate_active, a.gate_halt, a.codes_t, a.codes_t_pitch,
+                               nullptr, nullptr, cb.sd);
+        }
+    }
     if constexpr (G == 1 && PVW == 0 && NT32 == 8 && (SD == 16 || SD == 8)) {
         // chunks of at least kPipeMinSteps steps: the software-pipelined variant (same results)
-        static const bool pipe_on = [] {
-            const char *e = std::getenv("VQHIP_SCREEN_PIPE");
-            return !(e && e[0] == '0');
-        }();
         const uint64_t steps_per_chunk = (n_steps + n_chunks - 1) / n_chunks;
-        if (pipe_on && steps_per_chunk >= kPipeMinSteps && a.n < 0xFFFFFFC0ull) {
+        if (!piped && pipe_on && steps_per_chunk >= kPipeMinSteps && a.n < 0xFFFFFFC0ull) {
             piped = true;
             if constexpr (ACC) {
                 static PerDeviceOnce attr_set_p;
@@ -1743,7 +1872,8 @@ int launch_one_x32(const CodebookView &cb, const AssignArgs &a, hipStream_t stre
             hipLaunchKernelGGL((k_assign_screen_bf16_x32p<SD, NT32, ACC>), dim3(blocks), dim3(kBlock), dyn_lds_p, stream, a.X, a.n, a.d,
                                cb.m, cb.prepA32, cb.cn32, NT32 * 32, cb.meta, a.sub_list, a.n_sub, a.codes, a.wl_rows, a.wl_seg,
                                n_chunks, a.wl_stride, a.metric == VQHIP_COSINE ? 1 : 0, cb.k, cb.cen, a.gate_active,
-                               a.gate_halt, a.codes_t, a.codes_t_pitch, ACC ? a.acc_sums : nullptr, ACC ? a.acc_counts : nullptr);
+                               a.gate_halt, a.codes_t, a.codes_t_pitch, ACC ? a.acc_sums : nullptr, ACC ? a.acc_counts : nullptr,
+                               (uint32_t)SD);
         }
     }
     if (!piped)
@@ -1782,6 +1912,7 @@ int launch_wide(const CodebookView &cb, const AssignArgs &a, hipStream_t stream,
     uint32_t blocks = (uint32_t)((want_waves + kWavesPerBlock - 1) / kWavesPerBlock);
     while ((uint64_t)blocks * kWavesPerBlock < n_virt) ++blocks;
     a.n_seg = 0;  // the merge kernel appends to the unsegmented list
+    a.products = 6u;
     const size_t chunk_stride = (size_t)cb.m * groups * 24 * 4 * 64;
     hipLaunchKernelGGL((k_assign_screen_bf16_wide<NCH>), dim3(blocks), dim3(kBlock), 0, stream, a.X, a.n, a.d, cb.prepA32,
                        chunk_stride, cb.cn32, groups * 32, a.sub_list, a.n_sub, a.metric == VQHIP_COSINE ? 1 : 0, cb.k, cb.cen,
@@ -1880,8 +2011,15 @@ uint32_t screen_bf16_x32_mfmas(uint32_t sd_real) {
 }
 // X32 images of a codebook.  Squared-L2 / Euclidean: centred copy (cbc), its norms (cn32) and {mu, max|c-mu|,
 // coefficient} (cen), then the bf16 slices of -2(c - mu); cosine: bf16 slices of -c/|c| from the codebook as is.
+bool screen_bf16_three_products_supported(uint32_t sd, uint32_t k) {
+    uint32_t per = 0, groups = 0;
+    screen_bf16_x32_tiling(sd, k, &per, &groups);
+    return x32_padded_sd(sd) == 16 && per == 8 && groups == 1 && k >= 225 && k <= 256;
+}
+
+// prepA32_3: the two-slice image of the three-product form ([m][8][3][4][64]; squared-L2 / Euclidean), nullptr = none
 int launch_prepare_bf16_x32(const CodebookView &v, uint32_t *prepA32, int cosine, float *cbc, float *cen,
-                            float *cn32, hipStream_t stream) {
+                            float *cn32, hipStream_t stream, uint32_t *prepA32_3) {
     if (v.m == 0) return VQHIP_OK;
     uint32_t per = 0, groups = 0;
     screen_bf16_x32_tiling(v.sd, v.k, &per, &groups);
@@ -1890,7 +2028,7 @@ int launch_prepare_bf16_x32(const CodebookView &v, uint32_t *prepA32, int cosine
     const uint32_t sdp = x32_padded_sd(v.sd);
     if (!cosine) {
         hipLaunchKernelGGL(k_center_codebook_x32, dim3(v.m), dim3(256), 0, stream, v.cb, v.m, v.k, v.sd, sdp, nt32 * 32,
-                           screen_bf16_x32_mfmas(v.sd), cbc, cen, cn32);
+                           screen_bf16_x32_mfmas(v.sd), prepA32_3 ? 3u : 0u, cbc, cen, cn32);
         VQ_LAUNCH_CHECK("k_center_codebook_x32");
         src = cbc;  // sdp wide
     }
@@ -1900,13 +2038,16 @@ int launch_prepare_bf16_x32(const CodebookView &v, uint32_t *prepA32, int cosine
         for (uint32_t c = 0; c < sdp / 64; ++c) {
             const uint32_t live = v.sd > 64 * c ? std::min(64u, v.sd - 64 * c) : 0u;
             hipLaunchKernelGGL(k_prepare_bf16_x32, dim3(v.m, 16), dim3(256), 0, stream, src + 64 * c, v.m, v.k, live, stride, 64u,
-                               nt32, 24u, cosine, v.cnsqrt, prepA32 + c * chunk_stride);
+                               nt32, 24u, 6u, cosine, v.cnsqrt, prepA32 + c * chunk_stride);
         }
         VQ_LAUNCH_CHECK("k_prepare_bf16_x32");
         return VQHIP_OK;
     }
     hipLaunchKernelGGL(k_prepare_bf16_x32, dim3(v.m, 16), dim3(256), 0, stream, src, v.m, v.k, cosine ? v.sd : sdp,
-                       cosine ? v.sd : sdp, sdp, nt32, screen_bf16_x32_mfmas(v.sd), cosine, v.cnsqrt, prepA32);
+                       cosine ? v.sd : sdp, sdp, nt32, screen_bf16_x32_mfmas(v.sd), 6u, cosine, v.cnsqrt, prepA32);
+    if (prepA32_3 && !cosine)
+        hipLaunchKernelGGL(k_prepare_bf16_x32, dim3(v.m, 16), dim3(256), 0, stream, src, v.m, v.k, sdp, sdp, sdp, nt32, 3u, 3u, 0,
+                           v.cnsqrt, prepA32_3);
     VQ_LAUNCH_CHECK("k_prepare_bf16_x32");
     return VQHIP_OK;
 }

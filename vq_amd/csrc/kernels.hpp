@@ -37,7 +37,8 @@ struct CodebookView {
     const float *meta = nullptr;     // [m][4]            {max|c|, margin coefficient, -, -}
     const float *cnsqrt = nullptr;   // [m][k]            sqrt(sum c^2) (cosine's norm_b)
     const uint32_t *prepA32 = nullptr;  // [m][ceil(k/32)][NMF][4][64] same, 32x32x16 MFMA lane order
-    const float *cen = nullptr;      // [m][sd+4]  X32, L2: {mu[sd], max|c-mu|, margin coefficient, -, -}
+    const uint32_t *prepA32_3 = nullptr;  // [m][8][3][4][64] two rounded slices, three products (sub_dim 16 encode), or null
+    const float *cen = nullptr;      // [m][sd+4]  X32, L2: {mu[sd], max|c-mu|, margin coefficient, same for three products, -}
     const float *cn32 = nullptr;     // [m][ceil(k/32)*32]  X32, L2: |c-mu|^2, finite padding
 };
 
@@ -64,8 +65,9 @@ bool screen_bf16_x32_supported(uint32_t sd, uint32_t k);
 bool screen_bf16_fused_update_supported(uint32_t sd, uint32_t k);
 void screen_bf16_x32_tiling(uint32_t sd, uint32_t k, uint32_t *nt32_per_group, uint32_t *groups);
 uint32_t screen_bf16_x32_mfmas(uint32_t sd);
+bool screen_bf16_three_products_supported(uint32_t sd, uint32_t k);  // shapes with a three-product pipelined screen
 int launch_prepare_bf16_x32(const CodebookView &v, uint32_t *prepA32, int cosine, float *cbc, float *cen,
-                            float *cn32, hipStream_t stream);
+                            float *cn32, hipStream_t stream, uint32_t *prepA32_3 = nullptr);
 
 int launch_prepare_codebook(const CodebookView &v, float *prepA, float *prepCn, float *meta,
                             float *cnsqrt, hipStream_t stream);
@@ -80,6 +82,7 @@ struct AssignArgs {
     uint64_t n = 0;
     uint32_t d = 0;
     int metric = VQHIP_SQUARED_EUCLIDEAN;
+    bool encode = false;  // an encode pass (no training behind it): may take the three-product screen
     const uint32_t *sub_list = nullptr;  // device [n_sub] subspace ids to process
     uint32_t n_sub = 0;
     uint8_t *codes = nullptr;  // [n][m]
@@ -98,6 +101,7 @@ struct AssignArgs {
     uint32_t wl_seg_cap = 0;
     void *part = nullptr;            // grouped X32 screen: [m][G][n] uint4 partial verdicts
     mutable uint32_t n_seg = 0;
+    mutable uint32_t products = 0;   // out (bf16 screen): bf16 products per dimension of the kernel that ran, 6 or 3
     // fused update (training, screen_bf16_fused_update_supported shapes): partial slabs [chunk][n_sub][k][sd] /
     // [chunk][n_sub][k] that the screen fills with the sums / counts of the rows it proves; it reports the chunks it
     // used (acc_chunk_cap = slabs available / n_sub)
