@@ -693,17 +693,12 @@ inline RangeResult read_range(vqhip_range *raw) {
 }
 }  // namespace detail
 
-// Exact k-NN search over rows kept on the device (include/vqhip.h, vqhip_flat_*): rows [n][dim] f32 or f16, uploaded once
-// by the constructor; search / rerank give (row index, distance) pairs [nq][topk], nearest first, NaN last, ties to the
-// lower row.  The arguments are checked before the device is touched.
-class FlatIndex {
+namespace detail {
+// What the resident indexes share over their C handles (H and its destroy / search): the shape, the handle, and a search,
+// whose arguments are the same for every kind of row.  The arguments are checked before the device is touched.
+template <class H, int (*Destroy)(H *), int (*Search)(H *, const float *, std::uint32_t, std::uint32_t, std::uint32_t *, float *)>
+class ResidentIndex {
    public:
-    FlatIndex(const float *rows, std::size_t n, std::size_t dim, Distance distance = Distance()) {
-        init(rows, 0, n, dim, distance);
-    }
-    FlatIndex(const f16 *rows, std::size_t n, std::size_t dim, Distance distance = Distance()) {
-        init(rows, 1, n, dim, distance);
-    }
     std::size_t size() const { return n_; }
     std::size_t dim() const { return dim_; }
     const char *distance_metric() const { return distance_.name(); }
@@ -712,32 +707,66 @@ class FlatIndex {
         std::vector<std::uint32_t> idx;  // [nq][topk]
         std::vector<float> dist;         // [nq][topk]
     };
-    // queries [nq][dim]
+    // queries [nq][dim] f32
     Result search(const float *queries, std::size_t nq, std::size_t topk) const {
         if (topk == 0 || topk > 1024 || topk > n_)
             throw VqError::InvalidParameter("topk", "must be between 1 and min(n, 1024)");
         if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
         Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
-        if (nq) detail::check(vqhip_flat_search(flat_.get(), queries, (std::uint32_t)nq, (std::uint32_t)topk, r.idx.data(), r.dist.data()));
+        if (nq) check(Search(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)topk, r.idx.data(), r.dist.data()));
         return r;
     }
     Result search(const std::vector<float> &queries, std::size_t topk) const {
         if (queries.size() % dim_) throw VqError::DimensionMismatch(dim_, queries.size() % dim_);
         return search(queries.data(), queries.size() / dim_, topk);
     }
+
+   protected:
+    ResidentIndex() = default;
+    // the shape checks of an index of any dimension (BinaryIndex has a bound on it, and its own)
+    static void check_shape(std::size_t n, std::size_t dim) {
+        if (n == 0) throw VqError::EmptyInput();
+        if (dim == 0) throw VqError::InvalidParameter("dim", "must be at least 1");
+        if (n >= (std::size_t(1) << 32) || dim > 0xFFFFFFFFu) throw VqError::InvalidParameter("rows", "at most 2^32 - 1 rows of 2^32 - 1 dimensions");
+    }
+    // a created handle and its shape
+    void adopt(H *h, std::size_t n, std::size_t dim, Distance distance) {
+        ix_.reset(h);
+        n_ = n;
+        dim_ = dim;
+        distance_ = distance;
+    }
+    struct Del {
+        void operator()(H *p) const { (void)Destroy(p); }
+    };
+    std::unique_ptr<H, Del> ix_;
+    std::size_t n_ = 0, dim_ = 0;
+    Distance distance_;
+};
+
+// The two indexes of exact distances (FlatIndex, ScalarIndex) also answer range queries and rerank a caller's candidates.
+template <class H, int (*Destroy)(H *), int (*Search)(H *, const float *, std::uint32_t, std::uint32_t, std::uint32_t *, float *),
+          int (*Range)(H *, const float *, std::uint32_t, const float *, std::uint64_t, vqhip_range **),
+          int (*Rerank)(H *, const float *, std::uint32_t, const std::uint32_t *, std::uint32_t, std::uint32_t, std::uint32_t *, float *)>
+class ExactResidentIndex : public ResidentIndex<H, Destroy, Search> {
+    using Base = ResidentIndex<H, Destroy, Search>;
+
+   public:
+    using Result = typename Base::Result;
     // every row within radii[q] of query q (radii [nq], none NaN), at most max_results hits in all (more: FfiError)
     RangeResult range_search(const float *queries, std::size_t nq, const float *radii, std::uint64_t max_results = std::uint64_t(1) << 28) const {
-        detail::check_range_args(radii, nq, max_results);
+        check_range_args(radii, nq, max_results);
         if (nq == 0) return RangeResult{std::vector<std::uint64_t>(1, 0), {}, {}};
         vqhip_range *r = nullptr;
-        detail::check(vqhip_flat_range_search(flat_.get(), queries, (std::uint32_t)nq, radii, max_results, &r));
-        return detail::read_range(r);
+        check(Range(this->ix_.get(), queries, (std::uint32_t)nq, radii, max_results, &r));
+        return read_range(r);
     }
     RangeResult range_search(const std::vector<float> &queries, const std::vector<float> &radii,
                              std::uint64_t max_results = std::uint64_t(1) << 28) const {
-        if (queries.size() % dim_) throw VqError::DimensionMismatch(dim_, queries.size() % dim_);
-        if (radii.size() != queries.size() / dim_) throw VqError::DimensionMismatch(queries.size() / dim_, radii.size());
-        return range_search(queries.data(), queries.size() / dim_, radii.data(), max_results);
+        const std::size_t dim = this->dim_;
+        if (queries.size() % dim) throw VqError::DimensionMismatch(dim, queries.size() % dim);
+        if (radii.size() != queries.size() / dim) throw VqError::DimensionMismatch(queries.size() / dim, radii.size());
+        return range_search(queries.data(), queries.size() / dim, radii.data(), max_results);
     }
     // per query the topk nearest of its c candidate row ids cand [nq][c] (distinct within a query, each < n)
     Result rerank(const float *queries, std::size_t nq, const std::uint32_t *cand, std::size_t c, std::size_t topk) const {
@@ -745,39 +774,43 @@ class FlatIndex {
         if (topk == 0 || topk > c) throw VqError::InvalidParameter("topk", "must be between 1 and the number of candidates");
         if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
         for (std::size_t e = 0; e < nq * c; ++e)
-            if (cand[e] >= n_) throw VqError::InvalidParameter("candidates", "a row id is outside [0, n)");
+            if (cand[e] >= this->n_) throw VqError::InvalidParameter("candidates", "a row id is outside [0, n)");
         Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
         if (nq)
-            detail::check(vqhip_flat_rerank(flat_.get(), queries, (std::uint32_t)nq, cand, (std::uint32_t)c, (std::uint32_t)topk,
-                                            r.idx.data(), r.dist.data()));
+            check(Rerank(this->ix_.get(), queries, (std::uint32_t)nq, cand, (std::uint32_t)c, (std::uint32_t)topk, r.idx.data(),
+                         r.dist.data()));
         return r;
+    }
+};
+}  // namespace detail
+
+// Exact k-NN search over rows kept on the device (include/vqhip.h, vqhip_flat_*): rows [n][dim] f32 or f16, uploaded once
+// by the constructor; search / rerank give (row index, distance) pairs [nq][topk], nearest first, NaN last, ties to the
+// lower row.  The arguments are checked before the device is touched.
+class FlatIndex : public detail::ExactResidentIndex<vqhip_flat, vqhip_flat_destroy, vqhip_flat_search, vqhip_flat_range_search, vqhip_flat_rerank> {
+   public:
+    FlatIndex(const float *rows, std::size_t n, std::size_t dim, Distance distance = Distance()) {
+        init(rows, 0, n, dim, distance);
+    }
+    FlatIndex(const f16 *rows, std::size_t n, std::size_t dim, Distance distance = Distance()) {
+        init(rows, 1, n, dim, distance);
     }
 
    private:
-    struct Del {
-        void operator()(vqhip_flat *p) const { (void)vqhip_flat_destroy(p); }
-    };
     void init(const void *rows, int dtype, std::size_t n, std::size_t dim, Distance distance) {
-        if (n == 0) throw VqError::EmptyInput();
-        if (dim == 0) throw VqError::InvalidParameter("dim", "must be at least 1");
-        if (n >= (std::size_t(1) << 32) || dim > 0xFFFFFFFFu) throw VqError::InvalidParameter("rows", "at most 2^32 - 1 rows of 2^32 - 1 dimensions");
+        check_shape(n, dim);
         vqhip_flat *f = nullptr;
         detail::check(vqhip_flat_create(rows, n, (std::uint32_t)dim, dtype, (int)distance.kind(), &f));
-        flat_.reset(f);
-        n_ = n;
-        dim_ = dim;
-        distance_ = distance;
+        adopt(f, n, dim, distance);
     }
-    std::unique_ptr<vqhip_flat, Del> flat_;
-    std::size_t n_ = 0, dim_ = 0;
-    Distance distance_;
 };
 
 // Hamming index over packed BQ codes (include/vqhip.h, vqhip_binary_*): rows binarised by a BinaryQuantizer (f32 rows,
 // u8 codes or packed words [n][ceil(dim / 32)]), searched under squared Euclidean, Euclidean or Manhattan on the
-// dequantized vectors; (row id, distance) pairs [nq][topk], nearest first, ties to the lower row.  Cosine and every
-// other bad argument are refused before the device is touched.
-class BinaryIndex {
+// dequantized vectors; (row id, distance) pairs [nq][topk], nearest first, ties to the lower row.  The queries are
+// binarised by the index's quantizer on the device.  Cosine and every other bad argument are refused before the device
+// is touched.
+class BinaryIndex : public detail::ResidentIndex<vqhip_binary, vqhip_binary_destroy, vqhip_binary_search> {
    public:
     enum class Source { Rows = VQHIP_BINARY_F32, Codes = VQHIP_BINARY_U8, Packed = VQHIP_BINARY_PACKED };
     BinaryIndex(const float *rows, std::size_t n, std::size_t dim, BinaryQuantizer quantizer = BinaryQuantizer(0.0f, 0, 1),
@@ -795,29 +828,8 @@ class BinaryIndex {
         : quantizer_(quantizer) {
         init(words, Source::Packed, n, dim, distance);
     }
-    std::size_t size() const { return n_; }
-    std::size_t dim() const { return dim_; }
     std::size_t words_per_row() const { return (dim_ + 31) / 32; }
     const BinaryQuantizer &quantizer() const { return quantizer_; }
-    const char *distance_metric() const { return distance_.name(); }
-
-    struct Result {
-        std::vector<std::uint32_t> idx;  // [nq][topk]
-        std::vector<float> dist;         // [nq][topk]
-    };
-    // queries [nq][dim] f32, binarised by the index's quantizer on the device
-    Result search(const float *queries, std::size_t nq, std::size_t topk) const {
-        if (topk == 0 || topk > 1024 || topk > n_)
-            throw VqError::InvalidParameter("topk", "must be between 1 and min(n, 1024)");
-        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
-        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
-        if (nq) detail::check(vqhip_binary_search(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)topk, r.idx.data(), r.dist.data()));
-        return r;
-    }
-    Result search(const std::vector<float> &queries, std::size_t topk) const {
-        if (queries.size() % dim_) throw VqError::DimensionMismatch(dim_, queries.size() % dim_);
-        return search(queries.data(), queries.size() / dim_, topk);
-    }
     // the packed rows [n][words_per_row()]
     std::vector<std::uint32_t> packed() const {
         std::vector<std::uint32_t> out(n_ * words_per_row());
@@ -826,9 +838,6 @@ class BinaryIndex {
     }
 
    private:
-    struct Del {
-        void operator()(vqhip_binary *p) const { (void)vqhip_binary_destroy(p); }
-    };
     void init(const void *src, Source kind, std::size_t n, std::size_t dim, Distance distance) {
         if (n == 0) throw VqError::EmptyInput();
         if (dim == 0 || dim > VQHIP_BINARY_MAX_DIM) throw VqError::InvalidParameter("dim", "must be between 1 and 8192");
@@ -846,22 +855,17 @@ class BinaryIndex {
         vqhip_binary *b = nullptr;
         detail::check(vqhip_binary_create(src, (int)kind, n, (std::uint32_t)dim, quantizer_.threshold(), quantizer_.low(),
                                           quantizer_.high(), (int)distance.kind(), &b));
-        ix_.reset(b);
-        n_ = n;
-        dim_ = dim;
-        distance_ = distance;
+        adopt(b, n, dim, distance);
     }
     BinaryQuantizer quantizer_;
-    std::unique_ptr<vqhip_binary, Del> ix_;
-    std::size_t n_ = 0, dim_ = 0;
-    Distance distance_;
 };
 
 // Exact index over SQ codes kept on the device, one byte per dimension (include/vqhip.h, vqhip_sqindex_*): built from f32
-// rows (encoded on the device; only the codes stay) or from u8 codes, searched with f32 queries under any metric.  Every
-// result equals FlatIndex over quantizer.dequantize(codes): (row index, distance) pairs [nq][topk], nearest first, NaN
-// last, ties to the lower row.  The arguments are checked before the device is touched.
-class ScalarIndex {
+// rows (encoded on the device; only the codes stay) or from u8 codes, searched with f32 queries (never quantized) under
+// any metric.  Every result equals FlatIndex over quantizer.dequantize(codes): (row index, distance) pairs [nq][topk],
+// nearest first, NaN last, ties to the lower row.  The arguments are checked before the device is touched.
+class ScalarIndex
+    : public detail::ExactResidentIndex<vqhip_sqindex, vqhip_sqindex_destroy, vqhip_sqindex_search, vqhip_sqindex_range_search, vqhip_sqindex_rerank> {
    public:
     ScalarIndex(const float *rows, std::size_t n, std::size_t dim, ScalarQuantizer quantizer, Distance distance = Distance())
         : quantizer_(quantizer) {
@@ -871,55 +875,7 @@ class ScalarIndex {
         : quantizer_(quantizer) {
         init(codes, false, n, dim, distance);
     }
-    std::size_t size() const { return n_; }
-    std::size_t dim() const { return dim_; }
     const ScalarQuantizer &quantizer() const { return quantizer_; }
-    const char *distance_metric() const { return distance_.name(); }
-
-    struct Result {
-        std::vector<std::uint32_t> idx;  // [nq][topk]
-        std::vector<float> dist;         // [nq][topk]
-    };
-    // queries [nq][dim] f32, never quantized
-    Result search(const float *queries, std::size_t nq, std::size_t topk) const {
-        if (topk == 0 || topk > 1024 || topk > n_)
-            throw VqError::InvalidParameter("topk", "must be between 1 and min(n, 1024)");
-        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
-        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
-        if (nq) detail::check(vqhip_sqindex_search(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)topk, r.idx.data(), r.dist.data()));
-        return r;
-    }
-    Result search(const std::vector<float> &queries, std::size_t topk) const {
-        if (queries.size() % dim_) throw VqError::DimensionMismatch(dim_, queries.size() % dim_);
-        return search(queries.data(), queries.size() / dim_, topk);
-    }
-    // every row within radii[q] of query q (radii [nq], none NaN), at most max_results hits in all (more: FfiError)
-    RangeResult range_search(const float *queries, std::size_t nq, const float *radii, std::uint64_t max_results = std::uint64_t(1) << 28) const {
-        detail::check_range_args(radii, nq, max_results);
-        if (nq == 0) return RangeResult{std::vector<std::uint64_t>(1, 0), {}, {}};
-        vqhip_range *r = nullptr;
-        detail::check(vqhip_sqindex_range_search(ix_.get(), queries, (std::uint32_t)nq, radii, max_results, &r));
-        return detail::read_range(r);
-    }
-    RangeResult range_search(const std::vector<float> &queries, const std::vector<float> &radii,
-                             std::uint64_t max_results = std::uint64_t(1) << 28) const {
-        if (queries.size() % dim_) throw VqError::DimensionMismatch(dim_, queries.size() % dim_);
-        if (radii.size() != queries.size() / dim_) throw VqError::DimensionMismatch(queries.size() / dim_, radii.size());
-        return range_search(queries.data(), queries.size() / dim_, radii.data(), max_results);
-    }
-    // per query the topk nearest of its c candidate row ids cand [nq][c] (distinct within a query, each < n)
-    Result rerank(const float *queries, std::size_t nq, const std::uint32_t *cand, std::size_t c, std::size_t topk) const {
-        if (c == 0 || c > 4096) throw VqError::InvalidParameter("candidates", "between 1 and 4096 per query");
-        if (topk == 0 || topk > c) throw VqError::InvalidParameter("topk", "must be between 1 and the number of candidates");
-        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
-        for (std::size_t e = 0; e < nq * c; ++e)
-            if (cand[e] >= n_) throw VqError::InvalidParameter("candidates", "a row id is outside [0, n)");
-        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
-        if (nq)
-            detail::check(vqhip_sqindex_rerank(ix_.get(), queries, (std::uint32_t)nq, cand, (std::uint32_t)c, (std::uint32_t)topk,
-                                               r.idx.data(), r.dist.data()));
-        return r;
-    }
     // the codes [n][dim]
     std::vector<std::uint8_t> codes() const {
         std::vector<std::uint8_t> out(n_ * dim_);
@@ -928,13 +884,8 @@ class ScalarIndex {
     }
 
    private:
-    struct Del {
-        void operator()(vqhip_sqindex *p) const { (void)vqhip_sqindex_destroy(p); }
-    };
     void init(const void *src, bool rows, std::size_t n, std::size_t dim, Distance distance) {
-        if (n == 0) throw VqError::EmptyInput();
-        if (dim == 0) throw VqError::InvalidParameter("dim", "must be at least 1");
-        if (n >= (std::size_t(1) << 32) || dim > 0xFFFFFFFFu) throw VqError::InvalidParameter("rows", "at most 2^32 - 1 rows of 2^32 - 1 dimensions");
+        check_shape(n, dim);
         vqhip_sqindex *x = nullptr;
         const std::uint32_t levels = (std::uint32_t)quantizer_.levels();
         if (rows)
@@ -943,15 +894,9 @@ class ScalarIndex {
         else
             detail::check(vqhip_sqindex_create(quantizer_.min(), quantizer_.max(), levels, static_cast<const std::uint8_t *>(src), n,
                                                (std::uint32_t)dim, (int)distance.kind(), &x));
-        ix_.reset(x);
-        n_ = n;
-        dim_ = dim;
-        distance_ = distance;
+        adopt(x, n, dim, distance);
     }
     ScalarQuantizer quantizer_;
-    std::unique_ptr<vqhip_sqindex, Del> ix_;
-    std::size_t n_ = 0, dim_ = 0;
-    Distance distance_;
 };
 
 namespace detail {

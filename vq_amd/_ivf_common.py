@@ -9,9 +9,9 @@ import operator
 import numpy as np
 
 from . import _lib
+from ._resident_common import DEFAULT_MAX_RESULTS, _max_results, _radii
 from .distance import Distance
 from .errors import DimensionMismatch, InvalidParameter
-from .flat import DEFAULT_MAX_RESULTS, _max_results, _radii
 
 MAX_NLIST = 65536
 MAX_PROBE = 1024

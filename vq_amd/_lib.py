@@ -845,9 +845,51 @@ def _range_call(fn, raw, queries, nq: int, radii: np.ndarray, max_results: int, 
     return RangeResult(h)
 
 
-class Flat(Handle):
+class _ResidentHandle(Handle):
+    """What the three resident-index handles share: the calls that differ only in the symbol prefix.  A subclass sets
+    `_prefix` (and `_destroy`)."""
+
+    _prefix = ""
+
+    def _fn(self, name: str):
+        return getattr(load(), f"{self._prefix}_{name}")
+
+    def search(self, q: np.ndarray, topk: int):
+        nq = q.shape[0]
+        idx = np.empty((nq, topk), np.uint32)
+        dist = np.empty((nq, topk), np.float32)
+        if nq:
+            check(self._fn("search")(self.raw, ptr(q, _f32p), nq, int(topk), ptr(idx, _u32p), ptr(dist, _f32p)))
+        return idx, dist
+
+    def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int):
+        check(self._fn("search_device")(self.raw, C.c_void_p(dev_queries), int(nq), int(topk), C.c_void_p(dev_idx),
+                                        C.c_void_p(dev_dist)))
+
+
+class _ResidentExactHandle(_ResidentHandle):
+    """the two resident handles of exact distances: they also rerank candidates and answer range queries"""
+
+    def range_search(self, q: np.ndarray, radii: np.ndarray, max_results: int) -> RangeResult:
+        return _range_call(self._fn("range_search"), self.raw, ptr(q, _f32p), q.shape[0], radii, max_results)
+
+    def range_search_device(self, dev_queries: int, nq: int, radii: np.ndarray, max_results: int) -> RangeResult:
+        return _range_call(self._fn("range_search_device"), self.raw, C.c_void_p(dev_queries), nq, radii, max_results)
+
+    def rerank(self, q: np.ndarray, cand: np.ndarray, topk: int):
+        nq, c = cand.shape
+        idx = np.empty((nq, topk), np.uint32)
+        dist = np.empty((nq, topk), np.float32)
+        if nq:
+            check(self._fn("rerank")(self.raw, ptr(q, _f32p), nq, ptr(cand, _u32p), int(c), int(topk), ptr(idx, _u32p),
+                                     ptr(dist, _f32p)))
+        return idx, dist
+
+
+class Flat(_ResidentExactHandle):
     """vqhip_flat: rows resident on the device, exact k-NN search and exact rerank (k_knn.hip)"""
 
+    _prefix = "vqhip_flat"
     _destroy = "vqhip_flat_destroy"
 
     def __init__(self, rows: np.ndarray, metric: int, dev_rows: int | None = None, shape=None):
@@ -863,40 +905,14 @@ class Flat(Handle):
         super().__init__(h)
         self.n, self.d, self.dtype, self.metric = int(n), int(d), dtype, int(metric)
 
-    def search(self, q: np.ndarray, topk: int):
-        nq = q.shape[0]
-        idx = np.empty((nq, topk), np.uint32)
-        dist = np.empty((nq, topk), np.float32)
-        if nq:
-            check(load().vqhip_flat_search(self.raw, ptr(q, _f32p), nq, int(topk), ptr(idx, _u32p), ptr(dist, _f32p)))
-        return idx, dist
-
-    def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int):
-        check(load().vqhip_flat_search_device(self.raw, C.c_void_p(dev_queries), int(nq), int(topk), C.c_void_p(dev_idx),
-                                              C.c_void_p(dev_dist)))
-
-    def range_search(self, q: np.ndarray, radii: np.ndarray, max_results: int) -> RangeResult:
-        return _range_call(load().vqhip_flat_range_search, self.raw, ptr(q, _f32p), q.shape[0], radii, max_results)
-
-    def range_search_device(self, dev_queries: int, nq: int, radii: np.ndarray, max_results: int) -> RangeResult:
-        return _range_call(load().vqhip_flat_range_search_device, self.raw, C.c_void_p(dev_queries), nq, radii, max_results)
-
-    def rerank(self, q: np.ndarray, cand: np.ndarray, topk: int):
-        nq, c = cand.shape
-        idx = np.empty((nq, topk), np.uint32)
-        dist = np.empty((nq, topk), np.float32)
-        if nq:
-            check(load().vqhip_flat_rerank(self.raw, ptr(q, _f32p), nq, ptr(cand, _u32p), int(c), int(topk), ptr(idx, _u32p),
-                                           ptr(dist, _f32p)))
-        return idx, dist
-
 
 BINARY_F32, BINARY_U8, BINARY_PACKED = 0, 1, 2
 
 
-class Binary(Handle):
+class Binary(_ResidentHandle):
     """vqhip_binary: BQ bits packed 32 to a word on the device, exact Hamming top-k search (k_binary.hip)"""
 
+    _prefix = "vqhip_binary"
     _destroy = "vqhip_binary_destroy"
 
     def __init__(self, src, kind: int, n: int, d: int, threshold: float, low: int, high: int, metric: int,
@@ -918,23 +934,12 @@ class Binary(Handle):
         check(load().vqhip_binary_packed(self.raw, ptr(out, _u32p)))
         return out
 
-    def search(self, q: np.ndarray, topk: int):
-        nq = q.shape[0]
-        idx = np.empty((nq, topk), np.uint32)
-        dist = np.empty((nq, topk), np.float32)
-        if nq:
-            check(load().vqhip_binary_search(self.raw, ptr(q, _f32p), nq, int(topk), ptr(idx, _u32p), ptr(dist, _f32p)))
-        return idx, dist
 
-    def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int):
-        check(load().vqhip_binary_search_device(self.raw, C.c_void_p(dev_queries), int(nq), int(topk), C.c_void_p(dev_idx),
-                                                C.c_void_p(dev_dist)))
-
-
-class SQIndex(Handle):
+class SQIndex(_ResidentExactHandle):
     """vqhip_sqindex: SQ codes resident on the device, one byte per dimension, exact top-k search and exact rerank against
     f32 queries (k_sqindex.hip)"""
 
+    _prefix = "vqhip_sqindex"
     _destroy = "vqhip_sqindex_destroy"
 
     def __init__(self, src, rows: bool, n: int, d: int, mn: float, mx: float, levels: int, metric: int,
@@ -952,33 +957,6 @@ class SQIndex(Handle):
         out = np.empty((self.n, self.d), np.uint8)
         check(load().vqhip_sqindex_codes(self.raw, ptr(out, _u8p)))
         return out
-
-    def search(self, q: np.ndarray, topk: int):
-        nq = q.shape[0]
-        idx = np.empty((nq, topk), np.uint32)
-        dist = np.empty((nq, topk), np.float32)
-        if nq:
-            check(load().vqhip_sqindex_search(self.raw, ptr(q, _f32p), nq, int(topk), ptr(idx, _u32p), ptr(dist, _f32p)))
-        return idx, dist
-
-    def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int):
-        check(load().vqhip_sqindex_search_device(self.raw, C.c_void_p(dev_queries), int(nq), int(topk), C.c_void_p(dev_idx),
-                                                 C.c_void_p(dev_dist)))
-
-    def range_search(self, q: np.ndarray, radii: np.ndarray, max_results: int) -> RangeResult:
-        return _range_call(load().vqhip_sqindex_range_search, self.raw, ptr(q, _f32p), q.shape[0], radii, max_results)
-
-    def range_search_device(self, dev_queries: int, nq: int, radii: np.ndarray, max_results: int) -> RangeResult:
-        return _range_call(load().vqhip_sqindex_range_search_device, self.raw, C.c_void_p(dev_queries), nq, radii, max_results)
-
-    def rerank(self, q: np.ndarray, cand: np.ndarray, topk: int):
-        nq, c = cand.shape
-        idx = np.empty((nq, topk), np.uint32)
-        dist = np.empty((nq, topk), np.float32)
-        if nq:
-            check(load().vqhip_sqindex_rerank(self.raw, ptr(q, _f32p), nq, ptr(cand, _u32p), int(c), int(topk), ptr(idx, _u32p),
-                                              ptr(dist, _f32p)))
-        return idx, dist
 
 
 class _IVFHandle(Handle):

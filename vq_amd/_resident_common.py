@@ -1,0 +1,195 @@
+"""What ``FlatIndex``, ``ScalarIndex`` and ``BinaryIndex`` share: the rows of a caller's array that go to the device on the
+first search, the checks of queries and ``topk``, and search over the device handle.  A subclass keeps its constructors,
+the checks of its own source array, ``_make_handle``, ``__repr__`` and its file layout.  ``ExactResidentIndex`` adds the
+range search and the rerank of the two indexes whose distances are exact (not ``BinaryIndex``)."""
+from __future__ import annotations
+
+import operator
+
+import numpy as np
+
+from . import _lib
+from .distance import Distance
+from .errors import DimensionMismatch, EmptyInput, InvalidParameter
+
+MAX_TOPK = 1024
+MAX_CANDIDATES = 4096
+DEFAULT_MAX_RESULTS = 1 << 28  # hits a range search returns at most by default: 2 GB of idx + dist
+
+
+def _count(v, name: str) -> int:
+    try:
+        return operator.index(v)
+    except TypeError:
+        raise InvalidParameter(name, f"must be an integer, got {v!r}") from None
+
+
+def _nq(nq) -> int:
+    """the query count of a device-form call"""
+    n_q = _count(nq, "nq")
+    if n_q < 0 or n_q >= 1 << 32:
+        raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
+    return n_q
+
+
+def _radii(radius, nq: int) -> np.ndarray:
+    """the per-query radii float32 (nq,) of a range search from a scalar or nq values; NaN is refused"""
+    try:
+        r = np.asarray(radius, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise InvalidParameter("radius", f"must be a number or an array of {nq} numbers, got {radius!r}") from None
+    if r.ndim == 0:
+        r = np.full(nq, r, np.float32)
+    if r.ndim != 1:
+        raise InvalidParameter("radius", f"must be a scalar or a 1D array, got {r.ndim} dimensions")
+    if r.shape[0] != nq:
+        raise DimensionMismatch(nq, r.shape[0])
+    if bool(np.isnan(r).any()):
+        raise InvalidParameter("radius", f"is NaN for query {int(np.flatnonzero(np.isnan(r))[0])}")
+    return np.ascontiguousarray(r)
+
+
+def _max_results(max_results) -> int:
+    m = _count(max_results, "max_results")
+    if not 1 <= m < 1 << 64:
+        raise InvalidParameter("max_results", f"must be in [1, 2^64), got {m}")
+    return m
+
+
+def _check_distance(distance, default: Distance) -> Distance:
+    if distance is None:
+        distance = default
+    if not isinstance(distance, Distance):
+        raise InvalidParameter("distance", f"expected a Distance, got {type(distance).__name__}")
+    return distance
+
+
+class ResidentIndex:
+    """n rows of `dim` under `distance`; `_src` is the caller's array until the first search, `_ix` the device handle
+    from then on (None before)"""
+
+    def _set_source(self, a: np.ndarray, what: str, distance: Distance, dim: int | None = None) -> None:
+        """the shared end of every constructor: the shape checks of the source array `a` (`what` names it in errors;
+        `dim`: the dimension, where it is not the array's second extent) and the fields of this class"""
+        if a.ndim != 2:
+            raise ValueError("expected a 2D array (n, dim)")
+        if a.shape[0] == 0:
+            raise EmptyInput()
+        d = a.shape[1] if dim is None else dim
+        self._distance = distance
+        self._check_dim(d, what)
+        if a.shape[0] >= 1 << 32:
+            raise InvalidParameter(what, f"at most 2^32 - 1 rows, got {a.shape[0]}")
+        self._src = np.ascontiguousarray(a)
+        self._n, self._dim = int(a.shape[0]), int(d)
+        self._ix = None
+
+    def _check_dim(self, d: int, what: str) -> None:
+        if d == 0:
+            raise InvalidParameter(what, "dimension must be at least 1")
+
+    def __len__(self) -> int:
+        return self._n
+
+    @property
+    def dim(self) -> int:
+        return self._dim
+
+    @property
+    def distance(self) -> Distance:
+        return self._distance
+
+    def _make_handle(self):
+        """the _lib handle over `_src` (a subclass's)"""
+        raise NotImplementedError
+
+    def _index(self):
+        if self._ix is None:
+            self._ix = self._make_handle()
+            self._src = None  # on the device now
+        return self._ix
+
+    def _queries(self, queries) -> np.ndarray:
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2:
+            raise ValueError("expected a 2D array (nq, dim)")
+        if q.shape[1] != self._dim:
+            raise DimensionMismatch(self._dim, q.shape[1])
+        if q.shape[0] >= 1 << 32:
+            raise InvalidParameter("queries", f"at most 2^32 - 1 queries, got {q.shape[0]}")
+        return q
+
+    def _topk(self, topk, limit: int | None = None, what: str = "min(n, 1024)") -> int:
+        k = _count(topk, "topk")
+        if not 1 <= k <= (min(self._n, MAX_TOPK) if limit is None else limit):
+            raise InvalidParameter("topk", f"must be between 1 and {what}, got {k}")
+        return k
+
+    def search(self, queries, topk: int = 10):
+        """(nq, d) float32 queries -> (indices uint32 (nq, topk), distances float32 (nq, topk)), nearest first"""
+        return self._search(self._queries(queries), self._topk(topk))
+
+    def _search(self, q: np.ndarray, k: int):
+        if q.shape[0] == 0:
+            return np.empty((0, k), np.uint32), np.empty((0, k), np.float32)
+        return self._index().search(q, k)
+
+    def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int) -> None:
+        """device pointers: queries [nq][d] f32, results [nq][topk] uint32 / f32 (4-byte aligned); asynchronous on the
+        current stream"""
+        k = self._topk(topk)
+        n_q = _nq(nq)
+        self._index().search_device(int(dev_queries), n_q, k, int(dev_idx), int(dev_dist))
+
+
+class ExactResidentIndex(ResidentIndex):
+    """a ResidentIndex whose distances are exact (FlatIndex, ScalarIndex): range search and the rerank of candidates"""
+
+    def range_search(self, queries, radius, max_results: int = DEFAULT_MAX_RESULTS):
+        """every row within `radius` of each query: row i is a hit of query q iff D(q, i) <= radius[q] as a float32
+        comparison (NaN distances never hit).  `radius` is a scalar or nq values.  Returns (lims uint64 (nq + 1,),
+        idx uint32 (total,), dist float32 (total,)): the hits of query q are idx[lims[q]:lims[q + 1]], in ascending
+        row id.  More than `max_results` hits in all: FfiError (ERR_UNSUPPORTED)."""
+        q = self._queries(queries)
+        r = _radii(radius, q.shape[0])
+        m = _max_results(max_results)
+        if q.shape[0] == 0:
+            return np.zeros(1, np.uint64), np.empty(0, np.uint32), np.empty(0, np.float32)
+        return self._index().range_search(q, r, m).read()
+
+    def range_search_device(self, dev_queries: int, nq: int, radius, max_results: int = DEFAULT_MAX_RESULTS) -> "_lib.RangeResult":
+        """`range_search` with the queries [nq][d] f32 at a device pointer (4-byte aligned) and the result left on the
+        device: a RangeResult (.total, .lims, .device_pointers(), .read()).  Returns when the result is complete."""
+        n_q = _nq(nq)
+        r = _radii(radius, n_q)
+        m = _max_results(max_results)
+        return self._index().range_search_device(int(dev_queries), n_q, r, m)
+
+    def rerank(self, queries, candidates, topk: int = 10):
+        """per query, the `topk` nearest of its candidate row ids (nq, c), 1 <= c <= 4096, distinct within a query;
+        returns (indices uint32 (nq, topk), distances float32 (nq, topk)) in the order of `search`"""
+        q = self._queries(queries)
+        c = np.asarray(candidates)
+        if c.ndim == 1 and q.shape[0] == 1:
+            c = c[None, :]
+        if c.ndim != 2:
+            raise ValueError("expected candidates as a 2D array (nq, c)")
+        if c.shape[0] != q.shape[0]:
+            raise DimensionMismatch(q.shape[0], c.shape[0])
+        if c.dtype.kind not in "iu":
+            raise InvalidParameter("candidates", f"row ids must be integers, got {c.dtype}")
+        if not 1 <= c.shape[1] <= MAX_CANDIDATES:
+            raise InvalidParameter("candidates", f"between 1 and {MAX_CANDIDATES} per query, got {c.shape[1]}")
+        k = self._topk(topk, c.shape[1], "the number of candidates")
+        if q.shape[0] == 0:
+            return np.empty((0, k), np.uint32), np.empty((0, k), np.float32)
+        lo, hi = int(c.min()), int(c.max())
+        if lo < 0 or hi >= self._n:
+            bad = lo if lo < 0 else hi
+            raise InvalidParameter("candidates", f"row id {bad} is outside [0, {self._n})")
+        s = np.sort(c, axis=1)
+        if c.shape[1] > 1 and bool((s[:, 1:] == s[:, :-1]).any()):
+            raise InvalidParameter("candidates", "row ids must be distinct within a query")
+        return self._index().rerank(q, np.ascontiguousarray(c, dtype=np.uint32), k)

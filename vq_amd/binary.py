@@ -17,10 +17,11 @@ import struct
 import numpy as np
 
 from . import _lib
+from ._resident_common import ResidentIndex, _count
 from .bq import BinaryQuantizer
 from .distance import Distance
-from .errors import DimensionMismatch, EmptyInput, InvalidData, InvalidParameter
-from .flat import MAX_TOPK, _count, adc_then_rerank
+from .errors import DimensionMismatch, InvalidData, InvalidParameter
+from .flat import adc_then_rerank
 
 MAGIC = b"VQBINIX1"
 _HEADER = struct.Struct("<8sIIfIIQ")  # magic, metric, dim, threshold, low, high, n
@@ -61,7 +62,7 @@ def _check_params(dim: int, quantizer, distance) -> None:
         raise InvalidParameter("dim", f"must be between 1 and {MAX_DIM}, got {dim}")
 
 
-class BinaryIndex:
+class BinaryIndex(ResidentIndex):
     """Exact Hamming top-k over rows binarised by `quantizer` (default ``BinaryQuantizer(0.0)``) under `distance`
     (default Manhattan: with the default quantizer, D is the Hamming count)."""
 
@@ -102,67 +103,23 @@ class BinaryIndex:
         return self
 
     def _setup(self, a: np.ndarray, kind: int, quantizer, distance, dim: int | None = None) -> None:
-        if quantizer is None:
-            quantizer = BinaryQuantizer(0.0)
-        if distance is None:
-            distance = Distance.manhattan()
-        if a.ndim != 2:
-            raise ValueError("expected a 2D array (n, dim)")
-        if a.shape[0] == 0:
-            raise EmptyInput()
-        d = a.shape[1] if dim is None else dim
-        _check_params(d, quantizer, distance)
-        if a.shape[0] >= 1 << 32:
-            raise InvalidParameter("rows", f"at most 2^32 - 1 rows, got {a.shape[0]}")
-        self._src = np.ascontiguousarray(a)
+        self._quantizer = BinaryQuantizer(0.0) if quantizer is None else quantizer
+        self._set_source(a, "rows", Distance.manhattan() if distance is None else distance, dim)
         self._kind = kind
-        self._n, self._dim = int(a.shape[0]), int(d)
-        self._quantizer, self._distance = quantizer, distance
-        self._ix = None
 
-    def __len__(self) -> int:
-        return self._n
-
-    @property
-    def dim(self) -> int:
-        return self._dim
+    def _check_dim(self, d: int, what: str) -> None:
+        _check_params(d, self._quantizer, self._distance)
 
     @property
     def quantizer(self) -> BinaryQuantizer:
         return self._quantizer
 
-    @property
-    def distance(self) -> Distance:
-        return self._distance
-
     def __repr__(self) -> str:
         return f"BinaryIndex(n={self._n}, dim={self._dim}, quantizer={self._quantizer!r}, distance={self._distance!r})"
 
-    def _index(self) -> "_lib.Binary":
-        if self._ix is None:
-            q = self._quantizer
-            self._ix = _lib.Binary(self._src, self._kind, self._n, self._dim, q.threshold, q.low, q.high,
-                                   self._distance.metric)
-            self._src = None  # on the device now
-        return self._ix
-
-    def _queries(self, queries) -> np.ndarray:
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.ndim != 2:
-            raise ValueError("expected a 2D array (nq, dim)")
-        if q.shape[1] != self._dim:
-            raise DimensionMismatch(self._dim, q.shape[1])
-        if q.shape[0] >= 1 << 32:
-            raise InvalidParameter("queries", f"at most 2^32 - 1 queries, got {q.shape[0]}")
-        return q
-
-    def _topk(self, topk) -> int:
-        k = _count(topk, "topk")
-        if not 1 <= k <= min(self._n, MAX_TOPK):
-            raise InvalidParameter("topk", f"must be between 1 and min(n, 1024), got {k}")
-        return k
+    def _make_handle(self) -> "_lib.Binary":
+        q = self._quantizer
+        return _lib.Binary(self._src, self._kind, self._n, self._dim, q.threshold, q.low, q.high, self._distance.metric)
 
     def search(self, queries, topk: int = 10, *, rerank=None, candidates=None):
         """(nq, d) float32 queries -> (indices uint32 (nq, topk), distances float32 (nq, topk)), nearest first.
@@ -174,18 +131,7 @@ class BinaryIndex:
             return adc_then_rerank(self.search, self._n, self._dim, q, k, rerank, candidates)
         if candidates is not None:
             raise InvalidParameter("candidates", "only with rerank")
-        if q.shape[0] == 0:
-            return np.empty((0, k), np.uint32), np.empty((0, k), np.float32)
-        return self._index().search(q, k)
-
-    def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int) -> None:
-        """device pointers: queries [nq][d] f32, results [nq][topk] uint32 / f32 (4-byte aligned); asynchronous on the
-        current stream"""
-        k = self._topk(topk)
-        n_q = _count(nq, "nq")
-        if n_q < 0 or n_q >= 1 << 32:
-            raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
-        self._index().search_device(int(dev_queries), n_q, k, int(dev_idx), int(dev_dist))
+        return self._search(q, k)
 
     def packed(self) -> np.ndarray:
         """the packed rows, uint32 (n, ceil(dim / 32)), from the device"""

@@ -2715,51 +2715,57 @@ int vqhip_distance_batch(int metric, const float *a, const float *b, uint64_t n,
     VQ_API_END
 }
 
-// ------------------------------------------------------------------ exact k-NN (k_knn.hip) ----
+// ------------------------------------------------------------------ resident indexes: the shared host layer ----
+// What vqhip_flat, vqhip_sqindex and vqhip_binary have in common: the rows stay on the device from create on, a search
+// takes [nq][d] f32 queries to [nq][topk] results, and every call locks the handle and runs on the calling thread's stream.
 }  // extern "C"
 
-struct vqhip_flat {
+struct Resident {
     HandleSync sync;
     uint64_t n = 0;
     uint32_t d = 0;
-    int dtype = 0, metric = VQHIP_EUCLIDEAN;
-    DevBuf rows, rnorm;                            // the index: [n][d] f32 or f16 bits, |row| for cosine
-    DevBuf q, qnorm, dist, state, cand, idx, out;  // per-call workspaces
-    DevBuf rr_cand, rr_err;                        // rerank: candidate ids, the out-of-range flag
-    DevBuf radii, range_ws;                        // range search: the radii, the stage's counts and offsets
+    int metric = VQHIP_EUCLIDEAN;
+    DevBuf q, cand, idx, out;  // per-call workspaces
 };
 
-static int flat_check(uint64_t n, uint32_t d, int dtype, int metric) {
-    if (d == 0) return fail(VQHIP_ERR_INVALID_INPUT, "d must be at least 1");
+// The two indexes of exact distances.  T (vqhip_flat, vqhip_sqindex) keeps its rows and the three launcher calls that
+// read them: launch_search, launch_rerank and launch_range.
+template <class T>
+struct ExactResident : Resident {
+    DevBuf rnorm;               // |row| for cosine
+    DevBuf qnorm, dist, state;  // per-call workspaces
+    DevBuf rr_cand, rr_err;     // rerank: candidate ids, the out-of-range flag
+    DevBuf radii, range_ws;     // range search: the radii, the stage's counts and offsets
+
+    // the query norms of a cosine index into qnorm (NULL otherwise)
+    int qnorms(const float *queries_dev, uint32_t nq, const float **qn, hipStream_t s) {
+        *qn = nullptr;
+        if (!vq_is_cos(metric)) return VQHIP_OK;
+        VQ_TRY(qnorm.ensure((size_t)nq * 4));
+        VQ_TRY(launch_knn_norms(queries_dev, 0, nq, d, qnorm.as<float>(), s));
+        *qn = qnorm.as<float>();
+        return VQHIP_OK;
+    }
+
+    // queries_dev [nq][d] f32 on the device -> [nq][topk] results on the device, enqueued on s
+    int search_enqueue(const float *queries_dev, uint32_t nq, uint32_t topk, uint32_t *idx_dev, float *dist_dev, hipStream_t s) {
+        const uint32_t qb = knn_query_batch(n, nq);
+        VQ_TRY(dist.ensure((size_t)qb * n * 4));
+        VQ_TRY(state.ensure(knn_state_bytes(qb)));
+        VQ_TRY(cand.ensure(topk_cand_bytes(qb)));
+        const float *qn = nullptr;
+        VQ_TRY(qnorms(queries_dev, nq, &qn, s));
+        return static_cast<T *>(this)->launch_search(queries_dev, qn, nq, topk, idx_dev, dist_dev, s);
+    }
+};
+
+// every create takes 1 <= n < 2^32 rows and a metric of include/vqhip.h (two checks: each create has its own between them)
+static int check_rows(uint64_t n) {
     if (n == 0 || n >= (1ull << 32)) return fail(VQHIP_ERR_INVALID_INPUT, "n must be in [1, 2^32)");
-    if (dtype != 0 && dtype != 1) return fail(VQHIP_ERR_INVALID_INPUT, "dtype must be 0 (f32) or 1 (f16), not %d", dtype);
-    if (metric < VQHIP_SQUARED_EUCLIDEAN || metric > VQHIP_COSINE_UNCLAMPED) return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
     return VQHIP_OK;
 }
-
-// rows from host (kind = H2D) or device (D2D) memory into a new index
-static int flat_create(const void *src, hipMemcpyKind kind, uint64_t n, uint32_t d, int dtype, int metric, vqhip_flat **out) {
-    if (!out) return fail(VQHIP_ERR_NULL_PTR, "out is NULL");
-    *out = nullptr;
-    if (!src) return fail(VQHIP_ERR_NULL_PTR, "rows is NULL");
-    VQ_TRY(flat_check(n, d, dtype, metric));
-    VQ_TRY(require_gfx950());
-    hipStream_t s;
-    VQ_TRY(current_stream(&s));
-    std::unique_ptr<vqhip_flat> f(new vqhip_flat());
-    f->n = n;
-    f->d = d;
-    f->dtype = dtype;
-    f->metric = metric;
-    const size_t bytes = (size_t)n * d * (dtype == 1 ? 2 : 4);
-    VQ_TRY(f->rows.alloc(bytes));
-    VQ_HIP(hipMemcpyAsync(f->rows.p, src, bytes, kind, s));
-    if (vq_is_cos(metric)) {
-        VQ_TRY(f->rnorm.alloc((size_t)n * 4));
-        VQ_TRY(launch_knn_norms(f->rows.p, dtype, n, d, f->rnorm.as<float>(), s));
-    }
-    VQ_HIP(hipStreamSynchronize(s));  // the caller may free or change its rows once this returns
-    *out = f.release();
+static int check_metric(int metric) {
+    if (metric < VQHIP_SQUARED_EUCLIDEAN || metric > VQHIP_COSINE_UNCLAMPED) return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
     return VQHIP_OK;
 }
 
@@ -2767,6 +2773,24 @@ static int flat_create(const void *src, hipMemcpyKind kind, uint64_t n, uint32_t
 static int check_topk(uint64_t n, uint32_t topk) {
     if (topk == 0 || topk > 1024 || topk > n)
         return fail(VQHIP_ERR_INVALID_INPUT, "topk %u must be in [1, min(n, 1024)] (n = %llu)", topk, (unsigned long long)n);
+    return VQHIP_OK;
+}
+
+// Host rows that only pass through the device: n rows of row_b bytes at src go up through a staging buffer of at most
+// kStageBytes, and piece(device piece, first row, row count) queues the work on each.  Every piece has been waited for.
+constexpr size_t kStageBytes = 256u << 20;
+
+template <class F>
+static int staged_rows(const void *src, uint64_t n, size_t row_b, hipStream_t s, F &&piece) {
+    const uint64_t per = std::max<uint64_t>(1, kStageBytes / row_b);
+    DevBuf stage;
+    VQ_TRY(stage.alloc((size_t)std::min<uint64_t>(per, n) * row_b));
+    for (uint64_t r0 = 0; r0 < n; r0 += per) {
+        const uint64_t rn = std::min<uint64_t>(per, n - r0);
+        VQ_HIP(hipMemcpyAsync(stage.p, static_cast<const char *>(src) + r0 * row_b, (size_t)rn * row_b, hipMemcpyHostToDevice, s));
+        VQ_TRY(piece(stage.p, r0, rn));
+        VQ_HIP(hipStreamSynchronize(s));  // (the staging buffer is filled again)
+    }
     return VQHIP_OK;
 }
 
@@ -2789,21 +2813,121 @@ static int host_search(Entry &in, hipStream_t s, DevBuf &q, DevBuf &idx, DevBuf 
     return VQHIP_OK;
 }
 
-// queries_dev [nq][d] f32 on the device -> [nq][topk] results on the device, enqueued on s
-static int flat_search_enqueue(vqhip_flat *f, const float *queries_dev, uint32_t nq, uint32_t topk, uint32_t *idx_dev,
-                               float *dist_dev, hipStream_t s) {
-    const uint32_t qb = knn_query_batch(f->n, nq);
-    VQ_TRY(f->dist.ensure((size_t)qb * f->n * 4));
-    VQ_TRY(f->state.ensure(knn_state_bytes(qb)));
-    VQ_TRY(f->cand.ensure(topk_cand_bytes(qb)));
-    const float *qn = nullptr;
-    if (vq_is_cos(f->metric)) {
-        VQ_TRY(f->qnorm.ensure((size_t)nq * 4));
-        VQ_TRY(launch_knn_norms(queries_dev, 0, nq, f->d, f->qnorm.as<float>(), s));
-        qn = f->qnorm.as<float>();
+// The front of every search, rerank and read-back of a resident handle h, in the order every entry point checks: the
+// pointers, `checks` (the call's own, of its counts), nothing to do for nq == 0 (a read-back passes 1), the alignment of a
+// device form's queries (NULL: a host form), the device, the handle's lock and the calling thread's stream -- then
+// body(in, s).
+template <class H, class C, class F>
+static int resident_enter(H *h, bool args, C &&checks, uint32_t nq, const void *dev_queries, F &&body) {
+    if (!h || !args) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    VQ_TRY(checks());
+    if (nq == 0) return VQHIP_OK;
+    if (reinterpret_cast<uintptr_t>(dev_queries) & 3) return fail(VQHIP_ERR_INVALID_INPUT, "queries are not 4-byte aligned");
+    VQ_TRY(require_gfx950());
+    Entry in(h->sync);
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    return body(in, s);
+}
+static int no_checks() { return VQHIP_OK; }
+
+// the two search entry points of every resident index, over its search_enqueue(...)
+template <class T>
+static int resident_search(T *x, const float *queries, uint32_t nq, uint32_t topk, uint32_t *idx_out, float *dist_out) {
+    return resident_enter(x, queries && idx_out && dist_out, [&] { return check_topk(x->n, topk); }, nq, nullptr, [&](Entry &in, hipStream_t s) {
+        return host_search(in, s, x->q, x->idx, &x->out, queries, nq, x->d, topk, idx_out, dist_out, [&] {
+            return x->search_enqueue(x->q.template as<float>(), nq, topk, x->idx.template as<uint32_t>(), x->out.template as<float>(), s);
+        });
+    });
+}
+template <class T>
+static int resident_search_device(T *x, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx, void *dev_dist) {
+    return resident_enter(x, dev_queries && dev_idx && dev_dist, [&] { return check_topk(x->n, topk); }, nq, dev_queries, [&](Entry &, hipStream_t s) {
+        return x->search_enqueue(reinterpret_cast<const float *>(dev_queries), nq, topk, reinterpret_cast<uint32_t *>(dev_idx),
+                                 reinterpret_cast<float *>(dev_dist), s);
+    });
+}
+
+// the exact rerank of cand [nq][c] on a flat or a scalar index
+template <class T>
+static int exact_rerank(T *x, const float *queries, uint32_t nq, const uint32_t *cand, uint32_t c, uint32_t topk, uint32_t *idx_out,
+                        float *dist_out) {
+    auto checks = [&]() -> int {
+        if (c == 0 || c > 4096) return fail(VQHIP_ERR_INVALID_INPUT, "candidates per query %u must be in [1, 4096]", c);
+        if (topk == 0 || topk > c) return fail(VQHIP_ERR_INVALID_INPUT, "topk %u must be in [1, candidates = %u]", topk, c);
+        return VQHIP_OK;
+    };
+    return resident_enter(x, queries && cand && idx_out && dist_out, checks, nq, nullptr, [&](Entry &in, hipStream_t s) -> int {
+        const size_t q_b = (size_t)nq * x->d * 4, cand_b = (size_t)nq * c * 4, res_b = (size_t)nq * topk * 4;
+        VQ_TRY(x->q.ensure(q_b));
+        VQ_TRY(x->rr_cand.ensure(cand_b));
+        VQ_TRY(x->idx.ensure(res_b));
+        VQ_TRY(x->out.ensure(res_b));
+        VQ_TRY(x->rr_err.ensure(4));
+        VQ_HIP(hipMemcpyAsync(x->q.p, queries, q_b, hipMemcpyHostToDevice, s));
+        VQ_HIP(hipMemcpyAsync(x->rr_cand.p, cand, cand_b, hipMemcpyHostToDevice, s));
+        VQ_HIP(hipMemsetAsync(x->rr_err.p, 0, 4, s));
+        const float *qn = nullptr;
+        VQ_TRY(x->qnorms(x->q.template as<float>(), nq, &qn, s));
+        VQ_TRY(x->launch_rerank(qn, nq, c, topk, s));
+        uint32_t err = 0;
+        VQ_HIP(hipMemcpyAsync(&err, x->rr_err.p, 4, hipMemcpyDeviceToHost, s));
+        VQ_HIP(hipMemcpyAsync(idx_out, x->idx.p, res_b, hipMemcpyDeviceToHost, s));
+        VQ_HIP(hipMemcpyAsync(dist_out, x->out.p, res_b, hipMemcpyDeviceToHost, s));
+        VQ_HIP(hipStreamSynchronize(s));
+        in.synced();
+        if (err) return fail(VQHIP_ERR_INVALID_INPUT, "a candidate row id is >= n = %llu", (unsigned long long)x->n);
+        return VQHIP_OK;
+    });
+}
+
+// ------------------------------------------------------------------ exact k-NN (k_knn.hip) ----
+struct vqhip_flat : ExactResident<vqhip_flat> {
+    int dtype = 0;
+    DevBuf rows;  // [n][d] f32 or f16 bits
+
+    int launch_search(const float *queries_dev, const float *qn, uint32_t nq, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
+                      hipStream_t s) {
+        return launch_knn_search(metric, rows.p, dtype, n, d, rnorm.as<float>(), queries_dev, qn, nq, topk, dist.as<float>(), state.p,
+                                 cand.as<unsigned long long>(), idx_dev, dist_dev, s);
     }
-    return launch_knn_search(f->metric, f->rows.p, f->dtype, f->n, f->d, f->rnorm.as<float>(), queries_dev, qn, nq, topk,
-                             f->dist.as<float>(), f->state.p, f->cand.as<unsigned long long>(), idx_dev, dist_dev, s);
+    int launch_rerank(const float *qn, uint32_t nq, uint32_t c, uint32_t topk, hipStream_t s) {
+        return launch_knn_rerank(metric, rows.p, dtype, n, d, rnorm.as<float>(), q.as<float>(), qn, nq, rr_cand.as<uint32_t>(), c, topk,
+                                 idx.as<uint32_t>(), out.as<float>(), rr_err.as<uint32_t>(), s);
+    }
+    int launch_range(const float *queries_dev, const float *qn, uint32_t nq, uint64_t max_results, RangeOut *r, hipStream_t s) {
+        return launch_knn_range(metric, rows.p, dtype, n, d, rnorm.as<float>(), queries_dev, qn, nq, radii.as<float>(), max_results,
+                                dist.as<float>(), state.p, range_ws.p, r, s);
+    }
+};
+
+// rows from host (kind = H2D) or device (D2D) memory into a new index
+static int flat_create(const void *src, hipMemcpyKind kind, uint64_t n, uint32_t d, int dtype, int metric, vqhip_flat **out) {
+    if (!out) return fail(VQHIP_ERR_NULL_PTR, "out is NULL");
+    *out = nullptr;
+    if (!src) return fail(VQHIP_ERR_NULL_PTR, "rows is NULL");
+    if (d == 0) return fail(VQHIP_ERR_INVALID_INPUT, "d must be at least 1");
+    VQ_TRY(check_rows(n));
+    if (dtype != 0 && dtype != 1) return fail(VQHIP_ERR_INVALID_INPUT, "dtype must be 0 (f32) or 1 (f16), not %d", dtype);
+    VQ_TRY(check_metric(metric));
+    VQ_TRY(require_gfx950());
+    hipStream_t s;
+    VQ_TRY(current_stream(&s));
+    std::unique_ptr<vqhip_flat> f(new vqhip_flat());
+    f->n = n;
+    f->d = d;
+    f->dtype = dtype;
+    f->metric = metric;
+    const size_t bytes = (size_t)n * d * (dtype == 1 ? 2 : 4);
+    VQ_TRY(f->rows.alloc(bytes));
+    VQ_HIP(hipMemcpyAsync(f->rows.p, src, bytes, kind, s));
+    if (vq_is_cos(metric)) {
+        VQ_TRY(f->rnorm.alloc((size_t)n * 4));
+        VQ_TRY(launch_knn_norms(f->rows.p, dtype, n, d, f->rnorm.as<float>(), s));
+    }
+    VQ_HIP(hipStreamSynchronize(s));  // the caller may free or change its rows once this returns
+    *out = f.release();
+    return VQHIP_OK;
 }
 
 extern "C" {
@@ -2836,84 +2960,44 @@ int vqhip_flat_info(const vqhip_flat *f, uint64_t *n, uint32_t *d, int *dtype, i
 
 int vqhip_flat_search(vqhip_flat *f, const float *queries, uint32_t nq, uint32_t topk, uint32_t *idx_out, float *dist_out) {
     VQ_API_BEGIN
-    if (!f || !queries || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    VQ_TRY(check_topk(f->n, topk));
-    if (nq == 0) return VQHIP_OK;
-    VQ_TRY(require_gfx950());
-    Entry in(f->sync);
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    return host_search(in, s, f->q, f->idx, &f->out, queries, nq, f->d, topk, idx_out, dist_out, [&] {
-        return flat_search_enqueue(f, f->q.as<float>(), nq, topk, f->idx.as<uint32_t>(), f->out.as<float>(), s);
-    });
+    return resident_search(f, queries, nq, topk, idx_out, dist_out);
     VQ_API_END
 }
 
 int vqhip_flat_search_device(vqhip_flat *f, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx, void *dev_dist) {
     VQ_API_BEGIN
-    if (!f || !dev_queries || !dev_idx || !dev_dist) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    VQ_TRY(check_topk(f->n, topk));
-    if (nq == 0) return VQHIP_OK;
-    VQ_TRY(require_gfx950());
-    Entry in(f->sync);
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    return flat_search_enqueue(f, reinterpret_cast<const float *>(dev_queries), nq, topk, reinterpret_cast<uint32_t *>(dev_idx),
-                               reinterpret_cast<float *>(dev_dist), s);
+    return resident_search_device(f, dev_queries, nq, topk, dev_idx, dev_dist);
     VQ_API_END
 }
 
 int vqhip_flat_rerank(vqhip_flat *f, const float *queries, uint32_t nq, const uint32_t *cand, uint32_t c, uint32_t topk,
                       uint32_t *idx_out, float *dist_out) {
     VQ_API_BEGIN
-    if (!f || !queries || !cand || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    if (c == 0 || c > 4096) return fail(VQHIP_ERR_INVALID_INPUT, "candidates per query %u must be in [1, 4096]", c);
-    if (topk == 0 || topk > c) return fail(VQHIP_ERR_INVALID_INPUT, "topk %u must be in [1, candidates = %u]", topk, c);
-    if (nq == 0) return VQHIP_OK;
-    VQ_TRY(require_gfx950());
-    Entry in(f->sync);
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    VQ_TRY(f->q.ensure((size_t)nq * f->d * 4));
-    VQ_TRY(f->rr_cand.ensure((size_t)nq * c * 4));
-    VQ_TRY(f->idx.ensure((size_t)nq * topk * 4));
-    VQ_TRY(f->out.ensure((size_t)nq * topk * 4));
-    VQ_TRY(f->rr_err.ensure(4));
-    VQ_HIP(hipMemcpyAsync(f->q.p, queries, (size_t)nq * f->d * 4, hipMemcpyHostToDevice, s));
-    VQ_HIP(hipMemcpyAsync(f->rr_cand.p, cand, (size_t)nq * c * 4, hipMemcpyHostToDevice, s));
-    VQ_HIP(hipMemsetAsync(f->rr_err.p, 0, 4, s));
-    const float *qn = nullptr;
-    if (vq_is_cos(f->metric)) {
-        VQ_TRY(f->qnorm.ensure((size_t)nq * 4));
-        VQ_TRY(launch_knn_norms(f->q.p, 0, nq, f->d, f->qnorm.as<float>(), s));
-        qn = f->qnorm.as<float>();
-    }
-    VQ_TRY(launch_knn_rerank(f->metric, f->rows.p, f->dtype, f->n, f->d, f->rnorm.as<float>(), f->q.as<float>(), qn, nq,
-                             f->rr_cand.as<uint32_t>(), c, topk, f->idx.as<uint32_t>(), f->out.as<float>(), f->rr_err.as<uint32_t>(), s));
-    uint32_t err = 0;
-    VQ_HIP(hipMemcpyAsync(&err, f->rr_err.p, 4, hipMemcpyDeviceToHost, s));
-    VQ_HIP(hipMemcpyAsync(idx_out, f->idx.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
-    VQ_HIP(hipMemcpyAsync(dist_out, f->out.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
-    VQ_HIP(hipStreamSynchronize(s));
-    in.synced();
-    if (err) return fail(VQHIP_ERR_INVALID_INPUT, "a candidate row id is >= n = %llu", (unsigned long long)f->n);
-    return VQHIP_OK;
+    return exact_rerank(f, queries, nq, cand, c, topk, idx_out, dist_out);
     VQ_API_END
 }
 
 }  // extern "C"
 
 // ------------------------------------------------------------------ scalar index (k_sqindex.hip) ----
-struct vqhip_sqindex {
-    HandleSync sync;
-    uint64_t n = 0;
-    uint32_t d = 0, levels = 0;
+struct vqhip_sqindex : ExactResident<vqhip_sqindex> {
+    uint32_t levels = 0;
     float mn = 0, mx = 0, step = 0;
-    int metric = VQHIP_EUCLIDEAN;
-    DevBuf codes, rnorm;                           // the index: [n][d] u8, |v(row)| for cosine
-    DevBuf q, qnorm, dist, state, cand, idx, out;  // per-call workspaces
-    DevBuf rr_cand, rr_err;                        // rerank: candidate ids, the out-of-range flag
-    DevBuf radii, range_ws;                        // range search: the radii, the stage's counts and offsets
+    DevBuf codes;  // [n][d] u8
+
+    int launch_search(const float *queries_dev, const float *qn, uint32_t nq, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
+                      hipStream_t s) {
+        return launch_sq_search(metric, codes.as<uint8_t>(), n, d, mn, step, rnorm.as<float>(), queries_dev, qn, nq, topk, dist.as<float>(),
+                                state.p, cand.as<unsigned long long>(), idx_dev, dist_dev, s);
+    }
+    int launch_rerank(const float *qn, uint32_t nq, uint32_t c, uint32_t topk, hipStream_t s) {
+        return launch_sq_rerank(metric, codes.as<uint8_t>(), n, d, mn, step, rnorm.as<float>(), q.as<float>(), qn, nq, rr_cand.as<uint32_t>(),
+                                c, topk, idx.as<uint32_t>(), out.as<float>(), rr_err.as<uint32_t>(), s);
+    }
+    int launch_range(const float *queries_dev, const float *qn, uint32_t nq, uint64_t max_results, RangeOut *r, hipStream_t s) {
+        return launch_sq_range(metric, codes.as<uint8_t>(), n, d, mn, step, rnorm.as<float>(), queries_dev, qn, nq, radii.as<float>(),
+                               max_results, dist.as<float>(), state.p, range_ws.p, r, s);
+    }
 };
 
 // src: u8 codes [n][d] (rows == false) or f32 rows [n][d] to encode (rows == true), in host (kind = H2D) or device memory
@@ -2926,8 +3010,8 @@ static int sqindex_create(const void *src, hipMemcpyKind kind, bool rows, float 
     VQ_TRY(sq_check(mn, mx, levels, &step));
     if (!src) return fail(VQHIP_ERR_NULL_PTR, rows ? "rows is NULL" : "codes is NULL");
     if (d == 0) return fail(VQHIP_ERR_INVALID_INPUT, "d must be at least 1");
-    if (n == 0 || n >= (1ull << 32)) return fail(VQHIP_ERR_INVALID_INPUT, "n must be in [1, 2^32)");
-    if (metric < VQHIP_SQUARED_EUCLIDEAN || metric > VQHIP_COSINE_UNCLAMPED) return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
+    VQ_TRY(check_rows(n));
+    VQ_TRY(check_metric(metric));
     if (rows && kind == hipMemcpyDeviceToDevice && (reinterpret_cast<uintptr_t>(src) & 3))
         return fail(VQHIP_ERR_INVALID_INPUT, "rows are not 4-byte aligned");
     if (rows) VQ_TRY(sq_encode_op(mn, mx, levels, &op));
@@ -2942,17 +3026,10 @@ static int sqindex_create(const void *src, hipMemcpyKind kind, bool rows, float 
         VQ_HIP(hipMemcpyAsync(x->codes.p, src, bytes, kind, s));
     } else if (kind == hipMemcpyDeviceToDevice) {
         VQ_TRY(launch_sqbq_encode(op, static_cast<const float *>(src), bytes, x->codes.as<uint8_t>(), s));
-    } else {
-        // host rows: encoded through a staging buffer of at most 256 MB at a time, so that only the codes stay
-        const uint64_t per = std::max<uint64_t>(1, (256ull << 20) / ((uint64_t)d * 4));
-        DevBuf stage;
-        VQ_TRY(stage.alloc((size_t)std::min<uint64_t>(per, n) * d * 4));
-        for (uint64_t r0 = 0; r0 < n; r0 += per) {
-            const uint64_t rn = std::min<uint64_t>(per, n - r0);
-            VQ_HIP(hipMemcpyAsync(stage.p, static_cast<const float *>(src) + r0 * d, (size_t)rn * d * 4, hipMemcpyHostToDevice, s));
-            VQ_TRY(launch_sqbq_encode(op, stage.as<float>(), rn * d, x->codes.as<uint8_t>() + r0 * d, s));
-            VQ_HIP(hipStreamSynchronize(s));
-        }
+    } else {  // host rows are encoded a piece at a time, so that only the codes stay
+        VQ_TRY(staged_rows(src, n, (size_t)d * 4, s, [&](const void *piece, uint64_t r0, uint64_t rn) {
+            return launch_sqbq_encode(op, static_cast<const float *>(piece), rn * d, x->codes.as<uint8_t>() + r0 * d, s);
+        }));
     }
     if (vq_is_cos(metric)) {
         VQ_TRY(x->rnorm.alloc((size_t)n * 4));
@@ -2961,29 +3038,6 @@ static int sqindex_create(const void *src, hipMemcpyKind kind, bool rows, float 
     VQ_HIP(hipStreamSynchronize(s));  // the caller may free or change its source once this returns
     *out = x.release();
     return VQHIP_OK;
-}
-
-// the query norms of a cosine index into x->qnorm (NULL otherwise)
-static int sqindex_qnorms(vqhip_sqindex *x, const float *queries_dev, uint32_t nq, const float **qn, hipStream_t s) {
-    *qn = nullptr;
-    if (!vq_is_cos(x->metric)) return VQHIP_OK;
-    VQ_TRY(x->qnorm.ensure((size_t)nq * 4));
-    VQ_TRY(launch_knn_norms(queries_dev, 0, nq, x->d, x->qnorm.as<float>(), s));
-    *qn = x->qnorm.as<float>();
-    return VQHIP_OK;
-}
-
-// queries_dev [nq][d] f32 on the device -> [nq][topk] results on the device, enqueued on s
-static int sqindex_search_enqueue(vqhip_sqindex *x, const float *queries_dev, uint32_t nq, uint32_t topk, uint32_t *idx_dev,
-                                  float *dist_dev, hipStream_t s) {
-    const uint32_t qb = knn_query_batch(x->n, nq);
-    VQ_TRY(x->dist.ensure((size_t)qb * x->n * 4));
-    VQ_TRY(x->state.ensure(knn_state_bytes(qb)));
-    VQ_TRY(x->cand.ensure(topk_cand_bytes(qb)));
-    const float *qn = nullptr;
-    VQ_TRY(sqindex_qnorms(x, queries_dev, nq, &qn, s));
-    return launch_sq_search(x->metric, x->codes.as<uint8_t>(), x->n, x->d, x->mn, x->step, x->rnorm.as<float>(), queries_dev, qn, nq,
-                            topk, x->dist.as<float>(), x->state.p, x->cand.as<unsigned long long>(), idx_dev, dist_dev, s);
 }
 
 extern "C" {
@@ -3034,81 +3088,32 @@ int vqhip_sqindex_info(const vqhip_sqindex *x, uint64_t *n, uint32_t *d, int *me
 
 int vqhip_sqindex_codes(vqhip_sqindex *x, uint8_t *codes) {
     VQ_API_BEGIN
-    if (!x || !codes) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    VQ_TRY(require_gfx950());
-    Entry in(x->sync);
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    VQ_HIP(hipMemcpyAsync(codes, x->codes.p, (size_t)x->n * x->d, hipMemcpyDeviceToHost, s));
-    VQ_HIP(hipStreamSynchronize(s));
-    in.synced();
-    return VQHIP_OK;
+    return resident_enter(x, codes != nullptr, no_checks, 1, nullptr, [&](Entry &in, hipStream_t s) -> int {
+        VQ_HIP(hipMemcpyAsync(codes, x->codes.p, (size_t)x->n * x->d, hipMemcpyDeviceToHost, s));
+        VQ_HIP(hipStreamSynchronize(s));
+        in.synced();
+        return VQHIP_OK;
+    });
     VQ_API_END
 }
 
 int vqhip_sqindex_search(vqhip_sqindex *x, const float *queries, uint32_t nq, uint32_t topk, uint32_t *idx_out, float *dist_out) {
     VQ_API_BEGIN
-    if (!x || !queries || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    VQ_TRY(check_topk(x->n, topk));
-    if (nq == 0) return VQHIP_OK;
-    VQ_TRY(require_gfx950());
-    Entry in(x->sync);
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    return host_search(in, s, x->q, x->idx, &x->out, queries, nq, x->d, topk, idx_out, dist_out, [&] {
-        return sqindex_search_enqueue(x, x->q.as<float>(), nq, topk, x->idx.as<uint32_t>(), x->out.as<float>(), s);
-    });
+    return resident_search(x, queries, nq, topk, idx_out, dist_out);
     VQ_API_END
 }
 
 int vqhip_sqindex_search_device(vqhip_sqindex *x, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx,
                                 void *dev_dist) {
     VQ_API_BEGIN
-    if (!x || !dev_queries || !dev_idx || !dev_dist) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    VQ_TRY(check_topk(x->n, topk));
-    if (nq == 0) return VQHIP_OK;
-    if (reinterpret_cast<uintptr_t>(dev_queries) & 3) return fail(VQHIP_ERR_INVALID_INPUT, "queries are not 4-byte aligned");
-    VQ_TRY(require_gfx950());
-    Entry in(x->sync);
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    return sqindex_search_enqueue(x, reinterpret_cast<const float *>(dev_queries), nq, topk, reinterpret_cast<uint32_t *>(dev_idx),
-                                  reinterpret_cast<float *>(dev_dist), s);
+    return resident_search_device(x, dev_queries, nq, topk, dev_idx, dev_dist);
     VQ_API_END
 }
 
 int vqhip_sqindex_rerank(vqhip_sqindex *x, const float *queries, uint32_t nq, const uint32_t *cand, uint32_t c, uint32_t topk,
                          uint32_t *idx_out, float *dist_out) {
     VQ_API_BEGIN
-    if (!x || !queries || !cand || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    if (c == 0 || c > 4096) return fail(VQHIP_ERR_INVALID_INPUT, "candidates per query %u must be in [1, 4096]", c);
-    if (topk == 0 || topk > c) return fail(VQHIP_ERR_INVALID_INPUT, "topk %u must be in [1, candidates = %u]", topk, c);
-    if (nq == 0) return VQHIP_OK;
-    VQ_TRY(require_gfx950());
-    Entry in(x->sync);
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    VQ_TRY(x->q.ensure((size_t)nq * x->d * 4));
-    VQ_TRY(x->rr_cand.ensure((size_t)nq * c * 4));
-    VQ_TRY(x->idx.ensure((size_t)nq * topk * 4));
-    VQ_TRY(x->out.ensure((size_t)nq * topk * 4));
-    VQ_TRY(x->rr_err.ensure(4));
-    VQ_HIP(hipMemcpyAsync(x->q.p, queries, (size_t)nq * x->d * 4, hipMemcpyHostToDevice, s));
-    VQ_HIP(hipMemcpyAsync(x->rr_cand.p, cand, (size_t)nq * c * 4, hipMemcpyHostToDevice, s));
-    VQ_HIP(hipMemsetAsync(x->rr_err.p, 0, 4, s));
-    const float *qn = nullptr;
-    VQ_TRY(sqindex_qnorms(x, x->q.as<float>(), nq, &qn, s));
-    VQ_TRY(launch_sq_rerank(x->metric, x->codes.as<uint8_t>(), x->n, x->d, x->mn, x->step, x->rnorm.as<float>(), x->q.as<float>(), qn,
-                            nq, x->rr_cand.as<uint32_t>(), c, topk, x->idx.as<uint32_t>(), x->out.as<float>(),
-                            x->rr_err.as<uint32_t>(), s));
-    uint32_t err = 0;
-    VQ_HIP(hipMemcpyAsync(&err, x->rr_err.p, 4, hipMemcpyDeviceToHost, s));
-    VQ_HIP(hipMemcpyAsync(idx_out, x->idx.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
-    VQ_HIP(hipMemcpyAsync(dist_out, x->out.p, (size_t)nq * topk * 4, hipMemcpyDeviceToHost, s));
-    VQ_HIP(hipStreamSynchronize(s));
-    in.synced();
-    if (err) return fail(VQHIP_ERR_INVALID_INPUT, "a candidate row id is >= n = %llu", (unsigned long long)x->n);
-    return VQHIP_OK;
+    return exact_rerank(x, queries, nq, cand, c, topk, idx_out, dist_out);
     VQ_API_END
 }
 
@@ -3130,11 +3135,11 @@ static int range_args(const void *queries, const float *radii, uint32_t nq, uint
     return VQHIP_OK;
 }
 
-// One range call on a flat or a scalar index h: the queries (host: through h->q) and the radii go up, `run` queues the
-// index's driver, which leaves *out complete.  The index is looked at after range_args, so those checks need none.
-template <class H, class F>
+// One range call on a flat or a scalar index h: the queries (host: through h->q) and the radii go up, and the index's
+// driver, h->launch_range, leaves *out complete.  The index is looked at after range_args, so those checks need none.
+template <class H>
 static int range_search(H *h, const void *queries, bool host, uint32_t nq, const float *radii, uint64_t max_results,
-                        vqhip_range **out, F &&run) {
+                        vqhip_range **out) {
     VQ_TRY(range_args(queries, radii, nq, max_results, out));
     if (!h) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
     if (!host && (reinterpret_cast<uintptr_t>(queries) & 3)) return fail(VQHIP_ERR_INVALID_INPUT, "queries are not 4-byte aligned");
@@ -3154,34 +3159,12 @@ static int range_search(H *h, const void *queries, bool host, uint32_t nq, const
     VQ_TRY(h->dist.ensure((size_t)knn_query_batch(h->n, nq) * h->n * 4));
     VQ_TRY(h->state.ensure(knn_state_bytes(knn_query_batch(h->n, nq))));
     VQ_TRY(h->range_ws.ensure(range_ws_bytes(h->n, nq)));
-    VQ_TRY(run(qdev, &r->r, s));  // (every exit of the driver has waited for s)
+    const float *qn = nullptr;
+    if (nq) VQ_TRY(h->qnorms(qdev, nq, &qn, s));
+    VQ_TRY(h->launch_range(qdev, qn, nq, max_results, &r->r, s));  // (every exit of the driver has waited for s)
     in.synced();
     *out = r.release();
     return VQHIP_OK;
-}
-
-static int flat_range(vqhip_flat *f, const void *queries, bool host, uint32_t nq, const float *radii, uint64_t max_results,
-                      vqhip_range **out) {
-    return range_search(f, queries, host, nq, radii, max_results, out, [&](const float *qdev, RangeOut *r, hipStream_t s) -> int {
-        const float *qn = nullptr;
-        if (vq_is_cos(f->metric) && nq) {
-            VQ_TRY(f->qnorm.ensure((size_t)nq * 4));
-            VQ_TRY(launch_knn_norms(qdev, 0, nq, f->d, f->qnorm.as<float>(), s));
-            qn = f->qnorm.as<float>();
-        }
-        return launch_knn_range(f->metric, f->rows.p, f->dtype, f->n, f->d, f->rnorm.as<float>(), qdev, qn, nq, f->radii.as<float>(),
-                                max_results, f->dist.as<float>(), f->state.p, f->range_ws.p, r, s);
-    });
-}
-
-static int sqindex_range(vqhip_sqindex *x, const void *queries, bool host, uint32_t nq, const float *radii, uint64_t max_results,
-                         vqhip_range **out) {
-    return range_search(x, queries, host, nq, radii, max_results, out, [&](const float *qdev, RangeOut *r, hipStream_t s) -> int {
-        const float *qn = nullptr;
-        if (nq) VQ_TRY(sqindex_qnorms(x, qdev, nq, &qn, s));
-        return launch_sq_range(x->metric, x->codes.as<uint8_t>(), x->n, x->d, x->mn, x->step, x->rnorm.as<float>(), qdev, qn, nq,
-                               x->radii.as<float>(), max_results, x->dist.as<float>(), x->state.p, x->range_ws.p, r, s);
-    });
 }
 
 extern "C" {
@@ -3189,28 +3172,28 @@ extern "C" {
 int vqhip_flat_range_search(vqhip_flat *f, const float *queries, uint32_t nq, const float *radii, uint64_t max_results,
                             vqhip_range **out) {
     VQ_API_BEGIN
-    return flat_range(f, queries, true, nq, radii, max_results, out);
+    return range_search(f, queries, true, nq, radii, max_results, out);
     VQ_API_END
 }
 
 int vqhip_flat_range_search_device(vqhip_flat *f, const void *dev_queries, uint32_t nq, const float *radii, uint64_t max_results,
                                    vqhip_range **out) {
     VQ_API_BEGIN
-    return flat_range(f, dev_queries, false, nq, radii, max_results, out);
+    return range_search(f, dev_queries, false, nq, radii, max_results, out);
     VQ_API_END
 }
 
 int vqhip_sqindex_range_search(vqhip_sqindex *x, const float *queries, uint32_t nq, const float *radii, uint64_t max_results,
                                vqhip_range **out) {
     VQ_API_BEGIN
-    return sqindex_range(x, queries, true, nq, radii, max_results, out);
+    return range_search(x, queries, true, nq, radii, max_results, out);
     VQ_API_END
 }
 
 int vqhip_sqindex_range_search_device(vqhip_sqindex *x, const void *dev_queries, uint32_t nq, const float *radii,
                                       uint64_t max_results, vqhip_range **out) {
     VQ_API_BEGIN
-    return sqindex_range(x, dev_queries, false, nq, radii, max_results, out);
+    return range_search(x, dev_queries, false, nq, radii, max_results, out);
     VQ_API_END
 }
 
@@ -3251,28 +3234,42 @@ int vqhip_range_destroy(vqhip_range *r) {
 }  // extern "C"
 
 // ------------------------------------------------------------------ binary index (k_binary.hip) ----
-struct vqhip_binary {
-    HandleSync sync;
-    uint64_t n = 0;
-    uint32_t d = 0, W = 0, low = 0, high = 1;
-    float thr = 0;
-    int metric = VQHIP_MANHATTAN;
-    DevBuf words, table;                              // [n][W] packed rows, S [d + 1]
-    DevBuf q, qw, hist, sel, adc_sel, cnt, cand, idx, out;  // per-call workspaces
-};
-
 static constexpr uint32_t kBinaryBatch = 1024;  // queries per internal batch
+
+struct vqhip_binary : Resident {
+    uint32_t W = 0, low = 0, high = 1;
+    float thr = 0;
+    DevBuf words, table;                 // [n][W] packed rows, S [d + 1]
+    DevBuf qw, hist, sel, adc_sel, cnt;  // per-call workspaces
+
+    // queries_dev [nq][d] f32 on the device -> [nq][topk] results on the device, enqueued on s in batches of 1024
+    int search_enqueue(const float *queries_dev, uint32_t nq, uint32_t topk, uint32_t *idx_dev, float *dist_dev, hipStream_t s) {
+        const uint32_t qb = std::min(nq, kBinaryBatch);
+        VQ_TRY(qw.ensure((size_t)qb * W * 4));
+        VQ_TRY(hist.ensure(binary_hist_bytes(qb, d)));
+        VQ_TRY(sel.ensure((size_t)qb * sizeof(BinSel)));
+        VQ_TRY(adc_sel.ensure((size_t)qb * 8));
+        VQ_TRY(cnt.ensure((size_t)qb * 4));
+        VQ_TRY(cand.ensure(topk_cand_bytes(qb)));
+        for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
+            const uint32_t nb = std::min(qb, nq - q0);
+            VQ_TRY(launch_bq_pack(queries_dev + (size_t)q0 * d, VQHIP_BINARY_F32, nb, d, thr, high, qw.as<uint32_t>(), s));
+            VQ_TRY(launch_binary_search(words.as<uint32_t>(), n, d, metric, table.as<float>(), qw.as<uint32_t>(), nb, topk,
+                                        hist.as<uint32_t>(), sel.as<BinSel>(), adc_sel.as<uint32_t>(), cnt.as<uint32_t>(),
+                                        cand.as<unsigned long long>(), idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s));
+        }
+        return VQHIP_OK;
+    }
+};
 
 static int binary_check(int kind, uint64_t n, uint32_t d, float threshold, uint32_t low, uint32_t high, int metric) {
     if (kind != VQHIP_BINARY_F32 && kind != VQHIP_BINARY_U8 && kind != VQHIP_BINARY_PACKED)
         return fail(VQHIP_ERR_INVALID_INPUT, "source kind must be 0 (f32), 1 (u8 codes) or 2 (packed words), not %d", kind);
     if (d == 0 || d > VQHIP_BINARY_MAX_DIM) return fail(VQHIP_ERR_INVALID_INPUT, "d %u must be in [1, 8192]", d);
-    if (n == 0 || n >= (1ull << 32)) return fail(VQHIP_ERR_INVALID_INPUT, "n must be in [1, 2^32)");
+    VQ_TRY(check_rows(n));
     VQ_TRY(bq_check(threshold, low, high));
     if (vq_is_cos(metric)) return fail(VQHIP_ERR_UNSUPPORTED, "cosine is not a function of the Hamming distance alone");
-    if (metric != VQHIP_SQUARED_EUCLIDEAN && metric != VQHIP_EUCLIDEAN && metric != VQHIP_MANHATTAN)
-        return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
-    return VQHIP_OK;
+    return check_metric(metric);
 }
 
 static int binary_create(const void *src, hipMemcpyKind kind_copy, int kind, uint64_t n, uint32_t d, float threshold,
@@ -3311,43 +3308,13 @@ static int binary_create(const void *src, hipMemcpyKind kind_copy, int kind, uin
         }
     } else if (kind_copy == hipMemcpyDeviceToDevice) {
         VQ_TRY(launch_bq_pack(src, kind, n, d, threshold, high, b->words.as<uint32_t>(), s));
-    } else {
-        // host rows: through a staging buffer of at most 256 MB at a time
-        const size_t esz = kind == VQHIP_BINARY_U8 ? 1 : 4;
-        const uint64_t per = std::max<uint64_t>(1, (256ull << 20) / ((uint64_t)d * esz));
-        DevBuf stage;
-        VQ_TRY(stage.alloc((size_t)std::min<uint64_t>(per, n) * d * esz));
-        for (uint64_t r0 = 0; r0 < n; r0 += per) {
-            const uint64_t rn = std::min<uint64_t>(per, n - r0);
-            VQ_HIP(hipMemcpyAsync(stage.p, static_cast<const char *>(src) + r0 * d * esz, (size_t)rn * d * esz,
-                                  hipMemcpyHostToDevice, s));
-            VQ_TRY(launch_bq_pack(stage.p, kind, rn, d, threshold, high, b->words.as<uint32_t>() + r0 * W, s));
-            VQ_HIP(hipStreamSynchronize(s));
-        }
+    } else {  // host rows are packed a piece at a time
+        VQ_TRY(staged_rows(src, n, (size_t)d * (kind == VQHIP_BINARY_U8 ? 1 : 4), s, [&](const void *piece, uint64_t r0, uint64_t rn) {
+            return launch_bq_pack(piece, kind, rn, d, threshold, high, b->words.as<uint32_t>() + r0 * W, s);
+        }));
     }
     VQ_HIP(hipStreamSynchronize(s));  // the caller may free or change its source once this returns
     *out = b.release();
-    return VQHIP_OK;
-}
-
-// queries_dev [nq][d] f32 on the device -> [nq][topk] results on the device, enqueued on s in batches of 1024
-static int binary_search_enqueue(vqhip_binary *b, const float *queries_dev, uint32_t nq, uint32_t topk, uint32_t *idx_dev,
-                                 float *dist_dev, hipStream_t s) {
-    const uint32_t qb = std::min(nq, kBinaryBatch);
-    VQ_TRY(b->qw.ensure((size_t)qb * b->W * 4));
-    VQ_TRY(b->hist.ensure(binary_hist_bytes(qb, b->d)));
-    VQ_TRY(b->sel.ensure((size_t)qb * sizeof(BinSel)));
-    VQ_TRY(b->adc_sel.ensure((size_t)qb * 8));
-    VQ_TRY(b->cnt.ensure((size_t)qb * 4));
-    VQ_TRY(b->cand.ensure(topk_cand_bytes(qb)));
-    for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
-        const uint32_t nb = std::min(qb, nq - q0);
-        VQ_TRY(launch_bq_pack(queries_dev + (size_t)q0 * b->d, VQHIP_BINARY_F32, nb, b->d, b->thr, b->high, b->qw.as<uint32_t>(), s));
-        VQ_TRY(launch_binary_search(b->words.as<uint32_t>(), b->n, b->d, b->metric, b->table.as<float>(), b->qw.as<uint32_t>(), nb,
-                                    topk, b->hist.as<uint32_t>(), b->sel.as<BinSel>(), b->adc_sel.as<uint32_t>(),
-                                    b->cnt.as<uint32_t>(), b->cand.as<unsigned long long>(), idx_dev + (size_t)q0 * topk,
-                                    dist_dev + (size_t)q0 * topk, s));
-    }
     return VQHIP_OK;
 }
 
@@ -3363,19 +3330,14 @@ int vqhip_bq_pack(float threshold, const float *x, uint64_t n, uint32_t d, uint3
     hipStream_t s;
     VQ_TRY(current_stream(&s));
     const uint32_t W = bin_words(d);
-    const uint64_t per = std::max<uint64_t>(1, (256ull << 20) / ((uint64_t)d * 4));
-    const uint64_t rows = std::min<uint64_t>(per, n);
-    DevBuf dx, dw;
-    VQ_TRY(dx.alloc((size_t)rows * d * 4));
-    VQ_TRY(dw.alloc((size_t)rows * W * 4));
-    for (uint64_t r0 = 0; r0 < n; r0 += per) {
-        const uint64_t rn = std::min<uint64_t>(per, n - r0);
-        VQ_HIP(hipMemcpyAsync(dx.p, x + r0 * d, (size_t)rn * d * 4, hipMemcpyHostToDevice, s));
-        VQ_TRY(launch_bq_pack(dx.p, VQHIP_BINARY_F32, rn, d, threshold, 1, dw.as<uint32_t>(), s));
+    const size_t row_b = (size_t)d * 4;
+    DevBuf dw;
+    VQ_TRY(dw.alloc((size_t)std::min<uint64_t>(std::max<uint64_t>(1, kStageBytes / row_b), n) * W * 4));
+    return staged_rows(x, n, row_b, s, [&](const void *piece, uint64_t r0, uint64_t rn) -> int {
+        VQ_TRY(launch_bq_pack(piece, VQHIP_BINARY_F32, rn, d, threshold, 1, dw.as<uint32_t>(), s));
         VQ_HIP(hipMemcpyAsync(words + r0 * W, dw.p, (size_t)rn * W * 4, hipMemcpyDeviceToHost, s));
-        VQ_HIP(hipStreamSynchronize(s));
-    }
-    return VQHIP_OK;
+        return VQHIP_OK;
+    });
     VQ_API_END
 }
 
@@ -3431,45 +3393,24 @@ int vqhip_binary_info(const vqhip_binary *b, uint64_t *n, uint32_t *d, float *th
 
 int vqhip_binary_packed(vqhip_binary *b, uint32_t *words) {
     VQ_API_BEGIN
-    if (!b || !words) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    VQ_TRY(require_gfx950());
-    Entry in(b->sync);
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    VQ_HIP(hipMemcpyAsync(words, b->words.p, (size_t)b->n * b->W * 4, hipMemcpyDeviceToHost, s));
-    VQ_HIP(hipStreamSynchronize(s));
-    in.synced();
-    return VQHIP_OK;
+    return resident_enter(b, words != nullptr, no_checks, 1, nullptr, [&](Entry &in, hipStream_t s) -> int {
+        VQ_HIP(hipMemcpyAsync(words, b->words.p, (size_t)b->n * b->W * 4, hipMemcpyDeviceToHost, s));
+        VQ_HIP(hipStreamSynchronize(s));
+        in.synced();
+        return VQHIP_OK;
+    });
     VQ_API_END
 }
 
 int vqhip_binary_search(vqhip_binary *b, const float *queries, uint32_t nq, uint32_t topk, uint32_t *idx_out, float *dist_out) {
     VQ_API_BEGIN
-    if (!b || !queries || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    VQ_TRY(check_topk(b->n, topk));
-    if (nq == 0) return VQHIP_OK;
-    VQ_TRY(require_gfx950());
-    Entry in(b->sync);
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    return host_search(in, s, b->q, b->idx, &b->out, queries, nq, b->d, topk, idx_out, dist_out, [&] {
-        return binary_search_enqueue(b, b->q.as<float>(), nq, topk, b->idx.as<uint32_t>(), b->out.as<float>(), s);
-    });
+    return resident_search(b, queries, nq, topk, idx_out, dist_out);
     VQ_API_END
 }
 
 int vqhip_binary_search_device(vqhip_binary *b, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx, void *dev_dist) {
     VQ_API_BEGIN
-    if (!b || !dev_queries || !dev_idx || !dev_dist) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    VQ_TRY(check_topk(b->n, topk));
-    if (nq == 0) return VQHIP_OK;
-    if (reinterpret_cast<uintptr_t>(dev_queries) & 3) return fail(VQHIP_ERR_INVALID_INPUT, "queries are not 4-byte aligned");
-    VQ_TRY(require_gfx950());
-    Entry in(b->sync);
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    return binary_search_enqueue(b, reinterpret_cast<const float *>(dev_queries), nq, topk, reinterpret_cast<uint32_t *>(dev_idx),
-                                 reinterpret_cast<float *>(dev_dist), s);
+    return resident_search_device(b, dev_queries, nq, topk, dev_idx, dev_dist);
     VQ_API_END
 }
 
@@ -3508,10 +3449,6 @@ struct IvfLists {
 static int ivf_check_lists(const void *coarse, uint32_t nlist) {
     if (!coarse) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
     if (nlist == 0 || nlist > 65536) return fail(VQHIP_ERR_INVALID_INPUT, "nlist %u must be in [1, 65536]", nlist);
-    return VQHIP_OK;
-}
-static int ivf_check_metric(int metric) {
-    if (metric < VQHIP_SQUARED_EUCLIDEAN || metric > VQHIP_COSINE_UNCLAMPED) return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
     return VQHIP_OK;
 }
 static void ivf_init(IvfLists *ix, const float *coarse, uint32_t nlist, uint32_t dim, int metric, size_t row_b) {
@@ -3620,7 +3557,7 @@ static int ivf_no_hook() { return VQHIP_OK; }
 // queries_dev [nq][dim] f32 -> probe lists [nq][nprobe] on the device
 static int ivf_probe_enqueue(IvfLists *ix, const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t *lists_dev, hipStream_t s) {
     VQ_TRY(ix->probe_dist.ensure((size_t)nq * nprobe * 4));
-    return flat_search_enqueue(ix->flat, queries_dev, nq, nprobe, lists_dev, ix->probe_dist.as<float>(), s);
+    return ix->flat->search_enqueue(queries_dev, nq, nprobe, lists_dev, ix->probe_dist.as<float>(), s);
 }
 
 // Batches of queries bound a search's workspace: the distances of a batch (4 bytes per position of S(q), sized by the
@@ -3765,7 +3702,7 @@ int vqhip_ivfpq_create_ex(const float *coarse, uint32_t nlist, const float *code
     if (m == 0 || k == 0 || sub_dim == 0) return fail(VQHIP_ERR_INVALID_INPUT, "m, k and sub_dim must be positive");
     if (k > kMaxCentroids) return fail(VQHIP_ERR_UNSUPPORTED, "k=%u > 65536: codes are at most two bytes per subspace", k);
     if ((uint64_t)m * sub_dim >= (1ull << 32)) return fail(VQHIP_ERR_INVALID_INPUT, "dim = m * sub_dim must be below 2^32");
-    VQ_TRY(ivf_check_metric(metric));
+    VQ_TRY(check_metric(metric));
     if (vq_is_cos(metric)) return fail(VQHIP_ERR_UNSUPPORTED, "cosine distance is not a sum over subspaces: no ADC form");
     if (!adc_table_fits(m, k)) return fail_adc_table(m, k);
     std::unique_ptr<vqhip_ivfpq> ix(new vqhip_ivfpq());
@@ -4059,7 +3996,7 @@ int vqhip_ivfflat_create(const float *coarse, uint32_t nlist, uint32_t dim, int 
     VQ_TRY(ivf_check_lists(coarse, nlist));
     if (dim == 0) return fail(VQHIP_ERR_INVALID_INPUT, "dim must be at least 1");
     if (dtype != 0 && dtype != 1) return fail(VQHIP_ERR_INVALID_INPUT, "dtype must be 0 (f32) or 1 (f16), not %d", dtype);
-    VQ_TRY(ivf_check_metric(metric));
+    VQ_TRY(check_metric(metric));
     std::unique_ptr<vqhip_ivfflat> ix(new vqhip_ivfflat());
     ivf_init(ix.get(), coarse, nlist, dim, metric, (size_t)dim * (dtype == 1 ? 2 : 4));
     ix->dtype = dtype;
@@ -4139,7 +4076,7 @@ int vqhip_ivfsq_create(float min, float max, uint32_t levels, const float *coars
     VQ_TRY(sq_check(min, max, levels, &step));
     VQ_TRY(ivf_check_lists(coarse, nlist));
     if (dim == 0) return fail(VQHIP_ERR_INVALID_INPUT, "dim must be at least 1");
-    VQ_TRY(ivf_check_metric(metric));
+    VQ_TRY(check_metric(metric));
     std::unique_ptr<vqhip_ivfsq> ix(new vqhip_ivfsq());
     VQ_TRY(sq_encode_op(min, max, levels, &ix->op));
     ivf_init(ix.get(), coarse, nlist, dim, metric, dim);
@@ -4251,7 +4188,7 @@ int vqhip_ivfbin_create(float threshold, uint32_t low, uint32_t high, const floa
     if (vq_is_cos(metric)) return fail(VQHIP_ERR_UNSUPPORTED, "cosine is not a function of the Hamming distance alone");
     if (metric != VQHIP_SQUARED_EUCLIDEAN && metric != VQHIP_EUCLIDEAN && metric != VQHIP_MANHATTAN)
         return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
-    VQ_TRY(ivf_check_metric(coarse_metric));
+    VQ_TRY(check_metric(coarse_metric));
     std::unique_ptr<vqhip_ivfbin> ix(new vqhip_ivfbin());
     ivf_init(ix.get(), coarse, nlist, dim, metric, (size_t)bin_words(dim) * 4);
     ix->probe_metric = coarse_metric;

@@ -31,8 +31,8 @@ import numpy as np
 
 from . import _lib
 from .distance import Distance
-from .errors import DimensionMismatch, EmptyInput, InvalidData, InvalidParameter
-from .flat import DEFAULT_MAX_RESULTS, MAX_CANDIDATES, MAX_TOPK, _count, _max_results, _radii
+from ._resident_common import ExactResidentIndex, _check_distance
+from .errors import InvalidData, InvalidParameter
 from .sq import ScalarQuantizer
 
 MAGIC = b"VQSQIDX1"
@@ -41,7 +41,7 @@ _METRIC_NAMES = {_lib.SQUARED_EUCLIDEAN: "squared_euclidean", _lib.EUCLIDEAN: "e
                  _lib.COSINE: "cosine", _lib.COSINE_UNCLAMPED: "cosine_unclamped"}
 
 
-class ScalarIndex:
+class ScalarIndex(ExactResidentIndex):
     """Exact search over `rows` (n, d) float32, stored as the codes of `quantizer`, under `distance` (any metric, cosine
     included; default Euclidean)."""
 
@@ -64,137 +64,27 @@ class ScalarIndex:
     def _setup(self, a: np.ndarray, rows: bool, quantizer, distance) -> None:
         if not isinstance(quantizer, ScalarQuantizer):
             raise InvalidParameter("quantizer", f"expected a ScalarQuantizer, got {type(quantizer).__name__}")
-        if distance is None:
-            distance = Distance.euclidean()
-        if not isinstance(distance, Distance):
-            raise InvalidParameter("distance", f"expected a Distance, got {type(distance).__name__}")
-        what = "rows" if rows else "codes"
-        if a.ndim != 2:
-            raise ValueError("expected a 2D array (n, dim)")
-        if a.shape[0] == 0:
-            raise EmptyInput()
-        if a.shape[1] == 0:
-            raise InvalidParameter(what, "dimension must be at least 1")
-        if a.shape[0] >= 1 << 32:
-            raise InvalidParameter(what, f"at most 2^32 - 1 rows, got {a.shape[0]}")
-        self._src = np.ascontiguousarray(a)
+        distance = _check_distance(distance, Distance.euclidean())
+        self._set_source(a, "rows" if rows else "codes", distance)
         self._rows = rows
-        self._n, self._dim = int(a.shape[0]), int(a.shape[1])
-        self._quantizer, self._distance = quantizer, distance
-        self._ix = None
-
-    def __len__(self) -> int:
-        return self._n
-
-    @property
-    def dim(self) -> int:
-        return self._dim
+        self._quantizer = quantizer
 
     @property
     def quantizer(self) -> ScalarQuantizer:
         return self._quantizer
 
-    @property
-    def distance(self) -> Distance:
-        return self._distance
-
     def __repr__(self) -> str:
         return f"ScalarIndex(n={self._n}, dim={self._dim}, quantizer={self._quantizer!r}, distance={self._distance!r})"
 
-    def _index(self) -> "_lib.SQIndex":
-        if self._ix is None:
-            q = self._quantizer
-            self._ix = _lib.SQIndex(self._src, self._rows, self._n, self._dim, q._min, q._max, q.levels, self._distance.metric)
-            self._src = None  # on the device now
-        return self._ix
-
-    def _queries(self, queries) -> np.ndarray:
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.ndim != 2:
-            raise ValueError("expected a 2D array (nq, dim)")
-        if q.shape[1] != self._dim:
-            raise DimensionMismatch(self._dim, q.shape[1])
-        if q.shape[0] >= 1 << 32:
-            raise InvalidParameter("queries", f"at most 2^32 - 1 queries, got {q.shape[0]}")
-        return q
-
-    def _topk(self, topk, limit: int, what: str) -> int:
-        k = _count(topk, "topk")
-        if not 1 <= k <= limit:
-            raise InvalidParameter("topk", f"must be between 1 and {what}, got {k}")
-        return k
+    def _make_handle(self) -> "_lib.SQIndex":
+        q = self._quantizer
+        return _lib.SQIndex(self._src, self._rows, self._n, self._dim, q._min, q._max, q.levels, self._distance.metric)
 
     def codes(self) -> np.ndarray:
         """the codes, uint8 (n, d): the caller's for an index built from codes and not yet searched, else from the device"""
         if self._ix is None and not self._rows:
             return self._src.copy()
         return self._index().codes()
-
-    def search(self, queries, topk: int = 10):
-        """(nq, d) float32 queries -> (indices uint32 (nq, topk), distances float32 (nq, topk)), nearest first"""
-        q = self._queries(queries)
-        k = self._topk(topk, min(self._n, MAX_TOPK), "min(n, 1024)")
-        if q.shape[0] == 0:
-            return np.empty((0, k), np.uint32), np.empty((0, k), np.float32)
-        return self._index().search(q, k)
-
-    def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int) -> None:
-        """device pointers: queries [nq][d] f32, results [nq][topk] uint32 / f32 (4-byte aligned); asynchronous on the
-        current stream"""
-        k = self._topk(topk, min(self._n, MAX_TOPK), "min(n, 1024)")
-        n_q = _count(nq, "nq")
-        if n_q < 0 or n_q >= 1 << 32:
-            raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
-        self._index().search_device(int(dev_queries), n_q, k, int(dev_idx), int(dev_dist))
-
-    def range_search(self, queries, radius, max_results: int = DEFAULT_MAX_RESULTS):
-        """every row within `radius` of each query, as ``FlatIndex.range_search`` over the dequantized codes: (lims uint64
-        (nq + 1,), idx uint32 (total,), dist float32 (total,)), the hits of a query in ascending row id"""
-        q = self._queries(queries)
-        r = _radii(radius, q.shape[0])
-        m = _max_results(max_results)
-        if q.shape[0] == 0:
-            return np.zeros(1, np.uint64), np.empty(0, np.uint32), np.empty(0, np.float32)
-        return self._index().range_search(q, r, m).read()
-
-    def range_search_device(self, dev_queries: int, nq: int, radius, max_results: int = DEFAULT_MAX_RESULTS) -> "_lib.RangeResult":
-        """`range_search` with the queries [nq][d] f32 at a device pointer (4-byte aligned) and the result left on the
-        device: a RangeResult (.total, .lims, .device_pointers(), .read()).  Returns when the result is complete."""
-        n_q = _count(nq, "nq")
-        if n_q < 0 or n_q >= 1 << 32:
-            raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
-        r = _radii(radius, n_q)
-        m = _max_results(max_results)
-        return self._index().range_search_device(int(dev_queries), n_q, r, m)
-
-    def rerank(self, queries, candidates, topk: int = 10):
-        """per query, the `topk` nearest of its candidate row ids (nq, c), 1 <= c <= 4096, distinct within a query;
-        returns (indices uint32 (nq, topk), distances float32 (nq, topk)) in the order of `search`"""
-        q = self._queries(queries)
-        c = np.asarray(candidates)
-        if c.ndim == 1 and q.shape[0] == 1:
-            c = c[None, :]
-        if c.ndim != 2:
-            raise ValueError("expected candidates as a 2D array (nq, c)")
-        if c.shape[0] != q.shape[0]:
-            raise DimensionMismatch(q.shape[0], c.shape[0])
-        if c.dtype.kind not in "iu":
-            raise InvalidParameter("candidates", f"row ids must be integers, got {c.dtype}")
-        if not 1 <= c.shape[1] <= MAX_CANDIDATES:
-            raise InvalidParameter("candidates", f"between 1 and {MAX_CANDIDATES} per query, got {c.shape[1]}")
-        k = self._topk(topk, c.shape[1], "the number of candidates")
-        if q.shape[0] == 0:
-            return np.empty((0, k), np.uint32), np.empty((0, k), np.float32)
-        lo, hi = int(c.min()), int(c.max())
-        if lo < 0 or hi >= self._n:
-            bad = lo if lo < 0 else hi
-            raise InvalidParameter("candidates", f"row id {bad} is outside [0, {self._n})")
-        s = np.sort(c, axis=1)
-        if c.shape[1] > 1 and bool((s[:, 1:] == s[:, :-1]).any()):
-            raise InvalidParameter("candidates", "row ids must be distinct within a query")
-        return self._index().rerank(q, np.ascontiguousarray(c, dtype=np.uint32), k)
 
     # -- file -------------------------------------------------------------------------------
     def save(self, path) -> None:
