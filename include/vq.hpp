@@ -663,7 +663,8 @@ inline std::vector<std::vector<float>> lbg_quantize(const std::vector<std::vecto
 }
 
 // The result of a range search (include/vqhip.h, vqhip_*_range_search), CSR: the hits of query q are idx / dist
-// [lims[q], lims[q + 1]) -- the rows with D(q, row) <= radius[q], in ascending row id -- and lims[0] = 0.
+// [lims[q], lims[q + 1]) -- the rows with D(q, row) <= radius[q] (the binary indexes: H(q, row) <= radius[q] bits), in
+// ascending row id -- and lims[0] = 0.
 struct RangeResult {
     std::vector<std::uint64_t> lims;  // [nq + 1]
     std::vector<std::uint32_t> idx;   // [total]
@@ -830,6 +831,24 @@ class BinaryIndex : public detail::ResidentIndex<vqhip_binary, vqhip_binary_dest
     }
     std::size_t words_per_row() const { return (dim_ + 31) / 32; }
     const BinaryQuantizer &quantizer() const { return quantizer_; }
+    // every row within radii[q] bits of query q: H(q, row) <= radii[q], H the Hamming distance search selects on (radii
+    // [nq], any value: >= dim returns every row, 0 the exact bit matches); CSR and in ascending row id, dist the distance
+    // search reports for the row.  At most max_results hits in all (more: FfiError).
+    RangeResult hamming_range_search(const float *queries, std::size_t nq, const std::uint32_t *radii,
+                                     std::uint64_t max_results = std::uint64_t(1) << 28) const {
+        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
+        if (max_results == 0) throw VqError::InvalidParameter("max_results", "must be at least 1");
+        if (nq == 0) return RangeResult{std::vector<std::uint64_t>(1, 0), {}, {}};
+        vqhip_range *r = nullptr;
+        detail::check(vqhip_binary_range_search(ix_.get(), queries, (std::uint32_t)nq, radii, max_results, &r));
+        return detail::read_range(r);
+    }
+    RangeResult hamming_range_search(const std::vector<float> &queries, const std::vector<std::uint32_t> &radii,
+                                     std::uint64_t max_results = std::uint64_t(1) << 28) const {
+        if (queries.size() % dim_) throw VqError::DimensionMismatch(dim_, queries.size() % dim_);
+        if (radii.size() != queries.size() / dim_) throw VqError::DimensionMismatch(queries.size() / dim_, radii.size());
+        return hamming_range_search(queries.data(), queries.size() / dim_, radii.data(), max_results);
+    }
     // the packed rows [n][words_per_row()]
     std::vector<std::uint32_t> packed() const {
         std::vector<std::uint32_t> out(n_ * words_per_row());
@@ -1139,6 +1158,19 @@ class IVFBinaryIndex
     const BinaryQuantizer &quantizer() const { return quantizer_; }
     const char *coarse_distance_metric() const { return coarse_distance_.name(); }
     std::size_t words_per_row() const { return (dim_ + 31) / 32; }
+
+    // every row of the nprobe nearest lists within radii[q] bits of query q (BinaryIndex::hamming_range_search's rule
+    // and radii), CSR and in ascending row id; with nprobe == nlist it is BinaryIndex's hamming_range_search.  More than
+    // max_results hits in all: FfiError.
+    RangeResult hamming_range_search(const float *queries, std::size_t nq, const std::uint32_t *radii, std::size_t nprobe,
+                                     std::uint64_t max_results = std::uint64_t(1) << 28) const {
+        if (max_results == 0) throw VqError::InvalidParameter("max_results", "must be at least 1");
+        check_probe(nprobe, nq);
+        if (nq == 0) return RangeResult{std::vector<std::uint64_t>(1, 0), {}, {}};
+        vqhip_range *r = nullptr;
+        detail::check(vqhip_ivfbin_range_search(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, radii, max_results, &r));
+        return detail::read_range(r);
+    }
 
     // rows appended in order: list_ids [n] < nlist, words [n][words_per_row()], pad bits zero; returns the first new row id
     std::size_t add_packed(const std::uint32_t *list_ids, const std::uint32_t *words, std::size_t n) {

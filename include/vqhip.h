@@ -505,6 +505,7 @@ int vqhip_flat_rerank(vqhip_flat *f, const float *queries, uint32_t nq, const ui
 #define VQHIP_BINARY_U8 1
 #define VQHIP_BINARY_PACKED 2
 #define VQHIP_BINARY_MAX_DIM 8192
+#define VQHIP_BINARY_RANGE_BLOCK 8192 /* rows a workgroup of vqhip_binary_range_search counts and fills (k_bin_range) */
 int vqhip_bq_pack(float threshold, const float *x, uint64_t n, uint32_t d, uint32_t *words);
 int vqhip_bq_pack_device(float threshold, const void *dev_x, uint64_t n, uint32_t d, void *dev_words);
 typedef struct vqhip_binary vqhip_binary;
@@ -564,7 +565,8 @@ int vqhip_sqindex_rerank(vqhip_sqindex *x, const float *queries, uint32_t nq, co
 
 /* ---- exact range search over the flat and the scalar index (range.hpp) ------------------------
  * No reference counterpart.  (The inverted-file forms, vqhip_ivfflat_range_search and vqhip_ivfsq_range_search, are
- * declared with their indexes below and return the same vqhip_range.)  Per query q with radius r_q (one f32 per query, radii [nq] in HOST memory in both forms):
+ * declared with their indexes below and return the same vqhip_range, as do the Hamming-radius forms of the two binary
+ * indexes, vqhip_binary_range_search and vqhip_ivfbin_range_search.)  Per query q with radius r_q (one f32 per query, radii [nq] in HOST memory in both forms):
  *   hit     row i is a hit iff D(q, i) <= r_q as an f32 comparison, D being the index's distance exactly as search
  *           reports it (the root for Euclidean, the finished value for cosine).  A NaN distance never hits; r_q = +inf
  *           returns every row whose distance is not NaN; a negative radius returns nothing except where D can be
@@ -597,6 +599,20 @@ int vqhip_range_info(const vqhip_range *r, uint32_t *nq, uint64_t *total);
 int vqhip_range_read(const vqhip_range *r, uint64_t *lims, uint32_t *idx, float *dist);
 int vqhip_range_device(const vqhip_range *r, const void **dev_lims, const void **dev_idx, const void **dev_dist);
 int vqhip_range_destroy(vqhip_range *r);
+
+/* Hamming-radius range search over the binary index (k_binary.hip, k_bin_range; the result object and its rules are
+ * vqhip_flat_range_search's).  The query is stated in bits: query q has a radius h_q, one u32 per query, hradii [nq] in
+ * HOST memory in both forms, and row i is a hit iff H(q, i) <= h_q, H being exactly what vqhip_binary_search selects on
+ * (the query binarised by the index's rule, pad bits zero).  Any u32 is accepted: h_q >= d returns every row, h_q = 0 the
+ * exact bit matches.  dist holds the value search reports for the row, S[H] (sqrtf(S[H]) under Euclidean), as bits; the
+ * table is strictly increasing, so the integer cut is exact and there is no float boundary.  Within a query ascending row
+ * id; the same call returns identical arrays every time.  Checked in this order, before any device work: out, queries /
+ * hradii (NULL with nq > 0), max_results, and only then the index handle.  Batches: 1024 queries, fewer where
+ * nb * ceil(n / VQHIP_BINARY_RANGE_BLOCK) would pass 2^17 for nb > 1. */
+int vqhip_binary_range_search(vqhip_binary *b, const float *queries, uint32_t nq, const uint32_t *hradii, uint64_t max_results,
+                              vqhip_range **out);
+int vqhip_binary_range_search_device(vqhip_binary *b, const void *dev_queries, uint32_t nq, const uint32_t *hradii,
+                                     uint64_t max_results, vqhip_range **out);
 
 /* ---- inverted-file PQ index: search only the probed lists (k_ivf.hip) -----------------------
  * No reference counterpart.  An index holds coarse centroids C [nlist][dim] f32 (1 <= nlist <= 65536), PQ codebooks
@@ -810,6 +826,16 @@ int vqhip_ivfbin_search(vqhip_ivfbin *ix, const float *queries, uint32_t nq, uin
                         uint32_t *idx_out, float *dist_out);
 int vqhip_ivfbin_search_device(vqhip_ivfbin *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
                                void *dev_idx, void *dev_dist);
+/* Hamming-radius range search over the probed lists: row i is a hit of query q iff list[i] is in P(q) and H(q, i) <= h_q
+ * (hradii [nq] u32 in HOST memory, any value; the rules of vqhip_binary_range_search), the result and its order those of
+ * vqhip_ivfflat_range_search.  The stage behind the distances is that call's: the host hands it the f32 radius
+ * reported[min(h_q, dim)] of the index's table, and D <= that radius iff H <= h_q because the reported table is strictly
+ * increasing.  With nprobe == nlist the result equals vqhip_binary_range_search over the words in add order: lims, idx
+ * and distance bits.  The checks run in vqhip_ivfflat_range_search's order; an index without rows gives empty ranges. */
+int vqhip_ivfbin_range_search(vqhip_ivfbin *ix, const float *queries, uint32_t nq, uint32_t nprobe, const uint32_t *hradii,
+                              uint64_t max_results, vqhip_range **out);
+int vqhip_ivfbin_range_search_device(vqhip_ivfbin *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe,
+                                     const uint32_t *hradii, uint64_t max_results, vqhip_range **out);
 
 /* ---- TSVQ ----------------------------------------------------------------------------
  * build replaces TSVQNode::build (src/tsvq.rs:31-115); the tree comes back flattened in

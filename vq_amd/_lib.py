@@ -179,6 +179,10 @@ SIGNATURES = {
     "vqhip_flat_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, _f32p, C.c_uint64, _vpp]),
     "vqhip_sqindex_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, _f32p, C.c_uint64, _vpp]),
     "vqhip_sqindex_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, _f32p, C.c_uint64, _vpp]),
+    "vqhip_binary_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint64, _vpp]),
+    "vqhip_binary_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, _u32p, C.c_uint64, _vpp]),
+    "vqhip_ivfbin_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint64, _vpp]),
+    "vqhip_ivfbin_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _u32p, C.c_uint64, _vpp]),
     "vqhip_range_info": (C.c_int, [_vp, _u32p, _u64p]),
     "vqhip_range_read": (C.c_int, [_vp, _u64p, _u32p, _f32p]),
     "vqhip_range_device": (C.c_int, [_vp, _vpp, _vpp, _vpp]),
@@ -839,9 +843,10 @@ class RangeResult(Handle):
 
 
 def _range_call(fn, raw, queries, nq: int, radii: np.ndarray, max_results: int, *front) -> RangeResult:
-    """one range call of the C ABI; front: the arguments an index has between nq and the radii (nprobe)"""
+    """one range call of the C ABI; front: the arguments an index has between nq and the radii (nprobe); radii: float32
+    distances, or the uint32 Hamming radii of the two binary indexes"""
     h = C.c_void_p()
-    check(fn(raw, queries, int(nq), *front, ptr(radii, _f32p), int(max_results), C.byref(h)))
+    check(fn(raw, queries, int(nq), *front, ptr(radii, _u32p if radii.dtype == np.uint32 else _f32p), int(max_results), C.byref(h)))
     return RangeResult(h)
 
 
@@ -907,6 +912,7 @@ class Flat(_ResidentExactHandle):
 
 
 BINARY_F32, BINARY_U8, BINARY_PACKED = 0, 1, 2
+BINARY_RANGE_BLOCK = 8192  # VQHIP_BINARY_RANGE_BLOCK: rows a workgroup of the Hamming-radius range search counts and fills
 
 
 class Binary(_ResidentHandle):
@@ -933,6 +939,13 @@ class Binary(_ResidentHandle):
         out = np.empty((self.n, self.words), np.uint32)
         check(load().vqhip_binary_packed(self.raw, ptr(out, _u32p)))
         return out
+
+    def hamming_range_search(self, q: np.ndarray, hradii: np.ndarray, max_results: int) -> RangeResult:
+        """hradii: uint32 (nq,), the Hamming radius of every query"""
+        return _range_call(self._fn("range_search"), self.raw, ptr(q, _f32p), q.shape[0], hradii, max_results)
+
+    def hamming_range_search_device(self, dev_queries: int, nq: int, hradii: np.ndarray, max_results: int) -> RangeResult:
+        return _range_call(self._fn("range_search_device"), self.raw, C.c_void_p(dev_queries), nq, hradii, max_results)
 
 
 class SQIndex(_ResidentExactHandle):
@@ -1146,6 +1159,13 @@ class IVFBin(_IVFHandle):
         out = np.empty((self.info()[0], self.words), np.uint32)
         check(load().vqhip_ivfbin_packed(self.raw, ptr(out, _u32p)))
         return out
+
+    def hamming_range_search(self, q: np.ndarray, nprobe: int, hradii: np.ndarray, max_results: int) -> RangeResult:
+        """hradii: uint32 (nq,), the Hamming radius of every query"""
+        return _range_call(self._fn("range_search"), self.raw, ptr(q, _f32p), q.shape[0], hradii, max_results, int(nprobe))
+
+    def hamming_range_search_device(self, dev_queries: int, nq: int, nprobe: int, hradii: np.ndarray, max_results: int) -> RangeResult:
+        return _range_call(self._fn("range_search_device"), self.raw, C.c_void_p(dev_queries), nq, hradii, max_results, int(nprobe))
 
 
 def dequantize_f16(f16) -> np.ndarray:

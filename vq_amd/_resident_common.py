@@ -1,7 +1,8 @@
 """What ``FlatIndex``, ``ScalarIndex`` and ``BinaryIndex`` share: the rows of a caller's array that go to the device on the
 first search, the checks of queries and ``topk``, and search over the device handle.  A subclass keeps its constructors,
 the checks of its own source array, ``_make_handle``, ``__repr__`` and its file layout.  ``ExactResidentIndex`` adds the
-range search and the rerank of the two indexes whose distances are exact (not ``BinaryIndex``)."""
+range search and the rerank of the two indexes whose distances are exact (not ``BinaryIndex``, whose range search takes
+a radius in Hamming bits: ``_hamming_radii``)."""
 from __future__ import annotations
 
 import operator
@@ -47,6 +48,33 @@ def _radii(radius, nq: int) -> np.ndarray:
     if bool(np.isnan(r).any()):
         raise InvalidParameter("radius", f"is NaN for query {int(np.flatnonzero(np.isnan(r))[0])}")
     return np.ascontiguousarray(r)
+
+
+def _hamming_radii(radius, nq: int) -> np.ndarray:
+    """the per-query Hamming radii uint32 (nq,) of a binary index's range search from a non-negative integer or nq of
+    them; floats that are not integral, negatives and values >= 2^32 are refused"""
+    try:
+        r = np.asarray(radius)
+        if r.dtype.kind not in "iufb":
+            raise TypeError
+        r = r.astype(np.float64) if r.dtype.kind == "f" else r.astype(object)
+    except (TypeError, ValueError):
+        raise InvalidParameter("radius", f"must be a non-negative integer or an array of {nq} of them, got {radius!r}") from None
+    if r.ndim > 1:
+        raise InvalidParameter("radius", f"must be a scalar or a 1D array, got {r.ndim} dimensions")
+    flat = r.reshape(-1)
+    for j, v in enumerate(flat.tolist()):
+        where = "" if r.ndim == 0 else f" for query {j}"
+        if isinstance(v, float) and not v.is_integer():  # (NaN and the infinities are not integers either)
+            raise InvalidParameter("radius", f"must be an integer number of bits, got {v!r}{where}")
+        if not 0 <= int(v) < 1 << 32:
+            raise InvalidParameter("radius", f"must be in [0, 2^32), got {int(v)}{where}")
+    out = np.array([int(v) for v in flat.tolist()], dtype=np.uint32)
+    if r.ndim == 0:
+        out = np.full(nq, out[0], np.uint32)
+    if out.shape[0] != nq:
+        raise InvalidParameter("radius", f"one radius or one per query ({nq}), got {out.shape[0]}")
+    return np.ascontiguousarray(out)
 
 
 def _max_results(max_results) -> int:

@@ -6,6 +6,8 @@ u8 codes), row i / dimension t sits in word ``i * W + t // 32``, bit ``t % 32`` 
 and ``D(q, i) = Distance.compute(bq.dequantize(bq.quantize(q)), bq.dequantize(code_i))`` bit for bit for squared
 Euclidean, Euclidean and Manhattan -- a function of the Hamming distance alone, read from a table the library builds.
 Cosine is refused.  The result per query is the ``topk`` rows by ``(D, row id)`` ascending, ties to the lower row.
+``hamming_range_search`` answers the other query, every row within ``radius`` bits, as the CSR triple of
+``FlatIndex.range_search``.
 
 Every argument is checked here before the device is touched; the index goes to the device on the first search (until
 then it refers to the caller's array, which must not change in between).  ``save`` / ``load`` need no device.
@@ -17,7 +19,7 @@ import struct
 import numpy as np
 
 from . import _lib
-from ._resident_common import ResidentIndex, _count
+from ._resident_common import DEFAULT_MAX_RESULTS, ResidentIndex, _count, _hamming_radii, _max_results, _nq
 from .bq import BinaryQuantizer
 from .distance import Distance
 from .errors import DimensionMismatch, InvalidData, InvalidParameter
@@ -132,6 +134,29 @@ class BinaryIndex(ResidentIndex):
         if candidates is not None:
             raise InvalidParameter("candidates", "only with rerank")
         return self._search(q, k)
+
+    def hamming_range_search(self, queries, radius, max_results: int = DEFAULT_MAX_RESULTS):
+        """every row within `radius` bits of each query: row i is a hit of query q iff H(q, i) <= radius[q], H being the
+        Hamming distance `search` selects on (the query binarised by the quantizer's rule).  `radius` is a non-negative
+        integer below 2^32 or nq of them; a radius >= dim returns every row, 0 the exact bit matches.  Returns (lims
+        uint64 (nq + 1,), idx uint32 (total,), dist float32 (total,)): the hits of query q are idx[lims[q]:lims[q + 1]],
+        in ascending row id, and dist is the distance `search` reports for the row.  More than `max_results` hits in
+        all: FfiError (ERR_UNSUPPORTED).  (Named for its unit: a `range_search` takes a radius in the distance.)"""
+        q = self._queries(queries)
+        r = _hamming_radii(radius, q.shape[0])
+        m = _max_results(max_results)
+        if q.shape[0] == 0:
+            return np.zeros(1, np.uint64), np.empty(0, np.uint32), np.empty(0, np.float32)
+        return self._index().hamming_range_search(q, r, m).read()
+
+    def hamming_range_search_device(self, dev_queries: int, nq: int, radius,
+                                    max_results: int = DEFAULT_MAX_RESULTS) -> "_lib.RangeResult":
+        """`hamming_range_search` with the queries [nq][d] f32 at a device pointer (4-byte aligned) and the result left on
+        the device: a RangeResult (.total, .lims, .device_pointers(), .read()).  Returns when the result is complete."""
+        n_q = _nq(nq)
+        r = _hamming_radii(radius, n_q)
+        m = _max_results(max_results)
+        return self._index().hamming_range_search_device(int(dev_queries), n_q, r, m)
 
     def packed(self) -> np.ndarray:
         """the packed rows, uint32 (n, ceil(dim / 32)), from the device"""

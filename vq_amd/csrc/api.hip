@@ -13,6 +13,7 @@
 #include <mutex>
 #include <new>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "adc_plan.hpp"
@@ -3124,14 +3125,18 @@ struct vqhip_range {
     RangeOut r;
 };
 
-// What a range call checks without a device or an index: the pointers it reads and writes, max_results, the radii.
-static int range_args(const void *queries, const float *radii, uint32_t nq, uint64_t max_results, vqhip_range **out) {
+// What a range call checks without a device or an index: the pointers it reads and writes, max_results, the radii
+// (f32 distances; u32 Hamming radii of the binary indexes, where every value is one).
+template <class R>
+static int range_args(const void *queries, const R *radii, uint32_t nq, uint64_t max_results, vqhip_range **out) {
     if (!out) return fail(VQHIP_ERR_NULL_PTR, "out is NULL");
     *out = nullptr;
     if (nq && (!queries || !radii)) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
     if (max_results == 0) return fail(VQHIP_ERR_INVALID_INPUT, "max_results must be at least 1");
-    for (uint32_t q = 0; q < nq; ++q)
-        if (radii[q] != radii[q]) return fail(VQHIP_ERR_INVALID_INPUT, "the radius of query %u is NaN", q);
+    if constexpr (std::is_floating_point<R>::value) {
+        for (uint32_t q = 0; q < nq; ++q)
+            if (radii[q] != radii[q]) return fail(VQHIP_ERR_INVALID_INPUT, "the radius of query %u is NaN", q);
+    }
     return VQHIP_OK;
 }
 
@@ -3241,6 +3246,8 @@ struct vqhip_binary : Resident {
     float thr = 0;
     DevBuf words, table;                 // [n][W] packed rows, S [d + 1]
     DevBuf qw, hist, sel, adc_sel, cnt;  // per-call workspaces
+    DevBuf hcut, range_ws;               // range search: the clamped radii, the stage's counts and offsets
+    std::vector<uint32_t> h_hcut;        // the host side of hcut (the source of an asynchronous copy)
 
     // queries_dev [nq][d] f32 on the device -> [nq][topk] results on the device, enqueued on s in batches of 1024
     int search_enqueue(const float *queries_dev, uint32_t nq, uint32_t topk, uint32_t *idx_dev, float *dist_dev, hipStream_t s) {
@@ -3261,6 +3268,38 @@ struct vqhip_binary : Resident {
         return VQHIP_OK;
     }
 };
+
+// One Hamming-radius range call on a binary index: range_search's front (range_args' checks need no device and no
+// index), the queries (host: through b->q) and the radii, clamped to d and padded by a query group, go up, and
+// launch_binary_range leaves *out complete.
+static int binary_range(vqhip_binary *b, const void *queries, bool host, uint32_t nq, const uint32_t *hradii, uint64_t max_results,
+                        vqhip_range **out) {
+    VQ_TRY(range_args(queries, hradii, nq, max_results, out));
+    if (!b) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (!host && (reinterpret_cast<uintptr_t>(queries) & 3)) return fail(VQHIP_ERR_INVALID_INPUT, "queries are not 4-byte aligned");
+    VQ_TRY(require_gfx950());
+    Entry in(b->sync);
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    std::unique_ptr<vqhip_range> r(new vqhip_range());
+    const float *qdev = reinterpret_cast<const float *>(queries);
+    if (host && nq) {
+        VQ_TRY(b->q.ensure((size_t)nq * b->d * 4));
+        VQ_HIP(hipMemcpyAsync(b->q.p, queries, (size_t)nq * b->d * 4, hipMemcpyHostToDevice, s));
+        qdev = b->q.as<float>();
+    }
+    b->h_hcut.assign((size_t)nq + 32, 0u);
+    for (uint32_t q = 0; q < nq; ++q) b->h_hcut[q] = std::min(hradii[q], b->d);
+    VQ_TRY(b->hcut.ensure(b->h_hcut.size() * 4));
+    VQ_HIP(hipMemcpyAsync(b->hcut.p, b->h_hcut.data(), b->h_hcut.size() * 4, hipMemcpyHostToDevice, s));
+    VQ_TRY(b->qw.ensure((size_t)binary_range_batch(b->n, b->d, nq) * b->W * 4));
+    VQ_TRY(b->range_ws.ensure(binary_range_ws_bytes(b->n, b->d, nq)));
+    VQ_TRY(launch_binary_range(b->words.as<uint32_t>(), b->n, b->d, b->metric, b->table.as<float>(), qdev, b->thr, b->high, nq,
+                               b->hcut.as<uint32_t>(), max_results, b->qw.as<uint32_t>(), b->range_ws.p, &r->r, s));  // (has waited for s)
+    in.synced();
+    *out = r.release();
+    return VQHIP_OK;
+}
 
 static int binary_check(int kind, uint64_t n, uint32_t d, float threshold, uint32_t low, uint32_t high, int metric) {
     if (kind != VQHIP_BINARY_F32 && kind != VQHIP_BINARY_U8 && kind != VQHIP_BINARY_PACKED)
@@ -3411,6 +3450,20 @@ int vqhip_binary_search(vqhip_binary *b, const float *queries, uint32_t nq, uint
 int vqhip_binary_search_device(vqhip_binary *b, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx, void *dev_dist) {
     VQ_API_BEGIN
     return resident_search_device(b, dev_queries, nq, topk, dev_idx, dev_dist);
+    VQ_API_END
+}
+
+int vqhip_binary_range_search(vqhip_binary *b, const float *queries, uint32_t nq, const uint32_t *hradii, uint64_t max_results,
+                              vqhip_range **out) {
+    VQ_API_BEGIN
+    return binary_range(b, queries, true, nq, hradii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_binary_range_search_device(vqhip_binary *b, const void *dev_queries, uint32_t nq, const uint32_t *hradii,
+                                     uint64_t max_results, vqhip_range **out) {
+    VQ_API_BEGIN
+    return binary_range(b, dev_queries, false, nq, hradii, max_results, out);
     VQ_API_END
 }
 
@@ -3785,6 +3838,13 @@ struct IvfExact : IvfLists {
     DevBuf qnorm, inv, lists;      // per-call workspaces
     DevBuf radii, range_ws, stage;  // range search: the radii, the stage's counts and offsets, its staging areas
 
+    // the nq radii of a range call into this->radii
+    int radii_up(const float *r, uint32_t nq, hipStream_t s) {
+        VQ_TRY(radii.ensure((size_t)nq * 4));
+        VQ_HIP(hipMemcpyAsync(radii.p, r, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+        return VQHIP_OK;
+    }
+
     // queries_dev [nq][dim] f32 -> [nq][topk] results on the device, enqueued on s, in ivf_batch's batches;
     // launch(Q, qn or NULL, nb, batch, idx_dev, dist_dev) searches one batch
     template <class Launch>
@@ -3916,6 +3976,23 @@ struct vqhip_ivfbin : IvfLists {
     float thr = 0;
     DevBuf table;            // S [dim + 1]
     DevBuf qw, inv, lists;   // per-call workspaces: the batch's packed queries, the inverted probe table, the lists' state
+    DevBuf radii, range_ws, stage;  // range search: the radii, the stage's counts and offsets, its staging areas
+    std::vector<float> h_radii;     // the host side of radii (the source of an asynchronous copy)
+
+    // The Hamming radii of a range call as the f32 radii of the range stage: r_q = the distance the index reports for
+    // H = min(h_q, dim).  The reported table is strictly increasing, so D <= r_q iff H <= h_q.
+    int radii_up(const uint32_t *h, uint32_t nq, hipStream_t s) {
+        std::vector<float> S(dim + 1);
+        binary_table(dim, low, high, metric, S.data());
+        h_radii.resize(nq);
+        for (uint32_t q = 0; q < nq; ++q) {
+            const float v = S[std::min(h[q], dim)];
+            h_radii[q] = metric == VQHIP_EUCLIDEAN ? sqrtf(v) : v;
+        }
+        VQ_TRY(radii.ensure((size_t)nq * 4));
+        VQ_HIP(hipMemcpyAsync(radii.p, h_radii.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
+        return VQHIP_OK;
+    }
 
     int ready(hipStream_t s) {
         return ivf_ready(this, s, [&] {
@@ -3948,14 +4025,44 @@ struct vqhip_ivfbin : IvfLists {
         }
         return VQHIP_OK;
     }
+    // queries_dev [nq][dim] f32 and the radii (this->radii, [nq]) -> *out, complete on return, in search_enqueue's batches
+    int range_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint64_t max_results, RangeOut *out, hipStream_t s) {
+        VQ_TRY(launch_ivff_range_begin(out, nq, max_results, s));
+        if (n == 0) {  // no rows: every query's range is empty
+            VQ_HIP(hipMemsetAsync(out->lims.p, 0, ((size_t)nq + 1) * 8, s));
+            VQ_HIP(hipStreamSynchronize(s));
+            return VQHIP_OK;
+        }
+        IvfBatch b;
+        VQ_TRY(ivf_batch(this, nq, nprobe, 0, &b));
+        VQ_TRY(qw.ensure((size_t)b.nb_max * nw * 4));
+        VQ_TRY(inv.ensure((size_t)b.nb_max * nprobe * 4));
+        VQ_TRY(lists.ensure(ivfflat_lists_bytes(nlist)));
+        VQ_TRY(state.ensure(knn_state_bytes(b.nb_max)));
+        VQ_TRY(range_ws.ensure(ivff_range_ws_bytes(b.wstride, b.nb_max)));
+        for (uint32_t q0 = 0; q0 < nq; q0 += b.nb_max) {
+            const uint32_t nb = std::min(b.nb_max, nq - q0);
+            const float *Q = queries_dev + (size_t)q0 * dim;
+            VQ_TRY(ivf_probe_enqueue(this, Q, nb, nprobe, probe.as<uint32_t>(), s));
+            VQ_TRY(launch_bq_pack(Q, VQHIP_BINARY_F32, nb, dim, thr, high, qw.as<uint32_t>(), s));
+            VQ_TRY(launch_ivfbin_range(metric, d_payload.as<uint32_t>(), dim, table.as<float>(), d_ids.as<uint32_t>(), n,
+                                       d_off.as<uint32_t>(), nlist, max_list, qw.as<uint32_t>(), probe.as<uint32_t>(), nb, nprobe,
+                                       ivf_chunk((uint64_t)nb * b.per_q), b.wstride, W.as<float>(), pref.as<uint32_t>(), seg.as<uint32_t>(),
+                                       inv.as<uint32_t>(), lists.as<uint32_t>(), state.p, q0, radii.as<float>() + q0, range_ws.p, &stage,
+                                       max_results, out, s));
+        }
+        VQ_HIP(hipStreamSynchronize(s));
+        return VQHIP_OK;
+    }
 };
 
 
-// One range call on an inverted-file flat or scalar index: range_args' checks (no device, no index), nprobe as search
-// checks it, then the index's device, the calling thread's stream and the device state as search builds it; the queries
-// (host: through ix->q) and the radii go up and range_enqueue leaves *out complete.
-template <class T>
-static int ivf_range(T *ix, const void *queries, bool host, uint32_t nq, uint32_t nprobe, const float *radii, uint64_t max_results,
+// One range call on an inverted-file flat, scalar or binary index: range_args' checks (no device, no index), nprobe as
+// search checks it, then the index's device, the calling thread's stream and the device state as search builds it; the
+// queries (host: through ix->q) and the radii (radii_up: f32 distances, or the binary index's u32 Hamming radii as the
+// distances its table reports for them) go up and range_enqueue leaves *out complete.
+template <class T, class R>
+static int ivf_range(T *ix, const void *queries, bool host, uint32_t nq, uint32_t nprobe, const R *radii, uint64_t max_results,
                      vqhip_range **out) {
     VQ_TRY(range_args(queries, radii, nq, max_results, out));
     if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
@@ -3975,8 +4082,7 @@ static int ivf_range(T *ix, const void *queries, bool host, uint32_t nq, uint32_
             VQ_HIP(hipMemcpyAsync(ix->q.p, queries, (size_t)nq * ix->dim * 4, hipMemcpyHostToDevice, s));
             qdev = ix->q.template as<float>();
         }
-        VQ_TRY(ix->radii.ensure((size_t)nq * 4));
-        VQ_HIP(hipMemcpyAsync(ix->radii.p, radii, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+        VQ_TRY(ix->radii_up(radii, nq, s));
         VQ_TRY(ix->range_enqueue(qdev, nq, nprobe, max_results, &r->r, s));  // (every exit of the driver has waited for s)
     } else {
         VQ_TRY(launch_ivff_range_begin(&r->r, 0, max_results, s));
@@ -4306,6 +4412,20 @@ int vqhip_ivfbin_search(vqhip_ivfbin *ix, const float *queries, uint32_t nq, uin
                         float *dist_out) {
     VQ_API_BEGIN
     return ivf_search(ix, queries, nq, nprobe, topk, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_ivfbin_range_search(vqhip_ivfbin *ix, const float *queries, uint32_t nq, uint32_t nprobe, const uint32_t *hradii,
+                              uint64_t max_results, vqhip_range **out) {
+    VQ_API_BEGIN
+    return ivf_range(ix, queries, true, nq, nprobe, hradii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_ivfbin_range_search_device(vqhip_ivfbin *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, const uint32_t *hradii,
+                                     uint64_t max_results, vqhip_range **out) {
+    VQ_API_BEGIN
+    return ivf_range(ix, dev_queries, false, nq, nprobe, hradii, max_results, out);
     VQ_API_END
 }
 

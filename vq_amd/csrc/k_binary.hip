@@ -19,6 +19,7 @@
 //                        sqrtf for Euclidean
 // Roofline: VALU, 2 operations (v_xor, v_bcnt with accumulate) per 32 dimensions per (query, row) pair and scan.
 #include "kernels.hpp"
+#include "range.hpp"
 #include "topk.hpp"
 
 #include <algorithm>
@@ -399,6 +400,238 @@ int launch_binary_search(const uint32_t *P, uint64_t n, uint32_t d, int metric, 
     hipLaunchKernelGGL(k_adc_sort_out, dim3(nb), dim3(1024), (size_t)kAdcCand * 8, stream, cand, adc_sel, topk,
                        metric == VQHIP_EUCLIDEAN ? 1 : 0, idx_out, dist_out);
     VQ_LAUNCH_CHECK("k_adc_sort_out");
+    return VQHIP_OK;
+}
+
+// ------------------------------------------------------------------ Hamming-radius range search ----
+// Row i is a hit of query q iff H(q, i) <= hcut[q] (the caller's radius, clamped to d); the result is range.hpp's CSR,
+// the hits of a query in ascending row id, dist = S[H] (its root under Euclidean).  No H is materialised: the rows are
+// scanned twice, as a search scans them, and range.hpp's protocol runs between the scans.  Per batch of nb queries:
+//   launch_bq_pack        the batch's queries as words Q [nb][W]
+//   k_bin_range<COUNT>    workgroup = (block of kBinRangeRows consecutive rows) x (group of QG queries, their words in
+//                         LDS), k_bin_scan's lane-to-row mapping; every lane counts its hits per query in registers, the
+//                         counts are summed over the wave (shuffles) and the four waves (LDS) into cnt[q][blk]
+//   k_range_scan          (range.hpp) cnt -> off[q][blk] in query-major order, lims, the batch total
+//   range_room            (range.hpp) the 8-byte read, max_results, room for the hits
+//   k_bin_range<FILL>     the count's grid; a workgroup whose QG counts are all zero returns before it reads a row.  The
+//                         others recompute H; a hit of query q goes to base + off[q][blk] + its rank in the block.
+// Ascending row id within a block is the order (step, j, wave, lane) of the scan: a step is kScanBlock * kScanRR rows, row
+// j of a lane is base + j * kScanBlock + tid.  The rank of a hit is therefore
+//   the hits of earlier steps (run[q], uniform: the sum of the steps' totals)
+//   + for j = 1 the step's hits at j = 0, + the hits of earlier waves at the same (step, j)   (wave totals through LDS)
+//   + the hits of lower lanes of its wave at (step, j)                                         (the ballot, masked below the lane)
+// No slot depends on the order of an atomic; there are none.  A step's wave totals go through LDS as one word per (query,
+// wave), j = 0 in the low half and j = 1 in the high half (at most 64 each, their sums over four waves at most 256), in
+// two buffers used in turn: one barrier per step.
+namespace {
+
+enum { BIN_COUNT = 0, BIN_FILL = 1 };
+static_assert(kScanRR == 2, "k_bin_range<FILL> packs the two rows of a lane into one word");
+constexpr uint32_t kBinRangeRows = VQHIP_BINARY_RANGE_BLOCK;      // rows per workgroup: 16 steps
+constexpr uint32_t kBinRangeStep = kScanBlock * kScanRR;          // rows per step: 512
+static_assert(kBinRangeRows % kBinRangeStep == 0 && kBinRangeRows / kBinRangeStep * kScanRR < 256, "a block is whole steps, a lane's hits a byte");
+constexpr uint64_t kBinRangeEntries = 1ull << 17;                 // count entries of a batch of several queries, at most
+
+template <uint32_t QG, bool V4, int MODE>
+__global__ __launch_bounds__(kScanBlock, 3) void k_bin_range(const uint32_t *__restrict__ P, uint64_t n, uint32_t W,
+                                                         const uint32_t *__restrict__ Q, uint32_t nb,
+                                                         const uint32_t *__restrict__ hcut, uint32_t nblk,
+                                                         uint32_t *__restrict__ cnt, const unsigned long long *__restrict__ off,
+                                                         unsigned long long base, const float *__restrict__ S, int root,
+                                                         uint32_t *__restrict__ idx_out, float *__restrict__ dist_out) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t range_lds[];  // qs [QG][W]
+    __shared__ __attribute__((aligned(16))) uint32_t wt[2][QG][4];  // FILL: a step's wave totals; COUNT: wt[0][q][wave]
+    __shared__ uint32_t s_c[QG];                                     // FILL: the block's count per query
+    __shared__ unsigned long long s_at[QG];                          // FILL: the block's first slot per query
+    uint32_t *qs = range_lds;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const uint32_t q0 = blockIdx.y * QG;
+    const uint32_t qn = min(QG, nb - q0);
+    const uint64_t lo = (uint64_t)blockIdx.x * kBinRangeRows, hi = min(n, lo + kBinRangeRows);
+    uint32_t act = 0;  // FILL: bit q set where query q0 + q has hits in this block (uniform)
+    if constexpr (MODE == BIN_FILL) {
+        uint32_t mine = 0;
+        if (tid < QG) {
+            unsigned long long at = 0;
+            if (tid < qn) {
+                const size_t e = (size_t)(q0 + tid) * nblk + blockIdx.x;
+                mine = cnt[e];
+                at = base + off[e];
+            }
+            s_c[tid] = mine;
+            s_at[tid] = at;
+        }
+        if (!__syncthreads_or(mine != 0)) return;  // (uniform) nothing to write: no row is read
+#pragma unroll
+        for (uint32_t q = 0; q < QG; ++q) act |= (s_c[q] != 0 ? 1u : 0u) << q;
+        act = (uint32_t)__builtin_amdgcn_readfirstlane((int)act);
+    }
+    for (uint32_t e = tid; e < QG * W; e += kScanBlock) qs[e] = e / W < qn ? Q[(size_t)(q0 + e / W) * W + e % W] : 0u;
+    uint32_t cut[QG];  // (uniform addresses: hcut has QG entries of padding behind the last query)
+#pragma unroll
+    for (uint32_t q = 0; q < QG; ++q) cut[q] = hcut[q0 + q];
+    __syncthreads();
+    if constexpr (MODE == BIN_COUNT) {
+        uint32_t c[QG / 4];  // the lane's hits per query, four queries to a word: at most 2 * 16 per block, a byte each
+#pragma unroll
+        for (uint32_t q = 0; q < QG / 4; ++q) c[q] = 0;
+        for (uint64_t b0 = lo; b0 < hi; b0 += kBinRangeStep) {
+            uint64_t r[kScanRR];
+            bool ok[kScanRR];
+#pragma unroll
+            for (uint32_t j = 0; j < kScanRR; ++j) {
+                r[j] = b0 + tid + (uint64_t)j * kScanBlock;
+                ok[j] = r[j] < hi;
+            }
+            uint32_t h[kScanRR][QG];
+            bin_hamming<QG, V4>(P, r, ok, W, qs, h);
+#pragma unroll
+            for (uint32_t q = 0; q < QG; ++q)
+#pragma unroll
+                for (uint32_t j = 0; j < kScanRR; ++j) c[q / 4] += (ok[j] && h[j][q] <= cut[q]) ? 1u << (8 * (q % 4)) : 0u;
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < QG; ++q) {
+            uint32_t v = (c[q / 4] >> (8 * (q % 4))) & 0xFFu;
+#pragma unroll
+            for (uint32_t o = 32; o >= 1; o >>= 1) v += (uint32_t)__shfl_xor((int)v, (int)o);
+            if (lane == 0) wt[0][q][wv] = v;
+        }
+        __syncthreads();
+        if (tid < qn) cnt[(size_t)(q0 + tid) * nblk + blockIdx.x] = wt[0][tid][0] + wt[0][tid][1] + wt[0][tid][2] + wt[0][tid][3];
+    } else {
+        const unsigned long long below = (1ull << lane) - 1ull;
+        const uint32_t mk0 = wv > 0 ? 0xFFFFFFFFu : 0u, mk1 = wv > 1 ? 0xFFFFFFFFu : 0u, mk2 = wv > 2 ? 0xFFFFFFFFu : 0u;
+        uint32_t run[QG];  // the block's hits of earlier steps per query (uniform)
+#pragma unroll
+        for (uint32_t q = 0; q < QG; ++q) run[q] = 0;
+        uint32_t buf = 0;
+        for (uint64_t b0 = lo; b0 < hi; b0 += kBinRangeStep, buf ^= 1u) {  // (uniform bounds: every wave meets every barrier)
+            uint64_t r[kScanRR];
+            bool ok[kScanRR];
+#pragma unroll
+            for (uint32_t j = 0; j < kScanRR; ++j) {
+                r[j] = b0 + tid + (uint64_t)j * kScanBlock;
+                ok[j] = r[j] < hi;
+            }
+            uint32_t h[kScanRR][QG];
+            bin_hamming<QG, V4>(P, r, ok, W, qs, h);
+            uint32_t mine = 0, any = 0;  // mine: lane q holds the wave's totals of query q; any: the wave has a hit (uniform)
+#pragma unroll
+            for (uint32_t q = 0; q < QG; ++q) {
+                if (!((act >> q) & 1u)) continue;
+                const unsigned long long m0 = __ballot(ok[0] && h[0][q] <= cut[q]);
+                const unsigned long long m1 = __ballot(ok[1] && h[1][q] <= cut[q]);
+                const uint32_t pk = (uint32_t)__popcll(m0) | ((uint32_t)__popcll(m1) << 16);
+                mine = lane == q ? pk : mine;
+                any |= pk;
+            }
+            if (lane < QG) wt[buf][lane][wv] = mine;
+            if (!__syncthreads_or(any != 0)) continue;  // (uniform) no hit in the step
+#pragma unroll
+            for (uint32_t q = 0; q < QG; ++q) {
+                if (!((act >> q) & 1u)) continue;
+                const uint4 w = *reinterpret_cast<const uint4 *>(&wt[buf][q][0]);
+                const uint32_t pt = (uint32_t)__builtin_amdgcn_readfirstlane((int)(w.x + w.y + w.z + w.w));
+                asm volatile("" ::: "memory");  // (keeps the 32 LDS reads of this loop in their iterations: registers)
+                if (pt == 0) continue;
+                const uint32_t pb = (w.x & mk0) + (w.y & mk1) + (w.z & mk2);  // the earlier waves' totals
+                const uint32_t t0 = pt & 0xFFFFu;
+                const bool hit0 = ok[0] && h[0][q] <= cut[q], hit1 = ok[1] && h[1][q] <= cut[q];
+                const unsigned long long m0 = __ballot(hit0), m1 = __ballot(hit1);
+                if (hit0) {
+                    const unsigned long long slot = s_at[q] + run[q] + (pb & 0xFFFFu) + (uint32_t)__popcll(m0 & below);
+                    const float v = S[h[0][q]];
+                    idx_out[slot] = (uint32_t)r[0];
+                    dist_out[slot] = root ? sqrtf(v) : v;
+                }
+                if (hit1) {
+                    const unsigned long long slot = s_at[q] + run[q] + t0 + (pb >> 16) + (uint32_t)__popcll(m1 & below);
+                    const float v = S[h[1][q]];
+                    idx_out[slot] = (uint32_t)r[1];
+                    dist_out[slot] = root ? sqrtf(v) : v;
+                }
+                run[q] += t0 + (pt >> 16);
+            }
+        }
+    }
+}
+
+template <uint32_t QG, bool V4>
+int bin_range_launch(int mode, dim3 grid, size_t lds, const uint32_t *P, uint64_t n, uint32_t W, const uint32_t *Q, uint32_t nb,
+                     const uint32_t *hcut, uint32_t nblk, uint32_t *cnt, const unsigned long long *off, unsigned long long base,
+                     const float *S, int root, uint32_t *idx_out, float *dist_out, hipStream_t stream) {
+    if (mode == BIN_COUNT)
+        hipLaunchKernelGGL((k_bin_range<QG, V4, BIN_COUNT>), grid, dim3(kScanBlock), lds, stream, P, n, W, Q, nb, hcut, nblk, cnt, off,
+                           base, S, root, idx_out, dist_out);
+    else
+        hipLaunchKernelGGL((k_bin_range<QG, V4, BIN_FILL>), grid, dim3(kScanBlock), lds, stream, P, n, W, Q, nb, hcut, nblk, cnt, off,
+                           base, S, root, idx_out, dist_out);
+    VQ_LAUNCH_CHECK("k_bin_range");
+    return VQHIP_OK;
+}
+
+int bin_range_scan(int mode, const uint32_t *P, uint64_t n, uint32_t W, uint32_t d, const uint32_t *Q, uint32_t nb,
+                   const uint32_t *hcut, uint32_t nblk, uint32_t *cnt, const unsigned long long *off, unsigned long long base,
+                   const float *S, int root, uint32_t *idx_out, float *dist_out, hipStream_t stream) {
+    const uint32_t qg = bin_qg(d);
+    const dim3 grid(nblk, (nb + qg - 1) / qg);
+    const size_t lds = (size_t)qg * W * 4;  // at most 8 KB (QG = 8, W = 256): k_bin_scan's words without its histogram
+    const bool v4 = W % 4 == 0;
+    if (qg == 32)
+        return v4 ? bin_range_launch<32, true>(mode, grid, lds, P, n, W, Q, nb, hcut, nblk, cnt, off, base, S, root, idx_out, dist_out, stream)
+                  : bin_range_launch<32, false>(mode, grid, lds, P, n, W, Q, nb, hcut, nblk, cnt, off, base, S, root, idx_out, dist_out, stream);
+    return v4 ? bin_range_launch<8, true>(mode, grid, lds, P, n, W, Q, nb, hcut, nblk, cnt, off, base, S, root, idx_out, dist_out, stream)
+              : bin_range_launch<8, false>(mode, grid, lds, P, n, W, Q, nb, hcut, nblk, cnt, off, base, S, root, idx_out, dist_out, stream);
+}
+
+uint32_t bin_range_blocks(uint64_t n) { return (uint32_t)((n + kBinRangeRows - 1) / kBinRangeRows); }
+
+}  // namespace
+
+// Queries per batch: 1024 as a search, fewer where the batch would have more than 2^17 count entries (nb * ceil(n / 8192)
+// <= 2^17 whenever nb > 1, in whole query groups while there are any): k_range_scan is one workgroup, and 65 536 entries
+// cost it 0.10 ms.  A single-query batch over n < 2^32 rows has at most 2^19 entries.
+uint32_t binary_range_batch(uint64_t n, uint32_t d, uint32_t nq) {
+    const uint64_t nblk = bin_range_blocks(n);
+    uint64_t nb = std::min<uint64_t>(std::max<uint32_t>(nq, 1), 1024);
+    if (nb * nblk > kBinRangeEntries) {
+        nb = std::max<uint64_t>(1, kBinRangeEntries / nblk);
+        const uint32_t qg = bin_qg(d);
+        if (nb >= qg) nb -= nb % qg;
+    }
+    return (uint32_t)nb;
+}
+
+// total | off [qb][nblk] u64 | cnt [qb][nblk] u32, qb = binary_range_batch(n, d, nq)
+size_t binary_range_ws_bytes(uint64_t n, uint32_t d, uint32_t nq) {
+    return 16 + (size_t)binary_range_batch(n, d, nq) * bin_range_blocks(n) * 12;
+}
+
+int launch_binary_range(const uint32_t *P, uint64_t n, uint32_t d, int metric, const float *S, const float *queries_dev, float thr,
+                        uint32_t high, uint32_t nq, const uint32_t *hcut, uint64_t max_results, uint32_t *qw, void *range_ws,
+                        RangeOut *out, hipStream_t stream) {
+    VQ_TRY(range_begin(out, nq, max_results, stream));
+    const uint32_t W = bin_words(d), nblk = bin_range_blocks(n), qb = binary_range_batch(n, d, nq);
+    const int root = metric == VQHIP_EUCLIDEAN ? 1 : 0;
+    unsigned long long *total = reinterpret_cast<unsigned long long *>(range_ws);
+    unsigned long long *off = total + 2;
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(off + (size_t)qb * nblk);
+    for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
+        const uint32_t nb = std::min(qb, nq - q0);
+        VQ_TRY(launch_bq_pack(queries_dev + (size_t)q0 * d, VQHIP_BINARY_F32, nb, d, thr, high, qw, stream));
+        VQ_TRY(bin_range_scan(BIN_COUNT, P, n, W, d, qw, nb, hcut + q0, nblk, cnt, off, 0, S, root, nullptr, nullptr, stream));
+        hipLaunchKernelGGL(k_range_scan, dim3(1), dim3(1024), 0, stream, cnt, nb, nblk, (unsigned long long)out->total, off,
+                           out->lims.as<unsigned long long>() + q0 + 1, total);
+        VQ_LAUNCH_CHECK("k_range_scan");
+        uint64_t got = 0;
+        VQ_TRY(range_room(total, nb, q0, max_results, out, &got, stream));
+        if (got == 0) continue;
+        VQ_TRY(bin_range_scan(BIN_FILL, P, n, W, d, qw, nb, hcut + q0, nblk, cnt, off, (unsigned long long)out->total, S, root,
+                              out->idx.as<uint32_t>(), out->dist.as<float>(), stream));
+        out->total += got;
+    }
+    VQ_HIP(hipStreamSynchronize(stream));  // *out is complete on return
     return VQHIP_OK;
 }
 

@@ -15,6 +15,8 @@
 //                       query's words in LDS, one position per lane
 //   launch_ivff_select  k_ivff_hist and the selection stage over IvffSource (k_ivfflat.hip)
 // Which kernel computes a pair depends on the batch; H is an integer and both look D up in one table, so the bits do not.
+// A Hamming-radius range search (launch_ivfbin_range) puts the range stage (launch_ivff_range; DESIGN.md sections 17 and
+// 19) behind the same two distance passes (ivfbin_distances), as launch_ivfsq_range does.
 // LW = words per load of the row loader (4, 2 or 1: 16, 8 or 4 bytes), chosen per launch from W and the base pointer.
 #include "common.hpp"
 #include "ivf_plan.hpp"
@@ -246,19 +248,11 @@ int bin_load_width(const uint32_t *P, uint32_t W) {
     return 1;
 }
 
-// One batch of nb <= 1024 queries, packed (Q [nb][bin_words(d)], launch_bq_pack), whose probe lists (probe [nb][nprobe],
-// launch_knn_search over the f32 queries) are on the device.  P / ids / off: the index in list order, P [n][bin_words(d)];
-// S [d + 1] binary_table's; metric the reported distance's (VQHIP_EUCLIDEAN: the root of S).  The workspaces are
-// launch_ivfflat_search's.  Results [nb][topk] on the device.
-int launch_ivfbin_search(int metric, const uint32_t *P, uint32_t d, const float *S, const uint32_t *ids, const uint32_t *off,
-                         uint32_t nlist, uint64_t max_list, const uint32_t *Q, const uint32_t *probe, uint32_t nb, uint32_t nprobe,
-                         uint32_t topk, uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv,
-                         uint32_t *lists, void *state, unsigned long long *cand, uint32_t *idx_out, float *dist_out,
-                         hipStream_t stream) {
-    if (nb == 0) return VQHIP_OK;
-    if (d == 0 || d > VQHIP_BINARY_MAX_DIM) return fail(VQHIP_ERR_INVALID_INPUT, "d %u must be in [1, 8192]", d);
-    IvffPlan p;
-    VQ_TRY(launch_ivff_plan(off, nlist, max_list, probe, nb, nprobe, topk, pref, seg, inv, lists, state, &p, stream));
+// the two distance passes of a batch behind its plan: every D(q, i) of the probed lists into W, the key range into p
+static int ivfbin_distances(const IvffPlan &p, int metric, const uint32_t *P, uint32_t d, const float *S, const uint32_t *off,
+                            uint32_t nlist, const uint32_t *Q, const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t chunk,
+                            uint64_t wstride, float *W, const uint32_t *pref, const uint32_t *seg, const uint32_t *inv,
+                            hipStream_t stream) {
     const uint32_t Wn = bin_words(d);
     const int lw = bin_load_width(P, Wn), root = metric == VQHIP_EUCLIDEAN ? 1 : 0;
     const size_t lds = ((size_t)d + 1) * 4;
@@ -284,7 +278,40 @@ int launch_ivfbin_search(int metric, const uint32_t *P, uint32_t d, const float 
         else scan(k_ivfbin_scan<1>);
         VQ_LAUNCH_CHECK("k_ivfbin_scan");
     }
+    return VQHIP_OK;
+}
+
+// One batch of nb <= 1024 queries, packed (Q [nb][bin_words(d)], launch_bq_pack), whose probe lists (probe [nb][nprobe],
+// launch_knn_search over the f32 queries) are on the device.  P / ids / off: the index in list order, P [n][bin_words(d)];
+// S [d + 1] binary_table's; metric the reported distance's (VQHIP_EUCLIDEAN: the root of S).  The workspaces are
+// launch_ivfflat_search's.  Results [nb][topk] on the device.
+int launch_ivfbin_search(int metric, const uint32_t *P, uint32_t d, const float *S, const uint32_t *ids, const uint32_t *off,
+                         uint32_t nlist, uint64_t max_list, const uint32_t *Q, const uint32_t *probe, uint32_t nb, uint32_t nprobe,
+                         uint32_t topk, uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv,
+                         uint32_t *lists, void *state, unsigned long long *cand, uint32_t *idx_out, float *dist_out,
+                         hipStream_t stream) {
+    if (nb == 0) return VQHIP_OK;
+    if (d == 0 || d > VQHIP_BINARY_MAX_DIM) return fail(VQHIP_ERR_INVALID_INPUT, "d %u must be in [1, 8192]", d);
+    IvffPlan p;
+    VQ_TRY(launch_ivff_plan(off, nlist, max_list, probe, nb, nprobe, topk, pref, seg, inv, lists, state, &p, stream));
+    VQ_TRY(ivfbin_distances(p, metric, P, d, S, off, nlist, Q, probe, nb, nprobe, chunk, wstride, W, pref, seg, inv, stream));
     return launch_ivff_select(p, W, wstride, pref, seg, ids, nb, nprobe, topk, cand, idx_out, dist_out, stream);
+}
+
+// launch_ivfbin_search's batch with the range stage behind the distances (launch_ivff_range, k_ivfflat.hip; DESIGN.md
+// section 19): the arguments of launch_ivfsq_range with the rows and the batch's queries as words.  radii [nb] f32 on the
+// device: the reported distance of each query's Hamming radius, so that D <= radius iff H <= that radius.
+int launch_ivfbin_range(int metric, const uint32_t *P, uint32_t d, const float *S, const uint32_t *ids, uint64_t n, const uint32_t *off,
+                        uint32_t nlist, uint64_t max_list, const uint32_t *Q, const uint32_t *probe, uint32_t nb, uint32_t nprobe,
+                        uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists,
+                        void *state, uint32_t q0, const float *radii, void *range_ws, DevBuf *stage, uint64_t max_results,
+                        RangeOut *out, hipStream_t stream) {
+    if (nb == 0) return VQHIP_OK;
+    if (d == 0 || d > VQHIP_BINARY_MAX_DIM) return fail(VQHIP_ERR_INVALID_INPUT, "d %u must be in [1, 8192]", d);
+    IvffPlan p;
+    VQ_TRY(launch_ivff_plan(off, nlist, max_list, probe, nb, nprobe, 1, pref, seg, inv, lists, state, &p, stream));
+    VQ_TRY(ivfbin_distances(p, metric, P, d, S, off, nlist, Q, probe, nb, nprobe, chunk, wstride, W, pref, seg, inv, stream));
+    return launch_ivff_range(W, wstride, pref, seg, ids, n, nb, nprobe, q0, radii, range_ws, stage, max_results, out, stream);
 }
 
 }  // namespace vqhip

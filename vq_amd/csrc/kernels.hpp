@@ -384,6 +384,12 @@ int launch_ivfsq_range(int metric, const uint8_t *C, uint32_t d, float mn, float
                        const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref,
                        uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state, uint32_t q0, const float *radii, void *range_ws,
                        DevBuf *stage, uint64_t max_results, RangeOut *out, hipStream_t stream);
+// the same behind launch_ivfbin_search's distances: radii [nb] the reported distance of each query's Hamming radius
+int launch_ivfbin_range(int metric, const uint32_t *P, uint32_t d, const float *S, const uint32_t *ids, uint64_t n, const uint32_t *off,
+                        uint32_t nlist, uint64_t max_list, const uint32_t *Q, const uint32_t *probe, uint32_t nb, uint32_t nprobe,
+                        uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists,
+                        void *state, uint32_t q0, const float *radii, void *range_ws, DevBuf *stage, uint64_t max_results,
+                        RangeOut *out, hipStream_t stream);
 
 // exact search and rerank over resident SQ codes (k_sqindex.hip): C [n][d] u8, v(c) = mn + (float)c * step decoded on
 // the fly, rnorm [n] the decoded rows' norms (cosine only).  Batches and workspaces as launch_knn_search / _rerank; the
@@ -452,6 +458,15 @@ size_t binary_hist_bytes(uint32_t qb, uint32_t d);
 int launch_binary_search(const uint32_t *P, uint64_t n, uint32_t d, int metric, const float *S, const uint32_t *Q, uint32_t nb,
                          uint32_t topk, uint32_t *hist, BinSel *sel, uint32_t *adc_sel, uint32_t *cnt,
                          unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream);
+// Hamming-radius range search over the same rows: queries_dev [nq][d] f32 are packed a batch at a
+// time (binary_range_batch queries) into qw [batch][W]; hcut [nq + 32] on the device, the radii clamped to d with 32
+// entries of padding behind them; range_ws >= binary_range_ws_bytes(n, d, nq).  Row i is a hit of query q iff H <= hcut[q];
+// *out as launch_knn_range leaves it, complete on return.  More than max_results hits: VQHIP_ERR_UNSUPPORTED.
+uint32_t binary_range_batch(uint64_t n, uint32_t d, uint32_t nq);
+size_t binary_range_ws_bytes(uint64_t n, uint32_t d, uint32_t nq);
+int launch_binary_range(const uint32_t *P, uint64_t n, uint32_t d, int metric, const float *S, const float *queries_dev, float thr,
+                        uint32_t high, uint32_t nq, const uint32_t *hcut, uint64_t max_results, uint32_t *qw, void *range_ws,
+                        RangeOut *out, hipStream_t stream);
 
 int launch_synth_uniform(float *X, uint64_t n, uint32_t d, uint64_t seed, uint64_t row_offset,
                          hipStream_t stream);

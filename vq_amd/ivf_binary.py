@@ -11,7 +11,9 @@ coarse_distance).search(q, nprobe)`` for the float32 query -- it is never binari
 whose list is in ``P(q)``, ``H(q, i) = popcount(bits(q) xor words[i])``, ``D(q, i)`` ``BinaryIndex``'s reported distance
 for ``H`` and the result the ``topk`` rows of ``S(q)`` by ``(D, row id)`` ascending, which is ``(H, row id)``.  With
 ``nprobe == nlist`` the result equals ``BinaryIndex.from_packed(words, dim, quantizer, distance).search`` -- indices,
-and distances as uint32 bits.  Slots past ``|S(q)|`` hold id ``0xFFFFFFFF`` and distance ``+inf``.  Constructing,
+and distances as uint32 bits.  Slots past ``|S(q)|`` hold id ``0xFFFFFFFF`` and distance ``+inf``.
+``hamming_range_search`` returns every row of ``S(q)`` with ``H(q, i) <= radius`` instead, in ascending row id; with
+``nprobe == nlist`` it equals ``BinaryIndex.hamming_range_search``.  Constructing,
 ``add_packed``, ``add_codes``, saving and loading need no GPU; ``add`` and ``add_rows`` pack on the device; the device
 state is built by the first probe or search and follows every later add.
 
@@ -37,7 +39,9 @@ import struct
 import numpy as np
 
 from . import _lib
-from ._ivf_common import MAX_NLIST, IVFIndexBase, _Reader, _check_coarse, _check_distance, _check_file_lists, _train_coarse
+from ._ivf_common import (MAX_NLIST, IVFIndexBase, _count, _Reader, _check_coarse, _check_distance, _check_file_lists,
+                          _train_coarse)
+from ._resident_common import DEFAULT_MAX_RESULTS, _hamming_radii, _max_results
 from .binary import MAX_DIM, _check_params, _pad_ok, pack_bits, words_per_row
 from .bq import BinaryQuantizer
 from .distance import Distance
@@ -163,6 +167,34 @@ class IVFBinaryIndex(IVFIndexBase):
             self._ix = ix
             self._host_words = None
         return self._ix
+
+    # -- range search ----------------------------------------------------------------------
+    def hamming_range_search(self, queries, radius, nprobe: int = 8, max_results: int = DEFAULT_MAX_RESULTS):
+        """every row of the nprobe nearest lists within `radius` bits of each query: row i is a hit of query q iff its
+        list is probed and H(q, i) <= radius[q] (`BinaryIndex.hamming_range_search`'s rule and radii).  Returns (lims
+        uint64 (nq + 1,), idx uint32 (total,), dist float32 (total,)): the hits of query q are idx[lims[q]:lims[q + 1]],
+        in ascending row id, dist the distance `search` reports.  With nprobe == nlist the result equals
+        ``BinaryIndex.from_packed(words, ...).hamming_range_search``.  More than `max_results` hits in all: FfiError
+        (ERR_UNSUPPORTED)."""
+        q = self._queries(queries)
+        r = _hamming_radii(radius, q.shape[0])
+        p = self._nprobe(nprobe)
+        m = _max_results(max_results)
+        if q.shape[0] == 0:
+            return np.zeros(1, np.uint64), np.empty(0, np.uint32), np.empty(0, np.float32)
+        return self._handle().hamming_range_search(q, p, r, m).read()
+
+    def hamming_range_search_device(self, dev_queries: int, nq: int, radius, nprobe: int = 8,
+                                    max_results: int = DEFAULT_MAX_RESULTS) -> "_lib.RangeResult":
+        """`hamming_range_search` with the queries [nq][dim] f32 at a device pointer (4-byte aligned) and the result left
+        on the device: a RangeResult (.total, .lims, .device_pointers(), .read()).  Returns when the result is complete."""
+        n_q = _count(nq, "nq")
+        if n_q < 0 or n_q >= 1 << 32:
+            raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
+        r = _hamming_radii(radius, n_q)
+        p = self._nprobe(nprobe)
+        m = _max_results(max_results)
+        return self._handle().hamming_range_search_device(int(dev_queries), n_q, p, r, m)
 
     def close(self) -> None:
         """release the handle and its device state (the next probe or search builds it again); the words stay"""
