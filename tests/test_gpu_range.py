@@ -276,7 +276,7 @@ def test_device_form_at_an_offset_pointer(which):
 
 
 @pytest.mark.parametrize("metric", K.METRICS)
-@pytest.mark.parametrize("d", [3, 16, 100])  # the byte, the 16-byte and the 4-byte loader of k_sq_dist
+@pytest.mark.parametrize("d", [3, 16, 100])  # the byte, the 16-byte and the 4-byte loader of SqRows (k_knn_dist)
 def test_scalar_index_matches_statement_and_flat(metric, d):
     import vq_amd
 

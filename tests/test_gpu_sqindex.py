@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 F = np.float32
 NAMES = ["squared_euclidean", "euclidean", "manhattan", "cosine", "cosine_unclamped"]
-DIMS = [1, 3, 7, 31, 32, 33, 64, 100, 128, 129, 768]
+DIMS = [1, 3, 7, 31, 32, 33, 48, 64, 100, 128, 129, 768]
 NS = [1, 37, 63, 64, 65, 1037, 4099]
 
 

@@ -9,8 +9,9 @@
 // Schedule of one batch (launch_ivfbin_search): section 14's, step for step --
 //   launch_bq_pack      the batch's queries as words Q [nb][W] (k_binary.hip)
 //   launch_ivff_plan    k_ivff_plan, k_ivff_lists, k_ivff_invert (k_ivfflat.hip): pref / seg, cnt, the inverted probe table
-//   k_ivfbin_tile       k_ivff_tile's work item with both sides as words: an 8 x 4 register block of H over chunks of 32
-//                       words in LDS, three 16-byte LDS reads per 64 VALU operations
+//   k_ivfbin_tile       k_ivff_tile's work item and write-back (ivf_tile_open, ivf_tile_store, knn_key_range) with both sides
+//                       as words: an 8 x 4 register block of H over chunks of 32 words in LDS, three 16-byte LDS reads per
+//                       64 VALU operations
 //   k_ivfbin_scan       the lists probed by fewer than kIvffTileMin queries: one query x one chunk of positions, the
 //                       query's words in LDS, one position per lane
 //   launch_ivff_select  k_ivff_hist and the selection stage over IvffSource (k_ivfflat.hip)
@@ -19,9 +20,8 @@
 // 19) behind the same two distance passes (ivfbin_distances), as launch_ivfsq_range does.
 // LW = words per load of the row loader (4, 2 or 1: 16, 8 or 4 bytes), chosen per launch from W and the base pointer.
 #include "common.hpp"
-#include "ivf_plan.hpp"
+#include "ivf_tile.hpp"
 #include "kernels.hpp"
-#include "knn_tile.hpp"
 
 namespace vqhip {
 namespace {
@@ -64,33 +64,11 @@ __global__ __launch_bounds__(256) void k_ivfbin_tile(const uint32_t *__restrict_
     extern __shared__ float s_tab[];  // [d + 1]
     __shared__ __attribute__((aligned(16))) uint32_t qs[WC][TQ + 4];
     __shared__ __attribute__((aligned(16))) uint32_t rs[WC][TR + 4];
-    __shared__ uint32_t s_q[TQ], s_p[TQ];  // the tile's queries (0xFFFFFFFF: none) and the first position of the list in each
-    const uint32_t tile = blockIdx.x;
-    if (tile >= tstart[nlist]) return;  // (uniform)
-    uint32_t l = 0;
-    {  // the last list whose first tile is <= tile, and that has tiles (tstart is non-decreasing)
-        uint32_t lo = 0, hi = nlist;
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (tstart[mid] <= tile) lo = mid;
-            else hi = mid;
-        }
-        l = lo;
-    }
+    __shared__ uint32_t s_q[TQ], s_p[TQ];
+    uint32_t row0, nrows;
+    if (!ivf_tile_open(off, nlist, cnt, lstart, tstart, inv, pref, nprobe, s_q, s_p, &row0, &nrows)) return;
     const uint32_t tid = threadIdx.x, rg = tid & 15u, qg = tid >> 4;
-    const uint32_t e0 = (tile - tstart[l]) * TQ, en = min(TQ, cnt[l] - e0);
-    const uint32_t row0 = off[l], nrows = off[l + 1] - row0;
     const uint32_t *Pl = P + (uint64_t)row0 * Wn;  // the list's run
-    if (tid < TQ) {
-        uint32_t q = 0xFFFFFFFFu, p = 0;
-        if (tid < en) {
-            const uint32_t e = inv[lstart[l] + e0 + tid];
-            q = e / nprobe;
-            p = pref[(size_t)q * (nprobe + 1) + (e - q * nprobe)];
-        }
-        s_q[tid] = q;
-        s_p[tid] = p;
-    }
     bin_table_load(s_tab, S, d, root);
     __syncthreads();
     uint32_t lo[RQ], hi[RQ], qi[RQ];
@@ -115,7 +93,7 @@ __global__ __launch_bounds__(256) void k_ivfbin_tile(const uint32_t *__restrict_
             for (uint32_t e = 0; e < TQ * WC / 256; ++e) {
                 const uint32_t idx = tid + 256 * e, r = idx / WC, c = idx % WC;
                 const uint32_t q = s_q[r];
-                qs[c][r] = (q != 0xFFFFFFFFu && c < tc) ? Q[(size_t)q * Wn + t0 + c] : 0u;
+                qs[c][r] = (q != kKnnNone && c < tc) ? Q[(size_t)q * Wn + t0 + c] : 0u;
             }
 #pragma unroll
             for (uint32_t e = 0; e < TR * WC / LW / 256; ++e) {  // (64 rows x 32 / LW loads: 2, 4 or 8 per lane)
@@ -148,37 +126,10 @@ __global__ __launch_bounds__(256) void k_ivfbin_tile(const uint32_t *__restrict_
             }
         }
         const uint32_t rb = r0 + rg * RR;
-#pragma unroll
-        for (uint32_t a = 0; a < RQ; ++a) {
-            if (qi[a] == 0xFFFFFFFFu) continue;
-            float *wq = W + (size_t)qi[a] * wstride;
-            const uint64_t p0 = (uint64_t)s_p[qg * RQ + a] + rb;
-#pragma unroll
-            for (uint32_t b = 0; b < RR; ++b) {
-                if (rb + b >= nrows || p0 + b >= wstride) continue;
-                const float dv = s_tab[min(acc[a][b], d)];  // (H <= d: the pad bits of both sides are zero)
-                const uint32_t key = adc_key(dv);
-                if (key != 0xFFFFFFFFu) {
-                    lo[a] = min(lo[a], key);
-                    hi[a] = max(hi[a], key);
-                }
-                wq[p0 + b] = dv;  // (a run starts at any position: no 16-byte stores)
-            }
-        }
+        // (H <= d: the pad bits of both sides are zero)
+        ivf_tile_store(qi, s_p, rb, nrows, wstride, W, lo, hi, [&](uint32_t a, uint32_t b) { return s_tab[min(acc[a][b], d)]; });
     }
-    // the 16 lanes of a query group (lane bits 0-3) hold all of the workgroup's rows for its 8 queries
-#pragma unroll
-    for (uint32_t a = 0; a < RQ; ++a) {
-#pragma unroll
-        for (uint32_t o = 1; o < 16; o <<= 1) {
-            lo[a] = min(lo[a], (uint32_t)__shfl_xor((int)lo[a], (int)o));
-            hi[a] = max(hi[a], (uint32_t)__shfl_xor((int)hi[a], (int)o));
-        }
-        if (rg == 0 && qi[a] != 0xFFFFFFFFu && lo[a] <= hi[a]) {
-            atomicMin(&kmin[qi[a]], lo[a]);
-            atomicMax(&kmax[qi[a]], hi[a]);
-        }
-    }
+    knn_key_range(lo, hi, [&](uint32_t a) { return qi[a]; }, kmin, kmax);
 }
 
 // block (x = chunk of positions, y = query): the positions of the chunk whose list fewer than kIvffTileMin queries probe,

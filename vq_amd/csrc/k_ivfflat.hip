@@ -12,8 +12,8 @@
 //                  tiles; none for a list probed by fewer than kIvffTileMin queries)
 //   k_ivff_invert  the inverted probe table: inv[lstart[l] ..] = the (query, slot) pairs that probe l, in any order
 //   k_ivff_tile    work item = one list x one tile of 128 of its queries x a column of tiles of 64 of its rows: k_knn_dist's
-//                  8 x 4 register block over 32-dimension LDS chunks, the queries gathered through inv, every D written to
-//                  W[q][pref[q][slot] + r]; a list's rows are read once per query tile
+//                  8 x 4 register block over 32-dimension LDS chunks (knn_tile_pass), the queries gathered through inv,
+//                  every D written to W[q][pref[q][slot] + r]; a list's rows are read once per query tile
 //   k_ivff_scan    the lists probed by fewer than kIvffTileMin queries: work item = one query x one chunk of its positions,
 //                  the query in LDS, one position per lane, the same per-pair operation order
 //   k_ivff_hist    the key-space histogram of W[q][0 .. |S(q)|) over the range the two kernels found (integer atomics)
@@ -21,25 +21,21 @@
 // Which kernel computes a pair depends on the batch; both run one pair's operations in one order, so the bits do not.
 // A range search (launch_ivfflat_range) runs the plan and the two distance kernels as they are and then the range stage
 // over W (ivf_range.hpp) in place of the histogram and the selection.
+// The two distance kernels and ivff_distances live in ivf_tile.hpp, templated on the row source, and serve the SQ codes
+// of k_ivfsq.hip too; this file instantiates them over dense f32 / f16 rows and holds the stages every inverted-file
+// search over W shares (plan, lists, inverted table, histogram, selection, range).
 #include "common.hpp"
 #include "ivf_plan.hpp"
 #include "ivf_range.hpp"
+#include "ivf_tile.hpp"
 #include "kernels.hpp"
 #include "knn_tile.hpp"
 #include "topk.hpp"
-
-#include <type_traits>
 
 #pragma clang fp contract(off)
 
 namespace vqhip {
 namespace {
-
-template <typename RT>
-__device__ __forceinline__ float ivff_widen(RT v) {
-    if constexpr (std::is_same<RT, uint16_t>::value) return (float)__builtin_bit_cast(_Float16, v);  // exact
-    else return v;
-}
 
 __device__ __forceinline__ bool ivff_real(uint32_t l, uint32_t nlist, const uint32_t *__restrict__ off) {
     return l < nlist && off[l + 1] > off[l];
@@ -102,229 +98,6 @@ __global__ __launch_bounds__(1024) void k_ivff_invert(const uint32_t *__restrict
     if (at < lstart[l + 1] - lstart[l]) inv[lstart[l] + at] = q * nprobe + t;  // (always: fill counts what cnt counted)
 }
 
-// block (x = query tile of the batch's tstart[nlist] tiles, y = column of row tiles): k_knn_dist over the rows of one list
-// and the up to 128 queries of one tile of its run of inv.  Blocks past the last tile leave at once.
-template <int METRIC, typename RT>
-__global__ __launch_bounds__(256) void k_ivff_tile(const float *__restrict__ Q, const RT *__restrict__ X, uint32_t d,
-                                                   const float *__restrict__ qnorm, const float *__restrict__ rnorm,
-                                                   const uint32_t *__restrict__ off, uint32_t nlist, const uint32_t *__restrict__ cnt,
-                                                   const uint32_t *__restrict__ lstart, const uint32_t *__restrict__ tstart,
-                                                   const uint32_t *__restrict__ inv, const uint32_t *__restrict__ pref,
-                                                   uint32_t nprobe, uint64_t wstride, float *__restrict__ W,
-                                                   uint32_t *__restrict__ kmin, uint32_t *__restrict__ kmax) {
-    constexpr uint32_t RQ = kKnnRQ, RR = kKnnRR, TQ = kKnnTQ, TR = kKnnTR, KC = kKnnKC;
-    __shared__ __attribute__((aligned(16))) float qs[KC][TQ + 4];
-    __shared__ __attribute__((aligned(16))) float rs[KC][TR + 4];
-    __shared__ uint32_t s_q[TQ], s_p[TQ];  // the tile's queries (0xFFFFFFFF: none) and the first position of the list in each
-    const uint32_t tile = blockIdx.x;
-    if (tile >= tstart[nlist]) return;  // (uniform)
-    uint32_t l = 0;
-    {  // the last list whose first tile is <= tile, and that has tiles (tstart is non-decreasing)
-        uint32_t lo = 0, hi = nlist;
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (tstart[mid] <= tile) lo = mid;
-            else hi = mid;
-        }
-        l = lo;
-    }
-    const uint32_t tid = threadIdx.x, rg = tid & 15u, qg = tid >> 4;
-    const uint32_t e0 = (tile - tstart[l]) * TQ, en = min(TQ, cnt[l] - e0);
-    const uint32_t row0 = off[l], nrows = off[l + 1] - row0;
-    if (tid < TQ) {
-        uint32_t q = 0xFFFFFFFFu, p = 0;
-        if (tid < en) {
-            const uint32_t e = inv[lstart[l] + e0 + tid];
-            q = e / nprobe;
-            p = pref[(size_t)q * (nprobe + 1) + (e - q * nprobe)];
-        }
-        s_q[tid] = q;
-        s_p[tid] = p;
-    }
-    __syncthreads();
-    float qn[RQ];
-    uint32_t lo[RQ], hi[RQ], qi[RQ];
-#pragma unroll
-    for (uint32_t a = 0; a < RQ; ++a) {
-        qi[a] = s_q[qg * RQ + a];
-        qn[a] = (vq_is_cos(METRIC) && qi[a] != 0xFFFFFFFFu) ? qnorm[qi[a]] : 1.0f;
-        lo[a] = 0xFFFFFFFFu;
-        hi[a] = 0u;
-    }
-    const uint32_t nrt = (nrows + TR - 1) / TR;
-    for (uint32_t rt = blockIdx.y; rt < nrt; rt += gridDim.y) {
-        const uint32_t r0 = rt * TR;  // (within the list)
-        float acc[RQ][RR];
-#pragma unroll
-        for (uint32_t a = 0; a < RQ; ++a)
-#pragma unroll
-            for (uint32_t b = 0; b < RR; ++b) acc[a][b] = -0.0f;
-        for (uint32_t t0 = 0; t0 < d; t0 += KC) {
-            const uint32_t tc = min(KC, d - t0);
-            __syncthreads();  // the previous chunk's readers are done
-#pragma unroll
-            for (uint32_t e = 0; e < TQ * KC / 256; ++e) {
-                const uint32_t idx = tid + 256 * e, r = idx / KC, c = idx % KC;
-                const uint32_t q = s_q[r];
-                qs[c][r] = (q != 0xFFFFFFFFu && c < tc) ? Q[(size_t)q * d + t0 + c] : 0.0f;
-            }
-#pragma unroll
-            for (uint32_t e = 0; e < TR * KC / 256; ++e) {
-                const uint32_t idx = tid + 256 * e, r = idx / KC, c = idx % KC;
-                rs[c][r] = (r0 + r < nrows && c < tc) ? ivff_widen(X[((uint64_t)row0 + r0 + r) * d + t0 + c]) : 0.0f;
-            }
-            __syncthreads();
-            auto advance = [&](uint32_t t) {
-                const float4 qa = *reinterpret_cast<const float4 *>(&qs[t][qg * RQ]);
-                const float4 qb = *reinterpret_cast<const float4 *>(&qs[t][qg * RQ + 4]);
-                const float4 rv = *reinterpret_cast<const float4 *>(&rs[t][rg * RR]);
-                const float qv[RQ] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
-                const float rr[RR] = {rv.x, rv.y, rv.z, rv.w};
-#pragma unroll
-                for (uint32_t a = 0; a < RQ; ++a)
-#pragma unroll
-                    for (uint32_t b = 0; b < RR; ++b) acc[a][b] = knn_step<METRIC>(acc[a][b], qv[a], rr[b]);
-            };
-            if (tc == KC) {  // (unrolled by 8, as k_knn_dist: fully, the LDS reads cost a wave per SIMD)
-#pragma unroll 8
-                for (uint32_t t = 0; t < KC; ++t) advance(t);
-            } else {
-                for (uint32_t t = 0; t < tc; ++t) advance(t);
-            }
-        }
-        const uint32_t rb = r0 + rg * RR;
-        float rn[RR];
-#pragma unroll
-        for (uint32_t b = 0; b < RR; ++b) rn[b] = (vq_is_cos(METRIC) && rb + b < nrows) ? rnorm[(uint64_t)row0 + rb + b] : 1.0f;
-#pragma unroll
-        for (uint32_t a = 0; a < RQ; ++a) {
-            if (qi[a] == 0xFFFFFFFFu) continue;
-            float *wq = W + (size_t)qi[a] * wstride;
-            const uint64_t p0 = (uint64_t)s_p[qg * RQ + a] + rb;
-#pragma unroll
-            for (uint32_t b = 0; b < RR; ++b) {
-                if (rb + b >= nrows || p0 + b >= wstride) continue;
-                const float dv = knn_finish<METRIC>(acc[a][b], qn[a], rn[b]);
-                const uint32_t key = adc_key(dv);
-                if (key != 0xFFFFFFFFu) {
-                    lo[a] = min(lo[a], key);
-                    hi[a] = max(hi[a], key);
-                }
-                wq[p0 + b] = dv;  // (a run starts at any position: no 16-byte stores)
-            }
-        }
-    }
-    // the 16 lanes of a query group (lane bits 0-3) hold all of the workgroup's rows for its 8 queries
-#pragma unroll
-    for (uint32_t a = 0; a < RQ; ++a) {
-#pragma unroll
-        for (uint32_t o = 1; o < 16; o <<= 1) {
-            lo[a] = min(lo[a], (uint32_t)__shfl_xor((int)lo[a], (int)o));
-            hi[a] = max(hi[a], (uint32_t)__shfl_xor((int)hi[a], (int)o));
-        }
-        if (rg == 0 && qi[a] != 0xFFFFFFFFu && lo[a] <= hi[a]) {
-            atomicMin(&kmin[qi[a]], lo[a]);
-            atomicMax(&kmax[qi[a]], hi[a]);
-        }
-    }
-}
-
-// four consecutive elements of a row from element e (e and d multiples of 4: an 8- or 16-byte load)
-template <typename RT>
-__device__ __forceinline__ void ivff_load4(const RT *__restrict__ x, uint64_t e, float (&v)[4]) {
-    if constexpr (std::is_same<RT, uint16_t>::value) {
-        const uint2 w = *reinterpret_cast<const uint2 *>(x + e);
-        v[0] = ivff_widen<uint16_t>((uint16_t)(w.x & 0xFFFFu)), v[1] = ivff_widen<uint16_t>((uint16_t)(w.x >> 16));
-        v[2] = ivff_widen<uint16_t>((uint16_t)(w.y & 0xFFFFu)), v[3] = ivff_widen<uint16_t>((uint16_t)(w.y >> 16));
-    } else {
-        const float4 w = *reinterpret_cast<const float4 *>(x + e);
-        v[0] = w.x, v[1] = w.y, v[2] = w.z, v[3] = w.w;
-    }
-}
-
-// block (x = chunk of positions, y = query): the positions of the chunk whose list fewer than kIvffTileMin queries probe,
-// one per lane and pass; the query's dimensions in LDS, kIvffQC at a time.  Items past |S(q)| leave at once.
-template <int METRIC, typename RT>
-__global__ __launch_bounds__(256) void k_ivff_scan(const float *__restrict__ Q, const RT *__restrict__ X, uint32_t d,
-                                                   const float *__restrict__ qnorm, const float *__restrict__ rnorm,
-                                                   const uint32_t *__restrict__ probe, const uint32_t *__restrict__ cnt,
-                                                   const uint32_t *__restrict__ pref, const uint32_t *__restrict__ seg,
-                                                   uint32_t nprobe, uint32_t chunk, uint64_t wstride, float *__restrict__ W,
-                                                   uint32_t *__restrict__ kmin, uint32_t *__restrict__ kmax) {
-    __shared__ __attribute__((aligned(16))) float s_x[kIvffQC];
-    const uint32_t q = blockIdx.y, tid = threadIdx.x;
-    const uint32_t *pq = pref + (size_t)q * (nprobe + 1);
-    const uint32_t *sq = seg + (size_t)q * nprobe;
-    const uint32_t *lq = probe + (size_t)q * nprobe;
-    const uint32_t total = (uint32_t)min((uint64_t)pq[nprobe], wstride);
-    const uint64_t p0 = (uint64_t)blockIdx.x * chunk;
-    if (p0 >= total) return;  // (uniform)
-    const uint32_t p1 = (uint32_t)min((uint64_t)total, p0 + chunk);
-    const float *x = Q + (size_t)q * d;
-    const float qn = vq_is_cos(METRIC) ? qnorm[q] : 1.0f;
-    const bool once = d <= kIvffQC;  // the whole query stays in LDS
-    const bool vec = (d & 3u) == 0;
-    if (once) {
-        for (uint32_t t = tid; t < d; t += 256) s_x[t] = x[t];
-        __syncthreads();
-    }
-    float *wq = W + (size_t)q * wstride;
-    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
-    for (uint32_t base = (uint32_t)p0; base < p1; base += 256) {
-        const uint32_t pos = base + tid;
-        bool mine = false;
-        uint64_t row = 0;
-        if (pos < p1) {
-            const uint32_t slot = ivf_slot(pq, nprobe, pos);
-            mine = cnt[lq[slot]] < kIvffTileMin;  // (a position exists: its list is real)
-            row = (uint64_t)sq[slot] + (pos - pq[slot]);
-        }
-        if (!__syncthreads_or(mine)) continue;  // (uniform)
-        const RT *r = X + row * d;
-        float acc = -0.0f;
-        for (uint32_t t0 = 0; t0 < d; t0 += kIvffQC) {
-            const uint32_t tc = min(kIvffQC, d - t0);
-            if (!once) {
-                __syncthreads();
-                for (uint32_t t = tid; t < tc; t += 256) s_x[t] = x[t0 + t];
-                __syncthreads();
-            }
-            if (!mine) continue;
-            if (vec) {
-                for (uint32_t t = 0; t < tc; t += 4) {
-                    float v[4];
-                    ivff_load4<RT>(r, (uint64_t)t0 + t, v);
-                    const float4 xv = *reinterpret_cast<const float4 *>(&s_x[t]);
-                    acc = knn_step<METRIC>(acc, xv.x, v[0]);
-                    acc = knn_step<METRIC>(acc, xv.y, v[1]);
-                    acc = knn_step<METRIC>(acc, xv.z, v[2]);
-                    acc = knn_step<METRIC>(acc, xv.w, v[3]);
-                }
-            } else {
-                for (uint32_t t = 0; t < tc; ++t) acc = knn_step<METRIC>(acc, s_x[t], ivff_widen(r[(uint64_t)t0 + t]));
-            }
-        }
-        if (mine) {
-            const float dv = knn_finish<METRIC>(acc, qn, vq_is_cos(METRIC) ? rnorm[row] : 1.0f);
-            const uint32_t key = adc_key(dv);
-            if (key != 0xFFFFFFFFu) {
-                lo = min(lo, key);
-                hi = max(hi, key);
-            }
-            wq[pos] = dv;
-        }
-    }
-#pragma unroll
-    for (uint32_t o = 1; o < 64; o <<= 1) {
-        lo = min(lo, (uint32_t)__shfl_xor((int)lo, (int)o));
-        hi = max(hi, (uint32_t)__shfl_xor((int)hi, (int)o));
-    }
-    if ((tid & 63u) == 0 && lo <= hi) {
-        atomicMin(&kmin[q], lo);
-        atomicMax(&kmax[q], hi);
-    }
-}
-
 // k_knn_hist over the positions of S(q): hist[q][bin] += 1 (integer atomics: the counts do not depend on their order)
 __global__ __launch_bounds__(256) void k_ivff_hist(const float *__restrict__ W, uint64_t wstride, const uint32_t *__restrict__ pref,
                                                    uint32_t nprobe, const uint32_t *__restrict__ kmin,
@@ -367,22 +140,6 @@ struct IvffSource {
     __device__ uint32_t bin(float dval) const { return knn_bin(adc_key(dval), lo, hi); }
     uint32_t blocks() const { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((wstride + 255) / 256, 1), 64); }
 };
-
-template <class F>
-int ivff_dispatch(int metric, int dtype, F &&f) {
-    auto by_type = [&](auto mtag) -> int {
-        if (dtype == 1) return f(mtag, (const uint16_t *)nullptr);
-        return f(mtag, (const float *)nullptr);
-    };
-    switch (metric) {
-        case VQHIP_SQUARED_EUCLIDEAN: return by_type(std::integral_constant<int, VQHIP_SQUARED_EUCLIDEAN>());
-        case VQHIP_EUCLIDEAN: return by_type(std::integral_constant<int, VQHIP_EUCLIDEAN>());
-        case VQHIP_MANHATTAN: return by_type(std::integral_constant<int, VQHIP_MANHATTAN>());
-        case VQHIP_COSINE: return by_type(std::integral_constant<int, VQHIP_COSINE>());
-        case VQHIP_COSINE_UNCLAMPED: return by_type(std::integral_constant<int, VQHIP_COSINE_UNCLAMPED>());
-    }
-    return fail(VQHIP_ERR_INVALID_INPUT, "unknown metric %d", metric);
-}
 
 }  // namespace
 
@@ -441,31 +198,6 @@ int launch_ivff_range_begin(RangeOut *out, uint32_t nq, uint64_t max_results, hi
     return range_begin(out, nq, max_results, stream);
 }
 
-// the two distance passes of a batch behind its plan: every D(q, i) of the probed lists into W, the key range into p
-static int ivfflat_distances(const IvffPlan &p, int metric, const void *X, int dtype, uint32_t d, const float *rnorm, const uint32_t *off,
-                             uint32_t nlist, const float *queries, const float *qnorm, const uint32_t *probe, uint32_t nb,
-                             uint32_t nprobe, uint32_t chunk, uint64_t wstride, float *W, const uint32_t *pref, const uint32_t *seg,
-                             const uint32_t *inv, hipStream_t stream) {
-    const uint64_t items = (wstride + chunk - 1) / chunk;
-    return ivff_dispatch(metric, dtype, [&](auto mtag, auto rtag) -> int {
-        using RT = std::remove_const_t<std::remove_pointer_t<decltype(rtag)>>;
-        constexpr int M = decltype(mtag)::value;
-        if (p.tiles_max > 0) {
-            hipLaunchKernelGGL((k_ivff_tile<M, RT>), dim3((uint32_t)p.tiles_max, (uint32_t)p.cols), dim3(256), 0, stream, queries,
-                               reinterpret_cast<const RT *>(X), d, qnorm, rnorm, off, nlist, p.cnt, p.lstart, p.tstart, inv, pref,
-                               nprobe, wstride, W, p.kmin, p.kmax);
-            VQ_LAUNCH_CHECK("k_ivff_tile");
-        }
-        if (items > 0) {
-            hipLaunchKernelGGL((k_ivff_scan<M, RT>), dim3((uint32_t)items, nb), dim3(256), 0, stream, queries,
-                               reinterpret_cast<const RT *>(X), d, qnorm, rnorm, probe, p.cnt, pref, seg, nprobe, chunk, wstride, W,
-                               p.kmin, p.kmax);
-            VQ_LAUNCH_CHECK("k_ivff_scan");
-        }
-        return VQHIP_OK;
-    });
-}
-
 // One batch of nb <= 1024 queries (queries [nb][d] f32, qnorm [nb] under the cosines) whose probe lists
 // (probe [nb][nprobe], launch_knn_search) are on the device.  X / rnorm / ids / off: the index in list order.  W
 // [nb][wstride] with wstride >= every |S(q)|; pref [nb][nprobe + 1], seg and inv [nb][nprobe], lists >=
@@ -479,8 +211,10 @@ int launch_ivfflat_search(int metric, const void *X, int dtype, uint32_t d, cons
     if (nb == 0) return VQHIP_OK;
     IvffPlan p;
     VQ_TRY(launch_ivff_plan(off, nlist, max_list, probe, nb, nprobe, topk, pref, seg, inv, lists, state, &p, stream));
-    VQ_TRY(ivfflat_distances(p, metric, X, dtype, d, rnorm, off, nlist, queries, qnorm, probe, nb, nprobe, chunk, wstride, W, pref, seg,
-                             inv, stream));
+    VQ_TRY(knn_dense_rows(X, dtype, d, [&](auto rows) {
+        return ivff_distances(p, metric, rows, rnorm, off, nlist, queries, qnorm, probe, nb, nprobe, chunk, wstride, W, pref, seg, inv,
+                              stream);
+    }));
     return launch_ivff_select(p, W, wstride, pref, seg, ids, nb, nprobe, topk, cand, idx_out, dist_out, stream);
 }
 
@@ -496,8 +230,10 @@ int launch_ivfflat_range(int metric, const void *X, int dtype, uint32_t d, const
     if (nb == 0) return VQHIP_OK;
     IvffPlan p;
     VQ_TRY(launch_ivff_plan(off, nlist, max_list, probe, nb, nprobe, 1, pref, seg, inv, lists, state, &p, stream));
-    VQ_TRY(ivfflat_distances(p, metric, X, dtype, d, rnorm, off, nlist, queries, qnorm, probe, nb, nprobe, chunk, wstride, W, pref, seg,
-                             inv, stream));
+    VQ_TRY(knn_dense_rows(X, dtype, d, [&](auto rows) {
+        return ivff_distances(p, metric, rows, rnorm, off, nlist, queries, qnorm, probe, nb, nprobe, chunk, wstride, W, pref, seg, inv,
+                              stream);
+    }));
     return launch_ivff_range(W, wstride, pref, seg, ids, n, nb, nprobe, q0, radii, range_ws, stage, max_results, out, stream);
 }
 
