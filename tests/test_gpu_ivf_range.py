@@ -5,8 +5,9 @@ f16 rows and every SQ loader, dim 1 / 5 / 33 / 128 (36: the 4-byte SQ loader), a
 nprobe 1 / 3 / nlist; radii on a tied boundary, +inf and -1; nprobe == nlist against FlatIndex / ScalarIndex, the scalar
 index against the flat one over the dequantized rows; batches on both sides of the count (16 queries per list) from which
 the tile kernel takes a list; the ordering stage with three radix passes, segments spanning several blocks, empty segments
-and ragged lengths; two batches with two buffer growths; the cap; determinism; the device form; an add between two calls;
-an index without rows; consistency with search."""
+and ragged lengths; short queries behind a long one's finite distances in W on both load paths; two batches with two
+buffer growths; the cap; determinism; the device form; an add between two calls; an index without rows; consistency
+with search."""
 import os
 import re
 
@@ -248,6 +249,41 @@ def test_ordering_stage(big_ids, nprobe):
     for j in range(Q.shape[0]):
         assert (np.diff(got[1][int(got[0][j]):int(got[0][j + 1])].astype(np.int64)) > 0).all()
     _assert_same(ix.range_search(Q, r, nprobe=nprobe), got)  # determinism
+    ix.close()
+
+
+@pytest.mark.parametrize("longest", [4100, 4101])  # wstride 4100 / 4108: a float4 per lane; 4101 / 4109: scalar loads
+def test_short_queries_behind_a_long_one(longest):
+    """The bound of the count and fill passes: |S(q)| % 4 in {1, 2, 3} on both load paths, with FINITE distances of an
+    earlier call behind |S(q)| in W.  The first call's queries probe the long list and fill their rows of W; the second
+    call's, on the same index with the same nq and nprobe, probe lists of 5, 6, 11 and 13 rows.  A position at or past
+    |S(q)| must not hit under +inf, nor under a radius just above the largest true distance (the stale ones are smaller)."""
+    rng = np.random.default_rng(4100)
+    sizes = np.array([longest, 8, 5, 6])
+    coarse = np.zeros((4, 4), F)
+    coarse[:, 0] = [0.0, 120.0, 200.0, 210.0]  # list 1's second neighbour is list 2, list 2's and 3's are each other
+    lists = rng.permutation(np.repeat(np.arange(4), sizes)).astype(np.uint32)
+    rows = (coarse[lists] + F(0.01) * rng.standard_normal((lists.size, 4)).astype(F)).astype(F)
+    assert np.array_equal(np.bincount(lists, minlength=4), sizes)
+    ix = _flat_index(coarse, K.SQUARED_EUCLIDEAN, lists, rows)
+    long_q = (coarse[[0, 0, 0]] + F(0.01) * rng.standard_normal((3, 4)).astype(F)).astype(F)
+    short_q = (coarse[[2, 3, 1]] + F([1.0, 0.0, 0.0, 0.0])).astype(F)  # a unit off the centroid: true distances near 1
+    inf = np.full(3, np.inf, F)
+    for nprobe, per_long, per_short in ((1, [longest] * 3, [5, 6, 8]), (2, [longest + 8] * 3, [11, 11, 13])):
+        assert (longest + 8 * (nprobe - 1)) % 4 == longest % 4  # wstride: the nprobe largest lists
+        first = ix.range_search(long_q, inf, nprobe=nprobe)
+        assert np.diff(first[0].astype(np.int64)).tolist() == per_long
+        # what stays in W: finite, and the long list's positions, the first of every query, below every radius used next
+        assert np.isfinite(first[2]).all() and int((first[2] < 0.1).sum()) == 3 * longest
+        want = RR.search(K.SQUARED_EUCLIDEAN, coarse, lists, rows, short_q, nprobe, inf)
+        assert np.diff(want[0].astype(np.int64)).tolist() == per_short
+        probed = ([2], [3], [1]) if nprobe == 1 else ([2, 3], [3, 2], [1, 2])
+        for j in range(3):  # exactly the rows of its lists, in ascending id
+            assert np.array_equal(want[1][int(want[0][j]):int(want[0][j + 1])], np.flatnonzero(np.isin(lists, probed[j])))
+        _assert_same(ix.range_search(short_q, inf, nprobe=nprobe), want)
+        tight = np.array([np.nextafter(want[2][int(want[0][j]):int(want[0][j + 1])].max(), F(np.inf)) for j in range(3)], F)
+        assert tight.min() > 0.5
+        _assert_same(ix.range_search(short_q, tight, nprobe=nprobe), want)
     ix.close()
 
 

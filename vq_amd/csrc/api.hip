@@ -2727,6 +2727,8 @@ struct Resident {
     uint32_t d = 0;
     int metric = VQHIP_EUCLIDEAN;
     DevBuf q, cand, idx, out;  // per-call workspaces
+    uint32_t width() const { return d; }     // floats of a query
+    int on_device() { return VQHIP_OK; }     // (the rows stay where create put them: no device of its own to check)
 };
 
 // The two indexes of exact distances.  T (vqhip_flat, vqhip_sqindex) keeps its rows and the three launcher calls that
@@ -3140,36 +3142,56 @@ static int range_args(const void *queries, const R *radii, uint32_t nq, uint64_t
     return VQHIP_OK;
 }
 
-// One range call on a flat or a scalar index h: the queries (host: through h->q) and the radii go up, and the index's
-// driver, h->launch_range, leaves *out complete.  The index is looked at after range_args, so those checks need none.
-template <class H>
-static int range_search(H *h, const void *queries, bool host, uint32_t nq, const float *radii, uint64_t max_results,
-                        vqhip_range **out) {
+// The front of every range call on a handle h (a Resident or an IvfLists), in the order every entry point checks:
+// range_args (no device, no index), the handle, the alignment of a device form's queries, the handle's lock, `checks`
+// (the index's own, of what changes under add), the device, the index's device, the calling thread's stream.  Then the
+// result object, a host form's queries up through h->q, and body(queries on the device, the result, s) for nq > 0, which
+// leaves the result complete and has waited for s on every exit; no queries: the empty result, lims = [0].
+template <class H, class R, class C, class F>
+static int range_enter(H *h, const void *queries, bool host, uint32_t nq, const R *radii, uint64_t max_results, vqhip_range **out,
+                       C &&checks, F &&body) {
     VQ_TRY(range_args(queries, radii, nq, max_results, out));
     if (!h) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
     if (!host && (reinterpret_cast<uintptr_t>(queries) & 3)) return fail(VQHIP_ERR_INVALID_INPUT, "queries are not 4-byte aligned");
+    Entry in(h->sync);  // (an inverted file's n changes under add: read under the lock)
+    VQ_TRY(checks());
     VQ_TRY(require_gfx950());
-    Entry in(h->sync);
+    VQ_TRY(h->on_device());
     hipStream_t s;
     VQ_TRY(in.stream(&s));
     std::unique_ptr<vqhip_range> r(new vqhip_range());
-    const float *qdev = reinterpret_cast<const float *>(queries);
-    if (host && nq) {
-        VQ_TRY(h->q.ensure((size_t)nq * h->d * 4));
-        VQ_HIP(hipMemcpyAsync(h->q.p, queries, (size_t)nq * h->d * 4, hipMemcpyHostToDevice, s));
-        qdev = h->q.template as<float>();
+    if (nq) {
+        const float *qdev = reinterpret_cast<const float *>(queries);
+        if (host) {
+            VQ_TRY(h->q.ensure((size_t)nq * h->width() * 4));
+            VQ_HIP(hipMemcpyAsync(h->q.p, queries, (size_t)nq * h->width() * 4, hipMemcpyHostToDevice, s));
+            qdev = h->q.template as<float>();
+        }
+        VQ_TRY(body(qdev, &r->r, s));
+    } else {
+        VQ_TRY(launch_range_begin(&r->r, 0, max_results, s));
+        VQ_HIP(hipStreamSynchronize(s));
     }
-    VQ_TRY(h->radii.ensure((size_t)nq * 4));
-    if (nq) VQ_HIP(hipMemcpyAsync(h->radii.p, radii, (size_t)nq * 4, hipMemcpyHostToDevice, s));
-    VQ_TRY(h->dist.ensure((size_t)knn_query_batch(h->n, nq) * h->n * 4));
-    VQ_TRY(h->state.ensure(knn_state_bytes(knn_query_batch(h->n, nq))));
-    VQ_TRY(h->range_ws.ensure(range_ws_bytes(h->n, nq)));
-    const float *qn = nullptr;
-    if (nq) VQ_TRY(h->qnorms(qdev, nq, &qn, s));
-    VQ_TRY(h->launch_range(qdev, qn, nq, max_results, &r->r, s));  // (every exit of the driver has waited for s)
     in.synced();
     *out = r.release();
     return VQHIP_OK;
+}
+
+// One range call on a flat or a scalar index h: the radii go up, and the index's driver, h->launch_range, leaves the
+// result complete.
+template <class H>
+static int range_search(H *h, const void *queries, bool host, uint32_t nq, const float *radii, uint64_t max_results,
+                        vqhip_range **out) {
+    return range_enter(h, queries, host, nq, radii, max_results, out, no_checks, [&](const float *qdev, RangeOut *r, hipStream_t s) -> int {
+        VQ_TRY(h->radii.ensure((size_t)nq * 4));
+        VQ_HIP(hipMemcpyAsync(h->radii.p, radii, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+        VQ_TRY(h->dist.ensure((size_t)knn_query_batch(h->n, nq) * h->n * 4));
+        VQ_TRY(h->state.ensure(knn_state_bytes(knn_query_batch(h->n, nq))));
+        VQ_TRY(h->range_ws.ensure(range_ws_bytes(h->n, nq)));
+        const float *qn = nullptr;
+        VQ_TRY(h->qnorms(qdev, nq, &qn, s));
+        return h->launch_range(qdev, qn, nq, max_results, r, s);
+    });
 }
 
 extern "C" {
@@ -3269,36 +3291,20 @@ struct vqhip_binary : Resident {
     }
 };
 
-// One Hamming-radius range call on a binary index: range_search's front (range_args' checks need no device and no
-// index), the queries (host: through b->q) and the radii, clamped to d and padded by a query group, go up, and
-// launch_binary_range leaves *out complete.
+// One Hamming-radius range call on a binary index: the radii, clamped to d and padded by a query group, go up, and
+// launch_binary_range leaves the result complete.
 static int binary_range(vqhip_binary *b, const void *queries, bool host, uint32_t nq, const uint32_t *hradii, uint64_t max_results,
                         vqhip_range **out) {
-    VQ_TRY(range_args(queries, hradii, nq, max_results, out));
-    if (!b) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    if (!host && (reinterpret_cast<uintptr_t>(queries) & 3)) return fail(VQHIP_ERR_INVALID_INPUT, "queries are not 4-byte aligned");
-    VQ_TRY(require_gfx950());
-    Entry in(b->sync);
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    std::unique_ptr<vqhip_range> r(new vqhip_range());
-    const float *qdev = reinterpret_cast<const float *>(queries);
-    if (host && nq) {
-        VQ_TRY(b->q.ensure((size_t)nq * b->d * 4));
-        VQ_HIP(hipMemcpyAsync(b->q.p, queries, (size_t)nq * b->d * 4, hipMemcpyHostToDevice, s));
-        qdev = b->q.as<float>();
-    }
-    b->h_hcut.assign((size_t)nq + 32, 0u);
-    for (uint32_t q = 0; q < nq; ++q) b->h_hcut[q] = std::min(hradii[q], b->d);
-    VQ_TRY(b->hcut.ensure(b->h_hcut.size() * 4));
-    VQ_HIP(hipMemcpyAsync(b->hcut.p, b->h_hcut.data(), b->h_hcut.size() * 4, hipMemcpyHostToDevice, s));
-    VQ_TRY(b->qw.ensure((size_t)binary_range_batch(b->n, b->d, nq) * b->W * 4));
-    VQ_TRY(b->range_ws.ensure(binary_range_ws_bytes(b->n, b->d, nq)));
-    VQ_TRY(launch_binary_range(b->words.as<uint32_t>(), b->n, b->d, b->metric, b->table.as<float>(), qdev, b->thr, b->high, nq,
-                               b->hcut.as<uint32_t>(), max_results, b->qw.as<uint32_t>(), b->range_ws.p, &r->r, s));  // (has waited for s)
-    in.synced();
-    *out = r.release();
-    return VQHIP_OK;
+    return range_enter(b, queries, host, nq, hradii, max_results, out, no_checks, [&](const float *qdev, RangeOut *r, hipStream_t s) -> int {
+        b->h_hcut.assign((size_t)nq + 32, 0u);
+        for (uint32_t q = 0; q < nq; ++q) b->h_hcut[q] = std::min(hradii[q], b->d);
+        VQ_TRY(b->hcut.ensure(b->h_hcut.size() * 4));
+        VQ_HIP(hipMemcpyAsync(b->hcut.p, b->h_hcut.data(), b->h_hcut.size() * 4, hipMemcpyHostToDevice, s));
+        VQ_TRY(b->qw.ensure((size_t)binary_range_batch(b->n, b->d, nq) * b->W * 4));
+        VQ_TRY(b->range_ws.ensure(binary_range_ws_bytes(b->n, b->d, nq)));
+        return launch_binary_range(b->words.as<uint32_t>(), b->n, b->d, b->metric, b->table.as<float>(), qdev, b->thr, b->high, nq,
+                                   b->hcut.as<uint32_t>(), max_results, b->qw.as<uint32_t>(), b->range_ws.p, r, s);
+    });
 }
 
 static int binary_check(int kind, uint64_t n, uint32_t d, float threshold, uint32_t low, uint32_t high, int metric) {
@@ -3496,6 +3502,15 @@ struct IvfLists {
     DevBuf d_off, d_ids, d_payload;        // (d_payload is the index's own buffer: the loaders' alignment rests on its base)
     DevBuf q, probe, probe_dist, pref, seg, W, state, cand, idx, out;  // per-call workspaces
     ~IvfLists() { delete flat; }
+    uint32_t width() const { return dim; }  // floats of a query
+    // every device call runs on the index's device
+    int on_device() {
+        int cur = 0;
+        VQ_HIP(hipGetDevice(&cur));
+        if (dev < 0) dev = cur;
+        if (cur != dev) return fail(VQHIP_ERR_INVALID_INPUT, "the index lives on device %d, but device %d is current", dev, cur);
+        return VQHIP_OK;
+    }
 };
 
 // the checks every create shares (each create keeps its own between them, in its documented order) and the shared fields
@@ -3519,15 +3534,6 @@ static void ivf_init(IvfLists *ix, const float *coarse, uint32_t nlist, uint32_t
 static int ivf_check_probe(const IvfLists *ix, uint32_t nprobe) {
     const uint32_t hi = std::min<uint32_t>(ix->nlist, 1024);
     if (nprobe == 0 || nprobe > hi) return fail(VQHIP_ERR_INVALID_INPUT, "nprobe %u must be in [1, min(nlist, 1024)] = [1, %u]", nprobe, hi);
-    return VQHIP_OK;
-}
-
-// every device call runs on the index's device
-static int ivf_device(IvfLists *ix) {
-    int cur = 0;
-    VQ_HIP(hipGetDevice(&cur));
-    if (ix->dev < 0) ix->dev = cur;
-    if (cur != ix->dev) return fail(VQHIP_ERR_INVALID_INPUT, "the index lives on device %d, but device %d is current", ix->dev, cur);
     return VQHIP_OK;
 }
 
@@ -3645,7 +3651,7 @@ static int ivf_enter(T *ix, bool args, uint32_t nq, uint32_t nprobe, const uint3
     if (topk) VQ_TRY(check_topk(ix->n, *topk));
     if (nq == 0) return VQHIP_OK;
     VQ_TRY(require_gfx950());
-    VQ_TRY(ivf_device(ix));
+    VQ_TRY(ix->on_device());
     hipStream_t s;
     VQ_TRY(in.stream(&s));
     VQ_TRY(ix->ready(s));
@@ -3830,81 +3836,93 @@ int vqhip_ivfpq_search_device(vqhip_ivfpq *ix, const void *dev_queries, uint32_t
 
 }  // extern "C"
 
-// ------------------------------------------------------------------ inverted-file flat and scalar (k_ivfflat.hip, k_ivfsq.hip) ----
-// The two indexes of exact distances: IvfLists whose payload is the rows themselves (f32 or f16 elements) or their SQ
-// codes (dim bytes), with the rows' norms under the cosines.  They differ in the norms kernel and the search launch.
-struct IvfExact : IvfLists {
-    DevBuf d_rnorm;
-    DevBuf qnorm, inv, lists;      // per-call workspaces
+// ------------------------------------------------------------------ inverted files over W (k_ivfflat.hip, k_ivfsq.hip, k_ivfbin.hip) ----
+// What vqhip_ivfflat, vqhip_ivfsq and vqhip_ivfbin share behind IvfLists: a batch's distance passes leave every D(q, i)
+// of the probed lists in W, and the selection stage or the range stage runs behind them (IvfBatchView, kernels.hpp).
+// T supplies only what is its own:
+//   prepare(queries_dev, nq, nb_max, s)   once per call: the query norms under the cosines, or room for the packed queries
+//   distances(p, v, Q, q0, s)             one batch's distance passes behind its plan p (Q: the batch's queries, f32)
+//   radii_up(radii, nq, s)                the radii of a range call into this->radii as f32 distances
+template <class T>
+struct IvfOverW : IvfLists {
+    DevBuf inv, lists;              // per-call workspaces: the inverted probe table, the lists' state
     DevBuf radii, range_ws, stage;  // range search: the radii, the stage's counts and offsets, its staging areas
 
-    // the nq radii of a range call into this->radii
-    int radii_up(const float *r, uint32_t nq, hipStream_t s) {
-        VQ_TRY(radii.ensure((size_t)nq * 4));
-        VQ_HIP(hipMemcpyAsync(radii.p, r, (size_t)nq * 4, hipMemcpyHostToDevice, s));
-        return VQHIP_OK;
-    }
-
-    // queries_dev [nq][dim] f32 -> [nq][topk] results on the device, enqueued on s, in ivf_batch's batches;
-    // launch(Q, qn or NULL, nb, batch, idx_dev, dist_dev) searches one batch
-    template <class Launch>
-    int search_batches(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
-                       hipStream_t s, Launch &&launch) {
+    // The batch loop: queries_dev [nq][dim] f32 in ivf_batch's batches -- the probe, the plan, the index's distances, then
+    // stage(p, v, q0) behind them.  topk: the selection's; 0: the range stage follows (its workspace is sized here for
+    // the largest batch, and the plan's check is given 1).  Enqueued on s.
+    template <class Stage>
+    int batches(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk, hipStream_t s, Stage &&stage_fn) {
+        T *ix = static_cast<T *>(this);
         IvfBatch b;
         VQ_TRY(ivf_batch(this, nq, nprobe, 0, &b));
         VQ_TRY(inv.ensure((size_t)b.nb_max * nprobe * 4));
         VQ_TRY(lists.ensure(ivfflat_lists_bytes(nlist)));
         VQ_TRY(state.ensure(knn_state_bytes(b.nb_max)));
-        const float *qn = nullptr;
-        if (vq_is_cos(metric)) {  // once per call
-            VQ_TRY(qnorm.ensure((size_t)nq * 4));
-            VQ_TRY(launch_knn_norms(queries_dev, 0, nq, dim, qnorm.as<float>(), s));
-            qn = qnorm.as<float>();
-        }
+        if (topk == 0) VQ_TRY(range_ws.ensure(ivff_range_ws_bytes(b.wstride, b.nb_max)));
+        VQ_TRY(ix->prepare(queries_dev, nq, b.nb_max, s));
         for (uint32_t q0 = 0; q0 < nq; q0 += b.nb_max) {
             const uint32_t nb = std::min(b.nb_max, nq - q0);
             const float *Q = queries_dev + (size_t)q0 * dim;
-            VQ_TRY(ivf_probe_enqueue(this, Q, nb, nprobe, probe.as<uint32_t>(), s));
-            VQ_TRY(launch(Q, qn ? qn + q0 : nullptr, nb, b, idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk));
+            VQ_TRY(ivf_probe_enqueue(this, Q, nb, nprobe, probe.as<uint32_t>(), s));  // (the f32 queries, whatever the rows are)
+            const IvfBatchView v{d_ids.as<uint32_t>(), n, d_off.as<uint32_t>(), nlist, max_list,
+                                 probe.as<uint32_t>(), nb, nprobe, ivf_chunk((uint64_t)nb * b.per_q), b.wstride,
+                                 W.as<float>(), pref.as<uint32_t>(), seg.as<uint32_t>(), inv.as<uint32_t>(), lists.as<uint32_t>(), state.p};
+            IvffPlan p;
+            VQ_TRY(launch_ivff_plan(v, topk ? topk : 1, &p, s));
+            VQ_TRY(ix->distances(p, v, Q, q0, s));
+            VQ_TRY(stage_fn(p, v, q0));
         }
         return VQHIP_OK;
     }
 
-    // queries_dev [nq][dim] f32 and the radii (this->radii, [nq]) -> *out, complete on return, in search_batches' batches;
-    // launch(Q, qn or NULL, nb, batch, q0, radii of the batch) runs one batch's distances and the range stage
-    template <class Launch>
-    int range_batches(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint64_t max_results, RangeOut *out, hipStream_t s,
-                      Launch &&launch) {
-        VQ_TRY(launch_ivff_range_begin(out, nq, max_results, s));
+    // queries_dev [nq][dim] f32 -> [nq][topk] results on the device, enqueued on s
+    int search_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
+                       hipStream_t s) {
+        return batches(queries_dev, nq, nprobe, topk, s, [&](const IvffPlan &p, const IvfBatchView &v, uint32_t q0) {
+            return launch_ivff_select(p, v, topk, cand.as<unsigned long long>(), idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s);
+        });
+    }
+
+    // queries_dev [nq][dim] f32 and the radii (this->radii, [nq]) -> *out, complete on return
+    int range_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint64_t max_results, RangeOut *out, hipStream_t s) {
+        VQ_TRY(launch_range_begin(out, nq, max_results, s));
         if (n == 0) {  // no rows: every query's range is empty
             VQ_HIP(hipMemsetAsync(out->lims.p, 0, ((size_t)nq + 1) * 8, s));
             VQ_HIP(hipStreamSynchronize(s));
             return VQHIP_OK;
         }
-        IvfBatch b;
-        VQ_TRY(ivf_batch(this, nq, nprobe, 0, &b));
-        VQ_TRY(inv.ensure((size_t)b.nb_max * nprobe * 4));
-        VQ_TRY(lists.ensure(ivfflat_lists_bytes(nlist)));
-        VQ_TRY(state.ensure(knn_state_bytes(b.nb_max)));
-        VQ_TRY(range_ws.ensure(ivff_range_ws_bytes(b.wstride, b.nb_max)));
-        const float *qn = nullptr;
-        if (vq_is_cos(metric)) {  // once per call
-            VQ_TRY(qnorm.ensure((size_t)nq * 4));
-            VQ_TRY(launch_knn_norms(queries_dev, 0, nq, dim, qnorm.as<float>(), s));
-            qn = qnorm.as<float>();
-        }
-        for (uint32_t q0 = 0; q0 < nq; q0 += b.nb_max) {
-            const uint32_t nb = std::min(b.nb_max, nq - q0);
-            const float *Q = queries_dev + (size_t)q0 * dim;
-            VQ_TRY(ivf_probe_enqueue(this, Q, nb, nprobe, probe.as<uint32_t>(), s));
-            VQ_TRY(launch(Q, qn ? qn + q0 : nullptr, nb, b, q0, radii.as<float>() + q0));
-        }
+        VQ_TRY(batches(queries_dev, nq, nprobe, 0, s, [&](const IvffPlan &, const IvfBatchView &v, uint32_t q0) {
+            return launch_ivff_range(v, q0, radii.as<float>() + q0, range_ws.p, &stage, max_results, out, s);
+        }));
         VQ_HIP(hipStreamSynchronize(s));
         return VQHIP_OK;
     }
 };
 
-struct vqhip_ivfflat : IvfExact {
+// ------------------------------------------------------------------ inverted-file flat and scalar (k_ivfflat.hip, k_ivfsq.hip) ----
+// The two indexes of exact distances: the payload is the rows themselves (f32 or f16 elements) or their SQ codes (dim
+// bytes), with the rows' norms under the cosines.  They differ in the norms kernel and the distance launcher.
+template <class T>
+struct IvfExact : IvfOverW<T> {
+    DevBuf d_rnorm;
+    DevBuf qnorm;  // per-call workspace
+
+    int radii_up(const float *r, uint32_t nq, hipStream_t s) {
+        VQ_TRY(this->radii.ensure((size_t)nq * 4));
+        VQ_HIP(hipMemcpyAsync(this->radii.p, r, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+        return VQHIP_OK;
+    }
+    int prepare(const float *queries_dev, uint32_t nq, uint32_t, hipStream_t s) {
+        if (!vq_is_cos(this->metric)) return VQHIP_OK;
+        VQ_TRY(qnorm.ensure((size_t)nq * 4));
+        return launch_knn_norms(queries_dev, 0, nq, this->dim, qnorm.as<float>(), s);
+    }
+    // the norms of the batch at query q0 (NULL off the cosines)
+    const float *qnorms(uint32_t q0) const { return vq_is_cos(this->metric) ? qnorm.as<float>() + q0 : nullptr; }
+};
+
+struct vqhip_ivfflat : IvfExact<vqhip_ivfflat> {
     int dtype = 0;
 
     int ready(hipStream_t s) {
@@ -3914,28 +3932,12 @@ struct vqhip_ivfflat : IvfExact {
             return launch_knn_norms(d_payload.p, dtype, n, dim, d_rnorm.as<float>(), s);
         });
     }
-    int search_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
-                       hipStream_t s) {
-        return search_batches(queries_dev, nq, nprobe, topk, idx_dev, dist_dev, s,
-                              [&](const float *Q, const float *qn, uint32_t nb, const IvfBatch &b, uint32_t *idx_b, float *dist_b) {
-            return launch_ivfflat_search(metric, d_payload.p, dtype, dim, d_rnorm.as<float>(), d_ids.as<uint32_t>(), d_off.as<uint32_t>(),
-                                         nlist, max_list, Q, qn, probe.as<uint32_t>(), nb, nprobe, topk, ivf_chunk((uint64_t)nb * b.per_q),
-                                         b.wstride, W.as<float>(), pref.as<uint32_t>(), seg.as<uint32_t>(), inv.as<uint32_t>(),
-                                         lists.as<uint32_t>(), state.p, cand.as<unsigned long long>(), idx_b, dist_b, s);
-        });
-    }
-    int range_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint64_t max_results, RangeOut *out, hipStream_t s) {
-        return range_batches(queries_dev, nq, nprobe, max_results, out, s,
-                             [&](const float *Q, const float *qn, uint32_t nb, const IvfBatch &b, uint32_t q0, const float *rad) {
-            return launch_ivfflat_range(metric, d_payload.p, dtype, dim, d_rnorm.as<float>(), d_ids.as<uint32_t>(), n, d_off.as<uint32_t>(),
-                                        nlist, max_list, Q, qn, probe.as<uint32_t>(), nb, nprobe, ivf_chunk((uint64_t)nb * b.per_q),
-                                        b.wstride, W.as<float>(), pref.as<uint32_t>(), seg.as<uint32_t>(), inv.as<uint32_t>(),
-                                        lists.as<uint32_t>(), state.p, q0, rad, range_ws.p, &stage, max_results, out, s);
-        });
+    int distances(const IvffPlan &p, const IvfBatchView &v, const float *Q, uint32_t q0, hipStream_t s) {
+        return launch_ivfflat_distances(p, v, metric, d_payload.p, dtype, dim, d_rnorm.as<float>(), Q, qnorms(q0), s);
     }
 };
 
-struct vqhip_ivfsq : IvfExact {
+struct vqhip_ivfsq : IvfExact<vqhip_ivfsq> {
     uint32_t levels = 0;
     float mn = 0, mx = 0, step = 0;
     SqbqEncodeOp op;  // add_rows: the encode of this quantizer
@@ -3947,37 +3949,20 @@ struct vqhip_ivfsq : IvfExact {
             return launch_sq_norms(d_payload.as<uint8_t>(), n, dim, mn, step, d_rnorm.as<float>(), s);
         });
     }
-    int search_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
-                       hipStream_t s) {
-        return search_batches(queries_dev, nq, nprobe, topk, idx_dev, dist_dev, s,
-                              [&](const float *Q, const float *qn, uint32_t nb, const IvfBatch &b, uint32_t *idx_b, float *dist_b) {
-            return launch_ivfsq_search(metric, d_payload.as<uint8_t>(), dim, mn, step, d_rnorm.as<float>(), d_ids.as<uint32_t>(),
-                                       d_off.as<uint32_t>(), nlist, max_list, Q, qn, probe.as<uint32_t>(), nb, nprobe, topk,
-                                       ivf_chunk((uint64_t)nb * b.per_q), b.wstride, W.as<float>(), pref.as<uint32_t>(), seg.as<uint32_t>(),
-                                       inv.as<uint32_t>(), lists.as<uint32_t>(), state.p, cand.as<unsigned long long>(), idx_b, dist_b, s);
-        });
-    }
-    int range_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint64_t max_results, RangeOut *out, hipStream_t s) {
-        return range_batches(queries_dev, nq, nprobe, max_results, out, s,
-                             [&](const float *Q, const float *qn, uint32_t nb, const IvfBatch &b, uint32_t q0, const float *rad) {
-            return launch_ivfsq_range(metric, d_payload.as<uint8_t>(), dim, mn, step, d_rnorm.as<float>(), d_ids.as<uint32_t>(), n,
-                                      d_off.as<uint32_t>(), nlist, max_list, Q, qn, probe.as<uint32_t>(), nb, nprobe,
-                                      ivf_chunk((uint64_t)nb * b.per_q), b.wstride, W.as<float>(), pref.as<uint32_t>(), seg.as<uint32_t>(),
-                                      inv.as<uint32_t>(), lists.as<uint32_t>(), state.p, q0, rad, range_ws.p, &stage, max_results, out, s);
-        });
+    int distances(const IvffPlan &p, const IvfBatchView &v, const float *Q, uint32_t q0, hipStream_t s) {
+        return launch_ivfsq_distances(p, v, metric, d_payload.as<uint8_t>(), dim, mn, step, d_rnorm.as<float>(), Q, qnorms(q0), s);
     }
 };
 
 // ------------------------------------------------------------------ inverted-file binary (k_ivfbin.hip) ----
-// IvfLists whose payload is packed BQ words (bin_words(dim) words a row, pad bits zero).  Two metrics: `metric` of the
-// reported distance (the table S), `probe_metric` of the flat index over the centroids.
-struct vqhip_ivfbin : IvfLists {
+// The payload is packed BQ words (bin_words(dim) words a row, pad bits zero).  Two metrics: `metric` of the reported
+// distance (the table S), `probe_metric` of the flat index over the centroids.
+struct vqhip_ivfbin : IvfOverW<vqhip_ivfbin> {
     uint32_t nw = 0, low = 0, high = 1;  // nw: words a row
     float thr = 0;
-    DevBuf table;            // S [dim + 1]
-    DevBuf qw, inv, lists;   // per-call workspaces: the batch's packed queries, the inverted probe table, the lists' state
-    DevBuf radii, range_ws, stage;  // range search: the radii, the stage's counts and offsets, its staging areas
-    std::vector<float> h_radii;     // the host side of radii (the source of an asynchronous copy)
+    DevBuf table;                 // S [dim + 1]
+    DevBuf qw;                    // per-call workspace: the batch's packed queries
+    std::vector<float> h_radii;   // the host side of radii (the source of an asynchronous copy)
 
     // The Hamming radii of a range call as the f32 radii of the range stage: r_q = the distance the index reports for
     // H = min(h_q, dim).  The reported table is strictly increasing, so D <= r_q iff H <= h_q.
@@ -4004,93 +3989,25 @@ struct vqhip_ivfbin : IvfLists {
             return VQHIP_OK;
         }, ivf_no_hook);
     }
-    int search_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
-                       hipStream_t s) {
-        IvfBatch b;
-        VQ_TRY(ivf_batch(this, nq, nprobe, 0, &b));
-        VQ_TRY(qw.ensure((size_t)b.nb_max * nw * 4));
-        VQ_TRY(inv.ensure((size_t)b.nb_max * nprobe * 4));
-        VQ_TRY(lists.ensure(ivfflat_lists_bytes(nlist)));
-        VQ_TRY(state.ensure(knn_state_bytes(b.nb_max)));
-        for (uint32_t q0 = 0; q0 < nq; q0 += b.nb_max) {
-            const uint32_t nb = std::min(b.nb_max, nq - q0);
-            const float *Q = queries_dev + (size_t)q0 * dim;
-            VQ_TRY(ivf_probe_enqueue(this, Q, nb, nprobe, probe.as<uint32_t>(), s));  // (the f32 queries: never binarised)
-            VQ_TRY(launch_bq_pack(Q, VQHIP_BINARY_F32, nb, dim, thr, high, qw.as<uint32_t>(), s));
-            VQ_TRY(launch_ivfbin_search(metric, d_payload.as<uint32_t>(), dim, table.as<float>(), d_ids.as<uint32_t>(), d_off.as<uint32_t>(),
-                                        nlist, max_list, qw.as<uint32_t>(), probe.as<uint32_t>(), nb, nprobe, topk,
-                                        ivf_chunk((uint64_t)nb * b.per_q), b.wstride, W.as<float>(), pref.as<uint32_t>(), seg.as<uint32_t>(),
-                                        inv.as<uint32_t>(), lists.as<uint32_t>(), state.p, cand.as<unsigned long long>(),
-                                        idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s));
-        }
-        return VQHIP_OK;
-    }
-    // queries_dev [nq][dim] f32 and the radii (this->radii, [nq]) -> *out, complete on return, in search_enqueue's batches
-    int range_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint64_t max_results, RangeOut *out, hipStream_t s) {
-        VQ_TRY(launch_ivff_range_begin(out, nq, max_results, s));
-        if (n == 0) {  // no rows: every query's range is empty
-            VQ_HIP(hipMemsetAsync(out->lims.p, 0, ((size_t)nq + 1) * 8, s));
-            VQ_HIP(hipStreamSynchronize(s));
-            return VQHIP_OK;
-        }
-        IvfBatch b;
-        VQ_TRY(ivf_batch(this, nq, nprobe, 0, &b));
-        VQ_TRY(qw.ensure((size_t)b.nb_max * nw * 4));
-        VQ_TRY(inv.ensure((size_t)b.nb_max * nprobe * 4));
-        VQ_TRY(lists.ensure(ivfflat_lists_bytes(nlist)));
-        VQ_TRY(state.ensure(knn_state_bytes(b.nb_max)));
-        VQ_TRY(range_ws.ensure(ivff_range_ws_bytes(b.wstride, b.nb_max)));
-        for (uint32_t q0 = 0; q0 < nq; q0 += b.nb_max) {
-            const uint32_t nb = std::min(b.nb_max, nq - q0);
-            const float *Q = queries_dev + (size_t)q0 * dim;
-            VQ_TRY(ivf_probe_enqueue(this, Q, nb, nprobe, probe.as<uint32_t>(), s));
-            VQ_TRY(launch_bq_pack(Q, VQHIP_BINARY_F32, nb, dim, thr, high, qw.as<uint32_t>(), s));
-            VQ_TRY(launch_ivfbin_range(metric, d_payload.as<uint32_t>(), dim, table.as<float>(), d_ids.as<uint32_t>(), n,
-                                       d_off.as<uint32_t>(), nlist, max_list, qw.as<uint32_t>(), probe.as<uint32_t>(), nb, nprobe,
-                                       ivf_chunk((uint64_t)nb * b.per_q), b.wstride, W.as<float>(), pref.as<uint32_t>(), seg.as<uint32_t>(),
-                                       inv.as<uint32_t>(), lists.as<uint32_t>(), state.p, q0, radii.as<float>() + q0, range_ws.p, &stage,
-                                       max_results, out, s));
-        }
-        VQ_HIP(hipStreamSynchronize(s));
-        return VQHIP_OK;
+    int prepare(const float *, uint32_t, uint32_t nb_max, hipStream_t) { return qw.ensure((size_t)nb_max * nw * 4); }
+    int distances(const IvffPlan &p, const IvfBatchView &v, const float *Q, uint32_t, hipStream_t s) {
+        VQ_TRY(launch_bq_pack(Q, VQHIP_BINARY_F32, v.nb, dim, thr, high, qw.as<uint32_t>(), s));
+        return launch_ivfbin_distances(p, v, metric, d_payload.as<uint32_t>(), dim, table.as<float>(), qw.as<uint32_t>(), s);
     }
 };
 
-
-// One range call on an inverted-file flat, scalar or binary index: range_args' checks (no device, no index), nprobe as
-// search checks it, then the index's device, the calling thread's stream and the device state as search builds it; the
-// queries (host: through ix->q) and the radii (radii_up: f32 distances, or the binary index's u32 Hamming radii as the
-// distances its table reports for them) go up and range_enqueue leaves *out complete.
+// One range call on an inverted-file flat, scalar or binary index: nprobe as search checks it, then the device state as
+// search builds it; the radii (radii_up: f32 distances, or the binary index's u32 Hamming radii as the distances its table
+// reports for them) go up and range_enqueue leaves the result complete.
 template <class T, class R>
 static int ivf_range(T *ix, const void *queries, bool host, uint32_t nq, uint32_t nprobe, const R *radii, uint64_t max_results,
                      vqhip_range **out) {
-    VQ_TRY(range_args(queries, radii, nq, max_results, out));
-    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
-    if (!host && (reinterpret_cast<uintptr_t>(queries) & 3)) return fail(VQHIP_ERR_INVALID_INPUT, "queries are not 4-byte aligned");
-    Entry in(ix->sync);  // (n changes under add: read under the lock)
-    VQ_TRY(ivf_check_probe(ix, nprobe));
-    VQ_TRY(require_gfx950());
-    VQ_TRY(ivf_device(ix));
-    hipStream_t s;
-    VQ_TRY(in.stream(&s));
-    std::unique_ptr<vqhip_range> r(new vqhip_range());
-    const float *qdev = reinterpret_cast<const float *>(queries);
-    if (nq) {
+    return range_enter(ix, queries, host, nq, radii, max_results, out, [&] { return ivf_check_probe(ix, nprobe); },
+                       [&](const float *qdev, RangeOut *r, hipStream_t s) -> int {
         VQ_TRY(ix->ready(s));
-        if (host) {
-            VQ_TRY(ix->q.ensure((size_t)nq * ix->dim * 4));
-            VQ_HIP(hipMemcpyAsync(ix->q.p, queries, (size_t)nq * ix->dim * 4, hipMemcpyHostToDevice, s));
-            qdev = ix->q.template as<float>();
-        }
         VQ_TRY(ix->radii_up(radii, nq, s));
-        VQ_TRY(ix->range_enqueue(qdev, nq, nprobe, max_results, &r->r, s));  // (every exit of the driver has waited for s)
-    } else {
-        VQ_TRY(launch_ivff_range_begin(&r->r, 0, max_results, s));
-        VQ_HIP(hipStreamSynchronize(s));
-    }
-    in.synced();
-    *out = r.release();
-    return VQHIP_OK;
+        return ix->range_enqueue(qdev, nq, nprobe, max_results, r, s);
+    });
 }
 
 extern "C" {
@@ -4208,7 +4125,7 @@ int vqhip_ivfsq_add_rows(vqhip_ivfsq *ix, const uint32_t *list_ids, const float 
     VQ_API_BEGIN
     return ivf_add(ix, list_ids, rows, n, [&] {
         VQ_TRY(require_gfx950());
-        VQ_TRY(ivf_device(ix));
+        VQ_TRY(ix->on_device());
         const size_t have = ix->payload.size();
         ix->payload.resize(have + (size_t)n * ix->dim);
         const int rc = sqbq_encode_host(ix->op, rows, n * ix->dim, ix->payload.data() + have);  // vqhip_sq_encode's path
@@ -4342,7 +4259,7 @@ int vqhip_ivfbin_add_rows(vqhip_ivfbin *ix, const uint32_t *list_ids, const floa
     VQ_API_BEGIN
     return ivf_add(ix, list_ids, rows, n, [&] {
         VQ_TRY(require_gfx950());
-        VQ_TRY(ivf_device(ix));
+        VQ_TRY(ix->on_device());
         hipStream_t s;
         VQ_TRY(current_stream(&s));
         const size_t have = ix->payload.size();

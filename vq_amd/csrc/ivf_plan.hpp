@@ -56,5 +56,33 @@ __device__ __forceinline__ uint32_t ivf_row(const uint32_t *__restrict__ pq, con
     return sq[slot] + (pos - pq[slot]);
 }
 
+
+// The distances the inverted-file distance kernels leave, W[q][0 .. |S(q)|), as a position source of the selection stage
+// (topk.hpp; IvffSource, k_ivfflat.hip, adds the key bins) and of the range stage (range.hpp): a query's positions in
+// probe-slot order, the id of a position through the plan and the index's ids in list order.
+struct IvffRows {
+    using Pos = uint32_t;
+    static constexpr bool kRagged = true;  // count() <= wstride: what lies behind it is an earlier batch's
+    const float *W;
+    uint64_t wstride;
+    const uint32_t *pref, *seg, *ids;
+    uint32_t nprobe;
+    uint32_t total = 0;  // (device: of the opened query)
+    static __device__ IvffRows rows(const float *W, uint64_t wstride, const uint32_t *pref, const uint32_t *seg, const uint32_t *ids,
+                                    uint32_t nprobe) {
+        return {W, wstride, pref, seg, ids, nprobe};
+    }
+    __device__ void open(uint32_t q) {
+        W += (size_t)q * wstride;
+        pref += (size_t)q * (nprobe + 1);
+        seg += (size_t)q * nprobe;
+        total = (uint32_t)min((uint64_t)pref[nprobe], wstride);
+    }
+    __device__ Pos count() const { return total; }
+    __device__ const float *row() const { return W; }
+    __device__ float at(Pos pos) const { return W[pos]; }
+    __device__ uint32_t id(Pos pos) const { return ids[ivf_row(pref, seg, nprobe, pos)]; }
+};
+
 }  // namespace
 }  // namespace vqhip

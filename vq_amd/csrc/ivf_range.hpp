@@ -1,14 +1,11 @@
-// ivf_range.hpp -- the exact range stage behind vqhip_ivfflat_range_search and vqhip_ivfsq_range_search (k_ivfflat.hip;
-// DESIGN.md section 17): range.hpp's threshold compaction over the RAGGED distances the inverted-file distance kernels
-// leave -- W[q][0 .. |S(q)|), a query's positions in probe-slot order (ivf_plan.hpp) -- followed by a segmented sort that
-// puts each query's hits in ascending row id.  Semantics (include/vqhip.h): row i is a hit of query q iff i is in S(q) and
-// W[q][pos(i)] <= radii[q] as an f32 comparison (NaN never hits, -0.0 <= 0.0 holds).
-//   k_ivfr_count   grid (ceil(wstride / 4096), nb): the hits among a block's 4096 positions below |S(q)| -> cnt[q][blk];
-//                  k_range_count's lanes, strides and ballots, no atomics; a block past |S(q)| writes 0
-//   k_range_scan   (range.hpp, as it is) off[q][blk], the batch's end of every query into lims, the batch total
-//   range_room     (range.hpp) the 8-byte read, max_results, range_grow
-//   k_ivfr_fill    the count's grid: each hit (ids[row of its position], D) at off[q][blk] + its rank in the block, into a
-//                  staging area of the batch -- position order; a block without hits returns before it reads
+// ivf_range.hpp -- the exact range stage behind vqhip_ivfflat_range_search, vqhip_ivfsq_range_search and
+// vqhip_ivfbin_range_search (k_ivfflat.hip): range.hpp's threshold compaction over the RAGGED
+// distances the inverted-file distance kernels leave -- W[q][0 .. |S(q)|), a query's positions in probe-slot order
+// (IvffRows, ivf_plan.hpp) -- followed by a segmented sort that puts each query's hits in ascending row id.  Semantics
+// (include/vqhip.h): row i is a hit of query q iff i is in S(q) and W[q][pos(i)] <= radii[q] as an f32 comparison (NaN
+// never hits, -0.0 <= 0.0 holds).
+//   range_passes   (range.hpp, over IvffRows) count, scan, room and the fill: each hit (ids[row of its position], D) at
+//                  off[q][blk] + its rank in the block, into a staging area of the batch -- position order
 //   k_ivfr_sort    block = query, one launch per 8 bits of the row id (ceil(log2 n) bits in all): a stable LSD radix pass
 //                  over the query's segment, staging areas in turn, the last pass landing in the result at `base`
 // One probed list (nprobe == 1): positions are in row order already, and the fill writes the result itself.
@@ -29,122 +26,6 @@ namespace {
 
 constexpr uint32_t kIvfrSortThreads = 256;                    // (= the digits of a pass: thread t scans digit t)
 constexpr uint32_t kIvfrSortWaves = kIvfrSortThreads / 64;  // quarters of a segment
-
-// the four positions p0 .. p0 + 3 of a query's distances wq[0 .. len): v, and bit j set where position p0 + j is a hit.
-// VEC: wstride % 4 == 0, so q * wstride + p0 is a multiple of 4 and a float4 at p0 < len lies inside the query's row of W
-// (positions from len on hold what an earlier batch left: read, never a hit)
-template <bool VEC>
-__device__ __forceinline__ uint32_t ivfr_load(const float *__restrict__ wq, uint64_t len, uint64_t p0, float rad, float (&v)[4]) {
-    v[0] = v[1] = v[2] = v[3] = 0.0f;
-    uint32_t hits = 0;
-    if constexpr (VEC) {
-        if (p0 < len) {
-            const float4 a = *reinterpret_cast<const float4 *>(wq + p0);
-            v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w;
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) hits |= ((p0 + j < len && v[j] <= rad) ? 1u : 0u) << j;
-        }
-    } else {
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j)
-            if (p0 + j < len) {
-                v[j] = wq[p0 + j];
-                hits |= (v[j] <= rad ? 1u : 0u) << j;
-            }
-    }
-    return hits;
-}
-
-__device__ __forceinline__ uint64_t ivfr_len(const uint32_t *__restrict__ pref, uint32_t nprobe, uint32_t q, uint64_t wstride) {
-    return min((uint64_t)pref[(size_t)q * (nprobe + 1) + nprobe], wstride);
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(kRangeThreads) void k_ivfr_count(const float *__restrict__ W, uint64_t wstride,
-                                                              const uint32_t *__restrict__ pref, uint32_t nprobe,
-                                                              const float *__restrict__ radii, uint32_t nblk,
-                                                              uint32_t *__restrict__ cnt) {
-    __shared__ uint32_t wsum[kRangeThreads / 64];
-    const uint32_t q = blockIdx.y, tid = threadIdx.x;
-    const uint64_t len = ivfr_len(pref, nprobe, q, wstride);
-    const uint64_t pos0 = (uint64_t)blockIdx.x * kRangeRows;
-    if (pos0 >= len) {  // (uniform) past the query's positions
-        if (tid == 0) cnt[(size_t)q * nblk + blockIdx.x] = 0u;
-        return;
-    }
-    const float rad = radii[q];
-    const float *wq = W + (size_t)q * wstride;
-    uint32_t c = 0;  // the wave's hits (uniform)
-#pragma unroll
-    for (uint32_t s = 0; s < kRangeStrides; ++s) {
-        float v[4];
-        const uint32_t hits = ivfr_load<VEC>(wq, len, pos0 + (uint64_t)s * (kRangeThreads * 4) + tid * 4, rad, v);
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) c += (uint32_t)__popcll(__ballot((hits >> j) & 1u));
-    }
-    if ((tid & 63u) == 0) wsum[tid >> 6] = c;
-    __syncthreads();
-    if (tid == 0) cnt[(size_t)q * nblk + blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-// k_range_fill over positions: slot = off[q][blk] + the block's hits in front, counted from the batch's first hit
-// (idx_out / dist_out point at it: the staging area, or the result at `base` when nprobe == 1)
-template <bool VEC>
-__global__ __launch_bounds__(kRangeThreads) void k_ivfr_fill(const float *__restrict__ W, uint64_t wstride,
-                                                             const uint32_t *__restrict__ pref, const uint32_t *__restrict__ seg,
-                                                             const uint32_t *__restrict__ ids, uint32_t nprobe,
-                                                             const float *__restrict__ radii, uint32_t nblk,
-                                                             const uint32_t *__restrict__ cnt,
-                                                             const unsigned long long *__restrict__ off,
-                                                             uint32_t *__restrict__ idx_out, float *__restrict__ dist_out) {
-    __shared__ uint32_t wsum[kRangeStrides][kRangeThreads / 64];
-    const uint32_t q = blockIdx.y, tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-    const size_t entry = (size_t)q * nblk + blockIdx.x;
-    if (cnt[entry] == 0) return;  // (uniform) nothing to write: the distances are not read again
-    const uint32_t *pq = pref + (size_t)q * (nprobe + 1);
-    const uint32_t *sq = seg + (size_t)q * nprobe;
-    const uint64_t len = min((uint64_t)pq[nprobe], wstride);
-    const float rad = radii[q];
-    const float *wq = W + (size_t)q * wstride;
-    const uint64_t pos0 = (uint64_t)blockIdx.x * kRangeRows;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    float v[kRangeStrides][4];
-    uint32_t hits[kRangeStrides], pre[kRangeStrides];  // pre: the stride's hits in lower lanes of this wave
-#pragma unroll
-    for (uint32_t s = 0; s < kRangeStrides; ++s) {
-        hits[s] = ivfr_load<VEC>(wq, len, pos0 + (uint64_t)s * (kRangeThreads * 4) + tid * 4, rad, v[s]);
-        uint32_t p = 0, t = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) {
-            const unsigned long long m = __ballot((hits[s] >> j) & 1u);
-            p += (uint32_t)__popcll(m & below);
-            t += (uint32_t)__popcll(m);
-        }
-        pre[s] = p;
-        if (lane == 0) wsum[s][wv] = t;
-    }
-    __syncthreads();
-    const unsigned long long at = off[entry];  // the block's first slot: 64-bit throughout
-    uint32_t run = 0;                          // the block's hits in front of (stride s, wave w), in position order
-#pragma unroll
-    for (uint32_t s = 0; s < kRangeStrides; ++s) {
-        uint32_t mine = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < kRangeThreads / 64; ++w) {
-            if (w == wv) mine = run;
-            run += wsum[s][w];
-        }
-        unsigned long long slot = at + mine + pre[s];
-        const uint64_t p0 = pos0 + (uint64_t)s * (kRangeThreads * 4) + tid * 4;
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j)
-            if ((hits[s] >> j) & 1u) {  // (a hit is below len <= pq[nprobe] < 2^32)
-                idx_out[slot] = ids[ivf_row(pq, sq, nprobe, (uint32_t)(p0 + j))];
-                dist_out[slot] = v[s][j];
-                ++slot;
-            }
-    }
-}
 
 // One stable pass of the segmented LSD radix sort over bits [shift, shift + 8) of the row id.  lims: the result's lims at
 // the batch's first query (lims[q] .. lims[q + 1] is query q's segment, from `base` = lims[0]); src / dst point at the
@@ -229,63 +110,43 @@ inline uint32_t ivfr_passes(uint64_t n) {
     return std::max<uint32_t>(1, (bits + 7) / 8);
 }
 
-// bytes of the stage's workspace for batches of up to qb queries of wstride positions: range.hpp's layout over
-// blocks of positions
-inline size_t ivfr_ws_size(uint64_t wstride, uint32_t qb) { return range_ws_size(wstride, qb); }
-
-// The stage over one batch: W [nb][wstride] on the device (queued on `stream`) with pref / seg [nb] of the batch's plan,
-// ids the index's row ids in list order (n rows in all), radii [nb] on the device, ws >= ivfr_ws_size(wstride, nb), q0
-// the batch's first query in the result.  *stage: the staging areas, grown here to the batch's hits (16 bytes each).
-// Waits for the stream once.  A batch that takes the result past max_results is VQHIP_ERR_UNSUPPORTED.
+// The stage over one batch v: W [nb][wstride] on the device (queued on `stream`) with the batch's plan in pref / seg,
+// radii [nb] on the device, ws >= range_ws_size(wstride, nb), q0 the batch's first query in the result.  *stage: the
+// staging areas, grown here to the batch's hits (16 bytes each).  Waits for the stream once.  A batch that takes the
+// result past max_results is VQHIP_ERR_UNSUPPORTED.
 // k_range_scan's one-workgroup bound holds unchanged: a batch of several queries keeps nb * wstride <= 2^28 floats of W
 // (ivf_batch, api.hip), so it has at most nb * ceil(wstride / 4096) <= 2^16 + nb entries, and a single-query batch at most
 // 2^20 (wstride < 2^32).
-inline int ivfr_batch(const float *W, uint64_t wstride, const uint32_t *pref, const uint32_t *seg, const uint32_t *ids, uint64_t n,
-                      uint32_t nb, uint32_t nprobe, uint32_t q0, const float *radii, void *ws, DevBuf *stage, uint64_t max_results,
+inline int ivfr_batch(const IvfBatchView &v, uint32_t q0, const float *radii, void *ws, DevBuf *stage, uint64_t max_results,
                       RangeOut *out, hipStream_t stream) {
-    const uint32_t nblk = range_blocks(wstride);
-    unsigned long long *total = reinterpret_cast<unsigned long long *>(ws);
-    unsigned long long *off = total + 2;
-    uint32_t *cnt = reinterpret_cast<uint32_t *>(off + (size_t)nb * nblk);
-    unsigned long long *lims = out->lims.as<unsigned long long>() + q0;  // lims[0] = out->total: the batch's first hit
-    const bool vec = (wstride & 3u) == 0;
-    const dim3 grid(nblk, nb), block(kRangeThreads);
-    if (vec) hipLaunchKernelGGL(k_ivfr_count<true>, grid, block, 0, stream, W, wstride, pref, nprobe, radii, nblk, cnt);
-    else hipLaunchKernelGGL(k_ivfr_count<false>, grid, block, 0, stream, W, wstride, pref, nprobe, radii, nblk, cnt);
-    VQ_LAUNCH_CHECK("k_ivfr_count");
-    hipLaunchKernelGGL(k_range_scan, dim3(1), dim3(1024), 0, stream, cnt, nb, nblk, (unsigned long long)out->total, off, lims + 1, total);
-    VQ_LAUNCH_CHECK("k_range_scan");
+    const uint64_t base = out->total;  // lims[q0] = base: the batch's first hit
+    const uint32_t passes = v.nprobe == 1 ? 0 : ivfr_passes(v.n);
+    uint32_t *res_idx = nullptr, *a_idx = nullptr, *b_idx = nullptr;
+    float *res_dist = nullptr, *a_dist = nullptr, *b_dist = nullptr;
     uint64_t got = 0;
-    VQ_TRY(range_room(total, nb, q0, max_results, out, &got, stream));
-    if (got == 0) return VQHIP_OK;
-    const uint64_t base = out->total;
-    uint32_t *res_idx = out->idx.as<uint32_t>() + base;
-    float *res_dist = out->dist.as<float>() + base;
-    const uint32_t passes = nprobe == 1 ? 0 : ivfr_passes(n);
-    // staging areas A and B of the batch: idx | dist each; B only where a pass has to land outside A and the result
-    uint32_t *a_idx = nullptr, *b_idx = nullptr;
-    float *a_dist = nullptr, *b_dist = nullptr;
-    if (passes) {
-        VQ_TRY(stage->ensure((size_t)got * 4 * (passes > 1 ? 4 : 2)));
-        a_idx = stage->as<uint32_t>();
-        a_dist = reinterpret_cast<float *>(a_idx + got);
-        if (passes > 1) {
-            b_idx = a_idx + 2 * got;
-            b_dist = reinterpret_cast<float *>(b_idx + got);
+    VQ_TRY(range_passes<IvffRows>({v.W, v.wstride, v.pref, v.seg, v.ids, v.nprobe}, v.nb, q0, radii, ws, max_results, out, &got, stream,
+                                  [&](uint64_t g, uint32_t **idx, float **dist) -> int {
+        res_idx = out->idx.as<uint32_t>() + base;
+        res_dist = out->dist.as<float>() + base;
+        // staging areas A and B of the batch: idx | dist each; B only where a pass has to land outside A and the result
+        if (passes) {
+            VQ_TRY(stage->ensure((size_t)g * 4 * (passes > 1 ? 4 : 2)));
+            a_idx = stage->as<uint32_t>();
+            a_dist = reinterpret_cast<float *>(a_idx + g);
+            if (passes > 1) {
+                b_idx = a_idx + 2 * g;
+                b_dist = reinterpret_cast<float *>(b_idx + g);
+            }
         }
-    }
-    uint32_t *fill_idx = passes ? a_idx : res_idx;
-    float *fill_dist = passes ? a_dist : res_dist;
-    if (vec)
-        hipLaunchKernelGGL(k_ivfr_fill<true>, grid, block, 0, stream, W, wstride, pref, seg, ids, nprobe, radii, nblk, cnt, off, fill_idx,
-                           fill_dist);
-    else
-        hipLaunchKernelGGL(k_ivfr_fill<false>, grid, block, 0, stream, W, wstride, pref, seg, ids, nprobe, radii, nblk, cnt, off, fill_idx,
-                           fill_dist);
-    VQ_LAUNCH_CHECK("k_ivfr_fill");
+        *idx = passes ? a_idx : res_idx;
+        *dist = passes ? a_dist : res_dist;
+        return VQHIP_OK;
+    }));
+    if (got == 0) return VQHIP_OK;
+    const unsigned long long *lims = out->lims.as<unsigned long long>() + q0;
     for (uint32_t p = 0; p < passes; ++p) {  // A -> B -> A ..., the last pass into the result
         const bool from_a = (p & 1u) == 0, last = p + 1 == passes;
-        hipLaunchKernelGGL(k_ivfr_sort, dim3(nb), dim3(kIvfrSortThreads), 0, stream, lims, (unsigned long long)base,
+        hipLaunchKernelGGL(k_ivfr_sort, dim3(v.nb), dim3(kIvfrSortThreads), 0, stream, lims, (unsigned long long)base,
                            from_a ? a_idx : b_idx, from_a ? a_dist : b_dist, last ? res_idx : (from_a ? b_idx : a_idx),
                            last ? res_dist : (from_a ? b_dist : a_dist), 8 * p);
         VQ_LAUNCH_CHECK("k_ivfr_sort");

@@ -194,23 +194,23 @@ __global__ __launch_bounds__(256) void k_ivff_scan(const float *__restrict__ Q, 
     }
 }
 
-// the two distance passes of a batch behind its plan: every D(q, i) of the probed lists into W, the key range into p
+// the two distance passes of a batch behind its plan: every D(q, i) of the probed lists into v.W, the key range into p
 template <class ROWS>
-int ivff_distances(const IvffPlan &p, int metric, const ROWS &rows, const float *rnorm, const uint32_t *off, uint32_t nlist,
-                   const float *queries, const float *qnorm, const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t chunk,
-                   uint64_t wstride, float *W, const uint32_t *pref, const uint32_t *seg, const uint32_t *inv, hipStream_t stream) {
-    const uint64_t items = (wstride + chunk - 1) / chunk;
+int ivff_distances(const IvffPlan &p, const IvfBatchView &v, int metric, const ROWS &rows, const float *rnorm, const float *queries,
+                   const float *qnorm, hipStream_t stream) {
+    const uint64_t items = (v.wstride + v.chunk - 1) / v.chunk;
     return knn_metric_dispatch(metric, [&](auto mtag) -> int {
         constexpr int M = decltype(mtag)::value;
         if (p.tiles_max > 0) {
             hipLaunchKernelGGL((k_ivff_tile<M, ROWS>), dim3((uint32_t)p.tiles_max, (uint32_t)p.cols), dim3(256), 0, stream, queries,
-                               rows.X, rows.d, rows.sc, qnorm, rnorm, off, nlist, p.cnt, p.lstart, p.tstart, inv, pref, nprobe, wstride,
-                               W, p.kmin, p.kmax);
+                               rows.X, rows.d, rows.sc, qnorm, rnorm, v.off, v.nlist, p.cnt, p.lstart, p.tstart, v.inv, v.pref, v.nprobe,
+                               v.wstride, v.W, p.kmin, p.kmax);
             VQ_LAUNCH_CHECK("k_ivff_tile");
         }
         if (items > 0) {
-            hipLaunchKernelGGL((k_ivff_scan<M, typename ROWS::Walk>), dim3((uint32_t)items, nb), dim3(256), 0, stream, queries, rows.X,
-                               rows.d, rows.sc, qnorm, rnorm, probe, p.cnt, pref, seg, nprobe, chunk, wstride, W, p.kmin, p.kmax);
+            hipLaunchKernelGGL((k_ivff_scan<M, typename ROWS::Walk>), dim3((uint32_t)items, v.nb), dim3(256), 0, stream, queries, rows.X,
+                               rows.d, rows.sc, qnorm, rnorm, v.probe, p.cnt, v.pref, v.seg, v.nprobe, v.chunk, v.wstride, v.W, p.kmin,
+                               p.kmax);
             VQ_LAUNCH_CHECK("k_ivff_scan");
         }
         return VQHIP_OK;

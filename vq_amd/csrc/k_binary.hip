@@ -412,7 +412,7 @@ int launch_binary_search(const uint32_t *P, uint64_t n, uint32_t d, int metric, 
 //                         LDS), k_bin_scan's lane-to-row mapping; every lane counts its hits per query in registers, the
 //                         counts are summed over the wave (shuffles) and the four waves (LDS) into cnt[q][blk]
 //   k_range_scan          (range.hpp) cnt -> off[q][blk] in query-major order, lims, the batch total
-//   range_room            (range.hpp) the 8-byte read, max_results, room for the hits
+//   range_scan_room       (range.hpp) that scan, then the 8-byte read, max_results, room for the hits
 //   k_bin_range<FILL>     the count's grid; a workgroup whose QG counts are all zero returns before it reads a row.  The
 //                         others recompute H; a hit of query q goes to base + off[q][blk] + its rank in the block.
 // Ascending row id within a block is the order (step, j, wave, lane) of the scan: a step is kScanBlock * kScanRR rows, row
@@ -603,9 +603,9 @@ uint32_t binary_range_batch(uint64_t n, uint32_t d, uint32_t nq) {
     return (uint32_t)nb;
 }
 
-// total | off [qb][nblk] u64 | cnt [qb][nblk] u32, qb = binary_range_batch(n, d, nq)
+// range.hpp's workspace over qb = binary_range_batch(n, d, nq) queries of bin_range_blocks(n) count entries
 size_t binary_range_ws_bytes(uint64_t n, uint32_t d, uint32_t nq) {
-    return 16 + (size_t)binary_range_batch(n, d, nq) * bin_range_blocks(n) * 12;
+    return range_ws_entries((size_t)binary_range_batch(n, d, nq) * bin_range_blocks(n));
 }
 
 int launch_binary_range(const uint32_t *P, uint64_t n, uint32_t d, int metric, const float *S, const float *queries_dev, float thr,
@@ -614,20 +614,15 @@ int launch_binary_range(const uint32_t *P, uint64_t n, uint32_t d, int metric, c
     VQ_TRY(range_begin(out, nq, max_results, stream));
     const uint32_t W = bin_words(d), nblk = bin_range_blocks(n), qb = binary_range_batch(n, d, nq);
     const int root = metric == VQHIP_EUCLIDEAN ? 1 : 0;
-    unsigned long long *total = reinterpret_cast<unsigned long long *>(range_ws);
-    unsigned long long *off = total + 2;
-    uint32_t *cnt = reinterpret_cast<uint32_t *>(off + (size_t)qb * nblk);
+    const RangeWs w = vqhip::range_ws(range_ws, qb, nblk);
     for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
         const uint32_t nb = std::min(qb, nq - q0);
         VQ_TRY(launch_bq_pack(queries_dev + (size_t)q0 * d, VQHIP_BINARY_F32, nb, d, thr, high, qw, stream));
-        VQ_TRY(bin_range_scan(BIN_COUNT, P, n, W, d, qw, nb, hcut + q0, nblk, cnt, off, 0, S, root, nullptr, nullptr, stream));
-        hipLaunchKernelGGL(k_range_scan, dim3(1), dim3(1024), 0, stream, cnt, nb, nblk, (unsigned long long)out->total, off,
-                           out->lims.as<unsigned long long>() + q0 + 1, total);
-        VQ_LAUNCH_CHECK("k_range_scan");
+        VQ_TRY(bin_range_scan(BIN_COUNT, P, n, W, d, qw, nb, hcut + q0, nblk, w.cnt, w.off, 0, S, root, nullptr, nullptr, stream));
         uint64_t got = 0;
-        VQ_TRY(range_room(total, nb, q0, max_results, out, &got, stream));
+        VQ_TRY(range_scan_room(w, nb, nblk, q0, max_results, out, &got, stream));
         if (got == 0) continue;
-        VQ_TRY(bin_range_scan(BIN_FILL, P, n, W, d, qw, nb, hcut + q0, nblk, cnt, off, (unsigned long long)out->total, S, root,
+        VQ_TRY(bin_range_scan(BIN_FILL, P, n, W, d, qw, nb, hcut + q0, nblk, w.cnt, w.off, (unsigned long long)out->total, S, root,
                               out->idx.as<uint32_t>(), out->dist.as<float>(), stream));
         out->total += got;
     }

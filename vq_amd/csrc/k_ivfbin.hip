@@ -6,9 +6,9 @@
 //   D(q, i) = S[H] (binary_table), sqrtf(S[H]) under Euclidean -- the form k_ivff_tile stores for the metric, so the
 //             selection stage orders and reports it unchanged; S and its root are strictly increasing, so (D, row id)
 //             orders like (H, row id).
-// Schedule of one batch (launch_ivfbin_search): section 14's, step for step --
-//   launch_bq_pack      the batch's queries as words Q [nb][W] (k_binary.hip)
+// Schedule of one batch: section 14's, step for step, with launch_ivfbin_distances as its distance passes --
 //   launch_ivff_plan    k_ivff_plan, k_ivff_lists, k_ivff_invert (k_ivfflat.hip): pref / seg, cnt, the inverted probe table
+//   launch_bq_pack      the batch's queries as words Q [nb][W] (k_binary.hip; the caller's, in front of the two passes)
 //   k_ivfbin_tile       k_ivff_tile's work item and write-back (ivf_tile_open, ivf_tile_store, knn_key_range) with both sides
 //                       as words: an 8 x 4 register block of H over chunks of 32 words in LDS, three 16-byte LDS reads per
 //                       64 VALU operations
@@ -16,8 +16,9 @@
 //                       query's words in LDS, one position per lane
 //   launch_ivff_select  k_ivff_hist and the selection stage over IvffSource (k_ivfflat.hip)
 // Which kernel computes a pair depends on the batch; H is an integer and both look D up in one table, so the bits do not.
-// A Hamming-radius range search (launch_ivfbin_range) puts the range stage (launch_ivff_range; DESIGN.md sections 17 and
-// 19) behind the same two distance passes (ivfbin_distances), as launch_ivfsq_range does.
+// A Hamming-radius range search puts the range stage (launch_ivff_range; DESIGN.md sections 17 and 19) behind the same
+// two distance passes, with radii [nb] f32 the reported distance of each query's Hamming radius, so that D <= radius iff
+// H <= that radius.
 // LW = words per load of the row loader (4, 2 or 1: 16, 8 or 4 bytes), chosen per launch from W and the base pointer.
 #include "common.hpp"
 #include "ivf_tile.hpp"
@@ -199,20 +200,21 @@ int bin_load_width(const uint32_t *P, uint32_t W) {
     return 1;
 }
 
-// the two distance passes of a batch behind its plan: every D(q, i) of the probed lists into W, the key range into p
-static int ivfbin_distances(const IvffPlan &p, int metric, const uint32_t *P, uint32_t d, const float *S, const uint32_t *off,
-                            uint32_t nlist, const uint32_t *Q, const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t chunk,
-                            uint64_t wstride, float *W, const uint32_t *pref, const uint32_t *seg, const uint32_t *inv,
-                            hipStream_t stream) {
+// The two distance passes of a batch behind its plan (kernels.hpp): every D(q, i) of the probed lists into v.W, the key
+// range into p.  Q [nb][bin_words(d)]: the batch's queries, packed (launch_bq_pack).
+int launch_ivfbin_distances(const IvffPlan &p, const IvfBatchView &v, int metric, const uint32_t *P, uint32_t d, const float *S,
+                            const uint32_t *Q, hipStream_t stream) {
+    if (v.nb == 0) return VQHIP_OK;
+    if (d == 0 || d > VQHIP_BINARY_MAX_DIM) return fail(VQHIP_ERR_INVALID_INPUT, "d %u must be in [1, 8192]", d);
     const uint32_t Wn = bin_words(d);
     const int lw = bin_load_width(P, Wn), root = metric == VQHIP_EUCLIDEAN ? 1 : 0;
     const size_t lds = ((size_t)d + 1) * 4;
-    const uint64_t items = (wstride + chunk - 1) / chunk;
+    const uint64_t items = (v.wstride + v.chunk - 1) / v.chunk;
     if (p.tiles_max > 0) {
         const dim3 grid((uint32_t)p.tiles_max, (uint32_t)p.cols);
         auto tile = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, Q, P, Wn, d, S, root, off, nlist, p.cnt, p.lstart, p.tstart, inv, pref,
-                               nprobe, wstride, W, p.kmin, p.kmax);
+            hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, Q, P, Wn, d, S, root, v.off, v.nlist, p.cnt, p.lstart, p.tstart, v.inv,
+                               v.pref, v.nprobe, v.wstride, v.W, p.kmin, p.kmax);
         };
         if (lw == 4) tile(k_ivfbin_tile<4>);
         else if (lw == 2) tile(k_ivfbin_tile<2>);
@@ -221,8 +223,8 @@ static int ivfbin_distances(const IvffPlan &p, int metric, const uint32_t *P, ui
     }
     if (items > 0) {
         auto scan = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3((uint32_t)items, nb), dim3(256), lds, stream, Q, P, Wn, d, S, root, probe, p.cnt, pref, seg,
-                               nprobe, chunk, wstride, W, p.kmin, p.kmax);
+            hipLaunchKernelGGL(kernel, dim3((uint32_t)items, v.nb), dim3(256), lds, stream, Q, P, Wn, d, S, root, v.probe, p.cnt, v.pref,
+                               v.seg, v.nprobe, v.chunk, v.wstride, v.W, p.kmin, p.kmax);
         };
         if (lw == 4) scan(k_ivfbin_scan<4>);
         else if (lw == 2) scan(k_ivfbin_scan<2>);
@@ -230,39 +232,6 @@ static int ivfbin_distances(const IvffPlan &p, int metric, const uint32_t *P, ui
         VQ_LAUNCH_CHECK("k_ivfbin_scan");
     }
     return VQHIP_OK;
-}
-
-// One batch of nb <= 1024 queries, packed (Q [nb][bin_words(d)], launch_bq_pack), whose probe lists (probe [nb][nprobe],
-// launch_knn_search over the f32 queries) are on the device.  P / ids / off: the index in list order, P [n][bin_words(d)];
-// S [d + 1] binary_table's; metric the reported distance's (VQHIP_EUCLIDEAN: the root of S).  The workspaces are
-// launch_ivfflat_search's.  Results [nb][topk] on the device.
-int launch_ivfbin_search(int metric, const uint32_t *P, uint32_t d, const float *S, const uint32_t *ids, const uint32_t *off,
-                         uint32_t nlist, uint64_t max_list, const uint32_t *Q, const uint32_t *probe, uint32_t nb, uint32_t nprobe,
-                         uint32_t topk, uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv,
-                         uint32_t *lists, void *state, unsigned long long *cand, uint32_t *idx_out, float *dist_out,
-                         hipStream_t stream) {
-    if (nb == 0) return VQHIP_OK;
-    if (d == 0 || d > VQHIP_BINARY_MAX_DIM) return fail(VQHIP_ERR_INVALID_INPUT, "d %u must be in [1, 8192]", d);
-    IvffPlan p;
-    VQ_TRY(launch_ivff_plan(off, nlist, max_list, probe, nb, nprobe, topk, pref, seg, inv, lists, state, &p, stream));
-    VQ_TRY(ivfbin_distances(p, metric, P, d, S, off, nlist, Q, probe, nb, nprobe, chunk, wstride, W, pref, seg, inv, stream));
-    return launch_ivff_select(p, W, wstride, pref, seg, ids, nb, nprobe, topk, cand, idx_out, dist_out, stream);
-}
-
-// launch_ivfbin_search's batch with the range stage behind the distances (launch_ivff_range, k_ivfflat.hip; DESIGN.md
-// section 19): the arguments of launch_ivfsq_range with the rows and the batch's queries as words.  radii [nb] f32 on the
-// device: the reported distance of each query's Hamming radius, so that D <= radius iff H <= that radius.
-int launch_ivfbin_range(int metric, const uint32_t *P, uint32_t d, const float *S, const uint32_t *ids, uint64_t n, const uint32_t *off,
-                        uint32_t nlist, uint64_t max_list, const uint32_t *Q, const uint32_t *probe, uint32_t nb, uint32_t nprobe,
-                        uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists,
-                        void *state, uint32_t q0, const float *radii, void *range_ws, DevBuf *stage, uint64_t max_results,
-                        RangeOut *out, hipStream_t stream) {
-    if (nb == 0) return VQHIP_OK;
-    if (d == 0 || d > VQHIP_BINARY_MAX_DIM) return fail(VQHIP_ERR_INVALID_INPUT, "d %u must be in [1, 8192]", d);
-    IvffPlan p;
-    VQ_TRY(launch_ivff_plan(off, nlist, max_list, probe, nb, nprobe, 1, pref, seg, inv, lists, state, &p, stream));
-    VQ_TRY(ivfbin_distances(p, metric, P, d, S, off, nlist, Q, probe, nb, nprobe, chunk, wstride, W, pref, seg, inv, stream));
-    return launch_ivff_range(W, wstride, pref, seg, ids, n, nb, nprobe, q0, radii, range_ws, stage, max_results, out, stream);
 }
 
 }  // namespace vqhip

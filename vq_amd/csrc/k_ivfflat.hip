@@ -6,7 +6,7 @@
 //   D(q, i) = the flat index's distance (knn_tile.hpp: knn_step from -0.0 over ascending dimensions, knn_finish),
 //   result  = the topk rows of S(q) by (adc_key(D), row id) ascending; Euclidean ordered by the reported root; padding
 //             (|S(q)| < topk) idx 0xFFFFFFFF, dist +inf.
-// Schedule of one batch (launch_ivfflat_search):
+// Schedule of one batch (launch_ivff_plan, launch_ivfflat_distances, launch_ivff_select):
 //   k_ivff_plan    each query's prefix over its probed lists' lengths; cnt[l] = the batch's queries that probe list l
 //   k_ivff_lists   prefix sums over the lists: lstart[l] (the list's run of the inverted table) and tstart[l] (its query
 //                  tiles; none for a list probed by fewer than kIvffTileMin queries)
@@ -17,10 +17,10 @@
 //   k_ivff_scan    the lists probed by fewer than kIvffTileMin queries: work item = one query x one chunk of its positions,
 //                  the query in LDS, one position per lane, the same per-pair operation order
 //   k_ivff_hist    the key-space histogram of W[q][0 .. |S(q)|) over the range the two kernels found (integer atomics)
-//   launch_topk_select over IvffSource: IvfSource's positions and ids, KnnSource's bins.
+//   launch_topk_select over IvffSource: IvffRows' positions and ids (ivf_plan.hpp), KnnSource's bins.
 // Which kernel computes a pair depends on the batch; both run one pair's operations in one order, so the bits do not.
-// A range search (launch_ivfflat_range) runs the plan and the two distance kernels as they are and then the range stage
-// over W (ivf_range.hpp) in place of the histogram and the selection.
+// A range search runs the plan and the two distance kernels as they are and then the range stage over W
+// (launch_ivff_range: ivf_range.hpp) in place of the histogram and the selection.
 // The two distance kernels and ivff_distances live in ivf_tile.hpp, templated on the row source, and serve the SQ codes
 // of k_ivfsq.hip too; this file instantiates them over dense f32 / f16 rows and holds the stages every inverted-file
 // search over W shares (plan, lists, inverted table, histogram, selection, range).
@@ -116,27 +116,16 @@ __global__ __launch_bounds__(256) void k_ivff_hist(const float *__restrict__ W, 
         if (h[e]) atomicAdd(&hist[(size_t)q * kAdcBins + e], h[e]);
 }
 
-// the two kernels' output as a source of the selection stage (topk.hpp): IvfSource's positions and row ids (k_ivf.hip),
+// the two kernels' output as a source of the selection stage (topk.hpp): IvffRows' positions and row ids (ivf_plan.hpp),
 // KnnSource's key bins over [kmin[q], kmax[q]] (knn_tile.hpp)
-struct IvffSource {
-    using Pos = uint32_t;
-    const float *W;
-    uint64_t wstride;
-    const uint32_t *pref, *seg, *ids;
-    uint32_t nprobe;
+struct IvffSource : IvffRows {
     const uint32_t *kmin, *kmax;
-    uint32_t total = 0, lo = 0, hi = 0;  // (device: of the opened query)
+    uint32_t lo = 0, hi = 0;  // (device: of the opened query)
     __device__ void open(uint32_t q) {
-        W += (size_t)q * wstride;
-        pref += (size_t)q * (nprobe + 1);
-        seg += (size_t)q * nprobe;
-        total = (uint32_t)min((uint64_t)pref[nprobe], wstride);
+        IvffRows::open(q);
         lo = kmin[q];
         hi = kmax[q];
     }
-    __device__ Pos count() const { return total; }
-    __device__ float at(Pos pos) const { return W[pos]; }
-    __device__ uint32_t id(Pos pos) const { return ids[ivf_row(pref, seg, nprobe, pos)]; }
     __device__ uint32_t bin(float dval) const { return knn_bin(adc_key(dval), lo, hi); }
     uint32_t blocks() const { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((wstride + 255) / 256, 1), 64); }
 };
@@ -146,95 +135,63 @@ struct IvffSource {
 // cnt | fill | lstart | tstart of a batch: [nlist] + [nlist] + [nlist + 1] + [nlist + 1] words (cnt and fill zeroed per batch)
 size_t ivfflat_lists_bytes(uint32_t nlist) { return ((size_t)4 * nlist + 2) * 4; }
 
-// The stages of a batch before its distance passes, shared with k_ivfsq.hip: the batch's checks, the zeroed state, then
-// k_ivff_plan, k_ivff_lists and k_ivff_invert.  *p: where the distance passes find cnt / lstart / tstart and the key
+// The stages of a batch before its distance passes, the same for the three indexes: the batch's checks, the zeroed state,
+// then k_ivff_plan, k_ivff_lists and k_ivff_invert.  *p: where the distance passes find cnt / lstart / tstart and the key
 // range, and the grid of the tile kernel.
-int launch_ivff_plan(const uint32_t *off, uint32_t nlist, uint64_t max_list, const uint32_t *probe, uint32_t nb, uint32_t nprobe,
-                     uint32_t topk, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state, IvffPlan *p,
-                     hipStream_t stream) {
+int launch_ivff_plan(const IvfBatchView &v, uint32_t topk, IvffPlan *p, hipStream_t stream) {
+    const uint32_t nb = v.nb, nprobe = v.nprobe, nlist = v.nlist;
+    *p = IvffPlan{};
+    if (nb == 0) return VQHIP_OK;  // (no tiles: the distance passes and the stages behind them have nothing to do either)
     if (nb > 1024) return fail(VQHIP_ERR_INVALID_INPUT, "a batch holds at most 1024 queries");
     if (nprobe == 0 || nprobe > 1024) return fail(VQHIP_ERR_INVALID_INPUT, "nprobe must be in [1, 1024]");
     if (topk == 0 || topk > 1024) return fail(VQHIP_ERR_INVALID_INPUT, "topk must be in [1, 1024]");
-    uint32_t *cnt = lists, *fill = cnt + nlist, *lstart = fill + nlist, *tstart = lstart + nlist + 1;
-    uint32_t *kmin = reinterpret_cast<uint32_t *>(state), *kmax = kmin + nb;
+    uint32_t *cnt = v.lists, *fill = cnt + nlist, *lstart = fill + nlist, *tstart = lstart + nlist + 1;
+    uint32_t *kmin = reinterpret_cast<uint32_t *>(v.state), *kmax = kmin + nb;
     VQ_HIP(hipMemsetAsync(cnt, 0, (size_t)2 * nlist * 4, stream));
     VQ_HIP(hipMemsetAsync(kmin, 0xFF, (size_t)nb * 4, stream));
     VQ_HIP(hipMemsetAsync(kmax, 0, knn_state_bytes(nb) - (size_t)nb * 4, stream));
-    hipLaunchKernelGGL(k_ivff_plan, dim3(nb), dim3(1024), 0, stream, probe, nprobe, nlist, off, pref, seg, cnt);
+    hipLaunchKernelGGL(k_ivff_plan, dim3(nb), dim3(1024), 0, stream, v.probe, nprobe, nlist, v.off, v.pref, v.seg, cnt);
     VQ_LAUNCH_CHECK("k_ivff_plan");
     hipLaunchKernelGGL(k_ivff_lists, dim3(1), dim3(1024), 0, stream, cnt, nlist, lstart, tstart);
     VQ_LAUNCH_CHECK("k_ivff_lists");
-    hipLaunchKernelGGL(k_ivff_invert, dim3(nb), dim3(1024), 0, stream, probe, nprobe, nlist, off, lstart, fill, inv);
+    hipLaunchKernelGGL(k_ivff_invert, dim3(nb), dim3(1024), 0, stream, v.probe, nprobe, nlist, v.off, lstart, fill, v.inv);
     VQ_LAUNCH_CHECK("k_ivff_invert");
     // the tiles the batch can have: a list with tiles has at least kIvffTileMin pairs and one partial tile
     const uint64_t pairs = (uint64_t)nb * nprobe;
     const uint64_t tiles_max = std::min<uint64_t>(nlist, pairs / kIvffTileMin) + pairs / kKnnTQ;
     // about eight workgroups per CU in all: columns of row tiles per query tile, at most the largest list's
-    const uint64_t nrt = std::max<uint64_t>(1, (max_list + kKnnTR - 1) / kKnnTR);
+    const uint64_t nrt = std::max<uint64_t>(1, (v.max_list + kKnnTR - 1) / kKnnTR);
     const uint64_t cols = tiles_max ? std::min<uint64_t>({nrt, 64, ((uint64_t)num_cus() * 8 + tiles_max - 1) / tiles_max}) : 0;
     *p = IvffPlan{cnt, lstart, tstart, kmin, kmax, kmax + nb, tiles_max, cols};
     return VQHIP_OK;
 }
 
 // The stages behind the distance passes: k_ivff_hist over W and the selection stage over IvffSource.
-int launch_ivff_select(const IvffPlan &p, const float *W, uint64_t wstride, const uint32_t *pref, const uint32_t *seg,
-                       const uint32_t *ids, uint32_t nb, uint32_t nprobe, uint32_t topk, unsigned long long *cand, uint32_t *idx_out,
+int launch_ivff_select(const IvffPlan &p, const IvfBatchView &v, uint32_t topk, unsigned long long *cand, uint32_t *idx_out,
                        float *dist_out, hipStream_t stream) {
-    const TopkState st = topk_state(p.topk_ws, nb);
-    const IvffSource src{W, wstride, pref, seg, ids, nprobe, p.kmin, p.kmax};
-    hipLaunchKernelGGL(k_ivff_hist, dim3(src.blocks(), nb), dim3(256), 0, stream, W, wstride, pref, nprobe, p.kmin, p.kmax, st.hist);
+    if (v.nb == 0) return VQHIP_OK;
+    const TopkState st = topk_state(p.topk_ws, v.nb);
+    const IvffSource src{{v.W, v.wstride, v.pref, v.seg, v.ids, v.nprobe}, p.kmin, p.kmax};
+    hipLaunchKernelGGL(k_ivff_hist, dim3(src.blocks(), v.nb), dim3(256), 0, stream, v.W, v.wstride, v.pref, v.nprobe, p.kmin, p.kmax,
+                       st.hist);
     VQ_LAUNCH_CHECK("k_ivff_hist");
-    return launch_topk_select(src, nb, topk, 0, st, cand, idx_out, dist_out, stream);
+    return launch_topk_select(src, v.nb, topk, 0, st, cand, idx_out, dist_out, stream);
 }
 
-// The range stage behind the distance passes, shared with k_ivfsq.hip (ivf_range.hpp).
-size_t ivff_range_ws_bytes(uint64_t wstride, uint32_t nb) { return ivfr_ws_size(wstride, nb); }
-int launch_ivff_range(const float *W, uint64_t wstride, const uint32_t *pref, const uint32_t *seg, const uint32_t *ids, uint64_t n,
-                      uint32_t nb, uint32_t nprobe, uint32_t q0, const float *radii, void *range_ws, DevBuf *stage,
-                      uint64_t max_results, RangeOut *out, hipStream_t stream) {
-    return ivfr_batch(W, wstride, pref, seg, ids, n, nb, nprobe, q0, radii, range_ws, stage, max_results, out, stream);
-}
-int launch_ivff_range_begin(RangeOut *out, uint32_t nq, uint64_t max_results, hipStream_t stream) {
-    return range_begin(out, nq, max_results, stream);
+// The range stage behind the distance passes (ivf_range.hpp).  The key range the distance passes write into state is not
+// read.
+size_t ivff_range_ws_bytes(uint64_t wstride, uint32_t nb) { return range_ws_size(wstride, nb); }
+int launch_ivff_range(const IvfBatchView &v, uint32_t q0, const float *radii, void *range_ws, DevBuf *stage, uint64_t max_results,
+                      RangeOut *out, hipStream_t stream) {
+    if (v.nb == 0) return VQHIP_OK;
+    return ivfr_batch(v, q0, radii, range_ws, stage, max_results, out, stream);
 }
 
-// One batch of nb <= 1024 queries (queries [nb][d] f32, qnorm [nb] under the cosines) whose probe lists
-// (probe [nb][nprobe], launch_knn_search) are on the device.  X / rnorm / ids / off: the index in list order.  W
-// [nb][wstride] with wstride >= every |S(q)|; pref [nb][nprobe + 1], seg and inv [nb][nprobe], lists >=
-// ivfflat_lists_bytes(nlist), state >= knn_state_bytes(nb), cand >= topk_cand_bytes(nb); max_list: the rows of the
-// largest list.  Results [nb][topk] on the device.
-int launch_ivfflat_search(int metric, const void *X, int dtype, uint32_t d, const float *rnorm, const uint32_t *ids,
-                          const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
-                          const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
-                          float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state,
-                          unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream) {
-    if (nb == 0) return VQHIP_OK;
-    IvffPlan p;
-    VQ_TRY(launch_ivff_plan(off, nlist, max_list, probe, nb, nprobe, topk, pref, seg, inv, lists, state, &p, stream));
-    VQ_TRY(knn_dense_rows(X, dtype, d, [&](auto rows) {
-        return ivff_distances(p, metric, rows, rnorm, off, nlist, queries, qnorm, probe, nb, nprobe, chunk, wstride, W, pref, seg, inv,
-                              stream);
-    }));
-    return launch_ivff_select(p, W, wstride, pref, seg, ids, nb, nprobe, topk, cand, idx_out, dist_out, stream);
-}
-
-// launch_ivfflat_search's batch with the range stage behind the distances: the batch's hits (radii [nb] on the device)
-// go into *out behind the out->total it has, as queries q0 .. q0 + nb of the result.  n: the index's rows; range_ws >=
-// ivff_range_ws_bytes(wstride, nb).  The plan's topk check is given 1; the key range the distance passes write into
-// state is not read.  Waits for the stream once.
-int launch_ivfflat_range(int metric, const void *X, int dtype, uint32_t d, const float *rnorm, const uint32_t *ids, uint64_t n,
-                         const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
-                         const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref,
-                         uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state, uint32_t q0, const float *radii, void *range_ws,
-                         DevBuf *stage, uint64_t max_results, RangeOut *out, hipStream_t stream) {
-    if (nb == 0) return VQHIP_OK;
-    IvffPlan p;
-    VQ_TRY(launch_ivff_plan(off, nlist, max_list, probe, nb, nprobe, 1, pref, seg, inv, lists, state, &p, stream));
-    VQ_TRY(knn_dense_rows(X, dtype, d, [&](auto rows) {
-        return ivff_distances(p, metric, rows, rnorm, off, nlist, queries, qnorm, probe, nb, nprobe, chunk, wstride, W, pref, seg, inv,
-                              stream);
-    }));
-    return launch_ivff_range(W, wstride, pref, seg, ids, n, nb, nprobe, q0, radii, range_ws, stage, max_results, out, stream);
+// The distance passes of a batch over dense f32 / f16 rows.
+int launch_ivfflat_distances(const IvffPlan &p, const IvfBatchView &v, int metric, const void *X, int dtype, uint32_t d,
+                             const float *rnorm, const float *queries, const float *qnorm, hipStream_t stream) {
+    if (v.nb == 0) return VQHIP_OK;
+    return knn_dense_rows(X, dtype, d, [&](auto rows) { return ivff_distances(p, v, metric, rows, rnorm, queries, qnorm, stream); });
 }
 
 }  // namespace vqhip

@@ -40,6 +40,9 @@ uint32_t knn_query_batch(uint64_t n, uint32_t nq) {
 size_t knn_state_bytes(uint32_t qb) { return (size_t)qb * 2 * 4 + topk_state_bytes(qb); }
 
 size_t range_ws_bytes(uint64_t n, uint32_t nq) { return range_ws_size(n, knn_query_batch(n, nq)); }
+int launch_range_begin(RangeOut *out, uint32_t nq, uint64_t max_results, hipStream_t stream) {
+    return range_begin(out, nq, max_results, stream);
+}
 
 int launch_knn_search(int metric, const void *X, int dtype, uint64_t n, uint32_t d, const float *rnorm, const float *queries_dev,
                       const float *qnorm_dev, uint32_t nq, uint32_t topk, float *dist_ws, void *state_ws,

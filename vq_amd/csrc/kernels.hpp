@@ -291,18 +291,29 @@ int launch_ivf_rsearch(const uint8_t *codes, const uint32_t *ids, const uint32_t
                        const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
                        float *tabs, float *mm, float *W, uint32_t *pref, uint32_t *seg, float *bounds, void *state,
                        unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream);
-// inverted-file search over list-ordered rows (k_ivfflat.hip): one batch of nb <= 1024 queries whose probe lists are on the
-// device; X [n][d] f32 (dtype 0) or f16 bits (dtype 1) and rnorm [n] in list order, W [nb][wstride] (wstride >= every
-// query's |S(q)|), pref [nb][nprobe + 1], seg and inv [nb][nprobe], lists >= ivfflat_lists_bytes(nlist), state >=
-// knn_state_bytes(nb), cand >= topk_cand_bytes(nb); max_list the rows of the largest list
+// Inverted-file search over list-ordered rows, SQ codes or packed BQ words (k_ivfflat.hip, k_ivfsq.hip, k_ivfbin.hip).
+// One batch of nb <= 1024 queries whose probe lists are on the device, as every stage of it sees it:
+struct IvfBatchView {
+    // the index in list order: list l holds the rows ids[off[l] .. off[l + 1]); n rows in all, max_list in the largest list
+    const uint32_t *ids;
+    uint64_t n;
+    const uint32_t *off;
+    uint32_t nlist;
+    uint64_t max_list;
+    // the batch: probe [nb][nprobe] (launch_knn_search), positions per item of the scan kernels, floats of W per query
+    const uint32_t *probe;
+    uint32_t nb, nprobe, chunk;
+    uint64_t wstride;
+    // its workspaces: W [nb][wstride] (wstride >= every query's |S(q)|), pref [nb][nprobe + 1], seg and inv [nb][nprobe],
+    // lists >= ivfflat_lists_bytes(nlist), state >= knn_state_bytes(nb)
+    float *W;
+    uint32_t *pref, *seg, *inv, *lists;
+    void *state;
+};
 size_t ivfflat_lists_bytes(uint32_t nlist);
-int launch_ivfflat_search(int metric, const void *X, int dtype, uint32_t d, const float *rnorm, const uint32_t *ids,
-                          const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
-                          const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
-                          float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state,
-                          unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream);
-// the stages of such a batch around its distance passes (k_ivfflat.hip), shared with the search over SQ codes: plan =
-// the batch's checks, the zeroed state, k_ivff_plan / _lists / _invert; select = k_ivff_hist and the selection stage.
+// The stages of a batch around its distance passes (k_ivfflat.hip), the same for the three indexes: plan = the batch's
+// checks, the zeroed state, k_ivff_plan / _lists / _invert (topk: the selection's, 1 in front of a range stage); select
+// = k_ivff_hist and the selection stage, results [nb][topk] on the device, cand >= topk_cand_bytes(nb).
 // IvffPlan: the per-list counts and starts (in lists), the key range (in state) and the tile kernel's grid.
 struct IvffPlan {
     const uint32_t *cnt, *lstart, *tstart;
@@ -310,28 +321,22 @@ struct IvffPlan {
     void *topk_ws;             // the selection stage's state, behind kmin / kmax
     uint64_t tiles_max, cols;  // query tiles the batch can have; columns of row tiles per query tile (0: no tile kernel)
 };
-int launch_ivff_plan(const uint32_t *off, uint32_t nlist, uint64_t max_list, const uint32_t *probe, uint32_t nb, uint32_t nprobe,
-                     uint32_t topk, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state, IvffPlan *p,
-                     hipStream_t stream);
-int launch_ivff_select(const IvffPlan &p, const float *W, uint64_t wstride, const uint32_t *pref, const uint32_t *seg,
-                       const uint32_t *ids, uint32_t nb, uint32_t nprobe, uint32_t topk, unsigned long long *cand, uint32_t *idx_out,
+int launch_ivff_plan(const IvfBatchView &v, uint32_t topk, IvffPlan *p, hipStream_t stream);
+int launch_ivff_select(const IvffPlan &p, const IvfBatchView &v, uint32_t topk, unsigned long long *cand, uint32_t *idx_out,
                        float *dist_out, hipStream_t stream);
-// inverted-file search over list-ordered SQ codes (k_ivfsq.hip): launch_ivfflat_search with the rows as C [n][d] u8,
-// v(c) = mn + (float)c * step decoded on the fly, rnorm [n] from launch_sq_norms over C (cosine only); the same workspaces
-int launch_ivfsq_search(int metric, const uint8_t *C, uint32_t d, float mn, float step, const float *rnorm, const uint32_t *ids,
-                        const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
-                        const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
-                        float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state,
-                        unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream);
-// inverted-file search over list-ordered packed BQ words (k_ivfbin.hip): launch_ivfflat_search with the rows as P
-// [n][bin_words(d)] and the batch's queries packed the same way (Q [nb][bin_words(d)], launch_bq_pack); D = S[H], its root
-// under VQHIP_EUCLIDEAN, S [d + 1] binary_table's on the device; the same workspaces
+// The two distance passes of a batch behind its plan, what an index has of its own: every D(q, i) of the probed lists
+// into v.W, the key range into p.  queries [nb][d] f32, qnorm [nb] under the cosines; rows in list order:
+//   ivfflat  X [n][d] f32 (dtype 0) or f16 bits (dtype 1), rnorm [n] under the cosines
+//   ivfsq    C [n][d] u8, v(c) = mn + (float)c * step decoded on the fly, rnorm [n] from launch_sq_norms over C
+//   ivfbin   P [n][bin_words(d)] and the batch's queries packed the same way (Q [nb][bin_words(d)], launch_bq_pack);
+//            D = S[H], its root under VQHIP_EUCLIDEAN, S [d + 1] binary_table's on the device
+int launch_ivfflat_distances(const IvffPlan &p, const IvfBatchView &v, int metric, const void *X, int dtype, uint32_t d,
+                             const float *rnorm, const float *queries, const float *qnorm, hipStream_t stream);
+int launch_ivfsq_distances(const IvffPlan &p, const IvfBatchView &v, int metric, const uint8_t *C, uint32_t d, float mn, float step,
+                           const float *rnorm, const float *queries, const float *qnorm, hipStream_t stream);
 int bin_load_width(const uint32_t *P, uint32_t W);
-int launch_ivfbin_search(int metric, const uint32_t *P, uint32_t d, const float *S, const uint32_t *ids, const uint32_t *off,
-                         uint32_t nlist, uint64_t max_list, const uint32_t *Q, const uint32_t *probe, uint32_t nb, uint32_t nprobe,
-                         uint32_t topk, uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv,
-                         uint32_t *lists, void *state, unsigned long long *cand, uint32_t *idx_out, float *dist_out,
-                         hipStream_t stream);
+int launch_ivfbin_distances(const IvffPlan &p, const IvfBatchView &v, int metric, const uint32_t *P, uint32_t d, const float *S,
+                            const uint32_t *Q, hipStream_t stream);
 // exact k-NN search over resident rows and exact rerank of candidate lists (k_knn.hip); X [n][d] f32 (dtype 0) or f16
 // bits (dtype 1), rnorm [n] the rows' norms (cosine only, else unused)
 int launch_knn_norms(const void *X, int dtype, uint64_t n, uint32_t d, float *out, hipStream_t stream);
@@ -353,6 +358,8 @@ struct RangeOut {
 };
 // workspace of the range stage for batches of knn_query_batch(n, nq) queries
 size_t range_ws_bytes(uint64_t n, uint32_t nq);
+// an empty result for nq queries (range.hpp's range_begin): lims[0] = 0, room for min(kRangeInitCap, max_results) hits
+int launch_range_begin(RangeOut *out, uint32_t nq, uint64_t max_results, hipStream_t stream);
 // launch_knn_search's arguments with radii_dev [nq] f32 and max_results >= 1 in place of topk, range_ws >=
 // range_ws_bytes(n, nq) in place of the candidates; state_ws is written (kmin / kmax) and not read.  Waits for the
 // stream once per batch and once at the end: *out is complete on return.  More than max_results hits:
@@ -364,32 +371,14 @@ int launch_sq_range(int metric, const uint8_t *C, uint64_t n, uint32_t d, float 
                     const float *queries_dev, const float *qnorm_dev, uint32_t nq, const float *radii_dev, uint64_t max_results,
                     float *dist_ws, void *state_ws, void *range_ws, RangeOut *out, hipStream_t stream);
 
-// exact range search over the probed lists (ivf_range.hpp behind k_ivfflat.hip and k_ivfsq.hip): launch_ivfflat_search's
-// / launch_ivfsq_search's batch with radii [nb] on the device and the range stage in place of the selection.  The
-// batch's hits go into *out (begun by launch_ivff_range_begin) as queries q0 .. q0 + nb, in ascending row id per query; n:
-// the index's rows; range_ws >= ivff_range_ws_bytes(wstride, nb); *stage: the staging areas, grown as needed.  Waits for
-// the stream once per batch.  More than max_results hits: VQHIP_ERR_UNSUPPORTED.
+// exact range search over the probed lists (ivf_range.hpp behind k_ivfflat.hip): the range stage in place of the
+// selection behind a batch's distance passes, radii [nb] on the device (for the binary index the reported distance of each
+// query's Hamming radius).  The batch's hits go into *out (begun by launch_range_begin) as queries q0 .. q0 + nb, in
+// ascending row id per query; range_ws >= ivff_range_ws_bytes(wstride, nb); *stage: the staging areas, grown as needed.
+// Waits for the stream once per batch.  More than max_results hits: VQHIP_ERR_UNSUPPORTED.
 size_t ivff_range_ws_bytes(uint64_t wstride, uint32_t nb);
-int launch_ivff_range_begin(RangeOut *out, uint32_t nq, uint64_t max_results, hipStream_t stream);
-int launch_ivff_range(const float *W, uint64_t wstride, const uint32_t *pref, const uint32_t *seg, const uint32_t *ids, uint64_t n,
-                      uint32_t nb, uint32_t nprobe, uint32_t q0, const float *radii, void *range_ws, DevBuf *stage,
-                      uint64_t max_results, RangeOut *out, hipStream_t stream);
-int launch_ivfflat_range(int metric, const void *X, int dtype, uint32_t d, const float *rnorm, const uint32_t *ids, uint64_t n,
-                         const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
-                         const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref,
-                         uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state, uint32_t q0, const float *radii, void *range_ws,
-                         DevBuf *stage, uint64_t max_results, RangeOut *out, hipStream_t stream);
-int launch_ivfsq_range(int metric, const uint8_t *C, uint32_t d, float mn, float step, const float *rnorm, const uint32_t *ids, uint64_t n,
-                       const uint32_t *off, uint32_t nlist, uint64_t max_list, const float *queries, const float *qnorm,
-                       const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref,
-                       uint32_t *seg, uint32_t *inv, uint32_t *lists, void *state, uint32_t q0, const float *radii, void *range_ws,
-                       DevBuf *stage, uint64_t max_results, RangeOut *out, hipStream_t stream);
-// the same behind launch_ivfbin_search's distances: radii [nb] the reported distance of each query's Hamming radius
-int launch_ivfbin_range(int metric, const uint32_t *P, uint32_t d, const float *S, const uint32_t *ids, uint64_t n, const uint32_t *off,
-                        uint32_t nlist, uint64_t max_list, const uint32_t *Q, const uint32_t *probe, uint32_t nb, uint32_t nprobe,
-                        uint32_t chunk, uint64_t wstride, float *W, uint32_t *pref, uint32_t *seg, uint32_t *inv, uint32_t *lists,
-                        void *state, uint32_t q0, const float *radii, void *range_ws, DevBuf *stage, uint64_t max_results,
-                        RangeOut *out, hipStream_t stream);
+int launch_ivff_range(const IvfBatchView &v, uint32_t q0, const float *radii, void *range_ws, DevBuf *stage, uint64_t max_results,
+                      RangeOut *out, hipStream_t stream);
 
 // exact search and rerank over resident SQ codes (k_sqindex.hip): C [n][d] u8, v(c) = mn + (float)c * step decoded on
 // the fly, rnorm [n] the decoded rows' norms (cosine only).  Batches and workspaces as launch_knn_search / _rerank; the

@@ -99,10 +99,16 @@ __device__ __forceinline__ uint32_t adc_bin(float dval, float lo, float scale) {
 // the dense part of a source: dist[q][n], the row id is the position (offsets q * n + pos stay 64-bit)
 struct TopkRows {
     using Pos = uint64_t;
+    static constexpr bool kRagged = false;  // (range.hpp) every position of a query's row counts
     const float *dist;
     uint64_t n;
+    // (range.hpp) from the range kernels' arguments: a dense source has no plan and no ids
+    static __device__ TopkRows rows(const float *dist, uint64_t n, const uint32_t *, const uint32_t *, const uint32_t *, uint32_t) {
+        return {dist, n};
+    }
     __device__ void open(uint32_t q) { dist += (size_t)q * n; }
     __device__ Pos count() const { return n; }
+    __device__ const float *row() const { return dist; }
     __device__ float at(Pos pos) const { return dist[pos]; }
     __device__ uint32_t id(Pos pos) const { return (uint32_t)pos; }
 };
