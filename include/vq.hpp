@@ -671,7 +671,22 @@ struct RangeResult {
     std::vector<float> dist;          // [total]
 };
 
+// The row mask of a filtered call (include/vqhip.h): ceil(n / 32) words, row i allowed iff bit i & 31 of word i >> 5 is set.
+inline std::vector<std::uint32_t> pack_row_mask(const std::vector<bool> &allowed) {
+    std::vector<std::uint32_t> w((allowed.size() + 31) / 32, 0u);
+    for (std::size_t i = 0; i < allowed.size(); ++i)
+        if (allowed[i]) w[i >> 5] |= 1u << (i & 31);
+    return w;
+}
+
 namespace detail {
+// the argument checks of a filtered call, before the library is called: the mask's pointer; its length as a vector
+inline void check_row_mask(const std::uint32_t *allowed) {
+    if (!allowed) throw VqError::InvalidParameter("allowed", "the row mask is null");
+}
+inline void check_row_mask(const std::vector<std::uint32_t> &allowed, std::size_t n) {
+    if (allowed.size() != (n + 31) / 32) throw VqError::DimensionMismatch((n + 31) / 32, allowed.size());
+}
 struct RangeDel {
     void operator()(vqhip_range *p) const { (void)vqhip_range_destroy(p); }
 };
@@ -748,12 +763,51 @@ class ResidentIndex {
 // The two indexes of exact distances (FlatIndex, ScalarIndex) also answer range queries and rerank a caller's candidates.
 template <class H, int (*Destroy)(H *), int (*Search)(H *, const float *, std::uint32_t, std::uint32_t, std::uint32_t *, float *),
           int (*Range)(H *, const float *, std::uint32_t, const float *, std::uint64_t, vqhip_range **),
-          int (*Rerank)(H *, const float *, std::uint32_t, const std::uint32_t *, std::uint32_t, std::uint32_t, std::uint32_t *, float *)>
+          int (*Rerank)(H *, const float *, std::uint32_t, const std::uint32_t *, std::uint32_t, std::uint32_t, std::uint32_t *, float *),
+          int (*SearchMasked)(H *, const float *, std::uint32_t, std::uint32_t, const std::uint32_t *, std::uint32_t *, float *),
+          int (*RangeMasked)(H *, const float *, std::uint32_t, const float *, std::uint64_t, const std::uint32_t *, vqhip_range **)>
 class ExactResidentIndex : public ResidentIndex<H, Destroy, Search> {
     using Base = ResidentIndex<H, Destroy, Search>;
 
    public:
     using Result = typename Base::Result;
+    using Base::search;
+    // The filtered forms: `allowed` is the row mask of the call, ceil(n / 32) words (pack_row_mask).  search: the nearest
+    // among the allowed rows; a query with fewer than topk of them has idx 0xFFFFFFFF / dist +inf behind them.
+    Result search(const float *queries, std::size_t nq, std::size_t topk, const std::uint32_t *allowed) const {
+        check_row_mask(allowed);
+        if (topk == 0 || topk > 1024 || topk > this->n_)
+            throw VqError::InvalidParameter("topk", "must be between 1 and min(n, 1024)");
+        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
+        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
+        if (nq)
+            check(SearchMasked(this->ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)topk, allowed, r.idx.data(), r.dist.data()));
+        return r;
+    }
+    Result search(const std::vector<float> &queries, std::size_t topk, const std::vector<std::uint32_t> &allowed) const {
+        check_row_mask(allowed, this->n_);
+        if (queries.size() % this->dim_) throw VqError::DimensionMismatch(this->dim_, queries.size() % this->dim_);
+        return search(queries.data(), queries.size() / this->dim_, topk, allowed.data());
+    }
+    // range_search over the allowed rows only (the mask comes last: max_results has no default here, so that a literal 0
+    // in its place never reads as a null mask)
+    RangeResult range_search(const float *queries, std::size_t nq, const float *radii, std::uint64_t max_results,
+                             const std::uint32_t *allowed) const {
+        check_row_mask(allowed);
+        check_range_args(radii, nq, max_results);
+        if (nq == 0) return RangeResult{std::vector<std::uint64_t>(1, 0), {}, {}};
+        vqhip_range *r = nullptr;
+        check(RangeMasked(this->ix_.get(), queries, (std::uint32_t)nq, radii, max_results, allowed, &r));
+        return read_range(r);
+    }
+    RangeResult range_search(const std::vector<float> &queries, const std::vector<float> &radii, std::uint64_t max_results,
+                             const std::vector<std::uint32_t> &allowed) const {
+        const std::size_t dim = this->dim_;
+        check_row_mask(allowed, this->n_);
+        if (queries.size() % dim) throw VqError::DimensionMismatch(dim, queries.size() % dim);
+        if (radii.size() != queries.size() / dim) throw VqError::DimensionMismatch(queries.size() / dim, radii.size());
+        return range_search(queries.data(), queries.size() / dim, radii.data(), max_results, allowed.data());
+    }
     // every row within radii[q] of query q (radii [nq], none NaN), at most max_results hits in all (more: FfiError)
     RangeResult range_search(const float *queries, std::size_t nq, const float *radii, std::uint64_t max_results = std::uint64_t(1) << 28) const {
         check_range_args(radii, nq, max_results);
@@ -788,7 +842,8 @@ class ExactResidentIndex : public ResidentIndex<H, Destroy, Search> {
 // Exact k-NN search over rows kept on the device (include/vqhip.h, vqhip_flat_*): rows [n][dim] f32 or f16, uploaded once
 // by the constructor; search / rerank give (row index, distance) pairs [nq][topk], nearest first, NaN last, ties to the
 // lower row.  The arguments are checked before the device is touched.
-class FlatIndex : public detail::ExactResidentIndex<vqhip_flat, vqhip_flat_destroy, vqhip_flat_search, vqhip_flat_range_search, vqhip_flat_rerank> {
+class FlatIndex : public detail::ExactResidentIndex<vqhip_flat, vqhip_flat_destroy, vqhip_flat_search, vqhip_flat_range_search, vqhip_flat_rerank,
+                                                    vqhip_flat_search_masked, vqhip_flat_range_search_masked> {
    public:
     FlatIndex(const float *rows, std::size_t n, std::size_t dim, Distance distance = Distance()) {
         init(rows, 0, n, dim, distance);
@@ -884,7 +939,8 @@ class BinaryIndex : public detail::ResidentIndex<vqhip_binary, vqhip_binary_dest
 // any metric.  Every result equals FlatIndex over quantizer.dequantize(codes): (row index, distance) pairs [nq][topk],
 // nearest first, NaN last, ties to the lower row.  The arguments are checked before the device is touched.
 class ScalarIndex
-    : public detail::ExactResidentIndex<vqhip_sqindex, vqhip_sqindex_destroy, vqhip_sqindex_search, vqhip_sqindex_range_search, vqhip_sqindex_rerank> {
+    : public detail::ExactResidentIndex<vqhip_sqindex, vqhip_sqindex_destroy, vqhip_sqindex_search, vqhip_sqindex_range_search, vqhip_sqindex_rerank,
+                                        vqhip_sqindex_search_masked, vqhip_sqindex_range_search_masked> {
    public:
     ScalarIndex(const float *rows, std::size_t n, std::size_t dim, ScalarQuantizer quantizer, Distance distance = Distance())
         : quantizer_(quantizer) {

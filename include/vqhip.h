@@ -600,6 +600,44 @@ int vqhip_range_read(const vqhip_range *r, uint64_t *lims, uint32_t *idx, float 
 int vqhip_range_device(const vqhip_range *r, const void **dev_lims, const void **dev_idx, const void **dev_dist);
 int vqhip_range_destroy(vqhip_range *r);
 
+/* ---- filtered search: a row mask on the flat and the scalar index (knn_tile.hpp, topk.hpp, range.hpp) -------------
+ * No reference counterpart.  A ROW MASK of an index of n rows is ceil(n / 32) u32 words; row i is ALLOWED iff bit i & 31
+ * of word i >> 5 is set (a bool array through np.packbits(m, bitorder="little"), zero-padded to whole words and read as
+ * little-endian u32).  Bits at or past n in the last word are ignored, whatever they hold.  One mask serves all queries
+ * of a call.
+ *   search_masked        per query the first topk words (adc_key(D) << 32) | row, ascending, over the ALLOWED rows only;
+ *                        D is exactly the distance vqhip_flat_search / vqhip_sqindex_search report.  NaN distances of
+ *                        allowed rows sort last and are reported as 0x7FC00000; ties go to the lower allowed row; a query
+ *                        with fewer than topk allowed rows has the padding behind them, idx 0xFFFFFFFF and dist +inf (an
+ *                        allowed row with a NaN distance is a result and comes before the padding).  topk keeps its
+ *                        bound 1 .. min(n, 1024): the number of allowed rows does not bound it.
+ *   range_search_masked  row i is a hit of query q iff it is allowed and D(q, i) <= radii[q] as an f32 comparison; the
+ *                        CSR result, its order (ascending row id) and max_results are vqhip_flat_range_search's.
+ * A mask of all ones gives the unmasked call's result bit for bit; a mask of all zeros gives padding only (lims = 0 for a
+ * range search); the masked scalar index equals the masked flat index over the decoded rows.  A call without a mask (the
+ * entry points above) runs the kernels it always ran.
+ * allowed: HOST memory in the host forms (copied into a workspace of the handle), a 4-byte aligned DEVICE pointer in the
+ * device forms (else VQHIP_ERR_INVALID_INPUT); NULL is VQHIP_ERR_NULL_PTR.  The other arguments, their checks and the
+ * order of the checks are the unmasked siblings'; the mask's pointer is checked with the other pointers (range: behind
+ * the radii, before the index handle), all before any device work.  A row tile of 64 rows without an allowed row costs
+ * two mask words: no row is read and no distance computed. */
+int vqhip_flat_search_masked(vqhip_flat *f, const float *queries, uint32_t nq, uint32_t topk, const uint32_t *allowed,
+                             uint32_t *idx_out, float *dist_out);
+int vqhip_flat_search_masked_device(vqhip_flat *f, const void *dev_queries, uint32_t nq, uint32_t topk,
+                                    const uint32_t *dev_allowed, void *dev_idx, void *dev_dist);
+int vqhip_sqindex_search_masked(vqhip_sqindex *x, const float *queries, uint32_t nq, uint32_t topk, const uint32_t *allowed,
+                                uint32_t *idx_out, float *dist_out);
+int vqhip_sqindex_search_masked_device(vqhip_sqindex *x, const void *dev_queries, uint32_t nq, uint32_t topk,
+                                       const uint32_t *dev_allowed, void *dev_idx, void *dev_dist);
+int vqhip_flat_range_search_masked(vqhip_flat *f, const float *queries, uint32_t nq, const float *radii, uint64_t max_results,
+                                   const uint32_t *allowed, vqhip_range **out);
+int vqhip_flat_range_search_masked_device(vqhip_flat *f, const void *dev_queries, uint32_t nq, const float *radii,
+                                          uint64_t max_results, const uint32_t *dev_allowed, vqhip_range **out);
+int vqhip_sqindex_range_search_masked(vqhip_sqindex *x, const float *queries, uint32_t nq, const float *radii,
+                                      uint64_t max_results, const uint32_t *allowed, vqhip_range **out);
+int vqhip_sqindex_range_search_masked_device(vqhip_sqindex *x, const void *dev_queries, uint32_t nq, const float *radii,
+                                             uint64_t max_results, const uint32_t *dev_allowed, vqhip_range **out);
+
 /* Hamming-radius range search over the binary index (k_binary.hip, k_bin_range; the result object and its rules are
  * vqhip_flat_range_search's).  The query is stated in bits: query q has a radius h_q, one u32 per query, hradii [nq] in
  * HOST memory in both forms, and row i is a hit iff H(q, i) <= h_q, H being exactly what vqhip_binary_search selects on

@@ -15,6 +15,7 @@ from .errors import (DimensionMismatch, EmptyInput, FfiError, InvalidData, Inval
 from .binary import BinaryIndex
 from .bq import BinaryQuantizer
 from ._lib import RangeResult
+from ._resident_common import pack_row_mask
 from .flat import FlatIndex
 from .ivf import IVFPQIndex
 from .ivf_flat import IVFFlatIndex
@@ -27,7 +28,7 @@ from .tsvq import TSVQ
 
 __all__ = [
     "Distance", "BinaryIndex", "BinaryQuantizer", "FlatIndex", "IVFBinaryIndex", "IVFFlatIndex", "IVFPQIndex", "IVFScalarIndex", "RangeResult", "ScalarIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
-    "InvalidParameter", "InvalidData", "FfiError", "get_simd_backend",
+    "InvalidParameter", "InvalidData", "FfiError", "get_simd_backend", "pack_row_mask",
 ]
 
 

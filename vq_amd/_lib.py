@@ -179,6 +179,14 @@ SIGNATURES = {
     "vqhip_flat_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, _f32p, C.c_uint64, _vpp]),
     "vqhip_sqindex_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, _f32p, C.c_uint64, _vpp]),
     "vqhip_sqindex_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, _f32p, C.c_uint64, _vpp]),
+    "vqhip_flat_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p]),
+    "vqhip_flat_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "vqhip_sqindex_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p]),
+    "vqhip_sqindex_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "vqhip_flat_range_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, _f32p, C.c_uint64, _u32p, _vpp]),
+    "vqhip_flat_range_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, _f32p, C.c_uint64, _vp, _vpp]),
+    "vqhip_sqindex_range_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, _f32p, C.c_uint64, _u32p, _vpp]),
+    "vqhip_sqindex_range_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, _f32p, C.c_uint64, _vp, _vpp]),
     "vqhip_binary_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint64, _vpp]),
     "vqhip_binary_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, _u32p, C.c_uint64, _vpp]),
     "vqhip_ivfbin_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint64, _vpp]),
@@ -842,11 +850,13 @@ class RangeResult(Handle):
         return self.lims.copy(), idx, dist
 
 
-def _range_call(fn, raw, queries, nq: int, radii: np.ndarray, max_results: int, *front) -> RangeResult:
+def _range_call(fn, raw, queries, nq: int, radii: np.ndarray, max_results: int, *front, back=()) -> RangeResult:
     """one range call of the C ABI; front: the arguments an index has between nq and the radii (nprobe); radii: float32
-    distances, or the uint32 Hamming radii of the two binary indexes"""
+    distances, or the uint32 Hamming radii of the two binary indexes; back: the arguments between max_results and the
+    result (the row mask of a filtered call)"""
     h = C.c_void_p()
-    check(fn(raw, queries, int(nq), *front, ptr(radii, _u32p if radii.dtype == np.uint32 else _f32p), int(max_results), C.byref(h)))
+    check(fn(raw, queries, int(nq), *front, ptr(radii, _u32p if radii.dtype == np.uint32 else _f32p), int(max_results), *back,
+             C.byref(h)))
     return RangeResult(h)
 
 
@@ -880,6 +890,29 @@ class _ResidentExactHandle(_ResidentHandle):
 
     def range_search_device(self, dev_queries: int, nq: int, radii: np.ndarray, max_results: int) -> RangeResult:
         return _range_call(self._fn("range_search_device"), self.raw, C.c_void_p(dev_queries), nq, radii, max_results)
+
+    # the filtered forms: `allowed` uint32 (ceil(n / 32),) row-mask words on the host, `dev_allowed` the same at a device
+    # pointer (4-byte aligned)
+    def search_masked(self, q: np.ndarray, topk: int, allowed: np.ndarray):
+        nq = q.shape[0]
+        idx = np.empty((nq, topk), np.uint32)
+        dist = np.empty((nq, topk), np.float32)
+        if nq:
+            check(self._fn("search_masked")(self.raw, ptr(q, _f32p), nq, int(topk), ptr(allowed, _u32p), ptr(idx, _u32p),
+                                            ptr(dist, _f32p)))
+        return idx, dist
+
+    def search_masked_device(self, dev_queries: int, nq: int, topk: int, dev_allowed: int, dev_idx: int, dev_dist: int):
+        check(self._fn("search_masked_device")(self.raw, C.c_void_p(dev_queries), int(nq), int(topk), C.c_void_p(dev_allowed),
+                                               C.c_void_p(dev_idx), C.c_void_p(dev_dist)))
+
+    def range_search_masked(self, q: np.ndarray, radii: np.ndarray, max_results: int, allowed: np.ndarray) -> RangeResult:
+        return _range_call(self._fn("range_search_masked"), self.raw, ptr(q, _f32p), q.shape[0], radii, max_results,
+                           back=(ptr(allowed, _u32p),))
+
+    def range_search_masked_device(self, dev_queries: int, nq: int, radii: np.ndarray, max_results: int, dev_allowed: int) -> RangeResult:
+        return _range_call(self._fn("range_search_masked_device"), self.raw, C.c_void_p(dev_queries), nq, radii, max_results,
+                           back=(C.c_void_p(dev_allowed),))
 
     def rerank(self, q: np.ndarray, cand: np.ndarray, topk: int):
         nq, c = cand.shape

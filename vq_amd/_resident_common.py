@@ -2,7 +2,7 @@
 first search, the checks of queries and ``topk``, and search over the device handle.  A subclass keeps its constructors,
 the checks of its own source array, ``_make_handle``, ``__repr__`` and its file layout.  ``ExactResidentIndex`` adds the
 range search and the rerank of the two indexes whose distances are exact (not ``BinaryIndex``, whose range search takes
-a radius in Hamming bits: ``_hamming_radii``)."""
+a radius in Hamming bits: ``_hamming_radii``), and the row mask of their filtered calls (``pack_row_mask``)."""
 from __future__ import annotations
 
 import operator
@@ -75,6 +75,59 @@ def _hamming_radii(radius, nq: int) -> np.ndarray:
     if out.shape[0] != nq:
         raise InvalidParameter("radius", f"one radius or one per query ({nq}), got {out.shape[0]}")
     return np.ascontiguousarray(out)
+
+
+def mask_words(n: int) -> int:
+    """the uint32 words of a row mask over n rows"""
+    return (n + 31) // 32
+
+
+def _pack_bools(m: np.ndarray) -> np.ndarray:
+    """bool (n,) -> uint32 (ceil(n / 32),): row i is bit i & 31 of word i >> 5, the pad bits zero"""
+    by = np.packbits(m, bitorder="little")
+    out = np.zeros(mask_words(m.shape[0]) * 4, np.uint8)
+    out[:by.shape[0]] = by
+    return out.view("<u4").astype(np.uint32)
+
+
+def pack_row_mask(mask_or_ids, n: int) -> np.ndarray:
+    """The row mask of an index of `n` rows as uint32 words (ceil(n / 32),), the form ``search(..., allowed=)`` and
+    ``range_search(..., allowed=)`` take: row i is allowed iff bit ``i & 31`` of word ``i >> 5`` is set.
+    `mask_or_ids` is a bool array (n,) -- True: allowed -- or an integer array of allowed row ids in [0, n), in any
+    order, repeats welcome."""
+    rows = _count(n, "n")
+    if not 1 <= rows < 1 << 32:
+        raise InvalidParameter("n", f"must be in [1, 2^32), got {rows}")
+    a = np.asarray(mask_or_ids)
+    if a.ndim != 1:
+        raise InvalidParameter("mask_or_ids", f"must be a 1D array, got {a.ndim} dimensions")
+    if a.dtype == np.bool_:
+        if a.shape[0] != rows:
+            raise DimensionMismatch(rows, a.shape[0])
+        return _pack_bools(a)
+    if a.dtype.kind not in "iu":
+        raise InvalidParameter("mask_or_ids", f"must be a bool array or an integer array of row ids, got {a.dtype}")
+    m = np.zeros(rows, np.bool_)
+    if a.size:
+        lo, hi = int(a.min()), int(a.max())
+        if lo < 0 or hi >= rows:
+            raise InvalidParameter("mask_or_ids", f"row id {lo if lo < 0 else hi} is outside [0, {rows})")
+        m[a.astype(np.int64)] = True
+    return _pack_bools(m)
+
+
+def _allowed(allowed, n: int) -> np.ndarray:
+    """the row-mask words uint32 (ceil(n / 32),) of a filtered call from its `allowed` argument: a bool array (n,),
+    packed here, or the words themselves"""
+    a = np.asarray(allowed)
+    if a.dtype != np.bool_ and a.dtype != np.uint32:
+        raise InvalidParameter("allowed", f"must be a bool array ({n},) or uint32 words ({mask_words(n)},), got {a.dtype}")
+    if a.ndim != 1:
+        raise InvalidParameter("allowed", f"must be a 1D array, got {a.ndim} dimensions")
+    want = n if a.dtype == np.bool_ else mask_words(n)
+    if a.shape[0] != want:
+        raise DimensionMismatch(want, a.shape[0])
+    return _pack_bools(a) if a.dtype == np.bool_ else np.ascontiguousarray(a)
 
 
 def _max_results(max_results) -> int:
@@ -173,27 +226,60 @@ class ResidentIndex:
 
 
 class ExactResidentIndex(ResidentIndex):
-    """a ResidentIndex whose distances are exact (FlatIndex, ScalarIndex): range search and the rerank of candidates"""
+    """a ResidentIndex whose distances are exact (FlatIndex, ScalarIndex): range search, the rerank of candidates, and
+    the filtered forms of search and range search.  A filter is one row mask per call, `allowed`: a bool array (n,)
+    (True: the row may be returned) or its uint32 words (``pack_row_mask``); None: every row, the unfiltered call."""
 
-    def range_search(self, queries, radius, max_results: int = DEFAULT_MAX_RESULTS):
+    def search(self, queries, topk: int = 10, allowed=None):
+        """(nq, d) float32 queries -> (indices uint32 (nq, topk), distances float32 (nq, topk)), nearest first.  With
+        `allowed`, the nearest among the allowed rows only; a query with fewer than `topk` of them has the slots behind
+        them padded with index 0xFFFFFFFF and distance +inf (`topk` itself stays within 1 .. min(n, 1024))."""
+        q = self._queries(queries)
+        k = self._topk(topk)
+        if allowed is None:
+            return self._search(q, k)
+        w = _allowed(allowed, self._n)
+        if q.shape[0] == 0:
+            return np.empty((0, k), np.uint32), np.empty((0, k), np.float32)
+        return self._index().search_masked(q, k, w)
+
+    def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int, dev_allowed: int | None = None) -> None:
+        """device pointers: queries [nq][d] f32, results [nq][topk] uint32 / f32 (4-byte aligned); asynchronous on the
+        current stream.  `dev_allowed`: the row mask's ceil(n / 32) uint32 words at a device pointer (4-byte aligned)."""
+        k = self._topk(topk)
+        n_q = _nq(nq)
+        if dev_allowed is None:
+            self._index().search_device(int(dev_queries), n_q, k, int(dev_idx), int(dev_dist))
+        else:
+            self._index().search_masked_device(int(dev_queries), n_q, k, int(dev_allowed), int(dev_idx), int(dev_dist))
+
+    def range_search(self, queries, radius, max_results: int = DEFAULT_MAX_RESULTS, allowed=None):
         """every row within `radius` of each query: row i is a hit of query q iff D(q, i) <= radius[q] as a float32
         comparison (NaN distances never hit).  `radius` is a scalar or nq values.  Returns (lims uint64 (nq + 1,),
         idx uint32 (total,), dist float32 (total,)): the hits of query q are idx[lims[q]:lims[q + 1]], in ascending
-        row id.  More than `max_results` hits in all: FfiError (ERR_UNSUPPORTED)."""
+        row id.  More than `max_results` hits in all: FfiError (ERR_UNSUPPORTED).  With `allowed`, only allowed rows
+        hit."""
         q = self._queries(queries)
         r = _radii(radius, q.shape[0])
         m = _max_results(max_results)
+        w = None if allowed is None else _allowed(allowed, self._n)
         if q.shape[0] == 0:
             return np.zeros(1, np.uint64), np.empty(0, np.uint32), np.empty(0, np.float32)
-        return self._index().range_search(q, r, m).read()
+        if w is None:
+            return self._index().range_search(q, r, m).read()
+        return self._index().range_search_masked(q, r, m, w).read()
 
-    def range_search_device(self, dev_queries: int, nq: int, radius, max_results: int = DEFAULT_MAX_RESULTS) -> "_lib.RangeResult":
+    def range_search_device(self, dev_queries: int, nq: int, radius, max_results: int = DEFAULT_MAX_RESULTS,
+                            dev_allowed: int | None = None) -> "_lib.RangeResult":
         """`range_search` with the queries [nq][d] f32 at a device pointer (4-byte aligned) and the result left on the
-        device: a RangeResult (.total, .lims, .device_pointers(), .read()).  Returns when the result is complete."""
+        device: a RangeResult (.total, .lims, .device_pointers(), .read()).  Returns when the result is complete.
+        `dev_allowed`: the row mask's ceil(n / 32) uint32 words at a device pointer (4-byte aligned)."""
         n_q = _nq(nq)
         r = _radii(radius, n_q)
         m = _max_results(max_results)
-        return self._index().range_search_device(int(dev_queries), n_q, r, m)
+        if dev_allowed is None:
+            return self._index().range_search_device(int(dev_queries), n_q, r, m)
+        return self._index().range_search_masked_device(int(dev_queries), n_q, r, m, int(dev_allowed))
 
     def rerank(self, queries, candidates, topk: int = 10):
         """per query, the `topk` nearest of its candidate row ids (nq, c), 1 <= c <= 4096, distinct within a query;

@@ -2739,6 +2739,16 @@ struct ExactResident : Resident {
     DevBuf qnorm, dist, state;  // per-call workspaces
     DevBuf rr_cand, rr_err;     // rerank: candidate ids, the out-of-range flag
     DevBuf radii, range_ws;     // range search: the radii, the stage's counts and offsets
+    DevBuf mask_ws;             // a filtered host call's row mask on the device
+    const uint32_t *mask = nullptr;  // the row mask of the filtered call that holds the lock (MaskScope), NULL otherwise
+
+    size_t mask_bytes() const { return (size_t)((n + 31) / 32) * 4; }
+    // a host form's mask, ceil(n / 32) words, up into mask_ws
+    int stage_mask(const uint32_t *allowed, hipStream_t s) {
+        VQ_TRY(mask_ws.ensure(mask_bytes()));
+        VQ_HIP(hipMemcpyAsync(mask_ws.p, allowed, mask_bytes(), hipMemcpyHostToDevice, s));
+        return VQHIP_OK;
+    }
 
     // the query norms of a cosine index into qnorm (NULL otherwise)
     int qnorms(const float *queries_dev, uint32_t nq, const float **qn, hipStream_t s) {
@@ -2761,6 +2771,20 @@ struct ExactResident : Resident {
         return static_cast<T *>(this)->launch_search(queries_dev, qn, nq, topk, idx_dev, dist_dev, s);
     }
 };
+
+// The row mask of a filtered call for the launches it makes on the handle: set under the handle's lock, cleared on every
+// exit, so that a call without a mask finds NULL and takes the unmasked kernels.
+struct MaskScope {
+    const uint32_t *&slot;
+    MaskScope(const uint32_t *&s, const uint32_t *m) : slot(s) { slot = m; }
+    ~MaskScope() { slot = nullptr; }
+    MaskScope(const MaskScope &) = delete;
+    MaskScope &operator=(const MaskScope &) = delete;
+};
+static int check_mask_aligned(const void *dev_allowed) {
+    if (reinterpret_cast<uintptr_t>(dev_allowed) & 3) return fail(VQHIP_ERR_INVALID_INPUT, "the row mask is not 4-byte aligned");
+    return VQHIP_OK;
+}
 
 // every create takes 1 <= n < 2^32 rows and a metric of include/vqhip.h (two checks: each create has its own between them)
 static int check_rows(uint64_t n) {
@@ -2851,6 +2875,32 @@ static int resident_search_device(T *x, const void *dev_queries, uint32_t nq, ui
     });
 }
 
+// the two filtered search entry points of a flat or a scalar index: resident_search / _device with the row mask `allowed`
+// (host: ceil(n / 32) words staged into mask_ws; device: a 4-byte aligned pointer) in force for the launches
+template <class T>
+static int exact_search_masked(T *x, const float *queries, uint32_t nq, uint32_t topk, const uint32_t *allowed, uint32_t *idx_out,
+                               float *dist_out) {
+    return resident_enter(x, queries && idx_out && dist_out && allowed, [&] { return check_topk(x->n, topk); }, nq, nullptr,
+                          [&](Entry &in, hipStream_t s) -> int {
+        VQ_TRY(x->stage_mask(allowed, s));
+        MaskScope scope(x->mask, x->mask_ws.template as<uint32_t>());
+        return host_search(in, s, x->q, x->idx, &x->out, queries, nq, x->d, topk, idx_out, dist_out, [&] {
+            return x->search_enqueue(x->q.template as<float>(), nq, topk, x->idx.template as<uint32_t>(), x->out.template as<float>(), s);
+        });
+    });
+}
+template <class T>
+static int exact_search_masked_device(T *x, const void *dev_queries, uint32_t nq, uint32_t topk, const uint32_t *dev_allowed,
+                                      void *dev_idx, void *dev_dist) {
+    if (!dev_queries || !dev_idx || !dev_dist || !dev_allowed) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    VQ_TRY(check_mask_aligned(dev_allowed));
+    return resident_enter(x, true, [&] { return check_topk(x->n, topk); }, nq, dev_queries, [&](Entry &, hipStream_t s) {
+        MaskScope scope(x->mask, dev_allowed);
+        return x->search_enqueue(reinterpret_cast<const float *>(dev_queries), nq, topk, reinterpret_cast<uint32_t *>(dev_idx),
+                                 reinterpret_cast<float *>(dev_dist), s);
+    });
+}
+
 // the exact rerank of cand [nq][c] on a flat or a scalar index
 template <class T>
 static int exact_rerank(T *x, const float *queries, uint32_t nq, const uint32_t *cand, uint32_t c, uint32_t topk, uint32_t *idx_out,
@@ -2892,7 +2942,7 @@ struct vqhip_flat : ExactResident<vqhip_flat> {
     int launch_search(const float *queries_dev, const float *qn, uint32_t nq, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
                       hipStream_t s) {
         return launch_knn_search(metric, rows.p, dtype, n, d, rnorm.as<float>(), queries_dev, qn, nq, topk, dist.as<float>(), state.p,
-                                 cand.as<unsigned long long>(), idx_dev, dist_dev, s);
+                                 cand.as<unsigned long long>(), idx_dev, dist_dev, mask, s);
     }
     int launch_rerank(const float *qn, uint32_t nq, uint32_t c, uint32_t topk, hipStream_t s) {
         return launch_knn_rerank(metric, rows.p, dtype, n, d, rnorm.as<float>(), q.as<float>(), qn, nq, rr_cand.as<uint32_t>(), c, topk,
@@ -2900,7 +2950,7 @@ struct vqhip_flat : ExactResident<vqhip_flat> {
     }
     int launch_range(const float *queries_dev, const float *qn, uint32_t nq, uint64_t max_results, RangeOut *r, hipStream_t s) {
         return launch_knn_range(metric, rows.p, dtype, n, d, rnorm.as<float>(), queries_dev, qn, nq, radii.as<float>(), max_results,
-                                dist.as<float>(), state.p, range_ws.p, r, s);
+                                dist.as<float>(), state.p, range_ws.p, r, mask, s);
     }
 };
 
@@ -2973,6 +3023,20 @@ int vqhip_flat_search_device(vqhip_flat *f, const void *dev_queries, uint32_t nq
     VQ_API_END
 }
 
+int vqhip_flat_search_masked(vqhip_flat *f, const float *queries, uint32_t nq, uint32_t topk, const uint32_t *allowed,
+                             uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    return exact_search_masked(f, queries, nq, topk, allowed, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_flat_search_masked_device(vqhip_flat *f, const void *dev_queries, uint32_t nq, uint32_t topk, const uint32_t *dev_allowed,
+                                    void *dev_idx, void *dev_dist) {
+    VQ_API_BEGIN
+    return exact_search_masked_device(f, dev_queries, nq, topk, dev_allowed, dev_idx, dev_dist);
+    VQ_API_END
+}
+
 int vqhip_flat_rerank(vqhip_flat *f, const float *queries, uint32_t nq, const uint32_t *cand, uint32_t c, uint32_t topk,
                       uint32_t *idx_out, float *dist_out) {
     VQ_API_BEGIN
@@ -2991,7 +3055,7 @@ struct vqhip_sqindex : ExactResident<vqhip_sqindex> {
     int launch_search(const float *queries_dev, const float *qn, uint32_t nq, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
                       hipStream_t s) {
         return launch_sq_search(metric, codes.as<uint8_t>(), n, d, mn, step, rnorm.as<float>(), queries_dev, qn, nq, topk, dist.as<float>(),
-                                state.p, cand.as<unsigned long long>(), idx_dev, dist_dev, s);
+                                state.p, cand.as<unsigned long long>(), idx_dev, dist_dev, mask, s);
     }
     int launch_rerank(const float *qn, uint32_t nq, uint32_t c, uint32_t topk, hipStream_t s) {
         return launch_sq_rerank(metric, codes.as<uint8_t>(), n, d, mn, step, rnorm.as<float>(), q.as<float>(), qn, nq, rr_cand.as<uint32_t>(),
@@ -2999,7 +3063,7 @@ struct vqhip_sqindex : ExactResident<vqhip_sqindex> {
     }
     int launch_range(const float *queries_dev, const float *qn, uint32_t nq, uint64_t max_results, RangeOut *r, hipStream_t s) {
         return launch_sq_range(metric, codes.as<uint8_t>(), n, d, mn, step, rnorm.as<float>(), queries_dev, qn, nq, radii.as<float>(),
-                               max_results, dist.as<float>(), state.p, range_ws.p, r, s);
+                               max_results, dist.as<float>(), state.p, range_ws.p, r, mask, s);
     }
 };
 
@@ -3113,6 +3177,20 @@ int vqhip_sqindex_search_device(vqhip_sqindex *x, const void *dev_queries, uint3
     VQ_API_END
 }
 
+int vqhip_sqindex_search_masked(vqhip_sqindex *x, const float *queries, uint32_t nq, uint32_t topk, const uint32_t *allowed,
+                                uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    return exact_search_masked(x, queries, nq, topk, allowed, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_sqindex_search_masked_device(vqhip_sqindex *x, const void *dev_queries, uint32_t nq, uint32_t topk,
+                                       const uint32_t *dev_allowed, void *dev_idx, void *dev_dist) {
+    VQ_API_BEGIN
+    return exact_search_masked_device(x, dev_queries, nq, topk, dev_allowed, dev_idx, dev_dist);
+    VQ_API_END
+}
+
 int vqhip_sqindex_rerank(vqhip_sqindex *x, const float *queries, uint32_t nq, const uint32_t *cand, uint32_t c, uint32_t topk,
                          uint32_t *idx_out, float *dist_out) {
     VQ_API_BEGIN
@@ -3178,11 +3256,19 @@ static int range_enter(H *h, const void *queries, bool host, uint32_t nq, const 
 }
 
 // One range call on a flat or a scalar index h: the radii go up, and the index's driver, h->launch_range, leaves the
-// result complete.
+// result complete.  masked: a filtered call under the row mask `allowed` (a host form's is staged into mask_ws, a device
+// form's is 4-byte aligned); its pointer is checked behind range_args and, like them, before the handle.
 template <class H>
 static int range_search(H *h, const void *queries, bool host, uint32_t nq, const float *radii, uint64_t max_results,
-                        vqhip_range **out) {
+                        vqhip_range **out, bool masked = false, const uint32_t *allowed = nullptr) {
+    if (masked) {
+        VQ_TRY(range_args(queries, radii, nq, max_results, out));
+        if (!allowed) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+        if (!host) VQ_TRY(check_mask_aligned(allowed));
+    }
     return range_enter(h, queries, host, nq, radii, max_results, out, no_checks, [&](const float *qdev, RangeOut *r, hipStream_t s) -> int {
+        if (masked && host) VQ_TRY(h->stage_mask(allowed, s));
+        MaskScope scope(h->mask, !masked ? nullptr : host ? h->mask_ws.template as<uint32_t>() : allowed);
         VQ_TRY(h->radii.ensure((size_t)nq * 4));
         VQ_HIP(hipMemcpyAsync(h->radii.p, radii, (size_t)nq * 4, hipMemcpyHostToDevice, s));
         VQ_TRY(h->dist.ensure((size_t)knn_query_batch(h->n, nq) * h->n * 4));
@@ -3221,6 +3307,34 @@ int vqhip_sqindex_range_search_device(vqhip_sqindex *x, const void *dev_queries,
                                       uint64_t max_results, vqhip_range **out) {
     VQ_API_BEGIN
     return range_search(x, dev_queries, false, nq, radii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_flat_range_search_masked(vqhip_flat *f, const float *queries, uint32_t nq, const float *radii, uint64_t max_results,
+                                   const uint32_t *allowed, vqhip_range **out) {
+    VQ_API_BEGIN
+    return range_search(f, queries, true, nq, radii, max_results, out, true, allowed);
+    VQ_API_END
+}
+
+int vqhip_flat_range_search_masked_device(vqhip_flat *f, const void *dev_queries, uint32_t nq, const float *radii,
+                                          uint64_t max_results, const uint32_t *dev_allowed, vqhip_range **out) {
+    VQ_API_BEGIN
+    return range_search(f, dev_queries, false, nq, radii, max_results, out, true, dev_allowed);
+    VQ_API_END
+}
+
+int vqhip_sqindex_range_search_masked(vqhip_sqindex *x, const float *queries, uint32_t nq, const float *radii, uint64_t max_results,
+                                      const uint32_t *allowed, vqhip_range **out) {
+    VQ_API_BEGIN
+    return range_search(x, queries, true, nq, radii, max_results, out, true, allowed);
+    VQ_API_END
+}
+
+int vqhip_sqindex_range_search_masked_device(vqhip_sqindex *x, const void *dev_queries, uint32_t nq, const float *radii,
+                                             uint64_t max_results, const uint32_t *dev_allowed, vqhip_range **out) {
+    VQ_API_BEGIN
+    return range_search(x, dev_queries, false, nq, radii, max_results, out, true, dev_allowed);
     VQ_API_END
 }
 

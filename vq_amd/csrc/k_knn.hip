@@ -16,6 +16,8 @@
 //   launch_topk_select   the shared selection stage (topk.hpp) over those distances and bins
 // A range search (launch_knn_range) runs k_knn_dist over the same batches and then the range stage (range.hpp; DESIGN.md
 // 15) in place of the histogram and the selection.
+// A filtered search or range search (mask_dev: one row mask per call) runs k_knn_dist_masked, which leaves a
+// row tile without an allowed row after its two mask words, and stages that read a row's mask bit before its distance.
 // Roofline: VALU.  Squared L2 / Euclidean cost 3 unfused operations per (query, row, dimension), L1 2 (sub, then an add
 // that takes |.| as a source modifier), cosine 2 (mul, add).
 #include "kernels.hpp"
@@ -46,19 +48,21 @@ int launch_range_begin(RangeOut *out, uint32_t nq, uint64_t max_results, hipStre
 
 int launch_knn_search(int metric, const void *X, int dtype, uint64_t n, uint32_t d, const float *rnorm, const float *queries_dev,
                       const float *qnorm_dev, uint32_t nq, uint32_t topk, float *dist_ws, void *state_ws,
-                      unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev, hipStream_t stream) {
+                      unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev, const uint32_t *mask_dev,
+                      hipStream_t stream) {
     return knn_dense_rows(X, dtype, d, [&](auto rows) {
         return knn_search_rows(metric, rows, n, rnorm, queries_dev, qnorm_dev, nq, topk, dist_ws, state_ws, cand_ws, idx_out_dev,
-                               dist_out_dev, stream);
+                               dist_out_dev, mask_dev, stream);
     });
 }
 
 int launch_knn_range(int metric, const void *X, int dtype, uint64_t n, uint32_t d, const float *rnorm, const float *queries_dev,
                      const float *qnorm_dev, uint32_t nq, const float *radii_dev, uint64_t max_results, float *dist_ws,
-                     void *state_ws, void *range_ws, RangeOut *out, hipStream_t stream) {
+                     void *state_ws, void *range_ws, RangeOut *out, const uint32_t *mask_dev,
+                     hipStream_t stream) {
     return knn_dense_rows(X, dtype, d, [&](auto rows) {
         return knn_range_rows(metric, rows, n, rnorm, queries_dev, qnorm_dev, nq, radii_dev, max_results, dist_ws, state_ws, range_ws,
-                              out, stream);
+                              out, mask_dev, stream);
     });
 }
 

@@ -26,20 +26,22 @@ int launch_sq_norms(const uint8_t *C, uint64_t n, uint32_t d, float mn, float st
 // launch_knn_norms); the batches and workspaces are launch_knn_search's
 int launch_sq_search(int metric, const uint8_t *C, uint64_t n, uint32_t d, float mn, float step, const float *rnorm,
                      const float *queries_dev, const float *qnorm_dev, uint32_t nq, uint32_t topk, float *dist_ws, void *state_ws,
-                     unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev, hipStream_t stream) {
+                     unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev, const uint32_t *mask_dev,
+                      hipStream_t stream) {
     return sq_rows(C, d, mn, step, [&](auto rows) {
         return knn_search_rows(metric, rows, n, rnorm, queries_dev, qnorm_dev, nq, topk, dist_ws, state_ws, cand_ws, idx_out_dev,
-                               dist_out_dev, stream);
+                               dist_out_dev, mask_dev, stream);
     });
 }
 
 // launch_sq_search with the range stage behind the distances (launch_knn_range); range_ws >= range_ws_bytes(n, nq)
 int launch_sq_range(int metric, const uint8_t *C, uint64_t n, uint32_t d, float mn, float step, const float *rnorm,
                     const float *queries_dev, const float *qnorm_dev, uint32_t nq, const float *radii_dev, uint64_t max_results,
-                    float *dist_ws, void *state_ws, void *range_ws, RangeOut *out, hipStream_t stream) {
+                    float *dist_ws, void *state_ws, void *range_ws, RangeOut *out, const uint32_t *mask_dev,
+                     hipStream_t stream) {
     return sq_rows(C, d, mn, step, [&](auto rows) {
         return knn_range_rows(metric, rows, n, rnorm, queries_dev, qnorm_dev, nq, radii_dev, max_results, dist_ws, state_ws, range_ws,
-                              out, stream);
+                              out, mask_dev, stream);
     });
 }
 

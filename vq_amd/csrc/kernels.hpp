@@ -339,12 +339,15 @@ int launch_ivfbin_distances(const IvffPlan &p, const IvfBatchView &v, int metric
                             const uint32_t *Q, hipStream_t stream);
 // exact k-NN search over resident rows and exact rerank of candidate lists (k_knn.hip); X [n][d] f32 (dtype 0) or f16
 // bits (dtype 1), rnorm [n] the rows' norms (cosine only, else unused)
+// mask_dev (search and range, here and over SQ codes): the row mask of a filtered call on the device -- ceil(n / 32)
+// words, row i allowed iff bit i & 31 of word i >> 5 is set -- or NULL for the unmasked kernels.
 int launch_knn_norms(const void *X, int dtype, uint64_t n, uint32_t d, float *out, hipStream_t stream);
 uint32_t knn_query_batch(uint64_t n, uint32_t nq);
 size_t knn_state_bytes(uint32_t qb);
 int launch_knn_search(int metric, const void *X, int dtype, uint64_t n, uint32_t d, const float *rnorm, const float *queries_dev,
                       const float *qnorm_dev, uint32_t nq, uint32_t topk, float *dist_ws, void *state_ws,
-                      unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev, hipStream_t stream);
+                      unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev, const uint32_t *mask_dev,
+                      hipStream_t stream);
 int launch_knn_rerank(int metric, const void *X, int dtype, uint64_t n, uint32_t d, const float *rnorm, const float *queries_dev,
                       const float *qnorm_dev, uint32_t nq, const uint32_t *cand_dev, uint32_t c, uint32_t topk,
                       uint32_t *idx_out_dev, float *dist_out_dev, uint32_t *err_dev, hipStream_t stream);
@@ -366,10 +369,10 @@ int launch_range_begin(RangeOut *out, uint32_t nq, uint64_t max_results, hipStre
 // VQHIP_ERR_UNSUPPORTED.
 int launch_knn_range(int metric, const void *X, int dtype, uint64_t n, uint32_t d, const float *rnorm, const float *queries_dev,
                      const float *qnorm_dev, uint32_t nq, const float *radii_dev, uint64_t max_results, float *dist_ws,
-                     void *state_ws, void *range_ws, RangeOut *out, hipStream_t stream);
+                     void *state_ws, void *range_ws, RangeOut *out, const uint32_t *mask_dev, hipStream_t stream);
 int launch_sq_range(int metric, const uint8_t *C, uint64_t n, uint32_t d, float mn, float step, const float *rnorm,
                     const float *queries_dev, const float *qnorm_dev, uint32_t nq, const float *radii_dev, uint64_t max_results,
-                    float *dist_ws, void *state_ws, void *range_ws, RangeOut *out, hipStream_t stream);
+                    float *dist_ws, void *state_ws, void *range_ws, RangeOut *out, const uint32_t *mask_dev, hipStream_t stream);
 
 // exact range search over the probed lists (ivf_range.hpp behind k_ivfflat.hip): the range stage in place of the
 // selection behind a batch's distance passes, radii [nb] on the device (for the binary index the reported distance of each
@@ -386,7 +389,8 @@ int launch_ivff_range(const IvfBatchView &v, uint32_t q0, const float *radii, vo
 int launch_sq_norms(const uint8_t *C, uint64_t n, uint32_t d, float mn, float step, float *out, hipStream_t stream);
 int launch_sq_search(int metric, const uint8_t *C, uint64_t n, uint32_t d, float mn, float step, const float *rnorm,
                      const float *queries_dev, const float *qnorm_dev, uint32_t nq, uint32_t topk, float *dist_ws, void *state_ws,
-                     unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev, hipStream_t stream);
+                     unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev, const uint32_t *mask_dev,
+                     hipStream_t stream);
 int launch_sq_rerank(int metric, const uint8_t *C, uint64_t n, uint32_t d, float mn, float step, const float *rnorm,
                      const float *queries_dev, const float *qnorm_dev, uint32_t nq, const uint32_t *cand_dev, uint32_t c,
                      uint32_t topk, uint32_t *idx_out_dev, float *dist_out_dev, uint32_t *err_dev, hipStream_t stream);

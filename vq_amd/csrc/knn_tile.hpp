@@ -190,16 +190,32 @@ __global__ __launch_bounds__(256) void k_knn_norms(const typename ROWS::Elem *__
     }
 }
 
+// The row mask of row tile rt (rows rt * 64 .. + nvalid) as two words, bits at or past nvalid cleared.  The mask has
+// ceil(n / 32) words and is 4-byte aligned: two u32 reads, and the second only where the tile reaches past 32 rows (for
+// n = 33, 65 or 96 the last tile's second word does not exist).  Workgroup-uniform.
+__device__ __forceinline__ void knn_tile_mask(const uint32_t *__restrict__ mask, uint64_t rt, uint32_t nvalid, uint32_t &w0,
+                                              uint32_t &w1) {
+    w0 = mask[2 * rt];
+    w1 = nvalid > 32 ? mask[2 * rt + 1] : 0u;
+    if (nvalid < 32) w0 &= (1u << nvalid) - 1u;
+    else if (nvalid > 32 && nvalid < 64) w1 &= (1u << (nvalid - 32)) - 1u;
+}
+
 // dist[q][i] for the batch's nq queries.  Workgroup b owns query tile b % nqt and strides over the row tiles
 // b / nqt, b / nqt + gridDim.x / nqt, ... (gridDim.x is a multiple of nqt): the workgroups in flight at one time share
 // row tiles, so the rows come from HBM about once per call and from L2 for the other query tiles.  A padded row's
 // distance is not written, nor does it enter the key range.
 // kmin / kmax [nq]: the range of the non-NaN keys of each query (atomics, once per workgroup and query).
-template <int METRIC, class ROWS>
-__global__ __launch_bounds__(256) void k_knn_dist(const float *__restrict__ Q, uint32_t nq, const typename ROWS::Elem *__restrict__ X,
-                                                  uint64_t n, uint32_t d, typename ROWS::Scale sc, const float *__restrict__ qnorm,
-                                                  const float *__restrict__ rnorm, uint32_t nqt, uint64_t nrt, float *__restrict__ dist,
-                                                  uint32_t *__restrict__ kmin, uint32_t *__restrict__ kmax) {
+// MASKED (k_knn_dist_masked; mask: the call's row mask): a tile reads its two mask words first and, with no allowed row
+// below n, is left at once -- no tile pass, no rnorm, no store: its slots of dist keep what an earlier batch or call left
+// there, which is why everything behind a masked kernel reads the mask before a distance.  A tile with an allowed row is
+// computed and stored whole; only allowed rows enter the key range.
+template <int METRIC, class ROWS, bool MASKED>
+__device__ __forceinline__ void knn_dist_body(const float *__restrict__ Q, uint32_t nq, const typename ROWS::Elem *__restrict__ X,
+                                              uint64_t n, uint32_t d, typename ROWS::Scale sc, const float *__restrict__ qnorm,
+                                              const float *__restrict__ rnorm, uint32_t nqt, uint64_t nrt, float *__restrict__ dist,
+                                              uint32_t *__restrict__ kmin, uint32_t *__restrict__ kmax,
+                                              const uint32_t *__restrict__ mask) {
     constexpr uint32_t RQ = kKnnRQ, RR = kKnnRR, TQ = kKnnTQ, TR = kKnnTR, KC = kKnnKC;
     __shared__ __attribute__((aligned(16))) float qs[KC][TQ + 4];
     __shared__ __attribute__((aligned(16))) float rs[KC][TR + 4];
@@ -219,8 +235,16 @@ __global__ __launch_bounds__(256) void k_knn_dist(const float *__restrict__ Q, u
     }
     for (uint64_t rt = blockIdx.x / nqt; rt < nrt; rt += rstep) {
         const uint64_t row0 = rt * TR;
+        const uint32_t nvalid = (uint32_t)min((uint64_t)TR, n - row0);
+        uint32_t ok = 0xFu;  // MASKED: the mask bits of this lane's four rows
+        if constexpr (MASKED) {
+            uint32_t w0, w1;
+            knn_tile_mask(mask, rt, nvalid, w0, w1);
+            if ((w0 | w1) == 0u) continue;  // (uniform) nothing allowed in this tile
+            ok = ((rg < 8 ? w0 : w1) >> ((rg & 7u) * 4)) & 0xFu;
+        }
         float acc[RQ][RR];
-        knn_tile_pass<METRIC>(acc, qs, rs, Q, query_of, rows, row0, (uint32_t)min((uint64_t)TR, n - row0));
+        knn_tile_pass<METRIC>(acc, qs, rs, Q, query_of, rows, row0, nvalid);
         float rn[RR];
 #pragma unroll
         for (uint32_t b = 0; b < RR; ++b) {
@@ -237,7 +261,9 @@ __global__ __launch_bounds__(256) void k_knn_dist(const float *__restrict__ Q, u
             for (uint32_t b = 0; b < RR; ++b) {
                 dv[b] = knn_finish<METRIC>(acc[a][b], qn[a], rn[b]);
                 const uint32_t key = adc_key(dv[b]);
-                if (rbase + b < n && key != 0xFFFFFFFFu) {
+                bool in = rbase + b < n && key != 0xFFFFFFFFu;
+                if constexpr (MASKED) in = in && ((ok >> b) & 1u);
+                if (in) {
                     lo[a] = min(lo[a], key);
                     hi[a] = max(hi[a], key);
                 }
@@ -254,6 +280,24 @@ __global__ __launch_bounds__(256) void k_knn_dist(const float *__restrict__ Q, u
         }
     }
     knn_key_range(lo, hi, [&](uint32_t a) { return query_of(qg * RQ + a); }, kmin, kmax);
+}
+
+template <int METRIC, class ROWS>
+__global__ __launch_bounds__(256) void k_knn_dist(const float *__restrict__ Q, uint32_t nq, const typename ROWS::Elem *__restrict__ X,
+                                                  uint64_t n, uint32_t d, typename ROWS::Scale sc, const float *__restrict__ qnorm,
+                                                  const float *__restrict__ rnorm, uint32_t nqt, uint64_t nrt, float *__restrict__ dist,
+                                                  uint32_t *__restrict__ kmin, uint32_t *__restrict__ kmax) {
+    knn_dist_body<METRIC, ROWS, false>(Q, nq, X, n, d, sc, qnorm, rnorm, nqt, nrt, dist, kmin, kmax, nullptr);
+}
+
+template <int METRIC, class ROWS>
+__global__ __launch_bounds__(256) void k_knn_dist_masked(const float *__restrict__ Q, uint32_t nq,
+                                                         const typename ROWS::Elem *__restrict__ X, uint64_t n, uint32_t d,
+                                                         typename ROWS::Scale sc, const float *__restrict__ qnorm,
+                                                         const float *__restrict__ rnorm, uint32_t nqt, uint64_t nrt,
+                                                         float *__restrict__ dist, uint32_t *__restrict__ kmin,
+                                                         uint32_t *__restrict__ kmax, const uint32_t *__restrict__ mask) {
+    knn_dist_body<METRIC, ROWS, true>(Q, nq, X, n, d, sc, qnorm, rnorm, nqt, nrt, dist, kmin, kmax, mask);
 }
 
 // rerank: one workgroup per query computes D for its c candidates (the row of each gathered from the index, one
@@ -312,8 +356,47 @@ __attribute__((unused)) __global__ __launch_bounds__(256) void k_knn_hist(const 
         if (h[e]) atomicAdd(&hist[(size_t)q * kAdcBins + e], h[e]);
 }
 
+// k_knn_hist over the allowed rows only, four consecutive rows per lane: their mask bits are read first, and the distances
+// of a group without an allowed row not at all
+__attribute__((unused)) __global__ __launch_bounds__(256) void k_knn_hist_masked(const float *__restrict__ dist, uint64_t n,
+                                                                                 const uint32_t *__restrict__ kmin,
+                                                                                 const uint32_t *__restrict__ kmax,
+                                                                                 const uint32_t *__restrict__ mask,
+                                                                                 uint32_t *__restrict__ hist) {
+    __shared__ uint32_t h[kAdcBins];
+    const uint32_t q = blockIdx.y, lo = kmin[q], hi = kmax[q];
+    for (uint32_t e = threadIdx.x; e < kAdcBins; e += 256) h[e] = 0u;
+    __syncthreads();
+    const float *dq = dist + (size_t)q * n;
+    for (uint64_t i0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 4; i0 < n; i0 += (uint64_t)gridDim.x * 1024) {
+        const uint32_t ok = (mask[i0 >> 5] >> (uint32_t)(i0 & 31u)) & 0xFu;
+        if (ok == 0) continue;
+        float v[4];
+        masked_load4(dq, n, i0, ok, v);
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j)
+            if (((ok >> j) & 1u) && i0 + j < n) atomicAdd(&h[knn_bin(adc_key(v[j]), lo, hi)], 1u);
+    }
+    __syncthreads();
+    for (uint32_t e = threadIdx.x; e < kAdcBins; e += 256)
+        if (h[e]) atomicAdd(&hist[(size_t)q * kAdcBins + e], h[e]);
+}
+
 // the search as a source of the selection stage (topk.hpp): dense rows, k_knn_hist's key bins over [kmin[q], kmax[q]]
 struct KnnSource : TopkRows {
+    const uint32_t *kmin, *kmax;
+    uint32_t lo = 0, hi = 0;  // (device: of the opened query)
+    __device__ void open(uint32_t q) {
+        TopkRows::open(q);
+        lo = kmin[q];
+        hi = kmax[q];
+    }
+    __device__ uint32_t bin(float dval) const { return knn_bin(adc_key(dval), lo, hi); }
+    uint32_t blocks() const { return (uint32_t)std::min<uint64_t>((n + 255) / 256, 64); }
+};
+
+// KnnSource under a row mask: the allowed rows only (MaskedRows, topk.hpp)
+struct MaskedKnnSource : MaskedRows {
     const uint32_t *kmin, *kmax;
     uint32_t lo = 0, hi = 0;  // (device: of the opened query)
     __device__ void open(uint32_t q) {
@@ -360,10 +443,11 @@ int knn_norms_rows(const ROWS &rows, uint64_t n, float *out, hipStream_t stream)
 
 // The batched driver of a search over resident rows: per batch of knn_query_batch(n, nq) queries (their [batch][n] f32
 // distances under 1 GB) k_knn_dist into dist_ws, the key range into kmin | kmax at the head of state_ws (reset first
-// where the stage reads it), then stage(q0, nb, kmin, kmax).
+// where the stage reads it), then stage(q0, nb, kmin, kmax).  mask: the row mask of a filtered call on the device (ceil(n /
+// 32) words; k_knn_dist_masked), NULL for every row (k_knn_dist).
 template <class ROWS, class STAGE>
 int knn_batches(int metric, const ROWS &rows, uint64_t n, const float *rnorm, const float *queries_dev, const float *qnorm_dev,
-                uint32_t nq, float *dist_ws, void *state_ws, bool reset, hipStream_t stream, STAGE &&stage) {
+                uint32_t nq, float *dist_ws, void *state_ws, bool reset, const uint32_t *mask, hipStream_t stream, STAGE &&stage) {
     const uint32_t qb = knn_query_batch(n, nq), d = rows.d;
     uint32_t *kmin = reinterpret_cast<uint32_t *>(state_ws);
     uint32_t *kmax = kmin + qb;
@@ -379,8 +463,12 @@ int knn_batches(int metric, const ROWS &rows, uint64_t n, const float *rnorm, co
         // about eight workgroups per CU in all, each a column of row tiles for one query tile
         const uint64_t per_qt = std::max<uint64_t>(1, std::min<uint64_t>(nrt, ((uint64_t)num_cus() * 8 + nqt - 1) / nqt));
         VQ_TRY(knn_metric_dispatch(metric, [&](auto mtag) -> int {
-            hipLaunchKernelGGL((k_knn_dist<decltype(mtag)::value, ROWS>), dim3((uint32_t)(per_qt * nqt)), dim3(256), 0, stream, Qb, nb,
-                               rows.X, n, d, rows.sc, qn, rnorm, nqt, nrt, dist_ws, kmin, kmax);
+            if (mask)
+                hipLaunchKernelGGL((k_knn_dist_masked<decltype(mtag)::value, ROWS>), dim3((uint32_t)(per_qt * nqt)), dim3(256), 0, stream,
+                                   Qb, nb, rows.X, n, d, rows.sc, qn, rnorm, nqt, nrt, dist_ws, kmin, kmax, mask);
+            else
+                hipLaunchKernelGGL((k_knn_dist<decltype(mtag)::value, ROWS>), dim3((uint32_t)(per_qt * nqt)), dim3(256), 0, stream, Qb, nb,
+                                   rows.X, n, d, rows.sc, qn, rnorm, nqt, nrt, dist_ws, kmin, kmax);
             VQ_LAUNCH_CHECK("k_knn_dist");
             return VQHIP_OK;
         }));
@@ -390,16 +478,24 @@ int knn_batches(int metric, const ROWS &rows, uint64_t n, const float *rnorm, co
 }
 
 // queries_dev [nq][d] f32, qnorm_dev [nq] (cosine; launch_knn_norms), workspaces sized for knn_query_batch(n, nq) queries:
-// dist_ws >= qb * n floats, state_ws >= knn_state_bytes(qb), cand_ws >= topk_cand_bytes(qb); outputs [nq][topk] on the device
+// dist_ws >= qb * n floats, state_ws >= knn_state_bytes(qb), cand_ws >= topk_cand_bytes(qb); outputs [nq][topk] on the device.
+// mask_dev: the row mask of a filtered search (the allowed rows only, padding behind fewer than topk of them) or NULL.
 template <class ROWS>
 int knn_search_rows(int metric, const ROWS &rows, uint64_t n, const float *rnorm, const float *queries_dev, const float *qnorm_dev,
                     uint32_t nq, uint32_t topk, float *dist_ws, void *state_ws, unsigned long long *cand_ws, uint32_t *idx_out_dev,
-                    float *dist_out_dev, hipStream_t stream) {
+                    float *dist_out_dev, const uint32_t *mask_dev, hipStream_t stream) {
     if (topk == 0 || topk > 1024 || topk > n) return fail(VQHIP_ERR_INVALID_INPUT, "topk must be in [1, min(n, 1024)]");
     const uint32_t qb = knn_query_batch(n, nq);
-    return knn_batches(metric, rows, n, rnorm, queries_dev, qnorm_dev, nq, dist_ws, state_ws, true, stream,
+    return knn_batches(metric, rows, n, rnorm, queries_dev, qnorm_dev, nq, dist_ws, state_ws, true, mask_dev, stream,
                        [&](uint32_t q0, uint32_t nb, uint32_t *kmin, uint32_t *kmax) -> int {
         const TopkState st = topk_state(kmax + qb, qb);
+        if (mask_dev) {
+            const MaskedKnnSource src{{{dist_ws, n}, mask_dev}, kmin, kmax};
+            hipLaunchKernelGGL(k_knn_hist_masked, dim3(src.blocks(), nb), dim3(256), 0, stream, dist_ws, n, kmin, kmax, mask_dev, st.hist);
+            VQ_LAUNCH_CHECK("k_knn_hist_masked");
+            return launch_topk_select(src, nb, topk, 0, st, cand_ws, idx_out_dev + (size_t)q0 * topk, dist_out_dev + (size_t)q0 * topk,
+                                      stream);
+        }
         const KnnSource src{{dist_ws, n}, kmin, kmax};
         hipLaunchKernelGGL(k_knn_hist, dim3(src.blocks(), nb), dim3(256), 0, stream, dist_ws, n, kmin, kmax, st.hist);
         VQ_LAUNCH_CHECK("k_knn_hist");
@@ -410,16 +506,16 @@ int knn_search_rows(int metric, const ROWS &rows, uint64_t n, const float *rnorm
 
 // knn_search_rows with the range stage behind the distances: per batch k_knn_dist, then count -> scan -> (host: total,
 // cap, room) -> fill (range.hpp).  radii_dev [nq]; the kmin / kmax k_knn_dist writes are not read; *out is complete when
-// this returns.
+// this returns.  mask_dev: the row mask of a filtered call (only allowed rows hit) or NULL.
 template <class ROWS>
 int knn_range_rows(int metric, const ROWS &rows, uint64_t n, const float *rnorm, const float *queries_dev, const float *qnorm_dev,
                    uint32_t nq, const float *radii_dev, uint64_t max_results, float *dist_ws, void *state_ws, void *range_ws,
-                   RangeOut *out, hipStream_t stream) {
+                   RangeOut *out, const uint32_t *mask_dev, hipStream_t stream) {
     if (max_results == 0) return fail(VQHIP_ERR_INVALID_INPUT, "max_results must be at least 1");
     VQ_TRY(range_begin(out, nq, max_results, stream));
-    VQ_TRY(knn_batches(metric, rows, n, rnorm, queries_dev, qnorm_dev, nq, dist_ws, state_ws, false, stream,
+    VQ_TRY(knn_batches(metric, rows, n, rnorm, queries_dev, qnorm_dev, nq, dist_ws, state_ws, false, mask_dev, stream,
                        [&](uint32_t q0, uint32_t nb, uint32_t *, uint32_t *) -> int {
-        return range_batch(dist_ws, n, nb, q0, radii_dev + q0, range_ws, max_results, out, stream);
+        return range_batch(dist_ws, n, nb, q0, radii_dev + q0, range_ws, max_results, out, stream, mask_dev);
     }));
     VQ_HIP(hipStreamSynchronize(stream));
     return VQHIP_OK;

@@ -76,6 +76,23 @@ __device__ __forceinline__ uint32_t range_load(const float *__restrict__ dq, uin
     return hits;
 }
 
+// range_load for the source SRC: under a row mask (MaskedRows, topk.hpp) the four positions' mask bits come first, a
+// group without an allowed position is not loaded, and a disallowed position never hits, whatever its slot holds
+template <bool VEC, class SRC>
+__device__ __forceinline__ uint32_t range_hits(const SRC &src, const float *__restrict__ dq, uint64_t n, uint64_t r0, float rad,
+                                               float (&v)[4]) {
+    if constexpr (topk_masked<SRC>::value) {
+        const uint32_t ok = r0 < n ? src.allowed4(r0) : 0u;
+        if (ok == 0) {
+            v[0] = v[1] = v[2] = v[3] = 0.0f;
+            return 0;
+        }
+        return range_load<VEC, SRC::kRagged>(dq, n, r0, rad, v) & ok;
+    } else {
+        return range_load<VEC, SRC::kRagged>(dq, n, r0, rad, v);
+    }
+}
+
 template <bool VEC, class SRC>
 __global__ __launch_bounds__(kRangeThreads) void k_range_count(const float *__restrict__ dist, uint64_t stride,
                                                                const uint32_t *__restrict__ pref, const uint32_t *__restrict__ seg,
@@ -98,7 +115,7 @@ __global__ __launch_bounds__(kRangeThreads) void k_range_count(const float *__re
 #pragma unroll
     for (uint32_t s = 0; s < kRangeStrides; ++s) {
         float v[4];
-        const uint32_t hits = range_load<VEC, SRC::kRagged>(dq, n, row0 + (uint64_t)s * (kRangeThreads * 4) + tid * 4, rad, v);
+        const uint32_t hits = range_hits<VEC>(src, dq, n, row0 + (uint64_t)s * (kRangeThreads * 4) + tid * 4, rad, v);
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j) c += (uint32_t)__popcll(__ballot((hits >> j) & 1u));
     }
@@ -174,7 +191,7 @@ __global__ __launch_bounds__(kRangeThreads) void k_range_fill(const float *__res
     uint32_t hits[kRangeStrides], pre[kRangeStrides];  // pre: the stride's hits in lower lanes of this wave
 #pragma unroll
     for (uint32_t s = 0; s < kRangeStrides; ++s) {
-        hits[s] = range_load<VEC, SRC::kRagged>(dq, n, row0 + (uint64_t)s * (kRangeThreads * 4) + tid * 4, rad, v[s]);
+        hits[s] = range_hits<VEC>(src, dq, n, row0 + (uint64_t)s * (kRangeThreads * 4) + tid * 4, rad, v[s]);
         uint32_t p = 0, t = 0;
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j) {
@@ -307,15 +324,18 @@ int range_passes(const RangeRows &in, uint32_t nb, uint32_t q0, const float *rad
 
 // The stage over one batch of dense distances: dist [nb][n] on the device (queued on `stream`), radii [nb] on the
 // device, ws >= range_ws_size(n, nb), q0 the batch's first query in the result.  Waits for the stream once.  A batch that
-// takes the result past max_results is VQHIP_ERR_UNSUPPORTED.
+// takes the result past max_results is VQHIP_ERR_UNSUPPORTED.  mask: the row mask of a filtered call on the device
+// (ceil(n / 32) words), NULL for every row.
 inline int range_batch(const float *dist, uint64_t n, uint32_t nb, uint32_t q0, const float *radii, void *ws, uint64_t max_results,
-                       RangeOut *out, hipStream_t stream) {
+                       RangeOut *out, hipStream_t stream, const uint32_t *mask = nullptr) {
     uint64_t got = 0;
-    VQ_TRY(range_passes<TopkRows>({dist, n}, nb, q0, radii, ws, max_results, out, &got, stream, [&](uint64_t, uint32_t **idx, float **d) {
+    auto target = [&](uint64_t, uint32_t **idx, float **d) {
         *idx = out->idx.as<uint32_t>() + out->total;  // (the result's buffers as range_scan_room left them)
         *d = out->dist.as<float>() + out->total;
         return VQHIP_OK;
-    }));
+    };
+    if (mask) VQ_TRY(range_passes<MaskedRows>({dist, n, nullptr, nullptr, mask, 0}, nb, q0, radii, ws, max_results, out, &got, stream, target));
+    else VQ_TRY(range_passes<TopkRows>({dist, n}, nb, q0, radii, ws, max_results, out, &got, stream, target));
     out->total += got;
     return VQHIP_OK;
 }

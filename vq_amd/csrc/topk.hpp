@@ -10,6 +10,10 @@
 //                           bin(d)       the histogram bin of a distance (the bin the scan filled hist with)
 //                           blocks()     (host) the collect kernel's workgroups per query
 //                         TopkRows is the dense part (dist[q][n], id = position) of the ADC and k-NN sources
+//                         a masked source (MaskedRows: kMasked, allowed(pos), allowed4(p0), row()) counts only the positions its row mask
+//                         allows; the kernels skip the others before they read a distance, so what a disallowed
+//                         position's slot holds never matters.  Its dense ties go through k_adc_topk, whose select over
+//                         (key, id) words gives ties to the lowest allowed rows
 //   adc_key / adc_unkey : the order-preserving key of a distance (NaN sorts last, reported back as 0x7FC00000)
 //   adc_scale / adc_bin : the float histogram bin of the ADC and IVF scans
 //   adc_bitonic         : the bitonic sort of (key, id) words in LDS;  adc_emit: one result slot from a word
@@ -113,6 +117,38 @@ struct TopkRows {
     __device__ uint32_t id(Pos pos) const { return (uint32_t)pos; }
 };
 
+// The dense source under a row mask (include/vqhip.h: row i is allowed iff bit i & 31 of word i >> 5 is set; ceil(n / 32)
+// words, 4-byte aligned): only allowed positions count.  allowed4(r0): the bits of positions r0 .. r0 + 3, r0 a multiple
+// of 4 below n (bits at or past n are the caller's to drop).
+struct MaskedRows : TopkRows {
+    static constexpr bool kMasked = true;
+    const uint32_t *mask;
+    // (range.hpp) the mask travels in the range kernels' `ids` argument: a dense source has no ids of its own
+    static __device__ MaskedRows rows(const float *dist, uint64_t n, const uint32_t *, const uint32_t *, const uint32_t *ids, uint32_t) {
+        return {{dist, n}, ids};
+    }
+    __device__ bool allowed(Pos pos) const { return (mask[pos >> 5] >> (uint32_t)(pos & 31u)) & 1u; }
+    __device__ uint32_t allowed4(Pos r0) const { return (mask[r0 >> 5] >> (uint32_t)(r0 & 31u)) & 0xFu; }
+};
+
+// the distances of positions p0 .. p0 + 3 of a query's row dq[0 .. n), p0 a multiple of 4 below n: one float4 where n % 4 ==
+// 0 (then every row of the [q][n] workspace starts 16-byte aligned), else the positions below n whose bit of `ok` is set
+__device__ __forceinline__ void masked_load4(const float *__restrict__ dq, uint64_t n, uint64_t p0, uint32_t ok, float (&v)[4]) {
+    if ((n & 3u) == 0) {
+        const float4 a = *reinterpret_cast<const float4 *>(dq + p0);
+        v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w;
+    } else {
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) v[j] = (((ok >> j) & 1u) && p0 + j < n) ? dq[p0 + j] : 0.0f;
+    }
+}
+
+// whether a source has positions that do not count (kMasked); the sources without the member compile to what they were
+template <class Src, class = void>
+struct topk_masked : std::false_type {};
+template <class Src>
+struct topk_masked<Src, std::enable_if_t<Src::kMasked>> : std::true_type {};
+
 // per query of a batch of qb: hist [kAdcBins] | sel [2] = {bin of the cut, positions up to it} | cand_n, in this order
 // (topk_state_bytes(qb), kernels.hpp; a family's own prefix -- ADC's bounds, k-NN's kmin / kmax -- sits in front)
 struct TopkState {
@@ -184,11 +220,27 @@ __global__ __launch_bounds__(256) void k_adc_collect(Src src, const uint32_t *__
     src.open(q);
     const uint32_t bmax = sel[2 * q];
     const Pos total = src.count();
-    for (Pos pos = (Pos)blockIdx.x * 256 + threadIdx.x; pos < total; pos += (Pos)gridDim.x * 256) {
-        const float dv = src.at(pos);
-        if (src.bin(dv) <= bmax) {
-            const uint32_t at = atomicAdd(&cand_n[q], 1u);
-            if (at < kAdcCand) cand[(size_t)q * kAdcCand + at] = ((unsigned long long)adc_key(dv) << 32) | src.id(pos);
+    if constexpr (topk_masked<Src>::value) {
+        // four consecutive positions per lane: one mask read for the four, and no distance read without an allowed one
+        for (Pos p0 = ((Pos)blockIdx.x * 256 + threadIdx.x) * 4; p0 < total; p0 += (Pos)gridDim.x * 1024) {
+            const uint32_t ok = src.allowed4(p0);
+            if (ok == 0) continue;
+            float v[4];
+            masked_load4(src.row(), total, p0, ok, v);
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j)
+                if (((ok >> j) & 1u) && p0 + j < total && src.bin(v[j]) <= bmax) {
+                    const uint32_t at = atomicAdd(&cand_n[q], 1u);
+                    if (at < kAdcCand) cand[(size_t)q * kAdcCand + at] = ((unsigned long long)adc_key(v[j]) << 32) | src.id(p0 + j);
+                }
+        }
+    } else {
+        for (Pos pos = (Pos)blockIdx.x * 256 + threadIdx.x; pos < total; pos += (Pos)gridDim.x * 256) {
+            const float dv = src.at(pos);
+            if (src.bin(dv) <= bmax) {
+                const uint32_t at = atomicAdd(&cand_n[q], 1u);
+                if (at < kAdcCand) cand[(size_t)q * kAdcCand + at] = ((unsigned long long)adc_key(dv) << 32) | src.id(pos);
+            }
         }
     }
 }
@@ -238,6 +290,8 @@ __global__ __launch_bounds__(1024) void k_adc_topk(Src src, uint32_t topk, int t
             __syncthreads();
             const uint32_t prefix = s_prefix, himask = (shift == 24) ? 0u : (0xFFFFFFFFu << (shift + 8));
             for (Pos pos = tid; pos < total; pos += 1024) {
+                if constexpr (topk_masked<Src>::value)
+                    if (!src.allowed(pos)) continue;
                 const uint32_t key = adc_key(src.at(pos));
                 uint32_t v = key;
                 if (pass == 1) {
@@ -270,6 +324,8 @@ __global__ __launch_bounds__(1024) void k_adc_topk(Src src, uint32_t topk, int t
     win[tid] = ~0ull;
     __syncthreads();
     for (Pos pos = tid; pos < total; pos += 1024) {
+        if constexpr (topk_masked<Src>::value)
+            if (!src.allowed(pos)) continue;
         const uint32_t key = adc_key(src.at(pos));
         if (key > T) continue;
         const unsigned long long w = ((unsigned long long)key << 32) | src.id(pos);
@@ -401,7 +457,7 @@ int launch_topk_select(const Src &src, uint32_t nb, uint32_t topk, int take_sqrt
     hipLaunchKernelGGL(k_adc_sort_out, dim3(nb), dim3(1024), (size_t)kAdcCand * 8, stream, cand, st.sel, topk, take_sqrt, idx_out,
                        dist_out);
     VQ_LAUNCH_CHECK("k_adc_sort_out");
-    if constexpr (std::is_base_of<TopkRows, Src>::value)
+    if constexpr (std::is_base_of<TopkRows, Src>::value && !topk_masked<Src>::value)
         hipLaunchKernelGGL(k_adc_topk_rows, dim3(nb), dim3(1024), 0, stream, src, topk, take_sqrt, st.sel, idx_out, dist_out);
     else
         hipLaunchKernelGGL(k_adc_topk<Src>, dim3(nb), dim3(1024), 0, stream, src, topk, take_sqrt, st.sel, idx_out, dist_out);
