@@ -1060,6 +1060,41 @@ class IvfIndex {
         check(Range(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, radii, max_results, &r));
         return read_range(r);
     }
+    // The filtered forms of the same two indexes: `allowed` is the row mask of the call, ceil(n / 32) words for the n rows
+    // the index holds now (pack_row_mask).  Probing takes no mask; the searched set is the allowed rows of the probed lists.
+    template <int (*SearchMasked)(H *, const float *, std::uint32_t, std::uint32_t, std::uint32_t, const std::uint32_t *, std::uint32_t *,
+                                  float *)>
+    Result masked(const float *queries, std::size_t nq, std::size_t topk, std::size_t nprobe, const std::uint32_t *allowed) const {
+        check_row_mask(allowed);
+        check_probe(nprobe, nq);
+        if (topk == 0 || topk > 1024 || topk > n_) throw VqError::InvalidParameter("topk", "must be between 1 and min(n, 1024)");
+        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
+        if (nq)
+            check(SearchMasked(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, (std::uint32_t)topk, allowed, r.idx.data(),
+                               r.dist.data()));
+        return r;
+    }
+    template <int (*RangeMasked)(H *, const float *, std::uint32_t, std::uint32_t, const float *, std::uint64_t, const std::uint32_t *,
+                                 vqhip_range **)>
+    RangeResult range_masked(const float *queries, std::size_t nq, const float *radii, std::size_t nprobe, std::uint64_t max_results,
+                             const std::uint32_t *allowed) const {
+        check_row_mask(allowed);
+        check_range_args(radii, nq, max_results);
+        check_probe(nprobe, nq);
+        if (nq == 0) return RangeResult{std::vector<std::uint64_t>(1, 0), {}, {}};
+        vqhip_range *r = nullptr;
+        check(RangeMasked(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, radii, max_results, allowed, &r));
+        return read_range(r);
+    }
+    // the vector forms' checks: the mask's length against the rows the index holds, whole queries, one radius per query
+    std::size_t check_masked_vectors(const std::vector<float> &queries, const std::vector<std::uint32_t> &allowed,
+                                     const std::vector<float> *radii) const {
+        check_row_mask(allowed, n_);
+        if (queries.size() % dim_) throw VqError::DimensionMismatch(dim_, queries.size() % dim_);
+        const std::size_t nq = queries.size() / dim_;
+        if (radii && radii->size() != nq) throw VqError::DimensionMismatch(nq, radii->size());
+        return nq;
+    }
 };
 }  // namespace detail
 
@@ -1132,6 +1167,28 @@ class IVFFlatIndex : public detail::IvfIndex<vqhip_ivfflat, vqhip_ivfflat_destro
         return range<vqhip_ivfflat_range_search>(queries, nq, radii, nprobe, max_results);
     }
 
+    // The filtered forms (include/vqhip.h, vqhip_ivfflat_search_masked / _range_search_masked): the nearest among the allowed
+    // rows of the probed lists, padded with (0xFFFFFFFF, +inf) behind fewer than topk of them; only allowed rows hit a range
+    // query.  With nprobe == nlist they are FlatIndex's filtered search and range_search.  The mask comes last, and
+    // max_results has no default beside it, so that a literal 0 never reads as a null mask.
+    using IvfIndex::search;
+    Result search(const float *queries, std::size_t nq, std::size_t topk, std::size_t nprobe, const std::uint32_t *allowed) const {
+        return masked<vqhip_ivfflat_search_masked>(queries, nq, topk, nprobe, allowed);
+    }
+    Result search(const std::vector<float> &queries, std::size_t topk, std::size_t nprobe, const std::vector<std::uint32_t> &allowed) const {
+        const std::size_t nq = check_masked_vectors(queries, allowed, nullptr);
+        return search(queries.data(), nq, topk, nprobe, allowed.data());
+    }
+    RangeResult range_search(const float *queries, std::size_t nq, const float *radii, std::size_t nprobe, std::uint64_t max_results,
+                             const std::uint32_t *allowed) const {
+        return range_masked<vqhip_ivfflat_range_search_masked>(queries, nq, radii, nprobe, max_results, allowed);
+    }
+    RangeResult range_search(const std::vector<float> &queries, const std::vector<float> &radii, std::size_t nprobe,
+                             std::uint64_t max_results, const std::vector<std::uint32_t> &allowed) const {
+        const std::size_t nq = check_masked_vectors(queries, allowed, &radii);
+        return range_search(queries.data(), nq, radii.data(), nprobe, max_results, allowed.data());
+    }
+
     // rows appended in order: list_ids [n] < nlist, rows [n][dim] in the index's row type; returns the first new row id
     std::size_t add(const std::uint32_t *list_ids, const void *rows, std::size_t n) {
         check_add(list_ids, n, "rows");
@@ -1166,6 +1223,28 @@ class IVFScalarIndex
     RangeResult range_search(const float *queries, std::size_t nq, const float *radii, std::size_t nprobe,
                              std::uint64_t max_results = std::uint64_t(1) << 28) const {
         return range<vqhip_ivfsq_range_search>(queries, nq, radii, nprobe, max_results);
+    }
+
+    // The filtered forms (include/vqhip.h, vqhip_ivfsq_search_masked / _range_search_masked): the nearest among the allowed
+    // rows of the probed lists, padded with (0xFFFFFFFF, +inf) behind fewer than topk of them; only allowed rows hit a range
+    // query.  With nprobe == nlist they are ScalarIndex's filtered search and range_search.  The mask comes last, and
+    // max_results has no default beside it, so that a literal 0 never reads as a null mask.
+    using IvfIndex::search;
+    Result search(const float *queries, std::size_t nq, std::size_t topk, std::size_t nprobe, const std::uint32_t *allowed) const {
+        return masked<vqhip_ivfsq_search_masked>(queries, nq, topk, nprobe, allowed);
+    }
+    Result search(const std::vector<float> &queries, std::size_t topk, std::size_t nprobe, const std::vector<std::uint32_t> &allowed) const {
+        const std::size_t nq = check_masked_vectors(queries, allowed, nullptr);
+        return search(queries.data(), nq, topk, nprobe, allowed.data());
+    }
+    RangeResult range_search(const float *queries, std::size_t nq, const float *radii, std::size_t nprobe, std::uint64_t max_results,
+                             const std::uint32_t *allowed) const {
+        return range_masked<vqhip_ivfsq_range_search_masked>(queries, nq, radii, nprobe, max_results, allowed);
+    }
+    RangeResult range_search(const std::vector<float> &queries, const std::vector<float> &radii, std::size_t nprobe,
+                             std::uint64_t max_results, const std::vector<std::uint32_t> &allowed) const {
+        const std::size_t nq = check_masked_vectors(queries, allowed, &radii);
+        return range_search(queries.data(), nq, radii.data(), nprobe, max_results, allowed.data());
     }
 
     // rows appended in order: list_ids [n] < nlist, codes [n][dim] (every byte value is legal); returns the first new row id

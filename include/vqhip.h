@@ -815,6 +815,49 @@ int vqhip_ivfsq_range_search(vqhip_ivfsq *ix, const float *queries, uint32_t nq,
 int vqhip_ivfsq_range_search_device(vqhip_ivfsq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, const float *radii,
                                     uint64_t max_results, vqhip_range **out);
 
+/* ---- filtered search on the inverted-file flat and scalar index (ivf_view.hpp, ivf_tile.hpp) ------------------------
+ * No reference counterpart.  The ROW MASK is the flat index's (vqhip_flat_search_masked above): ceil(n / 32) u32 words,
+ * 4-byte aligned, n the rows in the index at the time of the call (it grows with every add); row i is ALLOWED iff bit
+ * i & 31 of word i >> 5 is set; bits at or past n are ignored; one mask serves all queries of a call.
+ *   probing              is unchanged: P(q) is the nprobe nearest lists, and vqhip_*_probe takes no mask (a list without an
+ *                        allowed row is probed like any other), which keeps nprobe == nlist equal to the exact filtered search.
+ *   searched set         S_a(q) = { i in S(q) : i allowed }.
+ *   search_masked        per query the first topk of S_a(q) by (adc_key(D), row id) ascending; D is exactly what the
+ *                        unmasked call reports.  Allowed rows with a NaN distance sort last, are reported as 0x7FC00000 and
+ *                        come before the padding; slots past |S_a(q)| hold idx 0xFFFFFFFF and dist +inf.  topk keeps its
+ *                        bound 1 .. min(n, 1024), whatever the mask.
+ *   range_search_masked  row i is a hit of query q iff i is in S_a(q) and D(q, i) <= radii[q] as an f32 comparison; the CSR
+ *                        result, its order (ascending row id within a query) and max_results are vqhip_ivfflat_range_search's.
+ * Identities: a mask of all ones gives the unmasked call's result bit for bit; with nprobe == nlist the result equals
+ * vqhip_flat_search_masked / vqhip_flat_range_search_masked (vqhip_sqindex_* for the scalar index) over the rows in add
+ * order under the same mask, indices and distance bits; at every nprobe the masked scalar index equals the masked flat
+ * index (dtype 0) over the rows vqhip_sq_decode gives for the codes; a mask of all zeros gives padding only (lims = 0 for
+ * a range search).  A call without a mask (the entry points above) launches the kernels it always launched.
+ * allowed: HOST memory in the host forms (copied into a workspace of the handle), a 4-byte aligned DEVICE pointer in the
+ * device forms (else VQHIP_ERR_INVALID_INPUT); NULL is VQHIP_ERR_NULL_PTR, reported with the other pointers (range: behind
+ * the radii, before the index handle) and before any device is touched.  The other arguments, their checks and the order
+ * of the checks are the unmasked siblings'.  A filtered call builds, once, the inverted file of its allowed rows on the
+ * device (8 bytes per row of workspace on the handle) and searches that: work behind the probe is proportional to the
+ * allowed rows of the probed lists.  vqhip_ivfpq and vqhip_ivfbin have no filtered form. */
+int vqhip_ivfflat_search_masked(vqhip_ivfflat *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                                const uint32_t *allowed, uint32_t *idx_out, float *dist_out);
+int vqhip_ivfflat_search_masked_device(vqhip_ivfflat *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                                       const uint32_t *dev_allowed, void *dev_idx, void *dev_dist);
+int vqhip_ivfflat_range_search_masked(vqhip_ivfflat *ix, const float *queries, uint32_t nq, uint32_t nprobe, const float *radii,
+                                      uint64_t max_results, const uint32_t *allowed, vqhip_range **out);
+int vqhip_ivfflat_range_search_masked_device(vqhip_ivfflat *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe,
+                                             const float *radii, uint64_t max_results, const uint32_t *dev_allowed,
+                                             vqhip_range **out);
+int vqhip_ivfsq_search_masked(vqhip_ivfsq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                              const uint32_t *allowed, uint32_t *idx_out, float *dist_out);
+int vqhip_ivfsq_search_masked_device(vqhip_ivfsq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                                     const uint32_t *dev_allowed, void *dev_idx, void *dev_dist);
+int vqhip_ivfsq_range_search_masked(vqhip_ivfsq *ix, const float *queries, uint32_t nq, uint32_t nprobe, const float *radii,
+                                    uint64_t max_results, const uint32_t *allowed, vqhip_range **out);
+int vqhip_ivfsq_range_search_masked_device(vqhip_ivfsq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe,
+                                           const float *radii, uint64_t max_results, const uint32_t *dev_allowed,
+                                           vqhip_range **out);
+
 /* ---- inverted-file binary index: Hamming top-k over packed BQ bits in the probed lists (k_ivfbin.hip) ---------
  * No reference counterpart.  vqhip_ivfflat's probe and schedule over vqhip_binary's codes.  An index is fixed by a
  * BinaryQuantizer(threshold, low, high) -- the parameters go through vqhip_bq_check, whose status and text create reports

@@ -219,7 +219,9 @@ class IVFIndexBase:
             return np.empty((0, t), np.uint32), np.empty((0, t), np.float32)
         return self._handle().search(q, p, t)
 
-    def _search_rerank(self, q, topk: int, nprobe: int, rerank, candidates):
+    def _search_rerank(self, q, topk: int, nprobe: int, rerank, candidates, allowed=None):
+        """allowed: the row-mask words of a filtered call (IVFFilterMixin) -- the first stage then returns allowed rows
+        only, and the reranker needs nothing"""
         from .flat import rerank_candidates
 
         c = rerank_candidates(len(self), self.dim, topk, rerank, candidates)
@@ -228,7 +230,10 @@ class IVFIndexBase:
         dist = np.full((nq, topk), np.inf, np.float32)
         if nq == 0:
             return idx, dist
-        hits, _ = self._handle().search(q, nprobe, c)
+        if allowed is None:
+            hits, _ = self._handle().search(q, nprobe, c)
+        else:
+            hits, _ = self._handle().search_masked(q, nprobe, c, allowed)
         real = (hits != PAD_ID).sum(axis=1)  # (padding follows every real hit)
         full = real == c
         if full.any():

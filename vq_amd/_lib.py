@@ -213,6 +213,10 @@ SIGNATURES = {
     "vqhip_ivfflat_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
     "vqhip_ivfflat_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _vpp]),
     "vqhip_ivfflat_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _vpp]),
+    "vqhip_ivfflat_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p]),
+    "vqhip_ivfflat_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "vqhip_ivfflat_range_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _u32p, _vpp]),
+    "vqhip_ivfflat_range_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _vp, _vpp]),
     "vqhip_ivfsq_create": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_int, _vpp]),
     "vqhip_ivfsq_destroy": (C.c_int, [_vp]),
     "vqhip_ivfsq_add_codes": (C.c_int, [_vp, _u32p, _u8p, C.c_uint64]),
@@ -225,6 +229,10 @@ SIGNATURES = {
     "vqhip_ivfsq_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
     "vqhip_ivfsq_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _vpp]),
     "vqhip_ivfsq_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _vpp]),
+    "vqhip_ivfsq_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p]),
+    "vqhip_ivfsq_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "vqhip_ivfsq_range_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _u32p, _vpp]),
+    "vqhip_ivfsq_range_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _vp, _vpp]),
     "vqhip_ivfbin_create": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, _vpp]),
     "vqhip_ivfbin_destroy": (C.c_int, [_vp]),
     "vqhip_ivfbin_add_packed": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64]),
@@ -1045,6 +1053,29 @@ class _IVFExactHandle(_IVFHandle):
 
     def range_search_device(self, dev_queries: int, nq: int, nprobe: int, radii: np.ndarray, max_results: int) -> RangeResult:
         return _range_call(self._fn("range_search_device"), self.raw, C.c_void_p(dev_queries), nq, radii, max_results, int(nprobe))
+
+    # the filtered forms: `allowed` uint32 (ceil(n / 32),) row-mask words on the host, `dev_allowed` the same at a device
+    # pointer (4-byte aligned)
+    def search_masked(self, q: np.ndarray, nprobe: int, topk: int, allowed: np.ndarray):
+        nq = q.shape[0]
+        idx = np.empty((nq, topk), np.uint32)
+        dist = np.empty((nq, topk), np.float32)
+        check(self._fn("search_masked")(self.raw, ptr(q, _f32p), nq, int(nprobe), int(topk), ptr(allowed, _u32p), ptr(idx, _u32p),
+                                        ptr(dist, _f32p)))
+        return idx, dist
+
+    def search_masked_device(self, dev_queries: int, nq: int, nprobe: int, topk: int, dev_allowed: int, dev_idx: int, dev_dist: int):
+        check(self._fn("search_masked_device")(self.raw, C.c_void_p(dev_queries), int(nq), int(nprobe), int(topk),
+                                               C.c_void_p(dev_allowed), C.c_void_p(dev_idx), C.c_void_p(dev_dist)))
+
+    def range_search_masked(self, q: np.ndarray, nprobe: int, radii: np.ndarray, max_results: int, allowed: np.ndarray) -> RangeResult:
+        return _range_call(self._fn("range_search_masked"), self.raw, ptr(q, _f32p), q.shape[0], radii, max_results, int(nprobe),
+                           back=(ptr(allowed, _u32p),))
+
+    def range_search_masked_device(self, dev_queries: int, nq: int, nprobe: int, radii: np.ndarray, max_results: int,
+                                   dev_allowed: int) -> RangeResult:
+        return _range_call(self._fn("range_search_masked_device"), self.raw, C.c_void_p(dev_queries), nq, radii, max_results,
+                           int(nprobe), back=(C.c_void_p(dev_allowed),))
 
 
 class IVFPQ(_IVFHandle):

@@ -3755,6 +3755,12 @@ static int ivf_batch(IvfLists *ix, uint32_t nq, uint32_t nprobe, uint64_t query_
     return VQHIP_OK;
 }
 
+// IvfView: the inverted file of a filtered call's allowed rows on the device (ivf_view.hpp; launch_ivf_view) -- what a
+// batch's view takes in place of d_off / d_ids, and the positions of its rows in the payload.  All NULL: every row.
+struct IvfView {
+    const uint32_t *pick = nullptr, *aids = nullptr, *aoff = nullptr;
+};
+
 // The front of every probe and search (T: an index with ready(s)): the checks in their order, the index's device, the
 // calling thread's stream, the device state -- then body(in, s).  topk NULL: a probe.
 template <class T, class F>
@@ -3795,6 +3801,28 @@ static int ivf_search_device(T *ix, const void *dev_queries, uint32_t nq, uint32
     return ivf_enter(ix, dev_queries && dev_idx && dev_dist, nq, nprobe, &topk, [&](Entry &, hipStream_t s) {
         return ix->search_enqueue(reinterpret_cast<const float *>(dev_queries), nq, nprobe, topk, reinterpret_cast<uint32_t *>(dev_idx),
                                   reinterpret_cast<float *>(dev_dist), s);
+    });
+}
+
+// The filtered forms of the two (vqhip_ivfflat and vqhip_ivfsq, IvfExact below): the row mask `allowed` (host: ceil(n /
+// 32) words, staged on the handle; device: a 4-byte aligned pointer) becomes the call's view once, after ready(s) and
+// under the handle's lock (ix->filtered), and the search runs over it.  A NULL mask is reported before a device is touched.
+template <class T>
+static int ivf_search_masked(T *ix, const void *queries, bool host, uint32_t nq, uint32_t nprobe, uint32_t topk, const uint32_t *allowed,
+                             void *idx_out, void *dist_out) {
+    if (!queries || !idx_out || !dist_out || !allowed) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (!host) VQ_TRY(check_mask_aligned(allowed));  // (like the pointers, before the handle is looked at)
+    return ivf_enter(ix, true, nq, nprobe, &topk, [&](Entry &in, hipStream_t s) -> int {
+        IvfView view;
+        VQ_TRY(ix->filtered(allowed, host, s, &view));
+        if (!host)
+            return ix->search_enqueue(reinterpret_cast<const float *>(queries), nq, nprobe, topk, reinterpret_cast<uint32_t *>(idx_out),
+                                      reinterpret_cast<float *>(dist_out), s, &view);
+        return host_search(in, s, ix->q, ix->idx, &ix->out, reinterpret_cast<const float *>(queries), nq, ix->dim, topk,
+                           reinterpret_cast<uint32_t *>(idx_out), reinterpret_cast<float *>(dist_out), [&] {
+            return ix->search_enqueue(ix->q.template as<float>(), nq, nprobe, topk, ix->idx.template as<uint32_t>(),
+                                      ix->out.template as<float>(), s, &view);
+        });
     });
 }
 
@@ -3964,9 +3992,11 @@ struct IvfOverW : IvfLists {
 
     // The batch loop: queries_dev [nq][dim] f32 in ivf_batch's batches -- the probe, the plan, the index's distances, then
     // stage(p, v, q0) behind them.  topk: the selection's; 0: the range stage follows (its workspace is sized here for
-    // the largest batch, and the plan's check is given 1).  Enqueued on s.
+    // the largest batch, and the plan's check is given 1).  Enqueued on s.  view: a filtered call's (NULL: every row); the
+    // batches then run over its lists and ids, wstride and max_list keeping their unfiltered bounds.
     template <class Stage>
-    int batches(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk, hipStream_t s, Stage &&stage_fn) {
+    int batches(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk, const IvfView *view, hipStream_t s,
+                Stage &&stage_fn) {
         T *ix = static_cast<T *>(this);
         IvfBatch b;
         VQ_TRY(ivf_batch(this, nq, nprobe, 0, &b));
@@ -3975,13 +4005,15 @@ struct IvfOverW : IvfLists {
         VQ_TRY(state.ensure(knn_state_bytes(b.nb_max)));
         if (topk == 0) VQ_TRY(range_ws.ensure(ivff_range_ws_bytes(b.wstride, b.nb_max)));
         VQ_TRY(ix->prepare(queries_dev, nq, b.nb_max, s));
+        const bool fv = view && view->pick;
         for (uint32_t q0 = 0; q0 < nq; q0 += b.nb_max) {
             const uint32_t nb = std::min(b.nb_max, nq - q0);
             const float *Q = queries_dev + (size_t)q0 * dim;
             VQ_TRY(ivf_probe_enqueue(this, Q, nb, nprobe, probe.as<uint32_t>(), s));  // (the f32 queries, whatever the rows are)
-            const IvfBatchView v{d_ids.as<uint32_t>(), n, d_off.as<uint32_t>(), nlist, max_list,
+            const IvfBatchView v{fv ? view->aids : d_ids.as<uint32_t>(), n, fv ? view->aoff : d_off.as<uint32_t>(), nlist, max_list,
                                  probe.as<uint32_t>(), nb, nprobe, ivf_chunk((uint64_t)nb * b.per_q), b.wstride,
-                                 W.as<float>(), pref.as<uint32_t>(), seg.as<uint32_t>(), inv.as<uint32_t>(), lists.as<uint32_t>(), state.p};
+                                 W.as<float>(), pref.as<uint32_t>(), seg.as<uint32_t>(), inv.as<uint32_t>(), lists.as<uint32_t>(), state.p,
+                                 fv ? view->pick : nullptr};
             IvffPlan p;
             VQ_TRY(launch_ivff_plan(v, topk ? topk : 1, &p, s));
             VQ_TRY(ix->distances(p, v, Q, q0, s));
@@ -3992,21 +4024,22 @@ struct IvfOverW : IvfLists {
 
     // queries_dev [nq][dim] f32 -> [nq][topk] results on the device, enqueued on s
     int search_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
-                       hipStream_t s) {
-        return batches(queries_dev, nq, nprobe, topk, s, [&](const IvffPlan &p, const IvfBatchView &v, uint32_t q0) {
+                       hipStream_t s, const IvfView *view = nullptr) {
+        return batches(queries_dev, nq, nprobe, topk, view, s, [&](const IvffPlan &p, const IvfBatchView &v, uint32_t q0) {
             return launch_ivff_select(p, v, topk, cand.as<unsigned long long>(), idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s);
         });
     }
 
     // queries_dev [nq][dim] f32 and the radii (this->radii, [nq]) -> *out, complete on return
-    int range_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint64_t max_results, RangeOut *out, hipStream_t s) {
+    int range_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint64_t max_results, RangeOut *out, hipStream_t s,
+                      const IvfView *view = nullptr) {
         VQ_TRY(launch_range_begin(out, nq, max_results, s));
         if (n == 0) {  // no rows: every query's range is empty
             VQ_HIP(hipMemsetAsync(out->lims.p, 0, ((size_t)nq + 1) * 8, s));
             VQ_HIP(hipStreamSynchronize(s));
             return VQHIP_OK;
         }
-        VQ_TRY(batches(queries_dev, nq, nprobe, 0, s, [&](const IvffPlan &, const IvfBatchView &v, uint32_t q0) {
+        VQ_TRY(batches(queries_dev, nq, nprobe, 0, view, s, [&](const IvffPlan &, const IvfBatchView &v, uint32_t q0) {
             return launch_ivff_range(v, q0, radii.as<float>() + q0, range_ws.p, &stage, max_results, out, s);
         }));
         VQ_HIP(hipStreamSynchronize(s));
@@ -4021,6 +4054,28 @@ template <class T>
 struct IvfExact : IvfOverW<T> {
     DevBuf d_rnorm;
     DevBuf qnorm;  // per-call workspace
+    DevBuf mask_ws;                         // a filtered host call's row mask on the device
+    DevBuf v_pick, v_aids, v_aoff, v_ws;  // a filtered call's view (8 bytes per row) and the workspace of its scan
+
+    // The view of a filtered call, built once per call: after ready(s), under the handle's lock, enqueued on s.  allowed:
+    // the row mask, ceil(n / 32) words for the n of this call -- a host form's goes up into mask_ws first.
+    int filtered(const uint32_t *allowed, bool host, hipStream_t s, IvfView *view) {
+        const uint64_t n = this->n;
+        if (host) {
+            const size_t mask_b = (size_t)((n + 31) / 32) * 4;
+            VQ_TRY(mask_ws.ensure(mask_b));
+            if (mask_b) VQ_HIP(hipMemcpyAsync(mask_ws.p, allowed, mask_b, hipMemcpyHostToDevice, s));
+            allowed = mask_ws.as<uint32_t>();
+        }
+        VQ_TRY(v_pick.ensure((size_t)n * 4));
+        VQ_TRY(v_aids.ensure((size_t)n * 4));
+        VQ_TRY(v_aoff.ensure(((size_t)this->nlist + 1) * 4));
+        VQ_TRY(v_ws.ensure(ivf_view_ws_bytes(n)));
+        VQ_TRY(launch_ivf_view(allowed, this->d_ids.template as<uint32_t>(), n, this->d_off.template as<uint32_t>(), this->nlist, v_ws.p,
+                               v_pick.as<uint32_t>(), v_aids.as<uint32_t>(), v_aoff.as<uint32_t>(), s));
+        *view = IvfView{v_pick.as<uint32_t>(), v_aids.as<uint32_t>(), v_aoff.as<uint32_t>()};
+        return VQHIP_OK;
+    }
 
     int radii_up(const float *r, uint32_t nq, hipStream_t s) {
         VQ_TRY(this->radii.ensure((size_t)nq * 4));
@@ -4123,6 +4178,23 @@ static int ivf_range(T *ix, const void *queries, bool host, uint32_t nq, uint32_
         return ix->range_enqueue(qdev, nq, nprobe, max_results, r, s);
     });
 }
+// ivf_range under the row mask `allowed` of a filtered call on a flat or a scalar index: the mask's pointer is checked
+// behind range_args and, like them, before the handle; the view is built behind ready(s) (ix->filtered).
+template <class T>
+static int ivf_range_masked(T *ix, const void *queries, bool host, uint32_t nq, uint32_t nprobe, const float *radii,
+                            uint64_t max_results, const uint32_t *allowed, vqhip_range **out) {
+    VQ_TRY(range_args(queries, radii, nq, max_results, out));
+    if (!allowed) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (!host) VQ_TRY(check_mask_aligned(allowed));
+    return range_enter(ix, queries, host, nq, radii, max_results, out, [&] { return ivf_check_probe(ix, nprobe); },
+                       [&](const float *qdev, RangeOut *r, hipStream_t s) -> int {
+        VQ_TRY(ix->ready(s));
+        IvfView view;
+        if (ix->n) VQ_TRY(ix->filtered(allowed, host, s, &view));  // (no rows: range_enqueue's empty result)
+        VQ_TRY(ix->radii_up(radii, nq, s));
+        return ix->range_enqueue(qdev, nq, nprobe, max_results, r, s, &view);
+    });
+}
 
 extern "C" {
 
@@ -4201,6 +4273,35 @@ int vqhip_ivfflat_range_search_device(vqhip_ivfflat *ix, const void *dev_queries
                                       uint64_t max_results, vqhip_range **out) {
     VQ_API_BEGIN
     return ivf_range(ix, dev_queries, false, nq, nprobe, radii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_ivfflat_search_masked(vqhip_ivfflat *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                                const uint32_t *allowed, uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    return ivf_search_masked(ix, queries, true, nq, nprobe, topk, allowed, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_ivfflat_search_masked_device(vqhip_ivfflat *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                                       const uint32_t *dev_allowed, void *dev_idx, void *dev_dist) {
+    VQ_API_BEGIN
+    return ivf_search_masked(ix, dev_queries, false, nq, nprobe, topk, dev_allowed, dev_idx, dev_dist);
+    VQ_API_END
+}
+
+int vqhip_ivfflat_range_search_masked(vqhip_ivfflat *ix, const float *queries, uint32_t nq, uint32_t nprobe, const float *radii,
+                                      uint64_t max_results, const uint32_t *allowed, vqhip_range **out) {
+    VQ_API_BEGIN
+    return ivf_range_masked(ix, queries, true, nq, nprobe, radii, max_results, allowed, out);
+    VQ_API_END
+}
+
+int vqhip_ivfflat_range_search_masked_device(vqhip_ivfflat *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe,
+                                             const float *radii, uint64_t max_results, const uint32_t *dev_allowed,
+                                             vqhip_range **out) {
+    VQ_API_BEGIN
+    return ivf_range_masked(ix, dev_queries, false, nq, nprobe, radii, max_results, dev_allowed, out);
     VQ_API_END
 }
 
@@ -4311,6 +4412,35 @@ int vqhip_ivfsq_range_search_device(vqhip_ivfsq *ix, const void *dev_queries, ui
                                     uint64_t max_results, vqhip_range **out) {
     VQ_API_BEGIN
     return ivf_range(ix, dev_queries, false, nq, nprobe, radii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_ivfsq_search_masked(vqhip_ivfsq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                              const uint32_t *allowed, uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    return ivf_search_masked(ix, queries, true, nq, nprobe, topk, allowed, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_ivfsq_search_masked_device(vqhip_ivfsq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                                     const uint32_t *dev_allowed, void *dev_idx, void *dev_dist) {
+    VQ_API_BEGIN
+    return ivf_search_masked(ix, dev_queries, false, nq, nprobe, topk, dev_allowed, dev_idx, dev_dist);
+    VQ_API_END
+}
+
+int vqhip_ivfsq_range_search_masked(vqhip_ivfsq *ix, const float *queries, uint32_t nq, uint32_t nprobe, const float *radii,
+                                    uint64_t max_results, const uint32_t *allowed, vqhip_range **out) {
+    VQ_API_BEGIN
+    return ivf_range_masked(ix, queries, true, nq, nprobe, radii, max_results, allowed, out);
+    VQ_API_END
+}
+
+int vqhip_ivfsq_range_search_masked_device(vqhip_ivfsq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe,
+                                           const float *radii, uint64_t max_results, const uint32_t *dev_allowed,
+                                           vqhip_range **out) {
+    VQ_API_BEGIN
+    return ivf_range_masked(ix, dev_queries, false, nq, nprobe, radii, max_results, dev_allowed, out);
     VQ_API_END
 }
 

@@ -6,6 +6,7 @@
 //   ivf_tile_store   the write-back of one row tile: every D into W[q][pref[q][slot] + r], the key range per lane
 //   k_ivff_tile      knn_tile_pass over the rows of one list, the queries gathered through inv
 //   k_ivff_scan      one query x one chunk of its positions, the query in LDS, one position per lane
+//   PickedRows       a row source behind the view of a filtered call (ivf_view.hpp): row j of it is row pick[j] of X
 //   ivff_distances   the host side of the two, templated on the row source as the kernels are
 // Every including file gets its own copy (an anonymous namespace); each .hip instantiates what it launches.
 #pragma once
@@ -18,6 +19,38 @@
 
 namespace vqhip {
 namespace {
+
+// The picked form of a row source ROWS, for the view of a filtered call (ivf_view.hpp): row j of the
+// source is row pick[j] of X, and a list of the view is the run aoff[l] .. aoff[l + 1] of pick.  It holds no loader of its
+// own: fill is ROWS::fill_rows with pick[row0 + r] as tile row r (a row's 32 dimensions of a chunk are still read by
+// consecutive lanes), walk is ROWS::walk of row pick[row], and row(j), the index of a row's norm, is pick[j].  Row offsets
+// stay 64-bit: (uint64_t)pick[j] * d.  The alignment conditions of ROWS rest on d and the base of X, so they hold for
+// any row.  pick travels in Scale, so the kernels' parameter lists are those of the unpicked instantiations.
+template <class S>
+struct PickedScale {  // (one type per Scale: a source and its Walk share it)
+    S sc;
+    const uint32_t *pick;
+};
+template <class ROWS>
+struct PickedRows {
+    using Elem = typename ROWS::Elem;
+    using Walk = PickedRows<typename ROWS::Walk>;
+    using Scale = PickedScale<typename ROWS::Scale>;
+    const Elem *X;
+    uint32_t d;
+    Scale sc;
+
+    __device__ __forceinline__ void fill(float (&rs)[kKnnKC][kKnnTR + 4], uint64_t row0, uint32_t nvalid, uint32_t t0,
+                                         uint32_t tc) const {
+        const uint32_t *__restrict__ p = sc.pick + row0;
+        ROWS{X, d, sc.sc}.fill_rows(rs, [&](uint32_t r) { return (uint64_t)p[r]; }, nvalid, t0, tc);
+    }
+    template <class F>
+    __device__ __forceinline__ void walk(uint64_t row, uint32_t t0, uint32_t tc, bool vec, F &&f) const {
+        ROWS{X, d, sc.sc}.walk((uint64_t)sc.pick[row], t0, tc, vec, f);
+    }
+    __device__ __forceinline__ uint64_t row(uint64_t j) const { return sc.pick[j]; }
+};
 
 // The work item of block x of a tile kernel: *row0 / *nrows the run of its list (the last list whose first tile is <=
 // the block's, and that has tiles: tstart is non-decreasing), s_q the tile's queries (kKnnNone: none) and s_p the first
@@ -115,7 +148,7 @@ __global__ __launch_bounds__(256) void k_ivff_tile(const float *__restrict__ Q, 
         const uint32_t rb = r0 + rg * RR;
         float rn[RR];
 #pragma unroll
-        for (uint32_t b = 0; b < RR; ++b) rn[b] = (vq_is_cos(METRIC) && rb + b < nrows) ? rnorm[(uint64_t)row0 + rb + b] : 1.0f;
+        for (uint32_t b = 0; b < RR; ++b) rn[b] = (vq_is_cos(METRIC) && rb + b < nrows) ? rnorm[rows.row((uint64_t)row0 + rb + b)] : 1.0f;
         ivf_tile_store(qi, s_p, rb, nrows, wstride, W, lo, hi,
                        [&](uint32_t a, uint32_t b) { return knn_finish<METRIC>(acc[a][b], qn[a], rn[b]); });
     }
@@ -174,7 +207,7 @@ __global__ __launch_bounds__(256) void k_ivff_scan(const float *__restrict__ Q, 
             rows.walk(row, t0, tc, vec, [&](uint32_t t, float v) { acc = knn_step<METRIC>(acc, s_x[t - t0], v); });
         }
         if (mine) {
-            const float dv = knn_finish<METRIC>(acc, qn, vq_is_cos(METRIC) ? rnorm[row] : 1.0f);
+            const float dv = knn_finish<METRIC>(acc, qn, vq_is_cos(METRIC) ? rnorm[rows.row(row)] : 1.0f);
             const uint32_t key = adc_key(dv);
             if (key != 0xFFFFFFFFu) {
                 lo = min(lo, key);
@@ -196,7 +229,7 @@ __global__ __launch_bounds__(256) void k_ivff_scan(const float *__restrict__ Q, 
 
 // the two distance passes of a batch behind its plan: every D(q, i) of the probed lists into v.W, the key range into p
 template <class ROWS>
-int ivff_distances(const IvffPlan &p, const IvfBatchView &v, int metric, const ROWS &rows, const float *rnorm, const float *queries,
+int ivff_launch(const IvffPlan &p, const IvfBatchView &v, int metric, const ROWS &rows, const float *rnorm, const float *queries,
                    const float *qnorm, hipStream_t stream) {
     const uint64_t items = (v.wstride + v.chunk - 1) / v.chunk;
     return knn_metric_dispatch(metric, [&](auto mtag) -> int {
@@ -215,6 +248,15 @@ int ivff_distances(const IvffPlan &p, const IvfBatchView &v, int metric, const R
         }
         return VQHIP_OK;
     });
+}
+
+// ivff_launch over the rows as they lie (v.pick NULL: the kernels of an unfiltered call, as they are) or over the view
+// of a filtered call (PickedRows: v.off and v.ids are the view's, v.pick its positions in X)
+template <class ROWS>
+int ivff_distances(const IvffPlan &p, const IvfBatchView &v, int metric, const ROWS &rows, const float *rnorm, const float *queries,
+                   const float *qnorm, hipStream_t stream) {
+    if (v.pick) return ivff_launch(p, v, metric, PickedRows<ROWS>{rows.X, rows.d, {rows.sc, v.pick}}, rnorm, queries, qnorm, stream);
+    return ivff_launch(p, v, metric, rows, rnorm, queries, qnorm, stream);
 }
 
 }  // namespace

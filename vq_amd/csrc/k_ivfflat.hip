@@ -24,10 +24,14 @@
 // The two distance kernels and ivff_distances live in ivf_tile.hpp, templated on the row source, and serve the SQ codes
 // of k_ivfsq.hip too; this file instantiates them over dense f32 / f16 rows and holds the stages every inverted-file
 // search over W shares (plan, lists, inverted table, histogram, selection, range).
+// A filtered call first builds the inverted file of its allowed rows (launch_ivf_view: ivf_view.hpp)
+// and runs this schedule over it: v.off / v.ids are the view's, and the two distance kernels are instantiated over
+// PickedRows (ivf_tile.hpp), which reads row v.pick[j] of X for row j of the view.  No other stage knows.
 #include "common.hpp"
 #include "ivf_plan.hpp"
 #include "ivf_range.hpp"
 #include "ivf_tile.hpp"
+#include "ivf_view.hpp"
 #include "kernels.hpp"
 #include "knn_tile.hpp"
 #include "topk.hpp"
@@ -187,7 +191,14 @@ int launch_ivff_range(const IvfBatchView &v, uint32_t q0, const float *radii, vo
     return ivfr_batch(v, q0, radii, range_ws, stage, max_results, out, stream);
 }
 
-// The distance passes of a batch over dense f32 / f16 rows.
+// The view of a filtered call (ivf_view.hpp): count, scan, fill and the lists' offsets, enqueued on stream.
+size_t ivf_view_ws_bytes(uint64_t n) { return ivfv_ws_bytes(n); }
+int launch_ivf_view(const uint32_t *allowed, const uint32_t *ids, uint64_t n, const uint32_t *off, uint32_t nlist, void *ws,
+                    uint32_t *pick, uint32_t *aids, uint32_t *aoff, hipStream_t stream) {
+    return ivfv_build(allowed, ids, n, off, nlist, ws, pick, aids, aoff, stream);
+}
+
+// The distance passes of a batch over dense f32 / f16 rows (v.pick: over the view of a filtered call).
 int launch_ivfflat_distances(const IvffPlan &p, const IvfBatchView &v, int metric, const void *X, int dtype, uint32_t d,
                              const float *rnorm, const float *queries, const float *qnorm, hipStream_t stream) {
     if (v.nb == 0) return VQHIP_OK;

@@ -13,6 +13,8 @@
 // Which kernel computes a pair depends on the batch; both run one pair's operations in one order, so the bits do not.
 // A range search puts the range stage (launch_ivff_range) behind the same plan and distance
 // passes.
+// A filtered call runs the same passes over the view of its allowed rows: v.pick set, the kernels
+// instantiated over PickedRows<SqRows<LW>> (ivf_tile.hpp), whose alignment conditions are SqRows' own.
 #include "common.hpp"
 #include "ivf_tile.hpp"
 #include "kernels.hpp"

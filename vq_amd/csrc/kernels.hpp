@@ -309,7 +309,18 @@ struct IvfBatchView {
     float *W;
     uint32_t *pref, *seg, *inv, *lists;
     void *state;
+    // a filtered call (ivf_view.hpp): ids and off above are the view's (the allowed rows only), and row j of the view is
+    // row pick[j] of the payload in list order; NULL: every row, the payload as it lies.  Read by the distance passes of
+    // the flat and the scalar index alone (launch_ivfbin_distances ignores it)
+    const uint32_t *pick = nullptr;
 };
+// The view of a filtered call on an inverted file: the inverted file of the allowed rows, built once per call on the
+// device (ivf_view.hpp, instantiated in k_ivfflat.hip).  allowed: the call's row mask, ceil(n / 32) words; ids / off: the
+// index in list order; pick / aids [n], aoff [nlist + 1], ws >= ivf_view_ws_bytes(n).  No atomics: the same call gives
+// the same arrays on every run.  Enqueued on stream, no host round trip.
+size_t ivf_view_ws_bytes(uint64_t n);
+int launch_ivf_view(const uint32_t *allowed, const uint32_t *ids, uint64_t n, const uint32_t *off, uint32_t nlist, void *ws,
+                    uint32_t *pick, uint32_t *aids, uint32_t *aoff, hipStream_t stream);
 size_t ivfflat_lists_bytes(uint32_t nlist);
 // The stages of a batch around its distance passes (k_ivfflat.hip), the same for the three indexes: plan = the batch's
 // checks, the zeroed state, k_ivff_plan / _lists / _invert (topk: the selection's, 1 in front of a range stage); select

@@ -10,6 +10,8 @@
 //                                    load is issued only where its row is below nvalid and its first dimension below tc,
 //                                    everything else becomes 0.0f
 //   walk(row, t0, tc, vec, f)        f(t, value) for t = t0 .. t0 + tc - 1 ascending
+//   row(j)                           the row of X behind row j of the source: j itself, but for a picked source
+//   fill_rows(rs, row_of, ...)       fill with tile row r read from row row_of(r) of X: the loader itself, written once
 // ROWS::Walk is the type the one-row-per-lane kernels are instantiated with (a source whose walk is the same code).
 // Every including file gets its own copy of the kernels (an anonymous namespace: no relocatable device code); each .hip
 // instantiates what it launches.
@@ -71,14 +73,23 @@ struct DenseRows {
     uint32_t d;
     Scale sc;
 
-    __device__ __forceinline__ void fill(float (&rs)[kKnnKC][kKnnTR + 4], uint64_t row0, uint32_t nvalid, uint32_t t0,
-                                         uint32_t tc) const {
+    // fill with tile row r read from row row_of(r) of X (asked only for r < nvalid): the one loader behind fill and the
+    // picked form of the source (PickedRows, ivf_tile.hpp)
+    template <class RF>
+    __device__ __forceinline__ void fill_rows(float (&rs)[kKnnKC][kKnnTR + 4], RF &&row_of, uint32_t nvalid, uint32_t t0,
+                                              uint32_t tc) const {
 #pragma unroll
         for (uint32_t e = 0; e < kKnnTR * kKnnKC / 256; ++e) {
             const uint32_t idx = threadIdx.x + 256 * e, r = idx / kKnnKC, c = idx % kKnnKC;
-            rs[c][r] = (r < nvalid && c < tc) ? knn_widen(X[(row0 + r) * d + t0 + c]) : 0.0f;
+            rs[c][r] = (r < nvalid && c < tc) ? knn_widen(X[row_of(r) * d + t0 + c]) : 0.0f;
         }
     }
+    __device__ __forceinline__ void fill(float (&rs)[kKnnKC][kKnnTR + 4], uint64_t row0, uint32_t nvalid, uint32_t t0,
+                                         uint32_t tc) const {
+        fill_rows(rs, [&](uint32_t r) { return row0 + r; }, nvalid, t0, tc);
+    }
+    // the row of X behind row j of the source (what a kernel indexes the rows' norms with)
+    __device__ __forceinline__ uint64_t row(uint64_t j) const { return j; }
     // vec: four elements per load (8 or 16 bytes); d, t0 and tc are multiples of 4 then
     template <class F>
     __device__ __forceinline__ void walk(uint64_t row, uint32_t t0, uint32_t tc, bool vec, F &&f) const {

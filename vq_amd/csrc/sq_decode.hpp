@@ -37,6 +37,13 @@ struct SqRows {
 
     __device__ __forceinline__ void fill(float (&rs)[kKnnKC][kKnnTR + 4], uint64_t row0, uint32_t nvalid, uint32_t t0,
                                          uint32_t tc) const {
+        fill_rows(rs, [&](uint32_t r) { return row0 + r; }, nvalid, t0, tc);
+    }
+    __device__ __forceinline__ uint64_t row(uint64_t j) const { return j; }
+    // tile row r read from row row_of(r) of X (asked only for r < nvalid): the one loader behind fill and PickedRows
+    template <class RF>
+    __device__ __forceinline__ void fill_rows(float (&rs)[kKnnKC][kKnnTR + 4], RF &&row_of, uint32_t nvalid, uint32_t t0,
+                                              uint32_t tc) const {
         constexpr uint32_t TR = kKnnTR, KC = kKnnKC;
         const uint32_t tid = threadIdx.x;
         const float mn = sc.mn, step = sc.step;
@@ -45,7 +52,7 @@ struct SqRows {
                 const uint32_t r = tid >> 1, c0 = (tid & 1u) * 16;
                 const bool ok = r < nvalid && c0 < tc;
                 uint4 w = make_uint4(0, 0, 0, 0);
-                if (ok) w = *reinterpret_cast<const uint4 *>(X + (row0 + r) * d + t0 + c0);
+                if (ok) w = *reinterpret_cast<const uint4 *>(X + row_of(r) * d + t0 + c0);
                 const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
                 for (uint32_t j = 0; j < 16; ++j)
@@ -57,7 +64,7 @@ struct SqRows {
                 const uint32_t idx = tid + 256 * e, r = idx / (KC / 4), c0 = (idx % (KC / 4)) * 4;
                 const bool ok = r < nvalid && c0 < tc;
                 uint32_t w = 0;
-                if (ok) w = *reinterpret_cast<const uint32_t *>(X + (row0 + r) * d + t0 + c0);
+                if (ok) w = *reinterpret_cast<const uint32_t *>(X + row_of(r) * d + t0 + c0);
 #pragma unroll
                 for (uint32_t j = 0; j < 4; ++j) rs[c0 + j][r] = ok ? sq_val((w >> (8 * j)) & 0xffu, mn, step) : 0.0f;
             }
@@ -65,7 +72,7 @@ struct SqRows {
 #pragma unroll
             for (uint32_t e = 0; e < TR * KC / 256; ++e) {
                 const uint32_t idx = tid + 256 * e, r = idx / KC, c1 = idx % KC;
-                rs[c1][r] = (r < nvalid && c1 < tc) ? sq_val(X[(row0 + r) * d + t0 + c1], mn, step) : 0.0f;
+                rs[c1][r] = (r < nvalid && c1 < tc) ? sq_val(X[row_of(r) * d + t0 + c1], mn, step) : 0.0f;
             }
         }
     }

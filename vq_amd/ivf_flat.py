@@ -29,6 +29,7 @@ import numpy as np
 from . import _lib
 from ._ivf_common import (MAX_NLIST, PAD_ID, IVFIndexBase, IVFRangeMixin, _Reader, _check_coarse, _check_distance,  # noqa: F401
                           _check_file_lists, _train_coarse)  # (PAD_ID: re-exported)
+from ._ivf_filter import IVFFilterMixin
 from .distance import Distance
 from .errors import DimensionMismatch, InvalidParameter
 
@@ -48,7 +49,7 @@ def _row_dtype(dtype) -> np.dtype:
     return dt
 
 
-class IVFFlatIndex(IVFRangeMixin, IVFIndexBase):
+class IVFFlatIndex(IVFFilterMixin, IVFRangeMixin, IVFIndexBase):
     """coarse centroids (nlist, dim) + distance + row dtype, and the rows added to it"""
 
     def __init__(self, coarse_centroids, distance: Distance | None = None, dtype=np.float32):
@@ -115,10 +116,11 @@ class IVFFlatIndex(IVFRangeMixin, IVFIndexBase):
         return self._ix
 
     # -- search -----------------------------------------------------------------------------
-    def search(self, queries, topk: int = 10, nprobe: int = 8):
+    def search(self, queries, topk: int = 10, nprobe: int = 8, allowed=None):
         """(nq, dim) float32 queries -> (indices uint32 (nq, topk), distances float32 (nq, topk)), nearest first; slots
-        past the probed rows hold 0xFFFFFFFF / +inf"""
-        return super().search(queries, topk, nprobe)
+        past the probed rows hold 0xFFFFFFFF / +inf.  `allowed`: a row mask (IVFFilterMixin) -- the nearest among the
+        allowed rows of the probed lists only"""
+        return super().search(queries, topk, nprobe, allowed=allowed)
 
     # -- file -------------------------------------------------------------------------------
     def save(self, path) -> None:

@@ -35,6 +35,7 @@ import numpy as np
 from . import _lib
 from ._ivf_common import (MAX_NLIST, IVFIndexBase, IVFRangeMixin, _Reader, _check_coarse, _check_distance, _check_file_lists,
                           _train_coarse)
+from ._ivf_filter import IVFFilterMixin
 from .distance import Distance
 from .errors import DimensionMismatch, InvalidParameter
 from .sq import ScalarQuantizer
@@ -44,7 +45,7 @@ _HEADER = struct.Struct("<8sIIIffIQ")
 _METRIC_NAMES = ["squared_euclidean", "euclidean", "manhattan", "cosine", "cosine_unclamped"]
 
 
-class IVFScalarIndex(IVFRangeMixin, IVFIndexBase):
+class IVFScalarIndex(IVFFilterMixin, IVFRangeMixin, IVFIndexBase):
     """coarse centroids (nlist, dim) + ScalarQuantizer + distance, and the rows added to it as codes"""
 
     def __init__(self, coarse_centroids, quantizer: ScalarQuantizer, distance: Distance | None = None):
