@@ -34,9 +34,19 @@
  * Per-vector calls (vqhip_pq_encode / vqhip_tsvq_encode with n <= 8) stage through buffers owned by
  * the CALL and give the handle back before they launch, so calls from many threads on one
  * quantizer overlap on the device.  A vqhip_dataset is immutable and complete when it is handed
- * out: share it freely.  What stays with the caller: a handle must outlive the calls on it
- * (destroy is not a synchronisation point), and caller-owned device buffers passed to *_device
- * forms are ordered by the caller.  Work is enqueued on the calling thread's current stream
+ * out: share it freely; so is a vqhip_range (every range search, the *_device forms too, waits for
+ * its result).  The search handles (flat, sqindex, binary, ivfpq, ivfflat, ivfsq, ivfbin) serialise
+ * their calls on the handle's lock: each call owns every workspace of the handle, a filtered call's
+ * row mask is in force for that call alone, and a call that needs a larger workspace frees the old
+ * one only after the device has finished with it.  An add to an inverted file may run beside
+ * searches of it from other threads: add and search take turns, so a search sees all rows of every
+ * add that had returned when it started and none or all of one that ran beside it -- n, list_sizes
+ * and the row mask's length (ceil(n / 32) words, read at the time of the call; a longer mask is
+ * fine, its bits at or past n are ignored) follow the same rule.  What stays with the caller: a
+ * handle must outlive the calls on it (destroy is not a synchronisation point), and caller-owned
+ * device buffers passed to *_device forms are ordered by the caller -- a later call of ANOTHER
+ * thread on the handle is ordered behind the queued work, the caller's own reads of the outputs
+ * are not.  Work is enqueued on the calling thread's current stream
  * (vqhip_set_stream; default: a per-thread stream the library creates) of the current HIP device.
  * vqhip_last_error / vqhip_last_assign_stats / vqhip_set_profiling are per calling thread.
  */
@@ -603,8 +613,8 @@ int vqhip_range_destroy(vqhip_range *r);
 /* ---- filtered search: a row mask on the flat and the scalar index (knn_tile.hpp, topk.hpp, range.hpp) -------------
  * No reference counterpart.  A ROW MASK of an index of n rows is ceil(n / 32) u32 words; row i is ALLOWED iff bit i & 31
  * of word i >> 5 is set (a bool array through np.packbits(m, bitorder="little"), zero-padded to whole words and read as
- * little-endian u32).  Bits at or past n in the last word are ignored, whatever they hold.  One mask serves all queries
- * of a call.
+ * little-endian u32).  Bits at or past n are ignored, whatever they hold: those of the last word, and any further words of
+ * a longer mask, which are never read.  One mask serves all queries of a call.
  *   search_masked        per query the first topk words (adc_key(D) << 32) | row, ascending, over the ALLOWED rows only;
  *                        D is exactly the distance vqhip_flat_search / vqhip_sqindex_search report.  NaN distances of
  *                        allowed rows sort last and are reported as 0x7FC00000; ties go to the lower allowed row; a query
