@@ -904,6 +904,43 @@ class BinaryIndex : public detail::ResidentIndex<vqhip_binary, vqhip_binary_dest
         if (radii.size() != queries.size() / dim_) throw VqError::DimensionMismatch(queries.size() / dim_, radii.size());
         return hamming_range_search(queries.data(), queries.size() / dim_, radii.data(), max_results);
     }
+    // The filtered forms (include/vqhip.h, vqhip_binary_search_masked / _range_search_masked): `allowed` is the row mask of
+    // the call, ceil(n / 32) words (pack_row_mask).  search: the nearest among the allowed rows by (H, row id); a query with
+    // fewer than topk of them has idx 0xFFFFFFFF / dist +inf behind them.  hamming_range_search: only allowed rows hit.  The
+    // mask comes last, and max_results has no default beside it, so that a literal 0 never reads as a null mask.
+    using ResidentIndex::search;
+    Result search(const float *queries, std::size_t nq, std::size_t topk, const std::uint32_t *allowed) const {
+        detail::check_row_mask(allowed);
+        if (topk == 0 || topk > 1024 || topk > n_) throw VqError::InvalidParameter("topk", "must be between 1 and min(n, 1024)");
+        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
+        Result r{std::vector<std::uint32_t>(nq * topk), std::vector<float>(nq * topk)};
+        if (nq)
+            detail::check(vqhip_binary_search_masked(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)topk, allowed, r.idx.data(),
+                                                     r.dist.data()));
+        return r;
+    }
+    Result search(const std::vector<float> &queries, std::size_t topk, const std::vector<std::uint32_t> &allowed) const {
+        detail::check_row_mask(allowed, n_);
+        if (queries.size() % dim_) throw VqError::DimensionMismatch(dim_, queries.size() % dim_);
+        return search(queries.data(), queries.size() / dim_, topk, allowed.data());
+    }
+    RangeResult hamming_range_search(const float *queries, std::size_t nq, const std::uint32_t *radii, std::uint64_t max_results,
+                                     const std::uint32_t *allowed) const {
+        detail::check_row_mask(allowed);
+        if (nq >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("queries", "at most 2^32 - 1 per call");
+        if (max_results == 0) throw VqError::InvalidParameter("max_results", "must be at least 1");
+        if (nq == 0) return RangeResult{std::vector<std::uint64_t>(1, 0), {}, {}};
+        vqhip_range *r = nullptr;
+        detail::check(vqhip_binary_range_search_masked(ix_.get(), queries, (std::uint32_t)nq, radii, max_results, allowed, &r));
+        return detail::read_range(r);
+    }
+    RangeResult hamming_range_search(const std::vector<float> &queries, const std::vector<std::uint32_t> &radii,
+                                     std::uint64_t max_results, const std::vector<std::uint32_t> &allowed) const {
+        detail::check_row_mask(allowed, n_);
+        if (queries.size() % dim_) throw VqError::DimensionMismatch(dim_, queries.size() % dim_);
+        if (radii.size() != queries.size() / dim_) throw VqError::DimensionMismatch(queries.size() / dim_, radii.size());
+        return hamming_range_search(queries.data(), queries.size() / dim_, radii.data(), max_results, allowed.data());
+    }
     // the packed rows [n][words_per_row()]
     std::vector<std::uint32_t> packed() const {
         std::vector<std::uint32_t> out(n_ * words_per_row());
@@ -1305,6 +1342,36 @@ class IVFBinaryIndex
         vqhip_range *r = nullptr;
         detail::check(vqhip_ivfbin_range_search(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, radii, max_results, &r));
         return detail::read_range(r);
+    }
+
+    // The filtered forms (include/vqhip.h, vqhip_ivfbin_search_masked / _range_search_masked): the nearest among the allowed
+    // rows of the probed lists, padded with (0xFFFFFFFF, +inf) behind fewer than topk of them; only allowed rows hit a range
+    // query.  `allowed`: ceil(n / 32) words for the n rows the index holds now.  With nprobe == nlist they are BinaryIndex's
+    // filtered forms.  The mask comes last, and max_results has no default beside it.
+    using IvfIndex::search;
+    Result search(const float *queries, std::size_t nq, std::size_t topk, std::size_t nprobe, const std::uint32_t *allowed) const {
+        return masked<vqhip_ivfbin_search_masked>(queries, nq, topk, nprobe, allowed);
+    }
+    Result search(const std::vector<float> &queries, std::size_t topk, std::size_t nprobe, const std::vector<std::uint32_t> &allowed) const {
+        const std::size_t nq = check_masked_vectors(queries, allowed, nullptr);
+        return search(queries.data(), nq, topk, nprobe, allowed.data());
+    }
+    RangeResult hamming_range_search(const float *queries, std::size_t nq, const std::uint32_t *radii, std::size_t nprobe,
+                                     std::uint64_t max_results, const std::uint32_t *allowed) const {
+        detail::check_row_mask(allowed);
+        if (max_results == 0) throw VqError::InvalidParameter("max_results", "must be at least 1");
+        check_probe(nprobe, nq);
+        if (nq == 0) return RangeResult{std::vector<std::uint64_t>(1, 0), {}, {}};
+        vqhip_range *r = nullptr;
+        detail::check(vqhip_ivfbin_range_search_masked(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, radii, max_results,
+                                                       allowed, &r));
+        return detail::read_range(r);
+    }
+    RangeResult hamming_range_search(const std::vector<float> &queries, const std::vector<std::uint32_t> &radii, std::size_t nprobe,
+                                     std::uint64_t max_results, const std::vector<std::uint32_t> &allowed) const {
+        const std::size_t nq = check_masked_vectors(queries, allowed, nullptr);
+        if (radii.size() != nq) throw VqError::DimensionMismatch(nq, radii.size());
+        return hamming_range_search(queries.data(), nq, radii.data(), nprobe, max_results, allowed.data());
     }
 
     // rows appended in order: list_ids [n] < nlist, words [n][words_per_row()], pad bits zero; returns the first new row id

@@ -662,6 +662,35 @@ int vqhip_binary_range_search(vqhip_binary *b, const float *queries, uint32_t nq
 int vqhip_binary_range_search_device(vqhip_binary *b, const void *dev_queries, uint32_t nq, const uint32_t *hradii,
                                      uint64_t max_results, vqhip_range **out);
 
+/* ---- filtered search on the binary index (k_binary.hip) ------------------------------------------------
+ * No reference counterpart.  The ROW MASK is the flat index's (vqhip_flat_search_masked above): ceil(n / 32) u32 words,
+ * row i ALLOWED iff bit i & 31 of word i >> 5 is set, bits at or past n ignored, one mask for all queries of a call.
+ *   search_masked        per query the first topk of the allowed rows by (H, row id) ascending; dist is the value
+ *                        vqhip_binary_search reports for the row, as bits.  topk keeps its bound 1 .. min(n, 1024) whatever
+ *                        the mask; slots past the number of allowed rows hold idx 0xFFFFFFFF and dist +inf.
+ *   range_search_masked  row i is a hit of query q iff it is allowed and H(q, i) <= h_q; the CSR result, its order
+ *                        (ascending row id), max_results, nq = 0 and the statuses are vqhip_binary_range_search's.
+ * A mask of all ones gives the unmasked call's result bit for bit; a mask of all zeros gives padding only (lims = 0 for a
+ * range search).  A call without a mask (the entry points above) launches the kernels it always launched.
+ * allowed: HOST memory in the host forms (copied into a workspace of the handle), a 4-byte aligned DEVICE pointer in the
+ * device forms (else VQHIP_ERR_INVALID_INPUT); NULL is VQHIP_ERR_NULL_PTR.  The other arguments, their checks and the
+ * order of the checks are the unmasked siblings'; the mask's pointer is checked with the other pointers (range: behind
+ * the radii, before the index handle), all before any device work.  The mask is read inside the scans: the 64 rows a
+ * wave takes at a time are two mask words, and a wave without an allowed row among them reads no row and no query word
+ * and counts no bit. */
+int vqhip_binary_search_masked(vqhip_binary *b, const float *queries, uint32_t nq, uint32_t topk, const uint32_t *allowed,
+                               uint32_t *idx_out, float *dist_out);
+int vqhip_binary_search_masked_device(vqhip_binary *b, const void *dev_queries, uint32_t nq, uint32_t topk,
+                                      const uint32_t *dev_allowed, void *dev_idx, void *dev_dist);
+int vqhip_binary_range_search_masked(vqhip_binary *b, const float *queries, uint32_t nq, const uint32_t *hradii,
+                                     uint64_t max_results, const uint32_t *allowed, vqhip_range **out);
+int vqhip_binary_range_search_masked_device(vqhip_binary *b, const void *dev_queries, uint32_t nq, const uint32_t *hradii,
+                                            uint64_t max_results, const uint32_t *dev_allowed, vqhip_range **out);
+/* Rows per scan workgroup of vqhip_binary_search_masked over n rows and `groups` query groups of a batch (host only, no
+ * device): a multiple of 64, so that a wave's 64 rows are two whole mask words, and at most 65472, so that no 16-bit half
+ * of a workgroup's histogram carries.  Workgroup x scans rows [x * slice, min(n, (x + 1) * slice)). */
+uint64_t vqhip_binary_masked_slice(uint64_t n, uint32_t groups);
+
 /* ---- inverted-file PQ index: search only the probed lists (k_ivf.hip) -----------------------
  * No reference counterpart.  An index holds coarse centroids C [nlist][dim] f32 (1 <= nlist <= 65536), PQ codebooks
  * cb [m][k][sub_dim] (dim = m * sub_dim) and a metric: squared Euclidean, Euclidean or Manhattan (cosine is refused with
@@ -848,7 +877,8 @@ int vqhip_ivfsq_range_search_device(vqhip_ivfsq *ix, const void *dev_queries, ui
  * the radii, before the index handle) and before any device is touched.  The other arguments, their checks and the order
  * of the checks are the unmasked siblings'.  A filtered call builds, once, the inverted file of its allowed rows on the
  * device (8 bytes per row of workspace on the handle) and searches that: work behind the probe is proportional to the
- * allowed rows of the probed lists.  vqhip_ivfpq and vqhip_ivfbin have no filtered form. */
+ * allowed rows of the probed lists.  vqhip_ivfbin takes the same view (below); vqhip_ivfpq has no filtered
+ * form. */
 int vqhip_ivfflat_search_masked(vqhip_ivfflat *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
                                 const uint32_t *allowed, uint32_t *idx_out, float *dist_out);
 int vqhip_ivfflat_search_masked_device(vqhip_ivfflat *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
@@ -927,6 +957,25 @@ int vqhip_ivfbin_range_search(vqhip_ivfbin *ix, const float *queries, uint32_t n
                               uint64_t max_results, vqhip_range **out);
 int vqhip_ivfbin_range_search_device(vqhip_ivfbin *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe,
                                      const uint32_t *hradii, uint64_t max_results, vqhip_range **out);
+/* Filtered search: vqhip_ivfflat_search_masked's mask, view and rules over this index's H and D.  n is the
+ * rows in the index at the time of the call; probing is unchanged; S_a(q) = { i in S(q) : i allowed }.
+ *   search_masked        per query the first topk of S_a(q) by (H, row id); dist as vqhip_ivfbin_search reports it;
+ *                        slots past |S_a(q)| hold idx 0xFFFFFFFF and dist +inf; topk keeps 1 .. min(n, 1024).
+ *   range_search_masked  row i is a hit of query q iff i is in S_a(q) and H(q, i) <= h_q; result, order, max_results and
+ *                        statuses are vqhip_ivfbin_range_search's; a mask on an index without rows gives empty ranges.
+ * Identities: all ones equals the unmasked call bit for bit; all zeros gives padding only (lims = 0); with nprobe == nlist
+ * the result equals vqhip_binary_search_masked / vqhip_binary_range_search_masked over the words in add order under the
+ * same mask.  allowed: as vqhip_ivfflat_search_masked takes it (NULL: VQHIP_ERR_NULL_PTR; a device mask that is not
+ * 4-byte aligned: VQHIP_ERR_INVALID_INPUT, both before the handle is looked at). */
+int vqhip_ivfbin_search_masked(vqhip_ivfbin *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                               const uint32_t *allowed, uint32_t *idx_out, float *dist_out);
+int vqhip_ivfbin_search_masked_device(vqhip_ivfbin *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                                      const uint32_t *dev_allowed, void *dev_idx, void *dev_dist);
+int vqhip_ivfbin_range_search_masked(vqhip_ivfbin *ix, const float *queries, uint32_t nq, uint32_t nprobe,
+                                     const uint32_t *hradii, uint64_t max_results, const uint32_t *allowed, vqhip_range **out);
+int vqhip_ivfbin_range_search_masked_device(vqhip_ivfbin *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe,
+                                            const uint32_t *hradii, uint64_t max_results, const uint32_t *dev_allowed,
+                                            vqhip_range **out);
 
 /* ---- TSVQ ----------------------------------------------------------------------------
  * build replaces TSVQNode::build (src/tsvq.rs:31-115); the tree comes back flattened in

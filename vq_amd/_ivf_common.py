@@ -99,6 +99,24 @@ def _check_file_lists(lists: np.ndarray, nlist: int) -> None:
         raise ValueError(f"corrupt index: a list id is outside [0, {nlist})")
 
 
+def rerank_hits(q: np.ndarray, hits: np.ndarray, topk: int, rerank):
+    """the exact rerank of a first stage that may be short: hits (nq, c) row ids with PAD_ID behind every real one (a
+    query whose probed lists, or whose allowed rows, are fewer than c).  A full query is reranked as it is; a short one
+    over its real hits, and keeps the padding behind them."""
+    nq, c = hits.shape
+    idx = np.full((nq, topk), PAD_ID, np.uint32)
+    dist = np.full((nq, topk), np.inf, np.float32)
+    real = (hits != PAD_ID).sum(axis=1)  # (padding follows every real hit)
+    full = real == c
+    if full.any():
+        idx[full], dist[full] = rerank.rerank(q[full], hits[full], topk)
+    for j in np.flatnonzero((real > 0) & ~full):  # a query with fewer hits keeps its padding
+        r = int(real[j])
+        t = min(topk, r)
+        idx[j, :t], dist[j, :t] = (a[0] for a in rerank.rerank(q[j:j + 1], hits[j:j + 1, :r], t))
+    return idx, dist
+
+
 class IVFIndexBase:
     """coarse centroids (nlist, dim) + distance + the list id of every added row; `_ix` is the device handle or None"""
 
@@ -225,24 +243,13 @@ class IVFIndexBase:
         from .flat import rerank_candidates
 
         c = rerank_candidates(len(self), self.dim, topk, rerank, candidates)
-        nq = q.shape[0]
-        idx = np.full((nq, topk), PAD_ID, np.uint32)
-        dist = np.full((nq, topk), np.inf, np.float32)
-        if nq == 0:
-            return idx, dist
+        if q.shape[0] == 0:
+            return np.empty((0, topk), np.uint32), np.empty((0, topk), np.float32)
         if allowed is None:
             hits, _ = self._handle().search(q, nprobe, c)
         else:
             hits, _ = self._handle().search_masked(q, nprobe, c, allowed)
-        real = (hits != PAD_ID).sum(axis=1)  # (padding follows every real hit)
-        full = real == c
-        if full.any():
-            idx[full], dist[full] = rerank.rerank(q[full], hits[full], topk)
-        for j in np.flatnonzero((real > 0) & ~full):  # a query with fewer hits keeps its padding
-            r = int(real[j])
-            t = min(topk, r)
-            idx[j, :t], dist[j, :t] = (a[0] for a in rerank.rerank(q[j:j + 1], hits[j:j + 1, :r], t))
-        return idx, dist
+        return rerank_hits(q, hits, topk, rerank)
 
     def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int, nprobe: int = 8) -> None:
         """device pointers: queries [nq][dim] f32, results [nq][topk] uint32 / f32; asynchronous on the current stream"""

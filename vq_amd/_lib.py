@@ -189,6 +189,15 @@ SIGNATURES = {
     "vqhip_sqindex_range_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, _f32p, C.c_uint64, _vp, _vpp]),
     "vqhip_binary_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint64, _vpp]),
     "vqhip_binary_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, _u32p, C.c_uint64, _vpp]),
+    "vqhip_binary_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p]),
+    "vqhip_binary_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "vqhip_binary_range_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint64, _u32p, _vpp]),
+    "vqhip_binary_range_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, _u32p, C.c_uint64, _vp, _vpp]),
+    "vqhip_binary_masked_slice": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+    "vqhip_ivfbin_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p]),
+    "vqhip_ivfbin_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "vqhip_ivfbin_range_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint64, _u32p, _vpp]),
+    "vqhip_ivfbin_range_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _u32p, C.c_uint64, _vp, _vpp]),
     "vqhip_ivfbin_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint64, _vpp]),
     "vqhip_ivfbin_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _u32p, C.c_uint64, _vpp]),
     "vqhip_range_info": (C.c_int, [_vp, _u32p, _u64p]),
@@ -890,14 +899,9 @@ class _ResidentHandle(Handle):
                                         C.c_void_p(dev_dist)))
 
 
-class _ResidentExactHandle(_ResidentHandle):
-    """the two resident handles of exact distances: they also rerank candidates and answer range queries"""
-
-    def range_search(self, q: np.ndarray, radii: np.ndarray, max_results: int) -> RangeResult:
-        return _range_call(self._fn("range_search"), self.raw, ptr(q, _f32p), q.shape[0], radii, max_results)
-
-    def range_search_device(self, dev_queries: int, nq: int, radii: np.ndarray, max_results: int) -> RangeResult:
-        return _range_call(self._fn("range_search_device"), self.raw, C.c_void_p(dev_queries), nq, radii, max_results)
+class _ResidentMaskedCalls:
+    """the filtered forms of a resident handle's search and range search (radii: float32 distances, or the binary index's
+    uint32 Hamming radii)"""
 
     # the filtered forms: `allowed` uint32 (ceil(n / 32),) row-mask words on the host, `dev_allowed` the same at a device
     # pointer (4-byte aligned)
@@ -921,6 +925,16 @@ class _ResidentExactHandle(_ResidentHandle):
     def range_search_masked_device(self, dev_queries: int, nq: int, radii: np.ndarray, max_results: int, dev_allowed: int) -> RangeResult:
         return _range_call(self._fn("range_search_masked_device"), self.raw, C.c_void_p(dev_queries), nq, radii, max_results,
                            back=(C.c_void_p(dev_allowed),))
+
+
+class _ResidentExactHandle(_ResidentMaskedCalls, _ResidentHandle):
+    """the two resident handles of exact distances: they also rerank candidates and answer range queries"""
+
+    def range_search(self, q: np.ndarray, radii: np.ndarray, max_results: int) -> RangeResult:
+        return _range_call(self._fn("range_search"), self.raw, ptr(q, _f32p), q.shape[0], radii, max_results)
+
+    def range_search_device(self, dev_queries: int, nq: int, radii: np.ndarray, max_results: int) -> RangeResult:
+        return _range_call(self._fn("range_search_device"), self.raw, C.c_void_p(dev_queries), nq, radii, max_results)
 
     def rerank(self, q: np.ndarray, cand: np.ndarray, topk: int):
         nq, c = cand.shape
@@ -956,7 +970,7 @@ BINARY_F32, BINARY_U8, BINARY_PACKED = 0, 1, 2
 BINARY_RANGE_BLOCK = 8192  # VQHIP_BINARY_RANGE_BLOCK: rows a workgroup of the Hamming-radius range search counts and fills
 
 
-class Binary(_ResidentHandle):
+class Binary(_ResidentMaskedCalls, _ResidentHandle):
     """vqhip_binary: BQ bits packed 32 to a word on the device, exact Hamming top-k search (k_binary.hip)"""
 
     _prefix = "vqhip_binary"
@@ -1045,14 +1059,9 @@ class _IVFHandle(Handle):
                                         C.c_void_p(dev_idx), C.c_void_p(dev_dist)))
 
 
-class _IVFExactHandle(_IVFHandle):
-    """the two inverted-file handles of exact distances: they also answer range queries"""
-
-    def range_search(self, q: np.ndarray, nprobe: int, radii: np.ndarray, max_results: int) -> RangeResult:
-        return _range_call(self._fn("range_search"), self.raw, ptr(q, _f32p), q.shape[0], radii, max_results, int(nprobe))
-
-    def range_search_device(self, dev_queries: int, nq: int, nprobe: int, radii: np.ndarray, max_results: int) -> RangeResult:
-        return _range_call(self._fn("range_search_device"), self.raw, C.c_void_p(dev_queries), nq, radii, max_results, int(nprobe))
+class _IVFMaskedCalls:
+    """the filtered forms of an inverted-file handle's search and range search (radii: float32 distances, or the binary
+    index's uint32 Hamming radii)"""
 
     # the filtered forms: `allowed` uint32 (ceil(n / 32),) row-mask words on the host, `dev_allowed` the same at a device
     # pointer (4-byte aligned)
@@ -1076,6 +1085,16 @@ class _IVFExactHandle(_IVFHandle):
                                    dev_allowed: int) -> RangeResult:
         return _range_call(self._fn("range_search_masked_device"), self.raw, C.c_void_p(dev_queries), nq, radii, max_results,
                            int(nprobe), back=(C.c_void_p(dev_allowed),))
+
+
+class _IVFExactHandle(_IVFMaskedCalls, _IVFHandle):
+    """the two inverted-file handles of exact distances: they also answer range queries"""
+
+    def range_search(self, q: np.ndarray, nprobe: int, radii: np.ndarray, max_results: int) -> RangeResult:
+        return _range_call(self._fn("range_search"), self.raw, ptr(q, _f32p), q.shape[0], radii, max_results, int(nprobe))
+
+    def range_search_device(self, dev_queries: int, nq: int, nprobe: int, radii: np.ndarray, max_results: int) -> RangeResult:
+        return _range_call(self._fn("range_search_device"), self.raw, C.c_void_p(dev_queries), nq, radii, max_results, int(nprobe))
 
 
 class IVFPQ(_IVFHandle):
@@ -1179,7 +1198,7 @@ class IVFSQ(_IVFExactHandle):
         return out
 
 
-class IVFBin(_IVFHandle):
+class IVFBin(_IVFMaskedCalls, _IVFHandle):
     """vqhip_ivfbin: inverted-file binary index -- coarse centroids, a BinaryQuantizer's bits packed 32 to a word in lists,
     Hamming top-k over the probed lists (k_ivfbin.hip).  Create, add_packed, add_codes, packed, info and list_sizes are
     host-only; add_rows packs on the device; the device state is built by the first probe or search."""
@@ -1230,6 +1249,11 @@ class IVFBin(_IVFHandle):
 
     def hamming_range_search_device(self, dev_queries: int, nq: int, nprobe: int, hradii: np.ndarray, max_results: int) -> RangeResult:
         return _range_call(self._fn("range_search_device"), self.raw, C.c_void_p(dev_queries), nq, hradii, max_results, int(nprobe))
+
+
+def binary_masked_slice(n: int, groups: int) -> int:
+    """rows per scan workgroup of a filtered BinaryIndex search over n rows and `groups` query groups (host only)"""
+    return int(load().vqhip_binary_masked_slice(int(n), int(groups)))
 
 
 def dequantize_f16(f16) -> np.ndarray:

@@ -7,7 +7,8 @@ and ``D(q, i) = Distance.compute(bq.dequantize(bq.quantize(q)), bq.dequantize(co
 Euclidean, Euclidean and Manhattan -- a function of the Hamming distance alone, read from a table the library builds.
 Cosine is refused.  The result per query is the ``topk`` rows by ``(D, row id)`` ascending, ties to the lower row.
 ``hamming_range_search`` answers the other query, every row within ``radius`` bits, as the CSR triple of
-``FlatIndex.range_search``.
+``FlatIndex.range_search``.  ``filtered_search`` and ``filtered_hamming_range_search`` answer both
+over the rows a mask allows (``BinaryFilterMixin``).
 
 Every argument is checked here before the device is touched; the index goes to the device on the first search (until
 then it refers to the caller's array, which must not change in between).  ``save`` / ``load`` need no device.
@@ -19,6 +20,7 @@ import struct
 import numpy as np
 
 from . import _lib
+from ._binary_filter import BinaryFilterMixin
 from ._resident_common import DEFAULT_MAX_RESULTS, ResidentIndex, _count, _hamming_radii, _max_results, _nq
 from .bq import BinaryQuantizer
 from .distance import Distance
@@ -64,7 +66,7 @@ def _check_params(dim: int, quantizer, distance) -> None:
         raise InvalidParameter("dim", f"must be between 1 and {MAX_DIM}, got {dim}")
 
 
-class BinaryIndex(ResidentIndex):
+class BinaryIndex(BinaryFilterMixin, ResidentIndex):
     """Exact Hamming top-k over rows binarised by `quantizer` (default ``BinaryQuantizer(0.0)``) under `distance`
     (default Manhattan: with the default quantizer, D is the Hamming count)."""
 

@@ -2875,7 +2875,7 @@ static int resident_search_device(T *x, const void *dev_queries, uint32_t nq, ui
     });
 }
 
-// the two filtered search entry points of a flat or a scalar index: resident_search / _device with the row mask `allowed`
+// the two filtered search entry points of a flat, a scalar or a binary index: resident_search / _device with the row mask `allowed`
 // (host: ceil(n / 32) words staged into mask_ws; device: a 4-byte aligned pointer) in force for the launches
 template <class T>
 static int exact_search_masked(T *x, const float *queries, uint32_t nq, uint32_t topk, const uint32_t *allowed, uint32_t *idx_out,
@@ -3384,6 +3384,16 @@ struct vqhip_binary : Resident {
     DevBuf qw, hist, sel, adc_sel, cnt;  // per-call workspaces
     DevBuf hcut, range_ws;               // range search: the clamped radii, the stage's counts and offsets
     std::vector<uint32_t> h_hcut;        // the host side of hcut (the source of an asynchronous copy)
+    DevBuf mask_ws;                      // a filtered host call's row mask on the device
+    const uint32_t *mask = nullptr;      // the row mask of the filtered call that holds the lock (MaskScope), NULL otherwise
+
+    // a host form's mask, ceil(n / 32) words, up into mask_ws
+    int stage_mask(const uint32_t *allowed, hipStream_t s) {
+        const size_t mask_b = (size_t)((n + 31) / 32) * 4;
+        VQ_TRY(mask_ws.ensure(mask_b));
+        VQ_HIP(hipMemcpyAsync(mask_ws.p, allowed, mask_b, hipMemcpyHostToDevice, s));
+        return VQHIP_OK;
+    }
 
     // queries_dev [nq][d] f32 on the device -> [nq][topk] results on the device, enqueued on s in batches of 1024
     int search_enqueue(const float *queries_dev, uint32_t nq, uint32_t topk, uint32_t *idx_dev, float *dist_dev, hipStream_t s) {
@@ -3399,17 +3409,25 @@ struct vqhip_binary : Resident {
             VQ_TRY(launch_bq_pack(queries_dev + (size_t)q0 * d, VQHIP_BINARY_F32, nb, d, thr, high, qw.as<uint32_t>(), s));
             VQ_TRY(launch_binary_search(words.as<uint32_t>(), n, d, metric, table.as<float>(), qw.as<uint32_t>(), nb, topk,
                                         hist.as<uint32_t>(), sel.as<BinSel>(), adc_sel.as<uint32_t>(), cnt.as<uint32_t>(),
-                                        cand.as<unsigned long long>(), idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s));
+                                        cand.as<unsigned long long>(), idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s, mask));
         }
         return VQHIP_OK;
     }
 };
 
 // One Hamming-radius range call on a binary index: the radii, clamped to d and padded by a query group, go up, and
-// launch_binary_range leaves the result complete.
+// launch_binary_range leaves the result complete.  masked: a filtered call under the row mask `allowed`, as range_search
+// takes it (a host form's is staged into mask_ws; the pointer is checked behind range_args and before the handle).
 static int binary_range(vqhip_binary *b, const void *queries, bool host, uint32_t nq, const uint32_t *hradii, uint64_t max_results,
-                        vqhip_range **out) {
+                        vqhip_range **out, bool masked = false, const uint32_t *allowed = nullptr) {
+    if (masked) {
+        VQ_TRY(range_args(queries, hradii, nq, max_results, out));
+        if (!allowed) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+        if (!host) VQ_TRY(check_mask_aligned(allowed));
+    }
     return range_enter(b, queries, host, nq, hradii, max_results, out, no_checks, [&](const float *qdev, RangeOut *r, hipStream_t s) -> int {
+        if (masked && host) VQ_TRY(b->stage_mask(allowed, s));
+        MaskScope scope(b->mask, !masked ? nullptr : host ? b->mask_ws.as<uint32_t>() : allowed);
         b->h_hcut.assign((size_t)nq + 32, 0u);
         for (uint32_t q = 0; q < nq; ++q) b->h_hcut[q] = std::min(hradii[q], b->d);
         VQ_TRY(b->hcut.ensure(b->h_hcut.size() * 4));
@@ -3417,7 +3435,7 @@ static int binary_range(vqhip_binary *b, const void *queries, bool host, uint32_
         VQ_TRY(b->qw.ensure((size_t)binary_range_batch(b->n, b->d, nq) * b->W * 4));
         VQ_TRY(b->range_ws.ensure(binary_range_ws_bytes(b->n, b->d, nq)));
         return launch_binary_range(b->words.as<uint32_t>(), b->n, b->d, b->metric, b->table.as<float>(), qdev, b->thr, b->high, nq,
-                                   b->hcut.as<uint32_t>(), max_results, b->qw.as<uint32_t>(), b->range_ws.p, r, s);
+                                   b->hcut.as<uint32_t>(), max_results, b->qw.as<uint32_t>(), b->range_ws.p, r, s, b->mask);
     });
 }
 
@@ -3570,6 +3588,36 @@ int vqhip_binary_search(vqhip_binary *b, const float *queries, uint32_t nq, uint
 int vqhip_binary_search_device(vqhip_binary *b, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx, void *dev_dist) {
     VQ_API_BEGIN
     return resident_search_device(b, dev_queries, nq, topk, dev_idx, dev_dist);
+    VQ_API_END
+}
+
+uint64_t vqhip_binary_masked_slice(uint64_t n, uint32_t groups) { return n ? binary_masked_slice(n, groups) : 0; }
+
+int vqhip_binary_search_masked(vqhip_binary *b, const float *queries, uint32_t nq, uint32_t topk, const uint32_t *allowed,
+                               uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    return exact_search_masked(b, queries, nq, topk, allowed, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_binary_search_masked_device(vqhip_binary *b, const void *dev_queries, uint32_t nq, uint32_t topk,
+                                      const uint32_t *dev_allowed, void *dev_idx, void *dev_dist) {
+    VQ_API_BEGIN
+    return exact_search_masked_device(b, dev_queries, nq, topk, dev_allowed, dev_idx, dev_dist);
+    VQ_API_END
+}
+
+int vqhip_binary_range_search_masked(vqhip_binary *b, const float *queries, uint32_t nq, const uint32_t *hradii,
+                                     uint64_t max_results, const uint32_t *allowed, vqhip_range **out) {
+    VQ_API_BEGIN
+    return binary_range(b, queries, true, nq, hradii, max_results, out, true, allowed);
+    VQ_API_END
+}
+
+int vqhip_binary_range_search_masked_device(vqhip_binary *b, const void *dev_queries, uint32_t nq, const uint32_t *hradii,
+                                            uint64_t max_results, const uint32_t *dev_allowed, vqhip_range **out) {
+    VQ_API_BEGIN
+    return binary_range(b, dev_queries, false, nq, hradii, max_results, out, true, dev_allowed);
     VQ_API_END
 }
 
@@ -3804,7 +3852,7 @@ static int ivf_search_device(T *ix, const void *dev_queries, uint32_t nq, uint32
     });
 }
 
-// The filtered forms of the two (vqhip_ivfflat and vqhip_ivfsq, IvfExact below): the row mask `allowed` (host: ceil(n /
+// The filtered forms of the two (vqhip_ivfflat, vqhip_ivfsq and vqhip_ivfbin, IvfOverW below): the row mask `allowed` (host: ceil(n /
 // 32) words, staged on the handle; device: a 4-byte aligned pointer) becomes the call's view once, after ready(s) and
 // under the handle's lock (ix->filtered), and the search runs over it.  A NULL mask is reported before a device is touched.
 template <class T>
@@ -3985,10 +4033,33 @@ int vqhip_ivfpq_search_device(vqhip_ivfpq *ix, const void *dev_queries, uint32_t
 //   prepare(queries_dev, nq, nb_max, s)   once per call: the query norms under the cosines, or room for the packed queries
 //   distances(p, v, Q, q0, s)             one batch's distance passes behind its plan p (Q: the batch's queries, f32)
 //   radii_up(radii, nq, s)                the radii of a range call into this->radii as f32 distances
+// A filtered call's view of the allowed rows (filtered(); DESIGN.md sections 23 and 24) is built here, for all three.
 template <class T>
 struct IvfOverW : IvfLists {
     DevBuf inv, lists;              // per-call workspaces: the inverted probe table, the lists' state
     DevBuf radii, range_ws, stage;  // range search: the radii, the stage's counts and offsets, its staging areas
+    DevBuf mask_ws;                 // a filtered host call's row mask on the device
+    DevBuf v_pick, v_aids, v_aoff, v_ws;  // a filtered call's view (8 bytes per row) and the workspace of its scan
+
+    // The view of a filtered call, built once per call: after ready(s), under the handle's lock, enqueued on s.  allowed:
+    // the row mask, ceil(n / 32) words for the n of this call -- a host form's goes up into mask_ws first.
+    int filtered(const uint32_t *allowed, bool host, hipStream_t s, IvfView *view) {
+        const uint64_t n = this->n;
+        if (host) {
+            const size_t mask_b = (size_t)((n + 31) / 32) * 4;
+            VQ_TRY(mask_ws.ensure(mask_b));
+            if (mask_b) VQ_HIP(hipMemcpyAsync(mask_ws.p, allowed, mask_b, hipMemcpyHostToDevice, s));
+            allowed = mask_ws.as<uint32_t>();
+        }
+        VQ_TRY(v_pick.ensure((size_t)n * 4));
+        VQ_TRY(v_aids.ensure((size_t)n * 4));
+        VQ_TRY(v_aoff.ensure(((size_t)this->nlist + 1) * 4));
+        VQ_TRY(v_ws.ensure(ivf_view_ws_bytes(n)));
+        VQ_TRY(launch_ivf_view(allowed, this->d_ids.template as<uint32_t>(), n, this->d_off.template as<uint32_t>(), this->nlist, v_ws.p,
+                               v_pick.as<uint32_t>(), v_aids.as<uint32_t>(), v_aoff.as<uint32_t>(), s));
+        *view = IvfView{v_pick.as<uint32_t>(), v_aids.as<uint32_t>(), v_aoff.as<uint32_t>()};
+        return VQHIP_OK;
+    }
 
     // The batch loop: queries_dev [nq][dim] f32 in ivf_batch's batches -- the probe, the plan, the index's distances, then
     // stage(p, v, q0) behind them.  topk: the selection's; 0: the range stage follows (its workspace is sized here for
@@ -4054,28 +4125,6 @@ template <class T>
 struct IvfExact : IvfOverW<T> {
     DevBuf d_rnorm;
     DevBuf qnorm;  // per-call workspace
-    DevBuf mask_ws;                         // a filtered host call's row mask on the device
-    DevBuf v_pick, v_aids, v_aoff, v_ws;  // a filtered call's view (8 bytes per row) and the workspace of its scan
-
-    // The view of a filtered call, built once per call: after ready(s), under the handle's lock, enqueued on s.  allowed:
-    // the row mask, ceil(n / 32) words for the n of this call -- a host form's goes up into mask_ws first.
-    int filtered(const uint32_t *allowed, bool host, hipStream_t s, IvfView *view) {
-        const uint64_t n = this->n;
-        if (host) {
-            const size_t mask_b = (size_t)((n + 31) / 32) * 4;
-            VQ_TRY(mask_ws.ensure(mask_b));
-            if (mask_b) VQ_HIP(hipMemcpyAsync(mask_ws.p, allowed, mask_b, hipMemcpyHostToDevice, s));
-            allowed = mask_ws.as<uint32_t>();
-        }
-        VQ_TRY(v_pick.ensure((size_t)n * 4));
-        VQ_TRY(v_aids.ensure((size_t)n * 4));
-        VQ_TRY(v_aoff.ensure(((size_t)this->nlist + 1) * 4));
-        VQ_TRY(v_ws.ensure(ivf_view_ws_bytes(n)));
-        VQ_TRY(launch_ivf_view(allowed, this->d_ids.template as<uint32_t>(), n, this->d_off.template as<uint32_t>(), this->nlist, v_ws.p,
-                               v_pick.as<uint32_t>(), v_aids.as<uint32_t>(), v_aoff.as<uint32_t>(), s));
-        *view = IvfView{v_pick.as<uint32_t>(), v_aids.as<uint32_t>(), v_aoff.as<uint32_t>()};
-        return VQHIP_OK;
-    }
 
     int radii_up(const float *r, uint32_t nq, hipStream_t s) {
         VQ_TRY(this->radii.ensure((size_t)nq * 4));
@@ -4178,10 +4227,11 @@ static int ivf_range(T *ix, const void *queries, bool host, uint32_t nq, uint32_
         return ix->range_enqueue(qdev, nq, nprobe, max_results, r, s);
     });
 }
-// ivf_range under the row mask `allowed` of a filtered call on a flat or a scalar index: the mask's pointer is checked
-// behind range_args and, like them, before the handle; the view is built behind ready(s) (ix->filtered).
-template <class T>
-static int ivf_range_masked(T *ix, const void *queries, bool host, uint32_t nq, uint32_t nprobe, const float *radii,
+// ivf_range under the row mask `allowed` of a filtered call (R: f32 radii, or the binary index's u32 Hamming radii): the
+// mask's pointer is checked behind range_args and, like them, before the handle; the view is built behind ready(s)
+// (ix->filtered).
+template <class T, class R>
+static int ivf_range_masked(T *ix, const void *queries, bool host, uint32_t nq, uint32_t nprobe, const R *radii,
                             uint64_t max_results, const uint32_t *allowed, vqhip_range **out) {
     VQ_TRY(range_args(queries, radii, nq, max_results, out));
     if (!allowed) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
@@ -4573,6 +4623,35 @@ int vqhip_ivfbin_search(vqhip_ivfbin *ix, const float *queries, uint32_t nq, uin
                         float *dist_out) {
     VQ_API_BEGIN
     return ivf_search(ix, queries, nq, nprobe, topk, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_ivfbin_search_masked(vqhip_ivfbin *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                               const uint32_t *allowed, uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    return ivf_search_masked(ix, queries, true, nq, nprobe, topk, allowed, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_ivfbin_search_masked_device(vqhip_ivfbin *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                                      const uint32_t *dev_allowed, void *dev_idx, void *dev_dist) {
+    VQ_API_BEGIN
+    return ivf_search_masked(ix, dev_queries, false, nq, nprobe, topk, dev_allowed, dev_idx, dev_dist);
+    VQ_API_END
+}
+
+int vqhip_ivfbin_range_search_masked(vqhip_ivfbin *ix, const float *queries, uint32_t nq, uint32_t nprobe, const uint32_t *hradii,
+                                     uint64_t max_results, const uint32_t *allowed, vqhip_range **out) {
+    VQ_API_BEGIN
+    return ivf_range_masked(ix, queries, true, nq, nprobe, hradii, max_results, allowed, out);
+    VQ_API_END
+}
+
+int vqhip_ivfbin_range_search_masked_device(vqhip_ivfbin *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe,
+                                            const uint32_t *hradii, uint64_t max_results, const uint32_t *dev_allowed,
+                                            vqhip_range **out) {
+    VQ_API_BEGIN
+    return ivf_range_masked(ix, dev_queries, false, nq, nprobe, hradii, max_results, dev_allowed, out);
     VQ_API_END
 }
 

@@ -17,6 +17,9 @@
 //                        by an ordered scan over the rows that stops once it has them
 //   k_adc_sort_out       (topk.hpp) the candidates sorted by (key, row) in LDS, the first topk out,
 //                        sqrtf for Euclidean
+// A filtered call (a row mask) runs the masked twins of the scans, the pick and the ties: the 64 rows a
+// wave takes at one (step, j) are two mask words (bin_mask64), a wave without an allowed row among them skips the step, and
+// the histogram, the cut and the candidates hold allowed rows only.  mask == NULL launches the kernels above as they are.
 // Roofline: VALU, 2 operations (v_xor, v_bcnt with accumulate) per 32 dimensions per (query, row) pair and scan.
 #include "kernels.hpp"
 #include "range.hpp"
@@ -143,15 +146,34 @@ __device__ __forceinline__ void bin_hamming(const uint32_t *__restrict__ P, cons
     }
 }
 
+// The row mask of a filtered call over the 64 rows [g, g + 64) that one wave takes at one (step, j):
+// g is a multiple of 64 and wave-uniform, so the rows are the two mask words g / 32 and g / 32 + 1, read as two u32 (the
+// mask is only 4-byte aligned) through uniform addresses -- the second only where it exists (nwords = ceil(n / 32)).  Bit
+// b of the result: row g + b is allowed and below hi (hi <= n, so the bits at or past n are cleared with them).
+__device__ __forceinline__ uint64_t bin_mask64(const uint32_t *__restrict__ mask, uint32_t nwords, uint64_t g, uint64_t hi) {
+    if (g >= hi) return 0;
+    const uint32_t k = (uint32_t)(g >> 5);
+    uint64_t m = mask[k];
+    if (k + 1 < nwords) m |= (uint64_t)mask[k + 1] << 32;
+    const uint64_t left = hi - g;
+    if (left < 64) m &= (1ull << left) - 1ull;
+    return m;
+}
+
+// the wave of a lane as a uniform value
+__device__ __forceinline__ uint32_t bin_wave() { return (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+
 // Q [nb][W] packed queries of the batch; workgroup (x, y) scans rows [x * slice, (x + 1) * slice) for queries
 // [y * QG, y * QG + QG) of them.  HIST: adds each query's histogram of H to hist [nb][d + 1].  COLLECT: appends the rows
 // that sel admits to cand [nb][kAdcCand] through the counters cnt [nb].
-template <uint32_t QG, bool V4, int MODE>
-__global__ __launch_bounds__(kScanBlock) void k_bin_scan(const uint32_t *__restrict__ P, uint64_t n, uint32_t W, uint32_t d,
-                                                        const uint32_t *__restrict__ Q, uint32_t nb, uint64_t slice,
-                                                        uint32_t *__restrict__ hist, const BinSel *__restrict__ sel,
-                                                        const float *__restrict__ S, unsigned long long *__restrict__ cand,
-                                                        uint32_t *__restrict__ cnt) {
+// MASKED: slice is a multiple of 64, so the 64 rows of a wave at (step, j) are two words of mask; a row counts only where
+// its bit is set, and a wave without an allowed row at either j leaves the step before it loads a row or a query word.
+template <uint32_t QG, bool V4, int MODE, bool MASKED>
+__device__ __forceinline__ void bin_scan_body(const uint32_t *__restrict__ P, uint64_t n, uint32_t W, uint32_t d,
+                                              const uint32_t *__restrict__ Q, uint32_t nb, uint64_t slice,
+                                              uint32_t *__restrict__ hist, const BinSel *__restrict__ sel,
+                                              const float *__restrict__ S, unsigned long long *__restrict__ cand,
+                                              uint32_t *__restrict__ cnt, const uint32_t *__restrict__ mask) {
     extern __shared__ uint32_t lds[];
     uint32_t *qs = lds;                 // [QG][W]
     uint32_t *hs = lds + QG * W;        // HIST: [QG][(d + 2) / 2] bin pairs; COLLECT: [QG][2] (cut, take ties)
@@ -169,13 +191,27 @@ __global__ __launch_bounds__(kScanBlock) void k_bin_scan(const uint32_t *__restr
     }
     __syncthreads();
     const uint64_t lo = (uint64_t)blockIdx.x * slice, hi = min(n, lo + slice);
-    for (uint64_t base = lo + threadIdx.x; base < hi; base += kScanBlock * kScanRR) {
+    // (MASKED: base is the step's first row, uniform; otherwise the lane's)
+    for (uint64_t base = MASKED ? lo : lo + threadIdx.x; base < hi; base += kScanBlock * kScanRR) {
         uint64_t r[kScanRR];
         bool ok[kScanRR];
+        if constexpr (MASKED) {
+            const uint32_t nwords = (uint32_t)((n + 31) >> 5), wv = bin_wave(), lane = threadIdx.x & 63u;
+            uint64_t m[kScanRR];
 #pragma unroll
-        for (uint32_t j = 0; j < kScanRR; ++j) {
-            r[j] = base + (uint64_t)j * kScanBlock;
-            ok[j] = r[j] < hi;
+            for (uint32_t j = 0; j < kScanRR; ++j) m[j] = bin_mask64(mask, nwords, base + (uint64_t)j * kScanBlock + wv * 64u, hi);
+            if (!(m[0] | m[1])) continue;  // (uniform) no allowed row in the wave's 128
+#pragma unroll
+            for (uint32_t j = 0; j < kScanRR; ++j) {
+                r[j] = base + (uint64_t)j * kScanBlock + threadIdx.x;
+                ok[j] = (m[j] >> lane) & 1ull;
+            }
+        } else {
+#pragma unroll
+            for (uint32_t j = 0; j < kScanRR; ++j) {
+                r[j] = base + (uint64_t)j * kScanBlock;
+                ok[j] = r[j] < hi;
+            }
         }
         uint32_t h[kScanRR][QG];
         bin_hamming<QG, V4>(P, r, ok, W, qs, h);
@@ -212,11 +248,36 @@ __global__ __launch_bounds__(kScanBlock) void k_bin_scan(const uint32_t *__restr
     }
 }
 
+template <uint32_t QG, bool V4, int MODE>
+__global__ __launch_bounds__(kScanBlock) void k_bin_scan(const uint32_t *__restrict__ P, uint64_t n, uint32_t W, uint32_t d,
+                                                        const uint32_t *__restrict__ Q, uint32_t nb, uint64_t slice,
+                                                        uint32_t *__restrict__ hist, const BinSel *__restrict__ sel,
+                                                        const float *__restrict__ S, unsigned long long *__restrict__ cand,
+                                                        uint32_t *__restrict__ cnt) {
+    bin_scan_body<QG, V4, MODE, false>(P, n, W, d, Q, nb, slice, hist, sel, S, cand, cnt, nullptr);
+}
+
+// (the second launch bound: the one instantiation whose mask registers would cost it a wave against its unmasked twin,
+// 81 VGPRs against 80, is held to the twin's six waves a SIMD; every other one is left to the compiler)
+template <uint32_t QG, bool V4, int MODE>
+__global__ __launch_bounds__(kScanBlock, (QG == 32 && !V4 && MODE == BIN_HIST) ? 6 : 1) void k_bin_scan_masked(
+                                                               const uint32_t *__restrict__ P, uint64_t n, uint32_t W, uint32_t d,
+                                                               const uint32_t *__restrict__ Q, uint32_t nb, uint64_t slice,
+                                                               uint32_t *__restrict__ hist, const BinSel *__restrict__ sel,
+                                                               const float *__restrict__ S, unsigned long long *__restrict__ cand,
+                                                               uint32_t *__restrict__ cnt, const uint32_t *__restrict__ mask) {
+    bin_scan_body<QG, V4, MODE, true>(P, n, W, d, Q, nb, slice, hist, sel, S, cand, cnt, mask);
+}
+
 // per query: the cut H* = the smallest H with count(H' <= H) >= topk; rows below it, rows at it; adc_sel [2 q + 1] = the
 // candidates k_adc_sort_out will find (heavy: topk)
-__global__ __launch_bounds__(256) void k_bin_pick(const uint32_t *__restrict__ hist, uint32_t d, uint32_t topk,
-                                                  BinSel *__restrict__ sel, uint32_t *__restrict__ adc_sel,
-                                                  uint32_t *__restrict__ cnt) {
+// UNDER (a filtered call: the histogram counts allowed rows only, and there may be fewer than topk of them): a query
+// whose total is below topk takes every allowed row -- cut d with its ties, not heavy, adc_sel [2 q + 1] = the total, which
+// k_adc_sort_out pads to topk.  Without it topk <= n keeps the walk inside the bins.
+template <bool UNDER>
+__device__ __forceinline__ void bin_pick_body(const uint32_t *__restrict__ hist, uint32_t d, uint32_t topk,
+                                              BinSel *__restrict__ sel, uint32_t *__restrict__ adc_sel,
+                                              uint32_t *__restrict__ cnt) {
     __shared__ unsigned long long seg_sum[256];
     __shared__ unsigned long long s_before;
     __shared__ uint32_t s_seg;
@@ -237,6 +298,16 @@ __global__ __launch_bounds__(256) void k_bin_pick(const uint32_t *__restrict__ h
         }
         s_before = cum;
         s_seg = j;
+        if constexpr (UNDER) {
+            if (j == 255 && cum + seg_sum[255] < topk) {  // (total < topk <= 1024)
+                const uint32_t total = (uint32_t)(cum + seg_sum[255]);
+                sel[q] = BinSel{d, total, 0u, 0u};
+                adc_sel[2 * q] = d;
+                adc_sel[2 * q + 1] = total;
+                cnt[q] = 0;
+                s_seg = 256;  // no thread walks a segment
+            }
+        }
     }
     __syncthreads();
     if (t == s_seg) {
@@ -255,10 +326,26 @@ __global__ __launch_bounds__(256) void k_bin_pick(const uint32_t *__restrict__ h
     }
 }
 
+__global__ __launch_bounds__(256) void k_bin_pick(const uint32_t *__restrict__ hist, uint32_t d, uint32_t topk,
+                                                  BinSel *__restrict__ sel, uint32_t *__restrict__ adc_sel,
+                                                  uint32_t *__restrict__ cnt) {
+    bin_pick_body<false>(hist, d, topk, sel, adc_sel, cnt);
+}
+
+__global__ __launch_bounds__(256) void k_bin_pick_masked(const uint32_t *__restrict__ hist, uint32_t d, uint32_t topk,
+                                                         BinSel *__restrict__ sel, uint32_t *__restrict__ adc_sel,
+                                                         uint32_t *__restrict__ cnt) {
+    bin_pick_body<true>(hist, d, topk, sel, adc_sel, cnt);
+}
+
 // heavy cut: the lowest sel.need row ids with H == H*, by an ordered scan in chunks of 1024 rows, to cand [q][less ..)
-__global__ __launch_bounds__(kTiesBlock) void k_bin_ties(const uint32_t *__restrict__ P, uint64_t n, uint32_t W,
-                                                         const uint32_t *__restrict__ Q, const BinSel *__restrict__ sel,
-                                                         const float *__restrict__ S, unsigned long long *__restrict__ cand) {
+// MASKED: the lowest allowed ones -- H is computed for allowed rows only (a chunk starts on a multiple of 1024, a wave's
+// rows are two words of mask)
+template <bool MASKED>
+__device__ __forceinline__ void bin_ties_body(const uint32_t *__restrict__ P, uint64_t n, uint32_t W,
+                                              const uint32_t *__restrict__ Q, const BinSel *__restrict__ sel,
+                                              const float *__restrict__ S, unsigned long long *__restrict__ cand,
+                                              const uint32_t *__restrict__ mask) {
     const uint32_t q = blockIdx.x;
     const BinSel s = sel[q];
     if (!s.heavy) return;
@@ -272,8 +359,10 @@ __global__ __launch_bounds__(kTiesBlock) void k_bin_ties(const uint32_t *__restr
     uint32_t taken = 0;  // uniform
     for (uint64_t base = 0; base < n && taken < s.need; base += kTiesBlock) {
         const uint64_t i = base + tid;
-        bool eq = false;
-        if (i < n) {
+        bool eq = false, in = i < n;
+        if constexpr (MASKED)
+            in = (bin_mask64(mask, (uint32_t)((n + 31) >> 5), base + (uint64_t)bin_wave() * 64u, n) >> lane) & 1ull;
+        if (in) {
             uint32_t h = 0;
             for (uint32_t c = 0; c < W; ++c) h = __builtin_popcount(P[i * W + c] ^ qw[c]) + h;
             eq = h == s.hstar;
@@ -292,6 +381,19 @@ __global__ __launch_bounds__(kTiesBlock) void k_bin_ties(const uint32_t *__restr
     }
 }
 
+__global__ __launch_bounds__(kTiesBlock) void k_bin_ties(const uint32_t *__restrict__ P, uint64_t n, uint32_t W,
+                                                         const uint32_t *__restrict__ Q, const BinSel *__restrict__ sel,
+                                                         const float *__restrict__ S, unsigned long long *__restrict__ cand) {
+    bin_ties_body<false>(P, n, W, Q, sel, S, cand, nullptr);
+}
+
+__global__ __launch_bounds__(kTiesBlock) void k_bin_ties_masked(const uint32_t *__restrict__ P, uint64_t n, uint32_t W,
+                                                                const uint32_t *__restrict__ Q, const BinSel *__restrict__ sel,
+                                                                const float *__restrict__ S, unsigned long long *__restrict__ cand,
+                                                                const uint32_t *__restrict__ mask) {
+    bin_ties_body<true>(P, n, W, Q, sel, S, cand, mask);
+}
+
 // QG queries per scan workgroup: their H histograms in 16-bit halves must fit in LDS with room for two workgroups a CU
 // where d allows it
 uint32_t bin_qg(uint32_t d) { return d <= 1024 ? 32u : 8u; }
@@ -303,7 +405,19 @@ size_t bin_scan_lds(uint32_t qg, uint32_t W, uint32_t d, int mode) {
 template <uint32_t QG, bool V4, int MODE>
 int bin_scan_launch(dim3 grid, size_t lds, const uint32_t *P, uint64_t n, uint32_t W, uint32_t d, const uint32_t *Q, uint32_t nb,
                     uint64_t slice, uint32_t *hist, const BinSel *sel, const float *S, unsigned long long *cand, uint32_t *cnt,
-                    hipStream_t stream) {
+                    const uint32_t *mask, hipStream_t stream) {
+    if (mask) {
+        static PerDeviceOnce attr_m;
+        if (attr_m.needed()) {
+            VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bin_scan_masked<QG, V4, MODE>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            attr_m.done();
+        }
+        hipLaunchKernelGGL((k_bin_scan_masked<QG, V4, MODE>), grid, dim3(kScanBlock), lds, stream, P, n, W, d, Q, nb, slice, hist,
+                           sel, S, cand, cnt, mask);
+        VQ_LAUNCH_CHECK("k_bin_scan_masked");
+        return VQHIP_OK;
+    }
     static PerDeviceOnce attr;
     if (attr.needed()) {
         VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bin_scan<QG, V4, MODE>),
@@ -318,21 +432,23 @@ int bin_scan_launch(dim3 grid, size_t lds, const uint32_t *P, uint64_t n, uint32
 
 template <int MODE>
 int bin_scan(const uint32_t *P, uint64_t n, uint32_t W, uint32_t d, const uint32_t *Q, uint32_t nb, uint32_t *hist,
-             const BinSel *sel, const float *S, unsigned long long *cand, uint32_t *cnt, hipStream_t stream) {
+             const BinSel *sel, const float *S, unsigned long long *cand, uint32_t *cnt, const uint32_t *mask,
+             hipStream_t stream) {
     const uint32_t qg = bin_qg(d), groups = (nb + qg - 1) / qg;
     // slices: at most 65535 rows each, and about 2048 workgroups in all where n allows 512 rows a workgroup
     uint64_t slices = std::max<uint64_t>((n + kSliceMax - 1) / kSliceMax,
                                          std::min<uint64_t>((2048 + groups - 1) / groups, (n + 511) / 512));
-    const uint64_t slice = (n + slices - 1) / slices;
+    uint64_t slice = (n + slices - 1) / slices;
+    if (mask) slice = binary_masked_slice(n, groups);
     slices = (n + slice - 1) / slice;
     const dim3 grid((uint32_t)slices, groups);
     const size_t lds = bin_scan_lds(qg, W, d, MODE);
     const bool v4 = W % 4 == 0;
     if (qg == 32)
-        return v4 ? bin_scan_launch<32, true, MODE>(grid, lds, P, n, W, d, Q, nb, slice, hist, sel, S, cand, cnt, stream)
-                  : bin_scan_launch<32, false, MODE>(grid, lds, P, n, W, d, Q, nb, slice, hist, sel, S, cand, cnt, stream);
-    return v4 ? bin_scan_launch<8, true, MODE>(grid, lds, P, n, W, d, Q, nb, slice, hist, sel, S, cand, cnt, stream)
-              : bin_scan_launch<8, false, MODE>(grid, lds, P, n, W, d, Q, nb, slice, hist, sel, S, cand, cnt, stream);
+        return v4 ? bin_scan_launch<32, true, MODE>(grid, lds, P, n, W, d, Q, nb, slice, hist, sel, S, cand, cnt, mask, stream)
+                  : bin_scan_launch<32, false, MODE>(grid, lds, P, n, W, d, Q, nb, slice, hist, sel, S, cand, cnt, mask, stream);
+    return v4 ? bin_scan_launch<8, true, MODE>(grid, lds, P, n, W, d, Q, nb, slice, hist, sel, S, cand, cnt, mask, stream)
+              : bin_scan_launch<8, false, MODE>(grid, lds, P, n, W, d, Q, nb, slice, hist, sel, S, cand, cnt, mask, stream);
 }
 
 template <typename T, bool VEC>
@@ -347,6 +463,16 @@ int pack_launch(const T *x, uint64_t n, uint32_t d, float thr, uint32_t high, ui
 }  // namespace
 
 uint32_t bin_words(uint32_t d) { return (d + 31) / 32; }
+
+// Rows per scan workgroup of a filtered call: bin_scan's slicing with every slice a multiple of 64, so that a wave's 64
+// rows are two whole mask words, and at most 65472 = 65535 rounded down to one (rounding 65535 up would let a 16-bit
+// histogram half carry).  groups: the query groups of the batch.
+uint64_t binary_masked_slice(uint64_t n, uint32_t groups) {
+    constexpr uint64_t kMax = kSliceMax / 64 * 64;
+    groups = std::max(groups, 1u);
+    const uint64_t slices = std::max<uint64_t>((n + kMax - 1) / kMax, std::min<uint64_t>((2048 + groups - 1) / groups, (n + 511) / 512));
+    return ((n + slices - 1) / slices + 63) / 64 * 64;
+}
 
 int binary_table(uint32_t d, uint32_t low, uint32_t high, int metric, float *S) {
     const float a = (float)high - (float)low;
@@ -385,17 +511,19 @@ size_t binary_hist_bytes(uint32_t qb, uint32_t d) { return (size_t)qb * (d + 1) 
 
 int launch_binary_search(const uint32_t *P, uint64_t n, uint32_t d, int metric, const float *S, const uint32_t *Q, uint32_t nb,
                          uint32_t topk, uint32_t *hist, BinSel *sel, uint32_t *adc_sel, uint32_t *cnt,
-                         unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream) {
+                         unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream, const uint32_t *mask) {
     if (topk == 0 || topk > 1024 || topk > n) return fail(VQHIP_ERR_INVALID_INPUT, "topk must be in [1, min(n, 1024)]");
     if (nb == 0) return VQHIP_OK;
     VQ_TRY(topk_sort_attr());
     const uint32_t W = bin_words(d);
     VQ_HIP(hipMemsetAsync(hist, 0, binary_hist_bytes(nb, d), stream));
-    VQ_TRY(bin_scan<BIN_HIST>(P, n, W, d, Q, nb, hist, sel, S, cand, cnt, stream));
-    hipLaunchKernelGGL(k_bin_pick, dim3(nb), dim3(256), 0, stream, hist, d, topk, sel, adc_sel, cnt);
+    VQ_TRY(bin_scan<BIN_HIST>(P, n, W, d, Q, nb, hist, sel, S, cand, cnt, mask, stream));
+    if (mask) hipLaunchKernelGGL(k_bin_pick_masked, dim3(nb), dim3(256), 0, stream, hist, d, topk, sel, adc_sel, cnt);
+    else hipLaunchKernelGGL(k_bin_pick, dim3(nb), dim3(256), 0, stream, hist, d, topk, sel, adc_sel, cnt);
     VQ_LAUNCH_CHECK("k_bin_pick");
-    VQ_TRY(bin_scan<BIN_COLLECT>(P, n, W, d, Q, nb, hist, sel, S, cand, cnt, stream));
-    hipLaunchKernelGGL(k_bin_ties, dim3(nb), dim3(kTiesBlock), (size_t)W * 4, stream, P, n, W, Q, sel, S, cand);
+    VQ_TRY(bin_scan<BIN_COLLECT>(P, n, W, d, Q, nb, hist, sel, S, cand, cnt, mask, stream));
+    if (mask) hipLaunchKernelGGL(k_bin_ties_masked, dim3(nb), dim3(kTiesBlock), (size_t)W * 4, stream, P, n, W, Q, sel, S, cand, mask);
+    else hipLaunchKernelGGL(k_bin_ties, dim3(nb), dim3(kTiesBlock), (size_t)W * 4, stream, P, n, W, Q, sel, S, cand);
     VQ_LAUNCH_CHECK("k_bin_ties");
     hipLaunchKernelGGL(k_adc_sort_out, dim3(nb), dim3(1024), (size_t)kAdcCand * 8, stream, cand, adc_sel, topk,
                        metric == VQHIP_EUCLIDEAN ? 1 : 0, idx_out, dist_out);
@@ -432,13 +560,23 @@ constexpr uint32_t kBinRangeStep = kScanBlock * kScanRR;          // rows per st
 static_assert(kBinRangeRows % kBinRangeStep == 0 && kBinRangeRows / kBinRangeStep * kScanRR < 256, "a block is whole steps, a lane's hits a byte");
 constexpr uint64_t kBinRangeEntries = 1ull << 17;                 // count entries of a batch of several queries, at most
 
-template <uint32_t QG, bool V4, int MODE>
+// MASKED (a filtered call): a block starts on a multiple of 8192, so a wave's 64 rows at (step, j)
+// are two words of mask (bin_mask64); a row is a hit only where its bit is set.  A wave without an allowed row at either j
+// skips the step's Hamming work: COUNT goes on to the next step, FILL still meets the step's barrier with zero totals.
+// The mask is the kernel's optional last argument (MASK: no type, or const uint32_t *), so the unmasked instantiation is
+// the kernel of an unfiltered call with its arguments, and nothing of the masked form is in it.
+template <uint32_t QG, bool V4, int MODE, class... MASK>
 __global__ __launch_bounds__(kScanBlock, 3) void k_bin_range(const uint32_t *__restrict__ P, uint64_t n, uint32_t W,
                                                          const uint32_t *__restrict__ Q, uint32_t nb,
                                                          const uint32_t *__restrict__ hcut, uint32_t nblk,
                                                          uint32_t *__restrict__ cnt, const unsigned long long *__restrict__ off,
                                                          unsigned long long base, const float *__restrict__ S, int root,
-                                                         uint32_t *__restrict__ idx_out, float *__restrict__ dist_out) {
+                                                         uint32_t *__restrict__ idx_out, float *__restrict__ dist_out,
+                                                         MASK... mask_arg) {
+    constexpr bool MASKED = sizeof...(MASK) == 1;
+    static_assert(sizeof...(MASK) <= 1, "one row mask at most");
+    [[maybe_unused]] const uint32_t *mask = nullptr;
+    if constexpr (MASKED) mask = (mask_arg, ...);
     extern __shared__ __attribute__((aligned(16))) uint32_t range_lds[];  // qs [QG][W]
     __shared__ __attribute__((aligned(16))) uint32_t wt[2][QG][4];  // FILL: a step's wave totals; COUNT: wt[0][q][wave]
     __shared__ uint32_t s_c[QG];                                     // FILL: the block's count per query
@@ -483,6 +621,15 @@ __global__ __launch_bounds__(kScanBlock, 3) void k_bin_range(const uint32_t *__r
                 r[j] = b0 + tid + (uint64_t)j * kScanBlock;
                 ok[j] = r[j] < hi;
             }
+            if constexpr (MASKED) {
+                const uint32_t nwords = (uint32_t)((n + 31) >> 5), wvu = bin_wave();
+                uint64_t m[kScanRR];
+#pragma unroll
+                for (uint32_t j = 0; j < kScanRR; ++j) m[j] = bin_mask64(mask, nwords, b0 + (uint64_t)j * kScanBlock + wvu * 64u, hi);
+                if (!(m[0] | m[1])) continue;  // (uniform; no barrier in this loop)
+#pragma unroll
+                for (uint32_t j = 0; j < kScanRR; ++j) ok[j] = (m[j] >> lane) & 1ull;
+            }
             uint32_t h[kScanRR][QG];
             bin_hamming<QG, V4>(P, r, ok, W, qs, h);
 #pragma unroll
@@ -514,17 +661,35 @@ __global__ __launch_bounds__(kScanBlock, 3) void k_bin_range(const uint32_t *__r
                 r[j] = b0 + tid + (uint64_t)j * kScanBlock;
                 ok[j] = r[j] < hi;
             }
-            uint32_t h[kScanRR][QG];
-            bin_hamming<QG, V4>(P, r, ok, W, qs, h);
-            uint32_t mine = 0, any = 0;  // mine: lane q holds the wave's totals of query q; any: the wave has a hit (uniform)
+            [[maybe_unused]] uint64_t m[kScanRR] = {~0ull, ~0ull};  // the wave's allowed rows at (step, j)
+            if constexpr (MASKED) {
+                const uint32_t nwords = (uint32_t)((n + 31) >> 5), wvu = bin_wave();
 #pragma unroll
-            for (uint32_t q = 0; q < QG; ++q) {
-                if (!((act >> q) & 1u)) continue;
-                const unsigned long long m0 = __ballot(ok[0] && h[0][q] <= cut[q]);
-                const unsigned long long m1 = __ballot(ok[1] && h[1][q] <= cut[q]);
-                const uint32_t pk = (uint32_t)__popcll(m0) | ((uint32_t)__popcll(m1) << 16);
-                mine = lane == q ? pk : mine;
-                any |= pk;
+                for (uint32_t j = 0; j < kScanRR; ++j) {
+                    m[j] = bin_mask64(mask, nwords, b0 + (uint64_t)j * kScanBlock + wvu * 64u, hi);
+                    ok[j] = (m[j] >> lane) & 1ull;
+                }
+            }
+            uint32_t h[kScanRR][QG];
+            if (!MASKED || (m[0] | m[1])) {  // (uniform)
+                bin_hamming<QG, V4>(P, r, ok, W, qs, h);
+            } else {  // no allowed row: ok is false in every lane, zero totals for the barrier below, and no h is ever a hit
+#pragma unroll
+                for (uint32_t j = 0; j < kScanRR; ++j)
+#pragma unroll
+                    for (uint32_t q = 0; q < QG; ++q) h[j][q] = 0;
+            }
+            uint32_t mine = 0, any = 0;  // mine: lane q holds the wave's totals of query q; any: the wave has a hit (uniform)
+            if (!MASKED || (m[0] | m[1])) {
+#pragma unroll
+                for (uint32_t q = 0; q < QG; ++q) {
+                    if (!((act >> q) & 1u)) continue;
+                    const unsigned long long m0 = __ballot(ok[0] && h[0][q] <= cut[q]);
+                    const unsigned long long m1 = __ballot(ok[1] && h[1][q] <= cut[q]);
+                    const uint32_t pk = (uint32_t)__popcll(m0) | ((uint32_t)__popcll(m1) << 16);
+                    mine = lane == q ? pk : mine;
+                    any |= pk;
+                }
             }
             if (lane < QG) wt[buf][lane][wv] = mine;
             if (!__syncthreads_or(any != 0)) continue;  // (uniform) no hit in the step
@@ -560,7 +725,17 @@ __global__ __launch_bounds__(kScanBlock, 3) void k_bin_range(const uint32_t *__r
 template <uint32_t QG, bool V4>
 int bin_range_launch(int mode, dim3 grid, size_t lds, const uint32_t *P, uint64_t n, uint32_t W, const uint32_t *Q, uint32_t nb,
                      const uint32_t *hcut, uint32_t nblk, uint32_t *cnt, const unsigned long long *off, unsigned long long base,
-                     const float *S, int root, uint32_t *idx_out, float *dist_out, hipStream_t stream) {
+                     const float *S, int root, uint32_t *idx_out, float *dist_out, const uint32_t *mask, hipStream_t stream) {
+    if (mask) {
+        if (mode == BIN_COUNT)
+            hipLaunchKernelGGL((k_bin_range<QG, V4, BIN_COUNT, const uint32_t *>), grid, dim3(kScanBlock), lds, stream, P, n, W, Q, nb, hcut, nblk,
+                               cnt, off, base, S, root, idx_out, dist_out, mask);
+        else
+            hipLaunchKernelGGL((k_bin_range<QG, V4, BIN_FILL, const uint32_t *>), grid, dim3(kScanBlock), lds, stream, P, n, W, Q, nb, hcut, nblk,
+                               cnt, off, base, S, root, idx_out, dist_out, mask);
+        VQ_LAUNCH_CHECK("k_bin_range (masked)");
+        return VQHIP_OK;
+    }
     if (mode == BIN_COUNT)
         hipLaunchKernelGGL((k_bin_range<QG, V4, BIN_COUNT>), grid, dim3(kScanBlock), lds, stream, P, n, W, Q, nb, hcut, nblk, cnt, off,
                            base, S, root, idx_out, dist_out);
@@ -573,16 +748,16 @@ int bin_range_launch(int mode, dim3 grid, size_t lds, const uint32_t *P, uint64_
 
 int bin_range_scan(int mode, const uint32_t *P, uint64_t n, uint32_t W, uint32_t d, const uint32_t *Q, uint32_t nb,
                    const uint32_t *hcut, uint32_t nblk, uint32_t *cnt, const unsigned long long *off, unsigned long long base,
-                   const float *S, int root, uint32_t *idx_out, float *dist_out, hipStream_t stream) {
+                   const float *S, int root, uint32_t *idx_out, float *dist_out, const uint32_t *mask, hipStream_t stream) {
     const uint32_t qg = bin_qg(d);
     const dim3 grid(nblk, (nb + qg - 1) / qg);
     const size_t lds = (size_t)qg * W * 4;  // at most 8 KB (QG = 8, W = 256): k_bin_scan's words without its histogram
     const bool v4 = W % 4 == 0;
     if (qg == 32)
-        return v4 ? bin_range_launch<32, true>(mode, grid, lds, P, n, W, Q, nb, hcut, nblk, cnt, off, base, S, root, idx_out, dist_out, stream)
-                  : bin_range_launch<32, false>(mode, grid, lds, P, n, W, Q, nb, hcut, nblk, cnt, off, base, S, root, idx_out, dist_out, stream);
-    return v4 ? bin_range_launch<8, true>(mode, grid, lds, P, n, W, Q, nb, hcut, nblk, cnt, off, base, S, root, idx_out, dist_out, stream)
-              : bin_range_launch<8, false>(mode, grid, lds, P, n, W, Q, nb, hcut, nblk, cnt, off, base, S, root, idx_out, dist_out, stream);
+        return v4 ? bin_range_launch<32, true>(mode, grid, lds, P, n, W, Q, nb, hcut, nblk, cnt, off, base, S, root, idx_out, dist_out, mask, stream)
+                  : bin_range_launch<32, false>(mode, grid, lds, P, n, W, Q, nb, hcut, nblk, cnt, off, base, S, root, idx_out, dist_out, mask, stream);
+    return v4 ? bin_range_launch<8, true>(mode, grid, lds, P, n, W, Q, nb, hcut, nblk, cnt, off, base, S, root, idx_out, dist_out, mask, stream)
+              : bin_range_launch<8, false>(mode, grid, lds, P, n, W, Q, nb, hcut, nblk, cnt, off, base, S, root, idx_out, dist_out, mask, stream);
 }
 
 uint32_t bin_range_blocks(uint64_t n) { return (uint32_t)((n + kBinRangeRows - 1) / kBinRangeRows); }
@@ -610,7 +785,7 @@ size_t binary_range_ws_bytes(uint64_t n, uint32_t d, uint32_t nq) {
 
 int launch_binary_range(const uint32_t *P, uint64_t n, uint32_t d, int metric, const float *S, const float *queries_dev, float thr,
                         uint32_t high, uint32_t nq, const uint32_t *hcut, uint64_t max_results, uint32_t *qw, void *range_ws,
-                        RangeOut *out, hipStream_t stream) {
+                        RangeOut *out, hipStream_t stream, const uint32_t *mask) {
     VQ_TRY(range_begin(out, nq, max_results, stream));
     const uint32_t W = bin_words(d), nblk = bin_range_blocks(n), qb = binary_range_batch(n, d, nq);
     const int root = metric == VQHIP_EUCLIDEAN ? 1 : 0;
@@ -618,12 +793,12 @@ int launch_binary_range(const uint32_t *P, uint64_t n, uint32_t d, int metric, c
     for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
         const uint32_t nb = std::min(qb, nq - q0);
         VQ_TRY(launch_bq_pack(queries_dev + (size_t)q0 * d, VQHIP_BINARY_F32, nb, d, thr, high, qw, stream));
-        VQ_TRY(bin_range_scan(BIN_COUNT, P, n, W, d, qw, nb, hcut + q0, nblk, w.cnt, w.off, 0, S, root, nullptr, nullptr, stream));
+        VQ_TRY(bin_range_scan(BIN_COUNT, P, n, W, d, qw, nb, hcut + q0, nblk, w.cnt, w.off, 0, S, root, nullptr, nullptr, mask, stream));
         uint64_t got = 0;
         VQ_TRY(range_scan_room(w, nb, nblk, q0, max_results, out, &got, stream));
         if (got == 0) continue;
         VQ_TRY(bin_range_scan(BIN_FILL, P, n, W, d, qw, nb, hcut + q0, nblk, w.cnt, w.off, (unsigned long long)out->total, S, root,
-                              out->idx.as<uint32_t>(), out->dist.as<float>(), stream));
+                              out->idx.as<uint32_t>(), out->dist.as<float>(), mask, stream));
         out->total += got;
     }
     VQ_HIP(hipStreamSynchronize(stream));  // *out is complete on return

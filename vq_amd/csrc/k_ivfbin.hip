@@ -20,6 +20,11 @@
 // two distance passes, with radii [nb] f32 the reported distance of each query's Hamming radius, so that D <= radius iff
 // H <= that radius.
 // LW = words per load of the row loader (4, 2 or 1: 16, 8 or 4 bytes), chosen per launch from W and the base pointer.
+// A filtered call (DESIGN.md sections 23 and 24) runs the same passes over the view of its allowed rows: v.off and v.ids are
+// the view's, and row j of the view is row v.pick[j] of P.  The two kernels take pick as an optional last argument (PICK:
+// no type, or const uint32_t *), so the unpicked instantiations are the kernels of an unfiltered call with their
+// arguments.  Row offsets stay 64-bit, (uint64_t)pick[j] * W, and the loaders' alignment rests on W and the base of P, so
+// it holds for any picked row.  No other stage knows.
 #include "common.hpp"
 #include "ivf_tile.hpp"
 #include "kernels.hpp"
@@ -53,23 +58,31 @@ __device__ __forceinline__ void bin_table_load(float *s_tab, const float *__rest
 // at word (off[l] + r) * W + t0 with t0 a multiple of 32, so W % LW == 0 and an LW-word-aligned base align every load; a
 // load is issued only where its row is inside the list and its first word below tc (a multiple of LW).  Padded rows,
 // queries and words are 0 in the tile and never reach a result.
-template <int LW>
+// Picked: row0 is a position of the view, so the rows of a tile are P[pick[row0 + r0 + r]]; the tile's 64 pick words go
+// into LDS once per row tile (s_pick), not once per chunk and load.  They are written before the first chunk's opening
+// barrier; their last readers, the previous tile's loads, lie before that tile's closing barrier.
+template <int LW, class... PICK>
 __global__ __launch_bounds__(256) void k_ivfbin_tile(const uint32_t *__restrict__ Q, const uint32_t *__restrict__ P, uint32_t Wn,
                                                      uint32_t d, const float *__restrict__ S, int root,
                                                      const uint32_t *__restrict__ off, uint32_t nlist, const uint32_t *__restrict__ cnt,
                                                      const uint32_t *__restrict__ lstart, const uint32_t *__restrict__ tstart,
                                                      const uint32_t *__restrict__ inv, const uint32_t *__restrict__ pref,
                                                      uint32_t nprobe, uint64_t wstride, float *__restrict__ W,
-                                                     uint32_t *__restrict__ kmin, uint32_t *__restrict__ kmax) {
+                                                     uint32_t *__restrict__ kmin, uint32_t *__restrict__ kmax, PICK... pick_arg) {
     constexpr uint32_t RQ = kKnnRQ, RR = kKnnRR, TQ = kKnnTQ, TR = kKnnTR, WC = kBinWC;
+    constexpr bool PICKED = sizeof...(PICK) == 1;
+    static_assert(sizeof...(PICK) <= 1, "one pick array at most");
     extern __shared__ float s_tab[];  // [d + 1]
     __shared__ __attribute__((aligned(16))) uint32_t qs[WC][TQ + 4];
     __shared__ __attribute__((aligned(16))) uint32_t rs[WC][TR + 4];
     __shared__ uint32_t s_q[TQ], s_p[TQ];
+    __shared__ uint32_t s_pick[PICKED ? TR : 1];  // picked: the row tile's rows in P
+    [[maybe_unused]] const uint32_t *pick = nullptr;
+    if constexpr (PICKED) pick = (pick_arg, ...);
     uint32_t row0, nrows;
     if (!ivf_tile_open(off, nlist, cnt, lstart, tstart, inv, pref, nprobe, s_q, s_p, &row0, &nrows)) return;
     const uint32_t tid = threadIdx.x, rg = tid & 15u, qg = tid >> 4;
-    const uint32_t *Pl = P + (uint64_t)row0 * Wn;  // the list's run
+    [[maybe_unused]] const uint32_t *Pl = P + (uint64_t)row0 * Wn;  // the list's run (unpicked: row0 is a row of P)
     bin_table_load(s_tab, S, d, root);
     __syncthreads();
     uint32_t lo[RQ], hi[RQ], qi[RQ];
@@ -82,6 +95,9 @@ __global__ __launch_bounds__(256) void k_ivfbin_tile(const uint32_t *__restrict_
     const uint32_t nrt = (nrows + TR - 1) / TR;
     for (uint32_t rt = blockIdx.y; rt < nrt; rt += gridDim.y) {
         const uint32_t r0 = rt * TR;  // (within the list)
+        if constexpr (PICKED) {
+            if (tid < TR) s_pick[tid] = r0 + tid < nrows ? pick[(uint64_t)row0 + r0 + tid] : 0u;
+        }
         uint32_t acc[RQ][RR];
 #pragma unroll
         for (uint32_t a = 0; a < RQ; ++a)
@@ -103,7 +119,11 @@ __global__ __launch_bounds__(256) void k_ivfbin_tile(const uint32_t *__restrict_
                 uint32_t w[LW];
 #pragma unroll
                 for (uint32_t j = 0; j < LW; ++j) w[j] = 0u;
-                if (ok) bin_load<LW>(Pl + (uint64_t)(r0 + r) * Wn + t0 + c0, w);
+                if constexpr (PICKED) {
+                    if (ok) bin_load<LW>(P + (uint64_t)s_pick[r] * Wn + t0 + c0, w);
+                } else {
+                    if (ok) bin_load<LW>(Pl + (uint64_t)(r0 + r) * Wn + t0 + c0, w);
+                }
 #pragma unroll
                 for (uint32_t j = 0; j < LW; ++j) rs[c0 + j][r] = w[j];
             }
@@ -134,14 +154,19 @@ __global__ __launch_bounds__(256) void k_ivfbin_tile(const uint32_t *__restrict_
 }
 
 // block (x = chunk of positions, y = query): the positions of the chunk whose list fewer than kIvffTileMin queries probe,
-// one per lane and pass; the query's W <= 256 words in LDS.  Items past |S(q)| leave at once.
-template <int LW>
+// one per lane and pass; the query's W <= 256 words in LDS.  Items past |S(q)| leave at once.  Picked: seg is a position
+// of the view, and the row is pick[that position].
+template <int LW, class... PICK>
 __global__ __launch_bounds__(256) void k_ivfbin_scan(const uint32_t *__restrict__ Q, const uint32_t *__restrict__ P, uint32_t Wn,
                                                      uint32_t d, const float *__restrict__ S, int root,
                                                      const uint32_t *__restrict__ probe, const uint32_t *__restrict__ cnt,
                                                      const uint32_t *__restrict__ pref, const uint32_t *__restrict__ seg,
                                                      uint32_t nprobe, uint32_t chunk, uint64_t wstride, float *__restrict__ W,
-                                                     uint32_t *__restrict__ kmin, uint32_t *__restrict__ kmax) {
+                                                     uint32_t *__restrict__ kmin, uint32_t *__restrict__ kmax, PICK... pick_arg) {
+    constexpr bool PICKED = sizeof...(PICK) == 1;
+    static_assert(sizeof...(PICK) <= 1, "one pick array at most");
+    [[maybe_unused]] const uint32_t *pick = nullptr;
+    if constexpr (PICKED) pick = (pick_arg, ...);
     extern __shared__ float s_tab[];  // [d + 1]
     __shared__ __attribute__((aligned(16))) uint32_t s_x[VQHIP_BINARY_MAX_DIM / 32];
     const uint32_t q = blockIdx.y, tid = threadIdx.x;
@@ -162,7 +187,8 @@ __global__ __launch_bounds__(256) void k_ivfbin_scan(const uint32_t *__restrict_
         if (pos >= p1) continue;
         const uint32_t slot = ivf_slot(pq, nprobe, pos);
         if (cnt[lq[slot]] >= kIvffTileMin) continue;  // (a position exists: its list is real; the tile kernel has it)
-        const uint64_t row = (uint64_t)sq[slot] + (pos - pq[slot]);
+        uint64_t row = (uint64_t)sq[slot] + (pos - pq[slot]);
+        if constexpr (PICKED) row = pick[row];
         const uint32_t *r = P + row * Wn;
         uint32_t h = 0;
         for (uint32_t t = 0; t < Wn; t += LW) {
@@ -201,7 +227,8 @@ int bin_load_width(const uint32_t *P, uint32_t W) {
 }
 
 // The two distance passes of a batch behind its plan (kernels.hpp): every D(q, i) of the probed lists into v.W, the key
-// range into p.  Q [nb][bin_words(d)]: the batch's queries, packed (launch_bq_pack).
+// range into p.  Q [nb][bin_words(d)]: the batch's queries, packed (launch_bq_pack).  v.pick: over the view of a filtered
+// call, the picked kernels.
 int launch_ivfbin_distances(const IvffPlan &p, const IvfBatchView &v, int metric, const uint32_t *P, uint32_t d, const float *S,
                             const uint32_t *Q, hipStream_t stream) {
     if (v.nb == 0) return VQHIP_OK;
@@ -212,21 +239,29 @@ int launch_ivfbin_distances(const IvffPlan &p, const IvfBatchView &v, int metric
     const uint64_t items = (v.wstride + v.chunk - 1) / v.chunk;
     if (p.tiles_max > 0) {
         const dim3 grid((uint32_t)p.tiles_max, (uint32_t)p.cols);
-        auto tile = [&](auto kernel) {
+        auto tile = [&](auto kernel, auto... pick) {
             hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, Q, P, Wn, d, S, root, v.off, v.nlist, p.cnt, p.lstart, p.tstart, v.inv,
-                               v.pref, v.nprobe, v.wstride, v.W, p.kmin, p.kmax);
+                               v.pref, v.nprobe, v.wstride, v.W, p.kmin, p.kmax, pick...);
         };
-        if (lw == 4) tile(k_ivfbin_tile<4>);
+        if (v.pick) {
+            if (lw == 4) tile(k_ivfbin_tile<4, const uint32_t *>, v.pick);
+            else if (lw == 2) tile(k_ivfbin_tile<2, const uint32_t *>, v.pick);
+            else tile(k_ivfbin_tile<1, const uint32_t *>, v.pick);
+        } else if (lw == 4) tile(k_ivfbin_tile<4>);
         else if (lw == 2) tile(k_ivfbin_tile<2>);
         else tile(k_ivfbin_tile<1>);
         VQ_LAUNCH_CHECK("k_ivfbin_tile");
     }
     if (items > 0) {
-        auto scan = [&](auto kernel) {
+        auto scan = [&](auto kernel, auto... pick) {
             hipLaunchKernelGGL(kernel, dim3((uint32_t)items, v.nb), dim3(256), lds, stream, Q, P, Wn, d, S, root, v.probe, p.cnt, v.pref,
-                               v.seg, v.nprobe, v.chunk, v.wstride, v.W, p.kmin, p.kmax);
+                               v.seg, v.nprobe, v.chunk, v.wstride, v.W, p.kmin, p.kmax, pick...);
         };
-        if (lw == 4) scan(k_ivfbin_scan<4>);
+        if (v.pick) {
+            if (lw == 4) scan(k_ivfbin_scan<4, const uint32_t *>, v.pick);
+            else if (lw == 2) scan(k_ivfbin_scan<2, const uint32_t *>, v.pick);
+            else scan(k_ivfbin_scan<1, const uint32_t *>, v.pick);
+        } else if (lw == 4) scan(k_ivfbin_scan<4>);
         else if (lw == 2) scan(k_ivfbin_scan<2>);
         else scan(k_ivfbin_scan<1>);
         VQ_LAUNCH_CHECK("k_ivfbin_scan");

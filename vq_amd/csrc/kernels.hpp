@@ -311,7 +311,7 @@ struct IvfBatchView {
     void *state;
     // a filtered call (ivf_view.hpp): ids and off above are the view's (the allowed rows only), and row j of the view is
     // row pick[j] of the payload in list order; NULL: every row, the payload as it lies.  Read by the distance passes of
-    // the flat and the scalar index alone (launch_ivfbin_distances ignores it)
+    // the flat, the scalar and the binary index
     const uint32_t *pick = nullptr;
 };
 // The view of a filtered call on an inverted file: the inverted file of the allowed rows, built once per call on the
@@ -458,10 +458,15 @@ int launch_bq_pack(const void *x, int kind, uint64_t n, uint32_t d, float thr, u
 int launch_bin_padcheck(const uint32_t *P, uint64_t n, uint32_t d, uint32_t *bad, hipStream_t stream);
 size_t binary_hist_bytes(uint32_t qb, uint32_t d);
 // Q [nb][W] packed queries, nb <= 1024; workspaces hist >= binary_hist_bytes(nb, d), sel [nb], adc_sel [2 nb], cnt [nb],
-// cand >= topk_cand_bytes(nb); results [nb][topk] on the device
+// cand >= topk_cand_bytes(nb); results [nb][topk] on the device.  mask (here and in launch_binary_range): the row mask of
+// a filtered call on the device, ceil(n / 32) words, 4-byte aligned -- the masked kernels, which
+// select among the allowed rows and pad a query with fewer than topk of them; NULL: the unmasked kernels as they are.
 int launch_binary_search(const uint32_t *P, uint64_t n, uint32_t d, int metric, const float *S, const uint32_t *Q, uint32_t nb,
                          uint32_t topk, uint32_t *hist, BinSel *sel, uint32_t *adc_sel, uint32_t *cnt,
-                         unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream);
+                         unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream,
+                         const uint32_t *mask = nullptr);
+// rows per scan workgroup of a filtered search over n rows and `groups` query groups: a multiple of 64, at most 65472
+uint64_t binary_masked_slice(uint64_t n, uint32_t groups);
 // Hamming-radius range search over the same rows: queries_dev [nq][d] f32 are packed a batch at a
 // time (binary_range_batch queries) into qw [batch][W]; hcut [nq + 32] on the device, the radii clamped to d with 32
 // entries of padding behind them; range_ws >= binary_range_ws_bytes(n, d, nq).  Row i is a hit of query q iff H <= hcut[q];
@@ -470,7 +475,7 @@ uint32_t binary_range_batch(uint64_t n, uint32_t d, uint32_t nq);
 size_t binary_range_ws_bytes(uint64_t n, uint32_t d, uint32_t nq);
 int launch_binary_range(const uint32_t *P, uint64_t n, uint32_t d, int metric, const float *S, const float *queries_dev, float thr,
                         uint32_t high, uint32_t nq, const uint32_t *hcut, uint64_t max_results, uint32_t *qw, void *range_ws,
-                        RangeOut *out, hipStream_t stream);
+                        RangeOut *out, hipStream_t stream, const uint32_t *mask = nullptr);
 
 int launch_synth_uniform(float *X, uint64_t n, uint32_t d, uint64_t seed, uint64_t row_offset,
                          hipStream_t stream);

@@ -13,7 +13,9 @@ for ``H`` and the result the ``topk`` rows of ``S(q)`` by ``(D, row id)`` ascend
 ``nprobe == nlist`` the result equals ``BinaryIndex.from_packed(words, dim, quantizer, distance).search`` -- indices,
 and distances as uint32 bits.  Slots past ``|S(q)|`` hold id ``0xFFFFFFFF`` and distance ``+inf``.
 ``hamming_range_search`` returns every row of ``S(q)`` with ``H(q, i) <= radius`` instead, in ascending row id; with
-``nprobe == nlist`` it equals ``BinaryIndex.hamming_range_search``.  Constructing,
+``nprobe == nlist`` it equals ``BinaryIndex.hamming_range_search``.  ``filtered_search`` and
+``filtered_hamming_range_search`` answer both over the allowed rows of the probed lists (``IVFBinaryFilterMixin``;
+DESIGN.md section 24).  Constructing,
 ``add_packed``, ``add_codes``, saving and loading need no GPU; ``add`` and ``add_rows`` pack on the device; the device
 state is built by the first probe or search and follows every later add.
 
@@ -39,6 +41,7 @@ import struct
 import numpy as np
 
 from . import _lib
+from ._binary_filter import IVFBinaryFilterMixin
 from ._ivf_common import (MAX_NLIST, IVFIndexBase, _count, _Reader, _check_coarse, _check_distance, _check_file_lists,
                           _train_coarse)
 from ._resident_common import DEFAULT_MAX_RESULTS, _hamming_radii, _max_results
@@ -52,7 +55,7 @@ _HEADER = struct.Struct("<8sIIIIfIIQ")
 _METRIC_NAMES = ["squared_euclidean", "euclidean", "manhattan", "cosine", "cosine_unclamped"]
 
 
-class IVFBinaryIndex(IVFIndexBase):
+class IVFBinaryIndex(IVFBinaryFilterMixin, IVFIndexBase):
     """coarse centroids (nlist, dim) + BinaryQuantizer (default ``BinaryQuantizer(0.0)``) + distance (default Manhattan)
     + coarse_distance (default Euclidean), and the rows added to it as packed words"""
 
