@@ -1172,6 +1172,18 @@ class IVFPQIndex
         return added(n, n ? vqhip_ivfpq_add(ix_.get(), list_ids, codes, n) : VQHIP_OK);
     }
 
+    // The filtered form (include/vqhip.h, vqhip_ivfpq_search_masked), plain and residual alike: the nearest among the
+    // allowed rows of the probed lists by ADC distance, padded with (0xFFFFFFFF, +inf) behind fewer than topk of them.
+    // `allowed` is the row mask of the call, ceil(n / 32) words for the n rows the index holds now (pack_row_mask).
+    using IvfIndex::search;
+    Result search(const float *queries, std::size_t nq, std::size_t topk, std::size_t nprobe, const std::uint32_t *allowed) const {
+        return masked<vqhip_ivfpq_search_masked>(queries, nq, topk, nprobe, allowed);
+    }
+    Result search(const std::vector<float> &queries, std::size_t topk, std::size_t nprobe, const std::vector<std::uint32_t> &allowed) const {
+        const std::size_t nq = check_masked_vectors(queries, allowed, nullptr);
+        return search(queries.data(), nq, topk, nprobe, allowed.data());
+    }
+
    private:
     std::size_t m_ = 0, k_ = 0;
     bool residual_ = false;

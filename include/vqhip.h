@@ -463,6 +463,24 @@ int vqhip_pq_adc_set_codes(vqhip_pq_encoder *enc, const uint8_t *codes, uint64_t
 int vqhip_pq_adc_search_resident(vqhip_pq_encoder *enc, const float *queries, uint32_t nq,
                                  uint32_t topk, uint32_t *idx_out, float *dist_out);
 int vqhip_pq_adc_last_redone(vqhip_pq_encoder *enc, uint32_t *queries_out);
+/* Filtered ADC search: the three calls above under a ROW MASK, `allowed`: ceil(n / 32) u32 words in HOST
+ * memory (copied once per call into a buffer of the encoder), n the rows of the call (the resident store's for
+ * search_resident_masked); row i is ALLOWED iff bit i & 31 of word i >> 5 is set; bits at or past n are ignored; one mask
+ * serves all queries of the call.  The result is the unfiltered statement restricted to the allowed rows: per query the
+ * first topk allowed rows by (adc_key(D), row index) ascending, D the sum above bit for bit; NaN sorts last and is reported
+ * as 0x7FC00000; Euclidean reports sqrtf(D); slots past the allowed rows of a query with fewer than topk of them hold idx
+ * 0xFFFFFFFF and dist +inf; topk keeps 1 .. min(n, 1024) whatever the mask.  All ones gives the unfiltered result bit for
+ * bit, all zeros padding only.  A filtered call always takes the full pass (a sample of evenly spaced rows says nothing
+ * about the allowed ones): its scan reads a wave's 64 rows' two mask words once, skips a wave without an allowed row and
+ * computes, writes and counts allowed rows only; vqhip_pq_adc_last_redone reports nq after it.  A NULL pointer, the mask
+ * among them, is VQHIP_ERR_NULL_PTR before the encoder is looked at; the other checks are the unfiltered calls'. */
+int vqhip_pq_adc_search_masked(vqhip_pq_encoder *enc, const uint8_t *codes, uint64_t n, const float *queries, uint32_t nq,
+                               uint32_t topk, const uint32_t *allowed, uint32_t *idx_out, float *dist_out);
+int vqhip_pq_adc_search_masked_device(vqhip_pq_encoder *enc, const void *dev_codes, uint64_t n, const float *queries,
+                                      uint32_t nq, uint32_t topk, const uint32_t *allowed, uint32_t *idx_out,
+                                      float *dist_out);
+int vqhip_pq_adc_search_resident_masked(vqhip_pq_encoder *enc, const float *queries, uint32_t nq, uint32_t topk,
+                                        const uint32_t *allowed, uint32_t *idx_out, float *dist_out);
 
 /* ---- exact k-NN search over resident rows, exact rerank (k_knn.hip) ------------------------
  * No reference counterpart (the crate has no search function).  An index holds n rows of d floats, given as f32
@@ -744,6 +762,20 @@ int vqhip_ivfpq_search_device(vqhip_ivfpq *ix, const void *dev_queries, uint32_t
 int vqhip_ivfpq_create_ex(const float *coarse, uint32_t nlist, const float *codebooks, uint32_t m, uint32_t k,
                           uint32_t sub_dim, int metric, uint32_t flags, vqhip_ivfpq **out);
 int vqhip_ivfpq_flags(const vqhip_ivfpq *ix, uint32_t *flags);
+/* Filtered search, plain and residual lists alike: the row mask, the view of the allowed rows and the rules
+ * of vqhip_ivfflat_search_masked (below) over this index's D.  n is the rows in the index at the time of the call; probing
+ * takes no mask; S_a(q) = { i in S(q) : i allowed }; per query the first topk of S_a(q) by (adc_key(D), row id), D the ADC
+ * sum above bit for bit (a residual index: of its list's table); NaN last as 0x7FC00000; Euclidean reports sqrtf(D); slots
+ * past |S_a(q)| hold idx 0xFFFFFFFF and dist +inf; topk keeps 1 .. min(n, 1024).  All ones equals the unmasked call bit for
+ * bit; with nprobe == nlist a non-residual index equals vqhip_pq_adc_search_masked over the codes in add order, indices
+ * and distance bits.  The scans read the codes of position j of the view at row pick[j] of the payload (64-bit offsets);
+ * a probe slot without an allowed row gets no residual table.  Arguments, checks and statuses are
+ * vqhip_ivfflat_search_masked[_device]'s: NULL (the mask included) is VQHIP_ERR_NULL_PTR and a device mask off 4-byte
+ * alignment VQHIP_ERR_INVALID_INPUT, both before the handle is looked at. */
+int vqhip_ivfpq_search_masked(vqhip_ivfpq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                              const uint32_t *allowed, uint32_t *idx_out, float *dist_out);
+int vqhip_ivfpq_search_masked_device(vqhip_ivfpq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                                     const uint32_t *dev_allowed, void *dev_idx, void *dev_dist);
 
 /* ---- inverted-file flat index: exact distances over the probed lists (k_ivfflat.hip) ---------
  * No reference counterpart.  An index holds coarse centroids C [nlist][dim] f32 (1 <= nlist <= 65536), a metric (any of
@@ -877,8 +909,8 @@ int vqhip_ivfsq_range_search_device(vqhip_ivfsq *ix, const void *dev_queries, ui
  * the radii, before the index handle) and before any device is touched.  The other arguments, their checks and the order
  * of the checks are the unmasked siblings'.  A filtered call builds, once, the inverted file of its allowed rows on the
  * device (8 bytes per row of workspace on the handle) and searches that: work behind the probe is proportional to the
- * allowed rows of the probed lists.  vqhip_ivfbin takes the same view (below); vqhip_ivfpq has no filtered
- * form. */
+ * allowed rows of the probed lists.  vqhip_ivfbin (below) and vqhip_ivfpq (above) take the same
+ * view. */
 int vqhip_ivfflat_search_masked(vqhip_ivfflat *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
                                 const uint32_t *allowed, uint32_t *idx_out, float *dist_out);
 int vqhip_ivfflat_search_masked_device(vqhip_ivfflat *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,

@@ -117,6 +117,16 @@ def rerank_hits(q: np.ndarray, hits: np.ndarray, topk: int, rerank):
     return idx, dist
 
 
+def filtered_adc_then_rerank(adc_search, n: int, dim: int, q: np.ndarray, topk: int, rerank, candidates):
+    """`flat.adc_then_rerank` behind a filtered first stage: `adc_search(q, c)` returns allowed rows only, PAD_ID behind them
+    where a query has fewer than c, so the exact rerank goes through `rerank_hits`"""
+    from .flat import rerank_candidates
+
+    c = rerank_candidates(n, dim, topk, rerank, candidates)
+    hits, _ = adc_search(q, c)
+    return rerank_hits(q, hits, topk, rerank)
+
+
 class IVFIndexBase:
     """coarse centroids (nlist, dim) + distance + the list id of every added row; `_ix` is the device handle or None"""
 

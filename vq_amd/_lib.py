@@ -104,6 +104,9 @@ SIGNATURES = {
     "vqhip_pq_adc_last_redone": (C.c_int, [_vp, _u32p]),
     "vqhip_pq_adc_set_codes": (C.c_int, [_vp, _u8p, C.c_uint64]),
     "vqhip_pq_adc_search_resident": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "vqhip_pq_adc_search_masked": (C.c_int, [_vp, _u8p, C.c_uint64, _f32p, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p]),
+    "vqhip_pq_adc_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint64, _f32p, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p]),
+    "vqhip_pq_adc_search_resident_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p]),
     "vqhip_selftest": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "vqhip_mfma_bf16_probe": (C.c_int, [_u16p, _u16p, _f32p, C.c_uint64, _f32p]),
     "vqhip_mfma_bf16_model": (C.c_int, [_u16p, _u16p, _f32p, C.c_uint64, _f32p]),
@@ -212,6 +215,8 @@ SIGNATURES = {
     "vqhip_ivfpq_probe": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p]),
     "vqhip_ivfpq_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _f32p]),
     "vqhip_ivfpq_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "vqhip_ivfpq_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p]),
+    "vqhip_ivfpq_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "vqhip_ivfflat_create": (C.c_int, [_f32p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, _vpp]),
     "vqhip_ivfflat_destroy": (C.c_int, [_vp]),
     "vqhip_ivfflat_add": (C.c_int, [_vp, _u32p, _vp, C.c_uint64]),
@@ -764,9 +769,10 @@ class PQEncoder(Handle):
     def set_engine(self, engine: int):
         check(load().vqhip_pq_encoder_set_engine(self.raw, engine))
 
-    def adc_search(self, codes, queries, topk: int):
+    def adc_search(self, codes, queries, topk: int, allowed=None):
         """top-k rows of `codes` [n][m] (u8, u16 above 256 centroids; numpy array, (device_ptr, n), or None = the store adc_set_codes uploaded) per query by asymmetric
-        distance; returns (idx uint32 [nq][topk], dist float32 [nq][topk])"""
+        distance; returns (idx uint32 [nq][topk], dist float32 [nq][topk]).  allowed: the row mask's uint32 (ceil(n / 32),)
+        words on the host -- the filtered forms (None: every row)"""
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -776,6 +782,17 @@ class PQEncoder(Handle):
         if nq == 0:
             return idx, dist
         lib = load()
+        if allowed is not None:
+            w, out = ptr(allowed, _u32p), (ptr(idx, _u32p), ptr(dist, _f32p))
+            if codes is None:
+                check(lib.vqhip_pq_adc_search_resident_masked(self.raw, ptr(q, _f32p), nq, int(topk), w, *out))
+            elif isinstance(codes, tuple):
+                dev_ptr, n = codes
+                check(lib.vqhip_pq_adc_search_masked_device(self.raw, C.c_void_p(dev_ptr), int(n), ptr(q, _f32p), nq, int(topk), w, *out))
+            else:
+                c = np.ascontiguousarray(codes, dtype=code_dtype(self.k))
+                check(lib.vqhip_pq_adc_search_masked(self.raw, ptr(c, _u8p), c.shape[0], ptr(q, _f32p), nq, int(topk), w, *out))
+            return idx, dist
         if codes is None:  # the codes adc_set_codes left on the device
             check(lib.vqhip_pq_adc_search_resident(self.raw, ptr(q, _f32p), nq, int(topk), ptr(idx, _u32p), ptr(dist, _f32p)))
         elif isinstance(codes, tuple):
@@ -1059,12 +1076,10 @@ class _IVFHandle(Handle):
                                         C.c_void_p(dev_idx), C.c_void_p(dev_dist)))
 
 
-class _IVFMaskedCalls:
-    """the filtered forms of an inverted-file handle's search and range search (radii: float32 distances, or the binary
-    index's uint32 Hamming radii)"""
+class _IVFMaskedSearch:
+    """the filtered forms of an inverted-file handle's search: `allowed` uint32 (ceil(n / 32),) row-mask words on the host,
+    `dev_allowed` the same at a device pointer (4-byte aligned)"""
 
-    # the filtered forms: `allowed` uint32 (ceil(n / 32),) row-mask words on the host, `dev_allowed` the same at a device
-    # pointer (4-byte aligned)
     def search_masked(self, q: np.ndarray, nprobe: int, topk: int, allowed: np.ndarray):
         nq = q.shape[0]
         idx = np.empty((nq, topk), np.uint32)
@@ -1076,6 +1091,10 @@ class _IVFMaskedCalls:
     def search_masked_device(self, dev_queries: int, nq: int, nprobe: int, topk: int, dev_allowed: int, dev_idx: int, dev_dist: int):
         check(self._fn("search_masked_device")(self.raw, C.c_void_p(dev_queries), int(nq), int(nprobe), int(topk),
                                                C.c_void_p(dev_allowed), C.c_void_p(dev_idx), C.c_void_p(dev_dist)))
+
+
+class _IVFMaskedCalls(_IVFMaskedSearch):
+    """and of its range search (radii: float32 distances, or the binary index's uint32 Hamming radii)"""
 
     def range_search_masked(self, q: np.ndarray, nprobe: int, radii: np.ndarray, max_results: int, allowed: np.ndarray) -> RangeResult:
         return _range_call(self._fn("range_search_masked"), self.raw, ptr(q, _f32p), q.shape[0], radii, max_results, int(nprobe),
@@ -1097,7 +1116,7 @@ class _IVFExactHandle(_IVFMaskedCalls, _IVFHandle):
         return _range_call(self._fn("range_search_device"), self.raw, C.c_void_p(dev_queries), nq, radii, max_results, int(nprobe))
 
 
-class IVFPQ(_IVFHandle):
+class IVFPQ(_IVFMaskedSearch, _IVFHandle):
     """vqhip_ivfpq: inverted-file PQ index -- coarse centroids, codebooks, rows in lists (k_ivf.hip).  Create, add and
     list_sizes are host-only; the device state is built by the first probe or search.  flags: IVF_RESIDUAL for lists
     whose codes quantise x - C[list]."""

@@ -879,6 +879,7 @@ struct vqhip_pq_encoder {
     int metric = VQHIP_EUCLIDEAN;
     int engine = VQHIP_ENGINE_AUTO;
     DevBuf xbuf, codes, f16buf, f32buf, adc_q, adc_lut, adc_dist, adc_idx, adc_out, adc_codes, adc_state, adc_cand, adc_redo, adc_resident;
+    DevBuf adc_mask;               // a filtered ADC call's row mask on the device
     uint64_t adc_resident_n = 0;   // rows of the code store vqhip_pq_adc_set_codes uploaded
     uint32_t adc_last_redone = 0;  // queries of the last ADC call that went through the full pass
     std::vector<uint32_t> all_subs;
@@ -2328,8 +2329,11 @@ int vqhip_pq_encode(vqhip_pq_encoder *enc, const float *rows, uint64_t n, uint8_
 }
 
 // ------------------------------------------------------------------------ ADC search ----
-int vqhip_pq_adc_search_device(vqhip_pq_encoder *enc, const void *dev_codes, uint64_t n, const float *queries,
-                               uint32_t nq, uint32_t topk, uint32_t *idx_out, float *dist_out) {
+// dev_mask: a filtered call's row mask on the device, ceil(n / 32) words (adc_search_masked below); NULL: every row.  A
+// filtered call never takes the sampled-threshold schedule -- a sample of evenly spaced rows says nothing about the
+// allowed ones -- and goes through the full pass with the masked scan and the masked source.
+static int adc_search(vqhip_pq_encoder *enc, const void *dev_codes, uint64_t n, const float *queries, uint32_t nq, uint32_t topk,
+                      uint32_t *idx_out, float *dist_out, const uint32_t *dev_mask) {
     VQ_API_BEGIN
     if (!enc || !dev_codes || !queries || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
     if (nq == 0) return VQHIP_OK;
@@ -2344,8 +2348,8 @@ int vqhip_pq_adc_search_device(vqhip_pq_encoder *enc, const void *dev_codes, uin
         uint32_t redone = 0;
         for (uint32_t q0 = 0; q0 < nq; q0 += kAdcCallQueries) {
             const uint32_t cn = std::min(kAdcCallQueries, nq - q0);
-            VQ_TRY(vqhip_pq_adc_search_device(enc, dev_codes, n, queries + (size_t)q0 * dim, cn, topk, idx_out + (size_t)q0 * topk,
-                                              dist_out + (size_t)q0 * topk));
+            VQ_TRY(adc_search(enc, dev_codes, n, queries + (size_t)q0 * dim, cn, topk, idx_out + (size_t)q0 * topk,
+                              dist_out + (size_t)q0 * topk, dev_mask));
             redone += enc->adc_last_redone;
         }
         enc->adc_last_redone = redone;
@@ -2361,7 +2365,7 @@ int vqhip_pq_adc_search_device(vqhip_pq_encoder *enc, const void *dev_codes, uin
     // the runtime that holds the calling thread (~12 us each; an 8-query call spent more time in its four copies than in
     // its kernels)
     const size_t q_b = (size_t)nq * dim * 4, nres = (size_t)nq * topk, pack_b = (2 * nres + 2 * (size_t)nq) * 4;
-    const bool fast = adc_fast_eligible(m, k, n, topk), staged = fast && q_b + pack_b <= (1u << 20);
+    const bool fast = !dev_mask && adc_fast_eligible(m, k, n, topk), staged = fast && q_b + pack_b <= (1u << 20);
     StageLease stage;
     if (staged) {
         VQ_TRY(stage.acquire(q_b + pack_b));
@@ -2379,7 +2383,7 @@ int vqhip_pq_adc_search_device(vqhip_pq_encoder *enc, const void *dev_codes, uin
         return launch_adc_search(enc->cs.cb.as<float>(), m, k, sd, enc->metric, reinterpret_cast<const uint8_t *>(dev_codes), n,
                                  enc->adc_q.as<float>() + (size_t)q0 * dim, cnt, topk, enc->adc_lut.as<float>(), enc->adc_dist.as<float>(),
                                  enc->adc_state.p, enc->adc_cand.as<unsigned long long>(), enc->adc_idx.as<uint32_t>() + (size_t)q0 * topk,
-                                 enc->adc_out.as<float>() + (size_t)q0 * topk, s, qg);
+                                 enc->adc_out.as<float>() + (size_t)q0 * topk, s, qg, dev_mask);
     };
     if (fast) {
         // one scan of the codes per batch of queries against a sampled threshold, only candidates written (k_adc.hip);
@@ -2436,6 +2440,73 @@ int vqhip_pq_adc_search_device(vqhip_pq_encoder *enc, const void *dev_codes, uin
     VQ_HIP(hipStreamSynchronize(s));
     in.synced();
     return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_pq_adc_search_device(vqhip_pq_encoder *enc, const void *dev_codes, uint64_t n, const float *queries,
+                               uint32_t nq, uint32_t topk, uint32_t *idx_out, float *dist_out) {
+    return adc_search(enc, dev_codes, n, queries, nq, topk, idx_out, dist_out, nullptr);
+}
+
+}  // extern "C"
+
+// The filtered forms: the host mask, ceil(n / 32) words, goes up once per call into the encoder's adc_mask, under the
+// encoder's lock; the search behind it is adc_search over the device codes that codes_up(s, &dev_codes) names or uploads.
+template <class CodesUp>
+static int adc_search_masked(vqhip_pq_encoder *enc, uint64_t n, const float *queries, uint32_t nq, uint32_t topk, const uint32_t *allowed,
+                             uint32_t *idx_out, float *dist_out, CodesUp &&codes_up) {
+    Entry in(enc->sync);
+    if (nq == 0) return VQHIP_OK;
+    if (n == 0 || n >= (1ull << 32)) return fail(VQHIP_ERR_INVALID_INPUT, "n must be in [1, 2^32)");
+    VQ_TRY(require_gfx950());
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));
+    const void *dev_codes = nullptr;
+    VQ_TRY(codes_up(s, &dev_codes));
+    const size_t mask_b = (size_t)((n + 31) / 32) * 4;
+    VQ_TRY(enc->adc_mask.ensure(mask_b));
+    VQ_HIP(hipMemcpyAsync(enc->adc_mask.p, allowed, mask_b, hipMemcpyHostToDevice, s));
+    return adc_search(enc, dev_codes, n, queries, nq, topk, idx_out, dist_out, enc->adc_mask.as<uint32_t>());
+}
+
+extern "C" {
+
+int vqhip_pq_adc_search_masked_device(vqhip_pq_encoder *enc, const void *dev_codes, uint64_t n, const float *queries, uint32_t nq,
+                                      uint32_t topk, const uint32_t *allowed, uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    if (!enc || !dev_codes || !queries || !allowed || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    return adc_search_masked(enc, n, queries, nq, topk, allowed, idx_out, dist_out, [&](hipStream_t, const void **codes) -> int {
+        *codes = dev_codes;
+        return VQHIP_OK;
+    });
+    VQ_API_END
+}
+
+int vqhip_pq_adc_search_resident_masked(vqhip_pq_encoder *enc, const float *queries, uint32_t nq, uint32_t topk, const uint32_t *allowed,
+                                        uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    if (!enc || !queries || !allowed || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(enc->sync);
+    if (!enc->adc_resident_n) return fail(VQHIP_ERR_INVALID_INPUT, "no codes loaded: call vqhip_pq_adc_set_codes first");
+    return adc_search_masked(enc, enc->adc_resident_n, queries, nq, topk, allowed, idx_out, dist_out,
+                             [&](hipStream_t, const void **codes) -> int {
+        *codes = enc->adc_resident.p;
+        return VQHIP_OK;
+    });
+    VQ_API_END
+}
+
+int vqhip_pq_adc_search_masked(vqhip_pq_encoder *enc, const uint8_t *codes, uint64_t n, const float *queries, uint32_t nq, uint32_t topk,
+                               const uint32_t *allowed, uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    if (!enc || !codes || !queries || !allowed || !idx_out || !dist_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    return adc_search_masked(enc, n, queries, nq, topk, allowed, idx_out, dist_out, [&](hipStream_t s, const void **dev_codes) -> int {
+        const size_t code_b = (size_t)n * enc->cs.m * code_bytes(enc->cs.k);
+        VQ_TRY(enc->adc_codes.ensure(code_b));
+        VQ_HIP(hipMemcpyAsync(enc->adc_codes.p, codes, code_b, hipMemcpyHostToDevice, s));
+        *dev_codes = enc->adc_codes.p;
+        return VQHIP_OK;
+    });
     VQ_API_END
 }
 
@@ -3809,6 +3880,32 @@ struct IvfView {
     const uint32_t *pick = nullptr, *aids = nullptr, *aoff = nullptr;
 };
 
+// IvfLists with a filtered call's view (DESIGN.md sections 23 to 25): what vqhip_ivfpq and IvfOverW's three share.
+struct IvfFiltered : IvfLists {
+    DevBuf mask_ws;                       // a filtered host call's row mask on the device
+    DevBuf v_pick, v_aids, v_aoff, v_ws;  // a filtered call's view (8 bytes per row) and the workspace of its scan
+
+    // The view of a filtered call, built once per call: after ready(s), under the handle's lock, enqueued on s.  allowed:
+    // the row mask, ceil(n / 32) words for the n of this call -- a host form's goes up into mask_ws first.
+    int filtered(const uint32_t *allowed, bool host, hipStream_t s, IvfView *view) {
+        const uint64_t n = this->n;
+        if (host) {
+            const size_t mask_b = (size_t)((n + 31) / 32) * 4;
+            VQ_TRY(mask_ws.ensure(mask_b));
+            if (mask_b) VQ_HIP(hipMemcpyAsync(mask_ws.p, allowed, mask_b, hipMemcpyHostToDevice, s));
+            allowed = mask_ws.as<uint32_t>();
+        }
+        VQ_TRY(v_pick.ensure((size_t)n * 4));
+        VQ_TRY(v_aids.ensure((size_t)n * 4));
+        VQ_TRY(v_aoff.ensure(((size_t)this->nlist + 1) * 4));
+        VQ_TRY(v_ws.ensure(ivf_view_ws_bytes(n)));
+        VQ_TRY(launch_ivf_view(allowed, this->d_ids.template as<uint32_t>(), n, this->d_off.template as<uint32_t>(), this->nlist, v_ws.p,
+                               v_pick.as<uint32_t>(), v_aids.as<uint32_t>(), v_aoff.as<uint32_t>(), s));
+        *view = IvfView{v_pick.as<uint32_t>(), v_aids.as<uint32_t>(), v_aoff.as<uint32_t>()};
+        return VQHIP_OK;
+    }
+};
+
 // The front of every probe and search (T: an index with ready(s)): the checks in their order, the index's device, the
 // calling thread's stream, the device state -- then body(in, s).  topk NULL: a probe.
 template <class T, class F>
@@ -3852,7 +3949,7 @@ static int ivf_search_device(T *ix, const void *dev_queries, uint32_t nq, uint32
     });
 }
 
-// The filtered forms of the two (vqhip_ivfflat, vqhip_ivfsq and vqhip_ivfbin, IvfOverW below): the row mask `allowed` (host: ceil(n /
+// The filtered forms of the two (vqhip_ivfpq, vqhip_ivfflat, vqhip_ivfsq and vqhip_ivfbin, IvfFiltered above): the row mask `allowed` (host: ceil(n /
 // 32) words, staged on the handle; device: a 4-byte aligned pointer) becomes the call's view once, after ready(s) and
 // under the handle's lock (ix->filtered), and the search runs over it.  A NULL mask is reported before a device is touched.
 template <class T>
@@ -3877,7 +3974,7 @@ static int ivf_search_masked(T *ix, const void *queries, bool host, uint32_t nq,
 // ------------------------------------------------------------------ inverted-file PQ (k_ivf.hip) ----
 // IvfLists whose payload is PQ codes (m codes of code_bytes(k) each), and the codebooks.  A residual index
 // (VQHIP_IVF_RESIDUAL) also keeps the coarse centroids on the device for its tables.
-struct vqhip_ivfpq : IvfLists {
+struct vqhip_ivfpq : IvfFiltered {
     uint32_t m = 0, k = 0, sd = 0;
     uint32_t flags = 0;     // VQHIP_IVF_RESIDUAL: codes of x - C[list]
     std::vector<float> cb;  // [m][k][sd]
@@ -3897,10 +3994,14 @@ struct vqhip_ivfpq : IvfLists {
     }
 
     // queries_dev [nq][dim] f32 -> [nq][topk] results on the device, enqueued on s, in ivf_batch's batches: a query's
-    // tables are one ADC table, nprobe of them in a residual index
+    // tables are one ADC table, nprobe of them in a residual index.  view: a filtered call's (NULL: every row) -- the batches
+    // then run over its lists, ids and positions, wstride and the chunk keeping their unfiltered bounds
     int search_enqueue(const float *queries_dev, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
-                       hipStream_t s) {
+                       hipStream_t s, const IvfView *view = nullptr) {
         const bool residual = (flags & VQHIP_IVF_RESIDUAL) != 0;
+        const bool fv = view && view->pick;
+        const uint32_t *ids = fv ? view->aids : d_ids.as<uint32_t>(), *off = fv ? view->aoff : d_off.as<uint32_t>();
+        const uint32_t *pick = fv ? view->pick : nullptr;
         const uint64_t tab_b = (uint64_t)m * k * 4 * (residual ? nprobe : 1);
         IvfBatch b;
         VQ_TRY(ivf_batch(this, nq, nprobe, tab_b, &b));
@@ -3917,18 +4018,18 @@ struct vqhip_ivfpq : IvfLists {
             const float *Q = queries_dev + (size_t)q0 * dim;
             VQ_TRY(ivf_probe_enqueue(this, Q, nb, nprobe, probe.as<uint32_t>(), s));
             if (residual) {
-                VQ_TRY(launch_ivf_rsearch(d_payload.as<uint8_t>(), d_ids.as<uint32_t>(), d_off.as<uint32_t>(), d_coarse.as<float>(), nlist,
+                VQ_TRY(launch_ivf_rsearch(d_payload.as<uint8_t>(), ids, off, d_coarse.as<float>(), nlist,
                                           d_cb.as<float>(), m, k, sd, metric, Q, probe.as<uint32_t>(), nb, nprobe, topk,
                                           ivf_rchunk((uint64_t)nb * b.per_q, k), b.wstride, rtab.as<float>(), rmm.as<float>(), W.as<float>(),
                                           pref.as<uint32_t>(), seg.as<uint32_t>(), bounds.as<float>(), state.p,
-                                          cand.as<unsigned long long>(), idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s));
+                                          cand.as<unsigned long long>(), idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s, pick));
                 continue;
             }
             VQ_TRY(launch_adc_lut(Q, nb, m, k, sd, d_cb.as<float>(), metric, lut.as<float>(), bounds.as<float>(), s));
-            VQ_TRY(launch_ivf_search(d_payload.as<uint8_t>(), d_ids.as<uint32_t>(), d_off.as<uint32_t>(), nlist, m, k, metric, lut.as<float>(),
+            VQ_TRY(launch_ivf_search(d_payload.as<uint8_t>(), ids, off, nlist, m, k, metric, lut.as<float>(),
                                      probe.as<uint32_t>(), nb, nprobe, topk, ivf_chunk((uint64_t)nb * b.per_q), b.wstride, W.as<float>(),
                                      pref.as<uint32_t>(), seg.as<uint32_t>(), bounds.as<float>(), state.p, cand.as<unsigned long long>(),
-                                     idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s));
+                                     idx_dev + (size_t)q0 * topk, dist_dev + (size_t)q0 * topk, s, pick));
         }
         return VQHIP_OK;
     }
@@ -4024,6 +4125,20 @@ int vqhip_ivfpq_search_device(vqhip_ivfpq *ix, const void *dev_queries, uint32_t
     VQ_API_END
 }
 
+int vqhip_ivfpq_search_masked(vqhip_ivfpq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk, const uint32_t *allowed,
+                              uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    return ivf_search_masked(ix, queries, true, nq, nprobe, topk, allowed, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_ivfpq_search_masked_device(vqhip_ivfpq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                                     const uint32_t *dev_allowed, void *dev_idx, void *dev_dist) {
+    VQ_API_BEGIN
+    return ivf_search_masked(ix, dev_queries, false, nq, nprobe, topk, dev_allowed, dev_idx, dev_dist);
+    VQ_API_END
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------ inverted files over W (k_ivfflat.hip, k_ivfsq.hip, k_ivfbin.hip) ----
@@ -4033,33 +4148,11 @@ int vqhip_ivfpq_search_device(vqhip_ivfpq *ix, const void *dev_queries, uint32_t
 //   prepare(queries_dev, nq, nb_max, s)   once per call: the query norms under the cosines, or room for the packed queries
 //   distances(p, v, Q, q0, s)             one batch's distance passes behind its plan p (Q: the batch's queries, f32)
 //   radii_up(radii, nq, s)                the radii of a range call into this->radii as f32 distances
-// A filtered call's view of the allowed rows (filtered(); DESIGN.md sections 23 and 24) is built here, for all three.
+// A filtered call's view of the allowed rows (IvfFiltered::filtered(); DESIGN.md sections 23 and 24) is built once per call.
 template <class T>
-struct IvfOverW : IvfLists {
+struct IvfOverW : IvfFiltered {
     DevBuf inv, lists;              // per-call workspaces: the inverted probe table, the lists' state
     DevBuf radii, range_ws, stage;  // range search: the radii, the stage's counts and offsets, its staging areas
-    DevBuf mask_ws;                 // a filtered host call's row mask on the device
-    DevBuf v_pick, v_aids, v_aoff, v_ws;  // a filtered call's view (8 bytes per row) and the workspace of its scan
-
-    // The view of a filtered call, built once per call: after ready(s), under the handle's lock, enqueued on s.  allowed:
-    // the row mask, ceil(n / 32) words for the n of this call -- a host form's goes up into mask_ws first.
-    int filtered(const uint32_t *allowed, bool host, hipStream_t s, IvfView *view) {
-        const uint64_t n = this->n;
-        if (host) {
-            const size_t mask_b = (size_t)((n + 31) / 32) * 4;
-            VQ_TRY(mask_ws.ensure(mask_b));
-            if (mask_b) VQ_HIP(hipMemcpyAsync(mask_ws.p, allowed, mask_b, hipMemcpyHostToDevice, s));
-            allowed = mask_ws.as<uint32_t>();
-        }
-        VQ_TRY(v_pick.ensure((size_t)n * 4));
-        VQ_TRY(v_aids.ensure((size_t)n * 4));
-        VQ_TRY(v_aoff.ensure(((size_t)this->nlist + 1) * 4));
-        VQ_TRY(v_ws.ensure(ivf_view_ws_bytes(n)));
-        VQ_TRY(launch_ivf_view(allowed, this->d_ids.template as<uint32_t>(), n, this->d_off.template as<uint32_t>(), this->nlist, v_ws.p,
-                               v_pick.as<uint32_t>(), v_aids.as<uint32_t>(), v_aoff.as<uint32_t>(), s));
-        *view = IvfView{v_pick.as<uint32_t>(), v_aids.as<uint32_t>(), v_aoff.as<uint32_t>()};
-        return VQHIP_OK;
-    }
 
     // The batch loop: queries_dev [nq][dim] f32 in ivf_batch's batches -- the probe, the plan, the index's distances, then
     // stage(p, v, q0) behind them.  topk: the selection's; 0: the range stage follows (its workspace is sized here for

@@ -81,13 +81,30 @@ struct AdcSource : TopkRows {
     uint32_t blocks() const { return 64; }
 };
 
+// the full pass under a row mask: the scan's allowed rows only, and the selection over them
+struct MaskedAdcSource : MaskedRows {
+    const float *bounds;
+    float lo = 0, scale = 0;  // (device: of the opened query)
+    __device__ void open(uint32_t q) {
+        TopkRows::open(q);
+        lo = bounds[2 * q];
+        scale = adc_scale(lo, bounds[2 * q + 1]);
+    }
+    __device__ uint32_t bin(float dval) const { return adc_bin(dval, lo, scale); }
+    uint32_t blocks() const { return 64; }
+};
+
 // dist[qq][i] for the queries q0 .. q0+nqb-1
 // blockIdx.y = batch of kAdcQB queries inside a group (round 6: the batches of a group run in ONE set of launches; the
 // per-query arrays -- lut, bounds, dist, hist -- are laid out over the group's queries, batch b owns queries 8b .. 8b+7)
-__global__ __launch_bounds__(256) void k_adc_scan(const uint8_t *__restrict__ codes, uint64_t n, uint32_t m,
-                                                  uint32_t k, const float *__restrict__ lut, uint32_t nq_group, uint32_t qb,
-                                                  const float *__restrict__ bounds, float *__restrict__ dist,
-                                                  uint32_t *__restrict__ hist) {
+// Masked (k_adc_scan_masked): a wave's 64 consecutive rows are two words of the row mask, one load per pass of the wave.
+// A wave without an allowed row among them loads no code, adds no term and writes nothing (no lane stays active);
+// otherwise only the allowed rows are computed, written to dist and counted.  Bits at or past n belong to no row.
+template <bool Masked>
+__device__ __forceinline__ void adc_scan_body(const uint8_t *__restrict__ codes, uint64_t n, uint32_t m, uint32_t k,
+                                              const float *__restrict__ lut, uint32_t nq_group, uint32_t qb,
+                                              const float *__restrict__ bounds, float *__restrict__ dist,
+                                              uint32_t *__restrict__ hist, const uint32_t *__restrict__ mask) {
     extern __shared__ __attribute__((aligned(16))) float lds_lut[];  // [nqb][m][k], then the block's histograms [nqb][kAdcBins]
     const uint32_t tab = m * k;
     const uint32_t q_first = blockIdx.y * qb;
@@ -108,6 +125,9 @@ __global__ __launch_bounds__(256) void k_adc_scan(const uint8_t *__restrict__ co
     }
     __syncthreads();
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        if constexpr (Masked) {  // (i < n: a bit at or past n is never read as a row's)
+            if (!((mask[i >> 5] >> (uint32_t)(i & 31u)) & 1u)) continue;
+        }
         float acc[kAdcQB];
 #pragma unroll
         for (uint32_t qq = 0; qq < kAdcQB; ++qq) acc[qq] = 0.0f;
@@ -143,6 +163,21 @@ __global__ __launch_bounds__(256) void k_adc_scan(const uint8_t *__restrict__ co
     __syncthreads();
     for (uint32_t e = threadIdx.x; e < nqb * kAdcBins; e += 256)
         if (lds_hist[e]) atomicAdd(&hist[e], lds_hist[e]);
+}
+
+__global__ __launch_bounds__(256) void k_adc_scan(const uint8_t *__restrict__ codes, uint64_t n, uint32_t m,
+                                                  uint32_t k, const float *__restrict__ lut, uint32_t nq_group, uint32_t qb,
+                                                  const float *__restrict__ bounds, float *__restrict__ dist,
+                                                  uint32_t *__restrict__ hist) {
+    adc_scan_body<false>(codes, n, m, k, lut, nq_group, qb, bounds, dist, hist, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_adc_scan_masked(const uint8_t *__restrict__ codes, uint64_t n, uint32_t m,
+                                                         uint32_t k, const float *__restrict__ lut, uint32_t nq_group,
+                                                         uint32_t qb, const float *__restrict__ bounds,
+                                                         float *__restrict__ dist, uint32_t *__restrict__ hist,
+                                                         const uint32_t *__restrict__ mask) {
+    adc_scan_body<true>(codes, n, m, k, lut, nq_group, qb, bounds, dist, hist, mask);
 }
 
 
@@ -423,11 +458,13 @@ int adc_fast_launch(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int l1
 }  // namespace
 
 // queries_dev [nq][m*sd]; workspaces sized for a group of `qgroup` queries (adc_query_group): lut_ws >= qgroup*m*k floats,
-// dist_ws >= qgroup*n floats, state_ws >= adc_state_bytes(qgroup), cand_ws >= topk_cand_bytes(qgroup); outputs on the device
+// dist_ws >= qgroup*n floats, state_ws >= adc_state_bytes(qgroup), cand_ws >= topk_cand_bytes(qgroup); outputs on the device.
+// mask: a filtered call's row mask on the device, ceil(n / 32) words (NULL: every row, today's kernels) -- the scan and the
+// selection then see the allowed rows only, and a query with fewer than topk of them is padded behind them.
 int launch_adc_search(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int metric, const uint8_t *codes, uint64_t n,
                       const float *queries_dev, uint32_t nq, uint32_t topk, float *lut_ws, float *dist_ws,
                       void *state_ws, unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev,
-                      hipStream_t stream, uint32_t qgroup) {
+                      hipStream_t stream, uint32_t qgroup, const uint32_t *mask) {
     if (vq_is_cos(metric))
         return fail(VQHIP_ERR_UNSUPPORTED, "cosine distance is not a sum over subspaces: no ADC form");
     if (topk == 0 || topk > 1024 || topk > n) return fail(VQHIP_ERR_INVALID_INPUT, "topk must be in [1, min(n, 1024)]");
@@ -438,6 +475,8 @@ int launch_adc_search(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int 
     static PerDeviceOnce attr;
     if (attr.needed()) {
         VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_adc_scan), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)kAdcFullScanLdsMax));
+        VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_adc_scan_masked), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)kAdcFullScanLdsMax));
         attr.done();
     }
@@ -466,6 +505,14 @@ int launch_adc_search(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int 
         hipLaunchKernelGGL(k_adc_lut, dim3(nqg, m), dim3(256), 0, stream, queries_dev + (size_t)q0 * m * sd, nqg, m, k, sd,
                            cb, l1, lut_ws, bounds);
         VQ_LAUNCH_CHECK("k_adc_lut");
+        if (mask) {
+            hipLaunchKernelGGL(k_adc_scan_masked, dim3((uint32_t)blocks, batches), dim3(256), scan_lds, stream,
+                               codes, n, m, k, lut_ws, nqg, qb, bounds, dist_ws, st.hist, mask);
+            VQ_LAUNCH_CHECK("k_adc_scan_masked");
+            VQ_TRY(launch_topk_select(MaskedAdcSource{{{dist_ws, n}, mask}, bounds}, nqg, topk, take_sqrt, st, cand_ws,
+                                      idx_out_dev + (size_t)q0 * topk, dist_out_dev + (size_t)q0 * topk, stream));
+            continue;
+        }
         hipLaunchKernelGGL(k_adc_scan, dim3((uint32_t)blocks, batches), dim3(256), scan_lds, stream,
                            codes, n, m, k, lut_ws, nqg, qb, bounds, dist_ws, st.hist);
         VQ_LAUNCH_CHECK("k_adc_scan");

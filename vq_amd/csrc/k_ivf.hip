@@ -10,6 +10,8 @@
 // histogram of the distances) -> launch_topk_select (topk.hpp) over IvfSource: the positions of
 // S(q), the row id of each through the plan's prefix.  The histogram only decides which positions become candidates;
 // every candidate carries its exact unique key, so the result does not depend on the bins.
+// A filtered call runs the same schedule over the view of its allowed rows (ivf_view.hpp): off / ids
+// are the view's, and the scans' Picked variants read the codes of position j at row pick[j] of the payload.
 #include "adc_plan.hpp"
 #include "common.hpp"
 #include "ivf_plan.hpp"
@@ -59,13 +61,23 @@ __global__ __launch_bounds__(1024) void k_ivf_plan(const uint32_t *__restrict__ 
     }
 }
 
+// the row of the payload behind position `at` of the list order: the position itself, or -- Picked, a filtered call
+// whose pref / seg are the plan over the view's aoff -- pick[at], the view's position `at`
+template <bool Picked>
+__device__ __forceinline__ uint64_t ivf_code_row(const uint32_t *__restrict__ pick, uint64_t at) {
+    if constexpr (Picked) return pick[at];
+    return at;
+}
+
 // work item (blockIdx.x, blockIdx.y = query): positions [x chunk, (x + 1) chunk) of S(q); items past |S(q)| leave at once.
 // W[q][pos] = D, hist[q][bin] += 1 (integer atomics: the counts do not depend on their order)
+template <bool Picked>
 __global__ __launch_bounds__(256) void k_ivf_scan(const uint8_t *__restrict__ codes, uint32_t m, uint32_t k,
                                                   const float *__restrict__ lut, const uint32_t *__restrict__ pref,
                                                   const uint32_t *__restrict__ seg, uint32_t nprobe,
                                                   const float *__restrict__ bounds, uint32_t chunk, uint64_t wstride,
-                                                  float *__restrict__ W, uint32_t *__restrict__ hist) {
+                                                  float *__restrict__ W, uint32_t *__restrict__ hist,
+                                                  const uint32_t *__restrict__ pick) {
     extern __shared__ __attribute__((aligned(16))) float lds_lut[];  // [m][k] table, then [kAdcBins] histogram
     const uint32_t q = blockIdx.y, tab = m * k;
     const uint32_t *pq = pref + (size_t)q * (nprobe + 1);
@@ -92,7 +104,7 @@ __global__ __launch_bounds__(256) void k_ivf_scan(const uint8_t *__restrict__ co
                 next = pq[slot + 1];
             }
             float acc[1];  // (topk.hpp's adc_row, the ADC scans' operation order, for one query's table)
-            adc_row<1>(codes, (uint64_t)sq[slot] + (pos - first), m, k, words, lds_lut, 1u, 0u, acc);
+            adc_row<1>(codes, ivf_code_row<Picked>(pick, (uint64_t)sq[slot] + (pos - first)), m, k, words, lds_lut, 1u, 0u, acc);
             const float dv = acc[0];
             wq[pos] = dv;
             atomicAdd(&lds_hist[adc_bin(dv, lo, scale)], 1u);
@@ -270,11 +282,13 @@ __global__ __launch_bounds__(1024) void k_ivf_rplan(const uint32_t *__restrict__
 
 // k_ivf_scan over residual lists: the chunk [p0, p1) of S(q) in slot runs; at each slot boundary the block (uniformly)
 // loads that slot's table into LDS.  W and the histogram exactly as k_ivf_scan writes them.
+template <bool Picked>
 __global__ __launch_bounds__(256) void k_ivf_rscan(const uint8_t *__restrict__ codes, uint32_t m, uint32_t k,
                                                    const float *__restrict__ tabs, const uint32_t *__restrict__ pref,
                                                    const uint32_t *__restrict__ seg, uint32_t nprobe,
                                                    const float *__restrict__ bounds, uint32_t chunk, uint64_t wstride,
-                                                   float *__restrict__ W, uint32_t *__restrict__ hist) {
+                                                   float *__restrict__ W, uint32_t *__restrict__ hist,
+                                                   const uint32_t *__restrict__ pick) {
     extern __shared__ __attribute__((aligned(16))) float lds_lut[];  // [m][k] table, then [kAdcBins] histogram
     const uint32_t q = blockIdx.y, tab = m * k;
     const uint32_t *pq = pref + (size_t)q * (nprobe + 1);
@@ -303,7 +317,7 @@ __global__ __launch_bounds__(256) void k_ivf_rscan(const uint8_t *__restrict__ c
         __syncthreads();
         for (uint32_t pos = a + threadIdx.x; pos < b; pos += 256) {
             float acc[1];  // (topk.hpp's adc_row, the ADC scans' operation order, for one table)
-            adc_row<1>(codes, (uint64_t)sq[slot] + (pos - pq[slot]), m, k, words, lds_lut, 1u, 0u, acc);
+            adc_row<1>(codes, ivf_code_row<Picked>(pick, (uint64_t)sq[slot] + (pos - pq[slot])), m, k, words, lds_lut, 1u, 0u, acc);
             const float dv = acc[0];
             wq[pos] = dv;
             atomicAdd(&lds_hist[adc_bin(dv, lo, scale)], 1u);
@@ -327,10 +341,9 @@ uint32_t ivf_chunk(uint64_t expected_positions) {
 static int ivf_attrs() {
     static PerDeviceOnce attr;
     if (attr.needed()) {
-        VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ivf_scan), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)kAdcFullScanLdsMax));
-        VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ivf_rscan), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)kAdcFullScanLdsMax));
+        for (const void *scan : {reinterpret_cast<const void *>(k_ivf_scan<false>), reinterpret_cast<const void *>(k_ivf_scan<true>),
+                                 reinterpret_cast<const void *>(k_ivf_rscan<false>), reinterpret_cast<const void *>(k_ivf_rscan<true>)})
+            VQ_HIP(hipFuncSetAttribute(scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAdcFullScanLdsMax));
         attr.done();
     }
     return VQHIP_OK;
@@ -339,11 +352,12 @@ static int ivf_attrs() {
 // One batch of nb queries whose probe lists (probe [nb][nprobe], launch_knn_search) and tables (lut [nb][m][k],
 // launch_adc_lut) are on the device.  codes / ids / off: the index in list order.  W [nb][wstride] with wstride >= every
 // |S(q)|; pref [nb][nprobe + 1], seg [nb][nprobe], bounds [nb][2], state >= topk_state_bytes(nb) (zeroed here),
-// cand >= topk_cand_bytes(nb).  Results [nb][topk] on the device.
+// cand >= topk_cand_bytes(nb).  Results [nb][topk] on the device.  pick: a filtered call's (ivf_view.hpp) -- ids / off are
+// then the view's aids / aoff, and position j of that list order is row pick[j] of codes; NULL: every row.
 int launch_ivf_search(const uint8_t *codes, const uint32_t *ids, const uint32_t *off, uint32_t nlist, uint32_t m, uint32_t k, int metric,
                       const float *lut, const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk,
                       uint64_t wstride, float *W, uint32_t *pref, uint32_t *seg, float *bounds, void *state,
-                      unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream) {
+                      unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream, const uint32_t *pick) {
     if (nb == 0) return VQHIP_OK;
     if (nprobe == 0 || nprobe > 1024) return fail(VQHIP_ERR_INVALID_INPUT, "nprobe must be in [1, 1024]");
     if (topk == 0 || topk > 1024) return fail(VQHIP_ERR_INVALID_INPUT, "topk must be in [1, 1024]");
@@ -356,8 +370,8 @@ int launch_ivf_search(const uint8_t *codes, const uint32_t *ids, const uint32_t 
     VQ_LAUNCH_CHECK("k_ivf_plan");
     const uint64_t items = (wstride + chunk - 1) / chunk;
     if (items > 0) {
-        hipLaunchKernelGGL(k_ivf_scan, dim3((uint32_t)items, nb), dim3(256), scan_lds, stream, codes, m, k, lut, pref, seg, nprobe,
-                           bounds, chunk, wstride, W, st.hist);
+        hipLaunchKernelGGL(pick ? k_ivf_scan<true> : k_ivf_scan<false>, dim3((uint32_t)items, nb), dim3(256), scan_lds, stream, codes, m,
+                           k, lut, pref, seg, nprobe, bounds, chunk, wstride, W, st.hist, pick);
         VQ_LAUNCH_CHECK("k_ivf_scan");
     }
     return launch_topk_select(IvfSource{W, wstride, pref, seg, ids, nprobe, bounds}, nb, topk, metric == VQHIP_EUCLIDEAN ? 1 : 0, st, cand,
@@ -377,12 +391,13 @@ uint32_t ivf_rchunk(uint64_t expected_positions, uint32_t k) {
 
 // One batch of nb queries over residual lists: queries [nb][dim] and probe [nb][nprobe] on the device, coarse [nlist][dim]
 // and cb [m][k][sd] the index's.  tabs >= ivf_rtab_bytes(nb, nprobe, m, k), mm >= ivf_rmm_bytes(nb, nprobe); the rest as
-// launch_ivf_search.
+// launch_ivf_search.  Under a view, k_ivf_rlut and k_ivf_rplan see the same aoff: a probe slot without an allowed row
+// gets no table and takes no part in the histogram range.
 int launch_ivf_rsearch(const uint8_t *codes, const uint32_t *ids, const uint32_t *off, const float *coarse, uint32_t nlist,
                        const float *cb, uint32_t m, uint32_t k, uint32_t sd, int metric, const float *queries,
                        const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
                        float *tabs, float *mm, float *W, uint32_t *pref, uint32_t *seg, float *bounds, void *state,
-                       unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream) {
+                       unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream, const uint32_t *pick) {
     if (nb == 0) return VQHIP_OK;
     if (nprobe == 0 || nprobe > 1024) return fail(VQHIP_ERR_INVALID_INPUT, "nprobe must be in [1, 1024]");
     if (topk == 0 || topk > 1024) return fail(VQHIP_ERR_INVALID_INPUT, "topk must be in [1, 1024]");
@@ -400,8 +415,8 @@ int launch_ivf_rsearch(const uint8_t *codes, const uint32_t *ids, const uint32_t
     VQ_LAUNCH_CHECK("k_ivf_rplan");
     const uint64_t items = (wstride + chunk - 1) / chunk;
     if (items > 0) {
-        hipLaunchKernelGGL(k_ivf_rscan, dim3((uint32_t)items, nb), dim3(256), scan_lds, stream, codes, m, k, tabs, pref, seg, nprobe,
-                           bounds, chunk, wstride, W, st.hist);
+        hipLaunchKernelGGL(pick ? k_ivf_rscan<true> : k_ivf_rscan<false>, dim3((uint32_t)items, nb), dim3(256), scan_lds, stream, codes,
+                           m, k, tabs, pref, seg, nprobe, bounds, chunk, wstride, W, st.hist, pick);
         VQ_LAUNCH_CHECK("k_ivf_rscan");
     }
     return launch_topk_select(IvfSource{W, wstride, pref, seg, ids, nprobe, bounds}, nb, topk, metric == VQHIP_EUCLIDEAN ? 1 : 0, st, cand,

@@ -249,7 +249,7 @@ int launch_tsvq_encode_small(const float *rows_dev, uint32_t n, uint32_t d, int 
 int launch_adc_search(const float *cb, uint32_t m, uint32_t k, uint32_t sd, int metric, const uint8_t *codes, uint64_t n,
                       const float *queries_dev, uint32_t nq, uint32_t topk, float *lut_ws, float *dist_ws,
                       void *state_ws, unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev,
-                      hipStream_t stream, uint32_t qgroup);
+                      hipStream_t stream, uint32_t qgroup, const uint32_t *mask = nullptr);
 uint32_t adc_query_batch();
 uint32_t adc_query_group(uint64_t n, uint32_t nq);  // queries that go through one set of launches (a multiple of the batch, all nq, or fewer where 4 n passes 1 GB)
 size_t adc_state_bytes(uint32_t qgroup);
@@ -280,7 +280,8 @@ uint32_t ivf_chunk(uint64_t expected_positions);
 int launch_ivf_search(const uint8_t *codes, const uint32_t *ids, const uint32_t *off, uint32_t nlist, uint32_t m, uint32_t k, int metric,
                       const float *lut, const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk,
                       uint64_t wstride, float *W, uint32_t *pref, uint32_t *seg, float *bounds, void *state,
-                      unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream);
+                      unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream,
+                      const uint32_t *pick = nullptr);
 // the same over residual lists (a row of list l encodes x - C[l]): the tables per (query, probe slot) are built here from
 // the queries, coarse [nlist][dim] and cb [m][k][sd]; tabs [nb][nprobe][m][k], mm [nb][nprobe][2]
 size_t ivf_rtab_bytes(uint32_t qb, uint32_t nprobe, uint32_t m, uint32_t k);
@@ -290,7 +291,8 @@ int launch_ivf_rsearch(const uint8_t *codes, const uint32_t *ids, const uint32_t
                        const float *cb, uint32_t m, uint32_t k, uint32_t sd, int metric, const float *queries,
                        const uint32_t *probe, uint32_t nb, uint32_t nprobe, uint32_t topk, uint32_t chunk, uint64_t wstride,
                        float *tabs, float *mm, float *W, uint32_t *pref, uint32_t *seg, float *bounds, void *state,
-                       unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream);
+                       unsigned long long *cand, uint32_t *idx_out, float *dist_out, hipStream_t stream,
+                       const uint32_t *pick = nullptr);
 // Inverted-file search over list-ordered rows, SQ codes or packed BQ words (k_ivfflat.hip, k_ivfsq.hip, k_ivfbin.hip).
 // One batch of nb <= 1024 queries whose probe lists are on the device, as every stage of it sees it:
 struct IvfBatchView {

@@ -31,6 +31,7 @@ import struct
 import numpy as np
 
 from . import _lib
+from ._resident_common import _allowed
 from ._ivf_common import (MAX_NLIST, MAX_PROBE, MAX_TOPK, PAD_ID, IVFIndexBase, _Reader,  # noqa: F401  (re-exported)
                           _check_distance, _check_file_lists, _check_nlist, _coarse_array, _count, _nearest_lists,
                           _train_coarse)
@@ -175,6 +176,36 @@ class IVFPQIndex(IVFIndexBase):
                 ix.add(self._lists, self._codes)
             self._ix = ix
         return self._ix
+
+    # -- filtered search ----------------------------------------------------------------------
+    def masked_search(self, queries, allowed, topk: int = 10, nprobe: int = 8, *, rerank=None, candidates: int | None = None):
+        """`search` among the allowed rows only.  allowed: one row mask for the call, a bool array (n,) (True: the row may
+        be returned) or its uint32 words (`pack_row_mask`), n being ``len(index)`` at the time of the call.  Probing takes
+        no mask: a query scans its nprobe nearest lists whatever they hold, and a query with fewer than `topk` allowed rows
+        in them has the slots behind them padded with 0xFFFFFFFF / +inf (`topk` itself stays within 1 .. min(n, 1024)).
+        With `rerank`, the mask filters the first stage: the reranker sees allowed rows only."""
+        q = self._queries(queries)
+        p = self._nprobe(nprobe)
+        t = self._topk(topk)
+        w = _allowed(allowed, len(self))
+        if rerank is not None:
+            return self._search_rerank(q, t, p, rerank, candidates, allowed=w)
+        if q.shape[0] == 0:
+            return np.empty((0, t), np.uint32), np.empty((0, t), np.float32)
+        return self._handle().search_masked(q, p, t, w)
+
+    def masked_search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int, dev_allowed: int,
+                             nprobe: int = 8) -> None:
+        """`search_device` among the allowed rows only; `dev_allowed`: the row mask's ceil(n / 32) uint32 words at a device
+        pointer (4-byte aligned)"""
+        p = self._nprobe(nprobe)
+        t = self._topk(topk)
+        n_q = _count(nq, "nq")
+        if n_q < 0 or n_q >= 1 << 32:
+            raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
+        if dev_allowed is None:
+            raise InvalidParameter("dev_allowed", "must be a device pointer, got None")
+        self._handle().search_masked_device(int(dev_queries), n_q, p, t, int(dev_allowed), int(dev_idx), int(dev_dist))
 
     # -- file -------------------------------------------------------------------------------
     def save(self, path) -> None:

@@ -273,20 +273,32 @@ class ProductQuantizer:
             return np.empty((0, self._m), _lib.code_dtype(self._k))
         return self._batch_encoder(X.shape[0]).encode(X, want_codes=True, want_f16=False)[0]
 
-    def search(self, codes, queries, topk: int = 10, *, rerank=None, candidates: int | None = None):
+    def search(self, codes, queries, topk: int = 10, *, rerank=None, candidates: int | None = None, allowed=None):
         """Asymmetric-distance search: the `topk` rows of `codes` (n, m) (uint8, uint16 above 256 centroids)
         nearest to each query under this quantizer's metric, distances from per-subspace tables.
         Returns (indices uint32 (nq, topk), distances float32 (nq, topk)); ties by lower row.
         Tables of m * k <= 38400 entries (one query's table in 150 KiB of LDS); larger ones raise FfiError
         (VQHIP_ERR_UNSUPPORTED).
         rerank: a FlatIndex or a ScalarIndex over the same n rows -- ADC then finds `candidates` rows per query (default
-        4 topk, at most 1024) and the result is their exact top-k under that index's metric (its `rerank`)."""
+        4 topk, at most 1024) and the result is their exact top-k under that index's metric (its `rerank`).
+        allowed: one row mask for the call, a bool array (n,) or its uint32 words (`pack_row_mask`) -- the nearest among the
+        allowed rows only, slots past them padded with 0xFFFFFFFF / +inf; with `rerank` it filters the first stage."""
+        w = None
+        if allowed is not None:
+            from ._resident_common import _allowed
+
+            w = _allowed(allowed, np.asarray(codes).shape[0])
         if rerank is not None:
             from .flat import adc_then_rerank
 
             q = np.ascontiguousarray(queries, dtype=np.float32)
             q = q[None, :] if q.ndim == 1 else q
             n = np.asarray(codes).shape[0]
+            if w is not None:
+                from ._ivf_common import filtered_adc_then_rerank
+
+                return filtered_adc_then_rerank(lambda qq, c: self.search(codes, qq, c, allowed=w), n, self._dim, q, topk, rerank,
+                                                candidates)
             return adc_then_rerank(lambda qq, c: self.search(codes, qq, c), n, self._dim, q, topk, rerank, candidates)
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
@@ -302,7 +314,7 @@ class ProductQuantizer:
             raise InvalidParameter("distance", "cosine distance is not a sum over subspaces: no ADC form")
         if codes.size and int(codes.max()) >= self._k:  # the scan indexes its LDS tables by code
             raise InvalidParameter("codes", f"a code is outside [0, {self._k})")
-        return self._enc.adc_search(codes, q, int(topk))
+        return self._enc.adc_search(codes, q, int(topk), allowed=w)
 
     def decode(self, codes) -> np.ndarray:
         """(n, m) codes -> (n, dim) float32 centroids (un-rounded); row blocks over the quantizer's devices"""

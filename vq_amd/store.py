@@ -132,19 +132,33 @@ class PQIndex:
         """what `ProductQuantizer::quantize` returned for these rows (f16, RNE; src/pq.rs:192-196)"""
         return self.reconstruct(rows).astype(np.float16)
 
-    def search(self, queries, topk: int = 10, *, rerank=None, candidates: int | None = None):
+    def search(self, queries, topk: int = 10, *, rerank=None, candidates: int | None = None, allowed=None):
         """top-k stored rows per query by asymmetric distance (device path; see ProductQuantizer.search, also for
         `rerank` / `candidates`: exact rerank of an ADC short list through a FlatIndex or a ScalarIndex over the same rows).
         Tables of m * k <= 38400 entries (one query's table in 150 KiB of LDS); larger ones raise FfiError
-        (VQHIP_ERR_UNSUPPORTED).  Answers for the current codes, codebooks and distance (see the class)."""
+        (VQHIP_ERR_UNSUPPORTED).  Answers for the current codes, codebooks and distance (see the class).
+        allowed: one row mask for the call, a bool array (n,) (True: the row may be returned) or its uint32 words
+        (`pack_row_mask`) -- the nearest among the allowed rows only; a query with fewer than `topk` of them has the slots
+        behind them padded with 0xFFFFFFFF / +inf (`topk` itself stays within 1 .. min(n, 1024)).  With `rerank`, the mask
+        filters the first stage: its candidates are allowed rows."""
         from . import _lib
         from .errors import DimensionMismatch, InvalidParameter
 
+        w = None
+        if allowed is not None:
+            from ._resident_common import _allowed
+
+            w = _allowed(allowed, len(self))
         if rerank is not None:
             from .flat import adc_then_rerank
 
             q = np.ascontiguousarray(queries, dtype=np.float32)
             q = q[None, :] if q.ndim == 1 else q
+            if w is not None:
+                from ._ivf_common import filtered_adc_then_rerank
+
+                return filtered_adc_then_rerank(lambda qq, c: self.search(qq, c, allowed=w), len(self), self.dim, q, topk, rerank,
+                                                candidates)
             return adc_then_rerank(lambda qq, c: self.search(qq, c), len(self), self.dim, q, topk, rerank, candidates)
 
         q = np.ascontiguousarray(queries, dtype=np.float32)
@@ -163,7 +177,7 @@ class PQIndex:
             enc = _lib.PQEncoder(self.codebooks, self.distance.metric)
             enc.adc_set_codes(np.asarray(self.codes))
             self._enc = enc
-        return enc.adc_search(None, q, int(topk))
+        return enc.adc_search(None, q, int(topk), allowed=w)
 
     # -- file -------------------------------------------------------------------------------
     def save(self, path) -> None:
