@@ -766,6 +766,13 @@ __host__ __device__ constexpr uint32_t x32p_acc_plane_bytes(int nt32) { return (
 __host__ __device__ constexpr uint32_t x32p_acc_bytes_per_wave(int sd, int nt32) {
     return (uint32_t)sd * x32p_acc_plane_bytes(nt32) + 64u + ((uint32_t)nt32 * 32u + 64u) * 4u;
 }
+// Which reduce an instantiation of the pipelined screen runs: the number of column classes of the grid reduce, or 0
+// for the two tagged chains.  Chosen per instantiation from its register count (profiles/NOTES.md, "grid reduce").
+__host__ __device__ constexpr int x32p_grid_cols(int sd, bool acc, int npr, int pvw) {
+    if (npr == 3) return pvw == 2 ? 0 : 8;  // float2 row parts: either grid shape spills 48 bytes against 12
+    if (sd == 8) return acc ? 4 : 8;        // fused update: 8 classes spill 40 bytes against 32, 4 classes 32
+    return 0;                               // sub_dim 16 on six products: one wave, four reduce gaps (not built)
+}
 
 // ---- variant X32P: the X32 kernel software-pipelined across steps -------------------------------------------
 // A lone wave pays an issue slot of ~5 cycles for EVERY instruction, VALU or not (profiles/ubench/valu_issue.hip), so
@@ -782,7 +789,10 @@ __host__ __device__ constexpr uint32_t x32p_acc_bytes_per_wave(int sd, int nt32)
 // steps runs one dummy step whose rows are clamped and whose tail writes nothing).  The arithmetic is the X32 kernel's
 // and the codes are the same bits; since round 4 a lane runs two chains under other tags (reduce_hg) and the encode form
 // shares one tail between two steps (tail_pair_piece), so a row whose gap sits within the tags' 64 ulps of the margin may
-// land on the other side of the test -- in the re-check list or out of it.  launch_one_x32 picks this variant for chunks of at least kPipeMinSteps steps, 8 tiles (k in 225..256),
+// land on the other side of the test -- in the re-check list or out of it.  Instantiations with NC > 0 run the grid
+// reduce instead (reduce_grid / fold_step: plain minima on untagged values, tags on the row and column minima only) and
+// finish a step's per-lane result inside the step; the same holds for rows that close to the margin.
+// launch_one_x32 picks this variant for chunks of at least kPipeMinSteps steps, 8 tiles (k in 225..256),
 // sub_dim 8 or 16, one centroid group.
 // NPR = term pairs per dimension.  6: the three truncated slices above.  3 (sub_dim 16, encode form, squared-L2 /
 // Euclidean): two ROUNDED slices per operand (split2_rne) and the products a1x1 + a2x1 + a1x2 -- MFMA f of a tile carries
@@ -793,7 +803,8 @@ __host__ __device__ constexpr uint32_t x32p_acc_bytes_per_wave(int sd, int nt32)
 // more rows in the exact re-check, which settles every code either way.  Slices that round to +-inf (|v| > 3.39e38)
 // leave inf - inf = NaN in the second slice: the row's values are NaN and it goes to the list like any non-finite row.
 // PVW > 0 (NPR = 3 only): the data's sub_dim is sdr < SD, loaded in parts of PVW floats, zeros behind (see the X32 kernel).
-template <int SD, int NT32, bool ACC = false, int NPR = 6, int PVW = 0>
+// NC = column classes of the grid reduce (reduce_grid below): 8 or 4; 0 keeps the two tagged chains (reduce_hg).
+template <int SD, int NT32, bool ACC = false, int NPR = 6, int PVW = 0, int NC = x32p_grid_cols(SD, ACC, NPR, PVW)>
 __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void k_assign_screen_bf16_x32p(
     const float *__restrict__ X, uint64_t n, uint32_t d, uint32_t m, const uint32_t *__restrict__ prepA32,
     const float *__restrict__ prepCn, uint32_t cn_stride, const float *__restrict__ meta,
@@ -1131,6 +1142,100 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
             }
         }
     };
+    // Grid reduce (NC > 0).  The 128 values a lane sees in a step (8 tiles x 16 elements, all of ONE row of X) form a
+    // grid: column class c = e & (NC - 1), row class rt = (16 / NC) tile + e / NC.  Plain minima run on the UNTAGGED
+    // values, one v_min3 per two new values: cm[c] over the step (NC chains, tile 0 starts them), and one minimum per
+    // row class, consumed at once.  Only those minima take a tag and enter a (minimum, second minimum) chain: the row
+    // minima under rt in (rq1, rq2), tile by tile, and the column minima under ct(c) = 8 (c >> 2) + (c & 3) once per
+    // step (fold_step).  The smallest value sits at (r*, c*), the second smallest s at (r', c') != (r*, c*): if r' != r* it is
+    // the minimum of row r' and the second smallest row minimum, else c' != c* and it is the second smallest column
+    // minimum; either chain's second minimum is a value of the grid other than the winner, so min(rq2, cq2) = s, and
+    // the winner is read off the two chains' tags: centroid 32 tile + 8 (e >> 2) + 4 h + (e & 3) = (rt << (NC == 8 ? 4 : 3)) + ct
+    // + 4 h.  When the minimum is not unique beyond the tags' perturbation the chains may name different cells -- the gap
+    // is then within the perturbation the margin budgets and the row goes to the re-check.  All values
+    // NaN: the untagged minima keep the +inf they start from, and a tagged +inf is a NaN pattern -- the lane's minimum is
+    // +inf or NaN and |m1| <= 3e38 fails either way.  (A row class of +inf next to finite values could drop the row chain's
+    // minimum through such a NaN; a value overflows only where (|x| + cmax)^2 does, and the test's T <= 3e38 lists the row.)
+    // Two-operand minima are written as v_min3 / v_med3 against +inf: the compiler canonicalises the operands of a
+    // v_min_f32 (a v_max x, x each).
+    static_assert(NC == 0 || ((NC == 8 || NC == 4) && NMF == 3), "grid reduce: 8 or 4 column classes, two reduce gaps per phase");
+    float cm[NC > 0 ? NC : 1];
+    float rq1 = 0.0f, rq2 = 0.0f;
+    float p_m1 = pinf, p_m2 = pinf;  // the finished step's per-lane result, parked until its tail runs
+    uint32_t p_j = 0;
+    auto med3 = [](float x, float y, float z) { return __builtin_amdgcn_fmed3f(x, y, z); };
+    auto tagged = [&](float v, uint32_t tag) { return __uint_as_float((__float_as_uint(v) & idx_mask) | tag); };
+    // half hf of finished tile ifin, in the gap behind MFMA hf of the phase
+    auto reduce_grid = [&](const f32x16 &fin, int ifin, int hf) {
+        if constexpr (NC == 8) {
+#pragma unroll
+            for (int c = 4 * hf; c < 4 * hf + 4; ++c) {
+                cm[c] = ifin == 0 ? min3(fin[c], fin[c + 8], pinf) : min3(cm[c], fin[c], fin[c + 8]);
+                asm volatile("" ::"v"(cm[c]));
+            }
+            float r = min3(fin[8 * hf], fin[8 * hf + 1], fin[8 * hf + 2]);
+            r = min3(r, fin[8 * hf + 3], fin[8 * hf + 4]);
+            r = min3(r, fin[8 * hf + 5], fin[8 * hf + 6]);
+            r = min3(r, fin[8 * hf + 7], pinf);
+            const float pr = tagged(r, (uint32_t)(2 * ifin + hf));
+            if (hf == 0) {
+                ta[0] = pr;
+                asm volatile("" ::"v"(ta[0]));
+            } else {
+                const float t = med3(ifin == 0 ? pinf : rq1, ta[0], pr);
+                rq1 = min3(ifin == 0 ? pinf : rq1, ta[0], pr);
+                rq2 = ifin == 0 ? t : min3(rq2, t, pinf);
+                asm volatile("" ::"v"(rq1), "v"(rq2));
+            }
+        } else if constexpr (NC == 4) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                cm[c] = (ifin == 0 && hf == 0) ? min3(fin[c], fin[c + 4], pinf) : min3(cm[c], fin[8 * hf + c], fin[8 * hf + 4 + c]);
+                asm volatile("" ::"v"(cm[c]));
+            }
+            float pr[2];
+#pragma unroll
+            for (int w = 0; w < 2; ++w) {
+                float r = min3(fin[8 * hf + 4 * w], fin[8 * hf + 4 * w + 1], fin[8 * hf + 4 * w + 2]);
+                r = min3(r, fin[8 * hf + 4 * w + 3], pinf);
+                pr[w] = tagged(r, (uint32_t)(4 * ifin + 2 * hf + w));
+            }
+            const bool fresh = ifin == 0 && hf == 0;
+            const float t = med3(fresh ? pinf : rq1, pr[0], pr[1]);
+            rq1 = min3(fresh ? pinf : rq1, pr[0], pr[1]);
+            if (hf == 0) {
+                ta[0] = t;
+                asm volatile("" ::"v"(rq1), "v"(ta[0]));
+            } else {
+                rq2 = min3(ifin == 0 ? pinf : rq2, ta[0], t);
+                asm volatile("" ::"v"(rq1), "v"(rq2));
+            }
+        }
+    };
+    const uint32_t h4 = 4 * h;
+    // the step's column minima into their chain, the two chains into the lane's (minimum, second minimum, centroid)
+    auto fold_step = [&]() {
+        if constexpr (NC > 0) {
+            float pc[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) pc[c] = tagged(cm[c], (uint32_t)(8 * (c >> 2) + (c & 3)));
+            float c1 = min3(pc[0], pc[1], pinf), c2 = med3(pc[0], pc[1], pinf);
+            float t1 = med3(c1, pc[2], pc[3]);
+            c1 = min3(c1, pc[2], pc[3]);
+            if constexpr (NC == 8) {
+                const float t2 = med3(c1, pc[4], pc[5]);
+                c1 = min3(c1, pc[4], pc[5]);
+                c2 = min3(c2, t1, t2);
+                t1 = med3(c1, pc[6], pc[7]);
+                c1 = min3(c1, pc[6], pc[7]);
+            }
+            p_m2 = min3(c2, t1, rq2);
+            p_m1 = rq1;
+            const uint32_t cj = (__float_as_uint(c1) & 11u) | h4;
+            p_j = ((__float_as_uint(rq1) & (NC == 8 ? 15u : 31u)) << (NC == 8 ? 4 : 3)) | cj;
+            asm volatile("" ::"v"(p_m1), "v"(p_m2), "v"(p_j));
+        }
+    };
     float t_m1 = 0.0f, t_m2 = 0.0f, t_xs = 0.0f;
     uint32_t t_j = 0;
     bool t_proven = false;
@@ -1290,7 +1395,9 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
     };
     // tail of a finished step in 4 pieces (the X32 kernel's tail, same order of operations)
     auto tail_piece = [&](int k, int tp, uint32_t tst, bool in_loop, bool no_step = false) {
-        if (k == 0) {
+        if (k == 0 && NC > 0) {
+            t_m1 = p_m1, t_m2 = p_m2, t_j = p_j;  // merged inside the step itself (fold_step)
+        } else if (k == 0) {
             // the lane's two chains -> (minimum, second minimum, centroid): element e = 4 tag[2:1] + 2 tag[0] + chain of
             // tile tag[5:3] is centroid 32 tile + 8 (e >> 2) + 4 h + (e & 3)
             const float a1 = q1[tp][0], a2 = q2[tp][0], b1 = q1[tp][1], b2 = q2[tp][1];
@@ -1477,9 +1584,14 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
                             }
                         }
                     } else {  // NMF == 3: one filler gap per phase
-                        if (f == 0) reduce_hg(acc[i & 3], i, 0, par), reduce_hg(acc[i & 3], i, 1, par);
-                        if (f == 1) reduce_hg(acc[i & 3], i, 2, par), reduce_hg(acc[i & 3], i, 3, par);
+                        if constexpr (NC > 0) {
+                            if (f < 2) reduce_grid(acc[i & 3], i, f);
+                        } else {
+                            if (f == 0) reduce_hg(acc[i & 3], i, 0, par), reduce_hg(acc[i & 3], i, 1, par);
+                            if (f == 1) reduce_hg(acc[i & 3], i, 2, par), reduce_hg(acc[i & 3], i, 3, par);
+                        }
                         if (f == 2) {
+                            if (i == NT32 - 1) fold_step();  // before tile 0 of the next step starts cm and the row chain again
                             if (i == 0) {
                                 if constexpr (kAccPair) { if (par == VQ_ACC_RELOAD_PAR) acc_reload_pair(st - VQ_ACC_RELOAD_PAR); }
                                 else acc_reload(st - 1);
