@@ -5,8 +5,15 @@ arguments, the data, the queries and a list of operations to run in order.  The 
 round-robin (every supported pair appears by construction); everything else is drawn.  A draw that would be an invalid call
 (topk > rows so far, nprobe > nlist, ...) is clamped here, so a case is a valid call by construction.
 
-`statement_search`, `statement_range`, `statement_rerank` and `dense_statement` dispatch a case to the numpy statements of
-tests/ref_*.py.  They make no arithmetic of their own.
+`draw_filtered(family, seed)` is the same case under other ops, drawn from a generator of its own (draw's stream is
+untouched; tests/golden/fuzz_search_draws_digests.json holds it): at least half of its query ops are the filtered searches,
+range searches and reranks and the Hamming-radius range searches (NEW_OPS), every filtered op with a row mask over the rows
+present at that op -- its kind one of MASK_KINDS, handed over in one of FORMS -- and some directly after close() or
+save / load.
+
+`statement_search`, `statement_range`, `statement_rerank` and `dense_statement`, and for the new ops
+`statement_filtered_search`, `statement_filtered_range`, `statement_hamming_range` and their dense forms, dispatch a case to
+the numpy statements of tests/ref_*.py.  They make no arithmetic of their own.
 """
 import zlib
 from dataclasses import dataclass
@@ -14,13 +21,18 @@ from dataclasses import dataclass
 import numpy as np
 
 import ref_binary as B
+import ref_binary_filter as BF
+import ref_binary_range as BR
+import ref_filter as RF
 import ref_ivf as I
+import ref_ivf_filter as RIF
 import ref_ivf_range as IRG
 import ref_ivf_residual as IRES
 import ref_ivfbin as IB
 import ref_ivfflat as IFL
 import ref_ivfsq as ISQ
 import ref_knn as K
+import ref_pq_filter as RPF
 import ref_range as RG
 import ref_sqbq as S
 import ref_sqindex as SI
@@ -97,7 +109,10 @@ def _op_text(o) -> str:
     if o["op"] == "add":
         return f"{o['how']}[{o['lo']}:{o['n']}]"
     extra = "".join(f" {k}={o[k]}" for k in ("candidates", "flat_metric") if k in o)
-    return f"{o['op']}(n={o['n']} topk={o['topk']}{extra})" if "topk" in o else f"{o['op']}(n={o['n']})"
+    if "mask" in o:  # a filtered op: the mask's kind, the form it is handed over in and the number of allowed rows
+        extra += f" mask={o['mask_kind']} form={o['form']} allowed={o['allowed']}"
+    extra += "".join(f" {k}" for k in ("after_close", "after_load") if o.get(k))
+    return f"{o['op']}(n={o['n']} topk={o['topk']}{extra})" if "topk" in o else f"{o['op']}(n={o['n']}{extra})"
 
 
 def seeds(family, scale=1):
@@ -148,23 +163,28 @@ def _draw_queries(rng, nq, dim, kind, row, coarse=None, lists=None):
     return np.ascontiguousarray(Q, F)
 
 
+def _query_op(rng, case, qops, n_now):
+    o = {"op": str(rng.choice(qops)), "n": n_now, "topk": min(case.topk, n_now)}
+    if o["op"] == "range_search":
+        del o["topk"]
+        o["radius"] = _draw_radius(rng, case, n_now)
+    if o["op"] == "rerank_search":
+        _draw_rerank(rng, o, n_now)
+    return o
+
+
+def _draw_rerank(rng, o, n_now):
+    t = o["topk"]
+    cap = min(n_now, 1024)
+    o["candidates"] = int(rng.choice([t, min(4 * t, cap), int(rng.integers(t, cap + 1))]))
+    o["flat_metric"] = int(rng.integers(0, 5))
+
+
 def _draw_ops(rng, case):
     """3 to 7 operations; an IVF family adds its rows in 1 to 3 uneven slices with queries between"""
     fam, n = case.family, case.n
     qops = QUERY_OPS[fam]
     ops = []
-
-    def query_op(n_now):
-        o = {"op": str(rng.choice(qops)), "n": n_now, "topk": min(case.topk, n_now)}
-        if o["op"] == "range_search":
-            del o["topk"]
-            o["radius"] = _draw_radius(rng, case, n_now)
-        if o["op"] == "rerank_search":
-            t = o["topk"]
-            cap = min(n_now, 1024)
-            o["candidates"] = int(rng.choice([t, min(4 * t, cap), int(rng.integers(t, cap + 1))]))
-            o["flat_metric"] = int(rng.integers(0, 5))
-        return o
 
     if fam in IVF:
         pieces = min(n, int(rng.choice([1, 2, 3])))
@@ -172,13 +192,13 @@ def _draw_ops(rng, case):
         for i in range(pieces):
             ops.append({"op": "add", "lo": cuts[i], "n": cuts[i + 1], "how": str(rng.choice(case.ctor["adds"]))})
             if i + 1 < pieces and rng.random() < 0.7:
-                ops.append(query_op(cuts[i + 1]))
+                ops.append(_query_op(rng, case, qops, cuts[i + 1]))
         room = 7 - len(ops)
         for _ in range(max(3 - len(ops), int(rng.integers(1, room + 1)))):
-            ops.append(query_op(n))
+            ops.append(_query_op(rng, case, qops, n))
     else:
         for _ in range(int(rng.integers(3, 8))):
-            ops.append(query_op(n))
+            ops.append(_query_op(rng, case, qops, n))
     return ops
 
 
@@ -404,7 +424,7 @@ def dense_statement_range(case: Case, n: int, radius):
 
 def rerank_rows(case: Case, n: int) -> np.ndarray:
     """the f32 rows of the exact index a rerank_search goes through"""
-    return (case.data["rows"] if case.family in ("binary", "ivfbin") else case.data["rerank_rows"])[:n]
+    return (case.data["rows"] if case.family in ("binary", "ivfbin", "ivfsq") else case.data["rerank_rows"])[:n]
 
 
 def statement_rerank(case: Case, n: int, hits, topk: int, flat_metric: int):
@@ -428,3 +448,274 @@ def probed_rows(case: Case, n: int) -> np.ndarray:
     P = I.probe(case.coarse_metric, case.data["coarse"], case.queries, case.nprobe)
     sizes = np.bincount(lists, minlength=case.nlist)
     return sizes[P.astype(np.int64)].sum(axis=1)
+
+
+# -- the second draw: the filtered and the Hamming-range calls ----------------------------------------------------------------
+FILTER_WORD = 0x46494C54  # the third seed word of draw_filtered's generator: draw()'s own stream never sees it
+NEW_OPS = {
+    "flat": ("filtered_search", "filtered_range_search"),
+    "scalar": ("filtered_search", "filtered_range_search"),
+    "binary": ("hamming_range_search", "filtered_search", "filtered_hamming_range_search", "filtered_rerank_search"),
+    "pq": ("filtered_search", "filtered_rerank_search"),
+    "ivfpq": ("filtered_search", "filtered_rerank_search"),
+    "ivfflat": ("filtered_search", "filtered_range_search"),
+    "ivfsq": ("filtered_search", "filtered_range_search", "filtered_rerank_search"),
+    "ivfbin": ("hamming_range_search", "filtered_search", "filtered_hamming_range_search", "filtered_rerank_search"),
+}
+FILTERED = ("filtered_search", "filtered_range_search", "filtered_hamming_range_search", "filtered_rerank_search")
+MASK_KINDS = ("ones", "zeros", "one_row", "random", "block64", "block", "all_but_few", "fewer_than_topk", "without_winners",
+              "higher_twins")
+RARE_KINDS = ("fewer_than_topk", "higher_twins", "one_list")  # not on every op: topk >= 2, the whole set, an IVF family
+FORMS = ("bool", "words", "ids", "words_tail")
+HAS_SAVE = tuple(f for f in FAMILIES if "save_load_search" in QUERY_OPS[f])
+
+
+def mask_kinds(family):
+    return MASK_KINDS + (("one_list",) if family in IVF else ())
+
+
+def _applies(case, kind, n_now, topk) -> bool:
+    if kind == "fewer_than_topk":
+        return topk >= 2
+    if kind == "higher_twins":  # the duplicates _plant / the code rows make sit at the end of the whole set
+        return n_now == case.n >= 2 and not case.dense_cut
+    return True
+
+
+def _draw_mask(rng, case, kind, n_now, topk) -> np.ndarray:
+    """bool (n_now,): the allowed rows of one filtered op"""
+    m = np.zeros(n_now, np.bool_)
+    if kind == "ones":
+        m[:] = True
+    elif kind == "one_row":
+        m[int(rng.choice([0, n_now - 1, int(rng.integers(0, n_now))]))] = True
+    elif kind == "random":
+        m = rng.random(n_now) < min(1.0, float(rng.choice([0.5, 0.03, 3 / n_now])))
+    elif kind == "block64":  # a run of whole 64-row groups (the last one as far as the rows go)
+        groups = (n_now + 63) // 64
+        a = int(rng.integers(0, groups))
+        m[64 * a:min(64 * int(rng.integers(a + 1, groups + 1)), n_now)] = True
+    elif kind == "block":
+        lo = int(rng.integers(0, n_now))
+        m[lo:int(rng.integers(lo + 1, n_now + 1))] = True
+    elif kind == "all_but_few":
+        few = int(rng.integers(1, 6))
+        if case.dense_cut:  # all but three rows are tied: more than 8192 of them stay allowed
+            few = min(few, max(1, case.n - 3 - 8193))
+        m[:] = True
+        m[rng.choice(n_now, min(few, n_now), replace=False)] = False
+    elif kind == "fewer_than_topk":
+        m[rng.choice(n_now, int(rng.integers(1, topk)), replace=False)] = True
+    elif kind == "without_winners":  # a kernel that ignored the mask would return exactly the rows left out
+        winners = statement_search(case, n_now, min(topk, 4))[0]
+        m[:] = True
+        m[winners[winners != I.PAD_ID].astype(np.int64)] = False
+    elif kind == "higher_twins":  # of every duplicate pair only the higher id: the distance bits stay, the id changes
+        m[:] = True
+        m[:7 if n_now >= 14 else 1] = False
+    elif kind == "one_list":
+        lists = case.data["lists"][:n_now]
+        live = np.unique(lists)
+        P = I.probe(case.coarse_metric, case.data["coarse"], case.queries, case.nprobe)
+        probing = np.array([int((P == l).any(axis=1).sum()) for l in live])  # the queries that probe each list with rows
+        some = live[(probing > 0) & (probing < case.nq)]
+        if some.size and rng.random() < 0.75:  # probed by some queries only: the others come back all padding
+            live = some
+        m = lists == live[int(rng.integers(0, live.size))]
+    elif kind != "zeros":
+        raise ValueError(kind)
+    return m
+
+
+def _draw_hamming_radius(rng, case, n_now):
+    """per-query integer radii from the case's own k-th Hamming distances; query 0 (equal to a duplicated row) gets 0: the
+    exact bit match and its duplicate; the last query `dim`: every row; with 17 queries or more, the one before it dim + 7"""
+    H = B.hamming(B.pack(B.bits_f32(case.queries, case.ctor["bq"][0])), case.data["words"][:n_now])
+    k = int(rng.integers(1, min(n_now, 40) + 1))
+    r = np.sort(H, axis=1)[:, k - 1].astype(np.int64)
+    r[0] = 0
+    if case.nq >= 2:
+        r[-1] = case.dim
+    if case.nq >= 17:
+        r[-2] = case.dim + 7
+    return r
+
+
+def _new_op(rng, case, name, n_now, nth):
+    """one of NEW_OPS over the first n_now rows; nth: how many filtered ops the case holds already -- the first two take
+    their mask kind round-robin from the seed, a dense-cut case the two kinds that reach the dense cut"""
+    fam, seed = case.family, case.seed
+    topk = min(case.topk, n_now)
+    o = {"op": name, "n": n_now}
+    if name in ("filtered_search", "filtered_rerank_search"):
+        o["topk"] = topk
+    if name == "filtered_rerank_search":
+        _draw_rerank(rng, o, n_now)
+    if name == "filtered_range_search":
+        o["radius"] = _draw_radius(rng, case, n_now)
+    if name.endswith("hamming_range_search"):
+        o["hradius"] = _draw_hamming_radius(rng, case, n_now)
+    if name not in FILTERED:
+        return o
+    kinds = mask_kinds(fam)
+    if case.dense_cut and nth < 2:
+        kind = ("all_but_few", ("without_winners", "random")[seed % 2])[nth]
+    elif nth < 2:
+        kind = kinds[(2 * seed + nth) % len(kinds)]
+    else:  # (the kinds that do not always apply are drawn more often where they do)
+        w = np.array([3.0 if k in RARE_KINDS else 1.0 for k in kinds])
+        kind = str(rng.choice(kinds, p=w / w.sum()))
+    if not _applies(case, kind, n_now, topk):
+        rare = [k for k in RARE_KINDS if k in kinds]
+        rare = rare[seed % len(rare):] + rare[:seed % len(rare)]
+        kind = next(k for k in rare + ["ones"] if _applies(case, k, n_now, topk))
+    mask = _draw_mask(rng, case, kind, n_now, topk)
+    o.update(mask_kind=kind, form=str(rng.choice(FORMS)), mask=mask, allowed=int(mask.sum()))
+    if o["form"] == "ids":
+        o["ids"] = rng.permutation(np.flatnonzero(mask)).astype(np.int64)
+    close = fam in IVF and (rng.random() < 0.12 or (nth == 0 and seed % 4 == 1))
+    load = fam in HAS_SAVE and (rng.random() < 0.12 or (nth == 0 and seed % 4 == 3))
+    if close:
+        o["after_close"] = True  # close() directly before: the filtered call is the first the fresh handle sees
+    elif load:
+        o["after_load"] = True   # save / load directly before: the filtered call goes to the loaded index, its first
+    return o
+
+
+def _draw_filtered_ops(rng, case):
+    """the length rules of _draw_ops; at least half of the query ops are NEW_OPS, the others the family's QUERY_OPS"""
+    fam, n, seed = case.family, case.n, case.seed
+    shape = []  # an add, or the number of rows a query op sees
+    if fam in IVF:
+        pieces = min(n, int(rng.choice([1, 2, 3])))
+        cuts = [0] + sorted(int(c) for c in rng.choice(np.arange(1, n), pieces - 1, replace=False)) + [n]
+        for i in range(pieces):
+            shape.append({"op": "add", "lo": cuts[i], "n": cuts[i + 1], "how": str(rng.choice(case.ctor["adds"]))})
+            if i + 1 < pieces and rng.random() < 0.7:
+                shape.append(cuts[i + 1])
+        room = 7 - len(shape)
+        shape += [n] * max(3 - len(shape), int(rng.integers(1, room + 1)))
+    else:
+        shape = [n] * int(rng.integers(3, 8))
+    slots = [i for i, s in enumerate(shape) if not isinstance(s, dict)]
+    new = {int(i) for i in rng.choice(slots, int(rng.integers((len(slots) + 1) // 2, len(slots) + 1)), replace=False)}
+    ops, nth_new, nth_filtered = [], 0, 0
+    for i, s in enumerate(shape):
+        if isinstance(s, dict):
+            ops.append(s)
+        elif i not in new:
+            ops.append(_query_op(rng, case, QUERY_OPS[fam], s))
+        else:
+            names = NEW_OPS[fam]
+            name = names[seed % len(names)] if nth_new == 0 else str(rng.choice(names))
+            if case.dense_cut and nth_filtered < 2 and name not in FILTERED:
+                name = "filtered_search"
+            ops.append(_new_op(rng, case, name, s, nth_filtered))
+            nth_new += 1
+            nth_filtered += name in FILTERED
+    return ops
+
+
+def draw_filtered(family: str, seed: int) -> Case:
+    """draw(family, seed) with its ops replaced: the same index, rows and queries under the filtered and the Hamming-range
+    calls, every filtered op with a mask of its own over the rows present at that op"""
+    case = draw(family, seed)
+    rng = np.random.default_rng([zlib.crc32(family.encode()), int(seed), FILTER_WORD])
+    case.ops = _draw_filtered_ops(rng, case)
+    return case
+
+
+# -- the statement a filtered op is held to -----------------------------------------------------------------------------------
+def _qwords(case):
+    return B.pack(B.bits_f32(case.queries, case.ctor["bq"][0]))
+
+
+def statement_filtered_search(case: Case, n: int, topk: int, mask):
+    """statement_search among the allowed rows: mask bool (n,)"""
+    c, d, Q, metric = case.ctor, case.data, case.queries, case.metric
+    fam = case.family
+    if fam == "flat":
+        return RF.search(metric, Q, d["stored"][:n].astype(F), topk, mask)
+    if fam == "scalar":
+        return RF.sq_search(metric, Q, c["sq"], d["codes"][:n], topk, mask)
+    if fam == "binary":
+        thr, low, high = c["bq"]
+        return BF.search(_qwords(case), d["words"][:n], case.dim, low, high, metric, topk, mask)
+    if fam == "pq":
+        return RPF.brute_dense_search(metric, d["codebooks"], d["codes"][:n], Q, topk, mask)
+    if fam == "ivfpq":
+        ref = RPF.brute_residual_search if c["residual"] else RPF.brute_search
+        return ref(metric, d["coarse"], d["codebooks"], d["lists"][:n], d["codes"][:n], Q, case.nprobe, topk, mask)
+    if fam == "ivfflat":
+        return RIF.search(metric, d["coarse"], d["lists"][:n], d["stored"][:n], Q, case.nprobe, topk, mask)
+    if fam == "ivfsq":
+        return RIF.sq_search(metric, d["coarse"], d["lists"][:n], c["sq"], d["codes"][:n], Q, case.nprobe, topk, mask)
+    if fam == "ivfbin":
+        return BF.ivf_search(metric, case.coarse_metric, d["coarse"], d["lists"][:n], c["bq"], d["words"][:n], case.dim, Q,
+                             case.nprobe, topk, mask)
+    raise ValueError(fam)
+
+
+def dense_statement_filtered(case: Case, n: int, topk: int, mask):
+    """the filtered statement of the resident index over the same first n rows: an IVF case's own at nprobe == nlist
+    (None for the residual IVFPQ index, which has no resident twin)"""
+    c, d, Q, metric = case.ctor, case.data, case.queries, case.metric
+    if case.family == "ivfflat":
+        return RF.search(metric, Q, d["stored"][:n].astype(F), topk, mask)
+    if case.family == "ivfsq":
+        return RF.sq_search(metric, Q, c["sq"], d["codes"][:n], topk, mask)
+    if case.family == "ivfbin":
+        thr, low, high = c["bq"]
+        return BF.search(_qwords(case), d["words"][:n], case.dim, low, high, metric, topk, mask)
+    if case.family == "ivfpq":
+        return None if c["residual"] else RPF.brute_dense_search(metric, d["codebooks"], d["codes"][:n], Q, topk, mask)
+    raise ValueError(case.family)
+
+
+def statement_filtered_range(case: Case, n: int, radius, mask):
+    """statement_range in which only allowed rows hit"""
+    c, d, Q, metric = case.ctor, case.data, case.queries, case.metric
+    if case.family == "flat":
+        return RF.range_search(metric, Q, d["stored"][:n].astype(F), radius, mask)
+    if case.family == "scalar":
+        return RF.sq_range_search(metric, Q, c["sq"], d["codes"][:n], radius, mask)
+    if case.family == "ivfflat":
+        return RIF.range_search(metric, d["coarse"], d["lists"][:n], d["stored"][:n], Q, case.nprobe, radius, mask)
+    if case.family == "ivfsq":
+        return RIF.sq_range_search(metric, d["coarse"], d["lists"][:n], c["sq"], d["codes"][:n], Q, case.nprobe, radius, mask)
+    raise ValueError(case.family)
+
+
+def dense_statement_filtered_range(case: Case, n: int, radius, mask):
+    c, d, Q, metric = case.ctor, case.data, case.queries, case.metric
+    if case.family == "ivfflat":
+        return RF.range_search(metric, Q, d["stored"][:n].astype(F), radius, mask)
+    if case.family == "ivfsq":
+        return RF.sq_range_search(metric, Q, c["sq"], d["codes"][:n], radius, mask)
+    raise ValueError(case.family)
+
+
+def statement_hamming_range(case: Case, n: int, hradius, mask=None, dense=False):
+    """(lims, idx, dist) of a Hamming-radius range search over the first n rows, among the allowed rows with a mask;
+    dense: the resident index's statement for an IVFBinaryIndex case"""
+    c, d = case.ctor, case.data
+    thr, low, high = c["bq"]
+    if case.family == "binary" or (dense and case.family == "ivfbin"):
+        if mask is None:
+            return BR.search(_qwords(case), d["words"][:n], case.dim, low, high, case.metric, hradius)
+        return BF.range_search(_qwords(case), d["words"][:n], case.dim, low, high, case.metric, hradius, mask)
+    if case.family == "ivfbin":
+        front = (case.metric, case.coarse_metric, d["coarse"], d["lists"][:n], c["bq"], d["words"][:n], case.dim, case.queries,
+                 case.nprobe, hradius)
+        return BR.ivf_search(*front) if mask is None else BF.ivf_range_search(*front, mask)
+    raise ValueError(case.family)
+
+
+def allowed_in_reach(case: Case, n: int, mask) -> np.ndarray:
+    """(nq,) the number of allowed rows a query can return: those of its probed lists (ref_ivf_filter.allowed_members), of a
+    resident index all of them"""
+    if case.family in DENSE:
+        return np.full(case.nq, int(np.count_nonzero(mask)), np.int64)
+    lists = case.data["lists"][:n]
+    P = I.probe(case.coarse_metric, case.data["coarse"], case.queries, case.nprobe)
+    return np.array([RIF.allowed_members(lists, P[j], mask).size for j in range(case.nq)], np.int64)
