@@ -679,7 +679,32 @@ inline std::vector<std::uint32_t> pack_row_mask(const std::vector<bool> &allowed
     return w;
 }
 
+// Removing rows (include/vqhip.h, "adding and removing rows"): the mask of a removal from row ids in [0, n), in any order,
+// repeats welcome -- true: the row is removed.
+inline std::vector<bool> remove_mask(const std::vector<std::uint32_t> &ids, std::size_t n) {
+    std::vector<bool> m(n, false);
+    for (std::uint32_t i : ids) {
+        if (i >= n) throw VqError::InvalidParameter("ids", "row id " + std::to_string(i) + " is outside [0, n)");
+        m[i] = true;
+    }
+    return m;
+}
+
 namespace detail {
+// the argument checks of an add and of a removal, before the library is called: the rows in all stay below 2^32; the
+// mask has n entries and leaves a row -- returns the old ids of the rows it leaves, in their new order
+inline void check_room(std::size_t n, std::size_t b) {
+    if (b >= (std::size_t(1) << 32) || n + b >= (std::size_t(1) << 32))
+        throw VqError::InvalidParameter("rows", "at most 2^32 - 1 rows in all");
+}
+inline std::vector<std::uint32_t> kept_rows(const std::vector<bool> &remove, std::size_t n) {
+    if (remove.size() != n) throw VqError::DimensionMismatch(n, remove.size());
+    std::vector<std::uint32_t> kept;
+    for (std::size_t i = 0; i < n; ++i)
+        if (!remove[i]) kept.push_back((std::uint32_t)i);
+    if (kept.empty()) throw VqError::InvalidParameter("remove", "would leave no row; an index holds at least one");
+    return kept;
+}
 // the argument checks of a filtered call, before the library is called: the mask's pointer; its length as a vector
 inline void check_row_mask(const std::uint32_t *allowed) {
     if (!allowed) throw VqError::InvalidParameter("allowed", "the row mask is null");
@@ -712,7 +737,8 @@ inline RangeResult read_range(vqhip_range *raw) {
 namespace detail {
 // What the resident indexes share over their C handles (H and its destroy / search): the shape, the handle, and a search,
 // whose arguments are the same for every kind of row.  The arguments are checked before the device is touched.
-template <class H, int (*Destroy)(H *), int (*Search)(H *, const float *, std::uint32_t, std::uint32_t, std::uint32_t *, float *)>
+template <class H, int (*Destroy)(H *), int (*Search)(H *, const float *, std::uint32_t, std::uint32_t, std::uint32_t *, float *),
+          int (*Remove)(H *, const std::uint32_t *, std::uint64_t *), int (*RemoveDevice)(H *, const std::uint32_t *, std::uint64_t *)>
 class ResidentIndex {
    public:
     std::size_t size() const { return n_; }
@@ -737,8 +763,44 @@ class ResidentIndex {
         return search(queries.data(), queries.size() / dim_, topk);
     }
 
+    // Adding and removing rows (include/vqhip.h, "adding and removing rows"): after any sequence of them every call
+    // returns bit for bit what a fresh index over the remaining rows returns.  The arguments are checked before the device
+    // is touched; adding no rows and removing none do not touch it.  Each class has its own add forms.
+    // remove_rows: `remove` [n], true: the row goes (or row ids, through remove_mask).  The other rows keep their order and
+    // move up; returns the old ids of the remaining rows in their new order.  Removing every row is refused.
+    std::vector<std::uint32_t> remove_rows(const std::vector<bool> &remove) {
+        std::vector<std::uint32_t> kept = kept_rows(remove, n_);
+        if (kept.size() == n_) return kept;
+        const std::vector<std::uint32_t> words = pack_row_mask(remove);
+        std::uint64_t gone = 0;
+        check(Remove(ix_.get(), words.data(), &gone));
+        n_ = kept.size();
+        return kept;
+    }
+    std::vector<std::uint32_t> remove_rows(const std::vector<std::uint32_t> &ids) { return remove_rows(remove_mask(ids, n_)); }
+    // the mask's ceil(n / 32) words at a device pointer (4-byte aligned; bit set: remove); returns the rows removed
+    std::size_t remove_rows_device(const std::uint32_t *dev_remove_words) {
+        if (!dev_remove_words) throw VqError::InvalidParameter("remove", "the mask is null");
+        std::uint64_t gone = 0;
+        check(RemoveDevice(ix_.get(), dev_remove_words, &gone));
+        n_ -= (std::size_t)gone;
+        return (std::size_t)gone;
+    }
+
    protected:
     ResidentIndex() = default;
+    // b rows through call(handle): their ids n .. n + b - 1
+    template <class F>
+    std::vector<std::uint32_t> append(const void *src, std::size_t b, F &&call) {
+        check_room(n_, b);
+        std::vector<std::uint32_t> ids(b);
+        if (b == 0) return ids;
+        if (!src) throw VqError::InvalidParameter("rows", "the source is null");
+        check(call(ix_.get()));
+        for (std::size_t i = 0; i < b; ++i) ids[i] = (std::uint32_t)(n_ + i);
+        n_ += b;
+        return ids;
+    }
     // the shape checks of an index of any dimension (BinaryIndex has a bound on it, and its own)
     static void check_shape(std::size_t n, std::size_t dim) {
         if (n == 0) throw VqError::EmptyInput();
@@ -765,9 +827,10 @@ template <class H, int (*Destroy)(H *), int (*Search)(H *, const float *, std::u
           int (*Range)(H *, const float *, std::uint32_t, const float *, std::uint64_t, vqhip_range **),
           int (*Rerank)(H *, const float *, std::uint32_t, const std::uint32_t *, std::uint32_t, std::uint32_t, std::uint32_t *, float *),
           int (*SearchMasked)(H *, const float *, std::uint32_t, std::uint32_t, const std::uint32_t *, std::uint32_t *, float *),
-          int (*RangeMasked)(H *, const float *, std::uint32_t, const float *, std::uint64_t, const std::uint32_t *, vqhip_range **)>
-class ExactResidentIndex : public ResidentIndex<H, Destroy, Search> {
-    using Base = ResidentIndex<H, Destroy, Search>;
+          int (*RangeMasked)(H *, const float *, std::uint32_t, const float *, std::uint64_t, const std::uint32_t *, vqhip_range **),
+          int (*Remove)(H *, const std::uint32_t *, std::uint64_t *), int (*RemoveDevice)(H *, const std::uint32_t *, std::uint64_t *)>
+class ExactResidentIndex : public ResidentIndex<H, Destroy, Search, Remove, RemoveDevice> {
+    using Base = ResidentIndex<H, Destroy, Search, Remove, RemoveDevice>;
 
    public:
     using Result = typename Base::Result;
@@ -843,7 +906,8 @@ class ExactResidentIndex : public ResidentIndex<H, Destroy, Search> {
 // by the constructor; search / rerank give (row index, distance) pairs [nq][topk], nearest first, NaN last, ties to the
 // lower row.  The arguments are checked before the device is touched.
 class FlatIndex : public detail::ExactResidentIndex<vqhip_flat, vqhip_flat_destroy, vqhip_flat_search, vqhip_flat_range_search, vqhip_flat_rerank,
-                                                    vqhip_flat_search_masked, vqhip_flat_range_search_masked> {
+                                                    vqhip_flat_search_masked, vqhip_flat_range_search_masked, vqhip_flat_remove,
+                                                    vqhip_flat_remove_device> {
    public:
     FlatIndex(const float *rows, std::size_t n, std::size_t dim, Distance distance = Distance()) {
         init(rows, 0, n, dim, distance);
@@ -851,10 +915,24 @@ class FlatIndex : public detail::ExactResidentIndex<vqhip_flat, vqhip_flat_destr
     FlatIndex(const f16 *rows, std::size_t n, std::size_t dim, Distance distance = Distance()) {
         init(rows, 1, n, dim, distance);
     }
+    bool half() const { return dtype_ == 1; }
+    // append b rows [b][dim] in the index's own element type (the other one is refused); returns their ids n .. n + b - 1
+    std::vector<std::uint32_t> add(const float *rows, std::size_t b) { return add_as(rows, 0, b); }
+    std::vector<std::uint32_t> add(const f16 *rows, std::size_t b) { return add_as(rows, 1, b); }
+    // the same from a device pointer to rows of the index's element type
+    std::vector<std::uint32_t> add_device(const void *dev_rows, std::size_t b) {
+        return append(dev_rows, b, [&](vqhip_flat *f) { return vqhip_flat_add_device(f, dev_rows, b); });
+    }
 
    private:
+    std::vector<std::uint32_t> add_as(const void *rows, int dtype, std::size_t b) {
+        if (dtype != dtype_) throw VqError::InvalidParameter("rows", dtype_ ? "the index holds f16 rows" : "the index holds f32 rows");
+        return append(rows, b, [&](vqhip_flat *f) { return vqhip_flat_add(f, rows, b); });
+    }
+    int dtype_ = 0;
     void init(const void *rows, int dtype, std::size_t n, std::size_t dim, Distance distance) {
         check_shape(n, dim);
+        dtype_ = dtype;
         vqhip_flat *f = nullptr;
         detail::check(vqhip_flat_create(rows, n, (std::uint32_t)dim, dtype, (int)distance.kind(), &f));
         adopt(f, n, dim, distance);
@@ -866,7 +944,8 @@ class FlatIndex : public detail::ExactResidentIndex<vqhip_flat, vqhip_flat_destr
 // dequantized vectors; (row id, distance) pairs [nq][topk], nearest first, ties to the lower row.  The queries are
 // binarised by the index's quantizer on the device.  Cosine and every other bad argument are refused before the device
 // is touched.
-class BinaryIndex : public detail::ResidentIndex<vqhip_binary, vqhip_binary_destroy, vqhip_binary_search> {
+class BinaryIndex : public detail::ResidentIndex<vqhip_binary, vqhip_binary_destroy, vqhip_binary_search, vqhip_binary_remove,
+                                                 vqhip_binary_remove_device> {
    public:
     enum class Source { Rows = VQHIP_BINARY_F32, Codes = VQHIP_BINARY_U8, Packed = VQHIP_BINARY_PACKED };
     BinaryIndex(const float *rows, std::size_t n, std::size_t dim, BinaryQuantizer quantizer = BinaryQuantizer(0.0f, 0, 1),
@@ -947,8 +1026,30 @@ class BinaryIndex : public detail::ResidentIndex<vqhip_binary, vqhip_binary_dest
         detail::check(vqhip_binary_packed(ix_.get(), out.data()));
         return out;
     }
+    // append b rows in one of the constructors' three forms -- f32 rows [b][dim], u8 codes [b][dim], packed words
+    // [b][words_per_row()] with the pad bits zero -- from host memory, or from a device pointer (f32 rows and words 4-byte
+    // aligned; a pad bit set there is an FfiError that leaves the index as it was); returns their ids n .. n + b - 1
+    std::vector<std::uint32_t> add(const float *rows, std::size_t b) { return add_from(rows, Source::Rows, b, false); }
+    std::vector<std::uint32_t> add_codes(const std::uint8_t *codes, std::size_t b) { return add_from(codes, Source::Codes, b, false); }
+    std::vector<std::uint32_t> add_packed(const std::uint32_t *words, std::size_t b) {
+        if (words) check_pad(words, b, dim_);
+        return add_from(words, Source::Packed, b, false);
+    }
+    std::vector<std::uint32_t> add_device(const void *dev_src, Source kind, std::size_t b) { return add_from(dev_src, kind, b, true); }
 
    private:
+    static void check_pad(const std::uint32_t *words, std::size_t n, std::size_t dim) {
+        if (dim % 32 == 0) return;
+        const std::size_t w = (dim + 31) / 32;
+        const std::uint32_t mask = (1u << (dim % 32)) - 1u;
+        for (std::size_t i = 0; i < n; ++i)
+            if (words[i * w + w - 1] & ~mask) throw VqError::InvalidParameter("words", "a row has a pad bit set");
+    }
+    std::vector<std::uint32_t> add_from(const void *src, Source kind, std::size_t b, bool device) {
+        return append(src, b, [&](vqhip_binary *h) {
+            return device ? vqhip_binary_add_device(h, src, (int)kind, b) : vqhip_binary_add(h, src, (int)kind, b);
+        });
+    }
     void init(const void *src, Source kind, std::size_t n, std::size_t dim, Distance distance) {
         if (n == 0) throw VqError::EmptyInput();
         if (dim == 0 || dim > VQHIP_BINARY_MAX_DIM) throw VqError::InvalidParameter("dim", "must be between 1 and 8192");
@@ -956,13 +1057,7 @@ class BinaryIndex : public detail::ResidentIndex<vqhip_binary, vqhip_binary_dest
         if (distance.kind() != Distance::SquaredEuclidean && distance.kind() != Distance::Euclidean &&
             distance.kind() != Distance::Manhattan)
             throw VqError::InvalidParameter("distance", "must be squared_euclidean, euclidean or manhattan");
-        if (kind == Source::Packed && dim % 32) {
-            const std::size_t w = (dim + 31) / 32;
-            const std::uint32_t mask = (1u << (dim % 32)) - 1u;
-            for (std::size_t i = 0; i < n; ++i)
-                if (static_cast<const std::uint32_t *>(src)[i * w + w - 1] & ~mask)
-                    throw VqError::InvalidParameter("words", "a row has a pad bit set");
-        }
+        if (kind == Source::Packed) check_pad(static_cast<const std::uint32_t *>(src), n, dim);
         vqhip_binary *b = nullptr;
         detail::check(vqhip_binary_create(src, (int)kind, n, (std::uint32_t)dim, quantizer_.threshold(), quantizer_.low(),
                                           quantizer_.high(), (int)distance.kind(), &b));
@@ -977,7 +1072,8 @@ class BinaryIndex : public detail::ResidentIndex<vqhip_binary, vqhip_binary_dest
 // nearest first, NaN last, ties to the lower row.  The arguments are checked before the device is touched.
 class ScalarIndex
     : public detail::ExactResidentIndex<vqhip_sqindex, vqhip_sqindex_destroy, vqhip_sqindex_search, vqhip_sqindex_range_search, vqhip_sqindex_rerank,
-                                        vqhip_sqindex_search_masked, vqhip_sqindex_range_search_masked> {
+                                        vqhip_sqindex_search_masked, vqhip_sqindex_range_search_masked, vqhip_sqindex_remove,
+                                        vqhip_sqindex_remove_device> {
    public:
     ScalarIndex(const float *rows, std::size_t n, std::size_t dim, ScalarQuantizer quantizer, Distance distance = Distance())
         : quantizer_(quantizer) {
@@ -993,6 +1089,20 @@ class ScalarIndex
         std::vector<std::uint8_t> out(n_ * dim_);
         detail::check(vqhip_sqindex_codes(ix_.get(), out.data()));
         return out;
+    }
+    // append b rows: f32 rows [b][dim], encoded on the device as the constructor encodes them, or u8 codes [b][dim] as they
+    // are; from host memory or a device pointer (f32 rows 4-byte aligned).  Returns their ids n .. n + b - 1.
+    std::vector<std::uint32_t> add(const float *rows, std::size_t b) {
+        return append(rows, b, [&](vqhip_sqindex *x) { return vqhip_sqindex_add_rows(x, rows, b); });
+    }
+    std::vector<std::uint32_t> add_device(const void *dev_rows, std::size_t b) {
+        return append(dev_rows, b, [&](vqhip_sqindex *x) { return vqhip_sqindex_add_rows_device(x, dev_rows, b); });
+    }
+    std::vector<std::uint32_t> add_codes(const std::uint8_t *codes, std::size_t b) {
+        return append(codes, b, [&](vqhip_sqindex *x) { return vqhip_sqindex_add_codes(x, codes, b); });
+    }
+    std::vector<std::uint32_t> add_codes_device(const void *dev_codes, std::size_t b) {
+        return append(dev_codes, b, [&](vqhip_sqindex *x) { return vqhip_sqindex_add_codes_device(x, dev_codes, b); });
     }
 
    private:

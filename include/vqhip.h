@@ -709,6 +709,51 @@ int vqhip_binary_range_search_masked_device(vqhip_binary *b, const void *dev_que
  * of a workgroup's histogram carries.  Workgroup x scans rows [x * slice, min(n, (x + 1) * slice)). */
 uint64_t vqhip_binary_masked_slice(uint64_t n, uint32_t groups);
 
+/* ---- adding and removing rows: the flat, the scalar and the binary index (k_compact.hip, compact.hpp) ----
+ * No reference counterpart.  An index is a sequence of rows R[0 .. n).
+ *   add(B), b >= 1 rows   R' = R ++ B: the new rows get the ids n .. n + b - 1.  What is stored for a new row is exactly
+ *                         what create stores for it: a flat index its bytes (in the index's own dtype), a scalar index its
+ *                         codes as given (add_codes) or the codes of the SQ encode rule, made on the device as
+ *                         vqhip_sqindex_create_rows makes them (add_rows), a binary index its packed bits from f32 rows, u8
+ *                         codes or packed words (`kind`, as in vqhip_binary_create; the pad-bit check of create applies to
+ *                         the added words, in the host and the device form).  Under the cosines the new rows' norms come
+ *                         from the launcher create uses, run over the appended slice.  n + b must stay below 2^32, else
+ *                         VQHIP_ERR_INVALID_INPUT.  n_add == 0 is VQHIP_OK and needs no device (only the handle is checked).
+ *   remove(S)             S is a mask of ceil(n / 32) u32 words: row i is removed iff bit i & 31 of word i >> 5 is set, bits
+ *                         at or past n ignored (the row mask's layout, with the other meaning).  R' is R without those rows,
+ *                         the order kept: a surviving row i becomes row i - |{s in S : s < i}|.  *removed = the number of
+ *                         rows removed.  Removing nothing changes nothing and allocates no payload (the host form does not
+ *                         touch the device for it).  Removing every row is VQHIP_ERR_INVALID_INPUT, since an index holds at
+ *                         least one row, and leaves the index as it was.
+ * INVARIANT: after any sequence of adds and removes, every call on the index -- search, its masked form, range search and
+ * its masked form, rerank, codes / packed, info -- returns bit for bit what a fresh index created from R' returns; the
+ * bounds on topk and the length of a row mask follow the current n.
+ * A call that fails (the allocation, the pad-bit check, the bound on n) leaves the index unchanged: the new buffer is
+ * allocated first and swapped in behind the last step that can fail.
+ * Threads and streams: these entry points take the handle's lock and order the caller's stream behind the handle's queued
+ * work like every other call on it.  They may free the old payload, so they synchronise their stream before they free and
+ * return synchronised: a search_device queued earlier on another stream completes on the old rows.  They allocate, so
+ * they cannot be captured into a graph.
+ * Memory: the payload grows geometrically -- a full buffer is replaced by one of max(needed, 1.5 x capacity) bytes -- so a
+ * sequence of small adds copies O(total) bytes.  A removal compacts out of place into an allocation sized for the
+ * survivors (peak: old + new) and frees the old buffer, which gives the memory back.
+ * rows / codes / src / remove_words: HOST memory in the host forms, DEVICE pointers in the _device forms (f32 rows, packed
+ * words and the remove mask 4-byte aligned, else VQHIP_ERR_INVALID_INPUT); NULL is VQHIP_ERR_NULL_PTR. */
+int vqhip_flat_add(vqhip_flat *f, const void *rows, uint64_t n_add);
+int vqhip_flat_add_device(vqhip_flat *f, const void *dev_rows, uint64_t n_add);
+int vqhip_flat_remove(vqhip_flat *f, const uint32_t *remove_words, uint64_t *removed);
+int vqhip_flat_remove_device(vqhip_flat *f, const uint32_t *dev_remove_words, uint64_t *removed);
+int vqhip_sqindex_add_codes(vqhip_sqindex *x, const uint8_t *codes, uint64_t n_add);
+int vqhip_sqindex_add_codes_device(vqhip_sqindex *x, const void *dev_codes, uint64_t n_add);
+int vqhip_sqindex_add_rows(vqhip_sqindex *x, const float *rows, uint64_t n_add);
+int vqhip_sqindex_add_rows_device(vqhip_sqindex *x, const void *dev_rows, uint64_t n_add);
+int vqhip_sqindex_remove(vqhip_sqindex *x, const uint32_t *remove_words, uint64_t *removed);
+int vqhip_sqindex_remove_device(vqhip_sqindex *x, const uint32_t *dev_remove_words, uint64_t *removed);
+int vqhip_binary_add(vqhip_binary *b, const void *src, int kind, uint64_t n_add);
+int vqhip_binary_add_device(vqhip_binary *b, const void *dev_src, int kind, uint64_t n_add);
+int vqhip_binary_remove(vqhip_binary *b, const uint32_t *remove_words, uint64_t *removed);
+int vqhip_binary_remove_device(vqhip_binary *b, const uint32_t *dev_remove_words, uint64_t *removed);
+
 /* ---- inverted-file PQ index: search only the probed lists (k_ivf.hip) -----------------------
  * No reference counterpart.  An index holds coarse centroids C [nlist][dim] f32 (1 <= nlist <= 65536), PQ codebooks
  * cb [m][k][sub_dim] (dim = m * sub_dim) and a metric: squared Euclidean, Euclidean or Manhattan (cosine is refused with

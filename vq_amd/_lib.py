@@ -197,6 +197,20 @@ SIGNATURES = {
     "vqhip_binary_range_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint64, _u32p, _vpp]),
     "vqhip_binary_range_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, _u32p, C.c_uint64, _vp, _vpp]),
     "vqhip_binary_masked_slice": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+    "vqhip_flat_add": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "vqhip_flat_add_device": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "vqhip_flat_remove": (C.c_int, [_vp, _u32p, _u64p]),
+    "vqhip_flat_remove_device": (C.c_int, [_vp, _vp, _u64p]),
+    "vqhip_sqindex_add_codes": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "vqhip_sqindex_add_codes_device": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "vqhip_sqindex_add_rows": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "vqhip_sqindex_add_rows_device": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "vqhip_sqindex_remove": (C.c_int, [_vp, _u32p, _u64p]),
+    "vqhip_sqindex_remove_device": (C.c_int, [_vp, _vp, _u64p]),
+    "vqhip_binary_add": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64]),
+    "vqhip_binary_add_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64]),
+    "vqhip_binary_remove": (C.c_int, [_vp, _u32p, _u64p]),
+    "vqhip_binary_remove_device": (C.c_int, [_vp, _vp, _u64p]),
     "vqhip_ivfbin_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p]),
     "vqhip_ivfbin_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "vqhip_ivfbin_range_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint64, _u32p, _vpp]),
@@ -914,6 +928,25 @@ class _ResidentHandle(Handle):
     def search_device(self, dev_queries: int, nq: int, topk: int, dev_idx: int, dev_dist: int):
         check(self._fn("search_device")(self.raw, C.c_void_p(dev_queries), int(nq), int(topk), C.c_void_p(dev_idx),
                                         C.c_void_p(dev_dist)))
+
+    # adding and removing rows; `self.n` follows every call
+    def add(self, name: str, src, n_add: int, *front):
+        """entry point `name` ("add", "add_codes_device", ...): `src` a C-contiguous host array or a device pointer (an
+        int), `front` what the entry point takes between the source and the count (the binary index's kind)"""
+        p = C.c_void_p(src) if isinstance(src, int) else src.ctypes.data_as(_vp)
+        check(self._fn(name)(self.raw, p, *front, int(n_add)))
+        self.n += int(n_add)
+
+    def remove(self, words) -> int:
+        """`words`: the remove mask uint32 (ceil(n / 32),) on the host, or a device pointer (an int) to it; returns the
+        number of rows removed"""
+        removed = C.c_uint64(0)
+        if isinstance(words, int):
+            check(self._fn("remove_device")(self.raw, C.c_void_p(words), C.byref(removed)))
+        else:
+            check(self._fn("remove")(self.raw, ptr(words, _u32p), C.byref(removed)))
+        self.n -= int(removed.value)
+        return int(removed.value)
 
 
 class _ResidentMaskedCalls:

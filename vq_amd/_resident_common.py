@@ -224,6 +224,88 @@ class ResidentIndex:
         n_q = _nq(nq)
         self._index().search_device(int(dev_queries), n_q, k, int(dev_idx), int(dev_dist))
 
+    # -- adding and removing rows (include/vqhip.h, "adding and removing rows") ----------------
+    # After any sequence of these, every call on the index returns bit for bit what a fresh index over the remaining rows
+    # returns.  A mutation first puts the index on the device (there is no host-side twin of the rows); every argument
+    # is checked before that, and a call that adds or removes nothing does not touch the device.  They allocate and
+    # return synchronised, so they cannot be captured into a graph.
+
+    def _add_form(self):
+        """(the entry point of ``add``, the dtype of its rows, what it passes between the source and the count) -- a
+        subclass's"""
+        raise NotImplementedError
+
+    def _room(self, b: int, what: str) -> None:
+        if self._n + b >= 1 << 32:
+            raise InvalidParameter(what, f"at most 2^32 - 1 rows in all, got {self._n} + {b}")
+
+    def _added(self, a, dtype, what: str, width: int | None = None) -> np.ndarray:
+        """the checks of a host array (b, width) of `dtype` that an add appends (`width`: the dimension by default)"""
+        a = a if isinstance(a, np.ndarray) else np.asarray(a)
+        if a.dtype != dtype:
+            raise InvalidParameter(what, f"dtype must be {np.dtype(dtype).name}, got {a.dtype}")
+        if a.ndim != 2:
+            raise ValueError(f"expected a 2D array (n, {'dim' if width is None else 'words'})")
+        w = self._dim if width is None else width
+        if a.shape[1] != w:
+            raise DimensionMismatch(w, a.shape[1])
+        self._room(a.shape[0], what)
+        return np.ascontiguousarray(a)
+
+    def _append(self, name: str, src, b: int, *front) -> np.ndarray:
+        """b rows from `src` (a checked host array, or a device pointer) through entry point `name`; their ids"""
+        if b == 0:
+            return np.empty(0, np.uint32)
+        self._index().add(name, src, b, *front)
+        ids = np.arange(self._n, self._n + b, dtype=np.uint32)
+        self._n += b
+        return ids
+
+    def _append_device(self, name: str, dev_src: int, n, *front) -> np.ndarray:
+        b = _count(n, "n")
+        if b < 0:
+            raise InvalidParameter("n", f"must be at least 0, got {b}")
+        self._room(b, "n")
+        return self._append(name, int(dev_src), b, *front)
+
+    def add(self, rows) -> np.ndarray:
+        """append `rows` (b, dim), in the dtype the index was built from rows of; returns their ids uint32 (b,): n .. n +
+        b - 1.  What is stored is what the constructor stores for the same rows."""
+        name, dtype, front = self._add_form()
+        a = self._added(rows, dtype, "rows")
+        return self._append(name, a, a.shape[0], *front)
+
+    def add_device(self, dev_rows: int, n: int) -> np.ndarray:
+        """``add`` with the rows [n][dim] at a device pointer (4-byte aligned, but for float16 rows); returns their ids"""
+        name, _, front = self._add_form()
+        return self._append_device(name + "_device", dev_rows, n, *front)
+
+    def remove_rows(self, mask_or_ids) -> np.ndarray:
+        """remove the rows of a bool mask (n,) -- True: remove -- or of an integer array of row ids in [0, n), in any
+        order, repeats welcome.  The remaining rows keep their order and move up: returns `kept` uint32, the old ids of
+        the remaining rows in their new order (``kept[new id] = old id``), for the caller's side tables.  Removing every
+        row is refused: an index holds at least one."""
+        a = np.asarray(mask_or_ids)
+        if a.size == 0 and a.ndim == 1 and a.dtype != np.bool_:
+            a = a.astype(np.int64)  # (an empty list of ids)
+        words = pack_row_mask(a, self._n)
+        gone = np.unpackbits(words.view(np.uint8), bitorder="little")[:self._n].astype(bool)
+        kept = np.flatnonzero(~gone).astype(np.uint32)
+        if kept.shape[0] == 0:
+            raise InvalidParameter("mask_or_ids", f"would leave no row of {self._n}; an index holds at least one")
+        if kept.shape[0] == self._n:
+            return kept
+        self._index().remove(words)
+        self._n = int(kept.shape[0])
+        return kept
+
+    def remove_rows_device(self, dev_remove: int) -> int:
+        """``remove_rows`` with the mask's ceil(n / 32) uint32 words at a device pointer (4-byte aligned; bit set:
+        remove); returns the number of rows removed.  A mask of every row is an FfiError (ERR_INVALID_INPUT)."""
+        removed = self._index().remove(int(dev_remove))
+        self._n -= removed
+        return removed
+
 
 class ExactResidentIndex(ResidentIndex):
     """a ResidentIndex whose distances are exact (FlatIndex, ScalarIndex): range search, the rerank of candidates, and

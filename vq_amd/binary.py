@@ -125,6 +125,27 @@ class BinaryIndex(BinaryFilterMixin, ResidentIndex):
         q = self._quantizer
         return _lib.Binary(self._src, self._kind, self._n, self._dim, q.threshold, q.low, q.high, self._distance.metric)
 
+    def _add_form(self):
+        return "add", np.float32, (_lib.BINARY_F32,)  # float32 rows, binarised on the device by the quantizer's rule
+
+    def add_codes(self, codes) -> np.ndarray:
+        """append u8 BQ codes (b, dim), bit = code >= high (``from_codes``'s form); returns their ids uint32 (b,)"""
+        a = self._added(codes, np.uint8, "codes")
+        return self._append("add", a, a.shape[0], _lib.BINARY_U8)
+
+    def add_packed(self, words) -> np.ndarray:
+        """append packed rows uint32 (b, ceil(dim / 32)) in the index layout, pad bits zero (``from_packed``'s form);
+        returns their ids uint32 (b,)"""
+        a = self._added(words, np.uint32, "words", words_per_row(self._dim))
+        if not _pad_ok(a, self._dim):
+            raise InvalidParameter("words", f"a row has a pad bit (dimension >= {self._dim}) set")
+        return self._append("add", a, a.shape[0], _lib.BINARY_PACKED)
+
+    def add_packed_device(self, dev_words: int, n: int) -> np.ndarray:
+        """``add_packed`` with the words [n][ceil(dim / 32)] at a device pointer (4-byte aligned); a pad bit set is an
+        FfiError (ERR_INVALID_INPUT) that leaves the index as it was.  Returns their ids."""
+        return self._append_device("add_device", dev_words, n, _lib.BINARY_PACKED)
+
     def search(self, queries, topk: int = 10, *, rerank=None, candidates=None):
         """(nq, d) float32 queries -> (indices uint32 (nq, topk), distances float32 (nq, topk)), nearest first.
         rerank: a FlatIndex or a ScalarIndex over the same rows -- the binary search gives `candidates` per query

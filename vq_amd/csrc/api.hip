@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "adc_plan.hpp"
+#include "compact.hpp"
 #include "kernels.hpp"
 
 namespace vqhip {
@@ -2798,6 +2799,7 @@ struct Resident {
     uint32_t d = 0;
     int metric = VQHIP_EUCLIDEAN;
     DevBuf q, cand, idx, out;  // per-call workspaces
+    DevBuf compact_ws;         // a removal's block counts and starts (k_compact.hip)
     uint32_t width() const { return d; }     // floats of a query
     int on_device() { return VQHIP_OK; }     // (the rows stay where create put them: no device of its own to check)
 };
@@ -2814,6 +2816,7 @@ struct ExactResident : Resident {
     const uint32_t *mask = nullptr;  // the row mask of the filtered call that holds the lock (MaskScope), NULL otherwise
 
     size_t mask_bytes() const { return (size_t)((n + 31) / 32) * 4; }
+    DevBuf *norm_buf() { return vq_is_cos(metric) ? &rnorm : nullptr; }
     // a host form's mask, ceil(n / 32) words, up into mask_ws
     int stage_mask(const uint32_t *allowed, hipStream_t s) {
         VQ_TRY(mask_ws.ensure(mask_bytes()));
@@ -2918,6 +2921,7 @@ static int host_search(Entry &in, hipStream_t s, DevBuf &q, DevBuf &idx, DevBuf 
 template <class H, class C, class F>
 static int resident_enter(H *h, bool args, C &&checks, uint32_t nq, const void *dev_queries, F &&body) {
     if (!h || !args) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    std::lock_guard<std::recursive_mutex> held(h->sync.mu);  // `checks` reads n, which an add or a removal on another thread changes
     VQ_TRY(checks());
     if (nq == 0) return VQHIP_OK;
     if (reinterpret_cast<uintptr_t>(dev_queries) & 3) return fail(VQHIP_ERR_INVALID_INPUT, "queries are not 4-byte aligned");
@@ -3005,11 +3009,118 @@ static int exact_rerank(T *x, const float *queries, uint32_t nq, const uint32_t 
     });
 }
 
+// ------------------------------------------------------------------ adding and removing rows (k_compact.hip) ----
+// include/vqhip.h, "adding and removing rows"; DESIGN.md section 26.  What a handle T offers for it: payload() (the DevBuf
+// of its rows, whose `bytes` is the capacity), row_bytes(), norm_buf() (rnorm under the cosines, else NULL) and
+// norms_enqueue(rows, count, out), the launcher its create uses over `count` rows.
+static void swap_buf(DevBuf &a, DevBuf &b) {
+    std::swap(a.p, b.p);
+    std::swap(a.bytes, b.bytes);
+}
+
+// Room for `total` rows of rb bytes where cur holds n: cur itself where its capacity reaches, else `grown`, a new buffer
+// of max(needed, 1.5 x capacity) bytes with the n rows copied in (queued on s).  *base: row 0 of whichever it is.
+static int grow_rows(DevBuf &cur, uint64_t n, uint64_t total, size_t rb, DevBuf &grown, char **base, hipStream_t s) {
+    const size_t need = (size_t)total * rb;
+    if (cur.p && cur.bytes >= need) {
+        *base = cur.as<char>();
+        return VQHIP_OK;
+    }
+    VQ_TRY(grown.alloc(std::max(need, cur.bytes + (cur.bytes + 1) / 2)));
+    VQ_HIP(hipMemcpyAsync(grown.p, cur.p, (size_t)n * rb, hipMemcpyDeviceToDevice, s));
+    *base = grown.as<char>();
+    return VQHIP_OK;
+}
+
+// R' = R ++ B: store(dst, s) writes the payload of the n_add new rows at dst (device memory behind row n - 1) and is the
+// last step that can fail; n, the payload and the norms change behind it.
+template <class T, class Store>
+static int resident_add(T *x, const void *src, uint64_t n_add, Store &&store) {
+    if (!x) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (n_add == 0) return VQHIP_OK;
+    auto checks = [&]() -> int {
+        if (n_add >= (1ull << 32) || x->n + n_add >= (1ull << 32))
+            return fail(VQHIP_ERR_INVALID_INPUT, "n + n_add = %llu + %llu must stay below 2^32", (unsigned long long)x->n,
+                        (unsigned long long)n_add);
+        return VQHIP_OK;
+    };
+    return resident_enter(x, src != nullptr, checks, 1, nullptr, [&](Entry &in, hipStream_t s) -> int {
+        const uint64_t n = x->n, total = n + n_add;
+        const size_t rb = x->row_bytes();
+        DevBuf grown, grown_norm;  // (freed here where the call fails)
+        char *base = nullptr, *nbase = nullptr;
+        DevBuf *norm = x->norm_buf();
+        int rc = grow_rows(x->payload(), n, total, rb, grown, &base, s);
+        if (rc == VQHIP_OK && norm) rc = grow_rows(*norm, n, total, 4, grown_norm, &nbase, s);
+        if (rc == VQHIP_OK) rc = store(base + n * rb, s);
+        if (rc == VQHIP_OK && norm) rc = x->norms_enqueue(base + n * rb, n_add, reinterpret_cast<float *>(nbase) + n, s);
+        // the old buffers are freed below and a failed call frees the grown ones: nothing may still run on either
+        const hipError_t e = hipStreamSynchronize(s);
+        in.synced();
+        VQ_TRY(rc);
+        VQ_HIP(e);
+        if (grown.p) swap_buf(x->payload(), grown);
+        if (grown_norm.p) swap_buf(*norm, grown_norm);
+        x->n = total;
+        return VQHIP_OK;
+    });
+}
+
+// R' = R without the rows of the mask `remove` (ceil(n / 32) words; host: staged into mask_ws), the order kept
+template <class T>
+static int resident_remove(T *x, const uint32_t *remove, bool host, uint64_t *removed) {
+    if (!x || !remove || !removed) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    *removed = 0;
+    std::lock_guard<std::recursive_mutex> held(x->sync.mu);
+    if (host) {  // what the device would count: an empty removal and one of every row end here, without a device
+        uint64_t kept = 0;
+        for (uint64_t w = 0; w < (x->n + 31) / 32; ++w) kept += compact_popc32(compact_keep_word(remove[w], w, x->n));
+        if (kept == x->n) return VQHIP_OK;
+        if (kept == 0) return fail(VQHIP_ERR_INVALID_INPUT, "the removal would leave no row (n = %llu)", (unsigned long long)x->n);
+    } else {
+        VQ_TRY(check_mask_aligned(remove));
+    }
+    return resident_enter(x, true, no_checks, 1, nullptr, [&](Entry &in, hipStream_t s) -> int {
+        const uint64_t n = x->n;
+        const size_t rb = x->row_bytes();
+        const uint32_t *mask = remove;
+        if (host) {
+            VQ_TRY(x->stage_mask(remove, s));
+            mask = x->mask_ws.template as<uint32_t>();
+        }
+        VQ_TRY(x->compact_ws.ensure(compact_ws_bytes(n)));
+        VQ_TRY(launch_compact_plan(mask, n, x->compact_ws.p, s));
+        uint32_t na = 0;
+        VQ_HIP(hipMemcpyAsync(&na, compact_survivors(x->compact_ws.p, n), 4, hipMemcpyDeviceToHost, s));
+        VQ_HIP(hipStreamSynchronize(s));
+        in.synced();
+        if (na == n) return VQHIP_OK;
+        if (na == 0) return fail(VQHIP_ERR_INVALID_INPUT, "the removal would leave no row (n = %llu)", (unsigned long long)n);
+        DevBuf rows, norms;  // sized for the survivors; the old buffers leave with them
+        DevBuf *norm = x->norm_buf();
+        VQ_TRY(rows.alloc((size_t)na * rb));
+        if (norm) VQ_TRY(norms.alloc((size_t)na * 4));
+        int rc = launch_compact_move(mask, n, x->compact_ws.p, x->payload().p, rows.p, rb, s);
+        if (rc == VQHIP_OK && norm) rc = launch_compact_move(mask, n, x->compact_ws.p, norm->p, norms.p, 4, s);
+        const hipError_t e = hipStreamSynchronize(s);  // before either side is freed
+        VQ_TRY(rc);
+        VQ_HIP(e);
+        swap_buf(x->payload(), rows);
+        if (norm) swap_buf(*norm, norms);
+        x->n = na;
+        *removed = n - na;
+        return VQHIP_OK;
+    });
+}
+
 // ------------------------------------------------------------------ exact k-NN (k_knn.hip) ----
 struct vqhip_flat : ExactResident<vqhip_flat> {
     int dtype = 0;
-    DevBuf rows;  // [n][d] f32 or f16 bits
+    DevBuf rows;  // [n][d] f32 or f16 bits; `bytes` is the capacity (an add grows it)
 
+    DevBuf &payload() { return rows; }
+    size_t row_bytes() const { return (size_t)d * (dtype == 1 ? 2 : 4); }
+    int norms_enqueue(const void *X, uint64_t count, float *out, hipStream_t s) { return launch_knn_norms(X, dtype, count, d, out, s); }
     int launch_search(const float *queries_dev, const float *qn, uint32_t nq, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
                       hipStream_t s) {
         return launch_knn_search(metric, rows.p, dtype, n, d, rnorm.as<float>(), queries_dev, qn, nq, topk, dist.as<float>(), state.p,
@@ -3052,6 +3163,14 @@ static int flat_create(const void *src, hipMemcpyKind kind, uint64_t n, uint32_t
     VQ_HIP(hipStreamSynchronize(s));  // the caller may free or change its rows once this returns
     *out = f.release();
     return VQHIP_OK;
+}
+
+// n_add rows in the index's dtype, from host (kind = H2D) or device (D2D) memory, behind the last row
+static int flat_add(vqhip_flat *f, const void *src, hipMemcpyKind kind, uint64_t n_add) {
+    return resident_add(f, src, n_add, [&](char *dst, hipStream_t s) -> int {
+        VQ_HIP(hipMemcpyAsync(dst, src, (size_t)n_add * f->row_bytes(), kind, s));
+        return VQHIP_OK;
+    });
 }
 
 extern "C" {
@@ -3115,14 +3234,43 @@ int vqhip_flat_rerank(vqhip_flat *f, const float *queries, uint32_t nq, const ui
     VQ_API_END
 }
 
+int vqhip_flat_add(vqhip_flat *f, const void *rows, uint64_t n_add) {
+    VQ_API_BEGIN
+    return flat_add(f, rows, hipMemcpyHostToDevice, n_add);
+    VQ_API_END
+}
+
+int vqhip_flat_add_device(vqhip_flat *f, const void *dev_rows, uint64_t n_add) {
+    VQ_API_BEGIN
+    return flat_add(f, dev_rows, hipMemcpyDeviceToDevice, n_add);
+    VQ_API_END
+}
+
+int vqhip_flat_remove(vqhip_flat *f, const uint32_t *remove_words, uint64_t *removed) {
+    VQ_API_BEGIN
+    return resident_remove(f, remove_words, true, removed);
+    VQ_API_END
+}
+
+int vqhip_flat_remove_device(vqhip_flat *f, const uint32_t *dev_remove_words, uint64_t *removed) {
+    VQ_API_BEGIN
+    return resident_remove(f, dev_remove_words, false, removed);
+    VQ_API_END
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------ scalar index (k_sqindex.hip) ----
 struct vqhip_sqindex : ExactResident<vqhip_sqindex> {
     uint32_t levels = 0;
     float mn = 0, mx = 0, step = 0;
-    DevBuf codes;  // [n][d] u8
+    DevBuf codes;  // [n][d] u8; `bytes` is the capacity (an add grows it)
 
+    DevBuf &payload() { return codes; }
+    size_t row_bytes() const { return d; }
+    int norms_enqueue(const void *C, uint64_t count, float *out, hipStream_t s) {
+        return launch_sq_norms(static_cast<const uint8_t *>(C), count, d, mn, step, out, s);
+    }
     int launch_search(const float *queries_dev, const float *qn, uint32_t nq, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
                       hipStream_t s) {
         return launch_sq_search(metric, codes.as<uint8_t>(), n, d, mn, step, rnorm.as<float>(), queries_dev, qn, nq, topk, dist.as<float>(),
@@ -3178,6 +3326,30 @@ static int sqindex_create(const void *src, hipMemcpyKind kind, bool rows, float 
     return VQHIP_OK;
 }
 
+// n_add rows behind the last: u8 codes as given (rows == false) or f32 rows through the encode of sqindex_create
+static int sqindex_add(vqhip_sqindex *x, const void *src, hipMemcpyKind kind, bool rows, uint64_t n_add) {
+    if (!x) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (n_add == 0) return VQHIP_OK;
+    SqbqEncodeOp op;
+    if (rows) {
+        if (kind == hipMemcpyDeviceToDevice && (reinterpret_cast<uintptr_t>(src) & 3))
+            return fail(VQHIP_ERR_INVALID_INPUT, "rows are not 4-byte aligned");
+        VQ_TRY(sq_encode_op(x->mn, x->mx, x->levels, &op));
+    }
+    return resident_add(x, src, n_add, [&](char *dst, hipStream_t s) -> int {
+        const uint32_t d = x->d;
+        uint8_t *codes = reinterpret_cast<uint8_t *>(dst);
+        if (!rows) {
+            VQ_HIP(hipMemcpyAsync(codes, src, (size_t)n_add * d, kind, s));
+            return VQHIP_OK;
+        }
+        if (kind == hipMemcpyDeviceToDevice) return launch_sqbq_encode(op, static_cast<const float *>(src), n_add * d, codes, s);
+        return staged_rows(src, n_add, (size_t)d * 4, s, [&](const void *piece, uint64_t r0, uint64_t rn) {
+            return launch_sqbq_encode(op, static_cast<const float *>(piece), rn * d, codes + r0 * d, s);
+        });
+    });
+}
+
 extern "C" {
 
 int vqhip_sqindex_create(float min, float max, uint32_t levels, const uint8_t *codes, uint64_t n, uint32_t d, int metric,
@@ -3222,6 +3394,42 @@ int vqhip_sqindex_info(const vqhip_sqindex *x, uint64_t *n, uint32_t *d, int *me
     if (max) *max = x->mx;
     if (levels) *levels = x->levels;
     return VQHIP_OK;
+}
+
+int vqhip_sqindex_add_codes(vqhip_sqindex *x, const uint8_t *codes, uint64_t n_add) {
+    VQ_API_BEGIN
+    return sqindex_add(x, codes, hipMemcpyHostToDevice, false, n_add);
+    VQ_API_END
+}
+
+int vqhip_sqindex_add_codes_device(vqhip_sqindex *x, const void *dev_codes, uint64_t n_add) {
+    VQ_API_BEGIN
+    return sqindex_add(x, dev_codes, hipMemcpyDeviceToDevice, false, n_add);
+    VQ_API_END
+}
+
+int vqhip_sqindex_add_rows(vqhip_sqindex *x, const float *rows, uint64_t n_add) {
+    VQ_API_BEGIN
+    return sqindex_add(x, rows, hipMemcpyHostToDevice, true, n_add);
+    VQ_API_END
+}
+
+int vqhip_sqindex_add_rows_device(vqhip_sqindex *x, const void *dev_rows, uint64_t n_add) {
+    VQ_API_BEGIN
+    return sqindex_add(x, dev_rows, hipMemcpyDeviceToDevice, true, n_add);
+    VQ_API_END
+}
+
+int vqhip_sqindex_remove(vqhip_sqindex *x, const uint32_t *remove_words, uint64_t *removed) {
+    VQ_API_BEGIN
+    return resident_remove(x, remove_words, true, removed);
+    VQ_API_END
+}
+
+int vqhip_sqindex_remove_device(vqhip_sqindex *x, const uint32_t *dev_remove_words, uint64_t *removed) {
+    VQ_API_BEGIN
+    return resident_remove(x, dev_remove_words, false, removed);
+    VQ_API_END
 }
 
 int vqhip_sqindex_codes(vqhip_sqindex *x, uint8_t *codes) {
@@ -3458,6 +3666,11 @@ struct vqhip_binary : Resident {
     DevBuf mask_ws;                      // a filtered host call's row mask on the device
     const uint32_t *mask = nullptr;      // the row mask of the filtered call that holds the lock (MaskScope), NULL otherwise
 
+    DevBuf &payload() { return words; }  // (`bytes` is the capacity: an add grows it)
+    size_t row_bytes() const { return (size_t)W * 4; }
+    DevBuf *norm_buf() { return nullptr; }
+    int norms_enqueue(const void *, uint64_t, float *, hipStream_t) { return VQHIP_OK; }
+
     // a host form's mask, ceil(n / 32) words, up into mask_ws
     int stage_mask(const uint32_t *allowed, hipStream_t s) {
         const size_t mask_b = (size_t)((n + 31) / 32) * 4;
@@ -3566,6 +3779,45 @@ static int binary_create(const void *src, hipMemcpyKind kind_copy, int kind, uin
     return VQHIP_OK;
 }
 
+// n_add rows of `kind` (vqhip_binary_create's three) behind the last, with create's checks of the source
+static int binary_add(vqhip_binary *b, const void *src, hipMemcpyKind kind_copy, int kind, uint64_t n_add) {
+    if (!b) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (n_add == 0) return VQHIP_OK;
+    if (!src) return fail(VQHIP_ERR_NULL_PTR, "source is NULL");
+    if (kind != VQHIP_BINARY_F32 && kind != VQHIP_BINARY_U8 && kind != VQHIP_BINARY_PACKED)
+        return fail(VQHIP_ERR_INVALID_INPUT, "source kind must be 0 (f32), 1 (u8 codes) or 2 (packed words), not %d", kind);
+    const bool dev = kind_copy == hipMemcpyDeviceToDevice;
+    if (dev && kind != VQHIP_BINARY_U8 && (reinterpret_cast<uintptr_t>(src) & 3))
+        return fail(VQHIP_ERR_INVALID_INPUT, kind == VQHIP_BINARY_F32 ? "rows are not 4-byte aligned" : "words are not 4-byte aligned");
+    const uint32_t d = b->d, W = b->W;  // (fixed at create)
+    if (kind == VQHIP_BINARY_PACKED && !dev && d % 32) {
+        const uint32_t *w = static_cast<const uint32_t *>(src), mask = (1u << (d % 32)) - 1u;
+        for (uint64_t i = 0; i < n_add; ++i)
+            if (w[i * W + W - 1] & ~mask) return fail(VQHIP_ERR_INVALID_INPUT, "added row %llu has a pad bit set", (unsigned long long)i);
+    }
+    return resident_add(b, src, n_add, [&](char *dst, hipStream_t s) -> int {
+        uint32_t *words = reinterpret_cast<uint32_t *>(dst);
+        if (kind == VQHIP_BINARY_PACKED) {
+            VQ_HIP(hipMemcpyAsync(words, src, (size_t)n_add * W * 4, kind_copy, s));
+            if (dev && d % 32) {
+                DevBuf bad;
+                uint32_t h_bad = 0;
+                VQ_TRY(bad.alloc(4));
+                VQ_HIP(hipMemsetAsync(bad.p, 0, 4, s));
+                VQ_TRY(launch_bin_padcheck(words, n_add, d, bad.as<uint32_t>(), s));
+                VQ_HIP(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, s));
+                VQ_HIP(hipStreamSynchronize(s));
+                if (h_bad) return fail(VQHIP_ERR_INVALID_INPUT, "an added packed row has a pad bit set");
+            }
+            return VQHIP_OK;
+        }
+        if (dev) return launch_bq_pack(src, kind, n_add, d, b->thr, b->high, words, s);
+        return staged_rows(src, n_add, (size_t)d * (kind == VQHIP_BINARY_U8 ? 1 : 4), s, [&](const void *piece, uint64_t r0, uint64_t rn) {
+            return launch_bq_pack(piece, kind, rn, d, b->thr, b->high, words + r0 * W, s);
+        });
+    });
+}
+
 extern "C" {
 
 int vqhip_bq_pack(float threshold, const float *x, uint64_t n, uint32_t d, uint32_t *words) {
@@ -3637,6 +3889,30 @@ int vqhip_binary_info(const vqhip_binary *b, uint64_t *n, uint32_t *d, float *th
     if (high) *high = b->high;
     if (metric) *metric = b->metric;
     return VQHIP_OK;
+}
+
+int vqhip_binary_add(vqhip_binary *b, const void *src, int kind, uint64_t n_add) {
+    VQ_API_BEGIN
+    return binary_add(b, src, hipMemcpyHostToDevice, kind, n_add);
+    VQ_API_END
+}
+
+int vqhip_binary_add_device(vqhip_binary *b, const void *dev_src, int kind, uint64_t n_add) {
+    VQ_API_BEGIN
+    return binary_add(b, dev_src, hipMemcpyDeviceToDevice, kind, n_add);
+    VQ_API_END
+}
+
+int vqhip_binary_remove(vqhip_binary *b, const uint32_t *remove_words, uint64_t *removed) {
+    VQ_API_BEGIN
+    return resident_remove(b, remove_words, true, removed);
+    VQ_API_END
+}
+
+int vqhip_binary_remove_device(vqhip_binary *b, const uint32_t *dev_remove_words, uint64_t *removed) {
+    VQ_API_BEGIN
+    return resident_remove(b, dev_remove_words, false, removed);
+    VQ_API_END
 }
 
 int vqhip_binary_packed(vqhip_binary *b, uint32_t *words) {

@@ -511,4 +511,14 @@ int bq_decode_lut(float threshold, uint32_t low, uint32_t high, SqbqDecodeLut *p
 int launch_sqbq_encode(const SqbqEncodeOp &p, const float *x, uint64_t count, uint8_t *codes, hipStream_t stream);
 int launch_sqbq_decode(const SqbqDecodeLut &p, const uint8_t *codes, uint64_t count, float *out, hipStream_t stream);
 
+// stable compaction of n rows of rb bytes under a remove mask on the device (k_compact.hip, compact.hpp): ceil(n / 32)
+// words, row i removed iff bit i & 31 of word i >> 5 is set.  launch_compact_plan counts and scans into ws (>=
+// compact_ws_bytes(n)) and leaves the number of survivors at compact_survivors(ws, n); launch_compact_move, once per
+// payload of the index, copies the survivors of src to dst (na * rb bytes, no overlap with src) in their old order.
+size_t compact_ws_bytes(uint64_t n);
+const uint32_t *compact_survivors(const void *ws, uint64_t n);
+int launch_compact_plan(const uint32_t *remove_dev, uint64_t n, void *ws, hipStream_t stream);
+int launch_compact_move(const uint32_t *remove_dev, uint64_t n, const void *ws, const void *src, void *dst, uint64_t rb,
+                        hipStream_t stream);
+
 }  // namespace vqhip

@@ -38,6 +38,9 @@ class FlatIndex(ExactResidentIndex):
     def _make_handle(self) -> "_lib.Flat":
         return _lib.Flat(self._src, self._distance.metric)
 
+    def _add_form(self):
+        return "add", self._dtype, ()  # rows in the index's own dtype, stored as they are
+
 
 def adc_then_rerank(adc_search, n: int, dim: int, queries: np.ndarray, topk: int, rerank, candidates):
     """the standard PQ pipeline: `adc_search(queries, c)` for a short list of c candidates per query (default 4 topk,

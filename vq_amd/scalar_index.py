@@ -80,6 +80,18 @@ class ScalarIndex(ExactResidentIndex):
         q = self._quantizer
         return _lib.SQIndex(self._src, self._rows, self._n, self._dim, q._min, q._max, q.levels, self._distance.metric)
 
+    def _add_form(self):
+        return "add_rows", np.float32, ()  # float32 rows, encoded on the device as the constructor encodes them
+
+    def add_codes(self, codes) -> np.ndarray:
+        """append u8 SQ codes (b, dim) as they are (``from_codes``'s form); returns their ids uint32 (b,)"""
+        a = self._added(codes, np.uint8, "codes")
+        return self._append("add_codes", a, a.shape[0])
+
+    def add_codes_device(self, dev_codes: int, n: int) -> np.ndarray:
+        """``add_codes`` with the codes [n][dim] at a device pointer; returns their ids"""
+        return self._append_device("add_codes_device", dev_codes, n)
+
     def codes(self) -> np.ndarray:
         """the codes, uint8 (n, d): the caller's for an index built from codes and not yet searched, else from the device"""
         if self._ix is None and not self._rows:
