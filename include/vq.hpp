@@ -1126,7 +1126,8 @@ namespace detail {
 // the shape, the add-side and probe-side checks, and the calls whose arguments are the same for every payload.
 template <class H, int (*Destroy)(H *), int (*ListSizes)(H *, std::uint64_t *),
           int (*Probe)(H *, const float *, std::uint32_t, std::uint32_t, std::uint32_t *),
-          int (*Search)(H *, const float *, std::uint32_t, std::uint32_t, std::uint32_t, std::uint32_t *, float *)>
+          int (*Search)(H *, const float *, std::uint32_t, std::uint32_t, std::uint32_t, std::uint32_t *, float *),
+          int (*Remove)(H *, const std::uint32_t *, std::uint64_t *), int (*Uploads)(const H *, std::uint64_t *)>
 class IvfIndex {
    public:
     std::size_t size() const { return n_; }
@@ -1157,6 +1158,32 @@ class IvfIndex {
         if (nq)
             check(Search(ix_.get(), queries, (std::uint32_t)nq, (std::uint32_t)nprobe, (std::uint32_t)topk, r.idx.data(), r.dist.data()));
         return r;
+    }
+
+    // Removing rows (include/vqhip.h, "removing rows from an inverted file"): `remove` [n], true: the row goes (or row ids,
+    // through remove_mask).  The other rows keep their order and their lists and move up; returns the old ids of the
+    // remaining rows in their new order.  Removing every row is allowed: the index is then empty, and adds work.  After any
+    // sequence of adds and removals every call returns bit for bit what a fresh index given the remaining rows in one add
+    // returns.  A device state that is current stays current; without one no device is touched.
+    std::vector<std::uint32_t> remove_rows(const std::vector<bool> &remove) {
+        if (remove.size() != n_) throw VqError::DimensionMismatch(n_, remove.size());
+        std::vector<std::uint32_t> kept;
+        for (std::size_t i = 0; i < n_; ++i)
+            if (!remove[i]) kept.push_back((std::uint32_t)i);
+        if (kept.size() == n_) return kept;
+        const std::vector<std::uint32_t> words = pack_row_mask(remove);
+        std::uint64_t gone = 0;
+        check(Remove(ix_.get(), words.data(), &gone));
+        n_ = kept.size();
+        return kept;
+    }
+    std::vector<std::uint32_t> remove_rows(const std::vector<std::uint32_t> &ids) { return remove_rows(remove_mask(ids, n_)); }
+    // how many times the device state has been built from the host rows (by the first probe or search, and by the first
+    // one after an add): a removal does not move it
+    std::uint64_t uploads() const {
+        std::uint64_t u = 0;
+        check(Uploads(ix_.get(), &u));
+        return u;
     }
 
    protected:
@@ -1250,7 +1277,8 @@ class IvfIndex {
 // (row id, ADC distance) pairs [nq][topk], nearest first; slots past the probed rows hold (0xFFFFFFFF, +inf).  The
 // constructor, add and list_sizes need no device; the arguments are checked before the device is touched.
 class IVFPQIndex
-    : public detail::IvfIndex<vqhip_ivfpq, vqhip_ivfpq_destroy, vqhip_ivfpq_list_sizes, vqhip_ivfpq_probe, vqhip_ivfpq_search> {
+    : public detail::IvfIndex<vqhip_ivfpq, vqhip_ivfpq_destroy, vqhip_ivfpq_list_sizes, vqhip_ivfpq_probe, vqhip_ivfpq_search,
+                              vqhip_ivfpq_remove, vqhip_ivfpq_uploads> {
    public:
     // residual: the codes of a row in list l quantise x - C[l] (include/vqhip.h, VQHIP_IVF_RESIDUAL)
     IVFPQIndex(const float *coarse, std::size_t nlist, const float *codebooks, std::size_t m, std::size_t k, std::size_t sub_dim,
@@ -1305,7 +1333,7 @@ class IVFPQIndex
 // first; slots past the probed rows hold (0xFFFFFFFF, +inf); with nprobe == nlist it is FlatIndex's search.  The
 // constructor, add and list_sizes need no device; the arguments are checked before the device is touched.
 class IVFFlatIndex : public detail::IvfIndex<vqhip_ivfflat, vqhip_ivfflat_destroy, vqhip_ivfflat_list_sizes, vqhip_ivfflat_probe,
-                                             vqhip_ivfflat_search> {
+                                             vqhip_ivfflat_search, vqhip_ivfflat_remove, vqhip_ivfflat_uploads> {
    public:
     enum class Rows { F32 = 0, F16 = 1 };
     IVFFlatIndex(const float *coarse, std::size_t nlist, std::size_t dim, Distance distance = Distance(), Rows rows = Rows::F32) {
@@ -1365,7 +1393,8 @@ class IVFFlatIndex : public detail::IvfIndex<vqhip_ivfflat, vqhip_ivfflat_destro
 // over quantizer.dequantize(codes) in the same lists; with nprobe == nlist it is ScalarIndex's search.  The constructor,
 // add_codes, codes and list_sizes need no device; the arguments are checked before the device is touched.
 class IVFScalarIndex
-    : public detail::IvfIndex<vqhip_ivfsq, vqhip_ivfsq_destroy, vqhip_ivfsq_list_sizes, vqhip_ivfsq_probe, vqhip_ivfsq_search> {
+    : public detail::IvfIndex<vqhip_ivfsq, vqhip_ivfsq_destroy, vqhip_ivfsq_list_sizes, vqhip_ivfsq_probe, vqhip_ivfsq_search,
+                              vqhip_ivfsq_remove, vqhip_ivfsq_uploads> {
    public:
     IVFScalarIndex(const float *coarse, std::size_t nlist, std::size_t dim, ScalarQuantizer quantizer, Distance distance = Distance())
         : quantizer_(quantizer) {
@@ -1435,7 +1464,8 @@ class IVFScalarIndex
 // probed rows hold (0xFFFFFFFF, +inf); with nprobe == nlist it is BinaryIndex's search.  The constructor, add_packed,
 // add_codes, packed and list_sizes need no device; the arguments are checked before the device is touched.
 class IVFBinaryIndex
-    : public detail::IvfIndex<vqhip_ivfbin, vqhip_ivfbin_destroy, vqhip_ivfbin_list_sizes, vqhip_ivfbin_probe, vqhip_ivfbin_search> {
+    : public detail::IvfIndex<vqhip_ivfbin, vqhip_ivfbin_destroy, vqhip_ivfbin_list_sizes, vqhip_ivfbin_probe, vqhip_ivfbin_search,
+                              vqhip_ivfbin_remove, vqhip_ivfbin_uploads> {
    public:
     IVFBinaryIndex(const float *coarse, std::size_t nlist, std::size_t dim, BinaryQuantizer quantizer = BinaryQuantizer(0.0f, 0, 1),
                    Distance distance = Distance(Distance::Manhattan), Distance coarse_distance = Distance())

@@ -1054,6 +1054,39 @@ int vqhip_ivfbin_range_search_masked_device(vqhip_ivfbin *ix, const void *dev_qu
                                             const uint32_t *hradii, uint64_t max_results, const uint32_t *dev_allowed,
                                             vqhip_range **out);
 
+/* ---- removing rows from an inverted file (k_ivf_remove.hip, ivf_remove.hpp, ivf_view.hpp) ----------------
+ * No reference counterpart.  An index is the sequence of its rows R[0 .. n) with their list ids L[0 .. n).
+ *   remove(S)   S is a HOST mask of ceil(n / 32) u32 words: row i is removed iff bit i & 31 of word i >> 5 is set, bits at
+ *               or past n ignored (vqhip_flat_remove's layout).  R', L' are R, L without those rows, the order kept: a
+ *               surviving row i becomes row i - |{s in S : s < i}|, in the list it was in.  *removed = the number of rows
+ *               removed.  Removing nothing changes nothing.  Removing every row is allowed, unlike on the resident
+ *               indexes: an inverted file may be empty, as a created one is, and later adds work.
+ * INVARIANT: after any sequence of adds and removes, every call on the index -- probe, search, search_device, the masked
+ * forms, range search and its masked forms, list_sizes, codes / packed, info -- returns bit for bit what a fresh index
+ * returns that was given L', R' in one add; the bounds on topk and the length of a row mask follow the current n.
+ * A call that fails leaves the index exactly as it was: everything that can fail runs before anything is swapped in.
+ * Where the work is done: without a current device state (no probe or search yet, or an add since the last one) the host
+ * rows are compacted in place and no device is touched, so a removal, like an add, works on a machine without a GPU.  With
+ * a current device state the removal runs on the device and the state STAYS current: the next search pays no upload
+ * (vqhip_*_uploads does not move).  The device state after it is byte for byte the one the first search of the fresh
+ * index would upload.  Peak device memory: old + new payload.
+ * There is no device-mask form: a handle keeps a host twin of every row (it is what an add rebuilds the device state
+ * from), and compacting the twin needs the mask on the host.
+ * Threads and streams: as vqhip_flat_remove -- the handle's lock, the caller's stream ordered behind the handle's queued
+ * work, synchronised before an old buffer is freed and on return: a search_device queued earlier on another stream
+ * completes on the old rows.  Not capturable into a graph.
+ * NULL ix, remove_words or removed: VQHIP_ERR_NULL_PTR, before anything else happens.
+ *   uploads     *uploads = the times the device state has been built from the host rows since create (by the first probe or
+ *               search, and by the first one after an add): whether the next search pays an upload.  Host only. */
+int vqhip_ivfpq_remove(vqhip_ivfpq *ix, const uint32_t *remove_words, uint64_t *removed);
+int vqhip_ivfflat_remove(vqhip_ivfflat *ix, const uint32_t *remove_words, uint64_t *removed);
+int vqhip_ivfsq_remove(vqhip_ivfsq *ix, const uint32_t *remove_words, uint64_t *removed);
+int vqhip_ivfbin_remove(vqhip_ivfbin *ix, const uint32_t *remove_words, uint64_t *removed);
+int vqhip_ivfpq_uploads(const vqhip_ivfpq *ix, uint64_t *uploads);
+int vqhip_ivfflat_uploads(const vqhip_ivfflat *ix, uint64_t *uploads);
+int vqhip_ivfsq_uploads(const vqhip_ivfsq *ix, uint64_t *uploads);
+int vqhip_ivfbin_uploads(const vqhip_ivfbin *ix, uint64_t *uploads);
+
 /* ---- TSVQ ----------------------------------------------------------------------------
  * build replaces TSVQNode::build (src/tsvq.rs:31-115); the tree comes back flattened in
  * pre-order (node 0 = root, left subtree, right subtree): centroids [cap][d], left/right

@@ -9,7 +9,7 @@ import operator
 import numpy as np
 
 from . import _lib
-from ._resident_common import DEFAULT_MAX_RESULTS, _max_results, _radii
+from ._resident_common import DEFAULT_MAX_RESULTS, _max_results, _radii, pack_row_mask
 from .distance import Distance
 from .errors import DimensionMismatch, InvalidParameter
 
@@ -201,6 +201,41 @@ class IVFIndexBase:
         n0 = len(self)
         self._lists = np.concatenate([self._lists, lid])
         return np.arange(n0, n0 + lid.shape[0], dtype=np.uint32)
+
+    def remove_rows(self, mask_or_ids) -> np.ndarray:
+        """remove the rows of a bool mask (n,) -- True: remove -- or of an integer array of row ids in [0, n), in any
+        order, repeats welcome.  The remaining rows keep their order, their lists and move up: returns `kept` uint32, the
+        old ids of the remaining rows in their new order (``kept[new id] = old id``), as ``ResidentIndex.remove_rows``
+        does -- so a reranker over the same rows follows with the same argument.  Removing every row is allowed: the
+        index is then as empty as a trained one, and adds work.  Every check runs before anything changes.  A device
+        state that is current stays current (the next search pays no upload); without one no device is touched."""
+        n = len(self)
+        a = np.asarray(mask_or_ids)
+        if a.size == 0 and a.ndim == 1 and a.dtype != np.bool_:
+            a = a.astype(np.int64)  # (an empty list of ids)
+        if n == 0:  # an empty index accepts only an empty removal
+            if a.ndim != 1:
+                raise InvalidParameter("mask_or_ids", f"must be a 1D array, got {a.ndim} dimensions")
+            if a.dtype != np.bool_ and a.dtype.kind not in "iu":
+                raise InvalidParameter("mask_or_ids", f"must be a bool array or an integer array of row ids, got {a.dtype}")
+            if a.size:
+                if a.dtype == np.bool_:
+                    raise DimensionMismatch(0, a.shape[0])
+                raise InvalidParameter("mask_or_ids", "the index holds no row")
+            return np.empty(0, np.uint32)
+        words = pack_row_mask(a, n)
+        gone = np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(bool)
+        kept = np.flatnonzero(~gone).astype(np.uint32)
+        if kept.shape[0] == n:
+            return kept
+        if self._ix is not None:
+            self._ix.remove(words)  # the handle first: the one step that can fail
+        self._lists = self._lists[kept]
+        self._removed(kept)
+        return kept
+
+    def _removed(self, kept: np.ndarray) -> None:
+        """a subclass's own host array follows a removal: `kept` are the old ids of the rows that stay, ascending"""
 
     # -- search -----------------------------------------------------------------------------
     def _queries(self, queries) -> np.ndarray:

@@ -275,6 +275,14 @@ SIGNATURES = {
     "vqhip_ivfpq_create_ex": (C.c_int, [_f32p, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
                                         _vpp]),
     "vqhip_ivfpq_flags": (C.c_int, [_vp, _u32p]),
+    "vqhip_ivfpq_remove": (C.c_int, [_vp, _u32p, _u64p]),
+    "vqhip_ivfflat_remove": (C.c_int, [_vp, _u32p, _u64p]),
+    "vqhip_ivfsq_remove": (C.c_int, [_vp, _u32p, _u64p]),
+    "vqhip_ivfbin_remove": (C.c_int, [_vp, _u32p, _u64p]),
+    "vqhip_ivfpq_uploads": (C.c_int, [_vp, _u64p]),
+    "vqhip_ivfflat_uploads": (C.c_int, [_vp, _u64p]),
+    "vqhip_ivfsq_uploads": (C.c_int, [_vp, _u64p]),
+    "vqhip_ivfbin_uploads": (C.c_int, [_vp, _u64p]),
     "vqhip_sq_check": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p]),
     "vqhip_sq_thresholds": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p]),
     "vqhip_sq_encode": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p, C.c_uint64, _u8p]),
@@ -1090,6 +1098,18 @@ class _IVFHandle(Handle):
         out = np.empty(self.nlist, np.uint64)
         check(self._fn("list_sizes")(self.raw, ptr(out, _u64p)))
         return out
+
+    def remove(self, words: np.ndarray) -> int:
+        """`words`: the remove mask uint32 (ceil(n / 32),) on the host; returns the number of rows removed"""
+        removed = C.c_uint64(0)
+        check(self._fn("remove")(self.raw, ptr(words, _u32p), C.byref(removed)))
+        return int(removed.value)
+
+    def uploads(self) -> int:
+        """how many times the device state has been built from the host rows since create"""
+        out = C.c_uint64(0)
+        check(self._fn("uploads")(self.raw, C.byref(out)))
+        return int(out.value)
 
     def probe(self, q: np.ndarray, nprobe: int) -> np.ndarray:
         nq = q.shape[0]

@@ -18,6 +18,7 @@
 
 #include "adc_plan.hpp"
 #include "compact.hpp"
+#include "ivf_remove.hpp"
 #include "kernels.hpp"
 
 namespace vqhip {
@@ -4004,6 +4005,7 @@ struct IvfLists {
     std::vector<uint64_t> sizes;     // [nlist] rows per list
     uint64_t n = 0, max_list = 0;
     bool dirty = true;                     // rows added since the last upload
+    uint64_t uploads = 0;                  // times ivf_ready has built the device state from the host rows
     int dev = -1;                          // the device of the index's state: current at create (-1: create saw no device;
                                            // then the first probe or search takes the current one)
     std::vector<uint64_t> largest_prefix;  // [nlist + 1] sums of the largest list sizes (the bound on |S(q)|)
@@ -4080,6 +4082,15 @@ static int ivf_list_sizes(IvfLists *ix, uint64_t *sizes) {
     return VQHIP_OK;
 }
 
+// what the batches of a search are sized by, from the list sizes: the largest list and the sums of the largest ones
+static void ivf_bounds(IvfLists *ix) {
+    std::vector<uint64_t> sorted(ix->sizes);
+    std::sort(sorted.begin(), sorted.end(), std::greater<uint64_t>());
+    ix->max_list = sorted[0];
+    ix->largest_prefix.assign(ix->nlist + 1, 0);
+    for (uint32_t l = 0; l < ix->nlist; ++l) ix->largest_prefix[l + 1] = ix->largest_prefix[l] + sorted[l];
+}
+
 // The device state, current with the host's rows (enqueued on s and waited for: host buffers are the copies' sources).
 // `first` runs once, after the coarse centroids are resident (an index's own tables); `resident` after every upload of a
 // non-empty payload (what an index derives from it on the device).
@@ -4112,12 +4123,9 @@ static int ivf_ready(IvfLists *ix, hipStream_t s, First &&first, Resident &&resi
         VQ_TRY(resident());
     }
     VQ_HIP(hipStreamSynchronize(s));
-    std::vector<uint64_t> sorted(ix->sizes);
-    std::sort(sorted.begin(), sorted.end(), std::greater<uint64_t>());
-    ix->max_list = sorted[0];
-    ix->largest_prefix.assign(ix->nlist + 1, 0);
-    for (uint32_t l = 0; l < ix->nlist; ++l) ix->largest_prefix[l + 1] = ix->largest_prefix[l] + sorted[l];
+    ivf_bounds(ix);
     ix->dirty = false;
+    ++ix->uploads;
     return VQHIP_OK;
 }
 static int ivf_no_hook() { return VQHIP_OK; }
@@ -4160,6 +4168,8 @@ struct IvfView {
 struct IvfFiltered : IvfLists {
     DevBuf mask_ws;                       // a filtered host call's row mask on the device
     DevBuf v_pick, v_aids, v_aoff, v_ws;  // a filtered call's view (8 bytes per row) and the workspace of its scan
+    DevBuf rm_prefix;                     // a removal's removed rows below every mask word (ivf_remove)
+    DevBuf *norm_buf() { return nullptr; }  // the rows' norms on the device, where an index keeps them
 
     // The view of a filtered call, built once per call: after ready(s), under the handle's lock, enqueued on s.  allowed:
     // the row mask, ceil(n / 32) words for the n of this call -- a host form's goes up into mask_ws first.
@@ -4181,6 +4191,94 @@ struct IvfFiltered : IvfLists {
         return VQHIP_OK;
     }
 };
+
+// the host rows without the removed ones, in place and in order: row_list, payload, sizes, n.  Nothing here can fail.
+static void ivf_remove_host(IvfLists *ix, const uint32_t *remove, uint64_t na) {
+    const size_t row_b = ix->row_b;
+    uint64_t j = 0;
+    for (uint64_t i = 0; i < ix->n; ++i) {
+        if ((remove[i >> 5] >> (i & 31)) & 1u) {
+            --ix->sizes[ix->row_list[i]];
+            continue;
+        }
+        if (j != i) {
+            ix->row_list[j] = ix->row_list[i];
+            memcpy(ix->payload.data() + (size_t)j * row_b, ix->payload.data() + (size_t)i * row_b, row_b);  // (j < i: no overlap)
+        }
+        ++j;
+    }
+    ix->row_list.resize(na);
+    ix->payload.resize((size_t)na * row_b);
+    ix->n = na;
+}
+
+// A removal (include/vqhip.h, "removing rows from an inverted file"): `remove` is a host mask of
+// ceil(n / 32) words.  Without a current device state the host rows are compacted and no device is touched.  With one,
+// the state stays current: the view of the surviving rows (launch_ivf_view over the complement of the mask) is their
+// inverted file with the old ids, k_ivf_take moves the payload (and the norms, T::norm_buf()) behind its `pick` into new
+// allocations, k_ivf_renumber gives the ids their new numbers, and the buffers are swapped in once everything that can
+// fail has run; the host rows follow.  The host knows the survivors' count and every list's size: nothing is read back.
+template <class T>
+static int ivf_remove(T *ix, const uint32_t *remove, uint64_t *removed) {
+    if (!ix || !remove || !removed) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    *removed = 0;
+    Entry in(ix->sync);
+    const uint64_t n = ix->n, words = (n + 31) / 32;
+    if (!ix->flat || ix->dirty) {  // no device state to keep current
+        uint64_t na = 0;
+        for (uint64_t w = 0; w < words; ++w) na += compact_popc32(compact_keep_word(remove[w], w, n));
+        if (na != n) ivf_remove_host(ix, remove, na);
+        *removed = n - na;
+        return VQHIP_OK;
+    }
+    std::vector<uint32_t> prefix(words), allowed(words);
+    const uint64_t gone = ivf_below_prefix(remove, n, prefix.data());
+    if (gone == 0) return VQHIP_OK;
+    const uint64_t na = n - gone;
+    for (uint64_t w = 0; w < words; ++w) allowed[w] = ~remove[w];  // (the view reads the bits of rows below n only)
+    VQ_TRY(require_gfx950());
+    VQ_TRY(ix->on_device());
+    hipStream_t s;
+    VQ_TRY(in.stream(&s));  // behind whatever the handle still has queued on another stream
+    DevBuf payload, ids, off, norms;  // the survivors' state; the old buffers leave with them (freed here where the call fails)
+    DevBuf *norm = ix->norm_buf();
+    auto enqueue = [&]() -> int {
+        VQ_TRY(ix->rm_prefix.ensure(words * 4));
+        IvfView v;
+        VQ_TRY(ix->filtered(allowed.data(), true, s, &v));
+        VQ_HIP(hipMemcpyAsync(ix->rm_prefix.p, prefix.data(), words * 4, hipMemcpyHostToDevice, s));
+        VQ_TRY(payload.alloc((size_t)na * ix->row_b));
+        VQ_TRY(ids.alloc((size_t)na * 4));
+        VQ_TRY(off.alloc(((size_t)ix->nlist + 1) * 4));
+        if (norm) VQ_TRY(norms.alloc((size_t)na * 4));
+        VQ_TRY(launch_ivf_take(v.pick, na, ix->d_payload.p, payload.p, ix->row_b, s));
+        if (norm) VQ_TRY(launch_ivf_take(v.pick, na, norm->p, norms.p, 4, s));
+        VQ_TRY(launch_ivf_renumber(v.aids, na, ix->mask_ws.template as<uint32_t>(), ix->rm_prefix.template as<uint32_t>(),
+                                   ids.template as<uint32_t>(), s));
+        VQ_HIP(hipMemcpyAsync(off.p, v.aoff, ((size_t)ix->nlist + 1) * 4, hipMemcpyDeviceToDevice, s));  // (v_aoff is a per-call workspace)
+        return VQHIP_OK;
+    };
+    const int rc = enqueue();
+    const hipError_t e = hipStreamSynchronize(s);  // before either side is freed; the host arrays were the copies' sources
+    in.synced();
+    VQ_TRY(rc);
+    VQ_HIP(e);
+    swap_buf(ix->d_payload, payload);
+    swap_buf(ix->d_ids, ids);
+    swap_buf(ix->d_off, off);
+    if (norm) swap_buf(*norm, norms);
+    ivf_remove_host(ix, remove, na);
+    ivf_bounds(ix);
+    *removed = gone;
+    return VQHIP_OK;
+}
+
+static int ivf_uploads(const IvfLists *ix, uint64_t *uploads) {
+    if (!ix || !uploads) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    std::lock_guard<std::recursive_mutex> lock(const_cast<IvfLists *>(ix)->sync.mu);
+    *uploads = ix->uploads;
+    return VQHIP_OK;
+}
 
 // The front of every probe and search (T: an index with ready(s)): the checks in their order, the index's device, the
 // calling thread's stream, the device state -- then body(in, s).  topk NULL: a probe.
@@ -4381,6 +4479,16 @@ int vqhip_ivfpq_list_sizes(vqhip_ivfpq *ix, uint64_t *sizes) {
     VQ_API_END
 }
 
+int vqhip_ivfpq_remove(vqhip_ivfpq *ix, const uint32_t *remove_words, uint64_t *removed) {
+    VQ_API_BEGIN
+    return ivf_remove(ix, remove_words, removed);
+    VQ_API_END
+}
+
+int vqhip_ivfpq_uploads(const vqhip_ivfpq *ix, uint64_t *uploads) {
+    return ivf_uploads(ix, uploads);
+}
+
 int vqhip_ivfpq_probe(vqhip_ivfpq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t *lists_out) {
     VQ_API_BEGIN
     return ivf_probe(ix, queries, nq, nprobe, lists_out);
@@ -4495,6 +4603,7 @@ struct IvfExact : IvfOverW<T> {
     DevBuf d_rnorm;
     DevBuf qnorm;  // per-call workspace
 
+    DevBuf *norm_buf() { return vq_is_cos(this->metric) ? &d_rnorm : nullptr; }  // (a removal moves the norms with the rows)
     int radii_up(const float *r, uint32_t nq, hipStream_t s) {
         VQ_TRY(this->radii.ensure((size_t)nq * 4));
         VQ_HIP(hipMemcpyAsync(this->radii.p, r, (size_t)nq * 4, hipMemcpyHostToDevice, s));
@@ -4661,6 +4770,16 @@ int vqhip_ivfflat_list_sizes(vqhip_ivfflat *ix, uint64_t *sizes) {
     VQ_API_END
 }
 
+int vqhip_ivfflat_remove(vqhip_ivfflat *ix, const uint32_t *remove_words, uint64_t *removed) {
+    VQ_API_BEGIN
+    return ivf_remove(ix, remove_words, removed);
+    VQ_API_END
+}
+
+int vqhip_ivfflat_uploads(const vqhip_ivfflat *ix, uint64_t *uploads) {
+    return ivf_uploads(ix, uploads);
+}
+
 int vqhip_ivfflat_probe(vqhip_ivfflat *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t *lists_out) {
     VQ_API_BEGIN
     return ivf_probe(ix, queries, nq, nprobe, lists_out);
@@ -4798,6 +4917,16 @@ int vqhip_ivfsq_codes(vqhip_ivfsq *ix, uint8_t *codes_out) {
     memcpy(codes_out, ix->payload.data(), ix->payload.size());
     return VQHIP_OK;
     VQ_API_END
+}
+
+int vqhip_ivfsq_remove(vqhip_ivfsq *ix, const uint32_t *remove_words, uint64_t *removed) {
+    VQ_API_BEGIN
+    return ivf_remove(ix, remove_words, removed);
+    VQ_API_END
+}
+
+int vqhip_ivfsq_uploads(const vqhip_ivfsq *ix, uint64_t *uploads) {
+    return ivf_uploads(ix, uploads);
 }
 
 int vqhip_ivfsq_probe(vqhip_ivfsq *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t *lists_out) {
@@ -4980,6 +5109,16 @@ int vqhip_ivfbin_packed(vqhip_ivfbin *ix, uint32_t *words_out) {
     memcpy(words_out, ix->payload.data(), ix->payload.size());
     return VQHIP_OK;
     VQ_API_END
+}
+
+int vqhip_ivfbin_remove(vqhip_ivfbin *ix, const uint32_t *remove_words, uint64_t *removed) {
+    VQ_API_BEGIN
+    return ivf_remove(ix, remove_words, removed);
+    VQ_API_END
+}
+
+int vqhip_ivfbin_uploads(const vqhip_ivfbin *ix, uint64_t *uploads) {
+    return ivf_uploads(ix, uploads);
 }
 
 int vqhip_ivfbin_probe(vqhip_ivfbin *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t *lists_out) {

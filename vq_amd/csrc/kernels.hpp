@@ -521,4 +521,12 @@ int launch_compact_plan(const uint32_t *remove_dev, uint64_t n, void *ws, hipStr
 int launch_compact_move(const uint32_t *remove_dev, uint64_t n, const void *ws, const void *src, void *dst, uint64_t rb,
                         hipStream_t stream);
 
+// removing rows from an inverted file on the device (k_ivf_remove.hip, ivf_remove.hpp), behind launch_ivf_view over the
+// mask of the rows that stay: launch_ivf_take copies row pick[j] of src (rb bytes a row) to row j of dst for j < na (no
+// overlap); launch_ivf_renumber writes ids[j] = aids[j] - (the removed rows under aids[j]), `allowed` the view's mask and
+// prefix[w] the removed rows below row 32 w.  Enqueued on stream.
+int launch_ivf_take(const uint32_t *pick, uint64_t na, const void *src, void *dst, uint64_t rb, hipStream_t stream);
+int launch_ivf_renumber(const uint32_t *aids, uint64_t na, const uint32_t *allowed, const uint32_t *prefix, uint32_t *ids,
+                        hipStream_t stream);
+
 }  // namespace vqhip

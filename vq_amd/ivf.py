@@ -168,6 +168,9 @@ class IVFPQIndex(IVFIndexBase):
         self._codes = np.concatenate([self._codes, c])
         return self._appended(lid)
 
+    def _removed(self, kept: np.ndarray) -> None:
+        self._codes = self._codes[kept]
+
     def _handle(self) -> "_lib.IVFPQ":
         if self._ix is None:
             ix = _lib.IVFPQ(self._coarse, self._codebooks, self._distance.metric,

@@ -161,6 +161,10 @@ class IVFBinaryIndex(IVFBinaryFilterMixin, IVFIndexBase):
             self._host_words = np.concatenate([self._host_words, w])
         return self._appended(lid)
 
+    def _removed(self, kept: np.ndarray) -> None:
+        if self._ix is None:  # (else the handle holds the only copy)
+            self._host_words = self._host_words[kept]
+
     def _handle(self) -> "_lib.IVFBin":
         if self._ix is None:
             q = self._quantizer

@@ -107,6 +107,9 @@ class IVFFlatIndex(IVFFilterMixin, IVFRangeMixin, IVFIndexBase):
         self._rows = np.concatenate([self._rows, r])
         return self._appended(lid)
 
+    def _removed(self, kept: np.ndarray) -> None:
+        self._rows = self._rows[kept]
+
     def _handle(self) -> "_lib.IVFFlat":
         if self._ix is None:
             ix = _lib.IVFFlat(self._coarse, self._distance.metric, self._dtype)

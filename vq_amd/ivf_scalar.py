@@ -121,6 +121,10 @@ class IVFScalarIndex(IVFFilterMixin, IVFRangeMixin, IVFIndexBase):
             self._host_codes = np.concatenate([self._host_codes, c])
         return self._appended(lid)
 
+    def _removed(self, kept: np.ndarray) -> None:
+        if self._ix is None:  # (else the handle holds the only copy)
+            self._host_codes = self._host_codes[kept]
+
     def _handle(self) -> "_lib.IVFSQ":
         if self._ix is None:
             q = self._quantizer
