@@ -1,4 +1,4 @@
-"""The lifecycle the three inverted-file indexes share (vq_amd/_ivf_common.py, the IvfLists layer of vq_amd/csrc/api.hip),
+"""The lifecycle the three inverted-file indexes share (vq_amd/_ivf_common.py, the IvfLists layer of vq_amd/csrc/api_ivf.hip),
 on the MI355X: IVFPQIndex, IVFFlatIndex (float32 and float16 rows) and IVFScalarIndex through the same steps -- search,
 add, search again (the rebuild of the device lists after a search), close and search, list sizes, probe, and a query
 whose only probed list is empty.  Every comparison is equality of indices and of distance bits; the expected values are

@@ -1,5 +1,5 @@
 """One handle through a sequence of calls, on every resident index (FlatIndex f32 / f16, ScalarIndex from rows / from
-codes, BinaryIndex from rows / from packed words) -- the steps of the host layer the three share (vq_amd/csrc/api.hip,
+codes, BinaryIndex from rows / from packed words) -- the steps of the host layer the three share (vq_amd/csrc/api_resident.hip,
 "resident indexes: the shared host layer").  The workspaces q / idx / out belong to the handle and are used by search,
 rerank and range search alike, so each step is compared with the numpy statements (tests/ref_knn.py, ref_sqindex.py,
 ref_binary.py, ref_range.py): a workspace left at an earlier call's size, or holding an earlier call's data, shows as a

@@ -5,7 +5,7 @@ The reference's quantizers are plain data -- `ProductQuantizer` (src/pq.rs:39-45
 may run on any number of threads at once, and `Vector` is built for rayon (src/core/vector.rs:22-23).
 pyvq serialises under the GIL (pyvq/src/pq.rs:96-107); this package calls through ctypes, which
 RELEASES the GIL, so the guarantee has to come from libvqhip: one lock per handle, call-owned staging on
-the per-vector path, stream order across threads (vq_amd/csrc/api.hip "handles under threads").
+the per-vector path, stream order across threads (vq_amd/csrc/api_common.hpp "handles under threads").
 
 Every result below is compared bit for bit with the CPU oracle."""
 import threading

@@ -115,7 +115,7 @@ inline uint32_t ivfr_passes(uint64_t n) {
 // staging areas, grown here to the batch's hits (16 bytes each).  Waits for the stream once.  A batch that takes the
 // result past max_results is VQHIP_ERR_UNSUPPORTED.
 // k_range_scan's one-workgroup bound holds unchanged: a batch of several queries keeps nb * wstride <= 2^28 floats of W
-// (ivf_batch, api.hip), so it has at most nb * ceil(wstride / 4096) <= 2^16 + nb entries, and a single-query batch at most
+// (ivf_batch, api_ivf.hip), so it has at most nb * ceil(wstride / 4096) <= 2^16 + nb entries, and a single-query batch at most
 // 2^20 (wstride < 2^32).
 inline int ivfr_batch(const IvfBatchView &v, uint32_t q0, const float *radii, void *ws, DevBuf *stage, uint64_t max_results,
                       RangeOut *out, hipStream_t stream) {
