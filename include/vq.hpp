@@ -939,6 +939,17 @@ class FlatIndex : public detail::ExactResidentIndex<vqhip_flat, vqhip_flat_destr
     }
 };
 
+namespace detail {
+// packed rows [n][ceil(dim / 32)] of the two binary indexes: no bit at or past dim may be set
+inline void check_pad_bits(const std::uint32_t *words, std::size_t n, std::size_t dim) {
+    if (dim % 32 == 0) return;
+    const std::size_t w = (dim + 31) / 32;
+    const std::uint32_t mask = (1u << (dim % 32)) - 1u;
+    for (std::size_t i = 0; i < n; ++i)
+        if (words[i * w + w - 1] & ~mask) throw VqError::InvalidParameter("words", "a row has a pad bit set");
+}
+}  // namespace detail
+
 // Hamming index over packed BQ codes (include/vqhip.h, vqhip_binary_*): rows binarised by a BinaryQuantizer (f32 rows,
 // u8 codes or packed words [n][ceil(dim / 32)]), searched under squared Euclidean, Euclidean or Manhattan on the
 // dequantized vectors; (row id, distance) pairs [nq][topk], nearest first, ties to the lower row.  The queries are
@@ -1038,13 +1049,7 @@ class BinaryIndex : public detail::ResidentIndex<vqhip_binary, vqhip_binary_dest
     std::vector<std::uint32_t> add_device(const void *dev_src, Source kind, std::size_t b) { return add_from(dev_src, kind, b, true); }
 
    private:
-    static void check_pad(const std::uint32_t *words, std::size_t n, std::size_t dim) {
-        if (dim % 32 == 0) return;
-        const std::size_t w = (dim + 31) / 32;
-        const std::uint32_t mask = (1u << (dim % 32)) - 1u;
-        for (std::size_t i = 0; i < n; ++i)
-            if (words[i * w + w - 1] & ~mask) throw VqError::InvalidParameter("words", "a row has a pad bit set");
-    }
+    static void check_pad(const std::uint32_t *words, std::size_t n, std::size_t dim) { detail::check_pad_bits(words, n, dim); }
     std::vector<std::uint32_t> add_from(const void *src, Source kind, std::size_t b, bool device) {
         return append(src, b, [&](vqhip_binary *h) {
             return device ? vqhip_binary_add_device(h, src, (int)kind, b) : vqhip_binary_add(h, src, (int)kind, b);
@@ -1119,6 +1124,69 @@ class ScalarIndex
         adopt(x, n, dim, distance);
     }
     ScalarQuantizer quantizer_;
+};
+
+// Exact index of f32 queries (never quantized) over BQ bits packed 32 to a word on the device (include/vqhip.h,
+// vqhip_abin_*): BinaryIndex's rows and word layout, but the distance is Distance::compute(q, v(bits)) with v(bit) = bit ?
+// high : low, under any metric, cosine included.  Every result equals FlatIndex over the dequantized rows and ScalarIndex
+// over the bits as 0/1 bytes under ScalarQuantizer(low, high, 2): (row index, distance) pairs [nq][topk], nearest first,
+// NaN last, ties to the lower row.  Built from f32 rows, u8 codes or packed words [n][ceil(dim / 32)] (pad bits zero); the
+// twin of a BinaryIndex b is AsymmetricBinaryIndex(b.packed().data(), b.size(), b.dim(), b.quantizer(), distance).  The
+// arguments are checked before the device is touched.
+class AsymmetricBinaryIndex
+    : public detail::ExactResidentIndex<vqhip_abin, vqhip_abin_destroy, vqhip_abin_search, vqhip_abin_range_search, vqhip_abin_rerank,
+                                        vqhip_abin_search_masked, vqhip_abin_range_search_masked, vqhip_abin_remove,
+                                        vqhip_abin_remove_device> {
+   public:
+    using Source = BinaryIndex::Source;
+    AsymmetricBinaryIndex(const float *rows, std::size_t n, std::size_t dim, BinaryQuantizer quantizer = BinaryQuantizer(0.0f, 0, 1),
+                          Distance distance = Distance())
+        : quantizer_(quantizer) {
+        init(rows, Source::Rows, n, dim, distance);
+    }
+    AsymmetricBinaryIndex(const std::uint8_t *codes, std::size_t n, std::size_t dim, BinaryQuantizer quantizer, Distance distance = Distance())
+        : quantizer_(quantizer) {
+        init(codes, Source::Codes, n, dim, distance);
+    }
+    AsymmetricBinaryIndex(const std::uint32_t *words, std::size_t n, std::size_t dim, BinaryQuantizer quantizer, Distance distance = Distance())
+        : quantizer_(quantizer) {
+        init(words, Source::Packed, n, dim, distance);
+    }
+    std::size_t words_per_row() const { return (dim_ + 31) / 32; }
+    const BinaryQuantizer &quantizer() const { return quantizer_; }
+    // the packed rows [n][words_per_row()]
+    std::vector<std::uint32_t> packed() const {
+        std::vector<std::uint32_t> out(n_ * words_per_row());
+        detail::check(vqhip_abin_packed(ix_.get(), out.data()));
+        return out;
+    }
+    // append b rows in one of the constructors' three forms, from host memory or from a device pointer (f32 rows and words
+    // 4-byte aligned; a pad bit set there is an FfiError that leaves the index as it was); returns their ids n .. n + b - 1
+    std::vector<std::uint32_t> add(const float *rows, std::size_t b) { return add_from(rows, Source::Rows, b, false); }
+    std::vector<std::uint32_t> add_codes(const std::uint8_t *codes, std::size_t b) { return add_from(codes, Source::Codes, b, false); }
+    std::vector<std::uint32_t> add_packed(const std::uint32_t *words, std::size_t b) {
+        if (words) detail::check_pad_bits(words, b, dim_);
+        return add_from(words, Source::Packed, b, false);
+    }
+    std::vector<std::uint32_t> add_device(const void *dev_src, Source kind, std::size_t b) { return add_from(dev_src, kind, b, true); }
+
+   private:
+    std::vector<std::uint32_t> add_from(const void *src, Source kind, std::size_t b, bool device) {
+        return append(src, b, [&](vqhip_abin *h) {
+            return device ? vqhip_abin_add_device(h, src, (int)kind, b) : vqhip_abin_add(h, src, (int)kind, b);
+        });
+    }
+    void init(const void *src, Source kind, std::size_t n, std::size_t dim, Distance distance) {
+        if (n == 0) throw VqError::EmptyInput();
+        if (dim == 0 || dim > VQHIP_BINARY_MAX_DIM) throw VqError::InvalidParameter("dim", "must be between 1 and 8192");
+        if (n >= (std::size_t(1) << 32)) throw VqError::InvalidParameter("rows", "at most 2^32 - 1 rows");
+        if (kind == Source::Packed && src) detail::check_pad_bits(static_cast<const std::uint32_t *>(src), n, dim);
+        vqhip_abin *x = nullptr;
+        detail::check(vqhip_abin_create(src, (int)kind, n, (std::uint32_t)dim, quantizer_.threshold(), quantizer_.low(), quantizer_.high(),
+                                        (int)distance.kind(), &x));
+        adopt(x, n, dim, distance);
+    }
+    BinaryQuantizer quantizer_;
 };
 
 namespace detail {

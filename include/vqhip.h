@@ -754,6 +754,67 @@ int vqhip_binary_add_device(vqhip_binary *b, const void *dev_src, int kind, uint
 int vqhip_binary_remove(vqhip_binary *b, const uint32_t *remove_words, uint64_t *removed);
 int vqhip_binary_remove_device(vqhip_binary *b, const uint32_t *dev_remove_words, uint64_t *removed);
 
+/* ---- asymmetric binary index: f32 queries over packed BQ bits, exact (k_abin.hip, bit_decode.hpp) -------
+ * No reference counterpart.  The binary index above binarises the query and ranks by the Hamming distance.  This index
+ * keeps the same bits and nothing else, leaves the query in f32 and computes its exact distance to the DEQUANTIZED row:
+ * the third index of exact distances beside vqhip_flat and vqhip_sqindex, at d / 8 bytes a row (W words, plus 4 bytes
+ * for the row norm under the cosines).
+ *   bits    a BinaryQuantizer(threshold, low, high) fixes them on the way in, as vqhip_binary's: f32 x: x >= threshold
+ *           (NaN -> 0, -0.0 == 0.0); u8 code c: c >= high.
+ *   layout  vqhip_binary's: row i, dimension t in u32 word i * W + t / 32, bit t % 32 (LSB first), W = ceil(d / 32), pad
+ *           bits zero.  vqhip_abin_packed gives exactly what vqhip_binary_packed gives for the same source.
+ *   v(bit)  = bit ? (float)high : (float)low, the BQ decode rule, on the way out.
+ *   D(q, i) = Distance::compute(q, v(bits[i])) bit for bit, for all five metrics, the cosines included: the pair summed
+ *           sequentially over t = 0..d-1 from -0.0f, one rounding per operation, no fused multiply-add; Euclidean = sqrtf
+ *           of the sum; cosine through vq_cosine_finish, the row norm sqrtf of the sequential sum of v^2 computed once at
+ *           create (and for the rows of an add) and the query norm once per call.  Queries are f32 and never quantized.
+ *   search / rerank / range_search and their masked forms = vqhip_flat_* over the rows vqhip_bq_decode gives for the
+ *           bits, and = vqhip_sqindex_* over the bits as 0/1 bytes under ScalarQuantizer(low, high, 2) (low + 1 * (high -
+ *           low) is exact for u8 values): equal indices, distances equal as uint32 bits.  That is the order (key(D),
+ *           row), NaN last and reported as 0x7FC00000, ties to the lower row; a masked query with fewer than topk allowed
+ *           rows is padded with idx 0xFFFFFFFF and dist +inf; a rerank id >= n is flagged on the device, never read, and
+ *           gives VQHIP_ERR_INVALID_INPUT.  Under a cosine with low = 0 a row without a set bit has norm 0 and takes
+ *           vq_cosine_finish's EPSILON rule, as the same row does in the flat index.
+ *   add / remove = the rules of "adding and removing rows" above: add takes create's three source kinds with create's
+ *           checks; a removal moves the row norms with the rows and computes none anew.
+ * Limits: 1 <= d <= 8192, 1 <= n < 2^32, 1 <= topk <= min(n, 1024), nq < 2^32 (served in batches), rerank lists of
+ * 1..4096 distinct ids.  The source of create and add is f32 rows [n][d] (kind VQHIP_BINARY_F32), u8 codes [n][d]
+ * (VQHIP_BINARY_U8) or packed words [n][W] (VQHIP_BINARY_PACKED: a set pad bit is VQHIP_ERR_INVALID_INPUT, in the host
+ * and the device form); device f32 rows and words are 4-byte aligned, else VQHIP_ERR_INVALID_INPUT.  Every metric of the
+ * flat index is accepted.  Every parameter is checked before any device work, in the order of the sibling entry points
+ * of vqhip_sqindex.  Host forms return when the results are there; search_device is asynchronous on the current stream.
+ * One lock per handle, as vqhip_flat's.  info: any output pointer may be NULL. */
+typedef struct vqhip_abin vqhip_abin;
+int vqhip_abin_create(const void *src, int kind, uint64_t n, uint32_t d, float threshold, uint32_t low, uint32_t high,
+                      int metric, vqhip_abin **out);
+int vqhip_abin_create_device(const void *dev_src, int kind, uint64_t n, uint32_t d, float threshold, uint32_t low,
+                             uint32_t high, int metric, vqhip_abin **out);
+int vqhip_abin_destroy(vqhip_abin *x);
+int vqhip_abin_info(const vqhip_abin *x, uint64_t *n, uint32_t *d, float *threshold, uint32_t *low, uint32_t *high,
+                    int *metric);
+int vqhip_abin_packed(vqhip_abin *x, uint32_t *words);
+int vqhip_abin_search(vqhip_abin *x, const float *queries, uint32_t nq, uint32_t topk, uint32_t *idx_out, float *dist_out);
+int vqhip_abin_search_device(vqhip_abin *x, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx,
+                             void *dev_dist);
+int vqhip_abin_search_masked(vqhip_abin *x, const float *queries, uint32_t nq, uint32_t topk, const uint32_t *allowed,
+                             uint32_t *idx_out, float *dist_out);
+int vqhip_abin_search_masked_device(vqhip_abin *x, const void *dev_queries, uint32_t nq, uint32_t topk,
+                                    const uint32_t *dev_allowed, void *dev_idx, void *dev_dist);
+int vqhip_abin_rerank(vqhip_abin *x, const float *queries, uint32_t nq, const uint32_t *cand, uint32_t c, uint32_t topk,
+                      uint32_t *idx_out, float *dist_out);
+int vqhip_abin_range_search(vqhip_abin *x, const float *queries, uint32_t nq, const float *radii, uint64_t max_results,
+                            vqhip_range **out);
+int vqhip_abin_range_search_device(vqhip_abin *x, const void *dev_queries, uint32_t nq, const float *radii,
+                                   uint64_t max_results, vqhip_range **out);
+int vqhip_abin_range_search_masked(vqhip_abin *x, const float *queries, uint32_t nq, const float *radii, uint64_t max_results,
+                                   const uint32_t *allowed, vqhip_range **out);
+int vqhip_abin_range_search_masked_device(vqhip_abin *x, const void *dev_queries, uint32_t nq, const float *radii,
+                                          uint64_t max_results, const uint32_t *dev_allowed, vqhip_range **out);
+int vqhip_abin_add(vqhip_abin *x, const void *src, int kind, uint64_t n_add);
+int vqhip_abin_add_device(vqhip_abin *x, const void *dev_src, int kind, uint64_t n_add);
+int vqhip_abin_remove(vqhip_abin *x, const uint32_t *remove_words, uint64_t *removed);
+int vqhip_abin_remove_device(vqhip_abin *x, const uint32_t *dev_remove_words, uint64_t *removed);
+
 /* ---- inverted-file PQ index: search only the probed lists (k_ivf.hip) -----------------------
  * No reference counterpart.  An index holds coarse centroids C [nlist][dim] f32 (1 <= nlist <= 65536), PQ codebooks
  * cb [m][k][sub_dim] (dim = m * sub_dim) and a metric: squared Euclidean, Euclidean or Manhattan (cosine is refused with

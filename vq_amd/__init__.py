@@ -2,8 +2,8 @@
 encode path of CogitatorTech/vq, and of its elementwise scalar / binary quantizers, behind the
 reference's own Quantizer interface, exact k-NN search over resident rows (FlatIndex), an inverted-file
 index over PQ codes (IVFPQIndex) one over the rows themselves (IVFFlatIndex) and one over SQ codes
-(IVFScalarIndex) and one over packed BQ bits (IVFBinaryIndex), a Hamming index over packed BQ codes (BinaryIndex) and an exact index over
-resident SQ codes (ScalarIndex).
+(IVFScalarIndex) and one over packed BQ bits (IVFBinaryIndex), a Hamming index over packed BQ codes (BinaryIndex), an exact index over
+resident SQ codes (ScalarIndex) and an exact index of f32 queries over packed BQ bits (AsymmetricBinaryIndex).
 
 The compute path is libvqhip.so (hand-written HIP for CDNA4, C ABI in include/vqhip.h).
 Importing the package does not need a GPU; using any quantizer does, and fails loudly
@@ -12,6 +12,7 @@ Importing the package does not need a GPU; using any quantizer does, and fails l
 from .distance import Distance
 from .errors import (DimensionMismatch, EmptyInput, FfiError, InvalidData, InvalidParameter,
                      VqError)
+from .asymmetric_binary import AsymmetricBinaryIndex
 from .binary import BinaryIndex
 from .bq import BinaryQuantizer
 from ._lib import RangeResult
@@ -27,7 +28,7 @@ from .sq import ScalarQuantizer
 from .tsvq import TSVQ
 
 __all__ = [
-    "Distance", "BinaryIndex", "BinaryQuantizer", "FlatIndex", "IVFBinaryIndex", "IVFFlatIndex", "IVFPQIndex", "IVFScalarIndex", "RangeResult", "ScalarIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
+    "Distance", "AsymmetricBinaryIndex", "BinaryIndex", "BinaryQuantizer", "FlatIndex", "IVFBinaryIndex", "IVFFlatIndex", "IVFPQIndex", "IVFScalarIndex", "RangeResult", "ScalarIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
     "InvalidParameter", "InvalidData", "FfiError", "get_simd_backend", "pack_row_mask",
 ]
 

@@ -211,6 +211,24 @@ SIGNATURES = {
     "vqhip_binary_add_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64]),
     "vqhip_binary_remove": (C.c_int, [_vp, _u32p, _u64p]),
     "vqhip_binary_remove_device": (C.c_int, [_vp, _vp, _u64p]),
+    "vqhip_abin_create": (C.c_int, [_vp, C.c_int, C.c_uint64, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_int, _vpp]),
+    "vqhip_abin_create_device": (C.c_int, [_vp, C.c_int, C.c_uint64, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_int, _vpp]),
+    "vqhip_abin_destroy": (C.c_int, [_vp]),
+    "vqhip_abin_info": (C.c_int, [_vp, _u64p, _u32p, C.POINTER(C.c_float), _u32p, _u32p, C.POINTER(C.c_int)]),
+    "vqhip_abin_packed": (C.c_int, [_vp, _u32p]),
+    "vqhip_abin_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "vqhip_abin_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "vqhip_abin_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p]),
+    "vqhip_abin_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "vqhip_abin_rerank": (C.c_int, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "vqhip_abin_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, _f32p, C.c_uint64, _vpp]),
+    "vqhip_abin_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, _f32p, C.c_uint64, _vpp]),
+    "vqhip_abin_range_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, _f32p, C.c_uint64, _u32p, _vpp]),
+    "vqhip_abin_range_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, _f32p, C.c_uint64, _vp, _vpp]),
+    "vqhip_abin_add": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64]),
+    "vqhip_abin_add_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64]),
+    "vqhip_abin_remove": (C.c_int, [_vp, _u32p, _u64p]),
+    "vqhip_abin_remove_device": (C.c_int, [_vp, _vp, _u64p]),
     "vqhip_ivfbin_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p]),
     "vqhip_ivfbin_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "vqhip_ivfbin_range_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint64, _u32p, _vpp]),
@@ -1082,6 +1100,30 @@ class SQIndex(_ResidentExactHandle):
     def codes(self) -> np.ndarray:
         out = np.empty((self.n, self.d), np.uint8)
         check(load().vqhip_sqindex_codes(self.raw, ptr(out, _u8p)))
+        return out
+
+
+class ABin(_ResidentExactHandle):
+    """vqhip_abin: BQ bits packed 32 to a word on the device, exact search, range search and rerank of f32 queries against
+    the dequantized rows (k_abin.hip)"""
+
+    _prefix = "vqhip_abin"
+    _destroy = "vqhip_abin_destroy"
+
+    def __init__(self, src, kind: int, n: int, d: int, threshold: float, low: int, high: int, metric: int,
+                 dev_src: int | None = None):
+        """src: a C-contiguous host array of the kind (f32 [n][d], u8 [n][d], u32 [n][W]), or dev_src a device pointer"""
+        h = C.c_void_p()
+        name = "vqhip_abin_create" + ("_device" if dev_src is not None else "")
+        p = C.c_void_p(dev_src) if dev_src is not None else src.ctypes.data_as(_vp)
+        check(getattr(load(), name)(p, int(kind), int(n), int(d), float(threshold), int(low), int(high), int(metric), C.byref(h)))
+        super().__init__(h)
+        self.n, self.d, self.metric = int(n), int(d), int(metric)
+        self.words = (self.d + 31) // 32
+
+    def packed(self) -> np.ndarray:
+        out = np.empty((self.n, self.words), np.uint32)
+        check(load().vqhip_abin_packed(self.raw, ptr(out, _u32p)))
         return out
 
 

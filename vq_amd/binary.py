@@ -148,7 +148,9 @@ class BinaryIndex(BinaryFilterMixin, ResidentIndex):
 
     def search(self, queries, topk: int = 10, *, rerank=None, candidates=None):
         """(nq, d) float32 queries -> (indices uint32 (nq, topk), distances float32 (nq, topk)), nearest first.
-        rerank: a FlatIndex or a ScalarIndex over the same rows -- the binary search gives `candidates` per query
+        rerank: a FlatIndex, a ScalarIndex or an AsymmetricBinaryIndex (the asymmetric twin over the same bits:
+        ``AsymmetricBinaryIndex.from_packed(self.packed(), self.dim, self.quantizer, distance)``) over the same rows -- the
+        binary search gives `candidates` per query
         (default 4 topk, at most 1024 and n), that index reranks them exactly in its own metric."""
         q = self._queries(queries)
         k = self._topk(topk)

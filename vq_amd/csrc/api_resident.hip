@@ -1,4 +1,4 @@
-// api_resident.hip -- extern "C" entry points of the resident indexes (vqhip_flat, vqhip_sqindex, vqhip_binary) and
+// api_resident.hip -- extern "C" entry points of the resident indexes (vqhip_flat, vqhip_sqindex, vqhip_binary, vqhip_abin) and
 // their host layer: searches, reranks, range searches, adding and removing rows.  Host-side orchestration only.
 #include <algorithm>
 #include <memory>
@@ -739,9 +739,71 @@ static int binary_range(vqhip_binary *b, const void *queries, bool host, uint32_
     });
 }
 
-static int binary_check(int kind, uint64_t n, uint32_t d, float threshold, uint32_t low, uint32_t high, int metric) {
+// ---- the three source kinds of packed rows (vqhip_binary's and vqhip_abin's create and add) ----
+static int bits_check_kind(int kind) {
     if (kind != VQHIP_BINARY_F32 && kind != VQHIP_BINARY_U8 && kind != VQHIP_BINARY_PACKED)
         return fail(VQHIP_ERR_INVALID_INPUT, "source kind must be 0 (f32), 1 (u8 codes) or 2 (packed words), not %d", kind);
+    return VQHIP_OK;
+}
+
+// a device source of f32 rows or packed words is read as dwords
+static int bits_check_aligned(const void *dev_src, int kind) {
+    if (kind == VQHIP_BINARY_F32 && (reinterpret_cast<uintptr_t>(dev_src) & 3))
+        return fail(VQHIP_ERR_INVALID_INPUT, "rows are not 4-byte aligned");
+    if (kind == VQHIP_BINARY_PACKED && (reinterpret_cast<uintptr_t>(dev_src) & 3))
+        return fail(VQHIP_ERR_INVALID_INPUT, "words are not 4-byte aligned");
+    return VQHIP_OK;
+}
+
+// host words [n][W]: no pad bit may be set (added: the rows of an add, named so in the message)
+static int bits_check_pad(const void *src, uint64_t n, uint32_t d, bool added) {
+    if (d % 32 == 0) return VQHIP_OK;
+    const uint32_t W = bin_words(d);
+    const uint32_t *w = static_cast<const uint32_t *>(src), mask = (1u << (d % 32)) - 1u;
+    for (uint64_t i = 0; i < n; ++i)
+        if (w[i * W + W - 1] & ~mask)
+            return fail(VQHIP_ERR_INVALID_INPUT, added ? "added row %llu has a pad bit set" : "row %llu has a pad bit set", (unsigned long long)i);
+    return VQHIP_OK;
+}
+
+// n rows of `kind` from host (kind_copy = H2D) or device memory as packed words at dst [n][W] on the device: words are
+// copied (a device source's pad bits checked behind the copy, which waits for s), rows and codes packed by the bit rule
+// (thr, high) -- host ones a piece at a time
+static int bits_store(const void *src, hipMemcpyKind kind_copy, int kind, uint64_t n, uint32_t d, float thr, uint32_t high,
+                      uint32_t *dst, bool added, hipStream_t s) {
+    const uint32_t W = bin_words(d);
+    if (kind == VQHIP_BINARY_PACKED) {
+        VQ_HIP(hipMemcpyAsync(dst, src, (size_t)n * W * 4, kind_copy, s));
+        if (kind_copy == hipMemcpyDeviceToDevice && d % 32) {
+            DevBuf bad;
+            uint32_t h_bad = 0;
+            VQ_TRY(bad.alloc(4));
+            VQ_HIP(hipMemsetAsync(bad.p, 0, 4, s));
+            VQ_TRY(launch_bin_padcheck(dst, n, d, bad.as<uint32_t>(), s));
+            VQ_HIP(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, s));
+            VQ_HIP(hipStreamSynchronize(s));
+            if (h_bad) return fail(VQHIP_ERR_INVALID_INPUT, added ? "an added packed row has a pad bit set" : "a packed row has a pad bit set");
+        }
+        return VQHIP_OK;
+    }
+    if (kind_copy == hipMemcpyDeviceToDevice) return launch_bq_pack(src, kind, n, d, thr, high, dst, s);
+    return staged_rows(src, n, (size_t)d * (kind == VQHIP_BINARY_U8 ? 1 : 4), s, [&](const void *piece, uint64_t r0, uint64_t rn) {
+        return launch_bq_pack(piece, kind, rn, d, thr, high, dst + r0 * W, s);
+    });
+}
+
+// what an add checks of its source before the handle's lock: the kind, a device source's alignment, a host source's pad bits
+static int bits_check_add(const void *src, hipMemcpyKind kind_copy, int kind, uint64_t n_add, uint32_t d) {
+    if (!src) return fail(VQHIP_ERR_NULL_PTR, "source is NULL");
+    VQ_TRY(bits_check_kind(kind));
+    const bool dev = kind_copy == hipMemcpyDeviceToDevice;
+    if (dev) VQ_TRY(bits_check_aligned(src, kind));
+    if (kind == VQHIP_BINARY_PACKED && !dev) VQ_TRY(bits_check_pad(src, n_add, d, true));
+    return VQHIP_OK;
+}
+
+static int binary_check(int kind, uint64_t n, uint32_t d, float threshold, uint32_t low, uint32_t high, int metric) {
+    VQ_TRY(bits_check_kind(kind));
     if (d == 0 || d > VQHIP_BINARY_MAX_DIM) return fail(VQHIP_ERR_INVALID_INPUT, "d %u must be in [1, 8192]", d);
     VQ_TRY(check_rows(n));
     VQ_TRY(bq_check(threshold, low, high));
@@ -756,11 +818,7 @@ static int binary_create(const void *src, hipMemcpyKind kind_copy, int kind, uin
     if (!src) return fail(VQHIP_ERR_NULL_PTR, "source is NULL");
     VQ_TRY(binary_check(kind, n, d, threshold, low, high, metric));
     const uint32_t W = bin_words(d);
-    if (kind == VQHIP_BINARY_PACKED && kind_copy == hipMemcpyHostToDevice && d % 32) {
-        const uint32_t *w = static_cast<const uint32_t *>(src), mask = (1u << (d % 32)) - 1u;
-        for (uint64_t i = 0; i < n; ++i)
-            if (w[i * W + W - 1] & ~mask) return fail(VQHIP_ERR_INVALID_INPUT, "row %llu has a pad bit set", (unsigned long long)i);
-    }
+    if (kind == VQHIP_BINARY_PACKED && kind_copy == hipMemcpyHostToDevice) VQ_TRY(bits_check_pad(src, n, d, false));
     VQ_TRY(require_gfx950());
     hipStream_t s;
     VQ_TRY(current_stream(&s));
@@ -771,25 +829,7 @@ static int binary_create(const void *src, hipMemcpyKind kind_copy, int kind, uin
     VQ_TRY(b->table.alloc((size_t)(d + 1) * 4));
     VQ_HIP(hipMemcpyAsync(b->table.p, S.data(), (size_t)(d + 1) * 4, hipMemcpyHostToDevice, s));
     VQ_TRY(b->words.alloc((size_t)n * W * 4));
-    if (kind == VQHIP_BINARY_PACKED) {
-        VQ_HIP(hipMemcpyAsync(b->words.p, src, (size_t)n * W * 4, kind_copy, s));
-        if (kind_copy == hipMemcpyDeviceToDevice && d % 32) {
-            DevBuf bad;
-            uint32_t h_bad = 0;
-            VQ_TRY(bad.alloc(4));
-            VQ_HIP(hipMemsetAsync(bad.p, 0, 4, s));
-            VQ_TRY(launch_bin_padcheck(b->words.as<uint32_t>(), n, d, bad.as<uint32_t>(), s));
-            VQ_HIP(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, s));
-            VQ_HIP(hipStreamSynchronize(s));
-            if (h_bad) return fail(VQHIP_ERR_INVALID_INPUT, "a packed row has a pad bit set");
-        }
-    } else if (kind_copy == hipMemcpyDeviceToDevice) {
-        VQ_TRY(launch_bq_pack(src, kind, n, d, threshold, high, b->words.as<uint32_t>(), s));
-    } else {  // host rows are packed a piece at a time
-        VQ_TRY(staged_rows(src, n, (size_t)d * (kind == VQHIP_BINARY_U8 ? 1 : 4), s, [&](const void *piece, uint64_t r0, uint64_t rn) {
-            return launch_bq_pack(piece, kind, rn, d, threshold, high, b->words.as<uint32_t>() + r0 * W, s);
-        }));
-    }
+    VQ_TRY(bits_store(src, kind_copy, kind, n, d, threshold, high, b->words.as<uint32_t>(), false, s));
     VQ_HIP(hipStreamSynchronize(s));  // the caller may free or change its source once this returns
     *out = b.release();
     return VQHIP_OK;
@@ -799,38 +839,9 @@ static int binary_create(const void *src, hipMemcpyKind kind_copy, int kind, uin
 static int binary_add(vqhip_binary *b, const void *src, hipMemcpyKind kind_copy, int kind, uint64_t n_add) {
     if (!b) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
     if (n_add == 0) return VQHIP_OK;
-    if (!src) return fail(VQHIP_ERR_NULL_PTR, "source is NULL");
-    if (kind != VQHIP_BINARY_F32 && kind != VQHIP_BINARY_U8 && kind != VQHIP_BINARY_PACKED)
-        return fail(VQHIP_ERR_INVALID_INPUT, "source kind must be 0 (f32), 1 (u8 codes) or 2 (packed words), not %d", kind);
-    const bool dev = kind_copy == hipMemcpyDeviceToDevice;
-    if (dev && kind != VQHIP_BINARY_U8 && (reinterpret_cast<uintptr_t>(src) & 3))
-        return fail(VQHIP_ERR_INVALID_INPUT, kind == VQHIP_BINARY_F32 ? "rows are not 4-byte aligned" : "words are not 4-byte aligned");
-    const uint32_t d = b->d, W = b->W;  // (fixed at create)
-    if (kind == VQHIP_BINARY_PACKED && !dev && d % 32) {
-        const uint32_t *w = static_cast<const uint32_t *>(src), mask = (1u << (d % 32)) - 1u;
-        for (uint64_t i = 0; i < n_add; ++i)
-            if (w[i * W + W - 1] & ~mask) return fail(VQHIP_ERR_INVALID_INPUT, "added row %llu has a pad bit set", (unsigned long long)i);
-    }
+    VQ_TRY(bits_check_add(src, kind_copy, kind, n_add, b->d));  // (d is fixed at create)
     return resident_add(b, src, n_add, [&](char *dst, hipStream_t s) -> int {
-        uint32_t *words = reinterpret_cast<uint32_t *>(dst);
-        if (kind == VQHIP_BINARY_PACKED) {
-            VQ_HIP(hipMemcpyAsync(words, src, (size_t)n_add * W * 4, kind_copy, s));
-            if (dev && d % 32) {
-                DevBuf bad;
-                uint32_t h_bad = 0;
-                VQ_TRY(bad.alloc(4));
-                VQ_HIP(hipMemsetAsync(bad.p, 0, 4, s));
-                VQ_TRY(launch_bin_padcheck(words, n_add, d, bad.as<uint32_t>(), s));
-                VQ_HIP(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, s));
-                VQ_HIP(hipStreamSynchronize(s));
-                if (h_bad) return fail(VQHIP_ERR_INVALID_INPUT, "an added packed row has a pad bit set");
-            }
-            return VQHIP_OK;
-        }
-        if (dev) return launch_bq_pack(src, kind, n_add, d, b->thr, b->high, words, s);
-        return staged_rows(src, n_add, (size_t)d * (kind == VQHIP_BINARY_U8 ? 1 : 4), s, [&](const void *piece, uint64_t r0, uint64_t rn) {
-            return launch_bq_pack(piece, kind, rn, d, b->thr, b->high, words + r0 * W, s);
-        });
+        return bits_store(src, kind_copy, kind, n_add, b->d, b->thr, b->high, reinterpret_cast<uint32_t *>(dst), true, s);
     });
 }
 
@@ -882,10 +893,7 @@ int vqhip_binary_create(const void *src, int kind, uint64_t n, uint32_t d, float
 int vqhip_binary_create_device(const void *dev_src, int kind, uint64_t n, uint32_t d, float threshold, uint32_t low,
                                uint32_t high, int metric, vqhip_binary **out) {
     VQ_API_BEGIN
-    if (kind == VQHIP_BINARY_F32 && (reinterpret_cast<uintptr_t>(dev_src) & 3))
-        return fail(VQHIP_ERR_INVALID_INPUT, "rows are not 4-byte aligned");
-    if (kind == VQHIP_BINARY_PACKED && (reinterpret_cast<uintptr_t>(dev_src) & 3))
-        return fail(VQHIP_ERR_INVALID_INPUT, "words are not 4-byte aligned");
+    VQ_TRY(bits_check_aligned(dev_src, kind));
     return binary_create(dev_src, hipMemcpyDeviceToDevice, kind, n, d, threshold, low, high, metric, out);
     VQ_API_END
 }
@@ -995,6 +1003,205 @@ int vqhip_binary_range_search_device(vqhip_binary *b, const void *dev_queries, u
                                      uint64_t max_results, vqhip_range **out) {
     VQ_API_BEGIN
     return binary_range(b, dev_queries, false, nq, hradii, max_results, out);
+    VQ_API_END
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ asymmetric binary index (k_abin.hip) ----
+// The binary index's packed rows under the exact distances of the flat and the scalar index: f32 queries against
+// v(bit) = bit ? high : low.  The third member of ExactResident.
+struct vqhip_abin : ExactResident<vqhip_abin> {
+    uint32_t W = 0, low = 0, high = 1;
+    float thr = 0;
+    DevBuf words;  // [n][W] packed rows; `bytes` is the capacity (an add grows it)
+
+    float lo() const { return (float)low; }
+    float hi() const { return (float)high; }
+    DevBuf &payload() { return words; }
+    size_t row_bytes() const { return (size_t)W * 4; }
+    int norms_enqueue(const void *P, uint64_t count, float *out, hipStream_t s) {
+        return launch_abin_norms(static_cast<const uint32_t *>(P), count, d, lo(), hi(), out, s);
+    }
+    int launch_search(const float *queries_dev, const float *qn, uint32_t nq, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
+                      hipStream_t s) {
+        return launch_abin_search(metric, words.as<uint32_t>(), n, d, lo(), hi(), rnorm.as<float>(), queries_dev, qn, nq, topk,
+                                  dist.as<float>(), state.p, cand.as<unsigned long long>(), idx_dev, dist_dev, mask, s);
+    }
+    int launch_rerank(const float *qn, uint32_t nq, uint32_t c, uint32_t topk, hipStream_t s) {
+        return launch_abin_rerank(metric, words.as<uint32_t>(), n, d, lo(), hi(), rnorm.as<float>(), q.as<float>(), qn, nq,
+                                  rr_cand.as<uint32_t>(), c, topk, idx.as<uint32_t>(), out.as<float>(), rr_err.as<uint32_t>(), s);
+    }
+    int launch_range(const float *queries_dev, const float *qn, uint32_t nq, uint64_t max_results, RangeOut *r, hipStream_t s) {
+        return launch_abin_range(metric, words.as<uint32_t>(), n, d, lo(), hi(), rnorm.as<float>(), queries_dev, qn, nq, radii.as<float>(),
+                                 max_results, dist.as<float>(), state.p, range_ws.p, r, mask, s);
+    }
+};
+
+// vqhip_binary_create's sources and checks, but for the metric: every one of the five, cosine included
+static int abin_create(const void *src, hipMemcpyKind kind_copy, int kind, uint64_t n, uint32_t d, float threshold, uint32_t low,
+                       uint32_t high, int metric, vqhip_abin **out) {
+    if (!out) return fail(VQHIP_ERR_NULL_PTR, "out is NULL");
+    *out = nullptr;
+    if (!src) return fail(VQHIP_ERR_NULL_PTR, "source is NULL");
+    VQ_TRY(bits_check_kind(kind));
+    if (d == 0 || d > VQHIP_BINARY_MAX_DIM) return fail(VQHIP_ERR_INVALID_INPUT, "d %u must be in [1, 8192]", d);
+    VQ_TRY(check_rows(n));
+    VQ_TRY(bq_check(threshold, low, high));
+    VQ_TRY(check_metric(metric));
+    if (kind == VQHIP_BINARY_PACKED && kind_copy == hipMemcpyHostToDevice) VQ_TRY(bits_check_pad(src, n, d, false));
+    VQ_TRY(require_gfx950());
+    hipStream_t s;
+    VQ_TRY(current_stream(&s));
+    std::unique_ptr<vqhip_abin> x(new vqhip_abin());
+    x->n = n, x->d = d, x->W = bin_words(d), x->low = low, x->high = high, x->thr = threshold, x->metric = metric;
+    VQ_TRY(x->words.alloc((size_t)n * x->W * 4));
+    VQ_TRY(bits_store(src, kind_copy, kind, n, d, threshold, high, x->words.as<uint32_t>(), false, s));
+    if (vq_is_cos(metric)) {
+        VQ_TRY(x->rnorm.alloc((size_t)n * 4));
+        VQ_TRY(x->norms_enqueue(x->words.p, n, x->rnorm.as<float>(), s));
+    }
+    VQ_HIP(hipStreamSynchronize(s));  // the caller may free or change its source once this returns
+    *out = x.release();
+    return VQHIP_OK;
+}
+
+// n_add rows of `kind` behind the last, with create's checks of the source
+static int abin_add(vqhip_abin *x, const void *src, hipMemcpyKind kind_copy, int kind, uint64_t n_add) {
+    if (!x) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (n_add == 0) return VQHIP_OK;
+    VQ_TRY(bits_check_add(src, kind_copy, kind, n_add, x->d));  // (d is fixed at create)
+    return resident_add(x, src, n_add, [&](char *dst, hipStream_t s) -> int {
+        return bits_store(src, kind_copy, kind, n_add, x->d, x->thr, x->high, reinterpret_cast<uint32_t *>(dst), true, s);
+    });
+}
+
+extern "C" {
+
+int vqhip_abin_create(const void *src, int kind, uint64_t n, uint32_t d, float threshold, uint32_t low, uint32_t high, int metric,
+                      vqhip_abin **out) {
+    VQ_API_BEGIN
+    return abin_create(src, hipMemcpyHostToDevice, kind, n, d, threshold, low, high, metric, out);
+    VQ_API_END
+}
+
+int vqhip_abin_create_device(const void *dev_src, int kind, uint64_t n, uint32_t d, float threshold, uint32_t low, uint32_t high,
+                             int metric, vqhip_abin **out) {
+    VQ_API_BEGIN
+    VQ_TRY(bits_check_aligned(dev_src, kind));
+    return abin_create(dev_src, hipMemcpyDeviceToDevice, kind, n, d, threshold, low, high, metric, out);
+    VQ_API_END
+}
+
+int vqhip_abin_destroy(vqhip_abin *x) {
+    delete x;
+    return VQHIP_OK;
+}
+
+int vqhip_abin_info(const vqhip_abin *x, uint64_t *n, uint32_t *d, float *threshold, uint32_t *low, uint32_t *high, int *metric) {
+    if (!x) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (n) *n = x->n;
+    if (d) *d = x->d;
+    if (threshold) *threshold = x->thr;
+    if (low) *low = x->low;
+    if (high) *high = x->high;
+    if (metric) *metric = x->metric;
+    return VQHIP_OK;
+}
+
+int vqhip_abin_packed(vqhip_abin *x, uint32_t *words) {
+    VQ_API_BEGIN
+    return resident_enter(x, words != nullptr, no_checks, 1, nullptr, [&](Entry &in, hipStream_t s) -> int {
+        VQ_HIP(hipMemcpyAsync(words, x->words.p, (size_t)x->n * x->W * 4, hipMemcpyDeviceToHost, s));
+        VQ_HIP(hipStreamSynchronize(s));
+        in.synced();
+        return VQHIP_OK;
+    });
+    VQ_API_END
+}
+
+int vqhip_abin_search(vqhip_abin *x, const float *queries, uint32_t nq, uint32_t topk, uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    return resident_search(x, queries, nq, topk, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_abin_search_device(vqhip_abin *x, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx, void *dev_dist) {
+    VQ_API_BEGIN
+    return resident_search_device(x, dev_queries, nq, topk, dev_idx, dev_dist);
+    VQ_API_END
+}
+
+int vqhip_abin_search_masked(vqhip_abin *x, const float *queries, uint32_t nq, uint32_t topk, const uint32_t *allowed,
+                             uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    return exact_search_masked(x, queries, nq, topk, allowed, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_abin_search_masked_device(vqhip_abin *x, const void *dev_queries, uint32_t nq, uint32_t topk, const uint32_t *dev_allowed,
+                                    void *dev_idx, void *dev_dist) {
+    VQ_API_BEGIN
+    return exact_search_masked_device(x, dev_queries, nq, topk, dev_allowed, dev_idx, dev_dist);
+    VQ_API_END
+}
+
+int vqhip_abin_rerank(vqhip_abin *x, const float *queries, uint32_t nq, const uint32_t *cand, uint32_t c, uint32_t topk,
+                      uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    return exact_rerank(x, queries, nq, cand, c, topk, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_abin_range_search(vqhip_abin *x, const float *queries, uint32_t nq, const float *radii, uint64_t max_results,
+                            vqhip_range **out) {
+    VQ_API_BEGIN
+    return range_search(x, queries, true, nq, radii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_abin_range_search_device(vqhip_abin *x, const void *dev_queries, uint32_t nq, const float *radii, uint64_t max_results,
+                                   vqhip_range **out) {
+    VQ_API_BEGIN
+    return range_search(x, dev_queries, false, nq, radii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_abin_range_search_masked(vqhip_abin *x, const float *queries, uint32_t nq, const float *radii, uint64_t max_results,
+                                   const uint32_t *allowed, vqhip_range **out) {
+    VQ_API_BEGIN
+    return range_search(x, queries, true, nq, radii, max_results, out, true, allowed);
+    VQ_API_END
+}
+
+int vqhip_abin_range_search_masked_device(vqhip_abin *x, const void *dev_queries, uint32_t nq, const float *radii,
+                                          uint64_t max_results, const uint32_t *dev_allowed, vqhip_range **out) {
+    VQ_API_BEGIN
+    return range_search(x, dev_queries, false, nq, radii, max_results, out, true, dev_allowed);
+    VQ_API_END
+}
+
+int vqhip_abin_add(vqhip_abin *x, const void *src, int kind, uint64_t n_add) {
+    VQ_API_BEGIN
+    return abin_add(x, src, hipMemcpyHostToDevice, kind, n_add);
+    VQ_API_END
+}
+
+int vqhip_abin_add_device(vqhip_abin *x, const void *dev_src, int kind, uint64_t n_add) {
+    VQ_API_BEGIN
+    return abin_add(x, dev_src, hipMemcpyDeviceToDevice, kind, n_add);
+    VQ_API_END
+}
+
+int vqhip_abin_remove(vqhip_abin *x, const uint32_t *remove_words, uint64_t *removed) {
+    VQ_API_BEGIN
+    return resident_remove(x, remove_words, true, removed);
+    VQ_API_END
+}
+
+int vqhip_abin_remove_device(vqhip_abin *x, const uint32_t *dev_remove_words, uint64_t *removed) {
+    VQ_API_BEGIN
+    return resident_remove(x, dev_remove_words, false, removed);
     VQ_API_END
 }
 

@@ -408,6 +408,22 @@ int launch_sq_rerank(int metric, const uint8_t *C, uint64_t n, uint32_t d, float
                      const float *queries_dev, const float *qnorm_dev, uint32_t nq, const uint32_t *cand_dev, uint32_t c,
                      uint32_t topk, uint32_t *idx_out_dev, float *dist_out_dev, uint32_t *err_dev, hipStream_t stream);
 
+// exact search, range search and rerank of f32 queries over resident packed BQ bits (k_abin.hip): P [n][bin_words(d)]
+// u32 in the binary index's layout, v(bit) = bit ? hi : lo decoded on the fly (lo / hi: the quantizer's low / high as
+// floats), rnorm [n] the decoded rows' norms (cosine only).  Batches and workspaces as launch_knn_search / _range /
+// _rerank; the query norms come from launch_knn_norms.
+int launch_abin_norms(const uint32_t *P, uint64_t n, uint32_t d, float lo, float hi, float *out, hipStream_t stream);
+int launch_abin_search(int metric, const uint32_t *P, uint64_t n, uint32_t d, float lo, float hi, const float *rnorm,
+                       const float *queries_dev, const float *qnorm_dev, uint32_t nq, uint32_t topk, float *dist_ws, void *state_ws,
+                       unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev, const uint32_t *mask_dev,
+                       hipStream_t stream);
+int launch_abin_range(int metric, const uint32_t *P, uint64_t n, uint32_t d, float lo, float hi, const float *rnorm,
+                      const float *queries_dev, const float *qnorm_dev, uint32_t nq, const float *radii_dev, uint64_t max_results,
+                      float *dist_ws, void *state_ws, void *range_ws, RangeOut *out, const uint32_t *mask_dev, hipStream_t stream);
+int launch_abin_rerank(int metric, const uint32_t *P, uint64_t n, uint32_t d, float lo, float hi, const float *rnorm,
+                       const float *queries_dev, const float *qnorm_dev, uint32_t nq, const uint32_t *cand_dev, uint32_t c,
+                       uint32_t topk, uint32_t *idx_out_dev, float *dist_out_dev, uint32_t *err_dev, hipStream_t stream);
+
 // prepared per-node data of the screened squared-L2 / Euclidean descent (k_tsvq_screen.hip)
 struct TsvqScreen {
     const float *w = nullptr;     // [n_int][d]  c_left - c_right of every two-child node; cosine: [n_int][2][d] unit vectors of the children

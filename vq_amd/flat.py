@@ -52,10 +52,10 @@ def adc_then_rerank(adc_search, n: int, dim: int, queries: np.ndarray, topk: int
 
 
 def rerank_candidates(n: int, dim: int, topk: int, rerank, candidates) -> int:
-    """the checks of a short list reranked through `rerank`, a FlatIndex or a ScalarIndex over the same n rows of dim:
-    the list's length (default 4 topk, at most 1024 and n)"""
+    """the checks of a short list reranked through `rerank`, a FlatIndex, a ScalarIndex or an AsymmetricBinaryIndex over the
+    same n rows of dim: the list's length (default 4 topk, at most 1024 and n)"""
     if not isinstance(rerank, ExactResidentIndex):
-        raise InvalidParameter("rerank", f"expected a FlatIndex or a ScalarIndex, got {type(rerank).__name__}")
+        raise InvalidParameter("rerank", f"expected a FlatIndex, a ScalarIndex or an AsymmetricBinaryIndex, got {type(rerank).__name__}")
     if len(rerank) != n:
         raise DimensionMismatch(n, len(rerank))
     if rerank.dim != dim:
