@@ -352,11 +352,8 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32) ? 2 : 1) void k_ass
     float pend_x[ACC ? DPH : 1];
     float4 pend_t[ACC ? DPH / 4 : 1];
     float4 *pend_slot = nullptr;
-#ifndef VQ_ACC_EXP
-#define VQ_ACC_EXP 0
-#endif
     auto acc_issue = [&]() {   // ranks of the pending step's rows; start reading the rows of ranks 0 (and 1)
-        if constexpr (ACC && VQ_ACC_EXP < 1) {
+        if constexpr (ACC) {
             uint32_t rank = (pend_mine && h == 0) ? pend_seq - pend_before : 0xFFFFFFFFu;
             rank = __builtin_amdgcn_permlane32_swap(rank, rank, false, false)[0];  // the row's other half takes the same turn
             pend_rank = rank;
@@ -369,7 +366,7 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32) ? 2 : 1) void k_ass
         }
     };
     auto acc_commit = [&]() {  // add and write back; rows of rank >= R (three of a cluster in one step) take turns after
-        if constexpr (ACC && VQ_ACC_EXP < 1) {
+        if constexpr (ACC) {
             if (pend_rank < R) {
 #pragma unroll
                 for (int q = 0; q < DPH / 4; ++q) {
@@ -725,7 +722,7 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32) ? 2 : 1) void k_ass
             pend_j = j;
 #pragma unroll
             for (int q = 0; q < DPH; ++q) pend_x[q] = xo[q];
-            if (VQ_ACC_EXP < 2 && pend_mine && h == 0) {
+            if (pend_mine && h == 0) {
                 pend_before = cnts[j];              // every lane reads before any lane adds (one wave, in order)
                 pend_seq = atomicAdd(&cnts[j], 1u);  // ds_add_rtn_u32: the rows of one cluster get before, before + 1, ...
             }
@@ -756,12 +753,6 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32) ? 2 : 1) void k_ass
 //   plane t (one dimension of all NT32*32 clusters) = NT32*32 doubles; planes of the upper lane half start 64 bytes
 //   (16 banks) later, so the two halves of an instruction use different banks; counts: u32 [NT32*32] + 64 dummies (the
 //   upper half's lanes add there: one address form, no exec masking)
-#ifndef VQ_ACC_F64
-#define VQ_ACC_F64 1
-#endif
-#ifndef VQ_ACC_RELOAD_PAR
-#define VQ_ACC_RELOAD_PAR 0  // the trip's step that re-reads the pair's rows: 0 = a whole step ahead of the tail that uses them
-#endif
 __host__ __device__ constexpr uint32_t x32p_acc_plane_bytes(int nt32) { return (uint32_t)nt32 * 32u * 8u; }
 __host__ __device__ constexpr uint32_t x32p_acc_bytes_per_wave(int sd, int nt32) {
     return (uint32_t)sd * x32p_acc_plane_bytes(nt32) + 64u + ((uint32_t)nt32 * 32u + 64u) * 4u;
@@ -846,11 +837,7 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
     }
     // fused update (ACC): this wave's sums + counts in LDS, one partial slab per (row chunk, subspace)
     extern __shared__ __attribute__((aligned(16))) float acc_lds[];
-    constexpr uint32_t R = x32_acc_copies(SD, NT32);
-    constexpr uint32_t kCopy = NT32 * 32 * SD;
-    float *sums = nullptr;
     uint32_t *cnts = nullptr;
-#if VQ_ACC_F64
     // (layout: x32p_acc_bytes_per_wave) sums64: plane t at byte t * kPlane (+ 64 for t >= DPH); counts behind them
     constexpr uint32_t kPlane = x32p_acc_plane_bytes(NT32);
     char *acc_wave = nullptr;
@@ -871,33 +858,6 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
             for (uint32_t e = lane; e < k_real; e += 64) pc[e] = cnts[e];
         }
     };
-#else
-    if constexpr (ACC) {
-        constexpr uint32_t kPerWave = NT32 * 32 * (R * SD + 1);
-        sums = acc_lds + (size_t)wave * kPerWave;
-        cnts = reinterpret_cast<uint32_t *>(sums + R * kCopy);
-        for (uint32_t e = lane; e < R * kCopy / 4; e += 64) reinterpret_cast<float4 *>(sums)[e] = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (uint32_t e = lane; e < NT32 * 32; e += 64) cnts[e] = 0u;
-    }
-    auto write_partial = [&]() {
-        if constexpr (ACC) {
-            float4 *ps = reinterpret_cast<float4 *>(acc_sums + ((size_t)chunk * n_sub + vv) * k_real * SD);
-            for (uint32_t e = lane; e < k_real * SD / 4; e += 64) {
-                float4 t = reinterpret_cast<const float4 *>(sums)[e];
-                if constexpr (R == 2) {
-                    const float4 u = reinterpret_cast<const float4 *>(sums + kCopy)[e];
-                    t.x = t.x + u.x;
-                    t.y = t.y + u.y;
-                    t.z = t.z + u.z;
-                    t.w = t.w + u.w;
-                }
-                ps[e] = t;
-            }
-            uint32_t *pc = acc_counts + ((size_t)chunk * n_sub + vv) * k_real;
-            for (uint32_t e = lane; e < k_real; e += 64) pc[e] = cnts[e];
-        }
-    };
-#endif
     if (st0 >= st1) {
         write_partial();  // an empty chunk still owns a (zero) slab
         if (lane == 0) seg_hdr[0] = 0u, seg_hdr[1] = 0u;
@@ -1044,7 +1004,7 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
         if (k == 0) {
 #pragma unroll
             for (int q = 0; q < DPH / 4; ++q) {
-                if constexpr (kTwo && (!ACC || VQ_ACC_F64)) {
+                if constexpr (kTwo) {
                     f32x4 dv = xn_[nb % kDeep][q] - mu4[q];
                     asm volatile("" : "+v"(dv));  // consumed HERE (see reduce_hg), the registers are free for the next load
                     xc[4 * q + 0] = dv[0], xc[4 * q + 1] = dv[1], xc[4 * q + 2] = dv[2], xc[4 * q + 3] = dv[3];
@@ -1239,15 +1199,9 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
     float t_m1 = 0.0f, t_m2 = 0.0f, t_xs = 0.0f;
     uint32_t t_j = 0;
     bool t_proven = false;
-    // Fused update of the rows a tail has just proven, spread over the step the tail runs in: the row's own values are
-    // RE-READ (they were consumed two steps ago; an L2 hit, issued in gap 0), the ticket (count before + returning add
-    // on the cluster's counter) is taken at the end of the tail, the accumulator rows are read in phase 6 and written
-    // back in phase 7 -- each LDS round trip hides behind the gaps in between.
-    bool pend_mine = false;
-    uint32_t pend_j = 0, pend_before = 0, pend_seq = 0, pend_rank = 0xFFFFFFFFu;
+    // Fused update of the rows a tail has just proven, one-step form (the tail behind the loop): the row's own values are
+    // RE-READ (they were consumed two steps ago; an L2 hit) and added at the end of the tail.
     float pend_x[ACC ? DPH : 1];
-    f32x4 pend_t[ACC ? DPH / 4 : 1];
-    float4 *pend_slot = nullptr;
     auto acc_reload = [&](uint32_t tst) {  // the rows of step tst, as loaded (the screen worked on x - mu)
         if constexpr (ACC) {
             uint32_t row = tst * 32 + p;
@@ -1263,9 +1217,8 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
             }
         }
     };
-    auto acc_ticket = [&](bool mine) {
+    auto acc_add_half_row = [&](bool mine) {
         if constexpr (ACC) {
-#if VQ_ACC_F64
             // the whole update: one atomic per dimension of this lane half + the cluster's count (lower half; the upper half
             // adds to a dummy word of its own), all without return -- nothing to wait for, nothing left for later gaps
             if (mine) {
@@ -1279,74 +1232,18 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
                 }
                 asm volatile("ds_add_u32 %0, %1" ::"v"(ac), "v"(one) : "memory");
             }
-            (void)pend_mine, (void)pend_j, (void)pend_before, (void)pend_seq;
-#else
-            pend_mine = mine;  // both lane halves of the row agree
-            pend_j = t_j;
-            if (pend_mine && h == 0) {
-                pend_before = cnts[pend_j];              // every lane reads before any lane adds (one wave, in order)
-                pend_seq = atomicAdd(&cnts[pend_j], 1u);  // ds_add_rtn_u32: the rows of one cluster get before, before + 1, ...
-            }
-#endif
         }
     };
-    auto acc_issue = [&]() {
-        if constexpr (ACC && !VQ_ACC_F64) {
-            uint32_t rank = (pend_mine && h == 0) ? pend_seq - pend_before : 0xFFFFFFFFu;
-            rank = __builtin_amdgcn_permlane32_swap(rank, rank, false, false)[0];  // the row's other half takes the same turn
-            pend_rank = rank;
-            const uint32_t copy = (R == 2 && rank == 1u) ? kCopy : 0u;
-            pend_slot = reinterpret_cast<float4 *>(__builtin_assume_aligned(sums + copy + (size_t)(pend_mine ? pend_j : 0u) * SD + DPH * h, 16));
-            // read by every lane (a lane without a turn reads a valid record and drops it), as ext_vector loads: the
-            // float4 STRUCT loads came out of the compiler as ds_read_b96 + ds_read2_b32 + ds_read_b32 pieces (twice the LDS
-            // instructions, 2.5x the bank-conflict cycles)
-#pragma unroll
-            for (int q = 0; q < DPH / 4; ++q) pend_t[q] = reinterpret_cast<const f32x4 *>(pend_slot)[q];
-        }
-    };
-    auto acc_commit = [&]() {
-        if constexpr (ACC && !VQ_ACC_F64) {
-            if (pend_rank < R) {
-#pragma unroll
-                for (int q = 0; q < DPH / 4; ++q) {
-                    f32x4 t = pend_t[q];
-                    t[0] = t[0] + pend_x[4 * q + 0];
-                    t[1] = t[1] + pend_x[4 * q + 1];
-                    t[2] = t[2] + pend_x[4 * q + 2];
-                    t[3] = t[3] + pend_x[4 * q + 3];
-                    reinterpret_cast<f32x4 *>(pend_slot)[q] = t;
-                }
-            }
-            for (uint32_t r = R;; ++r) {  // three or more rows of one cluster in a step take turns
-                if (!__any(pend_rank != 0xFFFFFFFFu && pend_rank >= r)) break;
-                if (pend_rank == r) {
-#pragma unroll
-                    for (int q = 0; q < DPH / 4; ++q) {
-                        float4 t = pend_slot[q];
-                        t.x = t.x + pend_x[4 * q + 0];
-                        t.y = t.y + pend_x[4 * q + 1];
-                        t.z = t.z + pend_x[4 * q + 2];
-                        t.w = t.w + pend_x[4 * q + 3];
-                        pend_slot[q] = t;
-                    }
-                }
-                __builtin_amdgcn_wave_barrier();
-            }
-            pend_mine = false;
-            pend_rank = 0xFFFFFFFFu;
-        }
-    };
-    // ACC, f64 form, in the loop: the update rides on the PAIRED tail (one tail for two steps, as in the encode form) -- there a
+    // ACC in the loop: the update rides on the PAIRED tail (one tail for two steps, as in the encode form) -- there a
     // lane owns a whole ROW's verdict (lanes 0..31 row p of step S - 1, lanes 32..63 row p of step S), so it re-reads the
     // row's SD values (gap 0 of the trip's second step; an L2 hit) and adds all of them: SD atomics + the count per lane and
     // two steps, the same number per step as the half-row form, and no second tail.  (The tail behind the loop is the one-step
     // form above.)
-    constexpr bool kAccPair = ACC && VQ_ACC_F64;
-    float pend_xr[kAccPair ? SD : 1];
+    float pend_xr[ACC ? SD : 1];
     // The upper lane half walks the dimensions rotated by DPH (its registers hold x[DPH..SD), x[0..DPH)): in every atomic
     // instruction the two halves then address different planes, 16 banks apart -- 32 rows per 16 bank pairs instead of 64.
     auto acc_reload_pair = [&](uint32_t S) {  // rows of steps S - 1 (lower lanes) and S (upper lanes), as loaded
-        if constexpr (kAccPair) {
+        if constexpr (ACC) {
             uint32_t row = (S - 1 + h) * 32 + p;
             row = row < n32 ? row : n32 - 1;
             const float *ptr = reinterpret_cast<const float *>(reinterpret_cast<const char *>(X + (size_t)s * SD) + (uint64_t)row * x_pitch);
@@ -1367,14 +1264,10 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
     bool upd_mine = false;
     uint32_t upd_j = 0;
     auto acc_update_begin = [&](bool mine) {
-        if constexpr (kAccPair) upd_mine = mine, upd_j = t_j;
+        if constexpr (ACC) upd_mine = mine, upd_j = t_j;
     };
     auto acc_update_piece = [&](int k) {
-#if VQ_ACC_F64
-        if constexpr (kAccPair) {
-#ifdef VQ_ACC_ABL
-            if (VQ_ACC_ABL == 1) return;  // (ablation builds only: timing without the atomics)
-#endif
+        if constexpr (ACC) {
             if (upd_mine) {
                 const uint32_t base = (uint32_t)(uintptr_t)(acc_wave) + upd_j * 8u;
                 if (k < kAccPieces) {
@@ -1391,10 +1284,9 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
                 }
             }
         }
-#endif
     };
     // tail of a finished step in 4 pieces (the X32 kernel's tail, same order of operations)
-    auto tail_piece = [&](int k, int tp, uint32_t tst, bool in_loop, bool no_step = false) {
+    auto tail_piece = [&](int k, int tp, uint32_t tst) {
         if (k == 0 && NC > 0) {
             t_m1 = p_m1, t_m2 = p_m2, t_j = p_j;  // merged inside the step itself (fold_step)
         } else if (k == 0) {
@@ -1434,14 +1326,13 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
             if (cosine) proven = proven && (t_m1 < -T) && (xnorm > 4e-10f);
             t_proven = proven;
         } else {
-            // In the loop the only tail without a step behind it is the first one (no_step: tst = st0 - 1, chains still +inf): it is
-            // aimed at the rows of step st0, which the real tail of st0 overwrites a step later; rows past n repeat row
-            // n - 1 (they were loaded from it) and both lane halves hold the same verdict -- so the code is stored
-            // by every lane, without a branch.  The tail after the loop may belong to a dummy step: it asks.
-            const bool valid = in_loop ? !no_step : (tst < st1);
-            const uint32_t row = (in_loop && !valid ? st0 : tst) * 32 + p;
+            // Only the tail behind the loop gets here (in the loop pieces 1 and 3 are tail_pair_piece's); it may belong to a
+            // dummy step, which writes nothing.  Rows past n repeat row n - 1 (they were loaded from it) and both lane
+            // halves hold the same verdict, so every lane stores the code.
+            const bool valid = tst < st1;
+            const uint32_t row = tst * 32 + p;
             const uint32_t rowc = row < n32 ? row : n32 - 1;
-            if (in_loop || valid) code_base[(uint64_t)rowc * code_stride] = (uint8_t)t_j;
+            if (valid) code_base[(uint64_t)rowc * code_stride] = (uint8_t)t_j;
             const bool writer = (h == 0) && (row < n32) && valid;
             const bool recheck = writer && !t_proven;
             const unsigned long long mask = __ballot(recheck);
@@ -1452,7 +1343,7 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
                 }
                 seg_count += (uint32_t)__popcll(mask);
             }
-            acc_ticket(t_proven && valid && (row < n32));
+            acc_add_half_row(t_proven && valid && (row < n32));
         }
     };
 
@@ -1560,25 +1451,20 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
                         if (f == 2 || f == 5) {
                             const int slot = 2 * i + (f == 5);  // 0..15
                             if (slot == 0) {
-                                if constexpr (kAccPair) { if (par == VQ_ACC_RELOAD_PAR) acc_reload_pair(st - VQ_ACC_RELOAD_PAR); }
-                                else acc_reload(st - 1);
+                                if (par == 0) acc_reload_pair(st);  // a whole step ahead of the tail that uses the rows
                                 split_piece(0, par ^ 1, st + 1 + kDeep, first);
                             } else if (slot <= 4) {
-                                if constexpr (ACC && !kAccPair) {
-                                    tail_piece(slot - 1, par ^ 1, st - 1, true, first && par == 0);
-                                } else if (par == 0) {  // step st - 1: the lane's own merge, parked for the partner step
-                                    if (slot == 1) tail_piece(0, 1, st - 1, true), tail_hold();
+                                if (par == 0) {  // step st - 1: the lane's own merge, parked for the partner step
+                                    if (slot == 1) tail_piece(0, 1, st - 1), tail_hold();
                                 } else {                // steps st - 2 and st - 1 together
-                                    if (slot == 1) tail_piece(0, 0, st - 1, true);
-                                    else if (slot == 3) tail_piece(2, 0, st - 1, true);
+                                    if (slot == 1) tail_piece(0, 0, st - 1);
+                                    else if (slot == 3) tail_piece(2, 0, st - 1);
                                     else tail_pair_piece(slot - 1, st - 1, first);
                                 }
                             }
                             else if (slot <= 10) split_piece(slot - 4, par ^ 1, st + 1 + kDeep);      // 2 splits, packs 0..3
                             else if (slot == 11) split_piece(7, par ^ 1, st + 1 + kDeep), split_piece(8, par ^ 1, st + 1 + kDeep);
-                            else if (slot == 12) { if constexpr (!kAccPair) acc_issue(); }
-                            else if (slot == 14) { if constexpr (!kAccPair) acc_commit(); }
-                            if constexpr (kAccPair) {  // the pair's update: four dimensions per gap behind the tail, the count last
+                            if constexpr (ACC) {  // the pair's update: four dimensions per gap behind the tail, the count last
                                 if (par == 1 && slot >= 5 && slot < 5 + kAccPieces) acc_update_piece(slot - 5);
                                 if (par == 1 && slot == 5 + kAccPieces) acc_update_piece(kAccPieces);
                             }
@@ -1593,25 +1479,18 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
                         if (f == 2) {
                             if (i == NT32 - 1) fold_step();  // before tile 0 of the next step starts cm and the row chain again
                             if (i == 0) {
-                                if constexpr (kAccPair) { if (par == VQ_ACC_RELOAD_PAR) acc_reload_pair(st - VQ_ACC_RELOAD_PAR); }
-                                else acc_reload(st - 1);
+                                if (par == 0) acc_reload_pair(st);  // a whole step ahead of the tail that uses the rows
                                 split_piece(0, par ^ 1, st + 1 + kDeep, first);
-                                tail_piece(0, par ^ 1, st - 1, true);
-                                if constexpr (ACC && !kAccPair) tail_piece(1, par ^ 1, st - 1, true, first && par == 0);
-                                else if (par == 0) tail_hold();
+                                tail_piece(0, par ^ 1, st - 1);
+                                if (par == 0) tail_hold();
                                 else tail_pair_piece(1, st - 1, first);
                             } else if (i == 1) {
-                                if constexpr (ACC && !kAccPair) tail_piece(2, par ^ 1, st - 1, true), tail_piece(3, par ^ 1, st - 1, true, first && par == 0);
-                                else if (par == 1) tail_piece(2, 0, st - 1, true), tail_pair_piece(3, st - 1, first);
+                                if (par == 1) tail_piece(2, 0, st - 1), tail_pair_piece(3, st - 1, first);
                                 split_piece(1, par ^ 1, st + 1 + kDeep);
                             } else if (i < kSplitPieces) {
                                 split_piece(i, par ^ 1, st + 1 + kDeep);
-                            } else if (i == 6) {
-                                if constexpr (!kAccPair) acc_issue();
-                            } else if (i == 7) {
-                                if constexpr (!kAccPair) acc_commit();
                             }
-                            if constexpr (kAccPair) {  // the pair's update: four dimensions per gap behind the tail, the count last
+                            if constexpr (ACC) {  // the pair's update: four dimensions per gap behind the tail, the count last
                                 if (par == 1 && i >= 5 && i < 5 + kAccPieces) acc_update_piece(i - 5);
                                 if (par == 1 && i == 5 + kAccPieces) acc_update_piece(kAccPieces);
                             }
@@ -1629,9 +1508,7 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
         const uint32_t last = st0 + ((nst + 1) & ~1u) - 1;  // parity 1
         acc_reload(last);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) tail_piece(k, 1, last, false);
-        acc_issue();
-        acc_commit();
+        for (int k = 0; k < 4; ++k) tail_piece(k, 1, last);
         write_partial();
     }
     if (lane == 0) seg_hdr[0] = seg_first, seg_hdr[1] = seg_count;
@@ -1980,7 +1857,7 @@ int launch_one_x32(const CodebookView &cb, const AssignArgs &a, hipStream_t stre
                     attr_set_p.done();
                 }
             }
-            const size_t dyn_lds_p = (ACC && VQ_ACC_F64) ? (size_t)kWavesPerBlock * x32p_acc_bytes_per_wave(SD, NT32) : dyn_lds;
+            const size_t dyn_lds_p = ACC ? (size_t)kWavesPerBlock * x32p_acc_bytes_per_wave(SD, NT32) : 0;
             hipLaunchKernelGGL((k_assign_screen_bf16_x32p<SD, NT32, ACC>), dim3(blocks), dim3(kBlock), dyn_lds_p, stream, a.X, a.n, a.d,
                                cb.m, cb.prepA32, cb.cn32, NT32 * 32, cb.meta, a.sub_list, a.n_sub, a.codes, a.wl_rows, a.wl_seg,
                                n_chunks, a.wl_stride, a.metric == VQHIP_COSINE ? 1 : 0, cb.k, cb.cen, a.gate_active,
