@@ -1189,6 +1189,92 @@ class AsymmetricBinaryIndex
     BinaryQuantizer quantizer_;
 };
 
+// Exact index of f32 queries (never quantized) over SQ codes of at most 16 levels kept on the device at four bits a
+// dimension (include/vqhip.h, vqhip_sq4index_*): dimension t of a row in bits 4 (t % 8) .. + 3 of its word t / 8, pad
+// nibbles zero.  Distance::compute(q, v(codes)) with v(c) = min + (float)c * step for every nibble value, under any metric,
+// cosine included.  Every result equals ScalarIndex over the same codes as bytes and FlatIndex over the dequantized rows:
+// (row index, distance) pairs [nq][topk], nearest first, NaN last, ties to the lower row.  Built from f32 rows (encoded and
+// packed on the device), u8 codes (each <= 15) or packed words [n][ceil(dim / 8)].  The arguments are checked before the
+// device is touched.
+class Scalar4Index
+    : public detail::ExactResidentIndex<vqhip_sq4index, vqhip_sq4index_destroy, vqhip_sq4index_search, vqhip_sq4index_range_search,
+                                        vqhip_sq4index_rerank, vqhip_sq4index_search_masked, vqhip_sq4index_range_search_masked,
+                                        vqhip_sq4index_remove, vqhip_sq4index_remove_device> {
+   public:
+    enum class Source { Rows = VQHIP_SQ4_F32, Codes = VQHIP_SQ4_U8, Packed = VQHIP_SQ4_PACKED };
+    Scalar4Index(const float *rows, std::size_t n, std::size_t dim, ScalarQuantizer quantizer, Distance distance = Distance())
+        : quantizer_(quantizer) {
+        init(rows, Source::Rows, n, dim, distance);
+    }
+    Scalar4Index(const std::uint8_t *codes, std::size_t n, std::size_t dim, ScalarQuantizer quantizer, Distance distance = Distance())
+        : quantizer_(quantizer) {
+        init(codes, Source::Codes, n, dim, distance);
+    }
+    Scalar4Index(const std::uint32_t *words, std::size_t n, std::size_t dim, ScalarQuantizer quantizer, Distance distance = Distance())
+        : quantizer_(quantizer) {
+        init(words, Source::Packed, n, dim, distance);
+    }
+    std::size_t words_per_row() const { return (dim_ + 7) / 8; }
+    const ScalarQuantizer &quantizer() const { return quantizer_; }
+    // the packed rows [n][words_per_row()]
+    std::vector<std::uint32_t> packed() const {
+        std::vector<std::uint32_t> out(n_ * words_per_row());
+        detail::check(vqhip_sq4index_packed(ix_.get(), out.data()));
+        return out;
+    }
+    // the codes unpacked [n][dim]
+    std::vector<std::uint8_t> codes() const {
+        const std::vector<std::uint32_t> words = packed();
+        const std::size_t W = words_per_row();
+        std::vector<std::uint8_t> out(n_ * dim_);
+        for (std::size_t i = 0; i < n_; ++i)
+            for (std::size_t t = 0; t < dim_; ++t) out[i * dim_ + t] = (std::uint8_t)((words[i * W + t / 8] >> (4 * (t % 8))) & 15u);
+        return out;
+    }
+    // append b rows in one of the constructors' three forms, from host memory or from a device pointer (f32 rows and words
+    // 4-byte aligned; a code above 15 or a pad nibble set there is an FfiError that leaves the index as it was); returns
+    // their ids n .. n + b - 1
+    std::vector<std::uint32_t> add(const float *rows, std::size_t b) { return add_from(rows, Source::Rows, b, false); }
+    std::vector<std::uint32_t> add_codes(const std::uint8_t *codes, std::size_t b) {
+        if (codes) check_codes(codes, b, dim_);
+        return add_from(codes, Source::Codes, b, false);
+    }
+    std::vector<std::uint32_t> add_packed(const std::uint32_t *words, std::size_t b) {
+        if (words) check_pad_nibbles(words, b, dim_);
+        return add_from(words, Source::Packed, b, false);
+    }
+    std::vector<std::uint32_t> add_device(const void *dev_src, Source kind, std::size_t b) { return add_from(dev_src, kind, b, true); }
+
+   private:
+    static void check_codes(const std::uint8_t *codes, std::size_t n, std::size_t dim) {
+        for (std::size_t i = 0; i < n * dim; ++i)
+            if (codes[i] > 15) throw VqError::InvalidParameter("codes", "a 4-bit code is at most 15");
+    }
+    static void check_pad_nibbles(const std::uint32_t *words, std::size_t n, std::size_t dim) {
+        if (dim % 8 == 0) return;
+        const std::size_t W = (dim + 7) / 8;
+        const std::uint32_t keep = (1u << (4 * (dim % 8))) - 1u;
+        for (std::size_t i = 0; i < n; ++i)
+            if (words[i * W + W - 1] & ~keep) throw VqError::InvalidParameter("words", "a row has a pad nibble set");
+    }
+    std::vector<std::uint32_t> add_from(const void *src, Source kind, std::size_t b, bool device) {
+        return append(src, b, [&](vqhip_sq4index *h) {
+            return device ? vqhip_sq4index_add_device(h, src, (int)kind, b) : vqhip_sq4index_add(h, src, (int)kind, b);
+        });
+    }
+    void init(const void *src, Source kind, std::size_t n, std::size_t dim, Distance distance) {
+        check_shape(n, dim);
+        if (quantizer_.levels() > 16) throw VqError::InvalidParameter("quantizer", "a 4-bit index holds at most 16 levels");
+        if (kind == Source::Codes && src) check_codes(static_cast<const std::uint8_t *>(src), n, dim);
+        if (kind == Source::Packed && src) check_pad_nibbles(static_cast<const std::uint32_t *>(src), n, dim);
+        vqhip_sq4index *x = nullptr;
+        detail::check(vqhip_sq4index_create(quantizer_.min(), quantizer_.max(), (std::uint32_t)quantizer_.levels(), src, (int)kind, n,
+                                            (std::uint32_t)dim, (int)distance.kind(), &x));
+        adopt(x, n, dim, distance);
+    }
+    ScalarQuantizer quantizer_;
+};
+
 namespace detail {
 // What the inverted-file indexes share over their C handles (H and its destroy / list_sizes / probe / search):
 // the shape, the add-side and probe-side checks, and the calls whose arguments are the same for every payload.

@@ -815,6 +815,75 @@ int vqhip_abin_add_device(vqhip_abin *x, const void *dev_src, int kind, uint64_t
 int vqhip_abin_remove(vqhip_abin *x, const uint32_t *remove_words, uint64_t *removed);
 int vqhip_abin_remove_device(vqhip_abin *x, const uint32_t *dev_remove_words, uint64_t *removed);
 
+/* ---- 4-bit scalar index: f32 queries over SQ codes packed eight to a word, exact (k_sq4index.hip, nibble_decode.hpp;
+ * DESIGN.md 29) -------
+ * No reference counterpart.  The scalar index above keeps one byte per dimension.  This index keeps the codes of a
+ * ScalarQuantizer of at most 16 levels at four bits a dimension and nothing else, leaves the query in f32 and computes
+ * its exact distance to the DEQUANTIZED row: the fourth index of exact distances beside vqhip_flat, vqhip_sqindex and
+ * vqhip_abin, at d / 2 bytes a row (W words, plus 4 bytes for the row norm under the cosines).
+ *   codes   a ScalarQuantizer(min, max, levels) with 2 <= levels <= 16 fixes them on the way in.  f32 rows go through
+ *           the SQ encode (vqhip_sq_quantize's code of every value, bit for bit, < levels); u8 codes are taken as they
+ *           are and must be <= 15.  Every nibble value 0..15 is legal, codes >= levels included, as every byte value is
+ *           in vqhip_sqindex.
+ *   layout  row i, dimension t in bits 4 (t % 8) .. 4 (t % 8) + 3 of u32 word i * W + t / 8 (dimension 8 j in the low
+ *           nibble), W = ceil(d / 8), pad nibbles zero.  Rows are word-aligned.
+ *   v(c)    = min + (float)c * step, step = (max - min) / (levels - 1): two roundings, never fused -- the decode of
+ *           vqhip_sqindex, on the way out.
+ *   D(q, i) = Distance::compute(q, v(codes[i])) bit for bit, for all five metrics: the pair summed sequentially over
+ *           t = 0..d-1 from -0.0f, one rounding per operation, no fused multiply-add; Euclidean = sqrtf of the sum; cosine
+ *           through vq_cosine_finish, the row norm sqrtf of the sequential sum of v^2 from -0.0f computed once at create
+ *           (and for the rows of an add) and the query norm once per call.  Queries are f32 and never quantized.
+ *   search / rerank / range_search and their masked forms = vqhip_sqindex_* over the same codes as bytes under the same
+ *           quantizer, and = vqhip_flat_* over the rows v(codes): equal indices, distances equal as uint32 bits.  That is
+ *           the order (key(D), row), NaN last and reported as 0x7FC00000, ties to the lower row; a masked query with
+ *           fewer than topk allowed rows is padded with idx 0xFFFFFFFF and dist +inf; a rerank id >= n is flagged on the
+ *           device, never read, and gives VQHIP_ERR_INVALID_INPUT.
+ *   add / remove = the rules of "adding and removing rows" above: add takes create's three source kinds with create's
+ *           checks, and a refused add leaves the index as it was; a removal moves the row norms with the rows.
+ * Limits: vqhip_sqindex's -- d >= 1, 1 <= n < 2^32, 1 <= topk <= min(n, 1024), nq < 2^32 (served in batches), rerank
+ * lists of 1..4096 distinct ids.  The source of create and add is f32 rows [n][d] (kind VQHIP_SQ4_F32), u8 codes [n][d]
+ * (VQHIP_SQ4_U8) or packed words [n][W] (VQHIP_SQ4_PACKED).  VQHIP_ERR_INVALID_INPUT: levels > 16; a u8 code above 15; a
+ * set pad nibble in packed words (both in the host and the device form: a host source is read before any device work, a
+ * device source is checked behind the pack / the copy with a flag word read back); device f32 rows or words that are not
+ * 4-byte aligned.  Every metric of the flat index is accepted.  Every parameter is checked before any device work, in the
+ * order of vqhip_sqindex_create: out, the quantizer, levels <= 16, the source pointer, d, n, the metric, the kind, the
+ * source.  Host forms return when the results are there; search_device is asynchronous on the current stream.  One lock
+ * per handle, as vqhip_flat's.  packed: words [n][W].  info: any output pointer may be NULL. */
+#define VQHIP_SQ4_F32 0
+#define VQHIP_SQ4_U8 1
+#define VQHIP_SQ4_PACKED 2
+typedef struct vqhip_sq4index vqhip_sq4index;
+int vqhip_sq4index_create(float min, float max, uint32_t levels, const void *src, int kind, uint64_t n, uint32_t d,
+                          int metric, vqhip_sq4index **out);
+int vqhip_sq4index_create_device(float min, float max, uint32_t levels, const void *dev_src, int kind, uint64_t n,
+                                 uint32_t d, int metric, vqhip_sq4index **out);
+int vqhip_sq4index_destroy(vqhip_sq4index *x);
+int vqhip_sq4index_info(const vqhip_sq4index *x, uint64_t *n, uint32_t *d, int *metric, float *min, float *max,
+                        uint32_t *levels);
+int vqhip_sq4index_packed(vqhip_sq4index *x, uint32_t *words);
+int vqhip_sq4index_search(vqhip_sq4index *x, const float *queries, uint32_t nq, uint32_t topk, uint32_t *idx_out,
+                          float *dist_out);
+int vqhip_sq4index_search_device(vqhip_sq4index *x, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx,
+                                 void *dev_dist);
+int vqhip_sq4index_search_masked(vqhip_sq4index *x, const float *queries, uint32_t nq, uint32_t topk,
+                                 const uint32_t *allowed, uint32_t *idx_out, float *dist_out);
+int vqhip_sq4index_search_masked_device(vqhip_sq4index *x, const void *dev_queries, uint32_t nq, uint32_t topk,
+                                        const uint32_t *dev_allowed, void *dev_idx, void *dev_dist);
+int vqhip_sq4index_rerank(vqhip_sq4index *x, const float *queries, uint32_t nq, const uint32_t *cand, uint32_t c,
+                          uint32_t topk, uint32_t *idx_out, float *dist_out);
+int vqhip_sq4index_range_search(vqhip_sq4index *x, const float *queries, uint32_t nq, const float *radii,
+                                uint64_t max_results, vqhip_range **out);
+int vqhip_sq4index_range_search_device(vqhip_sq4index *x, const void *dev_queries, uint32_t nq, const float *radii,
+                                       uint64_t max_results, vqhip_range **out);
+int vqhip_sq4index_range_search_masked(vqhip_sq4index *x, const float *queries, uint32_t nq, const float *radii,
+                                       uint64_t max_results, const uint32_t *allowed, vqhip_range **out);
+int vqhip_sq4index_range_search_masked_device(vqhip_sq4index *x, const void *dev_queries, uint32_t nq, const float *radii,
+                                              uint64_t max_results, const uint32_t *dev_allowed, vqhip_range **out);
+int vqhip_sq4index_add(vqhip_sq4index *x, const void *src, int kind, uint64_t n_add);
+int vqhip_sq4index_add_device(vqhip_sq4index *x, const void *dev_src, int kind, uint64_t n_add);
+int vqhip_sq4index_remove(vqhip_sq4index *x, const uint32_t *remove_words, uint64_t *removed);
+int vqhip_sq4index_remove_device(vqhip_sq4index *x, const uint32_t *dev_remove_words, uint64_t *removed);
+
 /* ---- inverted-file PQ index: search only the probed lists (k_ivf.hip) -----------------------
  * No reference counterpart.  An index holds coarse centroids C [nlist][dim] f32 (1 <= nlist <= 65536), PQ codebooks
  * cb [m][k][sub_dim] (dim = m * sub_dim) and a metric: squared Euclidean, Euclidean or Manhattan (cosine is refused with

@@ -229,6 +229,24 @@ SIGNATURES = {
     "vqhip_abin_add_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64]),
     "vqhip_abin_remove": (C.c_int, [_vp, _u32p, _u64p]),
     "vqhip_abin_remove_device": (C.c_int, [_vp, _vp, _u64p]),
+    "vqhip_sq4index_create": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _vp, C.c_int, C.c_uint64, C.c_uint32, C.c_int, _vpp]),
+    "vqhip_sq4index_create_device": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _vp, C.c_int, C.c_uint64, C.c_uint32, C.c_int, _vpp]),
+    "vqhip_sq4index_destroy": (C.c_int, [_vp]),
+    "vqhip_sq4index_info": (C.c_int, [_vp, _u64p, _u32p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), _u32p]),
+    "vqhip_sq4index_packed": (C.c_int, [_vp, _u32p]),
+    "vqhip_sq4index_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "vqhip_sq4index_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "vqhip_sq4index_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p]),
+    "vqhip_sq4index_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "vqhip_sq4index_rerank": (C.c_int, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "vqhip_sq4index_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, _f32p, C.c_uint64, _vpp]),
+    "vqhip_sq4index_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, _f32p, C.c_uint64, _vpp]),
+    "vqhip_sq4index_range_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, _f32p, C.c_uint64, _u32p, _vpp]),
+    "vqhip_sq4index_range_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, _f32p, C.c_uint64, _vp, _vpp]),
+    "vqhip_sq4index_add": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64]),
+    "vqhip_sq4index_add_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64]),
+    "vqhip_sq4index_remove": (C.c_int, [_vp, _u32p, _u64p]),
+    "vqhip_sq4index_remove_device": (C.c_int, [_vp, _vp, _u64p]),
     "vqhip_ivfbin_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p]),
     "vqhip_ivfbin_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "vqhip_ivfbin_range_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint64, _u32p, _vpp]),
@@ -1124,6 +1142,33 @@ class ABin(_ResidentExactHandle):
     def packed(self) -> np.ndarray:
         out = np.empty((self.n, self.words), np.uint32)
         check(load().vqhip_abin_packed(self.raw, ptr(out, _u32p)))
+        return out
+
+
+SQ4_F32, SQ4_U8, SQ4_PACKED = 0, 1, 2
+
+
+class SQ4Index(_ResidentExactHandle):
+    """vqhip_sq4index: SQ codes of at most 16 levels packed eight to a word on the device, exact search, range search and
+    rerank of f32 queries against the dequantized rows (k_sq4index.hip)"""
+
+    _prefix = "vqhip_sq4index"
+    _destroy = "vqhip_sq4index_destroy"
+
+    def __init__(self, src, kind: int, n: int, d: int, mn: float, mx: float, levels: int, metric: int,
+                 dev_src: int | None = None):
+        """src: a C-contiguous host array of the kind (f32 [n][d], u8 [n][d], u32 [n][W]), or dev_src a device pointer"""
+        h = C.c_void_p()
+        name = "vqhip_sq4index_create" + ("_device" if dev_src is not None else "")
+        p = C.c_void_p(dev_src) if dev_src is not None else src.ctypes.data_as(_vp)
+        check(getattr(load(), name)(mn, mx, int(levels), p, int(kind), int(n), int(d), int(metric), C.byref(h)))
+        super().__init__(h)
+        self.n, self.d, self.metric = int(n), int(d), int(metric)
+        self.words = (self.d + 7) // 8
+
+    def packed(self) -> np.ndarray:
+        out = np.empty((self.n, self.words), np.uint32)
+        check(load().vqhip_sq4index_packed(self.raw, ptr(out, _u32p)))
         return out
 
 

@@ -308,7 +308,7 @@ class ResidentIndex:
 
 
 class ExactResidentIndex(ResidentIndex):
-    """a ResidentIndex whose distances are exact (FlatIndex, ScalarIndex, AsymmetricBinaryIndex): range search, the rerank of candidates, and
+    """a ResidentIndex whose distances are exact (FlatIndex, ScalarIndex, Scalar4Index, AsymmetricBinaryIndex): range search, the rerank of candidates, and
     the filtered forms of search and range search.  A filter is one row mask per call, `allowed`: a bool array (n,)
     (True: the row may be returned) or its uint32 words (``pack_row_mask``); None: every row, the unfiltered call."""
 

@@ -23,7 +23,7 @@ struct Resident {
     int on_device() { return VQHIP_OK; }     // (the rows stay where create put them: no device of its own to check)
 };
 
-// The indexes of exact distances.  T (vqhip_flat, vqhip_sqindex, vqhip_abin) keeps its rows and the three launcher calls that
+// The indexes of exact distances.  T (vqhip_flat, vqhip_sqindex, vqhip_abin, vqhip_sq4index) keeps its rows and the three launcher calls that
 // read them: launch_search, launch_rerank and launch_range.
 template <class T>
 struct ExactResident : Resident {

@@ -1,4 +1,4 @@
-// api_resident.hip -- extern "C" entry points of the resident indexes (vqhip_flat, vqhip_sqindex, vqhip_binary, vqhip_abin) and
+// api_resident.hip -- extern "C" entry points of the resident indexes (vqhip_flat, vqhip_sqindex, vqhip_binary, vqhip_abin, vqhip_sq4index) and
 // their host layer: searches, reranks, range searches, adding and removing rows.  Host-side orchestration only.
 #include <algorithm>
 #include <memory>
@@ -1200,6 +1200,291 @@ int vqhip_abin_remove(vqhip_abin *x, const uint32_t *remove_words, uint64_t *rem
 }
 
 int vqhip_abin_remove_device(vqhip_abin *x, const uint32_t *dev_remove_words, uint64_t *removed) {
+    VQ_API_BEGIN
+    return resident_remove(x, dev_remove_words, false, removed);
+    VQ_API_END
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ 4-bit scalar index (k_sq4index.hip) ----
+// The scalar index's codes at four bits a dimension, eight to a word, under the same exact distances: f32 queries against
+// v(c) = min + (float)c * step.  The fourth member of ExactResident.
+struct vqhip_sq4index : ExactResident<vqhip_sq4index> {
+    uint32_t W = 0, levels = 0;
+    float mn = 0, mx = 0, step = 0;
+    DevBuf words;  // [n][W] packed rows; `bytes` is the capacity (an add grows it)
+
+    DevBuf &payload() { return words; }
+    size_t row_bytes() const { return (size_t)W * 4; }
+    int norms_enqueue(const void *P, uint64_t count, float *out, hipStream_t s) {
+        return launch_sq4_norms(static_cast<const uint32_t *>(P), count, d, mn, step, out, s);
+    }
+    int launch_search(const float *queries_dev, const float *qn, uint32_t nq, uint32_t topk, uint32_t *idx_dev, float *dist_dev,
+                      hipStream_t s) {
+        return launch_sq4_search(metric, words.as<uint32_t>(), n, d, mn, step, rnorm.as<float>(), queries_dev, qn, nq, topk,
+                                 dist.as<float>(), state.p, cand.as<unsigned long long>(), idx_dev, dist_dev, mask, s);
+    }
+    int launch_rerank(const float *qn, uint32_t nq, uint32_t c, uint32_t topk, hipStream_t s) {
+        return launch_sq4_rerank(metric, words.as<uint32_t>(), n, d, mn, step, rnorm.as<float>(), q.as<float>(), qn, nq,
+                                 rr_cand.as<uint32_t>(), c, topk, idx.as<uint32_t>(), out.as<float>(), rr_err.as<uint32_t>(), s);
+    }
+    int launch_range(const float *queries_dev, const float *qn, uint32_t nq, uint64_t max_results, RangeOut *r, hipStream_t s) {
+        return launch_sq4_range(metric, words.as<uint32_t>(), n, d, mn, step, rnorm.as<float>(), queries_dev, qn, nq, radii.as<float>(),
+                                max_results, dist.as<float>(), state.p, range_ws.p, r, mask, s);
+    }
+};
+
+static int sq4_check_levels(uint32_t levels) {
+    if (levels > 16) return fail(VQHIP_ERR_INVALID_INPUT, "levels %u: a 4-bit index holds at most 16", levels);
+    return VQHIP_OK;
+}
+
+// What create and add check of their source without a device: the pointer, the kind, a device source's alignment (f32
+// rows and words are read as dwords), a host source's codes (at most 15) and pad nibbles (zero).
+static int sq4_check_source(const void *src, hipMemcpyKind kind_copy, int kind, uint64_t n, uint32_t d, bool added) {
+    if (kind != VQHIP_SQ4_F32 && kind != VQHIP_SQ4_U8 && kind != VQHIP_SQ4_PACKED)
+        return fail(VQHIP_ERR_INVALID_INPUT, "source kind must be 0 (f32), 1 (u8 codes) or 2 (packed words), not %d", kind);
+    if (kind_copy == hipMemcpyDeviceToDevice) {
+        if (kind == VQHIP_SQ4_F32 && (reinterpret_cast<uintptr_t>(src) & 3)) return fail(VQHIP_ERR_INVALID_INPUT, "rows are not 4-byte aligned");
+        if (kind == VQHIP_SQ4_PACKED && (reinterpret_cast<uintptr_t>(src) & 3))
+            return fail(VQHIP_ERR_INVALID_INPUT, "words are not 4-byte aligned");
+        return VQHIP_OK;
+    }
+    if (kind == VQHIP_SQ4_U8) {
+        const uint8_t *c = static_cast<const uint8_t *>(src);
+        for (uint64_t i = 0; i < n; ++i)
+            for (uint32_t t = 0; t < d; ++t)
+                if (c[i * d + t] > 15)
+                    return fail(VQHIP_ERR_INVALID_INPUT, added ? "added row %llu holds code %u: a 4-bit code is at most 15" : "row %llu holds code %u: a 4-bit code is at most 15",
+                                (unsigned long long)i, (unsigned)c[i * d + t]);
+    } else if (kind == VQHIP_SQ4_PACKED && d % 8) {
+        const uint32_t W = sq4_words(d);
+        const uint32_t *w = static_cast<const uint32_t *>(src), keep = (1u << (4 * (d % 8))) - 1u;
+        for (uint64_t i = 0; i < n; ++i)
+            if (w[i * W + W - 1] & ~keep)
+                return fail(VQHIP_ERR_INVALID_INPUT, added ? "added row %llu has a pad nibble set" : "row %llu has a pad nibble set", (unsigned long long)i);
+    }
+    return VQHIP_OK;
+}
+
+// n rows of `kind` from host (kind_copy = H2D) or device memory as packed words at dst [n][W] on the device.  Words are
+// copied; codes are packed; f32 rows are encoded a piece at a time into a buffer of codes and packed from there, so that
+// only the words stay.  A device source of codes or words is checked behind the pack / the copy with a flag word read
+// back (which waits for s).
+static int sq4_store(const void *src, hipMemcpyKind kind_copy, int kind, uint64_t n, uint32_t d, const SqbqEncodeOp &op, uint32_t *dst,
+                     bool added, hipStream_t s) {
+    const uint32_t W = sq4_words(d);
+    const bool dev = kind_copy == hipMemcpyDeviceToDevice;
+    DevBuf bad;
+    VQ_TRY(bad.alloc(4));
+    VQ_HIP(hipMemsetAsync(bad.p, 0, 4, s));
+    if (kind == VQHIP_SQ4_PACKED) {
+        VQ_HIP(hipMemcpyAsync(dst, src, (size_t)n * W * 4, kind_copy, s));
+        if (dev) VQ_TRY(launch_sq4_padcheck(dst, n, d, bad.as<uint32_t>(), s));
+    } else if (kind == VQHIP_SQ4_U8) {
+        if (dev) {
+            VQ_TRY(launch_sq4_pack(static_cast<const uint8_t *>(src), n, d, dst, bad.as<uint32_t>(), s));
+        } else {
+            VQ_TRY(staged_rows(src, n, (size_t)d, s, [&](const void *piece, uint64_t r0, uint64_t rn) {
+                return launch_sq4_pack(static_cast<const uint8_t *>(piece), rn, d, dst + r0 * W, bad.as<uint32_t>(), s);
+            }));
+        }
+    } else {
+        const uint64_t per = std::max<uint64_t>(1, kStageBytes / ((size_t)d * 4));  // (staged_rows' piece for rows of 4 d bytes)
+        DevBuf codes;
+        VQ_TRY(codes.alloc((size_t)std::min<uint64_t>(per, n) * d));
+        auto piece = [&](const void *rows, uint64_t r0, uint64_t rn) -> int {
+            VQ_TRY(launch_sqbq_encode(op, static_cast<const float *>(rows), rn * d, codes.as<uint8_t>(), s));
+            return launch_sq4_pack(codes.as<uint8_t>(), rn, d, dst + r0 * W, bad.as<uint32_t>(), s);
+        };
+        if (dev) {
+            for (uint64_t r0 = 0; r0 < n; r0 += per)  // (in stream order: the codes of a piece are packed before the next encode)
+                VQ_TRY(piece(static_cast<const float *>(src) + r0 * d, r0, std::min<uint64_t>(per, n - r0)));
+            VQ_HIP(hipStreamSynchronize(s));  // before `codes` is freed
+        } else {
+            VQ_TRY(staged_rows(src, n, (size_t)d * 4, s, piece));
+        }
+    }
+    if (dev && kind != VQHIP_SQ4_F32) {
+        uint32_t h_bad = 0;
+        VQ_HIP(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, s));
+        VQ_HIP(hipStreamSynchronize(s));
+        if (h_bad && kind == VQHIP_SQ4_U8)
+            return fail(VQHIP_ERR_INVALID_INPUT, added ? "an added row holds a code above 15" : "a row holds a code above 15");
+        if (h_bad) return fail(VQHIP_ERR_INVALID_INPUT, added ? "an added packed row has a pad nibble set" : "a packed row has a pad nibble set");
+    }
+    VQ_HIP(hipStreamSynchronize(s));  // before `bad` is freed
+    return VQHIP_OK;
+}
+
+static int sq4index_create(const void *src, hipMemcpyKind kind_copy, int kind, float mn, float mx, uint32_t levels, uint64_t n,
+                           uint32_t d, int metric, vqhip_sq4index **out) {
+    if (!out) return fail(VQHIP_ERR_NULL_PTR, "out is NULL");
+    *out = nullptr;
+    SqbqEncodeOp op;
+    float step = 0;
+    VQ_TRY(sq_check(mn, mx, levels, &step));
+    VQ_TRY(sq4_check_levels(levels));
+    if (!src) return fail(VQHIP_ERR_NULL_PTR, "source is NULL");
+    if (d == 0) return fail(VQHIP_ERR_INVALID_INPUT, "d must be at least 1");
+    VQ_TRY(check_rows(n));
+    VQ_TRY(check_metric(metric));
+    VQ_TRY(sq4_check_source(src, kind_copy, kind, n, d, false));
+    VQ_TRY(sq_encode_op(mn, mx, levels, &op));
+    VQ_TRY(require_gfx950());
+    hipStream_t s;
+    VQ_TRY(current_stream(&s));
+    std::unique_ptr<vqhip_sq4index> x(new vqhip_sq4index());
+    x->n = n, x->d = d, x->W = sq4_words(d), x->levels = levels, x->mn = mn, x->mx = mx, x->step = step, x->metric = metric;
+    VQ_TRY(x->words.alloc((size_t)n * x->W * 4));
+    VQ_TRY(sq4_store(src, kind_copy, kind, n, d, op, x->words.as<uint32_t>(), false, s));
+    if (vq_is_cos(metric)) {
+        VQ_TRY(x->rnorm.alloc((size_t)n * 4));
+        VQ_TRY(x->norms_enqueue(x->words.p, n, x->rnorm.as<float>(), s));
+    }
+    VQ_HIP(hipStreamSynchronize(s));  // the caller may free or change its source once this returns
+    *out = x.release();
+    return VQHIP_OK;
+}
+
+// n_add rows of `kind` behind the last, with create's checks of the source
+static int sq4index_add(vqhip_sq4index *x, const void *src, hipMemcpyKind kind_copy, int kind, uint64_t n_add) {
+    if (!x) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (n_add == 0) return VQHIP_OK;
+    if (!src) return fail(VQHIP_ERR_NULL_PTR, "source is NULL");
+    VQ_TRY(sq4_check_source(src, kind_copy, kind, n_add, x->d, true));  // (d and the quantizer are fixed at create)
+    SqbqEncodeOp op;
+    VQ_TRY(sq_encode_op(x->mn, x->mx, x->levels, &op));
+    return resident_add(x, src, n_add, [&](char *dst, hipStream_t s) -> int {
+        return sq4_store(src, kind_copy, kind, n_add, x->d, op, reinterpret_cast<uint32_t *>(dst), true, s);
+    });
+}
+
+extern "C" {
+
+int vqhip_sq4index_create(float min, float max, uint32_t levels, const void *src, int kind, uint64_t n, uint32_t d, int metric,
+                          vqhip_sq4index **out) {
+    VQ_API_BEGIN
+    return sq4index_create(src, hipMemcpyHostToDevice, kind, min, max, levels, n, d, metric, out);
+    VQ_API_END
+}
+
+int vqhip_sq4index_create_device(float min, float max, uint32_t levels, const void *dev_src, int kind, uint64_t n, uint32_t d,
+                                 int metric, vqhip_sq4index **out) {
+    VQ_API_BEGIN
+    return sq4index_create(dev_src, hipMemcpyDeviceToDevice, kind, min, max, levels, n, d, metric, out);
+    VQ_API_END
+}
+
+int vqhip_sq4index_destroy(vqhip_sq4index *x) {
+    delete x;
+    return VQHIP_OK;
+}
+
+int vqhip_sq4index_info(const vqhip_sq4index *x, uint64_t *n, uint32_t *d, int *metric, float *min, float *max, uint32_t *levels) {
+    if (!x) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    if (n) *n = x->n;
+    if (d) *d = x->d;
+    if (metric) *metric = x->metric;
+    if (min) *min = x->mn;
+    if (max) *max = x->mx;
+    if (levels) *levels = x->levels;
+    return VQHIP_OK;
+}
+
+int vqhip_sq4index_packed(vqhip_sq4index *x, uint32_t *words) {
+    VQ_API_BEGIN
+    return resident_enter(x, words != nullptr, no_checks, 1, nullptr, [&](Entry &in, hipStream_t s) -> int {
+        VQ_HIP(hipMemcpyAsync(words, x->words.p, (size_t)x->n * x->W * 4, hipMemcpyDeviceToHost, s));
+        VQ_HIP(hipStreamSynchronize(s));
+        in.synced();
+        return VQHIP_OK;
+    });
+    VQ_API_END
+}
+
+int vqhip_sq4index_search(vqhip_sq4index *x, const float *queries, uint32_t nq, uint32_t topk, uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    return resident_search(x, queries, nq, topk, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_sq4index_search_device(vqhip_sq4index *x, const void *dev_queries, uint32_t nq, uint32_t topk, void *dev_idx,
+                                 void *dev_dist) {
+    VQ_API_BEGIN
+    return resident_search_device(x, dev_queries, nq, topk, dev_idx, dev_dist);
+    VQ_API_END
+}
+
+int vqhip_sq4index_search_masked(vqhip_sq4index *x, const float *queries, uint32_t nq, uint32_t topk, const uint32_t *allowed,
+                                 uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    return exact_search_masked(x, queries, nq, topk, allowed, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_sq4index_search_masked_device(vqhip_sq4index *x, const void *dev_queries, uint32_t nq, uint32_t topk,
+                                        const uint32_t *dev_allowed, void *dev_idx, void *dev_dist) {
+    VQ_API_BEGIN
+    return exact_search_masked_device(x, dev_queries, nq, topk, dev_allowed, dev_idx, dev_dist);
+    VQ_API_END
+}
+
+int vqhip_sq4index_rerank(vqhip_sq4index *x, const float *queries, uint32_t nq, const uint32_t *cand, uint32_t c, uint32_t topk,
+                          uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    return exact_rerank(x, queries, nq, cand, c, topk, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_sq4index_range_search(vqhip_sq4index *x, const float *queries, uint32_t nq, const float *radii, uint64_t max_results,
+                                vqhip_range **out) {
+    VQ_API_BEGIN
+    return range_search(x, queries, true, nq, radii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_sq4index_range_search_device(vqhip_sq4index *x, const void *dev_queries, uint32_t nq, const float *radii,
+                                       uint64_t max_results, vqhip_range **out) {
+    VQ_API_BEGIN
+    return range_search(x, dev_queries, false, nq, radii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_sq4index_range_search_masked(vqhip_sq4index *x, const float *queries, uint32_t nq, const float *radii,
+                                       uint64_t max_results, const uint32_t *allowed, vqhip_range **out) {
+    VQ_API_BEGIN
+    return range_search(x, queries, true, nq, radii, max_results, out, true, allowed);
+    VQ_API_END
+}
+
+int vqhip_sq4index_range_search_masked_device(vqhip_sq4index *x, const void *dev_queries, uint32_t nq, const float *radii,
+                                              uint64_t max_results, const uint32_t *dev_allowed, vqhip_range **out) {
+    VQ_API_BEGIN
+    return range_search(x, dev_queries, false, nq, radii, max_results, out, true, dev_allowed);
+    VQ_API_END
+}
+
+int vqhip_sq4index_add(vqhip_sq4index *x, const void *src, int kind, uint64_t n_add) {
+    VQ_API_BEGIN
+    return sq4index_add(x, src, hipMemcpyHostToDevice, kind, n_add);
+    VQ_API_END
+}
+
+int vqhip_sq4index_add_device(vqhip_sq4index *x, const void *dev_src, int kind, uint64_t n_add) {
+    VQ_API_BEGIN
+    return sq4index_add(x, dev_src, hipMemcpyDeviceToDevice, kind, n_add);
+    VQ_API_END
+}
+
+int vqhip_sq4index_remove(vqhip_sq4index *x, const uint32_t *remove_words, uint64_t *removed) {
+    VQ_API_BEGIN
+    return resident_remove(x, remove_words, true, removed);
+    VQ_API_END
+}
+
+int vqhip_sq4index_remove_device(vqhip_sq4index *x, const uint32_t *dev_remove_words, uint64_t *removed) {
     VQ_API_BEGIN
     return resident_remove(x, dev_remove_words, false, removed);
     VQ_API_END

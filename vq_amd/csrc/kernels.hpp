@@ -424,6 +424,27 @@ int launch_abin_rerank(int metric, const uint32_t *P, uint64_t n, uint32_t d, fl
                        const float *queries_dev, const float *qnorm_dev, uint32_t nq, const uint32_t *cand_dev, uint32_t c,
                        uint32_t topk, uint32_t *idx_out_dev, float *dist_out_dev, uint32_t *err_dev, hipStream_t stream);
 
+// exact search, range search and rerank of f32 queries over resident 4-bit SQ codes (k_sq4index.hip): P [n][sq4_words(d)]
+// u32, dimension t of a row in bits 4 (t % 8) .. + 3 of its word t / 8, v(c) = mn + (float)c * step decoded on the fly,
+// rnorm [n] the decoded rows' norms (cosine only).  Batches and workspaces as launch_knn_search / _range / _rerank; the
+// query norms come from launch_knn_norms.
+uint32_t sq4_words(uint32_t d);
+// C [n][d] u8 codes -> out [n][sq4_words(d)], pad nibbles zero; *bad |= 1 where a code is above 15 (the caller zeroes it)
+int launch_sq4_pack(const uint8_t *C, uint64_t n, uint32_t d, uint32_t *out, uint32_t *bad, hipStream_t stream);
+// *bad |= 1 where a packed row has a pad nibble set (the caller zeroes it first)
+int launch_sq4_padcheck(const uint32_t *P, uint64_t n, uint32_t d, uint32_t *bad, hipStream_t stream);
+int launch_sq4_norms(const uint32_t *P, uint64_t n, uint32_t d, float mn, float step, float *out, hipStream_t stream);
+int launch_sq4_search(int metric, const uint32_t *P, uint64_t n, uint32_t d, float mn, float step, const float *rnorm,
+                      const float *queries_dev, const float *qnorm_dev, uint32_t nq, uint32_t topk, float *dist_ws, void *state_ws,
+                      unsigned long long *cand_ws, uint32_t *idx_out_dev, float *dist_out_dev, const uint32_t *mask_dev,
+                      hipStream_t stream);
+int launch_sq4_range(int metric, const uint32_t *P, uint64_t n, uint32_t d, float mn, float step, const float *rnorm,
+                     const float *queries_dev, const float *qnorm_dev, uint32_t nq, const float *radii_dev, uint64_t max_results,
+                     float *dist_ws, void *state_ws, void *range_ws, RangeOut *out, const uint32_t *mask_dev, hipStream_t stream);
+int launch_sq4_rerank(int metric, const uint32_t *P, uint64_t n, uint32_t d, float mn, float step, const float *rnorm,
+                      const float *queries_dev, const float *qnorm_dev, uint32_t nq, const uint32_t *cand_dev, uint32_t c,
+                      uint32_t topk, uint32_t *idx_out_dev, float *dist_out_dev, uint32_t *err_dev, hipStream_t stream);
+
 // prepared per-node data of the screened squared-L2 / Euclidean descent (k_tsvq_screen.hip)
 struct TsvqScreen {
     const float *w = nullptr;     // [n_int][d]  c_left - c_right of every two-child node; cosine: [n_int][2][d] unit vectors of the children

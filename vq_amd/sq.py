@@ -13,6 +13,7 @@ import operator
 import numpy as np
 
 from . import _lib
+from .errors import DimensionMismatch, InvalidParameter
 
 
 def f32_arg(v) -> np.float32:
@@ -97,6 +98,46 @@ class ScalarQuantizer:
 
     def dequantize_device(self, dev_codes: int, count: int, dev_out: int):
         _lib.check(_lib.load().vqhip_sq_decode_device(*self._params, C.c_void_p(dev_codes), int(count), C.c_void_p(dev_out)))
+
+    # -- the 4-bit layout of Scalar4Index (include/vqhip.h, "4-bit scalar index"), on the host ----------------------
+    @staticmethod
+    def pack4_codes(codes) -> np.ndarray:
+        """uint8 codes (n, d), each <= 15 -> uint32 words (n, ceil(d / 8)): dimension t of a row is bits 4 (t % 8) ..
+        4 (t % 8) + 3 of its word t // 8, pad nibbles zero"""
+        c = codes if isinstance(codes, np.ndarray) else np.asarray(codes)
+        if c.dtype != np.uint8:
+            raise InvalidParameter("codes", f"dtype must be uint8, got {c.dtype}")
+        if c.ndim != 2:
+            raise ValueError("expected a 2D array (n, dim)")
+        if c.size and int(c.max()) > 15:
+            raise InvalidParameter("codes", f"a 4-bit code is at most 15, got {int(c.max())}")
+        n, d = c.shape
+        w = (d + 7) // 8
+        p = np.zeros((n, w * 8), np.uint32)
+        p[:, :d] = c
+        p = p.reshape(n, w, 8)
+        out = np.zeros((n, w), np.uint32)
+        for j in range(8):
+            out |= p[:, :, j] << np.uint32(4 * j)
+        return out
+
+    @staticmethod
+    def unpack4_batch(words, dim: int) -> np.ndarray:
+        """uint32 words (n, ceil(dim / 8)) in ``pack4_codes``' layout -> uint8 codes (n, dim); the pad nibbles are not
+        read"""
+        a = words if isinstance(words, np.ndarray) else np.asarray(words)
+        if a.dtype != np.uint32:
+            raise InvalidParameter("words", f"dtype must be uint32, got {a.dtype}")
+        if a.ndim != 2:
+            raise ValueError("expected a 2D array (n, words)")
+        d = usize_arg(dim)
+        if d < 1:
+            raise InvalidParameter("dim", "must be at least 1")
+        if a.shape[1] != (d + 7) // 8:
+            raise DimensionMismatch((d + 7) // 8, a.shape[1])
+        shifts = (np.arange(8, dtype=np.uint32) * np.uint32(4))[None, None, :]
+        c = (a[:, :, None] >> shifts) & np.uint32(15)
+        return np.ascontiguousarray(c.reshape(a.shape[0], -1)[:, :d].astype(np.uint8))
 
     def thresholds(self) -> np.ndarray:
         """float32 (levels,): [0] = -inf, [i] = the smallest input whose code is >= i (NaN if none) -- the table the
