@@ -1610,6 +1610,93 @@ class IVFScalarIndex
     ScalarQuantizer quantizer_;
 };
 
+// Inverted-file index over 4-bit SQ codes (include/vqhip.h, vqhip_ivfsq4_*): IVFScalarIndex for a ScalarQuantizer of at most
+// 16 levels, each row kept at four bits a dimension, eight dimensions a u32 word (Scalar4Index's layout, pad nibbles zero).
+// Rows are added as (list id, u8 codes <= 15) or (list id, packed words), both on the host, or as (list id, f32 row) encoded
+// and packed on the device.  Every result equals IVFScalarIndex over the same codes in the same lists, bit for bit; with
+// nprobe == nlist it is Scalar4Index's search.  The constructor, add_codes, add_packed, codes, packed and list_sizes need
+// no device; the arguments are checked before the device is touched.
+class IVFScalar4Index
+    : public detail::IvfIndex<vqhip_ivfsq4, vqhip_ivfsq4_destroy, vqhip_ivfsq4_list_sizes, vqhip_ivfsq4_probe, vqhip_ivfsq4_search,
+                              vqhip_ivfsq4_remove, vqhip_ivfsq4_uploads> {
+   public:
+    IVFScalar4Index(const float *coarse, std::size_t nlist, std::size_t dim, ScalarQuantizer quantizer, Distance distance = Distance())
+        : quantizer_(quantizer) {
+        check_nlist(nlist);
+        check_dim(dim);
+        if (quantizer_.levels() > 16) throw VqError::InvalidParameter("quantizer", "a 4-bit index holds at most 16 levels");
+        vqhip_ivfsq4 *ix = nullptr;
+        detail::check(vqhip_ivfsq4_create(quantizer_.min(), quantizer_.max(), (std::uint32_t)quantizer_.levels(), coarse,
+                                          (std::uint32_t)nlist, (std::uint32_t)dim, (int)distance.kind(), &ix));
+        adopt(ix, nlist, dim, distance);
+    }
+    const ScalarQuantizer &quantizer() const { return quantizer_; }
+    std::size_t words() const { return (dim_ + 7) / 8; }  // u32 words of a row
+
+    // IVFFlatIndex's range_search over the dequantized rows; with nprobe == nlist it is Scalar4Index's range_search
+    RangeResult range_search(const float *queries, std::size_t nq, const float *radii, std::size_t nprobe,
+                             std::uint64_t max_results = std::uint64_t(1) << 28) const {
+        return range<vqhip_ivfsq4_range_search>(queries, nq, radii, nprobe, max_results);
+    }
+
+    // The filtered forms (include/vqhip.h, vqhip_ivfsq4_search_masked / _range_search_masked), as IVFScalarIndex's
+    using IvfIndex::search;
+    Result search(const float *queries, std::size_t nq, std::size_t topk, std::size_t nprobe, const std::uint32_t *allowed) const {
+        return masked<vqhip_ivfsq4_search_masked>(queries, nq, topk, nprobe, allowed);
+    }
+    Result search(const std::vector<float> &queries, std::size_t topk, std::size_t nprobe, const std::vector<std::uint32_t> &allowed) const {
+        const std::size_t nq = check_masked_vectors(queries, allowed, nullptr);
+        return search(queries.data(), nq, topk, nprobe, allowed.data());
+    }
+    RangeResult range_search(const float *queries, std::size_t nq, const float *radii, std::size_t nprobe, std::uint64_t max_results,
+                             const std::uint32_t *allowed) const {
+        return range_masked<vqhip_ivfsq4_range_search_masked>(queries, nq, radii, nprobe, max_results, allowed);
+    }
+    RangeResult range_search(const std::vector<float> &queries, const std::vector<float> &radii, std::size_t nprobe,
+                             std::uint64_t max_results, const std::vector<std::uint32_t> &allowed) const {
+        const std::size_t nq = check_masked_vectors(queries, allowed, &radii);
+        return range_search(queries.data(), nq, radii.data(), nprobe, max_results, allowed.data());
+    }
+
+    // rows appended in order: list_ids [n] < nlist, codes [n][dim], each <= 15 (codes >= levels are legal); returns the
+    // first new row id.  A refused add leaves the index as it was.
+    std::size_t add_codes(const std::uint32_t *list_ids, const std::uint8_t *codes, std::size_t n) {
+        check_add(list_ids, n, "codes");
+        for (std::size_t e = 0; e < n * dim_; ++e)
+            if (codes[e] > 15) throw VqError::InvalidParameter("codes", "a 4-bit code is at most 15");
+        return added(n, n ? vqhip_ivfsq4_add_codes(ix_.get(), list_ids, codes, n) : VQHIP_OK);
+    }
+    // words [n][words()] in the index layout, pad nibbles zero
+    std::size_t add_packed(const std::uint32_t *list_ids, const std::uint32_t *packed, std::size_t n) {
+        check_add(list_ids, n, "words");
+        if (dim_ % 8) {
+            const std::uint32_t keep = (std::uint32_t(1) << (4 * (dim_ % 8))) - 1u;
+            for (std::size_t i = 0; i < n; ++i)
+                if (packed[i * words() + words() - 1] & ~keep) throw VqError::InvalidParameter("words", "a row has a pad nibble set");
+        }
+        return added(n, n ? vqhip_ivfsq4_add_packed(ix_.get(), list_ids, packed, n) : VQHIP_OK);
+    }
+    // rows [n][dim] f32, encoded and packed on the device (the quantizer's codes); only the words are kept
+    std::size_t add_rows(const std::uint32_t *list_ids, const float *rows, std::size_t n) {
+        check_add(list_ids, n, "rows");
+        return added(n, n ? vqhip_ivfsq4_add_rows(ix_.get(), list_ids, rows, n) : VQHIP_OK);
+    }
+    // the codes unpacked [n][dim] and the words [n][words()], in add order
+    std::vector<std::uint8_t> codes() const {
+        std::vector<std::uint8_t> out(n_ * dim_);
+        detail::check(vqhip_ivfsq4_codes(ix_.get(), out.data()));
+        return out;
+    }
+    std::vector<std::uint32_t> packed() const {
+        std::vector<std::uint32_t> out(n_ * words());
+        detail::check(vqhip_ivfsq4_packed(ix_.get(), out.data()));
+        return out;
+    }
+
+   private:
+    ScalarQuantizer quantizer_;
+};
+
 // Inverted-file index over packed BQ bits (include/vqhip.h, vqhip_ivfbin_*): coarse centroids [nlist][dim], a BinaryQuantizer,
 // rows added as (list id, packed words [ceil(dim / 32)]), as (list id, u8 codes) packed on the host, or as (list id, f32
 // row) packed on the device.  search computes the Hamming distance to the rows of the nprobe lists nearest to the f32

@@ -35,7 +35,7 @@
  * the CALL and give the handle back before they launch, so calls from many threads on one
  * quantizer overlap on the device.  A vqhip_dataset is immutable and complete when it is handed
  * out: share it freely; so is a vqhip_range (every range search, the *_device forms too, waits for
- * its result).  The search handles (flat, sqindex, binary, ivfpq, ivfflat, ivfsq, ivfbin) serialise
+ * its result).  The search handles (flat, sqindex, binary, ivfpq, ivfflat, ivfsq, ivfsq4, ivfbin) serialise
  * their calls on the handle's lock: each call owns every workspace of the handle, a filtered call's
  * row mask is in force for that call alone, and a call that needs a larger workspace frees the old
  * one only after the device has finished with it.  An add to an inverted file may run beside
@@ -1104,6 +1104,73 @@ int vqhip_ivfsq_range_search_masked(vqhip_ivfsq *ix, const float *queries, uint3
 int vqhip_ivfsq_range_search_masked_device(vqhip_ivfsq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe,
                                            const float *radii, uint64_t max_results, const uint32_t *dev_allowed,
                                            vqhip_range **out);
+
+/* ---- inverted-file 4-bit scalar index: exact distances to packed 4-bit SQ codes over the probed lists (k_ivfsq4.hip;
+ * DESIGN.md 30) ---------
+ * No reference counterpart.  vqhip_ivfsq with each row kept as vqhip_sq4index keeps it: four bits a dimension, eight
+ * dimensions a word.  An index is fixed by a ScalarQuantizer(min, max, levels) with 2 <= levels <= 16 -- the parameters go
+ * through vqhip_sq_check, whose status and text create reports unchanged, and behind it levels > 16 is
+ * VQHIP_ERR_INVALID_INPUT with vqhip_sq4index_create's text --, coarse centroids C [nlist][dim] f32 (1 <= nlist <= 65536), a
+ * metric (any of the five) and, per row i (ids in add order, n < 2^32 in all), a list id list[i] < nlist and dim four-bit
+ * codes.  Several adds equal one add of the concatenation.
+ *   layout  vqhip_sq4index's: dimension t of row i is bits 4 (t % 8) .. + 3 of u32 word i * W + t / 8, W = ceil(dim / 8);
+ *           pad nibbles (dimensions >= dim of the last word) are zero.
+ *   decode  v(c) = min + (float)c * step, un-fused, two roundings, for every nibble value 0 .. 15: codes >= levels are
+ *           legal and decode by the same formula.
+ *   P(q)    = exactly vqhip_ivfflat_probe over C under the same metric.  1 <= nprobe <= min(nlist, 1024).
+ *   S(q)    = { i : list[i] in P(q) }.
+ *   D(q, i) = Distance::compute(q, v(codes[i])) bit for bit, in the flat index's arithmetic and order (vqhip_ivfsq's D);
+ *             under the cosines the row norms are vqhip_sq4index's, computed once per upload of the rows.
+ *   search  = vqhip_ivfsq_search's: the topk rows of S(q) by (key(D), row id) ascending, 1 <= topk <= min(n, 1024), NaN
+ *             last as 0x7FC00000, padding idx 0xFFFFFFFF / dist +inf behind every real row.  Run-to-run deterministic.
+ * Identities, each for indices and for distances as uint32 bits, for search, search_masked, range_search and
+ * range_search_masked at every nprobe and topk: (1) the index equals vqhip_ivfsq over the same codes, one byte each, in the
+ * same lists; (2) it equals vqhip_ivfflat (dtype 0) over the rows vqhip_sq_decode gives for the codes, in the same lists; (3)
+ * with nprobe == nlist it equals vqhip_sq4index over the codes in add order on the same call; (4) after any sequence of
+ * adds and removes it equals a fresh index given the remaining rows in one add ("removing rows from an inverted file"
+ * below), a current device state staying current.
+ * add_codes takes host u8 codes [n][dim], each <= 15, and packs them on the host; add_packed takes host words [n][W]
+ * with every pad nibble zero; both are host-only.  add_rows takes host f32 rows [n][dim], encodes them on the device as
+ * vqhip_sq_encode does and packs them there (vqhip_sq4index's path for f32 rows), and keeps only the words; it is the one
+ * add that needs the device.  All three check every list id, then every code / pad nibble, on the host before anything is
+ * stored (VQHIP_ERR_INVALID_INPUT): a refused add leaves the index as it was.  codes copies the codes out unpacked
+ * (codes_out [n][dim] u8), packed copies the words (words_out [n][W]), both in add order and host-only.  info: any output
+ * pointer may be NULL.  The other entry points -- list_sizes, probe, search, search_device, the two range searches, the
+ * four masked forms (the ROW MASK of "filtered search on the inverted-file flat and scalar index" above), remove, uploads,
+ * destroy -- have vqhip_ivfsq's signatures, checks, order of checks, device ownership, batches and lock.  The host keeps
+ * 4 n W bytes, the device 4 n W (+ 4 n under the cosines, + 4 n of row ids): half of vqhip_ivfsq's for dim % 8 == 0. */
+typedef struct vqhip_ivfsq4 vqhip_ivfsq4;
+int vqhip_ivfsq4_create(float min, float max, uint32_t levels, const float *coarse, uint32_t nlist, uint32_t dim, int metric,
+                        vqhip_ivfsq4 **out);
+int vqhip_ivfsq4_destroy(vqhip_ivfsq4 *ix);
+int vqhip_ivfsq4_add_codes(vqhip_ivfsq4 *ix, const uint32_t *list_ids, const uint8_t *codes, uint64_t n);
+int vqhip_ivfsq4_add_packed(vqhip_ivfsq4 *ix, const uint32_t *list_ids, const uint32_t *words, uint64_t n);
+int vqhip_ivfsq4_add_rows(vqhip_ivfsq4 *ix, const uint32_t *list_ids, const float *rows, uint64_t n);
+int vqhip_ivfsq4_info(const vqhip_ivfsq4 *ix, uint64_t *n, uint32_t *nlist, uint32_t *dim, int *metric, float *min, float *max,
+                      uint32_t *levels);
+int vqhip_ivfsq4_list_sizes(vqhip_ivfsq4 *ix, uint64_t *sizes);
+int vqhip_ivfsq4_codes(vqhip_ivfsq4 *ix, uint8_t *codes_out);
+int vqhip_ivfsq4_packed(vqhip_ivfsq4 *ix, uint32_t *words_out);
+int vqhip_ivfsq4_probe(vqhip_ivfsq4 *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t *lists_out);
+int vqhip_ivfsq4_search(vqhip_ivfsq4 *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                        uint32_t *idx_out, float *dist_out);
+int vqhip_ivfsq4_search_device(vqhip_ivfsq4 *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                               void *dev_idx, void *dev_dist);
+int vqhip_ivfsq4_range_search(vqhip_ivfsq4 *ix, const float *queries, uint32_t nq, uint32_t nprobe, const float *radii,
+                              uint64_t max_results, vqhip_range **out);
+int vqhip_ivfsq4_range_search_device(vqhip_ivfsq4 *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe,
+                                     const float *radii, uint64_t max_results, vqhip_range **out);
+int vqhip_ivfsq4_search_masked(vqhip_ivfsq4 *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                               const uint32_t *allowed, uint32_t *idx_out, float *dist_out);
+int vqhip_ivfsq4_search_masked_device(vqhip_ivfsq4 *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                                      const uint32_t *dev_allowed, void *dev_idx, void *dev_dist);
+int vqhip_ivfsq4_range_search_masked(vqhip_ivfsq4 *ix, const float *queries, uint32_t nq, uint32_t nprobe, const float *radii,
+                                     uint64_t max_results, const uint32_t *allowed, vqhip_range **out);
+int vqhip_ivfsq4_range_search_masked_device(vqhip_ivfsq4 *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe,
+                                            const float *radii, uint64_t max_results, const uint32_t *dev_allowed,
+                                            vqhip_range **out);
+int vqhip_ivfsq4_remove(vqhip_ivfsq4 *ix, const uint32_t *remove_words, uint64_t *removed);
+int vqhip_ivfsq4_uploads(const vqhip_ivfsq4 *ix, uint64_t *uploads);
 
 /* ---- inverted-file binary index: Hamming top-k over packed BQ bits in the probed lists (k_ivfbin.hip) ---------
  * No reference counterpart.  vqhip_ivfflat's probe and schedule over vqhip_binary's codes.  An index is fixed by a

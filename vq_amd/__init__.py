@@ -2,7 +2,7 @@
 encode path of CogitatorTech/vq, and of its elementwise scalar / binary quantizers, behind the
 reference's own Quantizer interface, exact k-NN search over resident rows (FlatIndex), an inverted-file
 index over PQ codes (IVFPQIndex) one over the rows themselves (IVFFlatIndex) and one over SQ codes
-(IVFScalarIndex) and one over packed BQ bits (IVFBinaryIndex), a Hamming index over packed BQ codes (BinaryIndex), an exact index over
+(IVFScalarIndex), one over the same codes at four bits a dimension (IVFScalar4Index) and one over packed BQ bits (IVFBinaryIndex), a Hamming index over packed BQ codes (BinaryIndex), an exact index over
 resident SQ codes (ScalarIndex), one over the same codes at four bits a dimension (Scalar4Index) and an exact index of f32 queries over packed BQ bits (AsymmetricBinaryIndex).
 
 The compute path is libvqhip.so (hand-written HIP for CDNA4, C ABI in include/vqhip.h).
@@ -22,6 +22,7 @@ from .ivf import IVFPQIndex
 from .ivf_flat import IVFFlatIndex
 from .ivf_binary import IVFBinaryIndex
 from .ivf_scalar import IVFScalarIndex
+from .ivf_scalar4 import IVFScalar4Index
 from .pq import ProductQuantizer, fit_codebooks
 from .scalar4_index import Scalar4Index
 from .scalar_index import ScalarIndex
@@ -29,7 +30,7 @@ from .sq import ScalarQuantizer
 from .tsvq import TSVQ
 
 __all__ = [
-    "Distance", "AsymmetricBinaryIndex", "BinaryIndex", "BinaryQuantizer", "FlatIndex", "IVFBinaryIndex", "IVFFlatIndex", "IVFPQIndex", "IVFScalarIndex", "RangeResult", "Scalar4Index", "ScalarIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
+    "Distance", "AsymmetricBinaryIndex", "BinaryIndex", "BinaryQuantizer", "FlatIndex", "IVFBinaryIndex", "IVFFlatIndex", "IVFPQIndex", "IVFScalar4Index", "IVFScalarIndex", "RangeResult", "Scalar4Index", "ScalarIndex", "ScalarQuantizer", "ProductQuantizer", "TSVQ", "fit_codebooks", "VqError", "DimensionMismatch", "EmptyInput",
     "InvalidParameter", "InvalidData", "FfiError", "get_simd_backend", "pack_row_mask",
 ]
 

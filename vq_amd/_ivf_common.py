@@ -1,4 +1,4 @@
-"""What ``IVFPQIndex``, ``IVFFlatIndex``, ``IVFScalarIndex`` and ``IVFBinaryIndex`` share: the coarse centroids and list ids, the checks of
+"""What ``IVFPQIndex``, ``IVFFlatIndex``, ``IVFScalarIndex``, ``IVFScalar4Index`` and ``IVFBinaryIndex`` share: the coarse centroids and list ids, the checks of
 queries, ``nprobe`` and ``topk``, probe / search / rerank over the device handle, and the readers of the index files.
 A subclass keeps its payload (codes or rows), its add paths, ``_handle``, ``close`` and its file layout.
 ``IVFRangeMixin`` adds the range search of the two indexes whose distances are exact (not ``IVFPQIndex``)."""
@@ -313,7 +313,7 @@ class IVFIndexBase:
 
 
 class IVFRangeMixin:
-    """range search over the probed lists, for an IVFIndexBase whose distances are exact (IVFFlatIndex, IVFScalarIndex):
+    """range search over the probed lists, for an IVFIndexBase whose distances are exact (IVFFlatIndex, IVFScalarIndex, IVFScalar4Index):
     ``S(q)`` and ``D(q, i)`` are `search`'s at the same nprobe"""
 
     def range_search(self, queries, radius, nprobe: int = 8, max_results: int = DEFAULT_MAX_RESULTS):

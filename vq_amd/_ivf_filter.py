@@ -1,5 +1,5 @@
-"""``IVFFilterMixin`` -- the filtered forms of search and range search of the two inverted files whose distances are exact
-(``IVFFlatIndex``, ``IVFScalarIndex``; ``IVFBinaryIndex`` has ``_binary_filter.py``'s methods, ``IVFPQIndex`` its own ``masked_search``).  A
+"""``IVFFilterMixin`` -- the filtered forms of search and range search of the inverted files whose distances are exact
+(``IVFFlatIndex``, ``IVFScalarIndex``, ``IVFScalar4Index``; ``IVFBinaryIndex`` has ``_binary_filter.py``'s methods, ``IVFPQIndex`` its own ``masked_search``).  A
 filter is one row mask per call, `allowed`: a bool array (n,) (True: the row may be returned) or its uint32 words
 (``pack_row_mask``), n being ``len(index)`` at the time of the call; None: every row, the unfiltered call.  Probing takes no mask: ``P(q)`` is the nprobe nearest lists
 whatever they hold, and the searched set is the allowed rows of ``S(q)`` (include/vqhip.h, vqhip_ivfflat_search_masked)."""

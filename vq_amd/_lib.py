@@ -297,6 +297,26 @@ SIGNATURES = {
     "vqhip_ivfsq_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "vqhip_ivfsq_range_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _u32p, _vpp]),
     "vqhip_ivfsq_range_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _vp, _vpp]),
+    "vqhip_ivfsq4_create": (C.c_int, [C.c_float, C.c_float, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_int, _vpp]),
+    "vqhip_ivfsq4_destroy": (C.c_int, [_vp]),
+    "vqhip_ivfsq4_add_codes": (C.c_int, [_vp, _u32p, _u8p, C.c_uint64]),
+    "vqhip_ivfsq4_add_packed": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64]),
+    "vqhip_ivfsq4_add_rows": (C.c_int, [_vp, _u32p, _f32p, C.c_uint64]),
+    "vqhip_ivfsq4_info": (C.c_int, [_vp, _u64p, _u32p, _u32p, C.POINTER(C.c_int), _f32p, _f32p, _u32p]),
+    "vqhip_ivfsq4_list_sizes": (C.c_int, [_vp, _u64p]),
+    "vqhip_ivfsq4_codes": (C.c_int, [_vp, _u8p]),
+    "vqhip_ivfsq4_packed": (C.c_int, [_vp, _u32p]),
+    "vqhip_ivfsq4_probe": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p]),
+    "vqhip_ivfsq4_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "vqhip_ivfsq4_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "vqhip_ivfsq4_range_search": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _vpp]),
+    "vqhip_ivfsq4_range_search_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _vpp]),
+    "vqhip_ivfsq4_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _f32p]),
+    "vqhip_ivfsq4_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "vqhip_ivfsq4_range_search_masked": (C.c_int, [_vp, _f32p, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _u32p, _vpp]),
+    "vqhip_ivfsq4_range_search_masked_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _f32p, C.c_uint64, _vp, _vpp]),
+    "vqhip_ivfsq4_remove": (C.c_int, [_vp, _u32p, _u64p]),
+    "vqhip_ivfsq4_uploads": (C.c_int, [_vp, _u64p]),
     "vqhip_ivfbin_create": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, _f32p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, _vpp]),
     "vqhip_ivfbin_destroy": (C.c_int, [_vp]),
     "vqhip_ivfbin_add_packed": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64]),
@@ -1354,6 +1374,56 @@ class IVFSQ(_IVFExactHandle):
     def codes(self) -> np.ndarray:
         out = np.empty((self.info()[0], self.dim), np.uint8)
         check(load().vqhip_ivfsq_codes(self.raw, ptr(out, _u8p)))
+        return out
+
+
+class IVFSQ4(_IVFExactHandle):
+    """vqhip_ivfsq4: inverted-file 4-bit scalar index -- coarse centroids, a ScalarQuantizer's codes (levels <= 16) packed
+    eight to a word in lists, exact distances to the decoded rows over the probed lists (k_ivfsq4.hip).  Create, add_codes,
+    add_packed, codes, packed, info and list_sizes are host-only; add_rows encodes and packs on the device; the device
+    state is built by the first probe or search."""
+
+    _prefix = "vqhip_ivfsq4"
+    _destroy = "vqhip_ivfsq4_destroy"
+
+    def __init__(self, coarse, mn: float, mx: float, levels: int, metric: int):
+        c = f32c(coarse)
+        h = C.c_void_p()
+        check(load().vqhip_ivfsq4_create(mn, mx, int(levels), ptr(c, _f32p), c.shape[0], c.shape[1], int(metric), C.byref(h)))
+        super().__init__(h)
+        self.nlist, self.dim, self.metric = c.shape[0], c.shape[1], int(metric)
+        self.words = (self.dim + 7) // 8
+
+    def add_codes(self, list_ids, codes):
+        lid = np.ascontiguousarray(list_ids, dtype=np.uint32)
+        c = np.ascontiguousarray(codes, dtype=np.uint8)
+        check(load().vqhip_ivfsq4_add_codes(self.raw, ptr(lid, _u32p), ptr(c, _u8p), lid.shape[0]))
+
+    def add_packed(self, list_ids, words):
+        lid = np.ascontiguousarray(list_ids, dtype=np.uint32)
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        check(load().vqhip_ivfsq4_add_packed(self.raw, ptr(lid, _u32p), ptr(w, _u32p), lid.shape[0]))
+
+    def add_rows(self, list_ids, rows):
+        lid = np.ascontiguousarray(list_ids, dtype=np.uint32)
+        r = f32c(rows)
+        check(load().vqhip_ivfsq4_add_rows(self.raw, ptr(lid, _u32p), ptr(r, _f32p), lid.shape[0]))
+
+    def info(self):
+        n, nlist, dim, metric = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_int()
+        mn, mx, levels = C.c_float(), C.c_float(), C.c_uint32()
+        check(load().vqhip_ivfsq4_info(self.raw, C.byref(n), C.byref(nlist), C.byref(dim), C.byref(metric), C.byref(mn), C.byref(mx),
+                                       C.byref(levels)))
+        return int(n.value), int(nlist.value), int(dim.value), int(metric.value), float(mn.value), float(mx.value), int(levels.value)
+
+    def codes(self) -> np.ndarray:
+        out = np.empty((self.info()[0], self.dim), np.uint8)
+        check(load().vqhip_ivfsq4_codes(self.raw, ptr(out, _u8p)))
+        return out
+
+    def packed(self) -> np.ndarray:
+        out = np.empty((self.info()[0], self.words), np.uint32)
+        check(load().vqhip_ivfsq4_packed(self.raw, ptr(out, _u32p)))
         return out
 
 

@@ -1,5 +1,5 @@
 // api_ivf.hip -- extern "C" entry points of the inverted-file indexes (vqhip_ivfpq, vqhip_ivfflat, vqhip_ivfsq,
-// vqhip_ivfbin) and their host layer: the inverted lists, probe, search, range search, add and remove.  Host-side
+// vqhip_ivfsq4, vqhip_ivfbin) and their host layer: the inverted lists, probe, search, range search, add and remove.  Host-side
 // orchestration only.
 #include <algorithm>
 #include <cstring>
@@ -13,8 +13,8 @@
 #include "ivf_remove.hpp"
 
 // ------------------------------------------------------------------ inverted lists: the shared host layer ----
-// What vqhip_ivfpq, vqhip_ivfflat, vqhip_ivfsq and vqhip_ivfbin have in common.  Host state: the coarse centroids and every added
-// row's list id and payload (PQ codes, f32 / f16 elements, SQ codes or packed BQ words) in add order.  The device state -- a flat index
+// What vqhip_ivfpq, vqhip_ivfflat, vqhip_ivfsq, vqhip_ivfsq4 and vqhip_ivfbin have in common.  Host state: the coarse centroids and every added
+// row's list id and payload (PQ codes, f32 / f16 elements, SQ codes, packed 4-bit SQ words or packed BQ words) in add order.  The device state -- a flat index
 // over the centroids and the rows in list order (off / ids / payload) -- is built on the current device by the first
 // probe or search and rebuilt there after an add: a host counting sort gives the order (O(n) per rebuild), and the
 // payload goes up through a staging buffer of at most kIvfflatStage bytes, list order gathered a piece at a time.
@@ -622,9 +622,10 @@ struct IvfOverW : IvfFiltered {
     }
 };
 
-// ------------------------------------------------------------------ inverted-file flat and scalar (k_ivfflat.hip, k_ivfsq.hip) ----
-// The two indexes of exact distances: the payload is the rows themselves (f32 or f16 elements) or their SQ codes (dim
-// bytes), with the rows' norms under the cosines.  They differ in the norms kernel and the distance launcher.
+// ------------------------------------------------------------------ inverted-file flat and scalar (k_ivfflat.hip, k_ivfsq.hip, k_ivfsq4.hip) ----
+// The three indexes of exact distances: the payload is the rows themselves (f32 or f16 elements), their SQ codes (dim
+// bytes) or their 4-bit SQ codes (ceil(dim / 8) words), with the rows' norms under the cosines.  They differ in the norms
+// kernel and the distance launcher.
 template <class T>
 struct IvfExact : IvfOverW<T> {
     DevBuf d_rnorm;
@@ -674,6 +675,25 @@ struct vqhip_ivfsq : IvfExact<vqhip_ivfsq> {
     }
     int distances(const IvffPlan &p, const IvfBatchView &v, const float *Q, uint32_t q0, hipStream_t s) {
         return launch_ivfsq_distances(p, v, metric, d_payload.as<uint8_t>(), dim, mn, step, d_rnorm.as<float>(), Q, qnorms(q0), s);
+    }
+};
+
+// The scalar index at four bits a dimension (k_ivfsq4.hip): the payload is the packed words of
+// vqhip_sq4index's layout, W = sq4_words(dim) a row, pad nibbles zero, in add order on the host.
+struct vqhip_ivfsq4 : IvfExact<vqhip_ivfsq4> {
+    uint32_t W = 0, levels = 0;
+    float mn = 0, mx = 0, step = 0;
+    SqbqEncodeOp op;  // add_rows: the encode of this quantizer
+
+    int ready(hipStream_t s) {
+        return ivf_ready(this, s, ivf_no_hook, [&] {
+            if (!vq_is_cos(metric)) return VQHIP_OK;
+            VQ_TRY(d_rnorm.alloc((size_t)n * 4));
+            return launch_sq4_norms(d_payload.as<uint32_t>(), n, dim, mn, step, d_rnorm.as<float>(), s);
+        });
+    }
+    int distances(const IvffPlan &p, const IvfBatchView &v, const float *Q, uint32_t q0, hipStream_t s) {
+        return launch_ivfsq4_distances(p, v, metric, d_payload.as<uint32_t>(), dim, mn, step, d_rnorm.as<float>(), Q, qnorms(q0), s);
     }
 };
 
@@ -1014,6 +1034,215 @@ int vqhip_ivfsq_range_search_masked(vqhip_ivfsq *ix, const float *queries, uint3
 int vqhip_ivfsq_range_search_masked_device(vqhip_ivfsq *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe,
                                            const float *radii, uint64_t max_results, const uint32_t *dev_allowed,
                                            vqhip_range **out) {
+    VQ_API_BEGIN
+    return ivf_range_masked(ix, dev_queries, false, nq, nprobe, radii, max_results, dev_allowed, out);
+    VQ_API_END
+}
+
+int vqhip_ivfsq4_create(float min, float max, uint32_t levels, const float *coarse, uint32_t nlist, uint32_t dim, int metric,
+                        vqhip_ivfsq4 **out) {
+    VQ_API_BEGIN
+    if (!out) return fail(VQHIP_ERR_NULL_PTR, "out is NULL");
+    *out = nullptr;
+    float step = 0;
+    VQ_TRY(sq_check(min, max, levels, &step));
+    if (levels > 16) return fail(VQHIP_ERR_INVALID_INPUT, "levels %u: a 4-bit index holds at most 16", levels);  // (vqhip_sq4index's)
+    VQ_TRY(ivf_check_lists(coarse, nlist));
+    if (dim == 0) return fail(VQHIP_ERR_INVALID_INPUT, "dim must be at least 1");
+    VQ_TRY(check_metric(metric));
+    std::unique_ptr<vqhip_ivfsq4> ix(new vqhip_ivfsq4());
+    VQ_TRY(sq_encode_op(min, max, levels, &ix->op));
+    ix->W = sq4_words(dim);
+    ivf_init(ix.get(), coarse, nlist, dim, metric, (size_t)ix->W * 4);
+    ix->levels = levels;
+    ix->mn = min, ix->mx = max, ix->step = step;
+    *out = ix.release();
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_ivfsq4_destroy(vqhip_ivfsq4 *ix) {
+    delete ix;
+    return VQHIP_OK;
+}
+
+int vqhip_ivfsq4_add_codes(vqhip_ivfsq4 *ix, const uint32_t *list_ids, const uint8_t *codes, uint64_t n) {
+    VQ_API_BEGIN
+    return ivf_add(ix, list_ids, codes, n, [&] {
+        const uint32_t d = ix->dim, W = ix->W;
+        for (uint64_t i = 0; i < n; ++i)
+            for (uint32_t t = 0; t < d; ++t)
+                if (codes[i * d + t] > 15)
+                    return fail(VQHIP_ERR_INVALID_INPUT, "added row %llu holds code %u: a 4-bit code is at most 15", (unsigned long long)i,
+                                (unsigned)codes[i * d + t]);
+        const size_t have = ix->payload.size();
+        ix->payload.resize(have + (size_t)n * ix->row_b, 0);
+        uint32_t *w = reinterpret_cast<uint32_t *>(ix->payload.data() + have);  // (row_b is a multiple of 4, the vector's base aligned)
+        for (uint64_t i = 0; i < n; ++i)
+            for (uint32_t t = 0; t < d; ++t) w[i * W + t / 8] |= (uint32_t)codes[i * d + t] << (4 * (t % 8));
+        return VQHIP_OK;
+    });
+    VQ_API_END
+}
+
+int vqhip_ivfsq4_add_packed(vqhip_ivfsq4 *ix, const uint32_t *list_ids, const uint32_t *words, uint64_t n) {
+    VQ_API_BEGIN
+    return ivf_add(ix, list_ids, words, n, [&] {
+        if (ix->dim % 8) {
+            const uint32_t keep = (1u << (4 * (ix->dim % 8))) - 1u;
+            for (uint64_t i = 0; i < n; ++i)
+                if (words[i * ix->W + ix->W - 1] & ~keep)
+                    return fail(VQHIP_ERR_INVALID_INPUT, "added row %llu has a pad nibble set", (unsigned long long)i);
+        }
+        return ivf_append(ix, words, n);
+    });
+    VQ_API_END
+}
+
+int vqhip_ivfsq4_add_rows(vqhip_ivfsq4 *ix, const uint32_t *list_ids, const float *rows, uint64_t n) {
+    VQ_API_BEGIN
+    return ivf_add(ix, list_ids, rows, n, [&] {
+        VQ_TRY(require_gfx950());
+        VQ_TRY(ix->on_device());
+        hipStream_t s;
+        VQ_TRY(current_stream(&s));
+        const uint32_t d = ix->dim;
+        const size_t have = ix->payload.size(), row_b = ix->row_b;
+        ix->payload.resize(have + (size_t)n * row_b);
+        auto pack = [&]() -> int {  // vqhip_sq4index's path for f32 rows: encode a piece, pack it, and the words come down
+            const uint64_t per = std::max<uint64_t>(1, kStageBytes / ((size_t)d * 4));  // (staged_rows' piece for rows of 4 d bytes)
+            const uint64_t piece_n = std::min<uint64_t>(per, n);
+            DevBuf codes, words, bad;
+            VQ_TRY(codes.alloc((size_t)piece_n * d));
+            VQ_TRY(words.alloc((size_t)piece_n * row_b));
+            VQ_TRY(bad.alloc(4));
+            VQ_HIP(hipMemsetAsync(bad.p, 0, 4, s));  // (an encoded code is below levels <= 16: never set)
+            return staged_rows(rows, n, (size_t)d * 4, s, [&](const void *piece, uint64_t r0, uint64_t rn) -> int {
+                VQ_TRY(launch_sqbq_encode(ix->op, static_cast<const float *>(piece), rn * d, codes.as<uint8_t>(), s));
+                VQ_TRY(launch_sq4_pack(codes.as<uint8_t>(), rn, d, words.as<uint32_t>(), bad.as<uint32_t>(), s));
+                VQ_HIP(hipMemcpyAsync(ix->payload.data() + have + (size_t)r0 * row_b, words.p, (size_t)rn * row_b, hipMemcpyDeviceToHost, s));
+                return VQHIP_OK;  // (staged_rows waits for the piece)
+            });
+        };
+        const int rc = pack();
+        if (rc != VQHIP_OK) ix->payload.resize(have);  // (nothing is stored)
+        return rc;
+    });
+    VQ_API_END
+}
+
+int vqhip_ivfsq4_info(const vqhip_ivfsq4 *ix, uint64_t *n, uint32_t *nlist, uint32_t *dim, int *metric, float *min, float *max,
+                      uint32_t *levels) {
+    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    std::lock_guard<std::recursive_mutex> lock(const_cast<vqhip_ivfsq4 *>(ix)->sync.mu);  // (n changes under add)
+    if (n) *n = ix->n;
+    if (nlist) *nlist = ix->nlist;
+    if (dim) *dim = ix->dim;
+    if (metric) *metric = ix->metric;
+    if (min) *min = ix->mn;
+    if (max) *max = ix->mx;
+    if (levels) *levels = ix->levels;
+    return VQHIP_OK;
+}
+
+int vqhip_ivfsq4_list_sizes(vqhip_ivfsq4 *ix, uint64_t *sizes) {
+    VQ_API_BEGIN
+    return ivf_list_sizes(ix, sizes);
+    VQ_API_END
+}
+
+int vqhip_ivfsq4_codes(vqhip_ivfsq4 *ix, uint8_t *codes_out) {
+    VQ_API_BEGIN
+    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);
+    if (ix->n == 0) return VQHIP_OK;
+    if (!codes_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(ix->payload.data());
+    for (uint64_t i = 0; i < ix->n; ++i)
+        for (uint32_t t = 0; t < ix->dim; ++t) codes_out[i * ix->dim + t] = (uint8_t)((w[i * ix->W + t / 8] >> (4 * (t % 8))) & 15u);
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_ivfsq4_packed(vqhip_ivfsq4 *ix, uint32_t *words_out) {
+    VQ_API_BEGIN
+    if (!ix) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    Entry in(ix->sync);
+    if (ix->n == 0) return VQHIP_OK;
+    if (!words_out) return fail(VQHIP_ERR_NULL_PTR, "NULL argument");
+    memcpy(words_out, ix->payload.data(), ix->payload.size());
+    return VQHIP_OK;
+    VQ_API_END
+}
+
+int vqhip_ivfsq4_remove(vqhip_ivfsq4 *ix, const uint32_t *remove_words, uint64_t *removed) {
+    VQ_API_BEGIN
+    return ivf_remove(ix, remove_words, removed);
+    VQ_API_END
+}
+
+int vqhip_ivfsq4_uploads(const vqhip_ivfsq4 *ix, uint64_t *uploads) {
+    return ivf_uploads(ix, uploads);
+}
+
+int vqhip_ivfsq4_probe(vqhip_ivfsq4 *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t *lists_out) {
+    VQ_API_BEGIN
+    return ivf_probe(ix, queries, nq, nprobe, lists_out);
+    VQ_API_END
+}
+
+int vqhip_ivfsq4_search(vqhip_ivfsq4 *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk, uint32_t *idx_out,
+                        float *dist_out) {
+    VQ_API_BEGIN
+    return ivf_search(ix, queries, nq, nprobe, topk, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_ivfsq4_search_device(vqhip_ivfsq4 *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk, void *dev_idx,
+                               void *dev_dist) {
+    VQ_API_BEGIN
+    return ivf_search_device(ix, dev_queries, nq, nprobe, topk, dev_idx, dev_dist);
+    VQ_API_END
+}
+
+int vqhip_ivfsq4_range_search(vqhip_ivfsq4 *ix, const float *queries, uint32_t nq, uint32_t nprobe, const float *radii,
+                              uint64_t max_results, vqhip_range **out) {
+    VQ_API_BEGIN
+    return ivf_range(ix, queries, true, nq, nprobe, radii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_ivfsq4_range_search_device(vqhip_ivfsq4 *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, const float *radii,
+                                     uint64_t max_results, vqhip_range **out) {
+    VQ_API_BEGIN
+    return ivf_range(ix, dev_queries, false, nq, nprobe, radii, max_results, out);
+    VQ_API_END
+}
+
+int vqhip_ivfsq4_search_masked(vqhip_ivfsq4 *ix, const float *queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                               const uint32_t *allowed, uint32_t *idx_out, float *dist_out) {
+    VQ_API_BEGIN
+    return ivf_search_masked(ix, queries, true, nq, nprobe, topk, allowed, idx_out, dist_out);
+    VQ_API_END
+}
+
+int vqhip_ivfsq4_search_masked_device(vqhip_ivfsq4 *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe, uint32_t topk,
+                                      const uint32_t *dev_allowed, void *dev_idx, void *dev_dist) {
+    VQ_API_BEGIN
+    return ivf_search_masked(ix, dev_queries, false, nq, nprobe, topk, dev_allowed, dev_idx, dev_dist);
+    VQ_API_END
+}
+
+int vqhip_ivfsq4_range_search_masked(vqhip_ivfsq4 *ix, const float *queries, uint32_t nq, uint32_t nprobe, const float *radii,
+                                     uint64_t max_results, const uint32_t *allowed, vqhip_range **out) {
+    VQ_API_BEGIN
+    return ivf_range_masked(ix, queries, true, nq, nprobe, radii, max_results, allowed, out);
+    VQ_API_END
+}
+
+int vqhip_ivfsq4_range_search_masked_device(vqhip_ivfsq4 *ix, const void *dev_queries, uint32_t nq, uint32_t nprobe,
+                                            const float *radii, uint64_t max_results, const uint32_t *dev_allowed,
+                                            vqhip_range **out) {
     VQ_API_BEGIN
     return ivf_range_masked(ix, dev_queries, false, nq, nprobe, radii, max_results, dev_allowed, out);
     VQ_API_END

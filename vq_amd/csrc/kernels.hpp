@@ -347,6 +347,10 @@ int launch_ivfflat_distances(const IvffPlan &p, const IvfBatchView &v, int metri
                              const float *rnorm, const float *queries, const float *qnorm, hipStream_t stream);
 int launch_ivfsq_distances(const IvffPlan &p, const IvfBatchView &v, int metric, const uint8_t *C, uint32_t d, float mn, float step,
                            const float *rnorm, const float *queries, const float *qnorm, hipStream_t stream);
+//   ivfsq4   words [n][sq4_words(d)] u32, eight 4-bit codes a word (k_sq4index.hip's layout, pad nibbles zero), decoded as
+//            ivfsq's; rnorm [n] from launch_sq4_norms over the words (k_ivfsq4.hip)
+int launch_ivfsq4_distances(const IvffPlan &p, const IvfBatchView &v, int metric, const uint32_t *words, uint32_t d, float mn,
+                            float step, const float *rnorm, const float *queries, const float *qnorm, hipStream_t stream);
 int bin_load_width(const uint32_t *P, uint32_t W);
 int launch_ivfbin_distances(const IvffPlan &p, const IvfBatchView &v, int metric, const uint32_t *P, uint32_t d, const float *S,
                             const uint32_t *Q, hipStream_t stream);

@@ -7,6 +7,7 @@
     python -m vq_amd.evalcli bq   [--seed 66 --dim 384]
     python -m vq_amd.evalcli ivfflat [--seed 66 --dim 384 --nlist 256 --nprobe 1 8 32 --max-iters 10]
     python -m vq_amd.evalcli ivfsq   [--seed 66 --dim 384 --nlist 256 --nprobe 1 8 32 --max-iters 10 --levels 256]
+    python -m vq_amd.evalcli ivfsq4  [--seed 66 --dim 384 --nlist 256 --nprobe 1 8 32 --max-iters 10 --levels 16]
     python -m vq_amd.evalcli ivfbin  [--seed 66 --dim 384 --nlist 256 --nprobe 1 8 32 --max-iters 10 --threshold 0.5 --candidates 40 100]
 
 For every sample count of `NUM_SAMPLES` it prints the reference's three lines -- training time,
@@ -29,7 +30,7 @@ rows, as returned and with rerank=FlatIndex at each candidate count, beside Bina
 `ivfsq` is `ivfflat` for an IVFScalarIndex with ScalarQuantizer(0, 1, levels) over the same coarse centroids: per nprobe,
 recall@k against the exact search over the original rows (probing and quantization loss together), recall@k against the
 exact search over the dequantized rows (probing loss alone), and beside them IVFFlatIndex's recall over the original rows
-in the same lists.
+in the same lists.  `ivfsq4` reports the same figures for an IVFScalar4Index, `levels` at most 16 (default 16).
 
 Data: i.i.d. Uniform[0,1) like common.rs:43-53, from the library's counter-based generator
 (the reference's StdRng stream is not reproducible outside Rust).
@@ -207,16 +208,17 @@ def _report_ivfflat(args):
         ix.close()
 
 
-def _report_ivfsq(args):
+def _report_ivfsq(args, four_bit: bool = False):
     """recall@k of IVFScalarIndex.search against FlatIndex.search over the original and over the dequantized rows, per
-    nprobe, beside IVFFlatIndex's over the original rows in the same lists"""
+    nprobe, beside IVFFlatIndex's over the original rows in the same lists; four_bit: of IVFScalar4Index.search"""
     from . import _lib
     from .flat import FlatIndex
     from .ivf_flat import IVFFlatIndex
     from .ivf_scalar import IVFScalarIndex
+    from .ivf_scalar4 import IVFScalar4Index
     from .sq import ScalarQuantizer
 
-    title = "IVF-Scalar Index Evaluation"
+    title = "IVF-Scalar4 Index Evaluation" if four_bit else "IVF-Scalar Index Evaluation"
     print(title)
     print("=" * len(title))
     sq = ScalarQuantizer(0.0, 1.0, args.levels)
@@ -229,7 +231,7 @@ def _report_ivfsq(args):
         nlist = min(args.nlist, n)
         k = min(args.recall_k, n)
         t0 = time.perf_counter()
-        ix = IVFScalarIndex.train(X, nlist, sq, args.max_iters, seed=args.seed)
+        ix = (IVFScalar4Index if four_bit else IVFScalarIndex).train(X, nlist, sq, args.max_iters, seed=args.seed)
         train_ms = (time.perf_counter() - t0) * 1e3
         t0 = time.perf_counter()
         ix.add(X)
@@ -238,13 +240,13 @@ def _report_ivfsq(args):
         flat.add_rows(ix.list_ids, X)
         Q = X[::max(n // min(n, 1000), 1)]
         exact = FlatIndex(X).search(Q, k)[0]
-        exact_deq = FlatIndex(sq.dequantize_batch(ix.codes)).search(Q, k)[0]
+        exact_deq = FlatIndex(sq.dequantize_batch(ix.codes() if four_bit else ix.codes)).search(Q, k)[0]
         sizes = ix.list_sizes().astype(np.int64)
         if not args.json:
             print(f"\nSamples: {n}")
             print(f"  Training time: {train_ms:.0f} ms")
             print(f"  Add time: {add_ms:.0f} ms")
-            print(f"  Index bytes per row: {args.dim} (IVF-Flat f32: {4 * args.dim})")
+            print(f"  Index bytes per row: {4 * ((args.dim + 7) // 8) if four_bit else args.dim} (IVF-Flat f32: {4 * args.dim})")
         for nprobe in args.nprobe:
             p = min(nprobe, nlist)
             t0 = time.perf_counter()
@@ -351,7 +353,7 @@ def main(argv=None) -> int:
             p.add_argument("--max-iters", type=int, default=MAX_ITERS)
         else:
             p.add_argument("--max-depth", type=int, default=5)
-    for name in ("ivfflat", "ivfsq", "ivfbin"):
+    for name in ("ivfflat", "ivfsq", "ivfsq4", "ivfbin"):
         p = sub.add_parser(name)
         p.add_argument("--seed", type=int, default=SEED)
         p.add_argument("--dim", type=int, default=DIM)
@@ -363,6 +365,8 @@ def main(argv=None) -> int:
         p.add_argument("--json", action="store_true")
         if name == "ivfsq":
             p.add_argument("--levels", type=int, default=256)
+        if name == "ivfsq4":
+            p.add_argument("--levels", type=int, default=16)
         if name == "ivfbin":
             p.add_argument("--threshold", type=float, default=0.5)
             p.add_argument("--candidates", type=int, nargs="+", default=[40, 100])
@@ -370,8 +374,8 @@ def main(argv=None) -> int:
     if args.alg == "ivfflat":
         _report_ivfflat(args)
         return 0
-    if args.alg == "ivfsq":
-        _report_ivfsq(args)
+    if args.alg in ("ivfsq", "ivfsq4"):
+        _report_ivfsq(args, four_bit=args.alg == "ivfsq4")
         return 0
     if args.alg == "ivfbin":
         _report_ivfbin(args)
