@@ -11,15 +11,24 @@ range searches and reranks and the Hamming-radius range searches (NEW_OPS), ever
 present at that op -- its kind one of MASK_KINDS, handed over in one of FORMS -- and some directly after close() or
 save / load.
 
+`draw_mutated(family, seed)` is the same case again under adds, removes and the family's query ops between them, from a
+third generator (neither other stream moves), for the ten families whose index has `remove_rows` (MUTABLE).  A resident
+family is built over a prefix of its rows and adds the rest; a remove op has one of REMOVE_KINDS, handed over as a bool
+mask or as shuffled ids with repeats, some directly before close() or save / load.  Every op carries `present`, the
+original ids of the rows in the index behind it; a query op is held to the family's statement over
+`gathered(case, case.n, present)`, so row ids are positions in `present`.
+
 `statement_search`, `statement_range`, `statement_rerank` and `dense_statement`, and for the new ops
 `statement_filtered_search`, `statement_filtered_range`, `statement_hamming_range` and their dense forms, dispatch a case to
 the numpy statements of tests/ref_*.py.  They make no arithmetic of their own.
 """
+import dataclasses
 import zlib
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 
+import ref_abin as A
 import ref_binary as B
 import ref_binary_filter as BF
 import ref_binary_range as BR
@@ -31,9 +40,12 @@ import ref_ivf_residual as IRES
 import ref_ivfbin as IB
 import ref_ivfflat as IFL
 import ref_ivfsq as ISQ
+import ref_ivfsq4 as IS4
 import ref_knn as K
 import ref_pq_filter as RPF
+import ref_mutate as M
 import ref_range as RG
+import ref_sq4 as S4
 import ref_sqbq as S
 import ref_sqindex as SI
 from test_gpu_fuzz import KINDS, _draw_data
@@ -44,10 +56,12 @@ ALL5 = (0, 1, 2, 3, 4)
 SUMS = (0, 1, 2)  # the metrics with an ADC / Hamming form: no cosine
 
 # seeds per family at VQ_FUZZ_SCALE=1 (tests/test_fuzz_search_draws.py holds the coverage these give)
-N_FAMILY = {"flat": 24, "scalar": 16, "binary": 16, "pq": 16, "ivfpq": 16, "ivfflat": 24, "ivfsq": 16, "ivfbin": 16}
+N_FAMILY = {"flat": 24, "scalar": 16, "binary": 16, "pq": 16, "ivfpq": 16, "ivfflat": 24, "ivfsq": 16, "ivfbin": 16,
+            "abin": 16, "sq4": 16, "ivfsq4": 16}
 FAMILIES = tuple(N_FAMILY)
-DENSE = ("flat", "scalar", "binary", "pq")  # every row is a candidate of every query
-IVF = ("ivfpq", "ivfflat", "ivfsq", "ivfbin")
+DENSE = ("flat", "scalar", "binary", "pq", "abin", "sq4")  # every row is a candidate of every query
+IVF = ("ivfpq", "ivfflat", "ivfsq", "ivfbin", "ivfsq4")
+PACKED = ("abin", "sq4", "ivfsq4")  # exact f32 queries over packed words: the statements share one distance matrix a case
 PAIRS = {
     "flat": [(k, m) for m in ALL5 for k in ("flat_f32", "flat_f16")],
     "scalar": [("scalar", m) for m in ALL5],
@@ -57,6 +71,9 @@ PAIRS = {
     "ivfflat": [(k, m) for m in ALL5 for k in ("ivfflat_f32", "ivfflat_f16")],
     "ivfsq": [("ivfsq", m) for m in ALL5],
     "ivfbin": [("ivfbin", m) for m in SUMS],
+    "abin": [("abin", m) for m in ALL5],
+    "sq4": [("sq4", m) for m in ALL5],
+    "ivfsq4": [("ivfsq4", m) for m in ALL5],
 }
 # the operations after the rows are in (an IVF family also draws "add")
 QUERY_OPS = {
@@ -68,10 +85,14 @@ QUERY_OPS = {
     "ivfflat": ("search", "range_search", "close_search", "save_load_search"),
     "ivfsq": ("search", "range_search", "close_search", "save_load_search"),
     "ivfbin": ("search", "close_search", "save_load_search", "rerank_search"),
+    "abin": ("search", "range_search", "save_load_search"),
+    "sq4": ("search", "range_search", "save_load_search"),
+    "ivfsq4": ("search", "range_search", "close_search", "save_load_search", "rerank_search"),
 }
 NQ = (1, 3, 17, 40, 130)
 FLAT_DIMS = (1, 2, 3, 4, 5, 8, 16, 31, 32, 33, 36, 64, 100, 127, 128, 129, 200)
 BINARY_DIMS = (1, 31, 32, 33, 64, 65, 96, 128, 192, 1056)
+SQ4_DIMS = (1, 7, 8, 9, 15, 16, 17, 24, 31, 32, 33, 39, 40, 41, 63, 64, 65, 100, 129, 200)  # 8 to a word, 32 to a chunk
 RESIDUAL_TABLE_BUDGET = 150_000  # nq * probed lists with rows * dim: the residual statement builds one table per pair
 
 
@@ -94,6 +115,8 @@ class Case:
     data: dict          # the arrays: rows as drawn, as stored, list ids, coarse centroids, codebooks, codes, words
     queries: np.ndarray
     ops: list           # dicts {"op": name, "n": rows in the index after it, ...}, run in order
+    gathered: bool = False  # a case over some of another's rows (`gathered`): the planted duplicates are not at its end
+    cache: dict = field(default_factory=dict, repr=False, compare=False)  # a PACKED case's distance matrix, computed once
 
     def describe(self, upto=None) -> str:
         """the whole case in one line: a red seed replays from it"""
@@ -106,8 +129,13 @@ class Case:
 
 
 def _op_text(o) -> str:
+    if o["op"] == "add" and "hi" in o:  # a mutated case's add: the original rows lo .. hi - 1 arrive as ids at .. n - 1
+        return f"{o['how']}[{o['lo']}:{o['hi']}]@{o['at']}"
     if o["op"] == "add":
         return f"{o['how']}[{o['lo']}:{o['n']}]"
+    if o["op"] == "remove":
+        flags = "".join(f" {k}" for k in ("then_close", "then_load") if o.get(k))
+        return f"remove(n={o['n_before']}->{o['n']} kind={o['kind']} form={o['form']} removed={o['removed']}{flags})"
     extra = "".join(f" {k}={o[k]}" for k in ("candidates", "flat_metric") if k in o)
     if "mask" in o:  # a filtered op: the mask's kind, the form it is handed over in and the number of allowed rows
         extra += f" mask={o['mask_kind']} form={o['form']} allowed={o['allowed']}"
@@ -185,6 +213,8 @@ def _draw_ops(rng, case):
     fam, n = case.family, case.n
     qops = QUERY_OPS[fam]
     ops = []
+    if fam in PACKED:  # (their first two query ops go round-robin from the seed: every op often enough by construction)
+        return _draw_ops_in_turn(rng, case)
 
     if fam in IVF:
         pieces = min(n, int(rng.choice([1, 2, 3])))
@@ -202,15 +232,47 @@ def _draw_ops(rng, case):
     return ops
 
 
+def _draw_ops_in_turn(rng, case):
+    """_draw_ops with the first two query ops taken in turn from the seed"""
+    fam, n, seed = case.family, case.n, case.seed
+    qops = QUERY_OPS[fam]
+    ops, nth = [], 0
+
+    def query(n_now):
+        nonlocal nth
+        ops.append(_query_op(rng, case, qops if nth >= 2 else (qops[(2 * seed + nth) % len(qops)],), n_now))
+        nth += 1
+
+    if fam in IVF:
+        pieces = min(n, int(rng.choice([1, 2, 3])))
+        cuts = [0] + sorted(int(c) for c in rng.choice(np.arange(1, n), pieces - 1, replace=False)) + [n]
+        for i in range(pieces):
+            ops.append({"op": "add", "lo": cuts[i], "n": cuts[i + 1], "how": str(rng.choice(case.ctor["adds"]))})
+            if i + 1 < pieces and rng.random() < 0.7:
+                query(cuts[i + 1])
+        room = 7 - len(ops)
+        for _ in range(max(3 - len(ops), int(rng.integers(1, room + 1)))):
+            query(n)
+    else:
+        for _ in range(int(rng.integers(3, 8))):
+            query(n)
+    return ops
+
+
 def _draw_radius(rng, case, n_now):
     """per-query radii from the case's own k-th distances (ref_range.kth_distance), so that the hits are neither none nor
     all; query 0 (equal to a duplicated row) gets its 2nd distance: an exact tie on the boundary; the last query -1; with
     17 queries or more, the one before it +inf"""
-    X = decoded(case)[:n_now]
     nq = case.nq
-    k = int(rng.integers(1, min(n_now, 40) + 1))
-    r = RG.kth_distance(case.metric, case.queries, X, k)
-    r[0] = RG.kth_distance(case.metric, case.queries[:1], X, min(2, n_now))[0]
+    if case.family in PACKED:  # (the same k-th distances, off the case's one distance matrix)
+        k = int(rng.integers(1, min(n_now, 40) + 1))
+        r = A.topk(_matrix(case, n_now), k)[1][:, k - 1].copy()
+        r[0] = A.topk(_matrix(case, n_now)[:1], min(2, n_now))[1][0, -1]
+    else:
+        X = decoded(case)[:n_now]
+        k = int(rng.integers(1, min(n_now, 40) + 1))
+        r = RG.kth_distance(case.metric, case.queries, X, k)
+        r[0] = RG.kth_distance(case.metric, case.queries[:1], X, min(2, n_now))[0]
     r[np.isnan(r)] = F(1.0)  # (a NaN radius is refused)
     if nq >= 2:
         r[-1] = F(-1.0)
@@ -226,7 +288,22 @@ def decoded(case) -> np.ndarray:
         return d["stored"].astype(F)
     if case.family in ("scalar", "ivfsq"):
         return SI.decode(case.ctor["sq"], d["codes"])
+    if case.family in ("sq4", "ivfsq4"):
+        return S4.decode(d["words"], case.dim, *case.ctor["sq"])
+    if case.family == "abin":
+        return A.decode(d["words"], case.dim, *case.ctor["bq"][1:])
     raise ValueError(case.family)
+
+
+def _matrix(case, n: int) -> np.ndarray:
+    """D(q, i) float32 (nq, n) of a PACKED case over its first n rows, every row a candidate: ref_abin / ref_sq4's
+    distance_matrix, computed once a case (a row's distance does not depend on the other rows)"""
+    if "D" not in case.cache:
+        if case.family == "abin":
+            case.cache["D"] = A.distance_matrix(case.metric, case.queries, case.data["words"], case.dim, *case.ctor["bq"][1:])
+        else:
+            case.cache["D"] = S4.distance_matrix(case.metric, case.queries, case.data["words"], case.dim, *case.ctor["sq"])
+    return case.cache["D"][:, :n]
 
 
 # -- the draw ---------------------------------------------------------------------------------------------------------------
@@ -253,8 +330,10 @@ def draw(family: str, seed: int) -> Case:
             k = max(k, 2)
         dim = m * sd
         ctor.update(m=m, k=k, sub_dim=sd)
-    elif family in ("binary", "ivfbin"):
+    elif family in ("binary", "ivfbin", "abin"):
         dim = int(rng.choice(BINARY_DIMS)) if rng.random() < 0.5 else int(rng.integers(1, 1101))
+    elif family in ("sq4", "ivfsq4"):
+        dim = int(rng.choice(SQ4_DIMS)) if rng.random() < 0.5 else int(rng.integers(1, 201))
     else:
         dim = int(rng.choice(FLAT_DIMS)) if rng.random() < 0.5 else int(rng.integers(1, 201))
     if dense_cut:
@@ -268,6 +347,9 @@ def draw(family: str, seed: int) -> Case:
     if ivf:
         nlist = int(rng.choice([1, 2, 7, int(rng.integers(2, 40)), int(rng.integers(40, 301)),
                                 min(300, n + int(rng.integers(1, 50)))]))
+        if family == "ivfsq4" and seed % 8 == 3:  # more lists than rows by construction (elsewhere the seed count sees to it)
+            n = int(rng.integers(1, 40))
+            nlist = n + int(rng.integers(1, 50))
         nprobe = min(int(rng.choice([1, int(rng.integers(1, min(nlist, 8) + 1)), nlist])), nlist, 1024)
         if family == "ivfbin":
             coarse_metric = int(rng.integers(0, 5))
@@ -309,7 +391,9 @@ def draw(family: str, seed: int) -> Case:
         X = _draw_data(rng, n, dim, data_kind)
         if dense_cut:
             X[:] = X[0]
-            X[rng.integers(0, n, 3)] = np.nan
+            odd = rng.integers(0, n, 3)
+            if family not in PACKED:  # (sq_encode sends NaN to code 0 and a bit is a bit: those get stored words of their own)
+                X[odd] = np.nan
         else:
             _plant(rng, X, data.get("lists"))
         X = np.ascontiguousarray(X, F)
@@ -340,6 +424,33 @@ def draw(family: str, seed: int) -> Case:
             ctor.update(sq=sq, source=source)
             if ivf:
                 ctor.update(adds=("add_codes",) if source == "codes" else ("add_rows", "add_codes"))
+        elif family in ("sq4", "ivfsq4"):
+            sq = S4.QUANTIZERS[int(rng.integers(0, len(S4.QUANTIZERS)))]
+            source = str(rng.choice(["codes", "packed"] if dense_cut else ["rows", "codes", "packed"]))
+            codes = S.sq_encode(sq[0], sq[1], sq[2], X)
+            if source != "rows" and not dense_cut and n >= 16:
+                at = rng.integers(7, n - 7, 5)
+                codes[at] = rng.integers(0, 16, (5, dim)).astype(np.uint8)  # every nibble is legal (codes >= levels too)
+            if dense_cut:  # the three odd rows: all nibbles 15 (all 0 where the tied rows are all 15 themselves)
+                codes[odd] = 0 if bool((codes[0] == 15).all()) else 15
+            data["codes"] = codes
+            data["words"] = S4.pack4(codes)
+            ctor.update(sq=sq, source=source)
+            if ivf:
+                ctor.update(adds=("add_codes", "add_packed") if source != "rows" else ("add_rows", "add_codes", "add_packed"))
+            row0 = S4.decode(data["words"][:1], dim, *sq)[0]
+        elif family == "abin":
+            low, high = A.LOW_HIGH[int(rng.integers(0, len(A.LOW_HIGH)))]
+            thr = float(rng.choice([0.0, -0.5, 0.25, float(X[int(rng.integers(0, n)), int(rng.integers(0, dim))])]))
+            thr = float(F(thr)) if np.isfinite(thr) else 0.0
+            bits = B.bits_f32(X, thr)
+            data["bq_codes"] = S.bq_encode(thr, low, high, X)
+            if dense_cut:  # the three odd rows: every bit of the tied rows inverted
+                bits[odd] = ~bits[0]
+                data["bq_codes"][odd] = S.bq_encode(0.5, low, high, bits[odd])  # (True is 1.0: the code of a set bit)
+            data["words"] = B.pack(bits)
+            ctor.update(bq=(thr, low, high), source=str(rng.choice(["codes", "packed"] if dense_cut else ["rows", "codes", "packed"])))
+            row0 = A.decode(data["words"][:1], dim, low, high)[0]
         else:  # binary, ivfbin
             low, high = IB.LOW_HIGH[int(rng.integers(0, len(IB.LOW_HIGH)))]
             thr = float(rng.choice([0.0, -0.5, 0.25, float(X[int(rng.integers(0, n)), int(rng.integers(0, dim))])]))
@@ -383,6 +494,10 @@ def statement_search(case: Case, n: int, topk: int):
     if fam == "ivfbin":
         return IB.search(metric, case.coarse_metric, d["coarse"], d["lists"][:n], c["bq"], d["words"][:n], case.dim, Q,
                          case.nprobe, topk)
+    if fam in ("abin", "sq4"):
+        return A.topk(_matrix(case, n), topk)
+    if fam == "ivfsq4":
+        return IS4.search(metric, d["coarse"], d["lists"][:n], c["sq"], d["codes"][:n], Q, case.nprobe, topk)
     raise ValueError(fam)
 
 
@@ -396,6 +511,8 @@ def dense_statement(case: Case, n: int, topk: int):
     if case.family == "ivfbin":
         thr, low, high = c["bq"]
         return B.search(B.pack(B.bits_f32(Q, thr)), d["words"][:n], case.dim, low, high, metric, topk)
+    if case.family == "ivfsq4":  # ref_sq4 over the packed words
+        return A.topk(_matrix(case, n), topk)
     raise ValueError(case.family)
 
 
@@ -410,6 +527,10 @@ def statement_range(case: Case, n: int, radius):
         return IRG.search(metric, d["coarse"], d["lists"][:n], d["stored"][:n], Q, case.nprobe, radius)
     if case.family == "ivfsq":
         return IRG.sq_search(metric, d["coarse"], d["lists"][:n], c["sq"], d["codes"][:n], Q, case.nprobe, radius)
+    if case.family in ("abin", "sq4"):
+        return A.ranged(_matrix(case, n), radius)
+    if case.family == "ivfsq4":
+        return IS4.range_search(metric, d["coarse"], d["lists"][:n], c["sq"], d["codes"][:n], Q, case.nprobe, radius)
     raise ValueError(case.family)
 
 
@@ -419,12 +540,14 @@ def dense_statement_range(case: Case, n: int, radius):
         return RG.search(metric, Q, d["stored"][:n].astype(F), radius)
     if case.family == "ivfsq":
         return RG.sq_search(metric, Q, c["sq"], d["codes"][:n], radius)
+    if case.family == "ivfsq4":
+        return A.ranged(_matrix(case, n), radius)
     raise ValueError(case.family)
 
 
 def rerank_rows(case: Case, n: int) -> np.ndarray:
     """the f32 rows of the exact index a rerank_search goes through"""
-    return (case.data["rows"] if case.family in ("binary", "ivfbin", "ivfsq") else case.data["rerank_rows"])[:n]
+    return (case.data["rows"] if case.family in ("binary", "ivfbin", "ivfsq", "ivfsq4") else case.data["rerank_rows"])[:n]
 
 
 def statement_rerank(case: Case, n: int, hits, topk: int, flat_metric: int):
@@ -461,6 +584,9 @@ NEW_OPS = {
     "ivfflat": ("filtered_search", "filtered_range_search"),
     "ivfsq": ("filtered_search", "filtered_range_search", "filtered_rerank_search"),
     "ivfbin": ("hamming_range_search", "filtered_search", "filtered_hamming_range_search", "filtered_rerank_search"),
+    "abin": ("filtered_search", "filtered_range_search"),
+    "sq4": ("filtered_search", "filtered_range_search"),
+    "ivfsq4": ("filtered_search", "filtered_range_search", "filtered_rerank_search"),
 }
 FILTERED = ("filtered_search", "filtered_range_search", "filtered_hamming_range_search", "filtered_rerank_search")
 MASK_KINDS = ("ones", "zeros", "one_row", "random", "block64", "block", "all_but_few", "fewer_than_topk", "without_winners",
@@ -478,7 +604,7 @@ def _applies(case, kind, n_now, topk) -> bool:
     if kind == "fewer_than_topk":
         return topk >= 2
     if kind == "higher_twins":  # the duplicates _plant / the code rows make sit at the end of the whole set
-        return n_now == case.n >= 2 and not case.dense_cut
+        return n_now == case.n >= 2 and not case.dense_cut and not case.gathered
     return True
 
 
@@ -653,6 +779,10 @@ def statement_filtered_search(case: Case, n: int, topk: int, mask):
     if fam == "ivfbin":
         return BF.ivf_search(metric, case.coarse_metric, d["coarse"], d["lists"][:n], c["bq"], d["words"][:n], case.dim, Q,
                              case.nprobe, topk, mask)
+    if fam in ("abin", "sq4"):
+        return A.topk(_matrix(case, n), topk, mask)
+    if fam == "ivfsq4":
+        return IS4.search_masked(metric, d["coarse"], d["lists"][:n], c["sq"], d["codes"][:n], Q, case.nprobe, topk, mask)
     raise ValueError(fam)
 
 
@@ -669,6 +799,8 @@ def dense_statement_filtered(case: Case, n: int, topk: int, mask):
         return BF.search(_qwords(case), d["words"][:n], case.dim, low, high, metric, topk, mask)
     if case.family == "ivfpq":
         return None if c["residual"] else RPF.brute_dense_search(metric, d["codebooks"], d["codes"][:n], Q, topk, mask)
+    if case.family == "ivfsq4":
+        return A.topk(_matrix(case, n), topk, mask)
     raise ValueError(case.family)
 
 
@@ -683,6 +815,10 @@ def statement_filtered_range(case: Case, n: int, radius, mask):
         return RIF.range_search(metric, d["coarse"], d["lists"][:n], d["stored"][:n], Q, case.nprobe, radius, mask)
     if case.family == "ivfsq":
         return RIF.sq_range_search(metric, d["coarse"], d["lists"][:n], c["sq"], d["codes"][:n], Q, case.nprobe, radius, mask)
+    if case.family in ("abin", "sq4"):
+        return A.ranged(_matrix(case, n), radius, mask)
+    if case.family == "ivfsq4":
+        return IS4.range_search_masked(metric, d["coarse"], d["lists"][:n], c["sq"], d["codes"][:n], Q, case.nprobe, radius, mask)
     raise ValueError(case.family)
 
 
@@ -692,6 +828,8 @@ def dense_statement_filtered_range(case: Case, n: int, radius, mask):
         return RF.range_search(metric, Q, d["stored"][:n].astype(F), radius, mask)
     if case.family == "ivfsq":
         return RF.sq_range_search(metric, Q, c["sq"], d["codes"][:n], radius, mask)
+    if case.family == "ivfsq4":
+        return A.ranged(_matrix(case, n), radius, mask)
     raise ValueError(case.family)
 
 
@@ -719,3 +857,241 @@ def allowed_in_reach(case: Case, n: int, mask) -> np.ndarray:
     lists = case.data["lists"][:n]
     P = I.probe(case.coarse_metric, case.data["coarse"], case.queries, case.nprobe)
     return np.array([RIF.allowed_members(lists, P[j], mask).size for j in range(case.nq)], np.int64)
+
+
+# -- the third draw: rows added and removed -----------------------------------------------------------------------------------
+MUTATE_WORD = 0x4D555441  # the third seed word of draw_mutated's generator: neither draw() nor draw_filtered() sees it
+MUTABLE = tuple(f for f in FAMILIES if f != "pq")  # (PQIndex searches the caller's own codes: it has no remove_rows)
+N_MUTATED = {f: 24 for f in MUTABLE}  # seeds per family at VQ_FUZZ_SCALE=1: every remove kind twice a family takes these
+REMOVE_KINDS = ("one_row", "block", "block64", "word_straddle", "random", "all_but_one", "winners", "lower_twins", "nothing")
+IVF_REMOVE_KINDS = ("one_list", "everything")  # a resident index refuses a removal of every row
+REMOVES_P = (0.1, 0.3, 0.6)  # 1, 2 or 3 remove ops a case
+REMOVE_ORDER = {"nothing": 0, "one_row": 0, "lower_twins": 0, "word_straddle": 0, "winners": 1, "block64": 1, "one_list": 1,
+                "random": 2, "block": 2, "all_but_one": 3, "everything": 3}  # within a case: how few rows a kind leaves
+REMOVE_FORMS = ("bool", "ids")
+PER_ROW = ("rows", "stored", "codes", "words", "bq_codes", "rerank_rows", "lists")
+SEARCH_LIKE = ("search", "close_search", "save_load_search", "rerank_search")
+
+
+def mutated_seeds(family, scale=1):
+    return range(N_MUTATED[family] * scale)
+
+
+def remove_kinds(family):
+    return REMOVE_KINDS + (IVF_REMOVE_KINDS if family in IVF else ())
+
+
+def gathered(case: Case, n: int, rows) -> Case:
+    """the case over `rows` of its first n rows alone: every per-row array gathered (a PACKED case's distance matrix too:
+    a row's distances are its own), the rest as it is; row ids of the new case are positions in `rows`"""
+    rows = np.asarray(rows, np.int64)
+    data = {k: (v[:n][rows] if k in PER_ROW else v) for k, v in case.data.items()}
+    cache = {"D": _matrix(case, n)[:, rows]} if case.family in PACKED else {}
+    return dataclasses.replace(case, n=int(rows.size), data=data, gathered=True, cache=cache)
+
+
+def every_row(case: Case) -> Case:
+    """the case with every list probed: a range search at radius +inf (a Hamming radius past `dim`; for IVFPQIndex a
+    search at topk = n) then returns every row whose distance is not NaN, so every id shows"""
+    return dataclasses.replace(case, nprobe=case.nlist)
+
+
+def resident_adds(case: Case):
+    """the add methods of a resident case that store what the constructor stored (planted codes and the dense cut's odd
+    words exist as codes and words only)"""
+    fam, source = case.family, case.ctor.get("source")
+    if fam == "flat":
+        return ("add",)
+    if fam == "scalar":
+        return ("add", "add_codes") if source == "rows" else ("add_codes",)
+    if fam == "binary":
+        return ("add", "add_codes", "add_packed")
+    if fam in ("abin", "sq4"):
+        return ("add", "add_codes", "add_packed") if source == "rows" else ("add_codes", "add_packed")
+    raise ValueError(fam)
+
+
+def _twin_pairs(case: Case, present):
+    """positions in `present` of the lower row of every planted duplicate pair (_plant, the code rows) still whole"""
+    n = case.n
+    pairs = [(i, n - 7 + i) for i in range(7)] if n >= 14 else [(0, n - 1)] if n >= 2 else []
+    where = {int(r): p for p, r in enumerate(present.tolist())}
+    return np.array([where[a] for a, b in pairs if a in where and b in where], np.int64)
+
+
+def _remove_applies(case, G, kind, present, adds_left) -> bool:
+    n_now, ivf = int(present.size), case.family in IVF
+    if kind == "nothing":
+        return True
+    if n_now < 2 and not (ivf and adds_left):
+        return False  # (its one row stays: a query op follows)
+    if kind == "block64":
+        return n_now > 64
+    if kind == "word_straddle":
+        return n_now >= 34
+    if kind == "winners":
+        return ivf or n_now > 4
+    if kind == "lower_twins":
+        return not case.dense_cut and _twin_pairs(case, present).size > 0
+    if kind == "everything":
+        return adds_left > 0
+    return True
+
+
+def _draw_removal(rng, case, G, kind, present, adds_left) -> np.ndarray:
+    """bool (n_now,): the rows one remove op takes out -- all of them only from an IVF index with an add to come"""
+    n_now, ivf = int(present.size), case.family in IVF
+    m = np.zeros(n_now, np.bool_)
+    if kind == "one_row":
+        m[int(rng.choice([0, n_now - 1, int(rng.integers(0, n_now))]))] = True
+    elif kind == "block":
+        lo = int(rng.integers(0, n_now))
+        m[lo:int(rng.integers(lo + 1, n_now + 1))] = True
+    elif kind == "block64":  # a run of whole 64-row groups (the last one as far as the rows go), never all of them
+        groups = (n_now + 63) // 64
+        a = int(rng.integers(0, groups))
+        b = int(rng.integers(a + 1, groups + 1))
+        if a == 0 and b == groups:
+            a = 1
+        m[64 * a:min(64 * b, n_now)] = True
+    elif kind == "word_straddle":  # the last two rows of one 32-row mask word and the first two of the next
+        g = int(rng.integers(0, (n_now - 34) // 32 + 1))
+        m[32 * g + 30:32 * g + 34] = True
+    elif kind == "random":
+        m = rng.random(n_now) < float(rng.choice([0.5, 0.03]))
+    elif kind == "all_but_one":
+        m[:] = True
+        m[int(rng.choice([0, n_now - 1, int(rng.integers(0, n_now))]))] = False
+    elif kind == "winners":  # a removal that is ignored returns exactly these rows again
+        winners = statement_search(G, n_now, min(G.topk, n_now, 4))[0]
+        m[winners[winners != I.PAD_ID].astype(np.int64)] = True
+    elif kind == "lower_twins":  # the distance bits of the next search stay, the ids change
+        m[_twin_pairs(case, present)] = True
+    elif kind == "one_list":  # every row of one list with rows, mostly one that some query probes
+        lists = G.data["lists"]
+        live = np.unique(lists)
+        P = I.probe(case.coarse_metric, case.data["coarse"], case.queries, case.nprobe)
+        probed = live[np.isin(live, P)]
+        if probed.size and rng.random() < 0.75:
+            live = probed
+        m = lists == live[int(rng.integers(0, live.size))]
+    elif kind == "everything":
+        m[:] = True
+    elif kind != "nothing":
+        raise ValueError(kind)
+    if m.all() and not (ivf and adds_left):  # (block, random, the one row, the one list ...: a query op follows)
+        m[int(rng.integers(0, n_now))] = False
+    return m
+
+
+def _draw_mutated_ops(rng, case):
+    """4 to 9 ops: the adds (an IVF family's 1 to 3 slices; a resident family is built over a prefix and adds the rest in 0
+    to 2 slices), 1 to 3 removes and 3 or more of the family's QUERY_OPS + NEW_OPS between and behind them, the last op a
+    query.  Every op carries `present`: the original ids of the rows in the index behind it, in order."""
+    fam, n, seed = case.family, case.n, case.seed
+    ivf = fam in IVF
+    if ivf:
+        pieces = min(n, int(rng.choice([1, 2, 3])))
+        if seed % 8 == 2:
+            pieces = min(n, max(pieces, 2))  # (a removal of every row needs an add behind it)
+        hows = case.ctor["adds"]
+    else:
+        pieces = min(n - 1, int(rng.integers(0, 3))) + 1  # (the first piece is the constructor's)
+        hows = resident_adds(case)
+    cuts = [0] + sorted(int(c) for c in rng.choice(np.arange(1, n), pieces - 1, replace=False)) + [n]
+    adds = [{"op": "add", "lo": cuts[i], "hi": cuts[i + 1], "how": str(rng.choice(hows))} for i in range(pieces)]
+    present = np.empty(0, np.int64)
+    ops = []
+
+    def add():
+        nonlocal present
+        o = adds.pop(0)
+        o["at"] = int(present.size)  # the ids an add returns start at the current length
+        present = np.concatenate([present, np.arange(o["lo"], o["hi"], dtype=np.int64)])
+        o.update(n=int(present.size), present=present.copy())
+        ops.append(o)
+
+    if ivf:
+        add()
+    else:
+        present = np.arange(adds.pop(0)["hi"], dtype=np.int64)
+    removes = int(rng.choice([1, 2, 3], p=REMOVES_P))
+    queries = int(rng.integers(3, max(3, 9 - len(ops) - len(adds) - removes) + 1))
+    names = QUERY_OPS[fam] + NEW_OPS[fam]
+    # the kinds of the case's removes: the next ones of the round that goes through the seeds, those that leave few rows
+    # last.  The two kinds that need the case's help come by construction, one seed in eight each.
+    turn = remove_kinds(fam)
+    forced = "everything" if ivf and seed % 8 == 2 else "lower_twins" if seed % 8 == 5 else None
+    window = [turn[(4 * seed + i) % len(turn)] for i in range(removes)]
+    if forced:
+        window[0] = forced
+    window.sort(key=lambda k: -1 if k == forced else REMOVE_ORDER[k])
+    nth_remove = nth_query = nth_filtered = 0
+    while adds or removes or queries:
+        n_now = int(present.size)
+        tokens = (["add"] if adds else []) + (["remove"] if removes and n_now else []) + (["query"] if queries > 1 and n_now else [])
+        tok = str(rng.choice(tokens)) if tokens else "query"  # (the last query closes the case)
+        if forced == "everything" and nth_remove == 0 and removes and n_now:
+            tok = "remove"   # (while an add is still to come)
+        if forced == "lower_twins" and nth_remove == 0 and adds:
+            tok = "add"      # (both rows of a pair are in only behind the last add)
+        if tok == "add":
+            add()
+            continue
+        G = gathered(case, n, present)
+        if tok == "remove":
+            kind = window[nth_remove]
+            at = turn.index(kind)
+            if not _remove_applies(case, G, kind, present, len(adds)):  # (the next kind in turn that does)
+                ok = [k for k in turn[at:] + turn[:at] if k != "nothing" and _remove_applies(case, G, k, present, len(adds))]
+                kind = ok[0] if ok else "nothing"
+            gone = _draw_removal(rng, case, G, kind, present, len(adds))
+            o = {"op": "remove", "kind": kind, "form": str(rng.choice(REMOVE_FORMS)), "n_before": n_now,
+                 "removed": int(gone.sum())}
+            if o["form"] == "bool":
+                o["arg"] = gone
+            else:  # the ids shuffled, some of them twice
+                ids = np.flatnonzero(gone)
+                twice = rng.choice(ids, int(rng.integers(0, min(ids.size, 5) + 1))) if ids.size else ids
+                o["arg"] = rng.permutation(np.concatenate([ids, twice])).astype(np.int64)
+            present = present[M.kept(n_now, o["arg"]).astype(np.int64)]
+            o.update(n=int(present.size), present=present.copy())
+            close = ivf and (rng.random() < 0.15 or (nth_remove == 0 and seed % 4 == 1))
+            load = fam in HAS_SAVE and (rng.random() < 0.15 or (nth_remove == 0 and seed % 4 == 3))
+            if present.size and close:
+                o["then_close"] = True  # close() directly behind the remove: the next call rebuilds the handle
+            elif present.size and load:
+                o["then_load"] = True   # save / load directly behind: the run goes on with the loaded index
+            ops.append(o)
+            removes -= 1
+            nth_remove += 1
+            continue
+        name = names[(3 * seed + nth_query) % len(names)] if nth_query < 3 else str(rng.choice(names))
+        if name in NEW_OPS[fam]:
+            o = _new_op(rng, G, name, n_now, nth_filtered)
+            nth_filtered += name in FILTERED
+        else:
+            o = _query_op(rng, G, (name,), n_now)
+        o["present"] = present.copy()
+        ops.append(o)
+        queries -= 1
+        nth_query += 1
+    reranks = [o for o in ops if "flat_metric" in o]
+    for o in reranks:  # one flat metric a case: the reranker is one FlatIndex that follows the adds and removes
+        o["flat_metric"] = reranks[0]["flat_metric"]
+    return ops
+
+
+def draw_mutated(family: str, seed: int) -> Case:
+    """draw(family, seed) with its ops replaced: the same index, rows and queries under adds, removes and the family's query
+    ops, every query op held to its statement over `gathered(case, case.n, op["present"])`"""
+    case = draw(family, seed)
+    rng = np.random.default_rng([zlib.crc32(family.encode()), int(seed), MUTATE_WORD])
+    case.ops = _draw_mutated_ops(rng, case)
+    return case
+
+
+def built_over(case: Case) -> int:
+    """the rows a mutated resident case is built over: the prefix its first add starts behind (all rows without an add)"""
+    first = next((o for o in case.ops if o["op"] == "add"), None)
+    return case.n if first is None else first["lo"]

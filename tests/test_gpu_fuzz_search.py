@@ -1,5 +1,6 @@
-"""Randomised sweep of the eight search indexes on the MI355X against their numpy statements: FlatIndex, ScalarIndex,
-BinaryIndex, PQIndex.search, IVFPQIndex (plain and residual), IVFFlatIndex, IVFScalarIndex and IVFBinaryIndex.  A case
+"""Randomised sweep of the eleven search indexes on the MI355X against their numpy statements: FlatIndex, ScalarIndex,
+BinaryIndex, PQIndex.search, IVFPQIndex (plain and residual), IVFFlatIndex, IVFScalarIndex, IVFBinaryIndex,
+AsymmetricBinaryIndex, Scalar4Index and IVFScalar4Index.  A case
 (tests/fuzz_search_draws.py) is an index kind, a metric, data, queries and a drawn sequence of adds, searches, range
 searches, close(), save / load and rerank=; after every search the result must be the statement's over the rows added so
 far: indices equal, distances equal as uint32 bits, padding exactly 0xFFFFFFFF / +inf, range results equal in order and
@@ -12,13 +13,27 @@ over as bools, as words, as packed ids or as words with the bits past the rows s
 save / load.  Beyond the statement, each filtered call is held to: no masked-out row returned, padding exactly behind the
 allowed rows in reach, the unfiltered search of the same handle unchanged directly after, the unfiltered call under an
 all-ones mask, the resident twin under the same mask at nprobe == nlist, and a range result against the filtered top-k of
-its own hit count."""
+its own hit count.
+
+The three packed families are also held, one seed in four, to the identity their indexes claim: the 8-bit index over the
+unpacked codes under the same quantizer (a FlatIndex over the decoded bits for AsymmetricBinaryIndex) returns the same
+indices and distance bits.
+
+test_fuzz_<family>_mutated runs the cases under `draw_mutated`'s ops, for the ten families that remove rows (every one but
+pq): adds, remove_rows -- by bool mask or by shuffled ids with repeats -- and the family's query ops between them, some
+removes directly before close() or save / load.  `remove_rows` must return ref_mutate.kept and len() must follow; every
+query op is held to the family's statement over the rows present (`gathered`), row ids being positions among them; the
+first query behind a remove is also held to a fresh index built over those rows, both searched at topk = min(n, 1024)
+so that a wrong id of any row in reach shows, and with every list probed at a radius that takes every row, and
+a FlatIndex reranker follows every add and remove with the same
+argument."""
 import os
 
 import numpy as np
 import pytest
 
 import fuzz_search_draws as D
+import ref_mutate as M
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -64,25 +79,36 @@ def _distance(metric):
     return vq_amd.Distance(D.NAMES[metric])
 
 
-def _build(case):
-    """the case's index: a resident kind over its rows, an IVF kind without rows yet"""
+def _build(case, rows=None):
+    """the case's index: a resident kind over its rows (its first `rows` ones), an IVF kind without rows yet"""
     import vq_amd
     from vq_amd.store import PQIndex
 
-    c, d, dist = case.ctor, case.data, _distance(case.metric)
+    c, dist = case.ctor, _distance(case.metric)
+    d = case.data if rows is None else {k: (v[:rows] if k in D.PER_ROW else v) for k, v in case.data.items()}
     fam = case.family
     if fam == "flat":
         return vq_amd.FlatIndex(d["stored"], dist)
     if fam == "scalar":
         q = vq_amd.ScalarQuantizer(*c["sq"])
         return vq_amd.ScalarIndex(d["rows"], q, dist) if c["source"] == "rows" else vq_amd.ScalarIndex.from_codes(d["codes"], q, dist)
-    if fam == "binary":
+    if fam in ("binary", "abin"):
+        cls = vq_amd.BinaryIndex if fam == "binary" else vq_amd.AsymmetricBinaryIndex
         q = vq_amd.BinaryQuantizer(*c["bq"])
         if c["source"] == "rows":
-            return vq_amd.BinaryIndex(d["rows"], q, dist)
+            return cls(d["rows"], q, dist)
         if c["source"] == "codes":
-            return vq_amd.BinaryIndex.from_codes(d["bq_codes"], q, dist)
-        return vq_amd.BinaryIndex.from_packed(d["words"], case.dim, q, dist)
+            return cls.from_codes(d["bq_codes"], q, dist)
+        return cls.from_packed(d["words"], case.dim, q, dist)
+    if fam == "sq4":
+        q = vq_amd.ScalarQuantizer(*c["sq"])
+        if c["source"] == "rows":
+            return vq_amd.Scalar4Index(d["rows"], q, dist)
+        if c["source"] == "codes":
+            return vq_amd.Scalar4Index.from_codes(d["codes"], q, dist)
+        return vq_amd.Scalar4Index.from_packed(d["words"], case.dim, q, dist)
+    if fam == "ivfsq4":
+        return vq_amd.IVFScalar4Index(d["coarse"], vq_amd.ScalarQuantizer(*c["sq"]), dist)
     if fam == "pq":
         return PQIndex(d["codebooks"], d["codes"], dist)
     if fam == "ivfpq":
@@ -110,17 +136,45 @@ def _twin(case, n):
         return vq_amd.BinaryIndex.from_packed(d["words"][:n], case.dim, vq_amd.BinaryQuantizer(*c["bq"]), dist)
     if case.family == "ivfpq" and not c["residual"]:
         return PQIndex(d["codebooks"], d["codes"][:n], dist)
+    if case.family == "ivfsq4":
+        return vq_amd.Scalar4Index.from_packed(d["words"][:n], case.dim, vq_amd.ScalarQuantizer(*c["sq"]), dist)
     return None
 
 
+def _eight_bit(case, n):
+    """the index a packed family claims to equal bit for bit: the 8-bit one over the unpacked codes under the same
+    quantizer; for AsymmetricBinaryIndex a FlatIndex over the decoded rows"""
+    import vq_amd
+
+    c, d, dist = case.ctor, case.data, _distance(case.metric)
+    if case.family == "abin":
+        return vq_amd.FlatIndex(D.decoded(case)[:n], dist)
+    q = vq_amd.ScalarQuantizer(*c["sq"])
+    if case.family == "sq4":
+        return vq_amd.ScalarIndex.from_codes(d["codes"][:n], q, dist)
+    ix = vq_amd.IVFScalarIndex(d["coarse"], q, dist)
+    ix.add_codes(d["lists"][:n], d["codes"][:n])
+    return ix
+
+
+PAYLOAD = {("ivfpq", "add_codes"): "codes", ("ivfflat", "add_rows"): "stored", ("ivfsq", "add_codes"): "codes",
+           ("ivfsq", "add_rows"): "rows", ("ivfbin", "add_packed"): "words", ("ivfbin", "add_codes"): "bq_codes",
+           ("ivfbin", "add_rows"): "rows", ("ivfsq4", "add_rows"): "rows", ("ivfsq4", "add_codes"): "codes",
+           ("ivfsq4", "add_packed"): "words",
+           # the resident families (a mutated case):
+           ("flat", "add"): "stored", ("scalar", "add"): "rows", ("scalar", "add_codes"): "codes", ("binary", "add"): "rows",
+           ("binary", "add_codes"): "bq_codes", ("binary", "add_packed"): "words", ("abin", "add"): "rows",
+           ("abin", "add_codes"): "bq_codes", ("abin", "add_packed"): "words", ("sq4", "add"): "rows",
+           ("sq4", "add_codes"): "codes", ("sq4", "add_packed"): "words"}
+
+
 def _add(case, ix, op):
+    """an add op: draw's rows lo .. n - 1 keep their ids; a mutated case's rows lo .. hi - 1 arrive as ids at .. n - 1"""
     d = case.data
-    a = slice(op["lo"], op["n"])
-    payload = {("ivfpq", "add_codes"): "codes", ("ivfflat", "add_rows"): "stored", ("ivfsq", "add_codes"): "codes",
-               ("ivfsq", "add_rows"): "rows", ("ivfbin", "add_packed"): "words", ("ivfbin", "add_codes"): "bq_codes",
-               ("ivfbin", "add_rows"): "rows"}[(case.family, op["how"])]
-    ids = getattr(ix, op["how"])(d["lists"][a], d[payload][a])
-    assert np.array_equal(ids, np.arange(op["lo"], op["n"], dtype=np.uint32)), "row ids of the add"
+    a = slice(op["lo"], op.get("hi", op["n"]))
+    payload = d[PAYLOAD[case.family, op["how"]]][a]
+    ids = getattr(ix, op["how"])(d["lists"][a], payload) if case.family in D.IVF else getattr(ix, op["how"])(payload)
+    assert np.array_equal(ids, np.arange(op.get("at", op["lo"]), op["n"], dtype=np.uint32)), "row ids of the add"
 
 
 def _load(case, path):
@@ -128,7 +182,8 @@ def _load(case, path):
     from vq_amd.store import PQIndex
 
     cls = {"scalar": vq_amd.ScalarIndex, "binary": vq_amd.BinaryIndex, "pq": PQIndex, "ivfpq": vq_amd.IVFPQIndex,
-           "ivfflat": vq_amd.IVFFlatIndex, "ivfsq": vq_amd.IVFScalarIndex, "ivfbin": vq_amd.IVFBinaryIndex}[case.family]
+           "ivfflat": vq_amd.IVFFlatIndex, "ivfsq": vq_amd.IVFScalarIndex, "ivfbin": vq_amd.IVFBinaryIndex,
+           "abin": vq_amd.AsymmetricBinaryIndex, "sq4": vq_amd.Scalar4Index, "ivfsq4": vq_amd.IVFScalar4Index}[case.family]
     return cls.load(path)
 
 
@@ -137,7 +192,7 @@ def _close(ix):
         ix.close()
 
 
-RESIDENT = {"ivfflat": "flat", "ivfsq": "scalar", "ivfbin": "binary", "ivfpq": "pq"}  # the family of an IVF case's _twin
+RESIDENT = {"ivfflat": "flat", "ivfsq": "scalar", "ivfbin": "binary", "ivfpq": "pq", "ivfsq4": "sq4"}  # an IVF case's _twin
 
 
 def _allowed_arg(op):
@@ -183,10 +238,17 @@ def _only_allowed(idx, mask):
     assert out.size == 0, f"{out.size} masked-out rows returned, the first: row {out[0]}"
 
 
-def _new_op(case, ix, op, kw, want, path):
-    """one op of fuzz_search_draws.NEW_OPS on the handle `ix`"""
+def _exact(case, op, exact_of=None):
+    """the FlatIndex a rerank op goes through: a fresh one over the case's rerank rows, or the one `exact_of` keeps"""
     import vq_amd
 
+    if exact_of is not None:
+        return exact_of(op)
+    return vq_amd.FlatIndex(D.rerank_rows(case, op["n"]), _distance(op["flat_metric"]))
+
+
+def _new_op(case, ix, op, kw, want, path, exact_of=None):
+    """one op of fuzz_search_draws.NEW_OPS on the handle `ix`"""
     family, Q, name, n = case.family, case.queries, op["op"], op["n"]
     ivf = family in D.IVF
     topk = op.get("topk", min(case.topk, n))
@@ -226,8 +288,7 @@ def _new_op(case, ix, op, kw, want, path):
             if twin is not None:
                 _same(_filtered_search(RESIDENT[family], twin, Q, topk, allowed, {}), got)
         elif name == "filtered_rerank_search":
-            exact = vq_amd.FlatIndex(D.rerank_rows(case, n), _distance(op["flat_metric"]))
-            rerank = {"rerank": exact, "candidates": op["candidates"]}
+            rerank = {"rerank": _exact(case, op, exact_of), "candidates": op["candidates"]}
             got = _filtered_search(family, index, Q, topk, allowed, kw, **rerank)
             short = D.statement_filtered_search(case, n, op["candidates"], mask)  # the short list: the filtered statement ...
             first = _filtered_search(family, index, Q, op["candidates"], allowed, kw)
@@ -263,18 +324,23 @@ def _new_op(case, ix, op, kw, want, path):
             _close(index)
 
 
-def _run(family, seed, tmp_path, filtered=False):
-    case = (D.draw_filtered if filtered else D.draw)(family, seed)
-    ivf = family in D.IVF
-    Q = case.queries
-    kw = {"nprobe": case.nprobe} if ivf else {}
-    ix = _build(case)
+def _wanted(case):
+    """the search statement of `case`, each (n, topk) computed once"""
     wants = {}
 
     def want(n, topk):
         if (n, topk) not in wants:
             wants[n, topk] = D.statement_search(case, n, topk)
         return wants[n, topk]
+
+    return want
+
+
+def _query(case, ix, op, step, kw, want, tmp_path, filtered, exact_of=None):
+    """one query op on the handle `ix`, held to `case`'s statements"""
+    family, Q = case.family, case.queries
+    ivf = family in D.IVF
+    name, n = op["op"], op["n"]
 
     def checked_search(index, op):
         got = index.search(Q, op["topk"], **kw)
@@ -283,47 +349,174 @@ def _run(family, seed, tmp_path, filtered=False):
             _padding(case, got, D.probed_rows(case, op["n"]))
         return got
 
+    if name == "search":
+        got = checked_search(ix, op)
+        twin = _twin(case, n) if ivf and case.nprobe == case.nlist else None
+        if twin is not None:  # all lists probed: the resident index over the same rows
+            _same(twin.search(Q, op["topk"]), got)
+        if family in D.PACKED and case.seed % 4 == 0:  # the 8-bit index over the same codes: the same bits
+            other = _eight_bit(case, n)
+            _same(other.search(Q, op["topk"], **kw), got)
+            _close(other)
+    elif name == "range_search":
+        got = ix.range_search(Q, op["radius"], **kw)
+        _assert_same(got, D.statement_range(case, n, op["radius"]))
+        if ivf and case.nprobe == case.nlist:
+            _assert_same(_twin(case, n).range_search(Q, op["radius"]), got)
+    elif name == "close_search":
+        before = checked_search(ix, op)
+        ix.close()
+        _same(checked_search(ix, op), before)
+    elif name == "save_load_search":
+        before = checked_search(ix, op)
+        path = tmp_path / f"{family}_{step}.bin"
+        ix.save(path)
+        back = _load(case, path)
+        assert len(back) == n
+        _same(checked_search(back, op), before)
+        _close(back)
+    elif name == "rerank_search":
+        got = ix.search(Q, op["topk"], rerank=_exact(case, op, exact_of), candidates=op["candidates"], **kw)
+        short = want(n, op["candidates"])  # the short list is the statement's at topk = candidates ...
+        _same(ix.search(Q, op["candidates"], **kw), short)
+        _same(got, D.statement_rerank(case, n, short[0], op["topk"], op["flat_metric"]))  # ... reranked exactly
+    elif filtered and name in D.NEW_OPS[family]:
+        _new_op(case, ix, op, kw, want, tmp_path / f"{family}_{step}.bin", exact_of)
+    else:
+        raise ValueError(name)
+
+
+def _run(family, seed, tmp_path, filtered=False):
+    case = (D.draw_filtered if filtered else D.draw)(family, seed)
+    kw = {"nprobe": case.nprobe} if family in D.IVF else {}
+    ix = _build(case)
+    want = _wanted(case)
+    step = -1
+    try:
+        for step, op in enumerate(case.ops):
+            if op["op"] == "add":
+                _add(case, ix, op)
+                assert len(ix) == op["n"]
+            else:
+                _query(case, ix, op, step, kw, want, tmp_path, filtered)
+    except AssertionError as e:
+        raise AssertionError(f"{case.describe(step)} :: {e}") from e
+    finally:
+        _close(ix)
+
+
+class _Reranker:
+    """the FlatIndex a mutated case reranks through: it follows every add and every remove with the same argument (an
+    index emptied by a removal of every row starts again at the next add)"""
+
+    def __init__(self, case):
+        ops = [o for o in case.ops if "flat_metric" in o]
+        self.metric = ops[0]["flat_metric"] if ops else None  # (one flat metric a case: draw_mutated's)
+        self.rows = np.ascontiguousarray(D.rerank_rows(case, case.n), F) if ops else None
+        self.ix = None
+
+    def add(self, lo, hi):
+        import vq_amd
+
+        if self.metric is None:
+            return
+        if self.ix is None:
+            self.ix = vq_amd.FlatIndex(self.rows[lo:hi], _distance(self.metric))
+        else:
+            self.ix.add(self.rows[lo:hi])
+
+    def remove(self, op):
+        if self.ix is None:
+            return
+        if op["n"] == 0:
+            self.ix = None
+        else:
+            kept = self.ix.remove_rows(op["arg"].copy())
+            assert np.array_equal(kept, M.kept(op["n_before"], op["arg"])), "kept of the reranker's removal"
+
+    def __call__(self, op):
+        assert self.metric == op["flat_metric"] and len(self.ix) == op["n"]
+        return self.ix
+
+
+def _fresh(G):
+    """a new index over the rows of the gathered case `G`: the family's own constructor, an IVF kind with one add"""
+    ix = _build(G)
+    if G.family in D.IVF:
+        how = G.ctor["adds"][0]
+        getattr(ix, how)(G.data["lists"], G.data[PAYLOAD[G.family, how]])
+    return ix
+
+
+def _every_id(G, ix, n):
+    """the queries over every list at a radius that takes every row: the renumbered id of each row shows (IVFPQIndex has
+    no range search: its top min(n, 1024))"""
+    E = D.every_row(G)
+    kw = {"nprobe": E.nprobe} if G.family in D.IVF else {}
+    if "range_search" in D.QUERY_OPS[G.family]:
+        radius = np.full(G.nq, np.inf, F)
+        _assert_same(ix.range_search(E.queries, radius, **kw), D.statement_range(E, n, radius))
+    elif G.family in ("binary", "ivfbin"):
+        hradius = np.full(G.nq, G.dim + 7, np.int64)
+        _assert_same(ix.hamming_range_search(E.queries, hradius, **kw), D.statement_hamming_range(E, n, hradius))
+    else:
+        _same(ix.search(E.queries, min(n, 1024), **kw), D.statement_search(E, n, min(n, 1024)))
+
+
+def _run_mutated(family, seed, tmp_path):
+    case = D.draw_mutated(family, seed)
+    Q = case.queries
+    ivf = family in D.IVF
+    kw = {"nprobe": case.nprobe} if ivf else {}
+    ix = _build(case, None if ivf else D.built_over(case))
+    exact = _Reranker(case)
+    if not ivf:
+        exact.add(0, D.built_over(case))
+    G = want = None       # the case over the rows present, and its search statement
+    removed = False       # a remove since the last query op
     step = -1
     try:
         for step, op in enumerate(case.ops):
             name, n = op["op"], op["n"]
             if name == "add":
                 _add(case, ix, op)
+                exact.add(op["lo"], op["hi"])
                 assert len(ix) == n
-            elif name == "search":
-                got = checked_search(ix, op)
-                twin = _twin(case, n) if ivf and case.nprobe == case.nlist else None
-                if twin is not None:  # all lists probed: the resident index over the same rows
-                    _same(twin.search(Q, op["topk"]), got)
-            elif name == "range_search":
-                got = ix.range_search(Q, op["radius"], **kw)
-                _assert_same(got, D.statement_range(case, n, op["radius"]))
-                if ivf and case.nprobe == case.nlist:
-                    _assert_same(_twin(case, n).range_search(Q, op["radius"]), got)
-            elif name == "close_search":
-                before = checked_search(ix, op)
-                ix.close()
-                _same(checked_search(ix, op), before)
-            elif name == "save_load_search":
-                before = checked_search(ix, op)
-                path = tmp_path / f"{family}_{step}.bin"
-                ix.save(path)
-                back = _load(case, path)
-                assert len(back) == n
-                _same(checked_search(back, op), before)
-                _close(back)
-            elif name == "rerank_search":
-                import vq_amd
-
-                exact = vq_amd.FlatIndex(D.rerank_rows(case, n), _distance(op["flat_metric"]))
-                got = ix.search(Q, op["topk"], rerank=exact, candidates=op["candidates"], **kw)
-                short = want(n, op["candidates"])  # the short list is the statement's at topk = candidates ...
-                _same(ix.search(Q, op["candidates"], **kw), short)
-                _same(got, D.statement_rerank(case, n, short[0], op["topk"], op["flat_metric"]))  # ... reranked exactly
-            elif filtered and name in D.NEW_OPS[family]:
-                _new_op(case, ix, op, kw, want, tmp_path / f"{family}_{step}.bin")
-            else:
-                raise ValueError(name)
+                G = None
+                continue
+            if name == "remove":
+                kept = ix.remove_rows(op["arg"].copy())
+                assert kept.dtype == np.uint32 and np.array_equal(kept, M.kept(op["n_before"], op["arg"])), "kept of the removal"
+                assert len(ix) == n, f"len {len(ix)} behind the removal, not {n}"
+                exact.remove(op)
+                if op.get("then_close"):
+                    ix.close()
+                elif op.get("then_load"):
+                    path = tmp_path / f"{family}_{step}.bin"
+                    ix.save(path)
+                    back = _load(case, path)
+                    _close(ix)
+                    ix = back
+                    assert len(ix) == n
+                G, removed = None, True
+                continue
+            if G is None:
+                G = D.gathered(case, case.n, op["present"])
+                want = _wanted(G)
+            assert len(ix) == n == G.n
+            if removed:  # a fresh index over the same rows answers the same, at a topk that shows every id it can
+                topk = min(n, 1024)
+                got = ix.search(Q, topk, **kw)
+                _same(got, want(n, topk))
+                fresh = _fresh(G)
+                _same(fresh.search(Q, topk, **kw), got)
+                _close(fresh)
+                twin = _twin(G, n) if ivf and case.nprobe == case.nlist else None
+                if twin is not None:
+                    _same(twin.search(Q, topk), got)
+                _every_id(G, ix, n)
+                removed = False
+            _query(G, ix, op, step, kw, want, tmp_path, True, exact)
     except AssertionError as e:
         raise AssertionError(f"{case.describe(step)} :: {e}") from e
     finally:
@@ -408,3 +601,83 @@ def test_fuzz_ivfbin(seed, tmp_path):
 @pytest.mark.parametrize("seed", D.seeds("ivfbin", SCALE))
 def test_fuzz_ivfbin_filtered(seed, tmp_path):
     _run("ivfbin", seed, tmp_path, filtered=True)
+
+
+@pytest.mark.parametrize("seed", D.seeds("abin", SCALE))
+def test_fuzz_abin(seed, tmp_path):
+    _run("abin", seed, tmp_path)
+
+
+@pytest.mark.parametrize("seed", D.seeds("abin", SCALE))
+def test_fuzz_abin_filtered(seed, tmp_path):
+    _run("abin", seed, tmp_path, filtered=True)
+
+
+@pytest.mark.parametrize("seed", D.seeds("sq4", SCALE))
+def test_fuzz_sq4(seed, tmp_path):
+    _run("sq4", seed, tmp_path)
+
+
+@pytest.mark.parametrize("seed", D.seeds("sq4", SCALE))
+def test_fuzz_sq4_filtered(seed, tmp_path):
+    _run("sq4", seed, tmp_path, filtered=True)
+
+
+@pytest.mark.parametrize("seed", D.seeds("ivfsq4", SCALE))
+def test_fuzz_ivfsq4(seed, tmp_path):
+    _run("ivfsq4", seed, tmp_path)
+
+
+@pytest.mark.parametrize("seed", D.seeds("ivfsq4", SCALE))
+def test_fuzz_ivfsq4_filtered(seed, tmp_path):
+    _run("ivfsq4", seed, tmp_path, filtered=True)
+
+
+@pytest.mark.parametrize("seed", D.mutated_seeds("flat", SCALE))
+def test_fuzz_flat_mutated(seed, tmp_path):
+    _run_mutated("flat", seed, tmp_path)
+
+
+@pytest.mark.parametrize("seed", D.mutated_seeds("scalar", SCALE))
+def test_fuzz_scalar_mutated(seed, tmp_path):
+    _run_mutated("scalar", seed, tmp_path)
+
+
+@pytest.mark.parametrize("seed", D.mutated_seeds("binary", SCALE))
+def test_fuzz_binary_mutated(seed, tmp_path):
+    _run_mutated("binary", seed, tmp_path)
+
+
+@pytest.mark.parametrize("seed", D.mutated_seeds("ivfpq", SCALE))
+def test_fuzz_ivfpq_mutated(seed, tmp_path):
+    _run_mutated("ivfpq", seed, tmp_path)
+
+
+@pytest.mark.parametrize("seed", D.mutated_seeds("ivfflat", SCALE))
+def test_fuzz_ivfflat_mutated(seed, tmp_path):
+    _run_mutated("ivfflat", seed, tmp_path)
+
+
+@pytest.mark.parametrize("seed", D.mutated_seeds("ivfsq", SCALE))
+def test_fuzz_ivfsq_mutated(seed, tmp_path):
+    _run_mutated("ivfsq", seed, tmp_path)
+
+
+@pytest.mark.parametrize("seed", D.mutated_seeds("ivfbin", SCALE))
+def test_fuzz_ivfbin_mutated(seed, tmp_path):
+    _run_mutated("ivfbin", seed, tmp_path)
+
+
+@pytest.mark.parametrize("seed", D.mutated_seeds("abin", SCALE))
+def test_fuzz_abin_mutated(seed, tmp_path):
+    _run_mutated("abin", seed, tmp_path)
+
+
+@pytest.mark.parametrize("seed", D.mutated_seeds("sq4", SCALE))
+def test_fuzz_sq4_mutated(seed, tmp_path):
+    _run_mutated("sq4", seed, tmp_path)
+
+
+@pytest.mark.parametrize("seed", D.mutated_seeds("ivfsq4", SCALE))
+def test_fuzz_ivfsq4_mutated(seed, tmp_path):
+    _run_mutated("ivfsq4", seed, tmp_path)
