@@ -154,6 +154,10 @@ int vqhip_profile_collect(uint32_t *n_calls, double *primary_ms, double *recheck
  * pointers) that went through the library's transfer lanes (several host threads, each with its own stream: uploads,
  * kernels and downloads of different chunks overlap) rather than the one-stream path -- diagnostics and tests */
 int vqhip_xfer_lane_calls(uint64_t *calls);
+/* process-wide count of the HIP events the library's event pool holds (stage times with profiling on, the ordering
+ * event a call's last kernel carries): bounded by the events in use at one time, not by the number of calls --
+ * diagnostics and tests */
+int vqhip_event_pool_count(uint64_t *events);
 /* device-to-device copy on the current stream (plumbing for callers that all-reduce the
  * k-means slab in their own buffers) */
 int vqhip_memcpy_device(void *dst, const void *src, uint64_t bytes);

@@ -47,6 +47,7 @@ SIGNATURES = {
     "vqhip_last_assign_stats": (C.c_int, [_u64p, C.POINTER(C.c_int)]),
     "vqhip_last_screen_products": (C.c_int, [C.POINTER(C.c_int)]),
     "vqhip_xfer_lane_calls": (C.c_int, [C.POINTER(C.c_uint64)]),
+    "vqhip_event_pool_count": (C.c_int, [C.POINTER(C.c_uint64)]),
     "vqhip_set_profiling": (C.c_int, [C.c_int]),
     "vqhip_profile_collect": (C.c_int, [_u32p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vqhip_memcpy_device": (C.c_int, [_vp, _vp, C.c_uint64]),
@@ -1576,6 +1577,13 @@ def xfer_lane_calls() -> int:
     """host-batch calls of this process that went through the library's transfer lanes"""
     v = C.c_uint64(0)
     check(load().vqhip_xfer_lane_calls(C.byref(v)))
+    return int(v.value)
+
+
+def event_pool_count() -> int:
+    """HIP events the library's event pool holds (process-wide)"""
+    v = C.c_uint64(0)
+    check(load().vqhip_event_pool_count(C.byref(v)))
     return int(v.value)
 
 

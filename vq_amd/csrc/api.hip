@@ -242,12 +242,78 @@ struct AssignWorkspace {
     }
 };
 
-// Optional per-call HIP-event timing of the two assignment stages, recorded on the stream
-// the kernels are launched on (bench.py derives the roofline figure from it).
+// The event pool of api_common.hpp.  Never destroyed: events go back to it from destructors that may run at exit.
+struct EventPool {
+    std::mutex mu;
+    std::vector<hipEvent_t> free_list[64];
+    uint64_t alive = 0;
+};
+static EventPool &event_pool() {
+    static EventPool *pool = new EventPool;
+    return *pool;
+}
+int pooled_event(EventRef *out) {
+    EventPool &pool = event_pool();
+    int dev = 0;
+    VQ_HIP(hipGetDevice(&dev));
+    hipEvent_t e = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(pool.mu);
+        auto &fl = pool.free_list[dev & 63];
+        if (!fl.empty()) {
+            e = fl.back();
+            fl.pop_back();
+        }
+    }
+    if (!e) {
+        VQ_HIP(hipEventCreate(&e));
+        std::lock_guard<std::mutex> lk(pool.mu);
+        ++pool.alive;
+    }
+    PooledEvent *pe = new (std::nothrow) PooledEvent{e, dev};
+    if (pe) {
+        *out = EventRef(pe, [](PooledEvent *p) {
+            EventPool &pl = event_pool();
+            {
+                std::lock_guard<std::mutex> lk(pl.mu);
+                pl.free_list[p->device & 63].push_back(p->e);
+            }
+            delete p;
+        });
+        return VQHIP_OK;
+    }
+    {
+        std::lock_guard<std::mutex> lk(pool.mu);
+        pool.free_list[dev & 63].push_back(e);
+    }
+    return fail(VQHIP_ERR_FAILURE, "host allocation failed");
+}
+uint64_t pooled_event_count() {
+    EventPool &pool = event_pool();
+    std::lock_guard<std::mutex> lk(pool.mu);
+    return pool.alive;
+}
+
+// The event a call's last kernel carries for its handle: the handle's last one again when nobody else holds it (a
+// profiled pass that has not been collected yet would), else one from the pool.
+static int tail_event(HandleSync &h, EventRef *out) {
+    int dev = 0;
+    VQ_HIP(hipGetDevice(&dev));
+    if (h.kev && h.kev.use_count() == 1 && h.kev->device == dev) *out = h.kev;
+    else VQ_TRY(pooled_event(out));
+    return VQHIP_OK;
+}
+
+// Optional per-call timing of the two assignment stages (bench.py derives the roofline figure from it), read from
+// the kernels' own dispatches: the pass's first kernel carries `start`, the last kernel of each stage its stop event
+// (LaunchStage).  The screen stage runs from the start of its first kernel to the end of its last, the re-check stage
+// from there to the end of its own last kernel.
+struct ProfileCall {
+    EventRef start, primary_stop, recheck_stop;  // recheck_stop stays empty without a re-check stage (exact engine)
+};
 struct ProfileState {
     bool on = false;
-    std::vector<hipEvent_t> ev;  // triples: start, after screen (or exact), after re-check
-    std::vector<int> engines;
+    std::vector<ProfileCall> calls;
 };
 static thread_local ProfileState g_prof;
 
@@ -293,7 +359,7 @@ struct FusedAcc {
 // assignment of every row of X [n][d] for the listed subspaces -> codes [n][m]
 static int run_assign(CodebookState &cs, AssignWorkspace &ws, const float *X, uint64_t n, uint32_t d,
                       int metric, const std::vector<uint32_t> &subs, uint8_t *codes, int engine_req,
-                      hipStream_t stream, FusedAcc *fused = nullptr) {
+                      hipStream_t stream, FusedAcc *fused = nullptr, HandleSync *cover = nullptr) {
     if (n == 0 || subs.empty()) return VQHIP_OK;
     if (n >= (1ull << 32)) return fail(VQHIP_ERR_UNSUPPORTED, "more than 2^32-1 rows per device");
     if ((reinterpret_cast<uintptr_t>(X) & 15) != 0)
@@ -355,45 +421,52 @@ static int run_assign(CodebookState &cs, AssignWorkspace &ws, const float *X, ui
         a.gate_halt = fused->gate_halt;
     }
     CodebookView v = cs.view();
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+    // `cover`: the caller queues nothing behind this pass, so the pass's last kernel can carry the handle's ordering
+    // event and the call leaves without recording one (HandleSync)
+    LaunchStage primary, recheck;
+    LaunchStage &last = screened ? recheck : primary;
+    ProfileCall pc;
     if (g_prof.on) {
-        VQ_HIP(hipEventCreate(&e0));
-        VQ_HIP(hipEventCreate(&e1));
-        VQ_HIP(hipEventCreate(&e2));
-        g_prof.ev.push_back(e0);
-        g_prof.ev.push_back(e1);
-        g_prof.ev.push_back(e2);
-        g_prof.engines.push_back(engine);
+        VQ_TRY(pooled_event(&pc.start));
+        VQ_TRY(pooled_event(&pc.primary_stop));
+        if (screened) VQ_TRY(pooled_event(&pc.recheck_stop));
+        primary.start = pc.start->e;
+        primary.stop = pc.primary_stop->e;
+        if (screened) recheck.stop = pc.recheck_stop->e;
+    }
+    EventRef tail_ev = screened ? pc.recheck_stop : pc.primary_stop;
+    if (cover && !tail_ev) {
+        VQ_TRY(tail_event(*cover, &tail_ev));
+        last.stop = tail_ev->e;
     }
     if (screened) {
         // the single-pass bf16 screen fills wave-private list SEGMENTS (wl_seg); only the other screens append to the
         // per-subspace counters, which must start at zero
         const bool segmented = engine == VQHIP_ENGINE_MFMA_BF16 && cs.x32_groups == 1 && x32_padded_sd(cs.sd) <= 64;
         if (!segmented) VQ_HIP(hipMemsetAsync(ws.wl_count.p, 0, (size_t)cs.m * 4, stream));
-        if (e0) VQ_HIP(hipEventRecord(e0, stream));
+        a.stage = &primary;
         if (engine == VQHIP_ENGINE_MFMA_BF16) VQ_TRY(launch_assign_screen_bf16(v, a, stream));
         else VQ_TRY(launch_assign_screen(v, a, stream));
-        if (e1) VQ_HIP(hipEventRecord(e1, stream));
+        a.stage = &recheck;
         VQ_TRY(launch_assign_exact(v, a, true, stream));
         if (a.acc_sums) {  // the re-checked rows, now that their codes are final
             VQ_TRY(launch_accumulate_listed(cs.m, cs.k, cs.sd, X, d, codes, a.sub_list, a.n_sub, a.wl_rows, a.wl_stride, a.wl_seg,
-                                            a.n_seg, a.acc_chunks, fused->n_patch, a.acc_sums, a.acc_counts, stream));
+                                            a.n_seg, a.acc_chunks, fused->n_patch, a.acc_sums, a.acc_counts, stream, &recheck));
             fused->used = true;
             fused->chunks = a.acc_chunks + fused->n_patch;
         }
-        if (e2) VQ_HIP(hipEventRecord(e2, stream));
         // the re-check counts stay on the device: vqhip_last_assign_stats fetches them when somebody asks (a copy queued
         // behind every pass was one of five stream operations of a 10k-row encode)
         ws.last_n_seg = a.n_seg;
         ws.last_segmented = segmented;
         ws.stats_pending = true;
     } else {
-        if (e0) VQ_HIP(hipEventRecord(e0, stream));
+        a.stage = &primary;
         VQ_TRY(launch_assign_exact(v, a, false, stream));
-        if (e1) VQ_HIP(hipEventRecord(e1, stream));
-        if (e2) VQ_HIP(hipEventRecord(e2, stream));
         ws.stats_pending = false;
     }
+    if (cover && last.launches > 0) cover->cover(tail_ev);
+    if (pc.start) g_prof.calls.push_back(pc);
     ws.last_engine = engine;
     ws.last_products = (engine == VQHIP_ENGINE_MFMA_BF16) ? (int)a.products : 0;
     ThreadState &st = tls();
@@ -1147,20 +1220,30 @@ int vqhip_profile_collect(uint32_t *n_calls, double *primary_ms, double *recheck
     VQ_TRY(current_stream(&s));
     VQ_HIP(hipStreamSynchronize(s));
     double a = 0.0, b = 0.0;
-    const size_t calls = g_prof.ev.size() / 3;
-    for (size_t i = 0; i < calls; ++i) {
+    const size_t calls = g_prof.calls.size();
+    int rc = VQHIP_OK;
+    for (const ProfileCall &c : g_prof.calls) {
         float t01 = 0.f, t12 = 0.f;
-        VQ_HIP(hipEventElapsedTime(&t01, g_prof.ev[3 * i], g_prof.ev[3 * i + 1]));
-        VQ_HIP(hipEventElapsedTime(&t12, g_prof.ev[3 * i + 1], g_prof.ev[3 * i + 2]));
+        hipError_t e = hipEventElapsedTime(&t01, c.start->e, c.primary_stop->e);
+        if (e == hipSuccess && c.recheck_stop) e = hipEventElapsedTime(&t12, c.primary_stop->e, c.recheck_stop->e);
+        if (e != hipSuccess) {
+            rc = fail(VQHIP_ERR_RUNTIME, "hipEventElapsedTime failed: %s", hipGetErrorString(e));
+            break;
+        }
         a += t01;
-        b += t12;
+        b += t12 > 0.f ? t12 : 0.f;
     }
-    for (hipEvent_t e : g_prof.ev) (void)hipEventDestroy(e);
-    g_prof.ev.clear();
-    g_prof.engines.clear();
+    g_prof.calls.clear();
+    VQ_TRY(rc);
     if (n_calls) *n_calls = (uint32_t)calls;
     if (primary_ms) *primary_ms = a;
     if (recheck_ms) *recheck_ms = b;
+    return VQHIP_OK;
+}
+
+int vqhip_event_pool_count(uint64_t *events) {
+    if (!events) return fail(VQHIP_ERR_NULL_PTR, "events is NULL");
+    *events = pooled_event_count();
     return VQHIP_OK;
 }
 
@@ -2179,8 +2262,10 @@ int vqhip_pq_encode_device(vqhip_pq_encoder *enc, const void *dev_rows, uint64_t
         codes = enc->codes.as<uint8_t>();
     }
     g_last_ws = enc->ws_id;
+    // without the f16 output the pass's last kernel is the call's last stream operation
+    HandleSync *cover = (!dev_f16_out && in.handle().may_cover()) ? &in.handle() : nullptr;
     VQ_TRY(run_assign(enc->cs, enc->ws, reinterpret_cast<const float *>(dev_rows), n, enc->cs.m * enc->cs.sd,
-                      enc->metric, enc->all_subs, codes, enc->engine, s));
+                      enc->metric, enc->all_subs, codes, enc->engine, s, nullptr, cover));
     if (dev_f16_out) VQ_TRY(launch_gather_f16(enc->cs.view(), codes, n, reinterpret_cast<uint16_t *>(dev_f16_out), s));
     return VQHIP_OK;
     VQ_API_END
@@ -2801,10 +2886,20 @@ int vqhip_tsvq_encode_device(vqhip_tsvq *t, const void *dev_rows, uint64_t n, vo
         t->last_screened = true;
         VQ_TRY(t->scr_wl.ensure((size_t)n * 8));
         t->scr.wl = t->scr_wl.as<uint2>();
+        // when no gather follows, the descent's last kernel is the call's last stream operation: it carries the
+        // handle's ordering event (HandleSync) and the call leaves without recording one
+        HandleSync &h = in.handle();
+        LaunchStage tail;
+        EventRef tail_ev;
+        if ((!out || out_vec) && h.may_cover()) {
+            VQ_TRY(tail_event(h, &tail_ev));
+            tail.stop = tail_ev->e;
+        }
         // the reconstruction rides on the descent when it can be written in 16-byte pieces
         VQ_TRY(launch_tsvq_screen_encode(X, n, t->d, t->centroids.as<float>(), t->cnorm.as<float>(), t->left.as<int32_t>(),
                                          t->right.as<int32_t>(), t->metric, t->scr, leaf, s,
-                                         out_vec ? t->table16.as<uint16_t>() : nullptr, out_vec ? out : nullptr));
+                                         out_vec ? t->table16.as<uint16_t>() : nullptr, out_vec ? out : nullptr, &tail));
+        if (tail_ev && tail.launches > 0) h.cover(tail_ev);
         out_done = out_vec;
     } else {
         VQ_TRY(launch_tsvq_encode(X, n, t->d, t->centroids.as<float>(), t->cnorm.as<float>(), t->left.as<int32_t>(),

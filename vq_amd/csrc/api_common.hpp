@@ -2,6 +2,7 @@
 // per-handle lock and stream order, the exception fence of an entry point, and the two helpers of api.hip that the
 // index files call.  Internal to the library, like common.hpp.
 #pragma once
+#include <memory>
 #include <mutex>
 #include <new>
 
@@ -19,11 +20,29 @@ namespace vqhip {
 //     call on ANOTHER stream first waits for that tail through an event.  The event is recorded when the other
 //     stream shows up if the tail is one of the library's own per-thread streams (never destroyed); for a caller's
 //     stream (vqhip_set_stream) it is recorded when the call leaves, because the caller may destroy that stream later.
+//     A call whose last stream operation is a kernel records nothing: that kernel carries a pooled event as the stop
+//     event of its own dispatch (LaunchStage, kernels.hpp) and hands it over with `cover`.  Such an event completes
+//     with the kernel and outlives the stream like a recorded one, and it puts no marker behind the kernel.
+
+// Events for the dispatches of kernels (stage times, a call's last kernel).  One free list per device for the whole
+// process: an event goes back to it when its last holder lets go, on whichever thread that is, so no call creates or
+// destroys an event once the lists are warm.
+struct PooledEvent {
+    hipEvent_t e = nullptr;
+    int device = 0;
+};
+using EventRef = std::shared_ptr<PooledEvent>;
+int pooled_event(EventRef *out);   // defined in api.hip
+uint64_t pooled_event_count();     // events the pool has created and not destroyed
+
 struct HandleSync {
     std::recursive_mutex mu;
     hipEvent_t ev = nullptr;
+    EventRef kev;                // stop event of the last kernel of the call that left the tail, when tail_kernel
     hipStream_t tail = nullptr;  // stream holding queued work of this handle (nullptr: the last call synchronised)
     bool tail_lazy = false;      // the event for `tail` has not been recorded yet (library-owned stream)
+    bool tail_kernel = false;    // the tail's event is `kev`
+    bool covered = false;        // this call's last stream operation is a kernel that carries `kev`
     int depth = 0;
     ~HandleSync() {
         if (ev) (void)hipEventDestroy(ev);
@@ -35,21 +54,35 @@ struct HandleSync {
     // order stream s behind whatever this handle still has queued elsewhere
     int order(hipStream_t s) {
         if (tail && tail != s) {
-            VQ_TRY(event());
-            if (tail_lazy) VQ_HIP(hipEventRecord(ev, tail));
-            VQ_HIP(hipStreamWaitEvent(s, ev, 0));
+            if (tail_kernel) {
+                VQ_HIP(hipStreamWaitEvent(s, kev->e, 0));
+            } else {
+                VQ_TRY(event());
+                if (tail_lazy) VQ_HIP(hipEventRecord(ev, tail));
+                VQ_HIP(hipStreamWaitEvent(s, ev, 0));
+            }
             tail = nullptr;
         }
         return VQHIP_OK;
     }
+    // True for the outermost call of a handle: only its last kernel can be the last operation of the call.
+    bool may_cover() const { return depth == 1; }
+    // `e` is the stop event of the kernel just launched, and the call queues nothing behind that kernel
+    void cover(const EventRef &e) {
+        kev = e;
+        covered = true;
+    }
     void leave(hipStream_t s, bool synced) {
+        const bool by_kernel = covered;
+        covered = false;
         if (synced || !s) {
             if (synced) tail = nullptr;
             return;
         }
         tail = s;
-        tail_lazy = true;
-        if (tls().user_stream_set && tls().user_stream == s) {
+        tail_kernel = by_kernel;
+        tail_lazy = !by_kernel;
+        if (!by_kernel && tls().user_stream_set && tls().user_stream == s) {
             if (event() == VQHIP_OK && hipEventRecord(ev, s) == hipSuccess) tail_lazy = false;
         }
     }
@@ -73,6 +106,7 @@ class Entry {
         return VQHIP_OK;
     }
     void synced() { synced_ = true; }
+    HandleSync &handle() { return *h_; }
     // give the handle back before the call ends (the rest of the call touches nothing the handle owns mutably)
     void release() {
         if (!h_) return;

@@ -853,7 +853,7 @@ int dispatch_exact(const CodebookView &cb, const AssignArgs &a, bool wl, dim3 gr
             const dim3 rgrid((nseg * parts + 3) / 4, a.n_sub);
 #define VQ_RESIDENT(SDV, KPLV)                                                                                      \
     if (cb.sd == SDV && kpl == KPLV) {                                                                              \
-        hipLaunchKernelGGL((k_recheck_resident<METRIC, SDV, KPLV>), rgrid, dim3(256), 0, stream, a.X, a.d, cb.m, cb.k, \
+        vq_launch(a.stage, (k_recheck_resident<METRIC, SDV, KPLV>), rgrid, dim3(256), 0, stream, a.X, a.d, cb.m, cb.k, \
                            cb.cb, cb.cnsqrt, a.sub_list, wlr, a.wl_stride, wls, wlc, nseg, parts, a.codes);        \
         VQ_LAUNCH_CHECK("k_recheck_resident");                                                                      \
         return VQHIP_OK;                                                                                            \
@@ -869,7 +869,7 @@ int dispatch_exact(const CodebookView &cb, const AssignArgs &a, bool wl, dim3 gr
             const dim3 tgrid((uint32_t)num_cus(), a.n_sub);
 #define VQ_RECHECK_TILED(SDV)                                                                                        \
     if (cb.sd == SDV) {                                                                                              \
-        hipLaunchKernelGGL((k_recheck_tiled<METRIC, SDV>), tgrid, dim3(1024), 0, stream, a.X, a.d, cb.m, cb.k, cb.cb, \
+        vq_launch(a.stage, (k_recheck_tiled<METRIC, SDV>), tgrid, dim3(1024), 0, stream, a.X, a.d, cb.m, cb.k, cb.cb, \
                            cb.cnsqrt, a.sub_list, wlr, wlc, a.wl_stride, a.codes);                                    \
         VQ_LAUNCH_CHECK("k_recheck_tiled");                                                                          \
         return VQHIP_OK;                                                                                             \
@@ -879,14 +879,14 @@ int dispatch_exact(const CodebookView &cb, const AssignArgs &a, bool wl, dim3 gr
             VQ_RECHECK_TILED(160) VQ_RECHECK_TILED(192)
 #undef VQ_RECHECK_TILED
             // any other multiple of 4 in the wide screen's range
-            hipLaunchKernelGGL((k_recheck_tiled_any<METRIC>), tgrid, dim3(1024), (size_t)16 * cb.sd * 4, stream, a.X, a.d, cb.m,
+            vq_launch(a.stage, (k_recheck_tiled_any<METRIC>), tgrid, dim3(1024), (size_t)16 * cb.sd * 4, stream, a.X, a.d, cb.m,
                                cb.k, cb.sd, cb.cb, cb.cnsqrt, a.sub_list, wlr, wlc, a.wl_stride, a.codes);
             VQ_LAUNCH_CHECK("k_recheck_tiled_any");
             return VQHIP_OK;
         }
 #define VQ_RECHECK_CASE(SDV)                                                                   \
     case SDV:                                                                                  \
-        hipLaunchKernelGGL((k_recheck_wave<METRIC, SDV>), wgrid, dim3(seg ? 1024 : 256), 0, stream, a.X, a.d, \
+        vq_launch(a.stage, (k_recheck_wave<METRIC, SDV>), wgrid, dim3(seg ? 1024 : 256), 0, stream, a.X, a.d, \
                            cb.m, cb.k, cb.cb, cb.cnsqrt, a.sub_list, wlr, wlc, a.wl_stride,     \
                            wls, a.n_seg, a.codes);                                                           \
         VQ_LAUNCH_CHECK("k_recheck_wave");                                                     \
@@ -961,7 +961,7 @@ int dispatch_exact(const CodebookView &cb, const AssignArgs &a, bool wl, dim3 gr
     }
 #define VQ_EXACT_CASE(SDV)                                                                    \
     case SDV:                                                                                  \
-        hipLaunchKernelGGL((k_assign_exact<METRIC, SDV, false>), grid, dim3(kExactBlock), 0,   \
+        vq_launch(a.stage, (k_assign_exact<METRIC, SDV, false>), grid, dim3(kExactBlock), 0,   \
                            stream, a.X, a.n, a.d, cb.m, cb.k, cb.sd, cb.cb, cb.cnsqrt,         \
                            a.sub_list, wlr, wlc, a.wl_stride, a.codes);                        \
         break;
@@ -1006,12 +1006,12 @@ int dispatch_exact(const CodebookView &cb, const AssignArgs &a, bool wl, dim3 gr
     default:
         if (!wl) {  // any other sub_dim: rows staged through LDS (k_assign_exact_tiled)
             const dim3 tgrid((uint32_t)((a.n + kTiledRows - 1) / kTiledRows), a.n_sub);
-            hipLaunchKernelGGL((k_assign_exact_tiled<METRIC>), tgrid, dim3(256), 0, stream, a.X, a.n, a.d, cb.m, cb.k,
+            vq_launch(a.stage, (k_assign_exact_tiled<METRIC>), tgrid, dim3(256), 0, stream, a.X, a.n, a.d, cb.m, cb.k,
                                cb.sd, cb.cb, cb.cnsqrt, a.sub_list, a.codes);
             VQ_LAUNCH_CHECK("k_assign_exact_tiled");
             return VQHIP_OK;
         }
-        hipLaunchKernelGGL((k_assign_exact<METRIC, 1, true>), grid, dim3(kExactBlock), 0, stream,
+        vq_launch(a.stage, (k_assign_exact<METRIC, 1, true>), grid, dim3(kExactBlock), 0, stream,
                            a.X, a.n, a.d, cb.m, cb.k, cb.sd, cb.cb, cb.cnsqrt, a.sub_list, wlr, wlc,
                            a.wl_stride, a.codes);
     }

@@ -228,7 +228,7 @@ int launch_one(const CodebookView &cb, const AssignArgs &a, hipStream_t stream) 
     uint32_t blocks = (uint32_t)((want_waves + kScreenWavesPerBlock - 1) / kScreenWavesPerBlock);
     // total waves must be >= n_sub for n_chunks >= 1
     while ((uint64_t)blocks * kScreenWavesPerBlock < a.n_sub) ++blocks;
-    hipLaunchKernelGGL((k_assign_screen<SD, NT>), dim3(blocks), dim3(kScreenBlock), 0, stream, a.X,
+    vq_launch(a.stage, (k_assign_screen<SD, NT>), dim3(blocks), dim3(kScreenBlock), 0, stream, a.X,
                        a.n, a.d, cb.m, cb.prepA, cb.prepCn, cb.meta, a.sub_list, a.n_sub, a.codes,
                        a.wl_rows, a.wl_count, a.wl_stride);
     VQ_LAUNCH_CHECK("k_assign_screen");

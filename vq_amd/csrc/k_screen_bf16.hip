@@ -1838,7 +1838,7 @@ int launch_one_x32(const CodebookView &cb, const AssignArgs &a, hipStream_t stre
     if constexpr (G == 1 && SD == 16 && NT32 == 8 && !ACC && PVW != 4) {
         if (use3) {
             piped = true;
-            hipLaunchKernelGGL((k_assign_screen_bf16_x32p<SD, NT32, false, 3, PVW>), dim3(blocks), dim3(kBlock), 0, stream, a.X, a.n, a.d,
+            vq_launch(a.stage, (k_assign_screen_bf16_x32p<SD, NT32, false, 3, PVW>), dim3(blocks), dim3(kBlock), 0, stream, a.X, a.n, a.d,
                                cb.m, cb.prepA32_3, cb.cn32, NT32 * 32, cb.meta, a.sub_list, a.n_sub, a.codes, a.wl_rows, a.wl_seg,
                                n_chunks, a.wl_stride, 0, cb.k, cb.cen, a.gate_active, a.gate_halt, a.codes_t, a.codes_t_pitch,
                                nullptr, nullptr, cb.sd);
@@ -1858,7 +1858,7 @@ int launch_one_x32(const CodebookView &cb, const AssignArgs &a, hipStream_t stre
                 }
             }
             const size_t dyn_lds_p = ACC ? (size_t)kWavesPerBlock * x32p_acc_bytes_per_wave(SD, NT32) : 0;
-            hipLaunchKernelGGL((k_assign_screen_bf16_x32p<SD, NT32, ACC>), dim3(blocks), dim3(kBlock), dyn_lds_p, stream, a.X, a.n, a.d,
+            vq_launch(a.stage, (k_assign_screen_bf16_x32p<SD, NT32, ACC>), dim3(blocks), dim3(kBlock), dyn_lds_p, stream, a.X, a.n, a.d,
                                cb.m, cb.prepA32, cb.cn32, NT32 * 32, cb.meta, a.sub_list, a.n_sub, a.codes, a.wl_rows, a.wl_seg,
                                n_chunks, a.wl_stride, a.metric == VQHIP_COSINE ? 1 : 0, cb.k, cb.cen, a.gate_active,
                                a.gate_halt, a.codes_t, a.codes_t_pitch, ACC ? a.acc_sums : nullptr, ACC ? a.acc_counts : nullptr,
@@ -1866,21 +1866,21 @@ int launch_one_x32(const CodebookView &cb, const AssignArgs &a, hipStream_t stre
         }
     }
     if (!piped)
-        hipLaunchKernelGGL((k_assign_screen_bf16_x32<SD, NT32, G, PVW, ACC>), dim3(blocks), dim3(kBlock), dyn_lds, stream, a.X, a.n, a.d,
+        vq_launch(a.stage, (k_assign_screen_bf16_x32<SD, NT32, G, PVW, ACC>), dim3(blocks), dim3(kBlock), dyn_lds, stream, a.X, a.n, a.d,
                            cb.m, cb.prepA32, cb.cn32, NT32 * groups * 32, cb.meta, a.sub_list, a.n_sub, a.codes, a.wl_rows,
                            a.wl_seg, n_chunks, a.wl_stride, a.metric == VQHIP_COSINE ? 1 : 0, cb.k, cb.cen,
                            reinterpret_cast<uint4 *>(a.part), groups, cb.sd, ACC ? a.acc_sums : nullptr, ACC ? a.acc_counts : nullptr,
                            a.gate_active, a.gate_halt, (G == 1) ? a.codes_t : nullptr, a.codes_t_pitch);
     VQ_LAUNCH_CHECK("k_assign_screen_bf16_x32");
     if (G == 1 && a.codes_t) {
-        hipLaunchKernelGGL(k_codes_transpose, dim3((uint32_t)((a.n + 255) / 256)), dim3(256), (size_t)256 * codes_transpose_pitch(cb.m) + cb.m, stream,
+        vq_launch(a.stage, k_codes_transpose, dim3((uint32_t)((a.n + 255) / 256)), dim3(256), (size_t)256 * codes_transpose_pitch(cb.m) + cb.m, stream,
                            a.codes_t, a.codes_t_pitch, a.codes, a.n, cb.m, a.sub_list, a.n_sub, a.gate_active, a.gate_halt);
         VQ_LAUNCH_CHECK("k_codes_transpose");
     }
     if (G != 1) {
         uint64_t mblocks = (a.n + 255) / 256;
         if (mblocks > (uint64_t)num_cus() * 8) mblocks = (uint64_t)num_cus() * 8;
-        hipLaunchKernelGGL((k_merge_partials_x32<G>), dim3((uint32_t)mblocks, a.n_sub), dim3(256), 0, stream,
+        vq_launch(a.stage, (k_merge_partials_x32<G>), dim3((uint32_t)mblocks, a.n_sub), dim3(256), 0, stream,
                            reinterpret_cast<const uint4 *>(a.part), a.n, cb.m, (uint32_t)SD, a.sub_list, cb.cen, cb.meta,
                            a.metric == VQHIP_COSINE ? 1 : 0, a.codes, a.wl_rows, a.wl_count, a.wl_stride, cb.k, groups);
         VQ_LAUNCH_CHECK("k_merge_partials_x32");
@@ -1903,13 +1903,13 @@ int launch_wide(const CodebookView &cb, const AssignArgs &a, hipStream_t stream,
     a.n_seg = 0;  // the merge kernel appends to the unsegmented list
     a.products = 6u;
     const size_t chunk_stride = (size_t)cb.m * groups * 24 * 4 * 64;
-    hipLaunchKernelGGL((k_assign_screen_bf16_wide<NCH>), dim3(blocks), dim3(kBlock), 0, stream, a.X, a.n, a.d, cb.prepA32,
+    vq_launch(a.stage, (k_assign_screen_bf16_wide<NCH>), dim3(blocks), dim3(kBlock), 0, stream, a.X, a.n, a.d, cb.prepA32,
                        chunk_stride, cb.cn32, groups * 32, a.sub_list, a.n_sub, a.metric == VQHIP_COSINE ? 1 : 0, cb.k, cb.cen,
                        reinterpret_cast<uint4 *>(a.part), groups, cb.sd);
     VQ_LAUNCH_CHECK("k_assign_screen_bf16_wide");
     uint64_t mblocks = (a.n + 255) / 256;
     if (mblocks > (uint64_t)num_cus() * 8) mblocks = (uint64_t)num_cus() * 8;
-    hipLaunchKernelGGL((k_merge_partials_x32<0>), dim3((uint32_t)mblocks, a.n_sub), dim3(256), 0, stream,
+    vq_launch(a.stage, (k_merge_partials_x32<0>), dim3((uint32_t)mblocks, a.n_sub), dim3(256), 0, stream,
                        reinterpret_cast<const uint4 *>(a.part), a.n, cb.m, (uint32_t)(64 * NCH), a.sub_list, cb.cen, cb.meta,
                        a.metric == VQHIP_COSINE ? 1 : 0, a.codes, a.wl_rows, a.wl_count, a.wl_stride, cb.k, groups);
     VQ_LAUNCH_CHECK("k_merge_partials_x32");

@@ -682,7 +682,7 @@ __global__ __launch_bounds__(256) void k_tsvq_continue_any(const float *__restri
 
 template <int D, int LPR, int MODE, bool FOLD>
 int launch_screen(const float *X, uint64_t n, uint32_t d_real, const TsvqScreen &s, hipStream_t stream, int32_t *leaf,
-                  const uint4 *table16, uint4 *f16_out, uint32_t *count, const TsvqCont &ct) {
+                  const uint4 *table16, uint4 *f16_out, uint32_t *count, const TsvqCont &ct, LaunchStage *stage) {
     constexpr int RPW = 64 / LPR;
     constexpr int WAVES = (D >= 512) ? 4 : (D >= 256) ? 8 : kWaves;  // 512 / 256 / 128 VGPRs per lane
     const size_t lds_bytes = tsvq_screen_lds_bytes(s.n_int, MODE == kScrL2 ? 1 : 2, D);
@@ -698,10 +698,10 @@ int launch_screen(const float *X, uint64_t n, uint32_t d_real, const TsvqScreen 
     uint64_t grid = (n_tiles + WAVES - 1) / WAVES;
     if (grid > (uint64_t)num_cus()) grid = (uint64_t)num_cus();
     if (s.n_slots > s.n_int)
-        hipLaunchKernelGGL((k_tsvq_screen_descend<D, LPR, WAVES, MODE, true, FOLD>), dim3((uint32_t)grid), dim3(WAVES * 64), lds_bytes, stream, X, n,
+        vq_launch(stage, (k_tsvq_screen_descend<D, LPR, WAVES, MODE, true, FOLD>), dim3((uint32_t)grid), dim3(WAVES * 64), lds_bytes, stream, X, n,
                            d_real, s.w, s.info, s.mu, s.n_int, s.start_slot, s.R, s.coef_a, s.coef_b, leaf, s.wl, count, table16, f16_out, ct);
     else
-        hipLaunchKernelGGL((k_tsvq_screen_descend<D, LPR, WAVES, MODE, false, FOLD>), dim3((uint32_t)grid), dim3(WAVES * 64), lds_bytes, stream, X, n,
+        vq_launch(stage, (k_tsvq_screen_descend<D, LPR, WAVES, MODE, false, FOLD>), dim3((uint32_t)grid), dim3(WAVES * 64), lds_bytes, stream, X, n,
                            d_real, s.w, s.info, s.mu, s.n_int, s.start_slot, s.R, s.coef_a, s.coef_b, leaf, s.wl, count, table16, f16_out, ct);
     VQ_LAUNCH_CHECK("k_tsvq_screen_descend");
     return VQHIP_OK;
@@ -733,7 +733,7 @@ bool tsvq_screen_supported(uint32_t n_int, uint32_t n_nodes, uint32_t d, int met
 
 int launch_tsvq_screen_encode(const float *X, uint64_t n, uint32_t d, const float *centroids, const float *cnorm,
                               const int32_t *left, const int32_t *right, int metric, const TsvqScreen &s, int32_t *leaf,
-                              hipStream_t stream, const uint16_t *table16_h, uint16_t *f16_out_h) {
+                              hipStream_t stream, const uint16_t *table16_h, uint16_t *f16_out_h, LaunchStage *stage) {
     if (n == 0) return VQHIP_OK;
     // optional fused reconstruction (f16 node table -> f16 rows): needs whole 16-byte pieces
     const uint4 *table16 = reinterpret_cast<const uint4 *>(table16_h);
@@ -755,11 +755,11 @@ int launch_tsvq_screen_encode(const float *X, uint64_t n, uint32_t d, const floa
     const TsvqCont ct{centroids, cnorm, left, right, s.slot_node, s.node_slot, euclid, clear_next};
 #define VQ_TSVQ_DM(DV, MV)                                                                         \
     if constexpr (DV >= 64) {                                                                      \
-        VQ_TRY((launch_screen<DV, 8, MV, true>(X, n, d, s, stream, leaf, table16, f16_out, count, ct)));   \
+        VQ_TRY((launch_screen<DV, 8, MV, true>(X, n, d, s, stream, leaf, table16, f16_out, count, ct, stage)));   \
     } else if (d == DV) {                                                                          \
-        VQ_TRY((launch_screen<DV, 8, MV, true>(X, n, d, s, stream, leaf, table16, f16_out, count, ct)));   \
+        VQ_TRY((launch_screen<DV, 8, MV, true>(X, n, d, s, stream, leaf, table16, f16_out, count, ct, stage)));   \
     } else {                                                                                       \
-        VQ_TRY((launch_screen<DV, 8, MV, false>(X, n, d, s, stream, leaf, table16, f16_out, count, ct)));  \
+        VQ_TRY((launch_screen<DV, 8, MV, false>(X, n, d, s, stream, leaf, table16, f16_out, count, ct, stage)));  \
     }
 #define VQ_TSVQ_D(DV)                                                                              \
     case DV:                                                                                       \
@@ -779,7 +779,7 @@ int launch_tsvq_screen_encode(const float *X, uint64_t n, uint32_t d, const floa
 #undef VQ_TSVQ_D
 #undef VQ_TSVQ_DM
     if (d != dp && dp < 64) {  // d < 32 (8-byte pieces in tsvq_continue_entries): the run-time-length kernel
-        hipLaunchKernelGGL(k_tsvq_continue_any, dim3(256), dim3(256), 0, stream, X, d, centroids, cnorm, left, right, euclid,
+        vq_launch(stage, k_tsvq_continue_any, dim3(256), dim3(256), 0, stream, X, d, centroids, cnorm, left, right, euclid,
                            mode, s.slot_node, s.wl, count, leaf, table16, f16_out, clear_next);
         VQ_LAUNCH_CHECK("k_tsvq_continue_any");
     }

@@ -920,14 +920,14 @@ int launch_gather_rows(const float *X, uint32_t d, uint32_t m, uint32_t k, uint3
 int launch_accumulate_listed(uint32_t m, uint32_t k, uint32_t sd, const float *X, uint32_t d, const uint8_t *codes,
                              const uint32_t *sub_list, uint32_t n_sub, const uint32_t *wl_rows, uint64_t wl_stride,
                              const uint32_t *wl_seg, uint32_t n_seg, uint32_t first_chunk, uint32_t n_patch,
-                             float *partial_sums, uint32_t *partial_counts, hipStream_t stream) {
+                             float *partial_sums, uint32_t *partial_counts, hipStream_t stream, LaunchStage *stage) {
     if (n_sub == 0 || n_patch == 0) return VQHIP_OK;
     const uint32_t spp = (n_seg + n_patch - 1) / n_patch;
     const size_t lds = (size_t)k * (sd + 1) * 4;
     const dim3 grid(n_patch, n_sub);
 #define VQ_LISTED(KSV)                                                                                                  \
-    hipLaunchKernelGGL(k_accumulate_listed<KSV>, grid, dim3(64), lds, stream, X, d, m, k, codes, sub_list, wl_rows, wl_stride, \
-                       wl_seg, n_seg, spp, first_chunk, partial_sums, partial_counts)
+    vq_launch(stage, k_accumulate_listed<KSV>, grid, dim3(64), lds, stream, X, d, m, k, codes, sub_list, wl_rows, wl_stride, \
+              wl_seg, n_seg, spp, first_chunk, partial_sums, partial_counts)
     switch (sd) {
     case 8: VQ_LISTED(2); break;
     case 16: VQ_LISTED(4); break;

@@ -2,6 +2,8 @@
 // Every wrapper enqueues on `stream` and returns a vqhip status.
 #pragma once
 
+#include <hip/hip_ext.h>
+
 #include <mutex>
 #include <vector>
 
@@ -77,7 +79,30 @@ int launch_prepare_codebook(const CodebookView &v, float *prepA, float *prepCn, 
 // bytes (m = 124: m + 4 would put every row's byte s into one bank, a 32-way conflict on the scatter)
 __host__ __device__ constexpr uint32_t codes_transpose_pitch(uint32_t m) { return m + 4 + (((m + 4) % 128 == 0) ? 4u : 0u); }
 
+// Events that the kernels of one stage of a pass carry in their own dispatch (hipExtLaunchKernelGGL): they are filled
+// from the dispatch's completion signal.  A stop event adds nothing to the stream; a start event costs what a
+// recorded one does, so a pass has at most one.
+struct LaunchStage {
+    hipEvent_t start = nullptr;  // bound by the stage's first kernel
+    hipEvent_t stop = nullptr;   // bound by every kernel of the stage: its last kernel keeps it
+    uint32_t launches = 0;
+};
+
+// hipLaunchKernelGGL for the launch sites of a pass: with a stage that holds an event the kernel carries it
+template <class... P, class... A>
+inline void vq_launch(LaunchStage *st, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream,
+                      A &&...args) {
+    if (st && (st->start || st->stop)) {
+        hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, stream, st->start, st->stop, 0u, static_cast<P>(args)...);
+        st->start = nullptr;
+        ++st->launches;
+    } else {
+        hipLaunchKernelGGL(kernel, grid, block, lds, stream, static_cast<P>(args)...);
+    }
+}
+
 struct AssignArgs {
+    LaunchStage *stage = nullptr;  // the stage the next launch belongs to, or null
     const float *X = nullptr;  // [n][d]
     uint64_t n = 0;
     uint32_t d = 0;
@@ -154,7 +179,7 @@ int launch_accumulate(const UpdatePlan &p, const float *X, uint64_t n, uint32_t 
 int launch_accumulate_listed(uint32_t m, uint32_t k, uint32_t sd, const float *X, uint32_t d, const uint8_t *codes,
                              const uint32_t *sub_list, uint32_t n_sub, const uint32_t *wl_rows, uint64_t wl_stride,
                              const uint32_t *wl_seg, uint32_t n_seg, uint32_t first_chunk, uint32_t n_patch,
-                             float *partial_sums, uint32_t *partial_counts, hipStream_t stream);
+                             float *partial_sums, uint32_t *partial_counts, hipStream_t stream, LaunchStage *stage = nullptr);
 // fixed-order f64 combination of the fused path's slabs [chunk][position in the active list][k][sd]
 int launch_reduce_partials_pos(uint32_t m, uint32_t k, uint32_t sd, const float *partial_sums, const uint32_t *partial_counts,
                                uint32_t n_chunks, uint32_t n_sub, const int32_t *sub_pos, double *slab, hipStream_t stream,
@@ -472,7 +497,8 @@ uint32_t tsvq_screen_width(uint32_t d);  // instantiated width serving d (zero p
 bool tsvq_screen_supported(uint32_t n_int, uint32_t n_nodes, uint32_t d, int metric);
 int launch_tsvq_screen_encode(const float *X, uint64_t n, uint32_t d, const float *centroids, const float *cnorm,
                               const int32_t *left, const int32_t *right, int metric, const TsvqScreen &s, int32_t *leaf,
-                              hipStream_t stream, const uint16_t *table16 = nullptr, uint16_t *f16_out = nullptr);
+                              hipStream_t stream, const uint16_t *table16 = nullptr, uint16_t *f16_out = nullptr,
+                              LaunchStage *stage = nullptr);  // stage: events for the call's kernels to carry (the last keeps the stop)
 int launch_tsvq_gather_f16(const float *centroids, uint32_t d, const int32_t *leaf, uint64_t n, uint16_t *f16_out,
                            hipStream_t stream);
 int launch_tsvq_node_norms(const float *centroids, uint32_t n_nodes, uint32_t d, float *cnorm, hipStream_t stream);
