@@ -214,7 +214,7 @@ def test_python_bookkeeping_and_host_side_remove(dim):
     assert ix.add_codes(lists[:20], codes[:20]).tolist() == list(range(20))
     assert ix.add_packed(lists[20:50], words[20:50]).tolist() == list(range(20, 50))
     h = ix._handle()  # host-only: the rows move into the handle
-    assert ix._host_words is None and h.info() == (50, 5, dim, 1, *[float(F(v)) for v in SQ[:2]], SQ[2])
+    assert ix._host is None and h.info() == (50, 5, dim, 1, *[float(F(v)) for v in SQ[:2]], SQ[2])
     ix.add_codes(lists[50:70], codes[50:70])
     ix.add_packed(lists[70:], words[70:])
     assert np.array_equal(ix.codes(), codes) and np.array_equal(ix.packed(), words) and ix.packed().dtype == np.uint32

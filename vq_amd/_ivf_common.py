@@ -1,15 +1,19 @@
-"""What ``IVFPQIndex``, ``IVFFlatIndex``, ``IVFScalarIndex``, ``IVFScalar4Index`` and ``IVFBinaryIndex`` share: the coarse centroids and list ids, the checks of
-queries, ``nprobe`` and ``topk``, probe / search / rerank over the device handle, and the readers of the index files.
-A subclass keeps its payload (codes or rows), its add paths, ``_handle``, ``close`` and its file layout.
-``IVFRangeMixin`` adds the range search of the two indexes whose distances are exact (not ``IVFPQIndex``)."""
+"""What ``IVFPQIndex``, ``IVFFlatIndex``, ``IVFScalarIndex``, ``IVFScalar4Index`` and ``IVFBinaryIndex`` share: the coarse
+centroids and list ids, the front of every add, the payload (codes, rows or words) on the host and in the handle, the
+checks of queries, ``nprobe`` and ``topk``, probe / search / rerank over the device handle, and the one writer and
+reader of the index files.  A subclass keeps the checks of its own stored form, how its handle is made, and the fields
+of its file.  ``IVFEncodedBase`` is the base of the three indexes that encode float rows on the device and hand their
+payload to the handle.  ``IVFRangeMixin`` adds the range search of the indexes whose distances are exact (not
+``IVFPQIndex``)."""
 from __future__ import annotations
 
-import operator
+import math
+from typing import Callable, NamedTuple
 
 import numpy as np
 
 from . import _lib
-from ._resident_common import DEFAULT_MAX_RESULTS, _max_results, _radii, pack_row_mask
+from ._resident_common import DEFAULT_MAX_RESULTS, _count, _max_results, _nq, _radii, pack_row_mask
 from .distance import Distance
 from .errors import DimensionMismatch, InvalidParameter
 
@@ -17,13 +21,6 @@ MAX_NLIST = 65536
 MAX_PROBE = 1024
 MAX_TOPK = 1024
 PAD_ID = 0xFFFFFFFF
-
-
-def _count(v, name: str) -> int:
-    try:
-        return operator.index(v)
-    except TypeError:
-        raise InvalidParameter(name, f"must be an integer, got {v!r}") from None
 
 
 def _nearest_lists(coarse, X, metric: int) -> np.ndarray:
@@ -73,30 +70,30 @@ def _train_coarse(X, nlist: int, max_iters: int, distance: Distance, seed: int) 
     return ProductQuantizer(X, 1, nlist, max_iters, distance, seed).codebooks[0]
 
 
-class _Reader:
-    """the blocks of an index file, each checked for truncation"""
-
-    def __init__(self, f):
-        self._f = f
-
-    def block(self, count: int, dtype, what: str) -> np.ndarray:
-        dt = np.dtype(dtype)
-        raw = self._f.read(count * dt.itemsize)
-        if len(raw) != count * dt.itemsize:
-            raise ValueError(f"truncated {what}")
-        return np.frombuffer(raw, dtype=dt)
-
-    def lists(self, n: int) -> np.ndarray:
-        return self.block(n, "<u4", "list ids")
-
-    def end(self, what: str) -> None:
-        if self._f.read(1):
-            raise ValueError(f"trailing bytes after the {what}")
+class IVFFile(NamedTuple):
+    """what a subclass reads from a file's header (``_file``): the sizes, the payload block, and how to make the index"""
+    dim: int
+    nlist: int
+    n: int
+    payload: tuple  # (dtype in the file, items a row, the block's name)
+    make: Callable  # (coarse, *extra blocks) -> the index, empty
+    extra: tuple = ()  # blocks between the coarse centroids and the list ids: (shape, name), f32
+    check: Callable | None = None  # the payload's own check: raises ValueError
 
 
-def _check_file_lists(lists: np.ndarray, nlist: int) -> None:
-    if lists.size and int(lists.max()) >= nlist:
-        raise ValueError(f"corrupt index: a list id is outside [0, {nlist})")
+def sizes_ok(dim: int, nlist: int, n: int) -> bool:
+    """the header fields that every inverted file has"""
+    return 1 <= nlist <= MAX_NLIST and dim >= 1 and n < 1 << 32
+
+
+def _block(f, shape: tuple, dtype, what: str) -> np.ndarray:
+    """a block of an index file in the machine's byte order, checked for truncation"""
+    dt = np.dtype(dtype)
+    count = math.prod(shape)
+    raw = f.read(count * dt.itemsize)
+    if len(raw) != count * dt.itemsize:
+        raise ValueError(f"truncated {what}")
+    return np.frombuffer(raw, dtype=dt).astype(dt.newbyteorder("=")).reshape(shape)
 
 
 def rerank_hits(q: np.ndarray, hits: np.ndarray, topk: int, rerank):
@@ -128,12 +125,21 @@ def filtered_adc_then_rerank(adc_search, n: int, dim: int, q: np.ndarray, topk: 
 
 
 class IVFIndexBase:
-    """coarse centroids (nlist, dim) + distance + the list id of every added row; `_ix` is the device handle or None"""
+    """coarse centroids (nlist, dim) + distance + the list id of every added row; `_ix` is the device handle or None.
+    `_host` is the payload on the host, one stored row per added row -- or None once the handle holds the only copy.
+    A subclass states ``_new_handle()``, `_UPLOAD` (the handle's add entry that takes the stored form), `_READ_BACK` (the
+    handle's accessor of the stored form: the payload is then handed over to the handle, and read back by ``close``;
+    None: the host twin stays), and for its file `_HEADER`, `_MAGICS`, ``_header()``, ``_file()``."""
 
-    def _init_lists(self, coarse: np.ndarray, distance: Distance) -> None:
+    _UPLOAD = "add"
+    _READ_BACK = None
+
+    def _init_lists(self, coarse: np.ndarray, distance: Distance, payload: np.ndarray) -> None:
+        """payload: the empty (0, items a row) array of the stored form"""
         self._distance = distance
         self._coarse = coarse
         self._lists = np.empty(0, np.uint32)
+        self._host = payload
         self._ix = None
 
     # -- shape ------------------------------------------------------------------------------
@@ -197,10 +203,65 @@ class IVFIndexBase:
         if len(self) + n_new >= 1 << 32:
             raise InvalidParameter(what, "an index holds at most 2^32 - 1 rows")
 
+    def _add_shape(self, list_ids, a, what: str, width: int, shape_only: bool = False):
+        """the first half of an add's front: list ids (n,) against the array `a` (n, width), named `what` in the errors.
+        shape_only: a wrong width is reported as a wrong shape (IVFPQIndex).  Returns both as arrays."""
+        lid = np.asarray(list_ids)
+        a = np.asarray(a)
+        if lid.ndim != 1:
+            raise InvalidParameter("list_ids", "must be a 1D array (n,)")
+        if a.ndim != 2 or (shape_only and a.shape[1] != width):
+            raise InvalidParameter(what, f"must have shape (n, {width})")
+        if a.shape[1] != width:
+            raise DimensionMismatch(width, a.shape[1])
+        if a.shape[0] != lid.shape[0]:
+            raise DimensionMismatch(lid.shape[0], a.shape[0])
+        return lid, a
+
+    def _add_lists(self, lid: np.ndarray, what: str) -> np.ndarray:
+        """the second half: list ids in range and room for them; the list ids as uint32"""
+        self._check_list_ids(lid)
+        self._check_room(lid.shape[0], what)
+        return np.ascontiguousarray(lid, dtype=np.uint32)
+
+    def _add_front(self, list_ids, a, what: str, width: int):
+        """both halves, for a class whose checks of `a` itself come behind them"""
+        lid, a = self._add_shape(list_ids, a, what, width)
+        return self._add_lists(lid, what), a
+
+    def _append(self, lid: np.ndarray, given: np.ndarray, entry: str | None = None, stored=None) -> np.ndarray:
+        """append checked rows to whichever side holds the payload: `given` goes to the handle, if there is one, through
+        its add `entry` (default: the upload's); to the host array, if it holds the rows, as ``stored(given)`` (default:
+        as given).  Returns the new row ids."""
+        if self._ix is not None and lid.size:
+            getattr(self._ix, entry or self._UPLOAD)(lid, given)  # the handle first: the one step that can fail
+        if self._host is not None:
+            self._host = np.concatenate([self._host, given if stored is None else stored(given)])
+        return self._appended(lid)
+
     def _appended(self, lid: np.ndarray) -> np.ndarray:
         n0 = len(self)
         self._lists = np.concatenate([self._lists, lid])
         return np.arange(n0, n0 + lid.shape[0], dtype=np.uint32)
+
+    def _stored(self) -> np.ndarray:
+        """(n, items a row): the payload, from the host or from the handle that holds it"""
+        return self._host if self._host is not None else getattr(self._ix, self._READ_BACK)()
+
+    def _new_handle(self):
+        """the _lib handle over the coarse centroids, empty (a subclass's)"""
+        raise NotImplementedError
+
+    def _handle(self):
+        """the handle, made and given the rows on first use"""
+        if self._ix is None:
+            ix = self._new_handle()
+            if len(self):
+                getattr(ix, self._UPLOAD)(self._lists, self._host)
+            self._ix = ix
+            if self._READ_BACK is not None:
+                self._host = None  # the handle holds the only copy
+        return self._ix
 
     def remove_rows(self, mask_or_ids) -> np.ndarray:
         """remove the rows of a bool mask (n,) -- True: remove -- or of an integer array of row ids in [0, n), in any
@@ -231,11 +292,9 @@ class IVFIndexBase:
         if self._ix is not None:
             self._ix.remove(words)  # the handle first: the one step that can fail
         self._lists = self._lists[kept]
-        self._removed(kept)
+        if self._host is not None:  # (else the handle holds the only copy)
+            self._host = self._host[kept]
         return kept
-
-    def _removed(self, kept: np.ndarray) -> None:
-        """a subclass's own host array follows a removal: `kept` are the old ids of the rows that stay, ascending"""
 
     # -- search -----------------------------------------------------------------------------
     def _queries(self, queries) -> np.ndarray:
@@ -300,16 +359,84 @@ class IVFIndexBase:
         """device pointers: queries [nq][dim] f32, results [nq][topk] uint32 / f32; asynchronous on the current stream"""
         p = self._nprobe(nprobe)
         t = self._topk(topk)
-        n_q = _count(nq, "nq")
-        if n_q < 0 or n_q >= 1 << 32:
-            raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
+        n_q = _nq(nq)
         self._handle().search_device(int(dev_queries), n_q, p, t, int(dev_idx), int(dev_dist))
 
     def close(self) -> None:
-        """release the device handle (the next probe or search builds it again)"""
+        """release the handle and its device state (the next probe or search builds it again); the rows stay"""
         if self._ix is not None:
+            if self._host is None:
+                self._host = self._stored()
             self._ix.close()
             self._ix = None
+
+    # -- file -------------------------------------------------------------------------------
+    def _header(self) -> tuple:
+        """the fields of `_HEADER`, the magic first (a subclass's)"""
+        raise NotImplementedError
+
+    @classmethod
+    def _file(cls, *fields) -> IVFFile:
+        """the checks of a header's fields behind the magic's -- ValueError("corrupt index header...") -- and what they
+        say of the file (a subclass's)"""
+        raise NotImplementedError
+
+    def _file_extra(self) -> tuple:
+        """the arrays of `IVFFile.extra`"""
+        return ()
+
+    def save(self, path) -> None:
+        with open(path, "wb") as f:
+            f.write(self._HEADER.pack(*self._header()))
+            for block in (self._coarse, *self._file_extra()):
+                f.write(block.astype("<f4").tobytes())
+            f.write(self._lists.astype("<u4").tobytes())
+            stored = self._stored()
+            f.write(stored.astype(stored.dtype.newbyteorder("<")).tobytes())
+
+    @classmethod
+    def load(cls, path):
+        """read the class's file; every field, every list id and the payload are checked here, before anything can reach
+        the device"""
+        with open(path, "rb") as f:
+            head = f.read(cls._HEADER.size)
+            if len(head) != cls._HEADER.size:
+                raise ValueError("truncated index header")
+            fields = cls._HEADER.unpack(head)
+            if fields[0] not in cls._MAGICS:
+                raise ValueError(f"not a {' or '.join(m.decode() for m in cls._MAGICS)} file")
+            h = cls._file(*fields)
+            dtype, width, what = h.payload
+            coarse = _block(f, (h.nlist, h.dim), "<f4", "coarse centroids")
+            extra = [_block(f, shape, "<f4", name) for shape, name in h.extra]
+            lists = _block(f, (h.n,), "<u4", "list ids")
+            payload = _block(f, (h.n, width), dtype, what)
+            if f.read(1):
+                raise ValueError(f"trailing bytes after the {what}")
+        if lists.size and int(lists.max()) >= h.nlist:
+            raise ValueError(f"corrupt index: a list id is outside [0, {h.nlist})")
+        if h.check is not None:
+            h.check(payload)
+        self = h.make(coarse, *extra)
+        self._lists, self._host = lists, payload
+        return self
+
+
+class IVFEncodedBase(IVFIndexBase):
+    """an inverted file that stores codes or words, encodes float rows on the device, and hands its payload over to the
+    handle (IVFScalarIndex, IVFScalar4Index, IVFBinaryIndex)"""
+
+    def add_rows(self, list_ids, rows) -> np.ndarray:
+        """encode rows (n, dim) floating point, as float32, on the device -- into the stored form that the class's rule
+        gives (the codes of ``quantizer.quantize_batch``, packed where the index packs; the bits x >= threshold) -- and
+        append them into the lists list_ids (n,) < nlist; returns the new row ids"""
+        lid, r = self._add_front(list_ids, rows, "rows", self.dim)
+        if r.dtype.kind != "f":
+            raise InvalidParameter("rows", f"must be floating point, got {r.dtype}")
+        if lid.size:
+            with np.errstate(over="ignore"):
+                self._handle().add_rows(lid, np.ascontiguousarray(r, dtype=np.float32))
+        return self._appended(lid)
 
 
 class IVFRangeMixin:
@@ -333,9 +460,7 @@ class IVFRangeMixin:
                             max_results: int = DEFAULT_MAX_RESULTS) -> "_lib.RangeResult":
         """`range_search` with the queries [nq][dim] f32 at a device pointer (4-byte aligned) and the result left on the
         device: a RangeResult (.total, .lims, .device_pointers(), .read()).  Returns when the result is complete."""
-        n_q = _count(nq, "nq")
-        if n_q < 0 or n_q >= 1 << 32:
-            raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
+        n_q = _nq(nq)
         r = _radii(radius, n_q)
         p = self._nprobe(nprobe)
         m = _max_results(max_results)

@@ -7,16 +7,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._ivf_common import _count
-from ._resident_common import DEFAULT_MAX_RESULTS, _allowed, _max_results, _radii
-from .errors import InvalidParameter
-
-
-def _nq(nq) -> int:
-    n_q = _count(nq, "nq")
-    if n_q < 0 or n_q >= 1 << 32:
-        raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
-    return n_q
+from ._resident_common import DEFAULT_MAX_RESULTS, _allowed, _max_results, _nq, _radii
 
 
 class IVFFilterMixin:

@@ -1,8 +1,11 @@
-"""What ``FlatIndex``, ``ScalarIndex`` and ``BinaryIndex`` share: the rows of a caller's array that go to the device on the
-first search, the checks of queries and ``topk``, and search over the device handle.  A subclass keeps its constructors,
-the checks of its own source array, ``_make_handle``, ``__repr__`` and its file layout.  ``ExactResidentIndex`` adds the
-range search and the rerank of the two indexes whose distances are exact (not ``BinaryIndex``, whose range search takes
-a radius in Hamming bits: ``_hamming_radii``), and the row mask of their filtered calls (``pack_row_mask``)."""
+"""What ``FlatIndex``, ``ScalarIndex``, ``Scalar4Index``, ``BinaryIndex`` and ``AsymmetricBinaryIndex`` share: the rows of
+a caller's array that go to the device on the first search, the checks of queries and ``topk``, and search over the
+device handle.  A subclass keeps its constructors, the checks of its own source array, ``_make_handle``, ``__repr__``
+and the fields of its file.  ``ExactResidentIndex`` adds the range search and the rerank of the indexes whose distances
+are exact (not ``BinaryIndex``, whose range search takes a radius in Hamming bits: ``_hamming_radii``), and the row
+mask of their filtered calls (``pack_row_mask``).  ``PackedSourceMixin`` is the packed-words source of the three indexes
+that store words (``from_packed`` and the ``add_*`` forms); ``write_index_file`` / ``read_index_file`` are the one writer
+and reader of the four resident files.  ``_count`` and ``_nq`` serve the inverted files too."""
 from __future__ import annotations
 
 import operator
@@ -11,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from .distance import Distance
-from .errors import DimensionMismatch, EmptyInput, InvalidParameter
+from .errors import DimensionMismatch, EmptyInput, InvalidData, InvalidParameter
 
 MAX_TOPK = 1024
 MAX_CANDIDATES = 4096
@@ -143,6 +146,40 @@ def _check_distance(distance, default: Distance) -> Distance:
     if not isinstance(distance, Distance):
         raise InvalidParameter("distance", f"expected a Distance, got {type(distance).__name__}")
     return distance
+
+
+def write_index_file(path, header: bytes, payload: np.ndarray) -> None:
+    """a resident index file: the packed header, then the payload little endian"""
+    with open(path, "wb") as f:
+        f.write(header)
+        f.write(payload.astype(payload.dtype.newbyteorder("<")).tobytes())
+
+
+def read_index_file(path, header, magic: bytes, noun: str, fields):
+    """Read a resident index file of the struct `header` under `magic`; `noun` names the index in the messages.
+    ``fields(*header fields behind the magic)`` is the class's own checks: it returns (n, width, dtype, what, finish)
+    -- the payload is n * width items of `dtype`, `what` names it, and ``finish(payload (n, width))`` checks it and
+    makes the index.  Truncation and trailing bytes are refused here."""
+    with open(path, "rb") as f:
+        head = f.read(header.size)
+        if len(head) != header.size:
+            raise InvalidData(f"truncated {noun} header")
+        got = header.unpack(head)
+        if got[0] != magic:
+            raise InvalidData(f"not a {magic.decode()} file")
+        n, width, dtype, what, finish = fields(*got[1:])
+        dt = np.dtype(dtype)
+        raw = f.read(n * width * dt.itemsize)
+        if len(raw) != n * width * dt.itemsize:
+            raise InvalidData(f"truncated {what}")
+        if f.read(1):
+            raise InvalidData(f"trailing bytes after the {what}")
+    return finish(np.frombuffer(raw, dtype=dt).astype(dt.newbyteorder("=")).reshape(n, width))
+
+
+def check_file_rows(n: int) -> None:
+    if not 1 <= n < 1 << 32:
+        raise InvalidData(f"row count {n} is outside [1, 2^32)")
 
 
 class ResidentIndex:
@@ -389,3 +426,56 @@ class ExactResidentIndex(ResidentIndex):
         if c.shape[1] > 1 and bool((s[:, 1:] == s[:, :-1]).any()):
             raise InvalidParameter("candidates", "row ids must be distinct within a query")
         return self._index().rerank(q, np.ascontiguousarray(c, dtype=np.uint32), k)
+
+
+class PackedSourceMixin:
+    """in front of a ResidentIndex that stores uint32 words and takes rows in three forms -- float32 rows, u8 codes, the
+    words themselves (``BinaryIndex``, ``AsymmetricBinaryIndex``: 32 bits a word; ``Scalar4Index``: 8 nibbles).  A subclass
+    states `_F32`, `_U8`, `_PACKED` (the _lib source kinds), `_PAD` (what a pad position is called), `_words(dim)`,
+    `_pad_ok(words, dim)`, `_packed_dim(d)` (the check of ``from_packed``'s dim) and, where codes have a limit,
+    `_codes_ok(codes)`; its ``_setup(a, kind, quantizer, distance, dim=None)`` ends every constructor."""
+
+    _codes_ok = staticmethod(lambda codes: None)
+
+    @classmethod
+    def _from_packed(cls, words, dim, quantizer, distance):
+        a = words if isinstance(words, np.ndarray) else np.asarray(words)
+        if a.dtype != np.uint32:
+            raise InvalidParameter("words", f"dtype must be uint32, got {a.dtype}")
+        d = _count(dim, "dim")
+        if a.ndim != 2:
+            raise ValueError("expected a 2D array (n, words)")
+        cls._packed_dim(d)
+        if a.shape[1] != cls._words(d):
+            raise DimensionMismatch(cls._words(d), a.shape[1])
+        if not cls._pad_ok(a, d):
+            raise InvalidParameter("words", f"a row has a pad {cls._PAD} (dimension >= {d}) set")
+        self = cls.__new__(cls)
+        self._setup(a, cls._PACKED, quantizer, distance, dim=d)
+        return self
+
+    @property
+    def quantizer(self):
+        return self._quantizer
+
+    def _add_form(self):
+        return "add", np.float32, (self._F32,)  # float32 rows, put into words on the device as the constructor's are
+
+    def add_codes(self, codes) -> np.ndarray:
+        """append u8 codes (b, dim) in ``from_codes``'s form and under its limits; returns their ids uint32 (b,)"""
+        a = self._added(codes, np.uint8, "codes")
+        self._codes_ok(a)
+        return self._append("add", a, a.shape[0], self._U8)
+
+    def add_packed(self, words) -> np.ndarray:
+        """append packed rows uint32 (b, words of a row) in the index layout, pad positions zero (``from_packed``'s
+        form); returns their ids uint32 (b,)"""
+        a = self._added(words, np.uint32, "words", self._words(self._dim))
+        if not self._pad_ok(a, self._dim):
+            raise InvalidParameter("words", f"a row has a pad {self._PAD} (dimension >= {self._dim}) set")
+        return self._append("add", a, a.shape[0], self._PACKED)
+
+    def add_packed_device(self, dev_words: int, n: int) -> np.ndarray:
+        """``add_packed`` with the words [n][words of a row] at a device pointer (4-byte aligned); a pad position set is
+        an FfiError (ERR_INVALID_INPUT) that leaves the index as it was.  Returns their ids."""
+        return self._append_device("add_device", dev_words, n, self._PACKED)

@@ -37,59 +37,19 @@ import struct
 import numpy as np
 
 from . import _lib
-from ._resident_common import ExactResidentIndex, _check_distance, _count
-from .binary import MAX_DIM, _pad_ok, pack_bits, words_per_row
+from ._resident_common import ExactResidentIndex, _check_distance, read_index_file, write_index_file
+from .binary import PackedBitsSource, _check_dim
 from .bq import BinaryQuantizer
-from .distance import Distance
-from .errors import DimensionMismatch, InvalidData, InvalidParameter
+from .distance import METRIC_NAMES, Distance
+from .errors import InvalidParameter
 
 MAGIC = b"VQABINX1"
 _HEADER = struct.Struct("<8sQIIfII")  # magic, n, d, metric, threshold, low, high
-_METRIC_NAMES = {_lib.SQUARED_EUCLIDEAN: "squared_euclidean", _lib.EUCLIDEAN: "euclidean", _lib.MANHATTAN: "manhattan",
-                 _lib.COSINE: "cosine", _lib.COSINE_UNCLAMPED: "cosine_unclamped"}
 
 
-class AsymmetricBinaryIndex(ExactResidentIndex):
+class AsymmetricBinaryIndex(PackedBitsSource, ExactResidentIndex):
     """Exact search over `rows` (n, d) float32, stored as the bits of `quantizer` (default ``BinaryQuantizer(0.0)``),
     against float32 queries under `distance` (any metric, cosine included; default Euclidean)."""
-
-    def __init__(self, rows, quantizer: BinaryQuantizer | None = None, distance: Distance | None = None):
-        a = rows if isinstance(rows, np.ndarray) else np.asarray(rows)
-        if a.dtype != np.float32:
-            raise InvalidParameter("rows", f"dtype must be float32, got {a.dtype}")
-        self._setup(a, _lib.BINARY_F32, quantizer, distance)
-
-    @classmethod
-    def from_codes(cls, codes, quantizer: BinaryQuantizer | None = None,
-                   distance: Distance | None = None) -> "AsymmetricBinaryIndex":
-        """u8 BQ codes (n, d), e.g. ``quantizer.quantize_batch(rows)``; bit = code >= high"""
-        a = codes if isinstance(codes, np.ndarray) else np.asarray(codes)
-        if a.dtype != np.uint8:
-            raise InvalidParameter("codes", f"dtype must be uint8, got {a.dtype}")
-        self = cls.__new__(cls)
-        self._setup(a, _lib.BINARY_U8, quantizer, distance)
-        return self
-
-    @classmethod
-    def from_packed(cls, words, dim: int, quantizer: BinaryQuantizer | None = None,
-                    distance: Distance | None = None) -> "AsymmetricBinaryIndex":
-        """uint32 (n, ceil(dim / 32)) packed rows in ``BinaryIndex``'s layout, pad bits zero.  The asymmetric twin of a
-        ``BinaryIndex`` b is ``from_packed(b.packed(), b.dim, b.quantizer, distance)``."""
-        a = words if isinstance(words, np.ndarray) else np.asarray(words)
-        if a.dtype != np.uint32:
-            raise InvalidParameter("words", f"dtype must be uint32, got {a.dtype}")
-        d = _count(dim, "dim")
-        if a.ndim != 2:
-            raise ValueError("expected a 2D array (n, words)")
-        if not 1 <= d <= MAX_DIM:
-            raise InvalidParameter("dim", f"must be between 1 and {MAX_DIM}, got {d}")
-        if a.shape[1] != words_per_row(d):
-            raise DimensionMismatch(words_per_row(d), a.shape[1])
-        if not _pad_ok(a, d):
-            raise InvalidParameter("words", f"a row has a pad bit (dimension >= {d}) set")
-        self = cls.__new__(cls)
-        self._setup(a, _lib.BINARY_PACKED, quantizer, distance, dim=d)
-        return self
 
     def _setup(self, a: np.ndarray, kind: int, quantizer, distance, dim: int | None = None) -> None:
         quantizer = BinaryQuantizer(0.0) if quantizer is None else quantizer
@@ -101,12 +61,7 @@ class AsymmetricBinaryIndex(ExactResidentIndex):
         self._kind = kind
 
     def _check_dim(self, d: int, what: str) -> None:
-        if not 1 <= d <= MAX_DIM:
-            raise InvalidParameter("dim", f"must be between 1 and {MAX_DIM}, got {d}")
-
-    @property
-    def quantizer(self) -> BinaryQuantizer:
-        return self._quantizer
+        _check_dim(d)
 
     def __repr__(self) -> str:
         return (f"AsymmetricBinaryIndex(n={self._n}, dim={self._dim}, quantizer={self._quantizer!r}, "
@@ -116,27 +71,6 @@ class AsymmetricBinaryIndex(ExactResidentIndex):
         q = self._quantizer
         return _lib.ABin(self._src, self._kind, self._n, self._dim, q.threshold, q.low, q.high, self._distance.metric)
 
-    def _add_form(self):
-        return "add", np.float32, (_lib.BINARY_F32,)  # float32 rows, binarised on the device by the quantizer's rule
-
-    def add_codes(self, codes) -> np.ndarray:
-        """append u8 BQ codes (b, dim), bit = code >= high (``from_codes``'s form); returns their ids uint32 (b,)"""
-        a = self._added(codes, np.uint8, "codes")
-        return self._append("add", a, a.shape[0], _lib.BINARY_U8)
-
-    def add_packed(self, words) -> np.ndarray:
-        """append packed rows uint32 (b, ceil(dim / 32)) in the index layout, pad bits zero (``from_packed``'s form);
-        returns their ids uint32 (b,)"""
-        a = self._added(words, np.uint32, "words", words_per_row(self._dim))
-        if not _pad_ok(a, self._dim):
-            raise InvalidParameter("words", f"a row has a pad bit (dimension >= {self._dim}) set")
-        return self._append("add", a, a.shape[0], _lib.BINARY_PACKED)
-
-    def add_packed_device(self, dev_words: int, n: int) -> np.ndarray:
-        """``add_packed`` with the words [n][ceil(dim / 32)] at a device pointer (4-byte aligned); a pad bit set is an
-        FfiError (ERR_INVALID_INPUT) that leaves the index as it was.  Returns their ids."""
-        return self._append_device("add_device", dev_words, n, _lib.BINARY_PACKED)
-
     def packed(self) -> np.ndarray:
         """the packed rows, uint32 (n, ceil(dim / 32)): the caller's for an index built ``from_packed`` and not yet
         searched, else from the device"""
@@ -144,48 +78,18 @@ class AsymmetricBinaryIndex(ExactResidentIndex):
             return self._src.copy()
         return self._index().packed()
 
-    def _host_words(self) -> np.ndarray:
-        if self._ix is not None:
-            return self._ix.packed()
-        if self._kind == _lib.BINARY_PACKED:
-            return self._src
-        if self._kind == _lib.BINARY_U8:
-            return pack_bits(self._src >= np.uint8(self._quantizer.high))
-        return pack_bits(self._src >= np.float32(self._quantizer.threshold))
-
     # -- file -------------------------------------------------------------------------------
     def save(self, path) -> None:
         q = self._quantizer
-        with open(path, "wb") as f:
-            f.write(_HEADER.pack(MAGIC, self._n, self._dim, self._distance.metric, np.float32(q.threshold), q.low, q.high))
-            f.write(np.ascontiguousarray(self._host_words(), dtype="<u4").tobytes())
+        write_index_file(path, _HEADER.pack(MAGIC, self._n, self._dim, self._distance.metric, np.float32(q.threshold), q.low,
+                                            q.high), self._host_words())
 
     @classmethod
     def load(cls, path) -> "AsymmetricBinaryIndex":
         """read a VQABINX1 file; every field is checked here, before anything can reach the device"""
-        with open(path, "rb") as f:
-            head = f.read(_HEADER.size)
-            if len(head) != _HEADER.size:
-                raise InvalidData("truncated asymmetric binary index header")
-            magic, n, dim, metric, thr, low, high = _HEADER.unpack(head)
-            if magic != MAGIC:
-                raise InvalidData("not a VQABINX1 file")
-            if metric not in _METRIC_NAMES:
+        def fields(n, dim, metric, thr, low, high):
+            if metric >= len(METRIC_NAMES):
                 raise InvalidParameter("distance", f"unknown metric id {metric}")
-            if not 1 <= dim <= MAX_DIM:
-                raise InvalidParameter("dim", f"must be between 1 and {MAX_DIM}, got {dim}")
-            if not 1 <= n < 1 << 32:
-                raise InvalidData(f"row count {n} is outside [1, 2^32)")
-            if low > 255 or high > 255:
-                raise InvalidParameter("low/high", f"must fit in u8, got {low} / {high}")
-            quantizer = BinaryQuantizer(float(thr), low, high)  # the reference's own checks
-            w = words_per_row(dim)
-            raw = f.read(n * w * 4)
-            if len(raw) != n * w * 4:
-                raise InvalidData("truncated packed rows")
-            if f.read(1):
-                raise InvalidData("trailing bytes after the packed rows")
-        words = np.frombuffer(raw, dtype="<u4").astype(np.uint32).reshape(n, w)
-        if not _pad_ok(words, dim):
-            raise InvalidData(f"a row has a pad bit (dimension >= {dim}) set")
-        return cls.from_packed(words, dim, quantizer, Distance(_METRIC_NAMES[metric]))
+            return cls._file_payload(metric, dim, thr, low, high, n)
+
+        return read_index_file(path, _HEADER, MAGIC, "asymmetric binary index", fields)

@@ -21,10 +21,11 @@ import numpy as np
 
 from . import _lib
 from ._binary_filter import BinaryFilterMixin
-from ._resident_common import DEFAULT_MAX_RESULTS, ResidentIndex, _count, _hamming_radii, _max_results, _nq
+from ._resident_common import (DEFAULT_MAX_RESULTS, PackedSourceMixin, ResidentIndex, _hamming_radii, _max_results, _nq,
+                               check_file_rows, read_index_file, write_index_file)
 from .bq import BinaryQuantizer
-from .distance import Distance
-from .errors import DimensionMismatch, InvalidData, InvalidParameter
+from .distance import METRIC_NAMES, Distance
+from .errors import InvalidData, InvalidParameter
 from .flat import adc_then_rerank
 
 MAGIC = b"VQBINIX1"
@@ -54,6 +55,11 @@ def _pad_ok(words: np.ndarray, dim: int) -> bool:
     return not bool((words[:, -1] & ~mask).any())
 
 
+def _check_dim(dim: int) -> None:
+    if not 1 <= dim <= MAX_DIM:
+        raise InvalidParameter("dim", f"must be between 1 and {MAX_DIM}, got {dim}")
+
+
 def _check_params(dim: int, quantizer, distance) -> None:
     if not isinstance(quantizer, BinaryQuantizer):
         raise InvalidParameter("quantizer", f"expected a BinaryQuantizer, got {type(quantizer).__name__}")
@@ -62,13 +68,16 @@ def _check_params(dim: int, quantizer, distance) -> None:
     if distance.metric not in _METRICS:
         raise InvalidParameter("distance", f"{distance.name()} is not a function of the Hamming distance alone; "
                                            "use squared_euclidean, euclidean or manhattan")
-    if not 1 <= dim <= MAX_DIM:
-        raise InvalidParameter("dim", f"must be between 1 and {MAX_DIM}, got {dim}")
+    _check_dim(dim)
 
 
-class BinaryIndex(BinaryFilterMixin, ResidentIndex):
-    """Exact Hamming top-k over rows binarised by `quantizer` (default ``BinaryQuantizer(0.0)``) under `distance`
-    (default Manhattan: with the default quantizer, D is the Hamming count)."""
+class PackedBitsSource(PackedSourceMixin):
+    """the rows of ``BinaryIndex`` and ``AsymmetricBinaryIndex``, one bit a dimension: float32 rows (bit = x >=
+    threshold), u8 BQ codes (bit = code >= high) or the packed words, at construction and in every add; the words on the
+    host for ``save``; and the fields the two files share.  `quantizer` defaults to ``BinaryQuantizer(0.0)``."""
+
+    _F32, _U8, _PACKED, _PAD = _lib.BINARY_F32, _lib.BINARY_U8, _lib.BINARY_PACKED, "bit"
+    _words, _pad_ok, _packed_dim = staticmethod(words_per_row), staticmethod(_pad_ok), staticmethod(_check_dim)
 
     def __init__(self, rows, quantizer: BinaryQuantizer | None = None, distance: Distance | None = None):
         a = rows if isinstance(rows, np.ndarray) else np.asarray(rows)
@@ -77,7 +86,7 @@ class BinaryIndex(BinaryFilterMixin, ResidentIndex):
         self._setup(a, _lib.BINARY_F32, quantizer, distance)
 
     @classmethod
-    def from_codes(cls, codes, quantizer: BinaryQuantizer | None = None, distance: Distance | None = None) -> "BinaryIndex":
+    def from_codes(cls, codes, quantizer: BinaryQuantizer | None = None, distance: Distance | None = None):
         """u8 BQ codes (n, d), e.g. ``quantizer.quantize_batch(rows)``; bit = code >= high"""
         a = codes if isinstance(codes, np.ndarray) else np.asarray(codes)
         if a.dtype != np.uint8:
@@ -87,24 +96,40 @@ class BinaryIndex(BinaryFilterMixin, ResidentIndex):
         return self
 
     @classmethod
-    def from_packed(cls, words, dim: int, quantizer: BinaryQuantizer | None = None,
-                    distance: Distance | None = None) -> "BinaryIndex":
-        """uint32 (n, ceil(dim / 32)) packed rows in the index layout, pad bits zero"""
-        a = words if isinstance(words, np.ndarray) else np.asarray(words)
-        if a.dtype != np.uint32:
-            raise InvalidParameter("words", f"dtype must be uint32, got {a.dtype}")
-        d = _count(dim, "dim")
-        if a.ndim != 2:
-            raise ValueError("expected a 2D array (n, words)")
-        if not 1 <= d <= MAX_DIM:
-            raise InvalidParameter("dim", f"must be between 1 and {MAX_DIM}, got {d}")
-        if a.shape[1] != words_per_row(d):
-            raise DimensionMismatch(words_per_row(d), a.shape[1])
-        if not _pad_ok(a, d):
-            raise InvalidParameter("words", f"a row has a pad bit (dimension >= {d}) set")
-        self = cls.__new__(cls)
-        self._setup(a, _lib.BINARY_PACKED, quantizer, distance, dim=d)
-        return self
+    def from_packed(cls, words, dim: int, quantizer: BinaryQuantizer | None = None, distance: Distance | None = None):
+        """uint32 (n, ceil(dim / 32)) packed rows in the index layout, pad bits zero.  The asymmetric twin of a
+        ``BinaryIndex`` b is ``AsymmetricBinaryIndex.from_packed(b.packed(), b.dim, b.quantizer, distance)``."""
+        return cls._from_packed(words, dim, quantizer, distance)
+
+    def _host_words(self) -> np.ndarray:
+        if self._ix is not None:
+            return self._ix.packed()
+        if self._kind == _lib.BINARY_PACKED:
+            return self._src
+        if self._kind == _lib.BINARY_U8:
+            return pack_bits(self._src >= np.uint8(self._quantizer.high))
+        return pack_bits(self._src >= np.float32(self._quantizer.threshold))
+
+    @classmethod
+    def _file_payload(cls, metric: int, dim: int, thr, low: int, high: int, n: int):
+        """the checks of a file's fields behind the metric's, and its payload (`read_index_file`)"""
+        _check_dim(dim)
+        check_file_rows(n)
+        if low > 255 or high > 255:
+            raise InvalidParameter("low/high", f"must fit in u8, got {low} / {high}")
+        quantizer = BinaryQuantizer(float(thr), low, high)  # the reference's own checks
+
+        def finish(words):
+            if not _pad_ok(words, dim):
+                raise InvalidData(f"a row has a pad bit (dimension >= {dim}) set")
+            return cls.from_packed(words, dim, quantizer, Distance(METRIC_NAMES[metric]))
+
+        return n, words_per_row(dim), "<u4", "packed rows", finish
+
+
+class BinaryIndex(BinaryFilterMixin, PackedBitsSource, ResidentIndex):
+    """Exact Hamming top-k over rows binarised by `quantizer` (default ``BinaryQuantizer(0.0)``) under `distance`
+    (default Manhattan: with the default quantizer, D is the Hamming count)."""
 
     def _setup(self, a: np.ndarray, kind: int, quantizer, distance, dim: int | None = None) -> None:
         self._quantizer = BinaryQuantizer(0.0) if quantizer is None else quantizer
@@ -114,37 +139,12 @@ class BinaryIndex(BinaryFilterMixin, ResidentIndex):
     def _check_dim(self, d: int, what: str) -> None:
         _check_params(d, self._quantizer, self._distance)
 
-    @property
-    def quantizer(self) -> BinaryQuantizer:
-        return self._quantizer
-
     def __repr__(self) -> str:
         return f"BinaryIndex(n={self._n}, dim={self._dim}, quantizer={self._quantizer!r}, distance={self._distance!r})"
 
     def _make_handle(self) -> "_lib.Binary":
         q = self._quantizer
         return _lib.Binary(self._src, self._kind, self._n, self._dim, q.threshold, q.low, q.high, self._distance.metric)
-
-    def _add_form(self):
-        return "add", np.float32, (_lib.BINARY_F32,)  # float32 rows, binarised on the device by the quantizer's rule
-
-    def add_codes(self, codes) -> np.ndarray:
-        """append u8 BQ codes (b, dim), bit = code >= high (``from_codes``'s form); returns their ids uint32 (b,)"""
-        a = self._added(codes, np.uint8, "codes")
-        return self._append("add", a, a.shape[0], _lib.BINARY_U8)
-
-    def add_packed(self, words) -> np.ndarray:
-        """append packed rows uint32 (b, ceil(dim / 32)) in the index layout, pad bits zero (``from_packed``'s form);
-        returns their ids uint32 (b,)"""
-        a = self._added(words, np.uint32, "words", words_per_row(self._dim))
-        if not _pad_ok(a, self._dim):
-            raise InvalidParameter("words", f"a row has a pad bit (dimension >= {self._dim}) set")
-        return self._append("add", a, a.shape[0], _lib.BINARY_PACKED)
-
-    def add_packed_device(self, dev_words: int, n: int) -> np.ndarray:
-        """``add_packed`` with the words [n][ceil(dim / 32)] at a device pointer (4-byte aligned); a pad bit set is an
-        FfiError (ERR_INVALID_INPUT) that leaves the index as it was.  Returns their ids."""
-        return self._append_device("add_device", dev_words, n, _lib.BINARY_PACKED)
 
     def search(self, queries, topk: int = 10, *, rerank=None, candidates=None):
         """(nq, d) float32 queries -> (indices uint32 (nq, topk), distances float32 (nq, topk)), nearest first.
@@ -187,49 +187,18 @@ class BinaryIndex(BinaryFilterMixin, ResidentIndex):
         """the packed rows, uint32 (n, ceil(dim / 32)), from the device"""
         return self._index().packed()
 
-    def _host_words(self) -> np.ndarray:
-        if self._ix is not None:
-            return self._ix.packed()
-        if self._kind == _lib.BINARY_PACKED:
-            return self._src
-        if self._kind == _lib.BINARY_U8:
-            return pack_bits(self._src >= np.uint8(self._quantizer.high))
-        return pack_bits(self._src >= np.float32(self._quantizer.threshold))
-
     # -- file -------------------------------------------------------------------------------
     def save(self, path) -> None:
         q = self._quantizer
-        with open(path, "wb") as f:
-            f.write(_HEADER.pack(MAGIC, self._distance.metric, self._dim, np.float32(q.threshold), q.low, q.high, self._n))
-            f.write(np.ascontiguousarray(self._host_words(), dtype="<u4").tobytes())
+        write_index_file(path, _HEADER.pack(MAGIC, self._distance.metric, self._dim, np.float32(q.threshold), q.low, q.high,
+                                            self._n), self._host_words())
 
     @classmethod
     def load(cls, path) -> "BinaryIndex":
         """read a VQBINIX1 file; every field is checked here, before anything can reach the device"""
-        with open(path, "rb") as f:
-            head = f.read(_HEADER.size)
-            if len(head) != _HEADER.size:
-                raise InvalidData("truncated binary index header")
-            magic, metric, dim, thr, low, high, n = _HEADER.unpack(head)
-            if magic != MAGIC:
-                raise InvalidData("not a VQBINIX1 file")
+        def fields(metric, dim, thr, low, high, n):
             if metric not in _METRICS:
                 raise InvalidParameter("distance", f"metric id {metric} is not squared_euclidean, euclidean or manhattan")
-            if not 1 <= dim <= MAX_DIM:
-                raise InvalidParameter("dim", f"must be between 1 and {MAX_DIM}, got {dim}")
-            if not 1 <= n < 1 << 32:
-                raise InvalidData(f"row count {n} is outside [1, 2^32)")
-            if low > 255 or high > 255:
-                raise InvalidParameter("low/high", f"must fit in u8, got {low} / {high}")
-            quantizer = BinaryQuantizer(float(thr), low, high)  # the reference's own checks
-            w = words_per_row(dim)
-            raw = f.read(n * w * 4)
-            if len(raw) != n * w * 4:
-                raise InvalidData("truncated packed rows")
-            if f.read(1):
-                raise InvalidData("trailing bytes after the packed rows")
-        words = np.frombuffer(raw, dtype="<u4").astype(np.uint32).reshape(n, w)
-        if not _pad_ok(words, dim):
-            raise InvalidData(f"a row has a pad bit (dimension >= {dim}) set")
-        names = {_lib.SQUARED_EUCLIDEAN: "squared_euclidean", _lib.EUCLIDEAN: "euclidean", _lib.MANHATTAN: "manhattan"}
-        return cls.from_packed(words, dim, quantizer, Distance(names[metric]))
+            return cls._file_payload(metric, dim, thr, low, high, n)
+
+        return read_index_file(path, _HEADER, MAGIC, "binary index", fields)

@@ -18,13 +18,8 @@ _NAMES = {
     "cosine_unclamped": _lib.COSINE_UNCLAMPED,
     "cosine_simd": _lib.COSINE_UNCLAMPED,
 }
-_CANON = {
-    _lib.EUCLIDEAN: "euclidean",
-    _lib.SQUARED_EUCLIDEAN: "squared_euclidean",
-    _lib.MANHATTAN: "manhattan",
-    _lib.COSINE: "cosine",
-    _lib.COSINE_UNCLAMPED: "cosine_unclamped",
-}
+# the canonical name of every metric id (_lib.SQUARED_EUCLIDEAN .. _lib.COSINE_UNCLAMPED), the table of every index file
+METRIC_NAMES = ("squared_euclidean", "euclidean", "manhattan", "cosine", "cosine_unclamped")
 
 
 class Distance:
@@ -62,7 +57,7 @@ class Distance:
 
     def name(self) -> str:
         """``Distance::name`` (src/core/distance.rs:21-28)"""
-        return _CANON[self.metric]
+        return METRIC_NAMES[self.metric]
 
     def compute(self, a, b) -> float:
         """Distance between two vectors (``Distance::compute``, src/core/distance.rs:48-64).
@@ -78,7 +73,7 @@ class Distance:
         return float(pairwise_distance(self.metric, a[None, :], b[None, :])[0])
 
     def __repr__(self) -> str:
-        return f"Distance('{_CANON[self.metric]}')"
+        return f"Distance('{METRIC_NAMES[self.metric]}')"
 
     def __eq__(self, other) -> bool:
         return isinstance(other, Distance) and other.metric == self.metric

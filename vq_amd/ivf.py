@@ -31,17 +31,14 @@ import struct
 import numpy as np
 
 from . import _lib
-from ._resident_common import _allowed
-from ._ivf_common import (MAX_NLIST, MAX_PROBE, MAX_TOPK, PAD_ID, IVFIndexBase, _Reader,  # noqa: F401  (re-exported)
-                          _check_distance, _check_file_lists, _check_nlist, _coarse_array, _count, _nearest_lists,
-                          _train_coarse)
-from .distance import Distance
+from ._ivf_common import (MAX_NLIST, MAX_PROBE, MAX_TOPK, PAD_ID, IVFFile, IVFIndexBase,  # noqa: F401  (re-exported)
+                          _check_distance, _check_nlist, _coarse_array, _nearest_lists, _train_coarse, sizes_ok)
+from ._resident_common import _allowed, _nq
+from .distance import METRIC_NAMES, Distance
 from .errors import DimensionMismatch, InvalidParameter
 
 MAGIC = b"VQIVFPQ1"
 MAGIC_RESIDUAL = b"VQIVFRP1"
-_HEADER = struct.Struct("<8sIIIIIIQ")
-_METRIC_NAMES = ["squared_euclidean", "euclidean", "manhattan"]
 MAX_TABLE = 38400  # m * k: one query's ADC table in the LDS (include/vqhip.h)
 
 
@@ -80,10 +77,9 @@ class IVFPQIndex(IVFIndexBase):
             raise InvalidParameter("residual", f"must be a bool, got {type(residual).__name__}")
         distance = distance if distance is not None else Distance.euclidean()
         coarse, self._codebooks = _check_shape(coarse_centroids, codebooks, distance)
-        self._init_lists(coarse, distance)
-        self._residual = bool(residual)
         m, k = self._codebooks.shape[:2]
-        self._codes = np.empty((0, m), _code_dtype(k))
+        self._init_lists(coarse, distance, np.empty((0, m), _code_dtype(k)))
+        self._residual = bool(residual)
 
     # -- shape ------------------------------------------------------------------------------
     @property
@@ -106,7 +102,7 @@ class IVFPQIndex(IVFIndexBase):
     @property
     def codes(self) -> np.ndarray:
         """(n, m): every row's codes, in row order"""
-        return self._codes
+        return self._host
 
     def __repr__(self) -> str:
         return (f"IVFPQIndex(n={len(self)}, nlist={self.nlist}, dim={self.dim}, m={self.m}, k={self.k}, "
@@ -149,36 +145,15 @@ class IVFPQIndex(IVFIndexBase):
 
     def add_codes(self, list_ids, codes) -> np.ndarray:
         """append rows given as list ids (n,) < nlist and codes (n, m) < k; returns the new row ids"""
-        lid = np.asarray(list_ids)
-        c = np.asarray(codes)
-        if lid.ndim != 1:
-            raise InvalidParameter("list_ids", "must be a 1D array (n,)")
-        if c.ndim != 2 or c.shape[1] != self.m:
-            raise InvalidParameter("codes", f"must have shape (n, {self.m})")
-        if c.shape[0] != lid.shape[0]:
-            raise DimensionMismatch(lid.shape[0], c.shape[0])
-        self._check_list_ids(lid)
+        lid, c = self._add_shape(list_ids, codes, "codes", self.m, shape_only=True)
+        self._check_list_ids(lid)  # (the halves of _add_lists: the codes' own check stands between them)
         if c.size and (c.dtype.kind not in "iu" or int(c.min()) < 0 or int(c.max()) >= self.k):
             raise InvalidParameter("codes", f"must be integers in [0, {self.k})")
         self._check_room(lid.shape[0], "codes")
-        lid = np.ascontiguousarray(lid, dtype=np.uint32)
-        c = np.ascontiguousarray(c, dtype=_code_dtype(self.k))
-        if self._ix is not None and lid.size:
-            self._ix.add(lid, c)
-        self._codes = np.concatenate([self._codes, c])
-        return self._appended(lid)
+        return self._append(np.ascontiguousarray(lid, dtype=np.uint32), np.ascontiguousarray(c, dtype=_code_dtype(self.k)))
 
-    def _removed(self, kept: np.ndarray) -> None:
-        self._codes = self._codes[kept]
-
-    def _handle(self) -> "_lib.IVFPQ":
-        if self._ix is None:
-            ix = _lib.IVFPQ(self._coarse, self._codebooks, self._distance.metric,
-                            _lib.IVF_RESIDUAL if self._residual else 0)
-            if len(self):
-                ix.add(self._lists, self._codes)
-            self._ix = ix
-        return self._ix
+    def _new_handle(self) -> "_lib.IVFPQ":
+        return _lib.IVFPQ(self._coarse, self._codebooks, self._distance.metric, _lib.IVF_RESIDUAL if self._residual else 0)
 
     # -- filtered search ----------------------------------------------------------------------
     def masked_search(self, queries, allowed, topk: int = 10, nprobe: int = 8, *, rerank=None, candidates: int | None = None):
@@ -203,48 +178,31 @@ class IVFPQIndex(IVFIndexBase):
         pointer (4-byte aligned)"""
         p = self._nprobe(nprobe)
         t = self._topk(topk)
-        n_q = _count(nq, "nq")
-        if n_q < 0 or n_q >= 1 << 32:
-            raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
+        n_q = _nq(nq)
         if dev_allowed is None:
             raise InvalidParameter("dev_allowed", "must be a device pointer, got None")
         self._handle().search_masked_device(int(dev_queries), n_q, p, t, int(dev_allowed), int(dev_idx), int(dev_dist))
 
     # -- file -------------------------------------------------------------------------------
-    def save(self, path) -> None:
-        with open(path, "wb") as f:
-            magic = MAGIC_RESIDUAL if self._residual else MAGIC
-            f.write(_HEADER.pack(magic, self._distance.metric, self.dim, self.nlist, self.m, self.k, 0, len(self)))
-            f.write(self._coarse.astype("<f4").tobytes())
-            f.write(self._codebooks.astype("<f4").tobytes())
-            f.write(self._lists.astype("<u4").tobytes())
-            f.write(self._codes.astype(_code_dtype(self.k)).tobytes())
+    _HEADER, _MAGICS = struct.Struct("<8sIIIIIIQ"), (MAGIC, MAGIC_RESIDUAL)
+
+    def _header(self) -> tuple:
+        magic = MAGIC_RESIDUAL if self._residual else MAGIC
+        return magic, self._distance.metric, self.dim, self.nlist, self.m, self.k, 0, len(self)
+
+    def _file_extra(self) -> tuple:
+        return (self._codebooks,)
 
     @classmethod
-    def load(cls, path) -> "IVFPQIndex":
-        """read a VQIVFPQ1 (non-residual) or VQIVFRP1 (residual) file; every range is checked here, before anything can
-        reach the device"""
-        with open(path, "rb") as f:
-            head = f.read(_HEADER.size)
-            if len(head) != _HEADER.size:
-                raise ValueError("truncated index header")
-            magic, metric, dim, nlist, m, k, reserved, n = _HEADER.unpack(head)
-            if magic not in (MAGIC, MAGIC_RESIDUAL):
-                raise ValueError("not a VQIVFPQ1 or VQIVFRP1 file")
-            if (metric >= len(_METRIC_NAMES) or reserved != 0 or not 1 <= nlist <= MAX_NLIST or m == 0 or k == 0
-                    or k > 65536 or m * k > MAX_TABLE or dim == 0 or dim % m != 0 or n >= 1 << 32):
-                raise ValueError("corrupt index header")
-            sd = dim // m
-            r = _Reader(f)
-            coarse = r.block(nlist * dim, "<f4", "coarse centroids").reshape(nlist, dim)
-            cb = r.block(m * k * sd, "<f4", "codebooks").reshape(m, k, sd)
-            lists = r.lists(n)
-            codes = r.block(n * m, _code_dtype(k), "codes").reshape(n, m)
-            r.end("codes")
-        _check_file_lists(lists, nlist)
-        if n and int(codes.max()) >= k:
-            raise ValueError(f"corrupt index: a code is outside [0, {k})")
-        self = cls(coarse, cb, Distance(_METRIC_NAMES[metric]), residual=magic == MAGIC_RESIDUAL)
-        self._lists = lists.astype(np.uint32)
-        self._codes = codes.astype(_code_dtype(k))
-        return self
+    def _file(cls, magic, metric, dim, nlist, m, k, reserved, n) -> IVFFile:
+        if (metric > _lib.MANHATTAN or reserved != 0 or not sizes_ok(dim, nlist, n) or m == 0 or k == 0 or k > 65536
+                or m * k > MAX_TABLE or dim % m != 0):
+            raise ValueError("corrupt index header")
+
+        def check(codes):
+            if n and int(codes.max()) >= k:
+                raise ValueError(f"corrupt index: a code is outside [0, {k})")
+
+        return IVFFile(dim, nlist, n, (_code_dtype(k), m, "codes"),
+                       lambda coarse, cb: cls(coarse, cb, Distance(METRIC_NAMES[metric]), residual=magic == MAGIC_RESIDUAL),
+                       extra=(((m, k, dim // m), "codebooks"),), check=check)

@@ -42,20 +42,17 @@ import numpy as np
 
 from . import _lib
 from ._binary_filter import IVFBinaryFilterMixin
-from ._ivf_common import (MAX_NLIST, IVFIndexBase, _count, _Reader, _check_coarse, _check_distance, _check_file_lists,
-                          _train_coarse)
-from ._resident_common import DEFAULT_MAX_RESULTS, _hamming_radii, _max_results
+from ._ivf_common import MAX_NLIST, IVFEncodedBase, IVFFile, _check_coarse, _check_distance, _train_coarse
+from ._resident_common import DEFAULT_MAX_RESULTS, _hamming_radii, _max_results, _nq
 from .binary import MAX_DIM, _check_params, _pad_ok, pack_bits, words_per_row
 from .bq import BinaryQuantizer
-from .distance import Distance
-from .errors import DimensionMismatch, InvalidParameter
+from .distance import METRIC_NAMES, Distance
+from .errors import InvalidParameter
 
 MAGIC = b"VQIVFBN1"
-_HEADER = struct.Struct("<8sIIIIfIIQ")
-_METRIC_NAMES = ["squared_euclidean", "euclidean", "manhattan", "cosine", "cosine_unclamped"]
 
 
-class IVFBinaryIndex(IVFBinaryFilterMixin, IVFIndexBase):
+class IVFBinaryIndex(IVFBinaryFilterMixin, IVFEncodedBase):
     """coarse centroids (nlist, dim) + BinaryQuantizer (default ``BinaryQuantizer(0.0)``) + distance (default Manhattan)
     + coarse_distance (default Euclidean), and the rows added to it as packed words"""
 
@@ -68,10 +65,9 @@ class IVFBinaryIndex(IVFBinaryFilterMixin, IVFIndexBase):
         coarse_distance = _check_distance(coarse_distance)
         coarse = _check_coarse(coarse_centroids)
         _check_params(coarse.shape[1], quantizer, distance)
-        self._init_lists(coarse, distance)
+        self._init_lists(coarse, distance, np.empty((0, words_per_row(coarse.shape[1])), np.uint32))
         self._coarse_distance = coarse_distance
         self._quantizer = quantizer
-        self._host_words = np.empty((0, words_per_row(self.dim)), np.uint32)  # until the handle exists: it then holds the only copy
 
     # -- shape ------------------------------------------------------------------------------
     @property
@@ -85,7 +81,7 @@ class IVFBinaryIndex(IVFBinaryFilterMixin, IVFIndexBase):
 
     def packed(self) -> np.ndarray:
         """(n, ceil(dim / 32)) uint32: every row's words, in row order"""
-        return self._host_words if self._ix is None else self._ix.packed()
+        return self._stored()
 
     def __repr__(self) -> str:
         return (f"IVFBinaryIndex(n={len(self)}, nlist={self.nlist}, dim={self.dim}, quantizer={self._quantizer!r}, "
@@ -105,75 +101,29 @@ class IVFBinaryIndex(IVFBinaryFilterMixin, IVFIndexBase):
     def _assign_metric(self) -> int:
         return self._coarse_distance.metric
 
-    def _check_add(self, list_ids, a, what: str, width: int):
-        lid = np.asarray(list_ids)
-        a = np.asarray(a)
-        if lid.ndim != 1:
-            raise InvalidParameter("list_ids", "must be a 1D array (n,)")
-        if a.ndim != 2:
-            raise InvalidParameter(what, f"must have shape (n, {width})")
-        if a.shape[1] != width:
-            raise DimensionMismatch(width, a.shape[1])
-        if a.shape[0] != lid.shape[0]:
-            raise DimensionMismatch(lid.shape[0], a.shape[0])
-        self._check_list_ids(lid)
-        self._check_room(lid.shape[0], what)
-        return np.ascontiguousarray(lid, dtype=np.uint32), a
-
-    def add_rows(self, list_ids, rows) -> np.ndarray:
-        """pack rows (n, dim) floating point, as float32, on the device (bit = x >= threshold) and append the words into
-        the lists list_ids (n,) < nlist; returns the new row ids"""
-        lid, r = self._check_add(list_ids, rows, "rows", self.dim)
-        if r.dtype.kind != "f":
-            raise InvalidParameter("rows", f"must be floating point, got {r.dtype}")
-        if lid.size:
-            with np.errstate(over="ignore"):
-                self._handle().add_rows(lid, np.ascontiguousarray(r, dtype=np.float32))
-        return self._appended(lid)
-
     def add_codes(self, list_ids, codes) -> np.ndarray:
         """append rows given as list ids (n,) < nlist and BQ codes (n, dim) uint8 (bit = code >= high); returns the new
         row ids"""
-        lid, c = self._check_add(list_ids, codes, "codes", self.dim)
+        lid, c = self._add_front(list_ids, codes, "codes", self.dim)
         if c.dtype != np.uint8:
             raise InvalidParameter("codes", f"dtype must be uint8, got {c.dtype}")
-        c = np.ascontiguousarray(c)
-        if self._ix is not None:
-            if lid.size:
-                self._ix.add_codes(lid, c)
-        else:
-            self._host_words = np.concatenate([self._host_words, pack_bits(c >= np.uint8(self._quantizer.high))])
-        return self._appended(lid)
+        return self._append(lid, np.ascontiguousarray(c), "add_codes", lambda c: pack_bits(c >= np.uint8(self._quantizer.high)))
 
     def add_packed(self, list_ids, words) -> np.ndarray:
         """append rows given as list ids (n,) < nlist and packed words (n, ceil(dim / 32)) uint32 in the index layout, pad
         bits zero; returns the new row ids"""
-        lid, w = self._check_add(list_ids, words, "words", words_per_row(self.dim))
+        lid, w = self._add_front(list_ids, words, "words", words_per_row(self.dim))
         if w.dtype != np.uint32:
             raise InvalidParameter("words", f"dtype must be uint32, got {w.dtype}")
-        w = np.ascontiguousarray(w)
         if not _pad_ok(w, self.dim):
             raise InvalidParameter("words", f"a row has a pad bit (dimension >= {self.dim}) set")
-        if self._ix is not None:
-            if lid.size:
-                self._ix.add_packed(lid, w)
-        else:
-            self._host_words = np.concatenate([self._host_words, w])
-        return self._appended(lid)
+        return self._append(lid, np.ascontiguousarray(w))
 
-    def _removed(self, kept: np.ndarray) -> None:
-        if self._ix is None:  # (else the handle holds the only copy)
-            self._host_words = self._host_words[kept]
+    _UPLOAD, _READ_BACK = "add_packed", "packed"
 
-    def _handle(self) -> "_lib.IVFBin":
-        if self._ix is None:
-            q = self._quantizer
-            ix = _lib.IVFBin(self._coarse, q.threshold, q.low, q.high, self._distance.metric, self._coarse_distance.metric)
-            if len(self):
-                ix.add_packed(self._lists, self._host_words)
-            self._ix = ix
-            self._host_words = None
-        return self._ix
+    def _new_handle(self) -> "_lib.IVFBin":
+        q = self._quantizer
+        return _lib.IVFBin(self._coarse, q.threshold, q.low, q.high, self._distance.metric, self._coarse_distance.metric)
 
     # -- range search ----------------------------------------------------------------------
     def hamming_range_search(self, queries, radius, nprobe: int = 8, max_results: int = DEFAULT_MAX_RESULTS):
@@ -195,57 +145,34 @@ class IVFBinaryIndex(IVFBinaryFilterMixin, IVFIndexBase):
                                     max_results: int = DEFAULT_MAX_RESULTS) -> "_lib.RangeResult":
         """`hamming_range_search` with the queries [nq][dim] f32 at a device pointer (4-byte aligned) and the result left
         on the device: a RangeResult (.total, .lims, .device_pointers(), .read()).  Returns when the result is complete."""
-        n_q = _count(nq, "nq")
-        if n_q < 0 or n_q >= 1 << 32:
-            raise InvalidParameter("nq", f"must be in [0, 2^32), got {n_q}")
+        n_q = _nq(nq)
         r = _hamming_radii(radius, n_q)
         p = self._nprobe(nprobe)
         m = _max_results(max_results)
         return self._handle().hamming_range_search_device(int(dev_queries), n_q, p, r, m)
 
-    def close(self) -> None:
-        """release the handle and its device state (the next probe or search builds it again); the words stay"""
-        if self._ix is not None:
-            self._host_words = self._ix.packed()
-            super().close()
-
     # -- file -------------------------------------------------------------------------------
-    def save(self, path) -> None:
+    _HEADER, _MAGICS = struct.Struct("<8sIIIIfIIQ"), (MAGIC,)
+
+    def _header(self) -> tuple:
         q = self._quantizer
-        with open(path, "wb") as f:
-            f.write(_HEADER.pack(MAGIC, self._distance.metric, self._coarse_distance.metric, self.dim, self.nlist,
-                                 np.float32(q.threshold), q.low, q.high, len(self)))
-            f.write(self._coarse.astype("<f4").tobytes())
-            f.write(self._lists.astype("<u4").tobytes())
-            f.write(np.ascontiguousarray(self.packed(), dtype="<u4").tobytes())
+        return (MAGIC, self._distance.metric, self._coarse_distance.metric, self.dim, self.nlist, np.float32(q.threshold), q.low,
+                q.high, len(self))
 
     @classmethod
-    def load(cls, path) -> "IVFBinaryIndex":
-        """read a VQIVFBN1 file; every field and every pad bit is checked here, before anything can reach the device"""
-        with open(path, "rb") as f:
-            head = f.read(_HEADER.size)
-            if len(head) != _HEADER.size:
-                raise ValueError("truncated index header")
-            magic, metric, cmetric, dim, nlist, thr, low, high, n = _HEADER.unpack(head)
-            if magic != MAGIC:
-                raise ValueError("not a VQIVFBN1 file")
-            if (metric > _lib.MANHATTAN or cmetric >= len(_METRIC_NAMES) or not 1 <= nlist <= MAX_NLIST or not 1 <= dim <= MAX_DIM
-                    or n >= 1 << 32 or low > 255 or high > 255):
-                raise ValueError("corrupt index header")
-            try:
-                quantizer = BinaryQuantizer(float(thr), low, high)  # the reference's own checks
-            except (InvalidParameter, ValueError, OverflowError) as e:
-                raise ValueError(f"corrupt index header: {e}") from None
-            w = words_per_row(dim)
-            r = _Reader(f)
-            coarse = r.block(nlist * dim, "<f4", "coarse centroids").reshape(nlist, dim)
-            lists = r.lists(n)
-            words = r.block(n * w, "<u4", "words").astype(np.uint32).reshape(n, w)
-            r.end("words")
-        _check_file_lists(lists, nlist)
-        if not _pad_ok(words, dim):
-            raise ValueError(f"corrupt index: a row has a pad bit (dimension >= {dim}) set")
-        self = cls(coarse, quantizer, Distance(_METRIC_NAMES[metric]), Distance(_METRIC_NAMES[cmetric]))
-        self._lists = lists.astype(np.uint32)
-        self._host_words = words
-        return self
+    def _file(cls, magic, metric, cmetric, dim, nlist, thr, low, high, n) -> IVFFile:
+        if (metric > _lib.MANHATTAN or cmetric >= len(METRIC_NAMES) or not 1 <= nlist <= MAX_NLIST or not 1 <= dim <= MAX_DIM
+                or n >= 1 << 32 or low > 255 or high > 255):
+            raise ValueError("corrupt index header")
+        try:
+            quantizer = BinaryQuantizer(float(thr), low, high)  # the reference's own checks
+        except (InvalidParameter, ValueError, OverflowError) as e:
+            raise ValueError(f"corrupt index header: {e}") from None
+
+        def check(words):
+            if not _pad_ok(words, dim):
+                raise ValueError(f"corrupt index: a row has a pad bit (dimension >= {dim}) set")
+
+        return IVFFile(dim, nlist, n, ("<u4", words_per_row(dim), "words"),
+                       lambda coarse: cls(coarse, quantizer, Distance(METRIC_NAMES[metric]), Distance(METRIC_NAMES[cmetric])),
+                       check=check)

@@ -27,15 +27,13 @@ import struct
 import numpy as np
 
 from . import _lib
-from ._ivf_common import (MAX_NLIST, PAD_ID, IVFIndexBase, IVFRangeMixin, _Reader, _check_coarse, _check_distance,  # noqa: F401
-                          _check_file_lists, _train_coarse)  # (PAD_ID: re-exported)
+from ._ivf_common import (PAD_ID, IVFFile, IVFIndexBase, IVFRangeMixin, _check_coarse, _check_distance,  # noqa: F401
+                          _train_coarse, sizes_ok)  # (PAD_ID: re-exported)
 from ._ivf_filter import IVFFilterMixin
-from .distance import Distance
-from .errors import DimensionMismatch, InvalidParameter
+from .distance import METRIC_NAMES, Distance
+from .errors import InvalidParameter
 
 MAGIC = b"VQIVFFL1"
-_HEADER = struct.Struct("<8sIIIIQ")
-_METRIC_NAMES = ["squared_euclidean", "euclidean", "manhattan", "cosine", "cosine_unclamped"]
 _DTYPES = [np.dtype(np.float32), np.dtype(np.float16)]
 
 
@@ -54,9 +52,9 @@ class IVFFlatIndex(IVFFilterMixin, IVFRangeMixin, IVFIndexBase):
 
     def __init__(self, coarse_centroids, distance: Distance | None = None, dtype=np.float32):
         distance = _check_distance(distance)
-        self._init_lists(_check_coarse(coarse_centroids), distance)
+        coarse = _check_coarse(coarse_centroids)
         self._dtype = _row_dtype(dtype)
-        self._rows = np.empty((0, self.dim), self._dtype)
+        self._init_lists(coarse, distance, np.empty((0, coarse.shape[1]), self._dtype))
 
     # -- shape ------------------------------------------------------------------------------
     @property
@@ -66,7 +64,7 @@ class IVFFlatIndex(IVFFilterMixin, IVFRangeMixin, IVFIndexBase):
     @property
     def rows(self) -> np.ndarray:
         """(n, dim): every row as stored, in row order"""
-        return self._rows
+        return self._host
 
     def __repr__(self) -> str:
         return (f"IVFFlatIndex(n={len(self)}, nlist={self.nlist}, dim={self.dim}, dtype={self._dtype.name}, "
@@ -85,38 +83,16 @@ class IVFFlatIndex(IVFFilterMixin, IVFRangeMixin, IVFIndexBase):
     def add_rows(self, list_ids, rows) -> np.ndarray:
         """append rows (n, dim), converted to the index's dtype, into the lists list_ids (n,) < nlist; returns the new
         row ids"""
-        lid = np.asarray(list_ids)
-        r = np.asarray(rows)
-        if lid.ndim != 1:
-            raise InvalidParameter("list_ids", "must be a 1D array (n,)")
-        if r.ndim != 2:
-            raise InvalidParameter("rows", f"must have shape (n, {self.dim})")
-        if r.shape[1] != self.dim:
-            raise DimensionMismatch(self.dim, r.shape[1])
-        if r.shape[0] != lid.shape[0]:
-            raise DimensionMismatch(lid.shape[0], r.shape[0])
+        lid, r = self._add_shape(list_ids, rows, "rows", self.dim)
         if r.dtype.kind != "f":
             raise InvalidParameter("rows", f"must be floating point, got {r.dtype}")
-        self._check_list_ids(lid)
-        self._check_room(lid.shape[0], "rows")
-        lid = np.ascontiguousarray(lid, dtype=np.uint32)
+        lid = self._add_lists(lid, "rows")
         with np.errstate(over="ignore"):
             r = np.ascontiguousarray(r, dtype=self._dtype)
-        if self._ix is not None and lid.size:
-            self._ix.add(lid, r)
-        self._rows = np.concatenate([self._rows, r])
-        return self._appended(lid)
+        return self._append(lid, r)
 
-    def _removed(self, kept: np.ndarray) -> None:
-        self._rows = self._rows[kept]
-
-    def _handle(self) -> "_lib.IVFFlat":
-        if self._ix is None:
-            ix = _lib.IVFFlat(self._coarse, self._distance.metric, self._dtype)
-            if len(self):
-                ix.add(self._lists, self._rows)
-            self._ix = ix
-        return self._ix
+    def _new_handle(self) -> "_lib.IVFFlat":
+        return _lib.IVFFlat(self._coarse, self._distance.metric, self._dtype)
 
     # -- search -----------------------------------------------------------------------------
     def search(self, queries, topk: int = 10, nprobe: int = 8, allowed=None):
@@ -126,33 +102,14 @@ class IVFFlatIndex(IVFFilterMixin, IVFRangeMixin, IVFIndexBase):
         return super().search(queries, topk, nprobe, allowed=allowed)
 
     # -- file -------------------------------------------------------------------------------
-    def save(self, path) -> None:
-        with open(path, "wb") as f:
-            f.write(_HEADER.pack(MAGIC, self._distance.metric, self.dim, self.nlist, _DTYPES.index(self._dtype), len(self)))
-            f.write(self._coarse.astype("<f4").tobytes())
-            f.write(self._lists.astype("<u4").tobytes())
-            f.write(self._rows.astype(self._dtype.newbyteorder("<")).tobytes())
+    _HEADER, _MAGICS = struct.Struct("<8sIIIIQ"), (MAGIC,)
+
+    def _header(self) -> tuple:
+        return MAGIC, self._distance.metric, self.dim, self.nlist, _DTYPES.index(self._dtype), len(self)
 
     @classmethod
-    def load(cls, path) -> "IVFFlatIndex":
-        """read a VQIVFFL1 file; every range is checked here, before anything can reach the device"""
-        with open(path, "rb") as f:
-            head = f.read(_HEADER.size)
-            if len(head) != _HEADER.size:
-                raise ValueError("truncated index header")
-            magic, metric, dim, nlist, dtype, n = _HEADER.unpack(head)
-            if magic != MAGIC:
-                raise ValueError("not a VQIVFFL1 file")
-            if (metric >= len(_METRIC_NAMES) or dtype >= len(_DTYPES) or not 1 <= nlist <= MAX_NLIST or dim == 0
-                    or n >= 1 << 32):
-                raise ValueError("corrupt index header")
-            r = _Reader(f)
-            coarse = r.block(nlist * dim, "<f4", "coarse centroids").reshape(nlist, dim)
-            lists = r.lists(n)
-            rows = r.block(n * dim, _DTYPES[dtype].newbyteorder("<"), "rows").reshape(n, dim)
-            r.end("rows")
-        _check_file_lists(lists, nlist)
-        self = cls(coarse, Distance(_METRIC_NAMES[metric]), _DTYPES[dtype])
-        self._lists = lists.astype(np.uint32)
-        self._rows = rows.astype(_DTYPES[dtype])
-        return self
+    def _file(cls, magic, metric, dim, nlist, dtype, n) -> IVFFile:
+        if metric >= len(METRIC_NAMES) or dtype >= len(_DTYPES) or not sizes_ok(dim, nlist, n):
+            raise ValueError("corrupt index header")
+        return IVFFile(dim, nlist, n, (_DTYPES[dtype].newbyteorder("<"), dim, "rows"),
+                       lambda coarse: cls(coarse, Distance(METRIC_NAMES[metric]), _DTYPES[dtype]))

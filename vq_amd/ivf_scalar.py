@@ -33,28 +33,35 @@ import struct
 import numpy as np
 
 from . import _lib
-from ._ivf_common import (MAX_NLIST, IVFIndexBase, IVFRangeMixin, _Reader, _check_coarse, _check_distance, _check_file_lists,
-                          _train_coarse)
+from ._ivf_common import IVFEncodedBase, IVFFile, IVFRangeMixin, _check_coarse, _check_distance, _train_coarse, sizes_ok
 from ._ivf_filter import IVFFilterMixin
-from .distance import Distance
-from .errors import DimensionMismatch, InvalidParameter
+from .distance import METRIC_NAMES, Distance
+from .errors import InvalidParameter
 from .sq import ScalarQuantizer
 
 MAGIC = b"VQIVFSQ1"
-_HEADER = struct.Struct("<8sIIIffIQ")
-_METRIC_NAMES = ["squared_euclidean", "euclidean", "manhattan", "cosine", "cosine_unclamped"]
 
 
-class IVFScalarIndex(IVFFilterMixin, IVFRangeMixin, IVFIndexBase):
+def file_quantizer(metric: int, dim: int, nlist: int, n: int, mn: float, mx: float, levels: int) -> ScalarQuantizer:
+    """the checks of the header fields that the files of ``IVFScalarIndex`` and ``IVFScalar4Index`` share; their quantizer"""
+    if metric >= len(METRIC_NAMES) or not sizes_ok(dim, nlist, n):
+        raise ValueError("corrupt index header")
+    try:
+        return ScalarQuantizer(mn, mx, levels)  # the reference's own checks
+    except InvalidParameter as e:
+        raise ValueError(f"corrupt index header: {e}") from None
+
+
+class IVFScalarIndex(IVFFilterMixin, IVFRangeMixin, IVFEncodedBase):
     """coarse centroids (nlist, dim) + ScalarQuantizer + distance, and the rows added to it as codes"""
 
     def __init__(self, coarse_centroids, quantizer: ScalarQuantizer, distance: Distance | None = None):
         if not isinstance(quantizer, ScalarQuantizer):
             raise InvalidParameter("quantizer", f"expected a ScalarQuantizer, got {type(quantizer).__name__}")
         distance = _check_distance(distance)
-        self._init_lists(_check_coarse(coarse_centroids), distance)
+        coarse = _check_coarse(coarse_centroids)
+        self._init_lists(coarse, distance, np.empty((0, coarse.shape[1]), np.uint8))
         self._quantizer = quantizer
-        self._host_codes = np.empty((0, self.dim), np.uint8)  # until the handle exists: it then holds the only copy
 
     # -- shape ------------------------------------------------------------------------------
     @property
@@ -64,7 +71,7 @@ class IVFScalarIndex(IVFFilterMixin, IVFRangeMixin, IVFIndexBase):
     @property
     def codes(self) -> np.ndarray:
         """(n, dim) uint8: every row's codes, in row order"""
-        return self._host_codes if self._ix is None else self._ix.codes()
+        return self._stored()
 
     def __repr__(self) -> str:
         return (f"IVFScalarIndex(n={len(self)}, nlist={self.nlist}, dim={self.dim}, quantizer={self._quantizer!r}, "
@@ -81,98 +88,28 @@ class IVFScalarIndex(IVFFilterMixin, IVFRangeMixin, IVFIndexBase):
         distance = distance if distance is not None else Distance.euclidean()
         return cls(_train_coarse(X, nlist, max_iters, distance, seed), quantizer, distance)
 
-    def _check_add(self, list_ids, a, what: str):
-        lid = np.asarray(list_ids)
-        a = np.asarray(a)
-        if lid.ndim != 1:
-            raise InvalidParameter("list_ids", "must be a 1D array (n,)")
-        if a.ndim != 2:
-            raise InvalidParameter(what, f"must have shape (n, {self.dim})")
-        if a.shape[1] != self.dim:
-            raise DimensionMismatch(self.dim, a.shape[1])
-        if a.shape[0] != lid.shape[0]:
-            raise DimensionMismatch(lid.shape[0], a.shape[0])
-        self._check_list_ids(lid)
-        self._check_room(lid.shape[0], what)
-        return np.ascontiguousarray(lid, dtype=np.uint32), a
-
-    def add_rows(self, list_ids, rows) -> np.ndarray:
-        """encode rows (n, dim) floating point, as float32, on the device (the codes of quantizer.quantize_batch) and
-        append the codes into the lists list_ids (n,) < nlist; returns the new row ids"""
-        lid, r = self._check_add(list_ids, rows, "rows")
-        if r.dtype.kind != "f":
-            raise InvalidParameter("rows", f"must be floating point, got {r.dtype}")
-        if lid.size:
-            with np.errstate(over="ignore"):
-                self._handle().add_rows(lid, np.ascontiguousarray(r, dtype=np.float32))
-        return self._appended(lid)
-
     def add_codes(self, list_ids, codes) -> np.ndarray:
         """append rows given as list ids (n,) < nlist and codes (n, dim) uint8 (every byte value is legal); returns the
         new row ids"""
-        lid, c = self._check_add(list_ids, codes, "codes")
+        lid, c = self._add_front(list_ids, codes, "codes", self.dim)
         if c.dtype != np.uint8:
             raise InvalidParameter("codes", f"dtype must be uint8, got {c.dtype}")
-        c = np.ascontiguousarray(c)
-        if self._ix is not None:
-            if lid.size:
-                self._ix.add_codes(lid, c)
-        else:
-            self._host_codes = np.concatenate([self._host_codes, c])
-        return self._appended(lid)
+        return self._append(lid, np.ascontiguousarray(c))
 
-    def _removed(self, kept: np.ndarray) -> None:
-        if self._ix is None:  # (else the handle holds the only copy)
-            self._host_codes = self._host_codes[kept]
+    _UPLOAD, _READ_BACK = "add_codes", "codes"
 
-    def _handle(self) -> "_lib.IVFSQ":
-        if self._ix is None:
-            q = self._quantizer
-            ix = _lib.IVFSQ(self._coarse, q._min, q._max, q.levels, self._distance.metric)
-            if len(self):
-                ix.add_codes(self._lists, self._host_codes)
-            self._ix = ix
-            self._host_codes = None
-        return self._ix
-
-    def close(self) -> None:
-        """release the handle and its device state (the next probe or search builds it again); the codes stay"""
-        if self._ix is not None:
-            self._host_codes = self._ix.codes()
-            super().close()
+    def _new_handle(self) -> "_lib.IVFSQ":
+        q = self._quantizer
+        return _lib.IVFSQ(self._coarse, q._min, q._max, q.levels, self._distance.metric)
 
     # -- file -------------------------------------------------------------------------------
-    def save(self, path) -> None:
+    _HEADER, _MAGICS = struct.Struct("<8sIIIffIQ"), (MAGIC,)
+
+    def _header(self) -> tuple:
         q = self._quantizer
-        with open(path, "wb") as f:
-            f.write(_HEADER.pack(MAGIC, self._distance.metric, self.dim, self.nlist, q._min, q._max, q.levels, len(self)))
-            f.write(self._coarse.astype("<f4").tobytes())
-            f.write(self._lists.astype("<u4").tobytes())
-            f.write(np.ascontiguousarray(self.codes, dtype=np.uint8).tobytes())
+        return MAGIC, self._distance.metric, self.dim, self.nlist, q._min, q._max, q.levels, len(self)
 
     @classmethod
-    def load(cls, path) -> "IVFScalarIndex":
-        """read a VQIVFSQ1 file; every range is checked here, before anything can reach the device"""
-        with open(path, "rb") as f:
-            head = f.read(_HEADER.size)
-            if len(head) != _HEADER.size:
-                raise ValueError("truncated index header")
-            magic, metric, dim, nlist, mn, mx, levels, n = _HEADER.unpack(head)
-            if magic != MAGIC:
-                raise ValueError("not a VQIVFSQ1 file")
-            if metric >= len(_METRIC_NAMES) or not 1 <= nlist <= MAX_NLIST or dim == 0 or n >= 1 << 32:
-                raise ValueError("corrupt index header")
-            try:
-                quantizer = ScalarQuantizer(mn, mx, levels)  # the reference's own checks
-            except InvalidParameter as e:
-                raise ValueError(f"corrupt index header: {e}") from None
-            r = _Reader(f)
-            coarse = r.block(nlist * dim, "<f4", "coarse centroids").reshape(nlist, dim)
-            lists = r.lists(n)
-            codes = r.block(n * dim, np.uint8, "codes").reshape(n, dim)
-            r.end("codes")
-        _check_file_lists(lists, nlist)
-        self = cls(coarse, quantizer, Distance(_METRIC_NAMES[metric]))
-        self._lists = lists.astype(np.uint32)
-        self._host_codes = codes.copy()
-        return self
+    def _file(cls, magic, metric, dim, nlist, mn, mx, levels, n) -> IVFFile:
+        quantizer = file_quantizer(metric, dim, nlist, n, mn, mx, levels)
+        return IVFFile(dim, nlist, n, (np.uint8, dim, "codes"), lambda coarse: cls(coarse, quantizer, Distance(METRIC_NAMES[metric])))

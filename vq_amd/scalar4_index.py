@@ -37,16 +37,15 @@ import struct
 import numpy as np
 
 from . import _lib
-from ._resident_common import ExactResidentIndex, _check_distance, _count
-from .distance import Distance
-from .errors import DimensionMismatch, InvalidData, InvalidParameter
+from ._resident_common import ExactResidentIndex, PackedSourceMixin, _check_distance, read_index_file, write_index_file
+from .distance import METRIC_NAMES, Distance
+from .errors import InvalidData, InvalidParameter
+from .scalar_index import file_quantizer
 from .sq import ScalarQuantizer
 
 MAGIC = b"VQSQ4IX1"
 MAX_LEVELS = 16
 _HEADER = struct.Struct("<8sQIIffI")  # magic, n, d, metric, min, max, levels
-_METRIC_NAMES = {_lib.SQUARED_EUCLIDEAN: "squared_euclidean", _lib.EUCLIDEAN: "euclidean", _lib.MANHATTAN: "manhattan",
-                 _lib.COSINE: "cosine", _lib.COSINE_UNCLAMPED: "cosine_unclamped"}
 
 
 def words_per_row(d: int) -> int:
@@ -66,9 +65,18 @@ def _codes_ok(codes: np.ndarray, what: str = "codes") -> None:
         raise InvalidParameter(what, f"a 4-bit code is at most 15, got {int(codes.max())}")
 
 
-class Scalar4Index(ExactResidentIndex):
+def _packed_dim(d: int) -> None:
+    if d < 1:
+        raise InvalidParameter("dim", f"must be at least 1, got {d}")
+
+
+class Scalar4Index(PackedSourceMixin, ExactResidentIndex):
     """Exact search over `rows` (n, d) float32, stored as the 4-bit codes of `quantizer` (``levels <= 16``), against
     float32 queries under `distance` (any metric, cosine included; default Euclidean)."""
+
+    _F32, _U8, _PACKED, _PAD = _lib.SQ4_F32, _lib.SQ4_U8, _lib.SQ4_PACKED, "nibble"
+    _words, _pad_ok = staticmethod(words_per_row), staticmethod(_pad_ok)
+    _packed_dim, _codes_ok = staticmethod(_packed_dim), staticmethod(_codes_ok)
 
     def __init__(self, rows, quantizer: ScalarQuantizer, distance: Distance | None = None):
         a = rows if isinstance(rows, np.ndarray) else np.asarray(rows)
@@ -90,21 +98,7 @@ class Scalar4Index(ExactResidentIndex):
     @classmethod
     def from_packed(cls, words, dim: int, quantizer: ScalarQuantizer, distance: Distance | None = None) -> "Scalar4Index":
         """uint32 (n, ceil(dim / 8)) packed rows in ``ScalarQuantizer.pack4_codes``' layout, pad nibbles zero"""
-        a = words if isinstance(words, np.ndarray) else np.asarray(words)
-        if a.dtype != np.uint32:
-            raise InvalidParameter("words", f"dtype must be uint32, got {a.dtype}")
-        d = _count(dim, "dim")
-        if a.ndim != 2:
-            raise ValueError("expected a 2D array (n, words)")
-        if d < 1:
-            raise InvalidParameter("dim", f"must be at least 1, got {d}")
-        if a.shape[1] != words_per_row(d):
-            raise DimensionMismatch(words_per_row(d), a.shape[1])
-        if not _pad_ok(a, d):
-            raise InvalidParameter("words", f"a row has a pad nibble (dimension >= {d}) set")
-        self = cls.__new__(cls)
-        self._setup(a, _lib.SQ4_PACKED, quantizer, distance, dim=d)
-        return self
+        return cls._from_packed(words, dim, quantizer, distance)
 
     def _setup(self, a: np.ndarray, kind: int, quantizer, distance, dim: int | None = None) -> None:
         if not isinstance(quantizer, ScalarQuantizer):
@@ -116,10 +110,6 @@ class Scalar4Index(ExactResidentIndex):
         self._kind = kind
         self._quantizer = quantizer
 
-    @property
-    def quantizer(self) -> ScalarQuantizer:
-        return self._quantizer
-
     def __repr__(self) -> str:
         return f"Scalar4Index(n={self._n}, dim={self._dim}, quantizer={self._quantizer!r}, distance={self._distance!r})"
 
@@ -127,32 +117,10 @@ class Scalar4Index(ExactResidentIndex):
         q = self._quantizer
         return _lib.SQ4Index(self._src, self._kind, self._n, self._dim, q._min, q._max, q.levels, self._distance.metric)
 
-    def _add_form(self):
-        return "add", np.float32, (_lib.SQ4_F32,)  # float32 rows, encoded and packed on the device as the constructor's
-
-    def add_codes(self, codes) -> np.ndarray:
-        """append u8 SQ codes (b, dim), each <= 15 (``from_codes``'s form); returns their ids uint32 (b,)"""
-        a = self._added(codes, np.uint8, "codes")
-        _codes_ok(a)
-        return self._append("add", a, a.shape[0], _lib.SQ4_U8)
-
-    def add_packed(self, words) -> np.ndarray:
-        """append packed rows uint32 (b, ceil(dim / 8)) in the index layout, pad nibbles zero (``from_packed``'s form);
-        returns their ids uint32 (b,)"""
-        a = self._added(words, np.uint32, "words", words_per_row(self._dim))
-        if not _pad_ok(a, self._dim):
-            raise InvalidParameter("words", f"a row has a pad nibble (dimension >= {self._dim}) set")
-        return self._append("add", a, a.shape[0], _lib.SQ4_PACKED)
-
     def add_codes_device(self, dev_codes: int, n: int) -> np.ndarray:
         """``add_codes`` with the codes [n][dim] at a device pointer; a code above 15 is an FfiError
         (ERR_INVALID_INPUT) that leaves the index as it was.  Returns their ids."""
         return self._append_device("add_device", dev_codes, n, _lib.SQ4_U8)
-
-    def add_packed_device(self, dev_words: int, n: int) -> np.ndarray:
-        """``add_packed`` with the words [n][ceil(dim / 8)] at a device pointer (4-byte aligned); a pad nibble set is an
-        FfiError (ERR_INVALID_INPUT) that leaves the index as it was.  Returns their ids."""
-        return self._append_device("add_device", dev_words, n, _lib.SQ4_PACKED)
 
     def packed(self) -> np.ndarray:
         """the packed rows, uint32 (n, ceil(dim / 8)): from the caller's array for an index built ``from_packed`` or
@@ -172,37 +140,22 @@ class Scalar4Index(ExactResidentIndex):
     # -- file -------------------------------------------------------------------------------
     def save(self, path) -> None:
         q = self._quantizer
-        words = self.packed()
-        with open(path, "wb") as f:
-            f.write(_HEADER.pack(MAGIC, self._n, self._dim, self._distance.metric, q._min, q._max, q.levels))
-            f.write(np.ascontiguousarray(words, dtype="<u4").tobytes())
+        write_index_file(path, _HEADER.pack(MAGIC, self._n, self._dim, self._distance.metric, q._min, q._max, q.levels),
+                         self.packed())
 
     @classmethod
     def load(cls, path) -> "Scalar4Index":
         """read a VQSQ4IX1 file; every field is checked here, before anything can reach the device"""
-        with open(path, "rb") as f:
-            head = f.read(_HEADER.size)
-            if len(head) != _HEADER.size:
-                raise InvalidData("truncated 4-bit scalar index header")
-            magic, n, dim, metric, mn, mx, levels = _HEADER.unpack(head)
-            if magic != MAGIC:
-                raise InvalidData("not a VQSQ4IX1 file")
-            if metric not in _METRIC_NAMES:
-                raise InvalidParameter("distance", f"unknown metric id {metric}")
-            if dim < 1:
-                raise InvalidParameter("dim", "must be at least 1")
-            if not 1 <= n < 1 << 32:
-                raise InvalidData(f"row count {n} is outside [1, 2^32)")
-            quantizer = ScalarQuantizer(mn, mx, levels)  # the reference's own checks
+        def fields(n, dim, metric, mn, mx, levels):
+            quantizer = file_quantizer(metric, dim, n, mn, mx, levels)
             if levels > MAX_LEVELS:
                 raise InvalidParameter("quantizer", f"levels {levels}: a 4-bit index holds at most {MAX_LEVELS}")
-            w = words_per_row(dim)
-            raw = f.read(n * w * 4)
-            if len(raw) != n * w * 4:
-                raise InvalidData("truncated packed rows")
-            if f.read(1):
-                raise InvalidData("trailing bytes after the packed rows")
-        words = np.frombuffer(raw, dtype="<u4").astype(np.uint32).reshape(n, w)
-        if not _pad_ok(words, dim):
-            raise InvalidData(f"a row has a pad nibble (dimension >= {dim}) set")
-        return cls.from_packed(words, dim, quantizer, Distance(_METRIC_NAMES[metric]))
+
+            def finish(words):
+                if not _pad_ok(words, dim):
+                    raise InvalidData(f"a row has a pad nibble (dimension >= {dim}) set")
+                return cls.from_packed(words, dim, quantizer, Distance(METRIC_NAMES[metric]))
+
+            return n, words_per_row(dim), "<u4", "packed rows", finish
+
+        return read_index_file(path, _HEADER, MAGIC, "4-bit scalar index", fields)

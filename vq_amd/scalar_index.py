@@ -30,15 +30,23 @@ import struct
 import numpy as np
 
 from . import _lib
-from .distance import Distance
-from ._resident_common import ExactResidentIndex, _check_distance
-from .errors import InvalidData, InvalidParameter
+from ._resident_common import ExactResidentIndex, _check_distance, check_file_rows, read_index_file, write_index_file
+from .distance import METRIC_NAMES, Distance
+from .errors import InvalidParameter
 from .sq import ScalarQuantizer
 
 MAGIC = b"VQSQIDX1"
 _HEADER = struct.Struct("<8sQIIffI")  # magic, n, d, metric, min, max, levels
-_METRIC_NAMES = {_lib.SQUARED_EUCLIDEAN: "squared_euclidean", _lib.EUCLIDEAN: "euclidean", _lib.MANHATTAN: "manhattan",
-                 _lib.COSINE: "cosine", _lib.COSINE_UNCLAMPED: "cosine_unclamped"}
+
+
+def file_quantizer(metric: int, dim: int, n: int, mn: float, mx: float, levels: int) -> ScalarQuantizer:
+    """the checks of the fields that the files of ``ScalarIndex`` and ``Scalar4Index`` share; their quantizer"""
+    if metric >= len(METRIC_NAMES):
+        raise InvalidParameter("distance", f"unknown metric id {metric}")
+    if dim < 1:
+        raise InvalidParameter("dim", "must be at least 1")
+    check_file_rows(n)
+    return ScalarQuantizer(mn, mx, levels)  # the reference's own checks
 
 
 class ScalarIndex(ExactResidentIndex):
@@ -101,32 +109,14 @@ class ScalarIndex(ExactResidentIndex):
     # -- file -------------------------------------------------------------------------------
     def save(self, path) -> None:
         q = self._quantizer
-        codes = self.codes()
-        with open(path, "wb") as f:
-            f.write(_HEADER.pack(MAGIC, self._n, self._dim, self._distance.metric, q._min, q._max, q.levels))
-            f.write(np.ascontiguousarray(codes, dtype=np.uint8).tobytes())
+        write_index_file(path, _HEADER.pack(MAGIC, self._n, self._dim, self._distance.metric, q._min, q._max, q.levels),
+                         self.codes())
 
     @classmethod
     def load(cls, path) -> "ScalarIndex":
         """read a VQSQIDX1 file; every field is checked here, before anything can reach the device"""
-        with open(path, "rb") as f:
-            head = f.read(_HEADER.size)
-            if len(head) != _HEADER.size:
-                raise InvalidData("truncated scalar index header")
-            magic, n, dim, metric, mn, mx, levels = _HEADER.unpack(head)
-            if magic != MAGIC:
-                raise InvalidData("not a VQSQIDX1 file")
-            if metric not in _METRIC_NAMES:
-                raise InvalidParameter("distance", f"unknown metric id {metric}")
-            if dim < 1:
-                raise InvalidParameter("dim", "must be at least 1")
-            if not 1 <= n < 1 << 32:
-                raise InvalidData(f"row count {n} is outside [1, 2^32)")
-            quantizer = ScalarQuantizer(mn, mx, levels)  # the reference's own checks
-            raw = f.read(n * dim)
-            if len(raw) != n * dim:
-                raise InvalidData("truncated codes")
-            if f.read(1):
-                raise InvalidData("trailing bytes after the codes")
-        codes = np.frombuffer(raw, dtype=np.uint8).reshape(n, dim)
-        return cls.from_codes(codes, quantizer, Distance(_METRIC_NAMES[metric]))
+        def fields(n, dim, metric, mn, mx, levels):
+            quantizer = file_quantizer(metric, dim, n, mn, mx, levels)
+            return n, dim, np.uint8, "codes", lambda codes: cls.from_codes(codes, quantizer, Distance(METRIC_NAMES[metric]))
+
+        return read_index_file(path, _HEADER, MAGIC, "scalar index", fields)

@@ -23,12 +23,10 @@ import struct
 
 import numpy as np
 
-from .distance import Distance
+from .distance import METRIC_NAMES, Distance
 
 MAGIC = b"VQPQIDX1"
 _HEADER = struct.Struct("<8sIIIIQ")
-# metric ids of include/vqhip.h in id order (4 = the simd build's cosine without the epsilon rule and the clamp)
-_METRIC_NAMES = ["squared_euclidean", "euclidean", "manhattan", "cosine", "cosine_unclamped"]
 
 
 def _code_dtype(k: int):
@@ -195,7 +193,7 @@ class PQIndex:
             magic, metric, dim, m, k, n = _HEADER.unpack(head)
             if magic != MAGIC:
                 raise ValueError("not a VQPQIDX1 file")
-            if m == 0 or k == 0 or k > 65536 or dim == 0 or dim % m != 0 or metric >= len(_METRIC_NAMES):
+            if m == 0 or k == 0 or k > 65536 or dim == 0 or dim % m != 0 or metric >= len(METRIC_NAMES):
                 raise ValueError("corrupt index header")
             sd = dim // m
             cb = np.frombuffer(f.read(m * k * sd * 4), dtype="<f4")
@@ -217,5 +215,5 @@ class PQIndex:
         self = cls.__new__(cls)  # (the codes, maybe a memmap, were checked above: not through _checked's copy)
         self._codebooks = cb.reshape(m, k, sd).astype(np.float32)
         self._codes = codes
-        self._distance = Distance(_METRIC_NAMES[metric])
+        self._distance = Distance(METRIC_NAMES[metric])
         return self
