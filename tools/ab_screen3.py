@@ -1,6 +1,7 @@
 """A/B of two library builds on the sub_dim-16 encode screen by row family (C2's shape: 1M x 128, m = 8, k = 256): uniform,
 N(0,1) and clustered rows -- encode time, the screen and re-check stages (HIP events), the re-checked fraction, the number
-of bf16 products of the screen that ran (0 on a build without the export) and a crc of the codes.
+of bf16 products of the screen that ran (0 on a build without the export) and a crc of the codes.  A family named
+`kind:sd` runs at that sub_dim instead (1M x 8 sd; `uniform:14`, `uniform:15`: the padded forms of the same screen).
     VQHIP_LIB_PATH=ab/libvqhip_base.so python tools/ab_screen3.py ; python tools/ab_screen3.py    (alternate a few times)"""
 import os, sys, time, zlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -9,11 +10,10 @@ import torch
 from vq_amd import _lib
 _lib.load(); _lib.set_device(0)
 tag = os.path.basename(os.environ.get("VQHIP_LIB_PATH", "new"))
-n, m, k, sd = 1_000_000, 8, 256, 16
-d = m * sd
+n, m, k = 1_000_000, 8, 256
 
 
-def rows(kind):
+def rows(kind, d):
     g = torch.Generator(device="cuda").manual_seed(66)
     if kind == "uniform":
         return torch.rand((n, d), generator=g, device="cuda")
@@ -24,8 +24,10 @@ def rows(kind):
     return centers[pick] + 0.05 * torch.randn((n, d), generator=g, device="cuda")
 
 
-def run(kind, reps=6, inner=25):
-    X = rows(kind).contiguous()
+def run(name, reps=6, inner=25):
+    kind, _, sd = name.partition(":")
+    d = m * int(sd or 16)
+    X = rows(kind, d).contiguous()
     torch.cuda.synchronize()
     ds = _lib.Dataset.from_device(X.data_ptr(), n, d, keepalive=X)
     km = _lib.KMeans(ds, m, k)
@@ -48,10 +50,10 @@ def run(kind, reps=6, inner=25):
     _lib.set_profiling(False)
     crc = zlib.crc32(np.ascontiguousarray(dcodes.cpu().numpy()).tobytes()) & 0xffffffff
     te_s = sorted(te)
-    print(f"{tag:20s} {kind:9s}: encode ms min {min(te):.4f} median {te_s[len(te_s) // 2]:.4f}  screen {ms_screen / calls:.4f} recheck {ms_recheck / calls:.4f}"
+    print(f"{tag:20s} {name:9s}: encode ms min {min(te):.4f} median {te_s[len(te_s) // 2]:.4f}  screen {ms_screen / calls:.4f} recheck {ms_recheck / calls:.4f}"
           f"  rechecked {rech} ({100.0 * rech / (n * m):.3f} %) products {prod} crc {crc:08x}", flush=True)
     enc.close(); km.close(); ds.close()
 
 
-for kind in (sys.argv[1:] or ["uniform", "normal", "clustered"]):
-    run(kind)
+for name in (sys.argv[1:] or ["uniform", "normal", "clustered", "uniform:14", "uniform:15"]):
+    run(name)

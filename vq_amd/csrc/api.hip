@@ -138,7 +138,7 @@ struct CodebookState {
             screen_bf16_x32_tiling(sd, k, &per, &x32_groups);
             const size_t tiles = (size_t)per * x32_groups;  // image padded to whole centroid groups
             VQ_TRY(prepA32.alloc((size_t)m * tiles * screen_bf16_x32_mfmas(sd) * 4 * 64 * 4));
-            if (encode_only && screen_bf16_three_products_supported(sd, k)) VQ_TRY(prepA32_3.alloc((size_t)m * tiles * 3 * 4 * 64 * 4));
+            if (encode_only && screen_bf16_three_products_supported(sd, k)) VQ_TRY(prepA32_3.alloc((size_t)m * tiles * 2 * 4 * 64 * 4));  // two operands per tile
             const uint32_t sdp = x32_padded_sd(sd);  // >= sd: the screen kernel's sub_dim (zero padding)
             VQ_TRY(cbc.alloc((size_t)m * k * sdp * 4));
             VQ_TRY(cen.alloc((size_t)m * (sdp + 4) * 4));

@@ -760,7 +760,9 @@ __host__ __device__ constexpr uint32_t x32p_acc_bytes_per_wave(int sd, int nt32)
 // Which reduce an instantiation of the pipelined screen runs: the number of column classes of the grid reduce, or 0
 // for the two tagged chains.  Chosen per instantiation from its register count (profiles/NOTES.md, "grid reduce").
 __host__ __device__ constexpr int x32p_grid_cols(int sd, bool acc, int npr, int pvw) {
-    if (npr == 3) return pvw == 2 ? 0 : 8;  // float2 row parts: either grid shape spills 48 bytes against 12
+    // float2 row parts stay on the tagged chains: either grid shape spilled there while the A image took 96 registers;
+    // at 64 the grid fits, but its untagged values would list other rows within 64 ulps of the margin than before
+    if (npr == 3) return pvw == 2 ? 0 : 8;
     if (sd == 8) return acc ? 4 : 8;        // fused update: 8 classes spill 40 bytes against 32, 4 classes 32
     return 0;                               // sub_dim 16 on six products: one wave, four reduce gaps (not built)
 }
@@ -787,8 +789,9 @@ __host__ __device__ constexpr int x32p_grid_cols(int sd, bool acc, int npr, int 
 // sub_dim 8 or 16, one centroid group.
 // NPR = term pairs per dimension.  6: the three truncated slices above.  3 (sub_dim 16, encode form, squared-L2 /
 // Euclidean): two ROUNDED slices per operand (split2_rne) and the products a1x1 + a2x1 + a1x2 -- MFMA f of a tile carries
-// pair f for the lane half's 8 dimensions, so b[0] and b[1] are the same registers (x1) and b[2] is x2; three MFMAs per
-// tile, a 96-register A image in VGPRs and two waves per SIMD, i.e. the sub_dim-8 kernel's MFMA and reduce structure.
+// pair f for the lane half's 8 dimensions, so b[0] and b[1] are the same registers (x1) and b[2] is x2, a[0] and a[2]
+// the same registers (a1) and a[1] is a2; three MFMAs per tile, a 64-register A image in VGPRs (the two slices once
+// each) and two waves per SIMD, i.e. the sub_dim-8 kernel's MFMA and reduce structure.
 // The screen only has to PROVE winners: half the matrix work is paid for by a wider margin (the dropped terms are
 // <= 773 u |a||x| per dimension instead of 8 u; the codebook's three-product coefficient sits in cen[sd + 2]) and so by
 // more rows in the exact re-check, which settles every code either way.  Slices that round to +-inf (|v| > 3.39e38)
@@ -868,16 +871,18 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
     uint32_t seg_count = 0;
 
     __shared__ __attribute__((aligned(16))) float lds_cn[kWavesPerBlock][NT32 * 32];
-    bf16x8 a[NT32][NMF];
+    // three products: the image holds the two slices once each (operand 0 = a1, 1 = a2); MFMA 2 reads a1 again (asel)
+    constexpr int NA = (NPR == 3) ? 2 : NMF;
+    bf16x8 a[NT32][NA];
     {
-        const uint32_t *base = prepA32 + (size_t)s * NT32 * NMF * 4 * 64 + lane;
+        const uint32_t *base = prepA32 + (size_t)s * NT32 * NA * 4 * 64 + lane;
 #pragma unroll
         for (int i = 0; i < NT32; ++i)
 #pragma unroll
-            for (int f = 0; f < NMF; ++f) {
+            for (int f = 0; f < NA; ++f) {
                 u32x4 v;
 #pragma unroll
-                for (int w = 0; w < 4; ++w) v[w] = base[((i * NMF + f) * 4 + w) * 64];
+                for (int w = 0; w < 4; ++w) v[w] = base[((i * NA + f) * 4 + w) * 64];
                 a[i][f] = __builtin_bit_cast(bf16x8, v);
             }
         const float *pc = prepCn + (size_t)s * cn_stride;
@@ -919,7 +924,9 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
     // rows in flight, TWO steps deep (1024 waves x 2 KB per step in flight is ~2 MB, what 1.1 TB/s needs at ~2 us of
     // latency; one step deep the wave waited 19 % of its time): at the top of step st, xn_[par ^ 1] holds step st + 1
     // (about to be consumed, then reloaded with st + 1 + kDeep) and xn_[par] step st + 2
-    // (two waves per SIMD: one step deep -- the partner wave covers the latency and the registers are short)
+    // (two waves per SIMD: one step deep -- the partner wave covers the latency.  The three-product form has had the
+    // registers for two steps since its A image shrank to 64, and two steps deep measured no faster there: 0.2436 ms
+    // against 0.2421 at C2, profiles/NOTES.md "two-operand A image")
     constexpr int kDeep = kTwo ? 1 : 2;
     // kept as the 16-byte vectors the loads return and consumed as such (x - mu on whole vectors): handed on as scalars,
     // the packed subtraction paired lanes 0 / 3 and 1 / 2 of a vector and the register copies that pairing needs were
@@ -968,20 +975,25 @@ __global__ __launch_bounds__(kBlock, x32_two_waves(SD, NT32, NPR) ? 2 : 1) void 
     // tile) stays in registers and enters as the C operand of the tile's first MFMA -- no LDS re-read of the
     // accumulator's initial value for them (4 ds_read_b128 and a wait per tile; every instruction of a lone wave costs
     // an issue slot of ~5 cycles, profiles/ubench/valu_issue.hip).  (C and D of an MFMA share their register class, so
-    // the 64 spare AGPRs cannot hold the other tiles' images.)  Two waves per SIMD (sub_dim 8): LDS for all tiles.
-    constexpr int kCnV = kTwo ? 0 : (ACC ? 4 : 6);
+    // the 64 spare AGPRs cannot hold the other tiles' images.)  Two waves per SIMD: LDS for all tiles at sub_dim 8; the
+    // three-product form keeps two tiles' images in the 32 of the registers its 64-register A image left over (8 of a
+    // step's 32 ds_read_b128 less) -- except with 4-byte row parts (PVW 1), where that spills 72 bytes.
+    constexpr int kCnV = kTwo ? ((NPR == 3 && PVW != 1) ? 2 : 0) : (ACC ? 4 : 6);
     f32x16 cnr[kCnV > 0 ? kCnV : 1];
 #pragma unroll
     for (int i = 0; i < kCnV; ++i) init_acc(cnr[i], i);
+    auto asel = [](int f) { return (NPR == 3 && f == 2) ? 0 : f; };  // three products: pairs 0 and 2 share a1
     auto mfma = [&](f32x16 &accv, int ti, int f, const bf16x8 &bv) {
+        const bf16x8 &av = a[ti][asel(f)];
         if (f == 0 && ti < kCnV) {  // D = A B + |c|^2 (register image), the chain then runs in place
-            asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(accv) : "a"(a[ti][f]), "v"(bv), "v"(cnr[ti]));
+            if constexpr (kTwo) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(accv) : "v"(av), "v"(bv), "v"(cnr[ti]));
+            else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(accv) : "a"(av), "v"(bv), "v"(cnr[ti]));
             return;
         }
         // two waves per SIMD: a kernel that names AGPRs gets the register file split 128 : 128, and this one needs ~165
-        // VGPRs next to the 96 of the A image -- all of it in VGPRs (256) instead of spilling through v_accvgpr moves
-        if constexpr (kTwo) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(accv) : "v"(a[ti][f]), "v"(bv));
-        else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(accv) : "a"(a[ti][f]), "v"(bv));
+        // VGPRs next to the A image -- all of it in VGPRs (256) instead of spilling through v_accvgpr moves
+        if constexpr (kTwo) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(accv) : "v"(av), "v"(bv));
+        else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(accv) : "a"(av), "v"(bv));
     };
 
     bf16x8 b[2][NMF];
@@ -2006,7 +2018,8 @@ bool screen_bf16_three_products_supported(uint32_t sd, uint32_t k) {
     return x32_padded_sd(sd) == 16 && per == 8 && groups == 1 && k >= 225 && k <= 256;
 }
 
-// prepA32_3: the two-slice image of the three-product form ([m][8][3][4][64]; squared-L2 / Euclidean), nullptr = none
+// prepA32_3: the two-slice image of the three-product form ([m][8][2][4][64]: operand 0 = slice 1, operand 1 = slice 2
+// of -2(c - mu), each once -- the third product reads slice 1 again; squared-L2 / Euclidean), nullptr = none
 int launch_prepare_bf16_x32(const CodebookView &v, uint32_t *prepA32, int cosine, float *cbc, float *cen,
                             float *cn32, hipStream_t stream, uint32_t *prepA32_3) {
     if (v.m == 0) return VQHIP_OK;
@@ -2034,8 +2047,8 @@ int launch_prepare_bf16_x32(const CodebookView &v, uint32_t *prepA32, int cosine
     }
     hipLaunchKernelGGL(k_prepare_bf16_x32, dim3(v.m, 16), dim3(256), 0, stream, src, v.m, v.k, cosine ? v.sd : sdp,
                        cosine ? v.sd : sdp, sdp, nt32, screen_bf16_x32_mfmas(v.sd), 6u, cosine, v.cnsqrt, prepA32);
-    if (prepA32_3 && !cosine)
-        hipLaunchKernelGGL(k_prepare_bf16_x32, dim3(v.m, 16), dim3(256), 0, stream, src, v.m, v.k, sdp, sdp, sdp, nt32, 3u, 3u, 0,
+    if (prepA32_3 && !cosine)  // two operands per tile: pairs 0 and 1 name slices 1 and 2 (sub_dim 16: one pair per operand)
+        hipLaunchKernelGGL(k_prepare_bf16_x32, dim3(v.m, 16), dim3(256), 0, stream, src, v.m, v.k, sdp, sdp, sdp, nt32, 2u, 3u, 0,
                            v.cnsqrt, prepA32_3);
     VQ_LAUNCH_CHECK("k_prepare_bf16_x32");
     return VQHIP_OK;

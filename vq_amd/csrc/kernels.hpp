@@ -39,7 +39,7 @@ struct CodebookView {
     const float *meta = nullptr;     // [m][4]            {max|c|, margin coefficient, -, -}
     const float *cnsqrt = nullptr;   // [m][k]            sqrt(sum c^2) (cosine's norm_b)
     const uint32_t *prepA32 = nullptr;  // [m][ceil(k/32)][NMF][4][64] same, 32x32x16 MFMA lane order
-    const uint32_t *prepA32_3 = nullptr;  // [m][8][3][4][64] two rounded slices, three products (sub_dim 16 encode), or null
+    const uint32_t *prepA32_3 = nullptr;  // [m][8][2][4][64] the two rounded slices of -2(c - mu), once each; three products (sub_dim 16 encode), or null
     const float *cen = nullptr;      // [m][sd+4]  X32, L2: {mu[sd], max|c-mu|, margin coefficient, same for three products, -}
     const float *cn32 = nullptr;     // [m][ceil(k/32)*32]  X32, L2: |c-mu|^2, finite padding
 };
